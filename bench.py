@@ -3,6 +3,7 @@
 VLP16-shaped clouds, on N MI355X of one node.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full  # + roofline, spread, CPU baseline, C3 / C4 / C5 blocks, ...
     python bench.py --gpus N --steps K --warmup W          # starts its own N rank processes (self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -17,6 +18,13 @@ one RCCL all-gather of 32 f64 per residual evaluation.
 The unit of `value` is one correspondence query (one source point searched against
 its 27 neighbour voxels and reduced into the normal equations), counted over all
 outer iterations and all ranks.  Inputs are resident in HBM before the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything
+else it can measure -- the counted replay and roofline, the spread over further
+blocks, the PCIe-inclusive rate, the CPU baseline, concurrent contexts, the short
+C3 / C4 / C5 blocks, the other transports of a multi-rank run, C5's run without
+announcing the next frame -- is part of `--full` only.  `--dump-outputs DIR`
+writes what the last timed step returned (the final pose) as DIR/*.npy.
 """
 import argparse
 import json
@@ -258,6 +266,14 @@ def cpu_baseline(work, budget_s=10.0):
                       "CPU restatement of the reference algorithm (oracle/), not the reference binary"}
 
 
+def dump_outputs(out_dir, pose):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the pose of the align (of the last
+    frame's processCloud for C5) -- as float32 arrays; the inputs are seeded, so two builds can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pose_translation.npy"), np.asarray(pose.translation, np.float32))
+    np.save(os.path.join(out_dir, "pose_rotation_wxyz.npy"), np.asarray(pose.rotation, np.float32))
+
+
 def event_period(steps):
     """A step whose launches carry HIP events takes ~40 % longer (an event is a packet of its own on the stream): of a long
     block every 32nd step carries them (200 steps: 7 steps, 35 launches of each kernel), of a short one -- the driver's
@@ -265,11 +281,12 @@ def event_period(steps):
     return EVENT_PERIOD if steps >= 3 * EVENT_PERIOD else max(int(steps), 1)
 
 
-def streaming(args, lom, steps=None, warmup=None, cpu_frames=40):
+def streaming(args, lom, steps=None, warmup=None, cpu_frames=40, dump_dir=None):
     """BASELINE.json configs[4]: 10 Hz VLP16 sequence through the full per-frame pipeline
     (time-normalise, deskew, classify, range filter, two down-samplers, align, cleanup, keyframe
     insert; defaults of LidarOdometry::Params).  A step = one processCloud; frames are generated
-    on the host before the timed region.  Returns the line."""
+    on the host before the timed region.  Returns the line; the run without announcing the next
+    frame and the CPU baseline are part of it with --full only."""
     from lidar_odometry_demo_amd import synth
 
     steps = args.steps if steps is None else steps
@@ -294,10 +311,36 @@ def streaming(args, lom, steps=None, warmup=None, cpu_frames=40):
     queries = odo.stats["queries_total"] - q0   # waits for the last keyframe update: inside the timed region
     elapsed = time.perf_counter() - t0
     pose = odo.getCurrentPose()
+    if dump_dir:
+        dump_outputs(dump_dir, pose)
     odo_stats = dict(odo.stats)
     odo_counters = {"redone": odo.debugCounter(), "staged": odo.debugCounter(lom.capi.COUNTER_FRAMES_SENT_AHEAD),
                     "behind": odo.debugCounter(lom.capi.COUNTER_CLEANUPS_BEHIND_ALIGN)}
     del odo   # (its streams go with it: a process has four hardware queues, handles beyond that share them)
+    gt_t, gt_q = synth.sequence_pose(n_frames * synth.FRAME_PERIOD)
+    dq = abs(float(np.dot(pose.rotation.astype(np.float64), gt_q)))
+    line = {
+        "metric": "icp_correspondences_per_sec", "value": queries / elapsed / 1e6, "unit": "Mcorr/s", "n_gpus": 1,
+        "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "frames_per_s": steps / elapsed,
+        "config": {"workload": "C5: streaming 10 Hz VLP16 sequence, full per-frame pipeline, default params",
+                   "points_per_frame": int(np.mean([len(f) for f in frames])),
+                   "keyframe_voxels": odo_stats["keyframe_voxels"],
+                   "frames_redone_on_host_or_scans_redone": odo_counters["redone"],
+                   "frames_handed_over_by": "lom_odometry_process_sequence: the caller's frame loop in compiled code; it announces "
+                                            "frame i + 1 before frame i (lom_odometry_hint_next), which is then copied to pinned "
+                                            "memory while frame i's align runs",
+                   "frames_staged_during_the_previous_align": odo_counters["staged"],
+                   "cleanup_scans_behind_the_align": odo_counters["behind"],
+                   "matching_points_last": odo_stats["matching_points"],
+                   "drift_translation_m": float(np.linalg.norm(pose.translation.astype(np.float64) - gt_t)),
+                   "drift_rotation_rad": 2.0 * float(np.arccos(min(1.0, dq))),
+                   "drift_note": "x is weakly observable in the street-canyon scene and the reference's "
+                                 "translation prior holds it back; yaw, y and z track"},
+    }
+    if not args.full:
+        return line
     # beside it (never `value`): the same frames to a caller that does NOT hold the next frame while one is processed -- a
     # live sensor --, i.e. without lom_odometry_hint_next: each frame is copied to pinned memory at the start of its own call
     os.environ["LOM_NO_SEND_AHEAD"] = "1"   # (read once, at create)
@@ -315,30 +358,8 @@ def streaming(args, lom, steps=None, warmup=None, cpu_frames=40):
     same_pose = (live.getCurrentPose().translation.tobytes() == pose.translation.tobytes()
                  and live.getCurrentPose().rotation.tobytes() == pose.rotation.tobytes())
     del live
-    gt_t, gt_q = synth.sequence_pose(n_frames * synth.FRAME_PERIOD)
-    dq = abs(float(np.dot(pose.rotation.astype(np.float64), gt_q)))
-    line = {
-        "metric": "icp_correspondences_per_sec", "value": queries / elapsed / 1e6, "unit": "Mcorr/s", "n_gpus": 1,
-        "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "frames_per_s": steps / elapsed,
-        "config": {"workload": "C5: streaming 10 Hz VLP16 sequence, full per-frame pipeline, default params",
-                   "points_per_frame": int(np.mean([len(f) for f in frames])),
-                   "keyframe_voxels": odo_stats["keyframe_voxels"],
-                   "frames_redone_on_host_or_scans_redone": odo_counters["redone"],
-                   "frames_handed_over_by": "lom_odometry_process_sequence: the caller's frame loop in compiled code; it announces "
-                                            "frame i + 1 before frame i (lom_odometry_hint_next), which is then copied to pinned "
-                                            "memory while frame i's align runs",
-                   "frames_staged_during_the_previous_align": odo_counters["staged"],
-                   "ms_per_frame_without_announcing_the_next_frame": live_ms,
-                   "final_pose_bits_equal_without_announcing": bool(same_pose),
-                   "cleanup_scans_behind_the_align": odo_counters["behind"],
-                   "matching_points_last": odo_stats["matching_points"],
-                   "drift_translation_m": float(np.linalg.norm(pose.translation.astype(np.float64) - gt_t)),
-                   "drift_rotation_rad": 2.0 * float(np.arccos(min(1.0, dq))),
-                   "drift_note": "x is weakly observable in the street-canyon scene and the reference's "
-                                 "translation prior holds it back; yaw, y and z track"},
-    }
+    line["config"]["ms_per_frame_without_announcing_the_next_frame"] = live_ms
+    line["config"]["final_pose_bits_equal_without_announcing"] = bool(same_pose)
     if not args.no_cpu_baseline and cpu_frames > 0:
         from oracle import oracle as O
 
@@ -527,9 +548,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: roofline and kernel figures, the spread over further blocks, the "
+                         "PCIe-inclusive rate, the CPU baseline, concurrent contexts, the short C3 / C4 / C5 blocks, the "
+                         "other transports (N > 1) and C5's run without announcing the next frame")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (the pose) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default run only: skip the short C3 / C4 blocks and the 200-frame C5 block attached as extra_configs")
+                    help="--full, C2 only: skip the concurrent contexts, the short C3 / C4 blocks and the 200-frame C5 "
+                         "block attached as extra_configs")
     ap.add_argument("--config", choices=["C2", "C3", "C4", "C5"], default="C2",
                     help="C2 = BASELINE.json configs[1] (the bench line; weak-scaled with --gpus N); C3 = configs[2], "
                          "single GPU only; C4 = configs[3], 128x2048 scan range-sharded over --gpus N ranks (any N "
@@ -581,7 +609,7 @@ def main():
     if args.config not in ("C2", "C4") and n != 1:
         raise SystemExit(f"--config {args.config} is a single-GPU configuration")
     if args.config == "C5":
-        emit(streaming(args, lom))
+        emit(streaming(args, lom, dump_dir=args.dump_outputs))
         return
     progress("building the workload")
     work = build_workload(n, rank, args.config)
@@ -695,47 +723,51 @@ def main():
         elapsed = float(t.item())
     lm_ms, lm_profiled = tot["lm_kernel_ms"], tot["lm_profiled_launches"]
     valid_last = tot["valid_last"]
-    # the reference-algorithm counts of this align (all ranks take part: an align is a sequence of exchanges), untimed
     progress("timed block done")
-    replay = counted_replay(lom, grid, d_scan, guess)
-    # ... and what producing them costs the product: one block of K steps with the counts on (never `value`)
-    grid.setOption(lom.capi.OPT_COUNT_CANDIDATES, 1)
-    fence()
-    tc = time.perf_counter()
-    lom.align_repeat(grid, d_scan.data_ptr(), d_scan.shape[0], guess, args.steps)
-    fence()
-    counted_ms = (time.perf_counter() - tc) / args.steps * 1e3
-    grid.setOption(lom.capi.OPT_COUNT_CANDIDATES, 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pose)
 
-    # spread: EXTRA_BLOCKS further blocks of the same K steps, each fenced like the official one (never `value`)
-    block_ms = [elapsed / args.steps * 1e3]
-    for _ in range(EXTRA_BLOCKS):
+    if args.full:
+        # the reference-algorithm counts of this align (all ranks take part: an align is a sequence of exchanges), untimed
+        replay = counted_replay(lom, grid, d_scan, guess)
+        # ... and what producing them costs the product: one block of K steps with the counts on (never `value`)
+        grid.setOption(lom.capi.OPT_COUNT_CANDIDATES, 1)
         fence()
-        tb = time.perf_counter()
-        _, tot_b = lom.align_repeat(grid, d_scan.data_ptr(), d_scan.shape[0], guess, args.steps)
+        tc = time.perf_counter()
+        lom.align_repeat(grid, d_scan.data_ptr(), d_scan.shape[0], guess, args.steps)
         fence()
-        el = time.perf_counter() - tb
-        # the kernels' event samples of these blocks count as well (a short block carries the events of ONE step: five
-        # launches of each kernel are a thin average)
-        match_ms += tot_b["match_kernel_ms"]
-        profiled += tot_b["profiled_launches"]
-        lm_ms += tot_b["lm_kernel_ms"]
-        lm_profiled += tot_b["lm_profiled_launches"]
-        if use_dist:
-            t = torch.tensor([el], dtype=torch.float64, device="cpu" if one_device else dev)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            el = float(t.item())
-        block_ms.append(el / args.steps * 1e3)
+        counted_ms = (time.perf_counter() - tc) / args.steps * 1e3
+        grid.setOption(lom.capi.OPT_COUNT_CANDIDATES, 0)
 
-    # roofline probe for the dominant kernel, outside the timed region: a back-to-back train of
-    # k_match launches at the converged pose under one HIP event pair on the library's stream
-    train_us, train_bytes, train_requested, pair_us = grid.profileMatch(d_scan.data_ptr(), d_scan.shape[0], pose, 0.3,
-                                                                        reps=200)
-    # PCIe-inclusive variant (scan handed over as a host buffer every step); never `value`
-    t1 = time.perf_counter()
-    for _ in range(max(3, args.steps // 4)):
-        matcher.align(grid, work["shard"], guess)
-    pcie_ms = (time.perf_counter() - t1) / max(3, args.steps // 4) * 1e3
+        # spread: EXTRA_BLOCKS further blocks of the same K steps, each fenced like the official one (never `value`)
+        block_ms = [elapsed / args.steps * 1e3]
+        for _ in range(EXTRA_BLOCKS):
+            fence()
+            tb = time.perf_counter()
+            _, tot_b = lom.align_repeat(grid, d_scan.data_ptr(), d_scan.shape[0], guess, args.steps)
+            fence()
+            el = time.perf_counter() - tb
+            # the kernels' event samples of these blocks count as well (a short block carries the events of ONE step:
+            # five launches of each kernel are a thin average)
+            match_ms += tot_b["match_kernel_ms"]
+            profiled += tot_b["profiled_launches"]
+            lm_ms += tot_b["lm_kernel_ms"]
+            lm_profiled += tot_b["lm_profiled_launches"]
+            if use_dist:
+                t = torch.tensor([el], dtype=torch.float64, device="cpu" if one_device else dev)
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                el = float(t.item())
+            block_ms.append(el / args.steps * 1e3)
+
+        # roofline probe for the dominant kernel, outside the timed region: a back-to-back train of
+        # k_match launches at the converged pose under one HIP event pair on the library's stream
+        train_us, train_bytes, train_requested, pair_us = grid.profileMatch(d_scan.data_ptr(), d_scan.shape[0], pose,
+                                                                            0.3, reps=200)
+        # PCIe-inclusive variant (scan handed over as a host buffer every step); never `value`
+        t1 = time.perf_counter()
+        for _ in range(max(3, args.steps // 4)):
+            matcher.align(grid, work["shard"], guess)
+        pcie_ms = (time.perf_counter() - t1) / max(3, args.steps // 4) * 1e3
 
     # what a scaling run needs to be believed: who took part (rank ids gathered through the exchange object the
     # transport itself uses), on which devices, and every rank's own step time
@@ -766,70 +798,71 @@ def main():
     if rank == 0:
         # stats are global (summed over ranks) after the in-library all-gather
         value = queries / elapsed / 1e6
-        # -- the dominant kernel, k_match: duration measured live inside the timed region (HIP events on the
-        # library's stream around the launches of every 32nd step, of a short block's first step).  An event pair around ONE short kernel carries
-        # packet overhead; it is measured right here (same launches at the final pose once as a back-to-back
-        # train under one pair, once with a pair each) and subtracted: the result is what
-        # `rocprofv3 --kernel-trace --stats` reports as the kernel's average duration (profiles/).
-        event_overhead_us = max(0.0, pair_us - train_us)
-        in_loop_raw_us = match_ms * 1e3 / max(profiled, 1)
-        in_loop_us = max(in_loop_raw_us - event_overhead_us, 1e-3) if profiled else train_us
-        alg_per_launch = replay["algorithmic_bytes_per_launch"] / n      # counters are totals over ranks after the exchange
-        req_per_launch = train_requested if n == 1 else None   # counted at the final pose (the train)
-        achieved = alg_per_launch / (in_loop_us * 1e-6) / 1e9
-        traffic, traffic_source = traffic_record(args.config) if n == 1 else (None, None)
-        roof = match_roofline(int(d_scan.shape[0]), alg_per_launch, req_per_launch, in_loop_us, traffic, traffic_source, {
-            "avg_launch_us_method": "HIP event pairs around the k_match launches of every 32nd step (short blocks: the first step) inside the timed "
-                                    "region, minus the per-pair event overhead measured in this run",
-            "in_loop_raw_us": in_loop_raw_us,
-            "event_pair_overhead_us": event_overhead_us,
-            "in_loop_launches_measured": profiled,
-            "in_loop_launches_from": f"the timed block and the {EXTRA_BLOCKS} blocks of the same K steps behind it (ms_per_step_blocks)",
-            "train_avg_launch_us": train_us,
-            "train_note": "200 back-to-back launches at the final pose under one event pair (best case: warm caches, "
-                          "converged pose)",
-            "launches": launches,
-            "algorithmic_bytes_from": "a counted replay of the same align outside the timed region (LOM_OPT_COUNT_CANDIDATES: "
-                                      "every query looks up all 27 slots and tallies the reference algorithm's cand(q)); the "
-                                      "timed searches do not look up a neighbour voxel that the distance bound prunes",
-            "ms_per_step_with_counts": counted_ms,
-        }, big_map=(args.config != "C2"))
-        # -- the other kernels of the path
-        lm_raw_us = lm_ms * 1e3 / max(lm_profiled, 1)
-        lm_us = max(lm_raw_us - event_overhead_us, 1e-3) if lm_profiled else None
-        evals_per_launch = evals / max(outer, 1)
-        lm_bytes = 36.0 * (valid_last / n) * evals_per_launch   # 36 B per valid match and evaluation
         stored = grid.pointCount()
-        n_map = int(len(work["map_xyz"]))
-        ins_bytes = 40.0 * n_map + 24.0 * stored
-        kernels = [
-            {"kernel": "k_match", "algorithmic_bytes_per_launch": alg_per_launch, "avg_us": in_loop_us,
-             "gbs": achieved, "frac_of_hbm_peak": achieved / HBM_PEAK_GBS, "launches_per_step": launches / args.steps},
-            {"kernel": "k_lm (evaluation + reduction + exchange + LM policy, one launch per outer iteration)",
-             "algorithmic_bytes_per_launch": lm_bytes, "avg_us": lm_us,
-             "gbs": (lm_bytes / (lm_us * 1e-6) / 1e9 if lm_us else None),
-             "frac_of_hbm_peak": (lm_bytes / (lm_us * 1e-6) / 1e9 / HBM_PEAK_GBS if lm_us else None),
-             "evaluations_per_launch": evals_per_launch, "launches_per_step": outer / args.steps,
-             "workgroups": tot["lm_workgroups"], "cus_busy": tot["lm_workgroups"], "cus_total": 256,
-             "cus_note": "one workgroup per CU (its workgroups wait for each other: the grid is held to what is resident); "
-                         "the other CUs are free for concurrent callers (concurrent_contexts)",
-             "bytes_note": "36 B per valid match and evaluation (source point, plane origin, plane normal)",
-             "note": "a latency chain, not a stream: per evaluation one pass over <= 1 point per lane, a workgroup "
-                     "reduction, one exchange between the workgroups through HBM and a serial 6x6 policy step on one "
-                     "wave; phase stamps and SQ counters in profiles/"},
-            {"kernel": "insert chain of the bulk map build (k_bi_claim, k_bi_colscan, k_bi_scatter, k_bi_group, "
-                       "k_bi_flagscan, k_bi_place)",
-             "algorithmic_bytes_per_launch": ins_bytes, "avg_us": insert_us,
-             "gbs": ins_bytes / (insert_us * 1e-6) / 1e9, "frac_of_hbm_peak": ins_bytes / (insert_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-             "bytes_note": "per input point 24 B read (point, normal) + one 16-B slot; per stored point 24 B written",
-             "points": n_map, "stored": stored,
-             "note": "one call, all kernels under one HIP event pair; per-kernel split in profiles/ (kernel stats); "
-                     "the partitioned bulk insert (one slot look per point, a compare-and-swap per new voxel, everything per "
-                     "voxel in LDS, slab rows written side by side): bound by the scattered passes of the partition (16-byte "
-                     "records) and of the place kernel's gather of the input rows, not by bytes; the four-kernel path of "
-                     "batches up to 65,536 points takes 2.5-3x as long (tools/ab_insert.py, profiles/r04_i_ab_insert.txt)"},
-        ]
-        bsorted = sorted(block_ms)
+        if args.full:
+            # -- the dominant kernel, k_match: duration measured live inside the timed region (HIP events on the
+            # library's stream around the launches of every 32nd step, of a short block's first step).  An event pair around ONE short kernel carries
+            # packet overhead; it is measured right here (same launches at the final pose once as a back-to-back
+            # train under one pair, once with a pair each) and subtracted: the result is what
+            # `rocprofv3 --kernel-trace --stats` reports as the kernel's average duration (profiles/).
+            event_overhead_us = max(0.0, pair_us - train_us)
+            in_loop_raw_us = match_ms * 1e3 / max(profiled, 1)
+            in_loop_us = max(in_loop_raw_us - event_overhead_us, 1e-3) if profiled else train_us
+            alg_per_launch = replay["algorithmic_bytes_per_launch"] / n      # counters are totals over ranks after the exchange
+            req_per_launch = train_requested if n == 1 else None   # counted at the final pose (the train)
+            achieved = alg_per_launch / (in_loop_us * 1e-6) / 1e9
+            traffic, traffic_source = traffic_record(args.config) if n == 1 else (None, None)
+            roof = match_roofline(int(d_scan.shape[0]), alg_per_launch, req_per_launch, in_loop_us, traffic, traffic_source, {
+                "avg_launch_us_method": "HIP event pairs around the k_match launches of every 32nd step (short blocks: the first step) inside the timed "
+                                        "region, minus the per-pair event overhead measured in this run",
+                "in_loop_raw_us": in_loop_raw_us,
+                "event_pair_overhead_us": event_overhead_us,
+                "in_loop_launches_measured": profiled,
+                "in_loop_launches_from": f"the timed block and the {EXTRA_BLOCKS} blocks of the same K steps behind it (ms_per_step_blocks)",
+                "train_avg_launch_us": train_us,
+                "train_note": "200 back-to-back launches at the final pose under one event pair (best case: warm caches, "
+                              "converged pose)",
+                "launches": launches,
+                "algorithmic_bytes_from": "a counted replay of the same align outside the timed region (LOM_OPT_COUNT_CANDIDATES: "
+                                          "every query looks up all 27 slots and tallies the reference algorithm's cand(q)); the "
+                                          "timed searches do not look up a neighbour voxel that the distance bound prunes",
+                "ms_per_step_with_counts": counted_ms,
+            }, big_map=(args.config != "C2"))
+            # -- the other kernels of the path
+            lm_raw_us = lm_ms * 1e3 / max(lm_profiled, 1)
+            lm_us = max(lm_raw_us - event_overhead_us, 1e-3) if lm_profiled else None
+            evals_per_launch = evals / max(outer, 1)
+            lm_bytes = 36.0 * (valid_last / n) * evals_per_launch   # 36 B per valid match and evaluation
+            n_map = int(len(work["map_xyz"]))
+            ins_bytes = 40.0 * n_map + 24.0 * stored
+            kernels = [
+                {"kernel": "k_match", "algorithmic_bytes_per_launch": alg_per_launch, "avg_us": in_loop_us,
+                 "gbs": achieved, "frac_of_hbm_peak": achieved / HBM_PEAK_GBS, "launches_per_step": launches / args.steps},
+                {"kernel": "k_lm (evaluation + reduction + exchange + LM policy, one launch per outer iteration)",
+                 "algorithmic_bytes_per_launch": lm_bytes, "avg_us": lm_us,
+                 "gbs": (lm_bytes / (lm_us * 1e-6) / 1e9 if lm_us else None),
+                 "frac_of_hbm_peak": (lm_bytes / (lm_us * 1e-6) / 1e9 / HBM_PEAK_GBS if lm_us else None),
+                 "evaluations_per_launch": evals_per_launch, "launches_per_step": outer / args.steps,
+                 "workgroups": tot["lm_workgroups"], "cus_busy": tot["lm_workgroups"], "cus_total": 256,
+                 "cus_note": "one workgroup per CU (its workgroups wait for each other: the grid is held to what is resident); "
+                             "the other CUs are free for concurrent callers (concurrent_contexts)",
+                 "bytes_note": "36 B per valid match and evaluation (source point, plane origin, plane normal)",
+                 "note": "a latency chain, not a stream: per evaluation one pass over <= 1 point per lane, a workgroup "
+                         "reduction, one exchange between the workgroups through HBM and a serial 6x6 policy step on one "
+                         "wave; phase stamps and SQ counters in profiles/"},
+                {"kernel": "insert chain of the bulk map build (k_bi_claim, k_bi_colscan, k_bi_scatter, k_bi_group, "
+                           "k_bi_flagscan, k_bi_place)",
+                 "algorithmic_bytes_per_launch": ins_bytes, "avg_us": insert_us,
+                 "gbs": ins_bytes / (insert_us * 1e-6) / 1e9, "frac_of_hbm_peak": ins_bytes / (insert_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                 "bytes_note": "per input point 24 B read (point, normal) + one 16-B slot; per stored point 24 B written",
+                 "points": n_map, "stored": stored,
+                 "note": "one call, all kernels under one HIP event pair; per-kernel split in profiles/ (kernel stats); "
+                         "the partitioned bulk insert (one slot look per point, a compare-and-swap per new voxel, everything per "
+                         "voxel in LDS, slab rows written side by side): bound by the scattered passes of the partition (16-byte "
+                         "records) and of the place kernel's gather of the input rows, not by bytes; the four-kernel path of "
+                         "batches up to 65,536 points takes 2.5-3x as long (tools/ab_insert.py, profiles/r04_i_ab_insert.txt)"},
+            ]
+            bsorted = sorted(block_ms)
         line = {
             "metric": "icp_correspondences_per_sec",
             "value": value,
@@ -845,9 +878,6 @@ def main():
             "dtype_note": "f32 distances on f64-transformed queries (search); f64 residuals, Jacobians and solve",
             "data": "synthetic",
             "frames_per_s": args.steps / elapsed,
-            "ms_per_step_blocks": {"blocks": block_ms, "median": bsorted[len(bsorted) // 2], "min": bsorted[0],
-                                   "max": bsorted[-1],
-                                   "note": f"the official block first, then {EXTRA_BLOCKS} more blocks of {args.steps} steps"},
             "config": {
                 "workload": work["name"],
                 "ranks_seen": ranks_seen,
@@ -858,7 +888,6 @@ def main():
                 "scan_points_total": int(len(work["scan"])),
                 "map_points_stored": stored,
                 "map_voxels": grid.size(),
-                "pcie_inclusive_ms_per_step": pcie_ms,
                 "valid_match_rate": valid_last / max(1, int(len(work["scan"]))),
                 "outer_iterations_per_frame": outer / args.steps,
                 "evaluations_per_frame": evals / args.steps,
@@ -873,18 +902,23 @@ def main():
             },
             "host_breakdown_ms_per_step": {"in_launch_calls": launch_ms / args.steps,
                                            "waiting_for_results": wait_ms / args.steps},
-            "roofline": roof,
-            "roofline_kernels": kernels,
         }
+        if args.full:
+            line["ms_per_step_blocks"] = {"blocks": block_ms, "median": bsorted[len(bsorted) // 2], "min": bsorted[0],
+                                          "max": bsorted[-1],
+                                          "note": f"the official block first, then {EXTRA_BLOCKS} more blocks of {args.steps} steps"}
+            line["config"]["pcie_inclusive_ms_per_step"] = pcie_ms
+            line["roofline"] = roof
+            line["roofline_kernels"] = kernels
         progress("line assembled")
-        if n == 1 and not args.no_cpu_baseline:
+        if args.full and n == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(work)
             progress("cpu baseline done")
             line["speedup_vs_cpu_port"] = value / line["cpu_baseline"]["value"]
         line["pose"] = {"t": [float(v) for v in pose.translation], "q_wxyz": [float(v) for v in pose.rotation]}
         # (C2 only: on a slice of the GPU the 128 x 512-thread solve of the 64- / 128-beam scans is not co-resident, every
         # launch sits out its patience and the align is redone by the host-driven loop -- minutes per block)
-        if n == 1 and args.config == "C2" and not use_dist and not args.no_extras:
+        if args.full and n == 1 and args.config == "C2" and not use_dist and not args.no_extras:
             try:
                 cc = concurrent_contexts(lom, torch, grid, d_scan, guess, min(args.steps, 100), counts=(2, 3, 4, 8))
                 line["concurrent_contexts"] = dict(cc, note="k threads, one scan context each, the same scan against the one "
@@ -895,7 +929,7 @@ def main():
                 progress("concurrent contexts done")
             except Exception as e:  # noqa: BLE001
                 line["concurrent_contexts"] = {"error": repr(e)[:300]}
-        if n == 1 and args.config == "C2" and not args.no_extras and not use_dist:
+        if args.full and n == 1 and args.config == "C2" and not args.no_extras and not use_dist:
             # the other single-GPU configurations of BASELINE.json, short blocks on the same box (never `value`)
             extras = {}
             t_x = time.perf_counter()
@@ -937,8 +971,8 @@ def main():
     # The other transports, timed in the same run for comparison (never `value`): the north_star names an RCCL
     # all-reduce per iteration, the default is the device-to-device exchange -- both get a number.  The line is complete
     # before this block starts and a watchdog guards it: a transport that fails or hangs on some rank costs the side
-    # figure, not the line (LOM_BENCH_NO_COMPARE=1 skips the block).
-    if use_dist and not os.environ.get("LOM_BENCH_NO_COMPARE"):
+    # figure, not the line (LOM_BENCH_NO_COMPARE=1 skips the block; part of --full only).
+    if args.full and use_dist and not os.environ.get("LOM_BENCH_NO_COMPARE"):
         others = []
 
         def fire():

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Generates the committed fixtures under tests/golden/.  Run in the build
-container (it reads /root/reference, which does not exist on the GPU box):
+"""Generates the committed fixtures under tests/golden/ from the reference's one
+data file, committed xz-compressed as tests/golden/intersection00056.pcd.xz:
 
     python tests/golden/make_fixtures.py
 
@@ -20,6 +20,7 @@ they are NOT outputs of the reference binary (which cannot be built here).
 """
 import hashlib
 import json
+import lzma
 import os
 import sys
 
@@ -33,13 +34,13 @@ from oracle import oracle as O  # noqa: E402
 from lidar_odometry_demo_amd import synth  # noqa: E402
 from tests import scenes  # noqa: E402
 
-PCD = "/root/reference/test/test_data/intersection00056.pcd"
+PCD = os.path.join(HERE, "intersection00056.pcd.xz")
 
 
 def read_pcd_xyz(path):
     """Binary PCD v0.7 reader honouring FIELDS/SIZE/COUNT (fixture: 32 B/point)."""
     with open(path, "rb") as f:
-        raw = f.read()
+        raw = lzma.decompress(f.read()) if path.endswith(".xz") else f.read()
     head_end = raw.index(b"DATA binary\n") + len(b"DATA binary\n")
     hdr = {}
     for line in raw[:head_end].decode("ascii").splitlines():

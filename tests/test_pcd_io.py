@@ -1,14 +1,19 @@
 """Product-side PCD reader (lom_pcd_read = pcl::io::loadPCDFile<pcl::PointXYZ>, reference test/test.cpp:194):
 host code, runs without a GPU.  Checked on files written here in the layouts PCL writes (ascii, binary,
-packed and padded records) and -- in this container, where /root/reference exists -- on the reference's
-shipped test/test_data/intersection00056.pcd against the committed arrays of tests/golden/ (which
-tests/golden/make_fixtures.py produced with an independent Python parser)."""
+packed and padded records) and on the reference's shipped test/test_data/intersection00056.pcd (committed
+byte for byte, xz-compressed, as tests/golden/intersection00056.pcd.xz) against the committed arrays of
+tests/golden/ (which tests/golden/make_fixtures.py produced with an independent Python parser)."""
+import hashlib
+import lzma
 import os
 
 import numpy as np
 import pytest
 
-REF_PCD = "/root/reference/test/test_data/intersection00056.pcd"
+from tests.conftest import GOLDEN
+
+REF_PCD_XZ = os.path.join(GOLDEN, "intersection00056.pcd.xz")
+REF_PCD_SHA256 = "2c4656ca415a4985f06d8505d36e7a76dec4f604238fe980ba2a0a4d54a1b9e9"   # of the reference's file
 
 
 def _header(fields, sizes, types, counts, n, data):
@@ -98,9 +103,13 @@ def test_errors(lom, tmp_path):
         lom.loadPCDFile(nox)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PCD), reason="the reference checkout is only present in the build container")
-def test_reference_data_file_equals_the_committed_arrays(lom, fixture_cloud):
+def test_reference_data_file_equals_the_committed_arrays(lom, fixture_cloud, tmp_path):
     xyz, _ = fixture_cloud
-    got = lom.loadPCDFile(REF_PCD)
+    with open(REF_PCD_XZ, "rb") as f:
+        raw = lzma.decompress(f.read())
+    assert hashlib.sha256(raw).hexdigest() == REF_PCD_SHA256    # the reference's file, unchanged
+    path = tmp_path / "intersection00056.pcd"
+    path.write_bytes(raw)
+    got = lom.loadPCDFile(path)
     assert len(got) == 59691
     assert got.tobytes() == xyz.tobytes()

@@ -6,9 +6,12 @@
 #   afterwards:  git worktree remove --force _ab_old
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/gpurun_out/ab
+ARGS=${AB_ARGS:-}
 for i in 1 2 3; do
   for t in old new; do
     if [ $t = old ]; then D=$R/_ab_old; else D=$R; fi
+    # the roofline figures read below come with --full (a tree older than that option prints them without it)
+    AB_ARGS="$(grep -q -e '"--full"' $D/bench.py && echo --full) $ARGS"
     (cd $D && timeout -k 10 200 python bench.py --no-cpu-baseline --no-extras ${AB_ARGS:-} 2>/dev/null) > $R/gpurun_out/ab/ab_$t.json
     python3 -c "
 import json; d=json.load(open('$R/gpurun_out/ab/ab_$t.json')); r=d['roofline']; print('$t', round(d['ms_per_step'],4), 'k_match', round(r['avg_launch_us'],2), 'k_lm', round(d['roofline_kernels'][1]['avg_us'],2))"

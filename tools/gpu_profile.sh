@@ -14,29 +14,29 @@ run() { echo "== $*" >> "$OUT/log.txt"; timeout -k 10 "$@" >> "$OUT/log.txt" 2>&
 
 if [ "$PART" = all ] || [ "$PART" = lines ]; then
 # 1. bench lines (default = C2 with the CPU baseline; C3, C4, C5 without)
-timeout -k 10 300 python3 "$ROOT/bench.py" > "$OUT/bench_default_line.json" 2> "$OUT/bench_default.err"; echo "default rc=$?"
+timeout -k 10 300 python3 "$ROOT/bench.py" --full > "$OUT/bench_default_line.json" 2> "$OUT/bench_default.err"; echo "default rc=$?"
 for c in C3 C4 C5; do
-  timeout -k 10 300 python3 "$ROOT/bench.py" --config $c --no-cpu-baseline > "$OUT/bench_${c}_line.json" 2> "$OUT/bench_$c.err"; echo "$c rc=$?"
+  timeout -k 10 300 python3 "$ROOT/bench.py" --full --config $c --no-cpu-baseline > "$OUT/bench_${c}_line.json" 2> "$OUT/bench_$c.err"; echo "$c rc=$?"
 done
 fi
 if [ "$PART" = all ] || [ "$PART" = stats ]; then
 # 2. kernel stats of the same commands
 # (the default command itself, extras included: BENCH_rNN.json's numbers -- C2 line, C3 and C5 blocks -- must be reproducible
 #  from this one trace; then each configuration alone)
-run 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_default" -o kt -- python3 "$ROOT/bench.py" --no-cpu-baseline
-run 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_C2only" -o kt -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-extras
-run 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_C5" -o kt -- python3 "$ROOT/bench.py" --config C5 --no-cpu-baseline --steps 200
-run 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_C3" -o kt -- python3 "$ROOT/bench.py" --config C3 --no-cpu-baseline --no-extras --steps 50
+run 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_default" -o kt -- python3 "$ROOT/bench.py" --full --no-cpu-baseline
+run 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_C2only" -o kt -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-extras
+run 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_C5" -o kt -- python3 "$ROOT/bench.py" --full --config C5 --no-cpu-baseline --steps 200
+run 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt_C3" -o kt -- python3 "$ROOT/bench.py" --full --config C3 --no-cpu-baseline --no-extras --steps 50
 find "$OUT" -name "*kernel_stats.csv" | head
 fi
 if [ "$PART" = all ] || [ "$PART" = counters ]; then
 # 3. counters, separate passes (short runs: every dispatch is serialised under --pmc)
-B="python3 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+B="python3 $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 run 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o p -- $B
 run 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o p -- $B
 run 400 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU --output-format csv -d "$OUT/pmc_sq" -o p -- $B
 run 400 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum TCP_TCC_ATOMIC_WITH_RET_REQ_sum --output-format csv -d "$OUT/pmc_tcc" -o p -- $B
-B3="python3 $ROOT/bench.py --config C3 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
+B3="python3 $ROOT/bench.py --full --config C3 --steps 5 --warmup 1 --no-cpu-baseline --no-extras"
 run 400 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU --output-format csv -d "$OUT/pmc_sq_c3" -o p -- $B3
 run 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_c3" -o p -- $B3
 run 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_c3" -o p -- $B3

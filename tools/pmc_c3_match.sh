@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --config ${2:-C3} --no-cpu-baseline --no-extras --steps 10 --warmup 2"
+B="python3 $ROOT/bench.py --full --config ${2:-C3} --no-cpu-baseline --no-extras --steps 10 --warmup 2"
 pass() {
   name=$1; shift
   timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/raw_$name" -o p -- $B >> "$OUT/log.txt" 2>&1

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 pass() {
   name=$1; shift
-  timeout -k 10 200 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/raw_$name" -o p -- python3 "$ROOT/bench.py" --config $CFG --no-cpu-baseline --no-extras --steps 10 --warmup 2 >> "$OUT/log.txt" 2>&1
+  timeout -k 10 200 rocprofv3 --pmc "$@" --output-format csv -d "$OUT/raw_$name" -o p -- python3 "$ROOT/bench.py" --full --config $CFG --no-cpu-baseline --no-extras --steps 10 --warmup 2 >> "$OUT/log.txt" 2>&1
   echo "$name rc=$?" >> "$OUT/log.txt"
   python3 "$ROOT/tools/pmc_summary.py" "$OUT/raw_$name" k_match > "$OUT/pmc_${CFG}_$name.txt" 2>/dev/null
   rm -rf "$OUT/raw_$name"
