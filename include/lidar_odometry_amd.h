@@ -248,6 +248,43 @@ int lom_match_align_repeat(lom_map *m, const float *d_src_xyz, size_t n, size_t 
                            const float guess_t[3], const float guess_q_wxyz[4], int reps, float out_t[3],
                            float out_q_wxyz[4], lom_align_stats *total_or_null);
 
+/* ---- batched align: K (scan, guess) problems against ONE keyframe in one call ------------------------- */
+/* Multi-hypothesis alignment (one scan from K guesses: relocalisation, loop-closure checks), several scans of a rig, the
+ * reference's MatchingTest: CloudMatcher::align takes `const VoxelGrid&` (cloud_matcher.h:15-16), so all are legal
+ * against one map at once.  The K solves run side by side in one device-resident chain -- one correspondence launch and
+ * one solve launch per outer iteration for all problems of a round (csrc/match.hip "batched align").  Problems may share
+ * a cloud pointer and may differ in n (0 and 1 included).  Every result is BIT FOR BIT what lom_match_align* returns for
+ * that (scan, guess) on the same handle, its counters included. */
+typedef struct {
+    const float *xyz;          /* host pointer (lom_*_align_batch) or device pointer (lom_*_align_batch_device) */
+    size_t n, stride_bytes;
+    float guess_t[3], guess_q_wxyz[4];
+} lom_align_problem;
+
+typedef struct {
+    float t[3], q_wxyz[4];     /* the pose lom_match_align would return for this problem */
+    /* its stats: the counting fields (outer_iterations, lm_iterations, evaluations, match_launches, queries, valid_last,
+     * cand_total, occ_total, algorithmic_bytes, final_cost, last_step_norm, lm_workgroups) equal the single align's;
+     * host_fallback = 1 where this problem's solve gave up and it was redone alone through lom_match_align_device;
+     * the profiling fields read 0; host_launch_ms / host_wait_ms hold the whole call's times */
+    lom_align_stats stats;
+    int32_t round;             /* the round of the device-resident batch this problem ran in (0, 1, ...; rounds of one
+                                  call run one after another), -1 where the batch ran problem by problem */
+    int32_t pad;
+} lom_align_result;
+
+/* out[i] for p[i]; best_or_null: lom_align_batch_best(out, count).  count == 0 is valid (best = -1).
+ * With LOM_OPT_HOST_LM = 1 or an attached rank exchange the problems are aligned one after another through
+ * lom_match_align* (the same results by definition).  The batch has buffers of its own: the single align's state, a
+ * lom_map_radius_cleanup_after_align and an idle hook armed for the next single align are neither used nor consumed.
+ * LOM_OPT_TEST_GIVE_UP_AT_OUTER applies to the first problem of the first round only. */
+int lom_match_align_batch(lom_map *m, const lom_align_problem *p, int count, lom_align_result *out, int *best_or_null);
+int lom_match_align_batch_device(lom_map *m, const lom_align_problem *p, int count, lom_align_result *out,
+                                 int *best_or_null);
+/* the best result (host code, no GPU): the most valid_last; ties go to the lower final_cost, then to the lower index;
+ * -1 if count <= 0 or r == NULL */
+int lom_align_batch_best(const lom_align_result *r, int count);
+
 /* Diagnostic build of the correspondence kernel with shader-clock stamps after each phase of every
  * workgroup's first query (8 u64 per workgroup: entry, point transformed, slots probed, prefix in
  * LDS, candidates scanned, minimum known, record stored, exit).  Not a timing of the product kernel. */
@@ -335,10 +372,12 @@ typedef enum {
     LOM_OPT_TEST_GRID_GIVE_UP_UPDATE_DS = 104,   /* ... the next frame's update down-sampler ... */
     LOM_OPT_TEST_GRID_GIVE_UP_KEYFRAME = 105,    /* ... the keyframe (its next insert or cleanup) */
     /* lom_map_set_option again: */
-    LOM_OPT_TEST_BULK_PARTITION_MAX = 106        /* p > 0: a partition of the bulk insert may hold p points (at most the
+    LOM_OPT_TEST_BULK_PARTITION_MAX = 106,       /* p > 0: a partition of the bulk insert may hold p points (at most the
                                                     1,024 its workgroup has LDS for; 0 = that limit): a bulk insert with a
                                                     larger partition writes nothing and is redone by the four-kernel path
                                                     (counted by LOM_COUNTER_GRID_REDOS) */
+    LOM_OPT_TEST_BATCH_ROUND_MAX = 107           /* r > 0: a round of lom_match_align_batch holds at most r problems (0 = as
+                                                    many as are resident together): lets the tests force several rounds */
 } lom_option;
 int lom_map_set_option(lom_map *m, int option, int64_t value);
 /* diagnostics: LOM_COUNTER_GRID_REDOS = calls of this handle redone with the multi-launch scan after an
@@ -392,6 +431,10 @@ int lom_scan_align_device(lom_scan *s, const float *d_src_xyz, size_t n, size_t 
 int lom_scan_align_repeat(lom_scan *s, const float *d_src_xyz, size_t n, size_t stride_bytes, const float guess_t[3],
                           const float guess_q_wxyz[4], int reps, float out_t[3], float out_q_wxyz[4],
                           lom_align_stats *total_or_null);
+/* lom_match_align_batch / _batch_device on the context */
+int lom_scan_align_batch(lom_scan *s, const lom_align_problem *p, int count, lom_align_result *out, int *best_or_null);
+int lom_scan_align_batch_device(lom_scan *s, const lom_align_problem *p, int count, lom_align_result *out,
+                                int *best_or_null);
 int64_t lom_scan_find_pairs(lom_scan *s, const float *src_xyz, size_t n, size_t stride_bytes, const float t[3],
                             const float q_wxyz[4], float max_dist, lom_correspondence *out);
 int64_t lom_scan_find_pairs_sq(lom_scan *s, const float *src_xyz, size_t n, size_t stride_bytes, const float t[3],

@@ -328,7 +328,40 @@ public:
         if (rc != LOM_OK) throw Error(rc, lom_scan_last_error(ctx));
         return Pose3D::from(o);
     }
+    // K (cloud, guess) problems against one keyframe in one call (lom_scan_align_batch): the poses align() would return
+    // for each, bit for bit; per-problem stats in batch_stats, the best problem's index in best (-1 for none)
+    std::vector<Pose3D> alignBatch(const VoxelGrid &keyframe, const std::vector<const PointCloud<PointXYZ> *> &clouds,
+                                   const std::vector<Pose3D> &guesses)
+    {
+        if (clouds.size() != guesses.size()) throw Error(LOM_ERR_ARG, "alignBatch: one guess per cloud");
+        std::vector<lom_align_problem> p(clouds.size());
+        for (size_t i = 0; i < clouds.size(); i++) {
+            if (!clouds[i]) throw Error(LOM_ERR_ARG, "alignBatch: null cloud");
+            const lom_pose g = guesses[i].c();
+            p[i].xyz = clouds[i]->points.empty() ? nullptr : &clouds[i]->points.data()->x;
+            p[i].n = clouds[i]->points.size();
+            p[i].stride_bytes = sizeof(PointXYZ);
+            for (int a = 0; a < 3; a++) p[i].guess_t[a] = g.t[a];
+            for (int a = 0; a < 4; a++) p[i].guess_q_wxyz[a] = g.q[a];
+        }
+        std::vector<lom_align_result> r(p.size());
+        lom_scan *ctx = keyframe.scan_context();
+        const int rc = lom_scan_align_batch(ctx, p.data(), (int)p.size(), r.data(), &best);
+        if (rc != LOM_OK) throw Error(rc, lom_scan_last_error(ctx));
+        std::vector<Pose3D> out;
+        batch_stats.clear();
+        for (const lom_align_result &x : r) {
+            lom_pose o;
+            for (int a = 0; a < 3; a++) o.t[a] = x.t[a];
+            for (int a = 0; a < 4; a++) o.q[a] = x.q_wxyz[a];
+            out.push_back(Pose3D::from(o));
+            batch_stats.push_back(x.stats);
+        }
+        return out;
+    }
     lom_align_stats last_stats{};
+    std::vector<lom_align_stats> batch_stats;
+    int best = -1;
 };
 
 // ---- CloudTransformer::transform / transformWithNormals (src/utils/cloud_transform.h:43-97)

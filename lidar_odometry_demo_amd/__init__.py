@@ -298,6 +298,8 @@ class CloudMatcher:
 
     def __init__(self):
         self.stats = None
+        self.batch_stats = None
+        self.best = None
 
     def align(self, keyframe, planar_cloud, position_guess):
         xyz = capi.xyz_array(planar_cloud)
@@ -337,6 +339,44 @@ class CloudMatcher:
         a = np.array(raw[:], np.float64).reshape(5, 40)
         trace = [(a[e, :7].copy(), a[e, 8:40].copy()) for e in range(ne.value)]
         return Pose3D(np.array(ot[:], np.float32), np.array(oq[:], np.float32)), trace
+
+    def _batch(self, keyframe, problems, count, keep, device):
+        res = (capi.AlignResult * max(count, 1))()
+        best = C.c_int(-1)
+        fn, chk = _align_entry(keyframe, "align_batch_device" if device else "align_batch")
+        chk(fn(keyframe.handle, problems if count else None, count, res, C.byref(best)))
+        del keep
+        self.batch_stats = [dict(res[i].stats.asdict(), round=res[i].round) for i in range(count)]
+        self.best = best.value
+        return [Pose3D(np.array(res[i].t[:], np.float32), np.array(res[i].q_wxyz[:], np.float32)) for i in range(count)]
+
+    @staticmethod
+    def _problem(p, ptr, n, guess, stride_bytes):
+        p.xyz = ptr
+        p.n = int(n)
+        p.stride_bytes = int(stride_bytes)
+        p.guess_t[:] = [float(v) for v in np.asarray(guess.translation, np.float32)]
+        p.guess_q_wxyz[:] = [float(v) for v in np.asarray(guess.rotation, np.float32)]
+
+    def alignBatch(self, keyframe, clouds, guesses):
+        """K (cloud, guess) problems against one keyframe in ONE call (lom_match_align_batch): the K solves run side by
+        side on the device.  Returns the poses align() would return, bit for bit; per-problem stats in `batch_stats`,
+        the best problem's index (most valid correspondences, then lowest cost) in `best`.  `keyframe`: a VoxelGrid or a
+        ScanContext."""
+        if len(clouds) != len(guesses):
+            raise ValueError("one guess per cloud")
+        arrays = [capi.xyz_array(c) for c in clouds]
+        problems = (capi.AlignProblem * max(len(arrays), 1))()
+        for i, (xyz, g) in enumerate(zip(arrays, guesses)):
+            self._problem(problems[i], xyz.ctypes.data if len(xyz) else None, len(xyz), g, 12)
+        return self._batch(keyframe, problems, len(arrays), arrays, False)
+
+    def alignBatchDevice(self, keyframe, items, stride_bytes=12):
+        """alignBatch with device-resident clouds: items = [(device pointer, n, guess), ...]."""
+        problems = (capi.AlignProblem * max(len(items), 1))()
+        for i, (ptr, n, g) in enumerate(items):
+            self._problem(problems[i], ptr, n, g, stride_bytes)
+        return self._batch(keyframe, problems, len(items), None, True)
 
     def alignDevice(self, keyframe, d_src_ptr, n, position_guess, stride_bytes=12):
         """Source cloud already resident in HBM (device pointer, e.g. torch tensor.data_ptr())."""

@@ -57,6 +57,16 @@ class AlignStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AlignProblem(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("n", C.c_size_t), ("stride_bytes", C.c_size_t), ("guess_t", C.c_float * 3),
+                ("guess_q_wxyz", C.c_float * 4)]
+
+
+class AlignResult(C.Structure):
+    _fields_ = [("t", C.c_float * 3), ("q_wxyz", C.c_float * 4), ("stats", AlignStats), ("round", C.c_int32),
+                ("pad", C.c_int32)]
+
+
 # lidar_point::PointXYZIRT (src/lidar_point_type.h:13-21), 32 bytes
 POINT_XYZIRT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad0", "<f4"), ("intensity", "<f4"),
                          ("ring", "<u2"), ("pad1", "<u2"), ("time", "<f4"), ("pad2", "<f4")])
@@ -128,12 +138,15 @@ EXPORTED = [
     "lom_frontend_set_option", "lom_host_comm_set_timeout", "lom_host_comm_abort", "lom_host_comm_last_error",
     "lom_scan_create", "lom_scan_destroy", "lom_scan_last_error", "lom_scan_set_option", "lom_scan_set_stream",
     "lom_scan_get_stream", "lom_scan_create_on_partition", "lom_scan_align", "lom_scan_align_device", "lom_scan_align_repeat", "lom_scan_find_pairs", "lom_scan_find_pairs_sq",
+    "lom_match_align_batch", "lom_match_align_batch_device", "lom_scan_align_batch", "lom_scan_align_batch_device",
+    "lom_align_batch_best",
 ]
 
 # lom_option / counters of include/lidar_odometry_amd.h
 OPT_HOST_LM, OPT_DEVICE_PATIENCE_TICKS, OPT_DEBUG_LM_STAMPS, OPT_DEBUG_TIMING, OPT_NO_TEMPORAL_BOUND, OPT_COUNT_CANDIDATES = 1, 2, 3, 4, 5, 6
 OPT_TEST_GIVE_UP_AT_OUTER, OPT_TEST_GRID_GIVE_UP, OPT_TEST_FORCE_HOST_REDO = 100, 101, 102
 OPT_NO_BULK_INSERT, OPT_TEST_BULK_PARTITION_MAX = 7, 106
+OPT_TEST_BATCH_ROUND_MAX = 107
 OPT_TEST_GRID_GIVE_UP_MATCHING_DS, OPT_TEST_GRID_GIVE_UP_UPDATE_DS, OPT_TEST_GRID_GIVE_UP_KEYFRAME = 103, 104, 105
 COUNTER_GRID_REDOS = 0
 COUNTER_CLEANUPS_BEHIND_ALIGN = 1
@@ -225,6 +238,11 @@ def lib():
     L.lom_match_align_device.argtypes = L.lom_match_align.argtypes
     L.lom_debug_match_stamps.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_float, vp, C.c_size_t,
                                          C.POINTER(C.c_uint32)]
+    L.lom_match_align_batch.argtypes = [vp, C.POINTER(AlignProblem), C.c_int, C.POINTER(AlignResult), C.POINTER(C.c_int)]
+    L.lom_match_align_batch_device.argtypes = L.lom_match_align_batch.argtypes
+    L.lom_scan_align_batch.argtypes = L.lom_match_align_batch.argtypes
+    L.lom_scan_align_batch_device.argtypes = L.lom_match_align_batch.argtypes
+    L.lom_align_batch_best.argtypes = [C.POINTER(AlignResult), C.c_int]
     L.lom_match_align_repeat.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_int, fp, fp, C.POINTER(AlignStats)]
     L.lom_debug_eval_sums.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, dp, dp, dp]
     L.lom_debug_lm_trace.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_int, dp, C.POINTER(C.c_int), fp, fp,

@@ -229,6 +229,17 @@ struct lom_map {
     uint64_t spec_mutations = 0;
     uint32_t cleanups_taken = 0;  // radius cleanups that used such a scan (lom_map_debug_counter)
     unsigned long long report_seq = 0, lm_seq = 0, lm_launches = 0;
+    // batched align (lom_match_align_batch): buffers of its own -- per-problem solve states and descriptors, records,
+    // k_match counters, exchange sets per round slot, staged host scans -- and per-problem reports in pinned host memory;
+    // the single align's align_state / scan_on / xrec / report are never touched by it
+    lom::DeviceBuf batch_dev, batch_rec, batch_cnt, batch_xrec, batch_src;
+    void *h_batch = nullptr;  // pinned staging of the states and descriptors (one copy per call)
+    size_t h_batch_bytes = 0;
+    void *h_batch_report = nullptr, *d_batch_report = nullptr;  // AlignReport slots, 256 bytes each
+    size_t batch_report_slots = 0;
+    unsigned long long batch_report_seq = 0, batch_lm_seq = 0;
+    uint32_t lm_batch_per_cu[4] = {0, 0, 0, 0};  // k_lm blocks per CU a batch round may count on, per variant (cached)
+    int test_batch_round_max = 0;  // LOM_OPT_TEST_BATCH_ROUND_MAX: problems per round at most (0: by residency)
     uint32_t lm_max_blocks[4] = {0, 0, 0, 0};  // co-resident k_lm workgroups this device admits, per variant (occupancy query, cached)
     double last_counters[4] = {0, 0, 0, 0};  // valid, cand, occ, queries of the last k_match
 

@@ -230,6 +230,24 @@ struct Stamper<true> {
 };
 #define LOM_STAMP(i) stamper.mark(i)
 
+// Batched align (lom_match_align_batch): one problem of a round, read by the batch forms of k_match and k_lm from a
+// small array in HBM (blockIdx.y = the problem's place in the round).  Everything that belongs to one problem -- its
+// scan, records, search counters, solve state, exchange set and report -- hangs off its descriptor.
+struct BatchProblem {
+    const char *src;
+    size_t stride;
+    MatchRec *rec;
+    uint32_t *block_counters;
+    AlignState *state;
+    AlignReport *report;  // device view of pinned host memory
+    void *xrec;           // this round slot's exchange sets (XWord)
+    uint32_t n, match_blocks;
+    float guess_t[3], guess_q[4];
+    float max_sq;
+    double prior_b[3];
+};
+typedef const __attribute__((address_space(4))) BatchProblem *ConstBatch;  // read with scalar loads, like kernel arguments
+
 // kChained: the pose comes from the AlignState a previous k_lm left in HBM (read through the
 // constant address space: scalar loads, like kernel arguments), and the launch does nothing once
 // the outer loop has finished -- the host enqueues several outer iterations ahead.
@@ -241,17 +259,35 @@ struct Stamper<true> {
 // cand(q), the tests' n_cand / n_occ) need every one of the 27 slots.  Without them (the product's align, unless
 // LOM_OPT_COUNT_CANDIDATES asks) a neighbour voxel that the bound prunes is not even looked up: its slot is neither
 // hashed nor loaded -- the result cannot depend on whether a voxel exists whose points could not win.
-template <int G, int kU, int kMinWaves, bool kStamp = false, bool kChained = false, bool kPrev = kChained, bool kCount = true>
+// kBatch (chained only): one launch for all problems of a batched align's round -- blockIdx.y selects the problem
+// (`batch[blockIdx.y]`: scan, records, counters, state), blockIdx.x runs over THAT problem's search grid (workgroups
+// beyond it leave at once); per query everything is what the single align's launch does.
+template <int G, int kU, int kMinWaves, bool kStamp = false, bool kChained = false, bool kPrev = kChained, bool kCount = true,
+          bool kBatch = false>
 __global__ __launch_bounds__(kMatchThreads, kMinWaves) void k_match(MapView map, const char *__restrict__ src, size_t stride,
                                                          uint32_t n, PoseArgs Parg, int32_t *__restrict__ out_idx,
                                                          MatchRec *__restrict__ out_rec,
                                                          QStat *__restrict__ out_stat,
                                                          uint32_t *__restrict__ block_counters,
                                                          unsigned long long *__restrict__ stamps = nullptr,
-                                                         const AlignState *state = nullptr)
+                                                         const AlignState *state = nullptr,
+                                                         const BatchProblem *batch = nullptr)
 {
     static_assert(G == 16 && kU == 4, "one query per 16-lane DPP row, a chunk of four rows per lane and trip");
+    static_assert(!kBatch || (kChained && !kStamp), "the batch form is a chained search");
     constexpr uint32_t kRowsLog2 = 2;  // rows per chunk
+    uint32_t batch_grid = 0;  // (kBatch) this problem's search grid
+    if constexpr (kBatch) {
+        const ConstBatch d = (ConstBatch)(batch + blockIdx.y);
+        src = d->src;
+        stride = d->stride;
+        n = d->n;
+        out_rec = d->rec;
+        block_counters = d->block_counters;
+        state = d->state;
+        batch_grid = d->match_blocks;
+        if (blockIdx.x >= batch_grid) return;
+    }
     // the first query's source point is on its way before anything else: the chained form's pose comes through a
     // scalar-cache miss of its own, and the LDS tables below need a barrier -- one memory round trip instead of two
     // ahead of the first probe (the loop fetches the next query's point the same way, behind the current one's work)
@@ -306,7 +342,7 @@ __global__ __launch_bounds__(kMatchThreads, kMinWaves) void k_match(MapView map,
     __shared__ float s_gap[kGroups][12];      // per query [axis][to voxel i-1, 0, to voxel i+1]: squared pruning gaps
     const int gl = threadIdx.x % G;
     const int grp = threadIdx.x / G;
-    const uint32_t groups_total = gridDim.x * kGroups;
+    const uint32_t groups_total = (kBatch ? batch_grid : gridDim.x) * kGroups;
     // per-group counters live in LDS (one ds_add per counter and query by the writing lane):
     // four fewer live registers keep the kernel at 64 VGPRs without spilling
     if (gl < 4) s_cnt[grp][gl] = 0u;
@@ -1347,7 +1383,10 @@ __device__ __forceinline__ void accumulate_all(const MatchRec *__restrict__ rec,
 // kPolicyTwice (LOM_DEBUG_LM_TWICE=1 at create, a measurement aid): the first wave runs every policy step twice -- the
 // first time on state that is put back afterwards -- and the phase stamps time the second run: the same instructions
 // on the same data, with the step's code already in the instruction cache.
-template <int kT, int kBlocks = (int)kMaxLmBlocks, int kRegPts = 1, bool kPolicyTwice = false>
+// kBatch: one launch for all problems of a batched align's round (single GPU, no exchange, no debug outputs) --
+// blockIdx.y selects the problem (`batch[blockIdx.y]`: records, n, guess, state, k_match's counters, exchange set,
+// report), gridDim.x is the single align's grid for that problem; a give-up test applies to problem 0 of the launch.
+template <int kT, int kBlocks = (int)kMaxLmBlocks, int kRegPts = 1, bool kPolicyTwice = false, bool kBatch = false>
 __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uint32_t n, AlignState *state,
                                                      LmInit init, int first_outer,
                                                      const uint32_t *__restrict__ block_counters,
@@ -1356,8 +1395,21 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
                                                      unsigned long long report_seq,
                                                      unsigned long long timeout_ticks,
                                                      unsigned long long *dbg_stamps, P2pArgs px,
-                                                     double *dbg_trace, int test_give_up)
+                                                     double *dbg_trace, int test_give_up,
+                                                     const BatchProblem *batch = nullptr)
 {
+    static_assert(!kBatch || !kPolicyTwice, "the batch form is a product kernel");
+    if constexpr (kBatch) {
+        const ConstBatch d = (ConstBatch)(batch + blockIdx.y);
+        rec = d->rec;
+        n = d->n;
+        state = d->state;
+        block_counters = d->block_counters;
+        n_match_blocks = d->match_blocks;
+        xrec = reinterpret_cast<XWord *>(d->xrec);
+        report = d->report;
+        if (blockIdx.y != 0) test_give_up = 0;
+    }
     __shared__ double s_acc[(kT / 64) * 32];  // the waves' totals of one evaluation
     __shared__ double s_tot[kRecWords];
     __shared__ double s_part[kT];
@@ -1409,7 +1461,8 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
     {
         const int k = tid < 7 ? tid : 0;
         if (first_outer) {  // (uniform)
-            x0 = k < 4 ? init.q[k] : init.t[k - 4];
+            if constexpr (kBatch) x0 = k < 4 ? batch[blockIdx.y].guess_q[k] : batch[blockIdx.y].guess_t[k - 4];
+            else x0 = k < 4 ? init.q[k] : init.t[k - 4];
         } else {
             const float *from = k < 4 ? &state->pose_q[k] : &state->pose_t[k - 4];
             x0 = *from;
@@ -1528,11 +1581,13 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
                     counters[2] = s_tot[30];
                     counters[3] = px.nranks > 1 ? s_tot[31] : (double)n;
                 }
-                a = kRegState ? lmw2_begin<true>(W, r_lm, s_tot, s_x, init.prior_b, lane)
-                              : lmw2_begin<false>(W, s_lm, s_tot, s_x, init.prior_b, lane);
+                const double *prior_b = kBatch ? batch[blockIdx.y].prior_b : init.prior_b;
+                a = kRegState ? lmw2_begin<true>(W, r_lm, s_tot, s_x, prior_b, lane)
+                              : lmw2_begin<false>(W, s_lm, s_tot, s_x, prior_b, lane);
             } else {
-                a = kRegState ? lmw2_feed<true>(W, r_lm, s_tot, s_x, init.prior_b, lane)
-                              : lmw2_feed<false>(W, s_lm, s_tot, s_x, init.prior_b, lane);
+                const double *prior_b = kBatch ? batch[blockIdx.y].prior_b : init.prior_b;
+                a = kRegState ? lmw2_feed<true>(W, r_lm, s_tot, s_x, prior_b, lane)
+                              : lmw2_feed<false>(W, s_lm, s_tot, s_x, prior_b, lane);
             }
             // the point of the next evaluation lands in s_x
             if (a == LM_PROPOSE)
@@ -1572,7 +1627,7 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
     rotation_matrix(pq, R);  // voxel_grid.h:212
     for (int i = 0; i < 9; i++) st.P.R[i] = (double)R[i];
     for (int i = 0; i < 3; i++) st.P.t[i] = (double)pt[i];
-    st.P.max_sq = init.max_sq;
+    st.P.max_sq = kBatch ? batch[blockIdx.y].max_sq : init.max_sq;
     for (int a = 0; a < 3; a++) st.pose_t[a] = pt[a];
     for (int a = 0; a < 4; a++) st.pose_q[a] = pq[a];
     st.finished = finished;
@@ -1768,7 +1823,7 @@ static int launch_match(ScanCtx &c, const float t[3], const float q[4], float ma
         auto launch = [&](auto kernel, QStat *st, const AlignState *as) {
             hipLaunchKernelGGL(kernel, dim3(c.match_blocks), dim3(kMatchThreads), 0, m->stream, view_of(m), c.d_src, c.stride,
                                c.n, P, (int32_t *)m->scan_idx.p, (MatchRec *)m->scan_on.p, st, d_block_counters(m),
-                               (unsigned long long *)nullptr, as);
+                               (unsigned long long *)nullptr, as, (const BatchProblem *)nullptr);
         };
         QStat *st = (stats && !chained) ? (QStat *)m->scan_stats.p : (QStat *)nullptr;
         // (a chained launch always follows a search of the same scan: launch_pair's first pair is not chained)
@@ -2113,7 +2168,8 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
                                (const uint32_t *)d_block_counters(m), c.match_blocks, (XWord *)m->xrec.p, m->lm_seq,
                                reinterpret_cast<AlignReport *>(m->d_report), seq0 + (unsigned long long)i + 1,
                                m->patience_ticks, dbg, px,
-                               (d_trace && i == trace_outer) ? d_trace : (double *)nullptr, i == give_up_outer ? 1 : 0);
+                               (d_trace && i == trace_outer) ? d_trace : (double *)nullptr, i == give_up_outer ? 1 : 0,
+                               (const BatchProblem *)nullptr);
         };
         if (shape == kLmSmall)
             launch(k_lm<(int)kLmSmallThreads>);
@@ -2346,6 +2402,423 @@ static int stage_scan(lom_map *m, const float *src, size_t n, size_t stride, con
     if (rc != LOM_OK) return rc;
     if (bytes) LOM_HIP(m, hipMemcpyAsync(m->scan_src.p, src, bytes, hipMemcpyHostToDevice, m->stream));
     *d_src = (const char *)m->scan_src.p;
+    return LOM_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Batched align (lom_match_align_batch): K (scan, guess) problems against one keyframe, the K solves side by side in
+// ONE device-resident chain -- per outer iteration one k_match launch and one k_lm launch for all problems of a round.
+//
+// Grouping.  A problem runs with the k_lm variant (lm_shape) and grid (nb) the single align would give it on this handle,
+//   so the workgroup -> point assignment and every reduction order are the single align's: bit-equal results.  Problems
+//   are grouped by (variant, nb) in order of first appearance; a group runs as one or more rounds.
+// Rounds.  k_lm's workgroups wait for each other, so a round's whole grid must be resident at once: problems per round =
+//   floor(CUs x blocks per CU / nb), CUs of the context's partition where it has one.  Blocks per CU: the occupancy query
+//   for the batch kernel, capped at 2 (the query over-reports only where SGPRs bind, from 7 blocks of 256 threads per CU
+//   up -- MI355X "Residency and cooperative launch" -- far above the cap).  LOM_OPT_TEST_BATCH_ROUND_MAX caps it further.
+// Chain.  kPairsAhead pairs go out at once, then one pair per round of reports while any problem of the round is
+//   unfinished (a finished problem's later launches return at once, as the single align's do), at most 35.
+// Give-up.  A problem whose k_lm gave up (its error word) is redone alone through the single align; the others keep
+//   their device results.
+// Isolation.  Own states, records, counters, exchange sets and reports: the single align's align_state, scan_on, xrec
+//   and report, and the radius cleanup's scratch, are not touched.
+// ---------------------------------------------------------------------------
+struct BatchItem {
+    const char *src;
+    size_t stride;
+    uint32_t n;
+    float gt[3], gq[4];
+};
+
+static const void *lm_batch_kernel(LmShape shape)
+{
+    switch (shape) {
+    case kLmSmall: return reinterpret_cast<const void *>(k_lm<(int)kLmSmallThreads, (int)kMaxLmBlocks, 1, false, true>);
+    case kLmSmall2: return reinterpret_cast<const void *>(k_lm<(int)kLmSmallThreads, (int)kMaxLmBlocks, 2, false, true>);
+    case kLmMid: return reinterpret_cast<const void *>(k_lm<kEvalThreads, (int)kMaxLmBlocks, 1, false, true>);
+    default: return reinterpret_cast<const void *>(k_lm<kEvalThreads, (int)kMaxLmBlocksBig, 1, false, true>);
+    }
+}
+
+constexpr uint32_t kBatchBlocksPerCuCap = 2;
+
+static int lm_batch_per_cu(lom_map *m, LmShape shape, uint32_t *out)
+{
+    uint32_t &cached = m->lm_batch_per_cu[shape];
+    if (!cached) {
+        int per_cu = 0;
+        const int threads = (shape == kLmSmall || shape == kLmSmall2) ? (int)kLmSmallThreads : kEvalThreads;
+        LOM_HIP(m, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lm_batch_kernel(shape), threads, 0));
+        cached = (uint32_t)std::max(1, std::min(per_cu, (int)kBatchBlocksPerCuCap));
+    }
+    *out = cached;
+    return LOM_OK;
+}
+
+static int device_cus(lom_map *m, uint32_t *out)
+{
+    int cus = 0;
+    LOM_HIP(m, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
+    *out = m->partition_cus ? m->partition_cus : (uint32_t)std::max(1, cus);
+    return LOM_OK;
+}
+
+// the single align's result from a final report (align_chained's epilogue)
+static void result_from_report(const volatile AlignReport *rp, bool counted, uint32_t nb, lom_align_result &r)
+{
+    lom_align_stats &st = r.stats;
+    std::memset(&st, 0, sizeof st);
+    st.outer_iterations = rp->outer_done;
+    st.match_launches = rp->outer_done;
+    st.lm_iterations = rp->lm_iterations;
+    st.evaluations = rp->evaluations;
+    st.valid_last = (int64_t)rp->valid_last;
+    st.cand_total = (int64_t)rp->cand_total;
+    st.occ_total = (int64_t)rp->occ_total;
+    st.queries = (int64_t)rp->queries_total;
+    st.algorithmic_bytes = counted ? 444.0 * rp->queries_total + 12.0 * rp->cand_total + 12.0 * rp->valid_total : 0.0;
+    st.final_cost = rp->final_cost;
+    st.last_step_norm = rp->last_step_norm;
+    st.lm_workgroups = (int32_t)nb;
+    float pq[4] = {rp->pose_q[0], rp->pose_q[1], rp->pose_q[2], rp->pose_q[3]};
+    {   // cloud_matcher.cpp:175 rotation.normalize(), f32
+        const float n2 = (pq[0] * pq[0] + pq[1] * pq[1]) + (pq[2] * pq[2] + pq[3] * pq[3]);
+        const float nn = std::sqrt(n2);
+        for (int a = 0; a < 4; a++) pq[a] = pq[a] / nn;
+    }
+    for (int a = 0; a < 3; a++) r.t[a] = rp->pose_t[a];
+    for (int a = 0; a < 4; a++) r.q_wxyz[a] = pq[a];
+}
+
+static inline size_t round_up256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// all problems through the device-resident chain; gave_up[i]: problem i's solve gave up (to be redone)
+static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_align_result *out, std::vector<char> &gave_up,
+                               double &launch_s, double &wait_s)
+{
+    static_assert(sizeof(AlignReport) <= 256, "one report slot");
+    const uint32_t part = m->stream == m->own_stream ? m->partition_cus : 0u;
+    std::vector<LmShape> shape(count);
+    std::vector<uint32_t> nb(count), mb(count);
+    for (int i = 0; i < count; i++) {
+        const uint32_t n = it[i].n;
+        shape[i] = lm_shape(n);
+        const uint32_t threads = (shape[i] == kLmSmall || shape[i] == kLmSmall2) ? kLmSmallThreads : (uint32_t)kEvalThreads;
+        uint32_t limit = 0;
+        int rc = lm_block_limit(m, shape[i], &limit);
+        if (rc != LOM_OK) return rc;
+        nb[i] = std::min(std::min(std::max(1u, (n + threads - 1) / threads), shape[i] == kLmBig ? kMaxLmBlocksBig : kMaxLmBlocks),
+                         limit);
+        mb[i] = n ? match_grid(n, part) : 0u;
+    }
+    // groups by (variant, nb) in order of first appearance, cut into rounds; `order` lists the problems round by round
+    struct Round {
+        int first, size;  // range of `order`
+        LmShape shape;
+        uint32_t nb;
+    };
+    std::vector<int> order;
+    std::vector<Round> rounds;
+    {
+        std::vector<char> taken(count, 0);
+        uint32_t cus = 0;
+        int rc = device_cus(m, &cus);
+        if (rc != LOM_OK) return rc;
+        for (int i = 0; i < count; i++) {
+            if (taken[i]) continue;
+            uint32_t per_cu = 0;
+            if ((rc = lm_batch_per_cu(m, shape[i], &per_cu)) != LOM_OK) return rc;
+            int per_round = (int)std::max(1u, cus * per_cu / nb[i]);
+            if (m->test_batch_round_max > 0) per_round = std::min(per_round, m->test_batch_round_max);
+            std::vector<int> members;
+            for (int k = i; k < count; k++)
+                if (!taken[k] && shape[k] == shape[i] && nb[k] == nb[i]) {
+                    taken[k] = 1;
+                    members.push_back(k);
+                }
+            for (size_t a = 0; a < members.size(); a += (size_t)per_round) {
+                const int size = (int)std::min(members.size() - a, (size_t)per_round);
+                rounds.push_back(Round{(int)order.size(), size, shape[i], nb[i]});
+                for (int k = 0; k < size; k++) order.push_back(members[a + (size_t)k]);
+            }
+        }
+    }
+    int max_slots = 0;
+    for (const Round &r : rounds) max_slots = std::max(max_slots, r.size);
+    // buffers: records and k_match counters per problem, exchange sets per round slot, states + descriptors per problem
+    std::vector<size_t> off_rec(count), off_cnt(count);
+    size_t rec_bytes = 0, cnt_bytes = 0;
+    for (int i = 0; i < count; i++) {
+        off_rec[i] = rec_bytes;
+        rec_bytes += round_up256((size_t)std::max(it[i].n, 1u) * sizeof(MatchRec));
+        off_cnt[i] = cnt_bytes;
+        cnt_bytes += round_up256((size_t)std::max(mb[i], 1u) * 16);
+    }
+    const size_t xset_bytes = (size_t)2 * kMaxLmBlocksBig * kRecWords * sizeof(XWord);
+    const size_t states_bytes = round_up256((size_t)count * sizeof(AlignState));
+    const size_t dev_bytes = states_bytes + (size_t)count * sizeof(BatchProblem);
+    int rc;
+    if ((rc = ensure(m, m->batch_rec, rec_bytes)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->batch_cnt, cnt_bytes)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->batch_dev, dev_bytes)) != LOM_OK) return rc;
+    {
+        void *before = m->batch_xrec.p;
+        if ((rc = ensure(m, m->batch_xrec, (size_t)max_slots * xset_bytes)) != LOM_OK) return rc;
+        if (m->batch_xrec.p != before)  // fresh sets: no word may carry a sequence number of this call
+            LOM_HIP(m, hipMemsetAsync(m->batch_xrec.p, 0, m->batch_xrec.bytes, m->stream));
+    }
+    if (m->h_batch_bytes < dev_bytes) {
+        LOM_HIP(m, hipStreamSynchronize(m->stream));
+        if (m->h_batch) LOM_HIP(m, hipHostFree(m->h_batch));
+        m->h_batch = nullptr;
+        m->h_batch_bytes = 0;
+        const size_t bytes = std::max(dev_bytes, (size_t)4096);
+        hipError_t e = hipHostMalloc(&m->h_batch, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) return set_error(m, LOM_ERR_OOM, "hipHostMalloc(batch staging)", e);
+        m->h_batch_bytes = bytes;
+    }
+    if (m->batch_report_slots < (size_t)count) {
+        LOM_HIP(m, hipStreamSynchronize(m->stream));
+        if (m->h_batch_report) LOM_HIP(m, hipHostFree(m->h_batch_report));
+        m->h_batch_report = m->d_batch_report = nullptr;
+        m->batch_report_slots = 0;
+        const size_t slots = std::max((size_t)count, (size_t)16);
+        hipError_t e = hipHostMalloc(&m->h_batch_report, slots * 256, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&m->d_batch_report, m->h_batch_report, 0);
+        if (e != hipSuccess) return set_error(m, LOM_ERR_OOM, "hipHostMalloc(batch reports)", e);
+        std::memset(m->h_batch_report, 0, slots * 256);
+        m->batch_report_slots = slots;
+    }
+    // states (the guess as the first search's pose) and descriptors, in `order`, one copy to the device
+    AlignState *h_states = reinterpret_cast<AlignState *>(m->h_batch);
+    BatchProblem *h_desc = reinterpret_cast<BatchProblem *>((char *)m->h_batch + states_bytes);
+    AlignState *d_states = reinterpret_cast<AlignState *>(m->batch_dev.p);
+    const BatchProblem *d_desc = reinterpret_cast<const BatchProblem *>((char *)m->batch_dev.p + states_bytes);
+    for (const Round &r : rounds)
+        for (int k = 0; k < r.size; k++) {
+            const int j = r.first + k, i = order[j];
+            AlignState &st = h_states[j];
+            std::memset(&st, 0, sizeof st);
+            pose_args(it[i].gt, it[i].gq, sq_f32(0.3f), st.P);  // cloud_matcher.cpp:107, :139
+            for (int a = 0; a < 3; a++) st.pose_t[a] = it[i].gt[a];
+            for (int a = 0; a < 4; a++) st.pose_q[a] = it[i].gq[a];
+            BatchProblem &d = h_desc[j];
+            std::memset(&d, 0, sizeof d);
+            d.src = it[i].src;
+            d.stride = it[i].stride;
+            d.rec = reinterpret_cast<MatchRec *>((char *)m->batch_rec.p + off_rec[i]);
+            d.block_counters = reinterpret_cast<uint32_t *>((char *)m->batch_cnt.p + off_cnt[i]);
+            d.state = d_states + j;
+            d.report = reinterpret_cast<AlignReport *>((char *)m->d_batch_report + (size_t)j * 256);
+            d.xrec = (char *)m->batch_xrec.p + (size_t)k * xset_bytes;
+            d.n = it[i].n;
+            d.match_blocks = mb[i];
+            for (int a = 0; a < 3; a++) d.guess_t[a] = it[i].gt[a];
+            for (int a = 0; a < 4; a++) d.guess_q[a] = it[i].gq[a];
+            d.max_sq = 0.3f * 0.3f;                                              // :139, voxel_grid.h:215
+            for (int a = 0; a < 3; a++) d.prior_b[a] = (double)it[i].gt[a];  // :153
+            volatile AlignReport *rp = reinterpret_cast<volatile AlignReport *>((char *)m->h_batch_report + (size_t)j * 256);
+            rp->error = 0;
+        }
+    LOM_HIP(m, hipMemcpyAsync(m->batch_dev.p, m->h_batch, dev_bytes, hipMemcpyHostToDevice, m->stream));
+    const int give_up_outer = m->test_give_up_outer;  // one shot: the first problem of the first round
+    m->test_give_up_outer = -1;
+    const bool count_mode = m->opt_count;
+    P2pArgs px = p2p_args(m);
+    for (size_t ri = 0; ri < rounds.size(); ri++) {
+        const Round &R = rounds[ri];
+        uint32_t mb_max = 0;
+        for (int k = 0; k < R.size; k++) mb_max = std::max(mb_max, mb[order[R.first + k]]);
+        const BatchProblem *desc = d_desc + R.first;
+        const uint32_t threads = (R.shape == kLmSmall || R.shape == kLmSmall2) ? kLmSmallThreads : (uint32_t)kEvalThreads;
+        const unsigned long long seq0 = m->batch_report_seq;
+        int launched = 0;
+        auto launch_pair = [&]() -> int {
+            const int i = launched;
+            const double t_l = now_s();
+            if (mb_max) {
+                const bool prev = i > 0 && !m->opt_no_temporal;  // (the first search of a scan: no previous records)
+                PoseArgs P;
+                std::memset(&P, 0, sizeof P);
+                auto launch = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(mb_max, R.size), dim3(kMatchThreads), 0, m->stream, view_of(m),
+                                       (const char *)nullptr, (size_t)0, 0u, P, (int32_t *)nullptr, (MatchRec *)nullptr,
+                                       (QStat *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr,
+                                       (const AlignState *)nullptr, desc);
+                };
+                constexpr int W = kMatchMinWaves;
+                if (prev && count_mode) launch(k_match<kMatchG, kMatchRows, W, false, true, true, true, true>);
+                else if (prev) launch(k_match<kMatchG, kMatchRows, W, false, true, true, false, true>);
+                else if (count_mode) launch(k_match<kMatchG, kMatchRows, W, false, true, false, true, true>);
+                else launch(k_match<kMatchG, kMatchRows, W, false, true, false, false, true>);
+                LOM_HIP(m, hipGetLastError());
+            }
+            m->batch_lm_seq += 8;  // a solve spends at most 5 evaluations
+            LmInit init;
+            std::memset(&init, 0, sizeof init);
+            const int give_up = (ri == 0 && i == give_up_outer) ? 1 : 0;
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, dim3(R.nb, R.size), dim3(threads), 0, m->stream, (const MatchRec *)nullptr, 0u,
+                                   (AlignState *)nullptr, init, i == 0 ? 1 : 0, (const uint32_t *)nullptr, 0u,
+                                   (XWord *)nullptr, m->batch_lm_seq, (AlignReport *)nullptr,
+                                   seq0 + (unsigned long long)i + 1, m->patience_ticks, (unsigned long long *)nullptr, px,
+                                   (double *)nullptr, give_up, desc);
+            };
+            if (R.shape == kLmSmall) launch(k_lm<(int)kLmSmallThreads, (int)kMaxLmBlocks, 1, false, true>);
+            else if (R.shape == kLmSmall2) launch(k_lm<(int)kLmSmallThreads, (int)kMaxLmBlocks, 2, false, true>);
+            else if (R.shape == kLmMid) launch(k_lm<kEvalThreads, (int)kMaxLmBlocks, 1, false, true>);
+            else launch(k_lm<kEvalThreads, (int)kMaxLmBlocksBig, 1, false, true>);
+            LOM_HIP(m, hipGetLastError());
+            launch_s += now_s() - t_l;
+            launched++;
+            return LOM_OK;
+        };
+        std::vector<char> done(R.size, 0);
+        for (int i = 0; i < kPairsAhead; i++)
+            if ((rc = launch_pair()) != LOM_OK) return rc;
+        bool any_gave_up = false;
+        for (;;) {
+            const double t_w = now_s();
+            const unsigned long long want = seq0 + (unsigned long long)launched;
+            int open = 0;
+            for (int k = 0; k < R.size; k++) {
+                if (done[k]) continue;
+                const int j = R.first + k;
+                volatile AlignReport *rp = reinterpret_cast<volatile AlignReport *>((char *)m->h_batch_report + (size_t)j * 256);
+                uint64_t spins = 0;
+                while (rp->seq != want) {
+                    __builtin_ia32_pause();
+                    if (rp->error) break;
+                    if ((++spins & 0x3FFF) == 0) {
+                        const hipError_t e = hipStreamQuery(m->stream);
+                        if (e == hipSuccess) {
+                            if (rp->seq == want || rp->error) break;
+                            m->batch_report_seq = want;
+                            return set_error(m, LOM_ERR_HIP, "batched device solve ended without a report");
+                        } else if (e != hipErrorNotReady) {
+                            m->batch_report_seq = want;
+                            return set_error(m, LOM_ERR_HIP, "stream failed during the batched device solve", e);
+                        }
+                    }
+                }
+                __atomic_thread_fence(__ATOMIC_ACQUIRE);
+                const int i = order[j];
+                if (rp->error) {  // its later launches see the flag in its AlignState and return at once
+                    gave_up[i] = 1;
+                    out[i].round = (int32_t)ri;
+                    any_gave_up = true;
+                    done[k] = 1;
+                } else if (rp->finished) {
+                    result_from_report(rp, count_mode, R.nb, out[i]);
+                    out[i].round = (int32_t)ri;
+                    done[k] = 1;
+                } else {
+                    open++;
+                }
+            }
+            wait_s += now_s() - t_w;
+            if (open == 0 || launched >= 35) break;
+            if ((rc = launch_pair()) != LOM_OK) return rc;
+        }
+        m->batch_report_seq = seq0 + (unsigned long long)launched;
+        if (any_gave_up) LOM_HIP(m, hipStreamSynchronize(m->stream));
+    }
+    return LOM_OK;
+}
+
+static int align_batch(lom_map *m, const lom_align_problem *p, int count, lom_align_result *out, int *best, bool device_input)
+{
+    if (count == 0) {
+        if (best) *best = -1;
+        return LOM_OK;
+    }
+    for (int i = 0; i < count; i++)
+        if ((p[i].n && !p[i].xyz) || p[i].stride_bytes < 12 || (p[i].stride_bytes & 3) || p[i].n >= 0x7FFFFFFFull)
+            return LOM_ERR_ARG;
+    LOM_HIP(m, hipSetDevice(m->device));
+    m->last_error.clear();
+    double launch_s = 0.0, wait_s = 0.0;
+    int rc = resolve_pending(m);
+    if (rc != LOM_OK) return rc;
+    std::vector<BatchItem> it((size_t)count);
+    for (int i = 0; i < count; i++) {
+        it[i].src = (const char *)p[i].xyz;
+        it[i].stride = p[i].stride_bytes;
+        it[i].n = (uint32_t)p[i].n;
+        for (int a = 0; a < 3; a++) it[i].gt[a] = p[i].guess_t[a];
+        for (int a = 0; a < 4; a++) it[i].gq[a] = p[i].guess_q_wxyz[a];
+    }
+    if (!device_input) {
+        // host scans staged into one device buffer up front (a cloud shared by several problems once)
+        std::vector<size_t> off((size_t)count, 0);
+        size_t total = 0;
+        for (int i = 0; i < count; i++) {
+            int same = -1;
+            for (int k = 0; k < i && same < 0; k++)
+                if (p[k].xyz == p[i].xyz && p[k].n == p[i].n && p[k].stride_bytes == p[i].stride_bytes) same = k;
+            if (same >= 0) {
+                off[i] = off[same];
+                continue;
+            }
+            off[i] = total;
+            if (p[i].n) total += round_up256((p[i].n - 1) * p[i].stride_bytes + 12);
+        }
+        if ((rc = ensure(m, m->batch_src, std::max<size_t>(total, 256))) != LOM_OK) return rc;
+        const double t_l = now_s();
+        for (int i = 0; i < count; i++) {
+            bool first = true;
+            for (int k = 0; k < i && first; k++)
+                if (p[k].xyz == p[i].xyz && p[k].n == p[i].n && p[k].stride_bytes == p[i].stride_bytes) first = false;
+            it[i].src = (const char *)m->batch_src.p + off[i];
+            if (first && p[i].n)
+                LOM_HIP(m, hipMemcpyAsync((char *)m->batch_src.p + off[i], p[i].xyz, (p[i].n - 1) * p[i].stride_bytes + 12,
+                                          hipMemcpyHostToDevice, m->stream));
+        }
+        launch_s += now_s() - t_l;
+    }
+    // the single align's one-shot arms (a radius cleanup behind the next align, an idle hook) are the NEXT single align's:
+    // nothing below takes or runs them
+    const float spec = m->spec_radius;
+    void (*hook)(void *) = m->idle_hook;
+    void *hook_user = m->idle_user;
+    m->spec_radius = 0.f;
+    m->idle_hook = nullptr;
+    std::vector<char> redo((size_t)count, 0);
+    const bool chained = !m->comm && !m->host_comm && !m->opt_host_lm;
+    if (chained) {
+        server_stop(m);
+        rc = align_batch_chained(m, it.data(), count, out, redo, launch_s, wait_s);
+    } else {
+        // LOM_OPT_HOST_LM / an attached exchange: the single align's host-driven loop, problem by problem
+        std::fill(redo.begin(), redo.end(), 1);
+    }
+    for (int i = 0; rc == LOM_OK && i < count; i++) {
+        if (!redo[i]) continue;
+        m->last_error.clear();
+        if (!chained) out[i].round = -1;
+        rc = align_device_paths(m, it[i].src, it[i].n, it[i].stride, it[i].gt, it[i].gq, out[i].t, out[i].q_wxyz,
+                                &out[i].stats);
+        m->spec_radius = 0.f;
+        m->idle_hook = nullptr;
+        if (rc != LOM_OK) break;
+        if (chained) out[i].stats.host_fallback = 1;
+        launch_s += out[i].stats.host_launch_ms * 1e-3;
+        wait_s += out[i].stats.host_wait_ms * 1e-3;
+    }
+    m->spec_radius = spec;
+    m->idle_hook = hook;
+    m->idle_user = hook_user;
+    if (rc != LOM_OK) return rc;
+    for (int i = 0; i < count; i++) {
+        lom_align_stats &st = out[i].stats;
+        st.match_kernel_ms = 0.0;
+        st.profiled_launches = 0;
+        st.lm_kernel_ms = 0.0;
+        st.lm_profiled_launches = 0;
+        st.host_launch_ms = launch_s * 1e3;
+        st.host_wait_ms = wait_s * 1e3;
+    }
+    if (best) *best = lom_align_batch_best(out, count);
     return LOM_OK;
 }
 
@@ -2753,6 +3226,29 @@ int lom_match_align_repeat(lom_map *m, const float *d_src, size_t n, size_t stri
     }
     if (total) *total = acc;
     return LOM_OK;
+}
+
+int lom_align_batch_best(const lom_align_result *r, int count)
+{
+    if (!r || count <= 0) return -1;
+    int best = 0;
+    for (int i = 1; i < count; i++) {
+        const lom_align_stats &a = r[i].stats, &b = r[best].stats;
+        if (a.valid_last > b.valid_last || (a.valid_last == b.valid_last && a.final_cost < b.final_cost)) best = i;
+    }
+    return best;
+}
+
+int lom_match_align_batch(lom_map *m, const lom_align_problem *p, int count, lom_align_result *out, int *best)
+{
+    if (!m || count < 0 || (count > 0 && (!p || !out))) return LOM_ERR_ARG;
+    return align_batch(m, p, count, out, best, false);
+}
+
+int lom_match_align_batch_device(lom_map *m, const lom_align_problem *p, int count, lom_align_result *out, int *best)
+{
+    if (!m || count < 0 || (count > 0 && (!p || !out))) return LOM_ERR_ARG;
+    return align_batch(m, p, count, out, best, true);
 }
 
 int lom_match_align(lom_map *m, const float *src, size_t n, size_t stride, const float guess_t[3],

@@ -1990,6 +1990,14 @@ int lom_scan_align_repeat(lom_scan *s, const float *d_src, size_t n, size_t stri
 {
     return lom_match_align_repeat(reinterpret_cast<lom_map *>(s), d_src, n, stride, guess_t, guess_q, reps, out_t, out_q, total);
 }
+int lom_scan_align_batch(lom_scan *s, const lom_align_problem *p, int count, lom_align_result *out, int *best)
+{
+    return lom_match_align_batch(reinterpret_cast<lom_map *>(s), p, count, out, best);
+}
+int lom_scan_align_batch_device(lom_scan *s, const lom_align_problem *p, int count, lom_align_result *out, int *best)
+{
+    return lom_match_align_batch_device(reinterpret_cast<lom_map *>(s), p, count, out, best);
+}
 int64_t lom_scan_find_pairs(lom_scan *s, const float *src, size_t n, size_t stride, const float t[3], const float q[4],
                             float max_dist, lom_correspondence *out)
 {
@@ -2079,7 +2087,8 @@ void lom_map_destroy(lom_map *m)
     for (auto &b : m->scr)
         if (b.p) (void)hipFree(b.p);
     for (DeviceBuf *b : {&m->scan_src, &m->scan_idx, &m->scan_on, &m->scan_stats, &m->partials, &m->results, &m->gather,
-                         &m->align_state, &m->xrec, &m->dbg_trace, &m->dbg_stamps})
+                         &m->align_state, &m->xrec, &m->dbg_trace, &m->dbg_stamps, &m->batch_dev, &m->batch_rec,
+                         &m->batch_cnt, &m->batch_xrec, &m->batch_src})
         if (b->p) (void)hipFree(b->p);
     if (m->h_results) (void)hipHostFree(m->h_results);
     if (m->h_flags) (void)hipHostFree(m->h_flags);
@@ -2089,6 +2098,8 @@ void lom_map_destroy(lom_map *m)
     if (m->parent_ev) (void)hipEventDestroy(m->parent_ev);
     if (m->h_cmd) (void)hipHostFree(m->h_cmd);
     if (m->h_report) (void)hipHostFree(m->h_report);
+    if (m->h_batch) (void)hipHostFree(m->h_batch);
+    if (m->h_batch_report) (void)hipHostFree(m->h_batch_report);
     for (auto &e : m->prof_events)
         if (e) (void)hipEventDestroy(e);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
@@ -2138,6 +2149,10 @@ int lom_map_set_option(lom_map *m, int option, int64_t value)
     case LOM_OPT_TEST_GRID_GIVE_UP:
         if (value < -1 || value >= (1 << 20)) return LOM_ERR_ARG;
         m->test_grid_give_up = (int)value;
+        return LOM_OK;
+    case LOM_OPT_TEST_BATCH_ROUND_MAX:
+        if (value < 0 || value > (1 << 20)) return LOM_ERR_ARG;
+        m->test_batch_round_max = (int)value;
         return LOM_OK;
     default: return set_error(m, LOM_ERR_ARG, "unknown option");
     }
