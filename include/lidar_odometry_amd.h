@@ -285,6 +285,38 @@ int lom_match_align_batch_device(lom_map *m, const lom_align_problem *p, int cou
  * -1 if count <= 0 or r == NULL */
 int lom_align_batch_best(const lom_align_result *r, int count);
 
+/* ---- multi-map align: K (scan, guess) problems, each against a keyframe of its own, in one call -------------------- */
+/* Many independent streams on one GPU (a dataset of drives, several robots): each problem names its map, and the K solves
+ * run side by side in one device-resident chain on `runner`'s stream, as lom_match_align_batch's do.
+ * Same answers: out[i] is BIT FOR BIT what lom_match_align* (p[i].map, ...) returns for that scan and guess -- the pose
+ *   bytes and the counting fields (see lom_align_result) -- the promise lom_match_align_batch makes.
+ * Maps may repeat, and may differ in voxel size, max points per voxel, size and LOM_OPT_COUNT_CANDIDATES.  Problems are
+ *   grouped by (solve variant, counted or not); each keeps the solve grid its single align would use, and a round holds
+ *   as many as are resident together (LOM_OPT_TEST_BATCH_ROUND_MAX of the runner caps it).
+ * Arguments: LOM_ERR_ARG before any work for a NULL runner, count < 0, NULL p or out with count > 0, a NULL map, or a map
+ *   on another device than runner; count == 0 is valid (best = -1); *best_or_null is left alone on an error.
+ * Settling: every map is settled (its pending insert verified) before anything is launched; a map whose pending insert
+ *   fails fails the call first, its error in runner's lom_last_error with the problem's index.
+ * Stream order: runner's stream waits for the work already enqueued on every problem map's stream (a _nowait insert, a
+ *   cleanup); before the call returns every problem map's stream is ordered behind the chain's last launch, so that a
+ *   later insert or cleanup on a map cannot overtake the search.
+ * Problems whose map has LOM_OPT_HOST_LM or an attached exchange run through that map's own single align, one after
+ *   another (round = -1); a problem whose solve gave up is redone alone on its own map (host_fallback = 1).
+ *   LOM_OPT_TEST_GIVE_UP_AT_OUTER of a map applies to that map's first device-resident problem.
+ * Isolation as lom_match_align_batch, for every handle involved: armed radius cleanups and idle hooks stay armed, the
+ *   single align's state is not touched. */
+typedef struct {
+    lom_map *map;              /* the keyframe this problem aligns against */
+    const float *xyz;          /* host (lom_match_align_multi) or device (..._device) pointer */
+    size_t n, stride_bytes;
+    float guess_t[3], guess_q_wxyz[4];
+} lom_align_multi_problem;
+/* `runner`: the handle whose stream and batch buffers carry the chain; it may or may not be one of the problems' maps */
+int lom_match_align_multi(lom_map *runner, const lom_align_multi_problem *p, int count, lom_align_result *out,
+                          int *best_or_null);
+int lom_match_align_multi_device(lom_map *runner, const lom_align_multi_problem *p, int count, lom_align_result *out,
+                                 int *best_or_null);
+
 /* Diagnostic build of the correspondence kernel with shader-clock stamps after each phase of every
  * workgroup's first query (8 u64 per workgroup: entry, point transformed, slots probed, prefix in
  * LDS, candidates scanned, minimum known, record stored, exit).  Not a timing of the product kernel. */
@@ -659,6 +691,16 @@ int lom_odometry_process_cloud(lom_odometry *o, const lom_point_xyzirt *pts, siz
  * fails and returns its status; *done = frames processed */
 int lom_odometry_process_sequence(lom_odometry *o, const lom_point_xyzirt *const *frames, const size_t *n, size_t count,
                                   size_t *done);
+/* one frame for each of `count` distinct odometries on one device; for every i exactly what
+ * lom_odometry_process_cloud(o[i], frames[i], n[i]) would do -- poses, stats, keyframe, temp cloud -- with the
+ * aligns of all streams that have one run as one lom_match_align_multi.  status_out[i]: that stream's status;
+ * returns LOM_OK or the first failing stream's status.  A stream that fails is left as process_cloud leaves it.
+ * The stages of all streams are enqueued before any is waited for.  The batch neither runs the keyframe cleanup's scan
+ * behind the align nor sends hinted frames ahead (as with LOM_NO_CLEANUP_BEHIND_ALIGN / LOM_NO_SEND_AHEAD: the results
+ * are the same); a hint left on a handle is dropped.  LOM_ERR_ARG before any stream is touched for count < 0, a NULL
+ * array with count > 0, a NULL handle or frame, the same handle twice, or handles on different devices. */
+int lom_odometry_process_batch(lom_odometry *const *o, const lom_point_xyzirt *const *frames, const size_t *n, int count,
+                               int *status_out_or_null);
 /* A caller that already holds the frame that comes after the next lom_odometry_process_cloud (a recorded sequence; a
  * driver that buffers) says so here: while that call's align runs -- its thread would only watch the report -- the hinted
  * frame is copied into the front end's pinned staging buffer, and the process_cloud that then comes with exactly this

@@ -359,6 +359,43 @@ public:
         }
         return out;
     }
+    // K (cloud, guess) problems, problem i against *keyframes[i], in one call (lom_match_align_multi, keyframes[0] carries
+    // the device chain): the poses align(*keyframes[i], ...) would return, bit for bit; stats and best as alignBatch's
+    std::vector<Pose3D> alignMulti(const std::vector<const VoxelGrid *> &keyframes,
+                                   const std::vector<const PointCloud<PointXYZ> *> &clouds, const std::vector<Pose3D> &guesses)
+    {
+        if (clouds.size() != guesses.size() || clouds.size() != keyframes.size())
+            throw Error(LOM_ERR_ARG, "alignMulti: one keyframe and one guess per cloud");
+        std::vector<lom_align_multi_problem> p(clouds.size());
+        for (size_t i = 0; i < clouds.size(); i++) {
+            if (!clouds[i] || !keyframes[i]) throw Error(LOM_ERR_ARG, "alignMulti: null cloud or keyframe");
+            const lom_pose g = guesses[i].c();
+            p[i].map = keyframes[i]->handle();
+            p[i].xyz = clouds[i]->points.empty() ? nullptr : &clouds[i]->points.data()->x;
+            p[i].n = clouds[i]->points.size();
+            p[i].stride_bytes = sizeof(PointXYZ);
+            for (int a = 0; a < 3; a++) p[i].guess_t[a] = g.t[a];
+            for (int a = 0; a < 4; a++) p[i].guess_q_wxyz[a] = g.q[a];
+        }
+        std::vector<lom_align_result> r(p.size());
+        batch_stats.clear();
+        if (p.empty()) {
+            best = -1;
+            return {};
+        }
+        lom_map *runner = keyframes[0]->handle();
+        const int rc = lom_match_align_multi(runner, p.data(), (int)p.size(), r.data(), &best);
+        if (rc != LOM_OK) throw Error(rc, lom_last_error(runner));
+        std::vector<Pose3D> out;
+        for (const lom_align_result &x : r) {
+            lom_pose o;
+            for (int a = 0; a < 3; a++) o.t[a] = x.t[a];
+            for (int a = 0; a < 4; a++) o.q[a] = x.q_wxyz[a];
+            out.push_back(Pose3D::from(o));
+            batch_stats.push_back(x.stats);
+        }
+        return out;
+    }
     lom_align_stats last_stats{};
     std::vector<lom_align_stats> batch_stats;
     int best = -1;
@@ -509,6 +546,27 @@ public:
     {
         const int rc = lom_odometry_process_cloud(h_, input_cloud.points.data(), input_cloud.points.size());
         if (rc != LOM_OK) throw Error(rc, lom_odometry_last_error(h_));
+    }
+    // not in the reference: one frame for each of several distinct odometries on one device (lom_odometry_process_batch),
+    // for each exactly what processCloud would do; returns the per-stream statuses (LOM_OK where the stream advanced) and
+    // throws only where the call was refused before any stream moved
+    static std::vector<int> processBatch(const std::vector<LidarOdometry *> &odometries,
+                                         const std::vector<const CloudType *> &clouds)
+    {
+        if (odometries.size() != clouds.size()) throw Error(LOM_ERR_ARG, "processBatch: one cloud per odometry");
+        std::vector<lom_odometry *> h(odometries.size());
+        std::vector<const lom_point_xyzirt *> f(clouds.size());
+        std::vector<size_t> n(clouds.size());
+        for (size_t i = 0; i < clouds.size(); i++) {
+            if (!odometries[i] || !clouds[i]) throw Error(LOM_ERR_ARG, "processBatch: null odometry or cloud");
+            h[i] = odometries[i]->h_;
+            f[i] = clouds[i]->points.data();
+            n[i] = clouds[i]->points.size();
+        }
+        std::vector<int> st(h.size(), 1);  // (1: not written -- the call was refused)
+        const int rc = lom_odometry_process_batch(h.data(), f.data(), n.data(), (int)h.size(), st.data());
+        if (rc != LOM_OK && !st.empty() && st[0] == 1) throw Error(rc, "lom_odometry_process_batch");
+        return st;
     }
     // not in the reference: the cloud that will come after the next processCloud, for callers that hold it already; it must
     // stay unchanged until it has been processed (it is copied to pinned memory while that processCloud's align runs)

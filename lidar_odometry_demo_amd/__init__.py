@@ -378,6 +378,51 @@ class CloudMatcher:
             self._problem(problems[i], ptr, n, g, stride_bytes)
         return self._batch(keyframe, problems, len(items), None, True)
 
+    def _multi(self, runner, problems, count, keep, device):
+        res = (capi.AlignResult * max(count, 1))()
+        best = C.c_int(-1)
+        L = capi.lib()
+        fn = L.lom_match_align_multi_device if device else L.lom_match_align_multi
+        capi.check(fn(runner.handle, problems if count else None, count, res, C.byref(best)), runner.handle)
+        del keep
+        self.batch_stats = [dict(res[i].stats.asdict(), round=res[i].round) for i in range(count)]
+        self.best = best.value
+        return [Pose3D(np.array(res[i].t[:], np.float32), np.array(res[i].q_wxyz[:], np.float32)) for i in range(count)]
+
+    @staticmethod
+    def _multi_problems(keyframes, items):
+        problems = (capi.AlignMultiProblem * max(len(items), 1))()
+        for i, (kf, (ptr, n, g, stride_bytes)) in enumerate(zip(keyframes, items)):
+            if not isinstance(kf, VoxelGrid):
+                raise TypeError("alignMulti: every keyframe must be a VoxelGrid")
+            problems[i].map = kf.handle
+            CloudMatcher._problem(problems[i], ptr, n, g, stride_bytes)
+        return problems
+
+    def alignMulti(self, keyframes, clouds, guesses, runner=None):
+        """K (cloud, guess) problems, problem i against keyframes[i], in ONE call (lom_match_align_multi): the K solves
+        run side by side on the device.  Returns the poses align(keyframes[i], ...) would return, bit for bit; per-problem
+        stats in `batch_stats`, the best problem's index in `best`.  `runner` (a VoxelGrid, default keyframes[0]) carries
+        the device chain."""
+        if not (len(keyframes) == len(clouds) == len(guesses)):
+            raise ValueError("one keyframe and one guess per cloud")
+        arrays = [capi.xyz_array(c) for c in clouds]
+        items = [(a.ctypes.data if len(a) else None, len(a), g, 12) for a, g in zip(arrays, guesses)]
+        runner = runner if runner is not None else (keyframes[0] if keyframes else None)
+        if runner is None:
+            raise ValueError("alignMulti of no problems needs a runner")
+        return self._multi(runner, self._multi_problems(keyframes, items), len(items), arrays, False)
+
+    def alignMultiDevice(self, keyframes, items, runner=None, stride_bytes=12):
+        """alignMulti with device-resident clouds: items = [(device pointer, n, guess), ...], one per keyframe."""
+        if len(keyframes) != len(items):
+            raise ValueError("one keyframe per item")
+        runner = runner if runner is not None else (keyframes[0] if keyframes else None)
+        if runner is None:
+            raise ValueError("alignMultiDevice of no problems needs a runner")
+        full = [(ptr, n, g, stride_bytes) for ptr, n, g in items]
+        return self._multi(runner, self._multi_problems(keyframes, full), len(items), None, True)
+
     def alignDevice(self, keyframe, d_src_ptr, n, position_guess, stride_bytes=12):
         """Source cloud already resident in HBM (device pointer, e.g. torch tensor.data_ptr())."""
         ot, oq = (C.c_float * 3)(), (C.c_float * 4)()
@@ -620,6 +665,31 @@ class LidarOdometry:
         if rc != 0:
             text = capi.lib().lom_odometry_last_error(self._h)
             raise LomError(int(rc), (text.decode() if text else "") + f" (frame {done.value} of the sequence)")
+
+    @staticmethod
+    def processBatch(odometries, clouds):
+        """One frame for each of several distinct odometries on one device (lom_odometry_process_batch): for each exactly
+        what processCloud would do, with the aligns of all streams run as one call.  Raises LomError if any stream failed
+        (its `statuses` holds the per-stream codes); the other streams have still advanced."""
+        if len(odometries) != len(clouds):
+            raise ValueError("one cloud per odometry")
+        k = len(odometries)
+        arrs = [_cloud(c) for c in clouds]
+        hs = (C.c_void_p * max(k, 1))(*[o._h for o in odometries])
+        ptrs = (C.c_void_p * max(k, 1))(*[a.ctypes.data for a in arrs])
+        ns = (C.c_size_t * max(k, 1))(*[len(a) for a in arrs])
+        st = (C.c_int * max(k, 1))()
+        rc = capi.lib().lom_odometry_process_batch(hs, ptrs, ns, k, st)
+        if rc != 0:
+            codes = [int(st[i]) for i in range(k)] if rc != capi.ERR_ARG or any(st[i] for i in range(k)) else [int(rc)] * k
+            bad = [i for i, c in enumerate(codes) if c != 0]
+            texts = []
+            for i in bad:
+                t = capi.lib().lom_odometry_last_error(odometries[i]._h)
+                texts.append(f"stream {i}: {t.decode() if t else ''}")
+            err = LomError(int(rc), "; ".join(texts))
+            err.statuses = codes
+            raise err
 
     def getCurrentPose(self):                              # lidar_odometry.cpp:87-89
         p = capi.Pose()

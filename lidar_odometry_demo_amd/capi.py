@@ -62,6 +62,11 @@ class AlignProblem(C.Structure):
                 ("guess_q_wxyz", C.c_float * 4)]
 
 
+class AlignMultiProblem(C.Structure):
+    _fields_ = [("map", C.c_void_p), ("xyz", C.c_void_p), ("n", C.c_size_t), ("stride_bytes", C.c_size_t),
+                ("guess_t", C.c_float * 3), ("guess_q_wxyz", C.c_float * 4)]
+
+
 class AlignResult(C.Structure):
     _fields_ = [("t", C.c_float * 3), ("q_wxyz", C.c_float * 4), ("stats", AlignStats), ("round", C.c_int32),
                 ("pad", C.c_int32)]
@@ -139,7 +144,7 @@ EXPORTED = [
     "lom_scan_create", "lom_scan_destroy", "lom_scan_last_error", "lom_scan_set_option", "lom_scan_set_stream",
     "lom_scan_get_stream", "lom_scan_create_on_partition", "lom_scan_align", "lom_scan_align_device", "lom_scan_align_repeat", "lom_scan_find_pairs", "lom_scan_find_pairs_sq",
     "lom_match_align_batch", "lom_match_align_batch_device", "lom_scan_align_batch", "lom_scan_align_batch_device",
-    "lom_align_batch_best",
+    "lom_align_batch_best", "lom_match_align_multi", "lom_match_align_multi_device", "lom_odometry_process_batch",
 ]
 
 # lom_option / counters of include/lidar_odometry_amd.h
@@ -243,6 +248,9 @@ def lib():
     L.lom_scan_align_batch.argtypes = L.lom_match_align_batch.argtypes
     L.lom_scan_align_batch_device.argtypes = L.lom_match_align_batch.argtypes
     L.lom_align_batch_best.argtypes = [C.POINTER(AlignResult), C.c_int]
+    L.lom_match_align_multi.argtypes = [vp, C.POINTER(AlignMultiProblem), C.c_int, C.POINTER(AlignResult),
+                                        C.POINTER(C.c_int)]
+    L.lom_match_align_multi_device.argtypes = L.lom_match_align_multi.argtypes
     L.lom_match_align_repeat.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_int, fp, fp, C.POINTER(AlignStats)]
     L.lom_debug_eval_sums.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, dp, dp, dp]
     L.lom_debug_lm_trace.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_int, dp, C.POINTER(C.c_int), fp, fp,
@@ -281,6 +289,7 @@ def lib():
     L.lom_odometry_process_cloud.argtypes = [vp, vp, C.c_size_t]
     L.lom_odometry_hint_next.argtypes = [vp, vp, C.c_size_t]
     L.lom_odometry_process_sequence.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lom_odometry_process_batch.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int)]
     L.lom_odometry_get_pose.argtypes = [vp, pp]
     L.lom_odometry_get_stats.argtypes = [vp, C.POINTER(OdometryFrameStats)]
     L.lom_odometry_get_temp_cloud.argtypes = [vp, vp, C.c_size_t]

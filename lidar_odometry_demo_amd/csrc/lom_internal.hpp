@@ -240,6 +240,9 @@ struct lom_map {
     unsigned long long batch_report_seq = 0, batch_lm_seq = 0;
     uint32_t lm_batch_per_cu[4] = {0, 0, 0, 0};  // k_lm blocks per CU a batch round may count on, per variant (cached)
     int test_batch_round_max = 0;  // LOM_OPT_TEST_BATCH_ROUND_MAX: problems per round at most (0: by residency)
+    // lom_match_align_multi: recorded on this handle's stream -- as a problem map, for the runner to wait on before the
+    // chain; as the runner, after the chain, for the problem maps to wait on (created once, timing disabled)
+    hipEvent_t multi_ev = nullptr;
     uint32_t lm_max_blocks[4] = {0, 0, 0, 0};  // co-resident k_lm workgroups this device admits, per variant (occupancy query, cached)
     double last_counters[4] = {0, 0, 0, 0};  // valid, cand, occ, queries of the last k_match
 

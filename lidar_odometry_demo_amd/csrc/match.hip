@@ -230,10 +230,12 @@ struct Stamper<true> {
 };
 #define LOM_STAMP(i) stamper.mark(i)
 
-// Batched align (lom_match_align_batch): one problem of a round, read by the batch forms of k_match and k_lm from a
-// small array in HBM (blockIdx.y = the problem's place in the round).  Everything that belongs to one problem -- its
-// scan, records, search counters, solve state, exchange set and report -- hangs off its descriptor.
+// Batched align (lom_match_align_batch / _multi): one problem of a round, read by the batch forms of k_match and k_lm
+// from a small array in HBM (blockIdx.y = the problem's place in the round).  Everything that belongs to one problem --
+// the keyframe it searches, its scan, records, search counters, solve state, exchange set and report -- hangs off its
+// descriptor.
 struct BatchProblem {
+    MapView map;  // read by k_match only (k_lm sees the records)
     const char *src;
     size_t stride;
     MatchRec *rec;
@@ -242,6 +244,7 @@ struct BatchProblem {
     AlignReport *report;  // device view of pinned host memory
     void *xrec;           // this round slot's exchange sets (XWord)
     uint32_t n, match_blocks;
+    uint32_t lm_blocks;  // the solve's grid (k_lm workgroups)
     float guess_t[3], guess_q[4];
     float max_sq;
     double prior_b[3];
@@ -260,7 +263,7 @@ typedef const __attribute__((address_space(4))) BatchProblem *ConstBatch;  // re
 // LOM_OPT_COUNT_CANDIDATES asks) a neighbour voxel that the bound prunes is not even looked up: its slot is neither
 // hashed nor loaded -- the result cannot depend on whether a voxel exists whose points could not win.
 // kBatch (chained only): one launch for all problems of a batched align's round -- blockIdx.y selects the problem
-// (`batch[blockIdx.y]`: scan, records, counters, state), blockIdx.x runs over THAT problem's search grid (workgroups
+// (`batch[blockIdx.y]`: map, scan, records, counters, state), blockIdx.x runs over THAT problem's search grid (workgroups
 // beyond it leave at once); per query everything is what the single align's launch does.
 template <int G, int kU, int kMinWaves, bool kStamp = false, bool kChained = false, bool kPrev = kChained, bool kCount = true,
           bool kBatch = false>
@@ -279,6 +282,16 @@ __global__ __launch_bounds__(kMatchThreads, kMinWaves) void k_match(MapView map,
     uint32_t batch_grid = 0;  // (kBatch) this problem's search grid
     if constexpr (kBatch) {
         const ConstBatch d = (ConstBatch)(batch + blockIdx.y);
+        // (the `map` argument is unused)
+        map.table = d->map.table;
+        map.mask = d->map.mask;
+        map.shift = d->map.shift;
+        map.pts = d->map.pts;
+        map.nrm = d->map.nrm;
+        map.K = d->map.K;
+        map.voxel_size = d->map.voxel_size;
+        map.inv_voxel_size = d->map.inv_voxel_size;
+        map.prune_slack = d->map.prune_slack;
         src = d->src;
         stride = d->stride;
         n = d->n;
@@ -1031,7 +1044,9 @@ __device__ __forceinline__ double swap_add(double a, double b)
 // afterwards (no workgroup barrier behind the final sum); the caller's next __syncthreads()
 // releases s_acc / s_part for the following evaluation.
 //   s_acc: 32 doubles per wave;  s_part: kT doubles (kT = threads of the workgroup).
-template <int kT, int kBlocks>
+// kGridArg: the workgroups of the solve are `nb`, not gridDim.x (k_lm's batch form: one launch holds problems of
+// different grids, sized for the largest)
+template <int kT, int kBlocks, bool kGridArg = false>
 __device__ __forceinline__ void reduce_and_exchange(const double acc[28], double *s_acc, double *s_part,
                                                     const uint32_t *__restrict__ block_counters,
                                                     uint32_t n_match_blocks, XWord *set, uint32_t nb,
@@ -1077,7 +1092,8 @@ __device__ __forceinline__ void reduce_and_exchange(const double acc[28], double
         // wave sum is the permlane-swap / DPP fold of the residual sums (36 LDS-crossbar shuffles in round 2)
         double d0 = 0.0, d1 = 0.0, d2 = 0.0;
         if (n_match_blocks) {
-            const uint32_t chunk = (n_match_blocks + gridDim.x - 1) / gridDim.x;
+            const uint32_t grid = kGridArg ? nb : gridDim.x;
+            const uint32_t chunk = (n_match_blocks + grid - 1) / grid;
             if (chunk <= 64u) {
                 uint4 r = pre;
                 if constexpr (kT != 256) {  // (the 512-thread shapes have no registers to spare for the early load)
@@ -1385,7 +1401,8 @@ __device__ __forceinline__ void accumulate_all(const MatchRec *__restrict__ rec,
 // on the same data, with the step's code already in the instruction cache.
 // kBatch: one launch for all problems of a batched align's round (single GPU, no exchange, no debug outputs) --
 // blockIdx.y selects the problem (`batch[blockIdx.y]`: records, n, guess, state, k_match's counters, exchange set,
-// report), gridDim.x is the single align's grid for that problem; a give-up test applies to problem 0 of the launch.
+// report, solve grid): the problem's solve runs on the single align's grid for it (`lm_blocks` workgroups; those beyond
+// it in a launch sized for the round's largest leave at once); a give-up test applies to problem 0 of the launch.
 template <int kT, int kBlocks = (int)kMaxLmBlocks, int kRegPts = 1, bool kPolicyTwice = false, bool kBatch = false>
 __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uint32_t n, AlignState *state,
                                                      LmInit init, int first_outer,
@@ -1409,6 +1426,7 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
         xrec = reinterpret_cast<XWord *>(d->xrec);
         report = d->report;
         if (blockIdx.y != 0) test_give_up = 0;
+        if (blockIdx.x >= d->lm_blocks) return;  // (uniform: before any barrier)
     }
     __shared__ double s_acc[(kT / 64) * 32];  // the waves' totals of one evaluation
     __shared__ double s_tot[kRecWords];
@@ -1421,7 +1439,7 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
     LmShared r_lm;
     __shared__ int s_action, s_failed;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t nb = gridDim.x;
+    const uint32_t nb = kBatch ? ((ConstBatch)(batch + blockIdx.y))->lm_blocks : gridDim.x;
     const uint32_t first = blockIdx.x * blockDim.x + tid, step = nb * blockDim.x;
     // start-up loads issued together (one memory round trip, not three): this lane's first point --
     // it stays in registers for every evaluation of the solve --, the pose, the chain's stop flags
@@ -1530,7 +1548,7 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
         LM_STAMP(1);
         seq++;
         XWord *set = xrec + (size_t)(seq & 1) * kMaxLmBlocksBig * kRecWords;
-        reduce_and_exchange<kT, kBlocks>(acc, s_acc, s_part, block_counters, counters_from, set, nb, seq, timeout_ticks,
+        reduce_and_exchange<kT, kBlocks, kBatch>(acc, s_acc, s_part, block_counters, counters_from, set, nb, seq, timeout_ticks,
                             s_tot, &s_failed, &state->error, cnt_pre,
                             (dbg_stamps && first_outer && ev == 1) ? dbg_stamps + 32 : nullptr);
         counters_from = 0;
@@ -2406,28 +2424,36 @@ static int stage_scan(lom_map *m, const float *src, size_t n, size_t stride, con
 }
 
 // ---------------------------------------------------------------------------
-// Batched align (lom_match_align_batch): K (scan, guess) problems against one keyframe, the K solves side by side in
-// ONE device-resident chain -- per outer iteration one k_match launch and one k_lm launch for all problems of a round.
+// Batched align (lom_match_align_batch / lom_match_align_multi): K (scan, guess) problems, each against a keyframe of its
+// own (the batch: all against one), the K solves side by side in ONE device-resident chain on the RUNNER's stream -- per
+// outer iteration one k_match launch and one k_lm launch for all problems of a round.  A problem's descriptor carries
+// its keyframe's MapView; k_match reads it from there (k_lm reads records only).
 //
 // Grouping.  A problem runs with the k_lm variant (lm_shape) and grid (nb) the single align would give it on this handle,
 //   so the workgroup -> point assignment and every reduction order are the single align's: bit-equal results.  Problems
-//   are grouped by (variant, nb) in order of first appearance; a group runs as one or more rounds.
+//   are grouped by (variant, counted, temporal bound) -- the last two are template parameters of k_match and come from
+//   the problem's map -- in order of first appearance; a group runs as one or more rounds.  Grids may differ within a
+//   round: the launch is sized for the largest, and a problem's descriptor names its own (streams of similar clouds
+//   differ by a workgroup or two; one round per grid made K streams K rounds).
 // Rounds.  k_lm's workgroups wait for each other, so a round's whole grid must be resident at once: problems per round =
-//   floor(CUs x blocks per CU / nb), CUs of the context's partition where it has one.  Blocks per CU: the occupancy query
+//   floor(CUs x blocks per CU / the group's largest nb), CUs of the context's partition where it has one.  Blocks per CU: the occupancy query
 //   for the batch kernel, capped at 2 (the query over-reports only where SGPRs bind, from 7 blocks of 256 threads per CU
 //   up -- MI355X "Residency and cooperative launch" -- far above the cap).  LOM_OPT_TEST_BATCH_ROUND_MAX caps it further.
 // Chain.  kPairsAhead pairs go out at once, then one pair per round of reports while any problem of the round is
 //   unfinished (a finished problem's later launches return at once, as the single align's do), at most 35.
-// Give-up.  A problem whose k_lm gave up (its error word) is redone alone through the single align; the others keep
-//   their device results.
+// Give-up.  A problem whose k_lm gave up (its error word) is redone alone through the single align on its own map; the
+//   others keep their device results.  LOM_OPT_TEST_GIVE_UP_AT_OUTER (one shot per map) goes to the map's first problem,
+//   which opens a round of its group: the kernel applies the test to problem 0 of a launch.
 // Isolation.  Own states, records, counters, exchange sets and reports: the single align's align_state, scan_on, xrec
 //   and report, and the radius cleanup's scratch, are not touched.
 // ---------------------------------------------------------------------------
 struct BatchItem {
+    lom_map *map;  // the keyframe it searches
     const char *src;
     size_t stride;
     uint32_t n;
     float gt[3], gq[4];
+    int give_up_outer;  // LOM_OPT_TEST_GIVE_UP_AT_OUTER taken from its map (-1: none)
 };
 
 static const void *lm_batch_kernel(LmShape shape)
@@ -2511,12 +2537,17 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
                          limit);
         mb[i] = n ? match_grid(n, part) : 0u;
     }
-    // groups by (variant, nb) in order of first appearance, cut into rounds; `order` lists the problems round by round
+    // groups by (variant, counted, temporal) in order of first appearance, cut into rounds; `order` lists the problems round
+    // by round
     struct Round {
         int first, size;  // range of `order`
         LmShape shape;
-        uint32_t nb;
+        uint32_t nb;  // the largest solve grid of its problems: the launch's x dimension
+        bool counted, temporal;
+        int give_up_outer;  // of its problem 0
     };
+    auto counted = [&](int i) { return it[i].map->opt_count; };
+    auto temporal = [&](int i) { return !it[i].map->opt_no_temporal; };
     std::vector<int> order;
     std::vector<Round> rounds;
     {
@@ -2528,18 +2559,27 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
             if (taken[i]) continue;
             uint32_t per_cu = 0;
             if ((rc = lm_batch_per_cu(m, shape[i], &per_cu)) != LOM_OK) return rc;
-            int per_round = (int)std::max(1u, cus * per_cu / nb[i]);
-            if (m->test_batch_round_max > 0) per_round = std::min(per_round, m->test_batch_round_max);
             std::vector<int> members;
+            uint32_t nb_max = 0;
             for (int k = i; k < count; k++)
-                if (!taken[k] && shape[k] == shape[i] && nb[k] == nb[i]) {
+                if (!taken[k] && shape[k] == shape[i] && counted(k) == counted(i) && temporal(k) == temporal(i)) {
                     taken[k] = 1;
                     members.push_back(k);
+                    nb_max = std::max(nb_max, nb[k]);
                 }
-            for (size_t a = 0; a < members.size(); a += (size_t)per_round) {
-                const int size = (int)std::min(members.size() - a, (size_t)per_round);
-                rounds.push_back(Round{(int)order.size(), size, shape[i], nb[i]});
-                for (int k = 0; k < size; k++) order.push_back(members[a + (size_t)k]);
+            // (a round's launch is sized for its largest grid: residency is counted with the group's largest)
+            int per_round = (int)std::max(1u, cus * per_cu / nb_max);
+            if (m->test_batch_round_max > 0) per_round = std::min(per_round, m->test_batch_round_max);
+            // a problem that carries a give-up test opens a round (the kernel applies it to problem 0 of a launch)
+            for (size_t a = 0; a < members.size();) {
+                size_t size = 1;
+                while (a + size < members.size() && size < (size_t)per_round && it[members[a + size]].give_up_outer < 0) size++;
+                uint32_t grid = 0;
+                for (size_t k = 0; k < size; k++) grid = std::max(grid, nb[members[a + k]]);
+                rounds.push_back(Round{(int)order.size(), (int)size, shape[i], grid, counted(i), temporal(i),
+                                       it[members[a]].give_up_outer});
+                for (size_t k = 0; k < size; k++) order.push_back(members[a + k]);
+                a += size;
             }
         }
     }
@@ -2604,6 +2644,7 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
             for (int a = 0; a < 4; a++) st.pose_q[a] = it[i].gq[a];
             BatchProblem &d = h_desc[j];
             std::memset(&d, 0, sizeof d);
+            d.map = view_of(it[i].map);
             d.src = it[i].src;
             d.stride = it[i].stride;
             d.rec = reinterpret_cast<MatchRec *>((char *)m->batch_rec.p + off_rec[i]);
@@ -2613,6 +2654,7 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
             d.xrec = (char *)m->batch_xrec.p + (size_t)k * xset_bytes;
             d.n = it[i].n;
             d.match_blocks = mb[i];
+            d.lm_blocks = nb[i];
             for (int a = 0; a < 3; a++) d.guess_t[a] = it[i].gt[a];
             for (int a = 0; a < 4; a++) d.guess_q[a] = it[i].gq[a];
             d.max_sq = 0.3f * 0.3f;                                              // :139, voxel_grid.h:215
@@ -2621,9 +2663,6 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
             rp->error = 0;
         }
     LOM_HIP(m, hipMemcpyAsync(m->batch_dev.p, m->h_batch, dev_bytes, hipMemcpyHostToDevice, m->stream));
-    const int give_up_outer = m->test_give_up_outer;  // one shot: the first problem of the first round
-    m->test_give_up_outer = -1;
-    const bool count_mode = m->opt_count;
     P2pArgs px = p2p_args(m);
     for (size_t ri = 0; ri < rounds.size(); ri++) {
         const Round &R = rounds[ri];
@@ -2637,11 +2676,12 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
             const int i = launched;
             const double t_l = now_s();
             if (mb_max) {
-                const bool prev = i > 0 && !m->opt_no_temporal;  // (the first search of a scan: no previous records)
+                const bool prev = i > 0 && R.temporal;  // (the first search of a scan: no previous records)
+                const bool count_mode = R.counted;
                 PoseArgs P;
                 std::memset(&P, 0, sizeof P);
                 auto launch = [&](auto kernel) {
-                    hipLaunchKernelGGL(kernel, dim3(mb_max, R.size), dim3(kMatchThreads), 0, m->stream, view_of(m),
+                    hipLaunchKernelGGL(kernel, dim3(mb_max, R.size), dim3(kMatchThreads), 0, m->stream, MapView{},
                                        (const char *)nullptr, (size_t)0, 0u, P, (int32_t *)nullptr, (MatchRec *)nullptr,
                                        (QStat *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr,
                                        (const AlignState *)nullptr, desc);
@@ -2656,7 +2696,7 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
             m->batch_lm_seq += 8;  // a solve spends at most 5 evaluations
             LmInit init;
             std::memset(&init, 0, sizeof init);
-            const int give_up = (ri == 0 && i == give_up_outer) ? 1 : 0;
+            const int give_up = i == R.give_up_outer ? 1 : 0;
             auto launch = [&](auto kernel) {
                 hipLaunchKernelGGL(kernel, dim3(R.nb, R.size), dim3(threads), 0, m->stream, (const MatchRec *)nullptr, 0u,
                                    (AlignState *)nullptr, init, i == 0 ? 1 : 0, (const uint32_t *)nullptr, 0u,
@@ -2709,7 +2749,7 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
                     any_gave_up = true;
                     done[k] = 1;
                 } else if (rp->finished) {
-                    result_from_report(rp, count_mode, R.nb, out[i]);
+                    result_from_report(rp, R.counted, nb[i], out[i]);
                     out[i].round = (int32_t)ri;
                     done[k] = 1;
                 } else {
@@ -2726,88 +2766,159 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
     return LOM_OK;
 }
 
-static int align_batch(lom_map *m, const lom_align_problem *p, int count, lom_align_result *out, int *best, bool device_input)
+// The problems of one call, whichever entry point: `runner` carries the chain (stream, batch buffers), it[i].map is the
+// keyframe problem i searches.  Arguments are checked by the caller.
+static int align_multi(lom_map *m, BatchItem *it, int count, lom_align_result *out, int *best, bool device_input)
 {
     if (count == 0) {
         if (best) *best = -1;
         return LOM_OK;
     }
     for (int i = 0; i < count; i++)
-        if ((p[i].n && !p[i].xyz) || p[i].stride_bytes < 12 || (p[i].stride_bytes & 3) || p[i].n >= 0x7FFFFFFFull)
+        if ((it[i].n && !it[i].src) || it[i].stride < 12 || (it[i].stride & 3) || it[i].n >= 0x7FFFFFFFull)
             return LOM_ERR_ARG;
     LOM_HIP(m, hipSetDevice(m->device));
     m->last_error.clear();
     double launch_s = 0.0, wait_s = 0.0;
-    int rc = resolve_pending(m);
-    if (rc != LOM_OK) return rc;
-    std::vector<BatchItem> it((size_t)count);
-    for (int i = 0; i < count; i++) {
-        it[i].src = (const char *)p[i].xyz;
-        it[i].stride = p[i].stride_bytes;
-        it[i].n = (uint32_t)p[i].n;
-        for (int a = 0; a < 3; a++) it[i].gt[a] = p[i].guess_t[a];
-        for (int a = 0; a < 4; a++) it[i].gq[a] = p[i].guess_q_wxyz[a];
+    // the handles involved, runner first, each once
+    std::vector<lom_map *> maps{m};
+    for (int i = 0; i < count; i++)
+        if (std::find(maps.begin(), maps.end(), it[i].map) == maps.end()) maps.push_back(it[i].map);
+    auto problem_error = [&](int i, int rc) {
+        lom_map *pm = it[i].map;
+        if (pm == m) return rc;
+        const std::string why = "problem " + std::to_string(i) + ": " + pm->last_error;
+        return set_error(m, rc, why.c_str());
+    };
+    // every map settled before anything is launched (an insert nobody has looked at yet: the search must see its points)
+    for (size_t k = 0; k < maps.size(); k++) {
+        lom_map *pm = maps[k];
+        const bool searched = k > 0 || std::any_of(it, it + count, [&](const BatchItem &b) { return b.map == m; });
+        if (!searched) continue;
+        const int rcp = resolve_pending(pm);
+        if (rcp != LOM_OK) {
+            for (int i = 0; i < count; i++)
+                if (it[i].map == pm) return problem_error(i, rcp);
+        }
     }
+    // stream order in: what is enqueued on a problem map's stream (a _nowait insert, a cleanup) comes first
+    for (size_t k = 1; k < maps.size(); k++) {
+        lom_map *pm = maps[k];
+        if (pm->stream == m->stream) continue;
+        if (!pm->multi_ev) LOM_HIP(m, hipEventCreateWithFlags(&pm->multi_ev, hipEventDisableTiming));
+        LOM_HIP(m, hipEventRecord(pm->multi_ev, pm->stream));
+        LOM_HIP(m, hipStreamWaitEvent(m->stream, pm->multi_ev, 0));
+    }
+    int rc;
     if (!device_input) {
         // host scans staged into one device buffer up front (a cloud shared by several problems once)
         std::vector<size_t> off((size_t)count, 0);
+        std::vector<char> first((size_t)count, 1);
         size_t total = 0;
         for (int i = 0; i < count; i++) {
             int same = -1;
             for (int k = 0; k < i && same < 0; k++)
-                if (p[k].xyz == p[i].xyz && p[k].n == p[i].n && p[k].stride_bytes == p[i].stride_bytes) same = k;
+                if (it[k].src == it[i].src && it[k].n == it[i].n && it[k].stride == it[i].stride) same = k;
             if (same >= 0) {
                 off[i] = off[same];
+                first[i] = 0;
                 continue;
             }
             off[i] = total;
-            if (p[i].n) total += round_up256((p[i].n - 1) * p[i].stride_bytes + 12);
+            if (it[i].n) total += round_up256((it[i].n - 1) * it[i].stride + 12);
         }
         if ((rc = ensure(m, m->batch_src, std::max<size_t>(total, 256))) != LOM_OK) return rc;
         const double t_l = now_s();
         for (int i = 0; i < count; i++) {
-            bool first = true;
-            for (int k = 0; k < i && first; k++)
-                if (p[k].xyz == p[i].xyz && p[k].n == p[i].n && p[k].stride_bytes == p[i].stride_bytes) first = false;
+            const char *host = it[i].src;
             it[i].src = (const char *)m->batch_src.p + off[i];
-            if (first && p[i].n)
-                LOM_HIP(m, hipMemcpyAsync((char *)m->batch_src.p + off[i], p[i].xyz, (p[i].n - 1) * p[i].stride_bytes + 12,
+            if (first[i] && it[i].n)
+                LOM_HIP(m, hipMemcpyAsync((char *)m->batch_src.p + off[i], host, (it[i].n - 1) * it[i].stride + 12,
                                           hipMemcpyHostToDevice, m->stream));
         }
         launch_s += now_s() - t_l;
     }
-    // the single align's one-shot arms (a radius cleanup behind the next align, an idle hook) are the NEXT single align's:
-    // nothing below takes or runs them
-    const float spec = m->spec_radius;
-    void (*hook)(void *) = m->idle_hook;
-    void *hook_user = m->idle_user;
-    m->spec_radius = 0.f;
-    m->idle_hook = nullptr;
-    std::vector<char> redo((size_t)count, 0);
-    const bool chained = !m->comm && !m->host_comm && !m->opt_host_lm;
-    if (chained) {
-        server_stop(m);
-        rc = align_batch_chained(m, it.data(), count, out, redo, launch_s, wait_s);
-    } else {
-        // LOM_OPT_HOST_LM / an attached exchange: the single align's host-driven loop, problem by problem
-        std::fill(redo.begin(), redo.end(), 1);
+    // the single align's one-shot arms (a radius cleanup behind the next align, an idle hook) are the NEXT single align's,
+    // on every handle involved: nothing below takes or runs them
+    struct Arms {
+        float spec;
+        void (*hook)(void *);
+        void *user;
+    };
+    std::vector<Arms> arms(maps.size());
+    for (size_t k = 0; k < maps.size(); k++) {
+        arms[k] = Arms{maps[k]->spec_radius, maps[k]->idle_hook, maps[k]->idle_user};
+        maps[k]->spec_radius = 0.f;
+        maps[k]->idle_hook = nullptr;
     }
+    // device-resident chain: problems whose map is a plain single-GPU one (no LOM_OPT_HOST_LM, no exchange), on a runner
+    // without an exchange; the others go through their map's own single align, one after another
+    const bool runner_plain = !m->comm && !m->host_comm;
+    std::vector<char> redo((size_t)count, 0), chained((size_t)count, 0);
+    std::vector<int> idx;
+    for (int i = 0; i < count; i++) {
+        lom_map *pm = it[i].map;
+        chained[i] = runner_plain && !pm->comm && !pm->host_comm && !pm->opt_host_lm;
+        it[i].give_up_outer = -1;
+        if (!chained[i]) {
+            redo[i] = 1;
+            continue;
+        }
+        if (pm->test_give_up_outer >= 0) {  // one shot: this map's first problem
+            it[i].give_up_outer = pm->test_give_up_outer;
+            pm->test_give_up_outer = -1;
+        }
+        idx.push_back(i);
+    }
+    rc = LOM_OK;
+    if (!idx.empty()) {
+        for (lom_map *pm : maps) server_stop(pm);
+        std::vector<BatchItem> sub(idx.size());
+        std::vector<lom_align_result> res(idx.size());
+        std::vector<char> gave(idx.size(), 0);
+        for (size_t k = 0; k < idx.size(); k++) sub[k] = it[idx[k]];
+        rc = align_batch_chained(m, sub.data(), (int)sub.size(), res.data(), gave, launch_s, wait_s);
+        for (size_t k = 0; rc == LOM_OK && k < idx.size(); k++) {
+            out[idx[k]] = res[k];
+            redo[idx[k]] = gave[k];
+        }
+    }
+    // the redos and host-driven problems run on their maps' streams: the staged scans and the chain come first
+    bool ordered = false;
     for (int i = 0; rc == LOM_OK && i < count; i++) {
         if (!redo[i]) continue;
-        m->last_error.clear();
-        if (!chained) out[i].round = -1;
-        rc = align_device_paths(m, it[i].src, it[i].n, it[i].stride, it[i].gt, it[i].gq, out[i].t, out[i].q_wxyz,
+        lom_map *pm = it[i].map;
+        if (pm->stream != m->stream && !ordered) {
+            LOM_HIP(m, hipStreamSynchronize(m->stream));
+            ordered = true;
+        }
+        pm->last_error.clear();
+        if (!chained[i]) out[i].round = -1;
+        rc = align_device_paths(pm, it[i].src, it[i].n, it[i].stride, it[i].gt, it[i].gq, out[i].t, out[i].q_wxyz,
                                 &out[i].stats);
-        m->spec_radius = 0.f;
-        m->idle_hook = nullptr;
-        if (rc != LOM_OK) break;
-        if (chained) out[i].stats.host_fallback = 1;
+        pm->spec_radius = 0.f;
+        pm->idle_hook = nullptr;
+        if (rc != LOM_OK) {
+            rc = problem_error(i, rc);
+            break;
+        }
+        if (chained[i]) out[i].stats.host_fallback = 1;
         launch_s += out[i].stats.host_launch_ms * 1e-3;
         wait_s += out[i].stats.host_wait_ms * 1e-3;
     }
-    m->spec_radius = spec;
-    m->idle_hook = hook;
-    m->idle_user = hook_user;
+    for (size_t k = 0; k < maps.size(); k++) {
+        maps[k]->spec_radius = arms[k].spec;
+        maps[k]->idle_hook = arms[k].hook;
+        maps[k]->idle_user = arms[k].user;
+    }
+    // stream order out: the chain's trailing launches (finished problems' launches may still be queued) come before
+    // whatever is enqueued next on a problem map -- an insert, a cleanup
+    if (maps.size() > 1) {
+        if (!m->multi_ev) LOM_HIP(m, hipEventCreateWithFlags(&m->multi_ev, hipEventDisableTiming));
+        LOM_HIP(m, hipEventRecord(m->multi_ev, m->stream));
+        for (size_t k = 1; k < maps.size(); k++)
+            if (maps[k]->stream != m->stream) LOM_HIP(m, hipStreamWaitEvent(maps[k]->stream, m->multi_ev, 0));
+    }
     if (rc != LOM_OK) return rc;
     for (int i = 0; i < count; i++) {
         lom_align_stats &st = out[i].stats;
@@ -2820,6 +2931,38 @@ static int align_batch(lom_map *m, const lom_align_problem *p, int count, lom_al
     }
     if (best) *best = lom_align_batch_best(out, count);
     return LOM_OK;
+}
+
+static int align_batch(lom_map *m, const lom_align_problem *p, int count, lom_align_result *out, int *best, bool device_input)
+{
+    std::vector<BatchItem> it((size_t)std::max(count, 0));
+    for (int i = 0; i < count; i++) {
+        it[i].map = m;
+        it[i].src = (const char *)p[i].xyz;
+        it[i].stride = p[i].stride_bytes;
+        it[i].n = p[i].n >= 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)p[i].n;
+        for (int a = 0; a < 3; a++) it[i].gt[a] = p[i].guess_t[a];
+        for (int a = 0; a < 4; a++) it[i].gq[a] = p[i].guess_q_wxyz[a];
+    }
+    return align_multi(m, it.data(), count, out, best, device_input);
+}
+
+static int align_multi_entry(lom_map *m, const lom_align_multi_problem *p, int count, lom_align_result *out, int *best,
+                             bool device_input)
+{
+    if (!m || count < 0 || (count > 0 && (!p || !out))) return LOM_ERR_ARG;
+    for (int i = 0; i < count; i++)
+        if (!p[i].map || p[i].map->device != m->device) return LOM_ERR_ARG;  // (handle fields only: no device call)
+    std::vector<BatchItem> it((size_t)count);
+    for (int i = 0; i < count; i++) {
+        it[i].map = p[i].map;
+        it[i].src = (const char *)p[i].xyz;
+        it[i].stride = p[i].stride_bytes;
+        it[i].n = p[i].n >= 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)p[i].n;
+        for (int a = 0; a < 3; a++) it[i].gt[a] = p[i].guess_t[a];
+        for (int a = 0; a < 4; a++) it[i].gq[a] = p[i].guess_q_wxyz[a];
+    }
+    return align_multi(m, it.data(), count, out, best, device_input);
 }
 
 }  // namespace lom
@@ -3249,6 +3392,17 @@ int lom_match_align_batch_device(lom_map *m, const lom_align_problem *p, int cou
 {
     if (!m || count < 0 || (count > 0 && (!p || !out))) return LOM_ERR_ARG;
     return align_batch(m, p, count, out, best, true);
+}
+
+int lom_match_align_multi(lom_map *runner, const lom_align_multi_problem *p, int count, lom_align_result *out, int *best)
+{
+    return align_multi_entry(runner, p, count, out, best, false);
+}
+
+int lom_match_align_multi_device(lom_map *runner, const lom_align_multi_problem *p, int count, lom_align_result *out,
+                                 int *best)
+{
+    return align_multi_entry(runner, p, count, out, best, true);
 }
 
 int lom_match_align(lom_map *m, const float *src, size_t n, size_t stride, const float guess_t[3],

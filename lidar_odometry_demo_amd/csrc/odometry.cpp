@@ -511,6 +511,7 @@ private:
 
 struct lom_odometry {
     lom_odometry_params cfg;
+    int device = 0;
     lom_map *keyframe = nullptr;       // keyframe_           lidar_odometry.h:82
     // keyframe_downsampler lidar_odometry.cpp:37: two workspaces, alternating per frame -- its output feeds the
     // keyframe update of the frame, which runs on the keyframe's stream beside the NEXT frame's stages
@@ -601,6 +602,7 @@ int lom_odometry_create(const lom_odometry_params *params, int device, lom_odome
     lom_odometry *o = new (std::nothrow) lom_odometry();
     if (!o) return LOM_ERR_OOM;
     o->cfg = *params;
+    o->device = device;
     o->debug_timing = getenv("LOM_DEBUG_TIMING") != nullptr;
     o->no_cleanup_behind_align = getenv("LOM_NO_CLEANUP_BEHIND_ALIGN") != nullptr;
     o->no_send_ahead = getenv("LOM_NO_SEND_AHEAD") != nullptr;
@@ -812,11 +814,22 @@ int stages_on_host(lom_odometry *o, const lom_point_xyzirt *pts, size_t n, const
     return LOM_OK;
 }
 
+// what the enqueue half of the device stages hands to the finish half
+struct DeviceStages {
+    lom_map *reader = nullptr;  // the workspace whose read-back the finish half waits for
+    bool has_keyframe = false;
+    uint32_t seq_u = 0, seq_m = 0;
+    const float *d_fx = nullptr, *d_fn = nullptr;
+};
+
 // :25-47 on the device: the frame stays in HBM from its upload to its pose.  Front end (4 kernels), both
 // down-samplers (2 kernels each) fed with device-side counts, then ONE look at the host for the sizes the
-// align and the keyframe update are launched with.  Returns 1 when the front end hands the frame back.
-int stages_on_device(lom_odometry *o, const lom_point_xyzirt *pts, size_t n, const lom_pose &rel_inv, const lom_pose &ident,
-                     lom_odometry_frame_stats &cur, FrameInputs &in, StageTimer &tm)
+// align and the keyframe update are launched with.  Two halves around that look: stages_device_enqueue puts everything
+// on the streams and the read-back behind it, stages_device_finish waits for it, settles the previous frame's keyframe
+// update and takes the verdicts (lom_odometry_process_batch enqueues the stages of all its streams before it finishes
+// any).  Both return 1 when the front end hands the frame back.
+int stages_device_enqueue(lom_odometry *o, const lom_point_xyzirt *pts, size_t n, const lom_pose &rel_inv,
+                          const lom_pose &ident, FrameInputs &in, StageTimer &tm, DeviceStages &ds)
 {
     int rc;
     // front end and down-samplers take frames of up to ~170k points (their in-kernel scans cover 262144 cells /
@@ -856,7 +869,7 @@ int stages_on_device(lom_odometry *o, const lom_point_xyzirt *pts, size_t n, con
     // align; the keyframe-update cloud is enqueued behind the read-back the align waits for, runs beside the
     // align's first kernels, and its count and verdict are collected after the align (pending_update).
     const uint32_t *ptrs[12];
-    uint32_t seq_u = 0, seq_m = 0, got[12] = {0};
+    uint32_t seq_u = 0, seq_m = 0;
     const uint32_t *u_range = nullptr, *u_grid = nullptr, *m_range = nullptr, *m_grid = nullptr;
     int k = 0;
     ptrs[k++] = d_fe;      // 0 planar
@@ -894,6 +907,22 @@ int stages_on_device(lom_odometry *o, const lom_point_xyzirt *pts, size_t n, con
         ptrs[k++] = u_grid;   // 6
         if ((rc = lom_map_read_device_words_begin(reader, ptrs, k)) != LOM_OK) return fail_map(o, rc, reader);
     }
+    ds.reader = reader;
+    ds.has_keyframe = has_keyframe;
+    ds.seq_u = seq_u;
+    ds.seq_m = seq_m;
+    ds.d_fx = d_fx;
+    ds.d_fn = d_fn;
+    return LOM_OK;
+}
+
+int stages_device_finish(lom_odometry *o, lom_odometry_frame_stats &cur, FrameInputs &in, StageTimer &tm,
+                         const DeviceStages &ds)
+{
+    int rc;
+    lom_map *reader = ds.reader;
+    const bool has_keyframe = ds.has_keyframe;
+    uint32_t got[12] = {0};
     // the one wait before the align: counts and verdicts of what it needs
     if ((rc = lom_map_read_device_words_end(reader, got)) != LOM_OK) return fail_map(o, rc, reader);
     tm.lap("stages (device)");
@@ -905,7 +934,7 @@ int stages_on_device(lom_odometry *o, const lom_point_xyzirt *pts, size_t n, con
     }
     tm.lap("settle");
     const uint32_t fe_seq = lom_frontend_sequence(o->frontend);
-    const uint32_t seq_ds = has_keyframe ? seq_m : seq_u;
+    const uint32_t seq_ds = has_keyframe ? ds.seq_m : ds.seq_u;
     // An azimuth on a bin boundary, an organised cloud beyond the buffers -- or an in-kernel scan of the front end
     // or of the down-sampler that gave up waiting: such a grid has written nothing and left its tables at rest
     // (grid_scan.hpp), so the frame simply takes the host stages, whose kernels wait for nobody.
@@ -922,8 +951,8 @@ int stages_on_device(lom_odometry *o, const lom_point_xyzirt *pts, size_t n, con
     }
     cur.planar_points = got[0];
     cur.filtered_points = got[1];
-    in.d_fx = d_fx;
-    in.d_fn = d_fn;
+    in.d_fx = ds.d_fx;
+    in.d_fn = ds.d_fn;
     in.nf = got[1];
     if (has_keyframe) {
         in.nm = got[4];
@@ -974,6 +1003,171 @@ void send_next_frame_ahead(void *user)
     o->ahead_stage = stage;
 }
 
+// ---- processCloud in phases: lom_odometry_process_cloud runs them back to back, lom_odometry_process_batch runs each
+// phase for all its streams, with ONE align (lom_match_align_multi) for all streams that align
+struct Frame {
+    lom_odometry_frame_stats cur{};  // becomes o->last when the frame is through
+    StageTimer tm;
+    lom_pose relative, rel_inv, ident, guess, previous_next;
+    FrameInputs in;
+    DeviceStages ds;
+    int enq = 1;  // stages_device_enqueue's status (1: host stages)
+    explicit Frame(bool timing) : tm(timing) {}
+};
+
+// a hint is for the call that follows it, what was sent ahead for the call after that: neither outlives its call
+struct DropHints {
+    lom_odometry *o = nullptr;
+    const lom_point_xyzirt *sent_before = nullptr;
+    void arm(lom_odometry *od)
+    {
+        o = od;
+        o->hint_now = o->hint_pts;
+        o->hint_pts = nullptr;
+        sent_before = o->ahead_pts;
+    }
+    ~DropHints()
+    {
+        if (!o) return;
+        o->hint_now = nullptr;
+        if (o->ahead_pts == sent_before) o->ahead_pts = nullptr;  // (this call did not use it: the front end drops it)
+    }
+};
+
+constexpr int kFrameDone = 2;  // frame_stages: the frame initialised the keyframe, there is no align
+
+// :27-28 and the device stages' enqueue half
+void frame_enqueue(lom_odometry *o, Frame &f, const lom_point_xyzirt *pts, size_t n)
+{
+    lom_pose_relative_to(&o->previous, &o->current, &f.relative);  // :27
+    // :28 previous_transform_ = current_transform_ -- committed where the frame succeeds (the
+    // reference has no error channel; here a frame that fails must leave the state as it found it,
+    // or the next frame's constant-velocity guess and deskew would start from a zero motion)
+    f.previous_next = o->current;
+    lom::pose_inverse(f.relative, f.rel_inv);
+    lom_pose_identity(&f.ident);
+    o->parity ^= 1;
+    o->update_ds = o->update_ds2[o->parity];
+    f.enq = o->frontend ? stages_device_enqueue(o, pts, n, f.rel_inv, f.ident, f.in, f.tm, f.ds) : 1;
+}
+
+// the stages' finish (or the host stages), then :40-44 or :51: LOM_OK = the frame aligns next (f.guess, f.in.d_match),
+// kFrameDone = it initialised the keyframe, else the frame's failure
+int frame_stages(lom_odometry *o, Frame &f, const lom_point_xyzirt *pts, size_t n)
+{
+    int rc = f.enq;
+    if (rc == LOM_OK) rc = stages_device_finish(o, f.cur, f.in, f.tm, f.ds);
+    if (rc == 1) {
+        f.in = FrameInputs();
+        rc = stages_on_host(o, pts, n, f.rel_inv, f.ident, f.cur, f.in, f.tm);
+        f.cur.host_stages = 1;
+    }
+    if (rc != LOM_OK) return rc;
+    // :40 keyframe_.size() == 0 -- known on the host: the keyframe is empty until a frame has put voxels
+    // into it (nd > 0 points always create at least one), and stays non-empty unless a cleanup empties it
+    if (!o->keyframe_has_voxels) {  // :40-44 init keyframe
+        {   // the stages ran on a stale "has voxels" (the previous update emptied the keyframe meanwhile): the
+            // update cloud's count is still on its way
+            const char *why = nullptr;
+            const int rcu = collect_or_redo_update(o, f.in, &why);
+            if (rcu != LOM_OK) {
+                o->error = why ? why : "keyframe-update down-sampling failed";
+                return rcu;
+            }
+        }
+        if ((rc = lom_map_add_points_device(o->keyframe, f.in.d_down, f.in.d_down_n, (size_t)f.in.nd, 12)) != LOM_OK)
+            return fail_map(o, rc, o->keyframe);
+        f.cur.initialised_keyframe = 1;
+        f.cur.update_points = f.in.nd;
+        f.cur.keyframe_voxels = lom_map_size(o->keyframe);
+        o->keyframe_has_voxels = f.cur.keyframe_voxels > 0;
+        o->last = f.cur;
+        o->previous = f.previous_next;  // :28
+        return kFrameDone;
+    }
+    f.cur.matching_points = f.in.nm;
+    lom_pose_compose(&o->current, &f.relative, &f.guess);  // :51
+    return LOM_OK;
+}
+
+// after the align (:49-51): the update cloud's verdict, :53-63, :65 and the keyframe update (:67-70)
+int frame_commit(lom_odometry *o, Frame &f, const lom_align_stats &ast, lom_pose result)
+{
+    lom_odometry_frame_stats &cur = f.cur;
+    FrameInputs &in = f.in;
+    StageTimer &tm = f.tm;
+    int rc;
+    {   // the update cloud was down-sampled beside the align: its size and verdict (long since on the host)
+        const char *why = nullptr;
+        const int rcu = collect_or_redo_update(o, in, &why);
+        if (rcu != LOM_OK) {
+            o->error = why ? why : "keyframe-update down-sampling failed";
+            return rcu;
+        }
+    }
+    cur.update_points = in.nd;
+    cur.outer_iterations = ast.outer_iterations;
+    cur.queries = ast.queries;
+    o->queries_total += ast.queries;
+    cur.queries_total = o->queries_total;
+    tm.lap("align");
+    {  // :53-63 divergence guard
+        float ang[3];
+        delta_euler_deg(result.q, o->current.q, ang);
+        const float thr = o->cfg.angular_divergence_threshold;
+        bool ok = true;
+        for (int a = 0; a < 3; a++) ok = ok && (std::fabs(ang[a]) < thr || std::fabs(ang[a]) > 180 - thr);
+        if (!ok) {
+            result = f.guess;  // :61
+            cur.unstable_rotation = 1;
+        }
+    }
+    o->previous = f.previous_next;                                                                // :28
+    o->current = result;                                                                          // :65
+    o->last = cur;
+    // keyframe update (:67-70): same calls in the same order, on the helper thread when there is one
+    const lom_pose pose_now = o->current;
+    const size_t n_down = (size_t)in.nd;
+    const float *d_down = in.d_down, *d_down_n = in.d_down_n;
+    const double t_submit = o->debug_timing ? StageTimer::now() : 0.0;
+    auto update = [o, pose_now, d_down, d_down_n, n_down, t_submit]() -> int {
+        auto bad = [o](int rc, lom_map *m) {
+            o->deferred_error = lom_last_error(m);
+            return rc;
+        };
+        StageTimer ut(o->debug_timing);  // (the helper thread's own laps: "upd ..." lines)
+        if (o->debug_timing) std::fprintf(stderr, "  %-14s %8.1f us\n", "upd hand-off", (ut.t0 - t_submit) * 1e6);
+        int rc;
+        // :69 first: the rigid transform of the update cloud reads neither the map nor what the cleanup leaves, and its
+        // launch fills the time the cleanup spends waiting for its scan (enqueued behind the align) to report
+        const float *d_upd = nullptr, *d_upd_n = nullptr;
+        if ((rc = lom_transform_points_device(o->keyframe, &pose_now, d_down, d_down_n, n_down, 12, &d_upd,
+                                              &d_upd_n)) != LOM_OK)
+            return bad(rc, o->keyframe);
+        if ((rc = lom_map_radius_cleanup(o->keyframe, pose_now.t, o->cfg.keyframe_cleanup_range)) != LOM_OK)  // :67
+            return bad(rc, o->keyframe);
+        ut.lap("upd cleanup");
+        if ((rc = lom_map_add_points_device_nowait(o->keyframe, d_upd, d_upd_n, n_down, 12)) != LOM_OK)  // :70
+            return bad(rc, o->keyframe);
+        ut.lap("upd enqueue");
+        // one look at the host per update: the deferred verdict of the insert and the voxel count
+        if ((rc = lom_map_status(o->keyframe)) != LOM_OK) return bad(rc, o->keyframe);
+        ut.lap("upd status");
+        o->last.keyframe_voxels = lom_map_size(o->keyframe);
+        o->keyframe_has_voxels = o->last.keyframe_voxels > 0;
+        return LOM_OK;
+    };
+    if (o->deferred) {
+        o->deferred->submit(update);
+    } else if ((rc = update()) != LOM_OK) {
+        o->error = o->deferred_error;
+        return rc;
+    }
+    tm.lap("keyframe update");
+    tm.total();
+    return LOM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -990,148 +1184,100 @@ int lom_odometry_process_cloud(lom_odometry *o, const lom_point_xyzirt *pts, siz
 {
     if (!o || (!pts && n)) return LOM_ERR_ARG;
     try {
-        lom_odometry_frame_stats cur{};  // becomes o->last when the frame is through
-        StageTimer tm(o->debug_timing);
-        lom_pose relative, rel_inv, ident, guess, result;
-        lom_pose_relative_to(&o->previous, &o->current, &relative);  // :27
-        // :28 previous_transform_ = current_transform_ -- committed where the frame succeeds (the
-        // reference has no error channel; here a frame that fails must leave the state as it found it,
-        // or the next frame's constant-velocity guess and deskew would start from a zero motion)
-        const lom_pose previous_next = o->current;
-        lom::pose_inverse(relative, rel_inv);
-        lom_pose_identity(&ident);
-        FrameInputs in;
-        int rc = 1;
-        // a hint is for the call that follows it, what was sent ahead for the call after that: neither outlives its call
-        o->hint_now = o->hint_pts;
-        o->hint_pts = nullptr;
-        struct DropHints {
-            lom_odometry *o;
-            const lom_point_xyzirt *sent_before;
-            ~DropHints()
-            {
-                o->hint_now = nullptr;
-                if (o->ahead_pts == sent_before) o->ahead_pts = nullptr;  // (this call did not use it: the front end drops it)
-            }
-        } drop_hints{o, o->ahead_pts};
-        o->parity ^= 1;
-        o->update_ds = o->update_ds2[o->parity];
-        if (o->frontend) rc = stages_on_device(o, pts, n, rel_inv, ident, cur, in, tm);
-        if (rc == 1) {
-            in = FrameInputs();
-            rc = stages_on_host(o, pts, n, rel_inv, ident, cur, in, tm);
-            cur.host_stages = 1;
-        }
+        Frame f(o->debug_timing);
+        DropHints drop_hints;
+        drop_hints.arm(o);
+        frame_enqueue(o, f, pts, n);
+        int rc = frame_stages(o, f, pts, n);
+        if (rc == kFrameDone) return LOM_OK;
         if (rc != LOM_OK) return rc;
-        // :40 keyframe_.size() == 0 -- known on the host: the keyframe is empty until a frame has put voxels
-        // into it (nd > 0 points always create at least one), and stays non-empty unless a cleanup empties it
-        if (!o->keyframe_has_voxels) {  // :40-44 init keyframe
-            {   // the stages ran on a stale "has voxels" (the previous update emptied the keyframe meanwhile): the
-                // update cloud's count is still on its way
-                const char *why = nullptr;
-                const int rcu = collect_or_redo_update(o, in, &why);
-                if (rcu != LOM_OK) {
-                    o->error = why ? why : "keyframe-update down-sampling failed";
-                    return rcu;
-                }
-            }
-            if ((rc = lom_map_add_points_device(o->keyframe, in.d_down, in.d_down_n, (size_t)in.nd, 12)) != LOM_OK)
-                return fail_map(o, rc, o->keyframe);
-            cur.initialised_keyframe = 1;
-            cur.update_points = in.nd;
-            cur.keyframe_voxels = lom_map_size(o->keyframe);
-            o->keyframe_has_voxels = cur.keyframe_voxels > 0;
-            o->last = cur;
-            o->previous = previous_next;  // :28
-            return LOM_OK;
-        }
-        cur.matching_points = in.nm;
-        lom_pose_compose(&o->current, &relative, &guess);  // :51
         lom_align_stats ast;
+        lom_pose result;
         // :65-67: the keyframe update below starts with radiusCleanup(current_transform_.translation): its scan may run
         // right behind the align, on the align's own result
         if (!o->no_cleanup_behind_align) (void)lom_map_radius_cleanup_after_align(o->keyframe, o->cfg.keyframe_cleanup_range);
         // ... and the frame the caller has announced (lom_odometry_hint_next) is sent ahead while this thread would only
         // watch the align's report
         if (o->hint_now && o->frontend && o->temp_on_device) (void)lom_map_set_align_idle_hook(o->keyframe, send_next_frame_ahead, o);
-        if ((rc = lom_match_align_device(o->keyframe, in.d_match, (size_t)in.nm, 12, guess.t, guess.q, result.t, result.q,
-                                         &ast)) != LOM_OK) {  // :49-51
-            (void)in.collect_update(nullptr);
+        if ((rc = lom_match_align_device(o->keyframe, f.in.d_match, (size_t)f.in.nm, 12, f.guess.t, f.guess.q, result.t,
+                                         result.q, &ast)) != LOM_OK) {  // :49-51
+            (void)f.in.collect_update(nullptr);
             return fail_map(o, rc, o->keyframe);
         }
-        {   // the update cloud was down-sampled beside the align: its size and verdict (long since on the host)
-            const char *why = nullptr;
-            const int rcu = collect_or_redo_update(o, in, &why);
-            if (rcu != LOM_OK) {
-                o->error = why ? why : "keyframe-update down-sampling failed";
-                return rcu;
-            }
-        }
-        cur.update_points = in.nd;
-        cur.outer_iterations = ast.outer_iterations;
-        cur.queries = ast.queries;
-        o->queries_total += ast.queries;
-        cur.queries_total = o->queries_total;
-        tm.lap("align");
-        {  // :53-63 divergence guard
-            float ang[3];
-            delta_euler_deg(result.q, o->current.q, ang);
-            const float thr = o->cfg.angular_divergence_threshold;
-            bool ok = true;
-            for (int a = 0; a < 3; a++) ok = ok && (std::fabs(ang[a]) < thr || std::fabs(ang[a]) > 180 - thr);
-            if (!ok) {
-                result = guess;  // :61
-                cur.unstable_rotation = 1;
-            }
-        }
-        o->previous = previous_next;                                                                  // :28
-        o->current = result;                                                                          // :65
-        o->last = cur;
-        // keyframe update (:67-70): same calls in the same order, on the helper thread when there is one
-        const lom_pose pose_now = o->current;
-        const size_t n_down = (size_t)in.nd;
-        const float *d_down = in.d_down, *d_down_n = in.d_down_n;
-        const double t_submit = o->debug_timing ? StageTimer::now() : 0.0;
-        auto update = [o, pose_now, d_down, d_down_n, n_down, t_submit]() -> int {
-            auto bad = [o](int rc, lom_map *m) {
-                o->deferred_error = lom_last_error(m);
-                return rc;
-            };
-            StageTimer ut(o->debug_timing);  // (the helper thread's own laps: "upd ..." lines)
-            if (o->debug_timing) std::fprintf(stderr, "  %-14s %8.1f us\n", "upd hand-off", (ut.t0 - t_submit) * 1e6);
-            int rc;
-            // :69 first: the rigid transform of the update cloud reads neither the map nor what the cleanup leaves, and its
-            // launch fills the time the cleanup spends waiting for its scan (enqueued behind the align) to report
-            const float *d_upd = nullptr, *d_upd_n = nullptr;
-            if ((rc = lom_transform_points_device(o->keyframe, &pose_now, d_down, d_down_n, n_down, 12, &d_upd,
-                                                  &d_upd_n)) != LOM_OK)
-                return bad(rc, o->keyframe);
-            if ((rc = lom_map_radius_cleanup(o->keyframe, pose_now.t, o->cfg.keyframe_cleanup_range)) != LOM_OK)  // :67
-                return bad(rc, o->keyframe);
-            ut.lap("upd cleanup");
-            if ((rc = lom_map_add_points_device_nowait(o->keyframe, d_upd, d_upd_n, n_down, 12)) != LOM_OK)  // :70
-                return bad(rc, o->keyframe);
-            ut.lap("upd enqueue");
-            // one look at the host per update: the deferred verdict of the insert and the voxel count
-            if ((rc = lom_map_status(o->keyframe)) != LOM_OK) return bad(rc, o->keyframe);
-            ut.lap("upd status");
-            o->last.keyframe_voxels = lom_map_size(o->keyframe);
-            o->keyframe_has_voxels = o->last.keyframe_voxels > 0;
-            return LOM_OK;
-        };
-        if (o->deferred) {
-            o->deferred->submit(update);
-        } else if ((rc = update()) != LOM_OK) {
-            o->error = o->deferred_error;
-            return rc;
-        }
-        tm.lap("keyframe update");
-        tm.total();
-        return LOM_OK;
+        return frame_commit(o, f, ast, result);
     } catch (const std::bad_alloc &) {
         o->error = "host allocation failed";
         return LOM_ERR_OOM;
     }
+}
+
+int lom_odometry_process_batch(lom_odometry *const *o, const lom_point_xyzirt *const *frames, const size_t *n, int count,
+                               int *status_out)
+{
+    if (count < 0 || (count > 0 && (!o || !frames || !n))) return LOM_ERR_ARG;
+    for (int i = 0; i < count; i++) {
+        if (!o[i] || (!frames[i] && n[i]) || o[i]->device != o[0]->device) return LOM_ERR_ARG;
+        for (int j = 0; j < i; j++)
+            if (o[j] == o[i]) return LOM_ERR_ARG;
+    }
+    std::vector<int> st((size_t)count, LOM_OK);
+    try {
+        std::vector<std::unique_ptr<Frame>> f((size_t)count);
+        std::vector<DropHints> drop_hints((size_t)count);  // (no hint is followed: the batch arms no idle hook)
+        // every stream's stages go out before any is waited for: the K front ends overlap on the device
+        for (int i = 0; i < count; i++) {
+            f[i].reset(new Frame(o[i]->debug_timing));
+            drop_hints[i].arm(o[i]);
+            frame_enqueue(o[i], *f[i], frames[i], n[i]);
+        }
+        std::vector<int> aligning;
+        for (int i = 0; i < count; i++) {
+            const int rc = frame_stages(o[i], *f[i], frames[i], n[i]);
+            if (rc == LOM_OK) aligning.push_back(i);
+            else if (rc != kFrameDone) st[i] = rc;
+        }
+        // one align for all streams that align, on the first one's keyframe stream; no cleanup scan behind it
+        if (!aligning.empty()) {
+            const size_t k = aligning.size();
+            std::vector<lom_align_multi_problem> p(k);
+            std::vector<lom_align_result> res(k);
+            for (size_t a = 0; a < k; a++) {
+                const Frame &fr = *f[aligning[a]];
+                p[a].map = o[aligning[a]]->keyframe;
+                p[a].xyz = fr.in.d_match;
+                p[a].n = (size_t)fr.in.nm;
+                p[a].stride_bytes = 12;
+                std::memcpy(p[a].guess_t, fr.guess.t, sizeof p[a].guess_t);
+                std::memcpy(p[a].guess_q_wxyz, fr.guess.q, sizeof p[a].guess_q_wxyz);
+            }
+            lom_map *runner = o[aligning[0]]->keyframe;
+            const int rc = lom_match_align_multi_device(runner, p.data(), (int)k, res.data(), nullptr);  // :49-51
+            for (size_t a = 0; a < k; a++) {
+                const int i = aligning[a];
+                if (rc != LOM_OK) {
+                    (void)f[i]->in.collect_update(nullptr);
+                    st[i] = fail_map(o[i], rc, runner);
+                    continue;
+                }
+                lom_pose result;
+                std::memcpy(result.t, res[a].t, sizeof result.t);
+                std::memcpy(result.q, res[a].q_wxyz, sizeof result.q);
+                st[i] = frame_commit(o[i], *f[i], res[a].stats, result);
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        for (int i = 0; i < count; i++)
+            if (st[i] == LOM_OK) {
+                o[i]->error = "host allocation failed";
+                st[i] = LOM_ERR_OOM;
+            }
+    }
+    int rc = LOM_OK;
+    for (int i = 0; i < count; i++) {
+        if (status_out) status_out[i] = st[i];
+        if (rc == LOM_OK) rc = st[i];
+    }
+    return rc;
 }
 
 int lom_odometry_process_sequence(lom_odometry *o, const lom_point_xyzirt *const *frames, const size_t *n, size_t count,

@@ -2096,6 +2096,7 @@ void lom_map_destroy(lom_map *m)
     if (m->h_stage) (void)hipHostFree(m->h_stage);
     if (m->stage_ev) (void)hipEventDestroy(m->stage_ev);
     if (m->parent_ev) (void)hipEventDestroy(m->parent_ev);
+    if (m->multi_ev) (void)hipEventDestroy(m->multi_ev);
     if (m->h_cmd) (void)hipHostFree(m->h_cmd);
     if (m->h_report) (void)hipHostFree(m->h_report);
     if (m->h_batch) (void)hipHostFree(m->h_batch);

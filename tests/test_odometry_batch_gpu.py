@@ -1,0 +1,150 @@
+"""Batched odometry (lom_odometry_process_batch / LidarOdometry.processBatch): one frame for each of K independent
+streams per call.  The reference for every stream is the same frame sequence through processCloud on a fresh handle:
+every pose bit for bit, the frame stats, the temp cloud and the final keyframe."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from lidar_odometry_demo_amd import synth
+from tests.conftest import ROOT
+
+pytestmark = pytest.mark.gpu
+
+STAT_KEYS = ("planar_points", "filtered_points", "update_points", "matching_points", "keyframe_voxels", "queries",
+             "outer_iterations", "initialised_keyframe", "unstable_rotation", "host_stages", "queries_total")
+
+
+@functools.lru_cache(maxsize=None)
+def _boxes(seed):
+    return synth.make_boxes(seed)
+
+
+@functools.lru_cache(maxsize=None)
+def _frame(seed, k, beams=16):
+    return synth.make_sequence_frame(k, n_beams=beams, boxes=_boxes(seed))
+
+
+def _pose_bits(o):
+    p = o.getCurrentPose()
+    return np.asarray(p.translation, np.float32).tobytes() + np.asarray(p.rotation, np.float32).tobytes()
+
+
+def _keyframe_bytes(o):
+    xyz, nrm = o.getFullKeyFrameCloudWithNormals()
+    return xyz.tobytes() + nrm.tobytes()
+
+
+def _assert_same(a, b, where):
+    assert _pose_bits(a) == _pose_bits(b), where
+    sa, sb = a.stats, b.stats
+    for k in STAT_KEYS:
+        assert sa[k] == sb[k], (where, k, sa[k], sb[k])
+
+
+def _streams(k):
+    """(world seed, start frame, beams) per stream: different worlds and start frames, stream 1 a 64-beam sensor"""
+    return [(1000 + j, 2 * j, 64 if j == 1 else 16) for j in range(k)]
+
+
+@pytest.mark.parametrize("k,steps", [(4, 40), (8, 14)])
+def test_batch_equals_solo_runs(lom, k, steps):
+    spec = _streams(k)
+    batch = [lom.LidarOdometry() for _ in spec]
+    solo = [lom.LidarOdometry() for _ in spec]
+    if k == 8:  # several rounds of the align chain
+        batch[0].setOption(lom.capi.OPT_TEST_BATCH_ROUND_MAX, 3)
+    for t in range(steps):
+        frames = [_frame(seed, start + t, beams) for seed, start, beams in spec]
+        lom.LidarOdometry.processBatch(batch, frames)
+        for o, f in zip(solo, frames):
+            o.processCloud(f)
+        for j in range(k):
+            _assert_same(batch[j], solo[j], (t, j))
+    assert batch[0].stats["initialised_keyframe"] == 0 and batch[0].stats["outer_iterations"] > 0
+    for j in range(k):
+        assert _keyframe_bytes(batch[j]) == _keyframe_bytes(solo[j]), j
+        assert batch[j].getTempCloud().tobytes() == solo[j].getTempCloud().tobytes(), j
+
+
+def test_mixed_phases_in_one_call(lom):
+    """one stream on its first frame, one forced to the host stages, one whose front-end scan gives up, the rest
+    mid-sequence -- all in the same calls"""
+    spec = _streams(5)
+    batch = [lom.LidarOdometry() for _ in spec]
+    solo = [lom.LidarOdometry() for _ in spec]
+    joins = [3, 0, 0, 0, 0]  # stream 0 joins at step 3: its first frame initialises its keyframe
+    for t in range(7):
+        active = [j for j in range(len(spec)) if t >= joins[j]]
+        if t == 3:
+            for group in (batch, solo):
+                group[1].setOption(lom.capi.OPT_TEST_FORCE_HOST_REDO, 1)
+                group[2].setOption(lom.capi.OPT_TEST_GRID_GIVE_UP, 2)
+        if t == 5:
+            for group in (batch, solo):
+                group[1].setOption(lom.capi.OPT_TEST_FORCE_HOST_REDO, 0)
+                group[3].setOption(lom.capi.OPT_TEST_GRID_GIVE_UP_MATCHING_DS, 2)
+        frames = {j: _frame(spec[j][0], spec[j][1] + t - joins[j], spec[j][2]) for j in active}
+        lom.LidarOdometry.processBatch([batch[j] for j in active], [frames[j] for j in active])
+        for j in active:
+            solo[j].processCloud(frames[j])
+            _assert_same(batch[j], solo[j], (t, j))
+        if t == 3:
+            assert batch[0].stats["initialised_keyframe"] == 1
+            assert batch[1].stats["host_stages"] == 1 and batch[2].stats["host_stages"] == 1
+            assert batch[3].stats["host_stages"] == 0
+    for j in range(len(spec)):
+        assert _keyframe_bytes(batch[j]) == _keyframe_bytes(solo[j]), j
+
+
+def test_batch_and_process_cloud_alternate(lom):
+    spec = _streams(3)
+    batch = [lom.LidarOdometry() for _ in spec]
+    solo = [lom.LidarOdometry() for _ in spec]
+    for t in range(10):
+        frames = [_frame(seed, start + t, beams) for seed, start, beams in spec]
+        if t % 2 == 0:
+            lom.LidarOdometry.processBatch(batch, frames)
+        else:
+            for o, f in zip(batch, frames):
+                o.processCloud(f)
+        for o, f in zip(solo, frames):
+            o.processCloud(f)
+        for j in range(len(spec)):
+            _assert_same(batch[j], solo[j], (t, j))
+            if t % 2 == 0:
+                assert batch[j].getTempCloud().tobytes() == solo[j].getTempCloud().tobytes(), (t, j)
+    for j in range(len(spec)):
+        assert _keyframe_bytes(batch[j]) == _keyframe_bytes(solo[j]), j
+
+
+def test_argument_errors_move_no_stream(lom):
+    spec = _streams(2)
+    a, b = lom.LidarOdometry(), lom.LidarOdometry()
+    for t in range(3):
+        lom.LidarOdometry.processBatch([a, b], [_frame(s, st + t, bm) for s, st, bm in spec])
+    before = (_pose_bits(a), a.stats, _pose_bits(b), b.stats)
+    f = _frame(spec[0][0], 10, spec[0][2])
+    with pytest.raises(lom.LomError) as e:
+        lom.LidarOdometry.processBatch([a, a], [f, f])
+    assert e.value.code == lom.capi.ERR_ARG
+    L = lom.capi.lib()
+    hs = (C.c_void_p * 2)(a._h.value, None)
+    ptrs = (C.c_void_p * 2)(f.ctypes.data, f.ctypes.data)
+    ns = (C.c_size_t * 2)(len(f), len(f))
+    assert L.lom_odometry_process_batch(hs, ptrs, ns, 2, None) == lom.capi.ERR_ARG
+    assert (_pose_bits(a), a.stats, _pose_bits(b), b.stats) == before
+
+
+def test_cpp_mirror_process_batch(tmp_path, lom):
+    exe = str(tmp_path / "test_multi")
+    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "test_multi.cpp"), "-o", exe, "-L", libdir,
+                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+    assert "ALL PASSED" in r.stdout
