@@ -1037,16 +1037,33 @@ __device__ __forceinline__ double swap_add(double a, double b)
     }
 }
 
+// the kT / 32 partial sums of s_part added in order into s_tot[0..30] by one wave (lane = its thread's index in it)
+template <int kT>
+__device__ __forceinline__ void lm_final_sum(const double *s_part, double *s_tot, int lane)
+{
+    if (lane < 31) {
+        double v = 0.0;
+#pragma unroll
+        for (int g = 0; g < kT / 32; g++) v += s_part[g * 32 + lane];
+        s_tot[lane] = v;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // k_lm's evaluation epilogue: workgroup reduction of the 28 per-lane sums through LDS in a fixed
 // order, every row total published straight from the lane that holds it (plus the workgroup's
 // slice of k_match's counters), then all workgroups' words gathered and added in workgroup order
 // into s_tot[0..30] -- bitwise the same on every workgroup.  Only the first wave may read s_tot
 // afterwards (no workgroup barrier behind the final sum); the caller's next __syncthreads()
 // releases s_acc / s_part for the following evaluation.
-//   s_acc: 32 doubles per wave;  s_part: kT doubles (kT = threads of the workgroup).
+//   s_acc: 32 doubles per wave;  s_part: kT doubles (kT = threads that hold points).
 // kGridArg: the workgroups of the solve are `nb`, not gridDim.x (k_lm's batch form: one launch holds problems of
 // different grids, sized for the largest)
-template <int kT, int kBlocks, bool kGridArg = false>
+// kFinalSum = false (k_lm's 256-thread shapes): the caller's policy wave adds the kT / 32 partial sums in s_part itself
+// (lm_final_sum), behind the second __syncthreads() here; the kT threads of the point waves stop at that barrier.
+template <int kT, int kBlocks, bool kGridArg = false, bool kFinalSum = true>
 __device__ __forceinline__ void reduce_and_exchange(const double acc[28], double *s_acc, double *s_part,
                                                     const uint32_t *__restrict__ block_counters,
                                                     uint32_t n_match_blocks, XWord *set, uint32_t nb,
@@ -1201,18 +1218,10 @@ __device__ __forceinline__ void reduce_and_exchange(const double acc[28], double
     }
     RX_STAMP(3);
     __syncthreads();
-    if (tid < 64) {  // the first wave adds the kT / 32 partial sums in order and keeps the totals to itself
-        if (tid < 31) {
-            double v = 0.0;
-#pragma unroll
-            for (int g = 0; g < kT / 32; g++) v += s_part[g * 32 + tid];
-            s_tot[tid] = v;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if constexpr (kFinalSum) {
+        if (tid < 64) lm_final_sum<kT>(s_part, s_tot, tid);  // the first wave keeps the totals to itself
+        RX_STAMP(4);
     }
-    RX_STAMP(4);
 #undef RX_STAMP
 }
 
@@ -1403,8 +1412,13 @@ __device__ __forceinline__ void accumulate_all(const MatchRec *__restrict__ rec,
 // blockIdx.y selects the problem (`batch[blockIdx.y]`: records, n, guess, state, k_match's counters, exchange set,
 // report, solve grid): the problem's solve runs on the single align's grid for it (`lm_blocks` workgroups; those beyond
 // it in a launch sized for the round's largest leave at once); a give-up test applies to problem 0 of the launch.
+// kT: the threads that hold points.  The 256-thread shapes run one wave more (lm_threads): the POLICY WAVE, which holds
+// the solve's state and no points, while the four point waves hold the points and the accumulators.  Each role runs a
+// loop of its own, so the compiler allocates registers for each live set on its own (one loop carried both: 256 VGPRs +
+// 34-58 AGPRs and ~200 SGPR spills, one wave per SIMD); the roles meet at the three __syncthreads() of an evaluation.
+constexpr int lm_threads(int kT) { return kT == 256 ? kT + 64 : kT; }
 template <int kT, int kBlocks = (int)kMaxLmBlocks, int kRegPts = 1, bool kPolicyTwice = false, bool kBatch = false>
-__global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uint32_t n, AlignState *state,
+__global__ __launch_bounds__(lm_threads(kT)) void k_lm(const MatchRec *__restrict__ rec, uint32_t n, AlignState *state,
                                                      LmInit init, int first_outer,
                                                      const uint32_t *__restrict__ block_counters,
                                                      uint32_t n_match_blocks, XWord *xrec,
@@ -1428,19 +1442,22 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
         if (blockIdx.y != 0) test_give_up = 0;
         if (blockIdx.x >= d->lm_blocks) return;  // (uniform: before any barrier)
     }
-    __shared__ double s_acc[(kT / 64) * 32];  // the waves' totals of one evaluation
+    constexpr bool kRoles = lm_threads(kT) != kT;  // a policy wave of its own (wave kT / 64)
+    __shared__ double s_acc[(kT / 64) * 32];  // the point waves' totals of one evaluation
     __shared__ double s_tot[kRecWords];
     __shared__ double s_part[kT];
     __shared__ double s_x[7];
-    LmWave W;  // the solve's state: per-row part in the registers of the first wave, the rest in LDS (lm_wave.hpp)
+    LmWave W;  // the solve's state: per-row part in the registers of the policy wave, the rest in LDS (lm_wave.hpp)
     // the solve's uniform state: in every lane's registers in the 256-thread shapes, one copy in LDS in the 512-thread ones
     constexpr bool kRegState = kT == 256;
     __shared__ LmShared s_lm;
     LmShared r_lm;
     __shared__ int s_action, s_failed;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the wave that runs the policy (kRoles: it holds no points), and its first thread, which writes the state back
+    constexpr int kPolicyWave = kRoles ? kT / 64 : 0, kOwnerTid = kPolicyWave * 64;
     const uint32_t nb = kBatch ? ((ConstBatch)(batch + blockIdx.y))->lm_blocks : gridDim.x;
-    const uint32_t first = blockIdx.x * blockDim.x + tid, step = nb * blockDim.x;
+    const uint32_t first = blockIdx.x * (uint32_t)kT + tid, step = nb * (uint32_t)kT;
     // start-up loads issued together (one memory round trip, not three): this lane's first point --
     // it stays in registers for every evaluation of the solve --, the pose, the chain's stop flags
     // (the records' loads are ISSUED here and waited for behind the other start-up loads: left to the compiler, the second
@@ -1453,7 +1470,7 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
 #pragma unroll
     for (int p = 0; p < kRegPts; p++) {
         const uint32_t i = first + (uint32_t)p * step;
-        have[p] = i < n;
+        have[p] = tid < kT && i < n;
         const MatchRec *at = rec + (have[p] ? i : 0u);
         asm volatile("global_load_dwordx4 %0, %3, off\n\tglobal_load_dwordx4 %1, %3, off offset:16\n\t"
                      "global_load_dwordx4 %2, %3, off offset:32"
@@ -1527,6 +1544,13 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
         rb[p] = have[p] ? make_float4(raw_b[p].x, raw_b[p].y, raw_b[p].z, raw_b[p].w) : make_float4(0.f, 0.f, 0.f, 0.f);
         rc[p] = have[p] ? make_float4(raw_c[p].x, raw_c[p].y, raw_c[p].z, raw_c[p].w) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
+    // kRoles: the ranks' exchange arguments parked in LDS as well (read by the policy step only when ranks exchange)
+    __shared__ P2pArgs s_px;
+    if (kRoles && tid == 0) s_px = px;
+    auto ranks_args = [&]() -> const P2pArgs & {
+        if constexpr (kRoles) return s_px;
+        else return px;
+    };
     if (tid < 7) s_x[tid] = (double)x0;  // cloud_matcher.cpp:122-131
     if (tid == 0) s_failed = test_give_up;  // LOM_OPT_TEST_GIVE_UP_AT_OUTER: this launch behaves as if its waits had timed out
     __syncthreads();
@@ -1534,40 +1558,73 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
     uint32_t counters_from = n_match_blocks;  // k_match's counters are folded by the first evaluation only
     double counters[4] = {0.0, 0.0, 0.0, 0.0};  // valid, cand, occ of the last k_match; queries (all ranks)
     int action = LM_EVAL;
-    // LOM_DEBUG_LM: shader-clock stamps of workgroup 0's first lane in the first k_lm of the align
-    // (0 start, 1 accumulated, 3 totals known, 4 policy done)
-#define LM_STAMP(k)                                                                            \
-    if (dbg_stamps && first_outer && blockIdx.x == 0 && tid == 0 && ev < 5) {                  \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                            \
-        dbg_stamps[ev * 5 + (k)] = __builtin_amdgcn_s_memtime();                               \
+    // LOM_DEBUG_LM: shader-clock stamps of workgroup 0 in the first k_lm of the align (0 start, 1 accumulated: the first
+    // point lane; 3 totals known, 4 policy done: the policy wave's first lane)
+#define LM_STAMP(k)                                                                                          \
+    if (dbg_stamps && first_outer && blockIdx.x == 0 && tid == ((k) < 3 ? 0 : kOwnerTid) && ev < 5) {      \
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                          \
+        dbg_stamps[ev * 5 + (k)] = __builtin_amdgcn_s_memtime();                                             \
     }
+    // the wave index as a scalar: the roles' loops are branched around, not masked (a masked branch would keep the
+    // points live through the policy loop)
+    const bool policy_wave = __builtin_amdgcn_readfirstlane(wave) == kPolicyWave;
+    if (kRoles && !policy_wave) {
+        // ---- the point waves: accumulate, reduce-scatter, publish and gather; the policy wave does the rest ----
+        for (int ev = 0;; ev++) {
+            double acc[28];
+            LM_STAMP(0);
+            accumulate_all<kRegPts>(rec, n, first, step, ra, rb, rc, s_x, acc);
+            LM_STAMP(1);
+            seq++;
+            XWord *set = xrec + (size_t)(seq & 1) * kMaxLmBlocksBig * kRecWords;
+            reduce_and_exchange<kT, kBlocks, kBatch, false>(acc, s_acc, s_part, block_counters, counters_from, set, nb, seq,
+                                                            timeout_ticks, s_tot, &s_failed, &state->error, cnt_pre,
+                                                            (dbg_stamps && first_outer && ev == 1) ? dbg_stamps + 32 : nullptr);
+            counters_from = 0;
+            __syncthreads();  // the policy step is done: s_x holds the next point, s_action what comes next
+            if (s_failed || s_action != LM_EVAL) return;  // (uniform; the policy wave reports)
+        }
+    }
+    // ---- the policy wave (kRoles), or the whole workgroup (512 threads: the first wave runs the policy) ----
     for (int ev = 0; action == LM_EVAL; ev++) {
-        double acc[28];
-        LM_STAMP(0);
-        accumulate_all<kRegPts>(rec, n, first, step, ra, rb, rc, s_x, acc);
-        LM_STAMP(1);
         seq++;
-        XWord *set = xrec + (size_t)(seq & 1) * kMaxLmBlocksBig * kRecWords;
-        reduce_and_exchange<kT, kBlocks, kBatch>(acc, s_acc, s_part, block_counters, counters_from, set, nb, seq, timeout_ticks,
-                            s_tot, &s_failed, &state->error, cnt_pre,
-                            (dbg_stamps && first_outer && ev == 1) ? dbg_stamps + 32 : nullptr);
-        counters_from = 0;
-        if (px.nranks > 1 && wave == 0 && !s_failed) {
+        if constexpr (kRoles) {
+            // the point waves' two barriers of reduce_and_exchange, then their kT / 32 partial sums, added here
+            __syncthreads();
+            __syncthreads();
+            lm_final_sum<kT>(s_part, s_tot, lane);
+            if (dbg_stamps && first_outer && ev == 1 && blockIdx.x == 0 && tid == kOwnerTid) {
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                dbg_stamps[32 + 4] = __builtin_amdgcn_s_memtime();
+            }
+        } else {
+            double acc[28];
+            LM_STAMP(0);
+            accumulate_all<kRegPts>(rec, n, first, step, ra, rb, rc, s_x, acc);
+            LM_STAMP(1);
+            XWord *set = xrec + (size_t)(seq & 1) * kMaxLmBlocksBig * kRecWords;
+            reduce_and_exchange<kT, kBlocks, kBatch>(acc, s_acc, s_part, block_counters, counters_from, set, nb, seq,
+                                                     timeout_ticks, s_tot, &s_failed, &state->error, cnt_pre,
+                                                     (dbg_stamps && first_outer && ev == 1) ? dbg_stamps + 32 : nullptr);
+            counters_from = 0;
+        }
+        const bool ranks = ranks_args().nranks > 1;
+        if (ranks && policy_wave && !s_failed) {
             // ranks of one node: this GPU's totals become the totals over all ranks
             if (lane == 31) s_tot[31] = (double)n;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             // ten times the patience of the in-GPU waits: the peers are other processes
-            global_exchange(px, s_tot, seq, timeout_ticks * 10, &s_failed, blockIdx.x == 0, lane);
+            global_exchange(ranks_args(), s_tot, seq, timeout_ticks * 10, &s_failed, blockIdx.x == 0, lane);
         }
         LM_STAMP(3);
         // lom_debug_lm_trace: the point and the totals of every evaluation of this solve, as the
         // policy is about to see them ([ev][40]: x[7], pad, sums[32]; [200] = evaluations recorded)
-        if (dbg_trace && blockIdx.x == 0 && wave == 0 && !s_failed && ev < 5) {
+        if (dbg_trace && blockIdx.x == 0 && policy_wave && !s_failed && ev < 5) {
             if (lane < 7) dbg_trace[ev * 40 + lane] = s_x[lane];
             if (lane < 31) dbg_trace[ev * 40 + 8 + lane] = s_tot[lane];
-            if (lane == 31) dbg_trace[ev * 40 + 8 + 31] = px.nranks > 1 ? s_tot[31] : (double)n;
+            if (lane == 31) dbg_trace[ev * 40 + 8 + 31] = ranks ? s_tot[31] : (double)n;
             if (lane == 0) dbg_trace[200] = (double)(ev + 1);
         }
         LmWave W_keep = W;
@@ -1575,7 +1632,7 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
         double x_keep = 0.0;
 #pragma nounroll
         for (int rep = 0; rep < (kPolicyTwice ? 2 : 1); rep++)
-        if (wave == 0 && !s_failed) {
+        if (policy_wave && !s_failed) {
             if constexpr (kPolicyTwice) {
                 if (rep == 0) {
                     if (lane < 7) x_keep = s_x[lane];
@@ -1589,7 +1646,7 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
                     LM_STAMP(3);
                 }
             }
-            // the first wave holds the totals (s_tot) and runs the policy (lm_core.hpp's, lane-parallel and
+            // the policy wave holds the totals (s_tot) and runs the policy (lm_core.hpp's, lane-parallel and
             // register-resident: lm_wave.hpp)
             int a;
             if (ev == 0) {
@@ -1597,7 +1654,7 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
                     counters[0] = s_tot[28];
                     counters[1] = s_tot[29];
                     counters[2] = s_tot[30];
-                    counters[3] = px.nranks > 1 ? s_tot[31] : (double)n;
+                    counters[3] = ranks ? s_tot[31] : (double)n;
                 }
                 const double *prior_b = kBatch ? batch[blockIdx.y].prior_b : init.prior_b;
                 a = kRegState ? lmw2_begin<true>(W, r_lm, s_tot, s_x, prior_b, lane)
@@ -1615,9 +1672,9 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
         LM_STAMP(4);
         __syncthreads();
         if (s_failed) {  // uniform over the workgroup
-            if (tid == 0) {
+            if (tid == kOwnerTid) {
                 __hip_atomic_store(&state->error, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (px.nranks > 1) p2p_publish_abort(px);  // the peers leave their waits for this rank at once
+                if (ranks_args().nranks > 1) p2p_publish_abort(ranks_args());  // the peers leave their waits for this rank at once
                 __hip_atomic_store(&report->error, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
             return;
@@ -1625,8 +1682,8 @@ __global__ __launch_bounds__(kT) void k_lm(const MatchRec *__restrict__ rec, uin
         action = s_action;
     }
 #undef LM_STAMP
-    if (blockIdx.x != 0 || tid != 0) return;
-    // ---- end of the outer iteration (workgroup 0, one lane) ----
+    if (blockIdx.x != 0 || tid != kOwnerTid) return;
+    // ---- end of the outer iteration (workgroup 0, one lane of the policy wave) ----
     const LmShared &S = kRegState ? r_lm : s_lm;
     prev.outer_done = s_prev_i[0];
     prev.lm_iterations = s_prev_i[1];
@@ -2075,7 +2132,9 @@ constexpr int kDeviceLoopGaveUp = 100;
 // points per lane (C3 on 64 workgroups of 256) lose: 24.4-25.5 against 22.4 us.
 // Clouds beyond what 64 workgroups of 512 cover with two points per lane (C3, C4 on one GPU) take up to 128 workgroups:
 // the accumulation halves, the gather reads twice as many records (on C2-sized clouds that trade loses).
+// The 256-thread shapes launch one wave more, the policy wave (k_lm): nb and the point assignment count the 256 threads.
 constexpr uint32_t kLmSmallThreads = 256;
+constexpr uint32_t kLmSmallLaunch = (uint32_t)lm_threads((int)kLmSmallThreads);  // the point threads and the policy wave
 enum LmShape { kLmSmall = 0, kLmMid = 1, kLmBig = 2, kLmSmall2 = 3 };
 static LmShape lm_shape(uint32_t n)
 {
@@ -2094,11 +2153,11 @@ static int lm_block_limit(lom_map *m, LmShape shape, uint32_t *out)
         int per_cu = 0, cus = 0;
         if (shape == kLmSmall)
             LOM_HIP(m, hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                           &per_cu, reinterpret_cast<const void *>(k_lm<(int)kLmSmallThreads>), (int)kLmSmallThreads, 0));
+                           &per_cu, reinterpret_cast<const void *>(k_lm<(int)kLmSmallThreads>), (int)kLmSmallLaunch, 0));
         else if (shape == kLmSmall2)
             LOM_HIP(m, hipOccupancyMaxActiveBlocksPerMultiprocessor(
                            &per_cu, reinterpret_cast<const void *>(k_lm<(int)kLmSmallThreads, (int)kMaxLmBlocks, 2>),
-                           (int)kLmSmallThreads, 0));
+                           (int)kLmSmallLaunch, 0));
         else if (shape == kLmMid)
             LOM_HIP(m, hipOccupancyMaxActiveBlocksPerMultiprocessor(
                            &per_cu, reinterpret_cast<const void *>(k_lm<kEvalThreads>), kEvalThreads, 0));
@@ -2147,9 +2206,11 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
     // (tests, rehearsals) must all be resident together
     LmShape shape = lm_shape(c.n);
     if (m->p2p && shape == kLmBig) shape = kLmMid;
-    const uint32_t lm_threads = (shape == kLmSmall || shape == kLmSmall2) ? kLmSmallThreads : (uint32_t)kEvalThreads;
+    const bool small = shape == kLmSmall || shape == kLmSmall2;
+    const uint32_t lm_points = small ? kLmSmallThreads : (uint32_t)kEvalThreads;  // point threads of a workgroup
+    const uint32_t lm_block = small ? kLmSmallLaunch : (uint32_t)kEvalThreads;    // its threads
     if ((rc = lm_block_limit(m, shape, &nb_limit)) != LOM_OK) return rc;
-    const uint32_t nb = std::min(std::min(std::max(1u, (c.n + lm_threads - 1) / lm_threads),
+    const uint32_t nb = std::min(std::min(std::max(1u, (c.n + lm_points - 1) / lm_points),
                                           shape == kLmBig ? kMaxLmBlocksBig : kMaxLmBlocks),
                                  nb_limit);
     double *d_trace = nullptr;  // lom_debug_lm_trace: k_lm of outer iteration `trace_outer` records its evaluations
@@ -2181,7 +2242,7 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
         m->lm_seq += 8;  // a solve spends at most 5 evaluations
         px.set_base = (int)((m->lm_launches++ & 1ull) * 2ull);  // same launch count on every rank
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(nb), dim3(lm_threads), 0, m->stream, (const MatchRec *)m->scan_on.p, c.n,
+            hipLaunchKernelGGL(kernel, dim3(nb), dim3(lm_block), 0, m->stream, (const MatchRec *)m->scan_on.p, c.n,
                                (AlignState *)m->align_state.p, init, i == 0 ? 1 : 0,
                                (const uint32_t *)d_block_counters(m), c.match_blocks, (XWord *)m->xrec.p, m->lm_seq,
                                reinterpret_cast<AlignReport *>(m->d_report), seq0 + (unsigned long long)i + 1,
@@ -2473,7 +2534,7 @@ static int lm_batch_per_cu(lom_map *m, LmShape shape, uint32_t *out)
     uint32_t &cached = m->lm_batch_per_cu[shape];
     if (!cached) {
         int per_cu = 0;
-        const int threads = (shape == kLmSmall || shape == kLmSmall2) ? (int)kLmSmallThreads : kEvalThreads;
+        const int threads = (shape == kLmSmall || shape == kLmSmall2) ? (int)kLmSmallLaunch : kEvalThreads;
         LOM_HIP(m, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lm_batch_kernel(shape), threads, 0));
         cached = (uint32_t)std::max(1, std::min(per_cu, (int)kBatchBlocksPerCuCap));
     }
@@ -2669,7 +2730,7 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
         uint32_t mb_max = 0;
         for (int k = 0; k < R.size; k++) mb_max = std::max(mb_max, mb[order[R.first + k]]);
         const BatchProblem *desc = d_desc + R.first;
-        const uint32_t threads = (R.shape == kLmSmall || R.shape == kLmSmall2) ? kLmSmallThreads : (uint32_t)kEvalThreads;
+        const uint32_t threads = (R.shape == kLmSmall || R.shape == kLmSmall2) ? kLmSmallLaunch : (uint32_t)kEvalThreads;
         const unsigned long long seq0 = m->batch_report_seq;
         int launched = 0;
         auto launch_pair = [&]() -> int {
