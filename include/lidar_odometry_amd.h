@@ -391,6 +391,11 @@ typedef enum {
                                           (three device-scope atomics per point) instead of the partitioned bulk insert
                                           (csrc/voxel_map.hip "bulk insert").  Same map either way, bytewise; the switch exists
                                           for A/B timing (LOM_NO_BULK_INSERT=1 in the environment at create) */
+    LOM_OPT_QUALITY_REPORT = 8,        /* lom_odometry_set_option only.  1: every frame that runs an align is followed by
+                                          lom_match_quality_device on its matching cloud (still in HBM) at the pose the
+                                          align returned -- before the unstable-rotation override -- with the align's 0.3 m
+                                          gate; lom_odometry_get_quality hands out the last frame's report.  Default 0:
+                                          no extra launches, the same pose bytes */
     LOM_OPT_TEST_GIVE_UP_AT_OUTER = 100, /* k: the k_lm of outer iteration k of the NEXT align behaves as if its
                                           workgroups had timed out waiting (one shot; -1 = off) */
     LOM_OPT_TEST_GRID_GIVE_UP = 101,   /* b >= 0: in the NEXT map-maintenance call with an in-kernel scan, workgroups
@@ -471,6 +476,77 @@ int64_t lom_scan_find_pairs(lom_scan *s, const float *src_xyz, size_t n, size_t 
                             const float q_wxyz[4], float max_dist, lom_correspondence *out);
 int64_t lom_scan_find_pairs_sq(lom_scan *s, const float *src_xyz, size_t n, size_t stride_bytes, const float t[3],
                                const float q_wxyz[4], double max_dist_sq, lom_correspondence *out);
+
+/* ---- align quality report: information, covariance, degeneracy, fit ------------------------------------ */
+/* How good is a pose?  One correspondence search at the pose, then one evaluation of the align's own residual and
+ * Jacobian (csrc/k_eval.hpp point_terms) over its winners, reduced on the device in a fixed order (two calls with the
+ * same inputs return the same bytes, on a map handle and on a scan context alike), and a little host math
+ * (csrc/quality.cpp).
+ *
+ * Tangent order and units of `information` and `gradient` are the solver's own: rotation (3), then translation (3);
+ * the rotation tangent is the Ceres QuaternionManifold increment, i.e. HALF the rotation vector, applied on the left
+ * (world frame).  The translation prior of the align (weight 100 on each translation diagonal) is NOT included.
+ * `covariance` is in nav_msgs order -- x, y, z, then rotation about the fixed X, Y, Z axes in radians:
+ *     covariance = sigma2 * (S P H P^T S)^-1,   P: translation first,   S = diag(1, 1, 1, 1/2, 1/2, 1/2)
+ * by Cholesky.  No pseudo-inverse and no regularisation: where the factorisation meets a pivot <= 0 or a non-finite
+ * value, or valid < 7, covariance_valid = 0 and the 36 values read 0 (degenerate geometry: see eig_t / eig_r).  A caller
+ * who wants the prior in adds 100 to information[21], [28] and [35] and inverts that matrix themself. */
+typedef struct {
+    int64_t queries;           /* source points searched                                                     */
+    int64_t valid;             /* correspondences found                                                      */
+    int64_t inliers;           /* valid with r^2 <= 0.15^2: the branch in which the Huber weight is 1       */
+    double overlap;            /* valid / queries (0 for queries == 0)                                       */
+    double cost;               /* sum 0.5 rho(r^2): the align's cost at this pose, without the prior         */
+    double rmse;               /* sqrt(sum r^2 / valid), point-to-plane, metres (0 for valid == 0)           */
+    double rmse_inliers;       /* the same over the inliers                                                  */
+    double max_abs_residual;   /* max |r|                                                                    */
+    double mean_sq_dist;       /* sum |R p + t - o|^2 / valid: squared point-to-point distance to the winner
+                                  (the analogue of PCL's fitness score)                                      */
+    double sigma2;             /* sum w r^2 / max(1, valid - 6)                                              */
+    double sum_w;              /* sum of the Huber weights                                                   */
+    double information[36];    /* H = sum w J J^T, full symmetric, row-major                                 */
+    double gradient[6];        /* g = sum w J r                                                              */
+    double eig_t[3];           /* eigenvalues, ascending, of H_tt / sum_w: with unit normals the weighted mean of
+                                  n n^T, trace 1 -- each the share of the constraint on that direction       */
+    double eigvec_t[9];        /* row k: the unit eigenvector of eig_t[k]                                    */
+    double eig_r[3];           /* the same of H_rr / (4 sum_w) (4: half-angles to radians); m^2 of lever arm  */
+    double eigvec_r[9];
+    double covariance[36];     /* see above; row-major                                                       */
+    int32_t degenerate_t;      /* eig_t below min_eig_t (threshold <= 0: not counted, 0)                     */
+    int32_t degenerate_r;      /* eig_r below min_eig_r                                                      */
+    int32_t covariance_valid;
+    int32_t pad;
+} lom_quality_report;
+
+/* The reduced values of one evaluation, as the device leaves them: [0..27] the align's sums (LOM_NSUMS above: H upper
+ * triangle, g, cost); [28] sum w; [29] sum w r^2; [30] sum r^2 over valid; [31] sum r^2 over inliers;
+ * [32] sum |R p + t - o|^2; [33] valid; [34] inliers; [35] max |r|. */
+#define LOM_NQSUMS 36
+/* The host math alone (no device needed): fills *out from the reduced values, the number of queries and the two
+ * thresholds.  The thresholds are the caller's: the smallest share (eig_t) / lever arm in m^2 (eig_r) a direction must
+ * have to count as constrained.  Non-finite sums give covariance_valid = 0 and, for a non-finite block, NaN
+ * eigenvalues and no degeneracy count.  LOM_ERR_ARG for a NULL pointer or a negative count. */
+int lom_quality_from_sums(const double sums[LOM_NQSUMS], int64_t queries, float min_eig_t, float min_eig_r,
+                          lom_quality_report *out);
+/* One search at the f32 pose exactly as given (the quaternion is not re-normalised; max_dist squared in f32, as
+ * lom_match_find_pairs does), then the evaluation at that pose widened to f64; the host waits once.  n == 0 and zero
+ * correspondences are valid (all-zero report; valid = 0, covariance_valid = 0).  residual_out_or_null: n floats, the
+ * signed residual r of every source point, quiet NaN where it has no correspondence.
+ * Isolation as lom_match_align_batch: buffers of its own; the single align's state, an armed
+ * lom_map_radius_cleanup_after_align and an armed idle hook are neither used nor consumed. */
+int lom_match_quality(lom_map *m, const float *src_xyz, size_t n, size_t stride_bytes, const float t[3],
+                      const float q_wxyz[4], float max_dist, float min_eig_t, float min_eig_r, lom_quality_report *out,
+                      float *residual_out_or_null);
+/* same, source cloud and the optional residual array in device memory */
+int lom_match_quality_device(lom_map *m, const float *d_src_xyz, size_t n, size_t stride_bytes, const float t[3],
+                             const float q_wxyz[4], float max_dist, float min_eig_t, float min_eig_r,
+                             lom_quality_report *out, float *d_residual_out_or_null);
+int lom_scan_quality(lom_scan *s, const float *src_xyz, size_t n, size_t stride_bytes, const float t[3],
+                     const float q_wxyz[4], float max_dist, float min_eig_t, float min_eig_r, lom_quality_report *out,
+                     float *residual_out_or_null);
+int lom_scan_quality_device(lom_scan *s, const float *d_src_xyz, size_t n, size_t stride_bytes, const float t[3],
+                            const float q_wxyz[4], float max_dist, float min_eig_t, float min_eig_r,
+                            lom_quality_report *out, float *d_residual_out_or_null);
 
 /* ---- multi-GPU: source points range-sharded, map replicated ------------- */
 /* One all-gather of LOM_NSUMS f64 per residual evaluation over RCCL, summed in
@@ -716,6 +792,12 @@ int lom_odometry_get_pose(const lom_odometry *o, lom_pose *out);   /* getCurrent
  * NULL with cap 0 (count only). */
 int64_t lom_odometry_get_temp_cloud(const lom_odometry *o, lom_point_xyzirt *out, size_t cap);
 int lom_odometry_get_stats(const lom_odometry *o, lom_odometry_frame_stats *out);
+/* LOM_OPT_QUALITY_REPORT: the degeneracy thresholds of the per-frame report (lom_match_quality's min_eig_t / min_eig_r;
+ * both 0 = not counted until the caller sets them: the project has no measured basis for a default), and the report of
+ * the last frame that aligned -- LOM_ERR_STATE before the first such frame or with the option off.  With
+ * lom_odometry_process_batch every stream gets its own, one stream after another. */
+int lom_odometry_set_quality_thresholds(lom_odometry *o, float min_eig_t, float min_eig_r);
+int lom_odometry_get_quality(const lom_odometry *o, lom_quality_report *out);
 /* switches of the pipeline (LOM_OPT_TEST_FORCE_HOST_REDO, the LOM_OPT_TEST_GRID_GIVE_UP family) and, for every other
  * option, of its keyframe handle (the align's).  The environment is read once, by lom_odometry_create
  * (LOM_HOST_THREADS, LOM_SYNC_KEYFRAME_UPDATE, LOM_HOST_FRONTEND, LOM_DEBUG_TIMING, and the A/B switches

@@ -313,9 +313,31 @@ private:
     mutable std::vector<lom_scan *> scans_;
 };
 
+// lom_quality_report as it is: counts, fit, information (rotation first, half-angle tangent), block spectra, and the
+// 6x6 covariance in nav_msgs order (row-major; zeros with covariance_valid == 0 where the geometry is degenerate)
+using QualityReport = lom_quality_report;
+
 // ---- CloudMatcher (src/cloud_matcher.h) --------------------------------------------
 class CloudMatcher {
 public:
+    // How good is `pose` (what align() returned, a loop-closure candidate) for this cloud against this keyframe:
+    // lom_scan_quality on the calling thread's scan context.  residuals_or_null: resized to the cloud, the signed
+    // point-to-plane residual per point, NaN where it has no correspondence.
+    QualityReport quality(const VoxelGrid &keyframe, const PointCloud<PointXYZ> &cloud, const Pose3D &pose,
+                          float max_correspondence_distance = 0.3f, float min_eig_t = 0.f, float min_eig_r = 0.f,
+                          std::vector<float> *residuals_or_null = nullptr) const
+    {
+        const lom_pose g = pose.c();
+        const float *src = cloud.points.empty() ? nullptr : &cloud.points.data()->x;
+        if (residuals_or_null) residuals_or_null->resize(cloud.points.size());
+        float *res = residuals_or_null && !cloud.points.empty() ? residuals_or_null->data() : nullptr;
+        QualityReport out;
+        lom_scan *ctx = keyframe.scan_context();
+        const int rc = lom_scan_quality(ctx, src, cloud.points.size(), sizeof(PointXYZ), g.t, g.q,
+                                        max_correspondence_distance, min_eig_t, min_eig_r, &out, res);
+        if (rc != LOM_OK) throw Error(rc, lom_scan_last_error(ctx));
+        return out;
+    }
     Pose3D align(const VoxelGrid &keyframe, const PointCloud<PointXYZ> &planar_cloud, const Pose3D &position_guess)
     {
         const lom_pose g = position_guess.c();
@@ -574,6 +596,21 @@ public:
     {
         const int rc = lom_odometry_hint_next(h_, next_cloud.points.data(), next_cloud.points.size());
         if (rc != LOM_OK) throw Error(rc, lom_odometry_last_error(h_));
+    }
+    // LOM_OPT_QUALITY_REPORT: every frame that aligns also gets a quality report at the pose the align returned
+    void setQualityReport(bool on, float min_eig_t = 0.f, float min_eig_r = 0.f)
+    {
+        int rc = lom_odometry_set_quality_thresholds(h_, min_eig_t, min_eig_r);
+        if (rc == LOM_OK) rc = lom_odometry_set_option(h_, LOM_OPT_QUALITY_REPORT, on ? 1 : 0);
+        if (rc != LOM_OK) throw Error(rc, lom_odometry_last_error(h_));
+    }
+    // the last aligned frame's report; throws Error(LOM_ERR_STATE) before the first one or with the option off
+    QualityReport getQuality() const
+    {
+        QualityReport out;
+        const int rc = lom_odometry_get_quality(h_, &out);
+        if (rc != LOM_OK) throw Error(rc, "no quality report: the option is off or no frame has aligned yet");
+        return out;
     }
     Pose3D getCurrentPose() const  // :87-89
     {

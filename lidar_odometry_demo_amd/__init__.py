@@ -15,7 +15,7 @@ from . import capi
 from .capi import LomError  # noqa: F401
 
 __all__ = ["Pose3D", "VoxelGrid", "CloudMatcher", "ScanContext", "LidarOdometry", "transform_points", "pointTimeNormalize",
-           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "LomError", "capi"]
+           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "LomError", "capi", "quality_report"]
 
 
 class Pose3D:
@@ -228,6 +228,10 @@ class VoxelGrid:
                    self._h)
         return us.value
 
+    def quality(self, xyz, transform, max_correspondence_distance=0.3, min_eig_t=0.0, min_eig_r=0.0, residuals=False):
+        """lom_match_quality: see quality_report()."""
+        return quality_report(self, xyz, transform, max_correspondence_distance, min_eig_t, min_eig_r, residuals)
+
     def setProfiling(self, period):
         """HIP event pairs around the correspondence launches of every `period`-th align (True = 1, False = 0)."""
         capi.check(capi.lib().lom_map_set_profiling(self._h, int(period)), self._h)
@@ -273,6 +277,10 @@ class ScanContext:
             raise LomError(int(rc), text.decode() if text else "")
         return rc
 
+    def quality(self, xyz, transform, max_correspondence_distance=0.3, min_eig_t=0.0, min_eig_r=0.0, residuals=False):
+        """lom_scan_quality: see quality_report()."""
+        return quality_report(self, xyz, transform, max_correspondence_distance, min_eig_t, min_eig_r, residuals)
+
 
 def _align_entry(keyframe, name):
     """(function, checker) for a grid or a scan context"""
@@ -280,6 +288,30 @@ def _align_entry(keyframe, name):
     if isinstance(keyframe, ScanContext):
         return getattr(L, "lom_scan_" + name), keyframe._check
     return getattr(L, "lom_match_" + name), (lambda rc: capi.check(rc, keyframe.handle))
+
+
+def quality_report(keyframe, xyz, transform, max_correspondence_distance=0.3, min_eig_t=0.0, min_eig_r=0.0,
+                   residuals=False, raw=False):
+    """How good is `transform` for `xyz` against `keyframe` (a VoxelGrid or a ScanContext)?  One search at the pose as
+    given, one evaluation of the align's residuals and Jacobians over its winners (lom_match_quality): a dict of the
+    fields of lom_quality_report -- counts, overlap, rmse, the 6x6 information matrix (rotation first, half-angle
+    tangent), the spectra of its translation and rotation blocks with the number of eigenvalues below the caller's
+    thresholds, and the 6x6 covariance in nav_msgs order (zeros and covariance_valid = 0 where the geometry is
+    degenerate).  residuals=True adds "residuals": the signed point-to-plane residual per source point, NaN where it
+    has no correspondence.  raw=True returns the ctypes struct instead (its bytes compare exactly)."""
+    xyz = capi.xyz_array(xyz)
+    rep = capi.QualityReport()
+    res = np.empty(len(xyz), np.float32) if residuals else None
+    fn, chk = _align_entry(keyframe, "quality")
+    chk(fn(keyframe.handle, xyz.ctypes.data if len(xyz) else None, len(xyz), 12, capi.f3(transform.translation),
+           capi.f4(transform.rotation), float(max_correspondence_distance), float(min_eig_t), float(min_eig_r),
+           C.byref(rep), res.ctypes.data if residuals and len(xyz) else None))
+    if raw:
+        return (rep, res) if residuals else rep
+    out = rep.asdict()
+    if residuals:
+        out["residuals"] = res
+    return out
 
 
 def align_repeat(keyframe, d_src_ptr, n, position_guess, reps, stride_bytes=12):
@@ -422,6 +454,11 @@ class CloudMatcher:
             raise ValueError("alignMultiDevice of no problems needs a runner")
         full = [(ptr, n, g, stride_bytes) for ptr, n, g in items]
         return self._multi(runner, self._multi_problems(keyframes, full), len(items), None, True)
+
+    def quality(self, keyframe, planar_cloud, pose, max_correspondence_distance=0.3, min_eig_t=0.0, min_eig_r=0.0,
+                residuals=False):
+        """The quality report of `pose` (e.g. what align() returned) for this cloud and keyframe: quality_report()."""
+        return quality_report(keyframe, planar_cloud, pose, max_correspondence_distance, min_eig_t, min_eig_r, residuals)
 
     def alignDevice(self, keyframe, d_src_ptr, n, position_guess, stride_bytes=12):
         """Source cloud already resident in HBM (device pointer, e.g. torch tensor.data_ptr())."""
@@ -690,6 +727,22 @@ class LidarOdometry:
             err = LomError(int(rc), "; ".join(texts))
             err.statuses = codes
             raise err
+
+    def setQualityReport(self, on, min_eig_t=0.0, min_eig_r=0.0):
+        """LOM_OPT_QUALITY_REPORT: every frame that aligns also gets a quality report (getQuality)."""
+        rc = capi.lib().lom_odometry_set_quality_thresholds(self._h, float(min_eig_t), float(min_eig_r))
+        if rc != 0:
+            raise LomError(int(rc), "lom_odometry_set_quality_thresholds")
+        self.setOption(capi.OPT_QUALITY_REPORT, 1 if on else 0)
+
+    def getQuality(self, raw=False):
+        """The report of the last frame that aligned (a dict as quality_report() returns; raw=True: the ctypes struct).
+        LomError(LOM_ERR_STATE) before the first aligned frame or with the option off."""
+        rep = capi.QualityReport()
+        rc = capi.lib().lom_odometry_get_quality(self._h, C.byref(rep))
+        if rc != 0:
+            raise LomError(int(rc), "no quality report: the option is off or no frame has aligned yet")
+        return rep if raw else rep.asdict()
 
     def getCurrentPose(self):                              # lidar_odometry.cpp:87-89
         p = capi.Pose()

@@ -72,6 +72,37 @@ class AlignResult(C.Structure):
                 ("pad", C.c_int32)]
 
 
+NQSUMS = 36
+
+
+class QualityReport(C.Structure):
+    """lom_quality_report"""
+    _fields_ = [("queries", C.c_int64), ("valid", C.c_int64), ("inliers", C.c_int64), ("overlap", C.c_double),
+                ("cost", C.c_double), ("rmse", C.c_double), ("rmse_inliers", C.c_double),
+                ("max_abs_residual", C.c_double), ("mean_sq_dist", C.c_double), ("sigma2", C.c_double),
+                ("sum_w", C.c_double), ("information", C.c_double * 36), ("gradient", C.c_double * 6),
+                ("eig_t", C.c_double * 3), ("eigvec_t", C.c_double * 9), ("eig_r", C.c_double * 3),
+                ("eigvec_r", C.c_double * 9), ("covariance", C.c_double * 36), ("degenerate_t", C.c_int32),
+                ("degenerate_r", C.c_int32), ("covariance_valid", C.c_int32), ("pad", C.c_int32)]
+
+    _SHAPES = {"information": (6, 6), "covariance": (6, 6), "eigvec_t": (3, 3), "eigvec_r": (3, 3)}
+
+    def asdict(self):
+        """Scalars as Python numbers, arrays as numpy (information / covariance 6x6, eigenvectors 3x3 with row k the
+        eigenvector of eigenvalue k)."""
+        out = {}
+        for k, _ in self._fields_:
+            if k == "pad":
+                continue
+            v = getattr(self, k)
+            if isinstance(v, C.Array):
+                v = np.array(v[:], np.float64)
+                if k in self._SHAPES:
+                    v = v.reshape(self._SHAPES[k])
+            out[k] = v
+        return out
+
+
 # lidar_point::PointXYZIRT (src/lidar_point_type.h:13-21), 32 bytes
 POINT_XYZIRT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad0", "<f4"), ("intensity", "<f4"),
                          ("ring", "<u2"), ("pad1", "<u2"), ("time", "<f4"), ("pad2", "<f4")])
@@ -145,6 +176,8 @@ EXPORTED = [
     "lom_scan_get_stream", "lom_scan_create_on_partition", "lom_scan_align", "lom_scan_align_device", "lom_scan_align_repeat", "lom_scan_find_pairs", "lom_scan_find_pairs_sq",
     "lom_match_align_batch", "lom_match_align_batch_device", "lom_scan_align_batch", "lom_scan_align_batch_device",
     "lom_align_batch_best", "lom_match_align_multi", "lom_match_align_multi_device", "lom_odometry_process_batch",
+    "lom_quality_from_sums", "lom_match_quality", "lom_match_quality_device", "lom_scan_quality", "lom_scan_quality_device",
+    "lom_odometry_set_quality_thresholds", "lom_odometry_get_quality",
 ]
 
 # lom_option / counters of include/lidar_odometry_amd.h
@@ -152,6 +185,7 @@ OPT_HOST_LM, OPT_DEVICE_PATIENCE_TICKS, OPT_DEBUG_LM_STAMPS, OPT_DEBUG_TIMING, O
 OPT_TEST_GIVE_UP_AT_OUTER, OPT_TEST_GRID_GIVE_UP, OPT_TEST_FORCE_HOST_REDO = 100, 101, 102
 OPT_NO_BULK_INSERT, OPT_TEST_BULK_PARTITION_MAX = 7, 106
 OPT_TEST_BATCH_ROUND_MAX = 107
+OPT_QUALITY_REPORT = 8
 OPT_TEST_GRID_GIVE_UP_MATCHING_DS, OPT_TEST_GRID_GIVE_UP_UPDATE_DS, OPT_TEST_GRID_GIVE_UP_KEYFRAME = 103, 104, 105
 COUNTER_GRID_REDOS = 0
 COUNTER_CLEANUPS_BEHIND_ALIGN = 1
@@ -357,6 +391,14 @@ def lib():
     L.lom_scan_find_pairs.restype = C.c_int64
     L.lom_scan_find_pairs_sq.argtypes = L.lom_match_find_pairs_sq.argtypes
     L.lom_scan_find_pairs_sq.restype = C.c_int64
+    L.lom_quality_from_sums.argtypes = [dp, C.c_int64, C.c_float, C.c_float, C.POINTER(QualityReport)]
+    L.lom_match_quality.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_float, C.c_float, C.c_float,
+                                    C.POINTER(QualityReport), vp]
+    L.lom_match_quality_device.argtypes = L.lom_match_quality.argtypes
+    L.lom_scan_quality.argtypes = L.lom_match_quality.argtypes
+    L.lom_scan_quality_device.argtypes = L.lom_match_quality.argtypes
+    L.lom_odometry_set_quality_thresholds.argtypes = [vp, C.c_float, C.c_float]
+    L.lom_odometry_get_quality.argtypes = [vp, C.POINTER(QualityReport)]
     _lib = L
     return L
 

@@ -240,6 +240,11 @@ struct lom_map {
     unsigned long long batch_report_seq = 0, batch_lm_seq = 0;
     uint32_t lm_batch_per_cu[4] = {0, 0, 0, 0};  // k_lm blocks per CU a batch round may count on, per variant (cached)
     int test_batch_round_max = 0;  // LOM_OPT_TEST_BATCH_ROUND_MAX: problems per round at most (0: by residency)
+    // quality report (lom_match_quality*): buffers of its own, like the batch's -- staged host scan, winner indices and
+    // records of its search, k_match counters, per-workgroup records, per-point residuals -- and the reduced values in
+    // pinned host memory; neither the single align's buffers nor the map-maintenance scratch (scr[]) are touched
+    lom::DeviceBuf qual_src, qual_idx, qual_rec, qual_cnt, qual_part, qual_res;
+    double *h_qual = nullptr, *d_qual = nullptr;  // LOM_NQSUMS doubles
     // lom_match_align_multi: recorded on this handle's stream -- as a problem map, for the runner to wait on before the
     // chain; as the runner, after the chain, for the problem maps to wait on (created once, timing disabled)
     hipEvent_t multi_ev = nullptr;

@@ -20,7 +20,10 @@
 //             LOM_HOST_LM=1): the <= 64 records land in pinned host memory and the host adds
 //             them in workgroup order, or stay in HBM for the RCCL all-gather.
 //
-// The kernels live in k_match.hpp, k_eval.hpp and k_lm.hpp; this file is the one translation unit that instantiates
+//   k_quality the quality report of a pose (lom_match_quality*): one more evaluation over a search's records -- the
+//             align's 28 sums plus weights, residual statistics and counts -- reduced in a fixed order.
+//
+// The kernels live in k_match.hpp, k_eval.hpp, k_lm.hpp and k_quality.hpp; this file is the one translation unit that instantiates
 // and launches them: the kernel tables, the chained single and batched align, the host-driven path, the C entry points.
 //
 // Built with -ffp-contract=off (see voxel_map.hip).
@@ -36,6 +39,7 @@
 #include "k_eval.hpp"
 #include "k_lm.hpp"
 #include "k_match.hpp"
+#include "k_quality.hpp"
 #include "lm_core.hpp"
 #include "lm_wave.hpp"
 #include "lom_internal.hpp"
@@ -1602,6 +1606,83 @@ int lom_debug_eval_sums(lom_map *m, const float *src, size_t n, size_t stride, c
     m->profiling = was;
     if (rc == LOM_OK && hipStreamSynchronize(m->stream) != hipSuccess) rc = LOM_ERR_HIP;
     return rc;
+}
+
+// ---------------------------------------------------------------------------
+// Quality report (lom_match_quality* / lom_scan_quality*): one search at the f32 pose as given, k_quality at that pose
+// widened to f64, k_quality_sum into pinned host memory, ONE wait; the host math is lom_quality_from_sums (quality.cpp).
+// Isolation as the batched align: buffers of its own (lom_map::qual_*), nothing of the single align's state, of an armed
+// cleanup scan or idle hook, or of the map-maintenance scratch is read or written; neither call_seq nor mutations move.
+// The grid is k_eval's (eval_grid): a short, latency-bound kernel behind a k_match of a few microseconds.
+// ---------------------------------------------------------------------------
+static int quality_core(lom_map *m, const float *src, bool device_input, size_t n, size_t stride, const float t[3],
+                        const float q[4], float max_dist, float min_eig_t, float min_eig_r, lom_quality_report *out,
+                        float *residual_out)
+{
+    if (!m || (n && !src) || !t || !q || !out || !scan_args_ok(n, stride)) return LOM_ERR_ARG;
+    if (n == 0) {
+        const double zero[LOM_NQSUMS] = {};
+        return lom_quality_from_sums(zero, 0, min_eig_t, min_eig_r, out);
+    }
+    LOM_HIP(m, hipSetDevice(m->device));
+    m->last_error.clear();
+    int rc = resolve_pending(m);  // an insert nobody has looked at since: the search must see its points
+    if (rc != LOM_OK) return rc;
+    const uint32_t nn = (uint32_t)n;
+    const uint32_t mb = match_grid(nn, m->stream == m->own_stream ? m->partition_cus : 0u), nb = eval_grid(nn);
+    if ((rc = ensure(m, m->qual_idx, n * 4)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qual_rec, n * sizeof(MatchRec))) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qual_cnt, (size_t)kMaxMatchBlocks * 16)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qual_part, (size_t)kMaxEvalBlocks * kQualSums * 8)) != LOM_OK) return rc;
+    if (!m->h_qual) {
+        hipError_t e = hipHostMalloc((void **)&m->h_qual, LOM_NQSUMS * 8, hipHostMallocMapped | hipHostMallocCoherent);
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&m->d_qual, m->h_qual, 0);
+        if (e != hipSuccess) return set_error(m, LOM_ERR_OOM, "hipHostMalloc(quality sums)", e);
+    }
+    const char *d_src = (const char *)src;
+    float *d_res = residual_out;
+    if (!device_input) {
+        const size_t bytes = (n - 1) * stride + 12;
+        if ((rc = ensure(m, m->qual_src, bytes)) != LOM_OK) return rc;
+        LOM_HIP(m, hipMemcpyAsync(m->qual_src.p, src, bytes, hipMemcpyHostToDevice, m->stream));
+        d_src = (const char *)m->qual_src.p;
+        if (residual_out) {
+            if ((rc = ensure(m, m->qual_res, n * 4)) != LOM_OK) return rc;
+            d_res = (float *)m->qual_res.p;
+        }
+    }
+    PoseArgs P;
+    pose_args(t, q, sq_f32(max_dist), P);
+    EvalArgs E;
+    for (int a = 0; a < 4; a++) E.q[a] = (double)q[a];
+    for (int a = 0; a < 3; a++) E.t[a] = (double)t[a];
+    hipLaunchKernelGGL(match_kernel(false, false, m->opt_count, false), dim3(mb), dim3(kMatchThreads), 0, m->stream,
+                       view_of(m), d_src, stride, nn, P, (int32_t *)m->qual_idx.p, (MatchRec *)m->qual_rec.p,
+                       (QStat *)nullptr, (uint32_t *)m->qual_cnt.p, (unsigned long long *)nullptr,
+                       (const AlignState *)nullptr, (const BatchProblem *)nullptr);
+    hipLaunchKernelGGL(k_quality, dim3(nb), dim3(kEvalThreads), 0, m->stream, (const MatchRec *)m->qual_rec.p, nn, E,
+                       (double *)m->qual_part.p, d_res);
+    hipLaunchKernelGGL(k_quality_sum, dim3(1), dim3(64), 0, m->stream, (const double *)m->qual_part.p, nb, m->d_qual);
+    LOM_HIP(m, hipGetLastError());
+    if (!device_input && residual_out)
+        LOM_HIP(m, hipMemcpyAsync(residual_out, d_res, n * 4, hipMemcpyDeviceToHost, m->stream));
+    LOM_HIP(m, hipStreamSynchronize(m->stream));
+    double sums[LOM_NQSUMS];
+    std::memcpy(sums, m->h_qual, sizeof sums);
+    return lom_quality_from_sums(sums, (int64_t)n, min_eig_t, min_eig_r, out);
+}
+
+int lom_match_quality(lom_map *m, const float *src, size_t n, size_t stride, const float t[3], const float q[4],
+                      float max_dist, float min_eig_t, float min_eig_r, lom_quality_report *out, float *residual_out)
+{
+    return quality_core(m, src, false, n, stride, t, q, max_dist, min_eig_t, min_eig_r, out, residual_out);
+}
+
+int lom_match_quality_device(lom_map *m, const float *d_src, size_t n, size_t stride, const float t[3],
+                             const float q[4], float max_dist, float min_eig_t, float min_eig_r,
+                             lom_quality_report *out, float *d_residual_out)
+{
+    return quality_core(m, d_src, true, n, stride, t, q, max_dist, min_eig_t, min_eig_r, out, d_residual_out);
 }
 
 // parity entry: a whole align on the device-resident path (k_match / k_lm chain) that also returns what

@@ -548,6 +548,11 @@ struct lom_odometry {
     std::unique_ptr<Pool> pool;  // host workers for the per-point stages (std::execution::par in the reference)
     int64_t queries_total = 0;
     std::unique_ptr<Deferred> deferred;  // keyframe update of the previous frame
+    // LOM_OPT_QUALITY_REPORT: every frame that aligns is followed by lom_match_quality_device on its matching cloud at
+    // the pose the align returned; lom_odometry_get_quality hands out the last one
+    bool quality_on = false, have_quality = false;
+    float quality_min_eig_t = 0.f, quality_min_eig_r = 0.f;
+    lom_quality_report quality{};
     std::string deferred_error;
     // finish the previous frame's keyframe update; its failure is this call's failure
     int settle()
@@ -694,6 +699,10 @@ int lom_odometry_set_option(lom_odometry *o, int option, int64_t value)
     switch (option) {
     case LOM_OPT_TEST_FORCE_HOST_REDO: o->test_force_host_redo = value != 0; return LOM_OK;
     case LOM_OPT_DEBUG_TIMING: o->debug_timing = value != 0; return lom_map_set_option(o->keyframe, option, value);
+    case LOM_OPT_QUALITY_REPORT:
+        o->quality_on = value != 0;
+        o->have_quality = false;
+        return LOM_OK;
     case LOM_OPT_TEST_GRID_GIVE_UP:  // the front end's scan of the next frame
         return o->frontend ? lom_frontend_set_option(o->frontend, option, value) : LOM_ERR_STATE;
     case LOM_OPT_TEST_GRID_GIVE_UP_MATCHING_DS: return lom_map_set_option(o->matching_ds, LOM_OPT_TEST_GRID_GIVE_UP, value);
@@ -718,6 +727,22 @@ int64_t lom_odometry_debug_counter(const lom_odometry *o, int which)
         return rc != LOM_OK ? rc : lom_map_debug_counter(o->keyframe, which);
     }
     return LOM_ERR_ARG;
+}
+
+int lom_odometry_set_quality_thresholds(lom_odometry *o, float min_eig_t, float min_eig_r)
+{
+    if (!o) return LOM_ERR_ARG;
+    o->quality_min_eig_t = min_eig_t;
+    o->quality_min_eig_r = min_eig_r;
+    return LOM_OK;
+}
+
+int lom_odometry_get_quality(const lom_odometry *o, lom_quality_report *out)
+{
+    if (!o || !out) return LOM_ERR_ARG;
+    if (!o->quality_on || !o->have_quality) return LOM_ERR_STATE;  // option off, or no frame has aligned yet
+    *out = o->quality;
+    return LOM_OK;
 }
 
 int lom_odometry_get_stats(const lom_odometry *o, lom_odometry_frame_stats *out)
@@ -1090,6 +1115,17 @@ int frame_stages(lom_odometry *o, Frame &f, const lom_point_xyzirt *pts, size_t 
     return LOM_OK;
 }
 
+// LOM_OPT_QUALITY_REPORT: the report of the pose the align has just returned (before the divergence guard may replace
+// it), over the matching cloud still in HBM, at the align's own 0.3 m gate (cloud_matcher.cpp:139), against the keyframe
+// as the align saw it (its update comes later, in frame_commit)
+int frame_quality(lom_odometry *o, const Frame &f, const lom_pose &result)
+{
+    const int rc = lom_match_quality_device(o->keyframe, f.in.d_match, (size_t)f.in.nm, 12, result.t, result.q, 0.3f,
+                                            o->quality_min_eig_t, o->quality_min_eig_r, &o->quality, nullptr);
+    o->have_quality = rc == LOM_OK;
+    return rc;
+}
+
 // after the align (:49-51): the update cloud's verdict, :53-63, :65 and the keyframe update (:67-70)
 int frame_commit(lom_odometry *o, Frame &f, const lom_align_stats &ast, lom_pose result)
 {
@@ -1204,6 +1240,10 @@ int lom_odometry_process_cloud(lom_odometry *o, const lom_point_xyzirt *pts, siz
             (void)f.in.collect_update(nullptr);
             return fail_map(o, rc, o->keyframe);
         }
+        if (o->quality_on && (rc = frame_quality(o, f, result)) != LOM_OK) {
+            (void)f.in.collect_update(nullptr);
+            return fail_map(o, rc, o->keyframe);
+        }
         return frame_commit(o, f, ast, result);
     } catch (const std::bad_alloc &) {
         o->error = "host allocation failed";
@@ -1262,6 +1302,14 @@ int lom_odometry_process_batch(lom_odometry *const *o, const lom_point_xyzirt *c
                 lom_pose result;
                 std::memcpy(result.t, res[a].t, sizeof result.t);
                 std::memcpy(result.q, res[a].q_wxyz, sizeof result.q);
+                if (o[i]->quality_on) {  // per stream, one after another
+                    const int rq = frame_quality(o[i], *f[i], result);
+                    if (rq != LOM_OK) {
+                        (void)f[i]->in.collect_update(nullptr);
+                        st[i] = fail_map(o[i], rq, o[i]->keyframe);
+                        continue;
+                    }
+                }
                 st[i] = frame_commit(o[i], *f[i], res[a].stats, result);
             }
         }

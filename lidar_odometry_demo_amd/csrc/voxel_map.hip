@@ -2008,6 +2008,19 @@ int64_t lom_scan_find_pairs_sq(lom_scan *s, const float *src, size_t n, size_t s
 {
     return lom_match_find_pairs_sq(reinterpret_cast<lom_map *>(s), src, n, stride, t, q, max_dist_sq, out);
 }
+int lom_scan_quality(lom_scan *s, const float *src, size_t n, size_t stride, const float t[3], const float q[4],
+                     float max_dist, float min_eig_t, float min_eig_r, lom_quality_report *out, float *residual_out)
+{
+    return lom_match_quality(reinterpret_cast<lom_map *>(s), src, n, stride, t, q, max_dist, min_eig_t, min_eig_r, out,
+                             residual_out);
+}
+int lom_scan_quality_device(lom_scan *s, const float *d_src, size_t n, size_t stride, const float t[3], const float q[4],
+                            float max_dist, float min_eig_t, float min_eig_r, lom_quality_report *out,
+                            float *d_residual_out)
+{
+    return lom_match_quality_device(reinterpret_cast<lom_map *>(s), d_src, n, stride, t, q, max_dist, min_eig_t,
+                                    min_eig_r, out, d_residual_out);
+}
 
 int lom_map_create(float voxel_size, size_t max_points, size_t capacity_hint, int device, lom_map **out)
 {
@@ -2088,7 +2101,8 @@ void lom_map_destroy(lom_map *m)
         if (b.p) (void)hipFree(b.p);
     for (DeviceBuf *b : {&m->scan_src, &m->scan_idx, &m->scan_on, &m->scan_stats, &m->partials, &m->results, &m->gather,
                          &m->align_state, &m->xrec, &m->dbg_trace, &m->dbg_stamps, &m->batch_dev, &m->batch_rec,
-                         &m->batch_cnt, &m->batch_xrec, &m->batch_src})
+                         &m->batch_cnt, &m->batch_xrec, &m->batch_src, &m->qual_src, &m->qual_idx, &m->qual_rec,
+                         &m->qual_cnt, &m->qual_part, &m->qual_res})
         if (b->p) (void)hipFree(b->p);
     if (m->h_results) (void)hipHostFree(m->h_results);
     if (m->h_flags) (void)hipHostFree(m->h_flags);
@@ -2101,6 +2115,7 @@ void lom_map_destroy(lom_map *m)
     if (m->h_report) (void)hipHostFree(m->h_report);
     if (m->h_batch) (void)hipHostFree(m->h_batch);
     if (m->h_batch_report) (void)hipHostFree(m->h_batch_report);
+    if (m->h_qual) (void)hipHostFree(m->h_qual);
     for (auto &e : m->prof_events)
         if (e) (void)hipEventDestroy(e);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
