@@ -413,8 +413,10 @@ typedef enum {
                                                     1,024 its workgroup has LDS for; 0 = that limit): a bulk insert with a
                                                     larger partition writes nothing and is redone by the four-kernel path
                                                     (counted by LOM_COUNTER_GRID_REDOS) */
-    LOM_OPT_TEST_BATCH_ROUND_MAX = 107           /* r > 0: a round of lom_match_align_batch holds at most r problems (0 = as
+    LOM_OPT_TEST_BATCH_ROUND_MAX = 107,          /* r > 0: a round of lom_match_align_batch holds at most r problems (0 = as
                                                     many as are resident together): lets the tests force several rounds */
+    LOM_OPT_TEST_QUALITY_ROUND_MAX = 108         /* r > 0: a round of lom_match_quality_batch* holds at most r problems
+                                                    (0 = as many as its byte budget admits) */
 } lom_option;
 int lom_map_set_option(lom_map *m, int option, int64_t value);
 /* diagnostics: LOM_COUNTER_GRID_REDOS = calls of this handle redone with the multi-launch scan after an
@@ -547,6 +549,61 @@ int lom_scan_quality(lom_scan *s, const float *src_xyz, size_t n, size_t stride_
 int lom_scan_quality_device(lom_scan *s, const float *d_src_xyz, size_t n, size_t stride_bytes, const float t[3],
                             const float q_wxyz[4], float max_dist, float min_eig_t, float min_eig_r,
                             lom_quality_report *out, float *d_residual_out_or_null);
+
+/* ---- batched quality report: K (scan, pose) candidates against one keyframe in one call ------------------- */
+/* Scoring many candidate poses -- a lattice around a relocalisation or loop-closure guess, before the few best go to
+ * lom_match_align_batch -- in one call: one host wait whatever K is, device memory bounded whatever K is.
+ * Same definition as the single report: problem i gets one search at its f32 pose as given (not re-normalised; max_dist
+ *   squared in f32), then the evaluation at that pose widened to f64, over the LOM_NQSUMS values in their order.
+ * Clouds: problems may share a cloud (equal pointer, n and stride: the pose-lattice case is one cloud and K poses; the
+ *   host entries upload such a cloud once) and may differ in n, 0 and 1 included.  Every s-th point of a cloud is
+ *   stride_bytes * s and n / s.
+ * Rounds: the call runs as many rounds as a byte budget for a round's records and partial sums asks for (csrc/match.hip
+ *   kQualBatchBudgetBytes); all rounds are enqueued before the host waits, once.  LOM_OPT_TEST_QUALITY_ROUND_MAX caps a
+ *   round's problems for the tests.
+ * Determinism: the bytes of problem i's sums depend only on (map, cloud, n, stride, pose, max_dist, counted or not) --
+ *   not on K, on its place in the batch, on the round size, on what else is in the batch, on map handle versus scan
+ *   context (partitioned or not), or on the call.  Against lom_match_quality the counts are equal and every other sum
+ *   agrees to 1e-12 of its scale; byte equality with the single call is not promised.
+ * Arguments: LOM_ERR_ARG before any work for a NULL handle, count < 0, NULL p or output with count > 0, a problem with
+ *   n > 0 and NULL xyz, a stride that does not hold three aligned floats or n >= 2^31 - 1; count == 0 is valid (best = -1,
+ *   nothing is launched); *best_or_null is left alone on an error.  n == 0 or zero correspondences give all-zero sums
+ *   and an all-zero report, as the single call does.
+ * Isolation as lom_match_align_batch and the single report: buffers of its own; the single align's state, the single
+ *   report's buffers, an armed lom_map_radius_cleanup_after_align and an armed idle hook are neither used nor consumed.
+ *   LOM_OPT_HOST_LM and an attached exchange do not matter here. */
+typedef struct {
+    const float *xyz;          /* host (.._batch) or device (.._batch_device) pointer */
+    size_t n, stride_bytes;
+    float t[3], q_wxyz[4];     /* taken as given, not re-normalised, as lom_match_quality */
+} lom_quality_problem;
+/* the reduced values only: sums_out[i * LOM_NQSUMS + k] for p[i] */
+int lom_match_quality_batch_sums(lom_map *m, const lom_quality_problem *p, int count, float max_dist, double *sums_out);
+int lom_match_quality_batch_sums_device(lom_map *m, const lom_quality_problem *p, int count, float max_dist,
+                                        double *sums_out);
+/* full reports: out[i] = lom_quality_from_sums of p[i]'s values; best_or_null: lom_quality_batch_best(out, count) */
+int lom_match_quality_batch(lom_map *m, const lom_quality_problem *p, int count, float max_dist, float min_eig_t,
+                            float min_eig_r, lom_quality_report *out, int *best_or_null);
+int lom_match_quality_batch_device(lom_map *m, const lom_quality_problem *p, int count, float max_dist, float min_eig_t,
+                                   float min_eig_r, lom_quality_report *out, int *best_or_null);
+int lom_scan_quality_batch_sums(lom_scan *s, const lom_quality_problem *p, int count, float max_dist, double *sums_out);
+int lom_scan_quality_batch_sums_device(lom_scan *s, const lom_quality_problem *p, int count, float max_dist,
+                                       double *sums_out);
+int lom_scan_quality_batch(lom_scan *s, const lom_quality_problem *p, int count, float max_dist, float min_eig_t,
+                           float min_eig_r, lom_quality_report *out, int *best_or_null);
+int lom_scan_quality_batch_device(lom_scan *s, const lom_quality_problem *p, int count, float max_dist, float min_eig_t,
+                                  float min_eig_r, lom_quality_report *out, int *best_or_null);
+/* the best report (host code, no GPU): the most valid; ties go to the lower cost, then to the lower index; a report
+ * with queries == 0 ranks below any other; -1 if count <= 0 or r == NULL */
+int lom_quality_batch_best(const lom_quality_report *r, int count);
+/* The poses of a lattice around `centre` (host code, no GPU).  Along axis a: 2 * floor(half_extent[a] / step[a]) + 1
+ * nodes (a step <= 0 or an extent < step: one node, the centre); translation offsets in the world frame, added in f64 and
+ * rounded once to f32.  Yaw node j: q = yaw_z(j * step_yaw) * centre.q -- a left product about world Z, in f64,
+ * normalised, then rounded to f32.  Order: yaw outermost, then x, y, and z innermost, each ascending from the negative
+ * end.  Returns the number of nodes; with out == NULL or cap too small nothing is written and the number is still
+ * returned.  LOM_ERR_ARG for a NULL centre, a non-finite input, an all-zero quaternion or more than 2^31 - 1 nodes. */
+int lom_pose_lattice(const lom_pose *centre, const float half_extent_xyz[3], const float step_xyz[3],
+                     float half_extent_yaw_rad, float step_yaw_rad, lom_pose *out, int cap);
 
 /* ---- multi-GPU: source points range-sharded, map replicated ------------- */
 /* One all-gather of LOM_NSUMS f64 per residual evaluation over RCCL, summed in

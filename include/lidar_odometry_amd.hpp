@@ -317,6 +317,23 @@ private:
 // 6x6 covariance in nav_msgs order (row-major; zeros with covariance_valid == 0 where the geometry is degenerate)
 using QualityReport = lom_quality_report;
 
+// lom_pose_lattice: the poses of a lattice around `centre` -- per axis 2 * floor(half_extent / step) + 1 nodes (one where
+// the step is <= 0 or the extent below it), translation offsets in the world frame, yaw about world Z from the left;
+// order: yaw outermost, then x, y, and z innermost, each ascending
+inline std::vector<Pose3D> poseLattice(const Pose3D &centre, const Vector3f &half_extent_xyz, const Vector3f &step_xyz,
+                                       float half_extent_yaw_rad = 0.f, float step_yaw_rad = 0.f)
+{
+    const lom_pose c = centre.c();
+    const int n = lom_pose_lattice(&c, half_extent_xyz.v, step_xyz.v, half_extent_yaw_rad, step_yaw_rad, nullptr, 0);
+    if (n < 0) throw Error(n, "poseLattice: non-finite input or too many nodes");
+    std::vector<lom_pose> raw((size_t)n);
+    lom_pose_lattice(&c, half_extent_xyz.v, step_xyz.v, half_extent_yaw_rad, step_yaw_rad, raw.data(), n);
+    std::vector<Pose3D> out;
+    out.reserve(raw.size());
+    for (const lom_pose &p : raw) out.push_back(Pose3D::from(p));
+    return out;
+}
+
 // ---- CloudMatcher (src/cloud_matcher.h) --------------------------------------------
 class CloudMatcher {
 public:
@@ -337,6 +354,44 @@ public:
                                         max_correspondence_distance, min_eig_t, min_eig_r, &out, res);
         if (rc != LOM_OK) throw Error(rc, lom_scan_last_error(ctx));
         return out;
+    }
+    // K candidates scored in one call (lom_scan_quality_batch on the calling thread's scan context): report i is what
+    // quality(keyframe, *clouds[i], poses[i]) describes; the best candidate's index (most valid correspondences, then
+    // lowest cost) in `best`, -1 for none.  A cloud that appears several times is uploaded once.
+    std::vector<QualityReport> qualityBatch(const VoxelGrid &keyframe, const std::vector<const PointCloud<PointXYZ> *> &clouds,
+                                            const std::vector<Pose3D> &poses, float max_correspondence_distance = 0.3f,
+                                            float min_eig_t = 0.f, float min_eig_r = 0.f)
+    {
+        if (clouds.size() != poses.size()) throw Error(LOM_ERR_ARG, "qualityBatch: one pose per cloud");
+        std::vector<lom_quality_problem> p(clouds.size());
+        for (size_t i = 0; i < clouds.size(); i++) {
+            if (!clouds[i]) throw Error(LOM_ERR_ARG, "qualityBatch: null cloud");
+            const lom_pose g = poses[i].c();
+            p[i].xyz = clouds[i]->points.empty() ? nullptr : &clouds[i]->points.data()->x;
+            p[i].n = clouds[i]->points.size();
+            p[i].stride_bytes = sizeof(PointXYZ);
+            for (int a = 0; a < 3; a++) p[i].t[a] = g.t[a];
+            for (int a = 0; a < 4; a++) p[i].q_wxyz[a] = g.q[a];
+        }
+        std::vector<QualityReport> out(p.size());
+        lom_scan *ctx = keyframe.scan_context();
+        const int rc = lom_scan_quality_batch(ctx, p.data(), (int)p.size(), max_correspondence_distance, min_eig_t, min_eig_r,
+                                              out.data(), &best);
+        if (rc != LOM_OK) throw Error(rc, lom_scan_last_error(ctx));
+        return out;
+    }
+    // one cloud at many poses: the pose-lattice case (see poseLattice)
+    std::vector<QualityReport> qualityBatch(const VoxelGrid &keyframe, const PointCloud<PointXYZ> &cloud,
+                                            const std::vector<Pose3D> &poses, float max_correspondence_distance = 0.3f,
+                                            float min_eig_t = 0.f, float min_eig_r = 0.f)
+    {
+        return qualityBatch(keyframe, std::vector<const PointCloud<PointXYZ> *>(poses.size(), &cloud), poses,
+                            max_correspondence_distance, min_eig_t, min_eig_r);
+    }
+    // lom_quality_batch_best: the most valid, then the lower cost, then the lower index; -1 for none
+    static int bestQuality(const std::vector<QualityReport> &reports)
+    {
+        return lom_quality_batch_best(reports.data(), (int)reports.size());
     }
     Pose3D align(const VoxelGrid &keyframe, const PointCloud<PointXYZ> &planar_cloud, const Pose3D &position_guess)
     {

@@ -15,7 +15,8 @@ from . import capi
 from .capi import LomError  # noqa: F401
 
 __all__ = ["Pose3D", "VoxelGrid", "CloudMatcher", "ScanContext", "LidarOdometry", "transform_points", "pointTimeNormalize",
-           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "LomError", "capi", "quality_report"]
+           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "LomError", "capi", "quality_report",
+           "quality_report_batch", "pose_lattice"]
 
 
 class Pose3D:
@@ -232,6 +233,12 @@ class VoxelGrid:
         """lom_match_quality: see quality_report()."""
         return quality_report(self, xyz, transform, max_correspondence_distance, min_eig_t, min_eig_r, residuals)
 
+    def qualityBatch(self, clouds_or_cloud, poses, max_correspondence_distance=0.3, min_eig_t=0.0, min_eig_r=0.0,
+                     sums_only=False):
+        """lom_match_quality_batch: see quality_report_batch()."""
+        return quality_report_batch(self, clouds_or_cloud, poses, max_correspondence_distance, min_eig_t, min_eig_r,
+                                    sums_only)
+
     def setProfiling(self, period):
         """HIP event pairs around the correspondence launches of every `period`-th align (True = 1, False = 0)."""
         capi.check(capi.lib().lom_map_set_profiling(self._h, int(period)), self._h)
@@ -281,6 +288,12 @@ class ScanContext:
         """lom_scan_quality: see quality_report()."""
         return quality_report(self, xyz, transform, max_correspondence_distance, min_eig_t, min_eig_r, residuals)
 
+    def qualityBatch(self, clouds_or_cloud, poses, max_correspondence_distance=0.3, min_eig_t=0.0, min_eig_r=0.0,
+                     sums_only=False):
+        """lom_scan_quality_batch: see quality_report_batch()."""
+        return quality_report_batch(self, clouds_or_cloud, poses, max_correspondence_distance, min_eig_t, min_eig_r,
+                                    sums_only)
+
 
 def _align_entry(keyframe, name):
     """(function, checker) for a grid or a scan context"""
@@ -312,6 +325,72 @@ def quality_report(keyframe, xyz, transform, max_correspondence_distance=0.3, mi
     if residuals:
         out["residuals"] = res
     return out
+
+
+def quality_problems(items):
+    """A lom_quality_problem array from [(pointer or None, n, stride_bytes, pose), ...] (host or device pointers)."""
+    problems = (capi.QualityProblem * max(len(items), 1))()
+    for p, (ptr, n, stride_bytes, pose) in zip(problems, items):
+        p.xyz = ptr
+        p.n = int(n)
+        p.stride_bytes = int(stride_bytes)
+        p.t[:] = [float(v) for v in np.asarray(pose.translation, np.float32)]
+        p.q_wxyz[:] = [float(v) for v in np.asarray(pose.rotation, np.float32)]
+    return problems
+
+
+def quality_report_batch(keyframe, clouds_or_cloud, poses, max_correspondence_distance=0.3, min_eig_t=0.0, min_eig_r=0.0,
+                         sums_only=False, raw=False):
+    """quality_report() for K candidates in ONE call (lom_match_quality_batch): one host wait whatever K is.
+    `clouds_or_cloud`: one (n, 3) array scored at every pose of `poses` (the pose-lattice case: uploaded once), or a list
+    of K arrays, one per pose (an array that appears several times is uploaded once).  Returns (reports, best): a list of
+    K dicts as quality_report() returns them (raw=True: the ctypes array) and the index of the best candidate -- most
+    valid correspondences, then lowest cost; -1 for K == 0.  sums_only=True: the (K, 36) array of the reduced values
+    instead of the reports (lom_match_quality_batch_sums), best from them.  `keyframe`: a VoxelGrid or a ScanContext."""
+    if isinstance(clouds_or_cloud, np.ndarray) and clouds_or_cloud.ndim == 2:
+        one = capi.xyz_array(clouds_or_cloud)
+        arrays = [one] * len(poses)
+    else:
+        if len(clouds_or_cloud) != len(poses):
+            raise ValueError("one pose per cloud")
+        arrays = [c if isinstance(c, np.ndarray) and c.dtype == np.float32 and c.ndim == 2 and c.shape[1] == 3 and
+                  c.flags.c_contiguous else capi.xyz_array(c) for c in clouds_or_cloud]
+    count = len(arrays)
+    problems = quality_problems([(a.ctypes.data if len(a) else None, len(a), 12, g) for a, g in zip(arrays, poses)])
+    if sums_only:
+        sums = np.zeros((count, capi.NQSUMS), np.float64)
+        fn, chk = _align_entry(keyframe, "quality_batch_sums")
+        chk(fn(keyframe.handle, problems if count else None, count, float(max_correspondence_distance),
+               sums.ctypes.data_as(C.POINTER(C.c_double)) if count else None))
+        reps = (capi.QualityReport * max(count, 1))()
+        for i in range(count):
+            capi.check(capi.lib().lom_quality_from_sums(sums[i].ctypes.data_as(C.POINTER(C.c_double)), len(arrays[i]), 0.0,
+                                                        0.0, C.byref(reps[i])))
+        return sums, int(capi.lib().lom_quality_batch_best(reps, count))
+    reps = (capi.QualityReport * max(count, 1))()
+    best = C.c_int(-1)
+    fn, chk = _align_entry(keyframe, "quality_batch")
+    chk(fn(keyframe.handle, problems if count else None, count, float(max_correspondence_distance), float(min_eig_t),
+           float(min_eig_r), reps if count else None, C.byref(best)))
+    del arrays
+    if raw:
+        return reps, best.value
+    return [reps[i].asdict() for i in range(count)], best.value
+
+
+def pose_lattice(centre, half_extent_xyz, step_xyz, half_extent_yaw=0.0, step_yaw=0.0):
+    """lom_pose_lattice: the poses of a lattice around `centre` -- per axis 2 * floor(half_extent / step) + 1 nodes (one
+    where the step is <= 0 or the extent below it), translation offsets in the world frame, yaw about world Z applied
+    from the left (radians); order: yaw outermost, then x, y, and z innermost, each ascending."""
+    L = capi.lib()
+    c = centre._c()
+    he, st = capi.f3(half_extent_xyz), capi.f3(step_xyz)
+    n = L.lom_pose_lattice(C.byref(c), he, st, float(half_extent_yaw), float(step_yaw), None, 0)
+    if n < 0:
+        raise LomError(int(n), "lom_pose_lattice")
+    out = (capi.Pose * max(n, 1))()
+    capi.check(L.lom_pose_lattice(C.byref(c), he, st, float(half_extent_yaw), float(step_yaw), out, n))
+    return [Pose3D._from(out[i]) for i in range(n)]
 
 
 def align_repeat(keyframe, d_src_ptr, n, position_guess, reps, stride_bytes=12):
@@ -459,6 +538,13 @@ class CloudMatcher:
                 residuals=False):
         """The quality report of `pose` (e.g. what align() returned) for this cloud and keyframe: quality_report()."""
         return quality_report(keyframe, planar_cloud, pose, max_correspondence_distance, min_eig_t, min_eig_r, residuals)
+
+    def qualityBatch(self, keyframe, clouds_or_cloud, poses, max_correspondence_distance=0.3, min_eig_t=0.0,
+                     min_eig_r=0.0, sums_only=False):
+        """K candidate poses scored in one call: quality_report_batch(); the best candidate's index also in `best`."""
+        out, self.best = quality_report_batch(keyframe, clouds_or_cloud, poses, max_correspondence_distance, min_eig_t,
+                                              min_eig_r, sums_only)
+        return out, self.best
 
     def alignDevice(self, keyframe, d_src_ptr, n, position_guess, stride_bytes=12):
         """Source cloud already resident in HBM (device pointer, e.g. torch tensor.data_ptr())."""

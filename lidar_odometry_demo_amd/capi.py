@@ -103,6 +103,12 @@ class QualityReport(C.Structure):
         return out
 
 
+class QualityProblem(C.Structure):
+    """lom_quality_problem"""
+    _fields_ = [("xyz", C.c_void_p), ("n", C.c_size_t), ("stride_bytes", C.c_size_t), ("t", C.c_float * 3),
+                ("q_wxyz", C.c_float * 4)]
+
+
 # lidar_point::PointXYZIRT (src/lidar_point_type.h:13-21), 32 bytes
 POINT_XYZIRT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad0", "<f4"), ("intensity", "<f4"),
                          ("ring", "<u2"), ("pad1", "<u2"), ("time", "<f4"), ("pad2", "<f4")])
@@ -178,6 +184,9 @@ EXPORTED = [
     "lom_align_batch_best", "lom_match_align_multi", "lom_match_align_multi_device", "lom_odometry_process_batch",
     "lom_quality_from_sums", "lom_match_quality", "lom_match_quality_device", "lom_scan_quality", "lom_scan_quality_device",
     "lom_odometry_set_quality_thresholds", "lom_odometry_get_quality",
+    "lom_match_quality_batch_sums", "lom_match_quality_batch_sums_device", "lom_match_quality_batch",
+    "lom_match_quality_batch_device", "lom_scan_quality_batch_sums", "lom_scan_quality_batch_sums_device",
+    "lom_scan_quality_batch", "lom_scan_quality_batch_device", "lom_quality_batch_best", "lom_pose_lattice",
 ]
 
 # lom_option / counters of include/lidar_odometry_amd.h
@@ -185,6 +194,7 @@ OPT_HOST_LM, OPT_DEVICE_PATIENCE_TICKS, OPT_DEBUG_LM_STAMPS, OPT_DEBUG_TIMING, O
 OPT_TEST_GIVE_UP_AT_OUTER, OPT_TEST_GRID_GIVE_UP, OPT_TEST_FORCE_HOST_REDO = 100, 101, 102
 OPT_NO_BULK_INSERT, OPT_TEST_BULK_PARTITION_MAX = 7, 106
 OPT_TEST_BATCH_ROUND_MAX = 107
+OPT_TEST_QUALITY_ROUND_MAX = 108
 OPT_QUALITY_REPORT = 8
 OPT_TEST_GRID_GIVE_UP_MATCHING_DS, OPT_TEST_GRID_GIVE_UP_UPDATE_DS, OPT_TEST_GRID_GIVE_UP_KEYFRAME = 103, 104, 105
 COUNTER_GRID_REDOS = 0
@@ -397,6 +407,17 @@ def lib():
     L.lom_match_quality_device.argtypes = L.lom_match_quality.argtypes
     L.lom_scan_quality.argtypes = L.lom_match_quality.argtypes
     L.lom_scan_quality_device.argtypes = L.lom_match_quality.argtypes
+    L.lom_match_quality_batch_sums.argtypes = [vp, C.POINTER(QualityProblem), C.c_int, C.c_float, dp]
+    L.lom_match_quality_batch_sums_device.argtypes = L.lom_match_quality_batch_sums.argtypes
+    L.lom_scan_quality_batch_sums.argtypes = L.lom_match_quality_batch_sums.argtypes
+    L.lom_scan_quality_batch_sums_device.argtypes = L.lom_match_quality_batch_sums.argtypes
+    L.lom_match_quality_batch.argtypes = [vp, C.POINTER(QualityProblem), C.c_int, C.c_float, C.c_float, C.c_float,
+                                          C.POINTER(QualityReport), C.POINTER(C.c_int)]
+    L.lom_match_quality_batch_device.argtypes = L.lom_match_quality_batch.argtypes
+    L.lom_scan_quality_batch.argtypes = L.lom_match_quality_batch.argtypes
+    L.lom_scan_quality_batch_device.argtypes = L.lom_match_quality_batch.argtypes
+    L.lom_quality_batch_best.argtypes = [C.POINTER(QualityReport), C.c_int]
+    L.lom_pose_lattice.argtypes = [pp, fp, fp, C.c_float, C.c_float, pp, C.c_int]
     L.lom_odometry_set_quality_thresholds.argtypes = [vp, C.c_float, C.c_float]
     L.lom_odometry_get_quality.argtypes = [vp, C.POINTER(QualityReport)]
     _lib = L

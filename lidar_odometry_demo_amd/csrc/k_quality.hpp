@@ -1,4 +1,5 @@
-// Quality report of a pose: k_quality and k_quality_sum (see match.hip "quality report").  Device code only; match.hip
+// Quality report of a pose: k_quality and k_quality_sum, and their K-problem forms k_quality_batch and k_quality_batch_sum
+// (see match.hip "quality report" and "batched quality report").  Device code only; match.hip
 // is the one translation unit that instantiates and launches it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -70,6 +71,54 @@ __device__ __forceinline__ void quality_point(const float4 ra, const float4 rb, 
 }
 #pragma clang fp contract(off)
 
+// k_quality's fold of a workgroup's values into its record, for the batch form (k_quality itself keeps the code it was
+// verified with, statement for statement the same: inlining this function there reschedules its epilogue): half-wave
+// (k = tid / 32) takes value pass * kQualRows + k -- lane j adds the lanes' entries j, j + 32, ... in order, then the 32
+// partial results fold in a fixed butterfly.
+__device__ __forceinline__ void quality_block_reduce(const double (&acc)[kQualSums], double *__restrict__ s_red,
+                                                     double *__restrict__ out_rec, uint32_t block)
+{
+    const int tid = threadIdx.x, k = tid >> 5, j = tid & 31;
+#pragma unroll
+    for (int pass = 0; pass < kQualSums / kQualRows; pass++) {
+        if (pass) __syncthreads();  // the previous pass's reads are done
+#pragma unroll
+        for (int a = 0; a < kQualRows; a++) s_red[a * kAccStride + tid] = acc[pass * kQualRows + a];
+        __syncthreads();
+        if (k < kQualRows) {
+            const bool is_max = pass * kQualRows + k == kQualMaxSlot;
+            const double *row = s_red + k * kAccStride + j;
+            double v = 0.0;
+#pragma unroll 8
+            for (int i = 0; i < kEvalThreads / 32; i++) {
+                const double x = row[i * 32];
+                v = is_max ? fmax(v, x) : v + x;
+            }
+#pragma unroll
+            for (int d = 16; d >= 1; d >>= 1) {
+                const double x = __shfl_xor(v, d, 32);
+                v = is_max ? fmax(v, x) : v + x;
+            }
+            if (j == 0) out_rec[(size_t)block * kQualSums + pass * kQualRows + k] = v;
+        }
+    }
+}
+
+// lane k < kQualSums: the workgroups' records in workgroup order -> total k
+__device__ __forceinline__ void quality_sum_records(const double *__restrict__ rec, uint32_t n_rec,
+                                                    double *__restrict__ out)
+{
+    const int k = threadIdx.x;
+    if (k >= kQualSums) return;
+    const bool is_max = k == kQualMaxSlot;
+    double v = 0.0;
+    for (uint32_t b = 0; b < n_rec; b++) {
+        const double x = rec[(size_t)b * kQualSums + k];
+        v = is_max ? fmax(v, x) : v + x;
+    }
+    out[k] = v;
+}
+
 // residual_out: n floats or nullptr.  ONE instantiation serves both: the report's bytes must not depend on whether the
 // caller asked for the residuals, and two instantiations need not contract and order their f64 arithmetic alike.
 __global__ __launch_bounds__(kEvalThreads) void k_quality(const MatchRec *__restrict__ rec, uint32_t n, EvalArgs E,
@@ -117,15 +166,54 @@ __global__ __launch_bounds__(kEvalThreads) void k_quality(const MatchRec *__rest
 __global__ __launch_bounds__(64) void k_quality_sum(const double *__restrict__ rec, uint32_t n_rec,
                                                     double *__restrict__ out)
 {
-    const int k = threadIdx.x;
-    if (k >= kQualSums) return;
-    const bool is_max = k == kQualMaxSlot;
-    double v = 0.0;
-    for (uint32_t b = 0; b < n_rec; b++) {
-        const double x = rec[(size_t)b * kQualSums + k];
-        v = is_max ? fmax(v, x) : v + x;
+    quality_sum_records(rec, n_rec, out);
+}
+
+// ---------------------------------------------------------------------------
+// Batched form (lom_match_quality_batch*): K (scan, pose) problems of a round in one launch each of the search (the
+// batch form of k_match, whose pose comes from a per-problem AlignState the host filled), the evaluation and the sum.
+// blockIdx.y is the problem's place in the round; a problem keeps the evaluation grid the single report gives it
+// (eval_grid(n) workgroups, the launch is sized for the round's largest and the others' surplus workgroups leave at
+// once), so which lane sees which record and every reduction order depend on the problem's n alone: its totals do not
+// depend on what else is in the batch, on the round size or on the problem's place.  No per-point residuals here.
+// ---------------------------------------------------------------------------
+struct QualBatchProblem {
+    const MatchRec *rec;  // the records its search left
+    double *part;         // `grid` workgroup records of kQualSums doubles
+    double *out;          // its kQualSums totals
+    uint32_t n, grid;
+    EvalArgs E;
+};
+typedef const __attribute__((address_space(4))) QualBatchProblem *ConstQualBatch;  // scalar loads, like kernel arguments
+
+__global__ __launch_bounds__(kEvalThreads) void k_quality_batch(const QualBatchProblem *batch)
+{
+    __shared__ __attribute__((aligned(16))) double s_red[kQualRows * kAccStride];
+    const ConstQualBatch d = (ConstQualBatch)(batch + blockIdx.y);
+    const uint32_t grid = d->grid, n = d->n;
+    if (blockIdx.x >= grid) return;
+    const MatchRec *__restrict__ rec = d->rec;
+    EvalArgs E;
+#pragma unroll
+    for (int a = 0; a < 4; a++) E.q[a] = d->E.q[a];
+#pragma unroll
+    for (int a = 0; a < 3; a++) E.t[a] = d->E.t[a];
+    double acc[kQualSums];
+#pragma unroll
+    for (int k = 0; k < kQualSums; k++) acc[k] = 0.0;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += grid * blockDim.x) {
+        const float4 *r4 = reinterpret_cast<const float4 *>(rec + i);
+        const float4 ra = r4[0], rb = r4[1], rc = r4[2];
+        quality_point(ra, rb, rc, E, acc, nullptr, i);
     }
-    out[k] = v;
+    quality_block_reduce(acc, s_red, d->part, blockIdx.x);
+}
+
+// one wave per problem: its workgroups' records in workgroup order -> its totals in HBM (one copy per call fetches all)
+__global__ __launch_bounds__(64) void k_quality_batch_sum(const QualBatchProblem *batch)
+{
+    const ConstQualBatch d = (ConstQualBatch)(batch + blockIdx.x);
+    quality_sum_records(d->part, d->grid, d->out);
 }
 
 }  // namespace lom

@@ -245,6 +245,13 @@ struct lom_map {
     // pinned host memory; neither the single align's buffers nor the map-maintenance scratch (scr[]) are touched
     lom::DeviceBuf qual_src, qual_idx, qual_rec, qual_cnt, qual_part, qual_res;
     double *h_qual = nullptr, *d_qual = nullptr;  // LOM_NQSUMS doubles
+    // batched quality report (lom_match_quality_batch*): again buffers of its own -- uploaded host clouds, one round's
+    // records / k_match counters / workgroup records, the per-problem poses and descriptors, the per-problem totals --
+    // and a pinned host block that stages the descriptors on the way in and the totals on the way out
+    lom::DeviceBuf qualb_src, qualb_rec, qualb_cnt, qualb_part, qualb_dev, qualb_sums;
+    void *h_qualb = nullptr;
+    size_t h_qualb_bytes = 0;
+    int test_quality_round_max = 0;  // LOM_OPT_TEST_QUALITY_ROUND_MAX: problems per round at most (0: by the byte budget)
     // lom_match_align_multi: recorded on this handle's stream -- as a problem map, for the runner to wait on before the
     // chain; as the runner, after the chain, for the problem maps to wait on (created once, timing disabled)
     hipEvent_t multi_ev = nullptr;

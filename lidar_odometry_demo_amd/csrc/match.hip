@@ -22,6 +22,8 @@
 //
 //   k_quality the quality report of a pose (lom_match_quality*): one more evaluation over a search's records -- the
 //             align's 28 sums plus weights, residual statistics and counts -- reduced in a fixed order.
+//             k_quality_batch / k_quality_batch_sum: the same for the K (scan, pose) problems of a round of
+//             lom_match_quality_batch*, blockIdx.y the problem, behind the batch form of k_match.
 //
 // The kernels live in k_match.hpp, k_eval.hpp, k_lm.hpp and k_quality.hpp; this file is the one translation unit that instantiates
 // and launches them: the kernel tables, the chained single and batched align, the host-driven path, the C entry points.
@@ -1683,6 +1685,236 @@ int lom_match_quality_device(lom_map *m, const float *d_src, size_t n, size_t st
                              lom_quality_report *out, float *d_residual_out)
 {
     return quality_core(m, d_src, true, n, stride, t, q, max_dist, min_eig_t, min_eig_r, out, d_residual_out);
+}
+
+// ---------------------------------------------------------------------------
+// Batched quality report (lom_match_quality_batch* / lom_scan_quality_batch*): K (scan, pose) problems against this
+// keyframe, three launches per ROUND -- the batch form of k_match (blockIdx.y = the problem; its pose comes from a
+// per-problem AlignState block the host fills: the chained batch instantiation the batched align's first search uses, as
+// it is), k_quality_batch, k_quality_batch_sum -- every round enqueued before the host waits, once.
+// Same answers whatever the batch: a problem searches and evaluates with the grids the single report gives it
+//   (match_grid / eval_grid of its n), so its totals depend on the problem alone -- see k_quality.hpp.
+// Rounds.  A round's records (48 B per point), workgroup records and k_match counters fit kQualBatchBudgetBytes (a
+//   problem larger than that runs alone); problems go to rounds in the caller's order; the round buffers are reused by
+//   the next round, which the stream orders behind this one.  What grows with K is small: a pose block and two
+//   descriptors (about 0.6 KB) and LOM_NQSUMS totals per problem.  LOM_OPT_TEST_QUALITY_ROUND_MAX caps a round's problems too.
+//   64 MiB: a quarter of the 256 MiB last-level cache, so what a round's search writes is still on the chip when its
+//   evaluation reads it; 46 problems of a 28,800-point scan or 700 of a 1,900-point one -- several times the
+//   workgroups the device has compute units for -- so that more per round would buy nothing.
+// Clouds.  The host entries upload every distinct (pointer, n, stride) once, before the first round.
+// Isolation.  lom_map::qualb_*: nothing of the single align, the single report, an armed cleanup scan or idle hook, or the
+//   map-maintenance scratch is read or written; neither call_seq nor mutations move.
+// ---------------------------------------------------------------------------
+constexpr size_t kQualBatchBudgetBytes = (size_t)64 << 20;
+constexpr int kQualBatchRoundCap = 32768;  // problems per round at most (blockIdx.y)
+
+static int quality_batch_args_ok(const lom_map *m, const lom_quality_problem *p, int count, const void *out)
+{
+    if (!m || count < 0) return 0;
+    if (count > 0 && (!p || !out)) return 0;
+    for (int i = 0; i < count; i++)
+        if ((p[i].n && !p[i].xyz) || !scan_args_ok(p[i].n, p[i].stride_bytes)) return 0;
+    return 1;
+}
+
+// sums_out: count * LOM_NQSUMS doubles.  Arguments are checked by the caller.
+static int quality_batch_core(lom_map *m, const lom_quality_problem *p, int count, bool device_input, float max_dist,
+                              double *sums_out)
+{
+    std::vector<int> live;  // the problems with points, in the caller's order
+    for (int i = 0; i < count; i++)
+        if (p[i].n) live.push_back(i);
+    if (live.empty()) {
+        if (count) std::memset(sums_out, 0, (size_t)count * LOM_NQSUMS * 8);
+        return LOM_OK;
+    }
+    LOM_HIP(m, hipSetDevice(m->device));
+    m->last_error.clear();
+    int rc = resolve_pending(m);  // an insert nobody has looked at since: the search must see its points
+    if (rc != LOM_OK) return rc;
+    const int L = (int)live.size();
+    const uint32_t part_cus = m->stream == m->own_stream ? m->partition_cus : 0u;
+    // host clouds: every distinct (pointer, n, stride) once
+    std::vector<const char *> d_src(L);
+    if (device_input) {
+        for (int j = 0; j < L; j++) d_src[j] = (const char *)p[live[j]].xyz;
+    } else {
+        struct Cloud {
+            const float *xyz;
+            size_t n, stride, off;
+        };
+        std::vector<Cloud> clouds;
+        std::vector<int> cloud_of(L);
+        size_t src_bytes = 0;
+        for (int j = 0; j < L; j++) {
+            const lom_quality_problem &q = p[live[j]];
+            size_t c = 0;
+            // (the pose-lattice case hits its cloud at once: the newest is looked at first)
+            for (c = clouds.size(); c-- > 0;)
+                if (clouds[c].xyz == q.xyz && clouds[c].n == q.n && clouds[c].stride == q.stride_bytes) break;
+            if (c == (size_t)-1) {
+                c = clouds.size();
+                clouds.push_back(Cloud{q.xyz, q.n, q.stride_bytes, src_bytes});
+                src_bytes += round_up256((q.n - 1) * q.stride_bytes + 12);
+            }
+            cloud_of[j] = (int)c;
+        }
+        if ((rc = ensure(m, m->qualb_src, src_bytes)) != LOM_OK) return rc;
+        for (const Cloud &c : clouds)
+            LOM_HIP(m, hipMemcpyAsync((char *)m->qualb_src.p + c.off, c.xyz, (c.n - 1) * c.stride + 12,
+                                      hipMemcpyHostToDevice, m->stream));
+        for (int j = 0; j < L; j++) d_src[j] = (const char *)m->qualb_src.p + clouds[cloud_of[j]].off;
+    }
+    // rounds, and where a problem's records, counters and workgroup records lie in its round's buffers
+    struct Round {
+        int first, size;
+        uint32_t mb, nb;  // the launches' x extent: the largest search / evaluation grid of its problems
+    };
+    std::vector<Round> rounds;
+    std::vector<uint32_t> mb(L), nb(L);
+    std::vector<size_t> off_rec(L), off_cnt(L), off_part(L);
+    size_t rec_bytes = 0, cnt_bytes = 0, part_bytes = 0;
+    {
+        const int cap = m->test_quality_round_max > 0 ? std::min(m->test_quality_round_max, kQualBatchRoundCap) : kQualBatchRoundCap;
+        size_t r_rec = 0, r_cnt = 0, r_part = 0;
+        for (int j = 0; j < L; j++) {
+            const uint32_t n = (uint32_t)p[live[j]].n;
+            mb[j] = match_grid(n, part_cus);
+            nb[j] = eval_grid(n);
+            const size_t b_rec = round_up256((size_t)n * sizeof(MatchRec)), b_cnt = round_up256((size_t)mb[j] * 16),
+                         b_part = round_up256((size_t)nb[j] * kQualSums * 8);
+            const bool open = !rounds.empty() && rounds.back().size < cap &&
+                              r_rec + r_cnt + r_part + b_rec + b_cnt + b_part <= kQualBatchBudgetBytes;
+            if (!open) {
+                rounds.push_back(Round{j, 0, 0u, 0u});
+                r_rec = r_cnt = r_part = 0;
+            }
+            Round &R = rounds.back();
+            R.size++;
+            R.mb = std::max(R.mb, mb[j]);
+            R.nb = std::max(R.nb, nb[j]);
+            off_rec[j] = r_rec;
+            off_cnt[j] = r_cnt;
+            off_part[j] = r_part;
+            r_rec += b_rec;
+            r_cnt += b_cnt;
+            r_part += b_part;
+            rec_bytes = std::max(rec_bytes, r_rec);
+            cnt_bytes = std::max(cnt_bytes, r_cnt);
+            part_bytes = std::max(part_bytes, r_part);
+        }
+    }
+    const size_t states_bytes = round_up256((size_t)L * sizeof(AlignState));
+    const size_t match_desc_bytes = round_up256((size_t)L * sizeof(BatchProblem));
+    const size_t dev_bytes = states_bytes + match_desc_bytes + round_up256((size_t)L * sizeof(QualBatchProblem));
+    const size_t sums_bytes = (size_t)L * LOM_NQSUMS * 8;
+    if ((rc = ensure(m, m->qualb_rec, rec_bytes)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qualb_cnt, cnt_bytes)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qualb_part, part_bytes)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qualb_dev, dev_bytes)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qualb_sums, sums_bytes)) != LOM_OK) return rc;
+    if (m->h_qualb_bytes < dev_bytes + sums_bytes) {
+        LOM_HIP(m, hipStreamSynchronize(m->stream));  // (the uploads above do not read it)
+        if (m->h_qualb) LOM_HIP(m, hipHostFree(m->h_qualb));
+        m->h_qualb = nullptr;
+        m->h_qualb_bytes = 0;
+        const size_t bytes = std::max(dev_bytes + sums_bytes, (size_t)65536);
+        hipError_t e = hipHostMalloc(&m->h_qualb, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) return set_error(m, LOM_ERR_OOM, "hipHostMalloc(quality batch staging)", e);
+        m->h_qualb_bytes = bytes;
+    }
+    // per problem: the pose block the search reads, the search's descriptor, the evaluation's descriptor
+    AlignState *h_states = reinterpret_cast<AlignState *>(m->h_qualb);
+    BatchProblem *h_match = reinterpret_cast<BatchProblem *>((char *)m->h_qualb + states_bytes);
+    QualBatchProblem *h_eval = reinterpret_cast<QualBatchProblem *>((char *)m->h_qualb + states_bytes + match_desc_bytes);
+    double *h_sums = reinterpret_cast<double *>((char *)m->h_qualb + dev_bytes);
+    AlignState *d_states = reinterpret_cast<AlignState *>(m->qualb_dev.p);
+    const BatchProblem *d_match = reinterpret_cast<const BatchProblem *>((char *)m->qualb_dev.p + states_bytes);
+    const QualBatchProblem *d_eval =
+        reinterpret_cast<const QualBatchProblem *>((char *)m->qualb_dev.p + states_bytes + match_desc_bytes);
+    const MapView view = view_of(m);
+    const float max_sq = sq_f32(max_dist);
+    for (int j = 0; j < L; j++) {
+        const lom_quality_problem &q = p[live[j]];
+        AlignState &st = h_states[j];
+        std::memset(&st, 0, sizeof st);  // (finished = error = 0: the search runs)
+        pose_args(q.t, q.q_wxyz, max_sq, st.P);
+        BatchProblem &d = h_match[j];
+        std::memset(&d, 0, sizeof d);
+        d.map = view;
+        d.src = d_src[j];
+        d.stride = q.stride_bytes;
+        d.rec = reinterpret_cast<MatchRec *>((char *)m->qualb_rec.p + off_rec[j]);
+        d.block_counters = reinterpret_cast<uint32_t *>((char *)m->qualb_cnt.p + off_cnt[j]);
+        d.state = d_states + j;
+        d.n = (uint32_t)q.n;
+        d.match_blocks = mb[j];
+        QualBatchProblem &e = h_eval[j];
+        std::memset(&e, 0, sizeof e);
+        e.rec = d.rec;
+        e.part = reinterpret_cast<double *>((char *)m->qualb_part.p + off_part[j]);
+        e.out = (double *)m->qualb_sums.p + (size_t)j * LOM_NQSUMS;
+        e.n = d.n;
+        e.grid = nb[j];
+        for (int a = 0; a < 4; a++) e.E.q[a] = (double)q.q_wxyz[a];
+        for (int a = 0; a < 3; a++) e.E.t[a] = (double)q.t[a];
+    }
+    LOM_HIP(m, hipMemcpyAsync(m->qualb_dev.p, m->h_qualb, dev_bytes, hipMemcpyHostToDevice, m->stream));
+    PoseArgs P0;
+    std::memset(&P0, 0, sizeof P0);
+    for (const Round &R : rounds) {
+        hipLaunchKernelGGL(match_kernel(true, false, m->opt_count, true), dim3(R.mb, R.size), dim3(kMatchThreads), 0, m->stream,
+                           MapView{}, (const char *)nullptr, (size_t)0, 0u, P0, (int32_t *)nullptr, (MatchRec *)nullptr,
+                           (QStat *)nullptr, (uint32_t *)nullptr, (unsigned long long *)nullptr, (const AlignState *)nullptr,
+                           d_match + R.first);
+        hipLaunchKernelGGL(k_quality_batch, dim3(R.nb, R.size), dim3(kEvalThreads), 0, m->stream, d_eval + R.first);
+        hipLaunchKernelGGL(k_quality_batch_sum, dim3(R.size), dim3(64), 0, m->stream, d_eval + R.first);
+        LOM_HIP(m, hipGetLastError());
+    }
+    LOM_HIP(m, hipMemcpyAsync(h_sums, m->qualb_sums.p, sums_bytes, hipMemcpyDeviceToHost, m->stream));
+    LOM_HIP(m, hipStreamSynchronize(m->stream));
+    std::memset(sums_out, 0, (size_t)count * LOM_NQSUMS * 8);
+    for (int j = 0; j < L; j++) std::memcpy(sums_out + (size_t)live[j] * LOM_NQSUMS, h_sums + (size_t)j * LOM_NQSUMS, LOM_NQSUMS * 8);
+    return LOM_OK;
+}
+
+static int quality_batch_reports(lom_map *m, const lom_quality_problem *p, int count, bool device_input, float max_dist,
+                                 float min_eig_t, float min_eig_r, lom_quality_report *out, int *best)
+{
+    if (!quality_batch_args_ok(m, p, count, out)) return LOM_ERR_ARG;
+    std::vector<double> sums((size_t)count * LOM_NQSUMS);
+    int rc = quality_batch_core(m, p, count, device_input, max_dist, sums.data());
+    if (rc != LOM_OK) return rc;
+    for (int i = 0; i < count; i++)
+        if ((rc = lom_quality_from_sums(sums.data() + (size_t)i * LOM_NQSUMS, (int64_t)p[i].n, min_eig_t, min_eig_r, out + i)) != LOM_OK)
+            return rc;
+    if (best) *best = lom_quality_batch_best(out, count);
+    return LOM_OK;
+}
+
+int lom_match_quality_batch_sums(lom_map *m, const lom_quality_problem *p, int count, float max_dist, double *sums_out)
+{
+    if (!quality_batch_args_ok(m, p, count, sums_out)) return LOM_ERR_ARG;
+    return quality_batch_core(m, p, count, false, max_dist, sums_out);
+}
+
+int lom_match_quality_batch_sums_device(lom_map *m, const lom_quality_problem *p, int count, float max_dist,
+                                        double *sums_out)
+{
+    if (!quality_batch_args_ok(m, p, count, sums_out)) return LOM_ERR_ARG;
+    return quality_batch_core(m, p, count, true, max_dist, sums_out);
+}
+
+int lom_match_quality_batch(lom_map *m, const lom_quality_problem *p, int count, float max_dist, float min_eig_t,
+                            float min_eig_r, lom_quality_report *out, int *best)
+{
+    return quality_batch_reports(m, p, count, false, max_dist, min_eig_t, min_eig_r, out, best);
+}
+
+int lom_match_quality_batch_device(lom_map *m, const lom_quality_problem *p, int count, float max_dist, float min_eig_t,
+                                   float min_eig_r, lom_quality_report *out, int *best)
+{
+    return quality_batch_reports(m, p, count, true, max_dist, min_eig_t, min_eig_r, out, best);
 }
 
 // parity entry: a whole align on the device-resident path (k_match / k_lm chain) that also returns what

@@ -162,3 +162,69 @@ extern "C" int lom_quality_from_sums(const double sums[LOM_NQSUMS], int64_t quer
     }
     return LOM_OK;
 }
+
+// the best of a batch: most valid, then lower cost, then lower index; a report of no queries ranks below any other
+extern "C" int lom_quality_batch_best(const lom_quality_report *r, int count)
+{
+    if (!r || count <= 0) return -1;
+    int best = 0;
+    for (int i = 1; i < count; i++) {
+        const lom_quality_report &a = r[i], &b = r[best];
+        const bool a_empty = a.queries == 0, b_empty = b.queries == 0;
+        if (a_empty != b_empty) {
+            if (b_empty) best = i;
+            continue;
+        }
+        if (a.valid > b.valid || (a.valid == b.valid && a.cost < b.cost)) best = i;
+    }
+    return best;
+}
+
+// nodes -k .. k along one axis: k = floor(half_extent / step), 0 where the step is not positive or the extent below it
+static long long lattice_half_nodes(double half_extent, double step)
+{
+    if (!(step > 0.0) || half_extent < step) return 0;
+    return (long long)std::floor(half_extent / step);
+}
+
+extern "C" int lom_pose_lattice(const lom_pose *centre, const float half_extent_xyz[3], const float step_xyz[3],
+                                float half_extent_yaw_rad, float step_yaw_rad, lom_pose *out, int cap)
+{
+    if (!centre || !half_extent_xyz || !step_xyz) return LOM_ERR_ARG;
+    bool finite = std::isfinite(half_extent_yaw_rad) && std::isfinite(step_yaw_rad);
+    for (int a = 0; a < 3; a++)
+        finite = finite && std::isfinite(centre->t[a]) && std::isfinite(half_extent_xyz[a]) && std::isfinite(step_xyz[a]);
+    for (int a = 0; a < 4; a++) finite = finite && std::isfinite(centre->q[a]);
+    if (!finite) return LOM_ERR_ARG;
+    const double cw = (double)centre->q[0], cx = (double)centre->q[1], cy = (double)centre->q[2], cz = (double)centre->q[3];
+    if (!(cw * cw + cx * cx + cy * cy + cz * cz > 0.0)) return LOM_ERR_ARG;  // nothing to normalise
+    long long k[3];
+    const long long ky = lattice_half_nodes((double)half_extent_yaw_rad, (double)step_yaw_rad);
+    double total = (double)(2 * ky + 1);
+    for (int a = 0; a < 3; a++) {
+        k[a] = lattice_half_nodes((double)half_extent_xyz[a], (double)step_xyz[a]);
+        total *= (double)(2 * k[a] + 1);
+    }
+    if (!(total <= 2147483647.0) || ky > (1ll << 30) || k[0] > (1ll << 30) || k[1] > (1ll << 30) || k[2] > (1ll << 30))
+        return LOM_ERR_ARG;
+    const int count = (int)total;
+    if (!out || cap < count) return count;
+    lom_pose *o = out;
+    for (long long jy = -ky; jy <= ky; jy++) {
+        // yaw_z(angle) = (cos(angle / 2), 0, 0, sin(angle / 2)), times the centre's quaternion from the left
+        const double angle = (double)jy * (double)step_yaw_rad;
+        const double w1 = std::cos(0.5 * angle), z1 = std::sin(0.5 * angle);
+        double q[4] = {w1 * cw - z1 * cz, w1 * cx - z1 * cy, w1 * cy + z1 * cx, w1 * cz + z1 * cw};
+        const double norm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+        for (int a = 0; a < 4; a++) q[a] /= norm;
+        for (long long ix = -k[0]; ix <= k[0]; ix++)
+            for (long long iy = -k[1]; iy <= k[1]; iy++)
+                for (long long iz = -k[2]; iz <= k[2]; iz++, o++) {
+                    o->t[0] = (float)((double)centre->t[0] + (double)ix * (double)step_xyz[0]);
+                    o->t[1] = (float)((double)centre->t[1] + (double)iy * (double)step_xyz[1]);
+                    o->t[2] = (float)((double)centre->t[2] + (double)iz * (double)step_xyz[2]);
+                    for (int a = 0; a < 4; a++) o->q[a] = (float)q[a];
+                }
+    }
+    return count;
+}

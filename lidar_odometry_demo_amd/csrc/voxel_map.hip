@@ -2021,6 +2021,26 @@ int lom_scan_quality_device(lom_scan *s, const float *d_src, size_t n, size_t st
     return lom_match_quality_device(reinterpret_cast<lom_map *>(s), d_src, n, stride, t, q, max_dist, min_eig_t,
                                     min_eig_r, out, d_residual_out);
 }
+int lom_scan_quality_batch_sums(lom_scan *s, const lom_quality_problem *p, int count, float max_dist, double *sums_out)
+{
+    return lom_match_quality_batch_sums(reinterpret_cast<lom_map *>(s), p, count, max_dist, sums_out);
+}
+int lom_scan_quality_batch_sums_device(lom_scan *s, const lom_quality_problem *p, int count, float max_dist,
+                                       double *sums_out)
+{
+    return lom_match_quality_batch_sums_device(reinterpret_cast<lom_map *>(s), p, count, max_dist, sums_out);
+}
+int lom_scan_quality_batch(lom_scan *s, const lom_quality_problem *p, int count, float max_dist, float min_eig_t,
+                           float min_eig_r, lom_quality_report *out, int *best)
+{
+    return lom_match_quality_batch(reinterpret_cast<lom_map *>(s), p, count, max_dist, min_eig_t, min_eig_r, out, best);
+}
+int lom_scan_quality_batch_device(lom_scan *s, const lom_quality_problem *p, int count, float max_dist, float min_eig_t,
+                                  float min_eig_r, lom_quality_report *out, int *best)
+{
+    return lom_match_quality_batch_device(reinterpret_cast<lom_map *>(s), p, count, max_dist, min_eig_t, min_eig_r, out,
+                                          best);
+}
 
 int lom_map_create(float voxel_size, size_t max_points, size_t capacity_hint, int device, lom_map **out)
 {
@@ -2102,7 +2122,8 @@ void lom_map_destroy(lom_map *m)
     for (DeviceBuf *b : {&m->scan_src, &m->scan_idx, &m->scan_on, &m->scan_stats, &m->partials, &m->results, &m->gather,
                          &m->align_state, &m->xrec, &m->dbg_trace, &m->dbg_stamps, &m->batch_dev, &m->batch_rec,
                          &m->batch_cnt, &m->batch_xrec, &m->batch_src, &m->qual_src, &m->qual_idx, &m->qual_rec,
-                         &m->qual_cnt, &m->qual_part, &m->qual_res})
+                         &m->qual_cnt, &m->qual_part, &m->qual_res, &m->qualb_src, &m->qualb_rec, &m->qualb_cnt,
+                         &m->qualb_part, &m->qualb_dev, &m->qualb_sums})
         if (b->p) (void)hipFree(b->p);
     if (m->h_results) (void)hipHostFree(m->h_results);
     if (m->h_flags) (void)hipHostFree(m->h_flags);
@@ -2116,6 +2137,7 @@ void lom_map_destroy(lom_map *m)
     if (m->h_batch) (void)hipHostFree(m->h_batch);
     if (m->h_batch_report) (void)hipHostFree(m->h_batch_report);
     if (m->h_qual) (void)hipHostFree(m->h_qual);
+    if (m->h_qualb) (void)hipHostFree(m->h_qualb);
     for (auto &e : m->prof_events)
         if (e) (void)hipEventDestroy(e);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
@@ -2169,6 +2191,10 @@ int lom_map_set_option(lom_map *m, int option, int64_t value)
     case LOM_OPT_TEST_BATCH_ROUND_MAX:
         if (value < 0 || value > (1 << 20)) return LOM_ERR_ARG;
         m->test_batch_round_max = (int)value;
+        return LOM_OK;
+    case LOM_OPT_TEST_QUALITY_ROUND_MAX:
+        if (value < 0 || value > (1 << 20)) return LOM_ERR_ARG;
+        m->test_quality_round_max = (int)value;
         return LOM_OK;
     default: return set_error(m, LOM_ERR_ARG, "unknown option");
     }

@@ -1,0 +1,354 @@
+"""Batched quality report on the device (lom_match_quality_batch* / lom_scan_quality_batch*, csrc/k_quality.hpp
+k_quality_batch / k_quality_batch_sum, csrc/match.hip quality_batch_core) against the oracle and the single call.
+
+* parity: every problem's 28 align sums and `valid` against the oracle's Shard.match_eval at tests/test_eval_parity.py's
+  bar (assert_sums_close: 1e-12 of each sum's scale), the values [28..35] against the numpy restatement from the oracle's
+  correspondences (tests/quality_ref.py) at 1e-12 of their scale, `inliers` exact -- after asserting, for EVERY pose,
+  that no oracle residual lies within 1e-9 of the Huber knee (tests/test_quality_gpu._reference does);
+* against lom_match_quality: counts equal, sums at the same bar;
+* invariance: the BYTES of a problem's sums do not depend on K, its place, the round size, the rest of the batch, map
+  handle versus scan context (partitioned or not), or the call;
+* ragged batches (n = 0, 1, around the lane and workgroup sizes, strided views, a shared cloud, no correspondences, a
+  non-normalised quaternion), host and device entry; several rounds with a ragged last one;
+* isolation: armed cleanup scan and idle hook survive a batch call, the single align and report return the same bytes.
+
+The scenes and their oracle references are tests/test_quality_gpu.py's (computed once per process and shared).  Every
+test runs in the product and the counted search mode."""
+import ctypes as C
+import functools
+import math
+
+import numpy as np
+import pytest
+
+from tests import scenes
+from tests import test_quality_gpu as TQ
+from tests.test_eval_parity import assert_sums_close
+
+pytestmark = pytest.mark.gpu
+REL = 1e-12
+NQ = 36
+
+
+@pytest.fixture(autouse=True, params=["product", "counted"])
+def search_mode(request, monkeypatch):
+    monkeypatch.setenv("LOM_COUNT_CANDIDATES", "1" if request.param == "counted" else "0")
+    return request.param
+
+
+def _oracle_grid(vs, mx, mn):
+    from oracle import oracle as O
+
+    og = O.VoxelGrid(vs, 20)
+    og.addCloud(mx, mn)
+    return O, og
+
+
+@functools.lru_cache(maxsize=None)
+def _lattice_case():
+    """(voxel size, map xyz, map normals, scan, [(t, q)] * 31, [oracle reference] * 31): the four SYNTH_POSES, then the
+    27 lattice nodes around SYNTH_POSES[1]"""
+    import lidar_odometry_demo_amd as lom
+
+    vs, mx, mn, scan, refs4 = TQ._scene("synth")
+    O, og = _oracle_grid(vs, mx, mn)
+    nodes = lom.pose_lattice(lom.Pose3D(*TQ.SYNTH_POSES[1]), (0.25, 0.25, 0.0), (0.25, 0.25, 0.0), math.radians(2.5),
+                             math.radians(2.5))
+    assert len(nodes) == 27
+    refs = list(refs4) + [TQ._reference(O, og, scan, p.translation, p.rotation) for p in nodes]
+    poses = [r["pose"] for r in refs]
+    return vs, mx, mn, scan, poses, refs
+
+
+def _grid(lom, vs, mx, mn):
+    g = lom.VoxelGrid(vs, 20)
+    g.addCloud(mx, mn)
+    return g
+
+
+def _poses(lom, poses):
+    return [lom.Pose3D(t, q) for t, q in poses]
+
+
+def _check_sums(sums, ref, tag):
+    """one problem's LOM_NQSUMS values against its oracle reference"""
+    want = ref["sums"]
+    print(f"{tag}: valid {int(sums[33])}/{int(want[33])} inliers {int(sums[34])}/{int(want[34])} cost {sums[27]!r} "
+          f"oracle {want[27]!r}")
+    got32 = np.zeros(32)
+    got32[:28], got32[28] = sums[:28], sums[33]
+    got32[29:32] = ref["ref32"][29:32]            # (the report carries no candidate counters)
+    assert_sums_close(got32, ref["ref32"], (tag, "oracle"))
+    assert sums[33] == want[33] and sums[34] == want[34], tag
+    for k in (28, 29, 30, 31, 32, 35):            # sums of non-negative terms and a maximum: each to 1e-12 of itself
+        assert abs(sums[k] - want[k]) <= REL * abs(want[k]), (tag, k, sums[k], want[k])
+
+
+def _sums32(d):
+    """a report dict -> the 32-vector assert_sums_close takes (counters beyond `valid` zero)"""
+    out = np.zeros(32)
+    k = 0
+    for a in range(6):
+        for b in range(a, 6):
+            out[k] = d["information"][a, b]
+            k += 1
+    out[21:27], out[27], out[28] = d["gradient"], d["cost"], d["valid"]
+    return out
+
+
+def _raw_sums(lom, keyframe, items, device=False):
+    """lom_{match,scan}_quality_batch_sums[_device] on [(pointer, n, stride, pose), ...] -> (K, 36)"""
+    problems = lom.quality_problems(items)
+    sums = np.full((max(len(items), 1), NQ), 7.0)
+    fn, chk = lom._align_entry(keyframe, "quality_batch_sums_device" if device else "quality_batch_sums")
+    chk(fn(keyframe.handle, problems, len(items), 0.3, sums.ctypes.data_as(C.POINTER(C.c_double))))
+    return sums[:len(items)]
+
+
+# ---- 1. oracle parity on a lattice ------------------------------------------------------------------------------------
+
+def test_lattice_against_oracle(lom):
+    vs, mx, mn, scan, poses, refs = _lattice_case()
+    g = _grid(lom, vs, mx, mn)
+    sums, best = lom.quality_report_batch(g, scan, _poses(lom, poses), 0.3, sums_only=True)
+    assert sums.shape == (31, NQ)
+    for i, ref in enumerate(refs):
+        _check_sums(sums[i], ref, ("lattice", i))
+    rank = [(int(r["sums"][33]), -float(r["sums"][27])) for r in refs]
+    assert len(set(rank[4:])) == 27                      # the lattice's candidates are separated
+    want_best = max(range(31), key=lambda i: (rank[i], -i))
+    assert best == want_best
+    reports, best_r = lom.quality_report_batch(g, scan, _poses(lom, poses), 0.3, 0.05, 1.0)
+    assert best_r == want_best and [d["queries"] for d in reports] == [len(scan)] * 31
+
+
+# ---- 2. against the single call ---------------------------------------------------------------------------------------
+
+def test_batch_against_single_call(lom):
+    vs, mx, mn, scan, poses, refs = _lattice_case()
+    g = _grid(lom, vs, mx, mn)
+    P = _poses(lom, poses)
+    reports, best = lom.quality_report_batch(g, scan, P, 0.3, 0.05, 1.0, raw=True)
+    sums, best_s = lom.quality_report_batch(g, scan, P, 0.3, sums_only=True)
+    assert best == best_s
+    for i, pose in enumerate(P):
+        one = lom.quality_report(g, scan, pose, 0.3, 0.05, 1.0, raw=True)
+        b, s = reports[i].asdict(), one.asdict()
+        assert (b["queries"], b["valid"], b["inliers"]) == (s["queries"], s["valid"], s["inliers"]), i
+        assert_sums_close(_sums32(b), _sums32(s), ("single", i))
+        for k in ("sum_w", "rmse", "rmse_inliers", "mean_sq_dist", "sigma2", "max_abs_residual"):
+            assert abs(b[k] - s[k]) <= REL * abs(s[k]), (i, k, b[k], s[k])
+        # the full-report entry is lom_quality_from_sums on what the sums entry returns
+        again = lom.capi.QualityReport()
+        lom.capi.check(lom.capi.lib().lom_quality_from_sums(sums[i].ctypes.data_as(C.POINTER(C.c_double)), len(scan), 0.05,
+                                                            1.0, C.byref(again)))
+        assert TQ._raw(again) == TQ._raw(reports[i]), i
+
+
+# ---- 3. invariance ----------------------------------------------------------------------------------------------------
+
+def test_bytes_do_not_depend_on_the_batch(lom):
+    vs, mx, mn, scan, poses, refs = _lattice_case()
+    g = _grid(lom, vs, mx, mn)
+    P = _poses(lom, poses)
+    X = 3                                             # SYNTH_POSES[3]: residuals on both sides of the Huber knee
+    whole, _ = lom.quality_report_batch(g, scan, P, 0.3, sums_only=True)
+    want = whole[X].tobytes()
+    alone, _ = lom.quality_report_batch(g, scan, [P[X]], 0.3, sums_only=True)
+    assert alone[0].tobytes() == want
+    for place in (0, 13, 30):                         # the same batch rotated: the pose as problem 0, 13, 30
+        shift = place - X
+        rolled = [P[(i - shift) % 31] for i in range(31)]
+        got, _ = lom.quality_report_batch(g, scan, rolled, 0.3, sums_only=True)
+        assert got[place].tobytes() == want, place
+        assert np.roll(whole, shift, axis=0).tobytes() == got.tobytes(), place
+    rev, _ = lom.quality_report_batch(g, scan, P[::-1], 0.3, sums_only=True)
+    assert rev[30 - X].tobytes() == want and rev[::-1].tobytes() == whole.tobytes()
+    for r in (1, 2, 7):
+        g.setOption(lom.capi.OPT_TEST_QUALITY_ROUND_MAX, r)
+        got, _ = lom.quality_report_batch(g, scan, P, 0.3, sums_only=True)
+        assert got.tobytes() == whole.tobytes(), r
+    g.setOption(lom.capi.OPT_TEST_QUALITY_ROUND_MAX, 0)
+    for ctx in (lom.ScanContext(g), lom.ScanContext(g, partition=(1, 4))):
+        got, _ = ctx.qualityBatch(scan, P, 0.3, sums_only=True)
+        assert got.tobytes() == whole.tobytes()
+        ctx.setOption(lom.capi.OPT_TEST_QUALITY_ROUND_MAX, 7)
+        got, _ = ctx.qualityBatch(scan, P, 0.3, sums_only=True)
+        assert got.tobytes() == whole.tobytes()
+    again, _ = lom.quality_report_batch(g, scan, P, 0.3, sums_only=True)
+    assert again.tobytes() == whole.tobytes()
+    # a list of clouds (the same array K times) is the one-cloud form
+    listed, _ = g.qualityBatch([scan] * 31, P, 0.3, sums_only=True)
+    assert listed.tobytes() == whole.tobytes()
+
+
+# ---- 4. ragged batch --------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _ragged_case():
+    """[(first point, n, stride in points, (t, q), oracle reference or None for n == 0)]"""
+    vs, mx, mn, scan, refs4 = TQ._scene("synth")
+    O, og = _oracle_grid(vs, mx, mn)
+    t1, q1 = TQ.SYNTH_POSES[1]
+    rows = []
+    for n, step in ((0, 1), (1, 1), (15, 1), (17, 3), (511, 1), (513, 3), (1025, 1)):
+        sub = np.ascontiguousarray(scan[::step][:n])
+        assert len(sub) == n
+        rows.append((n, step, (t1, q1), TQ._reference(O, og, sub, t1, q1) if n else None))
+    N = len(scan)
+    rows.append((N, 1, TQ.SYNTH_POSES[0], refs4[0]))          # a shared cloud at two poses ...
+    rows.append((N, 1, TQ.SYNTH_POSES[1], refs4[1]))
+    far = ((500.0, 0.0, 0.0), (1, 0, 0, 0))
+    rows.append((N, 1, far, TQ._reference(O, og, scan, *far)))  # ... 500 m away: no correspondence ...
+    rows.append((N, 1, TQ.SYNTH_POSES[2], refs4[2]))          # ... and at a quaternion that is not normalised
+    return vs, mx, mn, scan, rows
+
+
+def test_ragged_batch_host_and_device(lom):
+    import torch
+
+    vs, mx, mn, scan, rows = _ragged_case()
+    g = _grid(lom, vs, mx, mn)
+    d_scan = torch.from_numpy(scan).cuda()
+    torch.cuda.synchronize()
+    out = {}
+    for device, base in ((False, scan.ctypes.data), (True, d_scan.data_ptr())):
+        items = [(base if n else None, n, 12 * step, lom.Pose3D(t, q)) for n, step, (t, q), _ in rows]
+        out[device] = _raw_sums(lom, g, items, device)
+    assert out[True].tobytes() == out[False].tobytes()
+    sums = out[False]
+    for i, (n, step, _, ref) in enumerate(rows):
+        if ref is None:
+            assert not sums[i].any(), i
+        else:
+            _check_sums(sums[i], ref, ("ragged", i, n, step))
+    assert not sums[9].any() and rows[9][3]["sums"][33] == 0     # the pose 500 m away: all-zero sums
+    assert sums[7, 33] > 0 and sums[8, 33] > 0 and sums[7].tobytes() != sums[8].tobytes()
+    # full reports of the same batch: queries are the problems' n, the empty ones all-zero, best among the full scans
+    problems = lom.quality_problems([(scan.ctypes.data if n else None, n, 12 * step, lom.Pose3D(t, q))
+                                     for n, step, (t, q), _ in rows])
+    reps = (lom.capi.QualityReport * len(rows))()
+    best = C.c_int(-5)
+    L = lom.capi.lib()
+    lom.capi.check(L.lom_match_quality_batch(g.handle, problems, len(rows), 0.3, 0.0, 0.0, reps, C.byref(best)), g.handle)
+    assert [r.queries for r in reps] == [row[0] for row in rows]
+    zero = lom.capi.QualityReport()      # what the single call reports for no points / no correspondences
+    for i in (0, 9):
+        lom.capi.check(L.lom_quality_from_sums((C.c_double * NQ)(), rows[i][0], 0.0, 0.0, C.byref(zero)))
+        assert TQ._raw(reps[i]) == TQ._raw(zero), i
+        assert reps[i].valid == 0 and reps[i].covariance_valid == 0 and not any(reps[i].information), i
+    valid = [int(r.valid) for r in reps]
+    assert best.value == max(range(len(rows)), key=lambda i: (rows[i][0] > 0, valid[i], -reps[i].cost, -i))
+    # count == 0: valid, best = -1, with and without the pointers
+    for p, o in ((None, None), (problems, reps)):
+        best = C.c_int(-5)
+        assert L.lom_match_quality_batch(g.handle, p, 0, 0.3, 0.0, 0.0, o, C.byref(best)) == 0
+        assert best.value == -1
+    assert L.lom_match_quality_batch_sums(g.handle, None, 0, 0.3, None) == 0
+    assert lom.quality_report_batch(g, scan, []) == ([], -1)
+    # a batch of empty problems only
+    got = _raw_sums(lom, g, [(None, 0, 12, lom.Pose3D())] * 3)
+    assert got.shape == (3, NQ) and not got.any()
+
+
+# ---- 5. larger K with rounds ------------------------------------------------------------------------------------------
+
+def test_rounds_with_a_ragged_last_one(lom):
+    vs, mx, mn, scan, refs = TQ._scene("C2")
+    assert len(scan) > 20000            # the VLP16-sized scan (16 x 1800 beams less the misses): some 50 workgroups a problem
+    g = _grid(lom, vs, mx, mn)
+    first, last = lom.Pose3D(*refs[0]["pose"]), lom.Pose3D(*refs[1]["pose"])
+    between = lom.pose_lattice(first, (0.06, 0.0, 0.0), (0.02, 0.0, 0.0))
+    assert len(between) == 7
+    P = [first] + [p for k, p in enumerate(between) if k != 3] + [last]      # (node 3 is the centre again)
+    assert len(P) == 8
+    g.setOption(lom.capi.OPT_TEST_QUALITY_ROUND_MAX, 3)                      # rounds of 3, 3, 2
+    three, _ = lom.quality_report_batch(g, scan, P, 0.3, sums_only=True)
+    g.setOption(lom.capi.OPT_TEST_QUALITY_ROUND_MAX, 0)
+    by_budget, _ = lom.quality_report_batch(g, scan, P, 0.3, sums_only=True)
+    _check_sums(three[0], refs[0], ("C2", 0))
+    _check_sums(three[7], refs[1], ("C2", 7))
+    assert three.tobytes() == by_budget.tobytes()
+    assert len({three[i].tobytes() for i in range(8)}) == 8
+
+
+# ---- 6. isolation -----------------------------------------------------------------------------------------------------
+
+def test_batch_call_leaves_the_handle_as_it_was(lom, oracle):
+    import torch
+
+    vs, mx, mn, scan, poses, refs = _lattice_case()
+    taken = lom.capi.COUNTER_CLEANUPS_BEHIND_ALIGN
+    g = _grid(lom, vs, mx, mn)
+    P = _poses(lom, poses)
+    g.radiusCleanup((0, 0, 0), 1e6)     # sizes the cleanup's scratch, as tests/test_quality_gpu.py does
+    guess = lom.Pose3D((0.05, -0.02, 0.0), scenes.angle_axis_q(0.01, (0, 0, 1)))
+    m = lom.CloudMatcher()
+    pose0 = m.align(g, scan, guess)
+    rep0, res0 = lom.quality_report(g, scan, guess, 0.3, 0.05, 1.0, residuals=True, raw=True)
+    g.radiusCleanupAfterAlign(6.0)
+    sums0, best0 = lom.quality_report_batch(g, scan, P, 0.3, sums_only=True)
+    pose1 = m.align(g, scan, guess)
+    assert pose1.translation.tobytes() == pose0.translation.tobytes() and pose1.rotation.tobytes() == pose0.rotation.tobytes()
+    rep1, res1 = lom.quality_report(g, scan, guess, 0.3, 0.05, 1.0, residuals=True, raw=True)
+    assert TQ._raw(rep1) == TQ._raw(rep0) and res1.tobytes() == res0.tobytes()
+    sums1, best1 = lom.quality_report_batch(g, scan, P, 0.3, sums_only=True)
+    assert sums1.tobytes() == sums0.tobytes() and best1 == best0
+    # the cleanup still takes the scan that ran behind the align
+    before = g.debugCounter(taken)
+    g.radiusCleanup(np.asarray(pose1.translation, np.float32), 6.0)
+    assert g.debugCounter(taken) - before == 1
+    # an idle hook armed for the next align is not consumed by a batch call
+    calls = []
+    HOOK = C.CFUNCTYPE(None, C.c_void_p)
+    hook = HOOK(lambda user: calls.append(1))
+    L = lom.capi.lib()
+    L.lom_map_set_align_idle_hook.argtypes = [C.c_void_p, HOOK, C.c_void_p]
+    assert L.lom_map_set_align_idle_hook(g.handle, hook, None) == 0
+    lom.quality_report_batch(g, scan, P[:5], 0.3)
+    assert calls == []
+    d_scan = torch.from_numpy(scan).cuda()
+    torch.cuda.synchronize()
+    m.alignDevice(g, d_scan.data_ptr(), len(scan), guess)
+    assert calls == [1]
+    L.lom_map_set_align_idle_hook(g.handle, HOOK(), None)
+
+
+# ---- 7. errors --------------------------------------------------------------------------------------------------------
+
+def test_argument_errors_leave_the_outputs_alone(lom):
+    vs, mx, mn, scan, poses, refs = _lattice_case()
+    g = _grid(lom, vs, mx, mn)
+    ctx = lom.ScanContext(g)
+    L = lom.capi.lib()
+    ERR = lom.capi.ERR_ARG
+    good = (scan.ctypes.data, len(scan), 12, lom.Pose3D())
+    bad_batches = {
+        "null xyz with n > 0": [good, (None, 5, 12, lom.Pose3D())],
+        "stride below three floats": [good, (scan.ctypes.data, 5, 8, lom.Pose3D())],
+        "stride not a multiple of four": [(scan.ctypes.data, 5, 14, lom.Pose3D()), good],
+        "too many points": [good, (scan.ctypes.data, 0x7FFFFFFF, 12, lom.Pose3D())],
+    }
+    sums = (C.c_double * (2 * NQ))(*([7.0] * (2 * NQ)))
+    reps = (lom.capi.QualityReport * 2)()
+    reps[0].queries = reps[1].queries = 77
+    best = C.c_int(42)
+    ok = lom.quality_problems([good, good])
+    for kind, h in (("match", g.handle), ("scan", ctx.handle)):
+        for suffix in ("", "_device"):
+            f_sums = getattr(L, f"lom_{kind}_quality_batch_sums{suffix}")
+            f_reps = getattr(L, f"lom_{kind}_quality_batch{suffix}")
+            assert f_sums(h, ok, -1, 0.3, sums) == ERR
+            assert f_sums(h, None, 2, 0.3, sums) == ERR
+            assert f_sums(h, ok, 2, 0.3, None) == ERR
+            assert f_reps(h, ok, -1, 0.3, 0.0, 0.0, reps, C.byref(best)) == ERR
+            assert f_reps(h, None, 2, 0.3, 0.0, 0.0, reps, C.byref(best)) == ERR
+            assert f_reps(h, ok, 2, 0.3, 0.0, 0.0, None, C.byref(best)) == ERR
+            for what, items in bad_batches.items():
+                p = lom.quality_problems(items)
+                assert f_sums(h, p, 2, 0.3, sums) == ERR, (kind, suffix, what)
+                assert f_reps(h, p, 2, 0.3, 0.0, 0.0, reps, C.byref(best)) == ERR, (kind, suffix, what)
+    assert list(sums) == [7.0] * (2 * NQ) and reps[0].queries == 77 and reps[1].queries == 77 and best.value == 42
+    # and the handle still works
+    got, _ = lom.quality_report_batch(g, scan, [lom.Pose3D(*poses[1])], 0.3, sums_only=True)
+    _check_sums(got[0], refs[1], "after errors")
