@@ -339,6 +339,19 @@ int lom_debug_eval_sums(lom_map *m, const float *src_xyz, size_t n, size_t strid
 int lom_debug_lm_trace(lom_map *m, const float *src_xyz, size_t n, size_t stride_bytes, const float guess_t[3],
                        const float guess_q_wxyz[4], int outer_index, double *trace_out, int *n_evals_out,
                        float out_t[3], float out_q_wxyz[4], lom_align_stats *stats_or_null);
+/* lom_debug_lm_policy: one form of the Levenberg-Marquardt policy of a solve, run on GIVEN sums (the policy sees
+ * nothing else of a scan or a map; no handle is needed).  form 0: csrc/lm_core.hpp on the host (no GPU needed);
+ * 1: csrc/lm_wave.hpp's first wave form; 2 / 3: the forms k_lm runs in its 512- / 256-thread shapes.  Forms 1-3 replay
+ * all n_solves solves on one 64-lane workgroup in one launch on the current device.
+ * Per solve s: n_evals[s] (1..5) evaluations are available, x0[s*7..] = the start point [qw qx qy qz tx ty tz],
+ * prior_b[s*3..], sums[(s*5 + e)*32 ..] = the LOM_NSUMS block of evaluation e (prior excluded).  Evaluation 0 is fed to
+ * the policy's begin, the others to its feed, until the policy answers 0 (done) or the evaluations run out.
+ * action_out[s*5 + e] = 1 (evaluate the point point_out[(s*5 + e)*7 ..] next) or 0 (done: point_out = the solution),
+ * -1 for evaluations not replayed.  recorded_out / evaluations_out / last_step_norm_out / cost_out [s]: the solve's
+ * results as lom_align_stats counts them. */
+int lom_debug_lm_policy(int form, int n_solves, const int *n_evals, const double *x0, const double *prior_b,
+                        const double *sums, int *action_out, double *point_out, int *recorded_out,
+                        int *evaluations_out, double *last_step_norm_out, double *cost_out);
 
 /* Record a HIP event pair around the correspondence launches of lom_match_align*
  * (stats->match_kernel_ms over stats->profiled_launches launches).  `period` = 0: off; 1: every

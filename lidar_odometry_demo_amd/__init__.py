@@ -404,6 +404,35 @@ def align_repeat(keyframe, d_src_ptr, n, position_guess, reps, stride_bytes=12):
     return Pose3D(np.array(ot[:], np.float32), np.array(oq[:], np.float32)), st.asdict()
 
 
+def debug_lm_policy(form, solves):
+    """One form of the LM policy on given sums (lom_debug_lm_policy): form 0 = lm_core.hpp on the host, 1-3 = the wave
+    forms of lm_wave.hpp on the GPU, all solves in one launch.  `solves`: [(x0[7], prior_b[3], sums[n_evals][32]), ...]
+    with 1 <= n_evals <= 5.  Returns per solve a dict: `actions` (1 evaluate / 0 done, one per evaluation replayed),
+    `points` (the candidate, or the solution with a 0), `recorded`, `evaluations`, `last_step_norm`, `cost`."""
+    n = len(solves)
+    ne = np.array([len(s[2]) for s in solves], np.int32)
+    x0 = np.ascontiguousarray([np.asarray(s[0], np.float64) for s in solves], np.float64).reshape(n, 7)
+    pb = np.ascontiguousarray([np.asarray(s[1], np.float64) for s in solves], np.float64).reshape(n, 3)
+    sums = np.zeros((n, 5, 32), np.float64)
+    for i, s in enumerate(solves):
+        sums[i, :len(s[2])] = np.asarray(s[2], np.float64).reshape(-1, 32)[:5]
+    act = np.empty((n, 5), np.int32)
+    pts = np.empty((n, 5, 7), np.float64)
+    rec, ev = np.empty(n, np.int32), np.empty(n, np.int32)
+    lsn, cost = np.empty(n, np.float64), np.empty(n, np.float64)
+    ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    capi.check(capi.lib().lom_debug_lm_policy(
+        int(form), n, ne.ctypes.data_as(ip), x0.ctypes.data_as(dp), pb.ctypes.data_as(dp), sums.ctypes.data_as(dp),
+        act.ctypes.data_as(ip), pts.ctypes.data_as(dp), rec.ctypes.data_as(ip), ev.ctypes.data_as(ip),
+        lsn.ctypes.data_as(dp), cost.ctypes.data_as(dp)))
+    out = []
+    for i in range(n):
+        k = int(np.sum(act[i] >= 0))
+        out.append({"actions": act[i, :k].tolist(), "points": pts[i, :k].copy(), "recorded": int(rec[i]),
+                    "evaluations": int(ev[i]), "last_step_norm": float(lsn[i]), "cost": float(cost[i])})
+    return out
+
+
 class CloudMatcher:
     """reference src/cloud_matcher.h:13-17 / src/cloud_matcher.cpp:105-178."""
 

@@ -25,7 +25,7 @@
 //             k_quality_batch / k_quality_batch_sum: the same for the K (scan, pose) problems of a round of
 //             lom_match_quality_batch*, blockIdx.y the problem, behind the batch form of k_match.
 //
-// The kernels live in k_match.hpp, k_eval.hpp, k_lm.hpp and k_quality.hpp; this file is the one translation unit that instantiates
+// The kernels live in k_match.hpp, k_eval.hpp, k_lm.hpp, k_quality.hpp and k_policy_probe.hpp (a test probe); this file is the one translation unit that instantiates
 // and launches them: the kernel tables, the chained single and batched align, the host-driven path, the C entry points.
 //
 // Built with -ffp-contract=off (see voxel_map.hip).
@@ -41,6 +41,7 @@
 #include "k_eval.hpp"
 #include "k_lm.hpp"
 #include "k_match.hpp"
+#include "k_policy_probe.hpp"
 #include "k_quality.hpp"
 #include "lm_core.hpp"
 #include "lm_wave.hpp"
@@ -1943,6 +1944,83 @@ int lom_debug_lm_trace(lom_map *m, const float *src, size_t n, size_t stride, co
     *n_evals_out = ne;
     for (int e = 0; e < ne && e < 5; e++) std::memcpy(trace_out + (size_t)e * 40, raw + (size_t)e * 40, 40 * sizeof(double));
     return LOM_OK;
+}
+
+// parity entry: one form of the LM policy on given sums (no map: the policy sees nothing else).  form 0 is lm_core.hpp on
+// the host; forms 1-3 are lm_wave.hpp's on one wave (k_policy_probe.hpp), all solves of the call in one launch.
+int lom_debug_lm_policy(int form, int n_solves, const int *n_evals, const double *x0, const double *prior_b,
+                        const double *sums, int *action_out, double *point_out, int *recorded_out,
+                        int *evaluations_out, double *last_step_norm_out, double *cost_out)
+{
+    if (form < 0 || form > 3 || n_solves < 1 || n_solves > 4096 || !n_evals || !x0 || !prior_b || !sums || !action_out ||
+        !point_out || !recorded_out || !evaluations_out || !last_step_norm_out || !cost_out)
+        return LOM_ERR_ARG;
+    for (int s = 0; s < n_solves; s++)
+        if (n_evals[s] < 1 || n_evals[s] > kProbeMaxEvals) return LOM_ERR_ARG;
+    const size_t ns = (size_t)n_solves, slots = ns * kProbeMaxEvals;
+    for (size_t i = 0; i < slots; i++) action_out[i] = -1;
+    std::memset(point_out, 0, slots * 7 * sizeof(double));
+    if (form == 0) {
+        for (size_t s = 0; s < ns; s++) {
+            LmState S;
+            for (int e = 0; e < n_evals[s]; e++) {
+                const size_t slot = s * kProbeMaxEvals + (size_t)e;
+                const int a = e == 0 ? lm_begin(S, sums + slot * 32, x0 + s * 7, prior_b + s * 3) : lm_feed(S, sums + slot * 32);
+                action_out[slot] = a;
+                std::memcpy(point_out + slot * 7, a == LM_EVAL ? S.cand : S.x, 7 * sizeof(double));
+                if (a != LM_EVAL) break;
+            }
+            recorded_out[s] = S.recorded;
+            evaluations_out[s] = S.evaluations;
+            last_step_norm_out[s] = S.last_step_norm;
+            cost_out[s] = S.cost;
+        }
+        return LOM_OK;
+    }
+    // one device buffer: the inputs, then the outputs, each 8-byte aligned
+    const size_t o_x0 = 0, o_pb = o_x0 + ns * 7 * 8, o_sums = o_pb + ns * 3 * 8, o_point = o_sums + slots * 32 * 8,
+                 o_lsn = o_point + slots * 7 * 8, o_cost = o_lsn + ns * 8, o_ne = o_cost + ns * 8, o_act = o_ne + ns * 4,
+                 o_rec = o_act + slots * 4, o_ev = o_rec + ns * 4, total = o_ev + ns * 4;
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return LOM_ERR_HIP;  // forms 1-3 need a GPU
+    char *d = nullptr;
+    if (hipMalloc((void **)&d, total) != hipSuccess) return LOM_ERR_OOM;
+    hipError_t e = hipMemset(d, 0, total);
+    if (e == hipSuccess) e = hipMemset(d + o_act, 0xFF, slots * 4);
+    if (e == hipSuccess) e = hipMemcpy(d + o_x0, x0, ns * 7 * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + o_pb, prior_b, ns * 3 * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + o_sums, sums, slots * 32 * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + o_ne, n_evals, ns * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        PolicyProbeArgs p;
+        p.n_solves = n_solves;
+        p.n_evals = (const int *)(d + o_ne);
+        p.x0 = (const double *)(d + o_x0);
+        p.prior_b = (const double *)(d + o_pb);
+        p.sums = (const double *)(d + o_sums);
+        p.action = (int *)(d + o_act);
+        p.point = (double *)(d + o_point);
+        p.recorded = (int *)(d + o_rec);
+        p.evaluations = (int *)(d + o_ev);
+        p.last_step_norm = (double *)(d + o_lsn);
+        p.cost = (double *)(d + o_cost);
+        if (form == 1)
+            hipLaunchKernelGGL(k_policy_probe<1>, dim3(1), dim3(64), 0, 0, p);
+        else if (form == 2)
+            hipLaunchKernelGGL(k_policy_probe<2>, dim3(1), dim3(64), 0, 0, p);
+        else
+            hipLaunchKernelGGL(k_policy_probe<3>, dim3(1), dim3(64), 0, 0, p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(action_out, d + o_act, slots * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(point_out, d + o_point, slots * 7 * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(recorded_out, d + o_rec, ns * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(evaluations_out, d + o_ev, ns * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(last_step_norm_out, d + o_lsn, ns * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(cost_out, d + o_cost, ns * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    return e == hipSuccess ? LOM_OK : LOM_ERR_HIP;
 }
 
 // diagnostic: per-workgroup phase stamps of one correspondence launch (shader clock ticks)

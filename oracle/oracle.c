@@ -759,6 +759,7 @@ typedef struct {
     int points;            /* distinct parameter points evaluated: iteration 0 + every candidate */
     double last_step_norm; /* summary.iterations.back().step_norm */
     double cost;
+    int rejected_steps, invalid_steps;
 } lm_result;
 
 /* Ceres 2.2 TrustRegionMinimizer + LevenbergMarquardtStrategy + DenseQRSolver
@@ -789,6 +790,8 @@ static int lm_solve(const match_t *M, size_t nm, double x[7], const double prior
     out->evaluations = 1;
     out->points = 1;
     out->last_step_norm = 0.0;
+    out->rejected_steps = 0;
+    out->invalid_steps = 0;
 
     /* IterationZero: cost, residuals, Jacobian, gradient; Jacobi scaling once */
     double cost = evaluate(M, nm, x, prior_b, res, J);
@@ -847,6 +850,7 @@ static int lm_solve(const match_t *M, size_t nm, double x[7], const double prior
             if (++invalid_run >= 5) break;
             radius /= decrease_factor;
             decrease_factor *= 2.0;
+            out->invalid_steps++;
             out->recorded_iterations++;
             out->last_step_norm = 0.0;
             continue;
@@ -893,6 +897,7 @@ static int lm_solve(const match_t *M, size_t nm, double x[7], const double prior
             radius /= decrease_factor;
             decrease_factor *= 2.0;
             reuse_diag = 1;
+            out->rejected_steps++;
         }
         out->recorded_iterations++;
         out->last_step_norm = sn;
@@ -963,6 +968,8 @@ int orc_align(const orc_map *m, const float *src, size_t n, size_t stride, const
         s.lm_iterations += lr.recorded_iterations;
         s.evaluations += lr.evaluations;
         s.points_evaluated += lr.points;
+        s.rejected_steps += lr.rejected_steps;
+        s.invalid_steps += lr.invalid_steps;
         s.queries += (int64_t)n;
         s.valid_last = (int64_t)nm;
         s.final_cost = lr.cost;

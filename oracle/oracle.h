@@ -121,6 +121,9 @@ typedef struct {
     int points_evaluated;     /* distinct parameter points evaluated (iteration 0 + every LM
                                  candidate, total): Ceres evaluates an accepted candidate twice (cost,
                                  then Jacobian), the product once -- this is the comparable count */
+    int rejected_steps;       /* evaluated candidates that were not taken (HandleUnsuccessfulStep), total */
+    int invalid_steps;        /* steps without an evaluation: failed solve or no model decrease
+                                 (HandleInvalidStep), total */
     int pad;
 } orc_align_stats;
 

@@ -62,6 +62,8 @@ class AlignStats(C.Structure):
         ("search_seconds", C.c_double),
         ("solve_seconds", C.c_double),
         ("points_evaluated", C.c_int),
+        ("rejected_steps", C.c_int),
+        ("invalid_steps", C.c_int),
         ("pad", C.c_int),
     ]
 
