@@ -747,6 +747,46 @@ uint32_t lom_frontend_sequence(const lom_frontend *f);
 /* test hook: the device's restatement of glibc's sinf (used by the per-point slerp) on n host values */
 int lom_debug_sinf(lom_frontend *f, const float *x, size_t n, float *out);
 
+/* ---- classifier for frames without rings (solid-state and non-repetitive scanners, PCD files, merged or down-sampled
+ * clouds, any message for which lom_pointcloud2_unpack sets the `ring` bit of missing_mask) ------------------------
+ * Planar / not planar and a normal per point from the point's neighbourhood in the frame itself; `ring` is not read.
+ *  1. index: a voxel map with voxel size `radius` that keeps the first `index_cap` points of a voxel, built from the
+ *     frame in input order (a workspace of the front end, reused frame after frame);
+ *  2. neighbours of point i: the STORED points of the 27 voxels around i's voxel with d^2 <= radius^2 (d^2 in f64
+ *     from the f32 coordinates); a point whose voxel was full is not stored, hence not its own neighbour; m = their number;
+ *  3. population covariance of d = p_j - p_i over the neighbours (f64), eigenvalues l0 <= l1 <= l2;
+ *  4. planar iff m >= min_neighbours, l0 + l1 + l2 > 0, l0 / (l0 + l1 + l2) <= max_variation and
+ *     l1 / l2 >= min_spread (which rejects a line);
+ *  5. normal = the unit eigenvector of l0, flipped so that n . p_i <= 0 (towards the sensor origin), rounded to f32;
+ *  6. output: the planar points in INPUT order, packed xyz + normals, their count in a device word; the range filter
+ *     follows.  A non-finite or out-of-range point fails the frame with LOM_ERR_RANGE, as it fails the down-samplers.
+ * There are no defaults: the project has no measured basis for any.  radius > 0, 1 <= index_cap <= 64,
+ * min_neighbours >= 3, 0 < max_variation <= 1/3, 0 <= min_spread < 1; anything else is LOM_ERR_ARG. */
+typedef struct {
+    float radius;
+    uint32_t index_cap, min_neighbours;
+    float max_variation, min_spread;
+} lom_neighbourhood_params;
+typedef struct { /* per INPUT point */
+    uint32_t neighbours;
+    int32_t planar;
+    double eig[3]; /* ascending; zero where there is no neighbour */
+} lom_neighbourhood_detail;
+enum { LOM_CLASSIFIER_RINGS = 0, LOM_CLASSIFIER_NEIGHBOURHOOD = 1 };
+/* The stage alone, host in / host out, on the front end's stream and workspace (it overwrites the deskewed cloud the
+ * last frame left in HBM).  Returns the number of planar points (no range filter); xyz_out / nrm_out: room for n
+ * points; detail_out_or_null: n records. */
+int64_t lom_classify_neighbourhood(lom_frontend *f, const lom_point_xyzirt *pts, size_t n, const lom_neighbourhood_params *p,
+                                   float *xyz_out, float *nrm_out, lom_neighbourhood_detail *detail_out_or_null);
+/* The classifier of the following lom_frontend_process calls.  With LOM_CLASSIFIER_NEIGHBOURHOOD (p required) a frame
+ * runs upload, time normalisation and deskew as they are, then the stage above, then the range filter;
+ * lom_frontend_wait never returns 1 for such a frame (there is no host version: a scan that gave up is redone on the
+ * device by kernels that wait for nobody) and counts_out = {planar, filtered, 0, 0}.  LOM_CLASSIFIER_RINGS (p ignored)
+ * is the default, and going back to it restores it bit for bit. */
+int lom_frontend_set_classifier(lom_frontend *f, int kind, const lom_neighbourhood_params *p_or_null);
+/* LOM_COUNTER_GRID_REDOS: neighbourhood stages of this front end redone after an in-kernel scan gave up */
+int64_t lom_frontend_debug_counter(const lom_frontend *f, int which);
+
 /* ---- file input: pcl::io::loadPCDFile<pcl::PointXYZ> (test/test.cpp:194) ---------------------------- */
 /* PCD v0.7 reader, host code without PCL: `DATA ascii` and `DATA binary`, fields located by name (x y z,
  * optionally normal_x normal_y normal_z), any SIZE / TYPE / COUNT layout -- e.g. the reference's shipped
@@ -873,6 +913,11 @@ int lom_odometry_get_quality(const lom_odometry *o, lom_quality_report *out);
  * (LOM_HOST_THREADS, LOM_SYNC_KEYFRAME_UPDATE, LOM_HOST_FRONTEND, LOM_DEBUG_TIMING, and the A/B switches
  * LOM_NO_CLEANUP_BEHIND_ALIGN, LOM_NO_SEND_AHEAD; lom_map_create reads LOM_DENSE_CLEANUP). */
 int lom_odometry_set_option(lom_odometry *o, int option, int64_t value);
+/* The classifier of the following frames (lom_frontend_set_classifier); process_cloud, process_sequence, process_batch,
+ * hint_next and LOM_OPT_QUALITY_REPORT work with either.  The neighbourhood classifier has no host version: choosing it on
+ * an object created with LOM_HOST_FRONTEND=1, or while LOM_OPT_TEST_FORCE_HOST_REDO is set (and setting that option while
+ * it is chosen), is LOM_ERR_STATE, and a frame beyond the device front end's size limit fails with LOM_ERR_ARG. */
+int lom_odometry_set_classifier(lom_odometry *o, int kind, const lom_neighbourhood_params *p_or_null);
 int64_t lom_odometry_debug_counter(const lom_odometry *o, int which); /* LOM_COUNTER_GRID_REDOS: all its handles + frames redone */
 /* test hook (teacher-forced parity tests): overwrite previous_transform_ / current_transform_
  * (lidar_odometry.h:84-85); the keyframe itself can be replaced through lom_odometry_keyframe() */

@@ -583,6 +583,53 @@ struct CloudClassifier {
     }
 };
 
+// ---- classifier for frames without rings (not in the reference; lom_classify_neighbourhood) ----------------------
+using NeighbourhoodParams = lom_neighbourhood_params;  // {radius, index_cap, min_neighbours, max_variation, min_spread}
+
+// the per-frame front end on the device (lom_frontend_*): here as the owner of the neighbourhood classifier's workspace
+class FrontEnd {
+public:
+    explicit FrontEnd(int device = 0)
+    {
+        const int rc = lom_frontend_create(device, nullptr, &h_);
+        if (rc != LOM_OK) throw Error(rc, "lom_frontend_create");
+    }
+    ~FrontEnd() { lom_frontend_destroy(h_); }
+    FrontEnd(const FrontEnd &) = delete;
+    FrontEnd &operator=(const FrontEnd &) = delete;
+    lom_frontend *handle() const { return h_; }
+    // LOM_CLASSIFIER_RINGS (params ignored) or LOM_CLASSIFIER_NEIGHBOURHOOD for the following lom_frontend_process calls
+    void setClassifier(int kind, const NeighbourhoodParams *params = nullptr)
+    {
+        const int rc = lom_frontend_set_classifier(h_, kind, params);
+        if (rc != LOM_OK) throw Error(rc, lom_frontend_last_error(h_));
+    }
+
+private:
+    lom_frontend *h_ = nullptr;
+};
+
+// the stage alone: the planar points of `input` in input order, with normals; `details` (optional): one record per input point
+inline PointCloud<PointNormal>::Ptr classifyNeighbourhood(FrontEnd &fe, const PointCloud<lom_point_xyzirt> &input,
+                                                          const NeighbourhoodParams &params,
+                                                          std::vector<lom_neighbourhood_detail> *details = nullptr)
+{
+    const size_t n = input.points.size();
+    std::vector<float> xyz(3 * n + 3), nrm(3 * n + 3);
+    if (details) details->resize(n);
+    const int64_t m = lom_classify_neighbourhood(fe.handle(), input.points.data(), n, &params, xyz.data(), nrm.data(),
+                                                 details ? details->data() : nullptr);
+    if (m < 0) throw Error((int)m, lom_frontend_last_error(fe.handle()));
+    auto planar = std::make_shared<PointCloud<PointNormal>>();
+    planar->points.resize((size_t)m);
+    for (size_t i = 0; i < (size_t)m; i++) {
+        PointNormal &p = planar->points[i];
+        p.x = xyz[3 * i], p.y = xyz[3 * i + 1], p.z = xyz[3 * i + 2];
+        p.normal_x = nrm[3 * i], p.normal_y = nrm[3 * i + 1], p.normal_z = nrm[3 * i + 2];
+    }
+    return planar;
+}
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)
@@ -650,6 +697,13 @@ public:
     void hintNextCloud(const CloudType &next_cloud)
     {
         const int rc = lom_odometry_hint_next(h_, next_cloud.points.data(), next_cloud.points.size());
+        if (rc != LOM_OK) throw Error(rc, lom_odometry_last_error(h_));
+    }
+    // the classifier of the following frames: LOM_CLASSIFIER_RINGS (the reference's, the default) or
+    // LOM_CLASSIFIER_NEIGHBOURHOOD for clouds without rings (params required)
+    void setClassifier(int kind, const NeighbourhoodParams *params = nullptr)
+    {
+        const int rc = lom_odometry_set_classifier(h_, kind, params);
         if (rc != LOM_OK) throw Error(rc, lom_odometry_last_error(h_));
     }
     // LOM_OPT_QUALITY_REPORT: every frame that aligns also gets a quality report at the pose the align returned

@@ -15,7 +15,7 @@ from . import capi
 from .capi import LomError  # noqa: F401
 
 __all__ = ["Pose3D", "VoxelGrid", "CloudMatcher", "ScanContext", "LidarOdometry", "transform_points", "pointTimeNormalize",
-           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "LomError", "capi", "quality_report",
+           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "classifyNeighbourhood", "neighbourhoodParams", "LomError", "capi", "quality_report",
            "quality_report_batch", "pose_lattice"]
 
 
@@ -647,6 +647,38 @@ def estimateNormals(xyz, radius, device=0, with_counts=False):
     return (nrm, cnt) if with_counts else nrm
 
 
+def neighbourhoodParams(params):
+    """capi.NeighbourhoodParams from one, from a dict with its five fields, or from a 5-tuple in the struct's order
+    (radius, index_cap, min_neighbours, max_variation, min_spread).  There are no defaults."""
+    if isinstance(params, capi.NeighbourhoodParams):
+        return params
+    names = [k for k, _ in capi.NeighbourhoodParams._fields_]
+    if isinstance(params, dict):
+        if sorted(params) != sorted(names):
+            raise TypeError(f"neighbourhood parameters: exactly {names}")
+        return capi.NeighbourhoodParams(**params)
+    vals = tuple(params)
+    if len(vals) != len(names):
+        raise TypeError(f"neighbourhood parameters: exactly {names}")
+    return capi.NeighbourhoodParams(*vals)
+
+
+def classifyNeighbourhood(points, params, details=False, frontend=None):
+    """The neighbourhood classifier alone (lom_classify_neighbourhood) on POINT_XYZIRT records whose `ring` is not read:
+    (planar xyz, normals) in input order, and with details=True a third array of capi.NEIGHBOURHOOD_DETAIL records, one
+    per input point.  `frontend`: the FrontEnd whose stream and workspace it uses (default: one made for the call)."""
+    a = _cloud(points)
+    fe = frontend if frontend is not None else FrontEnd()
+    p = neighbourhoodParams(params)
+    xyz = np.empty((max(len(a), 1), 3), np.float32)
+    nrm = np.empty((max(len(a), 1), 3), np.float32)
+    det = np.zeros(len(a), capi.NEIGHBOURHOOD_DETAIL) if details else None
+    n = fe._check(capi.lib().lom_classify_neighbourhood(fe._h, a.ctypes.data, len(a), C.byref(p), xyz.ctypes.data,
+                                                        nrm.ctypes.data, det.ctypes.data if details else None))
+    out = (xyz[:n].copy(), nrm[:n].copy())
+    return out + (det,) if details else out
+
+
 class FrontEnd:
     """The per-frame front end on the device (csrc/frontend.hip): pointTimeNormalize + transformNonRigid +
     CloudClassifier::classify + rangeFilter, results left in HBM."""
@@ -668,6 +700,17 @@ class FrontEnd:
         if rc < 0:
             raise LomError(int(rc), capi.lib().lom_frontend_last_error(self._h).decode())
         return rc
+
+    def setClassifier(self, kind, params=None):
+        """capi.CLASSIFIER_RINGS (the default) or capi.CLASSIFIER_NEIGHBOURHOOD (params required) for the frames that follow."""
+        p = neighbourhoodParams(params) if params is not None else None
+        self._check(capi.lib().lom_frontend_set_classifier(self._h, int(kind), C.byref(p) if p is not None else None))
+
+    def setOption(self, option, value):
+        self._check(capi.lib().lom_frontend_set_option(self._h, int(option), int(value)))
+
+    def debugCounter(self, which=capi.COUNTER_GRID_REDOS):
+        return int(capi.lib().lom_frontend_debug_counter(self._h, int(which)))
 
     def process(self, points, start_pose, end_pose, min_range, max_range):
         """Returns dict(deskewed, planar_points, xyz, normals, grid, redo_on_host)."""
@@ -789,6 +832,15 @@ class LidarOdometry:
 
     def debugCounter(self, which=capi.COUNTER_GRID_REDOS):
         return int(capi.lib().lom_odometry_debug_counter(self._h, int(which)))
+
+    def setClassifier(self, kind, params=None):
+        """lom_odometry_set_classifier: capi.CLASSIFIER_RINGS (the reference's, the default) or
+        capi.CLASSIFIER_NEIGHBOURHOOD for clouds without rings (params required: neighbourhoodParams)."""
+        p = neighbourhoodParams(params) if params is not None else None
+        rc = capi.lib().lom_odometry_set_classifier(self._h, int(kind), C.byref(p) if p is not None else None)
+        if rc != 0:
+            text = capi.lib().lom_odometry_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "lom_odometry_set_classifier")
 
     def processCloud(self, input_cloud):                   # lidar_odometry.cpp:22-77
         a = _cloud(input_cloud)

@@ -132,6 +132,18 @@ class OdometryFrameStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class NeighbourhoodParams(C.Structure):
+    """lom_neighbourhood_params (no defaults: every field is the caller's)"""
+    _fields_ = [("radius", C.c_float), ("index_cap", C.c_uint32), ("min_neighbours", C.c_uint32),
+                ("max_variation", C.c_float), ("min_spread", C.c_float)]
+
+
+# lom_neighbourhood_detail, one per input point
+NEIGHBOURHOOD_DETAIL = np.dtype([("neighbours", "<u4"), ("planar", "<i4"), ("eig", "<f8", 3)])
+assert NEIGHBOURHOOD_DETAIL.itemsize == 32
+CLASSIFIER_RINGS, CLASSIFIER_NEIGHBOURHOOD = 0, 1
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -187,6 +199,7 @@ EXPORTED = [
     "lom_match_quality_batch_sums", "lom_match_quality_batch_sums_device", "lom_match_quality_batch",
     "lom_match_quality_batch_device", "lom_scan_quality_batch_sums", "lom_scan_quality_batch_sums_device",
     "lom_scan_quality_batch", "lom_scan_quality_batch_device", "lom_quality_batch_best", "lom_pose_lattice",
+    "lom_classify_neighbourhood", "lom_frontend_set_classifier", "lom_frontend_debug_counter", "lom_odometry_set_classifier",
 ]
 
 # lom_option / counters of include/lidar_odometry_amd.h
@@ -381,6 +394,12 @@ def lib():
     L.lom_odometry_debug_counter.argtypes = [vp, C.c_int]
     L.lom_odometry_debug_counter.restype = C.c_int64
     L.lom_frontend_set_option.argtypes = [vp, C.c_int, C.c_int64]
+    L.lom_classify_neighbourhood.argtypes = [vp, vp, C.c_size_t, C.POINTER(NeighbourhoodParams), vp, vp, vp]
+    L.lom_classify_neighbourhood.restype = C.c_int64
+    L.lom_frontend_set_classifier.argtypes = [vp, C.c_int, C.POINTER(NeighbourhoodParams)]
+    L.lom_frontend_debug_counter.argtypes = [vp, C.c_int]
+    L.lom_frontend_debug_counter.restype = C.c_int64
+    L.lom_odometry_set_classifier.argtypes = [vp, C.c_int, C.POINTER(NeighbourhoodParams)]
     L.lom_host_comm_set_timeout.argtypes = [vp, C.c_double]
     L.lom_host_comm_abort.argtypes = [vp]
     L.lom_host_comm_last_error.argtypes = [vp]

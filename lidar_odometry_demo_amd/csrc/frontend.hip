@@ -32,6 +32,7 @@
 #include <string>
 
 #include "grid_scan.hpp"
+#include "k_neighbourhood.hpp"
 #include "lom_internal.hpp"
 #include "pose_math.hpp"
 
@@ -113,6 +114,7 @@ __device__ __forceinline__ float f32_unordered(uint32_t u)
 
 // words written for the host / the consumers:  [0] planar points  [1] filtered points  [2] H  [3] W
 //   [4] fall-back flag (sequence number of the frame that must be redone on the host)  [5] grid error
+//   [6] neighbourhood classifier: a point of the frame is out of range / not finite (sequence number)
 constexpr int kFeWords = 8;
 
 // `in` may be the pinned host buffer the frame was staged in (read over the host link, once): the kernel then leaves
@@ -432,6 +434,22 @@ struct lom_frontend {
     uint32_t n_last = 0;
     int test_grid_give_up = -1;  // LOM_OPT_TEST_GRID_GIVE_UP (one shot)
     bool dma_upload = false;     // LOM_FE_DMA_UPLOAD=1 at create
+    uint32_t stats_set = 0;      // which of the two FeStats sets the next frame uses
+    // neighbourhood classifier (lom_frontend_set_classifier, k_neighbourhood.hpp): the frame's voxel index is a map
+    // handle on this stream, created when the classifier is chosen and reused frame after frame
+    int kind = LOM_CLASSIFIER_RINGS, last_kind = LOM_CLASSIFIER_RINGS;  // chosen / of the last frame
+    lom_neighbourhood_params nb{};
+    lom_map *nb_index = nullptr;
+    unsigned long long *d_nb_blk = nullptr;  // workgroup totals of the multi-launch compaction
+    lom_neighbourhood_detail *d_nb_detail = nullptr;  // lom_classify_neighbourhood with details only
+    size_t nb_detail_cap = 0;
+    struct {  // the last run of the stage, for its redo
+        lom_neighbourhood_params p{};
+        float min_sq = 0.f, max_sq = 0.f;
+        int apply_range = 0;
+        bool detail = false;
+    } nb_last;
+    int64_t grid_redos = 0;  // neighbourhood stages redone by the multi-launch form (lom_frontend_debug_counter)
     std::string error;
 };
 
@@ -501,6 +519,111 @@ void frame_const(const lom_pose &start, const lom_pose &end, float min_range, fl
     F.max_sq = max_range * max_range;
 }
 
+int nb_fail_map(lom_frontend *f, int rc)
+{
+    f->error = lom_last_error(f->nb_index);
+    return rc;
+}
+
+// the index workspace for these parameters: created once, its slab stride follows index_cap, its voxel size is set by
+// the clear in front of every insert
+int nb_workspace(lom_frontend *f, const lom_neighbourhood_params &p)
+{
+    int rc;
+    if (!f->nb_index) {
+        // capacity hint 2^15: the table never reaches 16 times its smallest size for a frame the front end takes, so
+        // the insert never settles the table size (a read-back) afterwards
+        if ((rc = lom_map_create(p.radius, p.index_cap, (size_t)1 << 15, f->device, &f->nb_index)) != LOM_OK)
+            return fe_fail(f, rc, lom_last_error(nullptr));
+        if ((rc = lom_map_set_stream(f->nb_index, f->stream)) != LOM_OK) return nb_fail_map(f, rc);
+    }
+    if (!f->d_nb_blk) FE_HIP(f, hipMalloc((void **)&f->d_nb_blk, kNbMaxBlocks * sizeof(unsigned long long)));
+    if (f->nb_index->max_points != p.index_cap) {
+        if ((rc = lom_map_clear(f->nb_index, p.radius)) != LOM_OK) return nb_fail_map(f, rc);
+        if ((rc = lom_map_set_max_points(f->nb_index, p.index_cap)) != LOM_OK) return nb_fail_map(f, rc);
+    }
+    return LOM_OK;
+}
+
+void nb_launch_compact(lom_frontend *f, uint32_t N, float min_sq, float max_sq, int apply_range, uint32_t seq, bool multi)
+{
+    const float4 *rec = f->d_org;  // the organised cloud's buffer is free under this classifier: one record per input point
+    if (!multi) {
+        const uint32_t fail_from = f->test_grid_give_up < 0 ? 0xFFFFFFFFu : (uint32_t)f->test_grid_give_up;
+        f->test_grid_give_up = -1;
+        if (N <= kOnePassMax)
+            hipLaunchKernelGGL((k_nb_compact<1, 0>), dim3(std::max(1u, blocks_for(N))), dim3(kThreads), 0, f->stream, f->d_desk, rec, N,
+                               min_sq, max_sq, apply_range, f->d_xyz, f->d_nrm, fe_agg(f), f->d_nb_blk, seq, f->d_words, fail_from);
+        else
+            hipLaunchKernelGGL((k_nb_compact<kFeItems, 0>), dim3(blocks_for((N + kFeItems - 1) / kFeItems)), dim3(kThreads), 0,
+                               f->stream, f->d_desk, rec, N, min_sq, max_sq, apply_range, f->d_xyz, f->d_nrm, fe_agg(f),
+                               f->d_nb_blk, seq, f->d_words, fail_from);
+        return;
+    }
+    // the multi-launch form: totals, their scan, the write -- no workgroup waits for another
+    const uint32_t nb = std::max(1u, blocks_for(N));  // <= kNbMaxBlocks: N <= kFeItems * kOnePassMax
+    hipLaunchKernelGGL((k_nb_compact<1, 1>), dim3(nb), dim3(kThreads), 0, f->stream, f->d_desk, rec, N, min_sq, max_sq, apply_range,
+                       f->d_xyz, f->d_nrm, fe_agg(f), f->d_nb_blk, seq, f->d_words, 0xFFFFFFFFu);
+    hipLaunchKernelGGL(k_nb_offsets, dim3(1), dim3(kThreads), 0, f->stream, f->d_nb_blk, nb);
+    hipLaunchKernelGGL((k_nb_compact<1, 2>), dim3(nb), dim3(kThreads), 0, f->stream, f->d_desk, rec, N, min_sq, max_sq, apply_range,
+                       f->d_xyz, f->d_nrm, fe_agg(f), f->d_nb_blk, seq, f->d_words, 0xFFFFFFFFu);
+}
+
+// the stage on the N deskewed points in f->d_desk: index insert, evaluation, compaction -- enqueued, nothing waits.
+// redo: the insert waits for its own verdict (and redoes itself should its scan give up), the compaction takes the
+// multi-launch form.
+int nb_enqueue(lom_frontend *f, uint32_t N, const lom_neighbourhood_params &p, float min_sq, float max_sq, int apply_range,
+               bool detail, uint32_t seq, bool redo)
+{
+    int rc;
+    if ((rc = nb_workspace(f, p)) != LOM_OK) return rc;
+    lom_map *ix = f->nb_index;
+    f->nb_last.p = p;
+    f->nb_last.min_sq = min_sq, f->nb_last.max_sq = max_sq;
+    f->nb_last.apply_range = apply_range;
+    f->nb_last.detail = detail;
+    if ((rc = lom_map_clear(ix, p.radius)) != LOM_OK) return nb_fail_map(f, rc);
+    const uint32_t *d_range = nullptr, *d_grid = nullptr;
+    uint32_t idx_seq = 0;
+    if (N) {
+        rc = redo ? lom_map_add_points_device(ix, reinterpret_cast<const float *>(f->d_desk), nullptr, N, sizeof(lom_point_xyzirt))
+                  : lom_map_add_points_device_nowait(ix, reinterpret_cast<const float *>(f->d_desk), nullptr, N,
+                                                     sizeof(lom_point_xyzirt));
+        if (rc != LOM_OK) return nb_fail_map(f, rc);
+        if (!redo) lom_map_status_words(ix, &d_range, &d_grid, &idx_seq);
+    }
+    NbArgs A;
+    A.r2 = (double)p.radius * (double)p.radius;
+    A.max_variation = (double)p.max_variation;
+    A.min_spread = (double)p.min_spread;
+    A.min_neighbours = p.min_neighbours;
+    if (N) {
+        const uint32_t blocks = std::min(blocks_for(N, kNbBatch), 256u * 8u);
+        hipLaunchKernelGGL(k_nb_eval, dim3(blocks), dim3(kThreads), 0, f->stream, view_of(ix), f->d_desk, N, A, f->d_org,
+                           detail ? f->d_nb_detail : nullptr, d_range, d_grid, idx_seq, seq, f->d_words);
+    }
+    nb_launch_compact(f, N, min_sq, max_sq, apply_range, seq, redo);
+    FE_HIP(f, hipGetLastError());
+    return LOM_OK;
+}
+
+// after a wait: the words of the last neighbourhood stage are in h_words.  A point out of range fails the frame as it
+// fails the down-samplers; a scan that gave up -- the index insert's or the compaction's -- has written nothing, and the
+// stage is redone here by the forms that wait for nobody.
+int nb_settle(lom_frontend *f)
+{
+    if (f->h_words[6] == f->seq) return fe_fail(f, LOM_ERR_RANGE, "coordinate / radius out of range or not finite");
+    if (f->h_words[5] != f->seq) return LOM_OK;
+    f->grid_redos++;
+    int rc = nb_enqueue(f, f->n_last, f->nb_last.p, f->nb_last.min_sq, f->nb_last.max_sq, f->nb_last.apply_range,
+                        f->nb_last.detail, f->seq, true);
+    if (rc != LOM_OK) return rc;
+    FE_HIP(f, hipEventRecord(f->done_ev, f->stream));
+    FE_HIP(f, hipMemcpyAsync(f->h_words, f->d_words, kFeWords * 4, hipMemcpyDeviceToHost, f->stream));
+    FE_HIP(f, hipStreamSynchronize(f->stream));
+    return LOM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -550,6 +673,9 @@ void lom_frontend_destroy(lom_frontend *f)
     if (!f) return;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
+    if (f->nb_index) lom_map_destroy(f->nb_index);  // it runs on this stream: it goes first
+    for (void *p : {(void *)f->d_nb_blk, (void *)f->d_nb_detail})
+        if (p) (void)hipFree(p);
     for (void *p : {(void *)f->d_in, (void *)f->d_desk, (void *)f->d_win, (void *)f->d_org, (void *)f->d_xyz, (void *)f->d_nrm,
                     (void *)f->d_stats, (void *)f->d_words})
         if (p) (void)hipFree(p);
@@ -608,7 +734,8 @@ int lom_frontend_process(lom_frontend *f, const lom_point_xyzirt *pts, size_t n,
     }
     FrameConst F;
     frame_const(*start, *end, min_range, max_range, F);
-    FeStats *mine = f->d_stats + (seq & 1u), *next = f->d_stats + ((seq + 1u) & 1u);
+    FeStats *mine = f->d_stats + f->stats_set, *next = f->d_stats + (f->stats_set ^ 1u);
+    f->stats_set ^= 1u;
     const uint32_t cell_cap = (uint32_t)std::min<size_t>(f->cap_cells, (size_t)kFeItems * kOnePassMax);
     const uint32_t pt_blocks = std::max(1u, std::min(blocks_for(N), 1024u));
     hipLaunchKernelGGL(k_fe_stats, dim3(pt_blocks), dim3(kThreads), 0, f->stream, stats_in, N, mine, next, stats_keep);
@@ -616,6 +743,17 @@ int lom_frontend_process(lom_frontend *f, const lom_point_xyzirt *pts, size_t n,
     // the organised cloud has H * W cells, known on the device only: the grids cover what a frame of n points
     // normally needs (rings of equal size: H * W ~ n) with a margin; a larger cloud raises the fall-back flag
     const uint32_t cells_bound = (uint32_t)std::min<size_t>(cell_cap, (size_t)N + N / 2 + 4096);
+    f->last_kind = f->kind;
+    if (f->kind == LOM_CLASSIFIER_NEIGHBOURHOOD) {
+        // time normalisation and deskew as they are; with no room for an organised cloud k_fe_deskew leaves the cell
+        // table alone (its fall-back word [4] means nothing here: no azimuth bin is used)
+        hipLaunchKernelGGL(k_fe_deskew, dim3(pt_blocks), dim3(kThreads), 0, f->stream, f->d_in, N, F, mine, f->d_desk, f->d_win,
+                           0u, seq, f->d_words);
+        FE_HIP(f, hipGetLastError());
+        if ((rc = nb_enqueue(f, N, f->nb, F.min_sq, F.max_sq, 1, false, seq, false)) != LOM_OK) return rc;
+        FE_HIP(f, hipEventRecord(f->done_ev, f->stream));
+        return LOM_OK;
+    }
     hipLaunchKernelGGL(k_fe_deskew, dim3(pt_blocks), dim3(kThreads), 0, f->stream, f->d_in, N, F, mine, f->d_desk, f->d_win,
                        cells_bound, seq, f->d_words);
     hipLaunchKernelGGL(k_fe_curv, dim3(blocks_for(cells_bound)), dim3(kThreads), 0, f->stream, f->d_desk, f->d_win,
@@ -701,10 +839,75 @@ int lom_frontend_wait(lom_frontend *f, uint32_t counts_out[4])
     FE_HIP(f, hipSetDevice(f->device));
     FE_HIP(f, hipMemcpyAsync(f->h_words, f->d_words, kFeWords * 4, hipMemcpyDeviceToHost, f->stream));
     FE_HIP(f, hipStreamSynchronize(f->stream));
+    if (f->last_kind == LOM_CLASSIFIER_NEIGHBOURHOOD) {  // never 1: there is no host version, the device redoes its own frame
+        const int rc = nb_settle(f);
+        if (rc != LOM_OK) return rc;
+        if (counts_out)
+            for (int k = 0; k < 4; k++) counts_out[k] = f->h_words[k];
+        return LOM_OK;
+    }
     if (counts_out)
         for (int k = 0; k < 4; k++) counts_out[k] = f->h_words[k];
     // a grid that gave up has written nothing and left the cell table at rest: the frame goes to the host stages
     return (f->h_words[4] == f->seq || f->h_words[5] == f->seq) ? 1 : LOM_OK;
+}
+
+int lom_frontend_set_classifier(lom_frontend *f, int kind, const lom_neighbourhood_params *p)
+{
+    if (kind == LOM_CLASSIFIER_NEIGHBOURHOOD && !neighbourhood_params_ok(p)) return LOM_ERR_ARG;
+    if (!f || (kind != LOM_CLASSIFIER_RINGS && kind != LOM_CLASSIFIER_NEIGHBOURHOOD)) return LOM_ERR_ARG;
+    if (kind == LOM_CLASSIFIER_NEIGHBOURHOOD) {
+        FE_HIP(f, hipSetDevice(f->device));
+        const int rc = nb_workspace(f, *p);
+        if (rc != LOM_OK) return rc;
+        f->nb = *p;
+    }
+    f->kind = kind;
+    return LOM_OK;
+}
+
+int64_t lom_frontend_debug_counter(const lom_frontend *f, int which)
+{
+    if (!f || which != LOM_COUNTER_GRID_REDOS) return LOM_ERR_ARG;
+    return f->grid_redos + (f->nb_index ? lom_map_debug_counter(f->nb_index, which) : 0);
+}
+
+int64_t lom_classify_neighbourhood(lom_frontend *f, const lom_point_xyzirt *pts, size_t n, const lom_neighbourhood_params *p,
+                                   float *xyz_out, float *nrm_out, lom_neighbourhood_detail *detail_out)
+{
+    if (!neighbourhood_params_ok(p)) return LOM_ERR_ARG;
+    if (!f || (n && (!pts || !xyz_out || !nrm_out))) return LOM_ERR_ARG;
+    if (n + n / 2 + 4096 > (size_t)kFeItems * kOnePassMax) return fe_fail(f, LOM_ERR_ARG, "frame too large for the device front end");
+    FE_HIP(f, hipSetDevice(f->device));
+    f->error.clear();
+    int rc = fe_reserve(f, std::max<size_t>(n, 1));
+    if (rc != LOM_OK) return rc;
+    if (detail_out && n > f->nb_detail_cap) {
+        FE_HIP(f, hipStreamSynchronize(f->stream));
+        if (f->d_nb_detail) (void)hipFree(f->d_nb_detail);
+        f->d_nb_detail = nullptr;
+        f->nb_detail_cap = 0;
+        FE_HIP(f, hipMalloc((void **)&f->d_nb_detail, (n + n / 2) * sizeof(lom_neighbourhood_detail)));
+        f->nb_detail_cap = n + n / 2;
+    }
+    const uint32_t N = (uint32_t)n;
+    const uint32_t seq = ++f->seq;
+    f->n_last = N;
+    f->last_kind = LOM_CLASSIFIER_NEIGHBOURHOOD;
+    // the frame goes where the deskew would have left it
+    if (n) FE_HIP(f, hipMemcpyAsync(f->d_desk, pts, n * sizeof(lom_point_xyzirt), hipMemcpyHostToDevice, f->stream));
+    if ((rc = nb_enqueue(f, N, *p, 0.f, 0.f, 0, detail_out != nullptr, seq, false)) != LOM_OK) return rc;
+    uint32_t counts[4];
+    if ((rc = lom_frontend_wait(f, counts)) != LOM_OK) return rc;
+    const size_t np = counts[0];
+    if (np) {
+        FE_HIP(f, hipMemcpyAsync(xyz_out, f->d_xyz, np * 12, hipMemcpyDeviceToHost, f->stream));
+        FE_HIP(f, hipMemcpyAsync(nrm_out, f->d_nrm, np * 12, hipMemcpyDeviceToHost, f->stream));
+    }
+    if (detail_out && n)
+        FE_HIP(f, hipMemcpyAsync(detail_out, f->d_nb_detail, n * sizeof(lom_neighbourhood_detail), hipMemcpyDeviceToHost, f->stream));
+    FE_HIP(f, hipStreamSynchronize(f->stream));
+    return (int64_t)np;
 }
 
 // copies of the device results for callers on the host (getTempCloud, tests): what = 0 the deskewed cloud

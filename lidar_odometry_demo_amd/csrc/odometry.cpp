@@ -530,6 +530,7 @@ struct lom_odometry {
     // and it never goes from false to true on the helper thread.
     std::atomic<bool> keyframe_has_voxels{false};
     bool test_force_host_redo = false;  // LOM_OPT_TEST_FORCE_HOST_REDO
+    int classifier = LOM_CLASSIFIER_RINGS;  // lom_odometry_set_classifier; the neighbourhood classifier has no host version
     bool debug_timing = false;          // LOM_DEBUG_TIMING=1 at create / LOM_OPT_DEBUG_TIMING
     bool no_cleanup_behind_align = false;  // LOM_NO_CLEANUP_BEHIND_ALIGN=1 at create: the cleanup's scan waits for the host (A/B)
     bool no_send_ahead = false;            // LOM_NO_SEND_AHEAD=1 at create: hints are ignored (A/B)
@@ -697,7 +698,10 @@ int lom_odometry_set_option(lom_odometry *o, int option, int64_t value)
     int rc = o->settle();
     if (rc != LOM_OK) return rc;
     switch (option) {
-    case LOM_OPT_TEST_FORCE_HOST_REDO: o->test_force_host_redo = value != 0; return LOM_OK;
+    case LOM_OPT_TEST_FORCE_HOST_REDO:
+        if (value != 0 && o->classifier == LOM_CLASSIFIER_NEIGHBOURHOOD) return LOM_ERR_STATE;  // no host stages to redo with
+        o->test_force_host_redo = value != 0;
+        return LOM_OK;
     case LOM_OPT_DEBUG_TIMING: o->debug_timing = value != 0; return lom_map_set_option(o->keyframe, option, value);
     case LOM_OPT_QUALITY_REPORT:
         o->quality_on = value != 0;
@@ -719,6 +723,7 @@ int64_t lom_odometry_debug_counter(const lom_odometry *o, int which)
     if (which == LOM_COUNTER_GRID_REDOS) {
         int64_t v = o->grid_redos;
         for (lom_map *m : {o->keyframe, o->update_ds2[0], o->update_ds2[1], o->matching_ds}) v += lom_map_debug_counter(m, which);
+        if (o->frontend) v += lom_frontend_debug_counter(o->frontend, which);
         return v;
     }
     if (which == LOM_COUNTER_FRAMES_SENT_AHEAD) return (int64_t)o->frames_sent_ahead;
@@ -727,6 +732,23 @@ int64_t lom_odometry_debug_counter(const lom_odometry *o, int which)
         return rc != LOM_OK ? rc : lom_map_debug_counter(o->keyframe, which);
     }
     return LOM_ERR_ARG;
+}
+
+int lom_odometry_set_classifier(lom_odometry *o, int kind, const lom_neighbourhood_params *p)
+{
+    // the arguments first, then the state
+    if (kind != LOM_CLASSIFIER_RINGS && kind != LOM_CLASSIFIER_NEIGHBOURHOOD) return LOM_ERR_ARG;
+    if (kind == LOM_CLASSIFIER_NEIGHBOURHOOD && !lom::neighbourhood_params_ok(p)) return LOM_ERR_ARG;
+    if (!o) return LOM_ERR_ARG;
+    int rc = o->settle();
+    if (rc != LOM_OK) return rc;
+    if (kind == LOM_CLASSIFIER_NEIGHBOURHOOD && (!o->frontend || o->test_force_host_redo)) return LOM_ERR_STATE;
+    if (o->frontend && (rc = lom_frontend_set_classifier(o->frontend, kind, p)) != LOM_OK) {
+        o->error = lom_frontend_last_error(o->frontend);
+        return rc;
+    }
+    o->classifier = kind;
+    return LOM_OK;
 }
 
 int lom_odometry_set_quality_thresholds(lom_odometry *o, float min_eig_t, float min_eig_r)
@@ -859,7 +881,12 @@ int stages_device_enqueue(lom_odometry *o, const lom_point_xyzirt *pts, size_t n
     int rc;
     // front end and down-samplers take frames of up to ~170k points (their in-kernel scans cover 262144 cells /
     // points); larger ones go through the host stages
-    if (n > 170000) return 1;
+    const bool neighbourhood = o->classifier == LOM_CLASSIFIER_NEIGHBOURHOOD;
+    if (n > 170000) {
+        if (!neighbourhood) return 1;
+        o->error = "frame too large for the device front end (the neighbourhood classifier has no host version)";
+        return LOM_ERR_ARG;
+    }
     // the frame goes into the front end's pinned buffer by the worker pool (one pass over ~1 MB), then to HBM -- unless
     // it went there while the previous frame's align ran (lom_odometry_hint_next)
     const bool staged = o->ahead_pts != nullptr && o->ahead_pts == pts && o->ahead_n == n;
@@ -878,7 +905,7 @@ int stages_device_enqueue(lom_odometry *o, const lom_point_xyzirt *pts, size_t n
     }
     if ((rc = lom_frontend_process(o->frontend, stage, n, &rel_inv, &ident, o->cfg.lidar_min_range, o->cfg.lidar_max_range)) !=
         LOM_OK) {
-        if (rc == LOM_ERR_ARG) return 1;  // a frame beyond the front end's size limit
+        if (rc == LOM_ERR_ARG && !neighbourhood) return 1;  // a frame beyond the front end's size limit
         o->error = lom_frontend_last_error(o->frontend);
         return rc;
     }
@@ -918,6 +945,7 @@ int stages_device_enqueue(lom_odometry *o, const lom_point_xyzirt *pts, size_t n
         ptrs[k++] = d_nm;     // 4
         ptrs[k++] = m_range;  // 5
         ptrs[k++] = m_grid;   // 6
+        if (neighbourhood) ptrs[k++] = d_fe + 6;  // 7 front end: a point of the frame out of range
         reader = o->matching_ds;
         if ((rc = lom_map_read_device_words_begin(reader, ptrs, k)) != LOM_OK) return fail_map(o, rc, reader);
         if ((rc = update_downsample()) != LOM_OK) return rc;
@@ -930,6 +958,7 @@ int stages_device_enqueue(lom_odometry *o, const lom_point_xyzirt *pts, size_t n
         ptrs[k++] = d_nd;     // 4
         ptrs[k++] = u_range;  // 5
         ptrs[k++] = u_grid;   // 6
+        if (neighbourhood) ptrs[k++] = d_fe + 6;  // 7
         if ((rc = lom_map_read_device_words_begin(reader, ptrs, k)) != LOM_OK) return fail_map(o, rc, reader);
     }
     ds.reader = reader;
@@ -960,6 +989,44 @@ int stages_device_finish(lom_odometry *o, lom_odometry_frame_stats &cur, FrameIn
     tm.lap("settle");
     const uint32_t fe_seq = lom_frontend_sequence(o->frontend);
     const uint32_t seq_ds = has_keyframe ? ds.seq_m : ds.seq_u;
+    if (o->classifier == LOM_CLASSIFIER_NEIGHBOURHOOD) {
+        // No host stages behind this classifier, and no azimuth bin that could be ambiguous (word [4] means nothing).
+        // A point out of range fails the frame; a scan that gave up -- the front end's or a down-sampler's -- has
+        // written nothing: the front end redoes its stage with kernels that wait for nobody (lom_frontend_wait), and
+        // both down-samplers run again from its result, each waiting for its own verdict.
+        if (got[7] == fe_seq) {
+            (void)in.collect_update(nullptr);
+            o->error = "coordinate / radius out of range or not finite";
+            return LOM_ERR_RANGE;
+        }
+        if (got[3] == fe_seq || got[6] == seq_ds) {
+            (void)in.collect_update(nullptr);
+            uint32_t counts[4] = {got[0], got[1], 0, 0};
+            if (got[3] == fe_seq) {  // (counted by the front end itself)
+                if ((rc = lom_frontend_wait(o->frontend, counts)) != LOM_OK) {
+                    o->error = lom_frontend_last_error(o->frontend);
+                    return rc;
+                }
+            } else {
+                o->grid_redos++;
+            }
+            cur.planar_points = counts[0];
+            cur.filtered_points = counts[1];
+            in.d_fx = ds.d_fx;
+            in.d_fn = ds.d_fn;
+            in.nf = counts[1];
+            in.nd = lom_voxel_downsample_device(o->update_ds, o->cfg.keyframe_update_voxel_size, ds.d_fx, ds.d_fn, (size_t)in.nf, 12,
+                                                &in.d_down, &in.d_down_n);
+            if (in.nd < 0) return fail_map(o, (int)in.nd, o->update_ds);
+            if (has_keyframe) {
+                in.nm = lom_voxel_downsample_device(o->matching_ds, o->cfg.keyframe_matching_voxel_size, ds.d_fx, nullptr,
+                                                    (size_t)in.nf, 12, &in.d_match, nullptr);
+                if (in.nm < 0) return fail_map(o, (int)in.nm, o->matching_ds);
+            }
+            return LOM_OK;
+        }
+        got[2] = fe_seq - 1u;  // (never the frame's number: the checks below are the ring classifier's)
+    }
     // An azimuth on a bin boundary, an organised cloud beyond the buffers -- or an in-kernel scan of the front end
     // or of the down-sampler that gave up waiting: such a grid has written nothing and left its tables at rest
     // (grid_scan.hpp), so the frame simply takes the host stages, whose kernels wait for nobody.

@@ -153,4 +153,12 @@ LOM_HD void manifold_plus(const double x[7], const double d[6], double out[7])
     for (int i = 0; i < 3; i++) out[4 + i] = x[4 + i] + d[3 + i];
 }
 
+// the value ranges of lom_neighbourhood_params (host only; one rule for lom_frontend_* and lom_odometry_*)
+inline bool neighbourhood_params_ok(const lom_neighbourhood_params *p)
+{
+    return p && p->radius > 0.f && p->radius <= 3.402823466e+38f && p->index_cap >= 1u && p->index_cap <= 64u &&
+           p->min_neighbours >= 3u && p->max_variation > 0.f && p->max_variation <= 1.0f / 3.0f && p->min_spread >= 0.f &&
+           p->min_spread < 1.f;
+}
+
 }  // namespace lom

@@ -1,0 +1,256 @@
+"""Neighbourhood classifier on the device (csrc/k_neighbourhood.hpp, launched from csrc/frontend.hip) against the
+numpy f64 reference of tests/neighbourhood_ref.py: the stage alone, inside the front end, and under the odometry."""
+import json
+import os
+
+import numpy as np
+import pytest
+
+from lidar_odometry_demo_amd import synth
+from tests import neighbourhood_ref as R
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def fe(lom):
+    return lom.FrontEnd()
+
+
+@pytest.fixture(scope="module")
+def room():
+    xyz, lab = R.room_scene()
+    return xyz, lab, R.classify(xyz, R.ROOM_PARAMS)
+
+
+def check_against_reference(lom, fe, xyz, p, ref=None):
+    """Every per-point check of the issue; returns (planar xyz, normals, details) of the device."""
+    ref = R.classify(xyz, p) if ref is None else ref
+    n = len(xyz)
+    oxyz, onrm, det = lom.classifyNeighbourhood(R.cloud(xyz), p, details=True, frontend=fe)
+    assert det.shape == (n,)
+    ok_count = ~ref["ill_count"]
+    assert np.array_equal(det["neighbours"][ok_count], ref["neighbours"][ok_count])
+    ok_flag = ~ref["ill_flag"]
+    assert np.array_equal(det["planar"][ok_flag] != 0, ref["planar"][ok_flag])
+    # eigenvalues: f64 sums of at most 27 * 64 terms and a few Jacobi rotations
+    err = np.abs(det["eig"] - ref["eig"])[ok_count]
+    scale = ref["eig"][ok_count, 2:3]
+    print("n", n, "planar", int((det["planar"] != 0).sum()), "worst eigenvalue error / l2",
+          float((err / np.maximum(scale, 1e-300)).max()) if err.size else 0.0)
+    assert (err <= 1e-11 * scale).all()
+    # the output is exactly the flagged points, in input order; the returned count is the number of flags
+    flagged = det["planar"] != 0
+    assert len(oxyz) == len(onrm) == int(flagged.sum())
+    assert oxyz.tobytes() == np.ascontiguousarray(xyz[flagged], np.float32).tobytes()
+    if flagged.any():
+        nn = onrm.astype(np.float64)
+        assert np.allclose(np.linalg.norm(nn, axis=1), 1.0, atol=1e-5)
+        assert ((nn * xyz[flagged].astype(np.float64)).sum(1) <= 0).all()
+        stable = (ref["gap"] > R.GAP)[flagged] & ok_count[flagged]
+        dots = np.abs((nn * ref["normal"][flagged]).sum(1))
+        assert (dots[stable] > 1 - 1e-6).all(), np.sort(dots[stable])[:5]
+    return oxyz, onrm, det
+
+
+def test_room_scene(lom, fe, room):
+    xyz, lab, ref = room
+    _, _, det = check_against_reference(lom, fe, xyz, R.ROOM_PARAMS, ref)
+    planar = det["planar"] != 0
+    assert planar[lab == 0].mean() > 0.6 and not planar[lab != 0].any()
+
+
+def test_cap_semantics(lom, fe):
+    """First K of each voxel in input order; a point in a full voxel is not its own neighbour."""
+    xyz = R.blob_scene()
+    ref = R.classify(xyz, R.BLOB_PARAMS)
+    assert not ref["ill_count"].any()
+    _, _, det = check_against_reference(lom, fe, xyz, R.BLOB_PARAMS, ref)
+    assert np.array_equal(det["neighbours"], ref["neighbours"])
+    assert (~ref["stored"]).sum() > 100 and det["neighbours"].max() <= 27 * 16
+
+
+SPAN = 256  # points one workgroup of the compaction covers
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 15, 16, 17, SPAN - 1, SPAN, SPAN + 1, 2 * SPAN])
+def test_sizes_and_scan_boundaries(lom, fe, n):
+    xyz = R.plane_scene(n)
+    _, _, det = check_against_reference(lom, fe, xyz, R.ROOM_PARAMS)
+    if n >= SPAN - 1:
+        assert (det["planar"] != 0).sum() > n // 2  # the boundaries are crossed by an output that is not empty
+
+
+def test_all_planar_and_none_planar_frames(lom, fe):
+    full = R.plane_scene(3 * SPAN + 7)
+    ref = R.classify(full, R.ROOM_PARAMS)
+    assert ref["planar"].all()
+    oxyz, _, _ = check_against_reference(lom, fe, full, R.ROOM_PARAMS, ref)
+    assert len(oxyz) == len(full)
+    none = R.plane_scene(3 * SPAN + 7, planar=False)
+    ref = R.classify(none, R.ROOM_PARAMS)
+    assert not ref["planar"].any()
+    oxyz, _, _ = check_against_reference(lom, fe, none, R.ROOM_PARAMS, ref)
+    assert len(oxyz) == 0
+
+
+def test_bad_parameters_on_a_live_handle(lom, fe):
+    with pytest.raises(lom.LomError) as e:
+        lom.classifyNeighbourhood(R.cloud(R.blob_scene()), dict(R.ROOM_PARAMS, index_cap=65), frontend=fe)
+    assert e.value.code == lom.capi.ERR_ARG
+    with pytest.raises(lom.LomError) as e:
+        fe.setClassifier(lom.capi.CLASSIFIER_NEIGHBOURHOOD, None)
+    assert e.value.code == lom.capi.ERR_ARG
+    bad = R.blob_scene().copy()
+    bad[7, 1] = np.nan  # as the down-samplers treat such a frame
+    with pytest.raises(lom.LomError) as e:
+        lom.classifyNeighbourhood(R.cloud(bad), R.BLOB_PARAMS, frontend=fe)
+    assert e.value.code == lom.capi.ERR_RANGE
+
+
+@pytest.mark.parametrize("from_block", [1, 3 + 0x40000000])
+def test_give_up_is_redone_by_the_multi_launch_form(lom, room, from_block):
+    """The in-kernel scan gives up (from workgroup 1 on; workgroup 3 alone): the same bytes come out, one redo is counted."""
+    xyz, _, _ = room
+    f = lom.FrontEnd()
+    want = lom.classifyNeighbourhood(R.cloud(xyz), R.ROOM_PARAMS, details=True, frontend=f)
+    before = f.debugCounter(lom.capi.COUNTER_GRID_REDOS)
+    f.setOption(lom.capi.OPT_TEST_GRID_GIVE_UP, from_block)
+    got = lom.classifyNeighbourhood(R.cloud(xyz), R.ROOM_PARAMS, details=True, frontend=f)
+    assert f.debugCounter(lom.capi.COUNTER_GRID_REDOS) == before + 1
+    for a, b in zip(want, got):
+        assert a.tobytes() == b.tobytes()
+    again = lom.classifyNeighbourhood(R.cloud(xyz), R.ROOM_PARAMS, details=True, frontend=f)  # the hook is one shot
+    assert f.debugCounter(lom.capi.COUNTER_GRID_REDOS) == before + 1
+    assert again[0].tobytes() == want[0].tobytes()
+
+
+FRAME_PARAMS = R.params(radius=1.0, index_cap=64, min_neighbours=8, max_variation=0.01, min_spread=0.02)
+
+
+def _poses(lom):
+    q = synth.quat_from_ypr(0.6, 0.1, -0.05)
+    return [(lom.Pose3D((0.05, -0.02, 0.01), q), lom.Pose3D()),
+            (lom.Pose3D((0.4, 0.03, -0.02), synth.quat_from_ypr(-1.2, 0.0, 0.2)), lom.Pose3D((0.01, 0, 0), (1, 0, 0, 0)))]
+
+
+@pytest.mark.parametrize("which", [0, 1])
+def test_front_end_equals_the_host_composition(lom, which):
+    frame = synth.make_sequence_frame(3 + which)
+    start, end = _poses(lom)[which]
+    f = lom.FrontEnd()
+    ring_before = f.process(frame, start, end, 10.0, 30.0)
+    f.setClassifier(lom.capi.CLASSIFIER_NEIGHBOURHOOD, FRAME_PARAMS)
+    got = f.process(frame, start, end, 10.0, 30.0)
+    assert not got["redo_on_host"] and got["grid"] == (0, 0)
+    desk = lom.transformNonRigid(lom.pointTimeNormalize(frame), start, end)
+    assert got["deskewed"].tobytes() == desk.tobytes()
+    pxyz, pnrm = lom.classifyNeighbourhood(desk, FRAME_PARAMS)
+    fxyz, fnrm = lom.rangeFilter(pxyz, pnrm, 10.0, 30.0)
+    assert got["planar_points"] == len(pxyz) and len(pxyz) > 1000 and 0 < len(fxyz) < len(pxyz)
+    assert got["xyz"].tobytes() == fxyz.tobytes() and got["normals"].tobytes() == fnrm.tobytes()
+    # with the scan giving up in the middle of the frame: the same bytes, redone on the device, never "redo on the host"
+    f.setOption(lom.capi.OPT_TEST_GRID_GIVE_UP, 2)
+    again = f.process(frame, start, end, 10.0, 30.0)
+    assert not again["redo_on_host"] and f.debugCounter() == 1
+    assert again["xyz"].tobytes() == fxyz.tobytes() and again["normals"].tobytes() == fnrm.tobytes()
+    # back to the rings: the bytes of a front end that never left them
+    f.setClassifier(lom.capi.CLASSIFIER_RINGS)
+    back = f.process(frame, start, end, 10.0, 30.0)
+    fresh = lom.FrontEnd().process(frame, start, end, 10.0, 30.0)
+    for key in ("deskewed", "xyz", "normals"):
+        assert back[key].tobytes() == fresh[key].tobytes() == ring_before[key].tobytes(), key
+    for key in ("planar_points", "grid", "redo_on_host"):
+        assert back[key] == fresh[key] == ring_before[key], key
+
+
+# The two classifiers pick different points and estimate their normals differently (a cross product of two chords to
+# the previous ring against a plane fit over a 1 m ball), so the two odometries drift differently; the run recorded in
+# profiles/neighbourhood_odometry.json has the neighbourhood classifier's final position error at RATIO_RECORDED times
+# the ring classifier's.  The margin is twice that ratio, and at least the 2 the issue asks for.
+RATIO_RECORDED = 1.24
+MARGIN = max(2.0, 2.0 * RATIO_RECORDED)
+
+
+def _position_error(od, n_frames):
+    truth, _ = synth.sequence_pose(n_frames * synth.FRAME_PERIOD)
+    return float(np.linalg.norm(od.getCurrentPose().translation.astype(np.float64) - truth))
+
+
+def test_odometry_without_rings(lom):
+    n_frames = 20
+    boxes = synth.make_boxes()
+    frames = [synth.make_sequence_frame(k, boxes=boxes) for k in range(n_frames)]
+    ringless = []
+    for f in frames:
+        g = f.copy()
+        g["ring"] = 0
+        ringless.append(g)
+    kind = lom.capi.CLASSIFIER_NEIGHBOURHOOD
+    nb = lom.LidarOdometry()
+    nb.setClassifier(kind, FRAME_PARAMS)
+    nb.setQualityReport(True)
+    with pytest.raises(lom.LomError) as e:
+        nb.setOption(lom.capi.OPT_TEST_FORCE_HOST_REDO, 1)
+    assert e.value.code == lom.capi.ERR_STATE
+    poses = []
+    for k, f in enumerate(ringless):
+        if k + 1 < n_frames:
+            nb.hintNext(ringless[k + 1])
+        if k == 7:
+            nb.setOption(lom.capi.OPT_TEST_GRID_GIVE_UP, 5)  # one frame's scan gives up: redone on the device
+        nb.processCloud(f)
+        st = nb.stats
+        assert st["host_stages"] == 0, k
+        if k == 0:
+            assert st["initialised_keyframe"] == 1
+        else:
+            assert st["initialised_keyframe"] == 0 and st["outer_iterations"] > 0 and st["matching_points"] > 100, (k, st)
+            assert st["unstable_rotation"] == 0, (k, st)
+        p = nb.getCurrentPose()
+        poses.append(p.translation.tobytes() + p.rotation.tobytes())
+    assert nb.debugCounter() == 1
+    q = nb.getQuality()
+    assert q["valid"] > 100 and np.isfinite(q["rmse"])
+    # two streams stepped together: each exactly what processCloud does
+    a, b = lom.LidarOdometry(), lom.LidarOdometry()
+    for od in (a, b):
+        od.setClassifier(kind, FRAME_PARAMS)
+    for k, f in enumerate(ringless):
+        if k == 7:
+            a.setOption(lom.capi.OPT_TEST_GRID_GIVE_UP, 5)
+        lom.LidarOdometry.processBatch([a, b], [f, f])
+        for od in (a, b):
+            p = od.getCurrentPose()
+            assert p.translation.tobytes() + p.rotation.tobytes() == poses[k], k
+    # a sequence call, and back to the rings on the same object type
+    s = lom.LidarOdometry()
+    s.setClassifier(kind, FRAME_PARAMS)
+    s.processSequence(ringless)
+    p = s.getCurrentPose()
+    assert p.translation.tobytes() + p.rotation.tobytes() == poses[-1]
+    # accuracy: measured against the ring classifier on the same frames with their rings (the parent's behaviour)
+    ring = lom.LidarOdometry()
+    for f in frames:
+        ring.processCloud(f)
+    err_nb, err_ring = _position_error(nb, n_frames), _position_error(ring, n_frames)
+    zero = lom.LidarOdometry()  # what the ring classifier does without rings: recorded, not asserted
+    zero_planar, zero_error = [], None
+    try:
+        for f in ringless:
+            zero.processCloud(f)
+            zero_planar.append(int(zero.stats["planar_points"]))
+        err_zero = _position_error(zero, n_frames)
+    except lom.LomError as ex:
+        err_zero, zero_error = None, str(ex)
+    record = dict(frames=n_frames, params=FRAME_PARAMS, neighbourhood_error_m=err_nb, ring_error_m=err_ring,
+                  ratio=err_nb / err_ring, margin=MARGIN, neighbourhood_planar_last=int(nb.stats["planar_points"]),
+                  ring_planar_last=int(ring.stats["planar_points"]), ring_classifier_on_zero_rings=dict(
+                      error_m=err_zero, planar_points_max=max(zero_planar) if zero_planar else None, raised=zero_error))
+    print(json.dumps(record))
+    if os.environ.get("LOM_RECORD_PROFILES"):
+        with open(os.path.join(ROOT, "profiles", "neighbourhood_odometry.json"), "w") as fh:
+            json.dump(record, fh, indent=1)
+            fh.write("\n")
+    assert err_nb <= MARGIN * err_ring, record
