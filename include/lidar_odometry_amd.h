@@ -339,6 +339,17 @@ int lom_debug_eval_sums(lom_map *m, const float *src_xyz, size_t n, size_t strid
 int lom_debug_lm_trace(lom_map *m, const float *src_xyz, size_t n, size_t stride_bytes, const float guess_t[3],
                        const float guess_q_wxyz[4], int outer_index, double *trace_out, int *n_evals_out,
                        float out_t[3], float out_q_wxyz[4], lom_align_stats *stats_or_null);
+/* Outer iterations of the LAST device-resident lom_match_align* on this handle that the replay fold (LOM_OPT_REPLAY_FOLD)
+ * accounted for without running them: lom_align_stats.outer_iterations minus this many (k_match, k_lm) pairs did work.
+ * 0 after an align that took the host-driven loop. */
+int lom_debug_replayed_iterations(lom_map *m);
+/* The host driver's replay fold (lom_align_with_hooks: same rule, same function, csrc/lm_core.hpp), process-wide, default
+ * on; it never folds when hooks->allreduce is set.  Returns the previous setting.  For the tests. */
+int lom_debug_set_host_replay_fold(int on);
+/* The fold rule itself (csrc/lm_core.hpp, replay_fold_count; host code, no GPU): `outer` iterations are done, the last of
+ * them with `last_step_norm`; how many further iterations the reference's loop (cloud_matcher.cpp:117, :169-172) executes
+ * if each repeats that one. */
+int lom_debug_replay_fold_count(int outer, double last_step_norm);
 /* lom_debug_lm_policy: one form of the Levenberg-Marquardt policy of a solve, run on GIVEN sums (the policy sees
  * nothing else of a scan or a map; no handle is needed).  form 0: csrc/lm_core.hpp on the host (no GPU needed);
  * 1: csrc/lm_wave.hpp's first wave form; 2 / 3: the forms k_lm runs in its 512- / 256-thread shapes.  Forms 1-3 replay
@@ -409,6 +420,16 @@ typedef enum {
                                           align returned -- before the unstable-rotation override -- with the align's 0.3 m
                                           gate; lom_odometry_get_quality hands out the last frame's report.  Default 0:
                                           no extra launches, the same pose bytes */
+    LOM_OPT_REPLAY_FOLD = 9,           /* Default 1: the single device-resident align accounts for repeated outer iterations
+                                          instead of running them.  An outer iteration is a pure function of the f32 pose
+                                          it searches at; one that writes back that very pose is followed, in the reference,
+                                          by exact repeats of itself until the stop rule (which cannot fire before the fifth
+                                          iteration) ends the loop.  Pose bytes and every field of lom_align_stats are the
+                                          same either way -- the statistics describe the reference algorithm's align, folded
+                                          iterations included; lom_debug_replayed_iterations tells how many were folded.
+                                          0: every iteration runs (A/B timing, tests).  Never folds: the batched / multi-map
+                                          aligns, aligns whose ranks exchange sums (more than one rank), and an align that carries the profiling
+                                          events (lom_map_set_profiling: every bracketed launch runs) */
     LOM_OPT_TEST_GIVE_UP_AT_OUTER = 100, /* k: the k_lm of outer iteration k of the NEXT align behaves as if its
                                           workgroups had timed out waiting (one shot; -1 = off) */
     LOM_OPT_TEST_GRID_GIVE_UP = 101,   /* b >= 0: in the NEXT map-maintenance call with an in-kernel scan, workgroups

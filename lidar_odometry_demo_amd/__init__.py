@@ -103,6 +103,11 @@ class VoxelGrid:
     def debugCounter(self, which=capi.COUNTER_GRID_REDOS):
         return capi.check(capi.lib().lom_map_debug_counter(self._h, int(which)), self._h)
 
+    def replayedIterations(self):
+        """Outer iterations of the last device-resident align on this grid that the replay fold (capi.OPT_REPLAY_FOLD)
+        accounted for without running them."""
+        return capi.replayed_iterations(self._h)
+
     def setMaxPoints(self, max_points):                    # voxel_grid.h:56-59
         capi.check(capi.lib().lom_map_set_max_points(self._h, int(max_points)), self._h)
         self.max_points = int(max_points)

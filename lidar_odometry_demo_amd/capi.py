@@ -200,6 +200,7 @@ EXPORTED = [
     "lom_match_quality_batch_device", "lom_scan_quality_batch_sums", "lom_scan_quality_batch_sums_device",
     "lom_scan_quality_batch", "lom_scan_quality_batch_device", "lom_quality_batch_best", "lom_pose_lattice",
     "lom_classify_neighbourhood", "lom_frontend_set_classifier", "lom_frontend_debug_counter", "lom_odometry_set_classifier",
+    "lom_debug_replayed_iterations", "lom_debug_set_host_replay_fold", "lom_debug_replay_fold_count",
 ]
 
 # lom_option / counters of include/lidar_odometry_amd.h
@@ -209,6 +210,7 @@ OPT_NO_BULK_INSERT, OPT_TEST_BULK_PARTITION_MAX = 7, 106
 OPT_TEST_BATCH_ROUND_MAX = 107
 OPT_TEST_QUALITY_ROUND_MAX = 108
 OPT_QUALITY_REPORT = 8
+OPT_REPLAY_FOLD = 9
 OPT_TEST_GRID_GIVE_UP_MATCHING_DS, OPT_TEST_GRID_GIVE_UP_UPDATE_DS, OPT_TEST_GRID_GIVE_UP_KEYFRAME = 103, 104, 105
 COUNTER_GRID_REDOS = 0
 COUNTER_CLEANUPS_BEHIND_ALIGN = 1
@@ -314,6 +316,9 @@ def lib():
                                      C.POINTER(AlignStats)]
     L.lom_debug_lm_policy.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), dp, dp, dp, C.POINTER(C.c_int), dp,
                                       C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp]
+    L.lom_debug_replayed_iterations.argtypes = [vp]
+    L.lom_debug_set_host_replay_fold.argtypes = [C.c_int]
+    L.lom_debug_replay_fold_count.argtypes = [C.c_int, C.c_double]
     L.lom_map_set_profiling.argtypes = [vp, C.c_int]
     L.lom_map_set_stream.argtypes = [vp, vp]
     L.lom_profile_match.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_float, C.c_int, dp, dp, dp, dp]
@@ -475,6 +480,17 @@ def xyz_array(a):
     if a.ndim != 2 or a.shape[1] != 3:
         raise ValueError("expected an (n, 3) float32 array")
     return a
+
+
+def replayed_iterations(handle):
+    """lom_debug_replayed_iterations: outer iterations of the last device-resident align on `handle` (a map or a scan
+    context) that the replay fold accounted for without running them."""
+    return int(check(lib().lom_debug_replayed_iterations(handle), handle))
+
+
+def set_host_replay_fold(on):
+    """lom_debug_set_host_replay_fold: the host driver's replay fold, process-wide; returns the previous setting."""
+    return int(lib().lom_debug_set_host_replay_fold(int(bool(on))))
 
 
 def check(rc, handle=None):

@@ -11,6 +11,7 @@
 // minimiser of the same damped quadratic; poses agree far inside the 1e-4 m /
 // 1e-4 rad bar (tests/test_host_exchange.py, tests/test_gpu_parity.py).  The policy itself lives in
 // lm_core.hpp, shared with the device-resident loop.
+#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -54,9 +55,18 @@ int lm_solve(Evaluator &ev, const double first[LOM_NSUMS], double x[7], const do
     return LOM_OK;
 }
 
+// lom_debug_set_host_replay_fold: process-wide, default on
+std::atomic<int> g_replay_fold{1};
+
+bool same_bits(float a, float b) { return std::memcmp(&a, &b, sizeof a) == 0; }
+
 }  // namespace
 
 extern "C" {
+
+int lom_debug_set_host_replay_fold(int on) { return g_replay_fold.exchange(on ? 1 : 0); }
+
+int lom_debug_replay_fold_count(int outer, double last_step_norm) { return lom::replay_fold_count(outer, last_step_norm); }
 
 int lom_abi_version(void) { return LOM_ABI_VERSION; }
 
@@ -137,9 +147,30 @@ int lom_align_with_hooks(const lom_align_hooks *hooks, const float guess_t[3], c
         st.algorithmic_bytes += 444.0 * sums[31] + 12.0 * sums[29] + 12.0 * sums[28];
         st.final_cost = lr.cost;
         st.last_step_norm = lr.last_step_norm;
+        // Replay fold (lm_core.hpp, replay_fold_count): the pose written back is, bit for bit, the one this iteration
+        // searched at, so every further iteration repeats this one until the stop rule.  They are accounted for, not
+        // run.  From iteration 1 on, as on the device; not when ranks exchange sums (every rank would decide alike, but
+        // a disagreement leaves a rank waiting in the exchange: the follow-up named in DESIGN.md section 5).
+        bool same = i >= 1 && !hooks->allreduce && g_replay_fold.load() != 0;
+        for (int a = 0; a < 4; a++) same = same && same_bits((float)x[a], pq[a]);
+        for (int a = 0; a < 3; a++) same = same && same_bits((float)x[4 + a], pt[a]);
         for (int a = 0; a < 4; a++) pq[a] = (float)x[a];             // :161-164
         for (int a = 0; a < 3; a++) pt[a] = (float)x[4 + a];         // :165-167
         if (lr.last_step_norm < 1e-4 && i > 3) break;                // :169-172
+        if (same) {
+            const int folded = lom::replay_fold_count(i + 1, lr.last_step_norm);
+            for (int r = 0; r < folded; r++) {  // what the executed loop would have added, iteration by iteration
+                st.lm_iterations += lr.recorded;
+                st.evaluations += lr.evaluations;
+                st.cand_total += (int64_t)sums[29];
+                st.occ_total += (int64_t)sums[30];
+                st.queries += (int64_t)sums[31];
+                st.algorithmic_bytes += 444.0 * sums[31] + 12.0 * sums[29] + 12.0 * sums[28];
+            }
+            st.outer_iterations += folded;
+            st.match_launches += folded;
+            if (folded) break;
+        }
     }
     {   // :175 rotation.normalize(), f32
         const float n2 = (pq[0] * pq[0] + pq[1] * pq[1]) + (pq[2] * pq[2] + pq[3] * pq[3]);

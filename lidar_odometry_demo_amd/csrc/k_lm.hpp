@@ -448,6 +448,10 @@ __device__ __forceinline__ void accumulate_all(const MatchRec *__restrict__ rec,
 // the solve's state and no points, while the four point waves hold the points and the accumulators.  Each role runs a
 // loop of its own, so the compiler allocates registers for each live set on its own (one loop carried both: 256 VGPRs +
 // 34-58 AGPRs and ~200 SGPR spills, one wave per SIMD); the roles meet at the three __syncthreads() of an evaluation.
+// fold_report_seq (the single align; the batch form and ranks that exchange sums never fold): 0 = every outer iteration
+// runs; else the replay fold is on -- see the end of the kernel -- and this is the report sequence word the host looks
+// for first, that of pair kPairsAhead, which a launch that ends the align by folding before that pair writes in place of
+// its own.
 constexpr int lm_threads(int kT) { return kT == 256 ? kT + 64 : kT; }
 template <int kT, int kBlocks = (int)kMaxLmBlocks, int kRegPts = 1, bool kPolicyTwice = false, bool kBatch = false>
 __global__ __launch_bounds__(lm_threads(kT)) void k_lm(const MatchRec *__restrict__ rec, uint32_t n, AlignState *state,
@@ -456,6 +460,7 @@ __global__ __launch_bounds__(lm_threads(kT)) void k_lm(const MatchRec *__restric
                                                      uint32_t n_match_blocks, XWord *xrec,
                                                      unsigned long long seq_base, AlignReport *report,
                                                      unsigned long long report_seq,
+                                                     unsigned long long fold_report_seq,
                                                      unsigned long long timeout_ticks,
                                                      unsigned long long *dbg_stamps, P2pArgs px,
                                                      double *dbg_trace, int test_give_up,
@@ -584,6 +589,8 @@ __global__ __launch_bounds__(lm_threads(kT)) void k_lm(const MatchRec *__restric
         else return px;
     };
     if (tid < 7) s_x[tid] = (double)x0;  // cloud_matcher.cpp:122-131
+    __shared__ uint32_t s_pose0[7];  // the bits of the f32 pose this iteration searched at, for the replay fold at the end
+    if (!kBatch && tid < 7) s_pose0[tid] = __float_as_uint(x0);
     if (tid == 0) s_failed = test_give_up;  // LOM_OPT_TEST_GIVE_UP_AT_OUTER: this launch behaves as if its waits had timed out
     __syncthreads();
     unsigned long long seq = seq_base;
@@ -728,7 +735,23 @@ __global__ __launch_bounds__(lm_threads(kT)) void k_lm(const MatchRec *__restric
     float pq[4], pt[3];
     for (int a = 0; a < 4; a++) pq[a] = (float)S.x[a];      // :161-164
     for (int a = 0; a < 3; a++) pt[a] = (float)S.x[4 + a];  // :165-167
-    const int finished = ((S.last_step_norm < 1e-4 && outer > 3) || outer + 1 >= 35) ? 1 : 0;  // :117, :169-172
+    int finished = ((S.last_step_norm < 1e-4 && outer > 3) || outer + 1 >= 35) ? 1 : 0;  // :117, :169-172
+    // Replay fold (lm_core.hpp, replay_fold_count).  The pose written back equals, bit for bit, the pose this iteration
+    // searched at -- read from AlignState, where a previous k_lm derived P for k_match from exactly these seven words
+    // (not so in iteration 0, whose search took a PoseArgs built on the host) --: the next iteration would write the same
+    // records, add the same sums in the same order, take the same policy branches and end here again, and so on until
+    // the stop rule.  Those iterations are accounted for below instead of run; the kernels already enqueued for them
+    // find `finished` and return.  -0.0 against +0.0 is no equality.
+    int folded = 0;
+    if constexpr (!kBatch) {
+        if (fold_report_seq && !first_outer && !finished && ranks_args().nranks <= 1) {
+            bool same = true;
+            for (int a = 0; a < 4; a++) same = same && __float_as_uint(pq[a]) == s_pose0[a];
+            for (int a = 0; a < 3; a++) same = same && __float_as_uint(pt[a]) == s_pose0[4 + a];
+            if (same) folded = replay_fold_count(outer + 1, S.last_step_norm);
+            if (folded) finished = 1;
+        }
+    }
     AlignState st;
     float R[9];
     rotation_matrix(pq, R);  // voxel_grid.h:212
@@ -739,22 +762,32 @@ __global__ __launch_bounds__(lm_threads(kT)) void k_lm(const MatchRec *__restric
     for (int a = 0; a < 4; a++) st.pose_q[a] = pq[a];
     st.finished = finished;
     st.error = 0;
-    st.outer_done = outer + 1;
+    st.outer_done = outer + 1 + folded;
     st.lm_iterations = prev.lm_iterations + S.recorded;
     st.evaluations = prev.evaluations + S.evaluations;
-    st.pad = 0;
+    st.replayed = folded;
     st.valid_last = counters[0];
     st.valid_total = prev.valid_total + counters[0];
     st.cand_total = prev.cand_total + counters[1];
     st.occ_total = prev.occ_total + counters[2];
     st.queries_total = prev.queries_total + counters[3];
+    for (int r = 0; r < folded; r++) {  // each folded iteration adds what this one added, as the executed loop would have
+        st.lm_iterations += S.recorded;
+        st.evaluations += S.evaluations;
+        st.valid_total += counters[0];
+        st.cand_total += counters[1];
+        st.occ_total += counters[2];
+        st.queries_total += counters[3];
+    }
     st.final_cost = S.cost;
     st.last_step_norm = S.last_step_norm;
     *state = st;
     // The host reads its first report after the fifth outer iteration (the stop rule cannot fire
     // earlier, and it enqueued five pairs at once): the reports of iterations 1-4 would only cost
     // this kernel a PCIe round trip each.
+    // (a fold ends the align at iteration 5 or 35 of the reference's count, wherever it happens: it always reports)
     if (st.outer_done < kPairsAhead) return;
+    if (folded && report_seq < fold_report_seq) report_seq = fold_report_seq;  // the word the host is waiting for
     // report: payload as system-scope stores, drained, then the sequence word
     unsigned long long *dst_w = reinterpret_cast<unsigned long long *>(report);
     auto put = [&](size_t byte_off, unsigned long long v) {
@@ -766,7 +799,7 @@ __global__ __launch_bounds__(lm_threads(kT)) void k_lm(const MatchRec *__restric
     };
     put(offsetof(AlignReport, finished), two_i(st.finished, 0));
     put(offsetof(AlignReport, outer_done), two_i(st.outer_done, st.lm_iterations));
-    put(offsetof(AlignReport, evaluations), two_i(st.evaluations, 0));
+    put(offsetof(AlignReport, evaluations), two_i(st.evaluations, st.replayed));
     put(offsetof(AlignReport, pose_t), two_f(pt[0], pt[1]));
     put(offsetof(AlignReport, pose_t) + 8, two_f(pt[2], pq[0]));
     put(offsetof(AlignReport, pose_t) + 16, two_f(pq[1], pq[2]));

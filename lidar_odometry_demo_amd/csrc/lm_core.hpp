@@ -295,4 +295,20 @@ LOM_HD int lm_feed(LmState &S, const double *sums)
     return a == LM_PROPOSE ? lm_propose(S) : a;
 }
 
+// Replay fold.  An outer iteration of an align is a pure function of the f32 pose it searches at (scan, map and prior
+// anchor are fixed, every solve starts from radius 1e4): one that writes back the very pose it searched at is followed,
+// in the reference, by bit-for-bit repeats of itself until the stop rule ends the loop.  `outer`: iterations done so
+// far, the one that just ended included; `last_step_norm`: that solve's.  Returns how many further iterations the
+// reference executes if each repeats this one -- the loop of cloud_matcher.cpp:117 (cap 35) with the stop rule of
+// :169-172 (which cannot fire before the fifth iteration), run literally.
+LOM_HD int replay_fold_count(int outer, double last_step_norm)
+{
+    int further = 0;
+    for (int i = outer - 1; i < 35; i++) {  // :117; i = outer - 1: the iteration that just ended, then its repeats
+        if (i >= outer) further++;
+        if (last_step_norm < 1e-4 && i > 3) break;  // :169-172
+    }
+    return further;
+}
+
 }  // namespace lom

@@ -106,7 +106,7 @@ struct AlignState {
     int32_t error;     // a workgroup gave up waiting for the others
     int32_t outer_done;
     int32_t lm_iterations, evaluations;
-    int32_t pad;
+    int32_t replayed;  // of outer_done: iterations accounted for by the replay fold (k_lm's tail), not executed
     double valid_last, valid_total, cand_total, occ_total, queries_total;
     double final_cost, last_step_norm;
 };
@@ -115,7 +115,7 @@ struct AlignState {
 // by k_lm's workgroup 0 after every outer iteration, sequence word last
 struct AlignReport {
     unsigned long long seq;
-    int32_t finished, error, outer_done, lm_iterations, evaluations, pad;
+    int32_t finished, error, outer_done, lm_iterations, evaluations, replayed;
     float pose_t[3], pose_q[4];
     float pad2;
     double valid_last, valid_total, cand_total, occ_total, queries_total;
@@ -229,6 +229,7 @@ struct lom_map {
     uint64_t spec_mutations = 0;
     uint32_t cleanups_taken = 0;  // radius cleanups that used such a scan (lom_map_debug_counter)
     unsigned long long report_seq = 0, lm_seq = 0, lm_launches = 0;
+    int last_replayed = 0;  // outer iterations of the last align on this handle that the replay fold accounted for (lom_debug_replayed_iterations)
     // batched align (lom_match_align_batch): buffers of its own -- per-problem solve states and descriptors, records,
     // k_match counters, exchange sets per round slot, staged host scans -- and per-problem reports in pinned host memory;
     // the single align's align_state / scan_on / xrec / report are never touched by it
@@ -282,6 +283,7 @@ struct lom_map {
     bool opt_debug_timing = false;  // LOM_OPT_DEBUG_TIMING / LOM_DEBUG_TIMING=1
     bool opt_count = false;         // LOM_OPT_COUNT_CANDIDATES / LOM_COUNT_CANDIDATES=1: the searches also produce the reference-
                                     // algorithm counts (occupied voxels, stored points of all 27 neighbours): 27 slot loads per query
+    bool opt_replay_fold = true;    // LOM_OPT_REPLAY_FOLD: the single align folds repeated outer iterations (k_lm's tail; 0 = run them)
     bool opt_no_temporal = false;   // LOM_OPT_NO_TEMPORAL_BOUND / LOM_NO_TEMPORAL=1: every search at the plain max_dist bound
     unsigned long long patience_ticks = 5000000ull;  // bounded in-kernel waits: 50 ms of s_memrealtime (100 MHz)
     bool opt_no_bulk = false;       // LOM_OPT_NO_BULK_INSERT / LOM_NO_BULK_INSERT=1: batches above 65,536 points take the four-kernel path

@@ -369,6 +369,8 @@ static int hook_eval_fixed(void *user, const double q[4], const double t[3], dou
     return launch_eval(c, q, t, false, out);
 }
 
+static int hook_sums_exchanged(void *, double *, int) { return 0; }  // (launch_eval has exchanged them)
+
 static P2pArgs p2p_args(const lom_map *m)
 {
     P2pArgs A;
@@ -661,6 +663,17 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
         dbg = (unsigned long long *)m->dbg_stamps.p;
         LOM_HIP(m, hipMemsetAsync(dbg, 0, 40 * 8, m->stream));
     }
+    // The replay fold (k_lm's tail, LOM_OPT_REPLAY_FOLD): on for the single align of one GPU -- with or without an exchange
+    // attached, as long as it has one rank: nothing is exchanged then, and the align must not cost more for the
+    // communicator being there.  Out of scope, and so off: ranks that exchange sums (px.nranks > 1: every rank would take
+    // the same decision, but a disagreement is a hang) and the batched chains (kBatch compiles it out).  lom_debug_lm_trace runs the iteration it asks about, and so does an align with
+    // LOM_OPT_TEST_GIVE_UP_AT_OUTER armed: the k_lm it names has to run to give up.  An align that carries the profiling
+    // events (lom_map_set_profiling: every N-th) is a measurement of the kernels: each bracketed pair runs, so that
+    // profiled_launches stays match_launches and no empty kernel enters match_kernel_ms / lm_kernel_ms.
+    const unsigned long long fold_seq = (m->opt_replay_fold && px.nranks <= 1 && !trace_out && give_up_outer < 0 && !m->profiling)
+                                            ? seq0 + (unsigned long long)kPairsAhead
+                                            : 0ull;
+    m->last_replayed = 0;
     int lm_events = 0;
     auto launch_pair = [&](int i) -> int {
         int r = launch_match(c, guess_t, guess_q, sq_f32(0.3f), false, i > 0);
@@ -671,7 +684,7 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
         hipLaunchKernelGGL(kernel, dim3(nb), dim3(form.threads), 0, m->stream, (const MatchRec *)m->scan_on.p, c.n,
                            (AlignState *)m->align_state.p, init, i == 0 ? 1 : 0, (const uint32_t *)d_block_counters(m),
                            c.match_blocks, (XWord *)m->xrec.p, m->lm_seq, reinterpret_cast<AlignReport *>(m->d_report),
-                           seq0 + (unsigned long long)i + 1, m->patience_ticks, dbg, px,
+                           seq0 + (unsigned long long)i + 1, fold_seq, m->patience_ticks, dbg, px,
                            (d_trace && i == trace_outer) ? d_trace : (double *)nullptr, i == give_up_outer ? 1 : 0,
                            (const BatchProblem *)nullptr);
         LOM_HIP(m, hipGetLastError());
@@ -716,14 +729,16 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
     m->report_seq = seq0 + (unsigned long long)launched;
     lom_align_result res;
     result_from_report(rp, c.counted, nb, res);
+    m->last_replayed = (int)rp->replayed;
     lom_align_stats &st = res.stats;
     for (int a = 0; a < 3; a++) out_t[a] = res.t[a];
     for (int a = 0; a < 4; a++) out_q[a] = res.q_wxyz[a];
     if (m->profiling && c.prof_used) {
         LOM_HIP(m, hipStreamSynchronize(m->stream));
-        // kernels enqueued beyond the end of the loop return at once: only the executed iterations count
-        const int executed = std::min(c.prof_used, (int)rp->outer_done);
-        read_events(m, executed, lm_events, st);
+        // kernels enqueued beyond the end of the loop return at once: only the executed iterations count -- those the
+        // replay fold accounted for were not executed
+        const int executed = std::min(c.prof_used, (int)rp->outer_done - (int)rp->replayed);
+        read_events(m, executed, std::min(executed, lm_events), st);
         st.lm_profiled_launches = std::min(executed, lm_events);
     }
     st.host_launch_ms = c.launch_s * 1e3;
@@ -806,7 +821,10 @@ static int align_device_paths(lom_map *m, const char *d_src, size_t n, size_t st
     hooks.user = &c;
     hooks.match_eval = hook_match_eval;
     hooks.eval_fixed = hook_eval_fixed;
-    hooks.allreduce = nullptr;  // the rank-ordered all-gather sits inside launch_eval
+    // the rank-ordered all-gather sits inside launch_eval.  With more than one rank the hook is there all the same, doing
+    // nothing: the driver's replay fold (align_driver.cpp) is for aligns whose sums nobody exchanges
+    hooks.allreduce = ((m->comm || m->host_comm) && m->nranks > 1) ? hook_sums_exchanged : nullptr;
+    m->last_replayed = 0;
     lom_align_stats st;
     rc = lom_align_with_hooks(&hooks, guess_t, guess_q, out_t, out_q, &st);
     server_stop(m);
@@ -1060,7 +1078,7 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
             const int give_up = i == R.give_up_outer ? 1 : 0;
             hipLaunchKernelGGL(form.batch, dim3(R.nb, R.size), dim3(form.threads), 0, m->stream, (const MatchRec *)nullptr, 0u,
                                (AlignState *)nullptr, init, i == 0 ? 1 : 0, (const uint32_t *)nullptr, 0u, (XWord *)nullptr,
-                               m->batch_lm_seq, (AlignReport *)nullptr, seq0 + (unsigned long long)i + 1, m->patience_ticks,
+                               m->batch_lm_seq, (AlignReport *)nullptr, seq0 + (unsigned long long)i + 1, 0ull, m->patience_ticks,
                                (unsigned long long *)nullptr, px, (double *)nullptr, give_up, desc);
             LOM_HIP(m, hipGetLastError());
             launch_s += now_s() - t_l;
@@ -1917,6 +1935,9 @@ int lom_match_quality_batch_device(lom_map *m, const lom_quality_problem *p, int
 {
     return quality_batch_reports(m, p, count, true, max_dist, min_eig_t, min_eig_r, out, best);
 }
+
+// outer iterations of the last device-resident align on this handle that the replay fold accounted for instead of running
+int lom_debug_replayed_iterations(lom_map *m) { return m ? m->last_replayed : LOM_ERR_ARG; }
 
 // parity entry: a whole align on the device-resident path (k_match / k_lm chain) that also returns what
 // k_lm's policy saw in outer iteration `outer_index`: for every evaluation of that solve the point

@@ -1960,6 +1960,7 @@ int lom_scan_create_on_partition(lom_map *map, int part, int nparts, lom_scan **
     c->opt_debug_timing = map->opt_debug_timing;
     c->opt_no_temporal = map->opt_no_temporal;
     c->opt_count = map->opt_count;
+    c->opt_replay_fold = map->opt_replay_fold;
     c->patience_ticks = map->patience_ticks;
     if (handle_setup(c, part, nparts) != LOM_OK) {
         map->last_error = g_create_error;
@@ -2176,6 +2177,7 @@ int lom_map_set_option(lom_map *m, int option, int64_t value)
     case LOM_OPT_NO_TEMPORAL_BOUND: m->opt_no_temporal = value != 0; return LOM_OK;
     case LOM_OPT_COUNT_CANDIDATES: m->opt_count = value != 0; return LOM_OK;
     case LOM_OPT_NO_BULK_INSERT: m->opt_no_bulk = value != 0; return LOM_OK;
+    case LOM_OPT_REPLAY_FOLD: m->opt_replay_fold = value != 0; return LOM_OK;
     case LOM_OPT_TEST_BULK_PARTITION_MAX:
         if (value < 0 || value > (int64_t)kBiPartMax) return LOM_ERR_ARG;
         m->test_bulk_part_max = (uint32_t)value;
