@@ -128,6 +128,65 @@ struct DeviceBuf {
     size_t bytes = 0;
 };
 
+// one set of slab arrays (creation order), allocated and freed together (voxel_map.hip)
+struct Slabs {
+    unsigned long long *key = nullptr;  // [cap]
+    uint32_t *count = nullptr;          // [cap]
+    float *pts = nullptr, *nrm = nullptr;  // [cap][K][3]
+    uint32_t cap = 0;
+};
+
+// points per partition k_bi_group can hold in LDS (its larger shape); bounds LOM_OPT_TEST_BULK_PARTITION_MAX
+constexpr uint32_t kBiPartMax = 1024;
+
+// ---- lom_map::scr[]: the map-maintenance scratch ------------------------------------------------------------------
+// Grow-only device buffers, indexed by the enum below; voxel_map.hip is the only file that touches them.  Most slots
+// have one user.  The shared ones, by operation (element type: meaning):
+//
+//   slot      | insert, 4 kernels       | bulk insert               | radius cleanup     | down-sampler            | export / upload / transform
+//   ----------+-------------------------+---------------------------+--------------------+-------------------------+----------------------------
+//   S_IN_XYZ  | staged host points      | staged host points        |                    | staged host points      | f32[3]: exported / uploaded / transformed xyz
+//   S_IN_NRM  | staged host normals     | staged host normals       |                    | staged host normals     | f32[3]: ... normals
+//   S_PT_SLOT | u32: slot per point     | uint2: slot, old count    |                    | u32: slot per point     |
+//   S_PT_POS  | u32: arrival position   | uint4: partition records  |                    | f32[3]: kept normals    |
+//   S_FLAG    | u64: head flags (multi- | u32: bitmap of first      | u32: keep          | u32: flags (multi-      | u32: counts per slab
+//             |   launch form only)     |   appearances             |                    |   launch form only)     |
+//   S_RANK    | u64: their scan (ditto) | u32: bitmap word prefixes | u32: newid         | u32: ranks (ditto)      | u32: offsets per slab
+//   S_PT_OFF  | u32: bucket offset      | u32: ent_idx              |                    |                         |
+//   S_PT_M    | u32: bucket size        | u32: ent_w                |                    |                         |
+//   S_ITEMS   | u32: bucket lists       |                           |                    | f32[3]: kept xyz        |
+//   S_SCAN    | u64: scan temporaries   |                           | u32: scan temp.    | u32: scan temporaries   | u32: scan temporaries
+//
+// So S_FLAG / S_RANK carry five meanings and S_PT_POS three.  Nothing but call order keeps them apart; in particular
+// the cleanup scan enqueued behind an align (cleanup_scan_behind_align) leaves keep / newid in S_FLAG / S_RANK for a
+// later lom_map_radius_cleanup to take, across whatever the caller does in between.
+// S_BKT_* and S_DS_HEAD are per table slot and kept "at rest" between calls (ensure_rest); S_MISC holds the status
+// words ([0..1] u64 scan total, [4] u32 scan total / count, [5] range error, [6] voxel counter, [7] grid give-up,
+// [8] bulk insert sent back, [9..10] bulk insert, [12..15] cleanup scan behind an align) and, from byte 256, the block
+// aggregates of the single-pass kernels.
+enum {
+    S_IN_XYZ = 0,
+    S_IN_NRM,
+    S_PT_SLOT,
+    S_PT_POS,
+    S_FLAG,
+    S_RANK,
+    S_BKT_CNT,
+    S_BKT_HEAD,
+    S_BKT_OFF,
+    S_BKT_OLD,
+    S_PT_OFF,
+    S_PT_M,
+    S_ITEMS,
+    S_SCAN,
+    S_DS_HEAD,
+    S_MISC,
+    S_ENT_ROW,  // bulk insert: row of every survivor
+    S_HIST,     // bulk insert: [partition][block] counts
+    S_PART,     // bulk insert: partition sizes and starts
+    S_COUNT
+};
+
 }  // namespace lom
 
 struct lom_map {
@@ -168,20 +227,13 @@ struct lom_map {
     void *h_stage = nullptr;
     size_t h_stage_bytes = 0;
     hipEvent_t stage_ev = nullptr;
-    uint32_t slab_cap = 0;
-    unsigned long long *d_slab_key = nullptr;  // [slab_cap]
-    uint32_t *d_slab_count = nullptr;          // [slab_cap]
-    float *d_pts = nullptr;                    // [slab_cap][K][3]
-    float *d_nrm = nullptr;                    // [slab_cap][K][3]
+    lom::Slabs slabs;
     uint64_t n_points = 0;
     // second slab set: radiusCleanup compacts into it and swaps (no allocation per frame)
-    unsigned long long *alt_key = nullptr;
-    uint32_t *alt_count = nullptr;
-    float *alt_pts = nullptr, *alt_nrm = nullptr;
-    uint32_t alt_cap = 0;
+    lom::Slabs alt;
 
     // scratch (grown on demand, never shrunk)
-    lom::DeviceBuf scr[24];
+    lom::DeviceBuf scr[lom::S_COUNT];
     // sequence number of the last map-maintenance call (tags block aggregates and error words: no resets),
     // the one up to which lom_map_status has looked, and whether the table is known to be all-empty
     uint32_t call_seq = 0, status_seq = 0;
@@ -297,10 +349,13 @@ struct lom_map {
 
 namespace lom {
 
-int set_error(lom_map *m, int code, const char *what, hipError_t e = hipSuccess);
-int ensure(lom_map *m, DeviceBuf &b, size_t bytes);  // grow-only device buffer
+int set_error(lom_map *m, int code, const char *what, hipError_t e = hipSuccess);  // handle.hip
+int ensure(lom_map *m, DeviceBuf &b, size_t bytes);  // handle.hip: grow-only device buffer
 MapView view_of(const lom_map *m);
 int resolve_pending(lom_map *m);  // voxel_map.hip: redo the last single-pass insert if its in-kernel scan gave up
+int map_init(lom_map *m, size_t capacity_hint);  // voxel_map.hip: status words and the first table of a new map (lom_map_create)
+int settle_map(lom_map *map);  // voxel_map.hip: settle a pending insert and the voxel count, under the map's settle lock
+void slabs_free(Slabs &s);     // voxel_map.hip
 void cleanup_scan_behind_align(lom_map *m);  // voxel_map.hip: see lom_map_radius_cleanup_after_align
 
 #define LOM_HIP(m, expr)                                                        \

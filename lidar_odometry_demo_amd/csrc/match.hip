@@ -1357,7 +1357,7 @@ static int64_t find_pairs_core(lom_map *m, const float *src, size_t n, size_t st
     const uint32_t n_dead = mp->n_dead, dead_below = mp->dead_below;
     if (n_dead) {
         std::vector<uint32_t> cnt(dead_below);
-        LOM_HIP(m, hipMemcpy(cnt.data(), mp->d_slab_count, (size_t)dead_below * 4, hipMemcpyDeviceToHost));
+        LOM_HIP(m, hipMemcpy(cnt.data(), mp->slabs.count, (size_t)dead_below * 4, hipMemcpyDeviceToHost));
         dense.resize(dead_below);
         uint32_t live = 0;
         for (uint32_t s = 0; s < dead_below; s++) {

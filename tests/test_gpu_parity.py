@@ -1094,6 +1094,70 @@ def test_bulk_insert_beyond_two_million_points(lom, oracle):
     _assert_same_map(g, og)
 
 
+def test_bulk_insert_two_points_per_thread(lom, oracle, monkeypatch):
+    """LOM_BULK_PPT=2 at create: the claim / scatter passes of the bulk insert at two points per thread (k_bi_claim<2>,
+    k_bi_scatter<2>; four and eight are what the batch sizes of the tests above select).  One 70,000-point batch."""
+    monkeypatch.setenv("LOM_BULK_PPT", "2")
+    rng = np.random.default_rng(35)
+    g, og = _both(lom, oracle, 0.25, 3)
+    pts, nrm = _bulk_cloud(rng, 70_000, 500, 0.5)
+    g.addCloud(pts, nrm)
+    og.addCloud(pts, nrm)
+    assert g.size() == og.size() and g.debugCounter() == 0        # (the bulk path kept it: nothing sent back)
+    _assert_same_map(g, og)
+
+
+def _lattice(n):
+    """n points, one per voxel of size 1: the centres of a 64 x 64 x (n / 4096) block"""
+    i = np.arange(n)
+    return (np.stack([i % 64, (i // 64) % 64, i // 4096], axis=1) + 0.5).astype(np.float32)
+
+
+@pytest.mark.parametrize("erase", ["fewer_than_a_quarter", "more_than_a_quarter"])
+@pytest.mark.parametrize("n_vox", [65536 + 256, 262144 + 256])
+def test_radius_cleanup_in_kernel_scan_beyond_65536_voxels(lom, oracle, n_vox, erase):
+    """The cleanup's in-kernel scan at four voxels per thread (65,537 .. 262,144 voxels: k_cleanup_scan<4>) and at
+    sixteen (up to 1,048,576: k_cleanup_scan<16>), followed by either consumer: holes left in place (k_cleanup_mark,
+    fewer than a quarter of the voxels erased) and compaction (k_compact, more than a quarter).  A lattice with one
+    point per voxel, so that the voxel count is exact; an insert over the result afterwards."""
+    pts = _lattice(n_vox)
+    g, og = _both(lom, oracle, 1.0, 2)
+    g.addCloudWithoutNormals(pts)
+    og.addCloudWithoutNormals(pts)
+    assert g.size() == og.size() == n_vox
+    centre = np.array([32.0, 32.0, 0.0], np.float32)
+    d2 = ((pts - centre) ** 2).sum(axis=1)
+    r = float(np.sqrt(np.quantile(d2, 0.85 if erase == "fewer_than_a_quarter" else 0.5)))
+    g.radiusCleanup(centre, r)
+    og.radiusCleanup(centre, r)
+    erased = n_vox - og.size()
+    if erase == "fewer_than_a_quarter":
+        assert 0 < 4 * erased <= n_vox and g.debugCounter(lom.capi.COUNTER_EMPTY_SLABS) == erased
+    else:
+        assert 4 * erased > n_vox and g.debugCounter(lom.capi.COUNTER_EMPTY_SLABS) == 0
+    assert g.debugCounter() == 0                                  # (the in-kernel scan, not its multi-launch fallback)
+    _assert_same_map(g, og)
+    again = np.ascontiguousarray(pts[::3] + np.float32(0.25))     # erased voxels come back, kept ones take a second point
+    g.addCloudWithoutNormals(again)
+    og.addCloudWithoutNormals(again)
+    _assert_same_map(g, og)
+
+
+def test_fused_downsample_beyond_65536_points(lom, oracle):
+    """65,537 .. 262,144 points: the down-sampler's in-kernel scan at four points per thread (k_ds_emit<4>)."""
+    rng = np.random.default_rng(36)
+    pts = rng.uniform(-10, 10, (65536 + 256, 3)).astype(np.float32)
+    nrm = scenes._unit(rng.standard_normal(pts.shape)).astype(np.float32)
+    og = oracle.VoxelGrid(0.5, 1)
+    og.addCloud(pts, nrm)
+    oxyz, onrm = og.getCloud()
+    ws = lom.VoxelGrid(1.0, 1)
+    xyz, nrm_out = ws.downsample(pts, nrm, 0.5)
+    assert 0 < len(oxyz) < len(pts)
+    assert xyz.tobytes() == oxyz.tobytes() and nrm_out.tobytes() == onrm.tobytes()
+    assert ws.size() == 0 and ws.debugCounter() == 0              # left empty; the in-kernel scan, not its fallback
+
+
 def test_bulk_insert_range_error_inserts_nothing(lom, oracle):
     """voxel_grid.h casts unchecked; here a coordinate beyond the index range rejects the whole call (LOM_ERR_RANGE) --
     for a bulk batch too: the map is what it was, and the same batch without the bad point goes in afterwards."""
