@@ -749,6 +749,9 @@ int lom_frontend_process(lom_frontend *f, const lom_point_xyzirt *pts, size_t n,
  * its size, and the device words {planar points, filtered points, grid height, grid width, ...} */
 int lom_frontend_results(lom_frontend *f, const float **d_xyz, const float **d_nrm, const uint32_t **d_counts,
                          uint32_t *bound);
+/* device pointer and size of the last frame's deskewed cloud (what lom_frontend_fetch(what = 0) copies out), valid behind
+ * lom_frontend_done_event until the next frame is enqueued */
+int lom_frontend_deskewed(lom_frontend *f, const lom_point_xyzirt **d_out, uint32_t *n_out);
 /* wait for the frame: 0 = done on the device, 1 = redo this frame on the host, < 0 = lom_status;
  * counts_out = {planar, filtered, height, width} */
 int lom_frontend_wait(lom_frontend *f, uint32_t counts_out[4]);
@@ -872,6 +875,78 @@ const char *lom_pointcloud2_last_error(void);
 int64_t lom_estimate_normals(const float *xyz, size_t n, size_t stride_bytes, float radius, int device, float *nrm_out,
                              uint32_t *neighbours_out_or_null);
 
+/* ---- place recognition: scan descriptors and a device-resident database of them (not in the reference) ------------
+ * Which earlier place a scan belongs to, and how it is turned against that place: the stage before lom_pose_lattice /
+ * lom_match_quality_batch / lom_match_align.  A descriptor in the style of Scan Context (Kim and Kim,
+ * IROS 2018: a polar height image); a database of them in HBM; one call returns, for each of Q query descriptors, the k
+ * nearest entries with their column shift, searched exactly over all entries and all shifts.
+ *
+ * Definitions (R = rings, S = sectors):
+ *  - Cell of a point (x, y, z), f32.  In f64 from the f32 values: rho = sqrt(x^2 + y^2), ring = floor(rho / (max_range / R));
+ *    phi = atan2(y, x), moved into [0, 2 pi) (a phi that the addition of 2 pi rounds to 2 pi itself counts as 0),
+ *    sector = floor(phi / (2 pi / S)).  A point with ring >= R is ignored.  v = z - z_floor as one f32 subtraction; a point
+ *    with v <= 0 is ignored.
+ *  - Descriptor: an R x S array of f32, ring-major.  A cell holds the maximum v of its points, or 0 if it has none.  Every
+ *    stored value is >= 0, so its bit pattern orders like an unsigned integer.  The maximum does not depend on point order,
+ *    so the descriptor is a pure function of the point set.
+ *  - Bad and empty clouds: a non-finite coordinate fails the call with LOM_ERR_RANGE and nothing is stored; a cloud with
+ *    n = 0 gives the all-zero descriptor.
+ *  - Distance of query q to entry c at shift s: V = the columns j where both q's column j and c's column (j + s) mod S are
+ *    non-zero; d(s) = 1 - (1/|V|) sum_{j in V} cos(q_j, c_{(j+s) mod S}); where V is empty, d(s) = 1.  (The device works in
+ *    f32 on unit columns and reports max(d, 0).)  The pair's distance is the minimum over s; on equal distance bits the
+ *    smallest s wins.
+ *  - Result per query: the k entries of the searched id range with the smallest (distance, id); equal distance bits go to
+ *    the smaller id.  Slots beyond the number of entries searched hold id -1, distance +inf, shift 0.
+ *  - Shift to yaw: lom_place_shift_yaw(params, shift) = psi = ((S - shift) mod S) * 2 pi / S, the rotation about z that
+ *    takes the ENTRY's cloud onto the QUERY's cloud, to half a sector.  So the query sensor's rotation in the entry's
+ *    frame is Rz(-psi): a pose search for the query scan against the entry's keyframe starts at (0, 0, 0, Rz(-psi)).
+ *  - Invariance: the bits of a pair's (distance, shift) depend on the two descriptors only -- not on the number of
+ *    entries or queries, the id range, or the entry's position.
+ * There are no defaults.  1 <= rings <= 64, 1 <= sectors <= 64, max_range > 0 and finite, z_floor finite; anything else
+ * is LOM_ERR_ARG.  The database owns its stream; calls on one database are serialised by a lock inside it.  The _device
+ * forms read a cloud in HBM and wait on nothing but the database's own stream: the caller orders its producer
+ * (lom_place_db_wait_event, or a host wait), as with lom_map_add_points_device.  A NULL handle, a bad k, bad ids or a
+ * non-finite / negative descriptor value are refused with LOM_ERR_ARG before any device work. */
+typedef struct {
+    uint32_t rings, sectors;
+    float max_range, z_floor;
+} lom_place_params;
+typedef struct {
+    int64_t id;
+    float distance;
+    uint32_t shift;
+} lom_place_match;
+typedef struct lom_place_db lom_place_db;
+/* capacity_hint: entries to make room for at once; the database grows geometrically past it (ids and bytes stay) */
+int lom_place_db_create(const lom_place_params *params, int device, size_t capacity_hint, lom_place_db **out);
+void lom_place_db_destroy(lom_place_db *db);
+const char *lom_place_db_last_error(const lom_place_db *db); /* db == NULL: why the last create on this thread failed */
+int64_t lom_place_db_size(const lom_place_db *db);
+int lom_place_db_clear(lom_place_db *db); /* ids start again at 0 */
+int lom_place_db_params(const lom_place_db *db, lom_place_params *out);
+void *lom_place_db_stream(lom_place_db *db); /* hipStream_t */
+int lom_place_db_device(const lom_place_db *db);
+/* the database's stream waits for a hipEvent_t (e.g. lom_frontend_done_event) before what is enqueued next */
+int lom_place_db_wait_event(lom_place_db *db, void *hip_event);
+/* the raw R * S descriptor of a cloud; the database is a workspace here and is not changed */
+int lom_place_describe(lom_place_db *db, const float *xyz, size_t n, size_t stride_bytes, float *desc_out);
+int lom_place_describe_device(lom_place_db *db, const float *d_xyz, size_t n, size_t stride_bytes, float *desc_out);
+/* new entries; the return value is the id (0, 1, 2 ... in order of arrival) or a negative lom_status.  A raw descriptor
+ * takes the same kernel to its stored form as a cloud's does; with the _cloud forms the descriptor never leaves HBM. */
+int64_t lom_place_db_add(lom_place_db *db, const float *desc);
+int64_t lom_place_db_add_cloud(lom_place_db *db, const float *xyz, size_t n, size_t stride_bytes);
+int64_t lom_place_db_add_cloud_device(lom_place_db *db, const float *d_xyz, size_t n, size_t stride_bytes);
+int lom_place_db_get(lom_place_db *db, int64_t id, float *desc_out); /* the raw descriptor of an entry */
+/* q >= 1 descriptors (q * R * S values) against the entries [id_begin, id_end), 0 <= id_begin <= id_end <= size (a
+ * loop-closure caller leaves out the most recent entries this way; an empty range gives k empty slots); 1 <= k <= 64;
+ * out: q * k matches, the nearest first; all_dist_or_null: q * (id_end - id_begin) distances (minimum over the shifts) */
+int lom_place_db_query(lom_place_db *db, const float *desc, int q, int64_t id_begin, int64_t id_end, int k,
+                       lom_place_match *out, float *all_dist_or_null);
+/* one query straight from a cloud in HBM: describe + query with the descriptor staying on the device */
+int lom_place_db_query_cloud_device(lom_place_db *db, const float *d_xyz, size_t n, size_t stride_bytes, int64_t id_begin,
+                                    int64_t id_end, int k, lom_place_match *out);
+double lom_place_shift_yaw(const lom_place_params *params, uint32_t shift); /* NaN for invalid params */
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;
@@ -922,6 +997,13 @@ int lom_odometry_get_pose(const lom_odometry *o, lom_pose *out);   /* getCurrent
  * first frame, where the reference returns a null pointer); writes at most `cap` records; out may be
  * NULL with cap 0 (count only). */
 int64_t lom_odometry_get_temp_cloud(const lom_odometry *o, lom_point_xyzirt *out, size_t cap);
+/* The place descriptor (lom_place_describe) of that cloud -- the last frame's deskewed cloud -- through `db`, which
+ * must live on the odometry's device: read from the front end's copy in HBM where the frame's stages ran on the device
+ * (ordered behind the front end's done event), uploaded from the host copy for a host-stage frame; the result is the same
+ * either way.  add != 0: the descriptor also becomes a new entry of db, whose id goes to id_out_or_null.
+ * LOM_ERR_STATE before the first frame.  Reads only: no pose, counter or map of the odometry is touched. */
+int lom_odometry_place_descriptor(lom_odometry *o, lom_place_db *db, int add, float *desc_out_or_null,
+                                  int64_t *id_out_or_null);
 int lom_odometry_get_stats(const lom_odometry *o, lom_odometry_frame_stats *out);
 /* LOM_OPT_QUALITY_REPORT: the degeneracy thresholds of the per-frame report (lom_match_quality's min_eig_t / min_eig_r;
  * both 0 = not counted until the caller sets them: the project has no measured basis for a default), and the report of

@@ -630,6 +630,89 @@ inline PointCloud<PointNormal>::Ptr classifyNeighbourhood(FrontEnd &fe, const Po
     return planar;
 }
 
+// ---- place recognition (lom_place_*; not in the reference) --------------------------------------------
+// Scan descriptors (a polar height image in the style of Scan Context) and a database of them in HBM: which earlier
+// place a scan belongs to, and the yaw of a pose guess against it.  Definitions: lidar_odometry_amd.h.
+using PlaceParams = lom_place_params;  // {rings, sectors, max_range, z_floor}; there are no defaults
+using PlaceMatch = lom_place_match;    // {id, distance, shift}
+
+class PlaceDatabase {
+public:
+    explicit PlaceDatabase(const PlaceParams &params, size_t capacity_hint = 0, int device = 0) : params_(params)
+    {
+        const int rc = lom_place_db_create(&params, device, capacity_hint, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_place_db_last_error(nullptr));
+    }
+    ~PlaceDatabase() { lom_place_db_destroy(h_); }
+    PlaceDatabase(const PlaceDatabase &) = delete;
+    PlaceDatabase &operator=(const PlaceDatabase &) = delete;
+    lom_place_db *handle() const { return h_; }
+    const PlaceParams &params() const { return params_; }
+    size_t cells() const { return (size_t)params_.rings * params_.sectors; }
+    size_t size() const { return (size_t)check(lom_place_db_size(h_)); }
+    void clear() { check(lom_place_db_clear(h_)); }
+
+    // the raw rings x sectors descriptor (ring-major) of a cloud; any point type that starts with x, y, z
+    template <typename PointT>
+    std::vector<float> describe(const PointCloud<PointT> &cloud) const
+    {
+        std::vector<float> out(cells());
+        check(lom_place_describe(h_, reinterpret_cast<const float *>(cloud.points.data()), cloud.points.size(), sizeof(PointT),
+                                 out.data()));
+        return out;
+    }
+    int64_t add(const std::vector<float> &descriptor)
+    {
+        if (descriptor.size() != cells()) throw Error(LOM_ERR_ARG, "PlaceDatabase::add: rings * sectors values");
+        return check(lom_place_db_add(h_, descriptor.data()));
+    }
+    template <typename PointT>
+    int64_t addCloud(const PointCloud<PointT> &cloud)  // describe + add, the descriptor stays in HBM
+    {
+        return check(lom_place_db_add_cloud(h_, reinterpret_cast<const float *>(cloud.points.data()), cloud.points.size(),
+                                            sizeof(PointT)));
+    }
+    std::vector<float> get(int64_t id) const
+    {
+        std::vector<float> out(cells());
+        check(lom_place_db_get(h_, id, out.data()));
+        return out;
+    }
+    // q descriptors (q * rings * sectors values) against the entries [id_begin, id_end) (id_end < 0: all): q * k matches,
+    // the nearest first; all_dist_or_null: resized to q * (id_end - id_begin) distances
+    std::vector<PlaceMatch> query(const std::vector<float> &descriptors, int k, int64_t id_begin = 0, int64_t id_end = -1,
+                                  std::vector<float> *all_dist_or_null = nullptr) const
+    {
+        if (descriptors.empty() || descriptors.size() % cells()) throw Error(LOM_ERR_ARG, "PlaceDatabase::query: whole descriptors");
+        const int q = (int)(descriptors.size() / cells());
+        if (id_end < 0) id_end = (int64_t)size();
+        if (k < 1 || k > 64 || id_begin < 0 || id_begin > id_end) throw Error(LOM_ERR_ARG, "PlaceDatabase::query: k or id range");
+        std::vector<PlaceMatch> out((size_t)q * (size_t)k);
+        if (all_dist_or_null) all_dist_or_null->resize((size_t)q * (size_t)(id_end - id_begin));
+        check(lom_place_db_query(h_, descriptors.data(), q, id_begin, id_end, k, out.data(),
+                                 all_dist_or_null ? all_dist_or_null->data() : nullptr));
+        return out;
+    }
+    // psi = ((S - shift) mod S) 2 pi / S: the rotation about z that takes the entry's cloud onto the query's; the query
+    // sensor's rotation in the entry's frame is Rz(-psi)
+    static double shiftYaw(const PlaceParams &params, uint32_t shift)
+    {
+        const double yaw = lom_place_shift_yaw(&params, shift);
+        if (yaw != yaw) throw Error(LOM_ERR_ARG, "PlaceDatabase::shiftYaw: invalid parameters");
+        return yaw;
+    }
+    double shiftYaw(uint32_t shift) const { return shiftYaw(params_, shift); }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_place_db_last_error(h_));
+        return rc;
+    }
+    PlaceParams params_;
+    lom_place_db *h_ = nullptr;
+};
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)
@@ -719,6 +802,15 @@ public:
         QualityReport out;
         const int rc = lom_odometry_get_quality(h_, &out);
         if (rc != LOM_OK) throw Error(rc, "no quality report: the option is off or no frame has aligned yet");
+        return out;
+    }
+    // not in the reference: the place descriptor of the last frame's deskewed cloud (getTempCloud) through `db`; with
+    // id_out the descriptor also becomes a new entry of db.  Throws Error(LOM_ERR_STATE) before the first frame.
+    std::vector<float> placeDescriptor(PlaceDatabase &db, int64_t *id_out = nullptr) const
+    {
+        std::vector<float> out(db.cells());
+        const int rc = lom_odometry_place_descriptor(h_, db.handle(), id_out ? 1 : 0, out.data(), id_out);
+        if (rc != LOM_OK) throw Error(rc, rc == LOM_ERR_STATE ? "no frame yet" : lom_place_db_last_error(db.handle()));
         return out;
     }
     Pose3D getCurrentPose() const  // :87-89

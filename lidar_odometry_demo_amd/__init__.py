@@ -740,6 +740,119 @@ class FrontEnd:
         return out
 
 
+def placeParams(params):
+    """capi.PlaceParams from one, from a dict with its four fields, or from a 4-tuple in the struct's order
+    (rings, sectors, max_range, z_floor).  There are no defaults."""
+    if isinstance(params, capi.PlaceParams):
+        return params
+    names = [k for k, _ in capi.PlaceParams._fields_]
+    if isinstance(params, dict):
+        if sorted(params) != sorted(names):
+            raise TypeError(f"place parameters: exactly {names}")
+        return capi.PlaceParams(**params)
+    vals = tuple(params)
+    if len(vals) != len(names):
+        raise TypeError(f"place parameters: exactly {names}")
+    return capi.PlaceParams(*vals)
+
+
+def _place_cloud(cloud):
+    """(pointer owner, n, stride) of an (n, 3) float array or of POINT_XYZIRT records"""
+    a = np.asarray(cloud)
+    if a.dtype == capi.POINT_XYZIRT:
+        a = np.ascontiguousarray(a)
+        return a, len(a), 32
+    a = capi.xyz_array(a.reshape(-1, 3) if a.size == 0 else a)
+    return a, len(a), 12
+
+
+class PlaceDatabase:
+    """Scan descriptors (a polar height image in the style of Scan Context) and a database of them in HBM
+    (lom_place_db_*, include/lidar_odometry_amd.h): query() names, for each query descriptor, the k nearest entries and
+    the column shift against each; shiftYaw() turns a shift into the yaw of a pose guess.  numpy in and out."""
+
+    def __init__(self, params, capacity_hint=0, device=0):
+        self.params = placeParams(params)
+        h = C.c_void_p()
+        rc = capi.lib().lom_place_db_create(C.byref(self.params), int(device), int(capacity_hint), C.byref(h))
+        if rc != 0:
+            text = capi.lib().lom_place_db_last_error(None)
+            raise LomError(int(rc), text.decode() if text else "lom_place_db_create")
+        self._h = h
+        self.shape = (int(self.params.rings), int(self.params.sectors))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and capi is not None:
+            capi.lib().lom_place_db_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _check(self, rc):
+        if rc < 0:
+            text = capi.lib().lom_place_db_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "")
+        return rc
+
+    def __len__(self):
+        return int(self._check(capi.lib().lom_place_db_size(self._h)))
+
+    def clear(self):
+        self._check(capi.lib().lom_place_db_clear(self._h))
+
+    def _desc(self, desc, count=None):
+        d = np.ascontiguousarray(desc, np.float32)
+        cells = self.shape[0] * self.shape[1]
+        if d.size % cells or d.size == 0 or (count is not None and d.size != count * cells):
+            raise ValueError(f"expected descriptors of shape {self.shape}")
+        return d
+
+    def describe(self, cloud):
+        """The raw (rings, sectors) descriptor of an (n, 3) cloud or of POINT_XYZIRT records; the database is unchanged."""
+        a, n, stride = _place_cloud(cloud)
+        out = np.empty(self.shape, np.float32)
+        self._check(capi.lib().lom_place_describe(self._h, a.ctypes.data if n else None, n, stride, out.ctypes.data))
+        return out
+
+    def add(self, desc):
+        """A raw descriptor becomes a new entry; returns its id (0, 1, 2 ... in order of arrival)."""
+        d = self._desc(desc, 1)
+        return int(self._check(capi.lib().lom_place_db_add(self._h, d.ctypes.data)))
+
+    def addCloud(self, cloud):
+        """describe + add with the descriptor staying in HBM; returns the id."""
+        a, n, stride = _place_cloud(cloud)
+        return int(self._check(capi.lib().lom_place_db_add_cloud(self._h, a.ctypes.data if n else None, n, stride)))
+
+    def get(self, id):
+        out = np.empty(self.shape, np.float32)
+        self._check(capi.lib().lom_place_db_get(self._h, int(id), out.ctypes.data))
+        return out
+
+    def query(self, desc, k=1, id_begin=0, id_end=None, all_dist=False):
+        """desc: one (rings, sectors) descriptor or a stack of Q of them.  Returns a (Q, k) array of capi.PLACE_MATCH
+        (id, distance, shift; nearest first; id -1 / distance inf in slots beyond the entries searched), and with
+        all_dist=True also the (Q, id_end - id_begin) distances to every entry of the range."""
+        d = self._desc(desc)
+        q = d.size // (self.shape[0] * self.shape[1])
+        if id_end is None:
+            id_end = len(self)
+        out = np.zeros((q, max(int(k), 1)), capi.PLACE_MATCH)
+        n = max(int(id_end) - int(id_begin), 0)
+        alld = np.empty((q, n), np.float32) if all_dist else None
+        self._check(capi.lib().lom_place_db_query(self._h, d.ctypes.data, q, int(id_begin), int(id_end), int(k),
+                                                  out.ctypes.data, alld.ctypes.data if all_dist else None))
+        return (out, alld) if all_dist else out
+
+    def shiftYaw(self, shift):
+        """psi = ((S - shift) mod S) 2 pi / S: the rotation about z that takes the entry's cloud onto the query's; the
+        query sensor's rotation in the entry's frame is Rz(-psi)."""
+        return float(capi.lib().lom_place_shift_yaw(C.byref(self.params), int(shift)))
+
+
 def loadPCDFile(path, with_normals=False):
     """pcl::io::loadPCDFile<pcl::PointXYZ> (test/test.cpp:194) without PCL: (n, 3) float32 xyz
     (and normals when asked; zeros if the file has none)."""
@@ -929,6 +1042,18 @@ class LidarOdometry:
         out = np.empty(n, capi.POINT_XYZIRT)
         capi.check(capi.lib().lom_odometry_get_temp_cloud(self._h, out.ctypes.data, n))
         return out
+
+    def placeDescriptor(self, db, add=False):
+        """lom_odometry_place_descriptor: the place descriptor of the last frame's deskewed cloud (getTempCloud) through
+        the PlaceDatabase `db`; add=True also stores it and returns (descriptor, id).  LomError(LOM_ERR_STATE) before the
+        first frame."""
+        out = np.empty(db.shape, np.float32)
+        id_ = C.c_int64(-1)
+        rc = capi.lib().lom_odometry_place_descriptor(self._h, db.handle, 1 if add else 0, out.ctypes.data, C.byref(id_))
+        if rc != 0:
+            text = capi.lib().lom_place_db_last_error(db.handle)
+            raise LomError(int(rc), text.decode() if text else "lom_odometry_place_descriptor")
+        return (out, int(id_.value)) if add else out
 
     def debugSetState(self, previous, current, keyframe_xyz=None, keyframe_normals=None):
         """Test hook: overwrite the two poses and, if given, rebuild the keyframe from a full export

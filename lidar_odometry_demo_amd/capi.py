@@ -144,6 +144,16 @@ assert NEIGHBOURHOOD_DETAIL.itemsize == 32
 CLASSIFIER_RINGS, CLASSIFIER_NEIGHBOURHOOD = 0, 1
 
 
+class PlaceParams(C.Structure):
+    """lom_place_params (no defaults: every field is the caller's)"""
+    _fields_ = [("rings", C.c_uint32), ("sectors", C.c_uint32), ("max_range", C.c_float), ("z_floor", C.c_float)]
+
+
+# lom_place_match, one per (query, rank)
+PLACE_MATCH = np.dtype([("id", "<i8"), ("distance", "<f4"), ("shift", "<u4")])
+assert PLACE_MATCH.itemsize == 16 and C.sizeof(PlaceParams) == 16
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -201,6 +211,11 @@ EXPORTED = [
     "lom_scan_quality_batch", "lom_scan_quality_batch_device", "lom_quality_batch_best", "lom_pose_lattice",
     "lom_classify_neighbourhood", "lom_frontend_set_classifier", "lom_frontend_debug_counter", "lom_odometry_set_classifier",
     "lom_debug_replayed_iterations", "lom_debug_set_host_replay_fold", "lom_debug_replay_fold_count",
+    "lom_place_db_create", "lom_place_db_destroy", "lom_place_db_last_error", "lom_place_db_size", "lom_place_db_clear",
+    "lom_place_db_params", "lom_place_db_stream", "lom_place_db_device", "lom_place_db_wait_event", "lom_place_describe",
+    "lom_place_describe_device", "lom_place_db_add", "lom_place_db_add_cloud", "lom_place_db_add_cloud_device",
+    "lom_place_db_get", "lom_place_db_query", "lom_place_db_query_cloud_device", "lom_place_shift_yaw",
+    "lom_odometry_place_descriptor", "lom_frontend_deskewed",
 ]
 
 # lom_option / counters of include/lidar_odometry_amd.h
@@ -446,6 +461,35 @@ def lib():
     L.lom_pose_lattice.argtypes = [pp, fp, fp, C.c_float, C.c_float, pp, C.c_int]
     L.lom_odometry_set_quality_thresholds.argtypes = [vp, C.c_float, C.c_float]
     L.lom_odometry_get_quality.argtypes = [vp, C.POINTER(QualityReport)]
+    plp = C.POINTER(PlaceParams)
+    L.lom_place_db_create.argtypes = [plp, C.c_int, C.c_size_t, C.POINTER(vp)]
+    L.lom_place_db_destroy.argtypes = [vp]
+    L.lom_place_db_destroy.restype = None
+    L.lom_place_db_last_error.argtypes = [vp]
+    L.lom_place_db_last_error.restype = C.c_char_p
+    L.lom_place_db_size.argtypes = [vp]
+    L.lom_place_db_size.restype = C.c_int64
+    L.lom_place_db_clear.argtypes = [vp]
+    L.lom_place_db_params.argtypes = [vp, plp]
+    L.lom_place_db_stream.argtypes = [vp]
+    L.lom_place_db_stream.restype = vp
+    L.lom_place_db_device.argtypes = [vp]
+    L.lom_place_db_wait_event.argtypes = [vp, vp]
+    L.lom_place_describe.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+    L.lom_place_describe_device.argtypes = L.lom_place_describe.argtypes
+    L.lom_place_db_add.argtypes = [vp, vp]
+    L.lom_place_db_add.restype = C.c_int64
+    L.lom_place_db_add_cloud.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
+    L.lom_place_db_add_cloud.restype = C.c_int64
+    L.lom_place_db_add_cloud_device.argtypes = L.lom_place_db_add_cloud.argtypes
+    L.lom_place_db_add_cloud_device.restype = C.c_int64
+    L.lom_place_db_get.argtypes = [vp, C.c_int64, vp]
+    L.lom_place_db_query.argtypes = [vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, vp]
+    L.lom_place_db_query_cloud_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int64, C.c_int64, C.c_int, vp]
+    L.lom_place_shift_yaw.argtypes = [plp, C.c_uint32]
+    L.lom_place_shift_yaw.restype = C.c_double
+    L.lom_odometry_place_descriptor.argtypes = [vp, vp, C.c_int, vp, C.POINTER(C.c_int64)]
+    L.lom_frontend_deskewed.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint32)]
     _lib = L
     return L
 

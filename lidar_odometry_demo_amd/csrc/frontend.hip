@@ -809,6 +809,14 @@ int lom_frontend_results(lom_frontend *f, const float **d_xyz, const float **d_n
     return LOM_OK;
 }
 
+int lom_frontend_deskewed(lom_frontend *f, const lom_point_xyzirt **d_out, uint32_t *n_out)
+{
+    if (!f || !d_out || !n_out) return LOM_ERR_ARG;
+    *d_out = f->d_desk;
+    *n_out = f->n_last;
+    return LOM_OK;
+}
+
 void *lom_frontend_stream(lom_frontend *f) { return f ? (void *)f->stream : nullptr; }
 uint32_t lom_frontend_sequence(const lom_frontend *f) { return f ? f->seq : 0u; }
 

@@ -680,6 +680,33 @@ int64_t lom_odometry_get_temp_cloud(const lom_odometry *o, lom_point_xyzirt *out
     return (int64_t)n;
 }
 
+// the place descriptor of that cloud (csrc/place.hip): from the front end's copy in HBM, behind its done event, or from
+// the host copy of a host-stage frame; reads only
+int lom_odometry_place_descriptor(lom_odometry *o, lom_place_db *db, int add, float *desc_out, int64_t *id_out)
+{
+    if (!o || !db || (!add && !desc_out) || lom_place_db_device(db) != o->device) return LOM_ERR_ARG;
+    if (o->temp_points == 0) return LOM_ERR_STATE;  // no frame yet
+    const size_t stride = sizeof(lom_point_xyzirt);
+    const float *pts = nullptr;
+    size_t n = o->temp_points;
+    if (o->temp_on_device) {
+        const lom_point_xyzirt *d = nullptr;
+        uint32_t nd = 0;
+        int rc = lom_frontend_deskewed(o->frontend, &d, &nd);
+        if (rc == LOM_OK) rc = lom_place_db_wait_event(db, lom_frontend_done_event(o->frontend));
+        if (rc != LOM_OK) return rc;
+        pts = reinterpret_cast<const float *>(d);
+        n = nd;
+    } else {
+        pts = reinterpret_cast<const float *>(o->deskewed.data());
+    }
+    if (!add) return o->temp_on_device ? lom_place_describe_device(db, pts, n, stride, desc_out) : lom_place_describe(db, pts, n, stride, desc_out);
+    const int64_t id = o->temp_on_device ? lom_place_db_add_cloud_device(db, pts, n, stride) : lom_place_db_add_cloud(db, pts, n, stride);
+    if (id < 0) return (int)id;
+    if (id_out) *id_out = id;
+    return desc_out ? lom_place_db_get(db, id, desc_out) : LOM_OK;
+}
+
 // test hook: overwrite previous_transform_ / current_transform_ (lidar_odometry.h:84-85); together with
 // clear + add on lom_odometry_keyframe() this lets a test put the pipeline into a given state before a frame
 int lom_odometry_debug_set_state(lom_odometry *o, const lom_pose *previous, const lom_pose *current)
