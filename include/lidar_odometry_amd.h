@@ -118,6 +118,73 @@ typedef enum {
  * xyz_out / nrm_out may be NULL (count only). */
 int64_t lom_map_export(lom_map *m, int mode, float *xyz_out, float *nrm_out, size_t cap);
 
+/* ---- ray carving (not in the reference; nothing runs it unless asked) ------------------------------------------
+ * A scan proves the voxels its rays pass through empty: lom_map_carve_rays erases the voxels that enough rays of one
+ * call crossed and no endpoint of that call fell into.  The definition, operation by operation (tests/carve_ref.py
+ * restates it in numpy f64 and the results are compared bit for bit):
+ *
+ * Inputs: a map with voxel size v (f32), an origin o and n endpoints p_i, f32, in the map's frame, and the parameters
+ * below.  There are no defaults (no measured basis for any); margin < 0, min_range <= 0, max_range <= min_range, a
+ * non-finite value or min_crossings == 0 is LOM_ERR_ARG.
+ *
+ * Range errors: a non-finite origin or endpoint, or one whose voxel index (f32 x / v, the map's own rule) leaves
+ * (-2^20, 2^20), fails the call with LOM_ERR_RANGE, and so does a walk that leaves that range; the map is unchanged.
+ *
+ * Hits: every endpoint, whatever its ray's length, protects the voxel that contains it by the insert's index rule
+ * (the correctly rounded f32 quotient x / v, truncated toward zero): if that voxel is live, hit[voxel] = 1.
+ *
+ * Walk, per ray, all in f64 from the f32 inputs, every operation rounded on its own (no contraction):
+ *   V = (double)v, O = o, D = P - O, L = sqrt(Dx*Dx + (Dy*Dy + Dz*Dz)).
+ *   If !(L >= min_range) the ray is not walked (L == 0 too).
+ *   t_end = (min(L, max_range) - margin) / L.  If !(t_end > 0) the ray is not walked.
+ *   Start cell c_a = (int)trunc(O_a / V) per axis a.
+ *   Per axis with D_a != 0: s_a = +1 or -1, the sign of D_a; the next plane's index
+ *     b_a = s_a > 0 ? (c_a >= 0 ? c_a + 1 : c_a) : (c_a <= 0 ? c_a - 1 : c_a)
+ *   and t_a = ((double)b_a * V - O_a) / D_a.  With D_a == 0: t_a = +inf.
+ *   (The truncating index's geometry: cell 0 spans (-V, V), there is no plane at 0.)
+ *   Loop: 1. the current cell counts as crossed by this ray;
+ *         2. a = the axis with the smallest t_a, ties to x before y before z;
+ *         3. if !(t_a <= t_end): stop;
+ *         4. c_a += s_a; b_a and t_a again from the new c_a by the formulas above (t_a is never incremented);
+ *         5. if |c_a| >= 2^20: range error.
+ *   A negative t_a (O_a / V rounded onto a plane) simply sorts first.  A ray visits a cell at most once.  At most
+ *   3 * (ceil(max_range / V) + 2) steps can occur; the kernel's loop is bounded by that.
+ *
+ * Decision: cross[voxel] = the number of rays of this call that visited the live voxel; a table slot without a voxel
+ * (left by an earlier erase) counts for nothing.  A voxel is erased iff it is live, cross >= min_crossings and !hit.
+ * Erasing is what lom_map_radius_cleanup's erase is: an empty slab in place, or compaction once the holes are a quarter
+ * of the slabs (LOM_DENSE_CLEANUP=1: always); a later insert into the voxel creates it anew at the end of the
+ * creation order.  A cleanup scan armed with lom_map_radius_cleanup_after_align is never taken across a carve. */
+typedef struct {
+    float margin;           /* m; the walk stops this far before the endpoint; >= 0 */
+    float min_range;        /* m; shorter rays are not walked; > 0 */
+    float max_range;        /* m; longer rays are walked to here; > min_range */
+    uint32_t min_crossings; /* >= 1: rays that must cross a voxel in this call */
+} lom_carve_params;
+
+typedef struct {
+    uint64_t rays_walked, rays_skipped; /* rays_walked + rays_skipped == n */
+    uint64_t cells_visited;             /* step 1 of the loop, summed over all rays */
+    uint32_t voxels_crossed;            /* live voxels with cross >= 1 */
+    uint32_t voxels_protected;          /* live voxels with cross >= min_crossings that a hit kept */
+    uint32_t voxels_erased;
+} lom_carve_stats;
+
+/* n == 0: nothing happens, LOM_OK.  An empty map is a map like any other: the range verdict and rays_walked / cells_visited
+ * are those of the definition, nothing is crossed.  On an error the stats are all zero.  Map handles only (a scan
+ * context: LOM_ERR_ARG).  xyz: host memory, records of
+ * stride_bytes (>= 12, a multiple of 4) that begin with x, y, z. */
+int lom_map_carve_rays(lom_map *m, const float origin[3], const float *xyz, size_t n, size_t stride_bytes,
+                       const lom_carve_params *p, lom_carve_stats *stats_or_null);
+/* the same with the endpoints in device memory (the origin stays a host array); the handle's staging buffers -- what
+ * lom_transform_points_device returned -- are not touched */
+int lom_map_carve_rays_device(lom_map *m, const float origin[3], const float *d_xyz, size_t n, size_t stride_bytes,
+                              const lom_carve_params *p, lom_carve_stats *stats_or_null);
+/* erases nothing: per live voxel, in lom_map_export's order, this call's crossing count and hit flag (host xyz).
+ * Returns the number of live voxels; writes at most `cap` entries; either output may be NULL. */
+int64_t lom_map_carve_counts(lom_map *m, const float origin[3], const float *xyz, size_t n, size_t stride_bytes,
+                             const lom_carve_params *p, uint32_t *cross_out, uint8_t *hit_out, size_t cap);
+
 /* The reference's down-sampling idiom in one pass: VoxelGrid(voxel_size, 1).addCloud(cloud)
  * followed by getCloud() / getCloudWithoutNormals() (src/lidar_odometry.cpp:37-38,42,46-47,50):
  * the first point of every voxel in input order, returned in order of first appearance -- exactly
@@ -1021,6 +1088,13 @@ int lom_odometry_set_option(lom_odometry *o, int option, int64_t value);
  * an object created with LOM_HOST_FRONTEND=1, or while LOM_OPT_TEST_FORCE_HOST_REDO is set (and setting that option while
  * it is chosen), is LOM_ERR_STATE, and a frame beyond the device front end's size limit fails with LOM_ERR_ARG. */
 int lom_odometry_set_classifier(lom_odometry *o, int kind, const lom_neighbourhood_params *p_or_null);
+/* Ray carving in the keyframe update (see "ray carving" above).  NULL, the default, launches nothing.  With parameters
+ * set, the update of every frame that aligned runs lom_map_carve_rays_device between the radius cleanup and the insert
+ * (lidar_odometry.cpp:67 / :70): the origin is the frame's pose translation, the rays are its update cloud in the map
+ * frame.  The frame that initialises the keyframe carves nothing.  lom_odometry_get_carve_stats: the last carve's stats,
+ * LOM_ERR_STATE while none has run. */
+int lom_odometry_set_carve(lom_odometry *o, const lom_carve_params *p_or_null);
+int lom_odometry_get_carve_stats(const lom_odometry *o, lom_carve_stats *out);
 int64_t lom_odometry_debug_counter(const lom_odometry *o, int which); /* LOM_COUNTER_GRID_REDOS: all its handles + frames redone */
 /* test hook (teacher-forced parity tests): overwrite previous_transform_ / current_transform_
  * (lidar_odometry.h:84-85); the keyframe itself can be replaced through lom_odometry_keyframe() */

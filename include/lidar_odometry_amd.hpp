@@ -239,6 +239,15 @@ public:
     // not in the reference: says that the next align on this grid is followed by radiusCleanup(<its result translation>,
     // radius), as lidar_odometry.cpp:65-67 does -- the cleanup's scan then runs right behind the align (results never differ)
     void radiusCleanupAfterAlign(float radius) { check(lom_map_radius_cleanup_after_align(h_, radius)); }
+    // not in the reference: ray carving ("ray carving" in lidar_odometry_amd.h) -- erase the voxels that at least
+    // params.min_crossings rays origin -> cloud[i] of this call pass through and no cloud[i] falls into
+    lom_carve_stats carveRays(const Vector3f &origin, const PointCloud<PointXYZ> &cloud, const lom_carve_params &params)
+    {
+        lom_carve_stats st{};
+        check(lom_map_carve_rays(h_, origin.v, cloud.points.empty() ? nullptr : &cloud.points.data()->x, cloud.points.size(),
+                                 sizeof(PointXYZ), &params, &st));
+        return st;
+    }
 
     size_t size() const
     {
@@ -788,6 +797,19 @@ public:
     {
         const int rc = lom_odometry_set_classifier(h_, kind, params);
         if (rc != LOM_OK) throw Error(rc, lom_odometry_last_error(h_));
+    }
+    // ray carving in the keyframe update (lom_odometry_set_carve): nullptr, the default, launches nothing
+    void setCarve(const lom_carve_params *params)
+    {
+        const int rc = lom_odometry_set_carve(h_, params);
+        if (rc != LOM_OK) throw Error(rc, lom_odometry_last_error(h_));
+    }
+    // the last keyframe update's carve; false while none has run
+    bool carveStats(lom_carve_stats &out) const
+    {
+        const int rc = lom_odometry_get_carve_stats(h_, &out);
+        if (rc != LOM_OK && rc != LOM_ERR_STATE) throw Error(rc, lom_odometry_last_error(h_));
+        return rc == LOM_OK;
     }
     // LOM_OPT_QUALITY_REPORT: every frame that aligns also gets a quality report at the pose the align returned
     void setQualityReport(bool on, float min_eig_t = 0.f, float min_eig_r = 0.f)

@@ -15,7 +15,7 @@ from . import capi
 from .capi import LomError  # noqa: F401
 
 __all__ = ["Pose3D", "VoxelGrid", "CloudMatcher", "ScanContext", "LidarOdometry", "transform_points", "pointTimeNormalize",
-           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "classifyNeighbourhood", "neighbourhoodParams", "LomError", "capi", "quality_report",
+           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "classifyNeighbourhood", "neighbourhoodParams", "carveParams", "LomError", "capi", "quality_report",
            "quality_report_batch", "pose_lattice"]
 
 
@@ -181,6 +181,35 @@ class VoxelGrid:
         """Arm the next align on this grid to enqueue the scan of radiusCleanup(<its result translation>, radius) behind
         itself (lidar_odometry.cpp:65-67's pattern); the radiusCleanup that follows takes it if its arguments match."""
         capi.check(capi.lib().lom_map_radius_cleanup_after_align(self._h, float(radius)), self._h)
+
+    def carveRays(self, origin, xyz, params, device_ptr=None, n=None, stride_bytes=12):
+        """lom_map_carve_rays ("ray carving" in the header; not in the reference): erase the voxels that at least
+        params.min_crossings rays origin -> xyz[i] of this call pass through and no xyz[i] falls into.  Returns the call's
+        capi.CarveStats as a dict.  device_ptr / n: the endpoints are in device memory (lom_map_carve_rays_device)."""
+        p = carveParams(params)
+        st = capi.CarveStats()
+        if device_ptr is not None:
+            rc = capi.lib().lom_map_carve_rays_device(self._h, capi.f3(origin), device_ptr, int(n), int(stride_bytes),
+                                                      C.byref(p), C.byref(st))
+        else:
+            xyz = capi.xyz_array(xyz)
+            rc = capi.lib().lom_map_carve_rays(self._h, capi.f3(origin), xyz.ctypes.data, len(xyz), 12, C.byref(p),
+                                               C.byref(st))
+        capi.check(rc, self._h)
+        return st.asdict()
+
+    def carveCounts(self, origin, xyz, params):
+        """lom_map_carve_counts: what carveRays would decide on, nothing erased -- (cross uint32, hit uint8) per live
+        voxel in the export's order."""
+        p = carveParams(params)
+        xyz = capi.xyz_array(xyz)
+        nv = self.size()
+        cross, hit = np.zeros(nv, np.uint32), np.zeros(nv, np.uint8)
+        got = capi.check(capi.lib().lom_map_carve_counts(self._h, capi.f3(origin), xyz.ctypes.data, len(xyz), 12,
+                                                         C.byref(p), cross.ctypes.data, hit.ctypes.data, nv), self._h)
+        if got != nv:
+            raise LomError(capi.ERR_STATE, "lom_map_carve_counts: voxel count changed")
+        return cross, hit
 
     def findMatchingPairs(self, xyz, transform, max_correspondence_distance=0.3):
         """voxel_grid.h:206-234; one entry per source point in source order (index < 0: no match)."""
@@ -668,6 +697,22 @@ def neighbourhoodParams(params):
     return capi.NeighbourhoodParams(*vals)
 
 
+def carveParams(params):
+    """capi.CarveParams from one, from a dict with its four fields, or from a 4-tuple in the struct's order (margin,
+    min_range, max_range, min_crossings).  There are no defaults."""
+    if isinstance(params, capi.CarveParams):
+        return params
+    names = [k for k, _ in capi.CarveParams._fields_]
+    if isinstance(params, dict):
+        if sorted(params) != sorted(names):
+            raise TypeError(f"carve parameters: exactly {names}")
+        return capi.CarveParams(**params)
+    vals = tuple(params)
+    if len(vals) != len(names):
+        raise TypeError(f"carve parameters: exactly {names}")
+    return capi.CarveParams(*vals)
+
+
 def classifyNeighbourhood(points, params, details=False, frontend=None):
     """The neighbourhood classifier alone (lom_classify_neighbourhood) on POINT_XYZIRT records whose `ring` is not read:
     (planar xyz, normals) in input order, and with details=True a third array of capi.NEIGHBOURHOOD_DETAIL records, one
@@ -959,6 +1004,26 @@ class LidarOdometry:
         if rc != 0:
             text = capi.lib().lom_odometry_last_error(self._h)
             raise LomError(int(rc), text.decode() if text else "lom_odometry_set_classifier")
+
+    def setCarve(self, params=None):
+        """lom_odometry_set_carve: with parameters (carveParams), every keyframe update carves free space along the
+        frame's rays before it inserts them; None (the default) launches nothing."""
+        p = carveParams(params) if params is not None else None
+        rc = capi.lib().lom_odometry_set_carve(self._h, C.byref(p) if p is not None else None)
+        if rc != 0:
+            text = capi.lib().lom_odometry_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "lom_odometry_set_carve")
+
+    def carveStats(self):
+        """The last keyframe update's carve (capi.CarveStats as a dict); None while none has run."""
+        st = capi.CarveStats()
+        rc = capi.lib().lom_odometry_get_carve_stats(self._h, C.byref(st))
+        if rc == capi.ERR_STATE:
+            return None
+        if rc != 0:
+            text = capi.lib().lom_odometry_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "lom_odometry_get_carve_stats")
+        return st.asdict()
 
     def processCloud(self, input_cloud):                   # lidar_odometry.cpp:22-77
         a = _cloud(input_cloud)

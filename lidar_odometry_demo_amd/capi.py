@@ -138,6 +138,20 @@ class NeighbourhoodParams(C.Structure):
                 ("max_variation", C.c_float), ("min_spread", C.c_float)]
 
 
+class CarveParams(C.Structure):
+    """lom_carve_params (no defaults: every field is the caller's)"""
+    _fields_ = [("margin", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float), ("min_crossings", C.c_uint32)]
+
+
+class CarveStats(C.Structure):
+    """lom_carve_stats"""
+    _fields_ = [("rays_walked", C.c_uint64), ("rays_skipped", C.c_uint64), ("cells_visited", C.c_uint64),
+                ("voxels_crossed", C.c_uint32), ("voxels_protected", C.c_uint32), ("voxels_erased", C.c_uint32)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # lom_neighbourhood_detail, one per input point
 NEIGHBOURHOOD_DETAIL = np.dtype([("neighbours", "<u4"), ("planar", "<i4"), ("eig", "<f8", 3)])
 assert NEIGHBOURHOOD_DETAIL.itemsize == 32
@@ -216,6 +230,8 @@ EXPORTED = [
     "lom_place_describe_device", "lom_place_db_add", "lom_place_db_add_cloud", "lom_place_db_add_cloud_device",
     "lom_place_db_get", "lom_place_db_query", "lom_place_db_query_cloud_device", "lom_place_shift_yaw",
     "lom_odometry_place_descriptor", "lom_frontend_deskewed",
+    "lom_map_carve_rays", "lom_map_carve_rays_device", "lom_map_carve_counts", "lom_odometry_set_carve",
+    "lom_odometry_get_carve_stats",
 ]
 
 # lom_option / counters of include/lidar_odometry_amd.h
@@ -420,6 +436,12 @@ def lib():
     L.lom_frontend_debug_counter.argtypes = [vp, C.c_int]
     L.lom_frontend_debug_counter.restype = C.c_int64
     L.lom_odometry_set_classifier.argtypes = [vp, C.c_int, C.POINTER(NeighbourhoodParams)]
+    for fn in (L.lom_map_carve_rays, L.lom_map_carve_rays_device):
+        fn.argtypes = [vp, fp, vp, C.c_size_t, C.c_size_t, C.POINTER(CarveParams), C.POINTER(CarveStats)]
+    L.lom_map_carve_counts.argtypes = [vp, fp, vp, C.c_size_t, C.c_size_t, C.POINTER(CarveParams), vp, vp, C.c_size_t]
+    L.lom_map_carve_counts.restype = C.c_int64
+    L.lom_odometry_set_carve.argtypes = [vp, C.POINTER(CarveParams)]
+    L.lom_odometry_get_carve_stats.argtypes = [vp, C.POINTER(CarveStats)]
     L.lom_host_comm_set_timeout.argtypes = [vp, C.c_double]
     L.lom_host_comm_abort.argtypes = [vp]
     L.lom_host_comm_last_error.argtypes = [vp]

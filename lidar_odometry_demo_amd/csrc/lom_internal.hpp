@@ -160,6 +160,8 @@ constexpr uint32_t kBiPartMax = 1024;
 // So S_FLAG / S_RANK carry five meanings and S_PT_POS three.  Nothing but call order keeps them apart; in particular
 // the cleanup scan enqueued behind an align (cleanup_scan_behind_align) leaves keep / newid in S_FLAG / S_RANK for a
 // later lom_map_radius_cleanup to take, across whatever the caller does in between.
+// Ray carving (k_carve.hpp) keeps cross / hit / its status words in slots of its own (S_CARVE_*) and uses S_FLAG / S_RANK /
+// S_SCAN exactly as the radius cleanup does (keep, newid, scan temporaries).
 // S_BKT_* and S_DS_HEAD are per table slot and kept "at rest" between calls (ensure_rest); S_MISC holds the status
 // words ([0..1] u64 scan total, [4] u32 scan total / count, [5] range error, [6] voxel counter, [7] grid give-up,
 // [8] bulk insert sent back, [9..10] bulk insert, [12..15] cleanup scan behind an align) and, from byte 256, the block
@@ -184,6 +186,9 @@ enum {
     S_ENT_ROW,  // bulk insert: row of every survivor
     S_HIST,     // bulk insert: [partition][block] counts
     S_PART,     // bulk insert: partition sizes and starts
+    S_CARVE_CROSS,  // ray carving: u32 per slab, rays of this call that crossed the voxel
+    S_CARVE_HIT,    // ray carving: u32 per slab, an endpoint of this call fell into the voxel
+    S_CARVE_WORDS,  // ray carving: its status words (k_carve.hpp, CW_*)
     S_COUNT
 };
 

@@ -554,6 +554,11 @@ struct lom_odometry {
     bool quality_on = false, have_quality = false;
     float quality_min_eig_t = 0.f, quality_min_eig_r = 0.f;
     lom_quality_report quality{};
+    // lom_odometry_set_carve: the keyframe update carves along the update cloud's rays before it inserts them.  Read and
+    // written by the update (the helper thread, when there is one); the setter and the getter settle first.
+    bool carve_on = false, have_carve_stats = false;
+    lom_carve_params carve{};
+    lom_carve_stats carve_stats{};
     std::string deferred_error;
     // finish the previous frame's keyframe update; its failure is this call's failure
     int settle()
@@ -775,6 +780,28 @@ int lom_odometry_set_classifier(lom_odometry *o, int kind, const lom_neighbourho
         return rc;
     }
     o->classifier = kind;
+    return LOM_OK;
+}
+
+int lom_odometry_set_carve(lom_odometry *o, const lom_carve_params *p)
+{
+    // the arguments first, then the state
+    if (p && !lom::carve_params_ok(p)) return LOM_ERR_ARG;
+    if (!o) return LOM_ERR_ARG;
+    const int rc = o->settle();  // (the previous frame's update may still be reading the old setting)
+    if (rc != LOM_OK) return rc;
+    o->carve_on = p != nullptr;
+    if (p) o->carve = *p;
+    return LOM_OK;
+}
+
+int lom_odometry_get_carve_stats(const lom_odometry *o, lom_carve_stats *out)
+{
+    if (!o || !out) return LOM_ERR_ARG;
+    const int rc = const_cast<lom_odometry *>(o)->settle();  // the last carve belongs to the last frame's update
+    if (rc != LOM_OK) return rc;
+    if (!o->have_carve_stats) return LOM_ERR_STATE;
+    *out = o->carve_stats;
     return LOM_OK;
 }
 
@@ -1277,6 +1304,12 @@ int frame_commit(lom_odometry *o, Frame &f, const lom_align_stats &ast, lom_pose
         if ((rc = lom_map_radius_cleanup(o->keyframe, pose_now.t, o->cfg.keyframe_cleanup_range)) != LOM_OK)  // :67
             return bad(rc, o->keyframe);
         ut.lap("upd cleanup");
+        if (o->carve_on) {  // lom_odometry_set_carve: free space along this frame's rays, before its points go in
+            if ((rc = lom_map_carve_rays_device(o->keyframe, pose_now.t, d_upd, n_down, 12, &o->carve, &o->carve_stats)) != LOM_OK)
+                return bad(rc, o->keyframe);
+            o->have_carve_stats = true;
+            ut.lap("upd carve");
+        }
         if ((rc = lom_map_add_points_device_nowait(o->keyframe, d_upd, d_upd_n, n_down, 12)) != LOM_OK)  // :70
             return bad(rc, o->keyframe);
         ut.lap("upd enqueue");

@@ -161,4 +161,12 @@ inline bool neighbourhood_params_ok(const lom_neighbourhood_params *p)
            p->min_spread < 1.f;
 }
 
+// lom_carve_params: margin >= 0, 0 < min_range < max_range, all finite, min_crossings >= 1
+inline bool carve_params_ok(const lom_carve_params *p)
+{
+    const float big = 3.402823466e+38f;
+    return p && p->margin >= 0.f && p->margin <= big && p->min_range > 0.f && p->max_range > p->min_range &&
+           p->max_range <= big && p->min_crossings >= 1u;
+}
+
 }  // namespace lom
