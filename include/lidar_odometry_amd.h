@@ -1014,6 +1014,130 @@ int lom_place_db_query_cloud_device(lom_place_db *db, const float *d_xyz, size_t
                                     int64_t id_end, int k, lom_place_match *out);
 double lom_place_shift_yaw(const lom_place_params *params, uint32_t shift); /* NaN for invalid params */
 
+/* ---- pose graph: keyframe poses optimised on the device after a loop closure (not in the reference) ---------------
+ * The stage behind lom_place_db_query / lom_pose_lattice / lom_match_quality_batch / lom_match_align / the quality
+ * report: relative poses between keyframes, each with its information, go in as edges; the optimised
+ * keyframe poses come out.  The graph lives in HBM and its optimiser runs there.  Everything is f64: f32 cannot hold a
+ * kilometre-long trajectory to a millimetre.  There are no defaults.
+ *
+ *  - Node.  Node k has pose X_k = (R_k, t_k), stored as lom_graph_pose {t[3], q_wxyz[4]}; the quaternion is normalised
+ *    on entry.  A `fixed` flag is given when the node is added.  Ids are 0, 1, 2, ... in order of arrival.
+ *  - Edge.  (i, j, Z = (R_z, t_z), Omega, delta) with i != j.  Z is the measured pose of j in i's frame: for the align of
+ *    j's scan against i's keyframe, the align's result itself.  Omega is symmetric 6x6, row-major (its upper triangle is
+ *    read); tangent order is rotation (3, radians), then translation (3).  Omega is refused with LOM_ERR_ARG if its
+ *    Cholesky factorisation fails or a value is non-finite.  delta >= 0 is the Huber width on the Mahalanobis norm; 0
+ *    means no robust loss.
+ *  - Error of an edge.  e = [ Log(R_i^T R_j R_z^T) ; R_i^T (t_j - t_i) - t_z ], Log the rotation vector in (-pi, pi].
+ *    This is the left-perturbation error of the measurement; the quality report defines H the same way, so
+ *    lom_graph_information_from_quality is a scaling and nothing else.
+ *  - Cost.  Per edge s = e^T Omega e; rho(s) = s for delta == 0 or s <= delta^2, else 2 delta sqrt(s) - delta^2; weight
+ *    w = 1 resp. delta / sqrt(s); cost = sum 0.5 rho(s).  Linearisation: H = sum w A^T Omega A, g = sum w A^T Omega e
+ *    (IRLS, no second-order correction).
+ *  - Retraction.  R_k <- R_k Exp(a_k), t_k <- t_k + b_k; node tangent (a_k, b_k).  The quaternion is re-normalised
+ *    after each accepted step.
+ *  - Jacobians (exact).  With e_r the rotation part of e and t_ij = R_i^T (t_j - t_i):
+ *        de/d(a_i, b_i) = [ -Jl^-1(e_r), 0 ; [t_ij]x, -R_i^T ]
+ *        de/d(a_j, b_j) = [ Jl^-1(-e_r) R_z, 0 ; 0, R_i^T ]
+ *        Jl^-1(p) = I - 0.5 [p]x + c [p]x^2,  c = 1/th^2 - (1 + cos th) / (2 th sin th),  th = |p|;
+ *    below th = 1e-8 the series I - 0.5 [p]x + [p]x^2 / 12.
+ *  - Outer loop: Levenberg-Marquardt; the host decides, with one host wait per outer iteration.  Solve
+ *    (H_ff + lambda D) d = -g_f over the free nodes, D = diag(H_ff); x_new = x (+) d;
+ *    rho_gain = (cost - cost_new) / (0.5 d^T (lambda D d - g_f)).  rho_gain > 0: accept,
+ *    lambda *= max(1/3, 1 - (2 rho_gain - 1)^3), nu = 2 (lom_graph_lm_policy); otherwise lambda *= nu, nu *= 2.  Stop
+ *    when the poses in hand have max|g_f| <= gtol (LOM_GRAPH_STOP_GRADIENT: at the start, or after an accepted step),
+ *    or a step has max|d| <= xtol (LOM_GRAPH_STOP_STEP; the step is kept if it was accepted), or after max_outer
+ *    iterations (LOM_GRAPH_STOP_MAX_OUTER).  Non-finite or non-positive parameters are refused.
+ *  - Linear solve: preconditioned conjugate gradients on the device, from d = 0.  The preconditioner is block-Jacobi:
+ *    the inverse of each free node's 6x6 diagonal block of H_ff + lambda D, by Cholesky in one lane.  Stop at
+ *    r^T z <= pcg_rtol^2 * r0^T z0, or after max_pcg iterations.  A solve that hits max_pcg is not an error: the LM gain
+ *    test judges the step, and stats.pcg_capped counts such solves.
+ *  - Gauge: checked on the host before any device work, by union-find over the edges.  Every connected component must
+ *    contain a fixed node; otherwise lom_graph_optimize returns LOM_ERR_ARG and names a free node of the offending
+ *    component in lom_graph_last_error.  Nothing is regularised silently.
+ *  - Determinism: a result is a pure function of the nodes, the edges and their order; two runs return the same bytes.
+ *    Every sum over a node's incident edges runs in ascending edge id (a node's k-th incident edge goes to lane k mod 16
+ *    of a 16-lane row; the lanes' sums are added in lane order); every dot product is a fixed tree; there are no
+ *    floating-point atomics anywhere.
+ *  - Result: poses are read back as f64; lom_graph_stats.
+ * The handle owns its stream; calls on one graph are serialised by a lock inside it.  All ids, counts and values are
+ * validated before any device work; a refused call leaves the graph as it was.  The graph grows geometrically past the
+ * hints given at create. */
+typedef struct {
+    double t[3];
+    double q_wxyz[4];
+} lom_graph_pose;
+typedef struct {
+    double lambda0, gtol, xtol, pcg_rtol;
+    int32_t max_outer, max_pcg;
+} lom_graph_params;
+enum { LOM_GRAPH_STOP_GRADIENT = 1, LOM_GRAPH_STOP_STEP = 2, LOM_GRAPH_STOP_MAX_OUTER = 3 };
+typedef struct {
+    int32_t outer;      /* LM steps solved and judged                                  */
+    int32_t accepted;   /* ... of which accepted                                       */
+    int32_t pcg_total;  /* PCG iterations of all solves                                */
+    int32_t pcg_capped; /* solves that ran max_pcg iterations without meeting pcg_rtol */
+    int32_t stop_reason;
+    int32_t pad;
+    double cost_initial, cost_final; /* at the poses on entry / on return              */
+    double grad_max;                 /* max|g_f| at the poses on return                */
+    double lambda_final;
+} lom_graph_stats;
+typedef struct lom_graph lom_graph;
+
+int lom_graph_create(int device, size_t node_hint, size_t edge_hint, lom_graph **out);
+void lom_graph_destroy(lom_graph *g);
+const char *lom_graph_last_error(const lom_graph *g); /* g == NULL: why the last create on this thread failed */
+int lom_graph_clear(lom_graph *g);                    /* no nodes, no edges; ids start again at 0 */
+void *lom_graph_stream(lom_graph *g);                 /* hipStream_t */
+int lom_graph_device(const lom_graph *g);
+/* new nodes; the return value is the (first) id or a negative lom_status.  A pose with a non-finite value or a zero
+ * quaternion is LOM_ERR_ARG; with lom_graph_add_nodes nothing is added unless every pose is good.  fixed: one int per
+ * node, non-zero = the node keeps its pose. */
+int64_t lom_graph_add_node(lom_graph *g, const lom_graph_pose *pose, int fixed);
+int64_t lom_graph_add_nodes(lom_graph *g, const lom_graph_pose *poses, const int32_t *fixed, size_t n);
+/* new edges; the return value is the (first) id.  ij: n pairs (i, j); z: n poses; omega36: n * 36 values; delta: n values.
+ * LOM_ERR_ARG for i == j, a node that does not exist, a bad pose, a bad Omega or a negative / non-finite delta; with
+ * lom_graph_add_edges nothing is added unless every edge is good. */
+int64_t lom_graph_add_edge(lom_graph *g, int64_t i, int64_t j, const lom_graph_pose *z, const double omega36[36],
+                           double delta);
+int64_t lom_graph_add_edges(lom_graph *g, const int32_t *ij, const lom_graph_pose *z, const double *omega36,
+                            const double *delta, size_t n);
+int64_t lom_graph_node_count(const lom_graph *g);
+int64_t lom_graph_edge_count(const lom_graph *g);
+int lom_graph_get_poses(lom_graph *g, int64_t first, int64_t n, lom_graph_pose *out);
+int lom_graph_set_pose(lom_graph *g, int64_t id, const lom_graph_pose *pose);
+int lom_graph_set_fixed(lom_graph *g, int64_t id, int fixed);
+/* Levenberg-Marquardt as defined above, from the poses the graph holds, which it replaces.  A graph without an edge
+ * returns at once (cost 0, LOM_GRAPH_STOP_GRADIENT).  stats may be NULL. */
+int lom_graph_optimize(lom_graph *g, const lom_graph_params *params, lom_graph_stats *stats_or_null);
+/* One linearisation at the current poses, read back; any output may be NULL.  e_out: 6 per edge; w_out: 1 per edge;
+ * cost_out: 1; g_out: 6 per node; hdiag_out: 36 per node, the node's diagonal block of H_ff + lambda D, row-major.  A
+ * fixed node's g and block read 0.  lambda >= 0 and finite. */
+int lom_graph_evaluate(lom_graph *g, double lambda, double *e_out, double *w_out, double *cost_out, double *g_out,
+                       double *hdiag_out);
+/* y = (H_ff + lambda D) p at the current poses; p, y_out: 6 per node.  A fixed node's p counts as 0 and its y reads 0. */
+int lom_graph_debug_matvec(lom_graph *g, double lambda, const double *p, double *y_out);
+/* s = e^T Omega e of the edges [first, first + n) at the current poses: after an optimisation, what a caller looks at
+ * to drop a false closure (and then builds the graph again without it). */
+int lom_graph_edge_chi2(lom_graph *g, int64_t first, int64_t n, double *out);
+
+/* Host functions of the pose graph; none needs a device. */
+/* The gauge check alone.  fixed: n_nodes ints; ij: n_edges pairs.  LOM_OK, or LOM_ERR_ARG with *bad_node_or_null a free
+ * node of a component without a fixed node (-1 where an edge has i == j or names a node that does not exist). */
+int lom_graph_check_gauge(int64_t n_nodes, const int32_t *fixed, int64_t n_edges, const int32_t *ij,
+                          int64_t *bad_node_or_null);
+/* One step of the LM policy above.  denom = d^T (lambda D d - g_f).  Returns 1 (accepted) or 0 and updates *lambda and
+ * *nu; *rho_gain_out = (cost - cost_new) / (0.5 denom).  A rho_gain that is not a number rejects. */
+int lom_graph_lm_policy(double cost, double cost_new, double denom, double *lambda, double *nu, double *rho_gain_out);
+/* Omega of an edge from the quality report of the align that measured it: S (H + P) S with
+ * S = diag(1/2, 1/2, 1/2, 1, 1, 1) (the report's rotation tangent is half the rotation vector) and, for
+ * with_prior != 0, P = 100 on the three translation diagonals (the align's translation prior, which the report leaves
+ * out).  LOM_ERR_ARG for a report with valid < 7. */
+int lom_graph_information_from_quality(const lom_quality_report *report, int with_prior, double omega_out[36]);
+/* f32 pose (w, x, y, z quaternion) to the graph's and back (rounded to nearest) */
+int lom_graph_pose_from_f32(const lom_pose *in, lom_graph_pose *out);
+int lom_graph_pose_to_f32(const lom_graph_pose *in, lom_pose *out);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;

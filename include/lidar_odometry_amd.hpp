@@ -722,6 +722,98 @@ private:
     lom_place_db *h_ = nullptr;
 };
 
+// ---- pose graph (lom_graph_*; not in the reference) --------------------------------------------------------
+// Keyframe poses and the relative poses measured between them, in HBM, optimised on the device: the stage behind
+// PlaceDatabase::query, poseLattice / qualityBatch and align.  Definitions: lidar_odometry_amd.h ("pose graph").
+using GraphPose = lom_graph_pose;      // {t[3], q_wxyz[4]}, f64
+using GraphParams = lom_graph_params;  // {lambda0, gtol, xtol, pcg_rtol, max_outer, max_pcg}; there are no defaults
+using GraphStats = lom_graph_stats;
+
+class PoseGraph {
+public:
+    explicit PoseGraph(size_t node_hint = 0, size_t edge_hint = 0, int device = 0)
+    {
+        const int rc = lom_graph_create(device, node_hint, edge_hint, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_graph_last_error(nullptr));
+    }
+    ~PoseGraph() { lom_graph_destroy(h_); }
+    PoseGraph(const PoseGraph &) = delete;
+    PoseGraph &operator=(const PoseGraph &) = delete;
+    lom_graph *handle() const { return h_; }
+    void clear() { check(lom_graph_clear(h_)); }
+    size_t nodeCount() const { return (size_t)check(lom_graph_node_count(h_)); }
+    size_t edgeCount() const { return (size_t)check(lom_graph_edge_count(h_)); }
+
+    static GraphPose fromPose3D(const Pose3D &pose)
+    {
+        const lom_pose p = pose.c();
+        GraphPose out;
+        lom_graph_pose_from_f32(&p, &out);
+        return out;
+    }
+    static Pose3D toPose3D(const GraphPose &pose)
+    {
+        lom_pose p;
+        lom_graph_pose_to_f32(&pose, &p);
+        return Pose3D::from(p);
+    }
+    // Omega of an edge (rotation in radians, then translation; row-major 6x6) from the quality report of the align that
+    // measured it; withPrior: the align's translation prior, which the report leaves out
+    static std::vector<double> informationFromQuality(const QualityReport &report, bool withPrior)
+    {
+        std::vector<double> out(36);
+        const int rc = lom_graph_information_from_quality(&report, withPrior ? 1 : 0, out.data());
+        if (rc != LOM_OK) throw Error(rc, "PoseGraph::informationFromQuality: a report with fewer than 7 correspondences");
+        return out;
+    }
+
+    int64_t addNode(const GraphPose &pose, bool fixed) { return check(lom_graph_add_node(h_, &pose, fixed ? 1 : 0)); }
+    int64_t addNode(const Pose3D &pose, bool fixed) { return addNode(fromPose3D(pose), fixed); }
+    // the measured pose of node j in node i's frame, its 6x6 information, the Huber width (0: none)
+    int64_t addEdge(int64_t i, int64_t j, const GraphPose &measurement, const std::vector<double> &info, double delta)
+    {
+        if (info.size() != 36) throw Error(LOM_ERR_ARG, "PoseGraph::addEdge: 36 values of information");
+        return check(lom_graph_add_edge(h_, i, j, &measurement, info.data(), delta));
+    }
+    int64_t addEdge(int64_t i, int64_t j, const Pose3D &measurement, const std::vector<double> &info, double delta)
+    {
+        return addEdge(i, j, fromPose3D(measurement), info, delta);
+    }
+    int64_t addEdge(int64_t i, int64_t j, const Pose3D &measurement, const QualityReport &report, bool withPrior, double delta)
+    {
+        return addEdge(i, j, fromPose3D(measurement), informationFromQuality(report, withPrior), delta);
+    }
+    void setPose(int64_t id, const GraphPose &pose) { check(lom_graph_set_pose(h_, id, &pose)); }
+    void setFixed(int64_t id, bool fixed) { check(lom_graph_set_fixed(h_, id, fixed ? 1 : 0)); }
+    GraphStats optimize(const GraphParams &params)
+    {
+        GraphStats st;
+        check(lom_graph_optimize(h_, &params, &st));
+        return st;
+    }
+    std::vector<GraphPose> poses() const
+    {
+        std::vector<GraphPose> out(nodeCount());
+        check(lom_graph_get_poses(h_, 0, (int64_t)out.size(), out.data()));
+        return out;
+    }
+    // s = e^T Omega e of every edge at the current poses
+    std::vector<double> chi2() const
+    {
+        std::vector<double> out(edgeCount());
+        check(lom_graph_edge_chi2(h_, 0, (int64_t)out.size(), out.data()));
+        return out;
+    }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_graph_last_error(h_));
+        return rc;
+    }
+    lom_graph *h_ = nullptr;
+};
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)

@@ -16,7 +16,7 @@ from .capi import LomError  # noqa: F401
 
 __all__ = ["Pose3D", "VoxelGrid", "CloudMatcher", "ScanContext", "LidarOdometry", "transform_points", "pointTimeNormalize",
            "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "classifyNeighbourhood", "neighbourhoodParams", "carveParams", "LomError", "capi", "quality_report",
-           "quality_report_batch", "pose_lattice"]
+           "quality_report_batch", "pose_lattice", "PoseGraph", "graphParams", "graph_information_from_quality"]
 
 
 class Pose3D:
@@ -896,6 +896,159 @@ class PlaceDatabase:
         """psi = ((S - shift) mod S) 2 pi / S: the rotation about z that takes the entry's cloud onto the query's; the
         query sensor's rotation in the entry's frame is Rz(-psi)."""
         return float(capi.lib().lom_place_shift_yaw(C.byref(self.params), int(shift)))
+
+
+def graphParams(params):
+    """capi.GraphParams from one, or from a dict with exactly its six fields (lambda0, gtol, xtol, pcg_rtol, max_outer,
+    max_pcg).  There are no defaults."""
+    if isinstance(params, capi.GraphParams):
+        return params
+    names = [k for k, _ in capi.GraphParams._fields_]
+    if not isinstance(params, dict) or sorted(params) != sorted(names):
+        raise TypeError(f"pose graph parameters: exactly {names}")
+    return capi.GraphParams(**params)
+
+
+def graph_information_from_quality(report, with_prior=True):
+    """lom_graph_information_from_quality: the 6x6 Omega of an edge (rotation in radians, then translation) from the
+    quality report (capi.QualityReport) of the align that measured it."""
+    out = np.empty((6, 6), np.float64)
+    rc = capi.lib().lom_graph_information_from_quality(C.byref(report), int(bool(with_prior)), out.ctypes.data)
+    if rc != 0:
+        raise LomError(int(rc), "a quality report with fewer than 7 correspondences carries no information matrix")
+    return out
+
+
+def _graph_poses(poses):
+    """capi.GRAPH_POSE records from such records, from an (n, 7) array (t, then q wxyz) or from one pose of 7 values"""
+    a = np.asarray(poses)
+    if a.dtype == capi.GRAPH_POSE:
+        return np.ascontiguousarray(a).reshape(-1)
+    if isinstance(poses, Pose3D):
+        a = np.concatenate([poses.translation, poses.rotation])
+    a = np.ascontiguousarray(a, np.float64).reshape(-1, 7)
+    out = np.empty(len(a), capi.GRAPH_POSE)
+    out["t"], out["q_wxyz"] = a[:, :3], a[:, 3:]
+    return out
+
+
+class PoseGraph:
+    """Keyframe poses and the relative poses measured between them, in HBM, optimised on the device (lom_graph_*,
+    include/lidar_odometry_amd.h "pose graph").  Poses are (n, 7) float64 arrays: t, then the quaternion w x y z; an
+    edge's measurement is the pose of node j in node i's frame.  numpy in and out."""
+
+    def __init__(self, node_hint=0, edge_hint=0, device=0):
+        h = C.c_void_p()
+        rc = capi.lib().lom_graph_create(int(device), int(node_hint), int(edge_hint), C.byref(h))
+        if rc != 0:
+            text = capi.lib().lom_graph_last_error(None)
+            raise LomError(int(rc), text.decode() if text else "lom_graph_create")
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and capi is not None:
+            capi.lib().lom_graph_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _check(self, rc):
+        if rc < 0:
+            text = capi.lib().lom_graph_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "")
+        return rc
+
+    def clear(self):
+        self._check(capi.lib().lom_graph_clear(self._h))
+
+    def nodeCount(self):
+        return int(self._check(capi.lib().lom_graph_node_count(self._h)))
+
+    def edgeCount(self):
+        return int(self._check(capi.lib().lom_graph_edge_count(self._h)))
+
+    def addNode(self, pose, fixed=False):
+        p = _graph_poses(pose)
+        return int(self._check(capi.lib().lom_graph_add_node(self._h, p.ctypes.data, int(bool(fixed)))))
+
+    def addNodes(self, poses, fixed):
+        """Returns the first id; fixed: one flag per node."""
+        p = _graph_poses(poses)
+        f = np.ascontiguousarray(np.asarray(fixed) != 0, np.int32)
+        if len(f) != len(p):
+            raise ValueError("one fixed flag per pose")
+        return int(self._check(capi.lib().lom_graph_add_nodes(self._h, p.ctypes.data, f.ctypes.data, len(p))))
+
+    def addEdge(self, i, j, measurement, information, delta):
+        """information: the 6x6 Omega (rotation in radians, then translation), or the capi.QualityReport of the align that
+        measured the edge (taken with the align's translation prior: graph_information_from_quality)."""
+        if isinstance(information, capi.QualityReport):
+            information = graph_information_from_quality(information, True)
+        z = _graph_poses(measurement)
+        om = np.ascontiguousarray(information, np.float64).reshape(36)
+        return int(self._check(capi.lib().lom_graph_add_edge(self._h, int(i), int(j), z.ctypes.data, om.ctypes.data,
+                                                             float(delta))))
+
+    def addEdges(self, ij, measurements, informations, deltas):
+        """Returns the first id.  ij: (n, 2); measurements: (n, 7); informations: (n, 6, 6); deltas: n."""
+        e = np.ascontiguousarray(ij, np.int32).reshape(-1, 2)
+        z = _graph_poses(measurements)
+        om = np.ascontiguousarray(informations, np.float64).reshape(-1, 36)
+        d = np.ascontiguousarray(deltas, np.float64).reshape(-1)
+        if not len(e) == len(z) == len(om) == len(d):
+            raise ValueError("one measurement, information and delta per edge")
+        return int(self._check(capi.lib().lom_graph_add_edges(self._h, e.ctypes.data, z.ctypes.data, om.ctypes.data,
+                                                              d.ctypes.data, len(e))))
+
+    def poses(self, first=0, n=None):
+        """(n, 7) float64: t, then q wxyz"""
+        if n is None:
+            n = self.nodeCount() - int(first)
+        out = np.empty(max(int(n), 0), capi.GRAPH_POSE)
+        self._check(capi.lib().lom_graph_get_poses(self._h, int(first), int(n), out.ctypes.data))
+        return np.concatenate([out["t"], out["q_wxyz"]], axis=1)
+
+    def setPose(self, id, pose):
+        self._check(capi.lib().lom_graph_set_pose(self._h, int(id), _graph_poses(pose).ctypes.data))
+
+    def setFixed(self, id, fixed):
+        self._check(capi.lib().lom_graph_set_fixed(self._h, int(id), int(bool(fixed))))
+
+    def optimize(self, params):
+        """Levenberg-Marquardt on the device from the poses the graph holds; returns the stats as a dict."""
+        st = capi.GraphStats()
+        self._check(capi.lib().lom_graph_optimize(self._h, C.byref(graphParams(params)), C.byref(st)))
+        return st.asdict()
+
+    def evaluate(self, lam=0.0):
+        """One linearisation at the current poses: dict of e (m, 6), w (m), cost, g (n, 6), hdiag (n, 6, 6) -- the diagonal
+        blocks of H_ff + lam D; a fixed node's g and block read 0."""
+        n, m = self.nodeCount(), self.edgeCount()
+        e, w, cost = np.zeros((m, 6)), np.zeros(m), C.c_double()
+        g, hd = np.zeros((n, 6)), np.zeros((n, 6, 6))
+        self._check(capi.lib().lom_graph_evaluate(self._h, float(lam), e.ctypes.data, w.ctypes.data, C.addressof(cost),
+                                                  g.ctypes.data, hd.ctypes.data))
+        return {"e": e, "w": w, "cost": cost.value, "g": g, "hdiag": hd}
+
+    def matvec(self, lam, p):
+        """lom_graph_debug_matvec: (H_ff + lam D) p, (n, 6) in and out"""
+        p = np.ascontiguousarray(p, np.float64)
+        if p.shape != (self.nodeCount(), 6):
+            raise ValueError("p: 6 values per node")
+        y = np.zeros_like(p)
+        self._check(capi.lib().lom_graph_debug_matvec(self._h, float(lam), p.ctypes.data, y.ctypes.data))
+        return y
+
+    def chi2(self, first=0, n=None):
+        """s = e^T Omega e per edge at the current poses"""
+        if n is None:
+            n = self.edgeCount() - int(first)
+        out = np.zeros(max(int(n), 0))
+        self._check(capi.lib().lom_graph_edge_chi2(self._h, int(first), int(n), out.ctypes.data))
+        return out
 
 
 def loadPCDFile(path, with_normals=False):

@@ -168,6 +168,28 @@ PLACE_MATCH = np.dtype([("id", "<i8"), ("distance", "<f4"), ("shift", "<u4")])
 assert PLACE_MATCH.itemsize == 16 and C.sizeof(PlaceParams) == 16
 
 
+class GraphParams(C.Structure):
+    """lom_graph_params (no defaults: every field is the caller's)"""
+    _fields_ = [("lambda0", C.c_double), ("gtol", C.c_double), ("xtol", C.c_double), ("pcg_rtol", C.c_double),
+                ("max_outer", C.c_int32), ("max_pcg", C.c_int32)]
+
+
+class GraphStats(C.Structure):
+    """lom_graph_stats"""
+    _fields_ = [("outer", C.c_int32), ("accepted", C.c_int32), ("pcg_total", C.c_int32), ("pcg_capped", C.c_int32),
+                ("stop_reason", C.c_int32), ("pad", C.c_int32), ("cost_initial", C.c_double), ("cost_final", C.c_double),
+                ("grad_max", C.c_double), ("lambda_final", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+# lom_graph_pose, one per node / measurement
+GRAPH_POSE = np.dtype([("t", "<f8", 3), ("q_wxyz", "<f8", 4)])
+assert GRAPH_POSE.itemsize == 56 and C.sizeof(GraphParams) == 40 and C.sizeof(GraphStats) == 56
+GRAPH_STOP_GRADIENT, GRAPH_STOP_STEP, GRAPH_STOP_MAX_OUTER = 1, 2, 3
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -232,6 +254,11 @@ EXPORTED = [
     "lom_odometry_place_descriptor", "lom_frontend_deskewed",
     "lom_map_carve_rays", "lom_map_carve_rays_device", "lom_map_carve_counts", "lom_odometry_set_carve",
     "lom_odometry_get_carve_stats",
+    "lom_graph_create", "lom_graph_destroy", "lom_graph_last_error", "lom_graph_clear", "lom_graph_stream", "lom_graph_device",
+    "lom_graph_add_node", "lom_graph_add_nodes", "lom_graph_add_edge", "lom_graph_add_edges", "lom_graph_node_count",
+    "lom_graph_edge_count", "lom_graph_get_poses", "lom_graph_set_pose", "lom_graph_set_fixed", "lom_graph_optimize",
+    "lom_graph_evaluate", "lom_graph_debug_matvec", "lom_graph_edge_chi2", "lom_graph_check_gauge", "lom_graph_lm_policy",
+    "lom_graph_information_from_quality", "lom_graph_pose_from_f32", "lom_graph_pose_to_f32",
 ]
 
 # lom_option / counters of include/lidar_odometry_amd.h
@@ -512,6 +539,37 @@ def lib():
     L.lom_place_shift_yaw.restype = C.c_double
     L.lom_odometry_place_descriptor.argtypes = [vp, vp, C.c_int, vp, C.POINTER(C.c_int64)]
     L.lom_frontend_deskewed.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint32)]
+    L.lom_graph_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.lom_graph_destroy.argtypes = [vp]
+    L.lom_graph_destroy.restype = None
+    L.lom_graph_last_error.argtypes = [vp]
+    L.lom_graph_last_error.restype = C.c_char_p
+    L.lom_graph_clear.argtypes = [vp]
+    L.lom_graph_stream.argtypes = [vp]
+    L.lom_graph_stream.restype = vp
+    L.lom_graph_device.argtypes = [vp]
+    L.lom_graph_add_node.argtypes = [vp, vp, C.c_int]
+    L.lom_graph_add_nodes.argtypes = [vp, vp, vp, C.c_size_t]
+    L.lom_graph_add_edge.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, C.c_double]
+    L.lom_graph_add_edges.argtypes = [vp, vp, vp, vp, vp, C.c_size_t]
+    for fn in (L.lom_graph_add_node, L.lom_graph_add_nodes, L.lom_graph_add_edge, L.lom_graph_add_edges):
+        fn.restype = C.c_int64
+    L.lom_graph_node_count.argtypes = [vp]
+    L.lom_graph_node_count.restype = C.c_int64
+    L.lom_graph_edge_count.argtypes = [vp]
+    L.lom_graph_edge_count.restype = C.c_int64
+    L.lom_graph_get_poses.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    L.lom_graph_set_pose.argtypes = [vp, C.c_int64, vp]
+    L.lom_graph_set_fixed.argtypes = [vp, C.c_int64, C.c_int]
+    L.lom_graph_optimize.argtypes = [vp, C.POINTER(GraphParams), C.POINTER(GraphStats)]
+    L.lom_graph_evaluate.argtypes = [vp, C.c_double, vp, vp, vp, vp, vp]
+    L.lom_graph_debug_matvec.argtypes = [vp, C.c_double, vp, vp]
+    L.lom_graph_edge_chi2.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    L.lom_graph_check_gauge.argtypes = [C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+    L.lom_graph_lm_policy.argtypes = [C.c_double, C.c_double, C.c_double, dp, dp, dp]
+    L.lom_graph_information_from_quality.argtypes = [C.POINTER(QualityReport), C.c_int, vp]
+    L.lom_graph_pose_from_f32.argtypes = [pp, vp]
+    L.lom_graph_pose_to_f32.argtypes = [vp, pp]
     _lib = L
     return L
 
