@@ -252,7 +252,7 @@ int64_t lom_match_find_pairs(lom_map *m, const float *src_xyz, size_t n, size_t 
 int64_t lom_match_find_pairs_sq(lom_map *m, const float *src_xyz, size_t n, size_t stride_bytes,
                                 const float t[3], const float q_wxyz[4], double max_dist_sq,
                                 lom_correspondence *out);
-/* Parity entry for the temporal pruning bound of the align's searches (csrc/match.hip): a search at the pose
+/* Parity entry for the temporal pruning bound of the align's searches (csrc/match.hip, csrc/align.hip): a search at the pose
  * (t_prev, q_prev), then the search at (t, q) with the first one's winners as upper bounds -- what outer iterations
  * >= 2 of an align run.  The result must equal lom_match_find_pairs at (t, q) entry for entry, whatever the two poses
  * are (a winner that has left a query's 27 voxels is found out and that query searched again at the plain bound). */
@@ -319,7 +319,7 @@ int lom_match_align_repeat(lom_map *m, const float *d_src_xyz, size_t n, size_t 
 /* Multi-hypothesis alignment (one scan from K guesses: relocalisation, loop-closure checks), several scans of a rig, the
  * reference's MatchingTest: CloudMatcher::align takes `const VoxelGrid&` (cloud_matcher.h:15-16), so all are legal
  * against one map at once.  The K solves run side by side in one device-resident chain -- one correspondence launch and
- * one solve launch per outer iteration for all problems of a round (csrc/match.hip "batched align").  Problems may share
+ * one solve launch per outer iteration for all problems of a round (csrc/align_batch.hip "batched align").  Problems may share
  * a cloud pointer and may differ in n (0 and 1 included).  Every result is BIT FOR BIT what lom_match_align* returns for
  * that (scan, guess) on the same handle, its counters included. */
 typedef struct {
@@ -467,7 +467,7 @@ typedef enum {
     LOM_OPT_DEBUG_TIMING = 4,          /* 1: print host launch / wait times per evaluation (stderr) */
     LOM_OPT_NO_TEMPORAL_BOUND = 5,     /* 1: every correspondence search prunes at max_dist only.  Default 0: the searches
                                           of outer iterations >= 2 of an align also prune with the previous iteration's
-                                          winner (exact, verified per query: csrc/match.hip "temporal bound"); results
+                                          winner (exact, verified per query: csrc/k_match.hpp "temporal bound"); results
                                           are the same either way, this switch exists for A/B timing (LOM_NO_TEMPORAL=1
                                           in the environment at create) */
     LOM_OPT_COUNT_CANDIDATES = 6,      /* 1: every search also produces the counts of the reference ALGORITHM -- occupied voxels
@@ -659,7 +659,7 @@ int lom_scan_quality_device(lom_scan *s, const float *d_src_xyz, size_t n, size_
  * Clouds: problems may share a cloud (equal pointer, n and stride: the pose-lattice case is one cloud and K poses; the
  *   host entries upload such a cloud once) and may differ in n, 0 and 1 included.  Every s-th point of a cloud is
  *   stride_bytes * s and n / s.
- * Rounds: the call runs as many rounds as a byte budget for a round's records and partial sums asks for (csrc/match.hip
+ * Rounds: the call runs as many rounds as a byte budget for a round's records and partial sums asks for (csrc/quality_report.hip
  *   kQualBatchBudgetBytes); all rounds are enqueued before the host waits, once.  LOM_OPT_TEST_QUALITY_ROUND_MAX caps a
  *   round's problems for the tests.
  * Determinism: the bytes of problem i's sums depend only on (map, cloud, n, stride, pose, max_dist, counted or not) --

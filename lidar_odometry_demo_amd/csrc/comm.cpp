@@ -134,7 +134,7 @@ void abandon(lom_host_comm *hc, const std::string &why)
 // LOM_OK while A -- waiting for the same late rank -- reaches its deadline in that instant and returns LOM_ERR_COMM
 // (the two-generals residue of any deadline; a second "done" round would only move the window).  What IS promised: the
 // object is broken from then on for everybody -- A marked both its slots, so the ranks that came through fail at
-// their NEXT exchange, at once.  For the agreement after a device-to-device align (match.hip align_device) this means:
+// their NEXT exchange, at once.  For the agreement after a device-to-device align (align.hip align_device_paths) this means:
 // in that one instant a rank may return the align's pose with LOM_OK while a peer returns LOM_ERR_COMM for the same
 // align; the rank that came through learns it at its next call, which fails at once instead of computing alone.
 template <typename Take>

@@ -1,6 +1,7 @@
-// What every handle owns besides a map, and nothing that launches a kernel: error text and grow-only device buffers,
+// What every handle owns besides a map, and nothing that launches a kernel: error text, grow-only device buffers and
+// pinned host blocks, the buffer groups of the batched align and the quality reports and their release, scan uploads,
 // device queries, stream and pinned blocks (handle_setup), scan contexts (lom_scan_*: creation, destruction and the
-// forwarders to the lom_match_* entries of match.hip), lom_map_create / destroy and the run-time switches.  What these
+// forwarders to the lom_match_* entries of match.hip, align.hip, align_batch.hip and quality_report.hip), lom_map_create / destroy and the run-time switches.  What these
 // need from the map side -- the first table, settling a pending insert, freeing slabs -- are lom:: functions of
 // voxel_map.hip (lom_internal.hpp).
 #include <algorithm>
@@ -50,6 +51,96 @@ int ensure(lom_map *m, DeviceBuf &b, size_t bytes)
         return set_error(m, LOM_ERR_OOM, "hipMalloc", e);
     }
     b.bytes = nb;
+    return LOM_OK;
+}
+
+int ensure_pinned(lom_map *m, PinnedBuf &b, size_t need, size_t grow_to, unsigned flags, const char *what, bool *fresh)
+{
+    if (fresh) *fresh = false;
+    if (b.h && need <= b.bytes) return LOM_OK;
+    LOM_HIP(m, hipStreamSynchronize(m->stream));
+    if (b.h) LOM_HIP(m, hipHostFree(b.h));
+    b = PinnedBuf{};
+    hipError_t e = hipHostMalloc(&b.h, grow_to, flags);
+    if (e == hipSuccess && (flags & hipHostMallocMapped)) e = hipHostGetDevicePointer(&b.d, b.h, 0);
+    if (e != hipSuccess) {
+        if (b.h) (void)hipHostFree(b.h);
+        b = PinnedBuf{};
+        return set_error(m, LOM_ERR_OOM, what, e);
+    }
+    b.bytes = grow_to;
+    if (fresh) *fresh = true;
+    return LOM_OK;
+}
+
+void release(DeviceBuf &b)
+{
+    if (b.p) (void)hipFree(b.p);
+    b = DeviceBuf{};
+}
+void release(PinnedBuf &b)
+{
+    if (b.h) (void)hipHostFree(b.h);
+    b = PinnedBuf{};
+}
+void release(BatchAlignBufs &b)
+{
+    for (DeviceBuf *d : {&b.dev, &b.rec, &b.cnt, &b.xrec, &b.src}) release(*d);
+    release(b.stage);
+    release(b.reports);
+}
+void release(QualityBufs &b)
+{
+    for (DeviceBuf *d : {&b.src, &b.idx, &b.rec, &b.cnt, &b.part, &b.res}) release(*d);
+    release(b.sums);
+}
+void release(QualityBatchBufs &b)
+{
+    for (DeviceBuf *d : {&b.src, &b.rec, &b.cnt, &b.part, &b.dev, &b.sums}) release(*d);
+    release(b.stage);
+}
+
+static inline size_t scan_bytes(size_t n, size_t stride) { return n ? (n - 1) * stride + 12 : 0; }
+
+int upload_scan(lom_map *m, DeviceBuf &buf, const void *src, size_t n, size_t stride, const char **d_src)
+{
+    const size_t bytes = scan_bytes(n, stride);
+    const int rc = ensure(m, buf, std::max<size_t>(bytes, 16));
+    if (rc != LOM_OK) return rc;
+    if (bytes) LOM_HIP(m, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, m->stream));
+    *d_src = (const char *)buf.p;
+    return LOM_OK;
+}
+
+int upload_distinct(lom_map *m, DeviceBuf &buf, const HostCloud *clouds, int count, const char **d_src)
+{
+    struct Distinct {
+        HostCloud c;
+        size_t off;
+    };
+    std::vector<Distinct> distinct;
+    std::vector<size_t> off((size_t)count);
+    size_t total = 0;
+    for (int i = 0; i < count; i++) {
+        const HostCloud &c = clouds[i];
+        off[i] = total;
+        if (!c.n) continue;
+        // (many problems on one cloud hit it at once: the newest is looked at first)
+        size_t k = distinct.size();
+        while (k-- > 0)
+            if (distinct[k].c.p == c.p && distinct[k].c.n == c.n && distinct[k].c.stride == c.stride) break;
+        if (k != (size_t)-1) {
+            off[i] = distinct[k].off;
+            continue;
+        }
+        distinct.push_back(Distinct{c, total});
+        total += (scan_bytes(c.n, c.stride) + 255) & ~size_t(255);
+    }
+    const int rc = ensure(m, buf, std::max<size_t>(total, 256));
+    if (rc != LOM_OK) return rc;
+    for (const Distinct &d : distinct)
+        LOM_HIP(m, hipMemcpyAsync((char *)buf.p + d.off, d.c.p, scan_bytes(d.c.n, d.c.stride), hipMemcpyHostToDevice, m->stream));
+    for (int i = 0; i < count; i++) d_src[i] = (const char *)buf.p + off[i];
     return LOM_OK;
 }
 
@@ -189,7 +280,7 @@ const char *lom_scan_last_error(const lom_scan *s) { return s ? reinterpret_cast
 int lom_scan_set_option(lom_scan *s, int option, int64_t value) { return lom_map_set_option(as_map(s), option, value); }
 int lom_scan_set_stream(lom_scan *s, void *hip_stream) { return lom_map_set_stream(as_map(s), hip_stream); }
 void *lom_scan_get_stream(lom_scan *s) { return lom_map_get_stream(as_map(s)); }
-// cast-and-forward to the lom_match_* entry of the same name (match.hip), one macro per signature shape
+// cast-and-forward to the lom_match_* entry of the same name, one macro per signature shape
 #define LOM_SCAN_ALIGN(name)                                                                                              \
     int lom_scan_##name(lom_scan *s, const float *src, size_t n, size_t stride, const float guess_t[3],                  \
                         const float guess_q[4], float out_t[3], float out_q[4], lom_align_stats *stats)                  \
@@ -310,24 +401,20 @@ void lom_map_destroy(lom_map *m)
     for (auto &b : m->scr)
         if (b.p) (void)hipFree(b.p);
     for (DeviceBuf *b : {&m->scan_src, &m->scan_idx, &m->scan_on, &m->scan_stats, &m->partials, &m->results, &m->gather,
-                         &m->align_state, &m->xrec, &m->dbg_trace, &m->dbg_stamps, &m->batch_dev, &m->batch_rec,
-                         &m->batch_cnt, &m->batch_xrec, &m->batch_src, &m->qual_src, &m->qual_idx, &m->qual_rec,
-                         &m->qual_cnt, &m->qual_part, &m->qual_res, &m->qualb_src, &m->qualb_rec, &m->qualb_cnt,
-                         &m->qualb_part, &m->qualb_dev, &m->qualb_sums})
-        if (b->p) (void)hipFree(b->p);
+                         &m->align_state, &m->xrec, &m->dbg_trace, &m->dbg_stamps})
+        release(*b);
+    release(m->batch);
+    release(m->qual);
+    release(m->qualb);
+    release(m->h_stage);
     if (m->h_results) (void)hipHostFree(m->h_results);
     if (m->h_flags) (void)hipHostFree(m->h_flags);
     if (m->h_mail) (void)hipHostFree(m->h_mail);
-    if (m->h_stage) (void)hipHostFree(m->h_stage);
     if (m->stage_ev) (void)hipEventDestroy(m->stage_ev);
     if (m->parent_ev) (void)hipEventDestroy(m->parent_ev);
     if (m->multi_ev) (void)hipEventDestroy(m->multi_ev);
     if (m->h_cmd) (void)hipHostFree(m->h_cmd);
     if (m->h_report) (void)hipHostFree(m->h_report);
-    if (m->h_batch) (void)hipHostFree(m->h_batch);
-    if (m->h_batch_report) (void)hipHostFree(m->h_batch_report);
-    if (m->h_qual) (void)hipHostFree(m->h_qual);
-    if (m->h_qualb) (void)hipHostFree(m->h_qualb);
     for (auto &e : m->prof_events)
         if (e) (void)hipEventDestroy(e);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
@@ -381,11 +468,11 @@ int lom_map_set_option(lom_map *m, int option, int64_t value)
         return LOM_OK;
     case LOM_OPT_TEST_BATCH_ROUND_MAX:
         if (value < 0 || value > (1 << 20)) return LOM_ERR_ARG;
-        m->test_batch_round_max = (int)value;
+        m->batch.test_round_max = (int)value;
         return LOM_OK;
     case LOM_OPT_TEST_QUALITY_ROUND_MAX:
         if (value < 0 || value > (1 << 20)) return LOM_ERR_ARG;
-        m->test_quality_round_max = (int)value;
+        m->qualb.test_round_max = (int)value;
         return LOM_OK;
     default: return set_error(m, LOM_ERR_ARG, "unknown option");
     }

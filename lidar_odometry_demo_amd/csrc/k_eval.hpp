@@ -33,7 +33,6 @@ namespace lom {
 //                  is bounded by a wall-clock timeout (s_memrealtime), so the grid
 //                  always drains; the host relaunches if a server timed out.
 // ---------------------------------------------------------------------------
-constexpr int kRecWords = 32;    // doubles per record
 constexpr int kAccStride = kEvalThreads + 16;  // LDS row stride (doubles): rows k, k+1 land on disjoint banks
 
 struct EvalCmd {  // pinned host memory, written by the host only
@@ -45,9 +44,6 @@ struct EvalCmd {  // pinned host memory, written by the host only
 };
 constexpr unsigned int kCmdEval = 1, kCmdStop = 2;
 constexpr int kPublishPlain = 0, kPublishHost = 1, kPublishDevice = 2;
-constexpr int kPairsAhead = 5;  // (k_match, k_lm) pairs enqueued before the host looks at a report
-constexpr uint32_t kMaxLmBlocks = 64;    // workgroups of k_lm (one lane of a wave watches each record)
-constexpr uint32_t kMaxLmBlocksBig = 128;  // ... of its variant for large clouds; also the size of an exchange set
 
 // The f64 residual / Jacobian arithmetic below contracts a * b + c to one FMA (the library is built with
 // -ffp-contract=off for the f32 index and distance expressions of the search, which must round like the reference's

@@ -406,12 +406,6 @@ __global__ __launch_bounds__(64) void k_p2p_selftest(P2pArgs A, unsigned long lo
     }
 }
 
-struct LmInit {
-    float t[3], q[4];   // initial guess (cloud_matcher.cpp:107), used when `first`
-    double prior_b[3];  // NormalPrior anchor = the guess's translation (:153)
-    float max_sq;       // max_correspondence_distance^2 of the searches (:139, voxel_grid.h:215)
-};
-
 // kRegPts: this lane's first points (first, first + step, ...) stay in registers for every evaluation of the solve
 template <int kRegPts>
 __device__ __forceinline__ void accumulate_all(const MatchRec *__restrict__ rec, uint32_t n, uint32_t first,

@@ -1,4 +1,4 @@
-// Correspondence search of the scan matcher: MatchRec, the DPP row helpers and k_match (see match.hip for the
+// Correspondence search of the scan matcher: the DPP row helpers and k_match (see match.hip for the
 // overview).  Device code only; match.hip is the one translation unit that instantiates and launches it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,27 +7,10 @@
 #include <cstdint>
 
 #include "lom_internal.hpp"
+#include "match_launch.hpp"  // launch geometry (kMatch*, kEvalThreads), MatchRec, BatchProblem
 
 namespace lom {
 
-constexpr int kMatchThreads = 256;             // 4 waves
-constexpr int kMatchG = 16;                    // lanes per query: four queries per wave
-constexpr int kMatchRows = 4;                  // consecutive rows of a voxel per chunk: one search and 48 bytes per lane and trip
-constexpr int kMatchMinWaves = 7;              // waves per SIMD the register budget is held to (72 VGPRs)
-constexpr int kEvalThreads = 512;
-
-// what k_match leaves behind for the evaluations of one outer iteration: source point,
-// winner's stored point and normal, 48 bytes = three dwordx4 (coalesced for k_eval)
-// (the winner's point and the valid flag share one dwordx4: the next outer iteration's k_match reads exactly that
-// quarter back as its temporal pruning bound)
-struct __attribute__((aligned(16))) MatchRec {
-    float px, py, pz, nx;     // source_point_local (voxel_grid.h:226), plane_normal.x
-    float ox, oy, oz, valid;  // plane_origin; valid: 0.0f = no match, else the bits kRecValid | the winner's row in the slabs
-                              // (never zero, never a denormal: consumers test `!= 0.f`; the next search of the same scan
-                              // reads the row back: a query whose winner has not changed leaves its record alone)
-    float ny, nz, pad0, pad1;
-};
-static_assert(sizeof(MatchRec) == 48, "three dwordx4");
 constexpr uint32_t kRecValid = 0x40000000u;  // rows below 2^30 are told apart (a larger map still matches, it only rewrites)
 
 // per-query debug record written by k_match for lom_match_find_pairs
@@ -203,25 +186,6 @@ struct Stamper<true> {
 };
 #define LOM_STAMP(i) stamper.mark(i)
 
-// Batched align (lom_match_align_batch / _multi): one problem of a round, read by the batch forms of k_match and k_lm
-// from a small array in HBM (blockIdx.y = the problem's place in the round).  Everything that belongs to one problem --
-// the keyframe it searches, its scan, records, search counters, solve state, exchange set and report -- hangs off its
-// descriptor.
-struct BatchProblem {
-    MapView map;  // read by k_match only (k_lm sees the records)
-    const char *src;
-    size_t stride;
-    MatchRec *rec;
-    uint32_t *block_counters;
-    AlignState *state;
-    AlignReport *report;  // device view of pinned host memory
-    void *xrec;           // this round slot's exchange sets (XWord)
-    uint32_t n, match_blocks;
-    uint32_t lm_blocks;  // the solve's grid (k_lm workgroups)
-    float guess_t[3], guess_q[4];
-    float max_sq;
-    double prior_b[3];
-};
 typedef const __attribute__((address_space(4))) BatchProblem *ConstBatch;  // read with scalar loads, like kernel arguments
 
 // kChained: the pose comes from the AlignState a previous k_lm left in HBM (read through the

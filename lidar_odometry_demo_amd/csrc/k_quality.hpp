@@ -1,5 +1,5 @@
 // Quality report of a pose: k_quality and k_quality_sum, and their K-problem forms k_quality_batch and k_quality_batch_sum
-// (see match.hip "quality report" and "batched quality report").  Device code only; match.hip
+// (see quality_report.hip "quality report" and "batched quality report").  Device code only; match.hip
 // is the one translation unit that instantiates and launches it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -177,13 +177,6 @@ __global__ __launch_bounds__(64) void k_quality_sum(const double *__restrict__ r
 // once), so which lane sees which record and every reduction order depend on the problem's n alone: its totals do not
 // depend on what else is in the batch, on the round size or on the problem's place.  No per-point residuals here.
 // ---------------------------------------------------------------------------
-struct QualBatchProblem {
-    const MatchRec *rec;  // the records its search left
-    double *part;         // `grid` workgroup records of kQualSums doubles
-    double *out;          // its kQualSums totals
-    uint32_t n, grid;
-    EvalArgs E;
-};
 typedef const __attribute__((address_space(4))) QualBatchProblem *ConstQualBatch;  // scalar loads, like kernel arguments
 
 __global__ __launch_bounds__(kEvalThreads) void k_quality_batch(const QualBatchProblem *batch)

@@ -128,6 +128,40 @@ struct DeviceBuf {
     size_t bytes = 0;
 };
 
+// its pinned host counterpart (ensure_pinned): grow-only too, with the device view of a mapped block
+struct PinnedBuf {
+    void *h = nullptr;
+    void *d = nullptr;  // hipHostMallocMapped blocks only
+    size_t bytes = 0;
+};
+
+// Buffers of the batched align (lom_match_align_batch / _multi): per-problem solve states and descriptors, records,
+// k_match counters, exchange sets per round slot, staged host scans -- and per-problem reports in pinned host memory;
+// the single align's align_state / scan_on / xrec / report are never touched by it
+struct BatchAlignBufs {
+    DeviceBuf dev, rec, cnt, xrec, src;
+    PinnedBuf stage;    // pinned staging of the states and descriptors (one copy per call)
+    PinnedBuf reports;  // AlignReport slots, 256 bytes each (mapped)
+    unsigned long long report_seq = 0, lm_seq = 0;
+    uint32_t per_cu[4] = {0, 0, 0, 0};  // k_lm blocks per CU a batch round may count on, per variant (cached)
+    int test_round_max = 0;  // LOM_OPT_TEST_BATCH_ROUND_MAX: problems per round at most (0: by residency)
+};
+// ... of the quality report (lom_match_quality*): staged host scan, winner indices and records of its search, k_match
+// counters, per-workgroup records, per-point residuals -- and the reduced values in pinned host memory; neither the
+// single align's buffers nor the map-maintenance scratch (scr[]) are touched
+struct QualityBufs {
+    DeviceBuf src, idx, rec, cnt, part, res;
+    PinnedBuf sums;  // LOM_NQSUMS doubles (mapped)
+};
+// ... of the batched quality report (lom_match_quality_batch*): uploaded host clouds, one round's records / k_match
+// counters / workgroup records, the per-problem poses and descriptors, the per-problem totals -- and a pinned host block
+// that stages the descriptors on the way in and the totals on the way out
+struct QualityBatchBufs {
+    DeviceBuf src, rec, cnt, part, dev, sums;
+    PinnedBuf stage;
+    int test_round_max = 0;  // LOM_OPT_TEST_QUALITY_ROUND_MAX: problems per round at most (0: by the byte budget)
+};
+
 // one set of slab arrays (creation order), allocated and freed together (voxel_map.hip)
 struct Slabs {
     unsigned long long *key = nullptr;  // [cap]
@@ -229,8 +263,7 @@ struct lom_map {
     uint32_t n_vox_ub = 0;
     bool n_vox_stale = false;
     // pinned bounce buffer for host-resident inputs (truly asynchronous H2D) + "last copy done" event
-    void *h_stage = nullptr;
-    size_t h_stage_bytes = 0;
+    lom::PinnedBuf h_stage;
     hipEvent_t stage_ev = nullptr;
     lom::Slabs slabs;
     uint64_t n_points = 0;
@@ -287,29 +320,11 @@ struct lom_map {
     uint32_t cleanups_taken = 0;  // radius cleanups that used such a scan (lom_map_debug_counter)
     unsigned long long report_seq = 0, lm_seq = 0, lm_launches = 0;
     int last_replayed = 0;  // outer iterations of the last align on this handle that the replay fold accounted for (lom_debug_replayed_iterations)
-    // batched align (lom_match_align_batch): buffers of its own -- per-problem solve states and descriptors, records,
-    // k_match counters, exchange sets per round slot, staged host scans -- and per-problem reports in pinned host memory;
-    // the single align's align_state / scan_on / xrec / report are never touched by it
-    lom::DeviceBuf batch_dev, batch_rec, batch_cnt, batch_xrec, batch_src;
-    void *h_batch = nullptr;  // pinned staging of the states and descriptors (one copy per call)
-    size_t h_batch_bytes = 0;
-    void *h_batch_report = nullptr, *d_batch_report = nullptr;  // AlignReport slots, 256 bytes each
-    size_t batch_report_slots = 0;
-    unsigned long long batch_report_seq = 0, batch_lm_seq = 0;
-    uint32_t lm_batch_per_cu[4] = {0, 0, 0, 0};  // k_lm blocks per CU a batch round may count on, per variant (cached)
-    int test_batch_round_max = 0;  // LOM_OPT_TEST_BATCH_ROUND_MAX: problems per round at most (0: by residency)
-    // quality report (lom_match_quality*): buffers of its own, like the batch's -- staged host scan, winner indices and
-    // records of its search, k_match counters, per-workgroup records, per-point residuals -- and the reduced values in
-    // pinned host memory; neither the single align's buffers nor the map-maintenance scratch (scr[]) are touched
-    lom::DeviceBuf qual_src, qual_idx, qual_rec, qual_cnt, qual_part, qual_res;
-    double *h_qual = nullptr, *d_qual = nullptr;  // LOM_NQSUMS doubles
-    // batched quality report (lom_match_quality_batch*): again buffers of its own -- uploaded host clouds, one round's
-    // records / k_match counters / workgroup records, the per-problem poses and descriptors, the per-problem totals --
-    // and a pinned host block that stages the descriptors on the way in and the totals on the way out
-    lom::DeviceBuf qualb_src, qualb_rec, qualb_cnt, qualb_part, qualb_dev, qualb_sums;
-    void *h_qualb = nullptr;
-    size_t h_qualb_bytes = 0;
-    int test_quality_round_max = 0;  // LOM_OPT_TEST_QUALITY_ROUND_MAX: problems per round at most (0: by the byte budget)
+    // the batched align, the quality report and the batched quality report keep buffers of their own (handle.hip frees each
+    // group with its release function)
+    lom::BatchAlignBufs batch;
+    lom::QualityBufs qual;
+    lom::QualityBatchBufs qualb;
     // lom_match_align_multi: recorded on this handle's stream -- as a problem map, for the runner to wait on before the
     // chain; as the runner, after the chain, for the problem maps to wait on (created once, timing disabled)
     hipEvent_t multi_ev = nullptr;
@@ -356,6 +371,24 @@ namespace lom {
 
 int set_error(lom_map *m, int code, const char *what, hipError_t e = hipSuccess);  // handle.hip
 int ensure(lom_map *m, DeviceBuf &b, size_t bytes);  // handle.hip: grow-only device buffer
+// handle.hip: grow-only pinned host block.  One of at least `need` bytes is left alone; else the stream is synchronised
+// (what is enqueued may still read the old block), the old block freed and `grow_to` (>= need) bytes allocated with
+// `flags`, mapped into the device's address space where the flags ask for it.  *fresh: the block is new, its contents undefined.
+int ensure_pinned(lom_map *m, PinnedBuf &b, size_t need, size_t grow_to, unsigned flags, const char *what, bool *fresh = nullptr);
+void release(DeviceBuf &b);  // handle.hip: these free, at lom_map_destroy
+void release(PinnedBuf &b);
+void release(BatchAlignBufs &b);
+void release(QualityBufs &b);
+void release(QualityBatchBufs &b);
+// handle.hip: a host scan into `buf` (grown as needed), one asynchronous copy on the handle's stream
+int upload_scan(lom_map *m, DeviceBuf &buf, const void *src, size_t n, size_t stride, const char **d_src);
+// handle.hip: the host clouds of a problem list into `buf`, every distinct (pointer, n, stride) once, at 256-byte aligned
+// offsets in order of first appearance; d_src[i] is problem i's device address (an empty problem takes no room)
+struct HostCloud {
+    const void *p;
+    size_t n, stride;
+};
+int upload_distinct(lom_map *m, DeviceBuf &buf, const HostCloud *clouds, int count, const char **d_src);
 MapView view_of(const lom_map *m);
 int resolve_pending(lom_map *m);  // voxel_map.hip: redo the last single-pass insert if its in-kernel scan gave up
 int map_init(lom_map *m, size_t capacity_hint);  // voxel_map.hip: status words and the first table of a new map (lom_map_create)

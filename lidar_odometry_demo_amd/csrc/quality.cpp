@@ -1,6 +1,6 @@
 // Host math of the align quality report (lom_quality_from_sums): counts and fit figures, the full information matrix,
 // the spectra of its translation and rotation blocks, and the pose covariance by Cholesky.  Plain C++, no HIP: the
-// device part (k_quality.hpp, launched from match.hip) only produces the LOM_NQSUMS reduced values this file reads.
+// device part (k_quality.hpp, launched by match.hip for quality_report.hip) only produces the LOM_NQSUMS reduced values this file reads.
 #include <algorithm>
 #include <cmath>
 #include <cstring>

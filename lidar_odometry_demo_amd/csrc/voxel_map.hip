@@ -604,17 +604,11 @@ static int add_points_device(lom_map *m, const char *d_xyz, const char *d_nrm, s
 static int stage_pinned(lom_map *m, size_t bytes, char **out)
 {
     if (m->stage_ev) LOM_HIP(m, hipEventSynchronize(m->stage_ev));  // the previous H2D has read the buffer
-    if (bytes > m->h_stage_bytes) {
-        if (m->h_stage) LOM_HIP(m, hipHostFree(m->h_stage));
-        m->h_stage = nullptr;
-        m->h_stage_bytes = 0;
-        const size_t nb = std::max(bytes + bytes / 2, (size_t)1 << 20);
-        hipError_t e = hipHostMalloc(&m->h_stage, nb, hipHostMallocDefault);
-        if (e != hipSuccess) return set_error(m, LOM_ERR_OOM, "hipHostMalloc(stage)", e);
-        m->h_stage_bytes = nb;
-    }
+    const int rc = ensure_pinned(m, m->h_stage, bytes, std::max(bytes + bytes / 2, (size_t)1 << 20), hipHostMallocDefault,
+                                 "hipHostMalloc(stage)");
+    if (rc != LOM_OK) return rc;
     if (!m->stage_ev) LOM_HIP(m, hipEventCreateWithFlags(&m->stage_ev, hipEventDisableTiming));
-    *out = (char *)m->h_stage;
+    *out = (char *)m->h_stage.h;
     return LOM_OK;
 }
 
@@ -688,7 +682,7 @@ static int cleanup_scan_multi_launch(lom_map *m, uint32_t nv, const float center
 // only reads the map and writes scratch, so it can run right behind the align's last solve -- with the centre taken from
 // the align's state in HBM -- instead of a host round trip, a thread hand-off and a launch later.  The caller arms it
 // (lom_map_radius_cleanup_after_align), the next device-resident align on the handle enqueues scan and read-back behind
-// its first five (k_match, k_lm) pairs (match.hip), and lom_map_radius_cleanup takes the result if, and only if, it was
+// its first five (k_match, k_lm) pairs (align.hip), and lom_map_radius_cleanup takes the result if, and only if, it was
 // made for exactly its arguments on exactly this state of the map; everything else is the plain path below.
 constexpr size_t kSpecWordsOffset = 768;  // of h_report / d_report: the words of a scan enqueued behind an align
 constexpr int kSpecWords = 6;             // words 4 (kept), 7 (scan gave up), 12 (made for this call), 13..15 (centre used)

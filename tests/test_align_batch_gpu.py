@@ -145,6 +145,24 @@ def test_one_scan_many_guesses(lom, synth):
     assert m.best == _best_of(lom, singles)
 
 
+def test_shared_cloud_behind_another_on_a_handle_that_has_to_grow(lom, synth):
+    """the staging's other branches: a cloud several problems share that is not the call's first (an empty problem and a
+    second shared cloud between its uses), on a handle whose pinned blocks -- staged descriptors, report slots -- were
+    sized by a first call of two problems and grow for this one of twenty"""
+    g = _synth_grid(lom, synth)
+    scan = np.ascontiguousarray(synth["scan"], np.float32)
+    other = np.ascontiguousarray(scan[:300])
+    m = lom.CloudMatcher()
+    two = [lom.Pose3D(), lom.Pose3D()]
+    first = m.alignBatch(g, [other, scan], two)
+    guesses = _synth_problems(lom, k=20, seed=3)
+    clouds = [other, scan, scan, scan[:0], other] + [scan] * 15
+    poses = m.alignBatch(g, clouds, guesses)
+    _assert_equal(poses, m.batch_stats, _singles(lom, g, clouds, guesses))
+    again = m.alignBatch(g, [other, scan], two)
+    assert [_bits(p) for p in again] == [_bits(p) for p in first]
+
+
 # ---- 3. mixed sizes: several groups in one call ----------------------------------------------------------------------
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """Batched quality report on the device (lom_match_quality_batch* / lom_scan_quality_batch*, csrc/k_quality.hpp
-k_quality_batch / k_quality_batch_sum, csrc/match.hip quality_batch_core) against the oracle and the single call.
+k_quality_batch / k_quality_batch_sum, csrc/quality_report.hip quality_batch_core) against the oracle and the single call.
 
 * parity: every problem's 28 align sums and `valid` against the oracle's Shard.match_eval at tests/test_eval_parity.py's
   bar (assert_sums_close: 1e-12 of each sum's scale), the values [28..35] against the numpy restatement from the oracle's
@@ -270,6 +270,21 @@ def test_rounds_with_a_ragged_last_one(lom):
     _check_sums(three[7], refs[1], ("C2", 7))
     assert three.tobytes() == by_budget.tobytes()
     assert len({three[i].tobytes() for i in range(8)}) == 8
+
+
+def test_a_larger_second_call_grows_the_staging_block(lom):
+    """a handle whose pinned staging block a first call of three problems sized (64 KiB at the least) takes a call of 155,
+    which needs about 120 KB: the bytes those problems give on a fresh handle in a batch that fits the first block"""
+    vs, mx, mn, scan, poses, _ = _lattice_case()
+    small = np.ascontiguousarray(scan[:300])
+    P = _poses(lom, poses)
+    g = _grid(lom, vs, mx, mn)
+    few, _ = lom.quality_report_batch(g, small, P[:3], 0.3, sums_only=True)
+    many, _ = lom.quality_report_batch(g, small, P * 5, 0.3, sums_only=True)
+    want, _ = lom.quality_report_batch(_grid(lom, vs, mx, mn), small, P, 0.3, sums_only=True)
+    assert want[:, 33].any()
+    assert many.tobytes() == np.tile(want, (5, 1)).tobytes()
+    assert few.tobytes() == want[:3].tobytes()
 
 
 # ---- 6. isolation -----------------------------------------------------------------------------------------------------
