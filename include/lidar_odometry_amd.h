@@ -1138,6 +1138,89 @@ int lom_graph_information_from_quality(const lom_quality_report *report, int wit
 int lom_graph_pose_from_f32(const lom_pose *in, lom_graph_pose *out);
 int lom_graph_pose_to_f32(const lom_graph_pose *in, lom_pose *out);
 
+/* ---- scan archive and map assembly: rebuild a map from stored scans (not in the reference) -------------------------
+ * The stage behind lom_graph_optimize: the optimised keyframe poses come in, together with the scans
+ * they belong to, and the corrected map comes out -- a global map, or the odometry's keyframe
+ * (lom_odometry_rebuild_keyframe).  The scans live in HBM and never pass through the host.
+ *
+ *  - Archive.  An append-only store of clouds in their own sensor frame: f32 points and f32 normals, 12 + 12 bytes per
+ *    point, ragged lengths; a table on the host holds {offset, n} per scan.  Ids are 0, 1, 2, ... in order of arrival.
+ *    Normals are required: an archive scan is what addCloud takes.  n == 0 is a valid, empty scan.  A host cloud with a
+ *    non-finite coordinate is LOM_ERR_ARG; a device cloud is not looked at, and a non-finite coordinate in it is found
+ *    when it is assembled, as a range error.  An archive holds at most 2^32 points: the kernels index with 32 bits.
+ *  - Assembly.  lom_map_assemble(m, a, ids, poses, count, params, stats) leaves the map exactly as
+ *    lom_map_add_points(m, C, Cn, |C|, 12) would, where C is the concatenation of the kept, transformed points of scan
+ *    ids[k] at poses[k], for k = 0 .. count-1 in call order, and Cn their rotated normals.  Results are bytes, not
+ *    tolerances.
+ *  - Order is the priority.  A voxel keeps the first max_points points in that order, so the caller's order decides which
+ *    points survive: newest first, or oldest first, is the caller's choice.  An id may appear more than once, each time
+ *    with its own pose.
+ *  - Rotation.  The quaternion is normalised on entry as lom_graph_add_node does (q / sqrt(((w w + x x) + y y) + z z)).
+ *    With tx = 2x, ty = 2y, tz = 2z; twx = tx w, twy = ty w, twz = tz w; txx = tx x, txy = ty x, txz = tz x; tyy = ty y,
+ *    tyz = tz y, tzz = tz z, all f64 and every operation rounded on its own:
+ *        R = [ 1 - (tyy + tzz),  txy - twz,        txz + twy       ;
+ *              txy + twz,        1 - (txx + tzz),  tyz - twx       ;
+ *              txz - twy,        tyz + twx,        1 - (txx + tyy) ]   (row-major R0 .. R8)
+ *    computed on the host; lom_graph_pose_rotation_matrix returns the same nine values.  t is the pose's.
+ *  - Point.  x' = (f32)((R0 p0 + (R1 p1 + R2 p2)) + t0) in f64 from the f32 point, and y', z' likewise with rows 1 and
+ *    2: the association order of lom_transform_points, widened to f64, with one rounding to f32 at the end.
+ *  - Normal.  The same without t.
+ *  - Cull.  params NULL or radius <= 0 keeps everything.  Otherwise, on the f32 result, with d = p' - centre (f32): the
+ *    point is dropped iff dx dx + (dy dy + dz dz) > radius radius, all in f32, strict -- the predicate of
+ *    lom_map_radius_cleanup, so a point at exactly the radius stays.  (A NaN compares false and stays, for the insert to
+ *    refuse.)
+ *  - Atomicity.  The call is atomic like the insert: with a kept point out of range (|x' / voxel_size| >= 2^20) or
+ *    non-finite it returns LOM_ERR_RANGE and the map is unchanged.
+ *  - Validation.  Ids, poses (finite, non-zero quaternion), the cull's values (finite) and the devices (the map's and the
+ *    archive's must be the same; a scan context is refused) are checked before any launch: LOM_ERR_ARG.  More than 2^24
+ *    scans or 2^31 - 2 points in one call are refused the same way.  count == 0, or a cloud that is empty before or
+ *    after the cull, is LOM_OK and changes nothing.
+ *  - Stats.  scans = count; points_in = the sum of the scans' sizes; points_kept = |C|; voxels_before / voxels_after /
+ *    points_stored_after = lom_map_size and lom_map_point_count around the insert.  All zero on an error.
+ *  - Cost.  Without a cull: one kernel, the insert, and the insert's verdict as the only host wait.  With a cull: three
+ *    kernels (transform and count, prefix, compact), one read-back of |C| (4 bytes, one wait), then the insert.
+ * The archive owns its stream; calls on one archive are serialised by a lock inside it, and lom_map_assemble holds it.
+ * The archive's stream and the map's are ordered by events in both directions.  All arguments are validated before any
+ * device work; a refused call leaves the archive as it was.  The archive grows geometrically past the hints given at
+ * create (its clouds are copied device to device, ids and bytes stay); the staging buffers of the assembly belong to the
+ * archive and are reused call after call. */
+typedef struct lom_archive lom_archive;
+typedef struct {
+    float centre[3];
+    float radius; /* <= 0: keep everything */
+} lom_assemble_params;
+typedef struct {
+    int64_t scans, points_in, points_kept, voxels_before, voxels_after, points_stored_after;
+} lom_assemble_stats;
+
+int lom_archive_create(int device, size_t point_hint, size_t scan_hint, lom_archive **out);
+void lom_archive_destroy(lom_archive *a);
+const char *lom_archive_last_error(const lom_archive *a); /* a == NULL: why the last create on this thread failed */
+int lom_archive_clear(lom_archive *a);                    /* no scans; ids start again at 0 */
+void *lom_archive_stream(lom_archive *a);                 /* hipStream_t */
+int lom_archive_device(const lom_archive *a);
+/* the archive's stream waits for a hipEvent_t before what is enqueued next */
+int lom_archive_wait_event(lom_archive *a, void *hip_event);
+/* a new scan; the return value is its id or a negative lom_status.  Records of stride_bytes (>= 12, a multiple of 4)
+ * that begin with x, y, z resp. nx, ny, nz.  The caller's buffers are its own again when the call returns.  The _device
+ * form reads a cloud in HBM behind hip_event_or_null (the caller's producer), or behind nothing but the archive's own
+ * stream when that is NULL. */
+int64_t lom_archive_add(lom_archive *a, const float *xyz, const float *nrm, size_t n, size_t stride_bytes);
+int64_t lom_archive_add_device(lom_archive *a, const float *d_xyz, const float *d_nrm, size_t n, size_t stride_bytes,
+                               void *hip_event_or_null);
+int64_t lom_archive_scan_count(const lom_archive *a);
+int64_t lom_archive_point_count(const lom_archive *a);
+int64_t lom_archive_scan_size(const lom_archive *a, int64_t id);
+/* packed (12-byte) host copies of a scan; returns its size and writes at most `cap` points; either output may be NULL */
+int64_t lom_archive_get(lom_archive *a, int64_t id, float *xyz_out, float *nrm_out, size_t cap);
+int lom_map_assemble(lom_map *m, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses, size_t count,
+                     const lom_assemble_params *params_or_null, lom_assemble_stats *stats_or_null);
+/* Host function; needs no device.  int lom_graph_pose_rotation_matrix(const lom_graph_pose *pose, double R[9]): the
+ * row-major R of the formula above from a pose's quaternion, normalised first; LOM_ERR_ARG for NULL, a non-finite value
+ * or a zero quaternion.  It belongs to this section and not to the pose graph's, and is declared through its type. */
+typedef int(lom_pose64_rotation_fn)(const lom_graph_pose *pose, double R_rowmajor[9]);
+lom_pose64_rotation_fn lom_graph_pose_rotation_matrix;
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;
@@ -1195,6 +1278,26 @@ int64_t lom_odometry_get_temp_cloud(const lom_odometry *o, lom_point_xyzirt *out
  * LOM_ERR_STATE before the first frame.  Reads only: no pose, counter or map of the odometry is touched. */
 int lom_odometry_place_descriptor(lom_odometry *o, lom_place_db *db, int add, float *desc_out_or_null,
                                   int64_t *id_out_or_null);
+/* The last frame's update cloud -- what the keyframe update of that frame transforms and inserts: the planar, range-
+ * filtered cloud down-sampled at keyframe_update_voxel_size, with normals, in the sensor frame -- becomes a new scan of
+ * `a`, which must live on the odometry's device (LOM_ERR_ARG otherwise); its id goes to *id_out.  The cloud is in HBM
+ * whichever way the frame's stages ran, and is copied device to device; the result is the same either way.  The call
+ * waits for the pending keyframe update and for its own copy, so the next frame cannot overwrite what it reads.
+ * LOM_ERR_STATE before the first frame.  Reads only: no pose, counter or map of the odometry is touched. */
+int lom_odometry_archive_scan(lom_odometry *o, lom_archive *a, int64_t *id_out);
+/* Go on after a loop closure: the keyframe is built again from archived scans at corrected poses.  In this order:
+ *  1. the pending keyframe update is waited for (its failure is this call's, and nothing else happens);
+ *  2. an armed cleanup behind the align and a pending lom_odometry_hint_next are dropped;
+ *  3. the keyframe is cleared; it keeps its voxel size and keyframe_max_points_cnt;
+ *  4. lom_map_assemble(keyframe, a, ids, poses, count, {centre = new_current->t, radius = keyframe_cleanup_range}, stats);
+ *  5. with C = lom_pose_compose(new_current, lom_pose_inverse(current)):  previous = lom_pose_compose(C, previous), then
+ *     current = *new_current.
+ * LOM_ERR_STATE before the keyframe is initialised; LOM_ERR_ARG for NULL arguments or an archive on another device
+ * (both before anything is touched).  If the assembly fails -- a bad id or pose, a point out of range -- its status is
+ * returned, the poses stay as they were, and the keyframe is left cleared: the next frame initialises it anew, as the
+ * first frame does. */
+int lom_odometry_rebuild_keyframe(lom_odometry *o, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses,
+                                  size_t count, const lom_pose *new_current, lom_assemble_stats *stats_or_null);
 int lom_odometry_get_stats(const lom_odometry *o, lom_odometry_frame_stats *out);
 /* LOM_OPT_QUALITY_REPORT: the degeneracy thresholds of the per-frame report (lom_match_quality's min_eig_t / min_eig_r;
  * both 0 = not counted until the caller sets them: the project has no measured basis for a default), and the report of

@@ -133,6 +133,8 @@ public:
 };
 
 // ---- VoxelGrid (src/voxel_grid.h) -----------------------------------------------
+class ScanArchive;  // below, behind PoseGraph
+
 class VoxelGrid {
 public:
     struct Correspondence {  // voxel_grid.h:40-46 (f64 like the reference)
@@ -236,6 +238,10 @@ public:
     }
 
     void radiusCleanup(const Vector3f &point, float radius) { check(lom_map_radius_cleanup(h_, point.v, radius)); }
+    // not in the reference: the scans `ids` of the archive at the f64 `poses`, in call order, as one addCloud of their
+    // concatenation (lom_map_assemble); params: nullptr keeps everything, else only the points within radius of centre
+    inline lom_assemble_stats assemble(ScanArchive &archive, const std::vector<int64_t> &ids,
+                                       const std::vector<lom_graph_pose> &poses, const lom_assemble_params *params = nullptr);
     // not in the reference: says that the next align on this grid is followed by radiusCleanup(<its result translation>,
     // radius), as lidar_odometry.cpp:65-67 does -- the cleanup's scan then runs right behind the align (results never differ)
     void radiusCleanupAfterAlign(float radius) { check(lom_map_radius_cleanup_after_align(h_, radius)); }
@@ -814,6 +820,77 @@ private:
     lom_graph *h_ = nullptr;
 };
 
+// ---- scan archive and map assembly (lom_archive_*, lom_map_assemble; not in the reference) -------------------
+// Clouds with normals kept in HBM in their own sensor frame; VoxelGrid::assemble puts any of them, at f64 poses, into a
+// map in one call: the stage behind PoseGraph::optimize.  Definitions: lidar_odometry_amd.h ("scan archive and map assembly").
+using AssembleParams = lom_assemble_params;  // {centre[3], radius}; radius <= 0 keeps everything
+using AssembleStats = lom_assemble_stats;
+
+class ScanArchive {
+public:
+    explicit ScanArchive(size_t point_hint = 0, size_t scan_hint = 0, int device = 0)
+    {
+        const int rc = lom_archive_create(device, point_hint, scan_hint, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_archive_last_error(nullptr));
+    }
+    ~ScanArchive() { lom_archive_destroy(h_); }
+    ScanArchive(const ScanArchive &) = delete;
+    ScanArchive &operator=(const ScanArchive &) = delete;
+    lom_archive *handle() const { return h_; }
+    void clear() { check(lom_archive_clear(h_)); }
+    size_t size() const { return (size_t)check(lom_archive_scan_count(h_)); }
+    size_t pointCount() const { return (size_t)check(lom_archive_point_count(h_)); }
+    size_t scanSize(int64_t id) const { return (size_t)check(lom_archive_scan_size(h_, id)); }
+    // a new scan; returns its id
+    int64_t add(const PointCloud<PointNormal> &cloud)
+    {
+        const PointNormal *p = cloud.points.data();
+        const bool none = cloud.points.empty();
+        return check(lom_archive_add(h_, none ? nullptr : &p->x, none ? nullptr : &p->normal_x, cloud.points.size(),
+                                     sizeof(PointNormal)));
+    }
+    PointCloud<PointNormal>::Ptr get(int64_t id) const
+    {
+        const size_t n = scanSize(id);
+        std::vector<float> xyz(n * 3 + 3), nrm(n * 3 + 3);
+        check(lom_archive_get(h_, id, xyz.data(), nrm.data(), n));
+        auto out = std::make_shared<PointCloud<PointNormal>>();
+        out->points.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            PointNormal &q = out->points[i];
+            q.x = xyz[3 * i], q.y = xyz[3 * i + 1], q.z = xyz[3 * i + 2];
+            q.normal_x = nrm[3 * i], q.normal_y = nrm[3 * i + 1], q.normal_z = nrm[3 * i + 2];
+        }
+        return out;
+    }
+    // the row-major R the assembly uses for a pose (lom_graph_pose_rotation_matrix)
+    static std::vector<double> rotationMatrix(const lom_graph_pose &pose)
+    {
+        std::vector<double> R(9);
+        const int rc = lom_graph_pose_rotation_matrix(&pose, R.data());
+        if (rc != LOM_OK) throw Error(rc, "ScanArchive::rotationMatrix: a non-finite value or a zero quaternion");
+        return R;
+    }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_archive_last_error(h_));
+        return rc;
+    }
+    lom_archive *h_ = nullptr;
+};
+
+inline lom_assemble_stats VoxelGrid::assemble(ScanArchive &archive, const std::vector<int64_t> &ids,
+                                              const std::vector<lom_graph_pose> &poses, const lom_assemble_params *params)
+{
+    if (ids.size() != poses.size()) throw Error(LOM_ERR_ARG, "VoxelGrid::assemble: one pose per id");
+    lom_assemble_stats st;
+    const int rc = lom_map_assemble(h_, archive.handle(), ids.data(), poses.data(), ids.size(), params, &st);
+    if (rc != LOM_OK) throw Error(rc, lom_archive_last_error(archive.handle()));
+    return st;
+}
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)
@@ -926,6 +1003,27 @@ public:
         const int rc = lom_odometry_place_descriptor(h_, db.handle(), id_out ? 1 : 0, out.data(), id_out);
         if (rc != LOM_OK) throw Error(rc, rc == LOM_ERR_STATE ? "no frame yet" : lom_place_db_last_error(db.handle()));
         return out;
+    }
+    // not in the reference: the last frame's update cloud becomes a new scan of the archive; returns its id.  Throws
+    // Error(LOM_ERR_STATE) before the first frame.
+    int64_t archiveScan(ScanArchive &archive)
+    {
+        int64_t id = -1;
+        const int rc = lom_odometry_archive_scan(h_, archive.handle(), &id);
+        if (rc != LOM_OK) throw Error(rc, rc == LOM_ERR_STATE ? "no frame yet" : lom_odometry_last_error(h_));
+        return id;
+    }
+    // not in the reference: go on after a loop closure -- the keyframe again from the archive's scans `ids` at `poses`,
+    // culled at keyframe_cleanup_range around new_current, which becomes the current pose (lom_odometry_rebuild_keyframe)
+    lom_assemble_stats rebuildKeyframe(ScanArchive &archive, const std::vector<int64_t> &ids,
+                                       const std::vector<lom_graph_pose> &poses, const Pose3D &new_current)
+    {
+        if (ids.size() != poses.size()) throw Error(LOM_ERR_ARG, "rebuildKeyframe: one pose per id");
+        const lom_pose p = new_current.c();
+        lom_assemble_stats st;
+        const int rc = lom_odometry_rebuild_keyframe(h_, archive.handle(), ids.data(), poses.data(), ids.size(), &p, &st);
+        if (rc != LOM_OK) throw Error(rc, rc == LOM_ERR_STATE ? "no keyframe yet" : lom_odometry_last_error(h_));
+        return st;
     }
     Pose3D getCurrentPose() const  // :87-89
     {

@@ -138,6 +138,22 @@ class VoxelGrid:
         capi.check(capi.lib().lom_map_add_points_device(self._h, d_xyz_ptr, d_nrm_ptr, int(n), int(stride_bytes)),
                    self._h)
 
+    def assemble(self, archive, ids, poses, centre=None, radius=0.0):
+        """lom_map_assemble: the scans `ids` of the ScanArchive at `poses` ((n, 7) float64: t, then q wxyz) into this map
+        in call order, as one addCloud of their concatenation; with radius > 0 only the points within it of `centre`.
+        Returns the stats as a dict."""
+        ids, p = _assemble_args(ids, poses)
+        prm = None
+        if centre is not None or radius > 0.0:
+            prm = capi.AssembleParams(capi.f3((0, 0, 0) if centre is None else centre), float(radius))
+        st = capi.AssembleStats()
+        rc = capi.lib().lom_map_assemble(self._h, archive.handle, ids.ctypes.data, p.ctypes.data, len(ids),
+                                         C.byref(prm) if prm is not None else None, C.byref(st))
+        if rc != 0:
+            text = capi.lib().lom_archive_last_error(archive.handle)
+            raise LomError(int(rc), text.decode() if text else "lom_map_assemble")
+        return st.asdict()
+
     def size(self):                                        # voxel_grid.h:248-251
         return int(capi.check(capi.lib().lom_map_size(self._h), self._h))
 
@@ -932,6 +948,90 @@ def _graph_poses(poses):
     return out
 
 
+def graph_pose_rotation_matrix(pose):
+    """lom_graph_pose_rotation_matrix: the 3x3 float64 rotation matrix the map assembly uses for a pose (7 values: t,
+    then the quaternion w x y z, normalised first)."""
+    p = _graph_poses(pose)
+    if len(p) != 1:
+        raise TypeError("one pose of 7 values")
+    out = np.empty((3, 3), np.float64)
+    rc = capi.lib().lom_graph_pose_rotation_matrix(p.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise LomError(int(rc), "a pose with a non-finite value or a zero quaternion")
+    return out
+
+
+class ScanArchive:
+    """Clouds with normals kept in HBM in their own sensor frame (lom_archive_*, include/lidar_odometry_amd.h "scan
+    archive and map assembly"); VoxelGrid.assemble puts any of them, at float64 poses, into a map in one call."""
+
+    def __init__(self, point_hint=0, scan_hint=0, device=0):
+        h = C.c_void_p()
+        rc = capi.lib().lom_archive_create(int(device), int(point_hint), int(scan_hint), C.byref(h))
+        if rc != 0:
+            text = capi.lib().lom_archive_last_error(None)
+            raise LomError(int(rc), text.decode() if text else "lom_archive_create")
+        self._h = h
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and capi is not None:
+            capi.lib().lom_archive_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _check(self, rc):
+        if rc < 0:
+            text = capi.lib().lom_archive_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "")
+        return rc
+
+    def __len__(self):
+        return int(self._check(capi.lib().lom_archive_scan_count(self._h)))
+
+    def pointCount(self):
+        return int(self._check(capi.lib().lom_archive_point_count(self._h)))
+
+    def scanSize(self, id):
+        return int(self._check(capi.lib().lom_archive_scan_size(self._h, int(id))))
+
+    def clear(self):
+        self._check(capi.lib().lom_archive_clear(self._h))
+
+    def waitEvent(self, hip_event):
+        self._check(capi.lib().lom_archive_wait_event(self._h, hip_event))
+
+    def add(self, xyz, normals):
+        """a new scan from host arrays; returns its id"""
+        xyz, nrm = capi.xyz_array(xyz), capi.xyz_array(normals)
+        if len(xyz) != len(nrm):
+            raise ValueError("points and normals differ in length")
+        return int(self._check(capi.lib().lom_archive_add(self._h, xyz.ctypes.data, nrm.ctypes.data, len(xyz), 12)))
+
+    def addDevice(self, d_xyz_ptr, d_nrm_ptr, n, stride_bytes=12, hip_event=None):
+        """a new scan from device memory, read behind `hip_event` (a hipEvent_t) or the archive's own stream"""
+        return int(self._check(capi.lib().lom_archive_add_device(self._h, d_xyz_ptr, d_nrm_ptr, int(n), int(stride_bytes),
+                                                                hip_event)))
+
+    def get(self, id):
+        """(points, normals) of a scan, (n, 3) float32 each"""
+        n = self.scanSize(id)
+        xyz, nrm = np.empty((n, 3), np.float32), np.empty((n, 3), np.float32)
+        self._check(capi.lib().lom_archive_get(self._h, int(id), xyz.ctypes.data, nrm.ctypes.data, n))
+        return xyz, nrm
+
+
+def _assemble_args(ids, poses):
+    ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+    p = _graph_poses(poses) if len(ids) else np.empty(0, capi.GRAPH_POSE)
+    if len(p) != len(ids):
+        raise ValueError("one pose per id")
+    return ids, p
+
+
 class PoseGraph:
     """Keyframe poses and the relative poses measured between them, in HBM, optimised on the device (lom_graph_*,
     include/lidar_odometry_amd.h "pose graph").  Poses are (n, 7) float64 arrays: t, then the quaternion w x y z; an
@@ -1272,6 +1372,28 @@ class LidarOdometry:
             text = capi.lib().lom_place_db_last_error(db.handle)
             raise LomError(int(rc), text.decode() if text else "lom_odometry_place_descriptor")
         return (out, int(id_.value)) if add else out
+
+    def archiveScan(self, archive):
+        """lom_odometry_archive_scan: the last frame's update cloud becomes a new scan of the ScanArchive; returns its
+        id.  LomError(LOM_ERR_STATE) before the first frame."""
+        id_ = C.c_int64(-1)
+        rc = capi.lib().lom_odometry_archive_scan(self._h, archive.handle, C.byref(id_))
+        if rc != 0:
+            text = capi.lib().lom_odometry_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "lom_odometry_archive_scan")
+        return int(id_.value)
+
+    def rebuildKeyframe(self, archive, ids, poses, new_current):
+        """lom_odometry_rebuild_keyframe: the keyframe again from the archive's scans `ids` at `poses`, culled at
+        keyframe_cleanup_range around `new_current` (a Pose3D), which becomes the current pose; returns the stats."""
+        ids, p = _assemble_args(ids, poses)
+        st = capi.AssembleStats()
+        rc = capi.lib().lom_odometry_rebuild_keyframe(self._h, archive.handle, ids.ctypes.data, p.ctypes.data, len(ids),
+                                                      C.byref(new_current._c()), C.byref(st))
+        if rc != 0:
+            text = capi.lib().lom_odometry_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "lom_odometry_rebuild_keyframe")
+        return st.asdict()
 
     def debugSetState(self, previous, current, keyframe_xyz=None, keyframe_normals=None):
         """Test hook: overwrite the two poses and, if given, rebuild the keyframe from a full export

@@ -190,6 +190,23 @@ assert GRAPH_POSE.itemsize == 56 and C.sizeof(GraphParams) == 40 and C.sizeof(Gr
 GRAPH_STOP_GRADIENT, GRAPH_STOP_STEP, GRAPH_STOP_MAX_OUTER = 1, 2, 3
 
 
+class AssembleParams(C.Structure):
+    """lom_assemble_params (radius <= 0: keep everything)"""
+    _fields_ = [("centre", C.c_float * 3), ("radius", C.c_float)]
+
+
+class AssembleStats(C.Structure):
+    """lom_assemble_stats"""
+    _fields_ = [("scans", C.c_int64), ("points_in", C.c_int64), ("points_kept", C.c_int64), ("voxels_before", C.c_int64),
+                ("voxels_after", C.c_int64), ("points_stored_after", C.c_int64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(AssembleParams) == 16 and C.sizeof(AssembleStats) == 48
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -259,7 +276,13 @@ EXPORTED = [
     "lom_graph_edge_count", "lom_graph_get_poses", "lom_graph_set_pose", "lom_graph_set_fixed", "lom_graph_optimize",
     "lom_graph_evaluate", "lom_graph_debug_matvec", "lom_graph_edge_chi2", "lom_graph_check_gauge", "lom_graph_lm_policy",
     "lom_graph_information_from_quality", "lom_graph_pose_from_f32", "lom_graph_pose_to_f32",
+    "lom_archive_create", "lom_archive_destroy", "lom_archive_last_error", "lom_archive_clear", "lom_archive_stream",
+    "lom_archive_device", "lom_archive_wait_event", "lom_archive_add", "lom_archive_add_device", "lom_archive_scan_count",
+    "lom_archive_point_count", "lom_archive_scan_size", "lom_archive_get", "lom_map_assemble", "lom_odometry_archive_scan",
+    "lom_odometry_rebuild_keyframe",
 ]
+# ... and the one it declares through a function type (the "scan archive and map assembly" section)
+EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
 
 # lom_option / counters of include/lidar_odometry_amd.h
 OPT_HOST_LM, OPT_DEVICE_PATIENCE_TICKS, OPT_DEBUG_LM_STAMPS, OPT_DEBUG_TIMING, OPT_NO_TEMPORAL_BOUND, OPT_COUNT_CANDIDATES = 1, 2, 3, 4, 5, 6
@@ -570,6 +593,29 @@ def lib():
     L.lom_graph_information_from_quality.argtypes = [C.POINTER(QualityReport), C.c_int, vp]
     L.lom_graph_pose_from_f32.argtypes = [pp, vp]
     L.lom_graph_pose_to_f32.argtypes = [vp, pp]
+    L.lom_archive_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(vp)]
+    L.lom_archive_destroy.argtypes = [vp]
+    L.lom_archive_destroy.restype = None
+    L.lom_archive_last_error.argtypes = [vp]
+    L.lom_archive_last_error.restype = C.c_char_p
+    L.lom_archive_clear.argtypes = [vp]
+    L.lom_archive_stream.argtypes = [vp]
+    L.lom_archive_stream.restype = vp
+    L.lom_archive_device.argtypes = [vp]
+    L.lom_archive_wait_event.argtypes = [vp, vp]
+    L.lom_archive_add.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t]
+    L.lom_archive_add_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+    L.lom_archive_scan_count.argtypes = [vp]
+    L.lom_archive_point_count.argtypes = [vp]
+    L.lom_archive_scan_size.argtypes = [vp, C.c_int64]
+    L.lom_archive_get.argtypes = [vp, C.c_int64, vp, vp, C.c_size_t]
+    for fn in (L.lom_archive_add, L.lom_archive_add_device, L.lom_archive_scan_count, L.lom_archive_point_count,
+               L.lom_archive_scan_size, L.lom_archive_get):
+        fn.restype = C.c_int64
+    L.lom_map_assemble.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(AssembleParams), C.POINTER(AssembleStats)]
+    L.lom_graph_pose_rotation_matrix.argtypes = [vp, vp]
+    L.lom_odometry_archive_scan.argtypes = [vp, vp, C.POINTER(C.c_int64)]
+    L.lom_odometry_rebuild_keyframe.argtypes = [vp, vp, vp, vp, C.c_size_t, pp, C.POINTER(AssembleStats)]
     _lib = L
     return L
 

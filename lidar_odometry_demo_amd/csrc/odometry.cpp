@@ -560,6 +560,11 @@ struct lom_odometry {
     lom_carve_params carve{};
     lom_carve_stats carve_stats{};
     std::string deferred_error;
+    // lom_odometry_archive_scan: where the last frame left its update cloud in HBM (one of the update workspaces; packed
+    // points and normals).  Written where a frame succeeds, host values only.
+    const float *arch_xyz = nullptr, *arch_nrm = nullptr;
+    size_t arch_n = 0;
+    bool have_upd = false;
     // finish the previous frame's keyframe update; its failure is this call's failure
     int settle()
     {
@@ -710,6 +715,63 @@ int lom_odometry_place_descriptor(lom_odometry *o, lom_place_db *db, int add, fl
     if (id < 0) return (int)id;
     if (id_out) *id_out = id;
     return desc_out ? lom_place_db_get(db, id, desc_out) : LOM_OK;
+}
+
+// The last frame's update cloud into a scan archive (csrc/archive.hip), device to device.  The cloud's kernels are
+// through when the frame returns (the frame has collected its count and verdict), the helper thread only reads it, and
+// the call returns after its copy: the next frame's down-sampler, which writes the OTHER workspace and this one a frame
+// later, cannot touch what is read here.  Settling first keeps the keyframe's error channel in one place.
+int lom_odometry_archive_scan(lom_odometry *o, lom_archive *a, int64_t *id_out)
+{
+    if (!o || !a || !id_out || lom_archive_device(a) != o->device) return LOM_ERR_ARG;
+    if (!o->have_upd) return LOM_ERR_STATE;  // no frame yet
+    const int rc = o->settle();
+    if (rc != LOM_OK) return rc;
+    const int64_t id = lom_archive_add_device(a, o->arch_xyz, o->arch_nrm, o->arch_n, 12, nullptr);
+    if (id < 0) {
+        o->error = lom_archive_last_error(a);
+        return (int)id;
+    }
+    *id_out = id;
+    return LOM_OK;
+}
+
+// the keyframe again from archived scans at corrected poses: the steps of the header, in its order
+int lom_odometry_rebuild_keyframe(lom_odometry *o, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses,
+                                  size_t count, const lom_pose *new_current, lom_assemble_stats *stats)
+{
+    if (!o || !a || !new_current || (count && (!ids || !poses)) || lom_archive_device(a) != o->device) return LOM_ERR_ARG;
+    int rc = o->settle();  // 1.
+    if (rc != LOM_OK) return rc;
+    if (!o->keyframe_has_voxels) return LOM_ERR_STATE;
+    (void)lom_map_radius_cleanup_after_align(o->keyframe, 0.f);  // 2. (disarms)
+    o->hint_pts = nullptr;
+    o->hint_n = 0;
+    if ((rc = lom_map_clear(o->keyframe, o->cfg.keyframe_voxel_size)) != LOM_OK) {  // 3.
+        o->error = lom_last_error(o->keyframe);
+        return rc;
+    }
+    o->keyframe_has_voxels = false;
+    o->last.keyframe_voxels = 0;
+    lom_assemble_params prm;
+    for (int i = 0; i < 3; i++) prm.centre[i] = new_current->t[i];
+    prm.radius = o->cfg.keyframe_cleanup_range;
+    lom_assemble_stats st;
+    if ((rc = lom_map_assemble(o->keyframe, a, ids, poses, count, &prm, &st)) != LOM_OK) {  // 4.
+        o->error = lom_archive_last_error(a);
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return rc;
+    }
+    o->last.keyframe_voxels = st.voxels_after;
+    o->keyframe_has_voxels = st.voxels_after > 0;
+    lom_pose inv, corr, prev;  // 5.
+    lom_pose_inverse(&o->current, &inv);
+    lom_pose_compose(new_current, &inv, &corr);
+    lom_pose_compose(&corr, &o->previous, &prev);
+    o->previous = prev;
+    o->current = *new_current;
+    if (stats) *stats = st;
+    return LOM_OK;
 }
 
 // test hook: overwrite previous_transform_ / current_transform_ (lidar_odometry.h:84-85); together with
@@ -1223,6 +1285,7 @@ int frame_stages(lom_odometry *o, Frame &f, const lom_point_xyzirt *pts, size_t 
         }
         if ((rc = lom_map_add_points_device(o->keyframe, f.in.d_down, f.in.d_down_n, (size_t)f.in.nd, 12)) != LOM_OK)
             return fail_map(o, rc, o->keyframe);
+        o->arch_xyz = f.in.d_down, o->arch_nrm = f.in.d_down_n, o->arch_n = (size_t)f.in.nd, o->have_upd = true;
         f.cur.initialised_keyframe = 1;
         f.cur.update_points = f.in.nd;
         f.cur.keyframe_voxels = lom_map_size(o->keyframe);
@@ -1286,6 +1349,7 @@ int frame_commit(lom_odometry *o, Frame &f, const lom_align_stats &ast, lom_pose
     const lom_pose pose_now = o->current;
     const size_t n_down = (size_t)in.nd;
     const float *d_down = in.d_down, *d_down_n = in.d_down_n;
+    o->arch_xyz = d_down, o->arch_nrm = d_down_n, o->arch_n = n_down, o->have_upd = true;
     const double t_submit = o->debug_timing ? StageTimer::now() : 0.0;
     auto update = [o, pose_now, d_down, d_down_n, n_down, t_submit]() -> int {
         auto bad = [o](int rc, lom_map *m) {
