@@ -81,7 +81,7 @@ static void set_guess(const float gt[3], const float gq[4], LmInit &init)
 }
 
 // Wait until report `want` of a chain has arrived.  kReportArrived, kReportError (a workgroup gave up: the error word,
-// seen before or with the report) or a negative status recorded with set_error (the stream ended or failed without
+// seen before or with the report) or a negative status recorded with fail (the stream ended or failed without
 // either); the caller advances its sequence counter in every case.  An idle stream is looked at once more for the
 // report OR the error word: the batched align needs both (a problem that gave up writes no further report), and for
 // the single align it is the same as looking for the report alone, since its caller tests the error word first.
@@ -95,9 +95,9 @@ int wait_report(lom_map *m, const volatile AlignReport *rp, unsigned long long w
             const hipError_t e = hipStreamQuery(m->stream);
             if (e == hipSuccess) {
                 if (rp->seq == want || rp->error) break;
-                return set_error(m, LOM_ERR_HIP, (std::string(solve) + " ended without a report").c_str());
+                return fail(m, LOM_ERR_HIP, (std::string(solve) + " ended without a report").c_str());
             } else if (e != hipErrorNotReady) {
-                return set_error(m, LOM_ERR_HIP, (std::string("stream failed during the ") + solve).c_str(), e);
+                return fail(m, LOM_ERR_HIP, (std::string("stream failed during the ") + solve).c_str(), e);
             }
         }
     }
@@ -182,7 +182,7 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
     double *d_trace = nullptr;  // lom_debug_lm_trace: k_lm of outer iteration `trace_outer` records its evaluations
     if (trace_out) {
         if ((rc = ensure(m, m->dbg_trace, 201 * 8)) != LOM_OK) return rc;
-        d_trace = (double *)m->dbg_trace.p;
+        d_trace = m->dbg_trace.as<double>();
         LOM_HIP(m, hipMemsetAsync(d_trace, 0, 201 * 8, m->stream));
     }
     volatile AlignReport *rp = reinterpret_cast<volatile AlignReport *>(m->h_report);
@@ -196,7 +196,7 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
     unsigned long long *dbg = nullptr;  // LOM_OPT_DEBUG_LM_STAMPS: phase stamps of the last k_lm of the align
     if (m->opt_debug_lm) {
         if ((rc = ensure(m, m->dbg_stamps, 4096)) != LOM_OK) return rc;
-        dbg = (unsigned long long *)m->dbg_stamps.p;
+        dbg = m->dbg_stamps.as<unsigned long long>();
         LOM_HIP(m, hipMemsetAsync(dbg, 0, 40 * 8, m->stream));
     }
     // The replay fold (k_lm's tail, LOM_OPT_REPLAY_FOLD): on for the single align of one GPU -- with or without an exchange
@@ -238,7 +238,7 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
             // the kernels still enqueued see the flag in AlignState and return at once
             (void)hipStreamSynchronize(m->stream);
             m->align_state_dirty = true;
-            set_error(m, LOM_ERR_HIP, "device solve: a workgroup timed out waiting for the others");
+            fail(m, LOM_ERR_HIP, "device solve: a workgroup timed out waiting for the others");
             return kDeviceLoopGaveUp;
         }
         open = rp->finished ? 0 : 1;
@@ -298,7 +298,7 @@ static int align_chained(lom_map *m, const char *d_src, size_t n, size_t stride,
 int align_device_paths(lom_map *m, const char *d_src, size_t n, size_t stride, const float guess_t[3],
                               const float guess_q[4], float out_t[3], float out_q[4], lom_align_stats *stats)
 {
-    if (n >= kMaxScanPoints) return set_error(m, LOM_ERR_ARG, "too many source points");
+    if (n >= kMaxScanPoints) return fail(m, LOM_ERR_ARG, "too many source points");
     {   // an insert nobody has looked at since (no lom_map_status): the search must see its points
         const int rcp = resolve_pending(m);
         if (rcp != LOM_OK) return rcp;
@@ -325,17 +325,17 @@ int align_device_paths(lom_map *m, const char *d_src, size_t n, size_t stride, c
             if (host_comm_allreduce_deadline(m->host_comm, verdict, 2, deadline_s) != LOM_OK) {
                 m->p2p = false;
                 const std::string why = std::string("agreement after a device-to-device align failed: ") + host_comm_error(m->host_comm);
-                return set_error(m, LOM_ERR_COMM, why.c_str());
+                return fail(m, LOM_ERR_COMM, why.c_str());
             }
             if (verdict[1] != 0.0) {  // some rank cannot continue: the same for all
                 m->p2p = false;
                 (void)hipStreamSynchronize(m->stream);
                 if (hard) return rc;
-                return set_error(m, LOM_ERR_COMM, "a peer rank failed during a device-to-device align");
+                return fail(m, LOM_ERR_COMM, "a peer rank failed during a device-to-device align");
             }
             if (verdict[0] == 0.0) return LOM_OK;
             fprintf(stderr, "lidar_odometry_amd: device-to-device exchange given up on %d rank(s) (%s); rank %d redoes the align over the host exchange\n",
-                    (int)verdict[0], gave_up ? m->last_error.c_str() : "a peer gave up", m->rank);
+                    (int)verdict[0], gave_up ? m->error.c_str() : "a peer gave up", m->rank);
             (void)hipStreamSynchronize(m->stream);
             m->p2p = false;
         } else if (rc != kDeviceLoopGaveUp) {
@@ -344,7 +344,7 @@ int align_device_paths(lom_map *m, const char *d_src, size_t n, size_t stride, c
         // single GPU: k_lm's workgroups were not all resident within their patience (another process or
         // handle on the GPU, a CU mask): same align again through the host-driven loop, whose
         // workgroups never wait for each other
-        m->last_error.clear();
+        m->error.clear();
         fell_back = true;
     }
     int rc = scan_buffers(m, (uint32_t)n, false);
@@ -357,7 +357,7 @@ int align_device_paths(lom_map *m, const char *d_src, size_t n, size_t stride, c
     server_stop(m);
     if (!c.counted) st.algorithmic_bytes = 0.0;  // (SURVEY.md 8d's bytes need the counts: LOM_OPT_COUNT_CANDIDATES)
     if (rc != LOM_OK) {
-        if (m->last_error.empty()) set_error(m, rc, "align failed");
+        if (m->error.empty()) fail(m, rc, "align failed");
         // ranks of one node: a rank that leaves the loop tells its peers (they would wait for its sums otherwise)
         if (m->host_comm) (void)lom_host_comm_abort((lom_host_comm *)m->host_comm);
         return rc == LOM_ERR_HOOK ? LOM_ERR_HIP : rc;
@@ -402,7 +402,7 @@ int lom_match_align_device(lom_map *m, const float *d_src, size_t n, size_t stri
 {
     if (!m || (n && !d_src) || !guess_t || !guess_q || !out_t || !out_q || !stride_ok(stride)) return LOM_ERR_ARG;
     LOM_HIP(m, hipSetDevice(m->device));
-    m->last_error.clear();
+    m->error.clear();
     return align_device(m, (const char *)d_src, n, stride, guess_t, guess_q, out_t, out_q, stats);
 }
 
@@ -419,9 +419,9 @@ int lom_debug_lm_trace(lom_map *m, const float *src, size_t n, size_t stride, co
     if (!m || (n && !src) || !guess_t || !guess_q || !trace_out || !n_evals_out || !out_t || !out_q ||
         !scan_args_ok(n, stride) || outer_index < 0 || outer_index >= 35)
         return LOM_ERR_ARG;
-    if (m->comm || m->host_comm) return set_error(m, LOM_ERR_STATE, "not with an attached exchange");
+    if (m->comm || m->host_comm) return fail(m, LOM_ERR_STATE, "not with an attached exchange");
     LOM_HIP(m, hipSetDevice(m->device));
-    m->last_error.clear();
+    m->error.clear();
     const char *d_src = nullptr;
     int rc = upload_scan(m, m->scan_src, src, n, stride, &d_src);
     if (rc != LOM_OK) return rc;
@@ -444,7 +444,7 @@ int lom_match_align_repeat(lom_map *m, const float *d_src, size_t n, size_t stri
     if (!m || (n && !d_src) || !guess_t || !guess_q || !out_t || !out_q || reps < 1 || !stride_ok(stride))
         return LOM_ERR_ARG;
     LOM_HIP(m, hipSetDevice(m->device));
-    m->last_error.clear();
+    m->error.clear();
     lom_align_stats acc;
     std::memset(&acc, 0, sizeof acc);
     for (int r = 0; r < reps; r++) {
@@ -480,7 +480,7 @@ int lom_match_align(lom_map *m, const float *src, size_t n, size_t stride, const
 {
     if (!m || (n && !src) || !guess_t || !guess_q || !out_t || !out_q || !stride_ok(stride)) return LOM_ERR_ARG;
     LOM_HIP(m, hipSetDevice(m->device));
-    m->last_error.clear();
+    m->error.clear();
     const char *d_src = nullptr;
     int rc = upload_scan(m, m->scan_src, src, n, stride, &d_src);
     if (rc != LOM_OK) return rc;

@@ -171,18 +171,18 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
     AlignState *h_states = reinterpret_cast<AlignState *>(m->batch.stage.h);
     BatchProblem *h_desc = reinterpret_cast<BatchProblem *>((char *)m->batch.stage.h + states_bytes);
     AlignState *d_states = reinterpret_cast<AlignState *>(m->batch.dev.p);
-    const BatchProblem *d_desc = reinterpret_cast<const BatchProblem *>((char *)m->batch.dev.p + states_bytes);
+    const BatchProblem *d_desc = reinterpret_cast<const BatchProblem *>(m->batch.dev.as<char>() + states_bytes);
     for (const Round &r : rounds)
         for (int k = 0; k < r.size; k++) {
             const int j = r.first + k, i = order[j];
             AlignState &st = h_states[j];
             BatchProblem &d = h_desc[j];
             fill_search(d, st, view_of(it[i].map), it[i].src, it[i].stride, it[i].n, mb[i],
-                        reinterpret_cast<MatchRec *>((char *)m->batch.rec.p + off_rec[i]),
-                        reinterpret_cast<uint32_t *>((char *)m->batch.cnt.p + off_cnt[i]), d_states + j, it[i].gt, it[i].gq,
+                        reinterpret_cast<MatchRec *>(m->batch.rec.as<char>() + off_rec[i]),
+                        reinterpret_cast<uint32_t *>(m->batch.cnt.as<char>() + off_cnt[i]), d_states + j, it[i].gt, it[i].gq,
                         sq_f32(0.3f));  // cloud_matcher.cpp:139
             d.report = reinterpret_cast<AlignReport *>((char *)m->batch.reports.d + (size_t)j * 256);
-            d.xrec = (char *)m->batch.xrec.p + (size_t)k * kExchangeSetBytes;
+            d.xrec = m->batch.xrec.as<char>() + (size_t)k * kExchangeSetBytes;
             d.lm_blocks = nb[i];
             set_guess(it[i].gt, it[i].gq, d, st);
             volatile AlignReport *rp = reinterpret_cast<volatile AlignReport *>((char *)m->batch.reports.h + (size_t)j * 256);
@@ -259,7 +259,7 @@ static int align_multi(lom_map *m, BatchItem *it, int count, lom_align_result *o
     for (int i = 0; i < count; i++)
         if ((it[i].n && !it[i].src) || !scan_args_ok(it[i].n, it[i].stride)) return LOM_ERR_ARG;
     LOM_HIP(m, hipSetDevice(m->device));
-    m->last_error.clear();
+    m->error.clear();
     double launch_s = 0.0, wait_s = 0.0;
     // the handles involved, runner first, each once
     std::vector<lom_map *> maps{m};
@@ -268,8 +268,8 @@ static int align_multi(lom_map *m, BatchItem *it, int count, lom_align_result *o
     auto problem_error = [&](int i, int rc) {
         lom_map *pm = it[i].map;
         if (pm == m) return rc;
-        const std::string why = "problem " + std::to_string(i) + ": " + pm->last_error;
-        return set_error(m, rc, why.c_str());
+        const std::string why = "problem " + std::to_string(i) + ": " + pm->error;
+        return fail(m, rc, why.c_str());
     };
     // every map settled before anything is launched (an insert nobody has looked at yet: the search must see its points)
     for (size_t k = 0; k < maps.size(); k++) {
@@ -355,7 +355,7 @@ static int align_multi(lom_map *m, BatchItem *it, int count, lom_align_result *o
             LOM_HIP(m, hipStreamSynchronize(m->stream));
             ordered = true;
         }
-        pm->last_error.clear();
+        pm->error.clear();
         if (!chained[i]) out[i].round = -1;
         rc = align_device_paths(pm, it[i].src, it[i].n, it[i].stride, it[i].gt, it[i].gq, out[i].t, out[i].q_wxyz,
                                 &out[i].stats);

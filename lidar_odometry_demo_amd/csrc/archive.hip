@@ -19,90 +19,45 @@ using namespace lom;
 using assemble::ScanEntry;
 
 // The archive owns its stream and every buffer below; calls on one archive are serialised by `lock`.
-struct lom_archive {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct lom_archive : DeviceHandle {
     std::mutex lock;
     // the table (host) and the clouds (device): scan k is points [offset, offset + n) of both arrays, 12 bytes each
     std::vector<ScanEntry> table;
     uint64_t points = 0, cap_points = 0;
-    float *d_xyz = nullptr, *d_nrm = nullptr;
+    DeviceBuf xyz, nrm;
     // staging of the assembly, reused call after call and sized by the call: descriptors, the transformed cloud, the
     // [scan][block] matrix of kept counts and its prefix, the compacted cloud
     DeviceBuf desc, stage_xyz, stage_nrm, counts, offsets, out_xyz, out_nrm;
-    void *h_desc = nullptr;  // pinned: the descriptors on their way in
-    size_t h_desc_bytes = 0;
-    uint32_t *h_word = nullptr;  // pinned: the kept total on its way out
+    PinnedBuf h_desc;  // the descriptors on their way in
+    PinnedBuf h_word;  // the kept total on its way out
     // recorded on the archive's stream behind the kernels, for the map's stream to wait on before the insert; recorded on
     // the map's stream behind the insert, for the archive's stream to wait on before it overwrites the staging
     hipEvent_t ready_ev = nullptr, done_ev = nullptr;
     bool done_recorded = false;
-    std::string error;
+
+    float *d_xyz() const { return xyz.as<float>(); }
+    float *d_nrm() const { return nrm.as<float>(); }
 };
 
 namespace {
 
 thread_local std::string g_archive_create_error;
 
-int afail(lom_archive *a, int code, const std::string &what, hipError_t e = hipSuccess)
-{
-    std::string s = what;
-    if (e != hipSuccess) s += std::string(": ") + hipGetErrorString(e);
-    if (a)
-        a->error = s;
-    else
-        g_archive_create_error = s;
-    return code;
-}
-
-#define AR_HIP(a, expr)                                                    \
-    do {                                                                   \
-        hipError_t _e = (expr);                                            \
-        if (_e != hipSuccess) return afail((a), LOM_ERR_HIP, #expr, _e);   \
-    } while (0)
-
-// grow-only device buffer of the staging (nothing is carried over)
-int ensure_buf(lom_archive *a, DeviceBuf &b, size_t bytes)
-{
-    if (b.bytes >= bytes && b.p) return LOM_OK;
-    const size_t want = (std::max<size_t>(std::max(bytes, b.bytes + b.bytes / 2), 256) + 255) & ~size_t(255);
-    AR_HIP(a, hipStreamSynchronize(a->stream));  // what is enqueued may still use the old block
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr, b.bytes = 0;
-    if (hipMalloc(&b.p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        return afail(a, LOM_ERR_OOM, "hipMalloc (assembly staging)");
-    }
-    b.bytes = want;
-    return LOM_OK;
-}
-
 // room for `need` points: geometric growth, the stored clouds copied device to device in stream order
 int reserve_points(lom_archive *a, uint64_t need)
 {
-    if (need <= a->cap_points && a->d_xyz) return LOM_OK;
+    if (need <= a->cap_points && a->xyz.p) return LOM_OK;
     const uint64_t cap = std::max<uint64_t>(std::max(need, a->cap_points * 2), 1);
-    float *nx = nullptr, *nn = nullptr;
-    if (hipMalloc((void **)&nx, cap * 12) != hipSuccess || hipMalloc((void **)&nn, cap * 12) != hipSuccess) {
-        (void)hipGetLastError();
-        if (nx) (void)hipFree(nx);
-        return afail(a, LOM_ERR_OOM, "hipMalloc (scan archive)");
-    }
+    DeviceBuf nx, nn;
+    if (alloc(nx, cap * 12) != hipSuccess || alloc(nn, cap * 12) != hipSuccess) return fail(a, LOM_ERR_OOM, "hipMalloc (scan archive)");
     hipError_t e = hipSuccess;
     if (a->points) {
-        e = hipMemcpyAsync(nx, a->d_xyz, a->points * 12, hipMemcpyDeviceToDevice, a->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(nn, a->d_nrm, a->points * 12, hipMemcpyDeviceToDevice, a->stream);
+        e = hipMemcpyAsync(nx.p, a->xyz.p, a->points * 12, hipMemcpyDeviceToDevice, a->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(nn.p, a->nrm.p, a->points * 12, hipMemcpyDeviceToDevice, a->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(a->stream);  // the old blocks are freed below
-    if (e != hipSuccess) {
-        (void)hipFree(nx);
-        (void)hipFree(nn);
-        return afail(a, LOM_ERR_HIP, "growing the scan archive", e);
-    }
-    if (a->d_xyz) (void)hipFree(a->d_xyz);
-    if (a->d_nrm) (void)hipFree(a->d_nrm);
-    a->d_xyz = nx, a->d_nrm = nn, a->cap_points = cap;
+    if (e != hipSuccess) return fail(a, LOM_ERR_HIP, "growing the scan archive", e);
+    a->xyz = std::move(nx), a->nrm = std::move(nn), a->cap_points = cap;
     return LOM_OK;
 }
 
@@ -112,21 +67,21 @@ bool stride_ok(size_t stride) { return stride >= 12 && (stride & 3) == 0; }
 int64_t add_scan(lom_archive *a, const float *xyz, const float *nrm, size_t n, size_t stride, hipMemcpyKind kind)
 {
     if (a->points + n > assemble::kArchiveMaxPoints)
-        return afail(a, LOM_ERR_ARG, "more than 2^32 points in one archive (32-bit indices)");
-    if (hipSetDevice(a->device) != hipSuccess) return afail(a, LOM_ERR_HIP, "hipSetDevice");
+        return fail(a, LOM_ERR_ARG, "more than 2^32 points in one archive (32-bit indices)");
+    if (hipSetDevice(a->device) != hipSuccess) return fail(a, LOM_ERR_HIP, "hipSetDevice");
     if (n) {
         int rc = reserve_points(a, a->points + n);
         if (rc != LOM_OK) return rc;
-        float *dx = a->d_xyz + a->points * 3, *dn = a->d_nrm + a->points * 3;
+        float *dx = a->d_xyz() + a->points * 3, *dn = a->d_nrm() + a->points * 3;
         if (stride == 12) {
-            AR_HIP(a, hipMemcpyAsync(dx, xyz, n * 12, kind, a->stream));
-            AR_HIP(a, hipMemcpyAsync(dn, nrm, n * 12, kind, a->stream));
+            LOM_HIP(a, hipMemcpyAsync(dx, xyz, n * 12, kind, a->stream));
+            LOM_HIP(a, hipMemcpyAsync(dn, nrm, n * 12, kind, a->stream));
         } else {
-            AR_HIP(a, hipMemcpy2DAsync(dx, 12, xyz, stride, 12, n, kind, a->stream));
-            AR_HIP(a, hipMemcpy2DAsync(dn, 12, nrm, stride, 12, n, kind, a->stream));
+            LOM_HIP(a, hipMemcpy2DAsync(dx, 12, xyz, stride, 12, n, kind, a->stream));
+            LOM_HIP(a, hipMemcpy2DAsync(dn, 12, nrm, stride, 12, n, kind, a->stream));
         }
         // the caller's buffers are its own again when the call returns
-        AR_HIP(a, hipStreamSynchronize(a->stream));
+        LOM_HIP(a, hipStreamSynchronize(a->stream));
     }
     a->table.push_back(ScanEntry{a->points, (uint32_t)n});
     a->points += n;
@@ -140,10 +95,10 @@ int launch_transform(lom_archive *a, const assemble::Plan &plan, const lom_assem
     for (size_t c0 = 0; c0 < count; c0 += assemble::kAsmScansPerLaunch) {
         const uint32_t ny = (uint32_t)std::min<size_t>(assemble::kAsmScansPerLaunch, count - c0);
         hipLaunchKernelGGL(k_asm_transform<kCull>, dim3(plan.grid_x, ny), dim3(kAsmThreads), 0, a->stream,
-                           (const AsmScan *)a->desc.p + c0, a->d_xyz, a->d_nrm, (float *)a->stage_xyz.p,
-                           (float *)a->stage_nrm.p, kCull ? p->centre[0] : 0.f, kCull ? p->centre[1] : 0.f,
-                           kCull ? p->centre[2] : 0.f, r2, (uint32_t *)a->counts.p);
-        AR_HIP(a, hipGetLastError());
+                           a->desc.as<const AsmScan>() + c0, a->d_xyz(), a->d_nrm(), a->stage_xyz.as<float>(),
+                           a->stage_nrm.as<float>(), kCull ? p->centre[0] : 0.f, kCull ? p->centre[1] : 0.f,
+                           kCull ? p->centre[2] : 0.f, r2, a->counts.as<uint32_t>());
+        LOM_HIP(a, hipGetLastError());
     }
     return LOM_OK;
 }
@@ -157,27 +112,17 @@ int lom_archive_create(int device, size_t point_hint, size_t scan_hint, lom_arch
     if (!out) return LOM_ERR_ARG;
     *out = nullptr;
     if ((uint64_t)point_hint > assemble::kArchiveMaxPoints || scan_hint > assemble::kAsmMaxScans)
-        return afail(nullptr, LOM_ERR_ARG, "point_hint <= 2^32, scan_hint <= 2^24");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return afail(nullptr, LOM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    }
-    if (device < 0 || device >= ndev) return afail(nullptr, LOM_ERR_ARG, "device index out of range");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess)
-        return afail(nullptr, LOM_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return afail(nullptr, LOM_ERR_NO_DEVICE, "kernels are built for gfx950 only");
+        return create_fail(g_archive_create_error, LOM_ERR_ARG, "point_hint <= 2^32, scan_hint <= 2^24");
+    if (const int rc = check_device(device, g_archive_create_error); rc != LOM_OK) return rc;
     lom_archive *a = new (std::nothrow) lom_archive();
-    if (!a) return afail(nullptr, LOM_ERR_OOM, "host allocation");
+    if (!a) return create_fail(g_archive_create_error, LOM_ERR_OOM, "host allocation");
     a->device = device;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&a->ready_ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&a->done_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&a->h_word, 64, hipHostMallocDefault);
-    int rc = e == hipSuccess ? LOM_OK : afail(nullptr, LOM_ERR_HIP, "scan archive setup", e);
+    if (e == hipSuccess) e = alloc(a->h_word, 64, hipHostMallocDefault);
+    int rc = e == hipSuccess ? LOM_OK : create_fail(g_archive_create_error, LOM_ERR_HIP, "scan archive setup", e);
     if (rc == LOM_OK) {
         rc = reserve_points(a, std::max<size_t>(point_hint, 1));
         if (rc != LOM_OK) g_archive_create_error = a->error;
@@ -196,16 +141,10 @@ void lom_archive_destroy(lom_archive *a)
     if (!a) return;
     (void)hipSetDevice(a->device);
     if (a->stream) (void)hipStreamSynchronize(a->stream);
-    if (a->d_xyz) (void)hipFree(a->d_xyz);
-    if (a->d_nrm) (void)hipFree(a->d_nrm);
-    for (DeviceBuf *b : {&a->desc, &a->stage_xyz, &a->stage_nrm, &a->counts, &a->offsets, &a->out_xyz, &a->out_nrm})
-        if (b->p) (void)hipFree(b->p);
-    if (a->h_desc) (void)hipHostFree(a->h_desc);
-    if (a->h_word) (void)hipHostFree(a->h_word);
     if (a->ready_ev) (void)hipEventDestroy(a->ready_ev);
     if (a->done_ev) (void)hipEventDestroy(a->done_ev);
     if (a->stream) (void)hipStreamDestroy(a->stream);
-    delete a;
+    delete a;  // the buffers go with it
 }
 
 const char *lom_archive_last_error(const lom_archive *a) { return a ? a->error.c_str() : g_archive_create_error.c_str(); }
@@ -226,8 +165,8 @@ int lom_archive_wait_event(lom_archive *a, void *hip_event)
 {
     if (!a || !hip_event) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(a->lock);
-    AR_HIP(a, hipSetDevice(a->device));
-    AR_HIP(a, hipStreamWaitEvent(a->stream, (hipEvent_t)hip_event, 0));
+    LOM_HIP(a, hipSetDevice(a->device));
+    LOM_HIP(a, hipStreamWaitEvent(a->stream, (hipEvent_t)hip_event, 0));
     return LOM_OK;
 }
 
@@ -238,7 +177,7 @@ int64_t lom_archive_add(lom_archive *a, const float *xyz, const float *nrm, size
     for (size_t i = 0; i < n; i++) {
         const float *p = reinterpret_cast<const float *>(reinterpret_cast<const char *>(xyz) + i * stride);
         if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]))
-            return afail(a, LOM_ERR_ARG, "point " + std::to_string(i) + " has a coordinate that is not finite");
+            return fail(a, LOM_ERR_ARG, ("point " + std::to_string(i) + " has a coordinate that is not finite").c_str());
     }
     return add_scan(a, xyz, nrm, n, stride, hipMemcpyHostToDevice);
 }
@@ -249,8 +188,8 @@ int64_t lom_archive_add_device(lom_archive *a, const float *d_xyz, const float *
     if (!a || (n && (!d_xyz || !d_nrm)) || !stride_ok(stride)) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(a->lock);
     if (hip_event_or_null) {
-        AR_HIP(a, hipSetDevice(a->device));
-        AR_HIP(a, hipStreamWaitEvent(a->stream, (hipEvent_t)hip_event_or_null, 0));
+        LOM_HIP(a, hipSetDevice(a->device));
+        LOM_HIP(a, hipStreamWaitEvent(a->stream, (hipEvent_t)hip_event_or_null, 0));
     }
     return add_scan(a, d_xyz, d_nrm, n, stride, hipMemcpyDeviceToDevice);
 }
@@ -273,7 +212,7 @@ int64_t lom_archive_scan_size(const lom_archive *a, int64_t id)
 {
     if (!a) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(const_cast<lom_archive *>(a)->lock);
-    if (id < 0 || id >= (int64_t)a->table.size()) return afail(const_cast<lom_archive *>(a), LOM_ERR_ARG, "no scan with this id");
+    if (id < 0 || id >= (int64_t)a->table.size()) return fail(const_cast<lom_archive *>(a), LOM_ERR_ARG, "no scan with this id");
     return (int64_t)a->table[(size_t)id].n;
 }
 
@@ -281,14 +220,14 @@ int64_t lom_archive_get(lom_archive *a, int64_t id, float *xyz_out, float *nrm_o
 {
     if (!a) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(a->lock);
-    if (id < 0 || id >= (int64_t)a->table.size()) return afail(a, LOM_ERR_ARG, "no scan with this id");
+    if (id < 0 || id >= (int64_t)a->table.size()) return fail(a, LOM_ERR_ARG, "no scan with this id");
     const ScanEntry e = a->table[(size_t)id];
     const size_t n = std::min<size_t>(e.n, cap);
     if (n && (xyz_out || nrm_out)) {
-        AR_HIP(a, hipSetDevice(a->device));
-        if (xyz_out) AR_HIP(a, hipMemcpyAsync(xyz_out, a->d_xyz + e.offset * 3, n * 12, hipMemcpyDeviceToHost, a->stream));
-        if (nrm_out) AR_HIP(a, hipMemcpyAsync(nrm_out, a->d_nrm + e.offset * 3, n * 12, hipMemcpyDeviceToHost, a->stream));
-        AR_HIP(a, hipStreamSynchronize(a->stream));
+        LOM_HIP(a, hipSetDevice(a->device));
+        if (xyz_out) LOM_HIP(a, hipMemcpyAsync(xyz_out, a->d_xyz() + e.offset * 3, n * 12, hipMemcpyDeviceToHost, a->stream));
+        if (nrm_out) LOM_HIP(a, hipMemcpyAsync(nrm_out, a->d_nrm() + e.offset * 3, n * 12, hipMemcpyDeviceToHost, a->stream));
+        LOM_HIP(a, hipStreamSynchronize(a->stream));
     }
     return (int64_t)e.n;
 }
@@ -299,81 +238,73 @@ int lom_map_assemble(lom_map *m, lom_archive *a, const int64_t *ids, const lom_g
     if (!m || !a) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(a->lock);
     if (stats) std::memset(stats, 0, sizeof *stats);
-    if (m->parent) return afail(a, LOM_ERR_ARG, "a scan context has no map of its own");
-    if (m->device != a->device) return afail(a, LOM_ERR_ARG, "the map and the archive live on different devices");
+    if (m->parent) return fail(a, LOM_ERR_ARG, "a scan context has no map of its own");
+    if (m->device != a->device) return fail(a, LOM_ERR_ARG, "the map and the archive live on different devices");
     bool cull = false;
     std::string why;
     int rc = assemble::cull_of(params, &cull, why);
     assemble::Plan plan;
     if (rc == LOM_OK) rc = assemble::plan(a->table.data(), a->table.size(), ids, poses, count, plan, why);
-    if (rc != LOM_OK) return afail(a, rc, why);
+    if (rc != LOM_OK) return fail(a, rc, why.c_str());
     lom_assemble_stats st;
     std::memset(&st, 0, sizeof st);
     st.scans = (int64_t)count;
     st.points_in = st.points_kept = (int64_t)plan.points_in;
-    auto fail_map = [&](int code) { return afail(a, code, std::string("map: ") + lom_last_error(m)); };
+    auto fail_map = [&](int code) { return fail(a, code, (std::string("map: ") + lom_last_error(m)).c_str()); };
     if (stats) {
         st.voxels_before = lom_map_size(m);
         if (st.voxels_before < 0) return fail_map((int)st.voxels_before);
     }
     size_t kept = (size_t)plan.points_in;
     if (kept) {
-        AR_HIP(a, hipSetDevice(a->device));
+        LOM_HIP(a, hipSetDevice(a->device));
+        // (kept != 0: there is a scan, a point and a block, so none of the seven requests below is for zero bytes)
         const size_t desc_bytes = count * sizeof(AsmScan), cloud_bytes = kept * 12;
-        if ((rc = ensure_buf(a, a->desc, desc_bytes)) != LOM_OK) return rc;
-        if ((rc = ensure_buf(a, a->stage_xyz, cloud_bytes)) != LOM_OK) return rc;
-        if ((rc = ensure_buf(a, a->stage_nrm, cloud_bytes)) != LOM_OK) return rc;
+        if ((rc = ensure(a, a->desc, desc_bytes)) != LOM_OK) return rc;
+        if ((rc = ensure(a, a->stage_xyz, cloud_bytes)) != LOM_OK) return rc;
+        if ((rc = ensure(a, a->stage_nrm, cloud_bytes)) != LOM_OK) return rc;
         if (cull) {
-            if ((rc = ensure_buf(a, a->counts, (size_t)plan.blocks * 4)) != LOM_OK) return rc;
-            if ((rc = ensure_buf(a, a->offsets, ((size_t)plan.blocks + 1) * 4)) != LOM_OK) return rc;
-            if ((rc = ensure_buf(a, a->out_xyz, cloud_bytes)) != LOM_OK) return rc;
-            if ((rc = ensure_buf(a, a->out_nrm, cloud_bytes)) != LOM_OK) return rc;
+            if ((rc = ensure(a, a->counts, (size_t)plan.blocks * 4)) != LOM_OK) return rc;
+            if ((rc = ensure(a, a->offsets, ((size_t)plan.blocks + 1) * 4)) != LOM_OK) return rc;
+            if ((rc = ensure(a, a->out_xyz, cloud_bytes)) != LOM_OK) return rc;
+            if ((rc = ensure(a, a->out_nrm, cloud_bytes)) != LOM_OK) return rc;
         }
-        if (a->h_desc_bytes < desc_bytes) {
-            AR_HIP(a, hipStreamSynchronize(a->stream));
-            if (a->h_desc) (void)hipHostFree(a->h_desc);
-            a->h_desc = nullptr, a->h_desc_bytes = 0;
-            const size_t want = std::max(desc_bytes + desc_bytes / 2, (size_t)1 << 16);
-            if (hipHostMalloc(&a->h_desc, want, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                a->h_desc = nullptr;
-                return afail(a, LOM_ERR_OOM, "hipHostMalloc (assembly descriptors)");
-            }
-            a->h_desc_bytes = want;
-        }
+        if ((rc = ensure_pinned(a, a->h_desc, desc_bytes, std::max(desc_bytes + desc_bytes / 2, (size_t)1 << 16), hipHostMallocDefault,
+                                "hipHostMalloc (assembly descriptors)")) != LOM_OK)
+            return rc;
         // the previous call's insert has read the staging before this call writes it
-        if (a->done_recorded) AR_HIP(a, hipStreamWaitEvent(a->stream, a->done_ev, 0));
-        std::memcpy(a->h_desc, plan.scans.data(), desc_bytes);
-        AR_HIP(a, hipMemcpyAsync(a->desc.p, a->h_desc, desc_bytes, hipMemcpyHostToDevice, a->stream));
-        const float *cloud_xyz = (const float *)a->stage_xyz.p, *cloud_nrm = (const float *)a->stage_nrm.p;
+        if (a->done_recorded) LOM_HIP(a, hipStreamWaitEvent(a->stream, a->done_ev, 0));
+        std::memcpy(a->h_desc.h, plan.scans.data(), desc_bytes);
+        LOM_HIP(a, hipMemcpyAsync(a->desc.p, a->h_desc.h, desc_bytes, hipMemcpyHostToDevice, a->stream));
+        const float *cloud_xyz = a->stage_xyz.as<const float>(), *cloud_nrm = a->stage_nrm.as<const float>();
         if (!cull) {
             if ((rc = launch_transform<false>(a, plan, params, 0.f)) != LOM_OK) return rc;
         } else {
             const float r2 = params->radius * params->radius;
             if ((rc = launch_transform<true>(a, plan, params, r2)) != LOM_OK) return rc;
-            hipLaunchKernelGGL(k_asm_offsets, dim3(1), dim3(kAsmOffsetThreads), 0, a->stream, (const uint32_t *)a->counts.p,
-                               plan.blocks, (uint32_t *)a->offsets.p);
-            AR_HIP(a, hipGetLastError());
+            hipLaunchKernelGGL(k_asm_offsets, dim3(1), dim3(kAsmOffsetThreads), 0, a->stream, a->counts.as<const uint32_t>(),
+                               plan.blocks, a->offsets.as<uint32_t>());
+            LOM_HIP(a, hipGetLastError());
             for (size_t c0 = 0; c0 < count; c0 += assemble::kAsmScansPerLaunch) {
                 const uint32_t ny = (uint32_t)std::min<size_t>(assemble::kAsmScansPerLaunch, count - c0);
                 hipLaunchKernelGGL(k_asm_compact, dim3(plan.grid_x, ny), dim3(kAsmThreads), 0, a->stream,
-                                   (const AsmScan *)a->desc.p + c0, cloud_xyz, cloud_nrm, params->centre[0], params->centre[1],
-                                   params->centre[2], r2, (const uint32_t *)a->offsets.p, (float *)a->out_xyz.p,
-                                   (float *)a->out_nrm.p);
-                AR_HIP(a, hipGetLastError());
+                                   a->desc.as<const AsmScan>() + c0, cloud_xyz, cloud_nrm, params->centre[0], params->centre[1],
+                                   params->centre[2], r2, a->offsets.as<const uint32_t>(), a->out_xyz.as<float>(),
+                                   a->out_nrm.as<float>());
+                LOM_HIP(a, hipGetLastError());
             }
             // the one read-back before the insert: its size
-            AR_HIP(a, hipMemcpyAsync(a->h_word, (const uint32_t *)a->offsets.p + plan.blocks, 4, hipMemcpyDeviceToHost, a->stream));
-            AR_HIP(a, hipStreamSynchronize(a->stream));
-            kept = a->h_word[0];
-            cloud_xyz = (const float *)a->out_xyz.p, cloud_nrm = (const float *)a->out_nrm.p;
+            LOM_HIP(a, hipMemcpyAsync(a->h_word.h, a->offsets.as<const uint32_t>() + plan.blocks, 4, hipMemcpyDeviceToHost, a->stream));
+            LOM_HIP(a, hipStreamSynchronize(a->stream));
+            kept = a->h_word.as<uint32_t>()[0];
+            cloud_xyz = a->out_xyz.as<const float>(), cloud_nrm = a->out_nrm.as<const float>();
         }
         st.points_kept = (int64_t)kept;
         if (kept) {
-            AR_HIP(a, hipEventRecord(a->ready_ev, a->stream));
-            AR_HIP(a, hipStreamWaitEvent(m->stream, a->ready_ev, 0));
+            LOM_HIP(a, hipEventRecord(a->ready_ev, a->stream));
+            LOM_HIP(a, hipStreamWaitEvent(m->stream, a->ready_ev, 0));
             rc = lom_map_add_points_device(m, cloud_xyz, cloud_nrm, kept, 12);  // atomic: all of the cloud or nothing
-            AR_HIP(a, hipEventRecord(a->done_ev, m->stream));
+            LOM_HIP(a, hipEventRecord(a->done_ev, m->stream));
             a->done_recorded = true;
             if (rc != LOM_OK) return fail_map(rc);
         }

@@ -66,7 +66,7 @@ int comm_error(lom_map *m, const char *what, ncclResult_t e)
     std::string s = what;
     s += ": ";
     s += rccl().GetErrorString ? rccl().GetErrorString(e) : "rccl error";
-    return lom::set_error(m, LOM_ERR_COMM, s.c_str());
+    return m ? lom::fail(m, LOM_ERR_COMM, s.c_str()) : lom::create_fail(lom::map_create_error(), LOM_ERR_COMM, s.c_str());
 }
 
 }  // namespace
@@ -76,7 +76,7 @@ namespace lom {
 int comm_allgather_sums(lom_map *m, const double *d_send, double *d_recv, int count)
 {
     Rccl &r = rccl();
-    if (!r.ok || !m->comm) return set_error(m, LOM_ERR_COMM, "communicator not initialised");
+    if (!r.ok || !m->comm) return fail(m, LOM_ERR_COMM, "communicator not initialised");
     const ncclResult_t e = r.AllGather(d_send, d_recv, (size_t)count, ncclFloat64, (ncclComm_t)m->comm, m->stream);
     if (e != ncclSuccess) return comm_error(m, "ncclAllGather", e);
     return LOM_OK;
@@ -201,10 +201,10 @@ int host_comm_allreduce_deadline(void *hcv, double *buf, int count, double timeo
 int host_exchange_sums(lom_map *m, const double *mine, double *out)
 {
     lom_host_comm *hc = reinterpret_cast<lom_host_comm *>(m->host_comm);
-    if (!hc) return set_error(m, LOM_ERR_COMM, "host exchange not attached");
+    if (!hc) return fail(m, LOM_ERR_COMM, "host exchange not attached");
     for (int k = 0; k < LOM_NSUMS; k++) out[k] = mine[k];
     const int rc = lom_host_comm_allreduce(hc, out, LOM_NSUMS);
-    if (rc != LOM_OK) return set_error(m, rc, hc->error.c_str());
+    if (rc != LOM_OK) return fail(m, rc, hc->error.c_str());
     return LOM_OK;
 }
 
@@ -292,7 +292,7 @@ void lom_host_comm_destroy(lom_host_comm *hc)
 int lom_comm_attach_host(lom_map *m, lom_host_comm *hc)
 {
     if (!m) return LOM_ERR_ARG;
-    if (m->comm) return lom::set_error(m, LOM_ERR_STATE, "an RCCL communicator is already attached");
+    if (m->comm) return lom::fail(m, LOM_ERR_STATE, "an RCCL communicator is already attached");
     if (m->p2p) lom::p2p_detach(m);
     m->host_comm = hc;  // NULL detaches; the caller keeps ownership
     m->rank = hc ? hc->rank : 0;
@@ -307,7 +307,7 @@ int lom_comm_host_id(char id_out[LOM_COMM_ID_BYTES])
     const int fd = open("/dev/urandom", O_RDONLY);
     if (fd < 0 || read(fd, id_out, 16) != 16) {
         if (fd >= 0) close(fd);
-        return lom::set_error(nullptr, LOM_ERR_COMM, "/dev/urandom not readable");
+        return lom::create_fail(lom::map_create_error(), LOM_ERR_COMM, "/dev/urandom not readable");
     }
     close(fd);
     return LOM_OK;
@@ -318,7 +318,7 @@ int lom_comm_unique_id(char id_out[LOM_COMM_ID_BYTES])
     static_assert(LOM_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "id size");
     if (!id_out) return LOM_ERR_ARG;
     Rccl &r = rccl();
-    if (!r.ok) return lom::set_error(nullptr, LOM_ERR_COMM, "librccl.so could not be loaded");
+    if (!r.ok) return lom::create_fail(lom::map_create_error(), LOM_ERR_COMM, "librccl.so could not be loaded");
     ncclUniqueId id;
     const ncclResult_t e = r.GetUniqueId(&id);
     if (e != ncclSuccess) return comm_error(nullptr, "ncclGetUniqueId", e);
@@ -329,9 +329,9 @@ int lom_comm_unique_id(char id_out[LOM_COMM_ID_BYTES])
 int lom_comm_init(lom_map *m, int rank, int nranks, const char id_in[LOM_COMM_ID_BYTES])
 {
     if (!m || !id_in || nranks < 1 || rank < 0 || rank >= nranks) return LOM_ERR_ARG;
-    if (m->comm || m->host_comm) return lom::set_error(m, LOM_ERR_STATE, "communicator already initialised");
+    if (m->comm || m->host_comm) return lom::fail(m, LOM_ERR_STATE, "communicator already initialised");
     Rccl &r = rccl();
-    if (!r.ok) return lom::set_error(m, LOM_ERR_COMM, "librccl.so could not be loaded");
+    if (!r.ok) return lom::fail(m, LOM_ERR_COMM, "librccl.so could not be loaded");
     LOM_HIP(m, hipSetDevice(m->device));
     ncclUniqueId id;
     std::memcpy(id.internal, id_in, LOM_COMM_ID_BYTES);

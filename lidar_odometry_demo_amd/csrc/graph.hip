@@ -36,9 +36,7 @@ constexpr int64_t kGraphMax = 1ll << 27;  // nodes, edges: indices and n * 6 sta
 }  // namespace
 
 // The graph owns its stream and every buffer below; calls on one graph are serialised by `lock`.
-struct lom_graph {
-    int device = 0;
-    hipStream_t stream = nullptr;
+struct lom_graph : DeviceHandle {
     std::mutex lock;
     // the record
     std::vector<double> poses, Z, U, delta;  // [n][7], [m][7], [m][21], [m]
@@ -47,38 +45,21 @@ struct lom_graph {
     bool nodes_dirty = true, edges_dirty = true;
     size_t cap_n = 0, cap_m = 0;
     DeviceBuf buf[G_COUNT];
-    GraphReport *h_report = nullptr, *d_report = nullptr;  // pinned
-    std::string error;
+    PinnedBuf report;  // GraphReport: h_report the host's view, d_report the device's
+    GraphReport *h_report = nullptr, *d_report = nullptr;
 
     size_t n() const { return fixed.size(); }
     size_t m() const { return delta.size(); }
     template <typename T>
     T *dev(int which) const
     {
-        return (T *)buf[which].p;
+        return buf[which].as<T>();
     }
 };
 
 namespace {
 
 thread_local std::string g_graph_create_error;
-
-int gfail(lom_graph *g, int code, const std::string &what, hipError_t e = hipSuccess)
-{
-    std::string s = what;
-    if (e != hipSuccess) s += std::string(": ") + hipGetErrorString(e);
-    if (g)
-        g->error = s;
-    else
-        g_graph_create_error = s;
-    return code;
-}
-
-#define GR_HIP(g, expr)                                                    \
-    do {                                                                   \
-        hipError_t _e = (expr);                                            \
-        if (_e != hipSuccess) return gfail((g), LOM_ERR_HIP, #expr, _e);   \
-    } while (0)
 
 uint32_t blocks_of(size_t count, size_t per) { return (uint32_t)std::max<size_t>((count + per - 1) / per, 1); }
 
@@ -89,7 +70,7 @@ int reserve_device(lom_graph *g, size_t need_n, size_t need_m)
     if (!grow_n && !grow_m && g->buf[G_SCAL].p) return LOM_OK;
     const size_t cap_n = grow_n ? std::max(need_n, g->cap_n * 2) : g->cap_n;
     const size_t cap_m = grow_m ? std::max(need_m, g->cap_m * 2) : g->cap_m;
-    GR_HIP(g, hipStreamSynchronize(g->stream));
+    LOM_HIP(g, hipStreamSynchronize(g->stream));
     for (int b = 0; b < G_COUNT; b++) {
         const bool per_edge = b >= kFirstEdgeBuf && b != G_SCAL;
         if (b == G_SCAL ? g->buf[b].p != nullptr : !(per_edge ? grow_m : grow_n)) continue;
@@ -102,17 +83,12 @@ int reserve_device(lom_graph *g, size_t need_n, size_t need_m)
             bytes = (cap_n / kGraphRowsPerBlock + 2) * 8;
         else
             bytes = (per_edge ? cap_m : cap_n) * kBytesPer[b];
-        bytes = (std::max<size_t>(bytes, 8) + 255) & ~size_t(255);
-        if (g->buf[b].p) (void)hipFree(g->buf[b].p);
-        g->buf[b].p = nullptr, g->buf[b].bytes = 0;
-        if (hipMalloc(&g->buf[b].p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            g->buf[b].p = nullptr;
+        release(g->buf[b]);  // exactly this size, not 1.5 times the old one: the capacities above are the growth rule
+        if (ensure(g, g->buf[b], std::max<size_t>(bytes, 8)) != LOM_OK) {
             if (per_edge) g->cap_m = 0; else g->cap_n = 0;  // the next call allocates afresh
             g->nodes_dirty = g->edges_dirty = true;
-            return gfail(g, LOM_ERR_OOM, "hipMalloc (pose graph)");
+            return fail(g, LOM_ERR_OOM, "hipMalloc (pose graph)");
         }
-        g->buf[b].bytes = bytes;
     }
     if (grow_n) g->cap_n = cap_n, g->nodes_dirty = true;
     if (grow_m) g->cap_m = cap_m, g->edges_dirty = true;
@@ -126,23 +102,23 @@ int sync_device(lom_graph *g)
     int rc = reserve_device(g, std::max<size_t>(n, 1), std::max<size_t>(m, 1));
     if (rc != LOM_OK) return rc;
     if (g->nodes_dirty && n) {
-        GR_HIP(g, hipMemcpyAsync(g->buf[G_POSE].p, g->poses.data(), n * 56, hipMemcpyHostToDevice, g->stream));
-        GR_HIP(g, hipMemcpyAsync(g->buf[G_FIXED].p, g->fixed.data(), n * 4, hipMemcpyHostToDevice, g->stream));
+        LOM_HIP(g, hipMemcpyAsync(g->buf[G_POSE].p, g->poses.data(), n * 56, hipMemcpyHostToDevice, g->stream));
+        LOM_HIP(g, hipMemcpyAsync(g->buf[G_FIXED].p, g->fixed.data(), n * 4, hipMemcpyHostToDevice, g->stream));
     }
     if ((g->edges_dirty || g->nodes_dirty) && n) {  // (more nodes: a longer row_ptr)
         std::vector<uint32_t> row_ptr, entries;
         graph::build_csr((int64_t)n, (int64_t)m, g->ij.data(), row_ptr, entries);
-        GR_HIP(g, hipMemcpyAsync(g->buf[G_ROW].p, row_ptr.data(), (n + 1) * 4, hipMemcpyHostToDevice, g->stream));
-        if (m) GR_HIP(g, hipMemcpyAsync(g->buf[G_ENT].p, entries.data(), m * 8, hipMemcpyHostToDevice, g->stream));
-        GR_HIP(g, hipStreamSynchronize(g->stream));  // the vectors go out of scope
+        LOM_HIP(g, hipMemcpyAsync(g->buf[G_ROW].p, row_ptr.data(), (n + 1) * 4, hipMemcpyHostToDevice, g->stream));
+        if (m) LOM_HIP(g, hipMemcpyAsync(g->buf[G_ENT].p, entries.data(), m * 8, hipMemcpyHostToDevice, g->stream));
+        LOM_HIP(g, hipStreamSynchronize(g->stream));  // the vectors go out of scope
     }
     if (g->edges_dirty && m) {
-        GR_HIP(g, hipMemcpyAsync(g->buf[G_IJ].p, g->ij.data(), m * 8, hipMemcpyHostToDevice, g->stream));
-        GR_HIP(g, hipMemcpyAsync(g->buf[G_Z].p, g->Z.data(), m * 56, hipMemcpyHostToDevice, g->stream));
-        GR_HIP(g, hipMemcpyAsync(g->buf[G_U].p, g->U.data(), m * 168, hipMemcpyHostToDevice, g->stream));
-        GR_HIP(g, hipMemcpyAsync(g->buf[G_DELTA].p, g->delta.data(), m * 8, hipMemcpyHostToDevice, g->stream));
+        LOM_HIP(g, hipMemcpyAsync(g->buf[G_IJ].p, g->ij.data(), m * 8, hipMemcpyHostToDevice, g->stream));
+        LOM_HIP(g, hipMemcpyAsync(g->buf[G_Z].p, g->Z.data(), m * 56, hipMemcpyHostToDevice, g->stream));
+        LOM_HIP(g, hipMemcpyAsync(g->buf[G_U].p, g->U.data(), m * 168, hipMemcpyHostToDevice, g->stream));
+        LOM_HIP(g, hipMemcpyAsync(g->buf[G_DELTA].p, g->delta.data(), m * 8, hipMemcpyHostToDevice, g->stream));
     }
-    GR_HIP(g, hipStreamSynchronize(g->stream));  // pageable sources: the record may change as soon as this returns
+    LOM_HIP(g, hipStreamSynchronize(g->stream));  // pageable sources: the record may change as soon as this returns
     g->nodes_dirty = g->edges_dirty = false;
     return LOM_OK;
 }
@@ -154,7 +130,7 @@ int enqueue_linearise(lom_graph *g)
                        g->dev<const double>(G_POSE), g->dev<const int32_t>(G_IJ), g->dev<const double>(G_Z),
                        g->dev<const double>(G_U), g->dev<const double>(G_DELTA), g->dev<double>(G_E), g->dev<double>(G_S),
                        g->dev<double>(G_W), g->dev<double>(G_COST), g->dev<double>(G_B), g->dev<double>(G_C));
-    GR_HIP(g, hipGetLastError());
+    LOM_HIP(g, hipGetLastError());
     return LOM_OK;
 }
 
@@ -165,7 +141,7 @@ int enqueue_gather(lom_graph *g, double lambda)
                        g->dev<const int32_t>(G_FIXED), g->dev<const uint32_t>(G_ROW), g->dev<const uint32_t>(G_ENT),
                        g->dev<const double>(G_B), g->dev<const double>(G_C), lambda, g->dev<double>(G_G), g->dev<double>(G_HD),
                        g->dev<double>(G_D), g->dev<double>(G_MINV));
-    GR_HIP(g, hipGetLastError());
+    LOM_HIP(g, hipGetLastError());
     return LOM_OK;
 }
 
@@ -177,12 +153,12 @@ int enqueue_matvec(lom_graph *g, double lambda)
     hipLaunchKernelGGL(k_graph_mv_edge, dim3(blocks_of(m, kGraphThreads)), dim3(kGraphThreads), 0, g->stream, m,
                        g->dev<const int32_t>(G_IJ), g->dev<const int32_t>(G_FIXED), g->dev<const double>(G_B),
                        g->dev<const double>(G_P), g->dev<double>(G_UE), sc);
-    GR_HIP(g, hipGetLastError());
+    LOM_HIP(g, hipGetLastError());
     hipLaunchKernelGGL(k_graph_mv_node, dim3(blocks_of(n, kGraphRowsPerBlock)), dim3(kGraphThreads), 0, g->stream, n,
                        g->dev<const int32_t>(G_FIXED), g->dev<const uint32_t>(G_ROW), g->dev<const uint32_t>(G_ENT),
                        g->dev<const double>(G_B), g->dev<const double>(G_UE), g->dev<const double>(G_D), lambda,
                        g->dev<const double>(G_P), g->dev<double>(G_Y), g->dev<double>(G_PART_A), sc);
-    GR_HIP(g, hipGetLastError());
+    LOM_HIP(g, hipGetLastError());
     return LOM_OK;
 }
 
@@ -190,7 +166,7 @@ int enqueue_scalar(lom_graph *g, int mode, uint32_t count, int part, double rtol
 {
     hipLaunchKernelGGL(k_graph_cg_scalar, dim3(1), dim3(kGraphThreads), 0, g->stream, mode, count,
                        g->dev<const double>(part), rtol2, g->dev<GraphScalars>(G_SCAL));
-    GR_HIP(g, hipGetLastError());
+    LOM_HIP(g, hipGetLastError());
     return LOM_OK;
 }
 
@@ -205,7 +181,7 @@ int enqueue_pcg(lom_graph *g, double lambda, const lom_graph_params *prm)
     hipLaunchKernelGGL(k_graph_cg_init, dim3(nb), dim3(kGraphThreads), 0, g->stream, n, g->dev<const double>(G_G),
                        g->dev<const double>(G_MINV), g->dev<double>(G_X), g->dev<double>(G_R), g->dev<double>(G_ZV),
                        g->dev<double>(G_P), g->dev<double>(G_PART_B));
-    GR_HIP(g, hipGetLastError());
+    LOM_HIP(g, hipGetLastError());
     int rc = enqueue_scalar(g, GRAPH_SCALAR_INIT, nb, G_PART_B, rtol2);
     for (int it = 0; it < prm->max_pcg && rc == LOM_OK; it++) {
         if ((rc = enqueue_matvec(g, lambda)) != LOM_OK) break;
@@ -213,11 +189,11 @@ int enqueue_pcg(lom_graph *g, double lambda, const lom_graph_params *prm)
         hipLaunchKernelGGL(k_graph_cg_update, dim3(nb), dim3(kGraphThreads), 0, g->stream, n, g->dev<const double>(G_MINV),
                            g->dev<const double>(G_P), g->dev<const double>(G_Y), g->dev<double>(G_X), g->dev<double>(G_R),
                            g->dev<double>(G_ZV), g->dev<double>(G_PART_B), sc);
-        GR_HIP(g, hipGetLastError());
+        LOM_HIP(g, hipGetLastError());
         if ((rc = enqueue_scalar(g, GRAPH_SCALAR_BETA, nb, G_PART_B, rtol2)) != LOM_OK) break;
         hipLaunchKernelGGL(k_graph_cg_dir, dim3(blocks_of((size_t)n * 6, kGraphThreads)), dim3(kGraphThreads), 0, g->stream,
                            n * 6, g->dev<const double>(G_ZV), g->dev<double>(G_P), sc);
-        GR_HIP(g, hipGetLastError());
+        LOM_HIP(g, hipGetLastError());
     }
     return rc;
 }
@@ -228,7 +204,7 @@ int enqueue_report(lom_graph *g, double lambda, int with_step)
                        g->dev<const double>(G_COST), g->dev<const double>(G_COSTC), g->dev<const double>(G_G),
                        g->dev<const double>(G_D), g->dev<const double>(G_X), lambda, with_step,
                        g->dev<const GraphScalars>(G_SCAL), g->d_report);
-    GR_HIP(g, hipGetLastError());
+    LOM_HIP(g, hipGetLastError());
     return LOM_OK;
 }
 
@@ -239,7 +215,7 @@ int evaluate_now(lom_graph *g, double lambda)
     if (rc == LOM_OK) rc = enqueue_gather(g, lambda);
     if (rc == LOM_OK) rc = enqueue_report(g, lambda, 0);
     if (rc != LOM_OK) return rc;
-    GR_HIP(g, hipStreamSynchronize(g->stream));
+    LOM_HIP(g, hipStreamSynchronize(g->stream));
     return LOM_OK;
 }
 
@@ -259,26 +235,17 @@ int lom_graph_create(int device, size_t node_hint, size_t edge_hint, lom_graph *
     if (!out) return LOM_ERR_ARG;
     *out = nullptr;
     if (node_hint > (size_t)kGraphMax || edge_hint > (size_t)kGraphMax)
-        return gfail(nullptr, LOM_ERR_ARG, "node_hint, edge_hint <= 2^27");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return gfail(nullptr, LOM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    }
-    if (device < 0 || device >= ndev) return gfail(nullptr, LOM_ERR_ARG, "device index out of range");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess)
-        return gfail(nullptr, LOM_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return gfail(nullptr, LOM_ERR_NO_DEVICE, "kernels are built for gfx950 only");
+        return create_fail(g_graph_create_error, LOM_ERR_ARG, "node_hint, edge_hint <= 2^27");
+    if (const int rc = check_device(device, g_graph_create_error); rc != LOM_OK) return rc;
     lom_graph *g = new (std::nothrow) lom_graph();
-    if (!g) return gfail(nullptr, LOM_ERR_OOM, "host allocation");
+    if (!g) return create_fail(g_graph_create_error, LOM_ERR_OOM, "host allocation");
     g->device = device;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&g->h_report, sizeof(GraphReport), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&g->d_report, g->h_report, 0);
-    int rc = e == hipSuccess ? LOM_OK : gfail(nullptr, LOM_ERR_HIP, "pose graph setup", e);
+    if (e == hipSuccess) e = alloc(g->report, sizeof(GraphReport), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostGetDevicePointer((void **)&g->d_report, g->report.h, 0);
+    g->h_report = g->report.as<GraphReport>();
+    int rc = e == hipSuccess ? LOM_OK : create_fail(g_graph_create_error, LOM_ERR_HIP, "pose graph setup", e);
     if (rc == LOM_OK) {
         rc = reserve_device(g, std::max<size_t>(node_hint, 1), std::max<size_t>(edge_hint, 1));
         if (rc != LOM_OK) g_graph_create_error = g->error;
@@ -298,11 +265,8 @@ void lom_graph_destroy(lom_graph *g)
     if (!g) return;
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
-    for (DeviceBuf &b : g->buf)
-        if (b.p) (void)hipFree(b.p);
-    if (g->h_report) (void)hipHostFree(g->h_report);
     if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
+    delete g;  // the buffers go with it
 }
 
 const char *lom_graph_last_error(const lom_graph *g) { return g ? g->error.c_str() : g_graph_create_error.c_str(); }
@@ -323,9 +287,9 @@ int64_t lom_graph_add_nodes(lom_graph *g, const lom_graph_pose *poses, const int
 {
     if (!g || (n && (!poses || !fixed))) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(g->lock);
-    if (n > (size_t)kGraphMax || g->n() + n > (size_t)kGraphMax) return gfail(g, LOM_ERR_ARG, "more than 2^27 nodes");
+    if (n > (size_t)kGraphMax || g->n() + n > (size_t)kGraphMax) return fail(g, LOM_ERR_ARG, "more than 2^27 nodes");
     for (size_t k = 0; k < n; k++)
-        if (!graph::pose_ok(poses + k)) return gfail(g, LOM_ERR_ARG, "a pose is not finite or its quaternion is zero");
+        if (!graph::pose_ok(poses + k)) return fail(g, LOM_ERR_ARG, "a pose is not finite or its quaternion is zero");
     const int64_t first = (int64_t)g->n();
     for (size_t k = 0; k < n; k++) {
         double x[7];
@@ -349,13 +313,13 @@ int64_t lom_graph_add_edges(lom_graph *g, const int32_t *ij, const lom_graph_pos
 {
     if (!g || (n && (!ij || !z || !omega36 || !delta))) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(g->lock);
-    if (n > (size_t)kGraphMax || g->m() + n > (size_t)kGraphMax) return gfail(g, LOM_ERR_ARG, "more than 2^27 edges");
+    if (n > (size_t)kGraphMax || g->m() + n > (size_t)kGraphMax) return fail(g, LOM_ERR_ARG, "more than 2^27 edges");
     std::vector<double> U(n * 21);
     for (size_t k = 0; k < n; k++)
         if (!edge_ok(g, ij[2 * k], ij[2 * k + 1], z + k, omega36 + k * 36, delta[k], U.data() + k * 21))
-            return gfail(g, LOM_ERR_ARG,
-                         "edge " + std::to_string(k) + " of the call: i == j, a node that does not exist, a bad pose, an "
-                         "Omega that is not positive definite, or a negative delta");
+            return fail(g, LOM_ERR_ARG,
+                        ("edge " + std::to_string(k) + " of the call: i == j, a node that does not exist, a bad pose, an "
+                         "Omega that is not positive definite, or a negative delta").c_str());
     const int64_t first = (int64_t)g->m();
     for (size_t k = 0; k < n; k++) {
         double x[7];
@@ -374,7 +338,7 @@ int64_t lom_graph_add_edge(lom_graph *g, int64_t i, int64_t j, const lom_graph_p
     if (!g || !z || !omega36) return LOM_ERR_ARG;
     if (i < 0 || j < 0 || i >= kGraphMax || j >= kGraphMax) {
         std::lock_guard<std::mutex> lk(g->lock);
-        return gfail(g, LOM_ERR_ARG, "an edge names a node that does not exist");
+        return fail(g, LOM_ERR_ARG, "an edge names a node that does not exist");
     }
     const int32_t ij[2] = {(int32_t)i, (int32_t)j};
     return lom_graph_add_edges(g, ij, z, omega36, &delta, 1);
@@ -398,7 +362,7 @@ int lom_graph_get_poses(lom_graph *g, int64_t first, int64_t n, lom_graph_pose *
 {
     if (!g || n < 0 || first < 0 || (n && !out)) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(g->lock);
-    if (first > (int64_t)g->n() || n > (int64_t)g->n() - first) return gfail(g, LOM_ERR_ARG, "no node with this id");
+    if (first > (int64_t)g->n() || n > (int64_t)g->n() - first) return fail(g, LOM_ERR_ARG, "no node with this id");
     if (n) std::memcpy(out, g->poses.data() + first * 7, (size_t)n * 56);
     return LOM_OK;
 }
@@ -407,8 +371,8 @@ int lom_graph_set_pose(lom_graph *g, int64_t id, const lom_graph_pose *pose)
 {
     if (!g || !pose) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(g->lock);
-    if (id < 0 || id >= (int64_t)g->n()) return gfail(g, LOM_ERR_ARG, "no node with this id");
-    if (!graph::pose_ok(pose)) return gfail(g, LOM_ERR_ARG, "a pose is not finite or its quaternion is zero");
+    if (id < 0 || id >= (int64_t)g->n()) return fail(g, LOM_ERR_ARG, "no node with this id");
+    if (!graph::pose_ok(pose)) return fail(g, LOM_ERR_ARG, "a pose is not finite or its quaternion is zero");
     graph::normalised(pose, g->poses.data() + id * 7);
     g->nodes_dirty = true;
     return LOM_OK;
@@ -418,7 +382,7 @@ int lom_graph_set_fixed(lom_graph *g, int64_t id, int fixed)
 {
     if (!g) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(g->lock);
-    if (id < 0 || id >= (int64_t)g->n()) return gfail(g, LOM_ERR_ARG, "no node with this id");
+    if (id < 0 || id >= (int64_t)g->n()) return fail(g, LOM_ERR_ARG, "no node with this id");
     g->fixed[(size_t)id] = fixed ? 1 : 0;
     g->nodes_dirty = true;
     return LOM_OK;
@@ -429,10 +393,10 @@ int lom_graph_optimize(lom_graph *g, const lom_graph_params *params, lom_graph_s
     if (!g || !params) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(g->lock);
     if (!graph::params_ok(params))
-        return gfail(g, LOM_ERR_ARG, "lambda0, gtol, xtol, pcg_rtol finite and > 0; max_outer, max_pcg > 0");
+        return fail(g, LOM_ERR_ARG, "lambda0, gtol, xtol, pcg_rtol finite and > 0; max_outer, max_pcg > 0");
     int64_t bad = -1;
     if (graph::check_gauge((int64_t)g->n(), g->fixed.data(), (int64_t)g->m(), g->ij.data(), &bad) != LOM_OK)
-        return gfail(g, LOM_ERR_ARG, "gauge: the component of free node " + std::to_string(bad) + " holds no fixed node");
+        return fail(g, LOM_ERR_ARG, ("gauge: the component of free node " + std::to_string(bad) + " holds no fixed node").c_str());
     lom_graph_stats st;
     std::memset(&st, 0, sizeof st);
     st.lambda_final = params->lambda0;
@@ -441,7 +405,7 @@ int lom_graph_optimize(lom_graph *g, const lom_graph_params *params, lom_graph_s
         if (stats) *stats = st;
         return LOM_OK;
     }
-    GR_HIP(g, hipSetDevice(g->device));
+    LOM_HIP(g, hipSetDevice(g->device));
     int rc = sync_device(g);
     if (rc != LOM_OK) return rc;
     const uint32_t n = (uint32_t)g->n(), m = (uint32_t)g->m();
@@ -458,9 +422,9 @@ int lom_graph_optimize(lom_graph *g, const lom_graph_params *params, lom_graph_s
                            g->dev<const double>(G_X), g->dev<double>(G_CAND), g->dev<const int32_t>(G_IJ),
                            g->dev<const double>(G_Z), g->dev<const double>(G_U), g->dev<const double>(G_DELTA),
                            g->dev<double>(G_COSTC));
-        GR_HIP(g, hipGetLastError());
+        LOM_HIP(g, hipGetLastError());
         if ((rc = enqueue_report(g, lambda, 1)) != LOM_OK) return rc;
-        GR_HIP(g, hipStreamSynchronize(g->stream));  // the one wait of this outer iteration
+        LOM_HIP(g, hipStreamSynchronize(g->stream));  // the one wait of this outer iteration
         const GraphReport rep = *g->h_report;
         if (first) st.cost_initial = rep.cost;
         first = false;
@@ -493,8 +457,8 @@ int lom_graph_optimize(lom_graph *g, const lom_graph_params *params, lom_graph_s
             break;
         }
     }
-    GR_HIP(g, hipMemcpyAsync(g->poses.data(), g->buf[G_POSE].p, (size_t)n * 56, hipMemcpyDeviceToHost, g->stream));
-    GR_HIP(g, hipStreamSynchronize(g->stream));
+    LOM_HIP(g, hipMemcpyAsync(g->poses.data(), g->buf[G_POSE].p, (size_t)n * 56, hipMemcpyDeviceToHost, g->stream));
+    LOM_HIP(g, hipStreamSynchronize(g->stream));
     if (stats) *stats = st;
     return LOM_OK;
 }
@@ -512,16 +476,16 @@ int lom_graph_evaluate(lom_graph *g, double lambda, double *e_out, double *w_out
         if (hdiag_out) std::memset(hdiag_out, 0, n * 288);
         return LOM_OK;
     }
-    GR_HIP(g, hipSetDevice(g->device));
+    LOM_HIP(g, hipSetDevice(g->device));
     int rc = sync_device(g);
     if (rc == LOM_OK) rc = evaluate_now(g, lambda);
     if (rc != LOM_OK) return rc;
     if (cost_out) *cost_out = g->h_report->cost;
-    if (e_out) GR_HIP(g, hipMemcpyAsync(e_out, g->buf[G_E].p, m * 48, hipMemcpyDeviceToHost, g->stream));
-    if (w_out) GR_HIP(g, hipMemcpyAsync(w_out, g->buf[G_W].p, m * 8, hipMemcpyDeviceToHost, g->stream));
-    if (g_out) GR_HIP(g, hipMemcpyAsync(g_out, g->buf[G_G].p, n * 48, hipMemcpyDeviceToHost, g->stream));
-    if (hdiag_out) GR_HIP(g, hipMemcpyAsync(hdiag_out, g->buf[G_HD].p, n * 288, hipMemcpyDeviceToHost, g->stream));
-    GR_HIP(g, hipStreamSynchronize(g->stream));
+    if (e_out) LOM_HIP(g, hipMemcpyAsync(e_out, g->buf[G_E].p, m * 48, hipMemcpyDeviceToHost, g->stream));
+    if (w_out) LOM_HIP(g, hipMemcpyAsync(w_out, g->buf[G_W].p, m * 8, hipMemcpyDeviceToHost, g->stream));
+    if (g_out) LOM_HIP(g, hipMemcpyAsync(g_out, g->buf[G_G].p, n * 48, hipMemcpyDeviceToHost, g->stream));
+    if (hdiag_out) LOM_HIP(g, hipMemcpyAsync(hdiag_out, g->buf[G_HD].p, n * 288, hipMemcpyDeviceToHost, g->stream));
+    LOM_HIP(g, hipStreamSynchronize(g->stream));
     return LOM_OK;
 }
 
@@ -535,16 +499,16 @@ int lom_graph_debug_matvec(lom_graph *g, double lambda, const double *p, double 
         std::memset(y_out, 0, n * 48);
         return LOM_OK;
     }
-    GR_HIP(g, hipSetDevice(g->device));
+    LOM_HIP(g, hipSetDevice(g->device));
     int rc = sync_device(g);
     if (rc == LOM_OK) rc = enqueue_linearise(g);
     if (rc == LOM_OK) rc = enqueue_gather(g, lambda);
     if (rc != LOM_OK) return rc;
-    GR_HIP(g, hipMemsetAsync(g->buf[G_SCAL].p, 0, sizeof(GraphScalars), g->stream));  // done = 0: the kernels run
-    GR_HIP(g, hipMemcpyAsync(g->buf[G_P].p, p, n * 48, hipMemcpyHostToDevice, g->stream));
+    LOM_HIP(g, hipMemsetAsync(g->buf[G_SCAL].p, 0, sizeof(GraphScalars), g->stream));  // done = 0: the kernels run
+    LOM_HIP(g, hipMemcpyAsync(g->buf[G_P].p, p, n * 48, hipMemcpyHostToDevice, g->stream));
     if ((rc = enqueue_matvec(g, lambda)) != LOM_OK) return rc;
-    GR_HIP(g, hipMemcpyAsync(y_out, g->buf[G_Y].p, n * 48, hipMemcpyDeviceToHost, g->stream));
-    GR_HIP(g, hipStreamSynchronize(g->stream));
+    LOM_HIP(g, hipMemcpyAsync(y_out, g->buf[G_Y].p, n * 48, hipMemcpyDeviceToHost, g->stream));
+    LOM_HIP(g, hipStreamSynchronize(g->stream));
     return LOM_OK;
 }
 
@@ -552,14 +516,14 @@ int lom_graph_edge_chi2(lom_graph *g, int64_t first, int64_t n, double *out)
 {
     if (!g || first < 0 || n < 0 || (n && !out)) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> lk(g->lock);
-    if (first > (int64_t)g->m() || n > (int64_t)g->m() - first) return gfail(g, LOM_ERR_ARG, "no edge with this id");
+    if (first > (int64_t)g->m() || n > (int64_t)g->m() - first) return fail(g, LOM_ERR_ARG, "no edge with this id");
     if (n == 0) return LOM_OK;
-    GR_HIP(g, hipSetDevice(g->device));
+    LOM_HIP(g, hipSetDevice(g->device));
     int rc = sync_device(g);
     if (rc == LOM_OK) rc = enqueue_linearise(g);
     if (rc != LOM_OK) return rc;
-    GR_HIP(g, hipMemcpyAsync(out, g->dev<double>(G_S) + first, (size_t)n * 8, hipMemcpyDeviceToHost, g->stream));
-    GR_HIP(g, hipStreamSynchronize(g->stream));
+    LOM_HIP(g, hipMemcpyAsync(out, g->dev<double>(G_S) + first, (size_t)n * 8, hipMemcpyDeviceToHost, g->stream));
+    LOM_HIP(g, hipStreamSynchronize(g->stream));
     return LOM_OK;
 }
 

@@ -1,9 +1,10 @@
-// What every handle owns besides a map, and nothing that launches a kernel: error text, grow-only device buffers and
-// pinned host blocks, the buffer groups of the batched align and the quality reports and their release, scan uploads,
-// device queries, stream and pinned blocks (handle_setup), scan contexts (lom_scan_*: creation, destruction and the
-// forwarders to the lom_match_* entries of match.hip, align.hip, align_batch.hip and quality_report.hip), lom_map_create / destroy and the run-time switches.  What these
-// need from the map side -- the first table, settling a pending insert, freeing slabs -- are lom:: functions of
-// voxel_map.hip (lom_internal.hpp).
+// The core every device handle shares (device_handle.hpp): the device checks of a create, allocation into DeviceBuf /
+// PinnedBuf and their grow-only ensure / ensure_pinned.  Then what the map handle owns besides a map, and nothing that
+// launches a kernel: scan uploads, device queries, stream and pinned blocks (handle_setup), scan contexts (lom_scan_*:
+// creation, destruction and the forwarders to the lom_match_* entries of match.hip, align.hip, align_batch.hip and
+// quality_report.hip), lom_map_create / destroy and the run-time switches.  What these need from the map side -- the
+// first table, settling a pending insert, freeing table and slabs -- are lom:: functions of voxel_map.hip
+// (lom_internal.hpp).
 #include <algorithm>
 #include <cctype>
 #include <cstdio>
@@ -16,88 +17,78 @@
 namespace lom {
 
 // ---------------------------------------------------------------------------
-// error handling / buffers
+// the handle core (device_handle.hpp)
 // ---------------------------------------------------------------------------
 static thread_local std::string g_create_error;
+std::string &map_create_error() { return g_create_error; }
 
-int set_error(lom_map *m, int code, const char *what, hipError_t e)
+int check_device(int device, std::string &slot, bool name_device)
 {
-    std::string s = what ? what : "";
-    if (e != hipSuccess) {
-        s += ": ";
-        s += hipGetErrorString(e);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return create_fail(slot, LOM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
     }
-    if (m)
-        m->last_error = s;
-    else
-        g_create_error = s;
-    return code;
-}
-
-int ensure(lom_map *m, DeviceBuf &b, size_t bytes)
-{
-    if (bytes <= b.bytes) return LOM_OK;
-    size_t nb = std::max(bytes, b.bytes + b.bytes / 2);
-    nb = (nb + 255) & ~size_t(255);
-    if (b.p) {
-        LOM_HIP(m, hipStreamSynchronize(m->stream));
-        LOM_HIP(m, hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
+    if (device < 0 || device >= ndev) return create_fail(slot, LOM_ERR_ARG, "device index out of range");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess)
+        return create_fail(slot, LOM_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        std::string s = "kernels are built for gfx950 only";
+        if (name_device) s = std::string("device is ") + prop.gcnArchName + ", " + s;
+        return create_fail(slot, LOM_ERR_NO_DEVICE, s.c_str());
     }
-    hipError_t e = hipMalloc(&b.p, nb);
-    if (e != hipSuccess) {
-        b.p = nullptr;
-        return set_error(m, LOM_ERR_OOM, "hipMalloc", e);
-    }
-    b.bytes = nb;
     return LOM_OK;
 }
 
-int ensure_pinned(lom_map *m, PinnedBuf &b, size_t need, size_t grow_to, unsigned flags, const char *what, bool *fresh)
+hipError_t alloc(DeviceBuf &b, size_t bytes)
+{
+    const hipError_t e = hipMalloc(&b.p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        return e;
+    }
+    b.bytes = bytes;
+    return hipSuccess;
+}
+
+hipError_t alloc(PinnedBuf &b, size_t bytes, unsigned flags)
+{
+    hipError_t e = hipHostMalloc(&b.h, bytes, flags);
+    if (e != hipSuccess) b.h = nullptr;
+    if (e == hipSuccess && (flags & hipHostMallocMapped)) e = hipHostGetDevicePointer(&b.d, b.h, 0);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        release(b);
+        return e;
+    }
+    b.bytes = bytes;
+    return hipSuccess;
+}
+
+int ensure(DeviceHandle *h, DeviceBuf &b, size_t bytes)
+{
+    if (bytes <= b.bytes) return LOM_OK;
+    const size_t nb = grown_bytes(b.bytes, bytes);
+    if (b.p) {
+        LOM_HIP(h, hipStreamSynchronize(h->stream));
+        release(b);
+    }
+    const hipError_t e = alloc(b, nb);
+    return e == hipSuccess ? LOM_OK : fail(h, LOM_ERR_OOM, "hipMalloc", e);
+}
+
+int ensure_pinned(DeviceHandle *h, PinnedBuf &b, size_t need, size_t grow_to, unsigned flags, const char *what, bool *fresh)
 {
     if (fresh) *fresh = false;
     if (b.h && need <= b.bytes) return LOM_OK;
-    LOM_HIP(m, hipStreamSynchronize(m->stream));
-    if (b.h) LOM_HIP(m, hipHostFree(b.h));
-    b = PinnedBuf{};
-    hipError_t e = hipHostMalloc(&b.h, grow_to, flags);
-    if (e == hipSuccess && (flags & hipHostMallocMapped)) e = hipHostGetDevicePointer(&b.d, b.h, 0);
-    if (e != hipSuccess) {
-        if (b.h) (void)hipHostFree(b.h);
-        b = PinnedBuf{};
-        return set_error(m, LOM_ERR_OOM, what, e);
-    }
-    b.bytes = grow_to;
+    LOM_HIP(h, hipStreamSynchronize(h->stream));
+    release(b);
+    const hipError_t e = alloc(b, grow_to, flags);
+    if (e != hipSuccess) return fail(h, LOM_ERR_OOM, what, e);
     if (fresh) *fresh = true;
     return LOM_OK;
-}
-
-void release(DeviceBuf &b)
-{
-    if (b.p) (void)hipFree(b.p);
-    b = DeviceBuf{};
-}
-void release(PinnedBuf &b)
-{
-    if (b.h) (void)hipHostFree(b.h);
-    b = PinnedBuf{};
-}
-void release(BatchAlignBufs &b)
-{
-    for (DeviceBuf *d : {&b.dev, &b.rec, &b.cnt, &b.xrec, &b.src}) release(*d);
-    release(b.stage);
-    release(b.reports);
-}
-void release(QualityBufs &b)
-{
-    for (DeviceBuf *d : {&b.src, &b.idx, &b.rec, &b.cnt, &b.part, &b.res}) release(*d);
-    release(b.sums);
-}
-void release(QualityBatchBufs &b)
-{
-    for (DeviceBuf *d : {&b.src, &b.rec, &b.cnt, &b.part, &b.dev, &b.sums}) release(*d);
-    release(b.stage);
 }
 
 static inline size_t scan_bytes(size_t n, size_t stride) { return n ? (n - 1) * stride + 12 : 0; }
@@ -108,7 +99,7 @@ int upload_scan(lom_map *m, DeviceBuf &buf, const void *src, size_t n, size_t st
     const int rc = ensure(m, buf, std::max<size_t>(bytes, 16));
     if (rc != LOM_OK) return rc;
     if (bytes) LOM_HIP(m, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, m->stream));
-    *d_src = (const char *)buf.p;
+    *d_src = buf.as<const char>();
     return LOM_OK;
 }
 
@@ -139,8 +130,8 @@ int upload_distinct(lom_map *m, DeviceBuf &buf, const HostCloud *clouds, int cou
     const int rc = ensure(m, buf, std::max<size_t>(total, 256));
     if (rc != LOM_OK) return rc;
     for (const Distinct &d : distinct)
-        LOM_HIP(m, hipMemcpyAsync((char *)buf.p + d.off, d.c.p, scan_bytes(d.c.n, d.c.stride), hipMemcpyHostToDevice, m->stream));
-    for (int i = 0; i < count; i++) d_src[i] = (const char *)buf.p + off[i];
+        LOM_HIP(m, hipMemcpyAsync(buf.as<char>() + d.off, d.c.p, scan_bytes(d.c.n, d.c.stride), hipMemcpyHostToDevice, m->stream));
+    for (int i = 0; i < count; i++) d_src[i] = buf.as<const char>() + off[i];
     return LOM_OK;
 }
 
@@ -185,7 +176,7 @@ int lom_device_local_cpus(int device, char *out, size_t cap)
     return LOM_OK;
 }
 
-const char *lom_last_error(const lom_map *m) { return m ? m->last_error.c_str() : g_create_error.c_str(); }
+const char *lom_last_error(const lom_map *m) { return m ? m->error.c_str() : g_create_error.c_str(); }
 
 // what every handle owns besides a map: a stream and the pinned blocks the align talks to the host through
 // (part >= 0: the stream runs on partition `part` of `nparts` equal slices of the device's compute units)
@@ -216,20 +207,20 @@ static hipError_t create_stream(lom_map *m, int part, int nparts)
 
 static int handle_setup(lom_map *m, int part = -1, int nparts = 1)
 {
+    constexpr unsigned kMapped = hipHostMallocMapped | hipHostMallocCoherent;
     hipError_t e;
-    if ((e = hipSetDevice(m->device)) != hipSuccess ||
-        (e = create_stream(m, part, nparts)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&m->h_results, 1024 * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&m->h_flags, 64 * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess ||
-        (e = hipHostMalloc((void **)&m->h_mail, 64 * 32 * sizeof(double), hipHostMallocMapped | hipHostMallocCoherent)) !=
-            hipSuccess ||
-        (e = hipHostGetDevicePointer((void **)&m->d_mail, m->h_mail, 0)) != hipSuccess ||
-        (e = hipHostMalloc(&m->h_cmd, 256, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-        (e = hipHostGetDevicePointer(&m->d_cmd, m->h_cmd, 0)) != hipSuccess ||
-        (e = hipHostMalloc(&m->h_report, 1024, hipHostMallocMapped | hipHostMallocCoherent)) != hipSuccess ||
-        (e = hipHostGetDevicePointer(&m->d_report, m->h_report, 0)) != hipSuccess)
-        return set_error(nullptr, LOM_ERR_HIP, "handle setup", e);
+    if ((e = hipSetDevice(m->device)) != hipSuccess || (e = create_stream(m, part, nparts)) != hipSuccess ||
+        (e = alloc(m->pin_results, 1024 * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
+        (e = alloc(m->pin_flags, 64 * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess ||
+        (e = alloc(m->pin_mail, 64 * 32 * sizeof(double), kMapped)) != hipSuccess ||
+        (e = alloc(m->pin_cmd, 256, kMapped)) != hipSuccess || (e = alloc(m->pin_report, 1024, kMapped)) != hipSuccess)
+        return create_fail(g_create_error, LOM_ERR_HIP, "handle setup", e);
     m->stream = m->own_stream;
+    m->h_results = m->pin_results.as<double>();
+    m->h_flags = m->pin_flags.as<uint32_t>();
+    m->h_mail = m->pin_mail.as<double>(), m->d_mail = static_cast<double *>(m->pin_mail.d);
+    m->h_cmd = m->pin_cmd.h, m->d_cmd = m->pin_cmd.d;
+    m->h_report = m->pin_report.h, m->d_report = m->pin_report.d;
     std::memset(m->h_mail, 0, 64 * 32 * sizeof(double));
     std::memset(m->h_cmd, 0, 256);
     std::memset(m->h_report, 0, 1024);
@@ -247,14 +238,14 @@ int lom_scan_create_on_partition(lom_map *map, int part, int nparts, lom_scan **
     if (!map || !out) return LOM_ERR_ARG;
     *out = nullptr;
     if (part >= 0 && (nparts < 1 || nparts > 8 || part >= nparts))
-        return set_error(map, LOM_ERR_ARG, "partition index / count: 0 <= part < nparts <= 8");
-    if (map->parent) return set_error(map, LOM_ERR_ARG, "a scan context cannot be the keyframe of another");
+        return fail(map, LOM_ERR_ARG, "partition index / count: 0 <= part < nparts <= 8");
+    if (map->parent) return fail(map, LOM_ERR_ARG, "a scan context cannot be the keyframe of another");
     LOM_HIP(map, hipSetDevice(map->device));
     // settles a pending insert (nothing mutates the keyframe while contexts read it)
     const int rc = settle_map(map);
     if (rc != LOM_OK) return rc;
     lom_map *c = new (std::nothrow) lom_map();
-    if (!c) return set_error(map, LOM_ERR_OOM, "host allocation");
+    if (!c) return fail(map, LOM_ERR_OOM, "host allocation");
     c->device = map->device;
     c->parent = map;
     c->opt_host_lm = map->opt_host_lm;
@@ -265,7 +256,7 @@ int lom_scan_create_on_partition(lom_map *map, int part, int nparts, lom_scan **
     c->opt_replay_fold = map->opt_replay_fold;
     c->patience_ticks = map->patience_ticks;
     if (handle_setup(c, part, nparts) != LOM_OK) {
-        map->last_error = g_create_error;
+        map->error = g_create_error;
         lom_map_destroy(c);
         return LOM_ERR_HIP;
     }
@@ -276,7 +267,7 @@ int lom_scan_create_on_partition(lom_map *map, int part, int nparts, lom_scan **
 static lom_map *as_map(lom_scan *s) { return reinterpret_cast<lom_map *>(s); }
 
 void lom_scan_destroy(lom_scan *s) { lom_map_destroy(as_map(s)); }
-const char *lom_scan_last_error(const lom_scan *s) { return s ? reinterpret_cast<const lom_map *>(s)->last_error.c_str() : ""; }
+const char *lom_scan_last_error(const lom_scan *s) { return s ? reinterpret_cast<const lom_map *>(s)->error.c_str() : ""; }
 int lom_scan_set_option(lom_scan *s, int option, int64_t value) { return lom_map_set_option(as_map(s), option, value); }
 int lom_scan_set_stream(lom_scan *s, void *hip_stream) { return lom_map_set_stream(as_map(s), hip_stream); }
 void *lom_scan_get_stream(lom_scan *s) { return lom_map_get_stream(as_map(s)); }
@@ -338,22 +329,10 @@ int lom_map_create(float voxel_size, size_t max_points, size_t capacity_hint, in
     if (!out) return LOM_ERR_ARG;
     *out = nullptr;
     if (!(voxel_size > 0.f) || max_points == 0 || max_points > 65535)
-        return set_error(nullptr, LOM_ERR_ARG, "voxel_size must be > 0 and 1 <= max_points <= 65535");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return set_error(nullptr, LOM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    }
-    if (device < 0 || device >= ndev) return set_error(nullptr, LOM_ERR_ARG, "device index out of range");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess)
-        return set_error(nullptr, LOM_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        std::string s = std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only";
-        return set_error(nullptr, LOM_ERR_NO_DEVICE, s.c_str());
-    }
+        return create_fail(g_create_error, LOM_ERR_ARG, "voxel_size must be > 0 and 1 <= max_points <= 65535");
+    if (const int rc = check_device(device, g_create_error, true); rc != LOM_OK) return rc;
     lom_map *m = new (std::nothrow) lom_map();
-    if (!m) return set_error(nullptr, LOM_ERR_OOM, "host allocation");
+    if (!m) return create_fail(g_create_error, LOM_ERR_OOM, "host allocation");
     m->device = device;
     m->voxel_size = voxel_size;
     m->K = (uint32_t)max_points;
@@ -375,7 +354,7 @@ int lom_map_create(float voxel_size, size_t max_points, size_t capacity_hint, in
     }
     const int rc = map_init(m, capacity_hint);
     if (rc != LOM_OK) {
-        g_create_error = m->last_error.empty() ? "map setup failed" : m->last_error;
+        g_create_error = m->error.empty() ? "map setup failed" : m->error;
         lom_map_destroy(m);
         return rc;
     }
@@ -395,30 +374,13 @@ void lom_map_destroy(lom_map *m)
     }
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     if (m->comm || m->host_comm) lom_comm_finalize(m);
-    if (m->d_table) (void)hipFree(m->d_table);
-    slabs_free(m->slabs);
-    slabs_free(m->alt);
-    for (auto &b : m->scr)
-        if (b.p) (void)hipFree(b.p);
-    for (DeviceBuf *b : {&m->scan_src, &m->scan_idx, &m->scan_on, &m->scan_stats, &m->partials, &m->results, &m->gather,
-                         &m->align_state, &m->xrec, &m->dbg_trace, &m->dbg_stamps})
-        release(*b);
-    release(m->batch);
-    release(m->qual);
-    release(m->qualb);
-    release(m->h_stage);
-    if (m->h_results) (void)hipHostFree(m->h_results);
-    if (m->h_flags) (void)hipHostFree(m->h_flags);
-    if (m->h_mail) (void)hipHostFree(m->h_mail);
-    if (m->stage_ev) (void)hipEventDestroy(m->stage_ev);
-    if (m->parent_ev) (void)hipEventDestroy(m->parent_ev);
-    if (m->multi_ev) (void)hipEventDestroy(m->multi_ev);
-    if (m->h_cmd) (void)hipHostFree(m->h_cmd);
-    if (m->h_report) (void)hipHostFree(m->h_report);
+    map_free(m);
+    for (hipEvent_t e : {m->stage_ev, m->parent_ev, m->multi_ev})
+        if (e) (void)hipEventDestroy(e);
     for (auto &e : m->prof_events)
         if (e) (void)hipEventDestroy(e);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
-    delete m;
+    delete m;  // the buffers go with it
 }
 
 int lom_map_set_stream(lom_map *m, void *hip_stream)
@@ -474,7 +436,7 @@ int lom_map_set_option(lom_map *m, int option, int64_t value)
         if (value < 0 || value > (1 << 20)) return LOM_ERR_ARG;
         m->qualb.test_round_max = (int)value;
         return LOM_OK;
-    default: return set_error(m, LOM_ERR_ARG, "unknown option");
+    default: return fail(m, LOM_ERR_ARG, "unknown option");
     }
 }
 

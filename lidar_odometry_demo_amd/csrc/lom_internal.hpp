@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/lidar_odometry_amd.h"
+#include "device_handle.hpp"
 
 namespace lom {
 
@@ -123,17 +124,8 @@ struct AlignReport {
 };
 
 // ---- host-side handle ---------------------------------------------------------
-struct DeviceBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
-
-// its pinned host counterpart (ensure_pinned): grow-only too, with the device view of a mapped block
-struct PinnedBuf {
-    void *h = nullptr;
-    void *d = nullptr;  // hipHostMallocMapped blocks only
-    size_t bytes = 0;
-};
+// Device, stream, error text, LOM_HIP, the owning DeviceBuf / PinnedBuf and their grow-only ensure / ensure_pinned are
+// the same for every handle: device_handle.hpp.  Below is what the map handle (and a scan context, which is one) adds.
 
 // Buffers of the batched align (lom_match_align_batch / _multi): per-problem solve states and descriptors, records,
 // k_match counters, exchange sets per round slot, staged host scans -- and per-problem reports in pinned host memory;
@@ -228,8 +220,7 @@ enum {
 
 }  // namespace lom
 
-struct lom_map {
-    int device = 0;
+struct lom_map : lom::DeviceHandle {
     // a scan context (lom_scan_create): no table or slabs of its own, its kernels read the parent's
     lom_map *parent = nullptr;
     // map side: calls that changed the map (their kernels run on THIS handle's stream); context side: the count its
@@ -242,8 +233,7 @@ struct lom_map {
     // stream, pinned words and scratch: whoever does it (the map's own caller, a context's first call after a change,
     // lom_scan_create) holds this lock, so that several threads arriving together settle once.
     std::mutex settle_mutex;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    hipStream_t own_stream = nullptr;  // `stream` is this one unless lom_map_set_stream gave another
     // compute units this handle's own stream runs on: 0 = all of the device; a scan context on a partition
     // (lom_scan_create_on_partition) owns a stream with a CU mask, and its grids are sized for that many CUs
     uint32_t partition_cus = 0;
@@ -285,7 +275,8 @@ struct lom_map {
     // per-scan buffers of align/find_pairs
     lom::DeviceBuf scan_src, scan_idx, scan_on, scan_stats, partials, results;
 
-    // pinned host result buffer
+    // the pinned blocks of handle_setup (handle.hip) and the typed views of them that the align path uses
+    lom::PinnedBuf pin_results, pin_flags, pin_mail, pin_cmd, pin_report;
     double *h_results = nullptr;  // 1024 doubles (rank-ordered gather of up to 32 ranks)
     uint32_t *h_flags = nullptr;  // 64 words
     // mailbox: every k_eval workgroup stores one 32-double record (sums, counters,
@@ -320,8 +311,7 @@ struct lom_map {
     uint32_t cleanups_taken = 0;  // radius cleanups that used such a scan (lom_map_debug_counter)
     unsigned long long report_seq = 0, lm_seq = 0, lm_launches = 0;
     int last_replayed = 0;  // outer iterations of the last align on this handle that the replay fold accounted for (lom_debug_replayed_iterations)
-    // the batched align, the quality report and the batched quality report keep buffers of their own (handle.hip frees each
-    // group with its release function)
+    // the batched align, the quality report and the batched quality report keep buffers of their own
     lom::BatchAlignBufs batch;
     lom::QualityBufs qual;
     lom::QualityBatchBufs qualb;
@@ -363,23 +353,11 @@ struct lom_map {
     uint32_t test_bulk_part_max = 0;  // LOM_OPT_TEST_BULK_PARTITION_MAX: points a partition of the bulk insert may hold (0: the LDS limit)
     int test_grid_give_up = -1;     // LOM_OPT_TEST_GRID_GIVE_UP: first workgroup that gives up in the next in-kernel scan
     int test_give_up_outer = -1;    // LOM_OPT_TEST_GIVE_UP_AT_OUTER: k_lm of that outer iteration of the next align gives up
-
-    std::string last_error;
 };
 
 namespace lom {
 
-int set_error(lom_map *m, int code, const char *what, hipError_t e = hipSuccess);  // handle.hip
-int ensure(lom_map *m, DeviceBuf &b, size_t bytes);  // handle.hip: grow-only device buffer
-// handle.hip: grow-only pinned host block.  One of at least `need` bytes is left alone; else the stream is synchronised
-// (what is enqueued may still read the old block), the old block freed and `grow_to` (>= need) bytes allocated with
-// `flags`, mapped into the device's address space where the flags ask for it.  *fresh: the block is new, its contents undefined.
-int ensure_pinned(lom_map *m, PinnedBuf &b, size_t need, size_t grow_to, unsigned flags, const char *what, bool *fresh = nullptr);
-void release(DeviceBuf &b);  // handle.hip: these free, at lom_map_destroy
-void release(PinnedBuf &b);
-void release(BatchAlignBufs &b);
-void release(QualityBufs &b);
-void release(QualityBatchBufs &b);
+std::string &map_create_error();  // handle.hip: the map family's create slot (lom_last_error(NULL)), for comm.cpp
 // handle.hip: a host scan into `buf` (grown as needed), one asynchronous copy on the handle's stream
 int upload_scan(lom_map *m, DeviceBuf &buf, const void *src, size_t n, size_t stride, const char **d_src);
 // handle.hip: the host clouds of a problem list into `buf`, every distinct (pointer, n, stride) once, at 256-byte aligned
@@ -393,14 +371,8 @@ MapView view_of(const lom_map *m);
 int resolve_pending(lom_map *m);  // voxel_map.hip: redo the last single-pass insert if its in-kernel scan gave up
 int map_init(lom_map *m, size_t capacity_hint);  // voxel_map.hip: status words and the first table of a new map (lom_map_create)
 int settle_map(lom_map *map);  // voxel_map.hip: settle a pending insert and the voxel count, under the map's settle lock
-void slabs_free(Slabs &s);     // voxel_map.hip
+void map_free(lom_map *m);     // voxel_map.hip: the table and both slab sets (lom_map_destroy)
 void cleanup_scan_behind_align(lom_map *m);  // voxel_map.hip: see lom_map_radius_cleanup_after_align
-
-#define LOM_HIP(m, expr)                                                        \
-    do {                                                                        \
-        hipError_t _e = (expr);                                                 \
-        if (_e != hipSuccess) return lom::set_error((m), LOM_ERR_HIP, #expr, _e); \
-    } while (0)
 
 // RCCL (comm.cpp), loaded lazily with dlopen
 int comm_allgather_sums(lom_map *m, const double *d_send, double *d_recv, int count);

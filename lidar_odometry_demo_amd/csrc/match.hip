@@ -101,8 +101,8 @@ int scan_buffers(lom_map *m, uint32_t n, bool want_stats)
     return LOM_OK;
 }
 
-static uint32_t *d_block_counters(lom_map *m) { return (uint32_t *)((char *)m->results.p + 1024); }
-static double *d_sums(lom_map *m) { return (double *)m->results.p; }
+static uint32_t *d_block_counters(lom_map *m) { return (uint32_t *)(m->results.as<char>() + 1024); }
+static double *d_sums(lom_map *m) { return m->results.as<double>(); }
 
 // The k_match instantiation of a launch (every instantiation has the same signature).
 // <lanes per query, candidates per lane and trip, min waves per SIMD>: measured on C2 / C3
@@ -157,7 +157,7 @@ static void launch_k_match_stamps(lom_map *m, uint32_t blocks, const char *d_src
                                   const PoseArgs &P, unsigned long long *d_stamps)
 {
     hipLaunchKernelGGL((k_match<kMatchG, kMatchRows, kMatchMinWaves, true>), dim3(blocks), dim3(kMatchThreads), 0, m->stream,
-                       view_of(m), d_src, stride, n, P, (int32_t *)m->scan_idx.p, (MatchRec *)m->scan_on.p, (QStat *)nullptr,
+                       view_of(m), d_src, stride, n, P, m->scan_idx.as<int32_t>(), m->scan_on.as<MatchRec>(), (QStat *)nullptr,
                        d_block_counters(m), d_stamps);
 }
 
@@ -214,13 +214,13 @@ int launch_match(ScanCtx &c, const float t[3], const float q[4], float max_sq, b
             c.prof_used++;
             LOM_HIP(m, hipEventRecord(e0, m->stream));
         }
-        QStat *st = (stats && !chained) ? (QStat *)m->scan_stats.p : nullptr;
+        QStat *st = (stats && !chained) ? m->scan_stats.as<QStat>() : nullptr;
         // (a chained launch always follows a search of the same scan: launch_pair's first pair is not chained)
         const bool prev = (chained || c.have_prev) && !m->opt_no_temporal;
         const bool count = count_mode < 0 ? m->opt_count : count_mode != 0;
-        const AlignState *as = chained ? (const AlignState *)m->align_state.p : nullptr;
-        launch_k_match(m, prev, count, c.match_blocks, c.d_src, c.stride, c.n, P, (int32_t *)m->scan_idx.p,
-                       (MatchRec *)m->scan_on.p, st, d_block_counters(m), as);
+        const AlignState *as = chained ? m->align_state.as<const AlignState>() : nullptr;
+        launch_k_match(m, prev, count, c.match_blocks, c.d_src, c.stride, c.n, P, m->scan_idx.as<int32_t>(),
+                       m->scan_on.as<MatchRec>(), st, d_block_counters(m), as);
         LOM_HIP(m, hipGetLastError());
         c.counted = count;
         c.have_prev = true;
@@ -272,7 +272,7 @@ static int collect_records(lom_map *m, uint32_t nb, unsigned long long seq, doub
                     if (*flag == seq) break;
                     return 1;
                 } else if (e != hipErrorNotReady) {
-                    return set_error(m, LOM_ERR_HIP, "stream failed while waiting for an evaluation", e);
+                    return fail(m, LOM_ERR_HIP, "stream failed while waiting for an evaluation", e);
                 }
             }
         }
@@ -299,17 +299,17 @@ static int launch_eval(ScanCtx &c, const double q[4], const double t[3], bool fr
         const unsigned long long seq = ++m->mail_seq;
         if (nb) {
             hipLaunchKernelGGL(k_eval, dim3(nb), dim3(kEvalThreads), kEvalLdsBytes, m->stream,
-                               (const MatchRec *)m->scan_on.p, c.n, E, (const uint32_t *)d_block_counters(m),
-                               fresh_match ? c.match_blocks : 0u, (double *)m->partials.p, seq);
+                               m->scan_on.as<const MatchRec>(), c.n, E, (const uint32_t *)d_block_counters(m),
+                               fresh_match ? c.match_blocks : 0u, m->partials.as<double>(), seq);
         }
-        hipLaunchKernelGGL(k_sum_records, dim3(1), dim3(64), 0, m->stream, (const double *)m->partials.p, nb, c.n,
+        hipLaunchKernelGGL(k_sum_records, dim3(1), dim3(64), 0, m->stream, m->partials.as<const double>(), nb, c.n,
                            d_sums(m));
         LOM_HIP(m, hipGetLastError());
         c.launch_s += now_s() - t_launch;
         const double t_wait = now_s();
         rc = ensure(m, m->gather, (size_t)m->nranks * LOM_NSUMS * 8);
         if (rc != LOM_OK) return rc;
-        rc = comm_allgather_sums(m, d_sums(m), (double *)m->gather.p, LOM_NSUMS);
+        rc = comm_allgather_sums(m, d_sums(m), m->gather.as<double>(), LOM_NSUMS);
         if (rc != LOM_OK) return rc;
         LOM_HIP(m, hipMemcpyAsync(m->h_results, m->gather.p, (size_t)m->nranks * LOM_NSUMS * 8,
                                   hipMemcpyDeviceToHost, m->stream));
@@ -329,7 +329,7 @@ static int launch_eval(ScanCtx &c, const double q[4], const double t[3], bool fr
                 EvalCmd *cmd = reinterpret_cast<EvalCmd *>(m->h_cmd);
                 seq = ++m->mail_seq;
                 hipLaunchKernelGGL(k_eval_server, dim3(nb), dim3(kEvalThreads), kEvalLdsBytes, m->stream,
-                                   (const MatchRec *)m->scan_on.p, c.n, E, (const uint32_t *)d_block_counters(m),
+                                   m->scan_on.as<const MatchRec>(), c.n, E, (const uint32_t *)d_block_counters(m),
                                    fresh_match ? c.match_blocks : 0u, m->d_mail, seq,
                                    reinterpret_cast<const EvalCmd *>(m->d_cmd), (unsigned long long)cmd->seq,
                                    m->patience_ticks);
@@ -355,7 +355,7 @@ static int launch_eval(ScanCtx &c, const double q[4], const double t[3], bool fr
             if (rc < 0) return rc;
             m->server_alive = false;  // the server timed out and left (host was away > 50 ms): start another
             fresh_match = false;      // counters were already folded, or are folded again below
-            if (attempt >= 3) return set_error(m, LOM_ERR_HIP, "evaluation server did not answer");
+            if (attempt >= 3) return fail(m, LOM_ERR_HIP, "evaluation server did not answer");
         }
         out[31] = (double)c.n;
     }
@@ -470,9 +470,9 @@ void launch_k_lm(lom_map *m, LmShape shape, uint32_t blocks, uint32_t n, const L
     P2pArgs px = p2p_args(m);
     px.set_base = p2p_set_base;
     px.epoch = p2p_epoch;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kLmGeometry[shape].threads), 0, m->stream, (const MatchRec *)m->scan_on.p, n,
-                       (AlignState *)m->align_state.p, init, first_outer ? 1 : 0, (const uint32_t *)d_block_counters(m),
-                       match_blocks, (XWord *)m->xrec.p, m->lm_seq, reinterpret_cast<AlignReport *>(m->d_report), report_seq,
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kLmGeometry[shape].threads), 0, m->stream, m->scan_on.as<const MatchRec>(), n,
+                       m->align_state.as<AlignState>(), init, first_outer ? 1 : 0, (const uint32_t *)d_block_counters(m),
+                       match_blocks, m->xrec.as<XWord>(), m->lm_seq, reinterpret_cast<AlignReport *>(m->d_report), report_seq,
                        fold_report_seq, m->patience_ticks, dbg_stamps, px, dbg_trace, give_up ? 1 : 0,
                        (const BatchProblem *)nullptr);
 }
@@ -577,11 +577,11 @@ int64_t lom_debug_find_pairs_after(lom_map *m, const float *src, size_t n, size_
 int lom_comm_attach_p2p(lom_map *m, lom_host_comm *hc)
 {
     if (!m || !hc) return LOM_ERR_ARG;
-    if (m->comm) return set_error(m, LOM_ERR_STATE, "an RCCL communicator is already attached");
+    if (m->comm) return fail(m, LOM_ERR_STATE, "an RCCL communicator is already attached");
     LOM_HIP(m, hipSetDevice(m->device));
     int rank = 0, nranks = 1;
     if (host_comm_rank(hc, &rank, &nranks) != LOM_OK) return LOM_ERR_ARG;
-    if (nranks > kP2pMaxRanks) return set_error(m, LOM_ERR_ARG, "device-to-device exchange: at most 8 ranks");
+    if (nranks > kP2pMaxRanks) return fail(m, LOM_ERR_ARG, "device-to-device exchange: at most 8 ranks");
     p2p_detach(m);
     server_stop(m);
     // From here on every step is collective: a rank that fails locally still takes part in the
@@ -612,7 +612,7 @@ int lom_comm_attach_p2p(lom_map *m, lom_host_comm *hc)
     mine.ok = ok;
     if (lom_host_comm_allgather(hc, &mine, sizeof mine, all) != LOM_OK) {
         p2p_detach(m);
-        return set_error(m, LOM_ERR_COMM, "device-to-device exchange: handle exchange failed");
+        return fail(m, LOM_ERR_COMM, "device-to-device exchange: handle exchange failed");
     }
     for (int r = 0; r < nranks; r++) ok = ok && all[r].ok;
     if (ok) {
@@ -643,9 +643,9 @@ int lom_comm_attach_p2p(lom_map *m, lom_host_comm *hc)
         const P2pArgs A = p2p_args(m);
         m->p2p = false;
         hipLaunchKernelGGL(k_p2p_selftest, dim3(1), dim3(64), 0, m->stream, A, m->lm_seq, 200,
-                           m->patience_ticks, (uint32_t *)m->results.p);
+                           m->patience_ticks, m->results.as<uint32_t>());
         if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(res, (uint32_t *)m->results.p, 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+            hipMemcpyAsync(res, m->results.as<uint32_t>(), 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
             hipStreamSynchronize(m->stream) != hipSuccess)
             ok = 0;
         else if (res[0] != 0 || res[1] != 0)
@@ -658,7 +658,7 @@ int lom_comm_attach_p2p(lom_map *m, lom_host_comm *hc)
         p2p_detach(m);
         m->rank = 0;
         m->nranks = 1;
-        return set_error(m, LOM_ERR_COMM, "device-to-device exchange failed its self-test on some rank");
+        return fail(m, LOM_ERR_COMM, "device-to-device exchange failed its self-test on some rank");
     }
     m->host_comm = hc;  // rank / nranks bookkeeping as with the host exchange; the caller keeps ownership
     m->p2p = true;
@@ -739,7 +739,7 @@ int lom_profile_match(lom_map *m, const float *d_src, size_t n, size_t stride, c
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     m->profiling = was;
-    if (rc != LOM_OK) return set_error(m, rc, "lom_profile_match failed");
+    if (rc != LOM_OK) return fail(m, rc, "lom_profile_match failed");
     *avg_us_out = (double)ms * 1e3 / reps;
     if (bytes_out) *bytes_out = 444.0 * sums[31] + 12.0 * sums[29] + 12.0 * sums[28];
     if (requested_bytes_out) {
@@ -760,9 +760,9 @@ int lom_debug_eval_sums(lom_map *m, const float *src, size_t n, size_t stride, c
                         const float pose_q[4], const double q[4], const double t[3], double out[LOM_NSUMS])
 {
     if (!m || (n && !src) || !pose_t || !pose_q || !q || !t || !out || !scan_args_ok(n, stride)) return LOM_ERR_ARG;
-    if (m->comm || m->host_comm) return set_error(m, LOM_ERR_STATE, "not with an attached exchange");
+    if (m->comm || m->host_comm) return fail(m, LOM_ERR_STATE, "not with an attached exchange");
     LOM_HIP(m, hipSetDevice(m->device));
-    m->last_error.clear();
+    m->error.clear();
     const char *d_src = nullptr;
     int rc = upload_scan(m, m->scan_src, src, n, stride, &d_src);
     if (rc != LOM_OK) return rc;
@@ -815,8 +815,9 @@ int lom_debug_lm_policy(int form, int n_solves, const int *n_evals, const double
                  o_rec = o_act + slots * 4, o_ev = o_rec + ns * 4, total = o_ev + ns * 4;
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return LOM_ERR_HIP;  // forms 1-3 need a GPU
-    char *d = nullptr;
-    if (hipMalloc((void **)&d, total) != hipSuccess) return LOM_ERR_OOM;
+    DeviceBuf buf;
+    if (alloc(buf, total) != hipSuccess) return LOM_ERR_OOM;
+    char *d = buf.as<char>();
     hipError_t e = hipMemset(d, 0, total);
     if (e == hipSuccess) e = hipMemset(d + o_act, 0xFF, slots * 4);
     if (e == hipSuccess) e = hipMemcpy(d + o_x0, x0, ns * 7 * 8, hipMemcpyHostToDevice);
@@ -851,7 +852,6 @@ int lom_debug_lm_policy(int form, int n_solves, const int *n_evals, const double
     if (e == hipSuccess) e = hipMemcpy(evaluations_out, d + o_ev, ns * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(last_step_norm_out, d + o_lsn, ns * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(cost_out, d + o_cost, ns * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
     return e == hipSuccess ? LOM_OK : LOM_ERR_HIP;
 }
 
@@ -867,16 +867,16 @@ int lom_debug_match_stamps(lom_map *m, const float *d_src, size_t n, size_t stri
     server_stop(m);
     const uint32_t nb = match_grid((uint32_t)n);
     if (nb > cap_blocks) return LOM_ERR_ARG;
-    unsigned long long *d_st = nullptr;
-    LOM_HIP(m, hipMalloc(&d_st, (size_t)nb * 64));
+    DeviceBuf st;
+    LOM_HIP(m, alloc(st, (size_t)nb * 64));
+    unsigned long long *d_st = st.as<unsigned long long>();
     PoseArgs P;
     pose_args(t, q, sq_f32(max_dist), P);
     for (int rep = 0; rep < 3; rep++)  // the last launch's stamps are kept (warm caches, like an align)
         launch_k_match_stamps(m, nb, (const char *)d_src, stride, (uint32_t)n, P, d_st);
     hipError_t e = hipMemcpyAsync(stamps_out, d_st, (size_t)nb * 64, hipMemcpyDeviceToHost, m->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    (void)hipFree(d_st);
-    if (e != hipSuccess) return set_error(m, LOM_ERR_HIP, "stamp readback", e);
+    if (e != hipSuccess) return fail(m, LOM_ERR_HIP, "stamp readback", e);
     *n_blocks_out = nb;
     return LOM_OK;
 }

@@ -222,12 +222,13 @@ int64_t lom_estimate_normals(const float *xyz, size_t n, size_t stride, float ra
         if (m) lom_map_destroy(m);
         return rc;
     }
-    float *d_xyz = nullptr, *d_nrm = nullptr;
-    uint32_t *d_cnt = nullptr;
+    DeviceBuf b_xyz, b_nrm, b_cnt;  // freed when this returns
     const size_t bytes = (n - 1) * stride + 12;
-    hipError_t e = hipMalloc((void **)&d_xyz, bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_nrm, n * 12);
-    if (e == hipSuccess && neighbours_out) e = hipMalloc((void **)&d_cnt, n * 4);
+    hipError_t e = alloc(b_xyz, bytes);
+    if (e == hipSuccess) e = alloc(b_nrm, n * 12);
+    if (e == hipSuccess && neighbours_out) e = alloc(b_cnt, n * 4);
+    float *d_xyz = b_xyz.as<float>(), *d_nrm = b_nrm.as<float>();
+    uint32_t *d_cnt = b_cnt.as<uint32_t>();
     if (e == hipSuccess) e = hipMemcpyAsync(d_xyz, xyz, bytes, hipMemcpyHostToDevice, m->stream);
     if (e == hipSuccess) {
         const uint32_t groups = kNrmThreads / kNrmG;
@@ -239,9 +240,6 @@ int64_t lom_estimate_normals(const float *xyz, size_t n, size_t stride, float ra
     if (e == hipSuccess) e = hipMemcpyAsync(nrm_out, d_nrm, n * 12, hipMemcpyDeviceToHost, m->stream);
     if (e == hipSuccess && neighbours_out) e = hipMemcpyAsync(neighbours_out, d_cnt, n * 4, hipMemcpyDeviceToHost, m->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (d_xyz) (void)hipFree(d_xyz);
-    if (d_nrm) (void)hipFree(d_nrm);
-    if (d_cnt) (void)hipFree(d_cnt);
     lom_map_destroy(m);
     if (e != hipSuccess) return LOM_ERR_HIP;
     int64_t valid = 0;

@@ -15,46 +15,31 @@
 using namespace lom;
 
 // The database owns its stream, its entries and every buffer below; calls on one database are serialised by `lock`.
-struct lom_place_db {
+struct lom_place_db : DeviceHandle {
     lom_place_params params{};
-    int device = 0;
-    hipStream_t stream = nullptr;
     std::mutex lock;
     uint64_t size = 0, cap = 0;  // entries; cap is a multiple of kPlaceGroup
-    float *d_raw = nullptr;      // [cap][R][S]
-    float *d_unit = nullptr;     // [cap / 8][S][R][8]
-    unsigned long long *d_mask = nullptr;  // [cap]
-    uint32_t *d_acc = nullptr;   // R * S accumulation words, all zero between calls; then err[2]
-    uint32_t *d_err = nullptr;   // d_acc + R * S
+    DeviceBuf raw;   // f32 [cap][R][S]
+    DeviceBuf unit;  // f32 [cap / 8][S][R][8]
+    DeviceBuf mask;  // u64 [cap]
+    DeviceBuf acc;   // u32: R * S accumulation words, all zero between calls; then err[2]
     // per-call buffers, grow-only: uploaded clouds; uploaded descriptors; the queries' raw / unit / mask; pairs;
     // distances alone; matches
     DeviceBuf cloud, stage, q_raw, q_unit, q_mask, pairs, alld, match;
 #ifdef LOM_PLACE_TUNE  // the measuring build of tools/place_throughput.py only (make tune): E = 1, 2, 4 beside the shipped 8
     int query_entries = kPlaceGroup;  // LOM_PLACE_QUERY_ENTRIES at create: entries per LDS read
 #endif
-    std::string error;
+
+    float *d_raw() const { return raw.as<float>(); }
+    float *d_unit() const { return unit.as<float>(); }
+    unsigned long long *d_mask() const { return mask.as<unsigned long long>(); }
+    uint32_t *d_acc() const { return acc.as<uint32_t>(); }
+    uint32_t *d_err() const { return d_acc() + (size_t)params.rings * params.sectors; }
 };
 
 namespace {
 
 thread_local std::string g_place_create_error;
-
-int pfail(lom_place_db *db, int code, const char *what, hipError_t e = hipSuccess)
-{
-    std::string s = what;
-    if (e != hipSuccess) s += std::string(": ") + hipGetErrorString(e);
-    if (db)
-        db->error = s;
-    else
-        g_place_create_error = s;
-    return code;
-}
-
-#define PL_HIP(db, expr)                                                   \
-    do {                                                                   \
-        hipError_t _e = (expr);                                            \
-        if (_e != hipSuccess) return pfail((db), LOM_ERR_HIP, #expr, _e);  \
-    } while (0)
 
 bool params_ok(const lom_place_params *p)
 {
@@ -81,26 +66,6 @@ PlaceShape shape_of(const lom_place_db *db)
     return sh;
 }
 
-int pensure(lom_place_db *db, DeviceBuf &b, size_t bytes)
-{
-    if (bytes <= b.bytes) return LOM_OK;
-    size_t nb = std::max(bytes, b.bytes + b.bytes / 2);
-    nb = (nb + 255) & ~size_t(255);
-    if (b.p) {
-        PL_HIP(db, hipStreamSynchronize(db->stream));
-        PL_HIP(db, hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
-    }
-    if (hipMalloc(&b.p, nb) != hipSuccess) {
-        (void)hipGetLastError();
-        b.p = nullptr;
-        return pfail(db, LOM_ERR_OOM, "hipMalloc");
-    }
-    b.bytes = nb;
-    return LOM_OK;
-}
-
 // room for `need` entries: geometric growth; the entries move on the database's stream, ids and bytes stay
 int reserve_entries(lom_place_db *db, uint64_t need)
 {
@@ -108,32 +73,19 @@ int reserve_entries(lom_place_db *db, uint64_t need)
     uint64_t cap = std::max<uint64_t>(need, db->cap * 2);
     cap = (cap + kPlaceGroup - 1) / kPlaceGroup * kPlaceGroup;
     const size_t rs = cells_of(db);
-    float *raw = nullptr, *unit = nullptr;
-    unsigned long long *mask = nullptr;
-    if (hipMalloc((void **)&raw, cap * rs * 4) != hipSuccess || hipMalloc((void **)&unit, cap * rs * 4) != hipSuccess ||
-        hipMalloc((void **)&mask, cap * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        if (raw) (void)hipFree(raw);
-        if (unit) (void)hipFree(unit);
-        if (mask) (void)hipFree(mask);
-        return pfail(db, LOM_ERR_OOM, "hipMalloc (database entries)");
-    }
-    hipError_t e = hipMemsetAsync(unit, 0, cap * rs * 4, db->stream);  // a group's unused places are read, never reported
-    if (e == hipSuccess) e = hipMemsetAsync(mask, 0, cap * 8, db->stream);
+    DeviceBuf raw, unit, mask;
+    if (alloc(raw, cap * rs * 4) != hipSuccess || alloc(unit, cap * rs * 4) != hipSuccess || alloc(mask, cap * 8) != hipSuccess)
+        return fail(db, LOM_ERR_OOM, "hipMalloc (database entries)");
+    hipError_t e = hipMemsetAsync(unit.p, 0, cap * rs * 4, db->stream);  // a group's unused places are read, never reported
+    if (e == hipSuccess) e = hipMemsetAsync(mask.p, 0, cap * 8, db->stream);
     if (db->cap) {
-        if (e == hipSuccess) e = hipMemcpyAsync(raw, db->d_raw, db->cap * rs * 4, hipMemcpyDeviceToDevice, db->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(unit, db->d_unit, db->cap * rs * 4, hipMemcpyDeviceToDevice, db->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(mask, db->d_mask, db->cap * 8, hipMemcpyDeviceToDevice, db->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(raw.p, db->raw.p, db->cap * rs * 4, hipMemcpyDeviceToDevice, db->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(unit.p, db->unit.p, db->cap * rs * 4, hipMemcpyDeviceToDevice, db->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(mask.p, db->mask.p, db->cap * 8, hipMemcpyDeviceToDevice, db->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(db->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(raw), (void)hipFree(unit), (void)hipFree(mask);
-        return pfail(db, LOM_ERR_HIP, "growing the database", e);
-    }
-    if (db->d_raw) (void)hipFree(db->d_raw);
-    if (db->d_unit) (void)hipFree(db->d_unit);
-    if (db->d_mask) (void)hipFree(db->d_mask);
-    db->d_raw = raw, db->d_unit = unit, db->d_mask = mask, db->cap = cap;
+    if (e != hipSuccess) return fail(db, LOM_ERR_HIP, "growing the database", e);
+    db->raw = std::move(raw), db->unit = std::move(unit), db->mask = std::move(mask), db->cap = cap;  // the old blocks go
     return LOM_OK;
 }
 
@@ -151,8 +103,8 @@ int enqueue_bin(lom_place_db *db, const void *d_xyz, size_t n, size_t stride)
     if (!n) return LOM_OK;
     const uint32_t blocks = (uint32_t)std::min<size_t>((n + kPlaceBinThreads - 1) / kPlaceBinThreads, 1024);
     hipLaunchKernelGGL(k_place_bin, dim3(blocks), dim3(kPlaceBinThreads), 0, db->stream, (const char *)d_xyz, stride, (uint32_t)n,
-                       shape_of(db), db->d_acc, db->d_err);
-    PL_HIP(db, hipGetLastError());
+                       shape_of(db), db->d_acc(), db->d_err());
+    LOM_HIP(db, hipGetLastError());
     return LOM_OK;
 }
 
@@ -162,16 +114,16 @@ int enqueue_finish(lom_place_db *db, uint32_t *src, bool from_acc, uint32_t coun
                    unsigned long long *dst_mask, uint64_t first_slot, bool grouped)
 {
     hipLaunchKernelGGL(k_place_finish, dim3(count), dim3(64), 0, db->stream, src, db->params.rings, db->params.sectors,
-                       from_acc ? 1 : 0, dst_raw, dst_unit, dst_mask, first_slot, grouped ? 1 : 0, db->d_err);
-    PL_HIP(db, hipGetLastError());
+                       from_acc ? 1 : 0, dst_raw, dst_unit, dst_mask, first_slot, grouped ? 1 : 0, db->d_err());
+    LOM_HIP(db, hipGetLastError());
     return LOM_OK;
 }
 
 int ensure_query_slots(lom_place_db *db, size_t q)
 {
-    int rc = pensure(db, db->q_raw, q * cells_of(db) * 4);
-    if (rc == LOM_OK) rc = pensure(db, db->q_unit, q * cells_of(db) * 4);
-    if (rc == LOM_OK) rc = pensure(db, db->q_mask, q * 8);
+    int rc = ensure(db, db->q_raw, q * cells_of(db) * 4);
+    if (rc == LOM_OK) rc = ensure(db, db->q_unit, q * cells_of(db) * 4);
+    if (rc == LOM_OK) rc = ensure(db, db->q_mask, q * 8);
     return rc;
 }
 
@@ -180,9 +132,9 @@ void launch_query(lom_place_db *db, uint32_t tiles, uint32_t q, uint64_t id_begi
 {
     const size_t lds = (size_t)db->params.rings * 2 * db->params.sectors * 4;  // <= 32 KB
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_place_query<E>), dim3(tiles, q), dim3(kPlaceQueryWaves * 64), lds, db->stream,
-                       (const float *)db->d_unit, (const unsigned long long *)db->d_mask, (const float *)db->q_unit.p,
-                       (const unsigned long long *)db->q_mask.p, db->params.rings, db->params.sectors, id_begin, id_end,
-                       (PlacePair *)db->pairs.p, all_dist);
+                       (const float *)db->d_unit(), (const unsigned long long *)db->d_mask(), db->q_unit.as<const float>(),
+                       db->q_mask.as<const unsigned long long>(), db->params.rings, db->params.sectors, id_begin, id_end,
+                       db->pairs.as<PlacePair>(), all_dist);
 }
 
 void empty_matches(lom_place_match *out, size_t count)
@@ -199,13 +151,13 @@ int enqueue_search(lom_place_db *db, uint32_t q, int64_t id_begin, int64_t id_en
                    float *all_dist)
 {
     const uint64_t n = (uint64_t)(id_end - id_begin);
-    int rc = pensure(db, db->pairs, (size_t)q * n * sizeof(PlacePair));
-    if (rc == LOM_OK) rc = pensure(db, db->match, (size_t)q * k * sizeof(PlaceMatch));
-    if (rc == LOM_OK && all_dist) rc = pensure(db, db->alld, (size_t)q * n * 4);
+    int rc = ensure(db, db->pairs, (size_t)q * n * sizeof(PlacePair));
+    if (rc == LOM_OK) rc = ensure(db, db->match, (size_t)q * k * sizeof(PlaceMatch));
+    if (rc == LOM_OK && all_dist) rc = ensure(db, db->alld, (size_t)q * n * 4);
     if (rc != LOM_OK) return rc;
     const uint64_t base = (uint64_t)id_begin / kPlaceGroup * kPlaceGroup;
     const uint32_t tiles = (uint32_t)(((uint64_t)id_end - base + kPlaceTile - 1) / kPlaceTile);
-    float *d_all = all_dist ? (float *)db->alld.p : nullptr;
+    float *d_all = all_dist ? db->alld.as<float>() : nullptr;
 #ifdef LOM_PLACE_TUNE
     switch (db->query_entries) {
     case 1: launch_query<1>(db, tiles, q, (uint64_t)id_begin, (uint64_t)id_end, d_all); break;
@@ -216,12 +168,12 @@ int enqueue_search(lom_place_db *db, uint32_t q, int64_t id_begin, int64_t id_en
 #else
     launch_query<kPlaceGroup>(db, tiles, q, (uint64_t)id_begin, (uint64_t)id_end, d_all);
 #endif
-    PL_HIP(db, hipGetLastError());
-    hipLaunchKernelGGL(k_place_topk, dim3(q), dim3(kPlaceTopkThreads), 0, db->stream, (const PlacePair *)db->pairs.p, (uint32_t)n,
-                       (uint64_t)id_begin, k, (PlaceMatch *)db->match.p);
-    PL_HIP(db, hipGetLastError());
-    PL_HIP(db, hipMemcpyAsync(out, db->match.p, (size_t)q * k * sizeof(PlaceMatch), hipMemcpyDeviceToHost, db->stream));
-    if (all_dist) PL_HIP(db, hipMemcpyAsync(all_dist, d_all, (size_t)q * n * 4, hipMemcpyDeviceToHost, db->stream));
+    LOM_HIP(db, hipGetLastError());
+    hipLaunchKernelGGL(k_place_topk, dim3(q), dim3(kPlaceTopkThreads), 0, db->stream, db->pairs.as<const PlacePair>(), (uint32_t)n,
+                       (uint64_t)id_begin, k, db->match.as<PlaceMatch>());
+    LOM_HIP(db, hipGetLastError());
+    LOM_HIP(db, hipMemcpyAsync(out, db->match.p, (size_t)q * k * sizeof(PlaceMatch), hipMemcpyDeviceToHost, db->stream));
+    if (all_dist) LOM_HIP(db, hipMemcpyAsync(all_dist, d_all, (size_t)q * n * 4, hipMemcpyDeviceToHost, db->stream));
     return LOM_OK;
 }
 
@@ -235,9 +187,9 @@ int upload_cloud(lom_place_db *db, const void *xyz, size_t n, size_t stride)
 {
     if (!n) return LOM_OK;
     const size_t bytes = (n - 1) * stride + 12;
-    const int rc = pensure(db, db->cloud, bytes);
+    const int rc = ensure(db, db->cloud, bytes);
     if (rc != LOM_OK) return rc;
-    PL_HIP(db, hipMemcpyAsync(db->cloud.p, xyz, bytes, hipMemcpyHostToDevice, db->stream));
+    LOM_HIP(db, hipMemcpyAsync(db->cloud.p, xyz, bytes, hipMemcpyHostToDevice, db->stream));
     return LOM_OK;
 }
 
@@ -246,7 +198,7 @@ int upload_cloud(lom_place_db *db, const void *xyz, size_t n, size_t stride)
 int fail_at_rest(lom_place_db *db, int rc)
 {
     (void)hipGetLastError();
-    if (hipMemsetAsync(db->d_acc, 0, (cells_of(db) + 2) * 4, db->stream) != hipSuccess ||
+    if (hipMemsetAsync(db->d_acc(), 0, (cells_of(db) + 2) * 4, db->stream) != hipSuccess ||
         hipStreamSynchronize(db->stream) != hipSuccess)
         (void)hipGetLastError();
     return rc;
@@ -256,9 +208,9 @@ int fail_at_rest(lom_place_db *db, int rc)
 int wait_and_check(lom_place_db *db, bool check_points)
 {
     uint32_t status = 0;
-    if (check_points) PL_HIP(db, hipMemcpyAsync(&status, db->d_err + 1, 4, hipMemcpyDeviceToHost, db->stream));
-    PL_HIP(db, hipStreamSynchronize(db->stream));
-    if (status) return pfail(db, LOM_ERR_RANGE, "a point of the cloud is not finite");
+    if (check_points) LOM_HIP(db, hipMemcpyAsync(&status, db->d_err() + 1, 4, hipMemcpyDeviceToHost, db->stream));
+    LOM_HIP(db, hipStreamSynchronize(db->stream));
+    if (status) return fail(db, LOM_ERR_RANGE, "a point of the cloud is not finite");
     return LOM_OK;
 }
 
@@ -266,15 +218,15 @@ int describe_impl(lom_place_db *db, const void *xyz, size_t n, size_t stride, bo
 {
     if (!db || !desc_out || !cloud_args_ok(xyz, n, stride)) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> g(db->lock);
-    PL_HIP(db, hipSetDevice(db->device));
+    LOM_HIP(db, hipSetDevice(db->device));
     int rc = ensure_query_slots(db, 1);
     if (rc == LOM_OK && !on_device) rc = upload_cloud(db, xyz, n, stride);
     if (rc == LOM_OK) rc = enqueue_bin(db, on_device ? xyz : db->cloud.p, n, stride);
     if (rc == LOM_OK)
-        rc = enqueue_finish(db, db->d_acc, true, 1, (float *)db->q_raw.p, (float *)db->q_unit.p,
-                            (unsigned long long *)db->q_mask.p, 0, false);
+        rc = enqueue_finish(db, db->d_acc(), true, 1, db->q_raw.as<float>(), db->q_unit.as<float>(),
+                            db->q_mask.as<unsigned long long>(), 0, false);
     if (rc != LOM_OK) return fail_at_rest(db, rc);
-    PL_HIP(db, hipMemcpyAsync(desc_out, db->q_raw.p, cells_of(db) * 4, hipMemcpyDeviceToHost, db->stream));
+    LOM_HIP(db, hipMemcpyAsync(desc_out, db->q_raw.p, cells_of(db) * 4, hipMemcpyDeviceToHost, db->stream));
     return wait_and_check(db, true);  // on LOM_ERR_RANGE desc_out holds no descriptor
 }
 
@@ -282,11 +234,11 @@ int64_t add_cloud_impl(lom_place_db *db, const void *xyz, size_t n, size_t strid
 {
     if (!db || !cloud_args_ok(xyz, n, stride)) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> g(db->lock);
-    PL_HIP(db, hipSetDevice(db->device));
+    LOM_HIP(db, hipSetDevice(db->device));
     int rc = reserve_entries(db, db->size + 1);
     if (rc == LOM_OK && !on_device) rc = upload_cloud(db, xyz, n, stride);
     if (rc == LOM_OK) rc = enqueue_bin(db, on_device ? xyz : db->cloud.p, n, stride);
-    if (rc == LOM_OK) rc = enqueue_finish(db, db->d_acc, true, 1, db->d_raw, db->d_unit, db->d_mask, db->size, true);
+    if (rc == LOM_OK) rc = enqueue_finish(db, db->d_acc(), true, 1, db->d_raw(), db->d_unit(), db->d_mask(), db->size, true);
     if (rc != LOM_OK) return fail_at_rest(db, rc);
     // On LOM_ERR_RANGE k_place_finish has written the slot at `size` all the same; the slot stays beyond `size`, no call
     // reads it (queries and get stop at `size`) and the next add overwrites it whole: nothing is stored.
@@ -303,20 +255,10 @@ int lom_place_db_create(const lom_place_params *params, int device, size_t capac
     if (!out) return LOM_ERR_ARG;
     *out = nullptr;
     if (!params_ok(params))
-        return pfail(nullptr, LOM_ERR_ARG, "1 <= rings, sectors <= 64, max_range > 0 and finite, z_floor finite");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return pfail(nullptr, LOM_ERR_NO_DEVICE, "no HIP device visible (this library has no CPU fallback)");
-    }
-    if (device < 0 || device >= ndev) return pfail(nullptr, LOM_ERR_ARG, "device index out of range");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess)
-        return pfail(nullptr, LOM_ERR_NO_DEVICE, "hipGetDeviceProperties failed");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return pfail(nullptr, LOM_ERR_NO_DEVICE, "kernels are built for gfx950 only");
+        return create_fail(g_place_create_error, LOM_ERR_ARG, "1 <= rings, sectors <= 64, max_range > 0 and finite, z_floor finite");
+    if (const int rc = check_device(device, g_place_create_error); rc != LOM_OK) return rc;
     lom_place_db *db = new (std::nothrow) lom_place_db();
-    if (!db) return pfail(nullptr, LOM_ERR_OOM, "host allocation");
+    if (!db) return create_fail(g_place_create_error, LOM_ERR_OOM, "host allocation");
     db->params = *params;
     db->device = device;
 #ifdef LOM_PLACE_TUNE
@@ -328,12 +270,11 @@ int lom_place_db_create(const lom_place_params *params, int device, size_t capac
     const size_t acc_bytes = (cells_of(db) + 2) * 4;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&db->d_acc, acc_bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(db->d_acc, 0, acc_bytes, db->stream);  // at rest from here on
+    if (e == hipSuccess) e = alloc(db->acc, acc_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(db->d_acc(), 0, acc_bytes, db->stream);  // at rest from here on
     if (e == hipSuccess) e = hipStreamSynchronize(db->stream);
-    int rc = e == hipSuccess ? LOM_OK : pfail(nullptr, LOM_ERR_HIP, "database setup", e);
+    int rc = e == hipSuccess ? LOM_OK : create_fail(g_place_create_error, LOM_ERR_HIP, "database setup", e);
     if (rc == LOM_OK) {
-        db->d_err = db->d_acc + cells_of(db);
         rc = reserve_entries(db, std::max<size_t>(capacity_hint, 1));
         if (rc != LOM_OK) g_place_create_error = db->error;
     }
@@ -350,14 +291,8 @@ void lom_place_db_destroy(lom_place_db *db)
     if (!db) return;
     (void)hipSetDevice(db->device);
     if (db->stream) (void)hipStreamSynchronize(db->stream);
-    for (DeviceBuf *b : {&db->cloud, &db->stage, &db->q_raw, &db->q_unit, &db->q_mask, &db->pairs, &db->alld, &db->match})
-        if (b->p) (void)hipFree(b->p);
-    if (db->d_raw) (void)hipFree(db->d_raw);
-    if (db->d_unit) (void)hipFree(db->d_unit);
-    if (db->d_mask) (void)hipFree(db->d_mask);
-    if (db->d_acc) (void)hipFree(db->d_acc);
     if (db->stream) (void)hipStreamDestroy(db->stream);
-    delete db;
+    delete db;  // the buffers go with it
 }
 
 const char *lom_place_db_last_error(const lom_place_db *db) { return db ? db->error.c_str() : g_place_create_error.c_str(); }
@@ -391,8 +326,8 @@ int lom_place_db_wait_event(lom_place_db *db, void *hip_event)
 {
     if (!db || !hip_event) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> g(db->lock);
-    PL_HIP(db, hipSetDevice(db->device));
-    PL_HIP(db, hipStreamWaitEvent(db->stream, (hipEvent_t)hip_event, 0));
+    LOM_HIP(db, hipSetDevice(db->device));
+    LOM_HIP(db, hipStreamWaitEvent(db->stream, (hipEvent_t)hip_event, 0));
     return LOM_OK;
 }
 
@@ -411,16 +346,16 @@ int64_t lom_place_db_add(lom_place_db *db, const float *desc)
     if (!db || !desc) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> g(db->lock);
     const size_t rs = cells_of(db);
-    if (!descriptor_ok(desc, rs)) return pfail(db, LOM_ERR_ARG, "a descriptor value is negative or not finite");
-    PL_HIP(db, hipSetDevice(db->device));
+    if (!descriptor_ok(desc, rs)) return fail(db, LOM_ERR_ARG, "a descriptor value is negative or not finite");
+    LOM_HIP(db, hipSetDevice(db->device));
     int rc = reserve_entries(db, db->size + 1);
-    if (rc == LOM_OK) rc = pensure(db, db->stage, rs * 4);
+    if (rc == LOM_OK) rc = ensure(db, db->stage, rs * 4);
     if (rc != LOM_OK) return rc;
-    PL_HIP(db, hipMemcpyAsync(db->stage.p, desc, rs * 4, hipMemcpyHostToDevice, db->stream));
+    LOM_HIP(db, hipMemcpyAsync(db->stage.p, desc, rs * 4, hipMemcpyHostToDevice, db->stream));
     // the same kernel as a cloud's descriptor goes through: an entry has one origin for its unit form
-    if ((rc = enqueue_finish(db, (uint32_t *)db->stage.p, false, 1, db->d_raw, db->d_unit, db->d_mask, db->size, true)) != LOM_OK)
+    if ((rc = enqueue_finish(db, db->stage.as<uint32_t>(), false, 1, db->d_raw(), db->d_unit(), db->d_mask(), db->size, true)) != LOM_OK)
         return rc;
-    PL_HIP(db, hipStreamSynchronize(db->stream));  // `desc` is the caller's again
+    LOM_HIP(db, hipStreamSynchronize(db->stream));  // `desc` is the caller's again
     return (int64_t)db->size++;
 }
 
@@ -438,11 +373,11 @@ int lom_place_db_get(lom_place_db *db, int64_t id, float *desc_out)
 {
     if (!db || !desc_out) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> g(db->lock);
-    if (id < 0 || (uint64_t)id >= db->size) return pfail(db, LOM_ERR_ARG, "no entry with this id");
-    PL_HIP(db, hipSetDevice(db->device));
+    if (id < 0 || (uint64_t)id >= db->size) return fail(db, LOM_ERR_ARG, "no entry with this id");
+    LOM_HIP(db, hipSetDevice(db->device));
     const size_t rs = cells_of(db);
-    PL_HIP(db, hipMemcpyAsync(desc_out, db->d_raw + (size_t)id * rs, rs * 4, hipMemcpyDeviceToHost, db->stream));
-    PL_HIP(db, hipStreamSynchronize(db->stream));
+    LOM_HIP(db, hipMemcpyAsync(desc_out, db->d_raw() + (size_t)id * rs, rs * 4, hipMemcpyDeviceToHost, db->stream));
+    LOM_HIP(db, hipStreamSynchronize(db->stream));
     return LOM_OK;
 }
 
@@ -451,20 +386,20 @@ int lom_place_db_query(lom_place_db *db, const float *desc, int q, int64_t id_be
 {
     if (!db || !desc || !out || q < 1 || q > 65535 || k < 1 || k > 64 || id_begin > id_end) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> g(db->lock);
-    if (!range_ok(db, id_begin, id_end)) return pfail(db, LOM_ERR_ARG, "id range outside the database");
+    if (!range_ok(db, id_begin, id_end)) return fail(db, LOM_ERR_ARG, "id range outside the database");
     const size_t rs = cells_of(db);
-    if (!descriptor_ok(desc, (size_t)q * rs)) return pfail(db, LOM_ERR_ARG, "a descriptor value is negative or not finite");
+    if (!descriptor_ok(desc, (size_t)q * rs)) return fail(db, LOM_ERR_ARG, "a descriptor value is negative or not finite");
     if (id_begin == id_end) {  // an empty range is valid: k empty slots per query
         empty_matches(out, (size_t)q * k);
         return LOM_OK;
     }
-    PL_HIP(db, hipSetDevice(db->device));
-    int rc = pensure(db, db->stage, (size_t)q * rs * 4);
+    LOM_HIP(db, hipSetDevice(db->device));
+    int rc = ensure(db, db->stage, (size_t)q * rs * 4);
     if (rc == LOM_OK) rc = ensure_query_slots(db, (size_t)q);
     if (rc != LOM_OK) return rc;
-    PL_HIP(db, hipMemcpyAsync(db->stage.p, desc, (size_t)q * rs * 4, hipMemcpyHostToDevice, db->stream));
-    rc = enqueue_finish(db, (uint32_t *)db->stage.p, false, (uint32_t)q, nullptr, (float *)db->q_unit.p,
-                        (unsigned long long *)db->q_mask.p, 0, false);
+    LOM_HIP(db, hipMemcpyAsync(db->stage.p, desc, (size_t)q * rs * 4, hipMemcpyHostToDevice, db->stream));
+    rc = enqueue_finish(db, db->stage.as<uint32_t>(), false, (uint32_t)q, nullptr, db->q_unit.as<float>(),
+                        db->q_mask.as<unsigned long long>(), 0, false);
     if (rc == LOM_OK) rc = enqueue_search(db, (uint32_t)q, id_begin, id_end, k, out, all_dist);
     if (rc != LOM_OK) return rc;
     return wait_and_check(db, false);
@@ -475,12 +410,12 @@ int lom_place_db_query_cloud_device(lom_place_db *db, const float *d_xyz, size_t
 {
     if (!db || !out || k < 1 || k > 64 || id_begin > id_end || !cloud_args_ok(d_xyz, n, stride_bytes)) return LOM_ERR_ARG;
     std::lock_guard<std::mutex> g(db->lock);
-    if (!range_ok(db, id_begin, id_end)) return pfail(db, LOM_ERR_ARG, "id range outside the database");
-    PL_HIP(db, hipSetDevice(db->device));
+    if (!range_ok(db, id_begin, id_end)) return fail(db, LOM_ERR_ARG, "id range outside the database");
+    LOM_HIP(db, hipSetDevice(db->device));
     int rc = ensure_query_slots(db, 1);
     if (rc == LOM_OK) rc = enqueue_bin(db, d_xyz, n, stride_bytes);
     if (rc == LOM_OK)
-        rc = enqueue_finish(db, db->d_acc, true, 1, nullptr, (float *)db->q_unit.p, (unsigned long long *)db->q_mask.p, 0, false);
+        rc = enqueue_finish(db, db->d_acc(), true, 1, nullptr, db->q_unit.as<float>(), db->q_mask.as<unsigned long long>(), 0, false);
     if (rc == LOM_OK && id_begin < id_end) rc = enqueue_search(db, 1, id_begin, id_end, k, out, nullptr);
     if (rc != LOM_OK) return fail_at_rest(db, rc);
     if ((rc = wait_and_check(db, true)) != LOM_OK) {

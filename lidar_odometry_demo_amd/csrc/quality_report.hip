@@ -34,7 +34,7 @@ static int quality_core(lom_map *m, const float *src, bool device_input, size_t 
         return lom_quality_from_sums(zero, 0, min_eig_t, min_eig_r, out);
     }
     LOM_HIP(m, hipSetDevice(m->device));
-    m->last_error.clear();
+    m->error.clear();
     int rc = resolve_pending(m);  // an insert nobody has looked at since: the search must see its points
     if (rc != LOM_OK) return rc;
     const uint32_t nn = (uint32_t)n;
@@ -52,7 +52,7 @@ static int quality_core(lom_map *m, const float *src, bool device_input, size_t 
         if ((rc = upload_scan(m, m->qual.src, src, n, stride, &d_src)) != LOM_OK) return rc;
         if (residual_out) {
             if ((rc = ensure(m, m->qual.res, n * 4)) != LOM_OK) return rc;
-            d_res = (float *)m->qual.res.p;
+            d_res = m->qual.res.as<float>();
         }
     }
     PoseArgs P;
@@ -60,9 +60,9 @@ static int quality_core(lom_map *m, const float *src, bool device_input, size_t 
     EvalArgs E;
     for (int a = 0; a < 4; a++) E.q[a] = (double)q[a];
     for (int a = 0; a < 3; a++) E.t[a] = (double)t[a];
-    launch_k_match(m, false, m->opt_count, mb, d_src, stride, nn, P, (int32_t *)m->qual.idx.p, (MatchRec *)m->qual.rec.p, nullptr,
-                   (uint32_t *)m->qual.cnt.p);
-    launch_k_quality(m, nb, (const MatchRec *)m->qual.rec.p, nn, E, (double *)m->qual.part.p, d_res, (double *)m->qual.sums.d);
+    launch_k_match(m, false, m->opt_count, mb, d_src, stride, nn, P, m->qual.idx.as<int32_t>(), m->qual.rec.as<MatchRec>(), nullptr,
+                   m->qual.cnt.as<uint32_t>());
+    launch_k_quality(m, nb, m->qual.rec.as<const MatchRec>(), nn, E, m->qual.part.as<double>(), d_res, (double *)m->qual.sums.d);
     LOM_HIP(m, hipGetLastError());
     if (!device_input && residual_out)
         LOM_HIP(m, hipMemcpyAsync(residual_out, d_res, n * 4, hipMemcpyDeviceToHost, m->stream));
@@ -127,7 +127,7 @@ static int quality_batch_core(lom_map *m, const lom_quality_problem *p, int coun
         return LOM_OK;
     }
     LOM_HIP(m, hipSetDevice(m->device));
-    m->last_error.clear();
+    m->error.clear();
     int rc = resolve_pending(m);  // an insert nobody has looked at since: the search must see its points
     if (rc != LOM_OK) return rc;
     const int L = (int)live.size();
@@ -199,22 +199,22 @@ static int quality_batch_core(lom_map *m, const lom_quality_problem *p, int coun
     QualBatchProblem *h_eval = reinterpret_cast<QualBatchProblem *>((char *)m->qualb.stage.h + states_bytes + match_desc_bytes);
     double *h_sums = reinterpret_cast<double *>((char *)m->qualb.stage.h + dev_bytes);
     AlignState *d_states = reinterpret_cast<AlignState *>(m->qualb.dev.p);
-    const BatchProblem *d_match = reinterpret_cast<const BatchProblem *>((char *)m->qualb.dev.p + states_bytes);
+    const BatchProblem *d_match = reinterpret_cast<const BatchProblem *>(m->qualb.dev.as<char>() + states_bytes);
     const QualBatchProblem *d_eval =
-        reinterpret_cast<const QualBatchProblem *>((char *)m->qualb.dev.p + states_bytes + match_desc_bytes);
+        reinterpret_cast<const QualBatchProblem *>(m->qualb.dev.as<char>() + states_bytes + match_desc_bytes);
     const MapView view = view_of(m);
     const float max_sq = sq_f32(max_dist);
     for (int j = 0; j < L; j++) {
         const lom_quality_problem &q = p[live[j]];
         BatchProblem &d = h_match[j];
         fill_search(d, h_states[j], view, d_src[j], q.stride_bytes, (uint32_t)q.n, mb[j],
-                    reinterpret_cast<MatchRec *>((char *)m->qualb.rec.p + off_rec[j]),
-                    reinterpret_cast<uint32_t *>((char *)m->qualb.cnt.p + off_cnt[j]), d_states + j, q.t, q.q_wxyz, max_sq);
+                    reinterpret_cast<MatchRec *>(m->qualb.rec.as<char>() + off_rec[j]),
+                    reinterpret_cast<uint32_t *>(m->qualb.cnt.as<char>() + off_cnt[j]), d_states + j, q.t, q.q_wxyz, max_sq);
         QualBatchProblem &e = h_eval[j];
         std::memset(&e, 0, sizeof e);
         e.rec = d.rec;
-        e.part = reinterpret_cast<double *>((char *)m->qualb.part.p + off_part[j]);
-        e.out = (double *)m->qualb.sums.p + (size_t)j * LOM_NQSUMS;
+        e.part = reinterpret_cast<double *>(m->qualb.part.as<char>() + off_part[j]);
+        e.out = m->qualb.sums.as<double>() + (size_t)j * LOM_NQSUMS;
         e.n = d.n;
         e.grid = nb[j];
         for (int a = 0; a < 4; a++) e.E.q[a] = (double)q.q_wxyz[a];

@@ -74,7 +74,7 @@ static int table_alloc(lom_map *m, uint32_t cap, Slot **out)
 {
     Slot *t = nullptr;
     hipError_t e = hipMalloc(&t, (size_t)cap * sizeof(Slot));
-    if (e != hipSuccess) return set_error(m, LOM_ERR_OOM, "hipMalloc(table)", e);
+    if (e != hipSuccess) return fail(m, LOM_ERR_OOM, "hipMalloc(table)", e);
     hipLaunchKernelGGL(k_table_init, dim3(blocks_for(cap)), dim3(kThreads), 0, m->stream, t, cap);
     LOM_HIP(m, hipGetLastError());
     *out = t;
@@ -82,15 +82,15 @@ static int table_alloc(lom_map *m, uint32_t cap, Slot **out)
 }
 
 // scratch words: [0..1] u64 scan total, [2] flag, [4] u32 scan total, [6] device-side voxel counter
-static uint32_t *d_nvox(lom_map *m) { return (uint32_t *)m->scr[S_MISC].p + 6; }
-static uint32_t *d_word(lom_map *m, int i) { return (uint32_t *)m->scr[S_MISC].p + i; }
+static uint32_t *d_nvox(lom_map *m) { return m->scr[S_MISC].as<uint32_t>() + 6; }
+static uint32_t *d_word(lom_map *m, int i) { return m->scr[S_MISC].as<uint32_t>() + i; }
 
 // scratch slot `slot` grown to `count` elements of T (lom_internal.hpp: who keeps what in which slot)
 template <class T>
 static int scratch(lom_map *m, int slot, size_t count, T **out)
 {
     const int rc = ensure(m, m->scr[slot], count * sizeof(T));
-    *out = (T *)m->scr[slot].p;
+    *out = m->scr[slot].as<T>();
     return rc;
 }
 
@@ -132,13 +132,21 @@ static int rehash(lom_map *m, uint32_t new_cap)
     return LOM_OK;
 }
 
-void slabs_free(Slabs &s)
+static void slabs_free(Slabs &s)
 {
     if (s.key) (void)hipFree(s.key);
     if (s.count) (void)hipFree(s.count);
     if (s.pts) (void)hipFree(s.pts);
     if (s.nrm) (void)hipFree(s.nrm);
     s = Slabs();
+}
+
+void map_free(lom_map *m)
+{
+    if (m->d_table) (void)hipFree(m->d_table);
+    m->d_table = nullptr;
+    slabs_free(m->slabs);
+    slabs_free(m->alt);
 }
 
 // k_match reads a chunk of four consecutive 12-byte rows from any live row on: the rows behind the last slab exist
@@ -150,7 +158,7 @@ static int slabs_alloc(lom_map *m, uint32_t cap, Slabs &s)
         hipMalloc(&s.pts, pb + kRowPadBytes) != hipSuccess || hipMalloc(&s.nrm, pb + kRowPadBytes) != hipSuccess) {
         (void)hipGetLastError();
         slabs_free(s);
-        return set_error(m, LOM_ERR_OOM, "hipMalloc(slabs)");
+        return fail(m, LOM_ERR_OOM, "hipMalloc(slabs)");
     }
     s.cap = cap;
     return LOM_OK;
@@ -159,7 +167,7 @@ static int slabs_alloc(lom_map *m, uint32_t cap, Slabs &s)
 static int ensure_slabs(lom_map *m, uint64_t want)
 {
     if (want <= m->slabs.cap) return LOM_OK;
-    if (want > 0x7FFFFFFFull / std::max<uint32_t>(1, m->K)) return set_error(m, LOM_ERR_OOM, "map too large");
+    if (want > 0x7FFFFFFFull / std::max<uint32_t>(1, m->K)) return fail(m, LOM_ERR_OOM, "map too large");
     uint32_t nc = std::max<uint32_t>(4096, m->slabs.cap);
     while (nc < want) nc *= 2;
     Slabs s;
@@ -209,9 +217,9 @@ int gather_words_end(lom_map *m, uint32_t *out)
             const hipError_t e = hipStreamQuery(m->stream);
             if (e == hipSuccess) {
                 if ((uint32_t)(hw[i] >> 32) == tag) break;
-                return set_error(m, LOM_ERR_HIP, "device words did not arrive");
+                return fail(m, LOM_ERR_HIP, "device words did not arrive");
             }
-            if (e != hipErrorNotReady) return set_error(m, LOM_ERR_HIP, "stream failed while reading device words", e);
+            if (e != hipErrorNotReady) return fail(m, LOM_ERR_HIP, "stream failed while reading device words", e);
         }
         out[i] = (uint32_t)hw[i];
     }
@@ -243,7 +251,7 @@ static int ensure_rest(lom_map *m, DeviceBuf &b, size_t bytes, int fill)
     return LOM_OK;
 }
 
-static Granule *d_agg(lom_map *m) { return (Granule *)((char *)m->scr[S_MISC].p + 256); }
+static Granule *d_agg(lom_map *m) { return (Granule *)(m->scr[S_MISC].as<char>() + 256); }
 
 static int add_points_device(lom_map *m, const char *d_xyz, const char *d_nrm, size_t n, size_t stride,
                              bool validated_on_host, bool sync_status, bool allow_shrink = true, bool multi_launch = false);
@@ -290,13 +298,13 @@ static int map_status(lom_map *m)
             const int rc2 = add_points_device(m, m->pending_xyz, m->pending_nrm, pending, m->pending_stride, false, true, true, true);
             if (rc2 != LOM_OK) return rc2;
             if (range_seq > checked && range_seq != grid_seq)
-                return set_error(m, LOM_ERR_RANGE, "coordinate / voxel_size out of range or not finite");
+                return fail(m, LOM_ERR_RANGE, "coordinate / voxel_size out of range or not finite");
             return LOM_OK;
         }
-        return set_error(m, LOM_ERR_HIP,
+        return fail(m, LOM_ERR_HIP,
                          "a workgroup timed out waiting for the others of its grid; that call changed nothing, repeat it");
     }
-    if (range_seq > checked) return set_error(m, LOM_ERR_RANGE, "coordinate / voxel_size out of range or not finite");
+    if (range_seq > checked) return fail(m, LOM_ERR_RANGE, "coordinate / voxel_size out of range or not finite");
     return LOM_OK;
 }
 
@@ -318,7 +326,7 @@ int resolve_pending(lom_map *m)
         std::lock_guard<std::mutex> lock(p->settle_mutex);
         if (p->pending_n) {
             const int rc = settle_pending_locked(p);
-            if (rc != LOM_OK) return set_error(m, rc, p->last_error.c_str());
+            if (rc != LOM_OK) return fail(m, rc, p->error.c_str());
         }
         const uint64_t now = p->mutations;
         if (m->seen_mutations != now) {
@@ -442,7 +450,7 @@ static int bulk_scratch(lom_map *m, uint32_t N, const BulkShape &b)
     const bool fresh = m->scr[S_PART].bytes < (size_t)(2 * kBiMaxParts + 1 + 2 * 256 + 1) * 4;
     if ((rc = ensure(m, m->scr[S_PART], (size_t)(2 * kBiMaxParts + 1 + 2 * 256 + 1) * 4)) != LOM_OK) return rc;
     if (fresh) LOM_HIP(m, hipMemsetAsync(m->scr[S_PART].p, 0, m->scr[S_PART].bytes, m->stream));
-    return tiles <= 256 ? LOM_OK : set_error(m, LOM_ERR_ARG, "bulk insert: too many points");
+    return tiles <= 256 ? LOM_OK : fail(m, LOM_ERR_ARG, "bulk insert: too many points");
 }
 
 // The instantiations of the bulk insert's templated kernels (every instantiation of a family has the same signature):
@@ -476,13 +484,13 @@ static int add_points_bulk(lom_map *m, const char *d_xyz, const char *d_nrm, uin
     const BulkShape b = bulk_shape(N, m->cap, m->bulk_ppt);
     if ((rc = bulk_scratch(m, N, b)) != LOM_OK) return rc;
     if (worst > m->slabs.cap && (rc = ensure_slabs(m, worst + worst / 2)) != LOM_OK) return rc;
-    uint2 *pt_info = (uint2 *)m->scr[S_PT_SLOT].p;
-    uint32_t *flag_bits = (uint32_t *)m->scr[S_FLAG].p, *word_prefix = (uint32_t *)m->scr[S_RANK].p;
-    uint4 *part_rec = (uint4 *)m->scr[S_PT_POS].p;
-    uint32_t *ent_idx = (uint32_t *)m->scr[S_PT_OFF].p, *ent_w = (uint32_t *)m->scr[S_PT_M].p;
-    uint32_t *ent_row = (uint32_t *)m->scr[S_ENT_ROW].p;
-    uint32_t *hist = (uint32_t *)m->scr[S_HIST].p;
-    uint32_t *part_total = (uint32_t *)m->scr[S_PART].p, *part_start = part_total + kBiMaxParts;
+    uint2 *pt_info = m->scr[S_PT_SLOT].as<uint2>();
+    uint32_t *flag_bits = m->scr[S_FLAG].as<uint32_t>(), *word_prefix = m->scr[S_RANK].as<uint32_t>();
+    uint4 *part_rec = m->scr[S_PT_POS].as<uint4>();
+    uint32_t *ent_idx = m->scr[S_PT_OFF].as<uint32_t>(), *ent_w = m->scr[S_PT_M].as<uint32_t>();
+    uint32_t *ent_row = m->scr[S_ENT_ROW].as<uint32_t>();
+    uint32_t *hist = m->scr[S_HIST].as<uint32_t>();
+    uint32_t *part_total = m->scr[S_PART].as<uint32_t>(), *part_start = part_total + kBiMaxParts;
     uint32_t *tile_total = part_start + kBiMaxParts + 1, *tile_prefix = tile_total + 256, *tiles_done = tile_prefix + 256;
     const uint32_t n_tiles = (b.n_words + kBiTileWords - 1) / kBiTileWords;
     uint32_t *words = d_word(m, 0);
@@ -528,9 +536,9 @@ static int add_points_bulk(lom_map *m, const char *d_xyz, const char *d_nrm, uin
 static int add_points_device(lom_map *m, const char *d_xyz, const char *d_nrm, size_t n, size_t stride,
                              bool validated_on_host, bool sync_status, bool allow_shrink, bool multi_launch)
 {
-    if (m->parent) return set_error(m, LOM_ERR_STATE, "a scan context has no map of its own");
+    if (m->parent) return fail(m, LOM_ERR_STATE, "a scan context has no map of its own");
     if (n == 0) return LOM_OK;
-    if (n >= 0x7FFFFFFFull) return set_error(m, LOM_ERR_ARG, "too many points in one call");
+    if (n >= 0x7FFFFFFFull) return fail(m, LOM_ERR_ARG, "too many points in one call");
     const uint32_t N = (uint32_t)n;
     int rc;
     if ((rc = resolve_pending(m)) != LOM_OK) return rc;  // inserts apply in call order
@@ -561,7 +569,7 @@ static int add_points_device(lom_map *m, const char *d_xyz, const char *d_nrm, s
         if ((rc = scratch(m, S_RANK, N, &scan64)) != LOM_OK) return rc;
         if ((rc = scratch(m, S_SCAN, scan_tmp_words(N), &scan_tmp)) != LOM_OK) return rc;
     }
-    uint32_t *bcnt = (uint32_t *)m->scr[S_BKT_CNT].p, *bhead = (uint32_t *)m->scr[S_BKT_HEAD].p;
+    uint32_t *bcnt = m->scr[S_BKT_CNT].as<uint32_t>(), *bhead = m->scr[S_BKT_HEAD].as<uint32_t>();
     uint32_t *words = d_word(m, 0);
     const uint32_t seq = ++m->call_seq;
     m->mutations++;
@@ -578,7 +586,7 @@ static int add_points_device(lom_map *m, const char *d_xyz, const char *d_nrm, s
         // large batches: flags, one 64-bit scan (1-3 launches), assignment
         hipLaunchKernelGGL(k_ins_heads, g, b, 0, m->stream, m->d_table, N, pt_slot, bcnt, bhead, flag64, seq, words);
         LOM_HIP(m, hipGetLastError());
-        unsigned long long *d_total64 = (unsigned long long *)m->scr[S_MISC].p;
+        unsigned long long *d_total64 = m->scr[S_MISC].as<unsigned long long>();
         if ((rc = scan_exclusive<unsigned long long>(m, flag64, scan64, N, d_total64, scan_tmp)) != LOM_OK) return rc;
         hipLaunchKernelGGL(k_ins_assign, g, b, 0, m->stream, m->d_table, N, pt_slot, bhead, flag64, scan64, d_nvox(m),
                            m->slabs.key, boff, bold, seq, words);
@@ -629,7 +637,7 @@ static int stage_host_points(lom_map *m, const float *xyz, const float *nrm, siz
         std::memcpy(pin, hx, all);
         LOM_HIP(m, hipMemcpyAsync(m->scr[S_IN_XYZ].p, pin, all, hipMemcpyHostToDevice, m->stream));
         LOM_HIP(m, hipEventRecord(m->stage_ev, m->stream));
-        *d_xyz = (const char *)m->scr[S_IN_XYZ].p;
+        *d_xyz = m->scr[S_IN_XYZ].as<const char>();
         *d_nrm = *d_xyz + (hn - hx);
         return LOM_OK;
     }
@@ -639,11 +647,11 @@ static int stage_host_points(lom_map *m, const float *xyz, const float *nrm, siz
     if ((rc = stage_pinned(m, nrm ? 2 * padded : padded, &pin)) != LOM_OK) return rc;
     std::memcpy(pin, hx, bytes);
     LOM_HIP(m, hipMemcpyAsync(m->scr[S_IN_XYZ].p, pin, bytes, hipMemcpyHostToDevice, m->stream));
-    *d_xyz = (const char *)m->scr[S_IN_XYZ].p;
+    *d_xyz = m->scr[S_IN_XYZ].as<const char>();
     if (nrm) {
         std::memcpy(pin + padded, hn, bytes);
         LOM_HIP(m, hipMemcpyAsync(m->scr[S_IN_NRM].p, pin + padded, bytes, hipMemcpyHostToDevice, m->stream));
-        *d_nrm = (const char *)m->scr[S_IN_NRM].p;
+        *d_nrm = m->scr[S_IN_NRM].as<const char>();
     }
     LOM_HIP(m, hipEventRecord(m->stage_ev, m->stream));
     return LOM_OK;
@@ -657,7 +665,7 @@ static bool launch_cleanup_scan(lom_map *m, uint32_t nv, const float center[3], 
         uint32_t items;
         decltype(&k_cleanup_scan<1>) kernel;
     } forms[] = {{1, k_cleanup_scan<1>}, {4, k_cleanup_scan<4>}, {16, k_cleanup_scan<16>}};
-    uint32_t *keep = (uint32_t *)m->scr[S_FLAG].p, *newid = (uint32_t *)m->scr[S_RANK].p;
+    uint32_t *keep = m->scr[S_FLAG].as<uint32_t>(), *newid = m->scr[S_RANK].as<uint32_t>();
     for (const auto &f : forms) {
         if (nv > f.items * kOnePassMax) continue;
         hipLaunchKernelGGL(f.kernel, dim3(blocks_for((nv + f.items - 1) / f.items)), dim3(kThreads), 0, m->stream,
@@ -671,11 +679,11 @@ static bool launch_cleanup_scan(lom_map *m, uint32_t nv, const float center[3], 
 // the same through kernels that wait for nobody: flags, multi-launch scan; the number of voxels kept in word 4
 static int cleanup_scan_multi_launch(lom_map *m, uint32_t nv, const float center[3], float r2)
 {
-    uint32_t *keep = (uint32_t *)m->scr[S_FLAG].p, *newid = (uint32_t *)m->scr[S_RANK].p;
+    uint32_t *keep = m->scr[S_FLAG].as<uint32_t>(), *newid = m->scr[S_RANK].as<uint32_t>();
     hipLaunchKernelGGL(k_cleanup_flag, dim3(blocks_for(nv)), dim3(kThreads), 0, m->stream, m->slabs.pts, m->slabs.count, m->K, nv,
                        center[0], center[1], center[2], r2, keep);
     LOM_HIP(m, hipGetLastError());
-    return scan_exclusive(m, keep, newid, nv, d_word(m, 4), (uint32_t *)m->scr[S_SCAN].p);
+    return scan_exclusive(m, keep, newid, nv, d_word(m, 4), m->scr[S_SCAN].as<uint32_t>());
 }
 
 // lidar_odometry.cpp:65-67 calls radiusCleanup with the translation the align has just produced: the scan of that cleanup
@@ -700,7 +708,7 @@ void cleanup_scan_behind_align(lom_map *m)
     if (m->scr[S_FLAG].bytes < (size_t)nv * 4 || m->scr[S_RANK].bytes < (size_t)nv * 4 || nv > 16 * kOnePassMax) return;
     const float zero[3] = {0.f, 0.f, 0.f};
     const uint32_t seq = ++m->call_seq;
-    if (!launch_cleanup_scan(m, nv, zero, radius * radius, seq, (const AlignState *)m->align_state.p)) return;
+    if (!launch_cleanup_scan(m, nv, zero, radius * radius, seq, m->align_state.as<const AlignState>())) return;
     WordPtrs w;
     const int idx[kSpecWords] = {4, 7, 12, 13, 14, 15};
     for (int i = 0; i < 32; i++) w.p[i] = i < kSpecWords ? d_word(m, idx[i]) : nullptr;
@@ -757,7 +765,7 @@ int lom_map_clear(lom_map *m, float voxel_size)
 int lom_map_set_max_points(lom_map *m, size_t max_points)
 {
     if (!m || max_points == 0 || max_points > 65535) return LOM_ERR_ARG;
-    if (m->parent) return set_error(m, LOM_ERR_ARG, "a scan context cannot change its keyframe");
+    if (m->parent) return fail(m, LOM_ERR_ARG, "a scan context cannot change its keyframe");
     LOM_HIP(m, hipSetDevice(m->device));
     {
         const int rcn = refresh_nvox(m);  // also resolves a pending insert: it was made under the old value
@@ -772,7 +780,7 @@ int lom_map_set_max_points(lom_map *m, size_t max_points)
         slabs_free(m->alt);
         m->K = (uint32_t)max_points;
     } else if (max_points > m->K) {
-        if ((uint64_t)m->slabs.cap > 0x7FFFFFFFull / max_points) return set_error(m, LOM_ERR_OOM, "map too large");
+        if ((uint64_t)m->slabs.cap > 0x7FFFFFFFull / max_points) return fail(m, LOM_ERR_OOM, "map too large");
         m->mutations++;
         const uint32_t K0 = m->K, K1 = (uint32_t)max_points;
         const size_t pb = (size_t)m->slabs.cap * K1 * 3 * sizeof(float);
@@ -780,7 +788,7 @@ int lom_map_set_max_points(lom_map *m, size_t max_points)
         if (hipMalloc(&p1, pb + kRowPadBytes) != hipSuccess || hipMalloc(&n1, pb + kRowPadBytes) != hipSuccess) {
             (void)hipGetLastError();
             if (p1) (void)hipFree(p1);
-            return set_error(m, LOM_ERR_OOM, "hipMalloc(slabs)");
+            return fail(m, LOM_ERR_OOM, "hipMalloc(slabs)");
         }
         const size_t work = (size_t)m->n_vox * K0;
         hipLaunchKernelGGL(k_restride, dim3(blocks_for(work)), dim3(kThreads), 0, m->stream, m->slabs.pts, m->slabs.nrm,
@@ -838,7 +846,7 @@ int lom_profile_insert(lom_map *m, const float *d_xyz, const float *d_nrm, size_
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     if (rc != LOM_OK) return rc;
-    if (e != hipSuccess) return set_error(m, LOM_ERR_HIP, "lom_profile_insert", e);
+    if (e != hipSuccess) return fail(m, LOM_ERR_HIP, "lom_profile_insert", e);
     *total_us_out = (double)ms * 1e3;
     if ((rc = map_status(m)) != LOM_OK) return rc;
     // what lom_map_add_points_device does after a bulk insert: ~16 slots per voxel
@@ -870,7 +878,7 @@ int lom_map_add_points(lom_map *m, const float *xyz, const float *nrm, size_t n,
             bad |= !(fx > -kIdxLimit && fx < kIdxLimit) || !(fy > -kIdxLimit && fy < kIdxLimit) ||
                    !(fz > -kIdxLimit && fz < kIdxLimit);
         }
-        if (bad) return set_error(m, LOM_ERR_RANGE, "coordinate / voxel_size out of range or not finite");
+        if (bad) return fail(m, LOM_ERR_RANGE, "coordinate / voxel_size out of range or not finite");
     }
     const char *dx = nullptr, *dn = nullptr;
     int rc = resolve_pending(m);  // before the staging buffers (a pending insert's input) are overwritten
@@ -928,7 +936,7 @@ static int take_cleanup_behind_align(lom_map *m, const float center[3], float ra
 static int erase_unkept(lom_map *m, uint32_t nv, uint32_t n_keep)
 {
     int rc;
-    uint32_t *keep = (uint32_t *)m->scr[S_FLAG].p, *newid = (uint32_t *)m->scr[S_RANK].p;
+    uint32_t *keep = m->scr[S_FLAG].as<uint32_t>(), *newid = m->scr[S_RANK].as<uint32_t>();
     const uint32_t n_live = nv - m->n_dead;
     if (n_keep == n_live) return LOM_OK;
     if (!m->opt_dense_cleanup && (uint64_t)(nv - n_keep) * 4u <= (uint64_t)nv) {
@@ -1024,7 +1032,7 @@ static int carve_count(lom_map *m, uint32_t nv, const float origin[3], const cha
     for (int a = 0; a < 3; a++) {
         const float f = origin[a] / vs;
         if (!(f > -kIdxLimit && f < kIdxLimit))
-            return set_error(m, LOM_ERR_RANGE, "carve: origin / voxel_size out of range or not finite");
+            return fail(m, LOM_ERR_RANGE, "carve: origin / voxel_size out of range or not finite");
     }
     int rc;
     uint32_t *cross, *hit, *words;
@@ -1060,7 +1068,7 @@ static int carve_rays(lom_map *m, const float origin[3], const float *xyz, size_
 {
     int rc = carve_args(m, origin, xyz, n, stride, p);
     if (rc != LOM_OK) return rc;
-    if (m->parent) return set_error(m, LOM_ERR_ARG, "a scan context cannot change its keyframe");
+    if (m->parent) return fail(m, LOM_ERR_ARG, "a scan context cannot change its keyframe");
     if (stats) *stats = lom_carve_stats();
     if (n == 0) return LOM_OK;
     LOM_HIP(m, hipSetDevice(m->device));
@@ -1079,8 +1087,8 @@ static int carve_rays(lom_map *m, const float origin[3], const float *xyz, size_
     ++m->call_seq;
     m->mutations++;
     if ((rc = carve_count(m, nv, origin, d_xyz, (uint32_t)n, stride, *p)) != LOM_OK) return rc;
-    uint32_t *cross = (uint32_t *)m->scr[S_CARVE_CROSS].p, *hit = (uint32_t *)m->scr[S_CARVE_HIT].p,
-             *words = (uint32_t *)m->scr[S_CARVE_WORDS].p;
+    uint32_t *cross = m->scr[S_CARVE_CROSS].as<uint32_t>(), *hit = m->scr[S_CARVE_HIT].as<uint32_t>(),
+             *words = m->scr[S_CARVE_WORDS].as<uint32_t>();
     if (nv) {
         hipLaunchKernelGGL(k_carve_flag, dim3(blocks_for(nv)), dim3(kThreads), 0, m->stream, cross, hit, m->slabs.count, nv,
                            p->min_crossings, keep, words);
@@ -1093,7 +1101,7 @@ static int carve_rays(lom_map *m, const float origin[3], const float *xyz, size_
     ptrs[CW_COUNT] = d_word(m, 4);
     uint32_t got[CW_COUNT + 1];
     if ((rc = gather_words(m, ptrs, CW_COUNT + 1, got)) != LOM_OK) return rc;
-    if (got[CW_ERROR]) return set_error(m, LOM_ERR_RANGE, "carve: coordinate / voxel_size out of range or not finite");
+    if (got[CW_ERROR]) return fail(m, LOM_ERR_RANGE, "carve: coordinate / voxel_size out of range or not finite");
     const uint32_t n_keep = nv ? got[CW_COUNT] : 0u, n_live = nv - m->n_dead;
     if (stats) {
         stats->rays_walked = (uint64_t)got[CW_WALKED] | ((uint64_t)got[CW_WALKED + 1] << 32);
@@ -1123,7 +1131,7 @@ int64_t lom_map_carve_counts(lom_map *m, const float origin[3], const float *xyz
 {
     int rc = carve_args(m, origin, xyz, n, stride, p);
     if (rc != LOM_OK) return rc;
-    if (m->parent) return set_error(m, LOM_ERR_ARG, "carve counts are the map's, not a scan context's");
+    if (m->parent) return fail(m, LOM_ERR_ARG, "carve counts are the map's, not a scan context's");
     LOM_HIP(m, hipSetDevice(m->device));
     if ((rc = refresh_nvox(m)) != LOM_OK) return rc;
     const uint32_t nv = m->n_vox;  // (an empty map: the kernels run all the same, for the range verdict)
@@ -1140,7 +1148,7 @@ int64_t lom_map_carve_counts(lom_map *m, const float origin[3], const float *xyz
     }
     if (nv) LOM_HIP(m, hipMemcpyAsync(count.data(), m->slabs.count, (size_t)nv * 4, hipMemcpyDeviceToHost, m->stream));
     LOM_HIP(m, hipStreamSynchronize(m->stream));
-    if (words[CW_ERROR]) return set_error(m, LOM_ERR_RANGE, "carve: coordinate / voxel_size out of range or not finite");
+    if (words[CW_ERROR]) return fail(m, LOM_ERR_RANGE, "carve: coordinate / voxel_size out of range or not finite");
     size_t live = 0;
     for (uint32_t s = 0; s < nv; s++) {
         if (!count[s]) continue;  // (the export skips empty slabs)
@@ -1189,12 +1197,12 @@ static int downsample_core(lom_map *m, float voxel_size, const char *dx, const c
     if ((rc = ensure_rest(m, m->scr[S_DS_HEAD], (size_t)m->cap * 4, 0xFF)) != LOM_OK) return rc;
     if ((rc = scratch(m, S_ITEMS, (size_t)N * 3, &oxyz)) != LOM_OK) return rc;   // compacted xyz
     if ((rc = scratch(m, S_PT_POS, (size_t)N * 3, &onrm)) != LOM_OK) return rc;  // compacted normals
-    head = (uint32_t *)m->scr[S_DS_HEAD].p;
+    head = m->scr[S_DS_HEAD].as<uint32_t>();
     if (!want_normals) onrm = nullptr;
     const uint32_t seq = ++m->call_seq;
     const MapView v = view_of(m);
     const dim3 g(blocks_for(N)), b(kThreads);
-    if (n_dev && !one_pass) return set_error(m, LOM_ERR_ARG, "device-side point count: at most 262144 points");
+    if (n_dev && !one_pass) return fail(m, LOM_ERR_ARG, "device-side point count: at most 262144 points");
     hipLaunchKernelGGL(k_ds_claim, g, b, 0, m->stream, m->d_table, v.mask, v.shift, dx, stride, N, n_dev, voxel_size,
                        pt_slot, head, seq, d_word(m, 5));
     if (one_pass) {
@@ -1222,11 +1230,11 @@ static int downsample_core(lom_map *m, float voxel_size, const char *dx, const c
     if (m->h_flags[3] == seq) {
         // the in-kernel scan gave up: every kept point has still put its slot and head word back to rest, so the
         // workspace is empty again; same call through the flag / scan / write kernels, which wait for nobody
-        if (n_dev) return set_error(m, LOM_ERR_HIP, "a workgroup timed out waiting for the others of its grid");
+        if (n_dev) return fail(m, LOM_ERR_HIP, "a workgroup timed out waiting for the others of its grid");
         m->grid_redos++;
         return downsample_core(m, voxel_size, dx, dn, N, stride, want_normals, true, nullptr, true);
     }
-    if (m->h_flags[1] == seq) return set_error(m, LOM_ERR_RANGE, "coordinate / voxel_size out of range or not finite");
+    if (m->h_flags[1] == seq) return fail(m, LOM_ERR_RANGE, "coordinate / voxel_size out of range or not finite");
     return LOM_OK;
 }
 
@@ -1268,8 +1276,8 @@ int64_t lom_voxel_downsample_device(lom_map *ws, float voxel_size, const float *
     if ((rc = downsample_core(m, voxel_size, (const char *)d_xyz, (const char *)d_nrm, (uint32_t)n, stride,
                               d_nrm_out != nullptr, true)) != LOM_OK)
         return rc;
-    *d_xyz_out = (const float *)m->scr[S_ITEMS].p;
-    if (d_nrm_out) *d_nrm_out = (const float *)m->scr[S_PT_POS].p;
+    *d_xyz_out = m->scr[S_ITEMS].as<const float>();
+    if (d_nrm_out) *d_nrm_out = m->scr[S_PT_POS].as<const float>();
     return (int64_t)m->h_flags[0];
 }
 
@@ -1294,8 +1302,8 @@ int lom_voxel_downsample_device_nowait(lom_map *ws, float voxel_size, const floa
     if ((rc = downsample_core(m, voxel_size, (const char *)d_xyz, (const char *)d_nrm, (uint32_t)n_bound, stride,
                               d_nrm_out != nullptr, false, d_n)) != LOM_OK)
         return rc;
-    *d_xyz_out = (const float *)m->scr[S_ITEMS].p;
-    if (d_nrm_out) *d_nrm_out = (const float *)m->scr[S_PT_POS].p;
+    *d_xyz_out = m->scr[S_ITEMS].as<const float>();
+    if (d_nrm_out) *d_nrm_out = m->scr[S_PT_POS].as<const float>();
     return LOM_OK;
 }
 
@@ -1377,11 +1385,11 @@ int lom_transform_points_device(lom_map *m, const lom_pose *pose, const float *d
     rotation_matrix(pose->q, A.R);
     for (int i = 0; i < 3; i++) A.t[i] = pose->t[i];
     hipLaunchKernelGGL(k_transform, dim3(blocks_for((uint32_t)n)), dim3(kThreads), 0, m->stream, (const char *)d_xyz,
-                       (const char *)d_nrm, stride, (uint32_t)n, A, (float *)m->scr[S_IN_XYZ].p,
-                       with_n ? (float *)m->scr[S_IN_NRM].p : (float *)nullptr);
+                       (const char *)d_nrm, stride, (uint32_t)n, A, m->scr[S_IN_XYZ].as<float>(),
+                       with_n ? m->scr[S_IN_NRM].as<float>() : (float *)nullptr);
     LOM_HIP(m, hipGetLastError());
-    *d_xyz_out = (const float *)m->scr[S_IN_XYZ].p;
-    if (with_n) *d_nrm_out = (const float *)m->scr[S_IN_NRM].p;
+    *d_xyz_out = m->scr[S_IN_XYZ].as<const float>();
+    if (with_n) *d_nrm_out = m->scr[S_IN_NRM].as<const float>();
     return LOM_OK;
 }
 
@@ -1408,8 +1416,8 @@ int64_t lom_map_export(lom_map *m, int mode, float *xyz_out, float *nrm_out, siz
     if (want_n && (rc = ensure(m, m->scr[S_IN_NRM], total * 12)) != LOM_OK) return rc;
     const size_t work = (size_t)nv * m->K;
     hipLaunchKernelGGL(k_export_write, dim3(blocks_for(work)), dim3(kThreads), 0, m->stream, off, m->slabs.count, nv,
-                       m->K, mode, m->slabs.pts, m->slabs.nrm, (float *)m->scr[S_IN_XYZ].p,
-                       want_n ? (float *)m->scr[S_IN_NRM].p : (float *)nullptr);
+                       m->K, mode, m->slabs.pts, m->slabs.nrm, m->scr[S_IN_XYZ].as<float>(),
+                       want_n ? m->scr[S_IN_NRM].as<float>() : (float *)nullptr);
     LOM_HIP(m, hipGetLastError());
     const size_t take = std::min(total, cap);
     LOM_HIP(m, hipMemcpyAsync(xyz_out, m->scr[S_IN_XYZ].p, take * 12, hipMemcpyDeviceToHost, m->stream));

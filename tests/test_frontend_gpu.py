@@ -117,3 +117,22 @@ def test_frontend_64_beam_frame(lom, oracle):
     assert got["deskewed"].tobytes() == desk.tobytes()
     assert got["grid"] == grid and got["planar_points"] == n_planar
     assert got["xyz"].tobytes() == fx.tobytes() and got["normals"].tobytes() == fn.tobytes()
+
+
+def test_frontend_grows_between_frames(lom, oracle):
+    """One front end across a reallocation of its per-frame arrays: 9 points (room for 9 + 4 + 4096 = 4109), then the
+    whole frame (beyond that: every array is freed and allocated anew, the cell table put at rest again), then the 9
+    points again -- each bit-equal to the oracle's chain."""
+    fe = lom.FrontEnd()
+    base = synth.make_sequence_frame(2)
+    assert len(base) > 4109
+    small = np.ascontiguousarray(base[:9])
+    start, end = POSES[1]
+    want = {id(f): _oracle_chain(oracle, f, start, end, 4.0, 80.0) for f in (small, base)}
+    for i, f in enumerate((small, base, small)):
+        desk, n_planar, fx, fn, grid = want[id(f)]
+        got = fe.process(f, lom.Pose3D(*start), lom.Pose3D(*end), 4.0, 80.0)
+        assert not got["redo_on_host"], i
+        assert got["deskewed"].tobytes() == desk.tobytes(), i
+        assert got["grid"] == grid and got["planar_points"] == n_planar, i
+        assert got["xyz"].tobytes() == fx.tobytes() and got["normals"].tobytes() == fn.tobytes(), i

@@ -126,6 +126,23 @@ def test_give_up_is_redone_by_the_multi_launch_form(lom, room, from_block):
     assert again[0].tobytes() == want[0].tobytes()
 
 
+def test_details_across_a_growing_frame(lom, room):
+    """One front end over frames of 64, 4000 and 64 points with details: the detail buffer is freed and allocated anew
+    for the second; every frame gives the bytes of a front end that has seen nothing else."""
+    xyz, _, _ = room
+    assert len(xyz) >= 4000
+    f = lom.FrontEnd()
+    for i, n in enumerate((64, 4000, 64)):
+        frame = R.cloud(xyz[:n])
+        got = lom.classifyNeighbourhood(frame, R.ROOM_PARAMS, details=True, frontend=f)
+        want = lom.classifyNeighbourhood(frame, R.ROOM_PARAMS, details=True, frontend=lom.FrontEnd())
+        assert got[2].shape == (n,), i
+        for a, b in zip(want, got):
+            assert a.tobytes() == b.tobytes(), i
+        if n == 4000:
+            assert (got[2]["planar"] != 0).any()  # the comparison is of something
+
+
 FRAME_PARAMS = R.params(radius=1.0, index_cap=64, min_neighbours=8, max_variation=0.01, min_spread=0.02)
 
 
