@@ -9,7 +9,7 @@
 //   k_fe_planar    normals from the previous ring (:105-165), range filter, and the compaction of the
 //                  surviving planar points in ray-major order (one in-kernel scan, grid_scan.hpp)
 //
-// Bit-exactness against the host code of odometry.cpp (= oracle/pipeline.c): every f32 / f64 operation
+// Bit-exactness against the host code of host_stages.cpp (= oracle/pipeline.c): every f32 / f64 operation
 // below is the host's, in the host's order (-ffp-contract=off).  The three library calls are handled
 // like this: acos / sin of the FRAME's rotation angle are computed once on the host (glibc); the
 // per-point sin((1 - t) theta), sin(t theta) use glibc's own sinf algorithm restated below

@@ -1,7 +1,7 @@
 """Independent restatement, in numpy, of the stages LidarOdometry::processCloud runs before the align -- written
 straight from the reference text (src/utils/point_time_normalize.h:15-39, src/utils/cloud_transform.h:15-40,
 src/utils/cloud_classifier.h:19-168, src/utils/range_filter.h:13-28), NOT from oracle/pipeline.c or the product's
-csrc/odometry.cpp (those two share their text; a misreading common to both passes every oracle-vs-product test).
+csrc/host_stages.cpp (those two share their text; a misreading common to both passes every oracle-vs-product test).
 Test infrastructure: tests/golden/make_fixtures.py runs it in the build container to write the golden planar-point
 indices and normals of three seeded frames; tests/test_frontend_restatement.py compares oracle, host stages and
 device front end with those.

@@ -1,6 +1,6 @@
 """Rows f2 / f3 (deskew, classifier, filters) against an INDEPENDENT restatement of the reference text.
 
-oracle/pipeline.c and the product's host stages (csrc/odometry.cpp) share their text, and the device front end is
+oracle/pipeline.c and the product's host stages (csrc/host_stages.cpp) share their text, and the device front end is
 compared with that same oracle: a misreading of src/utils/*.h common to both would pass every such test.
 tests/restate_frontend.py restates the four stages in numpy straight from the reference's headers; its output for
 three seeded frames is pinned by digests in tests/golden/frontend_restated.npz (make_frontend_fixtures.py).  Here:
