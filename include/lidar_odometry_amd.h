@@ -516,8 +516,11 @@ typedef enum {
                                                     (counted by LOM_COUNTER_GRID_REDOS) */
     LOM_OPT_TEST_BATCH_ROUND_MAX = 107,          /* r > 0: a round of lom_match_align_batch holds at most r problems (0 = as
                                                     many as are resident together): lets the tests force several rounds */
-    LOM_OPT_TEST_QUALITY_ROUND_MAX = 108         /* r > 0: a round of lom_match_quality_batch* holds at most r problems
+    LOM_OPT_TEST_QUALITY_ROUND_MAX = 108,        /* r > 0: a round of lom_match_quality_batch* holds at most r problems
                                                     (0 = as many as its byte budget admits) */
+    LOM_OPT_TEST_VOTE_SLICE_MAX = 109            /* s in 1 .. 64: a launch of the scan votes (lom_map_carve_scans,
+                                                    lom_map_scan_votes) holds at most s scans (0 = 64, one bit each of
+                                                    a voxel's mask) */
 } lom_option;
 int lom_map_set_option(lom_map *m, int option, int64_t value);
 /* diagnostics: LOM_COUNTER_GRID_REDOS = calls of this handle redone with the multi-launch scan after an
@@ -1221,6 +1224,70 @@ int lom_map_assemble(lom_map *m, lom_archive *a, const int64_t *ids, const lom_g
 typedef int(lom_pose64_rotation_fn)(const lom_graph_pose *pose, double R_rowmajor[9]);
 lom_pose64_rotation_fn lom_graph_pose_rotation_matrix;
 
+/* ---- scan votes: moving objects out of an assembled map, scan by scan (not in the reference) ---------------------------
+ * A map assembled from K archived scans holds everything that ever moved through it, and lom_map_carve_rays cannot
+ * remove it: in such a map every voxel was hit by the scan that put it there.  Here every scan votes once per voxel --
+ * "I saw through it" or "I saw it" -- and a rule on the two counts decides.  The definition, operation by operation
+ * (tests/vote_ref.py restates it in numpy f64 and the results are compared bit for bit):
+ *
+ * Inputs: a map with voxel size v (f32), an archive, and ids[k], poses[k] for k = 0 .. count-1 exactly as
+ * lom_map_assemble takes them, and the parameters below.  There are no defaults; margin < 0, min_range <= 0,
+ * max_range <= min_range, clearance < 0, a non-finite value or min_free_scans == 0 is LOM_ERR_ARG.
+ *
+ * Per scan k:
+ *  1. Points and normals.  The endpoint p'_i and the normal n'_i of every point of the scan are the f32 results of the
+ *     assembly's transform ("Rotation", "Point" and "Normal" of the section above, byte for byte).  There is no cull:
+ *     every point of the scan is a ray.
+ *  2. Origin.  o_k = the pose's translation, each component rounded to f32.
+ *  3. Hits.  As the carve: every endpoint, whatever its ray's length, marks the live voxel that contains it by the
+ *     insert's index rule: hit_k[voxel] = 1.
+ *  4. Walk.  The walk of "ray carving" with O = o_k and P = p'_i -- the same start cell, plane rule, tie order,
+ *     recomputed t_a, step bound and range error -- but for t_end.  With N = n'_i, all f64 from the f32 inputs, every
+ *     operation rounded on its own:
+ *       c     = |Nx Dx + (Ny Dy + Nz Dz)| / L
+ *       reach = min(L, max_range) - margin
+ *       plane = L - clearance / c   when clearance > 0, else plane = reach
+ *       t_end = (plane < reach ? plane : reach) / L
+ *     The ray is walked iff L >= min_range and t_end > 0.  plane is where the ray comes within `clearance` of the plane
+ *     through its endpoint with its endpoint's normal: a ray that grazes a surface stops before it runs inside that
+ *     surface's layer of voxels.  With clearance > 0, a zero normal or a ray parallel to its plane has c == 0, plane =
+ *     -inf, and is not walked; a NaN normal leaves reach (the comparison is false).
+ *     cross_k[voxel] = 1 iff some walked ray of scan k visited the live voxel.
+ *  5. Votes.  seen[voxel] = sum over k of hit_k; free[voxel] = sum over k of (cross_k && !hit_k).  Both count scans, so
+ *     the density of points does not enter.  An id that appears twice votes twice, each time with its own pose.
+ *  6. Decision.  A live voxel is erased iff free >= min_free_scans and (u64)free >= (u64)free_per_seen * seen.  Erasing
+ *     is the carve's erase: in place, or compaction from a quarter of the slabs on (LOM_DENSE_CLEANUP=1: always); a later
+ *     insert creates the voxel anew at the end of the creation order.
+ *  7. Errors.  A non-finite origin or endpoint, or one whose voxel index leaves (-2^20, 2^20), or a walk that leaves
+ *     that range, in any scan: LOM_ERR_RANGE, and the map is unchanged.  Ids, poses, devices and a scan context are
+ *     refused as lom_map_assemble refuses them, before any launch (LOM_ERR_ARG).  count == 0 or only empty scans:
+ *     LOM_OK, nothing changes.
+ * The result is a pure function of the inputs: integer sums only, no order, and no dependence on how the scans are
+ * grouped into launches (64 at a time; LOM_OPT_TEST_VOTE_SLICE_MAX).  The call holds the archive's lock, counts as a
+ * change of the map, and a cleanup scan armed with lom_map_radius_cleanup_after_align is never taken across it.  The
+ * error text is the map's (lom_last_error). */
+typedef struct {
+    float margin, min_range, max_range; /* as lom_carve_params: >= 0, > 0, > min_range */
+    float clearance;         /* m, >= 0: the walk also ends where the ray is this close to its endpoint's plane; 0 = no such stop */
+    uint32_t min_free_scans; /* >= 1 */
+    uint32_t free_per_seen;  /* >= 0: free votes needed per seen vote */
+} lom_vote_params;
+typedef struct {
+    uint64_t scans;                     /* count */
+    uint64_t rays_walked, rays_skipped; /* rays_walked + rays_skipped == the sum of the scans' sizes */
+    uint64_t cells_visited;             /* step 1 of the walk's loop, summed over all rays */
+    uint32_t voxels_free;               /* live voxels with free >= 1 */
+    uint32_t voxels_protected;          /* live voxels with free >= min_free_scans that the ratio kept */
+    uint32_t voxels_erased;
+} lom_vote_stats;
+/* On an error the stats are all zero. */
+int lom_map_carve_scans(lom_map *m, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses, size_t count,
+                        const lom_vote_params *p, lom_vote_stats *stats_or_null);
+/* erases nothing: free / seen per live voxel in lom_map_export's order.  Returns the number of live voxels; writes at
+ * most `cap` entries; either output may be NULL.  Neither the map's change count nor an armed cleanup scan is touched. */
+int64_t lom_map_scan_votes(lom_map *m, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses, size_t count,
+                           const lom_vote_params *p, uint32_t *free_out, uint32_t *seen_out, size_t cap);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;
@@ -1322,6 +1389,14 @@ int lom_odometry_set_classifier(lom_odometry *o, int kind, const lom_neighbourho
  * LOM_ERR_STATE while none has run. */
 int lom_odometry_set_carve(lom_odometry *o, const lom_carve_params *p_or_null);
 int lom_odometry_get_carve_stats(const lom_odometry *o, lom_carve_stats *out);
+/* Scan votes in lom_odometry_rebuild_keyframe (see "scan votes" above).  NULL, the default: not one launch or byte of a
+ * rebuild changes.  With parameters set, the rebuild runs lom_map_carve_scans(keyframe, a, ids, poses, count, p) right
+ * after its step 4, so the movers that the archived update clouds still hold do not come back; a failure is handled as
+ * the assembly's failure is (its status is returned, the poses stay, the keyframe is left cleared).  voxels_after and
+ * points_stored_after of the rebuild's stats then describe the keyframe behind the votes.
+ * lom_odometry_get_rebuild_vote_stats: the stats of the last rebuild's votes, LOM_ERR_STATE before one ran. */
+int lom_odometry_set_rebuild_votes(lom_odometry *o, const lom_vote_params *p_or_null);
+int lom_odometry_get_rebuild_vote_stats(const lom_odometry *o, lom_vote_stats *out);
 int64_t lom_odometry_debug_counter(const lom_odometry *o, int which); /* LOM_COUNTER_GRID_REDOS: all its handles + frames redone */
 /* test hook (teacher-forced parity tests): overwrite previous_transform_ / current_transform_
  * (lidar_odometry.h:84-85); the keyframe itself can be replaced through lom_odometry_keyframe() */

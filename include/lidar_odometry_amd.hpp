@@ -254,6 +254,13 @@ public:
                                  sizeof(PointXYZ), &params, &st));
         return st;
     }
+    // not in the reference: scan votes ("scan votes" in lidar_odometry_amd.h) -- the scans `ids` of the archive at the
+    // f64 `poses` vote on this map's voxels, seen or seen through, and the voxels the rule of `params` condemns are erased
+    inline lom_vote_stats carveScans(ScanArchive &archive, const std::vector<int64_t> &ids,
+                                     const std::vector<lom_graph_pose> &poses, const lom_vote_params &params);
+    // ... erases nothing: free / seen per live voxel in the export's order
+    inline void scanVotes(ScanArchive &archive, const std::vector<int64_t> &ids, const std::vector<lom_graph_pose> &poses,
+                          const lom_vote_params &params, std::vector<uint32_t> &free_out, std::vector<uint32_t> &seen_out);
 
     size_t size() const
     {
@@ -891,6 +898,32 @@ inline lom_assemble_stats VoxelGrid::assemble(ScanArchive &archive, const std::v
     return st;
 }
 
+using VoteParams = lom_vote_params;  // {margin, min_range, max_range, clearance, min_free_scans, free_per_seen}
+using VoteStats = lom_vote_stats;
+
+inline lom_vote_stats VoxelGrid::carveScans(ScanArchive &archive, const std::vector<int64_t> &ids,
+                                            const std::vector<lom_graph_pose> &poses, const lom_vote_params &params)
+{
+    if (ids.size() != poses.size()) throw Error(LOM_ERR_ARG, "VoxelGrid::carveScans: one pose per id");
+    lom_vote_stats st;
+    check(lom_map_carve_scans(h_, archive.handle(), ids.data(), poses.data(), ids.size(), &params, &st));
+    return st;
+}
+
+inline void VoxelGrid::scanVotes(ScanArchive &archive, const std::vector<int64_t> &ids,
+                                 const std::vector<lom_graph_pose> &poses, const lom_vote_params &params,
+                                 std::vector<uint32_t> &free_out, std::vector<uint32_t> &seen_out)
+{
+    if (ids.size() != poses.size()) throw Error(LOM_ERR_ARG, "VoxelGrid::scanVotes: one pose per id");
+    const size_t nv = size();
+    free_out.assign(nv, 0u);
+    seen_out.assign(nv, 0u);
+    const int64_t got = lom_map_scan_votes(h_, archive.handle(), ids.data(), poses.data(), ids.size(), &params,
+                                           free_out.data(), seen_out.data(), nv);
+    if (got < 0) throw Error((int)got, lom_last_error(h_));
+    if ((size_t)got != nv) throw Error(LOM_ERR_STATE, "VoxelGrid::scanVotes: voxel count changed");
+}
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)
@@ -978,6 +1011,19 @@ public:
     {
         const int rc = lom_odometry_get_carve_stats(h_, &out);
         if (rc != LOM_OK && rc != LOM_ERR_STATE) throw Error(rc, lom_odometry_last_error(h_));
+        return rc == LOM_OK;
+    }
+    // scan votes in rebuildKeyframe (lom_odometry_set_rebuild_votes): nullptr, the default, changes nothing
+    void setRebuildVotes(const lom_vote_params *params)
+    {
+        const int rc = lom_odometry_set_rebuild_votes(h_, params);
+        if (rc != LOM_OK) throw Error(rc, "lom_odometry_set_rebuild_votes");
+    }
+    // the last rebuild's votes; false while none has run
+    bool rebuildVoteStats(lom_vote_stats &out) const
+    {
+        const int rc = lom_odometry_get_rebuild_vote_stats(h_, &out);
+        if (rc != LOM_OK && rc != LOM_ERR_STATE) throw Error(rc, "lom_odometry_get_rebuild_vote_stats");
         return rc == LOM_OK;
     }
     // LOM_OPT_QUALITY_REPORT: every frame that aligns also gets a quality report at the pose the align returned

@@ -15,7 +15,7 @@ from . import capi
 from .capi import LomError  # noqa: F401
 
 __all__ = ["Pose3D", "VoxelGrid", "CloudMatcher", "ScanContext", "LidarOdometry", "transform_points", "pointTimeNormalize",
-           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "classifyNeighbourhood", "neighbourhoodParams", "carveParams", "LomError", "capi", "quality_report",
+           "transformNonRigid", "rangeFilter", "classify", "loadPCDFile", "fromROSMsg", "toROSMsg", "estimateNormals", "FrontEnd", "classifyNeighbourhood", "neighbourhoodParams", "carveParams", "voteParams", "LomError", "capi", "quality_report",
            "quality_report_batch", "pose_lattice", "PoseGraph", "graphParams", "graph_information_from_quality"]
 
 
@@ -226,6 +226,30 @@ class VoxelGrid:
         if got != nv:
             raise LomError(capi.ERR_STATE, "lom_map_carve_counts: voxel count changed")
         return cross, hit
+
+    def carveScans(self, archive, ids, poses, params):
+        """lom_map_carve_scans ("scan votes" in the header; not in the reference): the scans `ids` of the ScanArchive at
+        `poses` vote on this map's voxels -- seen, or seen through -- and the voxels with at least params.min_free_scans
+        free votes and free >= params.free_per_seen * seen are erased.  Returns capi.VoteStats as a dict."""
+        p = voteParams(params)
+        ids, g = _assemble_args(ids, poses)
+        st = capi.VoteStats()
+        capi.check(capi.lib().lom_map_carve_scans(self._h, archive.handle, ids.ctypes.data, g.ctypes.data, len(ids),
+                                                  C.byref(p), C.byref(st)), self._h)
+        return st.asdict()
+
+    def scanVotes(self, archive, ids, poses, params):
+        """lom_map_scan_votes: what carveScans would decide on, nothing erased -- (free uint32, seen uint32) per live
+        voxel in the export's order."""
+        p = voteParams(params)
+        ids, g = _assemble_args(ids, poses)
+        nv = self.size()
+        free, seen = np.zeros(nv, np.uint32), np.zeros(nv, np.uint32)
+        got = capi.check(capi.lib().lom_map_scan_votes(self._h, archive.handle, ids.ctypes.data, g.ctypes.data, len(ids),
+                                                       C.byref(p), free.ctypes.data, seen.ctypes.data, nv), self._h)
+        if got != nv:
+            raise LomError(capi.ERR_STATE, "lom_map_scan_votes: voxel count changed")
+        return free, seen
 
     def findMatchingPairs(self, xyz, transform, max_correspondence_distance=0.3):
         """voxel_grid.h:206-234; one entry per source point in source order (index < 0: no match)."""
@@ -727,6 +751,22 @@ def carveParams(params):
     if len(vals) != len(names):
         raise TypeError(f"carve parameters: exactly {names}")
     return capi.CarveParams(*vals)
+
+
+def voteParams(params):
+    """capi.VoteParams from one, from a dict with its six fields, or from a 6-tuple in the struct's order (margin,
+    min_range, max_range, clearance, min_free_scans, free_per_seen).  There are no defaults."""
+    if isinstance(params, capi.VoteParams):
+        return params
+    names = [k for k, _ in capi.VoteParams._fields_]
+    if isinstance(params, dict):
+        if sorted(params) != sorted(names):
+            raise TypeError(f"vote parameters: exactly {names}")
+        return capi.VoteParams(**params)
+    vals = tuple(params)
+    if len(vals) != len(names):
+        raise TypeError(f"vote parameters: exactly {names}")
+    return capi.VoteParams(*vals)
 
 
 def classifyNeighbourhood(points, params, details=False, frontend=None):
@@ -1276,6 +1316,24 @@ class LidarOdometry:
         if rc != 0:
             text = capi.lib().lom_odometry_last_error(self._h)
             raise LomError(int(rc), text.decode() if text else "lom_odometry_get_carve_stats")
+        return st.asdict()
+
+    def setRebuildVotes(self, params=None):
+        """lom_odometry_set_rebuild_votes: with parameters (voteParams), rebuildKeyframe lets the scans vote the movers
+        out of the keyframe it has assembled (VoxelGrid.carveScans); None (the default) changes nothing."""
+        p = voteParams(params) if params is not None else None
+        rc = capi.lib().lom_odometry_set_rebuild_votes(self._h, C.byref(p) if p is not None else None)
+        if rc != 0:
+            raise LomError(int(rc), "lom_odometry_set_rebuild_votes")
+
+    def rebuildVoteStats(self):
+        """The last rebuild's votes (capi.VoteStats as a dict); None while none has run."""
+        st = capi.VoteStats()
+        rc = capi.lib().lom_odometry_get_rebuild_vote_stats(self._h, C.byref(st))
+        if rc == capi.ERR_STATE:
+            return None
+        if rc != 0:
+            raise LomError(int(rc), "lom_odometry_get_rebuild_vote_stats")
         return st.asdict()
 
     def processCloud(self, input_cloud):                   # lidar_odometry.cpp:22-77

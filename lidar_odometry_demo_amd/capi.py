@@ -207,6 +207,25 @@ class AssembleStats(C.Structure):
 assert C.sizeof(AssembleParams) == 16 and C.sizeof(AssembleStats) == 48
 
 
+class VoteParams(C.Structure):
+    """lom_vote_params (no defaults: every field is the caller's)"""
+    _fields_ = [("margin", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float), ("clearance", C.c_float),
+                ("min_free_scans", C.c_uint32), ("free_per_seen", C.c_uint32)]
+
+
+class VoteStats(C.Structure):
+    """lom_vote_stats"""
+    _fields_ = [("scans", C.c_uint64), ("rays_walked", C.c_uint64), ("rays_skipped", C.c_uint64),
+                ("cells_visited", C.c_uint64), ("voxels_free", C.c_uint32), ("voxels_protected", C.c_uint32),
+                ("voxels_erased", C.c_uint32)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(VoteParams) == 24 and C.sizeof(VoteStats) == 48
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -280,6 +299,7 @@ EXPORTED = [
     "lom_archive_device", "lom_archive_wait_event", "lom_archive_add", "lom_archive_add_device", "lom_archive_scan_count",
     "lom_archive_point_count", "lom_archive_scan_size", "lom_archive_get", "lom_map_assemble", "lom_odometry_archive_scan",
     "lom_odometry_rebuild_keyframe",
+    "lom_map_carve_scans", "lom_map_scan_votes", "lom_odometry_set_rebuild_votes", "lom_odometry_get_rebuild_vote_stats",
 ]
 # ... and the one it declares through a function type (the "scan archive and map assembly" section)
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
@@ -290,6 +310,7 @@ OPT_TEST_GIVE_UP_AT_OUTER, OPT_TEST_GRID_GIVE_UP, OPT_TEST_FORCE_HOST_REDO = 100
 OPT_NO_BULK_INSERT, OPT_TEST_BULK_PARTITION_MAX = 7, 106
 OPT_TEST_BATCH_ROUND_MAX = 107
 OPT_TEST_QUALITY_ROUND_MAX = 108
+OPT_TEST_VOTE_SLICE_MAX = 109
 OPT_QUALITY_REPORT = 8
 OPT_REPLAY_FOLD = 9
 OPT_TEST_GRID_GIVE_UP_MATCHING_DS, OPT_TEST_GRID_GIVE_UP_UPDATE_DS, OPT_TEST_GRID_GIVE_UP_KEYFRAME = 103, 104, 105
@@ -616,6 +637,11 @@ def lib():
     L.lom_graph_pose_rotation_matrix.argtypes = [vp, vp]
     L.lom_odometry_archive_scan.argtypes = [vp, vp, C.POINTER(C.c_int64)]
     L.lom_odometry_rebuild_keyframe.argtypes = [vp, vp, vp, vp, C.c_size_t, pp, C.POINTER(AssembleStats)]
+    L.lom_map_carve_scans.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(VoteParams), C.POINTER(VoteStats)]
+    L.lom_map_scan_votes.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(VoteParams), vp, vp, C.c_size_t]
+    L.lom_map_scan_votes.restype = C.c_int64
+    L.lom_odometry_set_rebuild_votes.argtypes = [vp, C.POINTER(VoteParams)]
+    L.lom_odometry_get_rebuild_vote_stats.argtypes = [vp, C.POINTER(VoteStats)]
     _lib = L
     return L
 

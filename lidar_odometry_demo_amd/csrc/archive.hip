@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "archive_internal.hpp"
 #include "assemble_host.hpp"
 #include "k_assemble.hpp"
 #include "lom_internal.hpp"
@@ -18,26 +19,7 @@
 using namespace lom;
 using assemble::ScanEntry;
 
-// The archive owns its stream and every buffer below; calls on one archive are serialised by `lock`.
-struct lom_archive : DeviceHandle {
-    std::mutex lock;
-    // the table (host) and the clouds (device): scan k is points [offset, offset + n) of both arrays, 12 bytes each
-    std::vector<ScanEntry> table;
-    uint64_t points = 0, cap_points = 0;
-    DeviceBuf xyz, nrm;
-    // staging of the assembly, reused call after call and sized by the call: descriptors, the transformed cloud, the
-    // [scan][block] matrix of kept counts and its prefix, the compacted cloud
-    DeviceBuf desc, stage_xyz, stage_nrm, counts, offsets, out_xyz, out_nrm;
-    PinnedBuf h_desc;  // the descriptors on their way in
-    PinnedBuf h_word;  // the kept total on its way out
-    // recorded on the archive's stream behind the kernels, for the map's stream to wait on before the insert; recorded on
-    // the map's stream behind the insert, for the archive's stream to wait on before it overwrites the staging
-    hipEvent_t ready_ev = nullptr, done_ev = nullptr;
-    bool done_recorded = false;
-
-    float *d_xyz() const { return xyz.as<float>(); }
-    float *d_nrm() const { return nrm.as<float>(); }
-};
+// (the handle itself: archive_internal.hpp)
 
 namespace {
 

@@ -436,6 +436,10 @@ int lom_map_set_option(lom_map *m, int option, int64_t value)
         if (value < 0 || value > (1 << 20)) return LOM_ERR_ARG;
         m->qualb.test_round_max = (int)value;
         return LOM_OK;
+    case LOM_OPT_TEST_VOTE_SLICE_MAX:
+        if (value < 0 || value > 64) return LOM_ERR_ARG;
+        m->vote.test_slice_max = (uint32_t)value;
+        return LOM_OK;
     default: return fail(m, LOM_ERR_ARG, "unknown option");
     }
 }

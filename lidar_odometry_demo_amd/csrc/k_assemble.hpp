@@ -13,14 +13,11 @@
 #include <cstdint>
 
 #include "assemble_host.hpp"
+#include "k_asm_scan.hpp"
 
 namespace lom {
 
-using assemble::AsmScan;
-using assemble::kAsmThreads;
-
-typedef const __attribute__((address_space(4))) AsmScan *ConstAsm;  // read with scalar loads, like kernel arguments
-
+// (AsmScan, kAsmThreads, ConstAsm: k_asm_scan.hpp)
 constexpr uint32_t kAsmWaves = kAsmThreads / 64;
 constexpr uint32_t kAsmOffsetThreads = 1024;
 

@@ -154,6 +154,14 @@ struct QualityBatchBufs {
     int test_round_max = 0;  // LOM_OPT_TEST_QUALITY_ROUND_MAX: problems per round at most (0: by the byte budget)
 };
 
+// ... of the scan votes (lom_map_carve_scans / lom_map_scan_votes, vote.hip): two u64 masks and two u32 counts per slab,
+// at rest (zero) between calls -- whoever dirties a word puts it back --, the status words (k_vote.hpp, VW_*) and the
+// call's scan descriptors; the erase itself uses the map-maintenance scratch as the carve does (erase_begin below)
+struct VoteBufs {
+    DeviceBuf hitmask, crossmask, free_votes, seen_votes, words, desc;
+    uint32_t test_slice_max = 0;  // LOM_OPT_TEST_VOTE_SLICE_MAX: scans per launch at most (0: 64)
+};
+
 // one set of slab arrays (creation order), allocated and freed together (voxel_map.hip)
 struct Slabs {
     unsigned long long *key = nullptr;  // [cap]
@@ -315,6 +323,7 @@ struct lom_map : lom::DeviceHandle {
     lom::BatchAlignBufs batch;
     lom::QualityBufs qual;
     lom::QualityBatchBufs qualb;
+    lom::VoteBufs vote;
     // lom_match_align_multi: recorded on this handle's stream -- as a problem map, for the runner to wait on before the
     // chain; as the runner, after the chain, for the problem maps to wait on (created once, timing disabled)
     hipEvent_t multi_ev = nullptr;
@@ -373,6 +382,18 @@ int map_init(lom_map *m, size_t capacity_hint);  // voxel_map.hip: status words 
 int settle_map(lom_map *map);  // voxel_map.hip: settle a pending insert and the voxel count, under the map's settle lock
 void map_free(lom_map *m);     // voxel_map.hip: the table and both slab sets (lom_map_destroy)
 void cleanup_scan_behind_align(lom_map *m);  // voxel_map.hip: see lom_map_radius_cleanup_after_align
+// voxel_map.hip: the erase of the ray carve, for an erase whose decision is made elsewhere (vote.hip), in this order --
+//   map_settle_nvox: a pending insert is settled, m->n_vox is exact;
+//   erase_begin: room for keep / newid / the scan's temporaries of m->n_vox slabs; the call counts as a change of the map
+//     (call_seq, mutations) and a cleanup scan armed behind an align is never taken now; *keep: one word per slab to fill;
+//   erase_rank: newid[] from keep[]; *d_kept: the device word that will hold the number of kept slabs;
+//   erase_finish: n_keep of the m->n_vox slabs stay -- in place, or compaction (erase_unkept).
+int map_settle_nvox(lom_map *m);
+int erase_begin(lom_map *m, uint32_t **keep);
+int erase_rank(lom_map *m, const uint32_t **d_kept);
+int erase_finish(lom_map *m, uint32_t n_keep);
+// voxel_map.hip: n device words in one read-back on the handle's stream (waits for them)
+int gather_words(lom_map *m, const uint32_t *const *ptrs, int n, uint32_t *out);
 
 // RCCL (comm.cpp), loaded lazily with dlopen
 int comm_allgather_sums(lom_map *m, const double *d_send, double *d_recv, int count);

@@ -9,6 +9,7 @@
 
 #include "odometry_internal.hpp"
 #include "pose_math.hpp"
+#include "vote_host.hpp"
 
 using namespace lom;
 
@@ -178,6 +179,20 @@ int lom_odometry_rebuild_keyframe(lom_odometry *o, lom_archive *a, const int64_t
         if (stats) std::memset(stats, 0, sizeof *stats);
         return rc;
     }
+    if (o->votes_on) {  // lom_odometry_set_rebuild_votes: the scans vote on what they have just built
+        lom_vote_stats vs;
+        if ((rc = lom_map_carve_scans(o->keyframe, a, ids, poses, count, &o->votes, &vs)) != LOM_OK) {
+            o->error = lom_last_error(o->keyframe);
+            (void)lom_map_clear(o->keyframe, o->cfg.keyframe_voxel_size);  // as after a failed assembly: left cleared
+            if (stats) std::memset(stats, 0, sizeof *stats);
+            return rc;
+        }
+        o->vote_stats = vs;
+        o->have_vote_stats = true;
+        st.voxels_after -= (int64_t)vs.voxels_erased;
+        const int64_t stored = lom_map_point_count(o->keyframe);
+        if (stored >= 0) st.points_stored_after = stored;
+    }
     o->last.keyframe_voxels = st.voxels_after;
     o->keyframe_has_voxels = st.voxels_after > 0;
     lom_pose inv, corr, prev;  // 5.
@@ -280,6 +295,24 @@ int lom_odometry_get_carve_stats(const lom_odometry *o, lom_carve_stats *out)
     if (rc != LOM_OK) return rc;
     if (!o->have_carve_stats) return LOM_ERR_STATE;
     *out = o->carve_stats;
+    return LOM_OK;
+}
+
+int lom_odometry_set_rebuild_votes(lom_odometry *o, const lom_vote_params *p)
+{
+    // the arguments first, then the state
+    if (p && !lom::vote::params_ok(p)) return LOM_ERR_ARG;
+    if (!o) return LOM_ERR_ARG;
+    o->votes_on = p != nullptr;
+    if (p) o->votes = *p;
+    return LOM_OK;
+}
+
+int lom_odometry_get_rebuild_vote_stats(const lom_odometry *o, lom_vote_stats *out)
+{
+    if (!o || !out) return LOM_ERR_ARG;
+    if (!o->have_vote_stats) return LOM_ERR_STATE;
+    *out = o->vote_stats;
     return LOM_OK;
 }
 

@@ -61,6 +61,10 @@ struct lom_odometry {
     bool carve_on = false, have_carve_stats = false;
     lom_carve_params carve{};
     lom_carve_stats carve_stats{};
+    // lom_odometry_set_rebuild_votes: lom_odometry_rebuild_keyframe votes the movers out of the keyframe it assembled
+    bool votes_on = false, have_vote_stats = false;
+    lom_vote_params votes{};
+    lom_vote_stats vote_stats{};
     std::string deferred_error;
     // lom_odometry_archive_scan: where the last frame left its update cloud in HBM (one of the update workspaces; packed
     // points and normals).  Written where a frame succeeds, host values only.

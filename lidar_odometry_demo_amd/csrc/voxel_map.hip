@@ -1427,3 +1427,37 @@ int64_t lom_map_export(lom_map *m, int mode, float *xyz_out, float *nrm_out, siz
 }
 
 }  // extern "C"
+
+// ---- the carve's erase for a decision made elsewhere (lom_internal.hpp; vote.hip) ---------------------------------------
+namespace lom {
+
+int map_settle_nvox(lom_map *m) { return refresh_nvox(m); }
+
+int erase_begin(lom_map *m, uint32_t **keep)
+{
+    int rc;
+    const uint32_t nv = m->n_vox;
+    *keep = nullptr;
+    if (nv) {
+        uint32_t *newid = nullptr, *scan_tmp = nullptr;
+        if ((rc = scratch(m, S_FLAG, (size_t)nv * 2, keep)) != LOM_OK) return rc;
+        if ((rc = scratch(m, S_RANK, (size_t)nv * 2, &newid)) != LOM_OK) return rc;
+        if ((rc = scratch(m, S_SCAN, scan_tmp_words(nv), &scan_tmp)) != LOM_OK) return rc;
+    }
+    // keep / newid go where a cleanup scan armed behind an align may have left its own: that scan is never taken now
+    m->spec_inflight = false;
+    ++m->call_seq;
+    m->mutations++;
+    return LOM_OK;
+}
+
+int erase_rank(lom_map *m, const uint32_t **d_kept)
+{
+    *d_kept = d_word(m, 4);
+    return scan_exclusive(m, m->scr[S_FLAG].as<uint32_t>(), m->scr[S_RANK].as<uint32_t>(), m->n_vox, d_word(m, 4),
+                          m->scr[S_SCAN].as<uint32_t>());
+}
+
+int erase_finish(lom_map *m, uint32_t n_keep) { return erase_unkept(m, m->n_vox, n_keep); }
+
+}  // namespace lom
