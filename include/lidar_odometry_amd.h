@@ -1288,6 +1288,135 @@ int lom_map_carve_scans(lom_map *m, lom_archive *a, const int64_t *ids, const lo
 int64_t lom_map_scan_votes(lom_map *m, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses, size_t count,
                            const lom_vote_params *p, uint32_t *free_out, uint32_t *seen_out, size_t cap);
 
+/* Scans without normals, for consumers that read points only (the occupancy grid below): a new scan whose normals are
+ * stored as zeros.
+ *   int64_t lom_archive_add_points(lom_archive *a, const float *xyz, size_t n, size_t stride_bytes);
+ *   int64_t lom_archive_add_points_device(lom_archive *a, const float *d_xyz, size_t n, size_t stride_bytes,
+ *                                         void *hip_event_or_null);
+ * Everything else is lom_archive_add / lom_archive_add_device (ids, strides, the finite check of a host cloud, the
+ * event).  Such a scan assembles like any other (its voxels get zero normals); in the scan votes a zero normal with
+ * clearance > 0 has c == 0, plane = -inf, and its ray is not walked (step 4 there) -- it still hits.  Like
+ * lom_graph_pose_rotation_matrix above, the two are declared through their types. */
+typedef int64_t(lom_archive_points_fn)(lom_archive *a, const float *xyz, size_t n, size_t stride_bytes);
+typedef int64_t(lom_archive_points_device_fn)(lom_archive *a, const float *d_xyz, size_t n, size_t stride_bytes,
+                                              void *hip_event_or_null);
+lom_archive_points_fn lom_archive_add_points;
+lom_archive_points_device_fn lom_archive_add_points_device;
+
+/* ---- occupancy grid: free, occupied and unknown cells from posed scans (not in the reference) ------------------------
+ * The map holds surfaces only: "measured empty" and "never looked at" are both a missing voxel.  A planner needs the
+ * difference, per ground cell, in the form of nav_msgs/OccupancyGrid.  Here every scan at its pose votes once per cell
+ * of a dense 2-D grid -- "a ray of mine passed through it" or "a point of mine fell into it" -- and a rule on the two
+ * integer counts classifies.  A handle family of its own beside the map path: nothing is launched unless a caller
+ * creates a grid.  The definition, operation by operation (tests/occupancy_ref.py restates it in numpy f64 and the
+ * results are compared exactly: counts are integer sums of bits, there is no tolerance anywhere):
+ *
+ * Grid.  lom_occupancy_geometry: cell (ix, iy) covers [origin + i r, origin + (i + 1) r) per axis; storage is row-major
+ * with y as the row, iy * width + ix.  The index rule is floor, NOT the map's truncation, in f64 from the f32 values:
+ * floor(((double)X - (double)origin_x) / (double)r).  A value is "in the grid" iff the floored f64 quotient q satisfies
+ * 0 <= q < width (resp. height), compared before any integer conversion.  r > 0 and finite, 1 <= width, height <= 16384,
+ * a finite origin; anything else is LOM_ERR_ARG.
+ *
+ * Ray parameters.  lom_occupancy_ray_params, no defaults: z_lo < 0 < z_hi (the height band relative to the scan
+ * origin's z, in the grid's frame), margin >= 0, min_range > 0, max_range > min_range, all finite, and
+ * max_range / resolution <= 2^20; anything else is LOM_ERR_ARG.
+ *
+ * Per scan k (pose = a lom_graph_pose, cloud = n points in the sensor frame), all f64 from f32 inputs, every operation
+ * rounded on its own, no contraction:
+ *  1. Endpoint.  p' is the f32 result of the assembly's "Rotation" and "Point" rules, byte for byte; P is p' widened.
+ *     Normals are never read.
+ *  2. Origin.  O = the pose's translation, each component rounded to f32 and widened.  G = (origin_x, origin_y) widened.
+ *     O2_a = O_a - G_a for a = x, y.  Start cell c_a = floor(O2_a / r).  If |c_a| >= 2^30 on either axis (or it is not
+ *     finite) the whole call is LOM_ERR_RANGE, before any launch, and nothing changes.
+ *  3. Ray.  D = P - O (three components);  L = sqrt(Dx Dx + (Dy Dy + Dz Dz));
+ *       t_band = Dz > 0 ? z_hi / Dz : (Dz < 0 ? z_lo / Dz : +inf)
+ *       reach  = (L < max_range ? L : max_range) - margin
+ *       q      = reach / L
+ *       t_end  = q < t_band ? q : t_band
+ *     The ray is walked iff L >= min_range and t_end > 0.
+ *  4. Hit.  The endpoint is a hit iff L >= min_range, L <= max_range, z_lo <= Dz <= z_hi and its cell
+ *     floor((P_a - G_a) / r), a = x, y, is in the grid; then hit_k[cell] = 1.  A non-finite endpoint is neither walked
+ *     nor a hit: the comparisons above already give that (a NaN fails them all; an infinite L exceeds max_range and
+ *     makes q, and with it t_end, zero).
+ *  5. Walk (2-D, parameter t along the 3-D ray).  Per axis a = x, y with D_a != 0: s_a = the sign of D_a, the next plane
+ *     b_a = s_a > 0 ? c_a + 1 : c_a, t_a = ((double)b_a r - O2_a) / D_a; with D_a == 0, t_a = +inf.  Loop:
+ *       1. the current cell counts as passed if it is in the grid;
+ *       2. a = the axis with the smaller t_a, ties to x;
+ *       3. if !(t_a <= t_end) stop;
+ *       4. c_a += s_a, and t_a is recomputed from the new c_a -- never incremented.
+ *     A t_a <= 0 (an origin on a plane) simply sorts first.  At most 2 (ceil(max_range / r) + 2) steps can occur, and
+ *     the kernel's loop is bounded by that.  Cells outside the grid count for nothing; an origin outside the grid is
+ *     legal.  pass_k[cell] = 1 iff some walked ray of scan k visited the cell.
+ *  6. Votes.  seen[cell] += hit_k;  free[cell] += pass_k && !hit_k.  Both are u32 and count scans, not rays.  An id given
+ *     twice votes twice.  Counts accumulate over calls until lom_occupancy_clear.
+ *  7. Classification.  lom_occupancy_rule with min_free_scans >= 1 and min_seen_scans >= 1 (else LOM_ERR_ARG):
+ *     LOM_OCC_FREE (0) iff free >= min_free_scans and (u64)free >= (u64)free_per_seen * seen -- the votes' erase rule;
+ *     else LOM_OCC_OCCUPIED (100) iff seen >= min_seen_scans; else LOM_OCC_UNKNOWN (-1).  int8, row-major: the values of
+ *     nav_msgs/OccupancyGrid.
+ * The result is a pure function of the inputs: it does not depend on the order of scans, rays or calls, on how scans are
+ * grouped into launches (LOM_OCC_OPT_TEST_SLICE_MAX), or on any kernel tuning (LOM_OCC_OPT_TEST_WINDOW).
+ *
+ * lom_occupancy_integrate takes K archived scans exactly as lom_map_assemble takes them; ids, poses and the device are
+ * refused before any launch the same way (LOM_ERR_ARG).  The call holds the archive's lock, and the archive's stream and
+ * the grid's are ordered by events in both directions.  The _cloud forms integrate one scan that is not in an archive:
+ * records of stride_bytes (>= 12, a multiple of 4) that begin with x, y, z, in host memory, or in HBM behind
+ * hip_event_or_null.  count == 0 or n == 0 is LOM_OK and changes nothing.  Stats: scans = count; rays_walked +
+ * rays_skipped = the sum of the scans' sizes; endpoints_marked = the rays that are hits; cells_visited = step 1 of the
+ * walk's loop summed over all rays, in the grid or not.  All zero on an error.  Every call returns with its work done.
+ * Calls on one grid are the caller's to serialise.  The error text is the grid's (lom_occupancy_last_error). */
+typedef struct lom_occupancy lom_occupancy;
+typedef struct {
+    float resolution;         /* m per cell */
+    float origin_x, origin_y; /* the corner of cell (0, 0) */
+    uint32_t width, height;   /* cells along x and along y */
+} lom_occupancy_geometry;
+typedef struct {
+    float z_lo, z_hi; /* < 0 < : the band around the scan origin's z */
+    float margin, min_range, max_range;
+} lom_occupancy_ray_params;
+typedef struct {
+    uint32_t min_free_scans; /* >= 1 */
+    uint32_t free_per_seen;  /* >= 0: free votes needed per seen vote */
+    uint32_t min_seen_scans; /* >= 1 */
+} lom_occupancy_rule;
+typedef struct {
+    uint64_t scans, rays_walked, rays_skipped, endpoints_marked, cells_visited;
+} lom_occupancy_stats;
+typedef struct {
+    uint64_t cells_free, cells_occupied, cells_unknown;
+} lom_occupancy_summary;
+enum { LOM_OCC_FREE = 0, LOM_OCC_OCCUPIED = 100, LOM_OCC_UNKNOWN = -1 };
+enum {
+    LOM_OCC_OPT_TEST_SLICE_MAX = 1, /* s in 1 .. 64: a launch holds at most s scans (0: what the scratch budget admits, 64 at most) */
+    LOM_OCC_OPT_TEST_WINDOW = 2     /* the side of the walk's LDS window in cells: a multiple of 32 up to 512; 0: no window, every
+                                       bit goes to global memory; < 0: the default */
+};
+int lom_occupancy_create(const lom_occupancy_geometry *geometry, int device, lom_occupancy **out);
+void lom_occupancy_destroy(lom_occupancy *g);
+const char *lom_occupancy_last_error(const lom_occupancy *g); /* g == NULL: why the last create on this thread failed */
+int lom_occupancy_clear(lom_occupancy *g);                    /* all counts to zero */
+int lom_occupancy_get_geometry(const lom_occupancy *g, lom_occupancy_geometry *out);
+void *lom_occupancy_stream(lom_occupancy *g); /* hipStream_t */
+int lom_occupancy_device(const lom_occupancy *g);
+int lom_occupancy_wait_event(lom_occupancy *g, void *hip_event);
+int lom_occupancy_set_option(lom_occupancy *g, int option, int64_t value);
+int lom_occupancy_integrate(lom_occupancy *g, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses, size_t count,
+                            const lom_occupancy_ray_params *p, lom_occupancy_stats *stats_or_null);
+int lom_occupancy_integrate_cloud(lom_occupancy *g, const float *xyz, size_t n, size_t stride_bytes,
+                                  const lom_graph_pose *pose, const lom_occupancy_ray_params *p,
+                                  lom_occupancy_stats *stats_or_null);
+int lom_occupancy_integrate_cloud_device(lom_occupancy *g, const float *d_xyz, size_t n, size_t stride_bytes,
+                                         const lom_graph_pose *pose, const lom_occupancy_ray_params *p,
+                                         void *hip_event_or_null, lom_occupancy_stats *stats_or_null);
+/* free / seen per cell, row-major; returns width * height and writes at most `cap` entries; either output may be NULL */
+int64_t lom_occupancy_counts(lom_occupancy *g, uint32_t *free_out, uint32_t *seen_out, size_t cap);
+/* step 7 over the whole grid: at most `cap` cells go to `out` (may be NULL with cap 0); the summary counts all cells */
+int lom_occupancy_classify(lom_occupancy *g, const lom_occupancy_rule *rule, int8_t *out, size_t cap,
+                           lom_occupancy_summary *summary_or_null);
+/* the same, left in HBM: *d_out holds width * height cells, complete on the grid's stream, valid until the next call
+ * on the handle */
+int lom_occupancy_classify_device(lom_occupancy *g, const lom_occupancy_rule *rule, const int8_t **d_out);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;
@@ -1352,6 +1481,18 @@ int lom_odometry_place_descriptor(lom_odometry *o, lom_place_db *db, int add, fl
  * waits for the pending keyframe update and for its own copy, so the next frame cannot overwrite what it reads.
  * LOM_ERR_STATE before the first frame.  Reads only: no pose, counter or map of the odometry is touched. */
 int lom_odometry_archive_scan(lom_odometry *o, lom_archive *a, int64_t *id_out);
+/* The last frame's deskewed cloud -- every point of it, not the planar, down-sampled update cloud -- becomes a new scan of
+ * `a` without normals (lom_archive_add_points): what an occupancy grid rebuilt after a loop closure needs, since the
+ * update clouds miss every obstacle that is not planar.  Read as lom_odometry_place_descriptor reads it (the front end's
+ * copy in HBM behind its done event, or the host copy of a host-stage frame; the same lifetime rule), records of 32
+ * bytes.  `a` must live on the odometry's device.  LOM_ERR_STATE before the first frame.  Reads only. */
+int lom_odometry_archive_deskewed(lom_odometry *o, lom_archive *a, int64_t *id_out);
+/* That cloud at the current pose (lom_odometry_get_pose through lom_graph_pose_from_f32) into an occupancy grid on the
+ * odometry's device: lom_occupancy_integrate_cloud_device behind the front end's done event, or
+ * lom_occupancy_integrate_cloud of the host copy of a host-stage frame; the result is the same either way.
+ * LOM_ERR_STATE before the first frame.  Reads only: no pose, counter or map of the odometry is touched. */
+int lom_odometry_occupancy_scan(lom_odometry *o, lom_occupancy *g, const lom_occupancy_ray_params *p,
+                                lom_occupancy_stats *stats_or_null);
 /* Go on after a loop closure: the keyframe is built again from archived scans at corrected poses.  In this order:
  *  1. the pending keyframe update is waited for (its failure is this call's, and nothing else happens);
  *  2. an armed cleanup behind the align and a pending lom_odometry_hint_next are dropped;

@@ -856,6 +856,12 @@ public:
         return check(lom_archive_add(h_, none ? nullptr : &p->x, none ? nullptr : &p->normal_x, cloud.points.size(),
                                      sizeof(PointNormal)));
     }
+    // a new scan without normals (zeros are stored): what an occupancy grid reads
+    int64_t addPoints(const PointCloud<PointXYZ> &cloud)
+    {
+        const bool none = cloud.points.empty();
+        return check(lom_archive_add_points(h_, none ? nullptr : &cloud.points.data()->x, cloud.points.size(), sizeof(PointXYZ)));
+    }
     PointCloud<PointNormal>::Ptr get(int64_t id) const
     {
         const size_t n = scanSize(id);
@@ -923,6 +929,81 @@ inline void VoxelGrid::scanVotes(ScanArchive &archive, const std::vector<int64_t
     if (got < 0) throw Error((int)got, lom_last_error(h_));
     if ((size_t)got != nv) throw Error(LOM_ERR_STATE, "VoxelGrid::scanVotes: voxel count changed");
 }
+
+// ---- OccupancyGrid (not in the reference) --------------------------------------------
+// A dense 2-D grid of free / seen scan counts on the device: posed scans vote once per cell, and classify() gives the int8
+// values of nav_msgs/OccupancyGrid (0 free, 100 occupied, -1 unknown), row-major with y as the row.  Definitions:
+// lidar_odometry_amd.h ("occupancy grid").
+using OccupancyGeometry = lom_occupancy_geometry;    // {resolution, origin_x, origin_y, width, height}
+using OccupancyRayParams = lom_occupancy_ray_params;  // {z_lo, z_hi, margin, min_range, max_range}
+using OccupancyRule = lom_occupancy_rule;            // {min_free_scans, free_per_seen, min_seen_scans}
+using OccupancyStats = lom_occupancy_stats;
+using OccupancySummary = lom_occupancy_summary;
+
+class OccupancyGrid {
+public:
+    explicit OccupancyGrid(const lom_occupancy_geometry &geometry, int device = 0)
+    {
+        const int rc = lom_occupancy_create(&geometry, device, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_occupancy_last_error(nullptr));
+    }
+    ~OccupancyGrid() { lom_occupancy_destroy(h_); }
+    OccupancyGrid(const OccupancyGrid &) = delete;
+    OccupancyGrid &operator=(const OccupancyGrid &) = delete;
+    lom_occupancy *handle() const { return h_; }
+    lom_occupancy_geometry geometry() const
+    {
+        lom_occupancy_geometry g;
+        check(lom_occupancy_get_geometry(h_, &g));
+        return g;
+    }
+    size_t cells() const
+    {
+        const lom_occupancy_geometry g = geometry();
+        return (size_t)g.width * g.height;
+    }
+    void clear() { check(lom_occupancy_clear(h_)); }
+    // the scans `ids` of the archive at `poses` vote
+    lom_occupancy_stats integrate(ScanArchive &archive, const std::vector<int64_t> &ids, const std::vector<lom_graph_pose> &poses,
+                                  const lom_occupancy_ray_params &params)
+    {
+        if (ids.size() != poses.size()) throw Error(LOM_ERR_ARG, "OccupancyGrid::integrate: one pose per id");
+        lom_occupancy_stats st;
+        check(lom_occupancy_integrate(h_, archive.handle(), ids.data(), poses.data(), ids.size(), &params, &st));
+        return st;
+    }
+    // one scan that is not in an archive
+    lom_occupancy_stats integrateCloud(const PointCloud<PointXYZ> &cloud, const lom_graph_pose &pose,
+                                       const lom_occupancy_ray_params &params)
+    {
+        lom_occupancy_stats st;
+        const bool none = cloud.points.empty();
+        check(lom_occupancy_integrate_cloud(h_, none ? nullptr : &cloud.points.data()->x, cloud.points.size(), sizeof(PointXYZ),
+                                            &pose, &params, &st));
+        return st;
+    }
+    void counts(std::vector<uint32_t> &free_out, std::vector<uint32_t> &seen_out) const
+    {
+        const size_t n = cells();
+        free_out.assign(n, 0u);
+        seen_out.assign(n, 0u);
+        check(lom_occupancy_counts(h_, free_out.data(), seen_out.data(), n));
+    }
+    std::vector<int8_t> classify(const lom_occupancy_rule &rule, lom_occupancy_summary *summary_or_null = nullptr)
+    {
+        std::vector<int8_t> out(cells());
+        check(lom_occupancy_classify(h_, &rule, out.data(), out.size(), summary_or_null));
+        return out;
+    }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_occupancy_last_error(h_));
+        return rc;
+    }
+    lom_occupancy *h_ = nullptr;
+};
 
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
@@ -1058,6 +1139,23 @@ public:
         const int rc = lom_odometry_archive_scan(h_, archive.handle(), &id);
         if (rc != LOM_OK) throw Error(rc, rc == LOM_ERR_STATE ? "no frame yet" : lom_odometry_last_error(h_));
         return id;
+    }
+    // not in the reference: the last frame's deskewed cloud, every point and no normals, becomes a new scan of the archive;
+    // returns its id.  Throws Error(LOM_ERR_STATE) before the first frame.
+    int64_t archiveDeskewed(ScanArchive &archive)
+    {
+        int64_t id = -1;
+        const int rc = lom_odometry_archive_deskewed(h_, archive.handle(), &id);
+        if (rc != LOM_OK) throw Error(rc, rc == LOM_ERR_STATE ? "no frame yet" : lom_odometry_last_error(h_));
+        return id;
+    }
+    // not in the reference: that cloud at the current pose votes on an occupancy grid (lom_odometry_occupancy_scan)
+    lom_occupancy_stats occupancyScan(OccupancyGrid &grid, const lom_occupancy_ray_params &params)
+    {
+        lom_occupancy_stats st;
+        const int rc = lom_odometry_occupancy_scan(h_, grid.handle(), &params, &st);
+        if (rc != LOM_OK) throw Error(rc, rc == LOM_ERR_STATE ? "no frame yet" : lom_occupancy_last_error(grid.handle()));
+        return st;
     }
     // not in the reference: go on after a loop closure -- the keyframe again from the archive's scans `ids` at `poses`,
     // culled at keyframe_cleanup_range around new_current, which becomes the current pose (lom_odometry_rebuild_keyframe)

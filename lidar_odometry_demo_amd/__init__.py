@@ -769,6 +769,32 @@ def voteParams(params):
     return capi.VoteParams(*vals)
 
 
+def _struct_from(cls, params, what):
+    if isinstance(params, cls):
+        return params
+    names = [k for k, _ in cls._fields_]
+    if isinstance(params, dict):
+        if sorted(params) != sorted(names):
+            raise TypeError(f"{what}: exactly {names}")
+        return cls(**params)
+    vals = tuple(params)
+    if len(vals) != len(names):
+        raise TypeError(f"{what}: exactly {names}")
+    return cls(*vals)
+
+
+def occupancyRayParams(params):
+    """capi.OccupancyRayParams from one, from a dict with its five fields, or from a 5-tuple in the struct's order (z_lo,
+    z_hi, margin, min_range, max_range).  There are no defaults."""
+    return _struct_from(capi.OccupancyRayParams, params, "occupancy ray parameters")
+
+
+def occupancyRule(rule):
+    """capi.OccupancyRule from one, from a dict with its three fields, or from a 3-tuple in the struct's order
+    (min_free_scans, free_per_seen, min_seen_scans)."""
+    return _struct_from(capi.OccupancyRule, rule, "occupancy rule")
+
+
 def classifyNeighbourhood(points, params, details=False, frontend=None):
     """The neighbourhood classifier alone (lom_classify_neighbourhood) on POINT_XYZIRT records whose `ring` is not read:
     (planar xyz, normals) in input order, and with details=True a third array of capi.NEIGHBOURHOOD_DETAIL records, one
@@ -1056,6 +1082,15 @@ class ScanArchive:
         return int(self._check(capi.lib().lom_archive_add_device(self._h, d_xyz_ptr, d_nrm_ptr, int(n), int(stride_bytes),
                                                                 hip_event)))
 
+    def addPoints(self, xyz):
+        """lom_archive_add_points: a new scan without normals (zeros are stored); returns its id"""
+        xyz = capi.xyz_array(xyz)
+        return int(self._check(capi.lib().lom_archive_add_points(self._h, xyz.ctypes.data, len(xyz), 12)))
+
+    def addPointsDevice(self, d_xyz_ptr, n, stride_bytes=12, hip_event=None):
+        """the same from device memory, read behind `hip_event` (a hipEvent_t) or the archive's own stream"""
+        return int(self._check(capi.lib().lom_archive_add_points_device(self._h, d_xyz_ptr, int(n), int(stride_bytes), hip_event)))
+
     def get(self, id):
         """(points, normals) of a scan, (n, 3) float32 each"""
         n = self.scanSize(id)
@@ -1070,6 +1105,92 @@ def _assemble_args(ids, poses):
     if len(p) != len(ids):
         raise ValueError("one pose per id")
     return ids, p
+
+
+class OccupancyGrid:
+    """A dense 2-D grid of free / seen scan counts on the device (lom_occupancy_*, include/lidar_odometry_amd.h
+    "occupancy grid"): posed scans vote once per cell, and classify() turns the counts into the int8 values of
+    nav_msgs/OccupancyGrid (0 free, 100 occupied, -1 unknown), shape (height, width)."""
+
+    def __init__(self, resolution, origin_xy, width, height, device=0):
+        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
+        h = C.c_void_p()
+        rc = capi.lib().lom_occupancy_create(C.byref(geo), int(device), C.byref(h))
+        if rc != 0:
+            text = capi.lib().lom_occupancy_last_error(None)
+            raise LomError(int(rc), text.decode() if text else "lom_occupancy_create")
+        self._h = h
+        self.width, self.height = int(width), int(height)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and capi is not None:
+            capi.lib().lom_occupancy_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _check(self, rc):
+        if rc < 0:
+            text = capi.lib().lom_occupancy_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "")
+        return rc
+
+    def geometry(self):
+        geo = capi.OccupancyGeometry()
+        self._check(capi.lib().lom_occupancy_get_geometry(self._h, C.byref(geo)))
+        return geo.asdict()
+
+    def setOption(self, option, value):
+        self._check(capi.lib().lom_occupancy_set_option(self._h, int(option), int(value)))
+
+    def waitEvent(self, hip_event):
+        self._check(capi.lib().lom_occupancy_wait_event(self._h, hip_event))
+
+    def clear(self):
+        self._check(capi.lib().lom_occupancy_clear(self._h))
+
+    def integrate(self, archive, ids, poses, ray_params):
+        """lom_occupancy_integrate: the scans `ids` of the ScanArchive at `poses` (n x 7 float64, t then q wxyz) vote;
+        returns capi.OccupancyStats as a dict"""
+        p = occupancyRayParams(ray_params)
+        ids, g = _assemble_args(ids, poses)
+        st = capi.OccupancyStats()
+        self._check(capi.lib().lom_occupancy_integrate(self._h, archive.handle, ids.ctypes.data, g.ctypes.data, len(ids),
+                                                       C.byref(p), C.byref(st)))
+        return st.asdict()
+
+    def integrateCloud(self, xyz, pose, ray_params, device_ptr=None, n=None, stride_bytes=12, hip_event=None):
+        """lom_occupancy_integrate_cloud: one scan that is not in an archive, a host array (n, 3) -- or, with device_ptr,
+        lom_occupancy_integrate_cloud_device: n records of stride_bytes in HBM behind `hip_event`"""
+        p = occupancyRayParams(ray_params)
+        g = _graph_poses(np.asarray(pose, np.float64).reshape(1, 7))
+        st = capi.OccupancyStats()
+        if device_ptr is not None:
+            rc = capi.lib().lom_occupancy_integrate_cloud_device(self._h, device_ptr, int(n), int(stride_bytes), g.ctypes.data,
+                                                                 C.byref(p), hip_event, C.byref(st))
+        else:
+            xyz = capi.xyz_array(xyz)
+            rc = capi.lib().lom_occupancy_integrate_cloud(self._h, xyz.ctypes.data, len(xyz), 12, g.ctypes.data, C.byref(p),
+                                                          C.byref(st))
+        self._check(rc)
+        return st.asdict()
+
+    def counts(self):
+        """(free, seen): uint32 arrays of shape (height, width)"""
+        free, seen = np.zeros((self.height, self.width), np.uint32), np.zeros((self.height, self.width), np.uint32)
+        self._check(capi.lib().lom_occupancy_counts(self._h, free.ctypes.data, seen.ctypes.data, free.size))
+        return free, seen
+
+    def classify(self, rule):
+        """(int8 array of shape (height, width), summary dict) by lom_occupancy_rule"""
+        r = occupancyRule(rule)
+        out = np.empty((self.height, self.width), np.int8)
+        sm = capi.OccupancySummary()
+        self._check(capi.lib().lom_occupancy_classify(self._h, C.byref(r), out.ctypes.data, out.size, C.byref(sm)))
+        return out, sm.asdict()
 
 
 class PoseGraph:
@@ -1440,6 +1561,26 @@ class LidarOdometry:
             text = capi.lib().lom_odometry_last_error(self._h)
             raise LomError(int(rc), text.decode() if text else "lom_odometry_archive_scan")
         return int(id_.value)
+
+    def archiveDeskewed(self, archive):
+        """lom_odometry_archive_deskewed: the last frame's deskewed cloud (getTempCloud), every point and no normals,
+        becomes a new scan of the ScanArchive; returns its id.  LomError(LOM_ERR_STATE) before the first frame."""
+        id_ = C.c_int64(-1)
+        rc = capi.lib().lom_odometry_archive_deskewed(self._h, archive.handle, C.byref(id_))
+        if rc != 0:
+            text = capi.lib().lom_odometry_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "lom_odometry_archive_deskewed")
+        return int(id_.value)
+
+    def occupancyScan(self, grid, ray_params):
+        """lom_odometry_occupancy_scan: that cloud at the current pose votes on the OccupancyGrid; returns the stats."""
+        p = occupancyRayParams(ray_params)
+        st = capi.OccupancyStats()
+        rc = capi.lib().lom_odometry_occupancy_scan(self._h, grid.handle, C.byref(p), C.byref(st))
+        if rc != 0:
+            text = capi.lib().lom_occupancy_last_error(grid.handle)
+            raise LomError(int(rc), text.decode() if text else "lom_odometry_occupancy_scan")
+        return st.asdict()
 
     def rebuildKeyframe(self, archive, ids, poses, new_current):
         """lom_odometry_rebuild_keyframe: the keyframe again from the archive's scans `ids` at `poses`, culled at

@@ -226,6 +226,50 @@ class VoteStats(C.Structure):
 assert C.sizeof(VoteParams) == 24 and C.sizeof(VoteStats) == 48
 
 
+class OccupancyGeometry(C.Structure):
+    """lom_occupancy_geometry"""
+    _fields_ = [("resolution", C.c_float), ("origin_x", C.c_float), ("origin_y", C.c_float), ("width", C.c_uint32),
+                ("height", C.c_uint32)]
+
+    def asdict(self):
+        return dict(resolution=float(self.resolution), origin_x=float(self.origin_x), origin_y=float(self.origin_y),
+                    width=int(self.width), height=int(self.height))
+
+
+class OccupancyRayParams(C.Structure):
+    """lom_occupancy_ray_params (no defaults: every field is the caller's)"""
+    _fields_ = [("z_lo", C.c_float), ("z_hi", C.c_float), ("margin", C.c_float), ("min_range", C.c_float),
+                ("max_range", C.c_float)]
+
+
+class OccupancyRule(C.Structure):
+    """lom_occupancy_rule"""
+    _fields_ = [("min_free_scans", C.c_uint32), ("free_per_seen", C.c_uint32), ("min_seen_scans", C.c_uint32)]
+
+
+class OccupancyStats(C.Structure):
+    """lom_occupancy_stats"""
+    _fields_ = [("scans", C.c_uint64), ("rays_walked", C.c_uint64), ("rays_skipped", C.c_uint64),
+                ("endpoints_marked", C.c_uint64), ("cells_visited", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class OccupancySummary(C.Structure):
+    """lom_occupancy_summary"""
+    _fields_ = [("cells_free", C.c_uint64), ("cells_occupied", C.c_uint64), ("cells_unknown", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(OccupancyGeometry) == 20 and C.sizeof(OccupancyRayParams) == 20 and C.sizeof(OccupancyRule) == 12
+assert C.sizeof(OccupancyStats) == 40 and C.sizeof(OccupancySummary) == 24
+OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = 0, 100, -1
+OCC_OPT_TEST_SLICE_MAX, OCC_OPT_TEST_WINDOW = 1, 2
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -300,9 +344,16 @@ EXPORTED = [
     "lom_archive_point_count", "lom_archive_scan_size", "lom_archive_get", "lom_map_assemble", "lom_odometry_archive_scan",
     "lom_odometry_rebuild_keyframe",
     "lom_map_carve_scans", "lom_map_scan_votes", "lom_odometry_set_rebuild_votes", "lom_odometry_get_rebuild_vote_stats",
+    "lom_odometry_archive_deskewed", "lom_odometry_occupancy_scan",
+    "lom_occupancy_create", "lom_occupancy_destroy", "lom_occupancy_last_error", "lom_occupancy_clear",
+    "lom_occupancy_get_geometry", "lom_occupancy_stream", "lom_occupancy_device", "lom_occupancy_wait_event",
+    "lom_occupancy_set_option", "lom_occupancy_integrate", "lom_occupancy_integrate_cloud",
+    "lom_occupancy_integrate_cloud_device", "lom_occupancy_counts", "lom_occupancy_classify", "lom_occupancy_classify_device",
 ]
 # ... and the one it declares through a function type (the "scan archive and map assembly" section)
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
+# ... and the two of the same section that came with the occupancy grid, declared the same way
+EXPORTED_BY_TYPE_POINTS = ["lom_archive_add_points", "lom_archive_add_points_device"]
 
 # lom_option / counters of include/lidar_odometry_amd.h
 OPT_HOST_LM, OPT_DEVICE_PATIENCE_TICKS, OPT_DEBUG_LM_STAMPS, OPT_DEBUG_TIMING, OPT_NO_TEMPORAL_BOUND, OPT_COUNT_CANDIDATES = 1, 2, 3, 4, 5, 6
@@ -642,6 +693,32 @@ def lib():
     L.lom_map_scan_votes.restype = C.c_int64
     L.lom_odometry_set_rebuild_votes.argtypes = [vp, C.POINTER(VoteParams)]
     L.lom_odometry_get_rebuild_vote_stats.argtypes = [vp, C.POINTER(VoteStats)]
+    L.lom_archive_add_points.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
+    L.lom_archive_add_points_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
+    L.lom_archive_add_points.restype = L.lom_archive_add_points_device.restype = C.c_int64
+    L.lom_odometry_archive_deskewed.argtypes = [vp, vp, C.POINTER(C.c_int64)]
+    L.lom_odometry_occupancy_scan.argtypes = [vp, vp, C.POINTER(OccupancyRayParams), C.POINTER(OccupancyStats)]
+    L.lom_occupancy_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
+    L.lom_occupancy_destroy.argtypes = [vp]
+    L.lom_occupancy_destroy.restype = None
+    L.lom_occupancy_last_error.argtypes = [vp]
+    L.lom_occupancy_last_error.restype = C.c_char_p
+    L.lom_occupancy_clear.argtypes = [vp]
+    L.lom_occupancy_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
+    L.lom_occupancy_stream.argtypes = [vp]
+    L.lom_occupancy_stream.restype = vp
+    L.lom_occupancy_device.argtypes = [vp]
+    L.lom_occupancy_wait_event.argtypes = [vp, vp]
+    L.lom_occupancy_set_option.argtypes = [vp, C.c_int, C.c_int64]
+    L.lom_occupancy_integrate.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(OccupancyRayParams), C.POINTER(OccupancyStats)]
+    L.lom_occupancy_integrate_cloud.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(OccupancyRayParams),
+                                                C.POINTER(OccupancyStats)]
+    L.lom_occupancy_integrate_cloud_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(OccupancyRayParams), vp,
+                                                       C.POINTER(OccupancyStats)]
+    L.lom_occupancy_counts.argtypes = [vp, vp, vp, C.c_size_t]
+    L.lom_occupancy_counts.restype = C.c_int64
+    L.lom_occupancy_classify.argtypes = [vp, C.POINTER(OccupancyRule), vp, C.c_size_t, C.POINTER(OccupancySummary)]
+    L.lom_occupancy_classify_device.argtypes = [vp, C.POINTER(OccupancyRule), C.POINTER(vp)]
     _lib = L
     return L
 

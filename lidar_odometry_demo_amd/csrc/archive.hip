@@ -45,7 +45,8 @@ int reserve_points(lom_archive *a, uint64_t need)
 
 bool stride_ok(size_t stride) { return stride >= 12 && (stride & 3) == 0; }
 
-// a new scan from `xyz` / `nrm` (records of `stride` bytes, host or device memory by `kind`); the archive's lock is held
+// a new scan from `xyz` / `nrm` (records of `stride` bytes, host or device memory by `kind`; nrm NULL: zeros are stored);
+// the archive's lock is held
 int64_t add_scan(lom_archive *a, const float *xyz, const float *nrm, size_t n, size_t stride, hipMemcpyKind kind)
 {
     if (a->points + n > assemble::kArchiveMaxPoints)
@@ -57,17 +58,41 @@ int64_t add_scan(lom_archive *a, const float *xyz, const float *nrm, size_t n, s
         float *dx = a->d_xyz() + a->points * 3, *dn = a->d_nrm() + a->points * 3;
         if (stride == 12) {
             LOM_HIP(a, hipMemcpyAsync(dx, xyz, n * 12, kind, a->stream));
-            LOM_HIP(a, hipMemcpyAsync(dn, nrm, n * 12, kind, a->stream));
+            if (nrm) LOM_HIP(a, hipMemcpyAsync(dn, nrm, n * 12, kind, a->stream));
         } else {
             LOM_HIP(a, hipMemcpy2DAsync(dx, 12, xyz, stride, 12, n, kind, a->stream));
-            LOM_HIP(a, hipMemcpy2DAsync(dn, 12, nrm, stride, 12, n, kind, a->stream));
+            if (nrm) LOM_HIP(a, hipMemcpy2DAsync(dn, 12, nrm, stride, 12, n, kind, a->stream));
         }
+        if (!nrm) LOM_HIP(a, hipMemsetAsync(dn, 0, n * 12, a->stream));
         // the caller's buffers are its own again when the call returns
         LOM_HIP(a, hipStreamSynchronize(a->stream));
     }
     a->table.push_back(ScanEntry{a->points, (uint32_t)n});
     a->points += n;
     return (int64_t)a->table.size() - 1;
+}
+
+// the two host forms (nrm NULL: lom_archive_add_points); the lock is taken here
+int64_t add_host(lom_archive *a, const float *xyz, const float *nrm, size_t n, size_t stride)
+{
+    std::lock_guard<std::mutex> lk(a->lock);
+    for (size_t i = 0; i < n; i++) {
+        const float *p = reinterpret_cast<const float *>(reinterpret_cast<const char *>(xyz) + i * stride);
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]))
+            return fail(a, LOM_ERR_ARG, ("point " + std::to_string(i) + " has a coordinate that is not finite").c_str());
+    }
+    return add_scan(a, xyz, nrm, n, stride, hipMemcpyHostToDevice);
+}
+
+// the two device forms
+int64_t add_device(lom_archive *a, const float *d_xyz, const float *d_nrm, size_t n, size_t stride, void *hip_event_or_null)
+{
+    std::lock_guard<std::mutex> lk(a->lock);
+    if (hip_event_or_null) {
+        LOM_HIP(a, hipSetDevice(a->device));
+        LOM_HIP(a, hipStreamWaitEvent(a->stream, (hipEvent_t)hip_event_or_null, 0));
+    }
+    return add_scan(a, d_xyz, d_nrm, n, stride, hipMemcpyDeviceToDevice);
 }
 
 template <bool kCull>
@@ -155,25 +180,26 @@ int lom_archive_wait_event(lom_archive *a, void *hip_event)
 int64_t lom_archive_add(lom_archive *a, const float *xyz, const float *nrm, size_t n, size_t stride)
 {
     if (!a || (n && (!xyz || !nrm)) || !stride_ok(stride)) return LOM_ERR_ARG;
-    std::lock_guard<std::mutex> lk(a->lock);
-    for (size_t i = 0; i < n; i++) {
-        const float *p = reinterpret_cast<const float *>(reinterpret_cast<const char *>(xyz) + i * stride);
-        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]))
-            return fail(a, LOM_ERR_ARG, ("point " + std::to_string(i) + " has a coordinate that is not finite").c_str());
-    }
-    return add_scan(a, xyz, nrm, n, stride, hipMemcpyHostToDevice);
+    return add_host(a, xyz, nrm, n, stride);
+}
+
+int64_t lom_archive_add_points(lom_archive *a, const float *xyz, size_t n, size_t stride)
+{
+    if (!a || (n && !xyz) || !stride_ok(stride)) return LOM_ERR_ARG;
+    return add_host(a, xyz, nullptr, n, stride);
 }
 
 int64_t lom_archive_add_device(lom_archive *a, const float *d_xyz, const float *d_nrm, size_t n, size_t stride,
                                void *hip_event_or_null)
 {
     if (!a || (n && (!d_xyz || !d_nrm)) || !stride_ok(stride)) return LOM_ERR_ARG;
-    std::lock_guard<std::mutex> lk(a->lock);
-    if (hip_event_or_null) {
-        LOM_HIP(a, hipSetDevice(a->device));
-        LOM_HIP(a, hipStreamWaitEvent(a->stream, (hipEvent_t)hip_event_or_null, 0));
-    }
-    return add_scan(a, d_xyz, d_nrm, n, stride, hipMemcpyDeviceToDevice);
+    return add_device(a, d_xyz, d_nrm, n, stride, hip_event_or_null);
+}
+
+int64_t lom_archive_add_points_device(lom_archive *a, const float *d_xyz, size_t n, size_t stride, void *hip_event_or_null)
+{
+    if (!a || (n && !d_xyz) || !stride_ok(stride)) return LOM_ERR_ARG;
+    return add_device(a, d_xyz, nullptr, n, stride, hip_event_or_null);
 }
 
 int64_t lom_archive_scan_count(const lom_archive *a)

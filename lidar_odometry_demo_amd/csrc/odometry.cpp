@@ -153,6 +153,66 @@ int lom_odometry_archive_scan(lom_odometry *o, lom_archive *a, int64_t *id_out)
     return LOM_OK;
 }
 
+// the last frame's deskewed cloud as lom_odometry_place_descriptor reads it: the front end's copy in HBM (*event: its done
+// event) or the host copy of a host-stage frame (*event NULL); records of sizeof(lom_point_xyzirt) bytes
+static int deskewed_cloud(lom_odometry *o, const float **pts, size_t *n, void **event)
+{
+    *n = o->temp_points;
+    *event = nullptr;
+    if (!o->temp_on_device) {
+        *pts = reinterpret_cast<const float *>(o->deskewed.data());
+        return LOM_OK;
+    }
+    const lom_point_xyzirt *d = nullptr;
+    uint32_t nd = 0;
+    const int rc = lom_frontend_deskewed(o->frontend, &d, &nd);
+    if (rc != LOM_OK) return rc;
+    *pts = reinterpret_cast<const float *>(d);
+    *n = nd;
+    *event = lom_frontend_done_event(o->frontend);
+    return LOM_OK;
+}
+
+// that cloud, every point of it and no normals, into a scan archive (csrc/archive.hip); reads only
+int lom_odometry_archive_deskewed(lom_odometry *o, lom_archive *a, int64_t *id_out)
+{
+    if (!o || !a || !id_out || lom_archive_device(a) != o->device) return LOM_ERR_ARG;
+    if (o->temp_points == 0) return LOM_ERR_STATE;  // no frame yet
+    const float *pts = nullptr;
+    size_t n = 0;
+    void *event = nullptr;
+    const int rc = deskewed_cloud(o, &pts, &n, &event);
+    if (rc != LOM_OK) return rc;
+    const size_t stride = sizeof(lom_point_xyzirt);
+    const int64_t id = o->temp_on_device ? lom_archive_add_points_device(a, pts, n, stride, event) : lom_archive_add_points(a, pts, n, stride);
+    if (id < 0) {
+        o->error = lom_archive_last_error(a);
+        return (int)id;
+    }
+    *id_out = id;
+    return LOM_OK;
+}
+
+// that cloud at the current pose into an occupancy grid (csrc/occupancy.hip); reads only
+int lom_odometry_occupancy_scan(lom_odometry *o, lom_occupancy *g, const lom_occupancy_ray_params *p, lom_occupancy_stats *stats)
+{
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (!o || !g || lom_occupancy_device(g) != o->device) return LOM_ERR_ARG;
+    if (o->temp_points == 0) return LOM_ERR_STATE;  // no frame yet
+    const float *pts = nullptr;
+    size_t n = 0;
+    void *event = nullptr;
+    int rc = deskewed_cloud(o, &pts, &n, &event);
+    if (rc != LOM_OK) return rc;
+    lom_graph_pose pose;
+    if ((rc = lom_graph_pose_from_f32(&o->current, &pose)) != LOM_OK) return rc;
+    const size_t stride = sizeof(lom_point_xyzirt);
+    rc = o->temp_on_device ? lom_occupancy_integrate_cloud_device(g, pts, n, stride, &pose, p, event, stats)
+                           : lom_occupancy_integrate_cloud(g, pts, n, stride, &pose, p, stats);
+    if (rc != LOM_OK) o->error = lom_occupancy_last_error(g);
+    return rc;
+}
+
 // the keyframe again from archived scans at corrected poses: the steps of the header, in its order
 int lom_odometry_rebuild_keyframe(lom_odometry *o, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses,
                                   size_t count, const lom_pose *new_current, lom_assemble_stats *stats)
