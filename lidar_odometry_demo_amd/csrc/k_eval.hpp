@@ -53,26 +53,77 @@ constexpr int kPublishPlain = 0, kPublishHost = 1, kPublishDevice = 2;
 struct PointTerms {
     double J[6], r;
 };
-// cloud_matcher.cpp:48-98 for one correspondence: residual and 1x6 tangent Jacobian
-__device__ __forceinline__ void point_terms(const float4 ra, const float4 rb, const float4 rc, const double q0,
-                                            const double q1, const double q2, const double q3, const double t0,
-                                            const double t1, const double t2, PointTerms &T)
+// |q|^2 - 1 of an evaluation's quaternion (uniform: once per evaluation, every lane may compute it).  About 1e-7 at the
+// start of every solve, whose quaternion is an f32 pose widened, and whatever the LM candidates drift to afterwards.
+__host__ __device__ __forceinline__ double quat_excess(const double q0, const double q1, const double q2,
+                                                       const double q3)
+{
+    return (((q0 * q0 - 1.0) + q1 * q1) + q2 * q2) + q3 * q3;
+}
+// cloud_matcher.cpp:54  (rot*local_point + t - plane_origin).dot(plane_normal); p, n and rp = rot*local_point (by the
+// unit-quaternion formula) are kept for the Jacobian
+struct PointGeom {
+    double p[3], nn[3], rp[3];
+};
+__host__ __device__ __forceinline__ double point_residual(const float4 ra, const float4 rb, const float4 rc,
+                                                          const double q0, const double q1, const double q2,
+                                                          const double q3, const double t0, const double t1,
+                                                          const double t2, PointGeom &G)
 {
     const double p[3] = {(double)ra.x, (double)ra.y, (double)ra.z};
     const double o[3] = {(double)rb.x, (double)rb.y, (double)rb.z};
     const double nn[3] = {(double)ra.w, (double)rc.x, (double)rc.y};
-    // cloud_matcher.cpp:54  (rot*local_point + t - plane_origin).dot(plane_normal)
-    double uv0 = q2 * p[2] - q3 * p[1];
-    double uv1 = q3 * p[0] - q1 * p[2];
-    double uv2 = q1 * p[1] - q2 * p[0];
-    uv0 += uv0;
-    uv1 += uv1;
-    uv2 += uv2;
-    const double rp0 = (p[0] + q0 * uv0) + (q2 * uv2 - q3 * uv1);
-    const double rp1 = (p[1] + q0 * uv1) + (q3 * uv0 - q1 * uv2);
-    const double rp2 = (p[2] + q0 * uv2) + (q1 * uv1 - q2 * uv0);
+    // rp = p + 2 (q0 c + u x c), c = u x p: the factor 2 rides on the last multiply-add
+    const double c0 = q2 * p[2] - q3 * p[1];
+    const double c1 = q3 * p[0] - q1 * p[2];
+    const double c2 = q1 * p[1] - q2 * p[0];
+    const double rp0 = p[0] + 2.0 * (q0 * c0 + (q2 * c2 - q3 * c1));
+    const double rp1 = p[1] + 2.0 * (q0 * c1 + (q3 * c0 - q1 * c2));
+    const double rp2 = p[2] + 2.0 * (q0 * c2 + (q1 * c1 - q2 * c0));
     const double e0 = rp0 + t0 - o[0], e1 = rp1 + t1 - o[1], e2 = rp2 + t2 - o[2];
-    T.r = e0 * nn[0] + (e1 * nn[1] + e2 * nn[2]);
+    for (int a = 0; a < 3; a++) {
+        G.p[a] = p[a];
+        G.nn[a] = nn[a];
+    }
+    G.rp[0] = rp0;
+    G.rp[1] = rp1;
+    G.rp[2] = rp2;
+    return e0 * nn[0] + (e1 * nn[1] + e2 * nn[2]);
+}
+// cloud_matcher.cpp:48-98 for one correspondence: residual and 1x6 tangent Jacobian.  qe = quat_excess(q).
+// The rotation columns in closed form, J[0..2] = 2 (h x n) with h = rp + qe p:
+//   the reference differentiates the homogeneous rotation H(q) p = |q|^2 R(q/|q|) p, which is multiplicative,
+//   H(a (x) q) = H(a) H(q), and its manifold steps on the left, q <- z (x) q, with H(1 + eps e_j) = I + 2 eps [e_j]x +
+//   O(eps^2): d r / d delta_j = 2 n . (e_j x H(q) p) = 2 (H(q) p x n)_j;
+//   and H(q) p = rp + (|q|^2 - 1) p, because 2 u (u.p) = 2 u x (u x p) + 2 |u|^2 p.
+__host__ __device__ __forceinline__ void point_terms(const float4 ra, const float4 rb, const float4 rc, const double q0,
+                                                     const double q1, const double q2, const double q3, const double qe,
+                                                     const double t0, const double t1, const double t2, PointTerms &T)
+{
+    PointGeom G;
+    T.r = point_residual(ra, rb, rc, q0, q1, q2, q3, t0, t1, t2, G);
+    const double *nn = G.nn;
+    const double h0 = G.rp[0] + qe * G.p[0], h1 = G.rp[1] + qe * G.p[1], h2 = G.rp[2] + qe * G.p[2];
+    const double c0 = h1 * nn[2] - h2 * nn[1];
+    const double c1 = h2 * nn[0] - h0 * nn[2];
+    const double c2 = h0 * nn[1] - h1 * nn[0];
+    T.J[0] = c0 + c0;
+    T.J[1] = c1 + c1;
+    T.J[2] = c2 + c2;
+    T.J[3] = nn[0];  // cloud_matcher.cpp:96-98
+    T.J[4] = nn[1];
+    T.J[5] = nn[2];
+}
+// The same terms the way the reference writes them (cloud_matcher.cpp:64-91 and Ceres' QuaternionManifold): four ambient
+// derivatives times the 4x3 plus-Jacobian.  No kernel calls it; tests/cpp/test_point_terms.cpp holds point_terms to it.
+__host__ __device__ __forceinline__ void point_terms_ambient(const float4 ra, const float4 rb, const float4 rc,
+                                                             const double q0, const double q1, const double q2,
+                                                             const double q3, const double t0, const double t1,
+                                                             const double t2, PointTerms &T)
+{
+    PointGeom G;
+    T.r = point_residual(ra, rb, rc, q0, q1, q2, q3, t0, t1, t2, G);
+    const double *p = G.p, *nn = G.nn;
     // cloud_matcher.cpp:64-91: ambient d r / d q_i = (dR/dq_i p).n
     double v0, v1, v2, ja[4];
     v0 = 2.0 * q0 * p[0] + 2.0 * -q3 * p[1] + 2.0 * q2 * p[2];
@@ -99,16 +150,59 @@ __device__ __forceinline__ void point_terms(const float4 ra, const float4 rb, co
     T.J[4] = nn[1];
     T.J[5] = nn[2];
 }
-// ceres::HuberLoss(0.15) (cloud_matcher.cpp:134); rho'' <= 0 -> plain IRLS weight rho'; then the 28 sums
-__device__ __forceinline__ void point_accumulate(const PointTerms &T, double acc[28])
+// 1 / d to f64 rounding without the IEEE divide: an estimate and two Newton steps (lm_wave.hpp's fast_rcp).  The host
+// form, for the comparison program, starts from an estimate 2^-24 off so that the steps have work to do there too.
+__host__ __device__ __forceinline__ double huber_rcp(const double d)
 {
-    const double r = T.r, s = r * r;
-    double rho0 = s, w = 1.0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    double y = __builtin_amdgcn_rcp(d);
+#else
+    double y = (1.0 / d) * (1.0 + 0x1p-24);
+#endif
+    double e = __builtin_fma(-d, y, 1.0);
+    y = __builtin_fma(y, e, y);
+    e = __builtin_fma(-d, y, 1.0);
+    return __builtin_fma(y, e, y);
+}
+// ceres::HuberLoss(0.15) (cloud_matcher.cpp:134) on s = r^2: rho = s, rho' = 1 up to s = 0.15^2; beyond it
+// rho = 2 a sqrt(s) - a^2, rho' = a / sqrt(s), floored at DBL_MIN; rho'' <= 0 -> plain IRLS weight rho'.  sqrt(r r) is |r|
+// to rounding, so neither a square root nor a divide nor a branch: two selects on |r| > 0.15 (strict, like s > 0.15^2:
+// r = 0 and |r| = 0.15 take the quadratic side; the side not selected may hold inf or NaN, which a select drops).
+struct HuberTerms {
+    double rho, w;
+};
+__host__ __device__ __forceinline__ HuberTerms huber_terms(const double r)
+{
+    const double a = fabs(r);
+    const bool big = a > 0.15;
+    // both sides are computed before the selects: written inside them, the reciprocal stays behind a branch.
+    // 2 a |r| - a^2 as a (2 |r| - a): one instruction more than 0.3 |r| - 0.0225, and two f64 constants fewer to keep in
+    // scalar registers through the solve (as 0.3 |r| - 0.0225, k_lm<512,128,1> spilled six more of them)
+    const double rho_big = 0.15 * (2.0 * a - 0.15), rho_small = r * r;
+    const double w_big = fmax(DBL_MIN, 0.15 * huber_rcp(a));
+    HuberTerms H;
+    H.rho = big ? rho_big : rho_small;
+    H.w = big ? w_big : 1.0;
+    return H;
+}
+// the form it replaces, with the square root and the divide (tests/cpp/test_point_terms.cpp; no kernel calls it)
+__host__ __device__ __forceinline__ HuberTerms huber_terms_sqrt(const double r)
+{
+    const double s = r * r;
+    HuberTerms H = {s, 1.0};
     if (s > 0.15 * 0.15) {
         const double rr = sqrt(s);
-        rho0 = 2.0 * 0.15 * rr - 0.15 * 0.15;
-        w = fmax(DBL_MIN, 0.15 / rr);
+        H.rho = 2.0 * 0.15 * rr - 0.15 * 0.15;
+        H.w = fmax(DBL_MIN, 0.15 / rr);
     }
+    return H;
+}
+// the robust weight, then the 28 sums
+__host__ __device__ __forceinline__ void point_accumulate(const PointTerms &T, double acc[28])
+{
+    const double r = T.r;
+    const HuberTerms H = huber_terms(r);
+    const double rho0 = H.rho, w = H.w;
     int k = 0;
 #pragma unroll
     for (int a = 0; a < 6; a++) {
@@ -123,10 +217,11 @@ __device__ __forceinline__ void point_accumulate(const PointTerms &T, double acc
 // cloud_matcher.cpp:48-102 for one correspondence, accumulated into the 28 sums
 __device__ __forceinline__ void accumulate_point(const float4 ra, const float4 rb, const float4 rc,
                                                  const double q0, const double q1, const double q2, const double q3,
-                                                 const double t0, const double t1, const double t2, double acc[28])
+                                                 const double qe, const double t0, const double t1, const double t2,
+                                                 double acc[28])
 {
     PointTerms T;
-    point_terms(ra, rb, rc, q0, q1, q2, q3, t0, t1, t2, T);
+    point_terms(ra, rb, rc, q0, q1, q2, q3, qe, t0, t1, t2, T);
     point_accumulate(T, acc);
 }
 #pragma clang fp contract(off)
@@ -221,10 +316,11 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval(const MatchRec *__restric
     double acc[28];
 #pragma unroll
     for (int k = 0; k < 28; k++) acc[k] = 0.0;
+    const double qe = quat_excess(E.q[0], E.q[1], E.q[2], E.q[3]);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float4 *r4 = reinterpret_cast<const float4 *>(rec + i);
         const float4 ra = r4[0], rb = r4[1], rc = r4[2];
-        if (rb.w != 0.f) accumulate_point(ra, rb, rc, E.q[0], E.q[1], E.q[2], E.q[3], E.t[0], E.t[1], E.t[2], acc);
+        if (rb.w != 0.f) accumulate_point(ra, rb, rc, E.q[0], E.q[1], E.q[2], E.q[3], qe, E.t[0], E.t[1], E.t[2], acc);
     }
     reduce_and_publish(acc, s_acc, s_cnt, block_counters, n_match_blocks, out_rec, seq, kPublishPlain);
 }
@@ -255,11 +351,12 @@ __global__ __launch_bounds__(kEvalThreads) void k_eval_server(const MatchRec *__
         double acc[28];
 #pragma unroll
         for (int k = 0; k < 28; k++) acc[k] = 0.0;
-        if (rb.w != 0.f) accumulate_point(ra, rb, rc, q0, q1, q2, q3, t0, t1, t2, acc);
+        const double qe = quat_excess(q0, q1, q2, q3);
+        if (rb.w != 0.f) accumulate_point(ra, rb, rc, q0, q1, q2, q3, qe, t0, t1, t2, acc);
         for (uint32_t i = first + step; i < n; i += step) {
             const float4 *r4 = reinterpret_cast<const float4 *>(rec + i);
             const float4 xa = r4[0], xb = r4[1], xc = r4[2];
-            if (xb.w != 0.f) accumulate_point(xa, xb, xc, q0, q1, q2, q3, t0, t1, t2, acc);
+            if (xb.w != 0.f) accumulate_point(xa, xb, xc, q0, q1, q2, q3, qe, t0, t1, t2, acc);
         }
         reduce_and_publish(acc, s_acc, s_cnt, block_counters, counters_from, out_rec, seq, kPublishHost);
         counters_from = 0;

@@ -413,6 +413,7 @@ __device__ __forceinline__ void accumulate_all(const MatchRec *__restrict__ rec,
                                                const float4 (&rc)[kRegPts], const double *x, double acc[28])
 {
     const double q0 = x[0], q1 = x[1], q2 = x[2], q3 = x[3], t0 = x[4], t1 = x[5], t2 = x[6];
+    const double qe = quat_excess(q0, q1, q2, q3);
 #pragma unroll
     for (int k = 0; k < 28; k++) acc[k] = 0.0;
     // The register points go through unconditionally and stage by stage -- residuals and Jacobians of all of them, then
@@ -421,13 +422,13 @@ __device__ __forceinline__ void accumulate_all(const MatchRec *__restrict__ rec,
     // normal: every term it adds is exactly zero.
     PointTerms T[kRegPts];
 #pragma unroll
-    for (int p = 0; p < kRegPts; p++) point_terms(ra[p], rb[p], rc[p], q0, q1, q2, q3, t0, t1, t2, T[p]);
+    for (int p = 0; p < kRegPts; p++) point_terms(ra[p], rb[p], rc[p], q0, q1, q2, q3, qe, t0, t1, t2, T[p]);
 #pragma unroll
     for (int p = 0; p < kRegPts; p++) point_accumulate(T[p], acc);
     for (uint32_t i = first + (uint32_t)kRegPts * step; i < n; i += step) {
         const float4 *r4 = reinterpret_cast<const float4 *>(rec + i);
         const float4 xa = r4[0], xb = r4[1], xc = r4[2];
-        if (xb.w != 0.f) accumulate_point(xa, xb, xc, q0, q1, q2, q3, t0, t1, t2, acc);
+        if (xb.w != 0.f) accumulate_point(xa, xb, xc, q0, q1, q2, q3, qe, t0, t1, t2, acc);
     }
 }
 

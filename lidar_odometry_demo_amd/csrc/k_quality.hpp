@@ -15,7 +15,7 @@ namespace lom {
 
 // ---------------------------------------------------------------------------
 // One evaluation over the records a search left, at the report's pose: the align's own residual, Jacobian and 28 sums
-// (point_terms / point_accumulate of k_eval.hpp, unchanged) plus what a caller judges the pose by.  One lane per
+// (point_terms / point_accumulate of k_eval.hpp) plus what a caller judges the pose by.  One lane per
 // record, grid-stride; LOM_NQSUMS f64 values per lane:
 //   [0..27] sum w J J^T (21), sum w J r (6), sum 0.5 rho     [28] sum w        [29] sum w r^2
 //   [30] sum r^2 over valid   [31] sum r^2 over inliers      [32] sum |R p + t - o|^2
@@ -33,7 +33,8 @@ static_assert(kQualSums % kQualRows == 0 && kQualRows * 32 <= kEvalThreads, "one
 
 #pragma clang fp contract(fast)  // as k_eval.hpp: f64 sums compared to 1e-12 of their scale, not bit for bit
 __device__ __forceinline__ void quality_point(const float4 ra, const float4 rb, const float4 rc, const EvalArgs &E,
-                                              double acc[kQualSums], float *__restrict__ residual_out, uint32_t i)
+                                              const double qe, double acc[kQualSums],
+                                              float *__restrict__ residual_out, uint32_t i)
 {
     if (rb.w == 0.f) {  // no correspondence
         if (residual_out) residual_out[i] = __builtin_nanf("");
@@ -41,11 +42,12 @@ __device__ __forceinline__ void quality_point(const float4 ra, const float4 rb, 
     }
     const double q0 = E.q[0], q1 = E.q[1], q2 = E.q[2], q3 = E.q[3];
     PointTerms T;
-    point_terms(ra, rb, rc, q0, q1, q2, q3, E.t[0], E.t[1], E.t[2], T);
+    point_terms(ra, rb, rc, q0, q1, q2, q3, qe, E.t[0], E.t[1], E.t[2], T);
     point_accumulate(T, acc);
     const double r = T.r, s = r * r;
     const bool inlier = !(s > 0.15 * 0.15);
-    double w = 1.0;  // the weight point_accumulate applied
+    // the weight point_accumulate applied, here still by huber_terms_sqrt's square root and divide (equal to rounding)
+    double w = 1.0;
     if (!inlier) w = fmax(DBL_MIN, 0.15 / sqrt(s));
     // e = R p + t - o, the rotation as point_terms applies it
     const double p[3] = {(double)ra.x, (double)ra.y, (double)ra.z};
@@ -129,10 +131,11 @@ __global__ __launch_bounds__(kEvalThreads) void k_quality(const MatchRec *__rest
     double acc[kQualSums];
 #pragma unroll
     for (int k = 0; k < kQualSums; k++) acc[k] = 0.0;
+    const double qe = quat_excess(E.q[0], E.q[1], E.q[2], E.q[3]);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float4 *r4 = reinterpret_cast<const float4 *>(rec + i);
         const float4 ra = r4[0], rb = r4[1], rc = r4[2];
-        quality_point(ra, rb, rc, E, acc, residual_out, i);
+        quality_point(ra, rb, rc, E, qe, acc, residual_out, i);
     }
     // half-wave (k = tid / 32) takes value pass * kQualRows + k: lane j adds the lanes' entries j, j + 32, ... in order,
     // then the 32 partial results fold in a fixed butterfly
@@ -194,10 +197,11 @@ __global__ __launch_bounds__(kEvalThreads) void k_quality_batch(const QualBatchP
     double acc[kQualSums];
 #pragma unroll
     for (int k = 0; k < kQualSums; k++) acc[k] = 0.0;
+    const double qe = quat_excess(E.q[0], E.q[1], E.q[2], E.q[3]);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += grid * blockDim.x) {
         const float4 *r4 = reinterpret_cast<const float4 *>(rec + i);
         const float4 ra = r4[0], rb = r4[1], rc = r4[2];
-        quality_point(ra, rb, rc, E, acc, nullptr, i);
+        quality_point(ra, rb, rc, E, qe, acc, nullptr, i);
     }
     quality_block_reduce(acc, s_red, d->part, blockIdx.x);
 }
