@@ -480,7 +480,7 @@ typedef enum {
                                           and takes the algorithmic bytes from a counted replay of the same align. */
     LOM_OPT_NO_BULK_INSERT = 7,        /* 1: inserts of more than 65,536 points take the four-kernel path of the smaller ones
                                           (three device-scope atomics per point) instead of the partitioned bulk insert
-                                          (csrc/voxel_map.hip "bulk insert").  Same map either way, bytewise; the switch exists
+                                          (csrc/map_insert.hip, add_points_bulk).  Same map either way, bytewise; the switch exists
                                           for A/B timing (LOM_NO_BULK_INSERT=1 in the environment at create) */
     LOM_OPT_QUALITY_REPORT = 8,        /* lom_odometry_set_option only.  1: every frame that runs an align is followed by
                                           lom_match_quality_device on its matching cloud (still in HBM) at the pose the

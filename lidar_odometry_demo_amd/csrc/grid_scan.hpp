@@ -1,5 +1,5 @@
 // Workgroup scan + in-kernel prefix over the workgroups of a grid, shared by the map-maintenance kernels
-// (voxel_map.hip) and the per-frame front end (frontend.hip).
+// (the map_*.hip files) and the per-frame front end (frontend.hip).
 //
 // Single-pass kernels for per-frame sizes: at most 256 workgroups of 256 threads, all resident at once.
 // What would be {flag kernel, 1-3 scan launches, consumer kernel} is one kernel: block-local scan, then
@@ -10,13 +10,15 @@
 // the error word and tells its caller (gave_up): it has NO valid prefix and must not write results that depend
 // on one -- only put per-slot scratch back to rest.  Kernels launched behind it in the same call see the error
 // word and do likewise, so a call that gave up changes nothing the next call could trip over; the host then
-// redoes it with the multi-launch scan (voxel_map.hip), or reports it where the inputs are gone.
+// redoes it with the multi-launch scan (voxel_map.hip: map_status), or reports it where the inputs are gone.
 // (A workgroup waits for its PREDECESSORS only, and the dispatcher starts workgroups in index order, so this
 // cannot deadlock; it gives up only when something else keeps the GPU from running the grid for 20 ms.)
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "map_words.hpp"
 
 namespace lom {
 

@@ -1,4 +1,4 @@
-// The bulk insert (batches above kOnePassMax points): k_bi_claim / colscan / scatter / group / flagscan / place.  Device code only; voxel_map.hip is the one translation unit
+// The bulk insert (batches above kOnePassMax points): k_bi_claim / colscan / scatter / group / flagscan / place.  Device code only; map_insert.hip is the one translation unit
 // that instantiates and launches it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -6,8 +6,8 @@
 #include <cstdint>
 
 #include "grid_scan.hpp"
-#include "k_table.hpp"
 #include "lom_internal.hpp"
+#include "table_device.hpp"
 
 namespace lom {
 
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kBiThreads) void k_bi_claim(Slot *table, uint32_t m
 {
     extern __shared__ uint32_t s_hist[];
     for (uint32_t b = threadIdx.x; b < n_parts; b += kBiThreads) s_hist[b] = 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) words[9] = *n_vox_dev;  // voxel count before this call (k_bi_place)
+    if (blockIdx.x == 0 && threadIdx.x == 0) words[MW_BULK_NVOX0] = *n_vox_dev;  // voxel count before this call (k_bi_place)
     const uint32_t first = blockIdx.x * kPpt * kBiThreads;
     if (threadIdx.x < kPpt * kBiThreads / 32) {  // this block's words of the bitmap of first appearances
         const uint32_t w = first / 32 + threadIdx.x;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kBiThreads) void k_bi_claim(Slot *table, uint32_t m
                 h[k] = hash_key(key[k], shift) & mask;
             } else {
                 pt_info[i] = make_uint2(kInvalidSlot, 0u);
-                __hip_atomic_store(words + 5, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // LOM_ERR_RANGE for this call
+                __hip_atomic_store(words + MW_RANGE, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // LOM_ERR_RANGE for this call
             }
         }
     }
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kBiThreads) void k_bi_colscan(uint32_t *hist, uint3
 {
     constexpr uint32_t kSlices = kBiThreads / 64;
     __shared__ uint32_t s_slice[kSlices][64];
-    if (words[5] == seq) return;
+    if (words[MW_RANGE] == seq) return;
     const uint32_t lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
     const uint32_t part = blockIdx.x * 64 + lane;
     const bool live = part < n_parts;
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(kBiThreads) void k_bi_colscan(uint32_t *hist, uint3
     }
     if (slice == 0 && live) {
         part_total[part] = total;
-        if (total > part_max) __hip_atomic_store(words + 8, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (total > part_max) __hip_atomic_store(words + MW_BULK_BACK, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(kBiThreads) void k_bi_scatter(uint32_t n, const uin
 {
     extern __shared__ uint32_t s_cur[];  // [n_parts] write cursor of this block in every partition's list
     __shared__ uint32_t s_w[kBiThreads / 64];
-    if (words[5] == seq || words[8] == seq) return;
+    if (words[MW_RANGE] == seq || words[MW_BULK_BACK] == seq) return;
     const uint32_t first = blockIdx.x * kPpt * kBiThreads;
     uint2 info[kPpt];
 #pragma unroll
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(kThreads) void k_bi_group(Slot *table, const uint32
     __shared__ uint16_t s_sst[kEntries];   // first position of the voxel's survivors in the output
     __shared__ uint32_t s_grp[kPartMax];
     __shared__ uint32_t s_w[kThreads / 64];
-    if (words[5] == seq || words[8] == seq) return;
+    if (words[MW_RANGE] == seq || words[MW_BULK_BACK] == seq) return;
     const uint32_t base = part_start[blockIdx.x];
     const uint32_t P = part_start[blockIdx.x + 1] - base;
     if (P == 0) return;
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(kThreads) void k_bi_flagscan(const uint32_t *__rest
 {
     __shared__ uint32_t s_w[kThreads / 64];
     __shared__ uint32_t s_last;
-    if (words[5] == seq || words[8] == seq) return;
+    if (words[MW_RANGE] == seq || words[MW_BULK_BACK] == seq) return;
     const uint32_t w0 = blockIdx.x * kBiTileWords + threadIdx.x * 4;
     uint32_t c[4], sum = 0;
 #pragma unroll
@@ -439,8 +439,8 @@ __global__ __launch_bounds__(kThreads) void k_bi_place(Slot *table, uint32_t n, 
                                                        uint32_t *n_vox_dev, uint32_t seq, const uint32_t *words)
 {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n || words[5] == seq || words[8] == seq) return;
-    const uint32_t n_vox_before = words[9];
+    if (j >= n || words[MW_RANGE] == seq || words[MW_BULK_BACK] == seq) return;
+    const uint32_t n_vox_before = words[MW_BULK_NVOX0];
     if (j == 0) *n_vox_dev = n_vox_before + *new_total;
     const uint32_t row = ent_row[j];
     if (row == kBiDropped) return;

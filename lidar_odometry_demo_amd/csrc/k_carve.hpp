@@ -1,5 +1,5 @@
 // Ray carving (include/lidar_odometry_amd.h, "ray carving"): k_carve_hits, k_carve_walk and k_carve_flag.  Device code
-// only; voxel_map.hip is the one translation unit that instantiates and launches it.
+// only; map_carve.hip is the one translation unit that instantiates and launches it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,7 +11,7 @@
 
 namespace lom {
 
-// the carve's own status words (scr[S_CARVE_WORDS], zeroed per call): the host reads them in one read-back
+// the carve's own status words (scratch slot S_CARVE_WORDS, zeroed per call): the host reads them in one read-back
 enum {
     CW_ERROR = 0,      // a non-finite / out-of-range endpoint, or a walk that left the index range
     CW_CROSSED = 1,    // live voxels some ray crossed

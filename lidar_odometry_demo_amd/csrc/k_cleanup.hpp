@@ -1,4 +1,4 @@
-// radiusCleanup: k_cleanup_flag / mark / scan and k_compact.  Device code only; voxel_map.hip is the one translation unit
+// radiusCleanup: k_cleanup_flag / mark / scan and k_compact.  Device code only; map_erase.hip is the one translation unit
 // that instantiates and launches it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -52,11 +52,11 @@ __global__ void k_cleanup_mark(Slot *table, uint32_t mask, uint32_t shift, const
 }
 
 // the same flags and their exclusive scan in one kernel (kItems consecutive voxels per thread, <= 256
-// workgroups): keep[], newid[] and the number of voxels kept (words[4])
+// workgroups): keep[], newid[] and the number of voxels kept (words[MW_COUNT])
 // `from`: the scan was enqueued behind an align on the same stream (lom_map_radius_cleanup_after_align) and takes its
 // centre from the pose that align ended with -- lidar_odometry.cpp:65-67: current_transform_ = result, then
 // radiusCleanup(current_transform_.translation, ...).  An align that has not ended there (more outer iterations to
-// come, a give-up) leaves words[12] = 0 and the scan undone; otherwise words[12] = seq and words[13..15] = the bits of
+// come, a give-up) leaves words[MW_SPEC_SEQ] = 0 and the scan undone; otherwise it is seq and words[MW_SPEC_CX..CZ] = the bits of
 // the centre used: the host takes the result only for exactly the centre it would have passed.  keep[] / newid[] are
 // scratch either way.
 template <int kItems>
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kThreads) void k_cleanup_scan(const float *pts, con
         cy = cs->pose_t[1];
         cz = cs->pose_t[2];
         if (!usable) {
-            if (blockIdx.x == 0 && threadIdx.x == 0) words[12] = 0u;
+            if (blockIdx.x == 0 && threadIdx.x == 0) words[MW_SPEC_SEQ] = 0u;
             return;
         }
     }
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(kThreads) void k_cleanup_scan(const float *pts, con
     unsigned long long total;
     const unsigned long long excl = block_scan64(mine, s_w, total);
     bool gave_up;
-    const unsigned long long before = grid_prefix64(total, agg, seq, words + 7, s_w, gave_up, test_fail_from);
+    const unsigned long long before = grid_prefix64(total, agg, seq, words + MW_GRID, s_w, gave_up, test_fail_from);
     uint32_t run = (uint32_t)(before + excl);
 #pragma unroll
     for (int k = 0; k < kItems; k++) {
@@ -108,12 +108,12 @@ __global__ __launch_bounds__(kThreads) void k_cleanup_scan(const float *pts, con
         run += f[k];
     }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        words[4] = (uint32_t)(before + total);
+        words[MW_COUNT] = (uint32_t)(before + total);
         if (from) {
-            words[13] = __float_as_uint(cx);
-            words[14] = __float_as_uint(cy);
-            words[15] = __float_as_uint(cz);
-            words[12] = seq;
+            words[MW_SPEC_CX] = __float_as_uint(cx);
+            words[MW_SPEC_CY] = __float_as_uint(cy);
+            words[MW_SPEC_CZ] = __float_as_uint(cz);
+            words[MW_SPEC_SEQ] = seq;
         }
     }
 }

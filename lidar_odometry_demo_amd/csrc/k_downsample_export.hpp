@@ -1,4 +1,4 @@
-// The fused down-sampler (k_ds_*), the export (k_export_*) and k_transform.  Device code only; voxel_map.hip is the one translation unit
+// The fused down-sampler (k_ds_*), the export (k_export_*) and k_transform.  Device code only; map_cloud.hip is the one translation unit
 // that instantiates and launches it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -6,8 +6,8 @@
 #include <cstdint>
 
 #include "grid_scan.hpp"
-#include "k_table.hpp"
 #include "lom_internal.hpp"
+#include "table_device.hpp"
 
 namespace lom {
 
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void k_ds_emit(Slot *table, uint32_t n, c
     unsigned long long total;
     const unsigned long long excl = block_scan64(mine, s_w, total);
     bool gave_up;
-    const unsigned long long before = grid_prefix64(total, agg, seq, words + 7, s_w, gave_up, test_fail_from);
+    const unsigned long long before = grid_prefix64(total, agg, seq, words + MW_GRID, s_w, gave_up, test_fail_from);
     uint32_t at = (uint32_t)(before + excl);
 #pragma unroll
     for (int k = 0; k < kItems; k++) {
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(kThreads) void k_ds_emit(Slot *table, uint32_t n, c
         head[h[k]] = 0xFFFFFFFFu;
     }
     // voxels kept; a grid that gave up reports none (whoever consumes the count on the device finds an empty cloud)
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) words[4] = gave_up ? 0u : (uint32_t)(before + total);
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) words[MW_COUNT] = gave_up ? 0u : (uint32_t)(before + total);
 }
 
 // ---------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // The streaming insert (batches up to kOnePassMax points, and the fallback of everything else): k_ins_claim2 /
-// assign2 / scatter2 / place2, and k_ins_heads / k_ins_assign of its multi-launch form.  Device code only; voxel_map.hip is the one translation unit
+// assign2 / scatter2 / place2, and k_ins_heads / k_ins_assign of its multi-launch form.  Device code only; map_insert.hip is the one translation unit
 // that instantiates and launches it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,8 +7,8 @@
 #include <cstdint>
 
 #include "grid_scan.hpp"
-#include "k_table.hpp"
 #include "lom_internal.hpp"
+#include "table_device.hpp"
 
 namespace lom {
 
@@ -26,7 +26,7 @@ __global__ void k_ins_heads(const Slot *table, uint32_t n, const uint32_t *pt_sl
     if (i >= n) return;
     const uint32_t h = pt_slot[i];
     unsigned long long f = 0;
-    if (words[5] != seq && h != 0xFFFFFFFFu && bkt_head[h] == i) {
+    if (words[MW_RANGE] != seq && h != 0xFFFFFFFFu && bkt_head[h] == i) {
         f = (unsigned long long)bkt_cnt[h] << 32;
         if (table[h].slab == kNoSlab) f |= 1ull;  // voxel_grid.h:83 it == end()
     }
@@ -39,7 +39,7 @@ __global__ void k_ins_assign(Slot *table, uint32_t n, const uint32_t *pt_slot, c
                              uint32_t *bkt_old, uint32_t seq, const uint32_t *words)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || words[5] == seq) return;
+    if (i >= n || words[MW_RANGE] == seq) return;
     const uint32_t h = pt_slot[i];
     if (h == 0xFFFFFFFFu || bkt_head[h] != i) return;
     const uint32_t n_vox_before = *n_vox_dev;  // device-side voxel counter (bumped by k_ins_place2)
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kThreads) void k_ins_claim2(Slot *table, uint32_t m
     int ix = 0, iy = 0, iz = 0;
     if (!voxel_index(p[0], vs, ix) || !voxel_index(p[1], vs, iy) || !voxel_index(p[2], vs, iz)) {
         pt_slot[i] = kInvalidSlot;
-        __hip_atomic_store(words + 5, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // LOM_ERR_RANGE for this call
+        __hip_atomic_store(words + MW_RANGE, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // LOM_ERR_RANGE for this call
         return;
     }
     const uint32_t h = claim_slot(table, mask, shift, pack_key(ix, iy, iz));
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(kThreads) void k_ins_assign2(Slot *table, uint32_t 
 {
     __shared__ unsigned long long s_w[8];
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    const bool failed = words[5] == seq;  // a point of this call was out of range: nothing is inserted
+    const bool failed = words[MW_RANGE] == seq;  // a point of this call was out of range: nothing is inserted
     uint32_t h = kInvalidSlot;
     bool is_head = false, is_new = false;
     uint32_t old_count = 0, m = 0;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kThreads) void k_ins_assign2(Slot *table, uint32_t 
     const unsigned long long v = ((unsigned long long)m << 32) | (is_new ? 1ull : 0ull);
     const unsigned long long excl = block_scan64(v, s_w, total);
     bool gave_up;
-    const unsigned long long before = grid_prefix64(total, agg, seq, words + 7, s_w, gave_up, test_fail_from);
+    const unsigned long long before = grid_prefix64(total, agg, seq, words + MW_GRID, s_w, gave_up, test_fail_from);
     // A workgroup without a prefix assigns nothing; what the others assigned before the give-up is taken back by
     // k_ins_place2 (slab ids at or beyond the voxel counter, which such a call does not advance).
     if (is_head && !gave_up) {
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void k_ins_assign2(Slot *table, uint32_t 
             slab_key[slab] = table[h].key;
         }
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0 && !gave_up) words[0] = (uint32_t)(before + total);  // new voxels of this call
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0 && !gave_up) words[MW_NEW_VOX] = (uint32_t)(before + total);  // new voxels of this call
 }
 
 __global__ __launch_bounds__(kThreads) void k_ins_scatter2(uint32_t n, const uint32_t *__restrict__ pt_slot,
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void k_ins_scatter2(uint32_t n, const uin
                                                            const uint32_t *words)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || words[5] == seq || words[7] == seq) return;  // a call that failed (range / grid give-up) inserts nothing
+    if (i >= n || words[MW_RANGE] == seq || words[MW_GRID] == seq) return;  // a call that failed (range / grid give-up) inserts nothing
     const uint32_t h = pt_slot[i];
     const uint32_t off = bkt_off[h];
     items[off + pt_pos[i]] = i;
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void k_ins_place2(Slot *table, uint32_t n
     const uint32_t h = pt_slot[i];
     if (h == kInvalidSlot) return;
     const bool is_head = bkt_head[h] == i;  // only this thread resets the word, and only after this read
-    if (words[7] == seq) {
+    if (words[MW_GRID] == seq) {
         // the scan of k_ins_assign2 gave up part-way: take back the slab ids the workgroups before the give-up
         // handed to NEW voxels (at or beyond the voxel counter, which this call does not advance), so that the
         // table is what it was before the call -- apart from claimed keys without a voxel, as after a range error
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void k_ins_place2(Slot *table, uint32_t n
             const uint32_t slab = table[h].slab;
             if (slab != kNoSlab && slab >= *n_vox_dev) table[h].slab = kNoSlab;
         }
-    } else if (words[5] != seq) {
+    } else if (words[MW_RANGE] != seq) {
         const uint32_t old = bkt_old[h];
         const uint32_t slab = table[h].slab;
         const uint32_t m = pt_m[i];
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void k_ins_place2(Slot *table, uint32_t n
             table[h].count = nc;
             slab_count[slab] = nc;
         }
-        if (i == 0) *n_vox_dev += words[0];  // point 0 is always the head of its voxel's bucket... and exists once
+        if (i == 0) *n_vox_dev += words[MW_NEW_VOX];  // point 0 is always the head of its voxel's bucket... and exists once
     }
     if (is_head) {  // scratch back to rest
         bkt_cnt[h] = 0u;

@@ -1,6 +1,6 @@
 // Generic exclusive prefix scan in global memory (the multi-launch fallback of the map's single-pass kernels): k_scan_tile,
 // k_scan_add and the host recursion scan_exclusive.  Device code only; voxel_map.hip is the one translation unit
-// that instantiates and launches it.
+// that instantiates and launches it -- the other map files scan through its scan_u32 / scan_u64 (map_internal.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,16 +81,6 @@ static int scan_exclusive(lom_map *m, const T *in, T *out, uint32_t n, T *d_tota
     hipLaunchKernelGGL(k_scan_add<T>, dim3(blocks_for(n)), dim3(kThreads), 0, m->stream, out, prefix, n);
     LOM_HIP(m, hipGetLastError());
     return LOM_OK;
-}
-
-static size_t scan_tmp_words(uint32_t n)
-{
-    size_t w = 0;
-    while (n > (uint32_t)kScanTile) {
-        n = (n + kScanTile - 1) / kScanTile;
-        w += 2 * (size_t)n;
-    }
-    return w + 16;
 }
 
 }  // namespace lom

@@ -1,6 +1,7 @@
-// The hash table itself and what every map kernel shares: k_table_init, claim_slot, k_rebuild, the 12-byte point
-// accessors, k_restride, and the device-words-to-host kernel k_gather_words.  Device code only; voxel_map.hip is the one translation unit
-// that instantiates and launches it.
+// The hash table's own kernels: k_table_init, k_rebuild, k_restride, and the device-words-to-host kernel k_gather_words.
+// Device code only; voxel_map.hip is the one translation unit that instantiates and launches it -- the other map files
+// reach these kernels through its host functions (map_internal.hpp: table_rebuild, launch_gather_words).  What the other
+// kernel headers share with these kernels (claim_slot, the 12-byte point accessors) is table_device.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 
 #include "grid_scan.hpp"
 #include "lom_internal.hpp"
+#include "table_device.hpp"
 
 namespace lom {
 
@@ -26,24 +28,6 @@ __global__ void k_table_init(Slot *table, uint32_t cap)
     }
 }
 
-__device__ inline uint32_t claim_slot(Slot *table, uint32_t mask, uint32_t shift, unsigned long long key)
-{
-    uint32_t h = hash_key(key, shift) & mask;
-    for (;;) {
-        // Look before the CAS: a slot that already shows this key needs no atomic (most points of a frame fall
-        // into voxels the map already has, and an atomic is a round trip to the memory side).  A stale view
-        // -- the slot still looks empty, or shows another key that is itself final -- only costs the CAS
-        // (keys never change once set) or moves on to the next slot exactly as the CAS would.
-        const unsigned long long seen = __hip_atomic_load(&table[h].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (seen == key) return h;
-        if (seen == kEmptyKey) {
-            const unsigned long long prev = atomicCAS(&table[h].key, kEmptyKey, key);
-            if (prev == kEmptyKey || prev == key) return h;
-        }
-        h = (h + 1) & mask;
-    }
-}
-
 // rebuild the table from the slab arrays (after rehash / cleanup)
 __global__ void k_rebuild(Slot *table, uint32_t mask, uint32_t shift, const unsigned long long *slab_key,
                           const uint32_t *slab_count, uint32_t n_vox)
@@ -56,20 +40,6 @@ __global__ void k_rebuild(Slot *table, uint32_t mask, uint32_t shift, const unsi
     table[h].count = c;
     table[h].slab = s;
 }
-
-__device__ inline const float *point_at(const char *base, size_t i, size_t stride)
-{
-    return reinterpret_cast<const float *>(base + i * stride);
-}
-
-// one 12-byte point as ONE memory instruction: a packed struct tells the compiler that the three floats are
-// contiguous and 4-byte aligned, and it issues global_load / global_store_dwordx3 -- on the scattered slab
-// writes that is one partial-line transaction per point instead of three
-struct __attribute__((packed, aligned(4))) Point3 {
-    float x, y, z;
-};
-__device__ __forceinline__ Point3 load3(const float *p) { return *reinterpret_cast<const Point3 *>(p); }
-__device__ __forceinline__ void store3(float *p, Point3 v) { *reinterpret_cast<Point3 *>(p) = v; }
 
 __global__ void k_set_word(uint32_t *w, uint32_t v)
 {

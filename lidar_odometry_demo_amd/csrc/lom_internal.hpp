@@ -140,7 +140,7 @@ struct BatchAlignBufs {
 };
 // ... of the quality report (lom_match_quality*): staged host scan, winner indices and records of its search, k_match
 // counters, per-workgroup records, per-point residuals -- and the reduced values in pinned host memory; neither the
-// single align's buffers nor the map-maintenance scratch (scr[]) are touched
+// single align's buffers nor the map-maintenance scratch (lom_map::scr) are touched
 struct QualityBufs {
     DeviceBuf src, idx, rec, cnt, part, res;
     PinnedBuf sums;  // LOM_NQSUMS doubles (mapped)
@@ -173,33 +173,9 @@ struct Slabs {
 // points per partition k_bi_group can hold in LDS (its larger shape); bounds LOM_OPT_TEST_BULK_PARTITION_MAX
 constexpr uint32_t kBiPartMax = 1024;
 
-// ---- lom_map::scr[]: the map-maintenance scratch ------------------------------------------------------------------
-// Grow-only device buffers, indexed by the enum below; voxel_map.hip is the only file that touches them.  Most slots
-// have one user.  The shared ones, by operation (element type: meaning):
-//
-//   slot      | insert, 4 kernels       | bulk insert               | radius cleanup     | down-sampler            | export / upload / transform
-//   ----------+-------------------------+---------------------------+--------------------+-------------------------+----------------------------
-//   S_IN_XYZ  | staged host points      | staged host points        |                    | staged host points      | f32[3]: exported / uploaded / transformed xyz
-//   S_IN_NRM  | staged host normals     | staged host normals       |                    | staged host normals     | f32[3]: ... normals
-//   S_PT_SLOT | u32: slot per point     | uint2: slot, old count    |                    | u32: slot per point     |
-//   S_PT_POS  | u32: arrival position   | uint4: partition records  |                    | f32[3]: kept normals    |
-//   S_FLAG    | u64: head flags (multi- | u32: bitmap of first      | u32: keep          | u32: flags (multi-      | u32: counts per slab
-//             |   launch form only)     |   appearances             |                    |   launch form only)     |
-//   S_RANK    | u64: their scan (ditto) | u32: bitmap word prefixes | u32: newid         | u32: ranks (ditto)      | u32: offsets per slab
-//   S_PT_OFF  | u32: bucket offset      | u32: ent_idx              |                    |                         |
-//   S_PT_M    | u32: bucket size        | u32: ent_w                |                    |                         |
-//   S_ITEMS   | u32: bucket lists       |                           |                    | f32[3]: kept xyz        |
-//   S_SCAN    | u64: scan temporaries   |                           | u32: scan temp.    | u32: scan temporaries   | u32: scan temporaries
-//
-// So S_FLAG / S_RANK carry five meanings and S_PT_POS three.  Nothing but call order keeps them apart; in particular
-// the cleanup scan enqueued behind an align (cleanup_scan_behind_align) leaves keep / newid in S_FLAG / S_RANK for a
-// later lom_map_radius_cleanup to take, across whatever the caller does in between.
-// Ray carving (k_carve.hpp) keeps cross / hit / its status words in slots of its own (S_CARVE_*) and uses S_FLAG / S_RANK /
-// S_SCAN exactly as the radius cleanup does (keep, newid, scan temporaries).
-// S_BKT_* and S_DS_HEAD are per table slot and kept "at rest" between calls (ensure_rest); S_MISC holds the status
-// words ([0..1] u64 scan total, [4] u32 scan total / count, [5] range error, [6] voxel counter, [7] grid give-up,
-// [8] bulk insert sent back, [9..10] bulk insert, [12..15] cleanup scan behind an align) and, from byte 256, the block
-// aggregates of the single-pass kernels.
+// ---- lom_map::scr: the map-maintenance scratch --------------------------------------------------------------------
+// Grow-only device buffers, indexed by the enum below; the five files of the voxel map are the only ones that touch
+// them.  Who keeps what in which slot is tabulated in map_internal.hpp; the status words of S_MISC are map_words.hpp.
 enum {
     S_IN_XYZ = 0,
     S_IN_NRM,
@@ -310,7 +286,7 @@ struct lom_map : lom::DeviceHandle {
     bool opt_dense_cleanup = false;  // LOM_DENSE_CLEANUP=1 at create: every radius cleanup closes its holes at once (as until round 4)
     void (*idle_hook)(void *) = nullptr;  // lom_map_set_align_idle_hook: one shot
     void *idle_user = nullptr;
-    // the scan of a radius cleanup enqueued behind an align (lom_map_radius_cleanup_after_align, voxel_map.hip)
+    // the scan of a radius cleanup enqueued behind an align (lom_map_radius_cleanup_after_align, map_erase.hip)
     float spec_radius = 0.f;     // > 0: the next device-resident align on this handle enqueues it
     bool spec_inflight = false;  // scan and read-back are on the stream; what they were made for:
     float spec_r = 0.f;
@@ -381,8 +357,8 @@ int resolve_pending(lom_map *m);  // voxel_map.hip: redo the last single-pass in
 int map_init(lom_map *m, size_t capacity_hint);  // voxel_map.hip: status words and the first table of a new map (lom_map_create)
 int settle_map(lom_map *map);  // voxel_map.hip: settle a pending insert and the voxel count, under the map's settle lock
 void map_free(lom_map *m);     // voxel_map.hip: the table and both slab sets (lom_map_destroy)
-void cleanup_scan_behind_align(lom_map *m);  // voxel_map.hip: see lom_map_radius_cleanup_after_align
-// voxel_map.hip: the erase of the ray carve, for an erase whose decision is made elsewhere (vote.hip), in this order --
+void cleanup_scan_behind_align(lom_map *m);  // map_erase.hip: see lom_map_radius_cleanup_after_align
+// map_erase.hip: the erase of the ray carve, for an erase whose decision is made elsewhere (vote.hip), in this order --
 //   map_settle_nvox: a pending insert is settled, m->n_vox is exact;
 //   erase_begin: room for keep / newid / the scan's temporaries of m->n_vox slabs; the call counts as a change of the map
 //     (call_seq, mutations) and a cleanup scan armed behind an align is never taken now; *keep: one word per slab to fill;

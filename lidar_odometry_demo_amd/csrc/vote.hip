@@ -1,7 +1,7 @@
 // Scan votes: every archived scan at its pose votes on the voxels of an assembled map -- seen, or seen through -- and a
 // rule on the two counts erases what moved.  Definitions: include/lidar_odometry_amd.h ("scan votes"); kernels:
 // k_vote.hpp; host planning (parameter ranges, slices, step bound): vote_host.cpp; DESIGN.md 7i.
-// New code beside the map path: the erase is the carve's (erase_begin / erase_rank / erase_finish of voxel_map.hip), the
+// New code beside the map path: the erase is the carve's (erase_begin / erase_rank / erase_finish of map_erase.hip), the
 // descriptors are the assembly's, and no default path launches any of this.
 #include <algorithm>
 #include <cstring>
