@@ -103,7 +103,12 @@ int lom_map_radius_cleanup(lom_map *m, const float center[3], float radius); /* 
  * only reads the map and writes scratch) behind its last solve, with the centre taken from its own result in HBM, and
  * the lom_map_radius_cleanup that follows takes that scan's result if -- and only if -- its centre and radius are
  * bit for bit what the scan used and the map has not been touched in between; otherwise it runs as if this had never
- * been called.  One shot (the next align only), map handles only (not scan contexts); results never differ. */
+ * been called.  "Touched" is any call that changes the map (insert, cleanup, carve, votes, clear, a raised
+ * lom_map_set_max_points) and any call that writes the scratch the scan's result waits in: lom_map_export and
+ * lom_map_point_count.  Searches, aligns, quality reports, carve counts, scan votes, lom_map_size, lom_map_status,
+ * upload and transform leave it takeable.  A scan that is not taken is never reported: should it have given up,
+ * lom_map_status does not say so, since no call of the caller's failed.  One shot (the next align only), map handles only
+ * (not scan contexts); results never differ. */
 int lom_map_radius_cleanup_after_align(lom_map *m, float radius);
 int64_t lom_map_size(const lom_map *m);        /* number of voxels, :248-251 */
 int64_t lom_map_point_count(const lom_map *m); /* number of stored points */

@@ -292,6 +292,7 @@ struct lom_map : lom::DeviceHandle {
     float spec_r = 0.f;
     uint32_t spec_seq = 0, spec_tag = 0, spec_nv = 0;
     uint64_t spec_mutations = 0;
+    uint32_t spec_gave_up_seq = 0;  // the last such scan that gave up and was not taken: no call's number, map_status skips it
     uint32_t cleanups_taken = 0;  // radius cleanups that used such a scan (lom_map_debug_counter)
     unsigned long long report_seq = 0, lm_seq = 0, lm_launches = 0;
     int last_replayed = 0;  // outer iterations of the last align on this handle that the replay fold accounted for (lom_debug_replayed_iterations)

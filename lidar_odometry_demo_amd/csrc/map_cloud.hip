@@ -202,6 +202,8 @@ int64_t lom_map_export(lom_map *m, int mode, float *xyz_out, float *nrm_out, siz
     if ((rc = refresh_nvox(m)) != LOM_OK) return rc;
     if (m->n_vox == 0) return 0;
     const uint32_t nv = m->n_vox;
+    // (counts and offsets go where a cleanup scan behind an align leaves keep / newid: scan_temps drops such a scan, and
+    // the radius cleanup that follows an export or a pointCount runs its own)
     uint32_t *cnt, *off, *scan_tmp;
     if ((rc = scan_temps(m, nv, nv, &cnt, &off, &scan_tmp)) != LOM_OK) return rc;
     hipLaunchKernelGGL(k_export_counts, dim3(blocks_for(nv)), dim3(kThreads), 0, m->stream, m->slabs.count, nv, mode, cnt);

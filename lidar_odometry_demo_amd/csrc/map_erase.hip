@@ -56,9 +56,9 @@ void cleanup_scan_behind_align(lom_map *m)
 {
     const float radius = m->spec_radius;
     m->spec_radius = 0.f;  // armed for one align
-    // (a scan nobody has asked for since -- the caller did something else with the map -- is simply superseded: the
-    // read-back of this one follows it on the stream and carries the next tag)
-    m->spec_inflight = false;
+    // (a scan nobody has asked for since -- the caller did something else with the map -- is superseded: the read-back
+    // of this one follows it on the stream and carries the next tag; its give-up word is looked at before that)
+    drop_cleanup_behind_align(m);
     if (!(radius > 0.f) || m->parent || m->n_vox_stale || m->pending_n.load() || m->n_vox == 0 || !m->align_state.p) return;
     const uint32_t nv = m->n_vox;
     // (scratch that has to grow: the plain path does that; an allocation here would wait for the align)
@@ -78,6 +78,30 @@ void cleanup_scan_behind_align(lom_map *m)
     m->spec_mutations = m->mutations.load();
 }
 
+// A scan that gave up has left its sequence number in MW_GRID, where map_status looks for calls that gave up.  Taken, the
+// cleanup redoes it and says so (status_seq).  Not taken, it is nobody's call and nobody's to repeat: whoever ends its
+// life without taking it -- another centre or radius, the map touched, its scratch handed to a writer, the next armed
+// align -- notes the number here, and map_status, which may come while the scan is still in flight, skips that number.
+static void note_scan_gave_up(lom_map *m, const uint32_t *got)  // got: in kSpecWords' order
+{
+    if (got[1] == m->spec_seq) m->spec_gave_up_seq = m->spec_seq;
+}
+
+void peek_cleanup_behind_align(lom_map *m)
+{
+    if (!m->spec_inflight) return;
+    uint32_t got[kSpecWordCount];
+    hipError_t e = hipSuccess;
+    // (the align has returned, so the read-back is through: no wait.  A stream that failed: whoever uses it next reports it)
+    if (poll_words(m, kSpecWordsOffset, m->spec_tag, kSpecWordCount, got, &e) == WORDS_ARRIVED) note_scan_gave_up(m, got);
+}
+
+void drop_cleanup_behind_align(lom_map *m)
+{
+    peek_cleanup_behind_align(m);
+    m->spec_inflight = false;
+}
+
 // the result of a scan enqueued behind an align, if it was made for this call: true = *seq_out is the scan's sequence
 // number, *kept_out the number of voxels it keeps, *grid_out its give-up word; false = not usable
 static bool take_cleanup_behind_align(lom_map *m, const float center[3], float radius, uint32_t *seq_out, uint32_t *kept_out,
@@ -94,7 +118,10 @@ static bool take_cleanup_behind_align(lom_map *m, const float center[3], float r
     const bool usable = got[2] == m->spec_seq && got[3] == cb[0] && got[4] == cb[1] && got[5] == cb[2] &&
                         std::memcmp(&radius, &m->spec_r, 4) == 0 && m->call_seq == m->spec_seq &&
                         m->mutations.load() == m->spec_mutations && m->n_vox == m->spec_nv && !m->n_vox_stale;
-    if (!usable) return false;
+    if (!usable) {
+        note_scan_gave_up(m, got);
+        return false;
+    }
     *kept_out = got[0];
     *grid_out = got[1];
     *seq_out = m->spec_seq;
@@ -151,7 +178,8 @@ int erase_begin(lom_map *m, uint32_t **keep)
         if ((rc = scan_temps(m, (size_t)nv * 2, nv, keep, &newid, &scan_tmp)) != LOM_OK) return rc;
     }
     // keep / newid go where a cleanup scan armed behind an align may have left its own: that scan is never taken now
-    m->spec_inflight = false;
+    // (scan_temps has said so; an empty map has not asked it)
+    drop_cleanup_behind_align(m);
     ++m->call_seq;
     m->mutations++;
     return LOM_OK;

@@ -33,9 +33,12 @@ namespace lom {
 //   S_ITEMS   | u32: bucket lists       |                           |                    | f32[3]: kept xyz        |
 //   S_SCAN    | u64: scan temporaries   |                           | u32: scan temp.    | u32: scan temporaries   | u32: scan temporaries
 //
-// So S_FLAG / S_RANK carry five meanings and S_PT_POS three.  Nothing but call order keeps them apart; in particular
-// the cleanup scan enqueued behind an align (cleanup_scan_behind_align) leaves keep / newid in S_FLAG / S_RANK for a
-// later lom_map_radius_cleanup to take, across whatever the caller does in between.
+// So S_FLAG / S_RANK carry five meanings and S_PT_POS three.  Within a call, call order keeps them apart.  One user
+// leaves them behind for a LATER call: the cleanup scan enqueued behind an align (cleanup_scan_behind_align) leaves keep /
+// newid in S_FLAG / S_RANK for the next lom_map_radius_cleanup to take.  So whoever is handed S_FLAG / S_RANK to write --
+// scan_temps with room > 0, and bulk_scratch (map_insert.hip), the one user that grows them itself -- drops that scan first
+// (drop_cleanup_behind_align): the cleanup then runs its own.  Readers of the map, and users of other slots, leave it
+// takeable (tests/test_map_call_order_gpu.py walks every public call through that gap).
 // Ray carving (k_carve.hpp) keeps cross / hit / its status words in slots of its own (S_CARVE_*) and uses S_FLAG / S_RANK /
 // S_SCAN exactly as the radius cleanup does (keep, newid, scan temporaries).
 // S_BKT_* and S_DS_HEAD are per table slot and kept "at rest" between calls (ensure_rest); S_MISC holds the status
@@ -90,12 +93,22 @@ size_t scan_tmp_words(uint32_t n);
 int scan_u32(lom_map *m, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *d_total, uint32_t *tmp);
 int scan_u64(lom_map *m, const unsigned long long *in, unsigned long long *out, uint32_t n, unsigned long long *d_total,
              unsigned long long *tmp);
+// map_erase.hip: a cleanup scan enqueued behind an align that nobody has taken yet.  Its keep / newid are about to be
+// overwritten, or the call it was made for cannot follow any more: it is never taken now.  Should it have given up, its
+// sequence number in MW_GRID is nobody's call: noted for map_status (spec_gave_up_seq), which looks with `peek` while
+// the scan is still in flight.
+void drop_cleanup_behind_align(lom_map *m);
+void peek_cleanup_behind_align(lom_map *m);
+
 // flags / their ranks / the scan's temporaries for a scan over n elements of T, from S_FLAG / S_RANK / S_SCAN: the first
-// two with room for `room` elements (0: as large as they are, their contents kept), the third as scan_tmp_words(n) asks
+// two with room for `room` elements (0: as large as they are, their contents kept -- a taken cleanup scan's; otherwise
+// the caller writes them, and a cleanup scan behind an align that left its own there is dropped), the third as
+// scan_tmp_words(n) asks
 template <class T>
 int scan_temps(lom_map *m, size_t room, uint32_t n, T **flag, T **rank, T **tmp)
 {
     int rc;
+    if (room) drop_cleanup_behind_align(m);
     if ((rc = scratch(m, S_FLAG, room, flag)) != LOM_OK) return rc;
     if ((rc = scratch(m, S_RANK, room, rank)) != LOM_OK) return rc;
     return scratch(m, S_SCAN, scan_tmp_words(n), tmp);

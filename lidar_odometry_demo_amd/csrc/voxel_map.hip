@@ -292,6 +292,9 @@ int map_status(lom_map *m)
     if (rc != LOM_OK) return rc;
     const uint32_t checked = m->status_seq;
     m->status_seq = m->call_seq;
+    // (a cleanup scan behind an align that gave up is no call of the user's: taken, the cleanup redoes it; not taken, or
+    // not yet, its number in MW_GRID is skipped below)
+    peek_cleanup_behind_align(m);
     if (m->n_vox_stale) {
         m->n_vox = r[MW_NVOX];
         m->n_vox_ub = m->n_vox;
@@ -303,7 +306,7 @@ int map_status(lom_map *m)
     // a bulk insert with a partition beyond k_bi_group's LDS wrote nothing: the four-kernel path redoes it, like a
     // single-pass insert whose scan gave up
     const uint32_t grid_seq = (pending && r[MW_BULK_BACK] == m->pending_seq) ? r[MW_BULK_BACK] : r[MW_GRID];
-    if (grid_seq > checked && grid_seq != m->grid_resolved_seq) {
+    if (grid_seq > checked && grid_seq != m->grid_resolved_seq && grid_seq != m->spec_gave_up_seq) {
         if (grid_seq == m->pending_seq && pending) {
             m->grid_redos++;
             m->grid_resolved_seq = grid_seq;

@@ -1,7 +1,10 @@
 """Device-to-device exchange between ranks (lom_comm_attach_p2p), two ranks as two processes on the
 one GPU a gpurun box has: each rank's buffer is IPC-mapped into the other process, the ranks' k_lm
 kernels run side by side and exchange their totals through those mappings.  (On a multi-GPU node the
-same stores travel over xGMI; that part cannot be exercised here.)"""
+same stores travel over xGMI; that part cannot be exercised here.)
+
+Every test runs in both search modes (search_mode below), the full-size one counted only.  The rank processes are
+spawned while the variable is set and create their handles under it: each reports what it saw."""
 import ctypes as C
 import multiprocessing as mp
 import os
@@ -12,7 +15,27 @@ import pytest
 
 from tests.conftest import ROOT
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("counted_search")]
+pytestmark = pytest.mark.gpu
+
+
+# ("counted" is what these tests ran under before there were two modes: its cases keep their ids, "product" adds to them)
+COUNTED = pytest.param("counted", id=pytest.HIDDEN_PARAM)
+
+
+@pytest.fixture(autouse=True, params=["product", COUNTED])
+def search_mode(request, monkeypatch):
+    """As tests/test_gpu_parity.py: "product" = the handles as a caller gets them (cand_total / occ_total read 0),
+    "counted" = LOM_COUNT_CANDIDATES=1 at create.  Set in os.environ, which the spawned rank processes inherit."""
+    monkeypatch.setenv("LOM_COUNT_CANDIDATES", "1" if request.param == "counted" else "0")
+    return request.param
+
+
+counted_only = pytest.mark.parametrize("search_mode", [COUNTED], indirect=True)
+
+
+def _mode_seen():
+    """what a rank process found in its environment when it created its handles"""
+    return "counted" if os.environ.get("LOM_COUNT_CANDIDATES") == "1" else "product"
 
 
 def _rank_main(rank, world, ident, q):
@@ -55,11 +78,11 @@ def _rank_main(rank, world, ident, q):
     out.append((p.translation.tobytes(), p.rotation.tobytes(), dict(m.stats)))
     L.lom_comm_finalize(g.handle)
     L.lom_host_comm_destroy(hc)
-    q.put((rank, "ok", out))
+    q.put((rank, "ok", out, _mode_seen()))
 
 
 @pytest.mark.parametrize("world", [2, 3])
-def test_ranks_exchange_on_the_device(lom, world):
+def test_ranks_exchange_on_the_device(lom, world, search_mode):
     from tests import scenes
 
     ctx = mp.get_context("spawn")
@@ -73,6 +96,7 @@ def test_ranks_exchange_on_the_device(lom, world):
         p.join(timeout=60)
         assert p.exitcode == 0
     assert all(r[1] == "ok" for r in res), res
+    assert all(r[3] == search_mode for r in res), res      # the switch reached every rank process
     sm = scenes.small_synth_case()
     g = lom.VoxelGrid(0.5, 20)
     g.addCloud(sm["map_xyz"], sm["map_nrm"])
@@ -86,6 +110,8 @@ def test_ranks_exchange_on_the_device(lom, world):
         assert dt < 1e-6 and dr < 1e-6, (dt, dr)         # and with the single-rank pose (summation order differs)
         for k in ("outer_iterations", "queries", "cand_total", "occ_total", "valid_last"):
             assert s0[k] == s1[k] == m.stats[k], k       # totals over all ranks
+        # the reference-algorithm counts: the ranks' handles produced them only when counted
+        assert (s0["cand_total"] > 0 and s0["occ_total"] > 0) if search_mode == "counted" else (s0["cand_total"] == s0["occ_total"] == 0)
     # after the forced failure (entries 2 and 3): host exchange, same answer as the first align
     ref = m.align(g, sm["scan"], lom.Pose3D((0.0, 0.0, 0.0), scenes.angle_axis_q(0.01, (0, 0, 1))))
     for i in (2, 3):
@@ -123,6 +149,7 @@ def _rank_main_c4(rank, world, ident, q, case_dir):
     q.put((rank, "ok", (p.translation.tobytes(), p.rotation.tobytes(), dict(m.stats))))
 
 
+@counted_only
 @pytest.mark.parametrize("world", [2, 3])
 def test_c4_range_sharded_on_the_device(lom, oracle, world, tmp_path):
     """BASELINE.json configs[3] (C4): the 128 x 2048 scan split into `world` contiguous index ranges, the
@@ -228,10 +255,10 @@ def _rank_main_give_up(rank, world, ident, q):
     out.append((p.translation.tobytes(), p.rotation.tobytes(), dict(m.stats), 0.0))
     L.lom_comm_finalize(g.handle)
     L.lom_host_comm_destroy(hc)
-    q.put((rank, "ok", out))
+    q.put((rank, "ok", out, _mode_seen()))
 
 
-def test_one_rank_gives_up_late_and_all_ranks_recover(lom):
+def test_one_rank_gives_up_late_and_all_ranks_recover(lom, search_mode):
     from tests import scenes
 
     world = 3
@@ -246,6 +273,7 @@ def test_one_rank_gives_up_late_and_all_ranks_recover(lom):
         p.join(timeout=60)
         assert p.exitcode == 0
     assert all(r[1] == "ok" for r in res), res
+    assert all(r[3] == search_mode for r in res), res      # the switch reached every rank process
     sm = scenes.small_synth_case()
     g = lom.VoxelGrid(0.5, 20)
     g.addCloud(sm["map_xyz"], sm["map_nrm"])
