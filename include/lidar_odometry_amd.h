@@ -1422,6 +1422,147 @@ int lom_occupancy_classify(lom_occupancy *g, const lom_occupancy_rule *rule, int
  * on the handle */
 int lom_occupancy_classify_device(lom_occupancy *g, const lom_occupancy_rule *rule, const int8_t **d_out);
 
+/* ---- elevation grid: ground height, slope, step and cost from posed scans (not in the reference) ----------------------
+ * The occupancy grid above is flat: a cell is hit when a point falls into a band around the sensor's z, and it carries no
+ * height.  A ground robot's planner asks for the 2.5-D product beside it -- ground height per cell, slope, step height,
+ * roughness and a traversability cost (the "elevation" and "traversability" layers of grid-map style stacks).  A handle
+ * family of its own: nothing is launched unless a caller creates a grid.  The definition, operation by operation
+ * (tests/elevation_ref.py restates it in numpy f64; every comparison is exact: the accumulators are integers, and every
+ * f64 operation below is rounded on its own, no contraction).  There are no floating-point atomics anywhere.
+ *
+ * Grid.  lom_elevation_geometry = the fields of lom_occupancy_geometry and z_ref.  Cell (ix, iy) covers
+ * [origin + i r, origin + (i + 1) r) per axis; storage is row-major with y as the row, iy * width + ix; the index rule is
+ * floor in f64 from the f32 values, floor(((double)X - (double)origin_x) / (double)r), and a value is "in the grid" iff
+ * the floored quotient q satisfies 0 <= q < width (resp. height), compared before any integer conversion.  r > 0 and
+ * finite, a finite origin, a finite z_ref, 1 <= width, height <= 8192; anything else is LOM_ERR_ARG.  A cell costs
+ * 33 bytes of HBM at rest (a record of 32 bytes: sum, count, zmin, zmax, 12 bytes of padding so that a record is one
+ * aligned 32-byte sector; 1 byte of cost) and 24 more (six f32 layers) from the first lom_elevation_layers on.
+ * Heights are kept in quanta of Q = 2^LOM_ELEV_QUANTUM_LOG2 m = 1/256 m, relative to z_ref.
+ *
+ * Which points count.  lom_elevation_point_params, no defaults: z_lo < 0 < z_hi, min_range > 0, max_range > min_range,
+ * all finite, max_range / resolution <= 2^20; anything else is LOM_ERR_ARG.  For scan k at its pose, the endpoint p',
+ * the origin O, D, L and the cell are exactly steps 1 to 4 of the occupancy definition (step 2's verdict included: a
+ * start cell beyond 2^30 or not finite is LOM_ERR_RANGE for the whole call, before any launch).  A point contributes iff
+ * it is a hit there: L >= min_range, L <= max_range, z_lo <= Dz <= z_hi, and its cell is in the grid; a non-finite
+ * endpoint fails those comparisons by itself.  Then
+ *     h = (double)p'_z - (double)z_ref;
+ *     if !(|h| < 2048) the point does not contribute and counts in points_out_of_height;
+ *     else zq = rint(h * 256.0), ties to even, so |zq| <= 2^19.
+ *
+ * Accumulators per cell, integers, accumulated over calls until lom_elevation_clear:
+ *     count u32 += 1 (empty: 0);  zmin i32 min= zq (empty: INT32_MAX);  zmax i32 max= zq (empty: INT32_MIN);
+ *     sum i64 += zq (empty: 0).
+ * An id given twice counts twice.  More than 2^32 - 1 points in one cell wrap its count: the caller's to avoid.
+ * Integer sums, minima and maxima do not depend on order, so the cells are a pure function of the inputs: independent of
+ * the order of points, scans and calls, and of any kernel tuning (LOM_ELEV_OPT_TEST_WAVE_MERGE).
+ *
+ * Stats.  scans = count; points = the sum of the scans' sizes; points_marked = the points that contributed;
+ * points_out_of_height as above (hits that did not); cells_new = the cells whose count left 0 in this call.  All zero
+ * on an error.
+ *
+ * Derived layers.  lom_elevation_layer_params: min_points >= 1, window R in 1 .. 4 (else LOM_ERR_ARG).  A cell is valid
+ * iff count >= min_points; its ground height is zmin.  For a valid cell c at (cx, cy) take the valid cells (cx + i, cy + j),
+ * -R <= i, j <= R, that lie in the grid -- c itself, i = j = 0, included -- with d = zmin(cx + i, cy + j) - zmin(c):
+ *  1. The int64 sums n = sum 1, Si = sum i, Sj = sum j, Sii = sum i i, Sij = sum i j, Sjj = sum j j, Sd = sum d,
+ *     Sid = sum i d, Sjd = sum j d.  All exact: n <= 81, |Si|, |Sj| <= 4 * 81 = 324, Sii, |Sij|, Sjj <= 16 * 81 = 1296,
+ *     |d| <= 2^20, so |Sd| <= 81 * 2^20 and |Sid|, |Sjd| <= 324 * 2^20.
+ *  2. The plane d ~ A i + B j + C by Cramer's rule in int64, each 3 x 3 determinant expanded along its first row:
+ *       det   = Sii * (Sjj * n   - Sj  * Sj) - Sij * (Sij * n   - Sj  * Si) + Si  * (Sij * Sj - Sjj * Si)
+ *       a_num = Sid * (Sjj * n   - Sj  * Sj) - Sij * (Sjd * n   - Sj  * Sd) + Si  * (Sjd * Sj - Sjj * Sd)
+ *       b_num = Sii * (Sjd * n   - Sj  * Sd) - Sid * (Sij * n   - Sj  * Si) + Si  * (Sij * Sd - Sjd * Si)
+ *       c_num = Sii * (Sjj * Sd  - Sjd * Sj) - Sij * (Sij * Sd  - Sjd * Si) + Sid * (Sij * Sj - Sjj * Si)
+ *     Every product of three sums is bounded by the largest one of its kind: in det, 1296 * 1296 * 81 < 2^28; in a_num
+ *     and b_num, (324 * 2^20) * 1296 * 81 < 2^45.1; in c_num, 1296 * 1296 * (81 * 2^20) < 2^47.1.  A determinant is
+ *     six such products, so |det| < 2^31, |a_num|, |b_num| < 2^47.7 and |c_num| < 2^49.7: all below 2^53, exact in
+ *     int64 and exactly convertible to f64.  det >= 0 always (a Gram determinant).
+ *  3. If det > 0:  A = (double)a_num / (double)det, B and C likewise;
+ *       slope = (sqrt(A * A + B * B) * Q) / (double)resolution            -- the rise over run
+ *       e = (double)d - ((A * (double)i + B * (double)j) + C),  S = sum e * e, added in row-major order (j ascending,
+ *       then i ascending) over the valid cells, starting from 0.0;
+ *       rough = sqrt(S / (double)n) * Q.
+ *  4. If det == 0 (fewer than three valid cells, or collinear ones): slope and rough are NaN.
+ *  5. step = Q * (double)(max |d| over the valid cells among the 8 neighbours |i|, |j| <= 1 in the grid), 0 if none.
+ *  6. span = Q * (double)(zmax(c) - zmin(c)).
+ * The f32 outputs min, max, mean, slope, rough, step: min = (float)((double)z_ref + (double)zmin * Q), max likewise,
+ * mean = (float)((double)z_ref + ((double)sum * Q) / (double)count); slope, rough and step are the f64 values rounded.
+ * All six are NaN where the cell is invalid.
+ *
+ * Cost.  lom_elevation_cost_params: max_slope, max_step, max_rough, max_span, all finite and > 0 (else LOM_ERR_ARG),
+ * widened to f64 and compared with the f64 values above.  int8, row-major, the values of a nav_msgs costmap:
+ *   LOM_ELEV_COST_UNKNOWN (-1) for an invalid cell;
+ *   LOM_ELEV_COST_LETHAL (100) iff span > max_span, or step > max_step, or det > 0 && slope > max_slope;
+ *   else floor(99 * min(m, 1)) with m = the largest of step / max_step, slope / max_slope and rough / max_rough, the
+ *   latter two taken as 0 where det == 0.
+ * Summary: cells_unknown + cells_lethal + cells_costed = width * height.
+ *
+ * lom_elevation_integrate takes K archived scans exactly as lom_occupancy_integrate takes them: ids, poses and the device
+ * are refused before any launch the same way, the call holds the archive's lock, and the two streams are ordered by
+ * events in both directions.  The _cloud forms integrate one scan that is not in an archive: records of stride_bytes
+ * (>= 12, a multiple of 4) that begin with x, y, z, in host memory, or in HBM behind hip_event_or_null.  count == 0 or
+ * n == 0 is LOM_OK and changes nothing.  All arguments are validated before any device work; a refused call changes
+ * nothing.  Every call returns with its work done.  Calls on one grid are the caller's to serialise.  The error text is
+ * the grid's (lom_elevation_last_error). */
+#define LOM_ELEV_QUANTUM_LOG2 (-8)
+typedef struct lom_elevation lom_elevation;
+typedef struct {
+    float resolution;         /* m per cell */
+    float origin_x, origin_y; /* the corner of cell (0, 0) */
+    uint32_t width, height;   /* cells along x and along y */
+    float z_ref;              /* heights are stored relative to it */
+} lom_elevation_geometry;
+typedef struct {
+    float z_lo, z_hi; /* < 0 < : the band around the scan origin's z */
+    float min_range, max_range;
+} lom_elevation_point_params;
+typedef struct {
+    uint64_t scans, points, points_marked, points_out_of_height, cells_new;
+} lom_elevation_stats;
+typedef struct {
+    uint32_t min_points; /* >= 1 */
+    uint32_t window;     /* R in 1 .. 4: the fit looks at (2R + 1)^2 cells */
+} lom_elevation_layer_params;
+typedef struct {
+    float max_slope, max_step, max_rough, max_span; /* rise over run; m; m; m */
+} lom_elevation_cost_params;
+typedef struct {
+    uint64_t cells_unknown, cells_lethal, cells_costed;
+} lom_elevation_summary;
+enum { LOM_ELEV_COST_UNKNOWN = -1, LOM_ELEV_COST_LETHAL = 100 };
+enum {
+    LOM_ELEV_OPT_TEST_WAVE_MERGE = 1 /* 0: every lane sends its own four atomics; 1 or < 0, the default: the lanes of a
+                                        wave that share a cell are merged first.  A test switch: the cells are the same. */
+};
+int lom_elevation_create(const lom_elevation_geometry *geometry, int device, lom_elevation **out);
+void lom_elevation_destroy(lom_elevation *g);
+const char *lom_elevation_last_error(const lom_elevation *g); /* g == NULL: why the last create on this thread failed */
+int lom_elevation_clear(lom_elevation *g);                    /* every cell to its empty values */
+int lom_elevation_get_geometry(const lom_elevation *g, lom_elevation_geometry *out);
+void *lom_elevation_stream(lom_elevation *g); /* hipStream_t */
+int lom_elevation_device(const lom_elevation *g);
+int lom_elevation_wait_event(lom_elevation *g, void *hip_event);
+int lom_elevation_set_option(lom_elevation *g, int option, int64_t value);
+int lom_elevation_integrate(lom_elevation *g, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses, size_t count,
+                            const lom_elevation_point_params *p, lom_elevation_stats *stats_or_null);
+int lom_elevation_integrate_cloud(lom_elevation *g, const float *xyz, size_t n, size_t stride_bytes,
+                                  const lom_graph_pose *pose, const lom_elevation_point_params *p,
+                                  lom_elevation_stats *stats_or_null);
+int lom_elevation_integrate_cloud_device(lom_elevation *g, const float *d_xyz, size_t n, size_t stride_bytes,
+                                         const lom_graph_pose *pose, const lom_elevation_point_params *p,
+                                         void *hip_event_or_null, lom_elevation_stats *stats_or_null);
+/* the accumulators per cell, row-major; returns width * height and writes at most `cap` entries; any output may be NULL */
+int64_t lom_elevation_cells(lom_elevation *g, uint32_t *count_out, int32_t *zmin_out, int32_t *zmax_out, int64_t *sum_out,
+                            size_t cap);
+/* the six f32 layers over the whole grid; at most `cap` cells go to each output; any output may be NULL */
+int lom_elevation_layers(lom_elevation *g, const lom_elevation_layer_params *lp, float *min_out, float *max_out,
+                         float *mean_out, float *slope_out, float *rough_out, float *step_out, size_t cap);
+/* the cost over the whole grid: at most `cap` cells go to `out` (may be NULL with cap 0); the summary counts all cells */
+int lom_elevation_cost(lom_elevation *g, const lom_elevation_layer_params *lp, const lom_elevation_cost_params *cp,
+                       int8_t *out, size_t cap, lom_elevation_summary *summary_or_null);
+/* the same, left in HBM: *d_out holds width * height cells, complete on the grid's stream, valid until the next call
+ * on the handle */
+int lom_elevation_cost_device(lom_elevation *g, const lom_elevation_layer_params *lp, const lom_elevation_cost_params *cp,
+                              const int8_t **d_out);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;
@@ -1498,6 +1639,11 @@ int lom_odometry_archive_deskewed(lom_odometry *o, lom_archive *a, int64_t *id_o
  * LOM_ERR_STATE before the first frame.  Reads only: no pose, counter or map of the odometry is touched. */
 int lom_odometry_occupancy_scan(lom_odometry *o, lom_occupancy *g, const lom_occupancy_ray_params *p,
                                 lom_occupancy_stats *stats_or_null);
+/* Its twin for an elevation grid on the odometry's device: lom_elevation_integrate_cloud_device behind the front end's
+ * done event, or lom_elevation_integrate_cloud of the host copy of a host-stage frame; the result is the same either way.
+ * LOM_ERR_STATE before the first frame.  Reads only: no pose, counter or map of the odometry is touched. */
+int lom_odometry_elevation_scan(lom_odometry *o, lom_elevation *g, const lom_elevation_point_params *p,
+                                lom_elevation_stats *stats_or_null);
 /* Go on after a loop closure: the keyframe is built again from archived scans at corrected poses.  In this order:
  *  1. the pending keyframe update is waited for (its failure is this call's, and nothing else happens);
  *  2. an armed cleanup behind the align and a pending lom_odometry_hint_next are dropped;

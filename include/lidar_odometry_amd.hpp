@@ -1005,6 +1005,103 @@ private:
     lom_occupancy *h_ = nullptr;
 };
 
+// ---- ElevationGrid (not in the reference) ---------------------------------------------
+// A dense 2-D grid of integer height accumulators on the device: every point of a posed scan that is an occupancy hit
+// adds its quantised height to its cell; layers() derives ground height, slope, roughness and step, cost() the int8
+// values of a costmap (-1 unknown, 0 .. 99, 100 lethal), row-major with y as the row.  Definitions:
+// lidar_odometry_amd.h ("elevation grid").
+using ElevationGeometry = lom_elevation_geometry;        // {resolution, origin_x, origin_y, width, height, z_ref}
+using ElevationPointParams = lom_elevation_point_params;  // {z_lo, z_hi, min_range, max_range}
+using ElevationLayerParams = lom_elevation_layer_params;  // {min_points, window}
+using ElevationCostParams = lom_elevation_cost_params;    // {max_slope, max_step, max_rough, max_span}
+using ElevationStats = lom_elevation_stats;
+using ElevationSummary = lom_elevation_summary;
+
+class ElevationGrid {
+public:
+    struct Cells {  // the accumulators, in quanta of 2^-8 m relative to z_ref
+        std::vector<uint32_t> count;
+        std::vector<int32_t> zmin, zmax;
+        std::vector<int64_t> sum;
+    };
+    struct Layers {  // NaN where a cell is invalid
+        std::vector<float> min, max, mean, slope, rough, step;
+    };
+
+    explicit ElevationGrid(const lom_elevation_geometry &geometry, int device = 0)
+    {
+        const int rc = lom_elevation_create(&geometry, device, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_elevation_last_error(nullptr));
+    }
+    ~ElevationGrid() { lom_elevation_destroy(h_); }
+    ElevationGrid(const ElevationGrid &) = delete;
+    ElevationGrid &operator=(const ElevationGrid &) = delete;
+    lom_elevation *handle() const { return h_; }
+    lom_elevation_geometry geometry() const
+    {
+        lom_elevation_geometry g;
+        check(lom_elevation_get_geometry(h_, &g));
+        return g;
+    }
+    size_t size() const
+    {
+        const lom_elevation_geometry g = geometry();
+        return (size_t)g.width * g.height;
+    }
+    void clear() { check(lom_elevation_clear(h_)); }
+    // the scans `ids` of the archive at `poses`
+    lom_elevation_stats integrate(ScanArchive &archive, const std::vector<int64_t> &ids, const std::vector<lom_graph_pose> &poses,
+                                  const lom_elevation_point_params &params)
+    {
+        if (ids.size() != poses.size()) throw Error(LOM_ERR_ARG, "ElevationGrid::integrate: one pose per id");
+        lom_elevation_stats st;
+        check(lom_elevation_integrate(h_, archive.handle(), ids.data(), poses.data(), ids.size(), &params, &st));
+        return st;
+    }
+    // one scan that is not in an archive
+    lom_elevation_stats integrateCloud(const PointCloud<PointXYZ> &cloud, const lom_graph_pose &pose,
+                                       const lom_elevation_point_params &params)
+    {
+        lom_elevation_stats st;
+        const bool none = cloud.points.empty();
+        check(lom_elevation_integrate_cloud(h_, none ? nullptr : &cloud.points.data()->x, cloud.points.size(), sizeof(PointXYZ),
+                                            &pose, &params, &st));
+        return st;
+    }
+    Cells cells() const
+    {
+        const size_t n = size();
+        Cells c;
+        c.count.assign(n, 0u), c.zmin.assign(n, 0), c.zmax.assign(n, 0), c.sum.assign(n, 0);
+        check(lom_elevation_cells(h_, c.count.data(), c.zmin.data(), c.zmax.data(), c.sum.data(), n));
+        return c;
+    }
+    Layers layers(const lom_elevation_layer_params &lp)
+    {
+        const size_t n = size();
+        Layers l;
+        for (std::vector<float> *v : {&l.min, &l.max, &l.mean, &l.slope, &l.rough, &l.step}) v->assign(n, 0.f);
+        check(lom_elevation_layers(h_, &lp, l.min.data(), l.max.data(), l.mean.data(), l.slope.data(), l.rough.data(),
+                                   l.step.data(), n));
+        return l;
+    }
+    std::vector<int8_t> cost(const lom_elevation_layer_params &lp, const lom_elevation_cost_params &cp,
+                             lom_elevation_summary *summary_or_null = nullptr)
+    {
+        std::vector<int8_t> out(size());
+        check(lom_elevation_cost(h_, &lp, &cp, out.data(), out.size(), summary_or_null));
+        return out;
+    }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_elevation_last_error(h_));
+        return rc;
+    }
+    lom_elevation *h_ = nullptr;
+};
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)
@@ -1155,6 +1252,14 @@ public:
         lom_occupancy_stats st;
         const int rc = lom_odometry_occupancy_scan(h_, grid.handle(), &params, &st);
         if (rc != LOM_OK) throw Error(rc, rc == LOM_ERR_STATE ? "no frame yet" : lom_occupancy_last_error(grid.handle()));
+        return st;
+    }
+    // not in the reference: that cloud at the current pose into an elevation grid (lom_odometry_elevation_scan)
+    lom_elevation_stats elevationScan(ElevationGrid &grid, const lom_elevation_point_params &params)
+    {
+        lom_elevation_stats st;
+        const int rc = lom_odometry_elevation_scan(h_, grid.handle(), &params, &st);
+        if (rc != LOM_OK) throw Error(rc, rc == LOM_ERR_STATE ? "no frame yet" : lom_elevation_last_error(grid.handle()));
         return st;
     }
     // not in the reference: go on after a loop closure -- the keyframe again from the archive's scans `ids` at `poses`,

@@ -795,6 +795,22 @@ def occupancyRule(rule):
     return _struct_from(capi.OccupancyRule, rule, "occupancy rule")
 
 
+def elevationPointParams(params):
+    """capi.ElevationPointParams from one, from a dict with its four fields, or from a 4-tuple in the struct's order (z_lo,
+    z_hi, min_range, max_range).  There are no defaults."""
+    return _struct_from(capi.ElevationPointParams, params, "elevation point parameters")
+
+
+def elevationLayerParams(params):
+    """capi.ElevationLayerParams from one, from a dict, or from a 2-tuple (min_points, window)."""
+    return _struct_from(capi.ElevationLayerParams, params, "elevation layer parameters")
+
+
+def elevationCostParams(params):
+    """capi.ElevationCostParams from one, from a dict, or from a 4-tuple (max_slope, max_step, max_rough, max_span)."""
+    return _struct_from(capi.ElevationCostParams, params, "elevation cost parameters")
+
+
 def classifyNeighbourhood(points, params, details=False, frontend=None):
     """The neighbourhood classifier alone (lom_classify_neighbourhood) on POINT_XYZIRT records whose `ring` is not read:
     (planar xyz, normals) in input order, and with details=True a third array of capi.NEIGHBOURHOOD_DETAIL records, one
@@ -1193,6 +1209,107 @@ class OccupancyGrid:
         return out, sm.asdict()
 
 
+class ElevationGrid:
+    """A dense 2-D grid of height accumulators on the device (lom_elevation_*, include/lidar_odometry_amd.h "elevation
+    grid"): every point of a posed scan that is an occupancy hit adds its quantised height to its cell; layers() derives
+    ground height, slope, roughness and step, cost() the int8 values of a costmap (-1 unknown, 0 .. 99, 100 lethal).  All
+    arrays have the shape (height, width)."""
+
+    LAYERS = ("min", "max", "mean", "slope", "rough", "step")
+
+    def __init__(self, resolution, origin_xy, width, height, z_ref=0.0, device=0):
+        geo = capi.ElevationGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height),
+                                     float(z_ref))
+        h = C.c_void_p()
+        rc = capi.lib().lom_elevation_create(C.byref(geo), int(device), C.byref(h))
+        if rc != 0:
+            text = capi.lib().lom_elevation_last_error(None)
+            raise LomError(int(rc), text.decode() if text else "lom_elevation_create")
+        self._h = h
+        self.width, self.height = int(width), int(height)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and capi is not None:
+            capi.lib().lom_elevation_destroy(h)
+            self._h = None
+
+    @property
+    def handle(self):
+        return self._h
+
+    def _check(self, rc):
+        if rc < 0:
+            text = capi.lib().lom_elevation_last_error(self._h)
+            raise LomError(int(rc), text.decode() if text else "")
+        return rc
+
+    def geometry(self):
+        geo = capi.ElevationGeometry()
+        self._check(capi.lib().lom_elevation_get_geometry(self._h, C.byref(geo)))
+        return geo.asdict()
+
+    def setOption(self, option, value):
+        self._check(capi.lib().lom_elevation_set_option(self._h, int(option), int(value)))
+
+    def waitEvent(self, hip_event):
+        self._check(capi.lib().lom_elevation_wait_event(self._h, hip_event))
+
+    def clear(self):
+        self._check(capi.lib().lom_elevation_clear(self._h))
+
+    def integrate(self, archive, ids, poses, point_params):
+        """lom_elevation_integrate: the scans `ids` of the ScanArchive at `poses` (n x 7 float64, t then q wxyz); returns
+        capi.ElevationStats as a dict"""
+        p = elevationPointParams(point_params)
+        ids, g = _assemble_args(ids, poses)
+        st = capi.ElevationStats()
+        self._check(capi.lib().lom_elevation_integrate(self._h, archive.handle, ids.ctypes.data, g.ctypes.data, len(ids),
+                                                       C.byref(p), C.byref(st)))
+        return st.asdict()
+
+    def integrateCloud(self, xyz, pose, point_params, device_ptr=None, n=None, stride_bytes=12, hip_event=None):
+        """lom_elevation_integrate_cloud: one scan that is not in an archive, a host array (n, 3) -- or, with device_ptr,
+        lom_elevation_integrate_cloud_device: n records of stride_bytes in HBM behind `hip_event`"""
+        p = elevationPointParams(point_params)
+        g = _graph_poses(np.asarray(pose, np.float64).reshape(1, 7))
+        st = capi.ElevationStats()
+        if device_ptr is not None:
+            rc = capi.lib().lom_elevation_integrate_cloud_device(self._h, device_ptr, int(n), int(stride_bytes), g.ctypes.data,
+                                                                 C.byref(p), hip_event, C.byref(st))
+        else:
+            xyz = capi.xyz_array(xyz)
+            rc = capi.lib().lom_elevation_integrate_cloud(self._h, xyz.ctypes.data, len(xyz), 12, g.ctypes.data, C.byref(p),
+                                                          C.byref(st))
+        self._check(rc)
+        return st.asdict()
+
+    def cells(self):
+        """(count uint32, zmin int32, zmax int32, sum int64): the accumulators, in quanta of 2^-8 m relative to z_ref"""
+        shape = (self.height, self.width)
+        count, zmin, zmax = np.zeros(shape, np.uint32), np.zeros(shape, np.int32), np.zeros(shape, np.int32)
+        total = np.zeros(shape, np.int64)
+        self._check(capi.lib().lom_elevation_cells(self._h, count.ctypes.data, zmin.ctypes.data, zmax.ctypes.data,
+                                                   total.ctypes.data, count.size))
+        return count, zmin, zmax, total
+
+    def layers(self, layer_params):
+        """dict of the six float32 layers (min, max, mean, slope, rough, step) by lom_elevation_layer_params"""
+        lp = elevationLayerParams(layer_params)
+        out = {k: np.empty((self.height, self.width), np.float32) for k in self.LAYERS}
+        self._check(capi.lib().lom_elevation_layers(self._h, C.byref(lp), *[out[k].ctypes.data for k in self.LAYERS],
+                                                    self.width * self.height))
+        return out
+
+    def cost(self, layer_params, cost_params):
+        """(int8 array, summary dict) by lom_elevation_layer_params and lom_elevation_cost_params"""
+        lp, cp = elevationLayerParams(layer_params), elevationCostParams(cost_params)
+        out = np.empty((self.height, self.width), np.int8)
+        sm = capi.ElevationSummary()
+        self._check(capi.lib().lom_elevation_cost(self._h, C.byref(lp), C.byref(cp), out.ctypes.data, out.size, C.byref(sm)))
+        return out, sm.asdict()
+
+
 class PoseGraph:
     """Keyframe poses and the relative poses measured between them, in HBM, optimised on the device (lom_graph_*,
     include/lidar_odometry_amd.h "pose graph").  Poses are (n, 7) float64 arrays: t, then the quaternion w x y z; an
@@ -1580,6 +1697,16 @@ class LidarOdometry:
         if rc != 0:
             text = capi.lib().lom_occupancy_last_error(grid.handle)
             raise LomError(int(rc), text.decode() if text else "lom_odometry_occupancy_scan")
+        return st.asdict()
+
+    def elevationScan(self, grid, point_params):
+        """lom_odometry_elevation_scan: that cloud at the current pose into the ElevationGrid; returns the stats."""
+        p = elevationPointParams(point_params)
+        st = capi.ElevationStats()
+        rc = capi.lib().lom_odometry_elevation_scan(self._h, grid.handle, C.byref(p), C.byref(st))
+        if rc != 0:
+            text = capi.lib().lom_elevation_last_error(grid.handle)
+            raise LomError(int(rc), text.decode() if text else "lom_odometry_elevation_scan")
         return st.asdict()
 
     def rebuildKeyframe(self, archive, ids, poses, new_current):

@@ -270,6 +270,55 @@ OCC_FREE, OCC_OCCUPIED, OCC_UNKNOWN = 0, 100, -1
 OCC_OPT_TEST_SLICE_MAX, OCC_OPT_TEST_WINDOW = 1, 2
 
 
+class ElevationGeometry(C.Structure):
+    """lom_elevation_geometry"""
+    _fields_ = [("resolution", C.c_float), ("origin_x", C.c_float), ("origin_y", C.c_float), ("width", C.c_uint32),
+                ("height", C.c_uint32), ("z_ref", C.c_float)]
+
+    def asdict(self):
+        return dict(resolution=float(self.resolution), origin_x=float(self.origin_x), origin_y=float(self.origin_y),
+                    width=int(self.width), height=int(self.height), z_ref=float(self.z_ref))
+
+
+class ElevationPointParams(C.Structure):
+    """lom_elevation_point_params (no defaults: every field is the caller's)"""
+    _fields_ = [("z_lo", C.c_float), ("z_hi", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float)]
+
+
+class ElevationLayerParams(C.Structure):
+    """lom_elevation_layer_params"""
+    _fields_ = [("min_points", C.c_uint32), ("window", C.c_uint32)]
+
+
+class ElevationCostParams(C.Structure):
+    """lom_elevation_cost_params"""
+    _fields_ = [("max_slope", C.c_float), ("max_step", C.c_float), ("max_rough", C.c_float), ("max_span", C.c_float)]
+
+
+class ElevationStats(C.Structure):
+    """lom_elevation_stats"""
+    _fields_ = [("scans", C.c_uint64), ("points", C.c_uint64), ("points_marked", C.c_uint64),
+                ("points_out_of_height", C.c_uint64), ("cells_new", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class ElevationSummary(C.Structure):
+    """lom_elevation_summary"""
+    _fields_ = [("cells_unknown", C.c_uint64), ("cells_lethal", C.c_uint64), ("cells_costed", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(ElevationGeometry) == 24 and C.sizeof(ElevationPointParams) == 16 and C.sizeof(ElevationLayerParams) == 8
+assert C.sizeof(ElevationCostParams) == 16 and C.sizeof(ElevationStats) == 40 and C.sizeof(ElevationSummary) == 24
+ELEV_QUANTUM_LOG2 = -8
+ELEV_COST_UNKNOWN, ELEV_COST_LETHAL = -1, 100
+ELEV_OPT_TEST_WAVE_MERGE = 1
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -349,6 +398,12 @@ EXPORTED = [
     "lom_occupancy_get_geometry", "lom_occupancy_stream", "lom_occupancy_device", "lom_occupancy_wait_event",
     "lom_occupancy_set_option", "lom_occupancy_integrate", "lom_occupancy_integrate_cloud",
     "lom_occupancy_integrate_cloud_device", "lom_occupancy_counts", "lom_occupancy_classify", "lom_occupancy_classify_device",
+    "lom_odometry_elevation_scan",
+    "lom_elevation_create", "lom_elevation_destroy", "lom_elevation_last_error", "lom_elevation_clear",
+    "lom_elevation_get_geometry", "lom_elevation_stream", "lom_elevation_device", "lom_elevation_wait_event",
+    "lom_elevation_set_option", "lom_elevation_integrate", "lom_elevation_integrate_cloud",
+    "lom_elevation_integrate_cloud_device", "lom_elevation_cells", "lom_elevation_layers", "lom_elevation_cost",
+    "lom_elevation_cost_device",
 ]
 # ... and the one it declares through a function type (the "scan archive and map assembly" section)
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
@@ -719,6 +774,30 @@ def lib():
     L.lom_occupancy_counts.restype = C.c_int64
     L.lom_occupancy_classify.argtypes = [vp, C.POINTER(OccupancyRule), vp, C.c_size_t, C.POINTER(OccupancySummary)]
     L.lom_occupancy_classify_device.argtypes = [vp, C.POINTER(OccupancyRule), C.POINTER(vp)]
+    L.lom_odometry_elevation_scan.argtypes = [vp, vp, C.POINTER(ElevationPointParams), C.POINTER(ElevationStats)]
+    L.lom_elevation_create.argtypes = [C.POINTER(ElevationGeometry), C.c_int, C.POINTER(vp)]
+    L.lom_elevation_destroy.argtypes = [vp]
+    L.lom_elevation_destroy.restype = None
+    L.lom_elevation_last_error.argtypes = [vp]
+    L.lom_elevation_last_error.restype = C.c_char_p
+    L.lom_elevation_clear.argtypes = [vp]
+    L.lom_elevation_get_geometry.argtypes = [vp, C.POINTER(ElevationGeometry)]
+    L.lom_elevation_stream.argtypes = [vp]
+    L.lom_elevation_stream.restype = vp
+    L.lom_elevation_device.argtypes = [vp]
+    L.lom_elevation_wait_event.argtypes = [vp, vp]
+    L.lom_elevation_set_option.argtypes = [vp, C.c_int, C.c_int64]
+    L.lom_elevation_integrate.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(ElevationPointParams), C.POINTER(ElevationStats)]
+    L.lom_elevation_integrate_cloud.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(ElevationPointParams),
+                                                C.POINTER(ElevationStats)]
+    L.lom_elevation_integrate_cloud_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(ElevationPointParams), vp,
+                                                       C.POINTER(ElevationStats)]
+    L.lom_elevation_cells.argtypes = [vp, vp, vp, vp, vp, C.c_size_t]
+    L.lom_elevation_cells.restype = C.c_int64
+    L.lom_elevation_layers.argtypes = [vp, C.POINTER(ElevationLayerParams), vp, vp, vp, vp, vp, vp, C.c_size_t]
+    L.lom_elevation_cost.argtypes = [vp, C.POINTER(ElevationLayerParams), C.POINTER(ElevationCostParams), vp, C.c_size_t,
+                                     C.POINTER(ElevationSummary)]
+    L.lom_elevation_cost_device.argtypes = [vp, C.POINTER(ElevationLayerParams), C.POINTER(ElevationCostParams), C.POINTER(vp)]
     _lib = L
     return L
 

@@ -213,6 +213,26 @@ int lom_odometry_occupancy_scan(lom_odometry *o, lom_occupancy *g, const lom_occ
     return rc;
 }
 
+// its twin for an elevation grid (csrc/elevation.hip); reads only
+int lom_odometry_elevation_scan(lom_odometry *o, lom_elevation *g, const lom_elevation_point_params *p, lom_elevation_stats *stats)
+{
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (!o || !g || lom_elevation_device(g) != o->device) return LOM_ERR_ARG;
+    if (o->temp_points == 0) return LOM_ERR_STATE;  // no frame yet
+    const float *pts = nullptr;
+    size_t n = 0;
+    void *event = nullptr;
+    int rc = deskewed_cloud(o, &pts, &n, &event);
+    if (rc != LOM_OK) return rc;
+    lom_graph_pose pose;
+    if ((rc = lom_graph_pose_from_f32(&o->current, &pose)) != LOM_OK) return rc;
+    const size_t stride = sizeof(lom_point_xyzirt);
+    rc = o->temp_on_device ? lom_elevation_integrate_cloud_device(g, pts, n, stride, &pose, p, event, stats)
+                           : lom_elevation_integrate_cloud(g, pts, n, stride, &pose, p, stats);
+    if (rc != LOM_OK) o->error = lom_elevation_last_error(g);
+    return rc;
+}
+
 // the keyframe again from archived scans at corrected poses: the steps of the header, in its order
 int lom_odometry_rebuild_keyframe(lom_odometry *o, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses,
                                   size_t count, const lom_pose *new_current, lom_assemble_stats *stats)
