@@ -827,27 +827,51 @@ def classifyNeighbourhood(points, params, details=False, frontend=None):
     return out + (det,) if details else out
 
 
-class FrontEnd:
-    """The per-frame front end on the device (csrc/frontend.hip): pointTimeNormalize + transformNonRigid +
-    CloudClassifier::classify + rangeFilter, results left in HBM."""
+class _Handle:
+    """A handle of the family lom_<_family>_*: its creation, destruction and last error."""
 
-    def __init__(self, device=0):
+    _family = None
+    _create_failed = None  # the text of a failed create; None: lom_<_family>_last_error(NULL), why it failed
+
+    def _call(self, name, *args):
+        return getattr(capi.lib(), f"lom_{self._family}_{name}")(*args)
+
+    def _create(self, *args):
+        """lom_<_family>_create(*args, &handle)"""
         h = C.c_void_p()
-        rc = capi.lib().lom_frontend_create(int(device), None, C.byref(h))
+        rc = self._call("create", *args, C.byref(h))
         if rc != 0:
-            raise LomError(int(rc), "lom_frontend_create failed")
+            if self._create_failed:
+                raise LomError(int(rc), self._create_failed)
+            text = self._call("last_error", None)
+            raise LomError(int(rc), text.decode() if text else f"lom_{self._family}_create")
         self._h = h
 
     def __del__(self):
         h = getattr(self, "_h", None)
-        if h and capi is not None:
-            capi.lib().lom_frontend_destroy(h)
+        if h and capi is not None:          # at interpreter shutdown the module may already be gone
+            self._call("destroy", h)
             self._h = None
+
+    @property
+    def handle(self):
+        return self._h
 
     def _check(self, rc):
         if rc < 0:
-            raise LomError(int(rc), capi.lib().lom_frontend_last_error(self._h).decode())
+            text = self._call("last_error", self._h)
+            raise LomError(int(rc), text.decode() if text else "")
         return rc
+
+
+class FrontEnd(_Handle):
+    """The per-frame front end on the device (csrc/frontend.hip): pointTimeNormalize + transformNonRigid +
+    CloudClassifier::classify + rangeFilter, results left in HBM."""
+
+    _family, _create_failed = "frontend", "lom_frontend_create failed"
+
+    def __init__(self, device=0):
+        self._create(int(device), None)
 
     def setClassifier(self, kind, params=None):
         """capi.CLASSIFIER_RINGS (the default) or capi.CLASSIFIER_NEIGHBOURHOOD (params required) for the frames that follow."""
@@ -909,36 +933,17 @@ def _place_cloud(cloud):
     return a, len(a), 12
 
 
-class PlaceDatabase:
+class PlaceDatabase(_Handle):
     """Scan descriptors (a polar height image in the style of Scan Context) and a database of them in HBM
     (lom_place_db_*, include/lidar_odometry_amd.h): query() names, for each query descriptor, the k nearest entries and
     the column shift against each; shiftYaw() turns a shift into the yaw of a pose guess.  numpy in and out."""
 
+    _family = "place_db"
+
     def __init__(self, params, capacity_hint=0, device=0):
         self.params = placeParams(params)
-        h = C.c_void_p()
-        rc = capi.lib().lom_place_db_create(C.byref(self.params), int(device), int(capacity_hint), C.byref(h))
-        if rc != 0:
-            text = capi.lib().lom_place_db_last_error(None)
-            raise LomError(int(rc), text.decode() if text else "lom_place_db_create")
-        self._h = h
+        self._create(C.byref(self.params), int(device), int(capacity_hint))
         self.shape = (int(self.params.rings), int(self.params.sectors))
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and capi is not None:
-            capi.lib().lom_place_db_destroy(h)
-            self._h = None
-
-    @property
-    def handle(self):
-        return self._h
-
-    def _check(self, rc):
-        if rc < 0:
-            text = capi.lib().lom_place_db_last_error(self._h)
-            raise LomError(int(rc), text.decode() if text else "")
-        return rc
 
     def __len__(self):
         return int(self._check(capi.lib().lom_place_db_size(self._h)))
@@ -1043,33 +1048,14 @@ def graph_pose_rotation_matrix(pose):
     return out
 
 
-class ScanArchive:
+class ScanArchive(_Handle):
     """Clouds with normals kept in HBM in their own sensor frame (lom_archive_*, include/lidar_odometry_amd.h "scan
     archive and map assembly"); VoxelGrid.assemble puts any of them, at float64 poses, into a map in one call."""
 
+    _family = "archive"
+
     def __init__(self, point_hint=0, scan_hint=0, device=0):
-        h = C.c_void_p()
-        rc = capi.lib().lom_archive_create(int(device), int(point_hint), int(scan_hint), C.byref(h))
-        if rc != 0:
-            text = capi.lib().lom_archive_last_error(None)
-            raise LomError(int(rc), text.decode() if text else "lom_archive_create")
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and capi is not None:
-            capi.lib().lom_archive_destroy(h)
-            self._h = None
-
-    @property
-    def handle(self):
-        return self._h
-
-    def _check(self, rc):
-        if rc < 0:
-            text = capi.lib().lom_archive_last_error(self._h)
-            raise LomError(int(rc), text.decode() if text else "")
-        return rc
+        self._create(int(device), int(point_hint), int(scan_hint))
 
     def __len__(self):
         return int(self._check(capi.lib().lom_archive_scan_count(self._h)))
@@ -1123,76 +1109,75 @@ def _assemble_args(ids, poses):
     return ids, p
 
 
-class OccupancyGrid:
+class _PosedScanGrid(_Handle):
+    """What OccupancyGrid and ElevationGrid share (csrc/grid_handle.hpp): a dense 2-D grid that integrates posed scans.  A
+    family names its geometry and stats structures (_geometry, _stats) and the converter of its parameters (_params)."""
+
+    def _create_grid(self, geo, device):
+        self._create(C.byref(geo), int(device))
+        self.width, self.height = int(geo.width), int(geo.height)
+
+    def geometry(self):
+        geo = self._geometry()
+        self._check(self._call("get_geometry", self._h, C.byref(geo)))
+        return geo.asdict()
+
+    def setOption(self, option, value):
+        self._check(self._call("set_option", self._h, int(option), int(value)))
+
+    def waitEvent(self, hip_event):
+        self._check(self._call("wait_event", self._h, hip_event))
+
+    def clear(self):
+        self._check(self._call("clear", self._h))
+
+    def _integrate(self, archive, ids, poses, params):
+        """lom_<family>_integrate: the scans `ids` of the ScanArchive at `poses` (n x 7 float64, t then q wxyz); returns the
+        family's stats (capi.OccupancyStats / capi.ElevationStats) as a dict"""
+        p = self._params(params)
+        ids, g = _assemble_args(ids, poses)
+        st = self._stats()
+        self._check(self._call("integrate", self._h, archive.handle, ids.ctypes.data, g.ctypes.data, len(ids), C.byref(p),
+                               C.byref(st)))
+        return st.asdict()
+
+    def _integrate_cloud(self, xyz, pose, params, device_ptr=None, n=None, stride_bytes=12, hip_event=None):
+        """lom_<family>_integrate_cloud: one scan that is not in an archive, a host array (n, 3) -- or, with device_ptr,
+        lom_<family>_integrate_cloud_device: n records of stride_bytes in HBM behind `hip_event`"""
+        p = self._params(params)
+        g = _graph_poses(np.asarray(pose, np.float64).reshape(1, 7))
+        st = self._stats()
+        if device_ptr is not None:
+            rc = self._call("integrate_cloud_device", self._h, device_ptr, int(n), int(stride_bytes), g.ctypes.data, C.byref(p),
+                            hip_event, C.byref(st))
+        else:
+            xyz = capi.xyz_array(xyz)
+            rc = self._call("integrate_cloud", self._h, xyz.ctypes.data, len(xyz), 12, g.ctypes.data, C.byref(p), C.byref(st))
+        self._check(rc)
+        return st.asdict()
+
+
+class OccupancyGrid(_PosedScanGrid):
     """A dense 2-D grid of free / seen scan counts on the device (lom_occupancy_*, include/lidar_odometry_amd.h
     "occupancy grid"): posed scans vote once per cell, and classify() turns the counts into the int8 values of
     nav_msgs/OccupancyGrid (0 free, 100 occupied, -1 unknown), shape (height, width)."""
 
+    _family, _geometry, _stats = "occupancy", capi.OccupancyGeometry, capi.OccupancyStats
+    _params = staticmethod(occupancyRayParams)
+
     def __init__(self, resolution, origin_xy, width, height, device=0):
-        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
-        h = C.c_void_p()
-        rc = capi.lib().lom_occupancy_create(C.byref(geo), int(device), C.byref(h))
-        if rc != 0:
-            text = capi.lib().lom_occupancy_last_error(None)
-            raise LomError(int(rc), text.decode() if text else "lom_occupancy_create")
-        self._h = h
-        self.width, self.height = int(width), int(height)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and capi is not None:
-            capi.lib().lom_occupancy_destroy(h)
-            self._h = None
-
-    @property
-    def handle(self):
-        return self._h
-
-    def _check(self, rc):
-        if rc < 0:
-            text = capi.lib().lom_occupancy_last_error(self._h)
-            raise LomError(int(rc), text.decode() if text else "")
-        return rc
-
-    def geometry(self):
-        geo = capi.OccupancyGeometry()
-        self._check(capi.lib().lom_occupancy_get_geometry(self._h, C.byref(geo)))
-        return geo.asdict()
-
-    def setOption(self, option, value):
-        self._check(capi.lib().lom_occupancy_set_option(self._h, int(option), int(value)))
-
-    def waitEvent(self, hip_event):
-        self._check(capi.lib().lom_occupancy_wait_event(self._h, hip_event))
-
-    def clear(self):
-        self._check(capi.lib().lom_occupancy_clear(self._h))
+        self._create_grid(capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width),
+                                                 int(height)), device)
 
     def integrate(self, archive, ids, poses, ray_params):
         """lom_occupancy_integrate: the scans `ids` of the ScanArchive at `poses` (n x 7 float64, t then q wxyz) vote;
         returns capi.OccupancyStats as a dict"""
-        p = occupancyRayParams(ray_params)
-        ids, g = _assemble_args(ids, poses)
-        st = capi.OccupancyStats()
-        self._check(capi.lib().lom_occupancy_integrate(self._h, archive.handle, ids.ctypes.data, g.ctypes.data, len(ids),
-                                                       C.byref(p), C.byref(st)))
-        return st.asdict()
+        return self._integrate(archive, ids, poses, ray_params)
 
     def integrateCloud(self, xyz, pose, ray_params, device_ptr=None, n=None, stride_bytes=12, hip_event=None):
         """lom_occupancy_integrate_cloud: one scan that is not in an archive, a host array (n, 3) -- or, with device_ptr,
         lom_occupancy_integrate_cloud_device: n records of stride_bytes in HBM behind `hip_event`"""
-        p = occupancyRayParams(ray_params)
-        g = _graph_poses(np.asarray(pose, np.float64).reshape(1, 7))
-        st = capi.OccupancyStats()
-        if device_ptr is not None:
-            rc = capi.lib().lom_occupancy_integrate_cloud_device(self._h, device_ptr, int(n), int(stride_bytes), g.ctypes.data,
-                                                                 C.byref(p), hip_event, C.byref(st))
-        else:
-            xyz = capi.xyz_array(xyz)
-            rc = capi.lib().lom_occupancy_integrate_cloud(self._h, xyz.ctypes.data, len(xyz), 12, g.ctypes.data, C.byref(p),
-                                                          C.byref(st))
-        self._check(rc)
-        return st.asdict()
+        return self._integrate_cloud(xyz, pose, ray_params, device_ptr, n, stride_bytes, hip_event)
 
     def counts(self):
         """(free, seen): uint32 arrays of shape (height, width)"""
@@ -1209,80 +1194,29 @@ class OccupancyGrid:
         return out, sm.asdict()
 
 
-class ElevationGrid:
+class ElevationGrid(_PosedScanGrid):
     """A dense 2-D grid of height accumulators on the device (lom_elevation_*, include/lidar_odometry_amd.h "elevation
     grid"): every point of a posed scan that is an occupancy hit adds its quantised height to its cell; layers() derives
     ground height, slope, roughness and step, cost() the int8 values of a costmap (-1 unknown, 0 .. 99, 100 lethal).  All
     arrays have the shape (height, width)."""
 
     LAYERS = ("min", "max", "mean", "slope", "rough", "step")
+    _family, _geometry, _stats = "elevation", capi.ElevationGeometry, capi.ElevationStats
+    _params = staticmethod(elevationPointParams)
 
     def __init__(self, resolution, origin_xy, width, height, z_ref=0.0, device=0):
-        geo = capi.ElevationGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height),
-                                     float(z_ref))
-        h = C.c_void_p()
-        rc = capi.lib().lom_elevation_create(C.byref(geo), int(device), C.byref(h))
-        if rc != 0:
-            text = capi.lib().lom_elevation_last_error(None)
-            raise LomError(int(rc), text.decode() if text else "lom_elevation_create")
-        self._h = h
-        self.width, self.height = int(width), int(height)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and capi is not None:
-            capi.lib().lom_elevation_destroy(h)
-            self._h = None
-
-    @property
-    def handle(self):
-        return self._h
-
-    def _check(self, rc):
-        if rc < 0:
-            text = capi.lib().lom_elevation_last_error(self._h)
-            raise LomError(int(rc), text.decode() if text else "")
-        return rc
-
-    def geometry(self):
-        geo = capi.ElevationGeometry()
-        self._check(capi.lib().lom_elevation_get_geometry(self._h, C.byref(geo)))
-        return geo.asdict()
-
-    def setOption(self, option, value):
-        self._check(capi.lib().lom_elevation_set_option(self._h, int(option), int(value)))
-
-    def waitEvent(self, hip_event):
-        self._check(capi.lib().lom_elevation_wait_event(self._h, hip_event))
-
-    def clear(self):
-        self._check(capi.lib().lom_elevation_clear(self._h))
+        self._create_grid(capi.ElevationGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width),
+                                                 int(height), float(z_ref)), device)
 
     def integrate(self, archive, ids, poses, point_params):
         """lom_elevation_integrate: the scans `ids` of the ScanArchive at `poses` (n x 7 float64, t then q wxyz); returns
         capi.ElevationStats as a dict"""
-        p = elevationPointParams(point_params)
-        ids, g = _assemble_args(ids, poses)
-        st = capi.ElevationStats()
-        self._check(capi.lib().lom_elevation_integrate(self._h, archive.handle, ids.ctypes.data, g.ctypes.data, len(ids),
-                                                       C.byref(p), C.byref(st)))
-        return st.asdict()
+        return self._integrate(archive, ids, poses, point_params)
 
     def integrateCloud(self, xyz, pose, point_params, device_ptr=None, n=None, stride_bytes=12, hip_event=None):
         """lom_elevation_integrate_cloud: one scan that is not in an archive, a host array (n, 3) -- or, with device_ptr,
         lom_elevation_integrate_cloud_device: n records of stride_bytes in HBM behind `hip_event`"""
-        p = elevationPointParams(point_params)
-        g = _graph_poses(np.asarray(pose, np.float64).reshape(1, 7))
-        st = capi.ElevationStats()
-        if device_ptr is not None:
-            rc = capi.lib().lom_elevation_integrate_cloud_device(self._h, device_ptr, int(n), int(stride_bytes), g.ctypes.data,
-                                                                 C.byref(p), hip_event, C.byref(st))
-        else:
-            xyz = capi.xyz_array(xyz)
-            rc = capi.lib().lom_elevation_integrate_cloud(self._h, xyz.ctypes.data, len(xyz), 12, g.ctypes.data, C.byref(p),
-                                                          C.byref(st))
-        self._check(rc)
-        return st.asdict()
+        return self._integrate_cloud(xyz, pose, point_params, device_ptr, n, stride_bytes, hip_event)
 
     def cells(self):
         """(count uint32, zmin int32, zmax int32, sum int64): the accumulators, in quanta of 2^-8 m relative to z_ref"""
@@ -1310,34 +1244,15 @@ class ElevationGrid:
         return out, sm.asdict()
 
 
-class PoseGraph:
+class PoseGraph(_Handle):
     """Keyframe poses and the relative poses measured between them, in HBM, optimised on the device (lom_graph_*,
     include/lidar_odometry_amd.h "pose graph").  Poses are (n, 7) float64 arrays: t, then the quaternion w x y z; an
     edge's measurement is the pose of node j in node i's frame.  numpy in and out."""
 
+    _family = "graph"
+
     def __init__(self, node_hint=0, edge_hint=0, device=0):
-        h = C.c_void_p()
-        rc = capi.lib().lom_graph_create(int(device), int(node_hint), int(edge_hint), C.byref(h))
-        if rc != 0:
-            text = capi.lib().lom_graph_last_error(None)
-            raise LomError(int(rc), text.decode() if text else "lom_graph_create")
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and capi is not None:
-            capi.lib().lom_graph_destroy(h)
-            self._h = None
-
-    @property
-    def handle(self):
-        return self._h
-
-    def _check(self, rc):
-        if rc < 0:
-            text = capi.lib().lom_graph_last_error(self._h)
-            raise LomError(int(rc), text.decode() if text else "")
-        return rc
+        self._create(int(device), int(node_hint), int(edge_hint))
 
     def clear(self):
         self._check(capi.lib().lom_graph_clear(self._h))

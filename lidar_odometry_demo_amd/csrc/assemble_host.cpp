@@ -1,9 +1,12 @@
 // Host planning of lom_map_assemble: validation of ids and poses, quaternion to rotation matrix, the offsets of every scan
 // in the concatenated cloud, grid sizes.  Plain C++, no HIP: archive.hip calls these, and lom_graph_pose_rotation_matrix is
 // part of the C ABI.  The kernels index points with 32 bits: a plan whose archive offsets reach 2^32 or whose call holds
-// more than an insert takes is refused here, before any device work.
+// more than an insert takes is refused here, before any device work.  Below them, what the planners built on these
+// descriptors share: the cut of a call into launches (vote, occupancy, elevation) and the start cells and first checks
+// of the two 2-D grids.
 #include "assemble_host.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 namespace lom {
@@ -112,6 +115,45 @@ int cull_of(const lom_assemble_params *p, bool *cull, std::string &why)
     }
     *cull = p->radius > 0.0f;
     return LOM_OK;
+}
+
+std::vector<Launch> cut_launches(const Plan &plan, uint32_t per)
+{
+    std::vector<Launch> out;
+    const size_t count = plan.scans.size();
+    for (size_t first = 0; first < count; first += per) {
+        Launch l;
+        l.first = (uint32_t)first;
+        l.count = (uint32_t)std::min<size_t>(per, count - first);
+        l.max_n = 0;
+        for (uint32_t k = 0; k < l.count; k++) l.max_n = std::max(l.max_n, plan.scans[first + k].n);
+        l.grid_x = (l.max_n + kAsmThreads - 1) / kAsmThreads;
+        if (l.max_n) out.push_back(l);
+    }
+    return out;
+}
+
+int plan_on_grid(const ScanEntry *table, size_t n_scans, const int64_t *ids, const lom_graph_pose *poses, size_t count,
+                 const GridFrame &frame, bool params_ok, const char *params_why, Plan &out,
+                 std::vector<int32_t> &cells, std::string &why)
+{
+    cells.clear();
+    int rc = plan(table, n_scans, ids, poses, count, out, why);
+    if (rc == LOM_OK && !params_ok) {
+        why = params_why;
+        rc = LOM_ERR_ARG;
+    }
+    if (rc == LOM_OK) cells.resize(count * 2);
+    for (size_t k = 0; k < count && rc == LOM_OK; k++)
+        if (!origin_cell(out.scans[k], frame, &cells[k * 2])) {
+            why = "origin of scan " + std::to_string(k) + " of the call: its cell is beyond 2^30 or not finite";
+            rc = LOM_ERR_RANGE;
+        }
+    if (rc != LOM_OK) {
+        out = Plan();
+        cells.clear();
+    }
+    return rc;
 }
 
 }  // namespace assemble

@@ -1,36 +1,61 @@
 // Elevation grid: every point of a posed scan that is an occupancy hit adds its quantised height to its cell of a dense
 // 2-D grid -- count, minimum, maximum, sum, all integers -- and a second pass derives ground height, slope, roughness,
 // step and a traversability cost.  Definitions: include/lidar_odometry_amd.h ("elevation grid"); kernels:
-// k_elevation.hpp; host planning (value ranges, start cells, launches): elevation_host.cpp; DESIGN.md 7k.  A handle family
-// of its own beside the map path: the descriptors are the assembly's, the clouds an archive's or the caller's, and no
-// default path launches any of this.
+// k_elevation.hpp; host planning (value ranges, launches): elevation_host.cpp; what a grid handle is and does around its
+// kernels, the integrate entry points included: grid_handle.hpp; DESIGN.md 7k.  A handle family of its own beside the map
+// path: the descriptors are the assembly's, the clouds an archive's or the caller's, and no default path launches any of
+// this.
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
 
-#include "archive_internal.hpp"
 #include "elevation_host.hpp"
+#include "grid_handle.hpp"
 #include "k_elevation.hpp"
 
 using namespace lom;
 
-// The grid owns its stream and every buffer below.
-struct lom_elevation : lom::DeviceHandle {
+// Beside the core's (grid_handle.hpp):
+struct lom_elevation : lom::GridHandle {
     lom_elevation_geometry geo{};
     lom::DeviceBuf cells;        // width * height records of 32 bytes
     lom::DeviceBuf cost;         // int8 per cell
     lom::DeviceBuf layers;       // six f32 planes, from the first lom_elevation_layers on
     lom::DeviceBuf unpacked;     // a chunk of the records as four arrays, on its way out (lom_elevation_cells)
-    lom::DeviceBuf desc, words;  // descriptors of a call; the status words
-    lom::DeviceBuf cloud;        // a host cloud on its way in, packed
-    lom::PinnedBuf h_words;      // the status words on their way out
-    hipEvent_t done_ev = nullptr;  // recorded behind a call's kernels, for the archive's stream to wait on
     uint32_t merge = 1;          // LOM_ELEV_OPT_TEST_WAVE_MERGE
 
     size_t n_cells() const { return (size_t)geo.width * geo.height; }
+
+    // the family's part of the integrate entry points
+    using Plan = elevation::Plan;
+    static constexpr const char *kName = "elevation";
+    static constexpr auto kPlan = &elevation::plan;  // (no option sets plan_cap here)
+
+    int run(const Plan &plan, const float *xyz, uint32_t stride_floats, const lom_elevation_point_params &p, lom_elevation_stats &st)
+    {
+        int rc;
+        if ((rc = grid_stage(this, plan.scans.scans, EW_COUNT)) != LOM_OK) return rc;
+        ElevArgs a;
+        a.resolution = geo.resolution, a.origin_x = geo.origin_x, a.origin_y = geo.origin_y, a.z_ref = geo.z_ref;
+        a.width = geo.width, a.height = geo.height;
+        a.z_lo = p.z_lo, a.z_hi = p.z_hi, a.min_range = p.min_range, a.max_range = p.max_range;
+        a.stride = stride_floats;
+        a.merge = merge;
+        for (const elevation::Launch &l : plan.launches) {
+            hipLaunchKernelGGL(k_elev_accumulate, dim3(l.grid_x, l.count), dim3(kAsmThreads), 0, stream,
+                               desc.as<const AsmScan>() + l.first, xyz, a, cells.as<ElevCell>(), words.as<uint32_t>());
+            LOM_HIP(this, hipGetLastError());
+        }
+        if ((rc = grid_read_words(this, EW_COUNT, true)) != LOM_OK) return rc;
+        const uint32_t *got = h_words.as<uint32_t>();
+        st.points = plan.scans.points_in;
+        st.points_marked = u64_of(got, EW_MARKED);
+        st.points_out_of_height = u64_of(got, EW_HEIGHT);
+        st.cells_new = u64_of(got, EW_NEW);
+        return LOM_OK;
+    }
 };
 
 namespace {
@@ -39,8 +64,6 @@ thread_local std::string g_elevation_create_error;
 
 constexpr size_t kUnpackChunk = size_t(1) << 22;  // cells of one lom_elevation_cells round: 80 MB of staging at most
 
-bool stride_ok(size_t stride) { return stride >= 12 && (stride & 3) == 0; }
-
 int clear_cells(lom_elevation *g)
 {
     const uint32_t n = (uint32_t)g->n_cells();
@@ -48,51 +71,6 @@ int clear_cells(lom_elevation *g)
                        g->cells.as<ElevCell>(), n);
     LOM_HIP(g, hipGetLastError());
     return LOM_OK;
-}
-
-// Every launch of the call, then the one read-back: the status words.  xyz: device memory, records of stride_floats; the
-// caller has ordered g->stream behind whoever produced it.
-int run(lom_elevation *g, const elevation::Plan &plan, const float *xyz, uint32_t stride_floats,
-        const lom_elevation_point_params &p, lom_elevation_stats &st)
-{
-    int rc;
-    const std::vector<assemble::AsmScan> &scans = plan.scans.scans;
-    const size_t desc_bytes = scans.size() * sizeof(assemble::AsmScan);
-    if ((rc = ensure(g, g->desc, desc_bytes)) != LOM_OK) return rc;
-    LOM_HIP(g, hipMemsetAsync(g->words.p, 0, (size_t)EW_COUNT * 4, g->stream));
-    // (the plan outlives the copy: the call waits for the stream before it returns)
-    LOM_HIP(g, hipMemcpyAsync(g->desc.p, scans.data(), desc_bytes, hipMemcpyHostToDevice, g->stream));
-    ElevArgs a;
-    a.resolution = g->geo.resolution, a.origin_x = g->geo.origin_x, a.origin_y = g->geo.origin_y, a.z_ref = g->geo.z_ref;
-    a.width = g->geo.width, a.height = g->geo.height;
-    a.z_lo = p.z_lo, a.z_hi = p.z_hi, a.min_range = p.min_range, a.max_range = p.max_range;
-    a.stride = stride_floats;
-    a.merge = g->merge;
-    for (const elevation::Launch &l : plan.launches) {
-        hipLaunchKernelGGL(k_elev_accumulate, dim3(l.grid_x, l.count), dim3(kAsmThreads), 0, g->stream,
-                           g->desc.as<const AsmScan>() + l.first, xyz, a, g->cells.as<ElevCell>(), g->words.as<uint32_t>());
-        LOM_HIP(g, hipGetLastError());
-    }
-    LOM_HIP(g, hipMemcpyAsync(g->h_words.h, g->words.p, (size_t)EW_COUNT * 4, hipMemcpyDeviceToHost, g->stream));
-    LOM_HIP(g, hipEventRecord(g->done_ev, g->stream));
-    LOM_HIP(g, hipStreamSynchronize(g->stream));
-    const uint32_t *got = g->h_words.as<uint32_t>();
-    st.points = plan.scans.points_in;
-    st.points_marked = (uint64_t)got[EW_MARKED] | ((uint64_t)got[EW_MARKED + 1] << 32);
-    st.points_out_of_height = (uint64_t)got[EW_HEIGHT] | ((uint64_t)got[EW_HEIGHT + 1] << 32);
-    st.cells_new = (uint64_t)got[EW_NEW] | ((uint64_t)got[EW_NEW + 1] << 32);
-    return LOM_OK;
-}
-
-// one scan that is not in an archive: a table of one entry, id 0
-int plan_cloud(lom_elevation *g, size_t n, const lom_graph_pose *pose, const lom_elevation_point_params *p, elevation::Plan &plan)
-{
-    if (n > assemble::kAsmMaxPoints) return fail(g, LOM_ERR_ARG, "elevation: more than 2^31 - 2 points in one cloud");
-    const assemble::ScanEntry e{0, (uint32_t)n};
-    const int64_t id = 0;
-    std::string why;
-    const int rc = elevation::plan(&e, 1, &id, pose, 1, g->geo, p, 0, plan, why);
-    return rc == LOM_OK ? LOM_OK : fail(g, rc, ("elevation: " + why).c_str());
 }
 
 // k_elev_derive over the whole grid: the layers named in `out` (six planes, each may be NULL) and, with cp, the cost
@@ -139,19 +117,14 @@ int lom_elevation_create(const lom_elevation_geometry *geometry, int device, lom
     if (!g) return create_fail(g_elevation_create_error, LOM_ERR_OOM, "host allocation");
     g->device = device;
     g->geo = *geometry;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&g->done_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = alloc(g->h_words, 64, hipHostMallocDefault);
-    int rc = e == hipSuccess ? LOM_OK : create_fail(g_elevation_create_error, LOM_ERR_HIP, "elevation grid setup", e);
-    if (rc == LOM_OK && (alloc(g->cells, g->n_cells() * sizeof(ElevCell)) != hipSuccess || alloc(g->cost, g->n_cells()) != hipSuccess ||
-                         alloc(g->words, 64) != hipSuccess))
+    int rc = grid_setup(g, g_elevation_create_error, "elevation grid setup", "hipMalloc (elevation grid)");
+    if (rc == LOM_OK && (alloc(g->cells, g->n_cells() * sizeof(ElevCell)) != hipSuccess || alloc(g->cost, g->n_cells()) != hipSuccess))
         rc = create_fail(g_elevation_create_error, LOM_ERR_OOM, "hipMalloc (elevation grid)");
     if (rc == LOM_OK) {
         const uint32_t n = (uint32_t)g->n_cells();
         hipLaunchKernelGGL(k_elev_clear, dim3((n + kElevThreads - 1) / kElevThreads), dim3(kElevThreads), 0, g->stream,
                            g->cells.as<ElevCell>(), n);
-        e = hipGetLastError();
+        hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
         if (e != hipSuccess) rc = create_fail(g_elevation_create_error, LOM_ERR_HIP, "elevation grid setup", e);
     }
@@ -163,15 +136,7 @@ int lom_elevation_create(const lom_elevation_geometry *geometry, int device, lom
     return LOM_OK;
 }
 
-void lom_elevation_destroy(lom_elevation *g)
-{
-    if (!g) return;
-    (void)hipSetDevice(g->device);
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    if (g->done_ev) (void)hipEventDestroy(g->done_ev);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;  // the buffers go with it
-}
+void lom_elevation_destroy(lom_elevation *g) { grid_destroy(g); }
 
 const char *lom_elevation_last_error(const lom_elevation *g) { return g ? g->error.c_str() : g_elevation_create_error.c_str(); }
 
@@ -193,14 +158,7 @@ int lom_elevation_get_geometry(const lom_elevation *g, lom_elevation_geometry *o
 
 void *lom_elevation_stream(lom_elevation *g) { return g ? (void *)g->stream : nullptr; }
 int lom_elevation_device(const lom_elevation *g) { return g ? g->device : LOM_ERR_ARG; }
-
-int lom_elevation_wait_event(lom_elevation *g, void *hip_event)
-{
-    if (!g || !hip_event) return LOM_ERR_ARG;
-    LOM_HIP(g, hipSetDevice(g->device));
-    LOM_HIP(g, hipStreamWaitEvent(g->stream, (hipEvent_t)hip_event, 0));
-    return LOM_OK;
-}
+int lom_elevation_wait_event(lom_elevation *g, void *hip_event) { return grid_wait_event(g, hip_event); }
 
 int lom_elevation_set_option(lom_elevation *g, int option, int64_t value)
 {
@@ -218,72 +176,20 @@ int lom_elevation_set_option(lom_elevation *g, int option, int64_t value)
 int lom_elevation_integrate(lom_elevation *g, lom_archive *a, const int64_t *ids, const lom_graph_pose *poses, size_t count,
                             const lom_elevation_point_params *p, lom_elevation_stats *stats)
 {
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!g || !a) return LOM_ERR_ARG;
-    std::lock_guard<std::mutex> lk(a->lock);
-    if (g->device != a->device) return fail(g, LOM_ERR_ARG, "elevation: the grid and the archive live on different devices");
-    elevation::Plan plan;
-    std::string why;
-    int rc = elevation::plan(a->table.data(), a->table.size(), ids, poses, count, g->geo, p, 0, plan, why);
-    if (rc != LOM_OK) return fail(g, rc, ("elevation: " + why).c_str());
-    lom_elevation_stats st;
-    std::memset(&st, 0, sizeof st);
-    st.scans = count;
-    if (!plan.launches.empty()) {
-        LOM_HIP(g, hipSetDevice(g->device));
-        // the archive's clouds are complete when its stream is (an add waits for its own copy; this orders the rest)
-        LOM_HIP(g, hipEventRecord(a->ready_ev, a->stream));
-        LOM_HIP(g, hipStreamWaitEvent(g->stream, a->ready_ev, 0));
-        if ((rc = run(g, plan, a->d_xyz(), 3, *p, st)) != LOM_OK) return rc;
-        // and what the archive does next comes behind this call's reads
-        LOM_HIP(g, hipStreamWaitEvent(a->stream, g->done_ev, 0));
-    }
-    if (stats) *stats = st;
-    return LOM_OK;
+    return grid_integrate(g, a, ids, poses, count, p, stats);
 }
 
 int lom_elevation_integrate_cloud_device(lom_elevation *g, const float *d_xyz, size_t n, size_t stride_bytes,
                                          const lom_graph_pose *pose, const lom_elevation_point_params *p, void *hip_event_or_null,
                                          lom_elevation_stats *stats)
 {
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!g) return LOM_ERR_ARG;
-    if ((n && !d_xyz) || !pose || !stride_ok(stride_bytes))
-        return fail(g, LOM_ERR_ARG, "elevation: a cloud, a pose and a stride >= 12 that is a multiple of 4");
-    elevation::Plan plan;
-    int rc = plan_cloud(g, n, pose, p, plan);
-    if (rc != LOM_OK) return rc;
-    lom_elevation_stats st;
-    std::memset(&st, 0, sizeof st);
-    st.scans = 1;
-    if (!plan.launches.empty()) {
-        LOM_HIP(g, hipSetDevice(g->device));
-        if (hip_event_or_null) LOM_HIP(g, hipStreamWaitEvent(g->stream, (hipEvent_t)hip_event_or_null, 0));
-        if ((rc = run(g, plan, d_xyz, (uint32_t)(stride_bytes / 4), *p, st)) != LOM_OK) return rc;
-    }
-    if (stats) *stats = st;
-    return LOM_OK;
+    return grid_integrate_cloud(g, d_xyz, false, n, stride_bytes, pose, p, hip_event_or_null, stats);
 }
 
 int lom_elevation_integrate_cloud(lom_elevation *g, const float *xyz, size_t n, size_t stride_bytes, const lom_graph_pose *pose,
                                   const lom_elevation_point_params *p, lom_elevation_stats *stats)
 {
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!g) return LOM_ERR_ARG;
-    if ((n && !xyz) || !pose || !stride_ok(stride_bytes))
-        return fail(g, LOM_ERR_ARG, "elevation: a cloud, a pose and a stride >= 12 that is a multiple of 4");
-    elevation::Plan plan;
-    int rc = plan_cloud(g, n, pose, p, plan);  // every refusal before the upload
-    if (rc != LOM_OK) return rc;
-    if (n) {
-        LOM_HIP(g, hipSetDevice(g->device));
-        if ((rc = ensure(g, g->cloud, n * 12)) != LOM_OK) return rc;
-        if (stride_bytes == 12)
-            LOM_HIP(g, hipMemcpyAsync(g->cloud.p, xyz, n * 12, hipMemcpyHostToDevice, g->stream));
-        else
-            LOM_HIP(g, hipMemcpy2DAsync(g->cloud.p, 12, xyz, stride_bytes, 12, n, hipMemcpyHostToDevice, g->stream));
-    }
-    return lom_elevation_integrate_cloud_device(g, g->cloud.as<const float>(), n, 12, pose, p, nullptr, stats);
+    return grid_integrate_cloud(g, xyz, true, n, stride_bytes, pose, p, nullptr, stats);
 }
 
 int64_t lom_elevation_cells(lom_elevation *g, uint32_t *count_out, int32_t *zmin_out, int32_t *zmax_out, int64_t *sum_out, size_t cap)
@@ -339,12 +245,9 @@ int lom_elevation_cost(lom_elevation *g, const lom_elevation_layer_params *lp, c
 {
     if (summary) std::memset(summary, 0, sizeof *summary);
     if (!g || (cap && !out)) return LOM_ERR_ARG;
-    const int rc = cost_on_device(g, lp, cp);
+    int rc = cost_on_device(g, lp, cp);
     if (rc != LOM_OK) return rc;
-    const size_t n = std::min(cap, g->n_cells());
-    if (n) LOM_HIP(g, hipMemcpyAsync(out, g->cost.p, n, hipMemcpyDeviceToHost, g->stream));
-    LOM_HIP(g, hipMemcpyAsync(g->h_words.h, g->words.p, (size_t)EC_COUNT * 4, hipMemcpyDeviceToHost, g->stream));
-    LOM_HIP(g, hipStreamSynchronize(g->stream));
+    if ((rc = grid_copy_out(g, out, g->cost, std::min(cap, g->n_cells()), EC_COUNT)) != LOM_OK) return rc;
     if (summary) {
         const uint32_t *t = g->h_words.as<uint32_t>();
         summary->cells_unknown = t[EC_UNKNOWN], summary->cells_lethal = t[EC_LETHAL], summary->cells_costed = t[EC_COSTED];

@@ -1,7 +1,7 @@
 // Host planning of the elevation grid (elevation_host.cpp), shared with elevation.hip.  Plain C++: nothing here needs a
 // device.  The scan descriptors and their checks are the assembly's (assemble_host.hpp); what is added is the value
-// ranges of the geometry and of the point, layer and cost parameters, the origins' start cells and their range verdict
-// (the occupancy definition's step 2), and the launches of a call.
+// ranges of the geometry and of the point, layer and cost parameters.  The origins' start cells and their range verdict
+// (assemble::origin_cell) and the cut into launches are shared with the occupancy grid and live there too.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -14,16 +14,11 @@ namespace lom {
 namespace elevation {
 
 constexpr uint32_t kMaxSide = 8192;      // cells per axis
-constexpr int32_t kCellLimit = 1 << 30;  // |start cell| stays below
 constexpr uint32_t kMaxWindow = 4;       // R of the layer parameters
 constexpr uint32_t kScansPerLaunch = assemble::kAsmScansPerLaunch;  // blockIdx.y of one launch
 
 // scans [first, first + count) of the call: one launch of k_elev_accumulate over the descriptors desc + first
-struct Launch {
-    uint32_t first, count;
-    uint32_t max_n;   // the largest scan of the launch
-    uint32_t grid_x;  // its workgroups
-};
+using Launch = assemble::Launch;
 
 struct Plan {
     assemble::Plan scans;         // descriptors in call order (out / blk are the assembly's and not read here)
@@ -38,8 +33,6 @@ bool point_params_ok(const lom_elevation_point_params *p, float resolution);
 bool layer_params_ok(const lom_elevation_layer_params *p);
 // all four finite and > 0
 bool cost_params_ok(const lom_elevation_cost_params *p);
-// the start cell of scan d (the occupancy definition's step 2); false: |c_a| >= 2^30 or not finite
-bool origin_cell(const assemble::AsmScan &d, const lom_elevation_geometry &g, int32_t c[2]);
 
 // Ids and poses are checked as lom_map_assemble checks them (assemble::plan), then the parameters (LOM_ERR_ARG), then
 // every origin's range (LOM_ERR_RANGE); a launch holds at most scans_per_launch scans (0: kScansPerLaunch).

@@ -14,6 +14,7 @@
 
 #include "assemble_host.hpp"
 #include "k_asm_scan.hpp"
+#include "k_posed_point.hpp"
 
 namespace lom {
 
@@ -36,8 +37,8 @@ __device__ inline uint32_t asm_rank(unsigned long long ballot)
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
 }
 
-// x' = (f32)((R0 p0 + (R1 p1 + R2 p2)) + t0) in f64 -- k_transform's association, widened, one rounding at the end --
-// and the normal likewise without t, written at the scan's place in the concatenated cloud.  kCull: the workgroup's
+// The point at the scan's pose (posed_point, k_posed_point.hpp: f64, one rounding at the end) and the normal likewise
+// without t, written at the scan's place in the concatenated cloud.  kCull: the workgroup's
 // count of points inside the radius goes to counts[scan's row + blockIdx.x].
 template <bool kCull>
 __global__ __launch_bounds__(kAsmThreads) void k_asm_transform(const AsmScan *scans, const float *__restrict__ xyz,
@@ -52,11 +53,9 @@ __global__ __launch_bounds__(kAsmThreads) void k_asm_transform(const AsmScan *sc
     bool keep = false;
     if (i < n) {
         const size_t s = ((size_t)d->src + i) * 3, o = ((size_t)d->out + i) * 3;
-        const double p0 = xyz[s], p1 = xyz[s + 1], p2 = xyz[s + 2];
+        float x, y, z;
+        posed_point(d, xyz + s, x, y, z);
         const double n0 = nrm[s], n1 = nrm[s + 1], n2 = nrm[s + 2];
-        const float x = (float)((d->R[0] * p0 + (d->R[1] * p1 + d->R[2] * p2)) + d->t[0]);
-        const float y = (float)((d->R[3] * p0 + (d->R[4] * p1 + d->R[5] * p2)) + d->t[1]);
-        const float z = (float)((d->R[6] * p0 + (d->R[7] * p1 + d->R[8] * p2)) + d->t[2]);
         out_xyz[o] = x, out_xyz[o + 1] = y, out_xyz[o + 2] = z;
         out_nrm[o] = (float)(d->R[0] * n0 + (d->R[1] * n1 + d->R[2] * n2));
         out_nrm[o + 1] = (float)(d->R[3] * n0 + (d->R[4] * n1 + d->R[5] * n2));

@@ -1,7 +1,8 @@
 // Elevation grid (include/lidar_odometry_amd.h, "elevation grid"): k_elev_clear, k_elev_accumulate, k_elev_unpack and
 // k_elev_derive.  Device code only; elevation.hip is the one translation unit that instantiates and launches it.  The
-// scan descriptor and its constant-address-space read are the assembly's (k_asm_scan.hpp); the transform and the hit
-// rule are k_occ_walk's, restated here so that no occupancy kernel changes.
+// scan descriptor and its constant-address-space read are the assembly's (k_asm_scan.hpp), the transform is the one every
+// posed-scan kernel uses (k_posed_point.hpp).  The hit rule is k_occ_walk's, restated here: shared as one device function
+// it changed the code of both kernels (see k_posed_point.hpp), and device code stays as it is.
 //
 // A cell is one aligned record of 32 bytes -- sum, count, zmin, zmax -- so its four accumulators share a sector.  All
 // accumulation is integer atomics: 64-bit add, 32-bit add, signed min and max; the result does not depend on any order.
@@ -12,6 +13,7 @@
 #include <cstdint>
 
 #include "k_asm_scan.hpp"
+#include "k_posed_point.hpp"
 
 namespace lom {
 
@@ -76,7 +78,7 @@ __device__ __forceinline__ bool elev_update(ElevCell *c, uint32_t cnt, int32_t l
 }
 
 // A lane per point of its scan (blockIdx.y), all scans of a call in one launch.  The point (12 bytes of a record) is
-// transformed as k_asm_transform does -- f64, one rounding to f32 -- and never stored.  Consecutive points of a ring land
+// transformed by posed_point and never stored.  Consecutive points of a ring land
 // in the same cell, so the lanes of a wave that share a cell are merged before anything goes to memory: the first
 // contributing lane's cell is broadcast, its sharers are reduced across the wave (a lone lane skips the reduction) and
 // retire, until none is left -- one count add, one min, one max and one 64-bit add per distinct cell per wave.
@@ -92,10 +94,8 @@ __global__ __launch_bounds__(kAsmThreads) void k_elev_accumulate(const AsmScan *
     int32_t zq = 0;
     if (i < n) {
         const size_t s = ((size_t)d->src + i) * a.stride;
-        const double p0 = xyz[s], p1 = xyz[s + 1], p2 = xyz[s + 2];
-        const float px = (float)((d->R[0] * p0 + (d->R[1] * p1 + d->R[2] * p2)) + d->t[0]);
-        const float py = (float)((d->R[3] * p0 + (d->R[4] * p1 + d->R[5] * p2)) + d->t[1]);
-        const float pz = (float)((d->R[6] * p0 + (d->R[7] * p1 + d->R[8] * p2)) + d->t[2]);
+        float px, py, pz;
+        posed_point(d, xyz + s, px, py, pz);
         const double r = (double)a.resolution, Gx = (double)a.origin_x, Gy = (double)a.origin_y;
         const double Ox = (double)(float)d->t[0], Oy = (double)(float)d->t[1], Oz = (double)(float)d->t[2];
         const double Dx = (double)px - Ox, Dy = (double)py - Oy, Dz = (double)pz - Oz;

@@ -1,6 +1,7 @@
 // Occupancy grid (include/lidar_odometry_amd.h, "occupancy grid"): k_occ_walk, k_occ_fold and k_occ_classify.  Device code
 // only; occupancy.hip is the one translation unit that instantiates and launches it.  The scan descriptor and its
-// constant-address-space read are the assembly's (k_asm_scan.hpp), the transform is k_asm_transform's.
+// constant-address-space read are the assembly's (k_asm_scan.hpp), the transform is the one every posed-scan kernel
+// uses (k_posed_point.hpp).
 //
 // A launch of k_occ_walk holds a slice of up to 64 scans: blockIdx.y names the scan and its two bitmaps, pass and hit, of
 // height x ceil(width / 32) u32 each.  Bits are only ever set, so a lane that goes to global memory first looks with a
@@ -13,6 +14,7 @@
 #include <cstdint>
 
 #include "k_asm_scan.hpp"
+#include "k_posed_point.hpp"
 
 namespace lom {
 
@@ -51,8 +53,8 @@ __device__ __forceinline__ double occ_t(int c, int s, double r, double O2, doubl
     return ((double)b * r - O2) / D;
 }
 
-// The hot path: a lane per ray of its scan.  The point (12 bytes of a record) is transformed as k_asm_transform does --
-// f64, one rounding to f32 -- and never stored.  cell: the scan's start cells (x, y per scan, the host's verdict).
+// The hot path: a lane per ray of its scan.  The point (12 bytes of a record) is transformed by posed_point
+// (k_posed_point.hpp) and never stored.  cell: the scan's start cells (x, y per scan, the host's verdict).
 // bitmaps: [scan of the slice][pass, hit][row][word].
 __global__ __launch_bounds__(kAsmThreads) void k_occ_walk(const AsmScan *scans, const int32_t *cell, const float *__restrict__ xyz,
                                                           OccArgs a, uint32_t *bitmaps, uint32_t *words)
@@ -77,10 +79,8 @@ __global__ __launch_bounds__(kAsmThreads) void k_occ_walk(const AsmScan *scans, 
     bool walk = false, is_hit = false;
     if (i < n) {
         const size_t s = ((size_t)d->src + i) * a.stride;
-        const double p0 = xyz[s], p1 = xyz[s + 1], p2 = xyz[s + 2];
-        const float px = (float)((d->R[0] * p0 + (d->R[1] * p1 + d->R[2] * p2)) + d->t[0]);
-        const float py = (float)((d->R[3] * p0 + (d->R[4] * p1 + d->R[5] * p2)) + d->t[1]);
-        const float pz = (float)((d->R[6] * p0 + (d->R[7] * p1 + d->R[8] * p2)) + d->t[2]);
+        float px, py, pz;
+        posed_point(d, xyz + s, px, py, pz);
         const double r = (double)a.resolution, Gx = (double)a.origin_x, Gy = (double)a.origin_y;
         const double Ox = (double)(float)d->t[0], Oy = (double)(float)d->t[1], Oz = (double)(float)d->t[2];
         const double O2x = Ox - Gx, O2y = Oy - Gy;

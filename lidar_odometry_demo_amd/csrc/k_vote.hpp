@@ -14,6 +14,7 @@
 #include "grid_scan.hpp"
 #include "k_asm_scan.hpp"
 #include "k_carve_cell.hpp"
+#include "k_posed_point.hpp"
 #include "lom_internal.hpp"
 
 namespace lom {
@@ -42,7 +43,7 @@ __device__ __forceinline__ void vote_mark(unsigned long long *mask, unsigned lon
 }
 
 // The hot path: a lane per ray of its scan.  The archive point and normal (24 bytes) are transformed as k_asm_transform
-// does -- f64, one rounding to f32 -- and never stored; the endpoint's voxel gets the scan's bit in hitmask, every live
+// does -- posed_point (k_posed_point.hpp), the normal likewise without t -- and never stored; the endpoint's voxel gets the scan's bit in hitmask, every live
 // voxel the walk visits gets it in crossmask.  The walk is k_carve_walk's but for t_end (the header's step 4).
 __global__ __launch_bounds__(kAsmThreads) void k_vote_walk(const AsmScan *scans, const float *__restrict__ xyz,
                                                            const float *__restrict__ nrm, VoteArgs a, const Slot *table,
@@ -59,11 +60,9 @@ __global__ __launch_bounds__(kAsmThreads) void k_vote_walk(const AsmScan *scans,
     bool walk = false, range_error = false;
     if (i < n) {
         const size_t s = ((size_t)d->src + i) * 3;
-        const double p0 = xyz[s], p1 = xyz[s + 1], p2 = xyz[s + 2];
+        float px, py, pz;
+        posed_point(d, xyz + s, px, py, pz);
         const double n0 = nrm[s], n1 = nrm[s + 1], n2 = nrm[s + 2];
-        const float px = (float)((d->R[0] * p0 + (d->R[1] * p1 + d->R[2] * p2)) + d->t[0]);
-        const float py = (float)((d->R[3] * p0 + (d->R[4] * p1 + d->R[5] * p2)) + d->t[1]);
-        const float pz = (float)((d->R[6] * p0 + (d->R[7] * p1 + d->R[8] * p2)) + d->t[2]);
         const float nx = (float)(d->R[0] * n0 + (d->R[1] * n1 + d->R[2] * n2));
         const float ny = (float)(d->R[3] * n0 + (d->R[4] * n1 + d->R[5] * n2));
         const float nz = (float)(d->R[6] * n0 + (d->R[7] * n1 + d->R[8] * n2));

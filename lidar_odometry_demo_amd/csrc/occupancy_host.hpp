@@ -1,7 +1,8 @@
 // Host planning of the occupancy grid (occupancy_host.cpp), shared with occupancy.hip.  Plain C++: nothing here needs a
 // device.  The scan descriptors and their checks are the assembly's (assemble_host.hpp); what is added is the value
-// ranges of the geometry, the ray parameters and the rule, the origins' start cells and their range verdict, the step
-// bound of the walk, the slice size the scratch budget admits, and the slices of a call with their bounding boxes.
+// ranges of the geometry, the ray parameters and the rule, the step bound of the walk, the slice size the scratch budget
+// admits, and the bounding boxes of a call's slices.  The origins' start cells and their range verdict
+// (assemble::origin_cell) and the cut into launches are shared with the elevation grid and live there too.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -17,7 +18,6 @@ constexpr uint32_t kSliceScans = 64;               // scans of one launch at mos
 constexpr uint32_t kMaxSide = 16384;               // cells per axis
 constexpr size_t kScratchBudget = size_t(256) << 20;  // bytes of pass + hit bitmaps a handle may own
 constexpr uint32_t kWindowMax = 512;               // side of the walk's LDS window in cells: 512 x 512 bits = 32 KB
-constexpr int32_t kCellLimit = 1 << 30;            // |start cell| stays below
 
 inline uint32_t words_per_row(uint32_t width) { return (width + 31u) / 32u; }
 // u32 words of one bitmap (a scan of a slice has two: pass and hit)
@@ -30,11 +30,8 @@ struct Box {
 };
 
 // scans [first, first + count) of the call: one launch of k_occ_walk over the descriptors desc + first, one k_occ_fold
-struct Slice {
-    uint32_t first, count;
-    uint32_t max_n;   // the largest scan of the slice
-    uint32_t grid_x;  // its workgroups
-    Box box;          // every cell a bit of the slice can fall into: origins +- max_range, clipped to the grid
+struct Slice : assemble::Launch {
+    Box box;  // every cell a bit of the slice can fall into: origins +- max_range, clipped to the grid
 };
 
 struct Plan {
@@ -51,8 +48,6 @@ bool rule_ok(const lom_occupancy_rule *r);
 uint32_t max_steps(float max_range, float resolution);
 // min(64, what kScratchBudget admits, at least 1), then capped by test_slice_max (0: no cap)
 uint32_t slice_scans(const lom_occupancy_geometry &g, uint32_t test_slice_max);
-// the start cell of scan d (the header's step 2); false: |c_a| >= 2^30 or not finite
-bool origin_cell(const assemble::AsmScan &d, const lom_occupancy_geometry &g, int32_t c[2]);
 // the cells within max_range of an origin at start cell c, two cells of slack, clipped to the grid
 Box box_of(const int32_t c[2], float max_range, const lom_occupancy_geometry &g);
 Box box_union(const Box &a, const Box &b);

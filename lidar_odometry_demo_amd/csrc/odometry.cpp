@@ -13,6 +13,48 @@
 
 using namespace lom;
 
+// the last frame's deskewed cloud as lom_odometry_place_descriptor reads it: the front end's copy in HBM (*event: its done
+// event) or the host copy of a host-stage frame (*event NULL); records of sizeof(lom_point_xyzirt) bytes
+static int deskewed_cloud(lom_odometry *o, const float **pts, size_t *n, void **event)
+{
+    *n = o->temp_points;
+    *event = nullptr;
+    if (!o->temp_on_device) {
+        *pts = reinterpret_cast<const float *>(o->deskewed.data());
+        return LOM_OK;
+    }
+    const lom_point_xyzirt *d = nullptr;
+    uint32_t nd = 0;
+    const int rc = lom_frontend_deskewed(o->frontend, &d, &nd);
+    if (rc != LOM_OK) return rc;
+    *pts = reinterpret_cast<const float *>(d);
+    *n = nd;
+    *event = lom_frontend_done_event(o->frontend);
+    return LOM_OK;
+}
+
+// that cloud at the current pose into a 2-D grid of family G (csrc/occupancy.hip, csrc/elevation.hip), through the
+// family's device-cloud or host-cloud integrate; reads only
+template <class G, class P, class S, class DeviceOf, class LastError, class FromDevice, class FromHost>
+static int grid_scan(lom_odometry *o, G *g, const P *p, S *stats, DeviceOf device_of, LastError last_error, FromDevice from_device,
+                     FromHost from_host)
+{
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (!o || !g || device_of(g) != o->device) return LOM_ERR_ARG;
+    if (o->temp_points == 0) return LOM_ERR_STATE;  // no frame yet
+    const float *pts = nullptr;
+    size_t n = 0;
+    void *event = nullptr;
+    int rc = deskewed_cloud(o, &pts, &n, &event);
+    if (rc != LOM_OK) return rc;
+    lom_graph_pose pose;
+    if ((rc = lom_graph_pose_from_f32(&o->current, &pose)) != LOM_OK) return rc;
+    const size_t stride = sizeof(lom_point_xyzirt);
+    rc = o->temp_on_device ? from_device(g, pts, n, stride, &pose, p, event, stats) : from_host(g, pts, n, stride, &pose, p, stats);
+    if (rc != LOM_OK) o->error = last_error(g);
+    return rc;
+}
+
 extern "C" {
 
 void lom_odometry_default_params(lom_odometry_params *p)
@@ -153,26 +195,6 @@ int lom_odometry_archive_scan(lom_odometry *o, lom_archive *a, int64_t *id_out)
     return LOM_OK;
 }
 
-// the last frame's deskewed cloud as lom_odometry_place_descriptor reads it: the front end's copy in HBM (*event: its done
-// event) or the host copy of a host-stage frame (*event NULL); records of sizeof(lom_point_xyzirt) bytes
-static int deskewed_cloud(lom_odometry *o, const float **pts, size_t *n, void **event)
-{
-    *n = o->temp_points;
-    *event = nullptr;
-    if (!o->temp_on_device) {
-        *pts = reinterpret_cast<const float *>(o->deskewed.data());
-        return LOM_OK;
-    }
-    const lom_point_xyzirt *d = nullptr;
-    uint32_t nd = 0;
-    const int rc = lom_frontend_deskewed(o->frontend, &d, &nd);
-    if (rc != LOM_OK) return rc;
-    *pts = reinterpret_cast<const float *>(d);
-    *n = nd;
-    *event = lom_frontend_done_event(o->frontend);
-    return LOM_OK;
-}
-
 // that cloud, every point of it and no normals, into a scan archive (csrc/archive.hip); reads only
 int lom_odometry_archive_deskewed(lom_odometry *o, lom_archive *a, int64_t *id_out)
 {
@@ -193,44 +215,16 @@ int lom_odometry_archive_deskewed(lom_odometry *o, lom_archive *a, int64_t *id_o
     return LOM_OK;
 }
 
-// that cloud at the current pose into an occupancy grid (csrc/occupancy.hip); reads only
 int lom_odometry_occupancy_scan(lom_odometry *o, lom_occupancy *g, const lom_occupancy_ray_params *p, lom_occupancy_stats *stats)
 {
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!o || !g || lom_occupancy_device(g) != o->device) return LOM_ERR_ARG;
-    if (o->temp_points == 0) return LOM_ERR_STATE;  // no frame yet
-    const float *pts = nullptr;
-    size_t n = 0;
-    void *event = nullptr;
-    int rc = deskewed_cloud(o, &pts, &n, &event);
-    if (rc != LOM_OK) return rc;
-    lom_graph_pose pose;
-    if ((rc = lom_graph_pose_from_f32(&o->current, &pose)) != LOM_OK) return rc;
-    const size_t stride = sizeof(lom_point_xyzirt);
-    rc = o->temp_on_device ? lom_occupancy_integrate_cloud_device(g, pts, n, stride, &pose, p, event, stats)
-                           : lom_occupancy_integrate_cloud(g, pts, n, stride, &pose, p, stats);
-    if (rc != LOM_OK) o->error = lom_occupancy_last_error(g);
-    return rc;
+    return grid_scan(o, g, p, stats, lom_occupancy_device, lom_occupancy_last_error, lom_occupancy_integrate_cloud_device,
+                     lom_occupancy_integrate_cloud);
 }
 
-// its twin for an elevation grid (csrc/elevation.hip); reads only
 int lom_odometry_elevation_scan(lom_odometry *o, lom_elevation *g, const lom_elevation_point_params *p, lom_elevation_stats *stats)
 {
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!o || !g || lom_elevation_device(g) != o->device) return LOM_ERR_ARG;
-    if (o->temp_points == 0) return LOM_ERR_STATE;  // no frame yet
-    const float *pts = nullptr;
-    size_t n = 0;
-    void *event = nullptr;
-    int rc = deskewed_cloud(o, &pts, &n, &event);
-    if (rc != LOM_OK) return rc;
-    lom_graph_pose pose;
-    if ((rc = lom_graph_pose_from_f32(&o->current, &pose)) != LOM_OK) return rc;
-    const size_t stride = sizeof(lom_point_xyzirt);
-    rc = o->temp_on_device ? lom_elevation_integrate_cloud_device(g, pts, n, stride, &pose, p, event, stats)
-                           : lom_elevation_integrate_cloud(g, pts, n, stride, &pose, p, stats);
-    if (rc != LOM_OK) o->error = lom_elevation_last_error(g);
-    return rc;
+    return grid_scan(o, g, p, stats, lom_elevation_device, lom_elevation_last_error, lom_elevation_integrate_cloud_device,
+                     lom_elevation_integrate_cloud);
 }
 
 // the keyframe again from archived scans at corrected poses: the steps of the header, in its order

@@ -10,9 +10,9 @@ namespace vote {
 
 bool params_ok(const lom_vote_params *p)
 {
-    const float big = 3.402823466e+38f;  // (a NaN fails every comparison below)
-    return p && p->margin >= 0.f && p->margin <= big && p->min_range > 0.f && p->max_range > p->min_range &&
-           p->max_range <= big && p->clearance >= 0.f && p->clearance <= big && p->min_free_scans >= 1u;
+    using assemble::kBig;  // (a NaN fails every comparison below)
+    return p && p->margin >= 0.f && p->margin <= kBig && p->min_range > 0.f && p->max_range > p->min_range &&
+           p->max_range <= kBig && p->clearance >= 0.f && p->clearance <= kBig && p->min_free_scans >= 1u;
 }
 
 uint32_t max_steps(float max_range, float voxel_size)
@@ -42,16 +42,7 @@ int plan(const assemble::ScanEntry *table, size_t n_scans, const int64_t *ids, c
         why = "vote parameters: margin >= 0, 0 < min_range < max_range, clearance >= 0, all finite, min_free_scans >= 1";
         return LOM_ERR_ARG;
     }
-    const uint32_t per = (slice_max == 0 || slice_max > kSliceScans) ? kSliceScans : slice_max;
-    for (size_t first = 0; first < count; first += per) {
-        Slice s;
-        s.first = (uint32_t)first;
-        s.count = (uint32_t)std::min<size_t>(per, count - first);
-        s.max_n = 0;
-        for (uint32_t k = 0; k < s.count; k++) s.max_n = std::max(s.max_n, out.scans.scans[first + k].n);
-        s.grid_x = (s.max_n + assemble::kAsmThreads - 1) / assemble::kAsmThreads;
-        if (s.max_n) out.slices.push_back(s);
-    }
+    out.slices = assemble::cut_launches(out.scans, (slice_max == 0 || slice_max > kSliceScans) ? kSliceScans : slice_max);
     return LOM_OK;
 }
 

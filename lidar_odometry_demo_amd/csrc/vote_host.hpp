@@ -15,11 +15,7 @@ namespace vote {
 constexpr uint32_t kSliceScans = 64;  // scans of one launch: a bit each in a voxel's 64-bit hit and cross masks
 
 // scans [first, first + count) of the call: one launch of k_vote_walk over the descriptors desc + first, one k_vote_fold
-struct Slice {
-    uint32_t first, count;
-    uint32_t max_n;   // the largest scan of the slice
-    uint32_t grid_x;  // its workgroups: blockIdx.x runs over them, blockIdx.y over the slice's scans
-};
+using Slice = assemble::Launch;
 
 struct Plan {
     assemble::Plan scans;       // descriptors in call order (out / blk are the assembly's and not read here)
