@@ -667,7 +667,7 @@ int lom_scan_quality_device(lom_scan *s, const float *d_src_xyz, size_t n, size_
  * Clouds: problems may share a cloud (equal pointer, n and stride: the pose-lattice case is one cloud and K poses; the
  *   host entries upload such a cloud once) and may differ in n, 0 and 1 included.  Every s-th point of a cloud is
  *   stride_bytes * s and n / s.
- * Rounds: the call runs as many rounds as a byte budget for a round's records and partial sums asks for (csrc/quality_report.hip
+ * Rounds: the call runs as many rounds as a byte budget for a round's records and partial sums asks for (csrc/match_plan.hpp
  *   kQualBatchBudgetBytes); all rounds are enqueued before the host waits, once.  LOM_OPT_TEST_QUALITY_ROUND_MAX caps a
  *   round's problems for the tests.
  * Determinism: the bytes of problem i's sums depend only on (map, cloud, n, stride, pose, max_dist, counted or not) --

@@ -19,27 +19,6 @@ namespace lom {
 // iteration; the pose travels from pair to pair through AlignState in HBM, so the host enqueues
 // pairs without waiting for results (chain_start / chain_continue).
 
-// k_lm's workgroups wait for each other inside the kernel, so all of them must be resident at once:
-// the grid never exceeds what the occupancy query admits on this device.
-// Workgroup size: 256 threads for clouds that 64 such workgroups cover with one point per lane (<= 16,384 points) or
-// with TWO points per lane, both in registers for the whole solve (<= 32,768: the VLP16 scan of C2), else 512:
-// the wave-level reduction is bound by the CU's f64 issue rate, and four waves -- one per SIMD -- are through it
-// in half the time of eight; the final sum adds 8 partial sums instead of 16; two register points per lane are
-// accumulated stage by stage so that their independent chains interleave (1.4k cycles for the two against 0.95k for
-// one).  C2 (profiles/r03_*): k_lm 18.9 -> 17.8 us per launch against 512 threads with one point per lane; eight
-// points per lane (C3 on 64 workgroups of 256) lose: 24.4-25.5 against 22.4 us.
-// Clouds beyond what 64 workgroups of 512 cover with two points per lane (C3, C4 on one GPU) take up to 128 workgroups:
-// the accumulation halves, the gather reads twice as many records (on C2-sized clouds that trade loses).
-LmShape lm_shape(uint32_t n)
-{
-    if (n <= kMaxLmBlocks * kLmSmallThreads) return kLmSmall;
-    if (n <= 2u * kMaxLmBlocks * kLmSmallThreads) return kLmSmall2;  // 256 threads, two points per lane in registers
-    // (for C3's 124k points 128 workgroups of 256 threads with four points per lane in registers -- no point re-read
-    // per evaluation -- measured the same as 512 threads with one: align 0.2315-0.2324 against 0.2314-0.2335 ms on one
-    // box; eight per lane for C4's 248k points lose, 0.448 against 0.343 ms: AGPR spills, eight points in a row)
-    return n <= 2u * kMaxLmBlocks * (uint32_t)kEvalThreads ? kLmMid : kLmBig;
-}
-
 // compute units a launch of this handle reaches: its partition's where it has one
 int device_cus(lom_map *m, uint32_t *out)
 {
@@ -49,6 +28,8 @@ int device_cus(lom_map *m, uint32_t *out)
     return LOM_OK;
 }
 
+// k_lm's workgroups wait for each other inside the kernel, so all of them must be resident at once:
+// the grid never exceeds what the occupancy query admits on this device (the shapes and their grids: match_plan.cpp).
 static int lm_block_limit(lom_map *m, LmShape shape, uint32_t *out)
 {
     uint32_t &cached = m->lm_max_blocks[shape];
@@ -66,11 +47,10 @@ static int lm_block_limit(lom_map *m, LmShape shape, uint32_t *out)
 // the grid of a solve: one point per point thread up to the shape's cap, and no more than is resident at once
 int lm_grid(lom_map *m, uint32_t n, LmShape shape, uint32_t *nb)
 {
-    const LmGeometry &f = kLmGeometry[shape];
     uint32_t limit = 0;
     const int rc = lm_block_limit(m, shape, &limit);
     if (rc != LOM_OK) return rc;
-    *nb = std::min(std::min(std::max(1u, (n + f.points - 1) / f.points), f.cap), limit);
+    *nb = lm_blocks(n, shape, limit);
     return LOM_OK;
 }
 

@@ -28,7 +28,8 @@ namespace lom {
 //   round: the launch is sized for the largest, and a problem's descriptor names its own (streams of similar clouds
 //   differ by a workgroup or two; one round per grid made K streams K rounds).
 // Rounds.  k_lm's workgroups wait for each other, so a round's whole grid must be resident at once: problems per round =
-//   floor(CUs x blocks per CU / the group's largest nb), CUs of the context's partition where it has one.  Blocks per CU: the occupancy query
+//   floor(CUs x blocks per CU / the group's largest nb), CUs of the context's partition where it has one
+//   (plan_align_rounds, match_plan.cpp: plain C++, tested on the CPU).  Blocks per CU: the occupancy query
 //   for the batch kernel, capped at 2 (the query over-reports only where SGPRs bind, from 7 blocks of 256 threads per CU
 //   up -- MI355X "Residency and cooperative launch" -- far above the cap).  LOM_OPT_TEST_BATCH_ROUND_MAX caps it further.
 // Chain.  kPairsAhead pairs go out at once, then one pair per round of reports while any problem of the round is
@@ -78,77 +79,40 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
 {
     static_assert(sizeof(AlignReport) <= 256, "one report slot");
     const uint32_t part = launch_partition(m);
-    std::vector<LmShape> shape(count);
-    std::vector<uint32_t> nb(count), mb(count);
+    std::vector<AlignPlanProblem> prob(count);
+    std::vector<uint32_t> mb(count);
     for (int i = 0; i < count; i++) {
         const uint32_t n = it[i].n;
-        shape[i] = lm_shape(n);
-        const int rc = lm_grid(m, n, shape[i], &nb[i]);
+        prob[i] = AlignPlanProblem{n, 0u, it[i].map->opt_count, !it[i].map->opt_no_temporal, it[i].give_up_outer};
+        const int rc = lm_grid(m, n, lm_shape(n), &prob[i].nb);
         if (rc != LOM_OK) return rc;
         mb[i] = n ? match_grid(n, part) : 0u;
     }
-    // groups by (variant, counted, temporal) in order of first appearance, cut into rounds; `order` lists the problems round
-    // by round
-    struct Round {
-        int first, size;  // range of `order`
-        LmShape shape;
-        uint32_t nb;  // the largest solve grid of its problems: the launch's x dimension
-        bool counted, temporal;
-        int give_up_outer;  // of its problem 0
-    };
-    auto counted = [&](int i) { return it[i].map->opt_count; };
-    auto temporal = [&](int i) { return !it[i].map->opt_no_temporal; };
-    std::vector<int> order;
-    std::vector<Round> rounds;
-    {
-        std::vector<char> taken(count, 0);
-        uint32_t cus = 0;
-        int rc = device_cus(m, &cus);
-        if (rc != LOM_OK) return rc;
-        for (int i = 0; i < count; i++) {
-            if (taken[i]) continue;
-            uint32_t per_cu = 0;
-            if ((rc = lm_batch_per_cu(m, shape[i], &per_cu)) != LOM_OK) return rc;
-            std::vector<int> members;
-            uint32_t nb_max = 0;
-            for (int k = i; k < count; k++)
-                if (!taken[k] && shape[k] == shape[i] && counted(k) == counted(i) && temporal(k) == temporal(i)) {
-                    taken[k] = 1;
-                    members.push_back(k);
-                    nb_max = std::max(nb_max, nb[k]);
-                }
-            // (a round's launch is sized for its largest grid: residency is counted with the group's largest)
-            int per_round = (int)std::max(1u, cus * per_cu / nb_max);
-            if (m->batch.test_round_max > 0) per_round = std::min(per_round, m->batch.test_round_max);
-            // a problem that carries a give-up test opens a round (the kernel applies it to problem 0 of a launch)
-            for (size_t a = 0; a < members.size();) {
-                size_t size = 1;
-                while (a + size < members.size() && size < (size_t)per_round && it[members[a + size]].give_up_outer < 0) size++;
-                uint32_t grid = 0;
-                for (size_t k = 0; k < size; k++) grid = std::max(grid, nb[members[a + k]]);
-                rounds.push_back(Round{(int)order.size(), (int)size, shape[i], grid, counted(i), temporal(i),
-                                       it[members[a]].give_up_outer});
-                for (size_t k = 0; k < size; k++) order.push_back(members[a + k]);
-                a += size;
-            }
-        }
+    // what the plan needs from the device: its compute units, k_lm's blocks per CU of the shapes that occur
+    uint32_t cus = 0, per_cu[4] = {};
+    int rc = device_cus(m, &cus);
+    if (rc != LOM_OK) return rc;
+    for (int i = 0; i < count; i++) {
+        const LmShape shape = lm_shape(it[i].n);
+        if (!per_cu[shape] && (rc = lm_batch_per_cu(m, shape, &per_cu[shape])) != LOM_OK) return rc;
     }
+    AlignPlan plan;
+    plan_align_rounds(prob.data(), count, cus, per_cu, m->batch.test_round_max, plan);
+    const std::vector<int> &order = plan.order;
+    const std::vector<AlignRound> &rounds = plan.rounds;
     int max_slots = 0;
-    for (const Round &r : rounds) max_slots = std::max(max_slots, r.size);
+    for (const AlignRound &r : rounds) max_slots = std::max(max_slots, r.size);
     // buffers: records and k_match counters per problem, exchange sets per round slot, states + descriptors per problem
     std::vector<size_t> off_rec(count), off_cnt(count);
-    size_t rec_bytes = 0, cnt_bytes = 0;
+    BlockLayout rec, cnt, dev;  // dev: the states, then the descriptors (the staging block is its copy)
     for (int i = 0; i < count; i++) {
-        off_rec[i] = rec_bytes;
-        rec_bytes += round_up256((size_t)std::max(it[i].n, 1u) * sizeof(MatchRec));
-        off_cnt[i] = cnt_bytes;
-        cnt_bytes += round_up256((size_t)std::max(mb[i], 1u) * 16);
+        off_rec[i] = rec.take((size_t)std::max(it[i].n, 1u) * sizeof(MatchRec));
+        off_cnt[i] = cnt.take((size_t)std::max(mb[i], 1u) * kMatchCounterBytes);
     }
-    const size_t states_bytes = round_up256((size_t)count * sizeof(AlignState));
-    const size_t dev_bytes = states_bytes + (size_t)count * sizeof(BatchProblem);
-    int rc;
-    if ((rc = ensure(m, m->batch.rec, rec_bytes)) != LOM_OK) return rc;
-    if ((rc = ensure(m, m->batch.cnt, cnt_bytes)) != LOM_OK) return rc;
+    dev.take((size_t)count * sizeof(AlignState));
+    const size_t off_desc = dev.take((size_t)count * sizeof(BatchProblem)), dev_bytes = dev.end;
+    if ((rc = ensure(m, m->batch.rec, rec.next)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->batch.cnt, cnt.next)) != LOM_OK) return rc;
     if ((rc = ensure(m, m->batch.dev, dev_bytes)) != LOM_OK) return rc;
     {
         void *before = m->batch.xrec.p;
@@ -169,10 +133,10 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
     }
     // states (the guess as the first search's pose) and descriptors, in `order`, one copy to the device
     AlignState *h_states = reinterpret_cast<AlignState *>(m->batch.stage.h);
-    BatchProblem *h_desc = reinterpret_cast<BatchProblem *>((char *)m->batch.stage.h + states_bytes);
+    BatchProblem *h_desc = reinterpret_cast<BatchProblem *>((char *)m->batch.stage.h + off_desc);
     AlignState *d_states = reinterpret_cast<AlignState *>(m->batch.dev.p);
-    const BatchProblem *d_desc = reinterpret_cast<const BatchProblem *>(m->batch.dev.as<char>() + states_bytes);
-    for (const Round &r : rounds)
+    const BatchProblem *d_desc = reinterpret_cast<const BatchProblem *>(m->batch.dev.as<char>() + off_desc);
+    for (const AlignRound &r : rounds)
         for (int k = 0; k < r.size; k++) {
             const int j = r.first + k, i = order[j];
             AlignState &st = h_states[j];
@@ -183,14 +147,14 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
                         sq_f32(0.3f));  // cloud_matcher.cpp:139
             d.report = reinterpret_cast<AlignReport *>((char *)m->batch.reports.d + (size_t)j * 256);
             d.xrec = m->batch.xrec.as<char>() + (size_t)k * kExchangeSetBytes;
-            d.lm_blocks = nb[i];
+            d.lm_blocks = prob[i].nb;
             set_guess(it[i].gt, it[i].gq, d, st);
             volatile AlignReport *rp = reinterpret_cast<volatile AlignReport *>((char *)m->batch.reports.h + (size_t)j * 256);
             rp->error = 0;
         }
     LOM_HIP(m, hipMemcpyAsync(m->batch.dev.p, m->batch.stage.h, dev_bytes, hipMemcpyHostToDevice, m->stream));
     for (size_t ri = 0; ri < rounds.size(); ri++) {
-        const Round &R = rounds[ri];
+        const AlignRound &R = rounds[ri];
         uint32_t mb_max = 0;
         for (int k = 0; k < R.size; k++) mb_max = std::max(mb_max, mb[order[R.first + k]]);
         const BatchProblem *desc = d_desc + R.first;
@@ -229,7 +193,7 @@ static int align_batch_chained(lom_map *m, const BatchItem *it, int count, lom_a
                     any_gave_up = true;
                     done[k] = 1;
                 } else if (rp->finished) {
-                    result_from_report(rp, R.counted, nb[i], out[i]);
+                    result_from_report(rp, R.counted, prob[i].nb, out[i]);
                     out[i].round = (int32_t)ri;
                     done[k] = 1;
                 } else {

@@ -75,20 +75,6 @@ static inline float threshold_f32(double max_sq)
     return f;
 }
 
-uint32_t match_grid(uint32_t n, uint32_t partition_cus)
-{
-    const uint32_t per_block = (uint32_t)(kMatchThreads / kMatchG);
-    const uint32_t need = (n + per_block - 1) / per_block;
-    const uint32_t cap = partition_cus ? partition_cus * (uint32_t)kMatchMinWaves : kMaxMatchBlocks;
-    return std::max(1u, std::min(need, cap));
-}
-
-uint32_t eval_grid(uint32_t n)
-{
-    const uint32_t need = (n + kEvalThreads - 1) / kEvalThreads;
-    return std::max(1u, std::min(need, kMaxEvalBlocks));
-}
-
 int scan_buffers(lom_map *m, uint32_t n, bool want_stats)
 {
     int rc;

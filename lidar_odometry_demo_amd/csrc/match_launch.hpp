@@ -1,33 +1,22 @@
-// What the matcher's host files -- align.hip, align_batch.hip, quality_report.hip -- may call and fill: the launch
-// geometry, the records and descriptors host and kernels exchange, the typed launchers of match.hip (one per kernel
-// form: each takes what that form reads and fills the parameters it does not read itself) and the pieces of the chained
-// align that the single and the batched align share.  No kernel is visible from here: a kernel of the matcher is named
-// -- instantiated, launched, queried -- in match.hip alone, and this header includes no k_*.hpp (they include it).
+// What the matcher's host files -- align.hip, align_batch.hip, quality_report.hip -- may call and fill: the records and
+// descriptors host and kernels exchange, the typed launchers of match.hip (one per kernel form: each takes what that
+// form reads and fills the parameters it does not read itself) and the pieces of the chained align that the single and
+// the batched align share.  The launch geometry and everything planned from sizes alone -- grids, k_lm shapes, the
+// rounds of the batched calls, block offsets -- is match_plan.hpp's, plain C++ that includes no HIP header; this header
+// includes it and keeps what needs a handle or a device type.  No kernel is visible from here: a kernel of the matcher
+// is named -- instantiated, launched, queried -- in match.hip alone, and this header includes no k_*.hpp (they include
+// it).
 #pragma once
 #include <algorithm>
 #include <ctime>
 
 #include "lom_internal.hpp"
+#include "match_plan.hpp"
 
 namespace lom {
 
-// ---- launch geometry ------------------------------------------------------------------------------------------------
-constexpr int kMatchThreads = 256;             // 4 waves
-constexpr int kMatchG = 16;                    // lanes per query: four queries per wave
-constexpr int kMatchRows = 4;                  // consecutive rows of a voxel per chunk: one search and 48 bytes per lane and trip
-constexpr int kMatchMinWaves = 7;              // waves per SIMD the register budget is held to (72 VGPRs)
-constexpr int kEvalThreads = 512;
-constexpr int kRecWords = 32;    // doubles per record
+// ---- of the handle and the chain (the launch geometry: match_plan.hpp) ---------------------------------------------------
 constexpr int kPairsAhead = 5;  // (k_match, k_lm) pairs enqueued before the host looks at a report
-constexpr uint32_t kMaxLmBlocks = 64;    // workgroups of k_lm (one lane of a wave watches each record)
-constexpr uint32_t kMaxLmBlocksBig = 128;  // ... of its variant for large clouds; also the size of an exchange set
-// a solve's pair of exchange sets (k_lm.hpp: 16-byte XWords)
-constexpr size_t kExchangeSetBytes = (size_t)2 * kMaxLmBlocksBig * kRecWords * 16;
-
-constexpr uint32_t kMaxMatchBlocks = 256u * (uint32_t)kMatchMinWaves;  // one resident round: kMatchMinWaves workgroups of 4 waves per CU
-constexpr uint32_t kMaxEvalBlocks = 64;  // records per launch (the host polls this many words)
-uint32_t match_grid(uint32_t n, uint32_t partition_cus = 0);  // (a context on a partition of the GPU: one resident round of ITS compute units)
-uint32_t eval_grid(uint32_t n);
 // the partition a launch of this handle is sized for: its own stream's, none on a caller's stream
 static inline uint32_t launch_partition(const lom_map *m) { return m->stream == m->own_stream ? m->partition_cus : 0u; }
 
@@ -43,7 +32,7 @@ struct __attribute__((aligned(16))) MatchRec {
                               // reads the row back: a query whose winner has not changed leaves its record alone)
     float ny, nz, pad0, pad1;
 };
-static_assert(sizeof(MatchRec) == 48, "three dwordx4");
+static_assert(sizeof(MatchRec) == kMatchRecBytes, "three dwordx4");
 struct QStat;  // k_match.hpp: the per-query debug record of lom_match_find_pairs
 
 // Batched align (lom_match_align_batch / _multi): one problem of a round, read by the batch forms of k_match and k_lm
@@ -80,15 +69,11 @@ struct QualBatchProblem {
     uint32_t n, grid;
     EvalArgs E;
 };
+static_assert(LOM_NQSUMS * sizeof(double) == kQualPartBytes, "a workgroup record of k_quality");
 
 // ---- scans, poses ------------------------------------------------------------------------------------------------------
-// a scan as the entry points take it: a stride that holds three floats and keeps them aligned, a count k_match's 32-bit
-// indices cover
-constexpr size_t kMaxScanPoints = 0x7FFFFFFFull;
-static inline bool stride_ok(size_t stride) { return stride >= 12 && !(stride & 3); }
-static inline bool scan_args_ok(size_t n, size_t stride) { return stride_ok(stride) && n < kMaxScanPoints; }
+// (what a scan's arguments must satisfy: match_plan.hpp)
 static inline float sq_f32(float max_dist) { return max_dist * max_dist; }  // voxel_grid.h:215
-static inline size_t round_up256(size_t b) { return (b + 255) & ~size_t(255); }
 static inline double now_s()
 {
     timespec ts;
@@ -139,22 +124,7 @@ int eval_kernel_attrs(lom_map *m);
 // the hooks of the host-driven loop (lom_align_with_hooks) over one scan: a search plus an evaluation, an evaluation
 lom_align_hooks eval_hooks(ScanCtx &c);
 
-// ---- k_lm's shapes ------------------------------------------------------------------------------------------------------
-// The 256-thread shapes launch one wave more, the policy wave (k_lm): nb and the point assignment count the 256 threads.
-constexpr uint32_t kLmSmallThreads = 256;
-constexpr uint32_t kLmSmallLaunch = kLmSmallThreads + 64;  // the point threads and the policy wave (lm_threads)
-enum LmShape { kLmSmall = 0, kLmMid = 1, kLmBig = 2, kLmSmall2 = 3 };
-struct LmGeometry {
-    uint32_t points;   // point threads of a workgroup
-    uint32_t threads;  // threads of a launch
-    uint32_t cap;      // most workgroups of a solve
-};
-constexpr LmGeometry kLmGeometry[4] = {
-    /* kLmSmall  */ {kLmSmallThreads, kLmSmallLaunch, kMaxLmBlocks},
-    /* kLmMid    */ {(uint32_t)kEvalThreads, (uint32_t)kEvalThreads, kMaxLmBlocks},
-    /* kLmBig    */ {(uint32_t)kEvalThreads, (uint32_t)kEvalThreads, kMaxLmBlocksBig},
-    /* kLmSmall2 */ {kLmSmallThreads, kLmSmallLaunch, kMaxLmBlocks},
-};
+// ---- k_lm's shapes (LmShape, kLmGeometry: match_plan.hpp) ------------------------------------------------------------------
 // hipOccupancyMaxActiveBlocksPerMultiprocessor of the shape's single or batch instantiation
 int lm_blocks_per_cu(lom_map *m, LmShape shape, bool batch, int *per_cu);
 
@@ -185,9 +155,8 @@ void launch_k_quality_batch(lom_map *m, uint32_t blocks, uint32_t problems, cons
 // resident: a caller sharing the GPU, a CU mask) or for a peer rank: the caller redoes the align
 // through the host-driven loop.
 constexpr int kDeviceLoopGaveUp = 100;
-LmShape lm_shape(uint32_t n);
 int device_cus(lom_map *m, uint32_t *out);  // compute units a launch of this handle reaches: its partition's where it has one
-int lm_grid(lom_map *m, uint32_t n, LmShape shape, uint32_t *nb);
+int lm_grid(lom_map *m, uint32_t n, LmShape shape, uint32_t *nb);  // lm_blocks under the handle's occupancy query
 constexpr int kReportArrived = 0, kReportError = 1;
 int wait_report(lom_map *m, const volatile AlignReport *rp, unsigned long long want, const char *solve);
 void result_from_report(const volatile AlignReport *rp, bool counted, uint32_t nb, lom_align_result &r);

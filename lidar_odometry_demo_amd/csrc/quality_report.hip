@@ -96,16 +96,12 @@ int lom_match_quality_device(lom_map *m, const float *d_src, size_t n, size_t st
 //   problem larger than that runs alone); problems go to rounds in the caller's order; the round buffers are reused by
 //   the next round, which the stream orders behind this one.  What grows with K is small: a pose block and two
 //   descriptors (about 0.6 KB) and LOM_NQSUMS totals per problem.  LOM_OPT_TEST_QUALITY_ROUND_MAX caps a round's problems too.
-//   64 MiB: a quarter of the 256 MiB last-level cache, so what a round's search writes is still on the chip when its
-//   evaluation reads it; 46 problems of a 28,800-point scan or 700 of a 1,900-point one -- several times the
-//   workgroups the device has compute units for -- so that more per round would buy nothing.
+//   The cut and the offsets are plan_quality_rounds' (match_plan.cpp: plain C++, tested on the CPU; the budget's
+//   reasons and figures are with kQualBatchBudgetBytes in match_plan.hpp).
 // Clouds.  The host entries upload every distinct (pointer, n, stride) once, before the first round.
 // Isolation.  lom_map::qualb: nothing of the single align, the single report, an armed cleanup scan or idle hook, or the
 //   map-maintenance scratch is read or written; neither call_seq nor mutations move.
 // ---------------------------------------------------------------------------
-constexpr size_t kQualBatchBudgetBytes = (size_t)64 << 20;
-constexpr int kQualBatchRoundCap = 32768;  // problems per round at most (blockIdx.y)
-
 static int quality_batch_args_ok(const lom_map *m, const lom_quality_problem *p, int count, const void *out)
 {
     if (!m || count < 0) return 0;
@@ -142,86 +138,53 @@ static int quality_batch_core(lom_map *m, const lom_quality_problem *p, int coun
         if ((rc = upload_distinct(m, m->qualb.src, clouds.data(), L, d_src.data())) != LOM_OK) return rc;
     }
     // rounds, and where a problem's records, counters and workgroup records lie in its round's buffers
-    struct Round {
-        int first, size;
-        uint32_t mb, nb;  // the launches' x extent: the largest search / evaluation grid of its problems
-    };
-    std::vector<Round> rounds;
-    std::vector<uint32_t> mb(L), nb(L);
-    std::vector<size_t> off_rec(L), off_cnt(L), off_part(L);
-    size_t rec_bytes = 0, cnt_bytes = 0, part_bytes = 0;
-    {
-        const int cap = m->qualb.test_round_max > 0 ? std::min(m->qualb.test_round_max, kQualBatchRoundCap) : kQualBatchRoundCap;
-        size_t r_rec = 0, r_cnt = 0, r_part = 0;
-        for (int j = 0; j < L; j++) {
-            const uint32_t n = (uint32_t)p[live[j]].n;
-            mb[j] = match_grid(n, part_cus);
-            nb[j] = eval_grid(n);
-            const size_t b_rec = round_up256((size_t)n * sizeof(MatchRec)), b_cnt = round_up256((size_t)mb[j] * 16),
-                         b_part = round_up256((size_t)nb[j] * LOM_NQSUMS * 8);
-            const bool open = !rounds.empty() && rounds.back().size < cap &&
-                              r_rec + r_cnt + r_part + b_rec + b_cnt + b_part <= kQualBatchBudgetBytes;
-            if (!open) {
-                rounds.push_back(Round{j, 0, 0u, 0u});
-                r_rec = r_cnt = r_part = 0;
-            }
-            Round &R = rounds.back();
-            R.size++;
-            R.mb = std::max(R.mb, mb[j]);
-            R.nb = std::max(R.nb, nb[j]);
-            off_rec[j] = r_rec;
-            off_cnt[j] = r_cnt;
-            off_part[j] = r_part;
-            r_rec += b_rec;
-            r_cnt += b_cnt;
-            r_part += b_part;
-            rec_bytes = std::max(rec_bytes, r_rec);
-            cnt_bytes = std::max(cnt_bytes, r_cnt);
-            part_bytes = std::max(part_bytes, r_part);
-        }
-    }
-    const size_t states_bytes = round_up256((size_t)L * sizeof(AlignState));
-    const size_t match_desc_bytes = round_up256((size_t)L * sizeof(BatchProblem));
-    const size_t dev_bytes = states_bytes + match_desc_bytes + round_up256((size_t)L * sizeof(QualBatchProblem));
+    std::vector<uint32_t> n_live(L);
+    for (int j = 0; j < L; j++) n_live[j] = (uint32_t)p[live[j]].n;
+    QualPlan plan;
+    plan_quality_rounds(n_live.data(), L, part_cus, m->qualb.test_round_max, plan);
+    // per problem: the pose block the search reads, the search's descriptor, the evaluation's descriptor
+    BlockLayout dev;
+    dev.take((size_t)L * sizeof(AlignState));
+    const size_t off_match = dev.take((size_t)L * sizeof(BatchProblem)), off_eval = dev.take((size_t)L * sizeof(QualBatchProblem));
+    const size_t dev_bytes = dev.next;
     const size_t sums_bytes = (size_t)L * LOM_NQSUMS * 8;
-    if ((rc = ensure(m, m->qualb.rec, rec_bytes)) != LOM_OK) return rc;
-    if ((rc = ensure(m, m->qualb.cnt, cnt_bytes)) != LOM_OK) return rc;
-    if ((rc = ensure(m, m->qualb.part, part_bytes)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qualb.rec, plan.rec_bytes)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qualb.cnt, plan.cnt_bytes)) != LOM_OK) return rc;
+    if ((rc = ensure(m, m->qualb.part, plan.part_bytes)) != LOM_OK) return rc;
     if ((rc = ensure(m, m->qualb.dev, dev_bytes)) != LOM_OK) return rc;
     if ((rc = ensure(m, m->qualb.sums, sums_bytes)) != LOM_OK) return rc;
     // (the uploads above do not read it)
     if ((rc = ensure_pinned(m, m->qualb.stage, dev_bytes + sums_bytes, std::max(dev_bytes + sums_bytes, (size_t)65536),
                             hipHostMallocDefault, "hipHostMalloc(quality batch staging)")) != LOM_OK)
         return rc;
-    // per problem: the pose block the search reads, the search's descriptor, the evaluation's descriptor
     AlignState *h_states = reinterpret_cast<AlignState *>(m->qualb.stage.h);
-    BatchProblem *h_match = reinterpret_cast<BatchProblem *>((char *)m->qualb.stage.h + states_bytes);
-    QualBatchProblem *h_eval = reinterpret_cast<QualBatchProblem *>((char *)m->qualb.stage.h + states_bytes + match_desc_bytes);
+    BatchProblem *h_match = reinterpret_cast<BatchProblem *>((char *)m->qualb.stage.h + off_match);
+    QualBatchProblem *h_eval = reinterpret_cast<QualBatchProblem *>((char *)m->qualb.stage.h + off_eval);
     double *h_sums = reinterpret_cast<double *>((char *)m->qualb.stage.h + dev_bytes);
     AlignState *d_states = reinterpret_cast<AlignState *>(m->qualb.dev.p);
-    const BatchProblem *d_match = reinterpret_cast<const BatchProblem *>(m->qualb.dev.as<char>() + states_bytes);
-    const QualBatchProblem *d_eval =
-        reinterpret_cast<const QualBatchProblem *>(m->qualb.dev.as<char>() + states_bytes + match_desc_bytes);
+    const BatchProblem *d_match = reinterpret_cast<const BatchProblem *>(m->qualb.dev.as<char>() + off_match);
+    const QualBatchProblem *d_eval = reinterpret_cast<const QualBatchProblem *>(m->qualb.dev.as<char>() + off_eval);
     const MapView view = view_of(m);
     const float max_sq = sq_f32(max_dist);
     for (int j = 0; j < L; j++) {
         const lom_quality_problem &q = p[live[j]];
+        const QualPlanProblem &at = plan.problems[j];
         BatchProblem &d = h_match[j];
-        fill_search(d, h_states[j], view, d_src[j], q.stride_bytes, (uint32_t)q.n, mb[j],
-                    reinterpret_cast<MatchRec *>(m->qualb.rec.as<char>() + off_rec[j]),
-                    reinterpret_cast<uint32_t *>(m->qualb.cnt.as<char>() + off_cnt[j]), d_states + j, q.t, q.q_wxyz, max_sq);
+        fill_search(d, h_states[j], view, d_src[j], q.stride_bytes, (uint32_t)q.n, at.mb,
+                    reinterpret_cast<MatchRec *>(m->qualb.rec.as<char>() + at.off_rec),
+                    reinterpret_cast<uint32_t *>(m->qualb.cnt.as<char>() + at.off_cnt), d_states + j, q.t, q.q_wxyz, max_sq);
         QualBatchProblem &e = h_eval[j];
         std::memset(&e, 0, sizeof e);
         e.rec = d.rec;
-        e.part = reinterpret_cast<double *>(m->qualb.part.as<char>() + off_part[j]);
+        e.part = reinterpret_cast<double *>(m->qualb.part.as<char>() + at.off_part);
         e.out = m->qualb.sums.as<double>() + (size_t)j * LOM_NQSUMS;
         e.n = d.n;
-        e.grid = nb[j];
+        e.grid = at.nb;
         for (int a = 0; a < 4; a++) e.E.q[a] = (double)q.q_wxyz[a];
         for (int a = 0; a < 3; a++) e.E.t[a] = (double)q.t[a];
     }
     LOM_HIP(m, hipMemcpyAsync(m->qualb.dev.p, m->qualb.stage.h, dev_bytes, hipMemcpyHostToDevice, m->stream));
-    for (const Round &R : rounds) {
+    for (const QualRound &R : plan.rounds) {
         launch_k_match_batch(m, false, m->opt_count, dim3(R.mb, R.size), d_match + R.first);
         launch_k_quality_batch(m, R.nb, (uint32_t)R.size, d_eval + R.first);
         LOM_HIP(m, hipGetLastError());
