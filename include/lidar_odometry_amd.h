@@ -1563,6 +1563,118 @@ int lom_elevation_cost(lom_elevation *g, const lom_elevation_layer_params *lp, c
 int lom_elevation_cost_device(lom_elevation *g, const lom_elevation_layer_params *lp, const lom_elevation_cost_params *cp,
                               const int8_t **d_out);
 
+/* ---- clearance grid: obstacle distance and inflated cost from the two grids (not in the reference) --------------------
+ * The occupancy and the elevation grid each leave an int8 plane in HBM.  A planner reads neither as it is: it reads, per
+ * cell, the distance to the nearest obstacle and a cost that is lethal on the obstacle, "inscribed" within the robot's
+ * radius and decays out to an inflation radius (the inflation layer of nav2-style stacks).  This handle family merges the
+ * two planes, computes an exact truncated Euclidean distance transform on the device and the inflated cost from it.
+ * Nothing is launched unless a caller creates a clearance grid.  The definition, operation by operation
+ * (tests/clearance_ref.py restates it in numpy; the distance is an integer -- squared cells -- so every comparison is
+ * exact; the one tolerance of the feature is the last ulp of exp() in the host-built cost table, see step 3):
+ *
+ * Grid.  lom_occupancy_geometry, reused: cell (ix, iy) covers [origin + i r, origin + (i + 1) r) per axis, storage is
+ * row-major with y as the row, the index rule is the occupancy grid's floor rule.  r > 0 and finite, a finite origin,
+ * 1 <= width, height <= 8192; anything else is LOM_ERR_ARG.  A cell costs 5 bytes and 1 bit of HBM at rest (base i8, d2 u16,
+ * cost i8, a bitmap bit), 2 more from the first update with host planes on.
+ *
+ * Inputs of an update.  Two full-grid int8 planes, either of which may be NULL (it then reads as all -1), not both:
+ * occ holds -1 / 0 / 100, elev holds -1 / 0 .. 99 / 100.  Any other value reads as -1, and a cell with such a value in
+ * either plane counts once in cells_invalid.  lom_clearance_params: 0 <= inscribed_radius <= inflation_radius,
+ * decay >= 0, all finite, no unknown bit in flags, R (step 2) <= 254; anything else is LOM_ERR_ARG.
+ *  1. Merge.  With o and e the cell's two values:
+ *       cleared  = e == 100 && (flags & LOM_CLEAR_FREE_CLEARS_ELEVATION) && o == 0: the cell counts in cells_cleared and
+ *                  reads e = 0 -- a FREE vote of the occupancy grid drops the ghost height a mover left;
+ *       base     = 100 if o == 100 || e == 100;  else e if 0 <= e <= 99;  else 0 if o == 0;  else -1.
+ *     A cell is an obstacle iff base == 100, or base == -1 and flags & LOM_CLEAR_UNKNOWN_IS_OBSTACLE.  Cells outside the
+ *     grid are never obstacles.
+ *  2. Distance.  R = floor((double)inflation_radius / (double)r), 0 <= R <= 254.  d2[cell] = the minimum over all obstacle
+ *     cells of dx^2 + dy^2, in cells, if that is <= R^2; else LOM_CLEAR_FAR (65535).  u16: 254^2 = 64516 fits.
+ *  3. Cost table, R^2 + 1 bytes, built on the host in f64.  With dist = sqrt((double)k) * (double)r, in this order:
+ *       table[0] = 100;  99 where dist <= inscribed_radius;  0 where dist > inflation_radius;
+ *       else floor(98 * exp(-(double)decay * (dist - (double)inscribed_radius))).
+ *     The device only indexes it: no transcendental runs on the device.  lom_clearance_cost_table gives the bytes.
+ *  4. Cost.  c = table[d2], 0 where d2 is far.  An obstacle gives 100; a known base (0 .. 99) gives max(base, c); an
+ *     unknown base gives c if c > 0, else -1.  int8, the value range of nav_msgs/OccupancyGrid.
+ *  5. Metres.  lom_clearance_distance gives (float)(sqrt((double)d2) * (double)r), +inf where d2 is far.
+ * Summary, counted over the updated rectangle: cells_lethal (cost 100), cells_inscribed (99), cells_costed (0 .. 98),
+ * cells_unknown (-1) -- the four add up to the rectangle's cells -- and cells_invalid, cells_cleared as above.
+ *
+ * Window.  An update takes an optional rectangle {x0, y0, width, height} in cells, clipped to the grid; NULL is the whole
+ * grid; an empty rectangle is LOM_OK and changes nothing.  Only the rectangle's d2 and cost are rewritten.  Obstacles up
+ * to R cells outside the rectangle count: they are read from the planes given to this call, so a windowed update over any
+ * rectangle gives, on that rectangle, the bytes of the full update of the same planes.  After create or
+ * lom_clearance_clear: d2 = far, cost = -1 everywhere.
+ *
+ * The result is a pure function of the inputs: it does not depend on the tile shape (LOM_CLEAR_OPT_TEST_TILE_ROWS), on
+ * the pruning of the column pass (LOM_CLEAR_OPT_TEST_NO_PRUNE) or on how the work is cut into launches.
+ *
+ * lom_clearance_update takes host planes of width * height bytes; _update_device takes planes in HBM that are complete
+ * when hip_event_or_null is (NULL: now).  _update_from_grids calls lom_occupancy_classify_device and
+ * lom_elevation_cost_device itself (either grid may be NULL, not both; the parameters of a NULL grid are not read) and
+ * orders the three streams by events in both directions; grids whose resolution, origin, width or height differ bit for
+ * bit from the clearance grid's, or that live on another device, are LOM_ERR_ARG before any launch, as are bad
+ * parameters of any of the three.  Every argument is validated before any device work; a refused call changes nothing
+ * and zeroes the summary.  Every call returns with its work done.  Calls on one grid are the caller's to serialise.  The
+ * error text is the grid's (lom_clearance_last_error). */
+typedef struct lom_clearance lom_clearance;
+typedef struct {
+    float inflation_radius; /* m: beyond it the distance is "far" and the table is 0 */
+    float inscribed_radius; /* m: within it the cost is 99 */
+    float decay;            /* 1 / m: the exponent of the decay between the two */
+    uint32_t flags;         /* LOM_CLEAR_* */
+} lom_clearance_params;
+typedef struct {
+    int32_t x0, y0;         /* may lie outside the grid: the rectangle is clipped */
+    uint32_t width, height; /* cells */
+} lom_clearance_window;
+typedef struct {
+    uint64_t cells_lethal, cells_inscribed, cells_costed, cells_unknown, cells_invalid, cells_cleared;
+} lom_clearance_summary;
+#define LOM_CLEAR_FAR 65535
+enum {
+    LOM_CLEAR_FREE_CLEARS_ELEVATION = 1, /* a lethal elevation cell that the occupancy grid calls free reads as 0 */
+    LOM_CLEAR_UNKNOWN_IS_OBSTACLE = 2    /* a cell unknown to both planes is an obstacle */
+};
+enum {
+    LOM_CLEAR_OPT_TEST_TILE_ROWS = 1, /* T in 1 .. 32: rows of a tile of the distance kernel; <= 0: the default, 32 */
+    LOM_CLEAR_OPT_TEST_NO_PRUNE = 2   /* 1: the column pass looks at all 2R + 1 rows; 0 or < 0, the default: it stops once
+                                         dy^2 reaches the best so far.  Test switches: the bytes are the same. */
+};
+int lom_clearance_create(const lom_occupancy_geometry *geometry, int device, lom_clearance **out);
+void lom_clearance_destroy(lom_clearance *c);
+const char *lom_clearance_last_error(const lom_clearance *c); /* c == NULL: why the last create on this thread failed */
+int lom_clearance_clear(lom_clearance *c);                    /* d2 = far, cost = -1 */
+int lom_clearance_get_geometry(const lom_clearance *c, lom_occupancy_geometry *out);
+void *lom_clearance_stream(lom_clearance *c); /* hipStream_t */
+int lom_clearance_device(const lom_clearance *c);
+int lom_clearance_wait_event(lom_clearance *c, void *hip_event);
+int lom_clearance_set_option(lom_clearance *c, int option, int64_t value);
+int lom_clearance_update(lom_clearance *c, const int8_t *occ_or_null, const int8_t *elev_or_null,
+                         const lom_clearance_params *params, const lom_clearance_window *window_or_null,
+                         lom_clearance_summary *summary_or_null);
+int lom_clearance_update_device(lom_clearance *c, const int8_t *d_occ_or_null, const int8_t *d_elev_or_null,
+                                void *hip_event_or_null, const lom_clearance_params *params,
+                                const lom_clearance_window *window_or_null, lom_clearance_summary *summary_or_null);
+int lom_clearance_update_from_grids(lom_clearance *c, lom_occupancy *occupancy_or_null, const lom_occupancy_rule *rule,
+                                    lom_elevation *elevation_or_null, const lom_elevation_layer_params *layer_params,
+                                    const lom_elevation_cost_params *cost_params, const lom_clearance_params *params,
+                                    const lom_clearance_window *window_or_null, lom_clearance_summary *summary_or_null);
+/* the cost over the whole grid: at most `cap` cells go to `out` (may be NULL with cap 0); the summary counts all cells of
+ * the plane as it stands (cells_invalid and cells_cleared are 0: they belong to an update) */
+int lom_clearance_cost(lom_clearance *c, int8_t *out, size_t cap, lom_clearance_summary *summary_or_null);
+/* the same plane, left in HBM: width * height cells, valid until the next update or clear on the handle */
+int lom_clearance_cost_device(lom_clearance *c, const int8_t **d_out);
+/* d2 per cell (step 2) and metres per cell (step 5), row-major; at most `cap` entries */
+int lom_clearance_distance_sq(lom_clearance *c, uint16_t *out, size_t cap);
+int lom_clearance_distance(lom_clearance *c, float *out, size_t cap);
+/* step 3 for these parameters on a grid of this resolution: returns R^2 + 1 and writes at most `cap` bytes (out may be
+ * NULL with cap 0); LOM_ERR_ARG for a bad geometry or bad parameters.  Needs no handle and no device. */
+int64_t lom_clearance_cost_table(const lom_clearance_params *params, const lom_occupancy_geometry *geometry, uint8_t *out,
+                                 size_t cap);
+/* n points (x, y in the grid's frame, f32 pairs in host memory): the cell by the floor rule, its distance in metres (step
+ * 5) and its cost; NaN and -1 for a point outside the grid or not a number.  Either output may be NULL. */
+int lom_clearance_query(lom_clearance *c, const float *xy, size_t n, float *dist_out, int8_t *cost_out);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;

@@ -1102,6 +1102,105 @@ private:
     lom_elevation *h_ = nullptr;
 };
 
+// ---- ClearanceGrid (not in the reference) ---------------------------------------------
+// Obstacle distance and inflated cost on the device: update() merges an occupancy and an elevation plane (int8,
+// row-major with y as the row, either may be NULL), computes the exact truncated squared distance to the nearest obstacle
+// (u16, cells) and the int8 cost of a costmap (-1 unknown, 0 .. 98, 99 inscribed, 100 lethal).  Definitions:
+// lidar_odometry_amd.h ("clearance grid").
+using ClearanceParams = lom_clearance_params;    // {inflation_radius, inscribed_radius, decay, flags}
+using ClearanceWindow = lom_clearance_window;    // {x0, y0, width, height}
+using ClearanceSummary = lom_clearance_summary;
+
+inline ClearanceParams clearanceParams(float inflation_radius, float inscribed_radius, float decay, uint32_t flags = 0)
+{
+    return ClearanceParams{inflation_radius, inscribed_radius, decay, flags};
+}
+
+class ClearanceGrid {
+public:
+    struct Query {  // NaN and -1 for a point outside the grid
+        std::vector<float> distance;
+        std::vector<int8_t> cost;
+    };
+
+    explicit ClearanceGrid(const lom_occupancy_geometry &geometry, int device = 0)
+    {
+        const int rc = lom_clearance_create(&geometry, device, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_clearance_last_error(nullptr));
+    }
+    ~ClearanceGrid() { lom_clearance_destroy(h_); }
+    ClearanceGrid(const ClearanceGrid &) = delete;
+    ClearanceGrid &operator=(const ClearanceGrid &) = delete;
+    lom_clearance *handle() const { return h_; }
+    lom_occupancy_geometry geometry() const
+    {
+        lom_occupancy_geometry g;
+        check(lom_clearance_get_geometry(h_, &g));
+        return g;
+    }
+    size_t size() const
+    {
+        const lom_occupancy_geometry g = geometry();
+        return (size_t)g.width * g.height;
+    }
+    void clear() { check(lom_clearance_clear(h_)); }
+    void setOption(int option, int64_t value) { check(lom_clearance_set_option(h_, option, value)); }
+    // host planes of size() cells each; either may be NULL
+    lom_clearance_summary update(const int8_t *occ_or_null, const int8_t *elev_or_null, const lom_clearance_params &params,
+                                 const lom_clearance_window *window_or_null = nullptr)
+    {
+        lom_clearance_summary s;
+        check(lom_clearance_update(h_, occ_or_null, elev_or_null, &params, window_or_null, &s));
+        return s;
+    }
+    // the planes of the two grids, left in HBM; either may be NULL
+    lom_clearance_summary updateFromGrids(OccupancyGrid *occupancy_or_null, const lom_occupancy_rule &rule,
+                                          ElevationGrid *elevation_or_null, const lom_elevation_layer_params &lp,
+                                          const lom_elevation_cost_params &cp, const lom_clearance_params &params,
+                                          const lom_clearance_window *window_or_null = nullptr)
+    {
+        lom_clearance_summary s;
+        check(lom_clearance_update_from_grids(h_, occupancy_or_null ? occupancy_or_null->handle() : nullptr, &rule,
+                                              elevation_or_null ? elevation_or_null->handle() : nullptr, &lp, &cp, &params,
+                                              window_or_null, &s));
+        return s;
+    }
+    std::vector<int8_t> cost(lom_clearance_summary *summary_or_null = nullptr)
+    {
+        std::vector<int8_t> out(size());
+        check(lom_clearance_cost(h_, out.data(), out.size(), summary_or_null));
+        return out;
+    }
+    std::vector<uint16_t> distanceSq()
+    {
+        std::vector<uint16_t> out(size());
+        check(lom_clearance_distance_sq(h_, out.data(), out.size()));
+        return out;
+    }
+    std::vector<float> distance()
+    {
+        std::vector<float> out(size());
+        check(lom_clearance_distance(h_, out.data(), out.size()));
+        return out;
+    }
+    // xy: n pairs in the grid's frame
+    Query query(const float *xy, size_t n)
+    {
+        Query q;
+        q.distance.assign(n, 0.f), q.cost.assign(n, 0);
+        check(lom_clearance_query(h_, xy, n, q.distance.data(), q.cost.data()));
+        return q;
+    }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_clearance_last_error(h_));
+        return rc;
+    }
+    lom_clearance *h_ = nullptr;
+};
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)

@@ -811,6 +811,12 @@ def elevationCostParams(params):
     return _struct_from(capi.ElevationCostParams, params, "elevation cost parameters")
 
 
+def clearanceParams(params):
+    """capi.ClearanceParams from one, from a dict with its four fields, or from a 4-tuple in the struct's order
+    (inflation_radius, inscribed_radius, decay, flags).  There are no defaults."""
+    return _struct_from(capi.ClearanceParams, params, "clearance parameters")
+
+
 def classifyNeighbourhood(points, params, details=False, frontend=None):
     """The neighbourhood classifier alone (lom_classify_neighbourhood) on POINT_XYZIRT records whose `ring` is not read:
     (planar xyz, normals) in input order, and with details=True a third array of capi.NEIGHBOURHOOD_DETAIL records, one
@@ -1242,6 +1248,110 @@ class ElevationGrid(_PosedScanGrid):
         sm = capi.ElevationSummary()
         self._check(capi.lib().lom_elevation_cost(self._h, C.byref(lp), C.byref(cp), out.ctypes.data, out.size, C.byref(sm)))
         return out, sm.asdict()
+
+
+class ClearanceGrid(_Handle):
+    """Obstacle distance and inflated cost on the device (lom_clearance_*, include/lidar_odometry_amd.h "clearance grid"):
+    update() merges an occupancy and an elevation plane (int8 arrays of shape (height, width), either may be None),
+    computes the exact truncated squared distance to the nearest obstacle and the int8 cost of a costmap (-1 unknown,
+    0 .. 98, 99 inscribed, 100 lethal).  A window is (x0, y0, width, height) in cells.  All arrays have the shape
+    (height, width)."""
+
+    _family = "clearance"
+
+    def __init__(self, resolution, origin_xy, width, height, device=0):
+        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
+        self._create(C.byref(geo), int(device))
+        self.width, self.height = int(width), int(height)
+
+    def geometry(self):
+        geo = capi.OccupancyGeometry()
+        self._check(self._call("get_geometry", self._h, C.byref(geo)))
+        return geo.asdict()
+
+    def setOption(self, option, value):
+        self._check(self._call("set_option", self._h, int(option), int(value)))
+
+    def waitEvent(self, hip_event):
+        self._check(self._call("wait_event", self._h, hip_event))
+
+    def clear(self):
+        self._check(self._call("clear", self._h))
+
+    @staticmethod
+    def _window(window):
+        return None if window is None else C.byref(capi.ClearanceWindow(*[int(v) for v in window]))
+
+    def _plane(self, a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.int8)
+        if a.shape != (self.height, self.width):
+            raise ValueError("expected an int8 array of shape (height, width)")
+        return a
+
+    def update(self, occ, elev, params, window=None, device=False, hip_event=None):
+        """lom_clearance_update: host planes -- or, with device=True, lom_clearance_update_device: occ and elev are device
+        pointers to planes in HBM, complete when `hip_event` is.  Returns capi.ClearanceSummary as a dict."""
+        p, sm = clearanceParams(params), capi.ClearanceSummary()
+        if device:
+            rc = self._call("update_device", self._h, occ, elev, hip_event, C.byref(p), self._window(window), C.byref(sm))
+        else:
+            occ, elev = self._plane(occ), self._plane(elev)
+            rc = self._call("update", self._h, None if occ is None else occ.ctypes.data, None if elev is None else elev.ctypes.data,
+                            C.byref(p), self._window(window), C.byref(sm))
+        self._check(rc)
+        return sm.asdict()
+
+    def updateFromGrids(self, occupancy, rule, elevation, layer_params, cost_params, params, window=None):
+        """lom_clearance_update_from_grids: the planes of an OccupancyGrid (by `rule`) and an ElevationGrid (by
+        `layer_params`, `cost_params`) of this geometry, left in HBM; either grid may be None"""
+        p, sm = clearanceParams(params), capi.ClearanceSummary()
+        r = None if occupancy is None else C.byref(occupancyRule(rule))
+        lp = None if elevation is None else C.byref(elevationLayerParams(layer_params))
+        cp = None if elevation is None else C.byref(elevationCostParams(cost_params))
+        self._check(self._call("update_from_grids", self._h, None if occupancy is None else occupancy.handle, r,
+                               None if elevation is None else elevation.handle, lp, cp, C.byref(p), self._window(window),
+                               C.byref(sm)))
+        return sm.asdict()
+
+    def cost(self):
+        """(int8 array, summary dict of the whole plane)"""
+        out, sm = np.empty((self.height, self.width), np.int8), capi.ClearanceSummary()
+        self._check(self._call("cost", self._h, out.ctypes.data, out.size, C.byref(sm)))
+        return out, sm.asdict()
+
+    def distanceSq(self):
+        """uint16 array: the squared distance to the nearest obstacle in cells, capi.CLEAR_FAR beyond the radius"""
+        out = np.empty((self.height, self.width), np.uint16)
+        self._check(self._call("distance_sq", self._h, out.ctypes.data, out.size))
+        return out
+
+    def distance(self):
+        """float32 array: that distance in metres, +inf beyond the radius"""
+        out = np.empty((self.height, self.width), np.float32)
+        self._check(self._call("distance", self._h, out.ctypes.data, out.size))
+        return out
+
+    def query(self, xy):
+        """(distance in metres float32, cost int8) of the cells of the points xy (n, 2), in the grid's frame; NaN and -1
+        outside the grid"""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        dist, cost = np.empty(len(xy), np.float32), np.empty(len(xy), np.int8)
+        self._check(self._call("query", self._h, xy.ctypes.data, len(xy), dist.ctypes.data, cost.ctypes.data))
+        return dist, cost
+
+
+def clearanceCostTable(params, resolution):
+    """lom_clearance_cost_table: the uint8 cost per squared distance, R^2 + 1 entries; needs no device"""
+    p = clearanceParams(params)
+    geo = capi.OccupancyGeometry(float(resolution), 0.0, 0.0, 1, 1)
+    n = capi.lib().lom_clearance_cost_table(C.byref(p), C.byref(geo), None, 0)
+    if n < 0:
+        raise LomError(int(n), "clearance cost table: bad parameters")
+    out = np.empty(n, np.uint8)
+    capi.lib().lom_clearance_cost_table(C.byref(p), C.byref(geo), out.ctypes.data, n)
+    return out
 
 
 class PoseGraph(_Handle):

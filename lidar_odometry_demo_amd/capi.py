@@ -319,6 +319,31 @@ ELEV_COST_UNKNOWN, ELEV_COST_LETHAL = -1, 100
 ELEV_OPT_TEST_WAVE_MERGE = 1
 
 
+class ClearanceParams(C.Structure):
+    """lom_clearance_params"""
+    _fields_ = [("inflation_radius", C.c_float), ("inscribed_radius", C.c_float), ("decay", C.c_float), ("flags", C.c_uint32)]
+
+
+class ClearanceWindow(C.Structure):
+    """lom_clearance_window"""
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class ClearanceSummary(C.Structure):
+    """lom_clearance_summary"""
+    _fields_ = [("cells_lethal", C.c_uint64), ("cells_inscribed", C.c_uint64), ("cells_costed", C.c_uint64),
+                ("cells_unknown", C.c_uint64), ("cells_invalid", C.c_uint64), ("cells_cleared", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(ClearanceParams) == 16 and C.sizeof(ClearanceWindow) == 16 and C.sizeof(ClearanceSummary) == 48
+CLEAR_FAR = 65535
+CLEAR_FREE_CLEARS_ELEVATION, CLEAR_UNKNOWN_IS_OBSTACLE = 1, 2
+CLEAR_OPT_TEST_TILE_ROWS, CLEAR_OPT_TEST_NO_PRUNE = 1, 2
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -404,6 +429,11 @@ EXPORTED = [
     "lom_elevation_set_option", "lom_elevation_integrate", "lom_elevation_integrate_cloud",
     "lom_elevation_integrate_cloud_device", "lom_elevation_cells", "lom_elevation_layers", "lom_elevation_cost",
     "lom_elevation_cost_device",
+    "lom_clearance_create", "lom_clearance_destroy", "lom_clearance_last_error", "lom_clearance_clear",
+    "lom_clearance_get_geometry", "lom_clearance_stream", "lom_clearance_device", "lom_clearance_wait_event",
+    "lom_clearance_set_option", "lom_clearance_update", "lom_clearance_update_device", "lom_clearance_update_from_grids",
+    "lom_clearance_cost", "lom_clearance_cost_device", "lom_clearance_distance_sq", "lom_clearance_distance",
+    "lom_clearance_cost_table", "lom_clearance_query",
 ]
 # ... and the one it declares through a function type (the "scan archive and map assembly" section)
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
@@ -798,6 +828,31 @@ def lib():
     L.lom_elevation_cost.argtypes = [vp, C.POINTER(ElevationLayerParams), C.POINTER(ElevationCostParams), vp, C.c_size_t,
                                      C.POINTER(ElevationSummary)]
     L.lom_elevation_cost_device.argtypes = [vp, C.POINTER(ElevationLayerParams), C.POINTER(ElevationCostParams), C.POINTER(vp)]
+    L.lom_clearance_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
+    L.lom_clearance_destroy.argtypes = [vp]
+    L.lom_clearance_destroy.restype = None
+    L.lom_clearance_last_error.argtypes = [vp]
+    L.lom_clearance_last_error.restype = C.c_char_p
+    L.lom_clearance_clear.argtypes = [vp]
+    L.lom_clearance_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
+    L.lom_clearance_stream.argtypes = [vp]
+    L.lom_clearance_stream.restype = vp
+    L.lom_clearance_device.argtypes = [vp]
+    L.lom_clearance_wait_event.argtypes = [vp, vp]
+    L.lom_clearance_set_option.argtypes = [vp, C.c_int, C.c_int64]
+    L.lom_clearance_update.argtypes = [vp, vp, vp, C.POINTER(ClearanceParams), C.POINTER(ClearanceWindow), C.POINTER(ClearanceSummary)]
+    L.lom_clearance_update_device.argtypes = [vp, vp, vp, vp, C.POINTER(ClearanceParams), C.POINTER(ClearanceWindow),
+                                              C.POINTER(ClearanceSummary)]
+    L.lom_clearance_update_from_grids.argtypes = [vp, vp, C.POINTER(OccupancyRule), vp, C.POINTER(ElevationLayerParams),
+                                                  C.POINTER(ElevationCostParams), C.POINTER(ClearanceParams),
+                                                  C.POINTER(ClearanceWindow), C.POINTER(ClearanceSummary)]
+    L.lom_clearance_cost.argtypes = [vp, vp, C.c_size_t, C.POINTER(ClearanceSummary)]
+    L.lom_clearance_cost_device.argtypes = [vp, C.POINTER(vp)]
+    L.lom_clearance_distance_sq.argtypes = [vp, vp, C.c_size_t]
+    L.lom_clearance_distance.argtypes = [vp, vp, C.c_size_t]
+    L.lom_clearance_cost_table.argtypes = [C.POINTER(ClearanceParams), C.POINTER(OccupancyGeometry), vp, C.c_size_t]
+    L.lom_clearance_cost_table.restype = C.c_int64
+    L.lom_clearance_query.argtypes = [vp, vp, C.c_size_t, vp, vp]
     _lib = L
     return L
 
