@@ -1675,6 +1675,119 @@ int64_t lom_clearance_cost_table(const lom_clearance_params *params, const lom_o
  * 5) and its cost; NaN and -1 for a point outside the grid or not a number.  Either output may be NULL. */
 int lom_clearance_query(lom_clearance *c, const float *xy, size_t n, float *dist_out, int8_t *cost_out);
 
+/* ---- navigation field: cost-to-go from goals over the clearance cost (not in the reference) ----------------------------
+ * The clearance grid leaves an inflated int8 cost plane in HBM.  A planner reads, per cell, the least total cost to reach
+ * a goal -- the navigation function of nav2-style stacks -- and a route from any start follows its descent.  This handle
+ * family computes that field on the device, entirely on integers, traces paths down it and answers point queries.
+ * Nothing is launched unless a caller creates a field.  The definition, operation by operation (tests/navfield_ref.py
+ * restates it with a heap Dijkstra on Python integers; the field is the unique fixed point of a relaxation, so every
+ * comparison is exact):
+ *
+ * Grid.  lom_occupancy_geometry, reused, with the clearance grid's rules: cell (ix, iy) covers [origin + i r, origin +
+ * (i + 1) r) per axis, storage is row-major with y as the row, the index rule is the floor rule.  r > 0 and finite, a
+ * finite origin, 1 <= width, height <= 8192; anything else is LOM_ERR_ARG.  A cell costs 5 bytes of HBM (P u32, the cost
+ * byte of the last solve i8).
+ *
+ * Input of a solve.  One full-grid int8 cost plane in the value range lom_clearance_cost writes: -1, 0 .. 99, 100.
+ * lom_navfield_params: neutral >= 1; 0 <= max_passable <= 98; neutral + 98 * factor <= 2^24 - 1; unknown_cost in
+ * 1 .. 2^24 - 1 when LOM_NAV_UNKNOWN_PASSABLE is set (it is not read otherwise); no unknown bit in flags; anything else is
+ * LOM_ERR_ARG.
+ *  1. Cell cost.  A table of 256 u32, built on the host and indexed by the cost byte read as unsigned: a value v in
+ *     0 .. max_passable gives neutral + factor * v; -1 gives unknown_cost under LOM_NAV_UNKNOWN_PASSABLE, else 0; every
+ *     other byte gives 0 -- max_passable + 1 .. 100, and the bytes outside -1 .. 100, which also count in cells_invalid.
+ *     0 means impassable.  Cells outside the grid are impassable.  lom_navfield_cell_costs gives the table.
+ *  2. Steps.  8-connected.  An axial step has length 5, a diagonal step 7 (7 / 5 is within 1.01 % of sqrt 2).  A step
+ *     from a to b is allowed iff both cells are passable and, for a diagonal step, so are the two cells that share an edge
+ *     with both: no corner is cut.  Its weight is len(a, b) * c[a]: a step pays for the cell it leaves.
+ *  3. Goals.  G cells, as int32 (ix, iy) pairs (LOM_NAV_CELLS) or as f32 (x, y) in metres by the floor rule
+ *     (LOM_NAV_METRES).  A goal outside the grid, not a number or on an impassable cell is skipped and counts in
+ *     goals_rejected; the others, duplicates once, count in goals_used.  G = 0 or goals_used == 0 is LOM_OK with every
+ *     cell unreached.
+ *  4. Field.  P[goal] = 0; else P[a] = the least total weight over all sequences of allowed steps from a to any goal;
+ *     u32.  LOM_NAV_UNREACHED = 0xFFFFFFFF, LOM_NAV_MAX = 0xFFFFFFFE.  A candidate above LOM_NAV_MAX is dropped: weights
+ *     are positive, so exactly the cells whose true value exceeds LOM_NAV_MAX read LOM_NAV_UNREACHED, and so does every
+ *     cell behind them.  range_exceeded = 1 iff, at the fixed point, some reached cell b and some allowed step a -> b
+ *     have P[b] + len * c[a] > LOM_NAV_MAX (computed in the summary pass, so it is deterministic).  Impassable cells read
+ *     LOM_NAV_UNREACHED.
+ *  5. Summary, counted over the grid: cells_blocked (impassable), cells_reached, cells_unreached (passable, not reached)
+ *     -- the three add up to the grid's cells -- cells_invalid, goals_used, goals_rejected, range_exceeded and
+ *     max_potential (0 if nothing is reached).
+ *  6. Paths.  K starts, as cells or metres.  A start outside the grid or on an unreached cell is not walked: length 0.
+ *     Otherwise, from cell a with P[a] > 0, the walk steps to the first b in the fixed order E, N, W, S, NE, NW, SW, SE
+ *     (+x is E, +y is N) for which the step is allowed and P[b] + len(a, b) * c[a] == P[a] -- one exists at the fixed
+ *     point -- and stops at P == 0.  Output: u16 (ix, iy) pairs in a [K, cap] buffer; the length counts start and goal and
+ *     is the full length even when it exceeds cap, only the first cap cells are written; the rest of a row is 0.  P falls
+ *     strictly along a path, so a walk is bounded by the number of cells.
+ *  7. Query.  n points in metres: the cell's P; LOM_NAV_UNREACHED for a point outside the grid or not a number.
+ * After create or lom_navfield_clear every cell is unreached, every cell impassable.
+ *
+ * The result is a pure function of plane, parameters and goals: it does not depend on the tile shape, on the number of
+ * launches, on the order in which workgroups run or on the test switches below.
+ *
+ * lom_navfield_solve takes a host plane of width * height bytes; _solve_device a plane in HBM that is complete when
+ * hip_event_or_null is (NULL: now); _solve_from_clearance takes lom_clearance_cost_device's plane and orders the two
+ * streams by events in both directions -- a clearance grid whose resolution, origin, width or height differ bit for bit,
+ * or that lives on another device, is LOM_ERR_ARG before any launch.  The field keeps a copy of the plane, so paths and
+ * queries do not depend on what becomes of the caller's.  Every argument is validated before any device work; a refused
+ * call changes nothing and zeroes the summary.  Every call returns with its work done.  Calls on one field are the
+ * caller's to serialise.  The error text is the field's (lom_navfield_last_error). */
+typedef struct lom_navfield lom_navfield;
+typedef struct {
+    uint32_t neutral;      /* the cost of a cell whose byte is 0, >= 1 */
+    uint32_t factor;       /* ... and what a unit of the byte adds */
+    uint32_t unknown_cost; /* the cost of a -1 cell under LOM_NAV_UNKNOWN_PASSABLE */
+    int8_t max_passable;   /* the largest passable byte, 0 .. 98 */
+    uint32_t flags;        /* LOM_NAV_* */
+} lom_navfield_params;
+typedef struct {
+    uint64_t cells_blocked, cells_reached, cells_unreached, cells_invalid, goals_used, goals_rejected, range_exceeded,
+        max_potential;
+} lom_navfield_summary;
+typedef struct {
+    uint64_t launches, waits; /* of k_nav_relax in the last solve, and the host's waits for them */
+    uint64_t tiles;           /* workgroups per launch */
+} lom_navfield_solve_stats;
+#define LOM_NAV_UNREACHED 0xFFFFFFFFu
+#define LOM_NAV_MAX 0xFFFFFFFEu
+enum { LOM_NAV_UNKNOWN_PASSABLE = 1 }; /* a -1 cell is passable at unknown_cost */
+enum { LOM_NAV_CELLS = 0, LOM_NAV_METRES = 1 }; /* what goals and starts are: int32 (ix, iy) pairs, f32 (x, y) pairs */
+enum {
+    LOM_NAV_OPT_TEST_INNER_CAP = 1, /* sweeps of a tile per launch, 1 .. 2^20; 1: a launch is one sweep per active tile; <= 0: the default */
+    LOM_NAV_OPT_TEST_BATCH = 2,     /* launches per wait, 1 .. 256; <= 0: the default */
+    LOM_NAV_OPT_TEST_ALL_TILES = 3  /* 1: every tile is active in every launch; 0 or < 0, the default: only marked tiles.
+                                       Test switches: the bytes are the same. */
+};
+int lom_navfield_create(const lom_occupancy_geometry *geometry, int device, lom_navfield **out);
+void lom_navfield_destroy(lom_navfield *f);
+const char *lom_navfield_last_error(const lom_navfield *f); /* f == NULL: why the last create on this thread failed */
+int lom_navfield_clear(lom_navfield *f);                    /* every cell unreached and impassable */
+int lom_navfield_get_geometry(const lom_navfield *f, lom_occupancy_geometry *out);
+void *lom_navfield_stream(lom_navfield *f); /* hipStream_t */
+int lom_navfield_device(const lom_navfield *f);
+int lom_navfield_wait_event(lom_navfield *f, void *hip_event);
+int lom_navfield_set_option(lom_navfield *f, int option, int64_t value);
+/* goals: n_goals pairs of goal_kind in host memory (may be NULL with n_goals 0), at most 2^24 */
+int lom_navfield_solve(lom_navfield *f, const int8_t *plane, const lom_navfield_params *params, int goal_kind, const void *goals,
+                       size_t n_goals, lom_navfield_summary *summary_or_null);
+int lom_navfield_solve_device(lom_navfield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_navfield_params *params,
+                              int goal_kind, const void *goals, size_t n_goals, lom_navfield_summary *summary_or_null);
+int lom_navfield_solve_from_clearance(lom_navfield *f, lom_clearance *clearance, const lom_navfield_params *params, int goal_kind,
+                                      const void *goals, size_t n_goals, lom_navfield_summary *summary_or_null);
+/* P over the whole grid, row-major: at most `cap` cells go to `out` (may be NULL with cap 0) */
+int lom_navfield_potential(lom_navfield *f, uint32_t *out, size_t cap);
+/* the same, left in HBM: width * height cells, valid until the next solve or clear on the handle */
+int lom_navfield_potential_device(lom_navfield *f, const uint32_t **d_out);
+/* step 6: n_starts pairs of start_kind in host memory (at most 2^24, n_starts * cap at most 2^28); cells_out: [n_starts,
+ * cap] u16 pairs (may be NULL with cap 0), lengths_out: n_starts u32 (may be NULL) */
+int lom_navfield_paths(lom_navfield *f, int start_kind, const void *starts, size_t n_starts, uint16_t *cells_out, size_t cap,
+                       uint32_t *lengths_out);
+/* step 7: n points (x, y in the grid's frame, f32 pairs in host memory, at most 2^30) */
+int lom_navfield_query(lom_navfield *f, const float *xy, size_t n, uint32_t *out);
+/* step 1 for these parameters; LOM_ERR_ARG for bad parameters.  Needs no handle and no device. */
+int lom_navfield_cell_costs(const lom_navfield_params *params, uint32_t *out256);
+/* the launches and waits of the last solve (zeros before the first) */
+int lom_navfield_stats(const lom_navfield *f, lom_navfield_solve_stats *out);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;

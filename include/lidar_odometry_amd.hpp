@@ -1201,6 +1201,115 @@ private:
     lom_clearance *h_ = nullptr;
 };
 
+// ---- NavField (not in the reference) ---------------------------------------------------
+// The navigation field on the device: solve() takes an int8 cost plane (row-major with y as the row, the value range
+// ClearanceGrid::cost() writes) and goals, and leaves per cell the least total cost to reach a goal (u32,
+// LOM_NAV_UNREACHED where there is no route); paths() walks down it, query() reads it at points in metres.  Definitions:
+// lidar_odometry_amd.h ("navigation field").
+using NavFieldParams = lom_navfield_params;  // {neutral, factor, unknown_cost, max_passable, flags}
+using NavFieldSummary = lom_navfield_summary;
+
+inline NavFieldParams navfieldParams(uint32_t neutral, uint32_t factor, uint32_t unknown_cost, int8_t max_passable, uint32_t flags = 0)
+{
+    return NavFieldParams{neutral, factor, unknown_cost, max_passable, flags};
+}
+
+class NavField {
+public:
+    struct Paths {  // cells: [K, cap] (ix, iy) pairs; lengths: the full length per start, 0 where none was walked
+        std::vector<uint16_t> cells;
+        std::vector<uint32_t> lengths;
+    };
+
+    explicit NavField(const lom_occupancy_geometry &geometry, int device = 0)
+    {
+        const int rc = lom_navfield_create(&geometry, device, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_navfield_last_error(nullptr));
+    }
+    ~NavField() { lom_navfield_destroy(h_); }
+    NavField(const NavField &) = delete;
+    NavField &operator=(const NavField &) = delete;
+    lom_navfield *handle() const { return h_; }
+    lom_occupancy_geometry geometry() const
+    {
+        lom_occupancy_geometry g;
+        check(lom_navfield_get_geometry(h_, &g));
+        return g;
+    }
+    size_t size() const
+    {
+        const lom_occupancy_geometry g = geometry();
+        return (size_t)g.width * g.height;
+    }
+    void clear() { check(lom_navfield_clear(h_)); }
+    void setOption(int option, int64_t value) { check(lom_navfield_set_option(h_, option, value)); }
+    // a host plane of size() cells; goals: n pairs of int32 cells
+    lom_navfield_summary solve(const int8_t *plane, const lom_navfield_params &params, const int32_t *goal_cells, size_t n)
+    {
+        lom_navfield_summary s;
+        check(lom_navfield_solve(h_, plane, &params, LOM_NAV_CELLS, goal_cells, n, &s));
+        return s;
+    }
+    // ... goals: n pairs of f32 metres
+    lom_navfield_summary solveMetres(const int8_t *plane, const lom_navfield_params &params, const float *goal_xy, size_t n)
+    {
+        lom_navfield_summary s;
+        check(lom_navfield_solve(h_, plane, &params, LOM_NAV_METRES, goal_xy, n, &s));
+        return s;
+    }
+    // the plane a ClearanceGrid of this geometry left in HBM
+    lom_navfield_summary solveFromClearance(ClearanceGrid &clearance, const lom_navfield_params &params, int goal_kind,
+                                            const void *goals, size_t n)
+    {
+        lom_navfield_summary s;
+        check(lom_navfield_solve_from_clearance(h_, clearance.handle(), &params, goal_kind, goals, n, &s));
+        return s;
+    }
+    std::vector<uint32_t> potential()
+    {
+        std::vector<uint32_t> out(size());
+        check(lom_navfield_potential(h_, out.data(), out.size()));
+        return out;
+    }
+    // starts: n pairs of start_kind (LOM_NAV_CELLS: int32, LOM_NAV_METRES: f32)
+    Paths paths(int start_kind, const void *starts, size_t n, size_t cap)
+    {
+        Paths p;
+        p.cells.assign(n * cap * 2, 0), p.lengths.assign(n, 0);
+        check(lom_navfield_paths(h_, start_kind, starts, n, p.cells.data(), cap, p.lengths.data()));
+        return p;
+    }
+    // xy: n pairs in the grid's frame
+    std::vector<uint32_t> query(const float *xy, size_t n)
+    {
+        std::vector<uint32_t> out(n);
+        check(lom_navfield_query(h_, xy, n, out.data()));
+        return out;
+    }
+    lom_navfield_solve_stats stats() const
+    {
+        lom_navfield_solve_stats s;
+        check(lom_navfield_stats(h_, &s));
+        return s;
+    }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_navfield_last_error(h_));
+        return rc;
+    }
+    lom_navfield *h_ = nullptr;
+};
+
+inline std::vector<uint32_t> navfieldCellCosts(const lom_navfield_params &params)
+{
+    std::vector<uint32_t> out(256);
+    const int rc = lom_navfield_cell_costs(&params, out.data());
+    if (rc != LOM_OK) throw Error(rc, "navigation field cell costs: bad parameters");
+    return out;
+}
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)

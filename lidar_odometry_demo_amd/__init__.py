@@ -817,6 +817,12 @@ def clearanceParams(params):
     return _struct_from(capi.ClearanceParams, params, "clearance parameters")
 
 
+def navfieldParams(params):
+    """capi.NavFieldParams from one, from a dict with its five fields, or from a 5-tuple in the struct's order (neutral,
+    factor, unknown_cost, max_passable, flags).  There are no defaults."""
+    return _struct_from(capi.NavFieldParams, params, "navigation field parameters")
+
+
 def classifyNeighbourhood(points, params, details=False, frontend=None):
     """The neighbourhood classifier alone (lom_classify_neighbourhood) on POINT_XYZIRT records whose `ring` is not read:
     (planar xyz, normals) in input order, and with details=True a third array of capi.NEIGHBOURHOOD_DETAIL records, one
@@ -1351,6 +1357,102 @@ def clearanceCostTable(params, resolution):
         raise LomError(int(n), "clearance cost table: bad parameters")
     out = np.empty(n, np.uint8)
     capi.lib().lom_clearance_cost_table(C.byref(p), C.byref(geo), out.ctypes.data, n)
+    return out
+
+
+class NavField(_Handle):
+    """The navigation field on the device (lom_navfield_*, include/lidar_odometry_amd.h "navigation field"): solve() takes
+    an int8 cost plane of shape (height, width) in the value range ClearanceGrid.cost() writes, and goals, and leaves per
+    cell the least total cost to reach a goal (uint32, capi.NAV_UNREACHED where there is no route); paths() walks down it,
+    query() reads it at points in metres.  Goals and starts are (n, 2) arrays: integers are cells (ix, iy), with
+    metres=True floats are (x, y) in the grid's frame."""
+
+    _family = "navfield"
+
+    def __init__(self, resolution, origin_xy, width, height, device=0):
+        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
+        self._create(C.byref(geo), int(device))
+        self.width, self.height = int(width), int(height)
+
+    def geometry(self):
+        geo = capi.OccupancyGeometry()
+        self._check(self._call("get_geometry", self._h, C.byref(geo)))
+        return geo.asdict()
+
+    def setOption(self, option, value):
+        self._check(self._call("set_option", self._h, int(option), int(value)))
+
+    def waitEvent(self, hip_event):
+        self._check(self._call("wait_event", self._h, hip_event))
+
+    def clear(self):
+        self._check(self._call("clear", self._h))
+
+    @staticmethod
+    def _points(points, metres):
+        """(kind, contiguous (n, 2) array)"""
+        if metres:
+            return capi.NAV_METRES, np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        return capi.NAV_CELLS, np.ascontiguousarray(points, np.int32).reshape(-1, 2)
+
+    def solve(self, plane, params, goals, metres=False, device=False, hip_event=None):
+        """lom_navfield_solve: a host plane -- or, with device=True, lom_navfield_solve_device: `plane` is a device pointer to
+        a plane in HBM, complete when `hip_event` is.  Returns capi.NavFieldSummary as a dict."""
+        p, sm = navfieldParams(params), capi.NavFieldSummary()
+        kind, g = self._points(goals, metres)
+        if device:
+            rc = self._call("solve_device", self._h, plane, hip_event, C.byref(p), kind, g.ctypes.data, len(g), C.byref(sm))
+        else:
+            plane = np.ascontiguousarray(plane, np.int8)
+            if plane.shape != (self.height, self.width):
+                raise ValueError("expected an int8 array of shape (height, width)")
+            rc = self._call("solve", self._h, plane.ctypes.data, C.byref(p), kind, g.ctypes.data, len(g), C.byref(sm))
+        self._check(rc)
+        return sm.asdict()
+
+    def solveFromClearance(self, clearance, params, goals, metres=False):
+        """lom_navfield_solve_from_clearance: the cost plane a ClearanceGrid of this geometry left in HBM"""
+        p, sm = navfieldParams(params), capi.NavFieldSummary()
+        kind, g = self._points(goals, metres)
+        self._check(self._call("solve_from_clearance", self._h, clearance.handle, C.byref(p), kind, g.ctypes.data, len(g), C.byref(sm)))
+        return sm.asdict()
+
+    def potential(self):
+        """uint32 array of shape (height, width): P per cell, capi.NAV_UNREACHED where no goal is reached"""
+        out = np.empty((self.height, self.width), np.uint32)
+        self._check(self._call("potential", self._h, out.ctypes.data, out.size))
+        return out
+
+    def paths(self, starts, cap, metres=False):
+        """(cells uint16 (K, cap, 2), lengths uint32 (K,)): the walk from each start down the field, (ix, iy) per cell; a
+        length counts start and goal, is 0 for a start outside the grid or unreached, and may exceed cap"""
+        kind, s = self._points(starts, metres)
+        cells, lengths = np.zeros((len(s), int(cap), 2), np.uint16), np.zeros(len(s), np.uint32)
+        self._check(self._call("paths", self._h, kind, s.ctypes.data, len(s), cells.ctypes.data, int(cap), lengths.ctypes.data))
+        return cells, lengths
+
+    def query(self, xy):
+        """uint32 P of the cells of the points xy (n, 2), in the grid's frame; capi.NAV_UNREACHED outside the grid"""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty(len(xy), np.uint32)
+        self._check(self._call("query", self._h, xy.ctypes.data, len(xy), out.ctypes.data))
+        return out
+
+    def stats(self):
+        """capi.NavFieldSolveStats of the last solve as a dict: launches, waits, tiles"""
+        st = capi.NavFieldSolveStats()
+        self._check(self._call("stats", self._h, C.byref(st)))
+        return st.asdict()
+
+
+def navfieldCellCosts(params):
+    """lom_navfield_cell_costs: the uint32 cost of a cell per cost byte (index: the byte read as unsigned), 0 = impassable;
+    needs no device"""
+    p = navfieldParams(params)
+    out = np.empty(256, np.uint32)
+    rc = capi.lib().lom_navfield_cell_costs(C.byref(p), out.ctypes.data)
+    if rc != 0:
+        raise LomError(int(rc), "navigation field cell costs: bad parameters")
     return out
 
 

@@ -344,6 +344,37 @@ CLEAR_FREE_CLEARS_ELEVATION, CLEAR_UNKNOWN_IS_OBSTACLE = 1, 2
 CLEAR_OPT_TEST_TILE_ROWS, CLEAR_OPT_TEST_NO_PRUNE = 1, 2
 
 
+class NavFieldParams(C.Structure):
+    """lom_navfield_params"""
+    _fields_ = [("neutral", C.c_uint32), ("factor", C.c_uint32), ("unknown_cost", C.c_uint32), ("max_passable", C.c_int8),
+                ("flags", C.c_uint32)]
+
+
+class NavFieldSummary(C.Structure):
+    """lom_navfield_summary"""
+    _fields_ = [("cells_blocked", C.c_uint64), ("cells_reached", C.c_uint64), ("cells_unreached", C.c_uint64),
+                ("cells_invalid", C.c_uint64), ("goals_used", C.c_uint64), ("goals_rejected", C.c_uint64),
+                ("range_exceeded", C.c_uint64), ("max_potential", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class NavFieldSolveStats(C.Structure):
+    """lom_navfield_solve_stats"""
+    _fields_ = [("launches", C.c_uint64), ("waits", C.c_uint64), ("tiles", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(NavFieldParams) == 20 and C.sizeof(NavFieldSummary) == 64 and C.sizeof(NavFieldSolveStats) == 24
+NAV_UNREACHED, NAV_MAX = 0xFFFFFFFF, 0xFFFFFFFE
+NAV_UNKNOWN_PASSABLE = 1
+NAV_CELLS, NAV_METRES = 0, 1
+NAV_OPT_TEST_INNER_CAP, NAV_OPT_TEST_BATCH, NAV_OPT_TEST_ALL_TILES = 1, 2, 3
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -434,6 +465,11 @@ EXPORTED = [
     "lom_clearance_set_option", "lom_clearance_update", "lom_clearance_update_device", "lom_clearance_update_from_grids",
     "lom_clearance_cost", "lom_clearance_cost_device", "lom_clearance_distance_sq", "lom_clearance_distance",
     "lom_clearance_cost_table", "lom_clearance_query",
+    "lom_navfield_create", "lom_navfield_destroy", "lom_navfield_last_error", "lom_navfield_clear",
+    "lom_navfield_get_geometry", "lom_navfield_stream", "lom_navfield_device", "lom_navfield_wait_event",
+    "lom_navfield_set_option", "lom_navfield_solve", "lom_navfield_solve_device", "lom_navfield_solve_from_clearance",
+    "lom_navfield_potential", "lom_navfield_potential_device", "lom_navfield_paths", "lom_navfield_query",
+    "lom_navfield_cell_costs", "lom_navfield_stats",
 ]
 # ... and the one it declares through a function type (the "scan archive and map assembly" section)
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
@@ -853,6 +889,28 @@ def lib():
     L.lom_clearance_cost_table.argtypes = [C.POINTER(ClearanceParams), C.POINTER(OccupancyGeometry), vp, C.c_size_t]
     L.lom_clearance_cost_table.restype = C.c_int64
     L.lom_clearance_query.argtypes = [vp, vp, C.c_size_t, vp, vp]
+    L.lom_navfield_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
+    L.lom_navfield_destroy.argtypes = [vp]
+    L.lom_navfield_destroy.restype = None
+    L.lom_navfield_last_error.argtypes = [vp]
+    L.lom_navfield_last_error.restype = C.c_char_p
+    L.lom_navfield_clear.argtypes = [vp]
+    L.lom_navfield_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
+    L.lom_navfield_stream.argtypes = [vp]
+    L.lom_navfield_stream.restype = vp
+    L.lom_navfield_device.argtypes = [vp]
+    L.lom_navfield_wait_event.argtypes = [vp, vp]
+    L.lom_navfield_set_option.argtypes = [vp, C.c_int, C.c_int64]
+    L.lom_navfield_solve.argtypes = [vp, vp, C.POINTER(NavFieldParams), C.c_int, vp, C.c_size_t, C.POINTER(NavFieldSummary)]
+    L.lom_navfield_solve_device.argtypes = [vp, vp, vp, C.POINTER(NavFieldParams), C.c_int, vp, C.c_size_t, C.POINTER(NavFieldSummary)]
+    L.lom_navfield_solve_from_clearance.argtypes = [vp, vp, C.POINTER(NavFieldParams), C.c_int, vp, C.c_size_t,
+                                                    C.POINTER(NavFieldSummary)]
+    L.lom_navfield_potential.argtypes = [vp, vp, C.c_size_t]
+    L.lom_navfield_potential_device.argtypes = [vp, C.POINTER(vp)]
+    L.lom_navfield_paths.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
+    L.lom_navfield_query.argtypes = [vp, vp, C.c_size_t, vp]
+    L.lom_navfield_cell_costs.argtypes = [C.POINTER(NavFieldParams), vp]
+    L.lom_navfield_stats.argtypes = [vp, C.POINTER(NavFieldSolveStats)]
     _lib = L
     return L
 

@@ -1,0 +1,386 @@
+// Navigation field: the least total cost to reach a goal, per cell, over an int8 cost plane; paths down it and point
+// queries.  Definitions: include/lidar_odometry_amd.h ("navigation field"); kernels: k_navfield.hpp; host planning (value
+// ranges, the cell-cost table, goal quantisation, tile counts, launch shapes): navfield_host.cpp; DESIGN.md 7m.  A handle
+// family of its own on the DeviceHandle core; no default path launches any of this.
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "device_handle.hpp"
+#include "k_navfield.hpp"
+#include "navfield_host.hpp"
+
+using namespace lom;
+
+static_assert(navfield::kThreads == kNavThreads && navfield::kTile == kNavTile && navfield::kMaxCellCost == kNavMaxCellCost,
+              "navfield_host.hpp and k_navfield.hpp disagree");
+static_assert(LOM_NAV_UNREACHED == kNavUnreached && LOM_NAV_MAX == kNavMax, "the header and k_navfield.hpp disagree");
+
+// The field owns its stream and every buffer below.
+struct lom_navfield : lom::DeviceHandle {
+    lom_occupancy_geometry geo{};
+    navfield::TileGrid tiles{};
+    lom::DeviceBuf field;            // u32 per cell
+    lom::DeviceBuf plane;            // the cost bytes of the last solve
+    lom::DeviceBuf table;            // 256 u32: the cell costs of the last solve
+    lom::DeviceBuf marks;            // 2 x n_tiles u32: the tiles active in an even and in an odd launch
+    lom::DeviceBuf flags;            // kBatchMax u32: "launch j of the batch marked a tile"
+    lom::DeviceBuf words;            // the summary words
+    lom::DeviceBuf points;           // goals or starts as int32 pairs, grow-only
+    lom::DeviceBuf path_cells, path_lengths;  // a paths call's results, grow-only
+    lom::DeviceBuf q_xy, q_out;      // a query's points and results, grow-only
+    lom::PinnedBuf h_table;          // the table on its way in
+    lom::PinnedBuf h_flags;          // the batch's flags and the summary words on their way out
+    hipEvent_t done_ev = nullptr;    // recorded behind a solve, for the clearance grid's stream to wait on
+    hipEvent_t in_ev = nullptr;      // recorded behind the clearance grid's plane, for this stream to wait on
+    uint32_t inner_cap = navfield::kInnerCapDefault;  // LOM_NAV_OPT_TEST_INNER_CAP
+    uint32_t batch = navfield::kBatchDefault;         // LOM_NAV_OPT_TEST_BATCH
+    uint32_t all_tiles = 0;                           // LOM_NAV_OPT_TEST_ALL_TILES
+    lom_navfield_solve_stats stats{};
+
+    size_t n_cells() const { return (size_t)geo.width * geo.height; }
+    NavArgs args() const { return NavArgs{geo.width, geo.height, tiles.tiles_x, tiles.tiles_y}; }
+};
+
+namespace {
+
+thread_local std::string g_navfield_create_error;
+
+constexpr const char *kParamsText =
+    "navigation field parameters: neutral >= 1, 0 <= max_passable <= 98, neutral + 98 * factor <= 2^24 - 1, known flags, "
+    "unknown_cost in 1 .. 2^24 - 1 under LOM_NAV_UNKNOWN_PASSABLE";
+
+// every cell unreached and impassable, no tile marked
+int fill(lom_navfield *f, bool plane_too)
+{
+    const size_t n = std::max(f->n_cells(), (size_t)2 * f->tiles.n_tiles);
+    hipLaunchKernelGGL(k_nav_fill, dim3(navfield::blocks_for(n)), dim3(kNavThreads), 0, f->stream, (uint32_t)f->n_cells(),
+                       2u * f->tiles.n_tiles, f->field.as<uint32_t>(), f->marks.as<uint32_t>());
+    LOM_HIP(f, hipGetLastError());
+    if (plane_too) {
+        LOM_HIP(f, hipMemsetAsync(f->plane.p, 0xFF, f->n_cells(), f->stream));
+        LOM_HIP(f, hipMemsetAsync(f->table.p, 0, 256 * 4, f->stream));
+    }
+    return LOM_OK;
+}
+
+void summary_from(const uint32_t *t, lom_navfield_summary *s)
+{
+    s->cells_blocked = t[NW_BLOCKED], s->cells_reached = t[NW_REACHED], s->cells_unreached = t[NW_UNREACHED];
+    s->cells_invalid = t[NW_INVALID], s->goals_used = t[NW_GOALS_USED], s->goals_rejected = t[NW_GOALS_REJECTED];
+    s->range_exceeded = t[NW_RANGE], s->max_potential = t[NW_MAX_POTENTIAL];
+}
+
+// the refusals of every solve form that need no device: the text, or NULL
+const char *solve_refusal(bool have_plane, const lom_navfield_params *p, int goal_kind, const void *goals, size_t n_goals)
+{
+    if (!have_plane) return "navigation field solve: a cost plane";
+    if (!navfield::params_ok(p)) return kParamsText;
+    if (goal_kind != LOM_NAV_CELLS && goal_kind != LOM_NAV_METRES) return "navigation field: goals are LOM_NAV_CELLS or LOM_NAV_METRES";
+    if ((n_goals && !goals) || n_goals > navfield::kMaxPoints) return "navigation field solve: goals, at most 2^24 of them";
+    return nullptr;
+}
+
+// n points of `kind` as int32 pairs in f->points, enqueued.  `cells` is the pageable staging block: the caller keeps it
+// until it has waited for the stream.
+int upload_points(lom_navfield *f, int kind, const void *pts, size_t n, std::vector<int32_t> &cells)
+{
+    if (!n) return LOM_OK;
+    cells.resize(2 * n);
+    navfield::quantise(f->geo, kind, pts, n, cells.data());
+    if (const int rc = ensure(f, f->points, n * 8); rc != LOM_OK) return rc;
+    LOM_HIP(f, hipMemcpyAsync(f->points.p, cells.data(), n * 8, hipMemcpyHostToDevice, f->stream));
+    return LOM_OK;
+}
+
+// A solve over a plane in HBM that this stream may read now: the copy of the plane, the seed, the relaxation in batches of
+// launches with one wait each, the report, then the wait.  The arguments are valid.
+int solve_on_device(lom_navfield *f, const int8_t *d_plane, const lom_navfield_params &p, int goal_kind, const void *goals,
+                    size_t n_goals, lom_navfield_summary *summary)
+{
+    // what can still fail for want of memory comes first: a refused call changes nothing
+    std::vector<int32_t> goal_cells;
+    if (const int rc = upload_points(f, goal_kind, goals, n_goals, goal_cells); rc != LOM_OK) return rc;
+    navfield::cell_costs(p, f->h_table.as<uint32_t>());  // (every call waits for its work: nothing enqueued reads the block)
+    LOM_HIP(f, hipMemcpyAsync(f->table.p, f->h_table.h, 256 * 4, hipMemcpyHostToDevice, f->stream));
+    if (d_plane != f->plane.as<const int8_t>())
+        LOM_HIP(f, hipMemcpyAsync(f->plane.p, d_plane, f->n_cells(), hipMemcpyDeviceToDevice, f->stream));
+    LOM_HIP(f, hipMemsetAsync(f->words.p, 0, (size_t)NW_COUNT * 4, f->stream));
+    if (const int rc = fill(f, false); rc != LOM_OK) return rc;
+    const NavArgs a = f->args();
+    const int8_t *const plane = f->plane.as<const int8_t>();
+    const uint32_t *const table = f->table.as<const uint32_t>();
+    uint32_t *const marks = f->marks.as<uint32_t>();
+    if (n_goals) {
+        hipLaunchKernelGGL(k_nav_seed, dim3(navfield::blocks_for(n_goals)), dim3(kNavThreads), 0, f->stream, plane, table, a,
+                           f->points.as<const int32_t>(), (uint32_t)n_goals, f->field.as<uint32_t>(), marks, f->words.as<uint32_t>());
+        LOM_HIP(f, hipGetLastError());
+    }
+    // Launch k reads the marks of parity k & 1 and writes the others.  A launch behind the fixed point finds no active
+    // tile (or, with all tiles, lowers nothing) and marks nothing, so the batch may run ahead of what the host knows.
+    f->stats = lom_navfield_solve_stats{0, 0, f->tiles.n_tiles};
+    const uint64_t bound = navfield::launch_bound(f->geo.width, f->geo.height);
+    const uint32_t B = f->batch;
+    for (;;) {
+        LOM_HIP(f, hipMemsetAsync(f->flags.p, 0, (size_t)B * 4, f->stream));
+        for (uint32_t j = 0; j < B; j++) {
+            const uint32_t parity = (uint32_t)(f->stats.launches & 1u);
+            hipLaunchKernelGGL(k_nav_relax, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0, f->stream, plane, table, a,
+                               f->inner_cap, f->all_tiles, f->field.as<uint32_t>(), marks + (size_t)parity * f->tiles.n_tiles,
+                               marks + (size_t)(parity ^ 1u) * f->tiles.n_tiles, f->flags.as<uint32_t>() + j);
+            LOM_HIP(f, hipGetLastError());
+            f->stats.launches++;
+        }
+        LOM_HIP(f, hipMemcpyAsync(f->h_flags.h, f->flags.p, (size_t)B * 4, hipMemcpyDeviceToHost, f->stream));
+        LOM_HIP(f, hipStreamSynchronize(f->stream));
+        f->stats.waits++;
+        if (f->h_flags.as<uint32_t>()[B - 1u] == 0u) break;  // the last launch marked nothing: the fixed point
+        if (f->stats.launches > bound) return fail(f, LOM_ERR_HIP, "navigation field: the relaxation did not settle");
+    }
+    hipLaunchKernelGGL(k_nav_report, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream, plane, table,
+                       f->field.as<const uint32_t>(), a, f->words.as<uint32_t>());
+    LOM_HIP(f, hipGetLastError());
+    LOM_HIP(f, hipMemcpyAsync(f->h_flags.h, f->words.p, (size_t)NW_COUNT * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    if (summary) summary_from(f->h_flags.as<uint32_t>(), summary);
+    return LOM_OK;
+}
+
+bool same_geometry(const lom_occupancy_geometry &a, const lom_occupancy_geometry &b)
+{
+    return std::memcmp(&a.resolution, &b.resolution, 4) == 0 && std::memcmp(&a.origin_x, &b.origin_x, 4) == 0 &&
+           std::memcmp(&a.origin_y, &b.origin_y, 4) == 0 && a.width == b.width && a.height == b.height;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lom_navfield_create(const lom_occupancy_geometry *geometry, int device, lom_navfield **out)
+{
+    if (!out) return LOM_ERR_ARG;
+    *out = nullptr;
+    if (!navfield::geometry_ok(geometry))
+        return create_fail(g_navfield_create_error, LOM_ERR_ARG,
+                           "navigation field geometry: resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192");
+    if (const int rc = check_device(device, g_navfield_create_error); rc != LOM_OK) return rc;
+    lom_navfield *f = new (std::nothrow) lom_navfield();
+    if (!f) return create_fail(g_navfield_create_error, LOM_ERR_OOM, "host allocation");
+    f->device = device;
+    f->geo = *geometry;
+    f->tiles = navfield::tile_grid(geometry->width, geometry->height);
+    int rc = LOM_OK;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->done_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->in_ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = alloc(f->h_table, 256 * 4, hipHostMallocDefault);
+    if (e == hipSuccess) e = alloc(f->h_flags, (size_t)navfield::kBatchMax * 4, hipHostMallocDefault);
+    if (e != hipSuccess) rc = create_fail(g_navfield_create_error, LOM_ERR_HIP, "navigation field setup", e);
+    const size_t n = f->n_cells();
+    if (rc == LOM_OK &&
+        (alloc(f->field, n * 4) != hipSuccess || alloc(f->plane, n) != hipSuccess || alloc(f->table, 256 * 4) != hipSuccess ||
+         alloc(f->marks, (size_t)2 * f->tiles.n_tiles * 4) != hipSuccess ||
+         alloc(f->flags, (size_t)navfield::kBatchMax * 4) != hipSuccess || alloc(f->words, 64) != hipSuccess))
+        rc = create_fail(g_navfield_create_error, LOM_ERR_OOM, "hipMalloc (navigation field)");
+    if (rc == LOM_OK) {
+        if (fill(f, true) != LOM_OK || (e = hipStreamSynchronize(f->stream)) != hipSuccess)
+            rc = create_fail(g_navfield_create_error, LOM_ERR_HIP, f->error.empty() ? "navigation field setup" : f->error.c_str(), e);
+    }
+    if (rc != LOM_OK) {
+        lom_navfield_destroy(f);
+        return rc;
+    }
+    *out = f;
+    return LOM_OK;
+}
+
+void lom_navfield_destroy(lom_navfield *f)
+{
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    if (f->stream) (void)hipStreamSynchronize(f->stream);
+    for (hipEvent_t ev : {f->done_ev, f->in_ev})
+        if (ev) (void)hipEventDestroy(ev);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;  // the buffers go with it
+}
+
+const char *lom_navfield_last_error(const lom_navfield *f) { return f ? f->error.c_str() : g_navfield_create_error.c_str(); }
+
+int lom_navfield_clear(lom_navfield *f)
+{
+    if (!f) return LOM_ERR_ARG;
+    LOM_HIP(f, hipSetDevice(f->device));
+    if (const int rc = fill(f, true); rc != LOM_OK) return rc;
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    return LOM_OK;
+}
+
+int lom_navfield_get_geometry(const lom_navfield *f, lom_occupancy_geometry *out)
+{
+    if (!f || !out) return LOM_ERR_ARG;
+    *out = f->geo;
+    return LOM_OK;
+}
+
+void *lom_navfield_stream(lom_navfield *f) { return f ? (void *)f->stream : nullptr; }
+int lom_navfield_device(const lom_navfield *f) { return f ? f->device : LOM_ERR_ARG; }
+
+int lom_navfield_wait_event(lom_navfield *f, void *hip_event)
+{
+    if (!f || !hip_event) return LOM_ERR_ARG;
+    LOM_HIP(f, hipSetDevice(f->device));
+    LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event, 0));
+    return LOM_OK;
+}
+
+int lom_navfield_set_option(lom_navfield *f, int option, int64_t value)
+{
+    if (!f) return LOM_ERR_ARG;
+    switch (option) {
+    case LOM_NAV_OPT_TEST_INNER_CAP:
+        if (value > (int64_t)navfield::kInnerCapMax) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_INNER_CAP: 1 .. 2^20, or <= 0 for the default");
+        f->inner_cap = value <= 0 ? navfield::kInnerCapDefault : (uint32_t)value;
+        return LOM_OK;
+    case LOM_NAV_OPT_TEST_BATCH:
+        if (value > (int64_t)navfield::kBatchMax) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_BATCH: 1 .. 256, or <= 0 for the default");
+        f->batch = value <= 0 ? navfield::kBatchDefault : (uint32_t)value;
+        return LOM_OK;
+    case LOM_NAV_OPT_TEST_ALL_TILES:
+        if (value > 1) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_ALL_TILES: 0, 1, or < 0 for the default");
+        f->all_tiles = value == 1 ? 1u : 0u;
+        return LOM_OK;
+    default:
+        return fail(f, LOM_ERR_ARG, "unknown navigation field option");
+    }
+}
+
+int lom_navfield_solve_device(lom_navfield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_navfield_params *params,
+                              int goal_kind, const void *goals, size_t n_goals, lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const char *why = solve_refusal(d_plane != nullptr, params, goal_kind, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
+    LOM_HIP(f, hipSetDevice(f->device));
+    if (hip_event_or_null) LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event_or_null, 0));
+    return solve_on_device(f, d_plane, *params, goal_kind, goals, n_goals, summary);
+}
+
+int lom_navfield_solve(lom_navfield *f, const int8_t *plane, const lom_navfield_params *params, int goal_kind, const void *goals,
+                       size_t n_goals, lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const char *why = solve_refusal(plane != nullptr, params, goal_kind, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
+    LOM_HIP(f, hipSetDevice(f->device));
+    // the goals first: their buffer is what can still be refused (no memory); then the plane goes straight to the field's copy
+    if (const int rc = n_goals ? ensure(f, f->points, n_goals * 8) : LOM_OK; rc != LOM_OK) return rc;
+    LOM_HIP(f, hipMemcpyAsync(f->plane.p, plane, f->n_cells(), hipMemcpyHostToDevice, f->stream));
+    return solve_on_device(f, f->plane.as<const int8_t>(), *params, goal_kind, goals, n_goals, summary);
+}
+
+int lom_navfield_solve_from_clearance(lom_navfield *f, lom_clearance *clearance, const lom_navfield_params *params, int goal_kind,
+                                      const void *goals, size_t n_goals, lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const char *why = solve_refusal(clearance != nullptr, params, goal_kind, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
+    lom_occupancy_geometry g;
+    if (lom_clearance_get_geometry(clearance, &g) != LOM_OK || !same_geometry(g, f->geo))
+        return fail(f, LOM_ERR_ARG, "navigation field: the clearance grid's resolution, origin, width or height differs");
+    if (lom_clearance_device(clearance) != f->device) return fail(f, LOM_ERR_ARG, "navigation field: the clearance grid lives on another device");
+    LOM_HIP(f, hipSetDevice(f->device));
+    // the clearance grid leaves its plane on its own stream; this stream reads it behind an event
+    const int8_t *d_plane = nullptr;
+    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
+        return fail(f, LOM_ERR_HIP, (std::string("navigation field: lom_clearance_cost_device: ") + lom_clearance_last_error(clearance)).c_str());
+    LOM_HIP(f, hipEventRecord(f->in_ev, (hipStream_t)lom_clearance_stream(clearance)));
+    LOM_HIP(f, hipStreamWaitEvent(f->stream, f->in_ev, 0));
+    const int rc = solve_on_device(f, d_plane, *params, goal_kind, goals, n_goals, summary);
+    if (rc != LOM_OK) return rc;
+    // and what the clearance grid does next to its plane comes behind this solve's reads
+    if (lom_clearance_wait_event(clearance, f->done_ev) != LOM_OK) return fail(f, LOM_ERR_HIP, "navigation field: lom_clearance_wait_event");
+    return LOM_OK;
+}
+
+int lom_navfield_potential(lom_navfield *f, uint32_t *out, size_t cap)
+{
+    if (!f || (cap && !out)) return LOM_ERR_ARG;
+    const size_t n = std::min(cap, f->n_cells());
+    if (!n) return LOM_OK;
+    LOM_HIP(f, hipSetDevice(f->device));
+    LOM_HIP(f, hipMemcpyAsync(out, f->field.p, n * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    return LOM_OK;
+}
+
+int lom_navfield_potential_device(lom_navfield *f, const uint32_t **d_out)
+{
+    if (!f || !d_out) return LOM_ERR_ARG;
+    *d_out = f->field.as<const uint32_t>();
+    return LOM_OK;
+}
+
+int lom_navfield_paths(lom_navfield *f, int start_kind, const void *starts, size_t n_starts, uint16_t *cells_out, size_t cap,
+                       uint32_t *lengths_out)
+{
+    if (!f) return LOM_ERR_ARG;
+    if (start_kind != LOM_NAV_CELLS && start_kind != LOM_NAV_METRES) return fail(f, LOM_ERR_ARG, "navigation field: starts are LOM_NAV_CELLS or LOM_NAV_METRES");
+    if ((n_starts && !starts) || n_starts > navfield::kMaxPoints) return fail(f, LOM_ERR_ARG, "navigation field paths: starts, at most 2^24 of them");
+    if (cap > navfield::kMaxPathCells || (cap && n_starts > navfield::kMaxPathCells / cap) || (n_starts && cap && !cells_out))
+        return fail(f, LOM_ERR_ARG, "navigation field paths: an output of n_starts * cap cells, at most 2^28");
+    if (!n_starts) return LOM_OK;
+    LOM_HIP(f, hipSetDevice(f->device));
+    const size_t cell_bytes = n_starts * cap * 4;
+    int rc;
+    if ((rc = ensure(f, f->path_cells, std::max(cell_bytes, (size_t)256))) != LOM_OK || (rc = ensure(f, f->path_lengths, n_starts * 4)) != LOM_OK)
+        return rc;
+    std::vector<int32_t> start_cells;
+    if ((rc = upload_points(f, start_kind, starts, n_starts, start_cells)) != LOM_OK) return rc;
+    if (cell_bytes) LOM_HIP(f, hipMemsetAsync(f->path_cells.p, 0, cell_bytes, f->stream));
+    hipLaunchKernelGGL(k_nav_trace, dim3(navfield::blocks_for(n_starts)), dim3(kNavThreads), 0, f->stream, f->plane.as<const int8_t>(),
+                       f->table.as<const uint32_t>(), f->field.as<const uint32_t>(), f->args(), f->points.as<const int32_t>(),
+                       (uint32_t)n_starts, (uint32_t)cap, f->path_cells.as<uint16_t>(), f->path_lengths.as<uint32_t>());
+    LOM_HIP(f, hipGetLastError());
+    if (cell_bytes) LOM_HIP(f, hipMemcpyAsync(cells_out, f->path_cells.p, cell_bytes, hipMemcpyDeviceToHost, f->stream));
+    if (lengths_out) LOM_HIP(f, hipMemcpyAsync(lengths_out, f->path_lengths.p, n_starts * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    return LOM_OK;
+}
+
+int lom_navfield_query(lom_navfield *f, const float *xy, size_t n, uint32_t *out)
+{
+    if (!f) return LOM_ERR_ARG;
+    if ((n && !xy) || n > (size_t)1 << 30) return fail(f, LOM_ERR_ARG, "navigation field query: points, at most 2^30 of them");
+    if (!n || !out) return LOM_OK;
+    LOM_HIP(f, hipSetDevice(f->device));
+    int rc;
+    if ((rc = ensure(f, f->q_xy, n * 8)) != LOM_OK || (rc = ensure(f, f->q_out, n * 4)) != LOM_OK) return rc;
+    LOM_HIP(f, hipMemcpyAsync(f->q_xy.p, xy, n * 8, hipMemcpyHostToDevice, f->stream));
+    hipLaunchKernelGGL(k_nav_query, dim3(navfield::blocks_for(n)), dim3(kNavThreads), 0, f->stream, f->q_xy.as<const float>(), (uint32_t)n,
+                       f->geo.resolution, f->geo.origin_x, f->geo.origin_y, f->args(), f->field.as<const uint32_t>(), f->q_out.as<uint32_t>());
+    LOM_HIP(f, hipGetLastError());
+    LOM_HIP(f, hipMemcpyAsync(out, f->q_out.p, n * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    return LOM_OK;
+}
+
+int lom_navfield_cell_costs(const lom_navfield_params *params, uint32_t *out256)
+{
+    if (!navfield::params_ok(params) || !out256) return LOM_ERR_ARG;
+    navfield::cell_costs(*params, out256);
+    return LOM_OK;
+}
+
+int lom_navfield_stats(const lom_navfield *f, lom_navfield_solve_stats *out)
+{
+    if (!f || !out) return LOM_ERR_ARG;
+    *out = f->stats;
+    return LOM_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,75 @@
+// Host planning of lom_navfield_*: value ranges, the cell-cost table, the quantisation of goals and starts, tile counts
+// and launch shapes.  Plain C++, no HIP: navfield.hip calls these, and tests/cpp/test_navfield.cpp compiles this file
+// alone.
+#include "navfield_host.hpp"
+
+#include <cmath>
+
+namespace lom {
+namespace navfield {
+
+bool geometry_ok(const lom_occupancy_geometry *g)
+{
+    return g && std::isfinite(g->resolution) && g->resolution > 0.f && std::isfinite(g->origin_x) && std::isfinite(g->origin_y) &&
+           g->width >= 1u && g->width <= kMaxSide && g->height >= 1u && g->height <= kMaxSide;
+}
+
+bool params_ok(const lom_navfield_params *p)
+{
+    if (!p || p->neutral < 1u || p->max_passable < 0 || p->max_passable > (int8_t)kMaxByteCost || (p->flags & ~kKnownFlags) != 0u)
+        return false;
+    // (64-bit: 98 * factor cannot wrap)
+    if ((uint64_t)p->neutral + (uint64_t)kMaxByteCost * p->factor > (uint64_t)kMaxCellCost) return false;
+    if ((p->flags & LOM_NAV_UNKNOWN_PASSABLE) && (p->unknown_cost < 1u || p->unknown_cost > kMaxCellCost)) return false;
+    return true;
+}
+
+void cell_costs(const lom_navfield_params &p, uint32_t out[256])
+{
+    for (uint32_t b = 0; b < 256u; b++) out[b] = 0u;
+    for (uint32_t v = 0; v <= (uint32_t)p.max_passable; v++) out[v] = p.neutral + p.factor * v;
+    if (p.flags & LOM_NAV_UNKNOWN_PASSABLE) out[255] = p.unknown_cost;  // the byte -1
+}
+
+bool cell_of_metres(const lom_occupancy_geometry &g, float x, float y, int32_t *ix, int32_t *iy)
+{
+    const double r = (double)g.resolution;
+    const double qx = std::floor(((double)x - (double)g.origin_x) / r), qy = std::floor(((double)y - (double)g.origin_y) / r);
+    // (a NaN fails every comparison)
+    if (qx >= 0.0 && qx < (double)g.width && qy >= 0.0 && qy < (double)g.height) {
+        *ix = (int32_t)qx, *iy = (int32_t)qy;
+        return true;
+    }
+    *ix = *iy = -1;
+    return false;
+}
+
+bool quantise(const lom_occupancy_geometry &g, int kind, const void *points, size_t n, int32_t *out)
+{
+    if (kind == LOM_NAV_CELLS) {
+        const int32_t *c = static_cast<const int32_t *>(points);
+        for (size_t i = 0; i < 2 * n; i++) out[i] = c[i];
+        return true;
+    }
+    if (kind == LOM_NAV_METRES) {
+        const float *m = static_cast<const float *>(points);
+        for (size_t i = 0; i < n; i++) (void)cell_of_metres(g, m[2 * i], m[2 * i + 1], out + 2 * i, out + 2 * i + 1);
+        return true;
+    }
+    return false;
+}
+
+TileGrid tile_grid(uint32_t width, uint32_t height)
+{
+    TileGrid t;
+    t.tiles_x = (width + kTile - 1u) / kTile, t.tiles_y = (height + kTile - 1u) / kTile;
+    t.n_tiles = t.tiles_x * t.tiles_y;  // at most 256 * 256
+    return t;
+}
+
+uint32_t blocks_for(size_t n) { return n ? (uint32_t)((n + kThreads - 1u) / kThreads) : 1u; }
+
+uint64_t launch_bound(uint32_t width, uint32_t height) { return 2ull * width * height + 64ull; }
+
+}  // namespace navfield
+}  // namespace lom

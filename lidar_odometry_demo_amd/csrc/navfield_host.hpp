@@ -1,0 +1,55 @@
+// Host planning of the navigation field (navfield_host.cpp), shared with navfield.hip.  Plain C++: nothing here needs a
+// device or a HIP header.  The value ranges of the geometry and the parameters, the cell-cost table, the quantisation of
+// goals and starts, the tile counts and the launch shapes.  Definitions: include/lidar_odometry_amd.h ("navigation
+// field").
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/lidar_odometry_amd.h"
+
+namespace lom {
+namespace navfield {
+
+constexpr uint32_t kMaxSide = 8192;                // cells per axis
+constexpr uint32_t kTile = 32;                     // a tile of k_nav_relax is 32 x 32 cells
+constexpr uint32_t kThreads = 256;                 // every kernel runs workgroups of four waves
+constexpr uint32_t kMaxCellCost = (1u << 24) - 1;  // of a passable cell: 7 * kMaxCellCost < 2^27 fits a u32 with room
+constexpr uint32_t kMaxByteCost = 98;              // the largest cost byte that may be passable
+constexpr uint32_t kKnownFlags = LOM_NAV_UNKNOWN_PASSABLE;
+constexpr uint32_t kInnerCapDefault = 64;          // sweeps of a tile per launch
+constexpr uint32_t kInnerCapMax = 1u << 20;
+constexpr uint32_t kBatchDefault = 16;             // launches per wait
+constexpr uint32_t kBatchMax = 256;
+constexpr size_t kMaxPoints = (size_t)1 << 24;     // goals of a solve, starts of a paths call
+constexpr size_t kMaxPathCells = (size_t)1 << 28;  // K * cap of a paths call
+
+// k_nav_relax: a workgroup per tile, tiles_x x tiles_y of them; the last column and row may be cut
+struct TileGrid {
+    uint32_t tiles_x, tiles_y, n_tiles;
+};
+
+// resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192
+bool geometry_ok(const lom_occupancy_geometry *g);
+// neutral >= 1, 0 <= max_passable <= 98, neutral + 98 * factor <= 2^24 - 1, known flags only, and unknown_cost in
+// 1 .. 2^24 - 1 where LOM_NAV_UNKNOWN_PASSABLE is set
+bool params_ok(const lom_navfield_params *p);
+// the header's step 1: the cost of a cell per cost byte (index: the byte read as unsigned), 0 = impassable
+void cell_costs(const lom_navfield_params &p, uint32_t out[256]);
+// a cost byte outside -1 .. 100
+inline bool byte_invalid(int8_t b) { return b < -1 || b > 100; }
+// The cell of a point in metres by the floor rule (f64 from the f32 values, compared before any conversion).  false: the
+// point is outside the grid or not a number, and *ix = *iy = -1.
+bool cell_of_metres(const lom_occupancy_geometry &g, float x, float y, int32_t *ix, int32_t *iy);
+// n goals or starts of either kind as int32 (ix, iy) pairs for the device: cells are passed on as they are (the device
+// refuses those outside the grid), metres go through cell_of_metres.  false: an unknown kind.
+bool quantise(const lom_occupancy_geometry &g, int kind, const void *points, size_t n, int32_t *out);
+TileGrid tile_grid(uint32_t width, uint32_t height);
+// workgroups of kThreads lanes for n lanes (at least one)
+uint32_t blocks_for(size_t n);
+// More launches than any solve needs: a cell whose best route has d steps is final one launch after the next cell of
+// that route is, so d + 1 launches settle it, and d is below the number of cells.  2 * cells + 64.
+uint64_t launch_bound(uint32_t width, uint32_t height);
+
+}  // namespace navfield
+}  // namespace lom
