@@ -1788,6 +1788,129 @@ int lom_navfield_cell_costs(const lom_navfield_params *params, uint32_t *out256)
 /* the launches and waits of the last solve (zeros before the first) */
 int lom_navfield_stats(const lom_navfield *f, lom_navfield_solve_stats *out);
 
+/* ---- frontier regions: connected cells labelled on the device, ranked goals (not in the reference) ----------------------
+ * The navigation field answers what it costs to get somewhere.  This handle family answers where to go: it labels the
+ * connected regions of a grid plane -- the frontier cells of an occupancy plane (FREE next to UNKNOWN, as an explorer
+ * reads nav_msgs/OccupancyGrid), or any byte range: obstacle blobs, connected free space, unreached pockets -- gives
+ * each region a record (size, box, centre, cheapest cell to reach) and leaves a ranked goal list in the form
+ * lom_navfield_solve takes under LOM_NAV_CELLS.  Nothing is launched unless a caller creates a region grid.  The
+ * definition, operation by operation (tests/regions_ref.py restates it with a flood fill on Python integers; everything
+ * is an integer, so every comparison is exact):
+ *
+ * Grid.  lom_occupancy_geometry, reused, with the navigation field's rules: row-major with y as the row, the linear
+ * index of cell (ix, iy) is iy * width + ix (below 2^26), the index rule is the floor rule.  r > 0 and finite, a finite
+ * origin, 1 <= width, height <= 8192; anything else is LOM_ERR_ARG.
+ *
+ * Inputs of an extract.  `plane`: a full-grid int8 plane, what lom_occupancy_classify writes; any byte is accepted.
+ * `cost`, optional: a full-grid int8 plane in lom_clearance_cost's range.  `potential`, optional: a full-grid u32 plane
+ * in lom_navfield_potential's form.  lom_regions_params: kind LOM_REGIONS_BYTES or LOM_REGIONS_FRONTIER; lo <= hi under
+ * LOM_REGIONS_BYTES (neither is read otherwise); 0 <= max_cost <= 99; min_cells >= 1; a known rank, and
+ * LOM_REGIONS_RANK_POTENTIAL only with a potential; no unknown bit in flags; anything else is LOM_ERR_ARG.
+ *  1. Membership.  LOM_REGIONS_BYTES: a cell is a member iff lo <= plane <= hi.  LOM_REGIONS_FRONTIER: iff plane == 0 and
+ *     at least one neighbour has plane == -1; the neighbours are the four edge neighbours, all eight under
+ *     LOM_REGIONS_NEIGHBOURS_8; a neighbour outside the grid is not unknown unless LOM_REGIONS_EDGE_UNKNOWN is set.  In
+ *     both kinds a member also needs 0 <= cost <= max_cost where a cost plane is given, and P != LOM_NAV_UNREACHED where
+ *     a potential is given.
+ *  2. Regions.  The 8-connected components of the members; the 4-connected ones under LOM_REGIONS_CONNECT_4.  The label
+ *     of a member is the least linear index in its component; every other cell reads LOM_REGIONS_NONE.  Labels are a u32
+ *     plane.
+ *  3. Dense order.  Regions are numbered 0, 1, ... by ascending label.  Only the first max_regions of them
+ *     (LOM_REGIONS_OPT_MAX_REGIONS, default 2^20) get a record; the summary counts all of them and the recorded ones.
+ *  4. Record.  lom_regions_record, 48 bytes, per recorded region: label; cells; sum_x, sum_y (the sums of ix and of iy);
+ *     the box min_x, min_y, max_x, max_y; the centroid cell cx = floor((2 sum_x + cells) / (2 cells)), cy likewise; the
+ *     centre cell, the member that minimises (ix - cx)^2 + (iy - cy)^2, ties to the least linear index; the entry cell,
+ *     the member with the least P, ties to the least linear index, and entry_potential, that P.  Without a potential the
+ *     entry cell is the centre cell and entry_potential is LOM_NAV_UNREACHED.  Both minima are one unsigned 64-bit
+ *     minimum of (key << 26) | linear index: d^2 is below 2^27, P below 2^32.
+ *  5. List.  The recorded regions with cells >= min_cells, sorted by rank, ties by ascending label:
+ *     LOM_REGIONS_RANK_LABEL; LOM_REGIONS_RANK_CELLS, largest first; LOM_REGIONS_RANK_POTENTIAL, least entry_potential
+ *     first.  The list holds at most max_regions records and is sorted on the host.
+ *  6. Goals.  The centre cells (LOM_REGIONS_GOAL_CENTRE) or the entry cells (LOM_REGIONS_GOAL_ENTRY) of the list, in list
+ *     order, as int32 (ix, iy) pairs.
+ *  7. Query.  n points in metres: the label of the cell; LOM_REGIONS_NONE for a point outside the grid or not a number.
+ *  8. Summary.  cells_member, regions, regions_recorded, regions_listed, largest_cells (the largest count among recorded
+ *     regions, 0 if none).
+ * After create or lom_regions_clear there is no member, no region and an empty list.
+ *
+ * The result is a pure function of the planes and the parameters: it does not depend on the tile shape, on the number of
+ * launches, on the order in which workgroups run or on the test switches below.
+ *
+ * lom_regions_extract takes host planes; _extract_device planes in HBM that are complete when hip_event_or_null is
+ * (NULL: now); _extract_from_grids reads lom_occupancy_classify_device, lom_clearance_cost_device (or no cost plane) and
+ * lom_navfield_potential_device (or no potential) and orders the streams by events in both directions -- a grid whose
+ * resolution, origin, width or height differ bit for bit, or that lives on another device, is LOM_ERR_ARG before any
+ * launch.  Every argument is validated before any device work; a refused call changes nothing and zeroes the summary.
+ * Every call returns with its work done.  Calls on one handle are the caller's to serialise.  The error text is the
+ * handle's (lom_regions_last_error). */
+typedef struct lom_regions lom_regions;
+typedef struct {
+    int32_t kind;       /* LOM_REGIONS_BYTES, LOM_REGIONS_FRONTIER */
+    int8_t lo, hi;      /* the byte range of LOM_REGIONS_BYTES */
+    int8_t max_cost;    /* the largest cost byte of a member where a cost plane is given, 0 .. 99 */
+    uint32_t min_cells; /* the smallest listed region, >= 1 */
+    int32_t rank;       /* LOM_REGIONS_RANK_* */
+    uint32_t flags;     /* LOM_REGIONS_NEIGHBOURS_8 | LOM_REGIONS_EDGE_UNKNOWN | LOM_REGIONS_CONNECT_4 */
+} lom_regions_params;
+typedef struct {
+    uint32_t label;                       /* offset 0: the least linear index of the region */
+    uint32_t cells;                       /* 4 */
+    uint64_t sum_x, sum_y;                /* 8, 16 */
+    uint16_t min_x, min_y, max_x, max_y;  /* 24 .. 31 */
+    uint16_t centroid_x, centroid_y;      /* 32, 34 */
+    uint16_t centre_x, centre_y;          /* 36, 38 */
+    uint16_t entry_x, entry_y;            /* 40, 42 */
+    uint32_t entry_potential;             /* 44 */
+} lom_regions_record;
+typedef struct {
+    uint64_t cells_member, regions, regions_recorded, regions_listed, largest_cells;
+} lom_regions_summary;
+typedef struct {
+    uint64_t launches, waits; /* kernel launches of the last extract, and the host's waits for them */
+    uint64_t tiles;           /* workgroups of k_reg_label_tile (0 under LOM_REGIONS_OPT_TEST_NO_TILES) */
+} lom_regions_extract_stats;
+#define LOM_REGIONS_NONE 0xFFFFFFFFu
+enum { LOM_REGIONS_BYTES = 0, LOM_REGIONS_FRONTIER = 1 };
+enum { LOM_REGIONS_NEIGHBOURS_8 = 1, LOM_REGIONS_EDGE_UNKNOWN = 2, LOM_REGIONS_CONNECT_4 = 4 };
+enum { LOM_REGIONS_RANK_LABEL = 0, LOM_REGIONS_RANK_CELLS = 1, LOM_REGIONS_RANK_POTENTIAL = 2 };
+enum { LOM_REGIONS_GOAL_CENTRE = 0, LOM_REGIONS_GOAL_ENTRY = 1 };
+enum {
+    LOM_REGIONS_OPT_MAX_REGIONS = 1,        /* records kept, 1 .. 2^26; <= 0: the default, 2^20 */
+    LOM_REGIONS_OPT_TEST_TILE_ROWS = 2,     /* rows of a tile of k_reg_label_tile: 1, 8 or 32; <= 0: the default */
+    LOM_REGIONS_OPT_TEST_NO_TILES = 3,      /* 1: no tile pass, every adjacency goes through k_reg_merge; 0 or < 0: the default */
+    LOM_REGIONS_OPT_TEST_NO_WAVE_MERGE = 4  /* 1: every member lane issues its own atomics; 0 or < 0: the default.
+                                               Test switches: the bytes are the same. */
+};
+int lom_regions_create(const lom_occupancy_geometry *geometry, int device, lom_regions **out);
+void lom_regions_destroy(lom_regions *r);
+const char *lom_regions_last_error(const lom_regions *r); /* r == NULL: why the last create on this thread failed */
+int lom_regions_clear(lom_regions *r);                    /* no member, no region, an empty list */
+int lom_regions_get_geometry(const lom_regions *r, lom_occupancy_geometry *out);
+void *lom_regions_stream(lom_regions *r); /* hipStream_t */
+int lom_regions_device(const lom_regions *r);
+int lom_regions_wait_event(lom_regions *r, void *hip_event);
+int lom_regions_set_option(lom_regions *r, int option, int64_t value);
+/* plane: width * height int8; cost_or_null: the same; potential_or_null: width * height u32 */
+int lom_regions_extract(lom_regions *r, const int8_t *plane, const int8_t *cost_or_null, const uint32_t *potential_or_null,
+                        const lom_regions_params *params, lom_regions_summary *summary_or_null);
+int lom_regions_extract_device(lom_regions *r, const int8_t *d_plane, const int8_t *d_cost_or_null,
+                               const uint32_t *d_potential_or_null, void *hip_event_or_null, const lom_regions_params *params,
+                               lom_regions_summary *summary_or_null);
+int lom_regions_extract_from_grids(lom_regions *r, lom_occupancy *occupancy, const lom_occupancy_rule *rule,
+                                   lom_clearance *clearance_or_null, lom_navfield *navfield_or_null,
+                                   const lom_regions_params *params, lom_regions_summary *summary_or_null);
+/* the labels over the whole grid, row-major: at most `cap` cells go to `out` (may be NULL with cap 0) */
+int lom_regions_labels(lom_regions *r, uint32_t *out, size_t cap);
+/* the same, left in HBM: width * height cells, valid until the next extract or clear on the handle */
+int lom_regions_labels_device(lom_regions *r, const uint32_t **d_out);
+/* step 5: at most `cap` records go to `out` (may be NULL with cap 0); *listed_or_null: the length of the list */
+int lom_regions_list(lom_regions *r, lom_regions_record *out, size_t cap, size_t *listed_or_null);
+/* step 6: at most `cap` int32 (ix, iy) pairs go to `out`; which: LOM_REGIONS_GOAL_CENTRE or LOM_REGIONS_GOAL_ENTRY */
+int lom_regions_goals(lom_regions *r, int which, int32_t *out, size_t cap, size_t *listed_or_null);
+/* step 7: n points (x, y in the grid's frame, f32 pairs in host memory, at most 2^30) */
+int lom_regions_query(lom_regions *r, const float *xy, size_t n, uint32_t *out);
+/* the launches and waits of the last extract (zeros before the first) */
+int lom_regions_stats(const lom_regions *r, lom_regions_extract_stats *out);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;

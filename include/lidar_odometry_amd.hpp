@@ -1310,6 +1310,108 @@ inline std::vector<uint32_t> navfieldCellCosts(const lom_navfield_params &params
     return out;
 }
 
+// ---- RegionGrid (not in the reference) -------------------------------------------------
+// Connected regions of a grid plane on the device: extract() takes an int8 plane (row-major with y as the row, what
+// OccupancyGrid::classify() writes), optionally a cost plane and a NavField potential, labels the regions of the
+// frontier cells (or of a byte range) and leaves a record per region and a ranked list; goals() gives the list's centre
+// or entry cells in the form NavField::solve() takes.  Definitions: lidar_odometry_amd.h ("frontier regions").
+using RegionsParams = lom_regions_params;  // {kind, lo, hi, max_cost, min_cells, rank, flags}
+using RegionsSummary = lom_regions_summary;
+using RegionsRecord = lom_regions_record;
+
+inline RegionsParams regionsParams(int32_t kind, int8_t lo, int8_t hi, int8_t max_cost, uint32_t min_cells, int32_t rank, uint32_t flags = 0)
+{
+    return RegionsParams{kind, lo, hi, max_cost, min_cells, rank, flags};
+}
+
+class RegionGrid {
+public:
+    explicit RegionGrid(const lom_occupancy_geometry &geometry, int device = 0)
+    {
+        const int rc = lom_regions_create(&geometry, device, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_regions_last_error(nullptr));
+    }
+    ~RegionGrid() { lom_regions_destroy(h_); }
+    RegionGrid(const RegionGrid &) = delete;
+    RegionGrid &operator=(const RegionGrid &) = delete;
+    lom_regions *handle() const { return h_; }
+    lom_occupancy_geometry geometry() const
+    {
+        lom_occupancy_geometry g;
+        check(lom_regions_get_geometry(h_, &g));
+        return g;
+    }
+    size_t size() const
+    {
+        const lom_occupancy_geometry g = geometry();
+        return (size_t)g.width * g.height;
+    }
+    void clear() { check(lom_regions_clear(h_)); }
+    void setOption(int option, int64_t value) { check(lom_regions_set_option(h_, option, value)); }
+    // host planes of size() cells; cost and potential may be NULL
+    lom_regions_summary extract(const int8_t *plane, const lom_regions_params &params, const int8_t *cost = nullptr,
+                                const uint32_t *potential = nullptr)
+    {
+        lom_regions_summary s;
+        check(lom_regions_extract(h_, plane, cost, potential, &params, &s));
+        return s;
+    }
+    // the planes an OccupancyGrid, a ClearanceGrid (or NULL) and a NavField (or NULL) of this geometry left in HBM
+    lom_regions_summary extractFromGrids(OccupancyGrid &occupancy, const lom_occupancy_rule &rule, ClearanceGrid *clearance,
+                                         NavField *navfield, const lom_regions_params &params)
+    {
+        lom_regions_summary s;
+        check(lom_regions_extract_from_grids(h_, occupancy.handle(), &rule, clearance ? clearance->handle() : nullptr,
+                                             navfield ? navfield->handle() : nullptr, &params, &s));
+        return s;
+    }
+    std::vector<uint32_t> labels()
+    {
+        std::vector<uint32_t> out(size());
+        check(lom_regions_labels(h_, out.data(), out.size()));
+        return out;
+    }
+    // the list of the last extract, in rank order
+    std::vector<lom_regions_record> list()
+    {
+        size_t n = 0;
+        check(lom_regions_list(h_, nullptr, 0, &n));
+        std::vector<lom_regions_record> out(n);
+        check(lom_regions_list(h_, out.data(), out.size(), nullptr));
+        return out;
+    }
+    // (ix, iy) pairs of the list's centre cells (LOM_REGIONS_GOAL_CENTRE) or entry cells (LOM_REGIONS_GOAL_ENTRY)
+    std::vector<int32_t> goals(int which = LOM_REGIONS_GOAL_CENTRE)
+    {
+        size_t n = 0;
+        check(lom_regions_goals(h_, which, nullptr, 0, &n));
+        std::vector<int32_t> out(2 * n);
+        check(lom_regions_goals(h_, which, out.data(), n, nullptr));
+        return out;
+    }
+    // xy: n pairs in the grid's frame
+    std::vector<uint32_t> query(const float *xy, size_t n)
+    {
+        std::vector<uint32_t> out(n);
+        check(lom_regions_query(h_, xy, n, out.data()));
+        return out;
+    }
+    lom_regions_extract_stats stats() const
+    {
+        lom_regions_extract_stats s;
+        check(lom_regions_stats(h_, &s));
+        return s;
+    }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_regions_last_error(h_));
+        return rc;
+    }
+    lom_regions *h_ = nullptr;
+};
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)

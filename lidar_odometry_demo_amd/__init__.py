@@ -823,6 +823,12 @@ def navfieldParams(params):
     return _struct_from(capi.NavFieldParams, params, "navigation field parameters")
 
 
+def regionsParams(params):
+    """capi.RegionsParams from one, from a dict with its seven fields, or from a 7-tuple in the struct's order (kind, lo, hi,
+    max_cost, min_cells, rank, flags).  There are no defaults."""
+    return _struct_from(capi.RegionsParams, params, "region parameters")
+
+
 def classifyNeighbourhood(points, params, details=False, frontend=None):
     """The neighbourhood classifier alone (lom_classify_neighbourhood) on POINT_XYZIRT records whose `ring` is not read:
     (planar xyz, normals) in input order, and with details=True a third array of capi.NEIGHBOURHOOD_DETAIL records, one
@@ -1454,6 +1460,101 @@ def navfieldCellCosts(params):
     if rc != 0:
         raise LomError(int(rc), "navigation field cell costs: bad parameters")
     return out
+
+
+class RegionGrid(_Handle):
+    """Connected regions of a grid plane on the device (lom_regions_*, include/lidar_odometry_amd.h "frontier regions"):
+    extract() takes an int8 plane of shape (height, width) -- what OccupancyGrid.classify() writes -- and optionally a cost
+    plane and a NavField potential, labels the regions of the frontier cells (or of a byte range) with the least linear
+    index of each, and leaves a record per region and a ranked list; goals() gives the list's centre or entry cells in the
+    form NavField.solve() takes."""
+
+    _family = "regions"
+
+    def __init__(self, resolution, origin_xy, width, height, device=0):
+        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
+        self._create(C.byref(geo), int(device))
+        self.width, self.height = int(width), int(height)
+
+    def geometry(self):
+        geo = capi.OccupancyGeometry()
+        self._check(self._call("get_geometry", self._h, C.byref(geo)))
+        return geo.asdict()
+
+    def setOption(self, option, value):
+        self._check(self._call("set_option", self._h, int(option), int(value)))
+
+    def waitEvent(self, hip_event):
+        self._check(self._call("wait_event", self._h, hip_event))
+
+    def clear(self):
+        self._check(self._call("clear", self._h))
+
+    def _plane(self, a, dtype):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape != (self.height, self.width):
+            raise ValueError("expected an array of shape (height, width)")
+        return a
+
+    def extract(self, plane, params, cost=None, potential=None, device=False, hip_event=None):
+        """lom_regions_extract: host planes (int8, int8 or None, uint32 or None) -- or, with device=True,
+        lom_regions_extract_device: device pointers to planes in HBM, complete when `hip_event` is.  Returns
+        capi.RegionsSummary as a dict."""
+        p, sm = regionsParams(params), capi.RegionsSummary()
+        if device:
+            rc = self._call("extract_device", self._h, plane, cost, potential, hip_event, C.byref(p), C.byref(sm))
+        else:
+            plane, cost, potential = self._plane(plane, np.int8), self._plane(cost, np.int8), self._plane(potential, np.uint32)
+            rc = self._call("extract", self._h, None if plane is None else plane.ctypes.data, None if cost is None else cost.ctypes.data,
+                            None if potential is None else potential.ctypes.data, C.byref(p), C.byref(sm))
+        self._check(rc)
+        return sm.asdict()
+
+    def extractFromGrids(self, occupancy, rule, clearance, navfield, params):
+        """lom_regions_extract_from_grids: the planes an OccupancyGrid (by `rule`), a ClearanceGrid (or None) and a NavField
+        (or None) of this geometry left in HBM"""
+        p, sm = regionsParams(params), capi.RegionsSummary()
+        self._check(self._call("extract_from_grids", self._h, occupancy.handle, C.byref(occupancyRule(rule)),
+                               None if clearance is None else clearance.handle, None if navfield is None else navfield.handle,
+                               C.byref(p), C.byref(sm)))
+        return sm.asdict()
+
+    def labels(self):
+        """uint32 array of shape (height, width): the least linear index of a member's region, capi.REGIONS_NONE elsewhere"""
+        out = np.empty((self.height, self.width), np.uint32)
+        self._check(self._call("labels", self._h, out.ctypes.data, out.size))
+        return out
+
+    def list(self):
+        """the list of the last extract: an array of capi.REGIONS_RECORD in rank order"""
+        n = C.c_size_t()
+        self._check(self._call("list", self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, capi.REGIONS_RECORD)
+        self._check(self._call("list", self._h, out.ctypes.data, len(out), None))
+        return out
+
+    def goals(self, which=capi.REGIONS_GOAL_CENTRE):
+        """int32 array (n, 2): the centre cells (or, with capi.REGIONS_GOAL_ENTRY, the entry cells) of the list, in list order"""
+        n = C.c_size_t()
+        self._check(self._call("goals", self._h, int(which), None, 0, C.byref(n)))
+        out = np.zeros((n.value, 2), np.int32)
+        self._check(self._call("goals", self._h, int(which), out.ctypes.data, len(out), None))
+        return out
+
+    def query(self, xy):
+        """uint32 label of the cells of the points xy (n, 2), in the grid's frame; capi.REGIONS_NONE outside the grid"""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        out = np.empty(len(xy), np.uint32)
+        self._check(self._call("query", self._h, xy.ctypes.data, len(xy), out.ctypes.data))
+        return out
+
+    def stats(self):
+        """capi.RegionsExtractStats of the last extract as a dict: launches, waits, tiles"""
+        st = capi.RegionsExtractStats()
+        self._check(self._call("stats", self._h, C.byref(st)))
+        return st.asdict()
 
 
 class PoseGraph(_Handle):

@@ -375,6 +375,43 @@ NAV_CELLS, NAV_METRES = 0, 1
 NAV_OPT_TEST_INNER_CAP, NAV_OPT_TEST_BATCH, NAV_OPT_TEST_ALL_TILES = 1, 2, 3
 
 
+class RegionsParams(C.Structure):
+    """lom_regions_params"""
+    _fields_ = [("kind", C.c_int32), ("lo", C.c_int8), ("hi", C.c_int8), ("max_cost", C.c_int8), ("min_cells", C.c_uint32),
+                ("rank", C.c_int32), ("flags", C.c_uint32)]
+
+
+class RegionsSummary(C.Structure):
+    """lom_regions_summary"""
+    _fields_ = [("cells_member", C.c_uint64), ("regions", C.c_uint64), ("regions_recorded", C.c_uint64),
+                ("regions_listed", C.c_uint64), ("largest_cells", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class RegionsExtractStats(C.Structure):
+    """lom_regions_extract_stats"""
+    _fields_ = [("launches", C.c_uint64), ("waits", C.c_uint64), ("tiles", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# lom_regions_record, 48 bytes
+REGIONS_RECORD = np.dtype([("label", "<u4"), ("cells", "<u4"), ("sum_x", "<u8"), ("sum_y", "<u8"), ("min_x", "<u2"), ("min_y", "<u2"),
+                           ("max_x", "<u2"), ("max_y", "<u2"), ("centroid_x", "<u2"), ("centroid_y", "<u2"), ("centre_x", "<u2"),
+                           ("centre_y", "<u2"), ("entry_x", "<u2"), ("entry_y", "<u2"), ("entry_potential", "<u4")])
+assert C.sizeof(RegionsParams) == 20 and C.sizeof(RegionsSummary) == 40 and C.sizeof(RegionsExtractStats) == 24
+assert REGIONS_RECORD.itemsize == 48
+REGIONS_NONE = 0xFFFFFFFF
+REGIONS_BYTES, REGIONS_FRONTIER = 0, 1
+REGIONS_NEIGHBOURS_8, REGIONS_EDGE_UNKNOWN, REGIONS_CONNECT_4 = 1, 2, 4
+REGIONS_RANK_LABEL, REGIONS_RANK_CELLS, REGIONS_RANK_POTENTIAL = 0, 1, 2
+REGIONS_GOAL_CENTRE, REGIONS_GOAL_ENTRY = 0, 1
+REGIONS_OPT_MAX_REGIONS, REGIONS_OPT_TEST_TILE_ROWS, REGIONS_OPT_TEST_NO_TILES, REGIONS_OPT_TEST_NO_WAVE_MERGE = 1, 2, 3, 4
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -470,6 +507,10 @@ EXPORTED = [
     "lom_navfield_set_option", "lom_navfield_solve", "lom_navfield_solve_device", "lom_navfield_solve_from_clearance",
     "lom_navfield_potential", "lom_navfield_potential_device", "lom_navfield_paths", "lom_navfield_query",
     "lom_navfield_cell_costs", "lom_navfield_stats",
+    "lom_regions_create", "lom_regions_destroy", "lom_regions_last_error", "lom_regions_clear", "lom_regions_get_geometry",
+    "lom_regions_stream", "lom_regions_device", "lom_regions_wait_event", "lom_regions_set_option", "lom_regions_extract",
+    "lom_regions_extract_device", "lom_regions_extract_from_grids", "lom_regions_labels", "lom_regions_labels_device",
+    "lom_regions_list", "lom_regions_goals", "lom_regions_query", "lom_regions_stats",
 ]
 # ... and the one it declares through a function type (the "scan archive and map assembly" section)
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
@@ -911,6 +952,28 @@ def lib():
     L.lom_navfield_query.argtypes = [vp, vp, C.c_size_t, vp]
     L.lom_navfield_cell_costs.argtypes = [C.POINTER(NavFieldParams), vp]
     L.lom_navfield_stats.argtypes = [vp, C.POINTER(NavFieldSolveStats)]
+    L.lom_regions_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
+    L.lom_regions_destroy.argtypes = [vp]
+    L.lom_regions_destroy.restype = None
+    L.lom_regions_last_error.argtypes = [vp]
+    L.lom_regions_last_error.restype = C.c_char_p
+    L.lom_regions_clear.argtypes = [vp]
+    L.lom_regions_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
+    L.lom_regions_stream.argtypes = [vp]
+    L.lom_regions_stream.restype = vp
+    L.lom_regions_device.argtypes = [vp]
+    L.lom_regions_wait_event.argtypes = [vp, vp]
+    L.lom_regions_set_option.argtypes = [vp, C.c_int, C.c_int64]
+    L.lom_regions_extract.argtypes = [vp, vp, vp, vp, C.POINTER(RegionsParams), C.POINTER(RegionsSummary)]
+    L.lom_regions_extract_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(RegionsParams), C.POINTER(RegionsSummary)]
+    L.lom_regions_extract_from_grids.argtypes = [vp, vp, C.POINTER(OccupancyRule), vp, vp, C.POINTER(RegionsParams),
+                                                 C.POINTER(RegionsSummary)]
+    L.lom_regions_labels.argtypes = [vp, vp, C.c_size_t]
+    L.lom_regions_labels_device.argtypes = [vp, C.POINTER(vp)]
+    L.lom_regions_list.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lom_regions_goals.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lom_regions_query.argtypes = [vp, vp, C.c_size_t, vp]
+    L.lom_regions_stats.argtypes = [vp, C.POINTER(RegionsExtractStats)]
     _lib = L
     return L
 
