@@ -1911,6 +1911,154 @@ int lom_regions_query(lom_regions *r, const float *xy, size_t n, uint32_t *out);
 /* the launches and waits of the last extract (zeros before the first) */
 int lom_regions_stats(const lom_regions *r, lom_regions_extract_stats *out);
 
+/* ---- visibility grid: rays cast from candidate viewpoints, goals picked by what they would see (not in the reference) ----
+ * The region grid ranks frontiers by label, size or travel cost; none of these says what a robot would see from a goal.
+ * This handle family casts B beams over a grid plane from each of K viewpoints at once and counts, per viewpoint, the
+ * distinct cells the beams see, by class -- the unknown ones are the expected gain of driving there -- keeps, on request,
+ * a simulated planar scan per viewpoint (end distance and end reason per beam) and the set of unknown cells each viewpoint
+ * sees, and selects next-best views from those sets greedily, gain against travel cost.  Nothing is launched unless a
+ * caller creates a visibility grid.  The definition, operation by operation (tests/visibility_ref.py restates it on
+ * Python integers; everything is an integer, so every comparison is exact):
+ *
+ * Grid.  lom_occupancy_geometry, reused, with the region grid's rules: row-major with y as the row.  r > 0 and finite, a
+ * finite origin, 1 <= width, height <= 8192; anything else is LOM_ERR_ARG.
+ *
+ * Plane.  A full-grid int8 plane; a cell with v < 0 is unknown, with 0 <= v < block_min free, with v >= block_min
+ * blocking.  lom_occupancy_classify's plane works with block_min = 100, lom_clearance_cost's with block_min = 99.
+ * lom_visibility_params: 4 <= beams <= 8192 (B); range_cells <= 254 (R); 1 <= block_min <= 100; unknown_depth <= 65535
+ * (D; 0: no limit); flags of LOM_VIS_KEEP_WINDOWS | LOM_VIS_KEEP_BEAMS only; anything else is LOM_ERR_ARG.
+ *  1. Direction table.  Beam b has the direction (dx, dy) = (lround(cos(2 pi b / B) * 32768), lround(sin(2 pi b / B) *
+ *     32768)), computed on the host in f64; lom_visibility_table gives the int32 pairs.
+ *  2. Walk.  From the centre of the start cell (x0, y0).  ax = |dx|, ay = |dy|, sx, sy the signs (a zero component never
+ *     steps), i, j the steps taken so far along x and y.  The next crossing: (2 i + 1) * ay against (2 j + 1) * ax, both
+ *     below 2^24.  Less: x steps.  Greater: y steps.  Equal: the ray passes exactly through a corner and both step at
+ *     once; the ray then ends at the current cell with reason LOM_VIS_END_CORNER when both side cells (x + sx, y) and
+ *     (x, y + sy) are blocking (a side cell outside the grid does not block); side cells are never marked seen.
+ *  3. At the cell stepped to, with step counts (ni, nj), in this order: outside the grid: end LOM_VIS_END_EDGE at the
+ *     previous cell; ni^2 + nj^2 > R^2: end LOM_VIS_END_RANGE at the previous cell; the cell is marked seen; v >=
+ *     block_min: end LOM_VIS_END_HIT at this cell; v < 0: it counts for this ray, and when D > 0 and the count reaches D
+ *     the ray ends LOM_VIS_END_UNKNOWN at this cell.  The start cell is marked seen once, is tested for nothing and counts
+ *     for no ray's D.
+ *  4. Viewpoints.  K int32 (ix, iy) pairs, in the form lom_regions_goals returns, 0 <= K <= 2^20.  A viewpoint outside
+ *     the grid or on a blocking cell is invalid: valid = 0, every count 0, every beam 0 (d2 = 0, LOM_VIS_END_INVALID), an
+ *     empty window.  Duplicates are cast independently.
+ *  5. Record.  lom_visibility_record, 32 bytes, per viewpoint: ix, iy; valid; seen, the distinct cells marked; unknown,
+ *     free, blocked, those cells by class (they sum to seen); hits, the beams that ended LOM_VIS_END_HIT.
+ *  6. Beams (LOM_VIS_KEEP_BEAMS).  One u32 per viewpoint and beam: d2 = i^2 + j^2 of the end cell in the low 24 bits, the
+ *     reason in the high 8.
+ *  7. Summary.  viewpoints; valid; unknown_total, the sum of unknown over the valid ones; unknown_max, the greatest
+ *     unknown among them, and unknown_argmax, the least index that has it (both 0 when none is valid).
+ *  8. Windows (LOM_VIS_KEEP_WINDOWS).  W_k, the unknown cells viewpoint k sees, as a bitmap of 2R + 1 rows of
+ *     ceil((2R + 1) / 32) u32 around the start cell: cell (ix, iy) is bit (ix - x0 + R) & 31 of word (ix - x0 + R) >> 5
+ *     of row iy - y0 + R.  The window holds the whole disc; what lies outside the grid reads 0.
+ *  9. Selection.  Needs the last cast to have kept its windows (LOM_ERR_STATE otherwise).  lom_visibility_select_params:
+ *     1 <= n <= 1024; 1 <= gain_weight <= 4096; cost_shift <= 31; min_gain >= 1.  cost: K u32, optional (none: every cost
+ *     is 0); a cost of LOM_NAV_UNREACHED excludes the viewpoint.  C, the covered set, is empty at the start of every
+ *     select.  Each round: g_k = |W_k \ C| for every valid, not yet picked, not excluded k; s_k = g_k * gain_weight -
+ *     (cost_k >> cost_shift) as int64; the winner is the greatest s_k among those with g_k >= min_gain, ties to the least
+ *     k; without one the selection ends; else C |= W_winner.  Output: up to n lom_visibility_pick (k, gain, score) in the
+ *     order picked, and their count.  -(2^32 - 1) <= s <= 2^30, so (s + 2^32) << 20 | (2^20 - 1 - k) orders the candidates
+ *     as one unsigned 64-bit maximum.
+ * After create or lom_visibility_clear there is no viewpoint: an empty summary, no records, no windows.
+ *
+ * The result is a pure function of the plane, the parameters and the viewpoints (and the costs): it does not depend on
+ * the order in which beams, waves or workgroups run or on the test switches below.
+ *
+ * lom_visibility_cast takes a host plane of width * height bytes; _cast_device a plane in HBM that is complete when
+ * hip_event_or_null is (NULL: now); _cast_from_occupancy takes lom_occupancy_classify_device's plane and orders the two
+ * streams by events in both directions -- a grid whose resolution, origin, width or height differ bit for bit, or that
+ * lives on another device, is LOM_ERR_ARG before any launch.  The handle keeps a copy of the plane.  The viewpoints are
+ * host memory in every form.  _select takes host costs; _select_from_navfield reads them on the device from
+ * lom_navfield_potential_device at the viewpoints' cells.  Every argument is validated and every allocation made before
+ * the first launch; a refused call changes nothing and zeroes the summary (the count of a select).  A cast is one host
+ * wait and a select is one host wait, whatever n.  Every call returns with its work done.  Calls on one handle are the
+ * caller's to serialise.  The error text is the handle's (lom_visibility_last_error). */
+typedef struct lom_visibility lom_visibility;
+typedef struct {
+    uint32_t beams;         /* B, 4 .. 8192 */
+    uint32_t range_cells;   /* R, 0 .. 254 */
+    int32_t block_min;      /* the least blocking value, 1 .. 100 */
+    uint32_t unknown_depth; /* D, 0 .. 65535; 0: no limit */
+    uint32_t flags;         /* LOM_VIS_KEEP_WINDOWS | LOM_VIS_KEEP_BEAMS */
+} lom_visibility_params;
+typedef struct {
+    int32_t ix, iy;                       /* offset 0, 4 */
+    uint32_t valid;                       /* 8 */
+    uint32_t seen;                        /* 12 */
+    uint32_t unknown, free, blocked;      /* 16, 20, 24 */
+    uint32_t hits;                        /* 28 */
+} lom_visibility_record;
+typedef struct {
+    uint64_t viewpoints, valid, unknown_total, unknown_max, unknown_argmax;
+} lom_visibility_summary;
+typedef struct {
+    uint32_t n;           /* the most entries picked, 1 .. 1024 */
+    uint32_t gain_weight; /* 1 .. 4096 */
+    uint32_t cost_shift;  /* 0 .. 31 */
+    uint32_t min_gain;    /* >= 1 */
+} lom_visibility_select_params;
+typedef struct {
+    uint32_t k;    /* the viewpoint's index */
+    uint32_t gain; /* g at the round it was picked */
+    int64_t score; /* s at that round */
+} lom_visibility_pick;
+typedef struct {
+    uint64_t launches, waits; /* kernel launches of the last cast or select, and the host's waits for them */
+} lom_visibility_call_stats;
+enum { LOM_VIS_KEEP_WINDOWS = 1, LOM_VIS_KEEP_BEAMS = 2 };
+enum {
+    LOM_VIS_END_INVALID = 0,
+    LOM_VIS_END_EDGE = 1,
+    LOM_VIS_END_RANGE = 2,
+    LOM_VIS_END_HIT = 3,
+    LOM_VIS_END_UNKNOWN = 4,
+    LOM_VIS_END_CORNER = 5
+};
+enum {
+    LOM_VIS_OPT_TEST_NO_LDS = 1,         /* 1: the seen bits go straight to the window in HBM; 0 or < 0: the default, LDS */
+    LOM_VIS_OPT_TEST_WAVES = 2,          /* waves of a workgroup of k_vis_cast: 1 or 4; <= 0: the default.  Test switches:
+                                            the bytes are the same. */
+    LOM_VIS_OPT_MAX_WINDOW_BYTES = 3     /* a cast whose windows in HBM (under LOM_VIS_KEEP_WINDOWS, or under
+                                            LOM_VIS_OPT_TEST_NO_LDS) would exceed this is LOM_ERR_ARG before any launch; <= 0:
+                                            the default, 256 MiB */
+};
+int lom_visibility_create(const lom_occupancy_geometry *geometry, int device, lom_visibility **out);
+void lom_visibility_destroy(lom_visibility *v);
+const char *lom_visibility_last_error(const lom_visibility *v); /* v == NULL: why the last create on this thread failed */
+int lom_visibility_clear(lom_visibility *v);                    /* no viewpoint, an empty summary */
+int lom_visibility_get_geometry(const lom_visibility *v, lom_occupancy_geometry *out);
+void *lom_visibility_stream(lom_visibility *v); /* hipStream_t */
+int lom_visibility_device(const lom_visibility *v);
+int lom_visibility_wait_event(lom_visibility *v, void *hip_event);
+int lom_visibility_set_option(lom_visibility *v, int option, int64_t value);
+/* step 1: 2 * beams int32 go to `out`; LOM_ERR_ARG for beams outside 4 .. 8192.  Needs no handle and no device. */
+int lom_visibility_table(uint32_t beams, int32_t *out);
+/* plane: width * height int8; viewpoints: k int32 (ix, iy) pairs in host memory (may be NULL with k 0) */
+int lom_visibility_cast(lom_visibility *v, const int8_t *plane, const int32_t *viewpoints, size_t k,
+                        const lom_visibility_params *params, lom_visibility_summary *summary_or_null);
+int lom_visibility_cast_device(lom_visibility *v, const int8_t *d_plane, void *hip_event_or_null, const int32_t *viewpoints,
+                               size_t k, const lom_visibility_params *params, lom_visibility_summary *summary_or_null);
+int lom_visibility_cast_from_occupancy(lom_visibility *v, lom_occupancy *occupancy, const lom_occupancy_rule *rule,
+                                       const int32_t *viewpoints, size_t k, const lom_visibility_params *params,
+                                       lom_visibility_summary *summary_or_null);
+/* step 5: at most `cap` records of the last cast go to `out` (may be NULL with cap 0); *count_or_null: K */
+int lom_visibility_records(lom_visibility *v, lom_visibility_record *out, size_t cap, size_t *count_or_null);
+/* step 6: at most `cap` u32 of the K * B of the last cast go to `out`, viewpoint by viewpoint; LOM_ERR_STATE when the last
+ * cast did not keep them */
+int lom_visibility_beams(lom_visibility *v, uint32_t *out, size_t cap);
+/* step 8, left in HBM: K windows of *words_per_window_or_null u32 each, valid until the next cast or clear on the handle;
+ * LOM_ERR_STATE when the last cast did not keep them */
+int lom_visibility_windows_device(lom_visibility *v, const uint32_t **d_out, size_t *words_per_window_or_null);
+/* the same, read back: at most `cap` u32 of the K windows go to `out` (may be NULL with cap 0), window by window */
+int lom_visibility_windows(lom_visibility *v, uint32_t *out, size_t cap, size_t *words_per_window_or_null);
+/* step 9: cost_or_null: K u32 in host memory; out: select->n entries; *picked: the entries written */
+int lom_visibility_select(lom_visibility *v, const lom_visibility_select_params *select, const uint32_t *cost_or_null,
+                          lom_visibility_pick *out, size_t *picked);
+int lom_visibility_select_from_navfield(lom_visibility *v, lom_navfield *navfield, const lom_visibility_select_params *select,
+                                        lom_visibility_pick *out, size_t *picked);
+/* the launches and waits of the last cast or select (zeros before the first) */
+int lom_visibility_stats(const lom_visibility *v, lom_visibility_call_stats *out);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;

@@ -1412,6 +1412,151 @@ private:
     lom_regions *h_ = nullptr;
 };
 
+// ---- VisibilityGrid (not in the reference) ----------------------------------------------
+// Rays cast over a grid plane from many viewpoints at once: cast() takes an int8 plane (row-major with y as the row, what
+// OccupancyGrid::classify() or ClearanceGrid::cost() writes) and int32 (ix, iy) viewpoints, what RegionGrid::goals()
+// returns, and leaves a record per viewpoint; beams() gives the simulated scans, windows() the unknown cells each
+// viewpoint sees, select() the greedy next-best views.  Definitions: lidar_odometry_amd.h ("visibility grid").
+using VisibilityParams = lom_visibility_params;  // {beams, range_cells, block_min, unknown_depth, flags}
+using VisibilitySummary = lom_visibility_summary;
+using VisibilityRecord = lom_visibility_record;
+using VisibilitySelectParams = lom_visibility_select_params;  // {n, gain_weight, cost_shift, min_gain}
+using VisibilityPick = lom_visibility_pick;
+
+inline VisibilityParams visibilityParams(uint32_t beams, uint32_t range_cells, int32_t block_min = 100, uint32_t unknown_depth = 0, uint32_t flags = 0)
+{
+    return VisibilityParams{beams, range_cells, block_min, unknown_depth, flags};
+}
+
+inline std::vector<int32_t> visibilityTable(uint32_t beams)
+{
+    std::vector<int32_t> out(2 * (size_t)(beams <= 8192 ? beams : 0));
+    const int rc = lom_visibility_table(beams, out.data());
+    if (rc != LOM_OK) throw Error(rc, "visibility table: 4 <= beams <= 8192");
+    return out;
+}
+
+class VisibilityGrid {
+public:
+    explicit VisibilityGrid(const lom_occupancy_geometry &geometry, int device = 0)
+    {
+        const int rc = lom_visibility_create(&geometry, device, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_visibility_last_error(nullptr));
+    }
+    ~VisibilityGrid() { lom_visibility_destroy(h_); }
+    VisibilityGrid(const VisibilityGrid &) = delete;
+    VisibilityGrid &operator=(const VisibilityGrid &) = delete;
+    lom_visibility *handle() const { return h_; }
+    lom_occupancy_geometry geometry() const
+    {
+        lom_occupancy_geometry g;
+        check(lom_visibility_get_geometry(h_, &g));
+        return g;
+    }
+    size_t size() const
+    {
+        const lom_occupancy_geometry g = geometry();
+        return (size_t)g.width * g.height;
+    }
+    int device() const { return lom_visibility_device(h_); }
+    void *stream() const { return lom_visibility_stream(h_); }
+    void waitEvent(void *hip_event) { check(lom_visibility_wait_event(h_, hip_event)); }
+    void clear() { check(lom_visibility_clear(h_)); }
+    void setOption(int option, int64_t value) { check(lom_visibility_set_option(h_, option, value)); }
+    // a host plane of size() cells; viewpoints: k (ix, iy) pairs
+    lom_visibility_summary cast(const int8_t *plane, const int32_t *viewpoints, size_t k, const lom_visibility_params &params)
+    {
+        lom_visibility_summary s;
+        check(lom_visibility_cast(h_, plane, viewpoints, k, &params, &s));
+        beams_ = params.beams;
+        return s;
+    }
+    // a plane in HBM, complete when hip_event is (NULL: now)
+    lom_visibility_summary castDevice(const int8_t *d_plane, void *hip_event, const int32_t *viewpoints, size_t k,
+                                      const lom_visibility_params &params)
+    {
+        lom_visibility_summary s;
+        check(lom_visibility_cast_device(h_, d_plane, hip_event, viewpoints, k, &params, &s));
+        beams_ = params.beams;
+        return s;
+    }
+    // the plane an OccupancyGrid of this geometry classifies by `rule`, in HBM
+    lom_visibility_summary castFromOccupancy(OccupancyGrid &occupancy, const lom_occupancy_rule &rule, const int32_t *viewpoints, size_t k,
+                                             const lom_visibility_params &params)
+    {
+        lom_visibility_summary s;
+        check(lom_visibility_cast_from_occupancy(h_, occupancy.handle(), &rule, viewpoints, k, &params, &s));
+        beams_ = params.beams;
+        return s;
+    }
+    std::vector<lom_visibility_record> records()
+    {
+        size_t n = 0;
+        check(lom_visibility_records(h_, nullptr, 0, &n));
+        std::vector<lom_visibility_record> out(n);
+        check(lom_visibility_records(h_, out.data(), out.size(), nullptr));
+        return out;
+    }
+    // K * B words under LOM_VIS_KEEP_BEAMS: d2 in the low 24 bits, the end reason in the high 8
+    std::vector<uint32_t> beams()
+    {
+        size_t n = 0;
+        check(lom_visibility_records(h_, nullptr, 0, &n));
+        std::vector<uint32_t> out(n * beams_);
+        check(lom_visibility_beams(h_, out.data(), out.size()));
+        return out;
+    }
+    // the K windows under LOM_VIS_KEEP_WINDOWS, read back; *words_per_window: the words of each
+    std::vector<uint32_t> windows(size_t *words_per_window = nullptr)
+    {
+        size_t n = 0, words = 0;
+        check(lom_visibility_records(h_, nullptr, 0, &n));
+        check(lom_visibility_windows(h_, nullptr, 0, &words));
+        std::vector<uint32_t> out(n * words);
+        check(lom_visibility_windows(h_, out.data(), out.size(), nullptr));
+        if (words_per_window) *words_per_window = words;
+        return out;
+    }
+    const uint32_t *windowsDevice(size_t *words_per_window = nullptr)
+    {
+        const uint32_t *d = nullptr;
+        check(lom_visibility_windows_device(h_, &d, words_per_window));
+        return d;
+    }
+    // cost: K u32 or NULL
+    std::vector<lom_visibility_pick> select(const lom_visibility_select_params &s, const uint32_t *cost = nullptr)
+    {
+        std::vector<lom_visibility_pick> out(s.n ? s.n : 1);
+        size_t n = 0;
+        check(lom_visibility_select(h_, &s, cost, out.data(), &n));
+        out.resize(n);
+        return out;
+    }
+    std::vector<lom_visibility_pick> selectFromNavfield(NavField &navfield, const lom_visibility_select_params &s)
+    {
+        std::vector<lom_visibility_pick> out(s.n ? s.n : 1);
+        size_t n = 0;
+        check(lom_visibility_select_from_navfield(h_, navfield.handle(), &s, out.data(), &n));
+        out.resize(n);
+        return out;
+    }
+    lom_visibility_call_stats stats() const
+    {
+        lom_visibility_call_stats s;
+        check(lom_visibility_stats(h_, &s));
+        return s;
+    }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_visibility_last_error(h_));
+        return rc;
+    }
+    lom_visibility *h_ = nullptr;
+    uint32_t beams_ = 0;
+};
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)

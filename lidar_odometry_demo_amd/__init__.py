@@ -829,6 +829,18 @@ def regionsParams(params):
     return _struct_from(capi.RegionsParams, params, "region parameters")
 
 
+def visibilityParams(params):
+    """capi.VisibilityParams from one, from a dict with its five fields, or from a 5-tuple in the struct's order (beams,
+    range_cells, block_min, unknown_depth, flags).  There are no defaults."""
+    return _struct_from(capi.VisibilityParams, params, "visibility parameters")
+
+
+def visibilitySelectParams(params):
+    """capi.VisibilitySelectParams from one, from a dict with its four fields, or from a 4-tuple in the struct's order (n,
+    gain_weight, cost_shift, min_gain).  There are no defaults."""
+    return _struct_from(capi.VisibilitySelectParams, params, "visibility select parameters")
+
+
 def classifyNeighbourhood(points, params, details=False, frontend=None):
     """The neighbourhood classifier alone (lom_classify_neighbourhood) on POINT_XYZIRT records whose `ring` is not read:
     (planar xyz, normals) in input order, and with details=True a third array of capi.NEIGHBOURHOOD_DETAIL records, one
@@ -1555,6 +1567,120 @@ class RegionGrid(_Handle):
         st = capi.RegionsExtractStats()
         self._check(self._call("stats", self._h, C.byref(st)))
         return st.asdict()
+
+
+class VisibilityGrid(_Handle):
+    """Rays cast over a grid plane from many viewpoints at once (lom_visibility_*, include/lidar_odometry_amd.h "visibility
+    grid"): cast() takes an int8 plane of shape (height, width) -- what OccupancyGrid.classify() or ClearanceGrid.cost()
+    writes -- and (K, 2) int32 viewpoints (ix, iy), what RegionGrid.goals() returns, and leaves a record per viewpoint: the
+    distinct cells its beams see, by class.  beams() gives the simulated scans, windows() the unknown cells each viewpoint
+    sees, select() the greedy next-best views, gain against travel cost."""
+
+    _family = "visibility"
+
+    def __init__(self, resolution, origin_xy, width, height, device=0):
+        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
+        self._create(C.byref(geo), int(device))
+        self.width, self.height = int(width), int(height)
+        self._beams = self._range = 0
+
+    def geometry(self):
+        geo = capi.OccupancyGeometry()
+        self._check(self._call("get_geometry", self._h, C.byref(geo)))
+        return geo.asdict()
+
+    def setOption(self, option, value):
+        self._check(self._call("set_option", self._h, int(option), int(value)))
+
+    def waitEvent(self, hip_event):
+        self._check(self._call("wait_event", self._h, hip_event))
+
+    def clear(self):
+        self._check(self._call("clear", self._h))
+
+    def _cast(self, name, head, viewpoints, params):
+        p, sm = visibilityParams(params), capi.VisibilitySummary()
+        vp = np.ascontiguousarray(viewpoints, np.int32).reshape(-1, 2)
+        self._check(self._call(name, self._h, *head, vp.ctypes.data if len(vp) else None, len(vp), C.byref(p), C.byref(sm)))
+        self._beams, self._range = int(p.beams), int(p.range_cells)
+        return sm.asdict()
+
+    def cast(self, plane, viewpoints, params, device=False, hip_event=None):
+        """lom_visibility_cast: a host plane -- or, with device=True, lom_visibility_cast_device: `plane` is a device pointer
+        to a plane in HBM, complete when `hip_event` is.  Returns capi.VisibilitySummary as a dict."""
+        if device:
+            return self._cast("cast_device", (plane, hip_event), viewpoints, params)
+        plane = np.ascontiguousarray(plane, np.int8)
+        if plane.shape != (self.height, self.width):
+            raise ValueError("expected an int8 array of shape (height, width)")
+        return self._cast("cast", (plane.ctypes.data,), viewpoints, params)
+
+    def castFromOccupancy(self, occupancy, rule, viewpoints, params):
+        """lom_visibility_cast_from_occupancy: the plane an OccupancyGrid of this geometry classifies by `rule`, in HBM"""
+        return self._cast("cast_from_occupancy", (occupancy.handle, C.byref(occupancyRule(rule))), viewpoints, params)
+
+    def records(self):
+        """the records of the last cast: an array of capi.VISIBILITY_RECORD, one per viewpoint"""
+        n = C.c_size_t()
+        self._check(self._call("records", self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, capi.VISIBILITY_RECORD)
+        self._check(self._call("records", self._h, out.ctypes.data, len(out), None))
+        return out
+
+    def beams(self):
+        """uint32 array (K, B) of the last cast under capi.VIS_KEEP_BEAMS: d2 in the low 24 bits, the end reason in the high 8"""
+        n = C.c_size_t()
+        self._check(self._call("records", self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, self._beams), np.uint32)
+        self._check(self._call("beams", self._h, out.ctypes.data, out.size))
+        return out
+
+    def windowsDevice(self):
+        """(device pointer, words per window) of the last cast's windows under capi.VIS_KEEP_WINDOWS"""
+        d, words = C.c_void_p(), C.c_size_t()
+        self._check(self._call("windows_device", self._h, C.byref(d), C.byref(words)))
+        return d.value, int(words.value)
+
+    def windows(self):
+        """uint32 array (K, 2R + 1, words per row): the unknown cells each viewpoint of the last cast sees, read back"""
+        n, words = C.c_size_t(), C.c_size_t()
+        self._check(self._call("records", self._h, None, 0, C.byref(n)))
+        self._check(self._call("windows", self._h, None, 0, C.byref(words)))
+        side = 2 * self._range + 1
+        out = np.zeros((n.value, side, words.value // side), np.uint32)
+        self._check(self._call("windows", self._h, out.ctypes.data, out.size, None))
+        return out
+
+    def _select(self, name, head, select):
+        s = visibilitySelectParams(select)
+        out, n = np.zeros(max(int(s.n), 1), capi.VISIBILITY_PICK), C.c_size_t()
+        self._check(self._call(name, self._h, *head, out.ctypes.data, C.byref(n)))
+        return out[:n.value].copy()
+
+    def select(self, select, cost=None):
+        """lom_visibility_select: the picks (capi.VISIBILITY_PICK: k, gain, score) in the order picked; cost: K uint32 or None"""
+        if cost is not None:
+            cost = np.ascontiguousarray(cost, np.uint32)
+        return self._select("select", (C.byref(visibilitySelectParams(select)), None if cost is None else cost.ctypes.data), select)
+
+    def selectFromNavfield(self, navfield, select):
+        """lom_visibility_select_from_navfield: the costs are a NavField's potential at the viewpoints' cells, read in HBM"""
+        return self._select("select_from_navfield", (navfield.handle, C.byref(visibilitySelectParams(select))), select)
+
+    def stats(self):
+        """capi.VisibilityCallStats of the last cast or select as a dict: launches, waits"""
+        st = capi.VisibilityCallStats()
+        self._check(self._call("stats", self._h, C.byref(st)))
+        return st.asdict()
+
+
+def visibilityTable(beams):
+    """lom_visibility_table: the int32 (dx, dy) of each of `beams` beams, shape (beams, 2); needs no device"""
+    out = np.zeros((max(int(beams), 0), 2), np.int32)
+    rc = capi.lib().lom_visibility_table(int(beams) & 0xFFFFFFFF, out.ctypes.data)
+    if rc != 0:
+        raise LomError(int(rc), "visibility table: 4 <= beams <= 8192")
+    return out
 
 
 class PoseGraph(_Handle):

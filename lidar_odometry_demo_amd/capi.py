@@ -412,6 +412,45 @@ REGIONS_GOAL_CENTRE, REGIONS_GOAL_ENTRY = 0, 1
 REGIONS_OPT_MAX_REGIONS, REGIONS_OPT_TEST_TILE_ROWS, REGIONS_OPT_TEST_NO_TILES, REGIONS_OPT_TEST_NO_WAVE_MERGE = 1, 2, 3, 4
 
 
+class VisibilityParams(C.Structure):
+    """lom_visibility_params"""
+    _fields_ = [("beams", C.c_uint32), ("range_cells", C.c_uint32), ("block_min", C.c_int32), ("unknown_depth", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class VisibilitySummary(C.Structure):
+    """lom_visibility_summary"""
+    _fields_ = [("viewpoints", C.c_uint64), ("valid", C.c_uint64), ("unknown_total", C.c_uint64), ("unknown_max", C.c_uint64),
+                ("unknown_argmax", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class VisibilitySelectParams(C.Structure):
+    """lom_visibility_select_params"""
+    _fields_ = [("n", C.c_uint32), ("gain_weight", C.c_uint32), ("cost_shift", C.c_uint32), ("min_gain", C.c_uint32)]
+
+
+class VisibilityCallStats(C.Structure):
+    """lom_visibility_call_stats"""
+    _fields_ = [("launches", C.c_uint64), ("waits", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# lom_visibility_record, 32 bytes, and lom_visibility_pick, 16 bytes
+VISIBILITY_RECORD = np.dtype([("ix", "<i4"), ("iy", "<i4"), ("valid", "<u4"), ("seen", "<u4"), ("unknown", "<u4"), ("free", "<u4"),
+                              ("blocked", "<u4"), ("hits", "<u4")])
+VISIBILITY_PICK = np.dtype([("k", "<u4"), ("gain", "<u4"), ("score", "<i8")])
+assert C.sizeof(VisibilityParams) == 20 and C.sizeof(VisibilitySummary) == 40 and C.sizeof(VisibilitySelectParams) == 16
+assert C.sizeof(VisibilityCallStats) == 16 and VISIBILITY_RECORD.itemsize == 32 and VISIBILITY_PICK.itemsize == 16
+VIS_KEEP_WINDOWS, VIS_KEEP_BEAMS = 1, 2
+VIS_END_INVALID, VIS_END_EDGE, VIS_END_RANGE, VIS_END_HIT, VIS_END_UNKNOWN, VIS_END_CORNER = 0, 1, 2, 3, 4, 5
+VIS_OPT_TEST_NO_LDS, VIS_OPT_TEST_WAVES, VIS_OPT_MAX_WINDOW_BYTES = 1, 2, 3
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -511,6 +550,11 @@ EXPORTED = [
     "lom_regions_stream", "lom_regions_device", "lom_regions_wait_event", "lom_regions_set_option", "lom_regions_extract",
     "lom_regions_extract_device", "lom_regions_extract_from_grids", "lom_regions_labels", "lom_regions_labels_device",
     "lom_regions_list", "lom_regions_goals", "lom_regions_query", "lom_regions_stats",
+    "lom_visibility_create", "lom_visibility_destroy", "lom_visibility_last_error", "lom_visibility_clear",
+    "lom_visibility_get_geometry", "lom_visibility_stream", "lom_visibility_device", "lom_visibility_wait_event",
+    "lom_visibility_set_option", "lom_visibility_table", "lom_visibility_cast", "lom_visibility_cast_device",
+    "lom_visibility_cast_from_occupancy", "lom_visibility_records", "lom_visibility_beams", "lom_visibility_windows_device",
+    "lom_visibility_windows",    "lom_visibility_select", "lom_visibility_select_from_navfield", "lom_visibility_stats",
 ]
 # ... and the one it declares through a function type (the "scan archive and map assembly" section)
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
@@ -974,6 +1018,30 @@ def lib():
     L.lom_regions_goals.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.lom_regions_query.argtypes = [vp, vp, C.c_size_t, vp]
     L.lom_regions_stats.argtypes = [vp, C.POINTER(RegionsExtractStats)]
+    L.lom_visibility_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
+    L.lom_visibility_destroy.argtypes = [vp]
+    L.lom_visibility_destroy.restype = None
+    L.lom_visibility_last_error.argtypes = [vp]
+    L.lom_visibility_last_error.restype = C.c_char_p
+    L.lom_visibility_clear.argtypes = [vp]
+    L.lom_visibility_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
+    L.lom_visibility_stream.argtypes = [vp]
+    L.lom_visibility_stream.restype = vp
+    L.lom_visibility_device.argtypes = [vp]
+    L.lom_visibility_wait_event.argtypes = [vp, vp]
+    L.lom_visibility_set_option.argtypes = [vp, C.c_int, C.c_int64]
+    L.lom_visibility_table.argtypes = [C.c_uint32, vp]
+    L.lom_visibility_cast.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(VisibilityParams), C.POINTER(VisibilitySummary)]
+    L.lom_visibility_cast_device.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(VisibilityParams), C.POINTER(VisibilitySummary)]
+    L.lom_visibility_cast_from_occupancy.argtypes = [vp, vp, C.POINTER(OccupancyRule), vp, C.c_size_t, C.POINTER(VisibilityParams),
+                                                     C.POINTER(VisibilitySummary)]
+    L.lom_visibility_records.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lom_visibility_beams.argtypes = [vp, vp, C.c_size_t]
+    L.lom_visibility_windows_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.lom_visibility_windows.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lom_visibility_select.argtypes = [vp, C.POINTER(VisibilitySelectParams), vp, vp, C.POINTER(C.c_size_t)]
+    L.lom_visibility_select_from_navfield.argtypes = [vp, vp, C.POINTER(VisibilitySelectParams), vp, C.POINTER(C.c_size_t)]
+    L.lom_visibility_stats.argtypes = [vp, C.POINTER(VisibilityCallStats)]
     _lib = L
     return L
 
