@@ -1139,9 +1139,11 @@ def _assemble_args(ids, poses):
     return ids, p
 
 
-class _PosedScanGrid(_Handle):
-    """What OccupancyGrid and ElevationGrid share (csrc/grid_handle.hpp): a dense 2-D grid that integrates posed scans.  A
-    family names its geometry and stats structures (_geometry, _stats) and the converter of its parameters (_params)."""
+class _Grid(_Handle):
+    """What every dense 2-D grid shares: a geometry structure (_geometry) it is created from and gives back, options, an
+    event for its stream to wait on, and a clear."""
+
+    _geometry = capi.OccupancyGeometry
 
     def _create_grid(self, geo, device):
         self._create(C.byref(geo), int(device))
@@ -1160,6 +1162,11 @@ class _PosedScanGrid(_Handle):
 
     def clear(self):
         self._check(self._call("clear", self._h))
+
+
+class _PosedScanGrid(_Grid):
+    """What OccupancyGrid and ElevationGrid share (csrc/grid_handle.hpp): a dense 2-D grid that integrates posed scans.  A
+    family names its geometry and stats structures (_geometry, _stats) and the converter of its parameters (_params)."""
 
     def _integrate(self, archive, ids, poses, params):
         """lom_<family>_integrate: the scans `ids` of the ScanArchive at `poses` (n x 7 float64, t then q wxyz); returns the
@@ -1274,7 +1281,28 @@ class ElevationGrid(_PosedScanGrid):
         return out, sm.asdict()
 
 
-class ClearanceGrid(_Handle):
+class _PlaneGrid(_Grid):
+    """What ClearanceGrid, NavField, RegionGrid and VisibilityGrid share (csrc/plane_handle.hpp): a dense 2-D grid of one
+    lom_occupancy_geometry that takes planes of shape (height, width)."""
+
+    _shape_text = "expected an int8 array of shape (height, width)"
+
+    def __init__(self, resolution, origin_xy, width, height, device=0):
+        self._create_grid(capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width),
+                                                 int(height)), device)
+
+    def _plane(self, a, dtype):
+        """a host plane as a contiguous array of `dtype`"""
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape != (self.height, self.width):
+            raise ValueError(self._shape_text)
+        return a
+
+    def _optional_plane(self, a, dtype):
+        return None if a is None else self._plane(a, dtype)
+
+
+class ClearanceGrid(_PlaneGrid):
     """Obstacle distance and inflated cost on the device (lom_clearance_*, include/lidar_odometry_amd.h "clearance grid"):
     update() merges an occupancy and an elevation plane (int8 arrays of shape (height, width), either may be None),
     computes the exact truncated squared distance to the nearest obstacle and the int8 cost of a costmap (-1 unknown,
@@ -1283,36 +1311,9 @@ class ClearanceGrid(_Handle):
 
     _family = "clearance"
 
-    def __init__(self, resolution, origin_xy, width, height, device=0):
-        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
-        self._create(C.byref(geo), int(device))
-        self.width, self.height = int(width), int(height)
-
-    def geometry(self):
-        geo = capi.OccupancyGeometry()
-        self._check(self._call("get_geometry", self._h, C.byref(geo)))
-        return geo.asdict()
-
-    def setOption(self, option, value):
-        self._check(self._call("set_option", self._h, int(option), int(value)))
-
-    def waitEvent(self, hip_event):
-        self._check(self._call("wait_event", self._h, hip_event))
-
-    def clear(self):
-        self._check(self._call("clear", self._h))
-
     @staticmethod
     def _window(window):
         return None if window is None else C.byref(capi.ClearanceWindow(*[int(v) for v in window]))
-
-    def _plane(self, a):
-        if a is None:
-            return None
-        a = np.ascontiguousarray(a, np.int8)
-        if a.shape != (self.height, self.width):
-            raise ValueError("expected an int8 array of shape (height, width)")
-        return a
 
     def update(self, occ, elev, params, window=None, device=False, hip_event=None):
         """lom_clearance_update: host planes -- or, with device=True, lom_clearance_update_device: occ and elev are device
@@ -1321,7 +1322,7 @@ class ClearanceGrid(_Handle):
         if device:
             rc = self._call("update_device", self._h, occ, elev, hip_event, C.byref(p), self._window(window), C.byref(sm))
         else:
-            occ, elev = self._plane(occ), self._plane(elev)
+            occ, elev = self._optional_plane(occ, np.int8), self._optional_plane(elev, np.int8)
             rc = self._call("update", self._h, None if occ is None else occ.ctypes.data, None if elev is None else elev.ctypes.data,
                             C.byref(p), self._window(window), C.byref(sm))
         self._check(rc)
@@ -1378,7 +1379,7 @@ def clearanceCostTable(params, resolution):
     return out
 
 
-class NavField(_Handle):
+class NavField(_PlaneGrid):
     """The navigation field on the device (lom_navfield_*, include/lidar_odometry_amd.h "navigation field"): solve() takes
     an int8 cost plane of shape (height, width) in the value range ClearanceGrid.cost() writes, and goals, and leaves per
     cell the least total cost to reach a goal (uint32, capi.NAV_UNREACHED where there is no route); paths() walks down it,
@@ -1386,25 +1387,6 @@ class NavField(_Handle):
     metres=True floats are (x, y) in the grid's frame."""
 
     _family = "navfield"
-
-    def __init__(self, resolution, origin_xy, width, height, device=0):
-        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
-        self._create(C.byref(geo), int(device))
-        self.width, self.height = int(width), int(height)
-
-    def geometry(self):
-        geo = capi.OccupancyGeometry()
-        self._check(self._call("get_geometry", self._h, C.byref(geo)))
-        return geo.asdict()
-
-    def setOption(self, option, value):
-        self._check(self._call("set_option", self._h, int(option), int(value)))
-
-    def waitEvent(self, hip_event):
-        self._check(self._call("wait_event", self._h, hip_event))
-
-    def clear(self):
-        self._check(self._call("clear", self._h))
 
     @staticmethod
     def _points(points, metres):
@@ -1421,9 +1403,7 @@ class NavField(_Handle):
         if device:
             rc = self._call("solve_device", self._h, plane, hip_event, C.byref(p), kind, g.ctypes.data, len(g), C.byref(sm))
         else:
-            plane = np.ascontiguousarray(plane, np.int8)
-            if plane.shape != (self.height, self.width):
-                raise ValueError("expected an int8 array of shape (height, width)")
+            plane = self._plane(plane, np.int8)
             rc = self._call("solve", self._h, plane.ctypes.data, C.byref(p), kind, g.ctypes.data, len(g), C.byref(sm))
         self._check(rc)
         return sm.asdict()
@@ -1474,7 +1454,7 @@ def navfieldCellCosts(params):
     return out
 
 
-class RegionGrid(_Handle):
+class RegionGrid(_PlaneGrid):
     """Connected regions of a grid plane on the device (lom_regions_*, include/lidar_odometry_amd.h "frontier regions"):
     extract() takes an int8 plane of shape (height, width) -- what OccupancyGrid.classify() writes -- and optionally a cost
     plane and a NavField potential, labels the regions of the frontier cells (or of a byte range) with the least linear
@@ -1482,33 +1462,7 @@ class RegionGrid(_Handle):
     form NavField.solve() takes."""
 
     _family = "regions"
-
-    def __init__(self, resolution, origin_xy, width, height, device=0):
-        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
-        self._create(C.byref(geo), int(device))
-        self.width, self.height = int(width), int(height)
-
-    def geometry(self):
-        geo = capi.OccupancyGeometry()
-        self._check(self._call("get_geometry", self._h, C.byref(geo)))
-        return geo.asdict()
-
-    def setOption(self, option, value):
-        self._check(self._call("set_option", self._h, int(option), int(value)))
-
-    def waitEvent(self, hip_event):
-        self._check(self._call("wait_event", self._h, hip_event))
-
-    def clear(self):
-        self._check(self._call("clear", self._h))
-
-    def _plane(self, a, dtype):
-        if a is None:
-            return None
-        a = np.ascontiguousarray(a, dtype)
-        if a.shape != (self.height, self.width):
-            raise ValueError("expected an array of shape (height, width)")
-        return a
+    _shape_text = "expected an array of shape (height, width)"
 
     def extract(self, plane, params, cost=None, potential=None, device=False, hip_event=None):
         """lom_regions_extract: host planes (int8, int8 or None, uint32 or None) -- or, with device=True,
@@ -1518,7 +1472,8 @@ class RegionGrid(_Handle):
         if device:
             rc = self._call("extract_device", self._h, plane, cost, potential, hip_event, C.byref(p), C.byref(sm))
         else:
-            plane, cost, potential = self._plane(plane, np.int8), self._plane(cost, np.int8), self._plane(potential, np.uint32)
+            plane, cost = self._optional_plane(plane, np.int8), self._optional_plane(cost, np.int8)
+            potential = self._optional_plane(potential, np.uint32)
             rc = self._call("extract", self._h, None if plane is None else plane.ctypes.data, None if cost is None else cost.ctypes.data,
                             None if potential is None else potential.ctypes.data, C.byref(p), C.byref(sm))
         self._check(rc)
@@ -1569,7 +1524,7 @@ class RegionGrid(_Handle):
         return st.asdict()
 
 
-class VisibilityGrid(_Handle):
+class VisibilityGrid(_PlaneGrid):
     """Rays cast over a grid plane from many viewpoints at once (lom_visibility_*, include/lidar_odometry_amd.h "visibility
     grid"): cast() takes an int8 plane of shape (height, width) -- what OccupancyGrid.classify() or ClearanceGrid.cost()
     writes -- and (K, 2) int32 viewpoints (ix, iy), what RegionGrid.goals() returns, and leaves a record per viewpoint: the
@@ -1577,26 +1532,7 @@ class VisibilityGrid(_Handle):
     sees, select() the greedy next-best views, gain against travel cost."""
 
     _family = "visibility"
-
-    def __init__(self, resolution, origin_xy, width, height, device=0):
-        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
-        self._create(C.byref(geo), int(device))
-        self.width, self.height = int(width), int(height)
-        self._beams = self._range = 0
-
-    def geometry(self):
-        geo = capi.OccupancyGeometry()
-        self._check(self._call("get_geometry", self._h, C.byref(geo)))
-        return geo.asdict()
-
-    def setOption(self, option, value):
-        self._check(self._call("set_option", self._h, int(option), int(value)))
-
-    def waitEvent(self, hip_event):
-        self._check(self._call("wait_event", self._h, hip_event))
-
-    def clear(self):
-        self._check(self._call("clear", self._h))
+    _beams = _range = 0  # of the last cast
 
     def _cast(self, name, head, viewpoints, params):
         p, sm = visibilityParams(params), capi.VisibilitySummary()
@@ -1610,10 +1546,7 @@ class VisibilityGrid(_Handle):
         to a plane in HBM, complete when `hip_event` is.  Returns capi.VisibilitySummary as a dict."""
         if device:
             return self._cast("cast_device", (plane, hip_event), viewpoints, params)
-        plane = np.ascontiguousarray(plane, np.int8)
-        if plane.shape != (self.height, self.width):
-            raise ValueError("expected an int8 array of shape (height, width)")
-        return self._cast("cast", (plane.ctypes.data,), viewpoints, params)
+        return self._cast("cast", (self._plane(plane, np.int8).ctypes.data,), viewpoints, params)
 
     def castFromOccupancy(self, occupancy, rule, viewpoints, params):
         """lom_visibility_cast_from_occupancy: the plane an OccupancyGrid of this geometry classifies by `rule`, in HBM"""

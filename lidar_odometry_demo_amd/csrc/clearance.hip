@@ -2,26 +2,24 @@
 // distance transform (squared cells, u16) and an inflated int8 cost.  Definitions: include/lidar_odometry_amd.h
 // ("clearance grid"); kernels: k_clearance.hpp; host planning (value ranges, R, the cost table, rectangles, launch
 // shapes): clearance_host.cpp; DESIGN.md 7l.  A handle family of its own: no scans are integrated here, so the handle is a
-// DeviceHandle and not a GridHandle, and no default path launches any of this.
+// PlaneHandle (plane_handle.hpp) and not a GridHandle, and no default path launches any of this.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <new>
 #include <string>
 #include <vector>
 
 #include "clearance_host.hpp"
-#include "device_handle.hpp"
 #include "elevation_host.hpp"
 #include "k_clearance.hpp"
 #include "occupancy_host.hpp"
+#include "plane_handle.hpp"
 
 using namespace lom;
 
 // The grid owns its stream and every buffer below.
-struct lom_clearance : lom::DeviceHandle {
-    lom_occupancy_geometry geo{};
+struct lom_clearance : lom::PlaneHandle {  // in_ev: the occupancy grid's, the elevation grid's
     lom::DeviceBuf base, d2, cost;      // int8, u16, int8 per cell
     lom::DeviceBuf bitmap;              // height x ceil(width / 64) u64: the obstacles
     lom::DeviceBuf table;               // the cost table of the last update, 254^2 + 1 bytes
@@ -29,19 +27,18 @@ struct lom_clearance : lom::DeviceHandle {
     lom::DeviceBuf in_occ, in_elev;     // host planes on their way in, from the first host update on
     lom::DeviceBuf q_xy, q_dist, q_cost;  // a query's points and results, grow-only
     lom::PinnedBuf h_words;             // the summary words on their way out
-    hipEvent_t done_ev = nullptr;       // recorded behind an update's kernels, for the producers' streams to wait on
-    hipEvent_t in_ev[2] = {nullptr, nullptr};  // recorded behind the two producers, for this stream to wait on
     std::vector<uint8_t> h_table;       // what `table` holds (empty: nothing yet)
     uint32_t tile_rows = clearance::kTileRowsMax;  // LOM_CLEAR_OPT_TEST_TILE_ROWS
     uint32_t no_prune = 0;                         // LOM_CLEAR_OPT_TEST_NO_PRUNE
 
-    size_t n_cells() const { return (size_t)geo.width * geo.height; }
     size_t n_words() const { return (size_t)geo.height * clearance::words_per_row(geo.width); }
 };
 
 namespace {
 
 thread_local std::string g_clearance_create_error;
+
+constexpr const char *kName = "clearance";  // the head of the texts of the plane-handle core
 
 constexpr const char *kParamsText =
     "clearance parameters: 0 <= inscribed_radius <= inflation_radius, decay >= 0, all finite, known flags, "
@@ -106,22 +103,6 @@ int update_on_device(lom_clearance *c, const int8_t *d_occ, const int8_t *d_elev
     return LOM_OK;
 }
 
-// n_bytes of a device plane to the caller, then the wait
-int copy_out(lom_clearance *c, void *out, const DeviceBuf &plane, size_t n_bytes)
-{
-    if (!n_bytes) return LOM_OK;
-    LOM_HIP(c, hipSetDevice(c->device));
-    LOM_HIP(c, hipMemcpyAsync(out, plane.p, n_bytes, hipMemcpyDeviceToHost, c->stream));
-    LOM_HIP(c, hipStreamSynchronize(c->stream));
-    return LOM_OK;
-}
-
-bool same_geometry(const lom_occupancy_geometry &a, const lom_occupancy_geometry &b)
-{
-    return std::memcmp(&a.resolution, &b.resolution, 4) == 0 && std::memcmp(&a.origin_x, &b.origin_x, 4) == 0 &&
-           std::memcmp(&a.origin_y, &b.origin_y, 4) == 0 && a.width == b.width && a.height == b.height;
-}
-
 }  // namespace
 
 extern "C" {
@@ -129,22 +110,10 @@ extern "C" {
 int lom_clearance_create(const lom_occupancy_geometry *geometry, int device, lom_clearance **out)
 {
     if (!out) return LOM_ERR_ARG;
-    *out = nullptr;
-    if (!clearance::geometry_ok(geometry))
-        return create_fail(g_clearance_create_error, LOM_ERR_ARG,
-                           "clearance geometry: resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192");
-    if (const int rc = check_device(device, g_clearance_create_error); rc != LOM_OK) return rc;
-    lom_clearance *c = new (std::nothrow) lom_clearance();
-    if (!c) return create_fail(g_clearance_create_error, LOM_ERR_OOM, "host allocation");
-    c->device = device;
-    c->geo = *geometry;
-    int rc = LOM_OK;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->in_ev[0], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->in_ev[1], hipEventDisableTiming);
-    if (e == hipSuccess) e = alloc(c->h_words, 64, hipHostMallocDefault);
+    lom_clearance *c = nullptr;
+    int rc = plane_new(geometry, device, g_clearance_create_error, kName, "clearance grid setup", 2, &c);
+    if (rc != LOM_OK) return rc;
+    hipError_t e = alloc(c->h_words, 64, hipHostMallocDefault);
     if (e != hipSuccess) rc = create_fail(g_clearance_create_error, LOM_ERR_HIP, "clearance grid setup", e);
     const size_t n = c->n_cells();
     if (rc == LOM_OK &&
@@ -169,18 +138,8 @@ int lom_clearance_create(const lom_occupancy_geometry *geometry, int device, lom
     return LOM_OK;
 }
 
-void lom_clearance_destroy(lom_clearance *c)
-{
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (hipEvent_t ev : {c->done_ev, c->in_ev[0], c->in_ev[1]})
-        if (ev) (void)hipEventDestroy(ev);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;  // the buffers go with it
-}
-
-const char *lom_clearance_last_error(const lom_clearance *c) { return c ? c->error.c_str() : g_clearance_create_error.c_str(); }
+void lom_clearance_destroy(lom_clearance *c) { plane_destroy(c); }
+const char *lom_clearance_last_error(const lom_clearance *c) { return plane_last_error(c, g_clearance_create_error); }
 
 int lom_clearance_clear(lom_clearance *c)
 {
@@ -191,23 +150,10 @@ int lom_clearance_clear(lom_clearance *c)
     return LOM_OK;
 }
 
-int lom_clearance_get_geometry(const lom_clearance *c, lom_occupancy_geometry *out)
-{
-    if (!c || !out) return LOM_ERR_ARG;
-    *out = c->geo;
-    return LOM_OK;
-}
-
-void *lom_clearance_stream(lom_clearance *c) { return c ? (void *)c->stream : nullptr; }
-int lom_clearance_device(const lom_clearance *c) { return c ? c->device : LOM_ERR_ARG; }
-
-int lom_clearance_wait_event(lom_clearance *c, void *hip_event)
-{
-    if (!c || !hip_event) return LOM_ERR_ARG;
-    LOM_HIP(c, hipSetDevice(c->device));
-    LOM_HIP(c, hipStreamWaitEvent(c->stream, (hipEvent_t)hip_event, 0));
-    return LOM_OK;
-}
+int lom_clearance_get_geometry(const lom_clearance *c, lom_occupancy_geometry *out) { return plane_get_geometry(c, out); }
+void *lom_clearance_stream(lom_clearance *c) { return plane_stream(c); }
+int lom_clearance_device(const lom_clearance *c) { return plane_device(c); }
+int lom_clearance_wait_event(lom_clearance *c, void *hip_event) { return plane_wait_event(c, hip_event); }
 
 int lom_clearance_set_option(lom_clearance *c, int option, int64_t value)
 {
@@ -272,20 +218,16 @@ int lom_clearance_update_from_grids(lom_clearance *c, lom_occupancy *occupancy, 
     if (!c) return LOM_ERR_ARG;
     if (const char *why = update_refusal(c, occupancy != nullptr, elevation != nullptr, params)) return fail(c, LOM_ERR_ARG, why);
     if (occupancy) {
-        lom_occupancy_geometry g;
-        if (lom_occupancy_get_geometry(occupancy, &g) != LOM_OK || !same_geometry(g, c->geo))
-            return fail(c, LOM_ERR_ARG, "clearance: the occupancy grid's resolution, origin, width or height differs");
-        if (lom_occupancy_device(occupancy) != c->device)
-            return fail(c, LOM_ERR_ARG, "clearance: the occupancy grid lives on another device");
+        lom_occupancy_geometry g{};
+        (void)lom_occupancy_get_geometry(occupancy, &g);
+        if (const int rc = plane_check_producer(c, kName, "occupancy grid", g, lom_occupancy_device(occupancy)); rc != LOM_OK) return rc;
         if (!occupancy::rule_ok(rule)) return fail(c, LOM_ERR_ARG, "occupancy rule: min_free_scans >= 1, min_seen_scans >= 1");
     }
     if (elevation) {
-        lom_elevation_geometry g;
-        if (lom_elevation_get_geometry(elevation, &g) != LOM_OK ||
-            !same_geometry(lom_occupancy_geometry{g.resolution, g.origin_x, g.origin_y, g.width, g.height}, c->geo))
-            return fail(c, LOM_ERR_ARG, "clearance: the elevation grid's resolution, origin, width or height differs");
-        if (lom_elevation_device(elevation) != c->device)
-            return fail(c, LOM_ERR_ARG, "clearance: the elevation grid lives on another device");
+        lom_elevation_geometry g{};
+        (void)lom_elevation_get_geometry(elevation, &g);
+        const lom_occupancy_geometry flat{g.resolution, g.origin_x, g.origin_y, g.width, g.height};
+        if (const int rc = plane_check_producer(c, kName, "elevation grid", flat, lom_elevation_device(elevation)); rc != LOM_OK) return rc;
         if (!elevation::layer_params_ok(layer_params)) return fail(c, LOM_ERR_ARG, "elevation layers: min_points >= 1, window in 1 .. 4");
         if (!elevation::cost_params_ok(cost_params))
             return fail(c, LOM_ERR_ARG, "elevation cost: max_slope, max_step, max_rough, max_span finite and > 0");
@@ -293,28 +235,22 @@ int lom_clearance_update_from_grids(lom_clearance *c, lom_occupancy *occupancy, 
     const clearance::Rect rect = clearance::clip(window, c->geo);
     if (rect.empty()) return LOM_OK;
     LOM_HIP(c, hipSetDevice(c->device));
-    // the producers leave their planes on their own streams; this stream reads them behind an event each
+    // the hand-off of plane_handle.hpp, once per producer: read behind it, update, release to it
     const int8_t *d_occ = nullptr, *d_elev = nullptr;
+    int rc;
     if (occupancy) {
         if (lom_occupancy_classify_device(occupancy, rule, &d_occ) != LOM_OK)
-            return fail(c, LOM_ERR_HIP, (std::string("clearance: lom_occupancy_classify_device: ") + lom_occupancy_last_error(occupancy)).c_str());
-        LOM_HIP(c, hipEventRecord(c->in_ev[0], (hipStream_t)lom_occupancy_stream(occupancy)));
-        LOM_HIP(c, hipStreamWaitEvent(c->stream, c->in_ev[0], 0));
+            return plane_fail_producer(c, kName, "lom_occupancy_classify_device", lom_occupancy_last_error(occupancy));
+        if ((rc = plane_read_behind(c, 0, lom_occupancy_stream(occupancy))) != LOM_OK) return rc;
     }
     if (elevation) {
         if (lom_elevation_cost_device(elevation, layer_params, cost_params, &d_elev) != LOM_OK)
-            return fail(c, LOM_ERR_HIP, (std::string("clearance: lom_elevation_cost_device: ") + lom_elevation_last_error(elevation)).c_str());
-        LOM_HIP(c, hipEventRecord(c->in_ev[1], (hipStream_t)lom_elevation_stream(elevation)));
-        LOM_HIP(c, hipStreamWaitEvent(c->stream, c->in_ev[1], 0));
+            return plane_fail_producer(c, kName, "lom_elevation_cost_device", lom_elevation_last_error(elevation));
+        if ((rc = plane_read_behind(c, 1, lom_elevation_stream(elevation))) != LOM_OK) return rc;
     }
-    const int rc = update_on_device(c, d_occ, d_elev, *params, rect, summary);
-    if (rc != LOM_OK) return rc;
-    // and what a producer does next to its plane comes behind this update's reads
-    if (occupancy && lom_occupancy_wait_event(occupancy, c->done_ev) != LOM_OK)
-        return fail(c, LOM_ERR_HIP, "clearance: lom_occupancy_wait_event");
-    if (elevation && lom_elevation_wait_event(elevation, c->done_ev) != LOM_OK)
-        return fail(c, LOM_ERR_HIP, "clearance: lom_elevation_wait_event");
-    return LOM_OK;
+    if ((rc = update_on_device(c, d_occ, d_elev, *params, rect, summary)) != LOM_OK) return rc;
+    if (occupancy && (rc = plane_release(c, kName, occupancy, lom_occupancy_wait_event, "lom_occupancy_wait_event")) != LOM_OK) return rc;
+    return elevation ? plane_release(c, kName, elevation, lom_elevation_wait_event, "lom_elevation_wait_event") : LOM_OK;
 }
 
 int lom_clearance_cost(lom_clearance *c, int8_t *out, size_t cap, lom_clearance_summary *summary)
@@ -347,7 +283,7 @@ int lom_clearance_cost_device(lom_clearance *c, const int8_t **d_out)
 int lom_clearance_distance_sq(lom_clearance *c, uint16_t *out, size_t cap)
 {
     if (!c || (cap && !out)) return LOM_ERR_ARG;
-    return copy_out(c, out, c->d2, std::min(cap, c->n_cells()) * 2);
+    return plane_copy_out(c, out, c->d2, std::min(cap, c->n_cells()) * 2);
 }
 
 int lom_clearance_distance(lom_clearance *c, float *out, size_t cap)
@@ -356,7 +292,7 @@ int lom_clearance_distance(lom_clearance *c, float *out, size_t cap)
     const size_t n = std::min(cap, c->n_cells());
     if (!n) return LOM_OK;
     std::vector<uint16_t> d2(n);
-    if (const int rc = copy_out(c, d2.data(), c->d2, n * 2); rc != LOM_OK) return rc;
+    if (const int rc = plane_copy_out(c, d2.data(), c->d2, n * 2); rc != LOM_OK) return rc;
     // step 5 per distinct value: d2 <= 254^2, or far
     std::vector<float> metres((size_t)clearance::kMaxRadius * clearance::kMaxRadius + 1);
     for (size_t k = 0; k < metres.size(); k++) metres[k] = (float)(std::sqrt((double)k) * (double)c->geo.resolution);

@@ -9,12 +9,6 @@
 namespace lom {
 namespace clearance {
 
-bool geometry_ok(const lom_occupancy_geometry *g)
-{
-    return g && std::isfinite(g->resolution) && g->resolution > 0.f && std::isfinite(g->origin_x) && std::isfinite(g->origin_y) &&
-           g->width >= 1u && g->width <= kMaxSide && g->height >= 1u && g->height <= kMaxSide;
-}
-
 uint32_t radius_cells(float inflation_radius, float resolution)
 {
     const double q = std::floor((double)inflation_radius / (double)resolution);

@@ -7,11 +7,11 @@
 #include <cstdint>
 
 #include "../../include/lidar_odometry_amd.h"
+#include "plane_geometry.hpp"
 
 namespace lom {
 namespace clearance {
 
-constexpr uint32_t kMaxSide = 8192;        // cells per axis
 constexpr uint32_t kMaxRadius = 254;       // R in cells: R^2 = 64516 fits a u16 below LOM_CLEAR_FAR
 constexpr uint32_t kTileCols = 64;         // a tile of k_clear_distance is one bitmap word wide ...
 constexpr uint32_t kTileRowsMax = 32;      // ... and T rows high, T in 1 .. 32
@@ -40,8 +40,7 @@ struct TileGrid {
     size_t lds_bytes;
 };
 
-// resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192
-bool geometry_ok(const lom_occupancy_geometry *g);
+using plane::geometry_ok;  // the rule of all four planning grids
 // floor((double)inflation_radius / (double)resolution); > kMaxRadius (also for a quotient that is no number): out of range
 uint32_t radius_cells(float inflation_radius, float resolution);
 // 0 <= inscribed_radius <= inflation_radius, decay >= 0, all finite, known flags only, radius_cells <= 254

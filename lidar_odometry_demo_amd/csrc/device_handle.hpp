@@ -1,7 +1,9 @@
 // What every device handle is: the device it lives on, the stream its work runs on, the text of its last error -- and
-// the blocks of device and pinned host memory it owns.  lom_map, lom_frontend, lom_place_db, lom_graph, lom_archive, lom_occupancy, lom_elevation,
-// lom_clearance, lom_navfield, lom_regions and lom_visibility derive from DeviceHandle; what is written once on DeviceHandle * is declared here (code: below and in handle.hip).
-// Host code only; nothing here launches a kernel.
+// the blocks of device and pinned host memory it owns.  lom_map, lom_frontend, lom_place_db, lom_graph and lom_archive
+// derive from DeviceHandle directly; lom_occupancy and lom_elevation through GridHandle (grid_handle.hpp: grids that
+// integrate posed scans); lom_clearance, lom_navfield, lom_regions and lom_visibility through PlaneHandle
+// (plane_handle.hpp: grids that read other handles' planes).  What is written once on DeviceHandle * is declared here
+// (code: below and in handle.hip).  Host code only; nothing here launches a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 

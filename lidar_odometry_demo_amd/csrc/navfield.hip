@@ -1,16 +1,15 @@
 // Navigation field: the least total cost to reach a goal, per cell, over an int8 cost plane; paths down it and point
 // queries.  Definitions: include/lidar_odometry_amd.h ("navigation field"); kernels: k_navfield.hpp; host planning (value
 // ranges, the cell-cost table, goal quantisation, tile counts, launch shapes): navfield_host.cpp; DESIGN.md 7m.  A handle
-// family of its own on the DeviceHandle core; no default path launches any of this.
+// family of its own on the PlaneHandle core (plane_handle.hpp); no default path launches any of this.
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
-#include "device_handle.hpp"
 #include "k_navfield.hpp"
 #include "navfield_host.hpp"
+#include "plane_handle.hpp"
 
 using namespace lom;
 
@@ -19,8 +18,7 @@ static_assert(navfield::kThreads == kNavThreads && navfield::kTile == kNavTile &
 static_assert(LOM_NAV_UNREACHED == kNavUnreached && LOM_NAV_MAX == kNavMax, "the header and k_navfield.hpp disagree");
 
 // The field owns its stream and every buffer below.
-struct lom_navfield : lom::DeviceHandle {
-    lom_occupancy_geometry geo{};
+struct lom_navfield : lom::PlaneHandle {  // in_ev: the clearance grid's
     navfield::TileGrid tiles{};
     lom::DeviceBuf field;            // u32 per cell
     lom::DeviceBuf plane;            // the cost bytes of the last solve
@@ -33,20 +31,19 @@ struct lom_navfield : lom::DeviceHandle {
     lom::DeviceBuf q_xy, q_out;      // a query's points and results, grow-only
     lom::PinnedBuf h_table;          // the table on its way in
     lom::PinnedBuf h_flags;          // the batch's flags and the summary words on their way out
-    hipEvent_t done_ev = nullptr;    // recorded behind a solve, for the clearance grid's stream to wait on
-    hipEvent_t in_ev = nullptr;      // recorded behind the clearance grid's plane, for this stream to wait on
     uint32_t inner_cap = navfield::kInnerCapDefault;  // LOM_NAV_OPT_TEST_INNER_CAP
     uint32_t batch = navfield::kBatchDefault;         // LOM_NAV_OPT_TEST_BATCH
     uint32_t all_tiles = 0;                           // LOM_NAV_OPT_TEST_ALL_TILES
     lom_navfield_solve_stats stats{};
 
-    size_t n_cells() const { return (size_t)geo.width * geo.height; }
     NavArgs args() const { return NavArgs{geo.width, geo.height, tiles.tiles_x, tiles.tiles_y}; }
 };
 
 namespace {
 
 thread_local std::string g_navfield_create_error;
+
+constexpr const char *kName = "navigation field";  // the head of the texts of the plane-handle core
 
 constexpr const char *kParamsText =
     "navigation field parameters: neutral >= 1, 0 <= max_passable <= 98, neutral + 98 * factor <= 2^24 - 1, known flags, "
@@ -149,12 +146,6 @@ int solve_on_device(lom_navfield *f, const int8_t *d_plane, const lom_navfield_p
     return LOM_OK;
 }
 
-bool same_geometry(const lom_occupancy_geometry &a, const lom_occupancy_geometry &b)
-{
-    return std::memcmp(&a.resolution, &b.resolution, 4) == 0 && std::memcmp(&a.origin_x, &b.origin_x, 4) == 0 &&
-           std::memcmp(&a.origin_y, &b.origin_y, 4) == 0 && a.width == b.width && a.height == b.height;
-}
-
 }  // namespace
 
 extern "C" {
@@ -162,22 +153,11 @@ extern "C" {
 int lom_navfield_create(const lom_occupancy_geometry *geometry, int device, lom_navfield **out)
 {
     if (!out) return LOM_ERR_ARG;
-    *out = nullptr;
-    if (!navfield::geometry_ok(geometry))
-        return create_fail(g_navfield_create_error, LOM_ERR_ARG,
-                           "navigation field geometry: resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192");
-    if (const int rc = check_device(device, g_navfield_create_error); rc != LOM_OK) return rc;
-    lom_navfield *f = new (std::nothrow) lom_navfield();
-    if (!f) return create_fail(g_navfield_create_error, LOM_ERR_OOM, "host allocation");
-    f->device = device;
-    f->geo = *geometry;
+    lom_navfield *f = nullptr;
+    int rc = plane_new(geometry, device, g_navfield_create_error, kName, "navigation field setup", 1, &f);
+    if (rc != LOM_OK) return rc;
     f->tiles = navfield::tile_grid(geometry->width, geometry->height);
-    int rc = LOM_OK;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->done_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->in_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = alloc(f->h_table, 256 * 4, hipHostMallocDefault);
+    hipError_t e = alloc(f->h_table, 256 * 4, hipHostMallocDefault);
     if (e == hipSuccess) e = alloc(f->h_flags, (size_t)navfield::kBatchMax * 4, hipHostMallocDefault);
     if (e != hipSuccess) rc = create_fail(g_navfield_create_error, LOM_ERR_HIP, "navigation field setup", e);
     const size_t n = f->n_cells();
@@ -198,18 +178,8 @@ int lom_navfield_create(const lom_occupancy_geometry *geometry, int device, lom_
     return LOM_OK;
 }
 
-void lom_navfield_destroy(lom_navfield *f)
-{
-    if (!f) return;
-    (void)hipSetDevice(f->device);
-    if (f->stream) (void)hipStreamSynchronize(f->stream);
-    for (hipEvent_t ev : {f->done_ev, f->in_ev})
-        if (ev) (void)hipEventDestroy(ev);
-    if (f->stream) (void)hipStreamDestroy(f->stream);
-    delete f;  // the buffers go with it
-}
-
-const char *lom_navfield_last_error(const lom_navfield *f) { return f ? f->error.c_str() : g_navfield_create_error.c_str(); }
+void lom_navfield_destroy(lom_navfield *f) { plane_destroy(f); }
+const char *lom_navfield_last_error(const lom_navfield *f) { return plane_last_error(f, g_navfield_create_error); }
 
 int lom_navfield_clear(lom_navfield *f)
 {
@@ -220,23 +190,10 @@ int lom_navfield_clear(lom_navfield *f)
     return LOM_OK;
 }
 
-int lom_navfield_get_geometry(const lom_navfield *f, lom_occupancy_geometry *out)
-{
-    if (!f || !out) return LOM_ERR_ARG;
-    *out = f->geo;
-    return LOM_OK;
-}
-
-void *lom_navfield_stream(lom_navfield *f) { return f ? (void *)f->stream : nullptr; }
-int lom_navfield_device(const lom_navfield *f) { return f ? f->device : LOM_ERR_ARG; }
-
-int lom_navfield_wait_event(lom_navfield *f, void *hip_event)
-{
-    if (!f || !hip_event) return LOM_ERR_ARG;
-    LOM_HIP(f, hipSetDevice(f->device));
-    LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event, 0));
-    return LOM_OK;
-}
+int lom_navfield_get_geometry(const lom_navfield *f, lom_occupancy_geometry *out) { return plane_get_geometry(f, out); }
+void *lom_navfield_stream(lom_navfield *f) { return plane_stream(f); }
+int lom_navfield_device(const lom_navfield *f) { return plane_device(f); }
+int lom_navfield_wait_event(lom_navfield *f, void *hip_event) { return plane_wait_event(f, hip_event); }
 
 int lom_navfield_set_option(lom_navfield *f, int option, int64_t value)
 {
@@ -289,33 +246,24 @@ int lom_navfield_solve_from_clearance(lom_navfield *f, lom_clearance *clearance,
     if (summary) std::memset(summary, 0, sizeof *summary);
     if (!f) return LOM_ERR_ARG;
     if (const char *why = solve_refusal(clearance != nullptr, params, goal_kind, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
-    lom_occupancy_geometry g;
-    if (lom_clearance_get_geometry(clearance, &g) != LOM_OK || !same_geometry(g, f->geo))
-        return fail(f, LOM_ERR_ARG, "navigation field: the clearance grid's resolution, origin, width or height differs");
-    if (lom_clearance_device(clearance) != f->device) return fail(f, LOM_ERR_ARG, "navigation field: the clearance grid lives on another device");
+    lom_occupancy_geometry g{};
+    (void)lom_clearance_get_geometry(clearance, &g);
+    int rc = plane_check_producer(f, kName, "clearance grid", g, lom_clearance_device(clearance));
+    if (rc != LOM_OK) return rc;
     LOM_HIP(f, hipSetDevice(f->device));
-    // the clearance grid leaves its plane on its own stream; this stream reads it behind an event
+    // the hand-off of plane_handle.hpp: read behind the clearance grid, solve, release to it
     const int8_t *d_plane = nullptr;
     if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
-        return fail(f, LOM_ERR_HIP, (std::string("navigation field: lom_clearance_cost_device: ") + lom_clearance_last_error(clearance)).c_str());
-    LOM_HIP(f, hipEventRecord(f->in_ev, (hipStream_t)lom_clearance_stream(clearance)));
-    LOM_HIP(f, hipStreamWaitEvent(f->stream, f->in_ev, 0));
-    const int rc = solve_on_device(f, d_plane, *params, goal_kind, goals, n_goals, summary);
-    if (rc != LOM_OK) return rc;
-    // and what the clearance grid does next to its plane comes behind this solve's reads
-    if (lom_clearance_wait_event(clearance, f->done_ev) != LOM_OK) return fail(f, LOM_ERR_HIP, "navigation field: lom_clearance_wait_event");
-    return LOM_OK;
+        return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
+    if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
+    if ((rc = solve_on_device(f, d_plane, *params, goal_kind, goals, n_goals, summary)) != LOM_OK) return rc;
+    return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
 }
 
 int lom_navfield_potential(lom_navfield *f, uint32_t *out, size_t cap)
 {
     if (!f || (cap && !out)) return LOM_ERR_ARG;
-    const size_t n = std::min(cap, f->n_cells());
-    if (!n) return LOM_OK;
-    LOM_HIP(f, hipSetDevice(f->device));
-    LOM_HIP(f, hipMemcpyAsync(out, f->field.p, n * 4, hipMemcpyDeviceToHost, f->stream));
-    LOM_HIP(f, hipStreamSynchronize(f->stream));
-    return LOM_OK;
+    return plane_copy_out(f, out, f->field, std::min(cap, f->n_cells()) * 4);
 }
 
 int lom_navfield_potential_device(lom_navfield *f, const uint32_t **d_out)

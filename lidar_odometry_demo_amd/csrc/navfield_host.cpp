@@ -8,12 +8,6 @@
 namespace lom {
 namespace navfield {
 
-bool geometry_ok(const lom_occupancy_geometry *g)
-{
-    return g && std::isfinite(g->resolution) && g->resolution > 0.f && std::isfinite(g->origin_x) && std::isfinite(g->origin_y) &&
-           g->width >= 1u && g->width <= kMaxSide && g->height >= 1u && g->height <= kMaxSide;
-}
-
 bool params_ok(const lom_navfield_params *p)
 {
     if (!p || p->neutral < 1u || p->max_passable < 0 || p->max_passable > (int8_t)kMaxByteCost || (p->flags & ~kKnownFlags) != 0u)

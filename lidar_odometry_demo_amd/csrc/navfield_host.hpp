@@ -7,11 +7,11 @@
 #include <cstdint>
 
 #include "../../include/lidar_odometry_amd.h"
+#include "plane_geometry.hpp"
 
 namespace lom {
 namespace navfield {
 
-constexpr uint32_t kMaxSide = 8192;                // cells per axis
 constexpr uint32_t kTile = 32;                     // a tile of k_nav_relax is 32 x 32 cells
 constexpr uint32_t kThreads = 256;                 // every kernel runs workgroups of four waves
 constexpr uint32_t kMaxCellCost = (1u << 24) - 1;  // of a passable cell: 7 * kMaxCellCost < 2^27 fits a u32 with room
@@ -29,8 +29,7 @@ struct TileGrid {
     uint32_t tiles_x, tiles_y, n_tiles;
 };
 
-// resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192
-bool geometry_ok(const lom_occupancy_geometry *g);
+using plane::geometry_ok;  // the rule of all four planning grids
 // neutral >= 1, 0 <= max_passable <= 98, neutral + 98 * factor <= 2^24 - 1, known flags only, and unknown_cost in
 // 1 .. 2^24 - 1 where LOM_NAV_UNKNOWN_PASSABLE is set
 bool params_ok(const lom_navfield_params *p);

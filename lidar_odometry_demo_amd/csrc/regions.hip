@@ -1,16 +1,15 @@
 // Region grid: the connected regions of a grid plane labelled on the device, a record per region, a ranked goal list.
 // Definitions: include/lidar_odometry_amd.h ("frontier regions"); kernels: k_regions.hpp; host planning (value ranges,
-// launch shapes, the list sort): regions_host.cpp; DESIGN.md 7n.  A handle family of its own on the DeviceHandle core; no
-// default path launches any of this.
+// launch shapes, the list sort): regions_host.cpp; DESIGN.md 7n.  A handle family of its own on the PlaneHandle core
+// (plane_handle.hpp); no default path launches any of this.
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
-#include "device_handle.hpp"
 #include "k_regions.hpp"
 #include "occupancy_host.hpp"
+#include "plane_handle.hpp"
 #include "regions_host.hpp"
 
 using namespace lom;
@@ -24,8 +23,7 @@ static_assert(LOM_REGIONS_NONE == kRegNone && LOM_NAV_UNREACHED == kRegUnreached
 static_assert(sizeof(RegRecord) == sizeof(lom_regions_record), "the record's layout");
 
 // The region grid owns its stream and every buffer below.
-struct lom_regions : lom::DeviceHandle {
-    lom_occupancy_geometry geo{};
+struct lom_regions : lom::PlaneHandle {  // in_ev: the occupancy grid's, the clearance grid's, the navigation field's
     lom::DeviceBuf labels;                    // u32 per cell
     lom::DeviceBuf number;                    // u32 per cell: a root's dense number
     lom::DeviceBuf bitmap, rootbits;          // u64 words, row-aligned: the members, the roots
@@ -35,8 +33,6 @@ struct lom_regions : lom::DeviceHandle {
     lom::DeviceBuf in_plane, in_cost, in_pot; // an extract's host planes on the device, grow-only
     lom::DeviceBuf q_xy, q_out;               // a query's points and results, grow-only
     lom::PinnedBuf h_words;                   // the summary words on their way out
-    hipEvent_t done_ev = nullptr;             // recorded behind an extract, for the producers' streams to wait on
-    hipEvent_t in_ev[3] = {nullptr, nullptr, nullptr};  // recorded behind each producer's plane, for this stream to wait on
     uint64_t max_regions = regions::kMaxRegionsDefault;  // LOM_REGIONS_OPT_MAX_REGIONS
     uint32_t tile_rows = regions::kTileRowsDefault;      // LOM_REGIONS_OPT_TEST_TILE_ROWS
     bool no_tiles = false, no_wave_merge = false;        // LOM_REGIONS_OPT_TEST_NO_TILES, _NO_WAVE_MERGE
@@ -49,13 +45,14 @@ struct lom_regions : lom::DeviceHandle {
     std::vector<lom_regions_record> host_records;
     std::vector<uint32_t> order;
 
-    size_t n_cells() const { return (size_t)geo.width * geo.height; }
     RegArgs args() const { return RegArgs{geo.width, geo.height, (geo.width + 63u) / 64u}; }
 };
 
 namespace {
 
 thread_local std::string g_regions_create_error;
+
+constexpr const char *kName = "region grid";  // the head of the texts of the plane-handle core
 
 constexpr const char *kParamsText =
     "region parameters: a known kind, lo <= hi under LOM_REGIONS_BYTES, 0 <= max_cost <= 99, min_cells >= 1, a known rank "
@@ -157,20 +154,10 @@ int ready_list(lom_regions *r)
     if (r->list_ready) return LOM_OK;
     const size_t n = (size_t)r->summary.regions_recorded;
     r->host_records.resize(n);
-    if (n) {
-        LOM_HIP(r, hipSetDevice(r->device));
-        LOM_HIP(r, hipMemcpyAsync(r->host_records.data(), r->records.p, n * sizeof(lom_regions_record), hipMemcpyDeviceToHost, r->stream));
-        LOM_HIP(r, hipStreamSynchronize(r->stream));
-    }
+    if (const int rc = plane_copy_out(r, r->host_records.data(), r->records, n * sizeof(lom_regions_record)); rc != LOM_OK) return rc;
     regions::sort_list(r->host_records.data(), n, r->list_min_cells, r->list_rank, r->order);
     r->list_ready = true;
     return LOM_OK;
-}
-
-bool same_geometry(const lom_occupancy_geometry &a, const lom_occupancy_geometry &b)
-{
-    return std::memcmp(&a.resolution, &b.resolution, 4) == 0 && std::memcmp(&a.origin_x, &b.origin_x, 4) == 0 &&
-           std::memcmp(&a.origin_y, &b.origin_y, 4) == 0 && a.width == b.width && a.height == b.height;
 }
 
 }  // namespace
@@ -180,23 +167,11 @@ extern "C" {
 int lom_regions_create(const lom_occupancy_geometry *geometry, int device, lom_regions **out)
 {
     if (!out) return LOM_ERR_ARG;
-    *out = nullptr;
-    if (!regions::geometry_ok(geometry))
-        return create_fail(g_regions_create_error, LOM_ERR_ARG,
-                           "region grid geometry: resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192");
-    if (const int rc = check_device(device, g_regions_create_error); rc != LOM_OK) return rc;
-    lom_regions *r = new (std::nothrow) lom_regions();
-    if (!r) return create_fail(g_regions_create_error, LOM_ERR_OOM, "host allocation");
-    r->device = device;
-    r->geo = *geometry;
+    lom_regions *r = nullptr;
+    int rc = plane_new(geometry, device, g_regions_create_error, kName, "region grid setup", 3, &r);
+    if (rc != LOM_OK) return rc;
     const regions::Plan pl = regions::plan(geometry->width, geometry->height, regions::kTileRowsDefault, false);
-    int rc = LOM_OK;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&r->done_ev, hipEventDisableTiming);
-    for (hipEvent_t &ev : r->in_ev)
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = alloc(r->h_words, 64, hipHostMallocDefault);
+    const hipError_t e = alloc(r->h_words, 64, hipHostMallocDefault);
     if (e != hipSuccess) rc = create_fail(g_regions_create_error, LOM_ERR_HIP, "region grid setup", e);
     const size_t n = r->n_cells();
     if (rc == LOM_OK &&
@@ -213,18 +188,8 @@ int lom_regions_create(const lom_occupancy_geometry *geometry, int device, lom_r
     return LOM_OK;
 }
 
-void lom_regions_destroy(lom_regions *r)
-{
-    if (!r) return;
-    (void)hipSetDevice(r->device);
-    if (r->stream) (void)hipStreamSynchronize(r->stream);
-    for (hipEvent_t ev : {r->done_ev, r->in_ev[0], r->in_ev[1], r->in_ev[2]})
-        if (ev) (void)hipEventDestroy(ev);
-    if (r->stream) (void)hipStreamDestroy(r->stream);
-    delete r;  // the buffers go with it
-}
-
-const char *lom_regions_last_error(const lom_regions *r) { return r ? r->error.c_str() : g_regions_create_error.c_str(); }
+void lom_regions_destroy(lom_regions *r) { plane_destroy(r); }
+const char *lom_regions_last_error(const lom_regions *r) { return plane_last_error(r, g_regions_create_error); }
 
 int lom_regions_clear(lom_regions *r)
 {
@@ -233,23 +198,10 @@ int lom_regions_clear(lom_regions *r)
     return reset(r);
 }
 
-int lom_regions_get_geometry(const lom_regions *r, lom_occupancy_geometry *out)
-{
-    if (!r || !out) return LOM_ERR_ARG;
-    *out = r->geo;
-    return LOM_OK;
-}
-
-void *lom_regions_stream(lom_regions *r) { return r ? (void *)r->stream : nullptr; }
-int lom_regions_device(const lom_regions *r) { return r ? r->device : LOM_ERR_ARG; }
-
-int lom_regions_wait_event(lom_regions *r, void *hip_event)
-{
-    if (!r || !hip_event) return LOM_ERR_ARG;
-    LOM_HIP(r, hipSetDevice(r->device));
-    LOM_HIP(r, hipStreamWaitEvent(r->stream, (hipEvent_t)hip_event, 0));
-    return LOM_OK;
-}
+int lom_regions_get_geometry(const lom_regions *r, lom_occupancy_geometry *out) { return plane_get_geometry(r, out); }
+void *lom_regions_stream(lom_regions *r) { return plane_stream(r); }
+int lom_regions_device(const lom_regions *r) { return plane_device(r); }
+int lom_regions_wait_event(lom_regions *r, void *hip_event) { return plane_wait_event(r, hip_event); }
 
 int lom_regions_set_option(lom_regions *r, int option, int64_t value)
 {
@@ -314,54 +266,46 @@ int lom_regions_extract_from_grids(lom_regions *r, lom_occupancy *occupancy, con
     if (const char *why = extract_refusal(occupancy != nullptr, navfield != nullptr, params)) return fail(r, LOM_ERR_ARG, why);
     if (!occupancy::rule_ok(rule))
         return fail(r, LOM_ERR_ARG, "occupancy rule: min_free_scans >= 1, min_seen_scans >= 1");
-    lom_occupancy_geometry g;
-    if (lom_occupancy_get_geometry(occupancy, &g) != LOM_OK || !same_geometry(g, r->geo))
-        return fail(r, LOM_ERR_ARG, "region grid: the occupancy grid's resolution, origin, width or height differs");
-    if (clearance && (lom_clearance_get_geometry(clearance, &g) != LOM_OK || !same_geometry(g, r->geo)))
-        return fail(r, LOM_ERR_ARG, "region grid: the clearance grid's resolution, origin, width or height differs");
-    if (navfield && (lom_navfield_get_geometry(navfield, &g) != LOM_OK || !same_geometry(g, r->geo)))
-        return fail(r, LOM_ERR_ARG, "region grid: the navigation field's resolution, origin, width or height differs");
+    // every producer's geometry first, then one text for the devices: the core's check is given this grid's own device
+    lom_occupancy_geometry og{}, cg{}, ng{};  // (one that cannot be read stays zero, which differs)
+    (void)lom_occupancy_get_geometry(occupancy, &og);
+    if (clearance) (void)lom_clearance_get_geometry(clearance, &cg);
+    if (navfield) (void)lom_navfield_get_geometry(navfield, &ng);
+    int rc;
+    if ((rc = plane_check_producer(r, kName, "occupancy grid", og, r->device)) != LOM_OK ||
+        (clearance && (rc = plane_check_producer(r, kName, "clearance grid", cg, r->device)) != LOM_OK) ||
+        (navfield && (rc = plane_check_producer(r, kName, "navigation field", ng, r->device)) != LOM_OK))
+        return rc;
     if (lom_occupancy_device(occupancy) != r->device || (clearance && lom_clearance_device(clearance) != r->device) ||
         (navfield && lom_navfield_device(navfield) != r->device))
         return fail(r, LOM_ERR_ARG, "region grid: a grid lives on another device");
     LOM_HIP(r, hipSetDevice(r->device));
-    // the producers leave their planes on their own streams; this stream reads them behind an event each
+    // the hand-off of plane_handle.hpp, once per producer: read behind it, extract, release to it
     const int8_t *d_plane = nullptr, *d_cost = nullptr;
     const uint32_t *d_pot = nullptr;
     if (lom_occupancy_classify_device(occupancy, rule, &d_plane) != LOM_OK || !d_plane)
-        return fail(r, LOM_ERR_HIP, (std::string("region grid: lom_occupancy_classify_device: ") + lom_occupancy_last_error(occupancy)).c_str());
-    LOM_HIP(r, hipEventRecord(r->in_ev[0], (hipStream_t)lom_occupancy_stream(occupancy)));
-    LOM_HIP(r, hipStreamWaitEvent(r->stream, r->in_ev[0], 0));
+        return plane_fail_producer(r, kName, "lom_occupancy_classify_device", lom_occupancy_last_error(occupancy));
+    if ((rc = plane_read_behind(r, 0, lom_occupancy_stream(occupancy))) != LOM_OK) return rc;
     if (clearance) {
         if (lom_clearance_cost_device(clearance, &d_cost) != LOM_OK || !d_cost)
-            return fail(r, LOM_ERR_HIP, (std::string("region grid: lom_clearance_cost_device: ") + lom_clearance_last_error(clearance)).c_str());
-        LOM_HIP(r, hipEventRecord(r->in_ev[1], (hipStream_t)lom_clearance_stream(clearance)));
-        LOM_HIP(r, hipStreamWaitEvent(r->stream, r->in_ev[1], 0));
+            return plane_fail_producer(r, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
+        if ((rc = plane_read_behind(r, 1, lom_clearance_stream(clearance))) != LOM_OK) return rc;
     }
     if (navfield) {
         if (lom_navfield_potential_device(navfield, &d_pot) != LOM_OK || !d_pot)
-            return fail(r, LOM_ERR_HIP, (std::string("region grid: lom_navfield_potential_device: ") + lom_navfield_last_error(navfield)).c_str());
-        LOM_HIP(r, hipEventRecord(r->in_ev[2], (hipStream_t)lom_navfield_stream(navfield)));
-        LOM_HIP(r, hipStreamWaitEvent(r->stream, r->in_ev[2], 0));
+            return plane_fail_producer(r, kName, "lom_navfield_potential_device", lom_navfield_last_error(navfield));
+        if ((rc = plane_read_behind(r, 2, lom_navfield_stream(navfield))) != LOM_OK) return rc;
     }
-    const int rc = extract_on_device(r, d_plane, d_cost, d_pot, *params, summary);
-    if (rc != LOM_OK) return rc;
-    // and what a producer does next to its plane comes behind this extract's reads
-    if (lom_occupancy_wait_event(occupancy, r->done_ev) != LOM_OK) return fail(r, LOM_ERR_HIP, "region grid: lom_occupancy_wait_event");
-    if (clearance && lom_clearance_wait_event(clearance, r->done_ev) != LOM_OK) return fail(r, LOM_ERR_HIP, "region grid: lom_clearance_wait_event");
-    if (navfield && lom_navfield_wait_event(navfield, r->done_ev) != LOM_OK) return fail(r, LOM_ERR_HIP, "region grid: lom_navfield_wait_event");
-    return LOM_OK;
+    if ((rc = extract_on_device(r, d_plane, d_cost, d_pot, *params, summary)) != LOM_OK) return rc;
+    if ((rc = plane_release(r, kName, occupancy, lom_occupancy_wait_event, "lom_occupancy_wait_event")) != LOM_OK) return rc;
+    if (clearance && (rc = plane_release(r, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event")) != LOM_OK) return rc;
+    return navfield ? plane_release(r, kName, navfield, lom_navfield_wait_event, "lom_navfield_wait_event") : LOM_OK;
 }
 
 int lom_regions_labels(lom_regions *r, uint32_t *out, size_t cap)
 {
     if (!r || (cap && !out)) return LOM_ERR_ARG;
-    const size_t n = std::min(cap, r->n_cells());
-    if (!n) return LOM_OK;
-    LOM_HIP(r, hipSetDevice(r->device));
-    LOM_HIP(r, hipMemcpyAsync(out, r->labels.p, n * 4, hipMemcpyDeviceToHost, r->stream));
-    LOM_HIP(r, hipStreamSynchronize(r->stream));
-    return LOM_OK;
+    return plane_copy_out(r, out, r->labels, std::min(cap, r->n_cells()) * 4);
 }
 
 int lom_regions_labels_device(lom_regions *r, const uint32_t **d_out)

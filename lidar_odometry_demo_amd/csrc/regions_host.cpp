@@ -11,12 +11,6 @@ namespace regions {
 static_assert(sizeof(lom_regions_record) == 48 && sizeof(lom_regions_params) == 20 && sizeof(lom_regions_summary) == 40,
               "the layouts the header documents");
 
-bool geometry_ok(const lom_occupancy_geometry *g)
-{
-    return g && std::isfinite(g->resolution) && g->resolution > 0.f && std::isfinite(g->origin_x) && std::isfinite(g->origin_y) &&
-           g->width >= 1u && g->width <= kMaxSide && g->height >= 1u && g->height <= kMaxSide;
-}
-
 bool params_ok(const lom_regions_params *p, bool have_potential)
 {
     if (!p || (p->kind != LOM_REGIONS_BYTES && p->kind != LOM_REGIONS_FRONTIER)) return false;

@@ -8,11 +8,11 @@
 #include <vector>
 
 #include "../../include/lidar_odometry_amd.h"
+#include "plane_geometry.hpp"
 
 namespace lom {
 namespace regions {
 
-constexpr uint32_t kMaxSide = 8192;           // cells per axis: a linear index fits 26 bits
 constexpr uint32_t kThreads = 256;            // every kernel runs workgroups of four waves
 constexpr uint32_t kTileCols = 64;            // a tile of k_reg_label_tile: one bitmap word wide ...
 constexpr uint32_t kTileRowsMax = 32;         // ... and 1, 8 or 32 rows high
@@ -37,8 +37,7 @@ struct Plan {
     uint32_t scan_blocks;               // workgroups of k_reg_scan_partial, <= 1024
 };
 
-// resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192
-bool geometry_ok(const lom_occupancy_geometry *g);
+using plane::geometry_ok;  // the rule of all four planning grids
 // a known kind; lo <= hi under LOM_REGIONS_BYTES; 0 <= max_cost <= 99; min_cells >= 1; a known rank, the potential's
 // only with a potential; known flags only
 bool params_ok(const lom_regions_params *p, bool have_potential);

@@ -2,16 +2,15 @@
 // the window of unknown cells each sees on request, and a greedy next-best-view selection over those windows.
 // Definitions: include/lidar_odometry_amd.h ("visibility grid"); kernels: k_visibility.hpp; host planning (value ranges,
 // the table, window sizes, launch shapes, the key): visibility_host.cpp; DESIGN.md 7o.  A handle family of its own on the
-// DeviceHandle core; no default path launches any of this.
+// PlaneHandle core (plane_handle.hpp); no default path launches any of this.
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <string>
 #include <vector>
 
-#include "device_handle.hpp"
 #include "k_visibility.hpp"
 #include "occupancy_host.hpp"
+#include "plane_handle.hpp"
 #include "visibility_host.hpp"
 
 using namespace lom;
@@ -24,8 +23,7 @@ static_assert(LOM_NAV_UNREACHED == kVisUnreached && LOM_VIS_END_INVALID == VIS_I
 static_assert(sizeof(VisRecord) == sizeof(lom_visibility_record) && sizeof(VisPick) == sizeof(lom_visibility_pick), "the records' layouts");
 
 // The visibility grid owns its stream and every buffer below.
-struct lom_visibility : lom::DeviceHandle {
-    lom_occupancy_geometry geo{};
+struct lom_visibility : lom::PlaneHandle {  // in_ev: the producer's of the call, the occupancy grid's or the navigation field's
     lom::DeviceBuf plane;                     // its own copy of the last cast's plane, i8 per cell
     lom::DeviceBuf table;                     // the direction table of table_beams beams, grow-only
     lom::DeviceBuf viewpoints, records;       // per viewpoint, grow-only
@@ -35,8 +33,6 @@ struct lom_visibility : lom::DeviceHandle {
     lom::DeviceBuf keys;                      // per round: the keys (u64), behind them the picks
     lom::DeviceBuf words;                     // the summary words
     lom::PinnedBuf h_words;                   // the summary words, or a selection's keys and picks, on their way out
-    hipEvent_t done_ev = nullptr;             // recorded behind the copy of a producer's plane, for its stream to wait on
-    hipEvent_t in_ev = nullptr;               // recorded behind a producer's plane, for this stream to wait on
     uint64_t max_window_bytes = visibility::kMaxWindowBytesDefault;  // LOM_VIS_OPT_MAX_WINDOW_BYTES
     uint32_t waves = visibility::kWavesDefault;                      // LOM_VIS_OPT_TEST_WAVES
     bool no_lds = false;                                             // LOM_VIS_OPT_TEST_NO_LDS
@@ -48,13 +44,13 @@ struct lom_visibility : lom::DeviceHandle {
     bool have_windows = false, have_beams = false;
     lom_visibility_summary summary{};
     lom_visibility_call_stats stats{};
-
-    size_t n_cells() const { return (size_t)geo.width * geo.height; }
 };
 
 namespace {
 
 thread_local std::string g_visibility_create_error;
+
+constexpr const char *kName = "visibility grid";  // the head of the texts of the plane-handle core
 
 constexpr size_t kPinnedBytes = (size_t)visibility::kSelectMax * (8 + sizeof(lom_visibility_pick));
 
@@ -207,12 +203,6 @@ int select_on_device(lom_visibility *v, const lom_visibility_select_params &s, c
     return LOM_OK;
 }
 
-bool same_geometry(const lom_occupancy_geometry &a, const lom_occupancy_geometry &b)
-{
-    return std::memcmp(&a.resolution, &b.resolution, 4) == 0 && std::memcmp(&a.origin_x, &b.origin_x, 4) == 0 &&
-           std::memcmp(&a.origin_y, &b.origin_y, 4) == 0 && a.width == b.width && a.height == b.height;
-}
-
 }  // namespace
 
 extern "C" {
@@ -220,22 +210,11 @@ extern "C" {
 int lom_visibility_create(const lom_occupancy_geometry *geometry, int device, lom_visibility **out)
 {
     if (!out) return LOM_ERR_ARG;
-    *out = nullptr;
-    if (!visibility::geometry_ok(geometry))
-        return create_fail(g_visibility_create_error, LOM_ERR_ARG,
-                           "visibility grid geometry: resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192");
-    if (const int rc = check_device(device, g_visibility_create_error); rc != LOM_OK) return rc;
-    lom_visibility *v = new (std::nothrow) lom_visibility();
-    if (!v) return create_fail(g_visibility_create_error, LOM_ERR_OOM, "host allocation");
-    v->device = device;
-    v->geo = *geometry;
+    lom_visibility *v = nullptr;
+    int rc = plane_new(geometry, device, g_visibility_create_error, kName, "visibility grid setup", 1, &v);
+    if (rc != LOM_OK) return rc;
     const visibility::Plan pl = visibility::plan(geometry->width, geometry->height, 0, visibility::kWavesDefault, false, 0);
-    int rc = LOM_OK;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->done_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->in_ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = alloc(v->h_words, kPinnedBytes, hipHostMallocDefault);
+    const hipError_t e = alloc(v->h_words, kPinnedBytes, hipHostMallocDefault);
     if (e != hipSuccess) rc = create_fail(g_visibility_create_error, LOM_ERR_HIP, "visibility grid setup", e);
     if (rc == LOM_OK && (alloc(v->plane, v->n_cells()) != hipSuccess || alloc(v->covered, (size_t)pl.covered_words * 4) != hipSuccess ||
                          alloc(v->words, (size_t)VW_COUNT * 8) != hipSuccess))
@@ -248,18 +227,8 @@ int lom_visibility_create(const lom_occupancy_geometry *geometry, int device, lo
     return LOM_OK;
 }
 
-void lom_visibility_destroy(lom_visibility *v)
-{
-    if (!v) return;
-    (void)hipSetDevice(v->device);
-    if (v->stream) (void)hipStreamSynchronize(v->stream);
-    for (hipEvent_t ev : {v->done_ev, v->in_ev})
-        if (ev) (void)hipEventDestroy(ev);
-    if (v->stream) (void)hipStreamDestroy(v->stream);
-    delete v;  // the buffers go with it
-}
-
-const char *lom_visibility_last_error(const lom_visibility *v) { return v ? v->error.c_str() : g_visibility_create_error.c_str(); }
+void lom_visibility_destroy(lom_visibility *v) { plane_destroy(v); }
+const char *lom_visibility_last_error(const lom_visibility *v) { return plane_last_error(v, g_visibility_create_error); }
 
 int lom_visibility_clear(lom_visibility *v)
 {
@@ -271,23 +240,10 @@ int lom_visibility_clear(lom_visibility *v)
     return LOM_OK;
 }
 
-int lom_visibility_get_geometry(const lom_visibility *v, lom_occupancy_geometry *out)
-{
-    if (!v || !out) return LOM_ERR_ARG;
-    *out = v->geo;
-    return LOM_OK;
-}
-
-void *lom_visibility_stream(lom_visibility *v) { return v ? (void *)v->stream : nullptr; }
-int lom_visibility_device(const lom_visibility *v) { return v ? v->device : LOM_ERR_ARG; }
-
-int lom_visibility_wait_event(lom_visibility *v, void *hip_event)
-{
-    if (!v || !hip_event) return LOM_ERR_ARG;
-    LOM_HIP(v, hipSetDevice(v->device));
-    LOM_HIP(v, hipStreamWaitEvent(v->stream, (hipEvent_t)hip_event, 0));
-    return LOM_OK;
-}
+int lom_visibility_get_geometry(const lom_visibility *v, lom_occupancy_geometry *out) { return plane_get_geometry(v, out); }
+void *lom_visibility_stream(lom_visibility *v) { return plane_stream(v); }
+int lom_visibility_device(const lom_visibility *v) { return plane_device(v); }
+int lom_visibility_wait_event(lom_visibility *v, void *hip_event) { return plane_wait_event(v, hip_event); }
 
 int lom_visibility_set_option(lom_visibility *v, int option, int64_t value)
 {
@@ -343,22 +299,20 @@ int lom_visibility_cast_from_occupancy(lom_visibility *v, lom_occupancy *occupan
     if (!v) return LOM_ERR_ARG;
     if (const char *why = cast_refusal(v, occupancy != nullptr, viewpoints, k, params)) return fail(v, LOM_ERR_ARG, why);
     if (!occupancy::rule_ok(rule)) return fail(v, LOM_ERR_ARG, "occupancy rule: min_free_scans >= 1, min_seen_scans >= 1");
-    lom_occupancy_geometry g;
-    if (lom_occupancy_get_geometry(occupancy, &g) != LOM_OK || !same_geometry(g, v->geo))
-        return fail(v, LOM_ERR_ARG, "visibility grid: the occupancy grid's resolution, origin, width or height differs");
-    if (lom_occupancy_device(occupancy) != v->device) return fail(v, LOM_ERR_ARG, "visibility grid: the occupancy grid lives on another device");
+    lom_occupancy_geometry g{};
+    (void)lom_occupancy_get_geometry(occupancy, &g);
+    int rc = plane_check_producer(v, kName, "occupancy grid", g, lom_occupancy_device(occupancy));
+    if (rc != LOM_OK) return rc;
     LOM_HIP(v, hipSetDevice(v->device));
-    if (const int rc = ensure_cast(v, k, *params); rc != LOM_OK) return rc;
-    // the producer leaves its plane on its own stream; this stream copies it behind an event
+    if ((rc = ensure_cast(v, k, *params)) != LOM_OK) return rc;
+    // the hand-off of plane_handle.hpp: read behind the occupancy grid -- a copy of its plane -- and release to it at once
     const int8_t *d_plane = nullptr;
     if (lom_occupancy_classify_device(occupancy, rule, &d_plane) != LOM_OK || !d_plane)
-        return fail(v, LOM_ERR_HIP, (std::string("visibility grid: lom_occupancy_classify_device: ") + lom_occupancy_last_error(occupancy)).c_str());
-    LOM_HIP(v, hipEventRecord(v->in_ev, (hipStream_t)lom_occupancy_stream(occupancy)));
-    LOM_HIP(v, hipStreamWaitEvent(v->stream, v->in_ev, 0));
+        return plane_fail_producer(v, kName, "lom_occupancy_classify_device", lom_occupancy_last_error(occupancy));
+    if ((rc = plane_read_behind(v, 0, lom_occupancy_stream(occupancy))) != LOM_OK) return rc;
     LOM_HIP(v, hipMemcpyAsync(v->plane.p, d_plane, v->n_cells(), hipMemcpyDeviceToDevice, v->stream));
-    // ... and what the producer does next to its plane comes behind that copy
     LOM_HIP(v, hipEventRecord(v->done_ev, v->stream));
-    if (lom_occupancy_wait_event(occupancy, v->done_ev) != LOM_OK) return fail(v, LOM_ERR_HIP, "visibility grid: lom_occupancy_wait_event");
+    if ((rc = plane_release(v, kName, occupancy, lom_occupancy_wait_event, "lom_occupancy_wait_event")) != LOM_OK) return rc;
     return cast_on_device(v, viewpoints, k, *params, summary);
 }
 
@@ -366,12 +320,7 @@ int lom_visibility_records(lom_visibility *v, lom_visibility_record *out, size_t
 {
     if (count) *count = 0;
     if (!v || (cap && !out)) return LOM_ERR_ARG;
-    const size_t n = std::min(cap, v->k);
-    if (n) {
-        LOM_HIP(v, hipSetDevice(v->device));
-        LOM_HIP(v, hipMemcpyAsync(out, v->records.p, n * sizeof(lom_visibility_record), hipMemcpyDeviceToHost, v->stream));
-        LOM_HIP(v, hipStreamSynchronize(v->stream));
-    }
+    if (const int rc = plane_copy_out(v, out, v->records, std::min(cap, v->k) * sizeof(lom_visibility_record)); rc != LOM_OK) return rc;
     if (count) *count = v->k;
     return LOM_OK;
 }
@@ -380,12 +329,7 @@ int lom_visibility_beams(lom_visibility *v, uint32_t *out, size_t cap)
 {
     if (!v || (cap && !out)) return LOM_ERR_ARG;
     if (!v->have_beams) return fail(v, LOM_ERR_STATE, "visibility beams: the last cast did not run under LOM_VIS_KEEP_BEAMS");
-    const size_t n = std::min(cap, v->k * v->params.beams);
-    if (!n) return LOM_OK;
-    LOM_HIP(v, hipSetDevice(v->device));
-    LOM_HIP(v, hipMemcpyAsync(out, v->beams.p, n * 4, hipMemcpyDeviceToHost, v->stream));
-    LOM_HIP(v, hipStreamSynchronize(v->stream));
-    return LOM_OK;
+    return plane_copy_out(v, out, v->beams, std::min(cap, v->k * v->params.beams) * 4);
 }
 
 int lom_visibility_windows_device(lom_visibility *v, const uint32_t **d_out, size_t *words_per_window)
@@ -406,11 +350,7 @@ int lom_visibility_windows(lom_visibility *v, uint32_t *out, size_t cap, size_t 
     if (!v->have_windows) return fail(v, LOM_ERR_STATE, "visibility windows: the last cast did not run under LOM_VIS_KEEP_WINDOWS");
     const size_t words = visibility::window(v->params.range_cells).words, n = std::min(cap, v->k * words);
     if (words_per_window) *words_per_window = words;
-    if (!n) return LOM_OK;
-    LOM_HIP(v, hipSetDevice(v->device));
-    LOM_HIP(v, hipMemcpyAsync(out, v->windows.p, n * 4, hipMemcpyDeviceToHost, v->stream));
-    LOM_HIP(v, hipStreamSynchronize(v->stream));
-    return LOM_OK;
+    return plane_copy_out(v, out, v->windows, n * 4);
 }
 
 int lom_visibility_select(lom_visibility *v, const lom_visibility_select_params *select, const uint32_t *cost, lom_visibility_pick *out,
@@ -438,10 +378,9 @@ int lom_visibility_select_from_navfield(lom_visibility *v, lom_navfield *navfiel
     if (!v) return LOM_ERR_ARG;
     if (!navfield) return fail(v, LOM_ERR_ARG, "visibility select: a navigation field");
     if (const int rc = select_refusal(v, select, out, picked); rc != LOM_OK) return rc;
-    lom_occupancy_geometry g;
-    if (lom_navfield_get_geometry(navfield, &g) != LOM_OK || !same_geometry(g, v->geo))
-        return fail(v, LOM_ERR_ARG, "visibility grid: the navigation field's resolution, origin, width or height differs");
-    if (lom_navfield_device(navfield) != v->device) return fail(v, LOM_ERR_ARG, "visibility grid: the navigation field lives on another device");
+    lom_occupancy_geometry g{};
+    (void)lom_navfield_get_geometry(navfield, &g);
+    if (const int rc = plane_check_producer(v, kName, "navigation field", g, lom_navfield_device(navfield)); rc != LOM_OK) return rc;
     if (!v->k) {
         v->stats = lom_visibility_call_stats{0, 0};
         return LOM_OK;
@@ -450,15 +389,14 @@ int lom_visibility_select_from_navfield(lom_visibility *v, lom_navfield *navfiel
     if (const int rc = ensure_select(v, *select); rc != LOM_OK) return rc;
     const uint32_t *d_pot = nullptr;
     if (lom_navfield_potential_device(navfield, &d_pot) != LOM_OK || !d_pot)
-        return fail(v, LOM_ERR_HIP, (std::string("visibility grid: lom_navfield_potential_device: ") + lom_navfield_last_error(navfield)).c_str());
-    LOM_HIP(v, hipEventRecord(v->in_ev, (hipStream_t)lom_navfield_stream(navfield)));
-    LOM_HIP(v, hipStreamWaitEvent(v->stream, v->in_ev, 0));
+        return plane_fail_producer(v, kName, "lom_navfield_potential_device", lom_navfield_last_error(navfield));
+    if (const int rc = plane_read_behind(v, 0, lom_navfield_stream(navfield)); rc != LOM_OK) return rc;
     hipLaunchKernelGGL(k_vis_costs, dim3(visibility::blocks_for(v->k)), dim3(kVisThreads), 0, v->stream, v->viewpoints.as<const int32_t>(), (uint32_t)v->k,
                        v->geo.width, v->geo.height, d_pot, v->cost.as<uint32_t>());
     LOM_HIP(v, hipGetLastError());
     // what the field does next to its potential comes behind that read
     LOM_HIP(v, hipEventRecord(v->done_ev, v->stream));
-    if (lom_navfield_wait_event(navfield, v->done_ev) != LOM_OK) return fail(v, LOM_ERR_HIP, "visibility grid: lom_navfield_wait_event");
+    if (const int rc = plane_release(v, kName, navfield, lom_navfield_wait_event, "lom_navfield_wait_event"); rc != LOM_OK) return rc;
     return select_on_device(v, *select, v->cost.as<const uint32_t>(), 1, out, picked);
 }
 

@@ -16,12 +16,6 @@ static_assert(sizeof(lom_visibility_params) == 20 && sizeof(lom_visibility_recor
 static_assert((uint64_t)(2u * kRangeMax + 1u) * (2u * kRangeMax + 1u) * kGainWeightMax <= (1ull << 30), "g * gain_weight <= 2^30");
 static_assert(kMaxViewpoints <= (1ull << kKeyIndexBits), "a viewpoint's index fits the key");
 
-bool geometry_ok(const lom_occupancy_geometry *g)
-{
-    return g && std::isfinite(g->resolution) && g->resolution > 0.f && std::isfinite(g->origin_x) && std::isfinite(g->origin_y) &&
-           g->width >= 1u && g->width <= kMaxSide && g->height >= 1u && g->height <= kMaxSide;
-}
-
 bool params_ok(const lom_visibility_params *p)
 {
     return p && p->beams >= kBeamsMin && p->beams <= kBeamsMax && p->range_cells <= kRangeMax && p->block_min >= kBlockMinLo &&

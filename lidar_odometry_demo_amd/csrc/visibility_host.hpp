@@ -7,11 +7,11 @@
 #include <cstdint>
 
 #include "../../include/lidar_odometry_amd.h"
+#include "plane_geometry.hpp"
 
 namespace lom {
 namespace visibility {
 
-constexpr uint32_t kMaxSide = 8192;            // cells per axis
 constexpr uint32_t kWaveLanes = 64;
 constexpr uint32_t kWavesDefault = 4;          // waves of a workgroup of k_vis_cast: 1 or 4 (LOM_VIS_OPT_TEST_WAVES)
 constexpr uint32_t kThreads = 256;             // every other kernel runs workgroups of four waves
@@ -49,8 +49,7 @@ struct Plan {
     uint32_t fill_blocks;      // ... and the workgroups that zero it
 };
 
-// resolution > 0 and finite, a finite origin, 1 <= width, height <= 8192
-bool geometry_ok(const lom_occupancy_geometry *g);
+using plane::geometry_ok;  // the rule of all four planning grids
 // 4 <= beams <= 8192, range_cells <= 254, 1 <= block_min <= 100, unknown_depth <= 65535, known flags only
 bool params_ok(const lom_visibility_params *p);
 // 1 <= n <= 1024, 1 <= gain_weight <= 4096, cost_shift <= 31, min_gain >= 1
