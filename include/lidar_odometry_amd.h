@@ -2059,6 +2059,153 @@ int lom_visibility_select_from_navfield(lom_visibility *v, lom_navfield *navfiel
 /* the launches and waits of the last cast or select (zeros before the first) */
 int lom_visibility_stats(const lom_visibility *v, lom_visibility_call_stats *out);
 
+/* ---- trajectory rollouts: velocity candidates scored on the cost plane (not in the reference) ------------------------
+ * lom_navfield_paths walks cells as a point robot; nothing above tests a robot's footprint at a heading or compares many
+ * candidate motions at once.  This handle family rolls K candidate command sequences out from each of M start states, tests
+ * the footprint at every pose against a cost plane, and picks, per state, the candidate with the best score: progress on
+ * a navigation potential against the cost gathered and the poses lost to a block.  One command per candidate is a dynamic
+ * window, several are sampled control sequences.  Nothing is launched unless a caller creates a rollout grid.  The
+ * definition, operation by operation (tests/rollout_ref.py restates it on Python integers; everything is an integer, so
+ * every comparison is exact):
+ *
+ * Units.  A position is Q15 cells, int32: 1 unit = 1/32768 cell, and the cell of a coordinate p is p >> 15 (arithmetic, so
+ * floor: -1 unit lies in cell -1).  An angle is 1/65536 turn, held mod 65536.  The direction table has T =
+ * LOM_ROLLOUT_TABLE = 4096 entries (C[b], S[b]), exactly lom_visibility_table(4096); an angle a reads entry a >> 4.
+ *
+ * Grid.  lom_occupancy_geometry, reused, with the planning grids' rules: row-major with y as the row.  r > 0 and finite, a
+ * finite origin, 1 <= width, height <= 8192; anything else is LOM_ERR_ARG.
+ *
+ * Planes.  The cost plane is a full-grid int8 plane: v >= lethal_min is lethal; v < 0 is unknown -- lethal when
+ * unknown_cost < 0, else it costs unknown_cost; any other cell costs v.  lom_clearance_cost's plane works with lethal_min
+ * 99 or 100.  The potential plane, optional, is u32 in lom_navfield_potential's form.
+ * lom_rollout_params: 1 <= segments <= 8 (L); 1 <= steps_per_segment <= 128 (Tn); S = L * Tn <= 1024; 1 <= lethal_min <=
+ * 100; -1 <= unknown_cost <= 98; min_steps <= S; progress_weight <= 256; cost_weight <= 4096; truncation_weight <= 2^20;
+ * flags of LOM_ROLLOUT_KEEP_RECORDS only; anything else is LOM_ERR_ARG.
+ * Inputs.  M states (x, y, a), 0 <= M <= 4096, with -2^29 <= x, y < 2^29 and a < 65536; K candidates of L commands (int16
+ * v, int16 w) each, candidate by candidate, 0 <= K <= 2^20 and M * K <= 2^22: v is Q15 cells per step, w angle units per
+ * step; F footprint samples (int32 fx, fy) in 1/256 cell in the robot's frame, 1 <= F <= 1024, |fx|, |fy| <= 16384;
+ * anything else is LOM_ERR_ARG.
+ *  1. Motion.  p_0 is the state.  For t = 0 .. S - 1 with l = t / Tn and b = a_t >> 4:  x_{t+1} = x_t + ((v_l * C[b] +
+ *     16384) >> 15), y_{t+1} = y_t + ((v_l * S[b] + 16384) >> 15), a_{t+1} = (a_t + w_l) & 65535.  Every product fits
+ *     int32.  The angle has a closed form per segment and the position is a prefix sum of integers, so no order of
+ *     summation changes it.
+ *  2. Pose test at p_t.  For each footprint sample, with b = a_t >> 4:  px = x_t + ((fx * C[b] - fy * S[b] + 128) >> 8),
+ *     py = y_t + ((fx * S[b] + fy * C[b] + 128) >> 8), cell (px >> 15, py >> 15).  The sample's code, in this order:
+ *     outside the grid LOM_ROLLOUT_EDGE (3); a lethal value LOM_ROLLOUT_COLLISION (2); unknown and lethal
+ *     LOM_ROLLOUT_UNKNOWN (1); else LOM_ROLLOUT_OK (0) with the cell's cost.  The pose's code is the greatest sample code,
+ *     its cost c_t the greatest cost over its OK samples.  A pose is free when its code is 0.
+ *  3. Record.  lom_rollout_record, 32 bytes, per state and candidate (state-major): free_poses = t*, the least blocked t
+ *     in 0 .. S, or S + 1 when there is none; reason, the code of pose t*, or 0; cost_sum and cost_max over the poses 0 ..
+ *     t* - 1; end_x, end_y, end_angle, pose t* - 1, or the state itself when t* = 0; end_potential, P at the end pose's
+ *     centre cell, LOM_NAV_UNREACHED outside the grid or without a potential plane.  A state whose own cell lies outside
+ *     the grid is invalid: all of its records have free_poses = 0, the reason LOM_ROLLOUT_INVALID (4), and the rest as
+ *     for t* = 0.
+ *  4. Score and pick.  P0 is P at the state's cell.  A candidate is admissible when free_poses > min_steps and, with a
+ *     potential plane, P0 and end_potential both differ from LOM_NAV_UNREACHED.  Its score, as int64:  s =
+ *     progress_weight * (P0 - end_potential) - cost_weight * cost_sum - truncation_weight * (S + 1 - free_poses); the first
+ *     term is 0 without a potential plane.  Per state, lom_rollout_pick: k, the greatest s among the admissible, ties to
+ *     the least k -- 0xFFFFFFFF, with score 0, when there is none; admissible, their count; score.  |s| < 2^41, so (s +
+ *     2^41) << 20 | (2^20 - 1 - k) orders the candidates as one unsigned 64-bit maximum.
+ *  5. Summary.  states (M); valid_states; candidates (M * K); admissible, over all states; states_without_pick.
+ * After create or lom_rollout_clear there is no state: no records.
+ *
+ * The result is a pure function of the planes, the parameters, the states, the commands and the footprint: it does not
+ * depend on the order in which lanes, waves or workgroups run, on the test switches below, or on early exits.
+ *
+ * lom_rollout_evaluate takes host planes of width * height cells; _evaluate_device planes in HBM, each complete when its
+ * event is (NULL: now), and reads them in place; _evaluate_from_grids reads lom_clearance_cost_device and, with a field,
+ * lom_navfield_potential_device in place and orders the streams by events in both directions -- a grid whose resolution,
+ * origin, width or height differ bit for bit, or that lives on another device, is LOM_ERR_ARG before any launch.  States,
+ * commands and footprint are host memory in every form; picks: M entries.  Every argument is validated and every
+ * allocation made before the first launch; a refused call changes nothing -- the records of the previous evaluation stay
+ * -- and zeroes the picks (the first min(M, 4096) of them) and the summary.  An evaluation is one host wait, whatever M,
+ * K and S.  Every call returns with its work done.  Calls on one handle are the caller's to serialise.  The error text is
+ * the handle's (lom_rollout_last_error). */
+#define LOM_ROLLOUT_TABLE 4096
+typedef struct lom_rollout lom_rollout;
+typedef struct {
+    uint32_t segments;          /* L, 1 .. 8 */
+    uint32_t steps_per_segment; /* Tn, 1 .. 128; S = L * Tn <= 1024 */
+    int32_t lethal_min;         /* the least lethal value, 1 .. 100 */
+    int32_t unknown_cost;       /* -1 .. 98; -1: unknown is lethal */
+    uint32_t min_steps;         /* 0 .. S */
+    uint32_t progress_weight;   /* 0 .. 256 */
+    uint32_t cost_weight;       /* 0 .. 4096 */
+    uint32_t truncation_weight; /* 0 .. 2^20 */
+    uint32_t flags;             /* LOM_ROLLOUT_KEEP_RECORDS */
+} lom_rollout_params;
+typedef struct {
+    int32_t x, y; /* Q15 cells */
+    uint32_t a;   /* 1/65536 turn, < 65536 */
+} lom_rollout_state;
+typedef struct {
+    uint32_t free_poses, reason;   /* offset 0, 4 */
+    uint32_t cost_sum, cost_max;   /* 8, 12 */
+    int32_t end_x, end_y;          /* 16, 20 */
+    uint32_t end_angle;            /* 24 */
+    uint32_t end_potential;        /* 28 */
+} lom_rollout_record;
+typedef struct {
+    uint32_t k;          /* the candidate's index, 0xFFFFFFFF: none */
+    uint32_t admissible; /* the state's admissible candidates */
+    int64_t score;
+} lom_rollout_pick;
+typedef struct {
+    uint64_t states, valid_states, candidates, admissible, states_without_pick;
+} lom_rollout_summary;
+typedef struct {
+    uint64_t launches, waits; /* kernel launches of the last evaluation, and the host's waits for them */
+} lom_rollout_call_stats;
+enum { LOM_ROLLOUT_KEEP_RECORDS = 1 };
+enum { LOM_ROLLOUT_OK = 0, LOM_ROLLOUT_UNKNOWN = 1, LOM_ROLLOUT_COLLISION = 2, LOM_ROLLOUT_EDGE = 3, LOM_ROLLOUT_INVALID = 4 };
+enum {
+    LOM_ROLLOUT_OPT_TEST_SERIAL = 1,       /* 1: the plain form, a lane per candidate stepping pose by pose; 0 or < 0: the
+                                              default, a lane per pose */
+    LOM_ROLLOUT_OPT_TEST_NO_LDS_PLANE = 2, /* 0: a window of the cost plane around the state is staged in LDS where that
+                                              window fits; 1 or < 0: the default, the plane is read in HBM */
+    LOM_ROLLOUT_OPT_TEST_WAVES = 3         /* waves of a workgroup of the lane-per-pose form: 1 or 4; <= 0: the default.  Test
+                                              switches: the bytes are the same. */
+};
+int lom_rollout_create(const lom_occupancy_geometry *geometry, int device, lom_rollout **out);
+void lom_rollout_destroy(lom_rollout *r);
+const char *lom_rollout_last_error(const lom_rollout *r); /* r == NULL: why the last create on this thread failed */
+int lom_rollout_clear(lom_rollout *r);                    /* no state, no records */
+int lom_rollout_get_geometry(const lom_rollout *r, lom_occupancy_geometry *out);
+void *lom_rollout_stream(lom_rollout *r); /* hipStream_t */
+int lom_rollout_device(const lom_rollout *r);
+int lom_rollout_wait_event(lom_rollout *r, void *hip_event);
+int lom_rollout_set_option(lom_rollout *r, int option, int64_t value);
+/* cost_plane: width * height int8; potential_or_null: width * height u32; states: m; commands: k * segments (v, w) int16
+ * pairs; footprint: f (fx, fy) int32 pairs; picks: m entries */
+int lom_rollout_evaluate(lom_rollout *r, const int8_t *cost_plane, const uint32_t *potential_or_null, const lom_rollout_state *states,
+                         size_t m, const int16_t *commands, size_t k, const int32_t *footprint, size_t f,
+                         const lom_rollout_params *params, lom_rollout_pick *picks, lom_rollout_summary *summary_or_null);
+int lom_rollout_evaluate_device(lom_rollout *r, const int8_t *d_cost_plane, void *cost_event_or_null, const uint32_t *d_potential_or_null,
+                                void *potential_event_or_null, const lom_rollout_state *states, size_t m, const int16_t *commands,
+                                size_t k, const int32_t *footprint, size_t f, const lom_rollout_params *params,
+                                lom_rollout_pick *picks, lom_rollout_summary *summary_or_null);
+int lom_rollout_evaluate_from_grids(lom_rollout *r, lom_clearance *clearance, lom_navfield *navfield_or_null,
+                                    const lom_rollout_state *states, size_t m, const int16_t *commands, size_t k,
+                                    const int32_t *footprint, size_t f, const lom_rollout_params *params, lom_rollout_pick *picks,
+                                    lom_rollout_summary *summary_or_null);
+/* step 3: at most `cap` records of the last evaluation go to `out` (may be NULL with cap 0), state-major; *count_or_null:
+ * M * K; LOM_ERR_STATE when the last evaluation did not run under LOM_ROLLOUT_KEEP_RECORDS */
+int lom_rollout_records(lom_rollout *r, lom_rollout_record *out, size_t cap, size_t *count_or_null);
+/* the launches and waits of the last evaluation (zeros before the first) */
+int lom_rollout_stats(const lom_rollout *r, lom_rollout_call_stats *out);
+/* Host-only helpers; none needs a handle or a device.
+ * A rectangular footprint, all in 1/256 cell: xs = -back, -back + spacing, ... while < front, then front; ys likewise over
+ * -half_width .. half_width; the lattice xs x ys (x-major), or with perimeter_only its border rows and columns.  At most
+ * `cap` pairs go to `out` (may be NULL with cap 0); *count: the samples.  0 <= front, back, half_width <= 16384, spacing
+ * >= 1, a count of at most 1024; anything else is LOM_ERR_ARG. */
+int lom_rollout_footprint_rectangle(int32_t front, int32_t back, int32_t half_width, int32_t spacing, int perimeter_only, int32_t *out,
+                                    size_t cap, size_t *count);
+/* x = floor(((double)x_m - origin_x) / resolution * 32768), y likewise, a = llround(yaw / (2 pi) * 65536) & 65535; a
+ * non-finite input or a position outside -2^29 .. 2^29 - 1 is LOM_ERR_ARG */
+int lom_rollout_state_from_pose(const lom_occupancy_geometry *geometry, float x_m, float y_m, float yaw, lom_rollout_state *out);
+/* step 1 alone: the S + 1 poses of one candidate (commands: segments pairs) go to `out` */
+int lom_rollout_poses(const lom_rollout_params *params, const lom_rollout_state *state, const int16_t *commands, lom_rollout_state *out);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;

@@ -1557,6 +1557,134 @@ private:
     uint32_t beams_ = 0;
 };
 
+// ---- RolloutGrid (not in the reference) --------------------------------------------------
+// Candidate command sequences rolled out from many start states at once: evaluate() tests the footprint at every pose
+// against a cost plane and picks, per state, the candidate with the best score; records() gives the record per state and
+// candidate.  Definitions: lidar_odometry_amd.h ("trajectory rollouts").
+using RolloutParams = lom_rollout_params;  // {segments, steps_per_segment, lethal_min, unknown_cost, min_steps, progress_weight, cost_weight, truncation_weight, flags}
+using RolloutState = lom_rollout_state;    // {x, y, a}
+using RolloutRecord = lom_rollout_record;
+using RolloutPick = lom_rollout_pick;
+using RolloutSummary = lom_rollout_summary;
+
+inline RolloutParams rolloutParams(uint32_t segments, uint32_t steps_per_segment, int32_t lethal_min = 100, int32_t unknown_cost = -1,
+                                   uint32_t min_steps = 0, uint32_t progress_weight = 1, uint32_t cost_weight = 1,
+                                   uint32_t truncation_weight = 0, uint32_t flags = 0)
+{
+    return RolloutParams{segments, steps_per_segment, lethal_min, unknown_cost, min_steps, progress_weight, cost_weight, truncation_weight, flags};
+}
+
+// (fx, fy) pairs in 1/256 cell
+inline std::vector<int32_t> rolloutFootprintRectangle(int32_t front, int32_t back, int32_t half_width, int32_t spacing, bool perimeter_only = false)
+{
+    size_t n = 0;
+    int rc = lom_rollout_footprint_rectangle(front, back, half_width, spacing, perimeter_only, nullptr, 0, &n);
+    std::vector<int32_t> out(2 * n);
+    if (rc == LOM_OK) rc = lom_rollout_footprint_rectangle(front, back, half_width, spacing, perimeter_only, out.data(), n, &n);
+    if (rc != LOM_OK) throw Error(rc, "rollout footprint: 0 <= front, back, half_width <= 16384, spacing >= 1, at most 1024 samples");
+    return out;
+}
+
+inline RolloutState rolloutStateFromPose(const lom_occupancy_geometry &geometry, float x_m, float y_m, float yaw)
+{
+    RolloutState s;
+    const int rc = lom_rollout_state_from_pose(&geometry, x_m, y_m, yaw, &s);
+    if (rc != LOM_OK) throw Error(rc, "rollout state: a valid geometry, a finite pose, -2^29 <= x, y < 2^29 in Q15 cells");
+    return s;
+}
+
+// the S + 1 poses of one candidate; commands: params.segments (v, w) pairs
+inline std::vector<RolloutState> rolloutPoses(const RolloutParams &params, const RolloutState &state, const int16_t *commands)
+{
+    const uint64_t steps = (uint64_t)params.segments * params.steps_per_segment;
+    std::vector<RolloutState> out(steps <= 1024 ? (size_t)steps + 1 : 1);
+    const int rc = lom_rollout_poses(&params, &state, commands, out.data());
+    if (rc != LOM_OK) throw Error(rc, "rollout poses: valid parameters, a valid state, `segments` commands");
+    return out;
+}
+
+class RolloutGrid {
+public:
+    struct Result {
+        std::vector<lom_rollout_pick> picks;  // one per state
+        lom_rollout_summary summary;
+    };
+    explicit RolloutGrid(const lom_occupancy_geometry &geometry, int device = 0)
+    {
+        const int rc = lom_rollout_create(&geometry, device, &h_);
+        if (rc != LOM_OK) throw Error(rc, lom_rollout_last_error(nullptr));
+    }
+    ~RolloutGrid() { lom_rollout_destroy(h_); }
+    RolloutGrid(const RolloutGrid &) = delete;
+    RolloutGrid &operator=(const RolloutGrid &) = delete;
+    lom_rollout *handle() const { return h_; }
+    lom_occupancy_geometry geometry() const
+    {
+        lom_occupancy_geometry g;
+        check(lom_rollout_get_geometry(h_, &g));
+        return g;
+    }
+    size_t size() const
+    {
+        const lom_occupancy_geometry g = geometry();
+        return (size_t)g.width * g.height;
+    }
+    int device() const { return lom_rollout_device(h_); }
+    void *stream() const { return lom_rollout_stream(h_); }
+    void waitEvent(void *hip_event) { check(lom_rollout_wait_event(h_, hip_event)); }
+    void clear() { check(lom_rollout_clear(h_)); }
+    void setOption(int option, int64_t value) { check(lom_rollout_set_option(h_, option, value)); }
+    // host planes of size() cells (potential may be NULL); commands: k * params.segments (v, w) pairs; footprint: f (fx, fy) pairs
+    Result evaluate(const int8_t *cost_plane, const uint32_t *potential, const lom_rollout_state *states, size_t m, const int16_t *commands,
+                    size_t k, const int32_t *footprint, size_t f, const lom_rollout_params &params)
+    {
+        Result r{std::vector<lom_rollout_pick>(m), {}};
+        check(lom_rollout_evaluate(h_, cost_plane, potential, states, m, commands, k, footprint, f, &params, r.picks.data(), &r.summary));
+        return r;
+    }
+    // planes in HBM, each complete when its event is (NULL: now)
+    Result evaluateDevice(const int8_t *d_cost_plane, void *cost_event, const uint32_t *d_potential, void *potential_event,
+                          const lom_rollout_state *states, size_t m, const int16_t *commands, size_t k, const int32_t *footprint, size_t f,
+                          const lom_rollout_params &params)
+    {
+        Result r{std::vector<lom_rollout_pick>(m), {}};
+        check(lom_rollout_evaluate_device(h_, d_cost_plane, cost_event, d_potential, potential_event, states, m, commands, k, footprint, f, &params,
+                                          r.picks.data(), &r.summary));
+        return r;
+    }
+    // the cost of a ClearanceGrid and the potential of a NavField (or none) of this geometry, read in HBM
+    Result evaluateFromGrids(ClearanceGrid &clearance, NavField *navfield, const lom_rollout_state *states, size_t m, const int16_t *commands,
+                             size_t k, const int32_t *footprint, size_t f, const lom_rollout_params &params)
+    {
+        Result r{std::vector<lom_rollout_pick>(m), {}};
+        check(lom_rollout_evaluate_from_grids(h_, clearance.handle(), navfield ? navfield->handle() : nullptr, states, m, commands, k, footprint, f,
+                                              &params, r.picks.data(), &r.summary));
+        return r;
+    }
+    std::vector<lom_rollout_record> records()
+    {
+        size_t n = 0;
+        check(lom_rollout_records(h_, nullptr, 0, &n));
+        std::vector<lom_rollout_record> out(n);
+        check(lom_rollout_records(h_, out.data(), out.size(), nullptr));
+        return out;
+    }
+    lom_rollout_call_stats stats() const
+    {
+        lom_rollout_call_stats s;
+        check(lom_rollout_stats(h_, &s));
+        return s;
+    }
+
+private:
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, lom_rollout_last_error(h_));
+        return rc;
+    }
+    lom_rollout *h_ = nullptr;
+};
+
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the
 // two key-frame exporters over lom_odometry_*.  lidar_point::PointXYZIRT (src/lidar_point_type.h:13-31)

@@ -1282,7 +1282,7 @@ class ElevationGrid(_PosedScanGrid):
 
 
 class _PlaneGrid(_Grid):
-    """What ClearanceGrid, NavField, RegionGrid and VisibilityGrid share (csrc/plane_handle.hpp): a dense 2-D grid of one
+    """What ClearanceGrid, NavField, RegionGrid, VisibilityGrid and RolloutGrid share (csrc/plane_handle.hpp): a dense 2-D grid of one
     lom_occupancy_geometry that takes planes of shape (height, width)."""
 
     _shape_text = "expected an int8 array of shape (height, width)"
@@ -1614,6 +1614,115 @@ def visibilityTable(beams):
     if rc != 0:
         raise LomError(int(rc), "visibility table: 4 <= beams <= 8192")
     return out
+
+
+class RolloutGrid(_PlaneGrid):
+    """Candidate command sequences rolled out from many start states at once (lom_rollout_*, include/lidar_odometry_amd.h
+    "trajectory rollouts"): evaluate() takes an int8 cost plane of shape (height, width) -- what ClearanceGrid.cost() writes
+    -- an optional uint32 potential (NavField.potential()), M states (capi.ROLLOUT_STATE, or an (M, 3) array of x, y, a), K
+    candidates of L (v, w) int16 commands as an array (K, L, 2), and F footprint samples (F, 2) int32, and returns the pick
+    per state (capi.ROLLOUT_PICK) and the summary.  records() gives the record per state and candidate."""
+
+    _family = "rollout"
+
+    @staticmethod
+    def _states(states):
+        s = np.asarray(states)
+        if s.dtype != capi.ROLLOUT_STATE:
+            s = np.asarray(states, np.int64).reshape(-1, 3)
+            out = np.zeros(len(s), capi.ROLLOUT_STATE)
+            if np.any(s[:, :2] < -2**31) or np.any(s[:, :2] >= 2**31) or np.any(s[:, 2] < 0) or np.any(s[:, 2] >= 2**32):
+                raise ValueError("rollout states: x, y int32 and a uint32")
+            out["x"], out["y"], out["a"] = s[:, 0], s[:, 1], s[:, 2]
+            s = out
+        return np.ascontiguousarray(s.reshape(-1))
+
+    def _evaluate(self, name, head, states, commands, footprint, params):
+        p, sm = rolloutParams(params), capi.RolloutSummary()
+        st = self._states(states)
+        cmd = np.ascontiguousarray(commands, np.int16)
+        per = 2 * max(int(p.segments), 1)  # int16 words of a candidate
+        # the library judges the parameters and, with `segments` out of range, reads no command; within it, it reads k * per
+        if 1 <= int(p.segments) <= 8 and ((cmd.ndim == 3 and cmd.shape[1:] != (per // 2, 2)) or cmd.size % per):
+            raise ValueError("rollout commands: (K, segments, 2) int16, or K * segments * 2 of them")
+        k = len(cmd) if cmd.ndim == 3 else cmd.size // per
+        fp = np.ascontiguousarray(footprint, np.int32).reshape(-1, 2)
+        picks = np.zeros(len(st), capi.ROLLOUT_PICK)
+        self._check(self._call(name, self._h, *head, st.ctypes.data if len(st) else None, len(st), cmd.ctypes.data if k else None,
+                               k, fp.ctypes.data if len(fp) else None, len(fp), C.byref(p),
+                               picks.ctypes.data if len(st) else None, C.byref(sm)))
+        return picks, sm.asdict()
+
+    def evaluate(self, cost_plane, potential, states, commands, footprint, params, device=False, cost_event=None,
+                 potential_event=None):
+        """lom_rollout_evaluate: host planes (potential may be None) -- or, with device=True, lom_rollout_evaluate_device:
+        the planes are device pointers, each complete when its event is.  Returns (picks, summary dict)."""
+        if device:
+            return self._evaluate("evaluate_device", (cost_plane, cost_event, potential, potential_event), states, commands,
+                                  footprint, params)
+        cost, pot = self._plane(cost_plane, np.int8), self._optional_plane(potential, np.uint32)
+        return self._evaluate("evaluate", (cost.ctypes.data, None if pot is None else pot.ctypes.data), states, commands, footprint,
+                              params)
+
+    def evaluateFromGrids(self, clearance, navfield, states, commands, footprint, params):
+        """lom_rollout_evaluate_from_grids: the cost of a ClearanceGrid and the potential of a NavField (or None) of this
+        geometry, read in HBM"""
+        return self._evaluate("evaluate_from_grids", (clearance.handle, None if navfield is None else navfield.handle), states,
+                              commands, footprint, params)
+
+    def records(self):
+        """the records of the last evaluation under capi.ROLLOUT_KEEP_RECORDS: an array of capi.ROLLOUT_RECORD, state-major"""
+        n = C.c_size_t()
+        self._check(self._call("records", self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, capi.ROLLOUT_RECORD)
+        self._check(self._call("records", self._h, out.ctypes.data if len(out) else None, len(out), None))
+        return out
+
+    def stats(self):
+        """capi.RolloutCallStats of the last evaluation as a dict: launches, waits"""
+        st = capi.RolloutCallStats()
+        self._check(self._call("stats", self._h, C.byref(st)))
+        return st.asdict()
+
+
+def rolloutParams(params):
+    """capi.RolloutParams from one, from a dict with its nine fields, or from a 9-tuple in the struct's order (segments,
+    steps_per_segment, lethal_min, unknown_cost, min_steps, progress_weight, cost_weight, truncation_weight, flags).  There
+    are no defaults."""
+    return _struct_from(capi.RolloutParams, params, "rollout parameters")
+
+
+def rolloutFootprintRectangle(front, back, half_width, spacing, perimeter_only=False):
+    """lom_rollout_footprint_rectangle: the (F, 2) int32 samples of a rectangle, all in 1/256 cell; needs no device"""
+    n = C.c_size_t()
+    args = (int(front), int(back), int(half_width), int(spacing), int(bool(perimeter_only)))
+    if capi.lib().lom_rollout_footprint_rectangle(*args, None, 0, C.byref(n)) != 0:
+        raise LomError(-1, "rollout footprint: 0 <= front, back, half_width <= 16384, spacing >= 1, at most 1024 samples")
+    out = np.zeros((n.value, 2), np.int32)
+    capi.lib().lom_rollout_footprint_rectangle(*args, out.ctypes.data, len(out), C.byref(n))
+    return out
+
+
+def rolloutStateFromPose(geometry, x_m, y_m, yaw):
+    """lom_rollout_state_from_pose: (x, y, a) of a pose in metres and radians on a grid given as capi.OccupancyGeometry or
+    its 5-tuple (resolution, origin_x, origin_y, width, height); needs no device"""
+    geo = geometry if isinstance(geometry, capi.OccupancyGeometry) else capi.OccupancyGeometry(*geometry)
+    out = np.zeros(1, capi.ROLLOUT_STATE)
+    if capi.lib().lom_rollout_state_from_pose(C.byref(geo), float(x_m), float(y_m), float(yaw), out.ctypes.data) != 0:
+        raise LomError(-1, "rollout state: a valid geometry, a finite pose, -2^29 <= x, y < 2^29 in Q15 cells")
+    return int(out["x"][0]), int(out["y"][0]), int(out["a"][0])
+
+
+def rolloutPoses(params, state, commands):
+    """lom_rollout_poses: the (S + 1, 3) int64 poses (x, y, a) of one candidate of L (v, w) commands; needs no device"""
+    p = rolloutParams(params)
+    st = RolloutGrid._states([state])
+    cmd = np.ascontiguousarray(commands, np.int16).reshape(-1, 2)
+    S = int(p.segments) * int(p.steps_per_segment)
+    out = np.zeros(max(S, 0) + 1 if S <= 1024 else 1, capi.ROLLOUT_STATE)
+    if len(cmd) != int(p.segments) or capi.lib().lom_rollout_poses(C.byref(p), st.ctypes.data, cmd.ctypes.data, out.ctypes.data) != 0:
+        raise LomError(-1, "rollout poses: valid parameters, a valid state, `segments` commands")
+    return np.stack([out["x"].astype(np.int64), out["y"].astype(np.int64), out["a"].astype(np.int64)], axis=1)
 
 
 class PoseGraph(_Handle):

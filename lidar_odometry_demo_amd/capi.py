@@ -451,6 +451,44 @@ VIS_END_INVALID, VIS_END_EDGE, VIS_END_RANGE, VIS_END_HIT, VIS_END_UNKNOWN, VIS_
 VIS_OPT_TEST_NO_LDS, VIS_OPT_TEST_WAVES, VIS_OPT_MAX_WINDOW_BYTES = 1, 2, 3
 
 
+class RolloutParams(C.Structure):
+    """lom_rollout_params"""
+    _fields_ = [("segments", C.c_uint32), ("steps_per_segment", C.c_uint32), ("lethal_min", C.c_int32), ("unknown_cost", C.c_int32),
+                ("min_steps", C.c_uint32), ("progress_weight", C.c_uint32), ("cost_weight", C.c_uint32),
+                ("truncation_weight", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class RolloutSummary(C.Structure):
+    """lom_rollout_summary"""
+    _fields_ = [("states", C.c_uint64), ("valid_states", C.c_uint64), ("candidates", C.c_uint64), ("admissible", C.c_uint64),
+                ("states_without_pick", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class RolloutCallStats(C.Structure):
+    """lom_rollout_call_stats"""
+    _fields_ = [("launches", C.c_uint64), ("waits", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# lom_rollout_state, 12 bytes, lom_rollout_record, 32 bytes, and lom_rollout_pick, 16 bytes
+ROLLOUT_STATE = np.dtype([("x", "<i4"), ("y", "<i4"), ("a", "<u4")])
+ROLLOUT_RECORD = np.dtype([("free_poses", "<u4"), ("reason", "<u4"), ("cost_sum", "<u4"), ("cost_max", "<u4"), ("end_x", "<i4"),
+                           ("end_y", "<i4"), ("end_angle", "<u4"), ("end_potential", "<u4")])
+ROLLOUT_PICK = np.dtype([("k", "<u4"), ("admissible", "<u4"), ("score", "<i8")])
+assert C.sizeof(RolloutParams) == 36 and C.sizeof(RolloutSummary) == 40 and C.sizeof(RolloutCallStats) == 16
+assert ROLLOUT_STATE.itemsize == 12 and ROLLOUT_RECORD.itemsize == 32 and ROLLOUT_PICK.itemsize == 16
+ROLLOUT_TABLE = 4096
+ROLLOUT_KEEP_RECORDS = 1
+ROLLOUT_OK, ROLLOUT_UNKNOWN, ROLLOUT_COLLISION, ROLLOUT_EDGE, ROLLOUT_INVALID = 0, 1, 2, 3, 4
+ROLLOUT_OPT_TEST_SERIAL, ROLLOUT_OPT_TEST_NO_LDS_PLANE, ROLLOUT_OPT_TEST_WAVES = 1, 2, 3
+ROLLOUT_NONE = 0xFFFFFFFF
+
+
 class Pc2Field(C.Structure):
     _fields_ = [("name", C.c_char_p), ("offset", C.c_uint32), ("datatype", C.c_uint8), ("count", C.c_uint32)]
 
@@ -555,6 +593,10 @@ EXPORTED = [
     "lom_visibility_set_option", "lom_visibility_table", "lom_visibility_cast", "lom_visibility_cast_device",
     "lom_visibility_cast_from_occupancy", "lom_visibility_records", "lom_visibility_beams", "lom_visibility_windows_device",
     "lom_visibility_windows",    "lom_visibility_select", "lom_visibility_select_from_navfield", "lom_visibility_stats",
+    "lom_rollout_create", "lom_rollout_destroy", "lom_rollout_last_error", "lom_rollout_clear", "lom_rollout_get_geometry",
+    "lom_rollout_stream", "lom_rollout_device", "lom_rollout_wait_event", "lom_rollout_set_option", "lom_rollout_evaluate",
+    "lom_rollout_evaluate_device", "lom_rollout_evaluate_from_grids", "lom_rollout_records", "lom_rollout_stats",
+    "lom_rollout_footprint_rectangle", "lom_rollout_state_from_pose", "lom_rollout_poses",
 ]
 # ... and the one it declares through a function type (the "scan archive and map assembly" section)
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
@@ -1042,6 +1084,29 @@ def lib():
     L.lom_visibility_select.argtypes = [vp, C.POINTER(VisibilitySelectParams), vp, vp, C.POINTER(C.c_size_t)]
     L.lom_visibility_select_from_navfield.argtypes = [vp, vp, C.POINTER(VisibilitySelectParams), vp, C.POINTER(C.c_size_t)]
     L.lom_visibility_stats.argtypes = [vp, C.POINTER(VisibilityCallStats)]
+    L.lom_rollout_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
+    L.lom_rollout_destroy.argtypes = [vp]
+    L.lom_rollout_destroy.restype = None
+    L.lom_rollout_last_error.argtypes = [vp]
+    L.lom_rollout_last_error.restype = C.c_char_p
+    L.lom_rollout_clear.argtypes = [vp]
+    L.lom_rollout_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
+    L.lom_rollout_stream.argtypes = [vp]
+    L.lom_rollout_stream.restype = vp
+    L.lom_rollout_device.argtypes = [vp]
+    L.lom_rollout_wait_event.argtypes = [vp, vp]
+    L.lom_rollout_set_option.argtypes = [vp, C.c_int, C.c_int64]
+    # states, m, commands, k, footprint, f, params, picks, summary: the tail of every evaluate form
+    tail = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(RolloutParams), vp, C.POINTER(RolloutSummary)]
+    L.lom_rollout_evaluate.argtypes = [vp, vp, vp] + tail
+    L.lom_rollout_evaluate_device.argtypes = [vp, vp, vp, vp, vp] + tail
+    L.lom_rollout_evaluate_from_grids.argtypes = [vp, vp, vp] + tail
+    L.lom_rollout_records.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.lom_rollout_stats.argtypes = [vp, C.POINTER(RolloutCallStats)]
+    L.lom_rollout_footprint_rectangle.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int, vp, C.c_size_t,
+                                                  C.POINTER(C.c_size_t)]
+    L.lom_rollout_state_from_pose.argtypes = [C.POINTER(OccupancyGeometry), C.c_float, C.c_float, C.c_float, vp]
+    L.lom_rollout_poses.argtypes = [C.POINTER(RolloutParams), vp, vp, vp]
     _lib = L
     return L
 
