@@ -605,30 +605,75 @@ struct CloudClassifier {
     }
 };
 
+// ---- handle owners (not in the reference) ---------------------------------------------------------------------
+// The base of every class below that owns one handle of a family of the C ABI with lom_<family>_destroy and
+// lom_<family>_last_error (VoxelGrid and LidarOdometry own more than that and stay on their own): the pointer, no copies,
+// handle(), the destroy, and check(), which throws with the handle's last error.  A constructor that throws leaves h_ null
+// for this destructor, and every lom_<family>_destroy returns at once for a null handle, so nobody tests h_.  The
+// destructor runs after the derived class's members are gone and reads none of them.
+template <typename H, auto Destroy, auto LastError>
+class Handle {
+public:
+    Handle(const Handle &) = delete;
+    Handle &operator=(const Handle &) = delete;
+    H *handle() const { return h_; }
+
+protected:
+    Handle() = default;
+    ~Handle() { Destroy(h_); }
+    void created(int rc) const  // a constructor's, with what lom_<family>_create returned
+    {
+        if (rc != LOM_OK) throw Error(rc, LastError(nullptr));
+    }
+    int64_t check(int64_t rc) const
+    {
+        if (rc < 0) throw Error((int)rc, LastError(h_));
+        return rc;
+    }
+    H *h_ = nullptr;
+};
+
+// ... and of the seven grids, by the nine entry points every grid family has: construction from a geometry G and a
+// device, geometry(), the cell count, clear(), setOption(), device(), stream() (a hipStream_t) and waitEvent() (the
+// grid's stream waits for a hipEvent_t before what is enqueued next)
+template <typename H, typename G, auto Create, auto Destroy, auto LastError, auto GetGeometry, auto Clear, auto SetOption, auto Device,
+          auto Stream, auto WaitEvent>
+class GridHandle : public Handle<H, Destroy, LastError> {
+public:
+    G geometry() const
+    {
+        G g;
+        this->check(GetGeometry(this->h_, &g));
+        return g;
+    }
+    void clear() { this->check(Clear(this->h_)); }
+    void setOption(int option, int64_t value) { this->check(SetOption(this->h_, option, value)); }
+    int device() const { return Device(this->h_); }
+    void *stream() const { return Stream(this->h_); }
+    void waitEvent(void *hip_event) { this->check(WaitEvent(this->h_, hip_event)); }
+
+protected:
+    GridHandle(const G &geometry, int device) { this->created(Create(&geometry, device, &this->h_)); }
+    size_t cellCount() const
+    {
+        const G g = geometry();
+        return (size_t)g.width * g.height;
+    }
+};
+
 // ---- classifier for frames without rings (not in the reference; lom_classify_neighbourhood) ----------------------
 using NeighbourhoodParams = lom_neighbourhood_params;  // {radius, index_cap, min_neighbours, max_variation, min_spread}
 
 // the per-frame front end on the device (lom_frontend_*): here as the owner of the neighbourhood classifier's workspace
-class FrontEnd {
+class FrontEnd : public Handle<lom_frontend, lom_frontend_destroy, lom_frontend_last_error> {
 public:
     explicit FrontEnd(int device = 0)
     {
         const int rc = lom_frontend_create(device, nullptr, &h_);
         if (rc != LOM_OK) throw Error(rc, "lom_frontend_create");
     }
-    ~FrontEnd() { lom_frontend_destroy(h_); }
-    FrontEnd(const FrontEnd &) = delete;
-    FrontEnd &operator=(const FrontEnd &) = delete;
-    lom_frontend *handle() const { return h_; }
     // LOM_CLASSIFIER_RINGS (params ignored) or LOM_CLASSIFIER_NEIGHBOURHOOD for the following lom_frontend_process calls
-    void setClassifier(int kind, const NeighbourhoodParams *params = nullptr)
-    {
-        const int rc = lom_frontend_set_classifier(h_, kind, params);
-        if (rc != LOM_OK) throw Error(rc, lom_frontend_last_error(h_));
-    }
-
-private:
-    lom_frontend *h_ = nullptr;
+    void setClassifier(int kind, const NeighbourhoodParams *params = nullptr) { check(lom_frontend_set_classifier(h_, kind, params)); }
 };
 
 // the stage alone: the planar points of `input` in input order, with normals; `details` (optional): one record per input point
@@ -658,17 +703,12 @@ inline PointCloud<PointNormal>::Ptr classifyNeighbourhood(FrontEnd &fe, const Po
 using PlaceParams = lom_place_params;  // {rings, sectors, max_range, z_floor}; there are no defaults
 using PlaceMatch = lom_place_match;    // {id, distance, shift}
 
-class PlaceDatabase {
+class PlaceDatabase : public Handle<lom_place_db, lom_place_db_destroy, lom_place_db_last_error> {
 public:
     explicit PlaceDatabase(const PlaceParams &params, size_t capacity_hint = 0, int device = 0) : params_(params)
     {
-        const int rc = lom_place_db_create(&params, device, capacity_hint, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_place_db_last_error(nullptr));
+        created(lom_place_db_create(&params, device, capacity_hint, &h_));
     }
-    ~PlaceDatabase() { lom_place_db_destroy(h_); }
-    PlaceDatabase(const PlaceDatabase &) = delete;
-    PlaceDatabase &operator=(const PlaceDatabase &) = delete;
-    lom_place_db *handle() const { return h_; }
     const PlaceParams &params() const { return params_; }
     size_t cells() const { return (size_t)params_.rings * params_.sectors; }
     size_t size() const { return (size_t)check(lom_place_db_size(h_)); }
@@ -726,13 +766,7 @@ public:
     double shiftYaw(uint32_t shift) const { return shiftYaw(params_, shift); }
 
 private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_place_db_last_error(h_));
-        return rc;
-    }
     PlaceParams params_;
-    lom_place_db *h_ = nullptr;
 };
 
 // ---- pose graph (lom_graph_*; not in the reference) --------------------------------------------------------
@@ -742,17 +776,12 @@ using GraphPose = lom_graph_pose;      // {t[3], q_wxyz[4]}, f64
 using GraphParams = lom_graph_params;  // {lambda0, gtol, xtol, pcg_rtol, max_outer, max_pcg}; there are no defaults
 using GraphStats = lom_graph_stats;
 
-class PoseGraph {
+class PoseGraph : public Handle<lom_graph, lom_graph_destroy, lom_graph_last_error> {
 public:
     explicit PoseGraph(size_t node_hint = 0, size_t edge_hint = 0, int device = 0)
     {
-        const int rc = lom_graph_create(device, node_hint, edge_hint, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_graph_last_error(nullptr));
+        created(lom_graph_create(device, node_hint, edge_hint, &h_));
     }
-    ~PoseGraph() { lom_graph_destroy(h_); }
-    PoseGraph(const PoseGraph &) = delete;
-    PoseGraph &operator=(const PoseGraph &) = delete;
-    lom_graph *handle() const { return h_; }
     void clear() { check(lom_graph_clear(h_)); }
     size_t nodeCount() const { return (size_t)check(lom_graph_node_count(h_)); }
     size_t edgeCount() const { return (size_t)check(lom_graph_edge_count(h_)); }
@@ -817,14 +846,6 @@ public:
         check(lom_graph_edge_chi2(h_, 0, (int64_t)out.size(), out.data()));
         return out;
     }
-
-private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_graph_last_error(h_));
-        return rc;
-    }
-    lom_graph *h_ = nullptr;
 };
 
 // ---- scan archive and map assembly (lom_archive_*, lom_map_assemble; not in the reference) -------------------
@@ -833,17 +854,12 @@ private:
 using AssembleParams = lom_assemble_params;  // {centre[3], radius}; radius <= 0 keeps everything
 using AssembleStats = lom_assemble_stats;
 
-class ScanArchive {
+class ScanArchive : public Handle<lom_archive, lom_archive_destroy, lom_archive_last_error> {
 public:
     explicit ScanArchive(size_t point_hint = 0, size_t scan_hint = 0, int device = 0)
     {
-        const int rc = lom_archive_create(device, point_hint, scan_hint, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_archive_last_error(nullptr));
+        created(lom_archive_create(device, point_hint, scan_hint, &h_));
     }
-    ~ScanArchive() { lom_archive_destroy(h_); }
-    ScanArchive(const ScanArchive &) = delete;
-    ScanArchive &operator=(const ScanArchive &) = delete;
-    lom_archive *handle() const { return h_; }
     void clear() { check(lom_archive_clear(h_)); }
     size_t size() const { return (size_t)check(lom_archive_scan_count(h_)); }
     size_t pointCount() const { return (size_t)check(lom_archive_point_count(h_)); }
@@ -884,14 +900,6 @@ public:
         if (rc != LOM_OK) throw Error(rc, "ScanArchive::rotationMatrix: a non-finite value or a zero quaternion");
         return R;
     }
-
-private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_archive_last_error(h_));
-        return rc;
-    }
-    lom_archive *h_ = nullptr;
 };
 
 inline lom_assemble_stats VoxelGrid::assemble(ScanArchive &archive, const std::vector<int64_t> &ids,
@@ -940,29 +948,13 @@ using OccupancyRule = lom_occupancy_rule;            // {min_free_scans, free_pe
 using OccupancyStats = lom_occupancy_stats;
 using OccupancySummary = lom_occupancy_summary;
 
-class OccupancyGrid {
+class OccupancyGrid
+    : public GridHandle<lom_occupancy, lom_occupancy_geometry, lom_occupancy_create, lom_occupancy_destroy, lom_occupancy_last_error,
+                        lom_occupancy_get_geometry, lom_occupancy_clear, lom_occupancy_set_option, lom_occupancy_device,
+                        lom_occupancy_stream, lom_occupancy_wait_event> {
 public:
-    explicit OccupancyGrid(const lom_occupancy_geometry &geometry, int device = 0)
-    {
-        const int rc = lom_occupancy_create(&geometry, device, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_occupancy_last_error(nullptr));
-    }
-    ~OccupancyGrid() { lom_occupancy_destroy(h_); }
-    OccupancyGrid(const OccupancyGrid &) = delete;
-    OccupancyGrid &operator=(const OccupancyGrid &) = delete;
-    lom_occupancy *handle() const { return h_; }
-    lom_occupancy_geometry geometry() const
-    {
-        lom_occupancy_geometry g;
-        check(lom_occupancy_get_geometry(h_, &g));
-        return g;
-    }
-    size_t cells() const
-    {
-        const lom_occupancy_geometry g = geometry();
-        return (size_t)g.width * g.height;
-    }
-    void clear() { check(lom_occupancy_clear(h_)); }
+    explicit OccupancyGrid(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
+    size_t cells() const { return cellCount(); }
     // the scans `ids` of the archive at `poses` vote
     lom_occupancy_stats integrate(ScanArchive &archive, const std::vector<int64_t> &ids, const std::vector<lom_graph_pose> &poses,
                                   const lom_occupancy_ray_params &params)
@@ -995,14 +987,6 @@ public:
         check(lom_occupancy_classify(h_, &rule, out.data(), out.size(), summary_or_null));
         return out;
     }
-
-private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_occupancy_last_error(h_));
-        return rc;
-    }
-    lom_occupancy *h_ = nullptr;
 };
 
 // ---- ElevationGrid (not in the reference) ---------------------------------------------
@@ -1017,7 +1001,10 @@ using ElevationCostParams = lom_elevation_cost_params;    // {max_slope, max_ste
 using ElevationStats = lom_elevation_stats;
 using ElevationSummary = lom_elevation_summary;
 
-class ElevationGrid {
+class ElevationGrid
+    : public GridHandle<lom_elevation, lom_elevation_geometry, lom_elevation_create, lom_elevation_destroy, lom_elevation_last_error,
+                        lom_elevation_get_geometry, lom_elevation_clear, lom_elevation_set_option, lom_elevation_device,
+                        lom_elevation_stream, lom_elevation_wait_event> {
 public:
     struct Cells {  // the accumulators, in quanta of 2^-8 m relative to z_ref
         std::vector<uint32_t> count;
@@ -1028,27 +1015,8 @@ public:
         std::vector<float> min, max, mean, slope, rough, step;
     };
 
-    explicit ElevationGrid(const lom_elevation_geometry &geometry, int device = 0)
-    {
-        const int rc = lom_elevation_create(&geometry, device, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_elevation_last_error(nullptr));
-    }
-    ~ElevationGrid() { lom_elevation_destroy(h_); }
-    ElevationGrid(const ElevationGrid &) = delete;
-    ElevationGrid &operator=(const ElevationGrid &) = delete;
-    lom_elevation *handle() const { return h_; }
-    lom_elevation_geometry geometry() const
-    {
-        lom_elevation_geometry g;
-        check(lom_elevation_get_geometry(h_, &g));
-        return g;
-    }
-    size_t size() const
-    {
-        const lom_elevation_geometry g = geometry();
-        return (size_t)g.width * g.height;
-    }
-    void clear() { check(lom_elevation_clear(h_)); }
+    explicit ElevationGrid(const lom_elevation_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
+    size_t size() const { return cellCount(); }
     // the scans `ids` of the archive at `poses`
     lom_elevation_stats integrate(ScanArchive &archive, const std::vector<int64_t> &ids, const std::vector<lom_graph_pose> &poses,
                                   const lom_elevation_point_params &params)
@@ -1092,14 +1060,6 @@ public:
         check(lom_elevation_cost(h_, &lp, &cp, out.data(), out.size(), summary_or_null));
         return out;
     }
-
-private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_elevation_last_error(h_));
-        return rc;
-    }
-    lom_elevation *h_ = nullptr;
 };
 
 // ---- ClearanceGrid (not in the reference) ---------------------------------------------
@@ -1116,35 +1076,18 @@ inline ClearanceParams clearanceParams(float inflation_radius, float inscribed_r
     return ClearanceParams{inflation_radius, inscribed_radius, decay, flags};
 }
 
-class ClearanceGrid {
+class ClearanceGrid
+    : public GridHandle<lom_clearance, lom_occupancy_geometry, lom_clearance_create, lom_clearance_destroy, lom_clearance_last_error,
+                        lom_clearance_get_geometry, lom_clearance_clear, lom_clearance_set_option, lom_clearance_device,
+                        lom_clearance_stream, lom_clearance_wait_event> {
 public:
     struct Query {  // NaN and -1 for a point outside the grid
         std::vector<float> distance;
         std::vector<int8_t> cost;
     };
 
-    explicit ClearanceGrid(const lom_occupancy_geometry &geometry, int device = 0)
-    {
-        const int rc = lom_clearance_create(&geometry, device, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_clearance_last_error(nullptr));
-    }
-    ~ClearanceGrid() { lom_clearance_destroy(h_); }
-    ClearanceGrid(const ClearanceGrid &) = delete;
-    ClearanceGrid &operator=(const ClearanceGrid &) = delete;
-    lom_clearance *handle() const { return h_; }
-    lom_occupancy_geometry geometry() const
-    {
-        lom_occupancy_geometry g;
-        check(lom_clearance_get_geometry(h_, &g));
-        return g;
-    }
-    size_t size() const
-    {
-        const lom_occupancy_geometry g = geometry();
-        return (size_t)g.width * g.height;
-    }
-    void clear() { check(lom_clearance_clear(h_)); }
-    void setOption(int option, int64_t value) { check(lom_clearance_set_option(h_, option, value)); }
+    explicit ClearanceGrid(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
+    size_t size() const { return cellCount(); }
     // host planes of size() cells each; either may be NULL
     lom_clearance_summary update(const int8_t *occ_or_null, const int8_t *elev_or_null, const lom_clearance_params &params,
                                  const lom_clearance_window *window_or_null = nullptr)
@@ -1191,14 +1134,6 @@ public:
         check(lom_clearance_query(h_, xy, n, q.distance.data(), q.cost.data()));
         return q;
     }
-
-private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_clearance_last_error(h_));
-        return rc;
-    }
-    lom_clearance *h_ = nullptr;
 };
 
 // ---- NavField (not in the reference) ---------------------------------------------------
@@ -1214,35 +1149,18 @@ inline NavFieldParams navfieldParams(uint32_t neutral, uint32_t factor, uint32_t
     return NavFieldParams{neutral, factor, unknown_cost, max_passable, flags};
 }
 
-class NavField {
+class NavField
+    : public GridHandle<lom_navfield, lom_occupancy_geometry, lom_navfield_create, lom_navfield_destroy, lom_navfield_last_error,
+                        lom_navfield_get_geometry, lom_navfield_clear, lom_navfield_set_option, lom_navfield_device, lom_navfield_stream,
+                        lom_navfield_wait_event> {
 public:
     struct Paths {  // cells: [K, cap] (ix, iy) pairs; lengths: the full length per start, 0 where none was walked
         std::vector<uint16_t> cells;
         std::vector<uint32_t> lengths;
     };
 
-    explicit NavField(const lom_occupancy_geometry &geometry, int device = 0)
-    {
-        const int rc = lom_navfield_create(&geometry, device, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_navfield_last_error(nullptr));
-    }
-    ~NavField() { lom_navfield_destroy(h_); }
-    NavField(const NavField &) = delete;
-    NavField &operator=(const NavField &) = delete;
-    lom_navfield *handle() const { return h_; }
-    lom_occupancy_geometry geometry() const
-    {
-        lom_occupancy_geometry g;
-        check(lom_navfield_get_geometry(h_, &g));
-        return g;
-    }
-    size_t size() const
-    {
-        const lom_occupancy_geometry g = geometry();
-        return (size_t)g.width * g.height;
-    }
-    void clear() { check(lom_navfield_clear(h_)); }
-    void setOption(int option, int64_t value) { check(lom_navfield_set_option(h_, option, value)); }
+    explicit NavField(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
+    size_t size() const { return cellCount(); }
     // a host plane of size() cells; goals: n pairs of int32 cells
     lom_navfield_summary solve(const int8_t *plane, const lom_navfield_params &params, const int32_t *goal_cells, size_t n)
     {
@@ -1292,14 +1210,6 @@ public:
         check(lom_navfield_stats(h_, &s));
         return s;
     }
-
-private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_navfield_last_error(h_));
-        return rc;
-    }
-    lom_navfield *h_ = nullptr;
 };
 
 inline std::vector<uint32_t> navfieldCellCosts(const lom_navfield_params &params)
@@ -1324,30 +1234,13 @@ inline RegionsParams regionsParams(int32_t kind, int8_t lo, int8_t hi, int8_t ma
     return RegionsParams{kind, lo, hi, max_cost, min_cells, rank, flags};
 }
 
-class RegionGrid {
+class RegionGrid
+    : public GridHandle<lom_regions, lom_occupancy_geometry, lom_regions_create, lom_regions_destroy, lom_regions_last_error,
+                        lom_regions_get_geometry, lom_regions_clear, lom_regions_set_option, lom_regions_device, lom_regions_stream,
+                        lom_regions_wait_event> {
 public:
-    explicit RegionGrid(const lom_occupancy_geometry &geometry, int device = 0)
-    {
-        const int rc = lom_regions_create(&geometry, device, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_regions_last_error(nullptr));
-    }
-    ~RegionGrid() { lom_regions_destroy(h_); }
-    RegionGrid(const RegionGrid &) = delete;
-    RegionGrid &operator=(const RegionGrid &) = delete;
-    lom_regions *handle() const { return h_; }
-    lom_occupancy_geometry geometry() const
-    {
-        lom_occupancy_geometry g;
-        check(lom_regions_get_geometry(h_, &g));
-        return g;
-    }
-    size_t size() const
-    {
-        const lom_occupancy_geometry g = geometry();
-        return (size_t)g.width * g.height;
-    }
-    void clear() { check(lom_regions_clear(h_)); }
-    void setOption(int option, int64_t value) { check(lom_regions_set_option(h_, option, value)); }
+    explicit RegionGrid(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
+    size_t size() const { return cellCount(); }
     // host planes of size() cells; cost and potential may be NULL
     lom_regions_summary extract(const int8_t *plane, const lom_regions_params &params, const int8_t *cost = nullptr,
                                 const uint32_t *potential = nullptr)
@@ -1402,14 +1295,6 @@ public:
         check(lom_regions_stats(h_, &s));
         return s;
     }
-
-private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_regions_last_error(h_));
-        return rc;
-    }
-    lom_regions *h_ = nullptr;
 };
 
 // ---- VisibilityGrid (not in the reference) ----------------------------------------------
@@ -1436,33 +1321,13 @@ inline std::vector<int32_t> visibilityTable(uint32_t beams)
     return out;
 }
 
-class VisibilityGrid {
+class VisibilityGrid
+    : public GridHandle<lom_visibility, lom_occupancy_geometry, lom_visibility_create, lom_visibility_destroy, lom_visibility_last_error,
+                        lom_visibility_get_geometry, lom_visibility_clear, lom_visibility_set_option, lom_visibility_device,
+                        lom_visibility_stream, lom_visibility_wait_event> {
 public:
-    explicit VisibilityGrid(const lom_occupancy_geometry &geometry, int device = 0)
-    {
-        const int rc = lom_visibility_create(&geometry, device, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_visibility_last_error(nullptr));
-    }
-    ~VisibilityGrid() { lom_visibility_destroy(h_); }
-    VisibilityGrid(const VisibilityGrid &) = delete;
-    VisibilityGrid &operator=(const VisibilityGrid &) = delete;
-    lom_visibility *handle() const { return h_; }
-    lom_occupancy_geometry geometry() const
-    {
-        lom_occupancy_geometry g;
-        check(lom_visibility_get_geometry(h_, &g));
-        return g;
-    }
-    size_t size() const
-    {
-        const lom_occupancy_geometry g = geometry();
-        return (size_t)g.width * g.height;
-    }
-    int device() const { return lom_visibility_device(h_); }
-    void *stream() const { return lom_visibility_stream(h_); }
-    void waitEvent(void *hip_event) { check(lom_visibility_wait_event(h_, hip_event)); }
-    void clear() { check(lom_visibility_clear(h_)); }
-    void setOption(int option, int64_t value) { check(lom_visibility_set_option(h_, option, value)); }
+    explicit VisibilityGrid(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
+    size_t size() const { return cellCount(); }
     // a host plane of size() cells; viewpoints: k (ix, iy) pairs
     lom_visibility_summary cast(const int8_t *plane, const int32_t *viewpoints, size_t k, const lom_visibility_params &params)
     {
@@ -1548,12 +1413,6 @@ public:
     }
 
 private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_visibility_last_error(h_));
-        return rc;
-    }
-    lom_visibility *h_ = nullptr;
     uint32_t beams_ = 0;
 };
 
@@ -1603,37 +1462,17 @@ inline std::vector<RolloutState> rolloutPoses(const RolloutParams &params, const
     return out;
 }
 
-class RolloutGrid {
+class RolloutGrid
+    : public GridHandle<lom_rollout, lom_occupancy_geometry, lom_rollout_create, lom_rollout_destroy, lom_rollout_last_error,
+                        lom_rollout_get_geometry, lom_rollout_clear, lom_rollout_set_option, lom_rollout_device, lom_rollout_stream,
+                        lom_rollout_wait_event> {
 public:
     struct Result {
         std::vector<lom_rollout_pick> picks;  // one per state
         lom_rollout_summary summary;
     };
-    explicit RolloutGrid(const lom_occupancy_geometry &geometry, int device = 0)
-    {
-        const int rc = lom_rollout_create(&geometry, device, &h_);
-        if (rc != LOM_OK) throw Error(rc, lom_rollout_last_error(nullptr));
-    }
-    ~RolloutGrid() { lom_rollout_destroy(h_); }
-    RolloutGrid(const RolloutGrid &) = delete;
-    RolloutGrid &operator=(const RolloutGrid &) = delete;
-    lom_rollout *handle() const { return h_; }
-    lom_occupancy_geometry geometry() const
-    {
-        lom_occupancy_geometry g;
-        check(lom_rollout_get_geometry(h_, &g));
-        return g;
-    }
-    size_t size() const
-    {
-        const lom_occupancy_geometry g = geometry();
-        return (size_t)g.width * g.height;
-    }
-    int device() const { return lom_rollout_device(h_); }
-    void *stream() const { return lom_rollout_stream(h_); }
-    void waitEvent(void *hip_event) { check(lom_rollout_wait_event(h_, hip_event)); }
-    void clear() { check(lom_rollout_clear(h_)); }
-    void setOption(int option, int64_t value) { check(lom_rollout_set_option(h_, option, value)); }
+    explicit RolloutGrid(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
+    size_t size() const { return cellCount(); }
     // host planes of size() cells (potential may be NULL); commands: k * params.segments (v, w) pairs; footprint: f (fx, fy) pairs
     Result evaluate(const int8_t *cost_plane, const uint32_t *potential, const lom_rollout_state *states, size_t m, const int16_t *commands,
                     size_t k, const int32_t *footprint, size_t f, const lom_rollout_params &params)
@@ -1675,14 +1514,6 @@ public:
         check(lom_rollout_stats(h_, &s));
         return s;
     }
-
-private:
-    int64_t check(int64_t rc) const
-    {
-        if (rc < 0) throw Error((int)rc, lom_rollout_last_error(h_));
-        return rc;
-    }
-    lom_rollout *h_ = nullptr;
 };
 
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------

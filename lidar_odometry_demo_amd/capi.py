@@ -516,92 +516,347 @@ class AlignHooks(C.Structure):
                 ("allreduce", ALLREDUCE_FN)]
 
 
-# every symbol include/lidar_odometry_amd.h declares
-EXPORTED = [
-    "lom_abi_version", "lom_device_count", "lom_device_local_cpus", "lom_pose_identity", "lom_pose_compose", "lom_pose_inverse",
-    "lom_pose_relative_to", "lom_pose_rotation_matrix", "lom_transform_points", "lom_map_create",
-    "lom_map_destroy", "lom_last_error", "lom_map_clear", "lom_map_set_max_points", "lom_map_add_points",
-    "lom_map_add_points_device", "lom_map_add_points_device_nowait", "lom_map_status", "lom_map_radius_cleanup", "lom_map_radius_cleanup_after_align", "lom_map_size", "lom_map_point_count",
-    "lom_map_export", "lom_voxel_downsample", "lom_voxel_downsample_device", "lom_upload_points",
-    "lom_transform_points_device", "lom_map_get_stream", "lom_match_find_pairs", "lom_match_find_pairs_sq", "lom_debug_find_pairs_after", "lom_match_align", "lom_match_align_device", "lom_match_align_repeat", "lom_debug_match_stamps", "lom_debug_eval_sums", "lom_debug_lm_trace", "lom_debug_lm_policy",
-    "lom_map_set_profiling", "lom_profile_match", "lom_profile_insert", "lom_map_set_stream", "lom_comm_unique_id", "lom_comm_init",
-    "lom_comm_finalize", "lom_comm_host_id", "lom_host_comm_create", "lom_host_comm_allreduce",
-    "lom_host_comm_destroy", "lom_host_comm_allgather", "lom_comm_attach_host", "lom_comm_attach_p2p", "lom_align_with_hooks", "lom_point_time_normalize", "lom_transform_non_rigid",
-    "lom_range_filter", "lom_cloud_classify", "lom_odometry_default_params", "lom_odometry_create",
-    "lom_odometry_destroy", "lom_odometry_process_cloud", "lom_odometry_process_sequence", "lom_odometry_hint_next", "lom_odometry_get_pose", "lom_odometry_get_stats", "lom_odometry_get_temp_cloud", "lom_odometry_debug_set_state",
-    "lom_odometry_keyframe", "lom_odometry_last_error", "lom_pcd_read", "lom_pcd_last_error", "lom_estimate_normals", "lom_frontend_create", "lom_frontend_destroy", "lom_frontend_last_error",
-    "lom_frontend_process", "lom_frontend_results", "lom_frontend_wait", "lom_frontend_fetch", "lom_frontend_stream", "lom_frontend_stage", "lom_map_set_align_idle_hook", "lom_frontend_done_event", "lom_map_wait_event", "lom_frontend_sequence", "lom_map_status_words", "lom_debug_sinf",
-    "lom_voxel_downsample_device_nowait", "lom_map_read_device_words", "lom_map_read_device_words_begin", "lom_map_read_device_words_end",
-    "lom_pointcloud2_unpack", "lom_pointcloud2_layout", "lom_pointcloud2_pack_xyz", "lom_pointcloud2_last_error",
-    "lom_map_set_option", "lom_map_debug_counter", "lom_odometry_set_option", "lom_odometry_debug_counter",
-    "lom_frontend_set_option", "lom_host_comm_set_timeout", "lom_host_comm_abort", "lom_host_comm_last_error",
-    "lom_scan_create", "lom_scan_destroy", "lom_scan_last_error", "lom_scan_set_option", "lom_scan_set_stream",
-    "lom_scan_get_stream", "lom_scan_create_on_partition", "lom_scan_align", "lom_scan_align_device", "lom_scan_align_repeat", "lom_scan_find_pairs", "lom_scan_find_pairs_sq",
-    "lom_match_align_batch", "lom_match_align_batch_device", "lom_scan_align_batch", "lom_scan_align_batch_device",
-    "lom_align_batch_best", "lom_match_align_multi", "lom_match_align_multi_device", "lom_odometry_process_batch",
-    "lom_quality_from_sums", "lom_match_quality", "lom_match_quality_device", "lom_scan_quality", "lom_scan_quality_device",
-    "lom_odometry_set_quality_thresholds", "lom_odometry_get_quality",
-    "lom_match_quality_batch_sums", "lom_match_quality_batch_sums_device", "lom_match_quality_batch",
-    "lom_match_quality_batch_device", "lom_scan_quality_batch_sums", "lom_scan_quality_batch_sums_device",
-    "lom_scan_quality_batch", "lom_scan_quality_batch_device", "lom_quality_batch_best", "lom_pose_lattice",
-    "lom_classify_neighbourhood", "lom_frontend_set_classifier", "lom_frontend_debug_counter", "lom_odometry_set_classifier",
-    "lom_debug_replayed_iterations", "lom_debug_set_host_replay_fold", "lom_debug_replay_fold_count",
-    "lom_place_db_create", "lom_place_db_destroy", "lom_place_db_last_error", "lom_place_db_size", "lom_place_db_clear",
-    "lom_place_db_params", "lom_place_db_stream", "lom_place_db_device", "lom_place_db_wait_event", "lom_place_describe",
-    "lom_place_describe_device", "lom_place_db_add", "lom_place_db_add_cloud", "lom_place_db_add_cloud_device",
-    "lom_place_db_get", "lom_place_db_query", "lom_place_db_query_cloud_device", "lom_place_shift_yaw",
-    "lom_odometry_place_descriptor", "lom_frontend_deskewed",
-    "lom_map_carve_rays", "lom_map_carve_rays_device", "lom_map_carve_counts", "lom_odometry_set_carve",
-    "lom_odometry_get_carve_stats",
-    "lom_graph_create", "lom_graph_destroy", "lom_graph_last_error", "lom_graph_clear", "lom_graph_stream", "lom_graph_device",
-    "lom_graph_add_node", "lom_graph_add_nodes", "lom_graph_add_edge", "lom_graph_add_edges", "lom_graph_node_count",
-    "lom_graph_edge_count", "lom_graph_get_poses", "lom_graph_set_pose", "lom_graph_set_fixed", "lom_graph_optimize",
-    "lom_graph_evaluate", "lom_graph_debug_matvec", "lom_graph_edge_chi2", "lom_graph_check_gauge", "lom_graph_lm_policy",
-    "lom_graph_information_from_quality", "lom_graph_pose_from_f32", "lom_graph_pose_to_f32",
-    "lom_archive_create", "lom_archive_destroy", "lom_archive_last_error", "lom_archive_clear", "lom_archive_stream",
-    "lom_archive_device", "lom_archive_wait_event", "lom_archive_add", "lom_archive_add_device", "lom_archive_scan_count",
-    "lom_archive_point_count", "lom_archive_scan_size", "lom_archive_get", "lom_map_assemble", "lom_odometry_archive_scan",
-    "lom_odometry_rebuild_keyframe",
-    "lom_map_carve_scans", "lom_map_scan_votes", "lom_odometry_set_rebuild_votes", "lom_odometry_get_rebuild_vote_stats",
-    "lom_odometry_archive_deskewed", "lom_odometry_occupancy_scan",
-    "lom_occupancy_create", "lom_occupancy_destroy", "lom_occupancy_last_error", "lom_occupancy_clear",
-    "lom_occupancy_get_geometry", "lom_occupancy_stream", "lom_occupancy_device", "lom_occupancy_wait_event",
-    "lom_occupancy_set_option", "lom_occupancy_integrate", "lom_occupancy_integrate_cloud",
-    "lom_occupancy_integrate_cloud_device", "lom_occupancy_counts", "lom_occupancy_classify", "lom_occupancy_classify_device",
-    "lom_odometry_elevation_scan",
-    "lom_elevation_create", "lom_elevation_destroy", "lom_elevation_last_error", "lom_elevation_clear",
-    "lom_elevation_get_geometry", "lom_elevation_stream", "lom_elevation_device", "lom_elevation_wait_event",
-    "lom_elevation_set_option", "lom_elevation_integrate", "lom_elevation_integrate_cloud",
-    "lom_elevation_integrate_cloud_device", "lom_elevation_cells", "lom_elevation_layers", "lom_elevation_cost",
-    "lom_elevation_cost_device",
-    "lom_clearance_create", "lom_clearance_destroy", "lom_clearance_last_error", "lom_clearance_clear",
-    "lom_clearance_get_geometry", "lom_clearance_stream", "lom_clearance_device", "lom_clearance_wait_event",
-    "lom_clearance_set_option", "lom_clearance_update", "lom_clearance_update_device", "lom_clearance_update_from_grids",
-    "lom_clearance_cost", "lom_clearance_cost_device", "lom_clearance_distance_sq", "lom_clearance_distance",
-    "lom_clearance_cost_table", "lom_clearance_query",
-    "lom_navfield_create", "lom_navfield_destroy", "lom_navfield_last_error", "lom_navfield_clear",
-    "lom_navfield_get_geometry", "lom_navfield_stream", "lom_navfield_device", "lom_navfield_wait_event",
-    "lom_navfield_set_option", "lom_navfield_solve", "lom_navfield_solve_device", "lom_navfield_solve_from_clearance",
-    "lom_navfield_potential", "lom_navfield_potential_device", "lom_navfield_paths", "lom_navfield_query",
-    "lom_navfield_cell_costs", "lom_navfield_stats",
-    "lom_regions_create", "lom_regions_destroy", "lom_regions_last_error", "lom_regions_clear", "lom_regions_get_geometry",
-    "lom_regions_stream", "lom_regions_device", "lom_regions_wait_event", "lom_regions_set_option", "lom_regions_extract",
-    "lom_regions_extract_device", "lom_regions_extract_from_grids", "lom_regions_labels", "lom_regions_labels_device",
-    "lom_regions_list", "lom_regions_goals", "lom_regions_query", "lom_regions_stats",
-    "lom_visibility_create", "lom_visibility_destroy", "lom_visibility_last_error", "lom_visibility_clear",
-    "lom_visibility_get_geometry", "lom_visibility_stream", "lom_visibility_device", "lom_visibility_wait_event",
-    "lom_visibility_set_option", "lom_visibility_table", "lom_visibility_cast", "lom_visibility_cast_device",
-    "lom_visibility_cast_from_occupancy", "lom_visibility_records", "lom_visibility_beams", "lom_visibility_windows_device",
-    "lom_visibility_windows",    "lom_visibility_select", "lom_visibility_select_from_navfield", "lom_visibility_stats",
-    "lom_rollout_create", "lom_rollout_destroy", "lom_rollout_last_error", "lom_rollout_clear", "lom_rollout_get_geometry",
-    "lom_rollout_stream", "lom_rollout_device", "lom_rollout_wait_event", "lom_rollout_set_option", "lom_rollout_evaluate",
-    "lom_rollout_evaluate_device", "lom_rollout_evaluate_from_grids", "lom_rollout_records", "lom_rollout_stats",
-    "lom_rollout_footprint_rectangle", "lom_rollout_state_from_pose", "lom_rollout_poses",
-]
-# ... and the one it declares through a function type (the "scan archive and map assembly" section)
+# ---- the prototypes: every function include/lidar_odometry_amd.h declares, name -> (restype, argtypes).  lib() applies the
+# table as it is; tests/test_capi_prototypes.py holds it against the header (return type and parameter count).
+_P = C.POINTER
+_int, _i64, _size, _u32, _float, _double, _str = C.c_int, C.c_int64, C.c_size_t, C.c_uint32, C.c_float, C.c_double, C.c_char_p
+_fp, _dp, _pp, _vp = _P(C.c_float), _P(C.c_double), _P(Pose), C.c_void_p
+IDLE_HOOK_FN = C.CFUNCTYPE(None, C.c_void_p)  # lom_map_set_align_idle_hook
+
+
+def _family(stem, create_args):
+    """create / destroy / last_error of the handle family lom_<stem>_*; create_args: what comes before the handle out"""
+    return {f"lom_{stem}_create": (_int, [*create_args, _P(_vp)]), f"lom_{stem}_destroy": (None, [_vp]),
+            f"lom_{stem}_last_error": (_str, [_vp])}
+
+
+def _grid_family(stem, geometry):
+    """the nine entry points every grid family has"""
+    return {**_family(stem, [_P(geometry), _int]), f"lom_{stem}_clear": (_int, [_vp]),
+            f"lom_{stem}_get_geometry": (_int, [_vp, _P(geometry)]), f"lom_{stem}_stream": (_vp, [_vp]),
+            f"lom_{stem}_device": (_int, [_vp]), f"lom_{stem}_wait_event": (_int, [_vp, _vp]),
+            f"lom_{stem}_set_option": (_int, [_vp, _int, _i64])}
+
+
+# argument lists that several entry points share: a map's and a scan context's forms, host and device
+_ADD = [_vp, _vp, _vp, _size, _size]
+_PAIRS = [_vp, _vp, _size, _size, _fp, _fp, _float, _vp]
+_PAIRS_SQ = [_vp, _vp, _size, _size, _fp, _fp, _double, _vp]
+_ALIGN = [_vp, _vp, _size, _size, _fp, _fp, _fp, _fp, _P(AlignStats)]
+_ALIGN_REPEAT = [_vp, _vp, _size, _size, _fp, _fp, _int, _fp, _fp, _P(AlignStats)]
+_ALIGN_BATCH = [_vp, _P(AlignProblem), _int, _P(AlignResult), _P(_int)]
+_ALIGN_MULTI = [_vp, _P(AlignMultiProblem), _int, _P(AlignResult), _P(_int)]
+_QUALITY = [_vp, _vp, _size, _size, _fp, _fp, _float, _float, _float, _P(QualityReport), _vp]
+_QUALITY_BATCH_SUMS = [_vp, _P(QualityProblem), _int, _float, _dp]
+_QUALITY_BATCH = [_vp, _P(QualityProblem), _int, _float, _float, _float, _P(QualityReport), _P(_int)]
+_CARVE = [_vp, _fp, _vp, _size, _size, _P(CarveParams), _P(CarveStats)]
+_DESCRIBE = [_vp, _vp, _size, _size, _vp]
+_ADD_CLOUD = [_vp, _vp, _size, _size]
+_CLASSIFIER = [_vp, _int, _P(NeighbourhoodParams)]
+_OPTION = [_vp, _int, _i64]
+# states, m, commands, k, footprint, f, params, picks, summary: the tail of every rollout evaluate form
+_ROLLOUT_TAIL = [_vp, _size, _vp, _size, _vp, _size, _P(RolloutParams), _vp, _P(RolloutSummary)]
+
+PROTOTYPES = {
+    "lom_abi_version": (_int, []),
+    "lom_device_count": (_int, []),
+    "lom_device_local_cpus": (_int, [_int, _str, _size]),
+    "lom_pose_identity": (None, [_pp]),
+    "lom_pose_compose": (None, [_pp, _pp, _pp]),
+    "lom_pose_inverse": (None, [_pp, _pp]),
+    "lom_pose_relative_to": (None, [_pp, _pp, _pp]),
+    "lom_pose_rotation_matrix": (None, [_pp, _fp]),
+    "lom_transform_points": (_int, [_pp, _vp, _vp, _size, _size, _vp, _vp, _size]),
+    # ---- the map (its last error is lom_last_error) and what runs on it
+    "lom_map_create": (_int, [_float, _size, _size, _int, _P(_vp)]),
+    "lom_map_destroy": (None, [_vp]),
+    "lom_last_error": (_str, [_vp]),
+    "lom_map_clear": (_int, [_vp, _float]),
+    "lom_map_set_max_points": (_int, [_vp, _size]),
+    "lom_map_add_points": (_int, _ADD),
+    "lom_map_add_points_device": (_int, _ADD),
+    "lom_map_add_points_device_nowait": (_int, _ADD),
+    "lom_map_status": (_int, [_vp]),
+    "lom_map_status_words": (_int, [_vp, _P(_vp), _P(_vp), _P(_u32)]),
+    "lom_map_radius_cleanup": (_int, [_vp, _fp, _float]),
+    "lom_map_radius_cleanup_after_align": (_int, [_vp, _float]),
+    "lom_map_size": (_i64, [_vp]),
+    "lom_map_point_count": (_i64, [_vp]),
+    "lom_map_export": (_i64, [_vp, _int, _vp, _vp, _size]),
+    "lom_map_carve_rays": (_int, _CARVE),
+    "lom_map_carve_rays_device": (_int, _CARVE),
+    "lom_map_carve_counts": (_i64, [_vp, _fp, _vp, _size, _size, _P(CarveParams), _vp, _vp, _size]),
+    "lom_voxel_downsample": (_i64, [_vp, _float, _vp, _vp, _size, _size, _vp, _vp, _size]),
+    "lom_upload_points": (_int, [_vp, _vp, _vp, _size, _size, _P(_vp), _P(_vp)]),
+    "lom_voxel_downsample_device": (_i64, [_vp, _float, _vp, _vp, _size, _size, _P(_vp), _P(_vp)]),
+    "lom_voxel_downsample_device_nowait": (_int, [_vp, _float, _vp, _vp, _size, _vp, _size, _P(_vp), _P(_vp), _P(_vp)]),
+    "lom_map_read_device_words": (_int, [_vp, _P(_vp), _int, _P(_u32)]),
+    "lom_map_read_device_words_begin": (_int, [_vp, _P(_vp), _int]),
+    "lom_map_read_device_words_end": (_int, [_vp, _P(_u32)]),
+    "lom_transform_points_device": (_int, [_vp, _vp, _vp, _vp, _size, _size, _P(_vp), _P(_vp)]),
+    "lom_match_find_pairs": (_i64, _PAIRS),
+    "lom_match_find_pairs_sq": (_i64, _PAIRS_SQ),
+    "lom_debug_find_pairs_after": (_i64, [_vp, _vp, _size, _size, _fp, _fp, _fp, _fp, _float, _vp]),
+    "lom_match_align": (_int, _ALIGN),
+    "lom_match_align_device": (_int, _ALIGN),
+    "lom_match_align_repeat": (_int, _ALIGN_REPEAT),
+    "lom_match_align_batch": (_int, _ALIGN_BATCH),
+    "lom_match_align_batch_device": (_int, _ALIGN_BATCH),
+    "lom_align_batch_best": (_int, [_P(AlignResult), _int]),
+    "lom_match_align_multi": (_int, _ALIGN_MULTI),
+    "lom_match_align_multi_device": (_int, _ALIGN_MULTI),
+    "lom_debug_match_stamps": (_int, [_vp, _vp, _size, _size, _fp, _fp, _float, _vp, _size, _P(_u32)]),
+    "lom_debug_eval_sums": (_int, [_vp, _vp, _size, _size, _fp, _fp, _dp, _dp, _dp]),
+    "lom_debug_lm_trace": (_int, [_vp, _vp, _size, _size, _fp, _fp, _int, _dp, _P(_int), _fp, _fp, _P(AlignStats)]),
+    "lom_debug_replayed_iterations": (_int, [_vp]),
+    "lom_debug_set_host_replay_fold": (_int, [_int]),
+    "lom_debug_replay_fold_count": (_int, [_int, _double]),
+    "lom_debug_lm_policy": (_int, [_int, _int, _P(_int), _dp, _dp, _dp, _P(_int), _dp, _P(_int), _P(_int), _dp, _dp]),
+    "lom_map_set_profiling": (_int, [_vp, _int]),
+    "lom_profile_match": (_int, [_vp, _vp, _size, _size, _fp, _fp, _float, _int, _dp, _dp, _dp, _dp]),
+    "lom_profile_insert": (_int, [_vp, _vp, _vp, _size, _size, _dp]),
+    "lom_map_set_option": (_int, _OPTION),
+    "lom_map_debug_counter": (_i64, [_vp, _int]),
+    "lom_map_wait_event": (_int, [_vp, _vp]),
+    "lom_map_set_align_idle_hook": (_int, [_vp, IDLE_HOOK_FN, _vp]),
+    "lom_map_set_stream": (_int, [_vp, _vp]),
+    "lom_map_get_stream": (_vp, [_vp]),
+    # ---- scan contexts
+    **_family("scan", [_vp]),
+    "lom_scan_create_on_partition": (_int, [_vp, _int, _int, _P(_vp)]),
+    "lom_scan_set_option": (_int, _OPTION),
+    "lom_scan_set_stream": (_int, [_vp, _vp]),
+    "lom_scan_get_stream": (_vp, [_vp]),
+    "lom_scan_align": (_int, _ALIGN),
+    "lom_scan_align_device": (_int, _ALIGN),
+    "lom_scan_align_repeat": (_int, _ALIGN_REPEAT),
+    "lom_scan_align_batch": (_int, _ALIGN_BATCH),
+    "lom_scan_align_batch_device": (_int, _ALIGN_BATCH),
+    "lom_scan_find_pairs": (_i64, _PAIRS),
+    "lom_scan_find_pairs_sq": (_i64, _PAIRS_SQ),
+    # ---- quality reports
+    "lom_quality_from_sums": (_int, [_dp, _i64, _float, _float, _P(QualityReport)]),
+    "lom_match_quality": (_int, _QUALITY),
+    "lom_match_quality_device": (_int, _QUALITY),
+    "lom_scan_quality": (_int, _QUALITY),
+    "lom_scan_quality_device": (_int, _QUALITY),
+    "lom_match_quality_batch_sums": (_int, _QUALITY_BATCH_SUMS),
+    "lom_match_quality_batch_sums_device": (_int, _QUALITY_BATCH_SUMS),
+    "lom_scan_quality_batch_sums": (_int, _QUALITY_BATCH_SUMS),
+    "lom_scan_quality_batch_sums_device": (_int, _QUALITY_BATCH_SUMS),
+    "lom_match_quality_batch": (_int, _QUALITY_BATCH),
+    "lom_match_quality_batch_device": (_int, _QUALITY_BATCH),
+    "lom_scan_quality_batch": (_int, _QUALITY_BATCH),
+    "lom_scan_quality_batch_device": (_int, _QUALITY_BATCH),
+    "lom_quality_batch_best": (_int, [_P(QualityReport), _int]),
+    "lom_pose_lattice": (_int, [_pp, _fp, _fp, _float, _float, _pp, _int]),
+    # ---- communicators and hooks
+    "lom_comm_unique_id": (_int, [_str]),
+    "lom_comm_init": (_int, [_vp, _int, _int, _str]),
+    "lom_comm_finalize": (_int, [_vp]),
+    "lom_comm_host_id": (_int, [_str]),
+    **_family("host_comm", [_int, _int, _str]),
+    "lom_host_comm_allreduce": (_int, [_vp, _dp, _int]),
+    "lom_host_comm_set_timeout": (_int, [_vp, _double]),
+    "lom_host_comm_abort": (_int, [_vp]),
+    "lom_host_comm_allgather": (_int, [_vp, _vp, _size, _vp]),
+    "lom_comm_attach_host": (_int, [_vp, _vp]),
+    "lom_comm_attach_p2p": (_int, [_vp, _vp]),
+    "lom_align_with_hooks": (_int, [_P(AlignHooks), _fp, _fp, _fp, _fp, _P(AlignStats)]),
+    # ---- the stages before the align on the host, and the front end
+    "lom_point_time_normalize": (None, [_vp, _size, _vp]),
+    "lom_transform_non_rigid": (None, [_vp, _size, _pp, _pp, _vp]),
+    "lom_range_filter": (_size, [_vp, _vp, _size, _float, _float, _vp, _vp]),
+    "lom_cloud_classify": (_size, [_vp, _size, _vp, _vp, _P(_size), _P(_size)]),
+    **_family("frontend", [_int, _vp]),
+    "lom_frontend_set_option": (_int, _OPTION),
+    "lom_frontend_process": (_int, [_vp, _vp, _size, _pp, _pp, _float, _float]),
+    "lom_frontend_results": (_int, [_vp, _P(_vp), _P(_vp), _P(_vp), _P(_u32)]),
+    "lom_frontend_deskewed": (_int, [_vp, _P(_vp), _P(_u32)]),
+    "lom_frontend_wait": (_int, [_vp, _P(_u32)]),
+    "lom_frontend_fetch": (_i64, [_vp, _int, _vp, _vp, _size]),
+    "lom_frontend_stage": (_int, [_vp, _size, _P(_vp)]),
+    "lom_frontend_done_event": (_vp, [_vp]),
+    "lom_frontend_stream": (_vp, [_vp]),
+    "lom_frontend_sequence": (_u32, [_vp]),
+    "lom_debug_sinf": (_int, [_vp, _vp, _size, _vp]),
+    "lom_classify_neighbourhood": (_i64, [_vp, _vp, _size, _P(NeighbourhoodParams), _vp, _vp, _vp]),
+    "lom_frontend_set_classifier": (_int, _CLASSIFIER),
+    "lom_frontend_debug_counter": (_i64, [_vp, _int]),
+    # ---- files and messages
+    "lom_pcd_read": (_i64, [_str, _vp, _vp, _size, _P(PcdInfo)]),
+    "lom_pcd_last_error": (_str, []),
+    "lom_pointcloud2_unpack": (_i64, [_P(Pc2View), _vp, _size, _P(_u32)]),
+    "lom_pointcloud2_layout": (_int, [_int, _P(Pc2Field), _P(_u32)]),
+    "lom_pointcloud2_pack_xyz": (_i64, [_vp, _size, _size, _vp, _size]),
+    "lom_pointcloud2_last_error": (_str, []),
+    "lom_estimate_normals": (_i64, [_vp, _size, _size, _float, _int, _vp, _vp]),
+    # ---- place recognition
+    **_family("place_db", [_P(PlaceParams), _int, _size]),
+    "lom_place_db_size": (_i64, [_vp]),
+    "lom_place_db_clear": (_int, [_vp]),
+    "lom_place_db_params": (_int, [_vp, _P(PlaceParams)]),
+    "lom_place_db_stream": (_vp, [_vp]),
+    "lom_place_db_device": (_int, [_vp]),
+    "lom_place_db_wait_event": (_int, [_vp, _vp]),
+    "lom_place_describe": (_int, _DESCRIBE),
+    "lom_place_describe_device": (_int, _DESCRIBE),
+    "lom_place_db_add": (_i64, [_vp, _vp]),
+    "lom_place_db_add_cloud": (_i64, _ADD_CLOUD),
+    "lom_place_db_add_cloud_device": (_i64, _ADD_CLOUD),
+    "lom_place_db_get": (_int, [_vp, _i64, _vp]),
+    "lom_place_db_query": (_int, [_vp, _vp, _int, _i64, _i64, _int, _vp, _vp]),
+    "lom_place_db_query_cloud_device": (_int, [_vp, _vp, _size, _size, _i64, _i64, _int, _vp]),
+    "lom_place_shift_yaw": (_double, [_P(PlaceParams), _u32]),
+    # ---- pose graph
+    **_family("graph", [_int, _size, _size]),
+    "lom_graph_clear": (_int, [_vp]),
+    "lom_graph_stream": (_vp, [_vp]),
+    "lom_graph_device": (_int, [_vp]),
+    "lom_graph_add_node": (_i64, [_vp, _vp, _int]),
+    "lom_graph_add_nodes": (_i64, [_vp, _vp, _vp, _size]),
+    "lom_graph_add_edge": (_i64, [_vp, _i64, _i64, _vp, _vp, _double]),
+    "lom_graph_add_edges": (_i64, [_vp, _vp, _vp, _vp, _vp, _size]),
+    "lom_graph_node_count": (_i64, [_vp]),
+    "lom_graph_edge_count": (_i64, [_vp]),
+    "lom_graph_get_poses": (_int, [_vp, _i64, _i64, _vp]),
+    "lom_graph_set_pose": (_int, [_vp, _i64, _vp]),
+    "lom_graph_set_fixed": (_int, [_vp, _i64, _int]),
+    "lom_graph_optimize": (_int, [_vp, _P(GraphParams), _P(GraphStats)]),
+    "lom_graph_evaluate": (_int, [_vp, _double, _vp, _vp, _vp, _vp, _vp]),
+    "lom_graph_debug_matvec": (_int, [_vp, _double, _vp, _vp]),
+    "lom_graph_edge_chi2": (_int, [_vp, _i64, _i64, _vp]),
+    "lom_graph_check_gauge": (_int, [_i64, _vp, _i64, _vp, _P(_i64)]),
+    "lom_graph_lm_policy": (_int, [_double, _double, _double, _dp, _dp, _dp]),
+    "lom_graph_information_from_quality": (_int, [_P(QualityReport), _int, _vp]),
+    "lom_graph_pose_from_f32": (_int, [_pp, _vp]),
+    "lom_graph_pose_to_f32": (_int, [_vp, _pp]),
+    # ---- scan archive, map assembly, scan votes
+    **_family("archive", [_int, _size, _size]),
+    "lom_archive_clear": (_int, [_vp]),
+    "lom_archive_stream": (_vp, [_vp]),
+    "lom_archive_device": (_int, [_vp]),
+    "lom_archive_wait_event": (_int, [_vp, _vp]),
+    "lom_archive_add": (_i64, _ADD),
+    "lom_archive_add_device": (_i64, [*_ADD, _vp]),
+    "lom_archive_scan_count": (_i64, [_vp]),
+    "lom_archive_point_count": (_i64, [_vp]),
+    "lom_archive_scan_size": (_i64, [_vp, _i64]),
+    "lom_archive_get": (_i64, [_vp, _i64, _vp, _vp, _size]),
+    "lom_map_assemble": (_int, [_vp, _vp, _vp, _vp, _size, _P(AssembleParams), _P(AssembleStats)]),
+    "lom_graph_pose_rotation_matrix": (_int, [_vp, _vp]),
+    "lom_map_carve_scans": (_int, [_vp, _vp, _vp, _vp, _size, _P(VoteParams), _P(VoteStats)]),
+    "lom_map_scan_votes": (_i64, [_vp, _vp, _vp, _vp, _size, _P(VoteParams), _vp, _vp, _size]),
+    "lom_archive_add_points": (_i64, _ADD_CLOUD),
+    "lom_archive_add_points_device": (_i64, [*_ADD_CLOUD, _vp]),
+    # ---- occupancy grid
+    **_grid_family("occupancy", OccupancyGeometry),
+    "lom_occupancy_integrate": (_int, [_vp, _vp, _vp, _vp, _size, _P(OccupancyRayParams), _P(OccupancyStats)]),
+    "lom_occupancy_integrate_cloud": (_int, [_vp, _vp, _size, _size, _vp, _P(OccupancyRayParams), _P(OccupancyStats)]),
+    "lom_occupancy_integrate_cloud_device": (_int, [_vp, _vp, _size, _size, _vp, _P(OccupancyRayParams), _vp, _P(OccupancyStats)]),
+    "lom_occupancy_counts": (_i64, [_vp, _vp, _vp, _size]),
+    "lom_occupancy_classify": (_int, [_vp, _P(OccupancyRule), _vp, _size, _P(OccupancySummary)]),
+    "lom_occupancy_classify_device": (_int, [_vp, _P(OccupancyRule), _P(_vp)]),
+    # ---- elevation grid
+    **_grid_family("elevation", ElevationGeometry),
+    "lom_elevation_integrate": (_int, [_vp, _vp, _vp, _vp, _size, _P(ElevationPointParams), _P(ElevationStats)]),
+    "lom_elevation_integrate_cloud": (_int, [_vp, _vp, _size, _size, _vp, _P(ElevationPointParams), _P(ElevationStats)]),
+    "lom_elevation_integrate_cloud_device": (_int, [_vp, _vp, _size, _size, _vp, _P(ElevationPointParams), _vp, _P(ElevationStats)]),
+    "lom_elevation_cells": (_i64, [_vp, _vp, _vp, _vp, _vp, _size]),
+    "lom_elevation_layers": (_int, [_vp, _P(ElevationLayerParams), _vp, _vp, _vp, _vp, _vp, _vp, _size]),
+    "lom_elevation_cost": (_int, [_vp, _P(ElevationLayerParams), _P(ElevationCostParams), _vp, _size, _P(ElevationSummary)]),
+    "lom_elevation_cost_device": (_int, [_vp, _P(ElevationLayerParams), _P(ElevationCostParams), _P(_vp)]),
+    # ---- clearance grid
+    **_grid_family("clearance", OccupancyGeometry),
+    "lom_clearance_update": (_int, [_vp, _vp, _vp, _P(ClearanceParams), _P(ClearanceWindow), _P(ClearanceSummary)]),
+    "lom_clearance_update_device": (_int, [_vp, _vp, _vp, _vp, _P(ClearanceParams), _P(ClearanceWindow), _P(ClearanceSummary)]),
+    "lom_clearance_update_from_grids": (_int, [_vp, _vp, _P(OccupancyRule), _vp, _P(ElevationLayerParams), _P(ElevationCostParams),
+                                               _P(ClearanceParams), _P(ClearanceWindow), _P(ClearanceSummary)]),
+    "lom_clearance_cost": (_int, [_vp, _vp, _size, _P(ClearanceSummary)]),
+    "lom_clearance_cost_device": (_int, [_vp, _P(_vp)]),
+    "lom_clearance_distance_sq": (_int, [_vp, _vp, _size]),
+    "lom_clearance_distance": (_int, [_vp, _vp, _size]),
+    "lom_clearance_cost_table": (_i64, [_P(ClearanceParams), _P(OccupancyGeometry), _vp, _size]),
+    "lom_clearance_query": (_int, [_vp, _vp, _size, _vp, _vp]),
+    # ---- navigation field
+    **_grid_family("navfield", OccupancyGeometry),
+    "lom_navfield_solve": (_int, [_vp, _vp, _P(NavFieldParams), _int, _vp, _size, _P(NavFieldSummary)]),
+    "lom_navfield_solve_device": (_int, [_vp, _vp, _vp, _P(NavFieldParams), _int, _vp, _size, _P(NavFieldSummary)]),
+    "lom_navfield_solve_from_clearance": (_int, [_vp, _vp, _P(NavFieldParams), _int, _vp, _size, _P(NavFieldSummary)]),
+    "lom_navfield_potential": (_int, [_vp, _vp, _size]),
+    "lom_navfield_potential_device": (_int, [_vp, _P(_vp)]),
+    "lom_navfield_paths": (_int, [_vp, _int, _vp, _size, _vp, _size, _vp]),
+    "lom_navfield_query": (_int, [_vp, _vp, _size, _vp]),
+    "lom_navfield_cell_costs": (_int, [_P(NavFieldParams), _vp]),
+    "lom_navfield_stats": (_int, [_vp, _P(NavFieldSolveStats)]),
+    # ---- frontier regions
+    **_grid_family("regions", OccupancyGeometry),
+    "lom_regions_extract": (_int, [_vp, _vp, _vp, _vp, _P(RegionsParams), _P(RegionsSummary)]),
+    "lom_regions_extract_device": (_int, [_vp, _vp, _vp, _vp, _vp, _P(RegionsParams), _P(RegionsSummary)]),
+    "lom_regions_extract_from_grids": (_int, [_vp, _vp, _P(OccupancyRule), _vp, _vp, _P(RegionsParams), _P(RegionsSummary)]),
+    "lom_regions_labels": (_int, [_vp, _vp, _size]),
+    "lom_regions_labels_device": (_int, [_vp, _P(_vp)]),
+    "lom_regions_list": (_int, [_vp, _vp, _size, _P(_size)]),
+    "lom_regions_goals": (_int, [_vp, _int, _vp, _size, _P(_size)]),
+    "lom_regions_query": (_int, [_vp, _vp, _size, _vp]),
+    "lom_regions_stats": (_int, [_vp, _P(RegionsExtractStats)]),
+    # ---- visibility grid
+    **_grid_family("visibility", OccupancyGeometry),
+    "lom_visibility_table": (_int, [_u32, _vp]),
+    "lom_visibility_cast": (_int, [_vp, _vp, _vp, _size, _P(VisibilityParams), _P(VisibilitySummary)]),
+    "lom_visibility_cast_device": (_int, [_vp, _vp, _vp, _vp, _size, _P(VisibilityParams), _P(VisibilitySummary)]),
+    "lom_visibility_cast_from_occupancy": (_int, [_vp, _vp, _P(OccupancyRule), _vp, _size, _P(VisibilityParams), _P(VisibilitySummary)]),
+    "lom_visibility_records": (_int, [_vp, _vp, _size, _P(_size)]),
+    "lom_visibility_beams": (_int, [_vp, _vp, _size]),
+    "lom_visibility_windows_device": (_int, [_vp, _P(_vp), _P(_size)]),
+    "lom_visibility_windows": (_int, [_vp, _vp, _size, _P(_size)]),
+    "lom_visibility_select": (_int, [_vp, _P(VisibilitySelectParams), _vp, _vp, _P(_size)]),
+    "lom_visibility_select_from_navfield": (_int, [_vp, _vp, _P(VisibilitySelectParams), _vp, _P(_size)]),
+    "lom_visibility_stats": (_int, [_vp, _P(VisibilityCallStats)]),
+    # ---- trajectory rollouts
+    **_grid_family("rollout", OccupancyGeometry),
+    "lom_rollout_evaluate": (_int, [_vp, _vp, _vp] + _ROLLOUT_TAIL),
+    "lom_rollout_evaluate_device": (_int, [_vp, _vp, _vp, _vp, _vp] + _ROLLOUT_TAIL),
+    "lom_rollout_evaluate_from_grids": (_int, [_vp, _vp, _vp] + _ROLLOUT_TAIL),
+    "lom_rollout_records": (_int, [_vp, _vp, _size, _P(_size)]),
+    "lom_rollout_stats": (_int, [_vp, _P(RolloutCallStats)]),
+    "lom_rollout_footprint_rectangle": (_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _int, _vp, _size, _P(_size)]),
+    "lom_rollout_state_from_pose": (_int, [_P(OccupancyGeometry), _float, _float, _float, _vp]),
+    "lom_rollout_poses": (_int, [_P(RolloutParams), _vp, _vp, _vp]),
+    # ---- the odometry
+    "lom_odometry_default_params": (None, [_P(OdometryParams)]),
+    **_family("odometry", [_P(OdometryParams), _int]),
+    "lom_odometry_process_cloud": (_int, [_vp, _vp, _size]),
+    "lom_odometry_process_sequence": (_int, [_vp, _P(_vp), _P(_size), _size, _P(_size)]),
+    "lom_odometry_process_batch": (_int, [_P(_vp), _P(_vp), _P(_size), _int, _P(_int)]),
+    "lom_odometry_hint_next": (_int, [_vp, _vp, _size]),
+    "lom_odometry_get_pose": (_int, [_vp, _pp]),
+    "lom_odometry_get_temp_cloud": (_i64, [_vp, _vp, _size]),
+    "lom_odometry_place_descriptor": (_int, [_vp, _vp, _int, _vp, _P(_i64)]),
+    "lom_odometry_archive_scan": (_int, [_vp, _vp, _P(_i64)]),
+    "lom_odometry_archive_deskewed": (_int, [_vp, _vp, _P(_i64)]),
+    "lom_odometry_occupancy_scan": (_int, [_vp, _vp, _P(OccupancyRayParams), _P(OccupancyStats)]),
+    "lom_odometry_elevation_scan": (_int, [_vp, _vp, _P(ElevationPointParams), _P(ElevationStats)]),
+    "lom_odometry_rebuild_keyframe": (_int, [_vp, _vp, _vp, _vp, _size, _pp, _P(AssembleStats)]),
+    "lom_odometry_get_stats": (_int, [_vp, _P(OdometryFrameStats)]),
+    "lom_odometry_set_quality_thresholds": (_int, [_vp, _float, _float]),
+    "lom_odometry_get_quality": (_int, [_vp, _P(QualityReport)]),
+    "lom_odometry_set_option": (_int, _OPTION),
+    "lom_odometry_set_classifier": (_int, _CLASSIFIER),
+    "lom_odometry_set_carve": (_int, [_vp, _P(CarveParams)]),
+    "lom_odometry_get_carve_stats": (_int, [_vp, _P(CarveStats)]),
+    "lom_odometry_set_rebuild_votes": (_int, [_vp, _P(VoteParams)]),
+    "lom_odometry_get_rebuild_vote_stats": (_int, [_vp, _P(VoteStats)]),
+    "lom_odometry_debug_counter": (_i64, [_vp, _int]),
+    "lom_odometry_debug_set_state": (_int, [_vp, _pp, _pp]),
+    "lom_odometry_keyframe": (_vp, [_vp]),
+}
+# the one function the header declares through a function type (the "scan archive and map assembly" section) ...
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
 # ... and the two of the same section that came with the occupancy grid, declared the same way
 EXPORTED_BY_TYPE_POINTS = ["lom_archive_add_points", "lom_archive_add_points_device"]
+# every symbol include/lidar_odometry_amd.h declares with its parameters
+EXPORTED = [name for name in PROTOTYPES if name not in EXPORTED_BY_TYPE + EXPORTED_BY_TYPE_POINTS]
 
 # lom_option / counters of include/lidar_odometry_amd.h
 OPT_HOST_LM, OPT_DEVICE_PATIENCE_TICKS, OPT_DEBUG_LM_STAMPS, OPT_DEBUG_TIMING, OPT_NO_TEMPORAL_BOUND, OPT_COUNT_CANDIDATES = 1, 2, 3, 4, 5, 6
@@ -654,459 +909,9 @@ def lib():
             "or `make -C lidar_odometry_demo_amd/csrc`.  There is no CPU fallback.")
     _share_hip_runtime_with_torch()
     L = C.CDLL(LIB_PATH)
-    fp, dp, pp, vp = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(Pose), C.c_void_p
-    L.lom_abi_version.restype = C.c_int
-    L.lom_device_count.restype = C.c_int
-    L.lom_device_local_cpus.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
-    L.lom_pose_identity.argtypes = [pp]
-    L.lom_pose_compose.argtypes = [pp, pp, pp]
-    L.lom_pose_inverse.argtypes = [pp, pp]
-    L.lom_pose_relative_to.argtypes = [pp, pp, pp]
-    L.lom_pose_rotation_matrix.argtypes = [pp, fp]
-    L.lom_transform_points.argtypes = [pp, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t]
-    L.lom_map_create.argtypes = [C.c_float, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(vp)]
-    L.lom_map_destroy.argtypes = [vp]
-    L.lom_map_destroy.restype = None
-    L.lom_last_error.argtypes = [vp]
-    L.lom_last_error.restype = C.c_char_p
-    L.lom_map_clear.argtypes = [vp, C.c_float]
-    L.lom_map_set_max_points.argtypes = [vp, C.c_size_t]
-    L.lom_map_add_points.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t]
-    L.lom_map_add_points_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t]
-    L.lom_map_add_points_device_nowait.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t]
-    L.lom_map_status.argtypes = [vp]
-    L.lom_map_radius_cleanup.argtypes = [vp, fp, C.c_float]
-    L.lom_map_radius_cleanup_after_align.argtypes = [vp, C.c_float]
-    L.lom_map_size.argtypes = [vp]
-    L.lom_map_size.restype = C.c_int64
-    L.lom_map_point_count.argtypes = [vp]
-    L.lom_map_point_count.restype = C.c_int64
-    L.lom_map_export.argtypes = [vp, C.c_int, vp, vp, C.c_size_t]
-    L.lom_map_export.restype = C.c_int64
-    L.lom_voxel_downsample.argtypes = [vp, C.c_float, vp, vp, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t]
-    L.lom_voxel_downsample.restype = C.c_int64
-    L.lom_voxel_downsample_device.argtypes = [vp, C.c_float, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(vp), C.POINTER(vp)]
-    L.lom_voxel_downsample_device.restype = C.c_int64
-    L.lom_upload_points.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(vp), C.POINTER(vp)]
-    L.lom_upload_points.restype = C.c_int
-    L.lom_transform_points_device.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, C.POINTER(vp), C.POINTER(vp)]
-    L.lom_transform_points_device.restype = C.c_int
-    L.lom_map_get_stream.argtypes = [vp]
-    L.lom_map_get_stream.restype = vp
-    L.lom_match_find_pairs.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_float, vp]
-    L.lom_match_find_pairs.restype = C.c_int64
-    L.lom_match_find_pairs_sq.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_double, vp]
-    L.lom_match_find_pairs_sq.restype = C.c_int64
-    L.lom_debug_find_pairs_after.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, fp, fp, C.c_float, vp]
-    L.lom_debug_find_pairs_after.restype = C.c_int64
-    L.lom_match_align.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, fp, fp, C.POINTER(AlignStats)]
-    L.lom_match_align_device.argtypes = L.lom_match_align.argtypes
-    L.lom_debug_match_stamps.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_float, vp, C.c_size_t,
-                                         C.POINTER(C.c_uint32)]
-    L.lom_match_align_batch.argtypes = [vp, C.POINTER(AlignProblem), C.c_int, C.POINTER(AlignResult), C.POINTER(C.c_int)]
-    L.lom_match_align_batch_device.argtypes = L.lom_match_align_batch.argtypes
-    L.lom_scan_align_batch.argtypes = L.lom_match_align_batch.argtypes
-    L.lom_scan_align_batch_device.argtypes = L.lom_match_align_batch.argtypes
-    L.lom_align_batch_best.argtypes = [C.POINTER(AlignResult), C.c_int]
-    L.lom_match_align_multi.argtypes = [vp, C.POINTER(AlignMultiProblem), C.c_int, C.POINTER(AlignResult),
-                                        C.POINTER(C.c_int)]
-    L.lom_match_align_multi_device.argtypes = L.lom_match_align_multi.argtypes
-    L.lom_match_align_repeat.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_int, fp, fp, C.POINTER(AlignStats)]
-    L.lom_debug_eval_sums.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, dp, dp, dp]
-    L.lom_debug_lm_trace.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_int, dp, C.POINTER(C.c_int), fp, fp,
-                                     C.POINTER(AlignStats)]
-    L.lom_debug_lm_policy.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), dp, dp, dp, C.POINTER(C.c_int), dp,
-                                      C.POINTER(C.c_int), C.POINTER(C.c_int), dp, dp]
-    L.lom_debug_replayed_iterations.argtypes = [vp]
-    L.lom_debug_set_host_replay_fold.argtypes = [C.c_int]
-    L.lom_debug_replay_fold_count.argtypes = [C.c_int, C.c_double]
-    L.lom_map_set_profiling.argtypes = [vp, C.c_int]
-    L.lom_map_set_stream.argtypes = [vp, vp]
-    L.lom_profile_match.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_float, C.c_int, dp, dp, dp, dp]
-    L.lom_profile_insert.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, dp]
-    L.lom_comm_unique_id.argtypes = [C.c_char_p]
-    L.lom_comm_init.argtypes = [vp, C.c_int, C.c_int, C.c_char_p]
-    L.lom_comm_finalize.argtypes = [vp]
-    L.lom_comm_host_id.argtypes = [C.c_char_p]
-    L.lom_host_comm_create.argtypes = [C.c_int, C.c_int, C.c_char_p, C.POINTER(vp)]
-    L.lom_host_comm_allreduce.argtypes = [vp, dp, C.c_int]
-    L.lom_host_comm_destroy.argtypes = [vp]
-    L.lom_host_comm_destroy.restype = None
-    L.lom_comm_attach_host.argtypes = [vp, vp]
-    L.lom_comm_attach_p2p.argtypes = [vp, vp]
-    L.lom_comm_attach_p2p.restype = C.c_int
-    L.lom_host_comm_allgather.argtypes = [vp, vp, C.c_size_t, vp]
-    L.lom_host_comm_allgather.restype = C.c_int
-    L.lom_align_with_hooks.argtypes = [C.POINTER(AlignHooks), fp, fp, fp, fp, C.POINTER(AlignStats)]
-    L.lom_point_time_normalize.argtypes = [vp, C.c_size_t, vp]
-    L.lom_point_time_normalize.restype = None
-    L.lom_transform_non_rigid.argtypes = [vp, C.c_size_t, pp, pp, vp]
-    L.lom_transform_non_rigid.restype = None
-    L.lom_range_filter.argtypes = [vp, vp, C.c_size_t, C.c_float, C.c_float, vp, vp]
-    L.lom_range_filter.restype = C.c_size_t
-    L.lom_cloud_classify.argtypes = [vp, C.c_size_t, vp, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.lom_cloud_classify.restype = C.c_size_t
-    L.lom_odometry_default_params.argtypes = [C.POINTER(OdometryParams)]
-    L.lom_odometry_default_params.restype = None
-    L.lom_odometry_create.argtypes = [C.POINTER(OdometryParams), C.c_int, C.POINTER(vp)]
-    L.lom_odometry_destroy.argtypes = [vp]
-    L.lom_odometry_destroy.restype = None
-    L.lom_odometry_process_cloud.argtypes = [vp, vp, C.c_size_t]
-    L.lom_odometry_hint_next.argtypes = [vp, vp, C.c_size_t]
-    L.lom_odometry_process_sequence.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_size_t)]
-    L.lom_odometry_process_batch.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_int)]
-    L.lom_odometry_get_pose.argtypes = [vp, pp]
-    L.lom_odometry_get_stats.argtypes = [vp, C.POINTER(OdometryFrameStats)]
-    L.lom_odometry_get_temp_cloud.argtypes = [vp, vp, C.c_size_t]
-    L.lom_odometry_get_temp_cloud.restype = C.c_int64
-    L.lom_odometry_debug_set_state.argtypes = [vp, pp, pp]
-    L.lom_odometry_keyframe.argtypes = [vp]
-    L.lom_odometry_keyframe.restype = vp
-    L.lom_odometry_last_error.argtypes = [vp]
-    L.lom_odometry_last_error.restype = C.c_char_p
-    L.lom_frontend_create.argtypes = [C.c_int, vp, C.POINTER(vp)]
-    L.lom_frontend_destroy.argtypes = [vp]
-    L.lom_frontend_destroy.restype = None
-    L.lom_frontend_last_error.argtypes = [vp]
-    L.lom_frontend_last_error.restype = C.c_char_p
-    L.lom_frontend_process.argtypes = [vp, vp, C.c_size_t, pp, pp, C.c_float, C.c_float]
-    L.lom_frontend_results.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint32)]
-    L.lom_frontend_wait.argtypes = [vp, C.POINTER(C.c_uint32)]
-    L.lom_frontend_fetch.argtypes = [vp, C.c_int, vp, vp, C.c_size_t]
-    L.lom_frontend_fetch.restype = C.c_int64
-    L.lom_frontend_stream.argtypes = [vp]
-    L.lom_frontend_stream.restype = vp
-    L.lom_debug_sinf.argtypes = [vp, vp, C.c_size_t, vp]
-    L.lom_voxel_downsample_device_nowait.argtypes = [vp, C.c_float, vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp),
-                                                     C.POINTER(vp), C.POINTER(vp)]
-    L.lom_map_read_device_words.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(C.c_uint32)]
-    L.lom_map_read_device_words_begin.argtypes = [vp, C.POINTER(vp), C.c_int]
-    L.lom_map_read_device_words_end.argtypes = [vp, C.POINTER(C.c_uint32)]
-    L.lom_estimate_normals.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_float, C.c_int, vp, vp]
-    L.lom_estimate_normals.restype = C.c_int64
-    L.lom_pcd_read.argtypes = [C.c_char_p, vp, vp, C.c_size_t, C.POINTER(PcdInfo)]
-    L.lom_pcd_read.restype = C.c_int64
-    L.lom_pcd_last_error.restype = C.c_char_p
-    L.lom_pointcloud2_unpack.argtypes = [C.POINTER(Pc2View), vp, C.c_size_t, C.POINTER(C.c_uint32)]
-    L.lom_pointcloud2_unpack.restype = C.c_int64
-    L.lom_pointcloud2_layout.argtypes = [C.c_int, C.POINTER(Pc2Field), C.POINTER(C.c_uint32)]
-    L.lom_pointcloud2_pack_xyz.argtypes = [vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]
-    L.lom_pointcloud2_pack_xyz.restype = C.c_int64
-    L.lom_pointcloud2_last_error.restype = C.c_char_p
-    L.lom_map_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_map_debug_counter.argtypes = [vp, C.c_int]
-    L.lom_map_debug_counter.restype = C.c_int64
-    L.lom_odometry_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_odometry_debug_counter.argtypes = [vp, C.c_int]
-    L.lom_odometry_debug_counter.restype = C.c_int64
-    L.lom_frontend_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_classify_neighbourhood.argtypes = [vp, vp, C.c_size_t, C.POINTER(NeighbourhoodParams), vp, vp, vp]
-    L.lom_classify_neighbourhood.restype = C.c_int64
-    L.lom_frontend_set_classifier.argtypes = [vp, C.c_int, C.POINTER(NeighbourhoodParams)]
-    L.lom_frontend_debug_counter.argtypes = [vp, C.c_int]
-    L.lom_frontend_debug_counter.restype = C.c_int64
-    L.lom_odometry_set_classifier.argtypes = [vp, C.c_int, C.POINTER(NeighbourhoodParams)]
-    for fn in (L.lom_map_carve_rays, L.lom_map_carve_rays_device):
-        fn.argtypes = [vp, fp, vp, C.c_size_t, C.c_size_t, C.POINTER(CarveParams), C.POINTER(CarveStats)]
-    L.lom_map_carve_counts.argtypes = [vp, fp, vp, C.c_size_t, C.c_size_t, C.POINTER(CarveParams), vp, vp, C.c_size_t]
-    L.lom_map_carve_counts.restype = C.c_int64
-    L.lom_odometry_set_carve.argtypes = [vp, C.POINTER(CarveParams)]
-    L.lom_odometry_get_carve_stats.argtypes = [vp, C.POINTER(CarveStats)]
-    L.lom_host_comm_set_timeout.argtypes = [vp, C.c_double]
-    L.lom_host_comm_abort.argtypes = [vp]
-    L.lom_host_comm_last_error.argtypes = [vp]
-    L.lom_host_comm_last_error.restype = C.c_char_p
-    L.lom_scan_create.argtypes = [vp, C.POINTER(vp)]
-    L.lom_scan_create_on_partition.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
-    L.lom_scan_create_on_partition.restype = C.c_int
-    L.lom_scan_destroy.argtypes = [vp]
-    L.lom_scan_destroy.restype = None
-    L.lom_scan_last_error.argtypes = [vp]
-    L.lom_scan_last_error.restype = C.c_char_p
-    L.lom_scan_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_scan_set_stream.argtypes = [vp, vp]
-    L.lom_scan_get_stream.argtypes = [vp]
-    L.lom_scan_get_stream.restype = vp
-    L.lom_scan_align.argtypes = L.lom_match_align.argtypes
-    L.lom_scan_align_device.argtypes = L.lom_match_align.argtypes
-    L.lom_scan_align_repeat.argtypes = L.lom_match_align_repeat.argtypes
-    L.lom_scan_find_pairs.argtypes = L.lom_match_find_pairs.argtypes
-    L.lom_scan_find_pairs.restype = C.c_int64
-    L.lom_scan_find_pairs_sq.argtypes = L.lom_match_find_pairs_sq.argtypes
-    L.lom_scan_find_pairs_sq.restype = C.c_int64
-    L.lom_quality_from_sums.argtypes = [dp, C.c_int64, C.c_float, C.c_float, C.POINTER(QualityReport)]
-    L.lom_match_quality.argtypes = [vp, vp, C.c_size_t, C.c_size_t, fp, fp, C.c_float, C.c_float, C.c_float,
-                                    C.POINTER(QualityReport), vp]
-    L.lom_match_quality_device.argtypes = L.lom_match_quality.argtypes
-    L.lom_scan_quality.argtypes = L.lom_match_quality.argtypes
-    L.lom_scan_quality_device.argtypes = L.lom_match_quality.argtypes
-    L.lom_match_quality_batch_sums.argtypes = [vp, C.POINTER(QualityProblem), C.c_int, C.c_float, dp]
-    L.lom_match_quality_batch_sums_device.argtypes = L.lom_match_quality_batch_sums.argtypes
-    L.lom_scan_quality_batch_sums.argtypes = L.lom_match_quality_batch_sums.argtypes
-    L.lom_scan_quality_batch_sums_device.argtypes = L.lom_match_quality_batch_sums.argtypes
-    L.lom_match_quality_batch.argtypes = [vp, C.POINTER(QualityProblem), C.c_int, C.c_float, C.c_float, C.c_float,
-                                          C.POINTER(QualityReport), C.POINTER(C.c_int)]
-    L.lom_match_quality_batch_device.argtypes = L.lom_match_quality_batch.argtypes
-    L.lom_scan_quality_batch.argtypes = L.lom_match_quality_batch.argtypes
-    L.lom_scan_quality_batch_device.argtypes = L.lom_match_quality_batch.argtypes
-    L.lom_quality_batch_best.argtypes = [C.POINTER(QualityReport), C.c_int]
-    L.lom_pose_lattice.argtypes = [pp, fp, fp, C.c_float, C.c_float, pp, C.c_int]
-    L.lom_odometry_set_quality_thresholds.argtypes = [vp, C.c_float, C.c_float]
-    L.lom_odometry_get_quality.argtypes = [vp, C.POINTER(QualityReport)]
-    plp = C.POINTER(PlaceParams)
-    L.lom_place_db_create.argtypes = [plp, C.c_int, C.c_size_t, C.POINTER(vp)]
-    L.lom_place_db_destroy.argtypes = [vp]
-    L.lom_place_db_destroy.restype = None
-    L.lom_place_db_last_error.argtypes = [vp]
-    L.lom_place_db_last_error.restype = C.c_char_p
-    L.lom_place_db_size.argtypes = [vp]
-    L.lom_place_db_size.restype = C.c_int64
-    L.lom_place_db_clear.argtypes = [vp]
-    L.lom_place_db_params.argtypes = [vp, plp]
-    L.lom_place_db_stream.argtypes = [vp]
-    L.lom_place_db_stream.restype = vp
-    L.lom_place_db_device.argtypes = [vp]
-    L.lom_place_db_wait_event.argtypes = [vp, vp]
-    L.lom_place_describe.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
-    L.lom_place_describe_device.argtypes = L.lom_place_describe.argtypes
-    L.lom_place_db_add.argtypes = [vp, vp]
-    L.lom_place_db_add.restype = C.c_int64
-    L.lom_place_db_add_cloud.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
-    L.lom_place_db_add_cloud.restype = C.c_int64
-    L.lom_place_db_add_cloud_device.argtypes = L.lom_place_db_add_cloud.argtypes
-    L.lom_place_db_add_cloud_device.restype = C.c_int64
-    L.lom_place_db_get.argtypes = [vp, C.c_int64, vp]
-    L.lom_place_db_query.argtypes = [vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_int, vp, vp]
-    L.lom_place_db_query_cloud_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, C.c_int64, C.c_int64, C.c_int, vp]
-    L.lom_place_shift_yaw.argtypes = [plp, C.c_uint32]
-    L.lom_place_shift_yaw.restype = C.c_double
-    L.lom_odometry_place_descriptor.argtypes = [vp, vp, C.c_int, vp, C.POINTER(C.c_int64)]
-    L.lom_frontend_deskewed.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint32)]
-    L.lom_graph_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(vp)]
-    L.lom_graph_destroy.argtypes = [vp]
-    L.lom_graph_destroy.restype = None
-    L.lom_graph_last_error.argtypes = [vp]
-    L.lom_graph_last_error.restype = C.c_char_p
-    L.lom_graph_clear.argtypes = [vp]
-    L.lom_graph_stream.argtypes = [vp]
-    L.lom_graph_stream.restype = vp
-    L.lom_graph_device.argtypes = [vp]
-    L.lom_graph_add_node.argtypes = [vp, vp, C.c_int]
-    L.lom_graph_add_nodes.argtypes = [vp, vp, vp, C.c_size_t]
-    L.lom_graph_add_edge.argtypes = [vp, C.c_int64, C.c_int64, vp, vp, C.c_double]
-    L.lom_graph_add_edges.argtypes = [vp, vp, vp, vp, vp, C.c_size_t]
-    for fn in (L.lom_graph_add_node, L.lom_graph_add_nodes, L.lom_graph_add_edge, L.lom_graph_add_edges):
-        fn.restype = C.c_int64
-    L.lom_graph_node_count.argtypes = [vp]
-    L.lom_graph_node_count.restype = C.c_int64
-    L.lom_graph_edge_count.argtypes = [vp]
-    L.lom_graph_edge_count.restype = C.c_int64
-    L.lom_graph_get_poses.argtypes = [vp, C.c_int64, C.c_int64, vp]
-    L.lom_graph_set_pose.argtypes = [vp, C.c_int64, vp]
-    L.lom_graph_set_fixed.argtypes = [vp, C.c_int64, C.c_int]
-    L.lom_graph_optimize.argtypes = [vp, C.POINTER(GraphParams), C.POINTER(GraphStats)]
-    L.lom_graph_evaluate.argtypes = [vp, C.c_double, vp, vp, vp, vp, vp]
-    L.lom_graph_debug_matvec.argtypes = [vp, C.c_double, vp, vp]
-    L.lom_graph_edge_chi2.argtypes = [vp, C.c_int64, C.c_int64, vp]
-    L.lom_graph_check_gauge.argtypes = [C.c_int64, vp, C.c_int64, vp, C.POINTER(C.c_int64)]
-    L.lom_graph_lm_policy.argtypes = [C.c_double, C.c_double, C.c_double, dp, dp, dp]
-    L.lom_graph_information_from_quality.argtypes = [C.POINTER(QualityReport), C.c_int, vp]
-    L.lom_graph_pose_from_f32.argtypes = [pp, vp]
-    L.lom_graph_pose_to_f32.argtypes = [vp, pp]
-    L.lom_archive_create.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(vp)]
-    L.lom_archive_destroy.argtypes = [vp]
-    L.lom_archive_destroy.restype = None
-    L.lom_archive_last_error.argtypes = [vp]
-    L.lom_archive_last_error.restype = C.c_char_p
-    L.lom_archive_clear.argtypes = [vp]
-    L.lom_archive_stream.argtypes = [vp]
-    L.lom_archive_stream.restype = vp
-    L.lom_archive_device.argtypes = [vp]
-    L.lom_archive_wait_event.argtypes = [vp, vp]
-    L.lom_archive_add.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t]
-    L.lom_archive_add_device.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, vp]
-    L.lom_archive_scan_count.argtypes = [vp]
-    L.lom_archive_point_count.argtypes = [vp]
-    L.lom_archive_scan_size.argtypes = [vp, C.c_int64]
-    L.lom_archive_get.argtypes = [vp, C.c_int64, vp, vp, C.c_size_t]
-    for fn in (L.lom_archive_add, L.lom_archive_add_device, L.lom_archive_scan_count, L.lom_archive_point_count,
-               L.lom_archive_scan_size, L.lom_archive_get):
-        fn.restype = C.c_int64
-    L.lom_map_assemble.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(AssembleParams), C.POINTER(AssembleStats)]
-    L.lom_graph_pose_rotation_matrix.argtypes = [vp, vp]
-    L.lom_odometry_archive_scan.argtypes = [vp, vp, C.POINTER(C.c_int64)]
-    L.lom_odometry_rebuild_keyframe.argtypes = [vp, vp, vp, vp, C.c_size_t, pp, C.POINTER(AssembleStats)]
-    L.lom_map_carve_scans.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(VoteParams), C.POINTER(VoteStats)]
-    L.lom_map_scan_votes.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(VoteParams), vp, vp, C.c_size_t]
-    L.lom_map_scan_votes.restype = C.c_int64
-    L.lom_odometry_set_rebuild_votes.argtypes = [vp, C.POINTER(VoteParams)]
-    L.lom_odometry_get_rebuild_vote_stats.argtypes = [vp, C.POINTER(VoteStats)]
-    L.lom_archive_add_points.argtypes = [vp, vp, C.c_size_t, C.c_size_t]
-    L.lom_archive_add_points_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp]
-    L.lom_archive_add_points.restype = L.lom_archive_add_points_device.restype = C.c_int64
-    L.lom_odometry_archive_deskewed.argtypes = [vp, vp, C.POINTER(C.c_int64)]
-    L.lom_odometry_occupancy_scan.argtypes = [vp, vp, C.POINTER(OccupancyRayParams), C.POINTER(OccupancyStats)]
-    L.lom_occupancy_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
-    L.lom_occupancy_destroy.argtypes = [vp]
-    L.lom_occupancy_destroy.restype = None
-    L.lom_occupancy_last_error.argtypes = [vp]
-    L.lom_occupancy_last_error.restype = C.c_char_p
-    L.lom_occupancy_clear.argtypes = [vp]
-    L.lom_occupancy_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
-    L.lom_occupancy_stream.argtypes = [vp]
-    L.lom_occupancy_stream.restype = vp
-    L.lom_occupancy_device.argtypes = [vp]
-    L.lom_occupancy_wait_event.argtypes = [vp, vp]
-    L.lom_occupancy_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_occupancy_integrate.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(OccupancyRayParams), C.POINTER(OccupancyStats)]
-    L.lom_occupancy_integrate_cloud.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(OccupancyRayParams),
-                                                C.POINTER(OccupancyStats)]
-    L.lom_occupancy_integrate_cloud_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(OccupancyRayParams), vp,
-                                                       C.POINTER(OccupancyStats)]
-    L.lom_occupancy_counts.argtypes = [vp, vp, vp, C.c_size_t]
-    L.lom_occupancy_counts.restype = C.c_int64
-    L.lom_occupancy_classify.argtypes = [vp, C.POINTER(OccupancyRule), vp, C.c_size_t, C.POINTER(OccupancySummary)]
-    L.lom_occupancy_classify_device.argtypes = [vp, C.POINTER(OccupancyRule), C.POINTER(vp)]
-    L.lom_odometry_elevation_scan.argtypes = [vp, vp, C.POINTER(ElevationPointParams), C.POINTER(ElevationStats)]
-    L.lom_elevation_create.argtypes = [C.POINTER(ElevationGeometry), C.c_int, C.POINTER(vp)]
-    L.lom_elevation_destroy.argtypes = [vp]
-    L.lom_elevation_destroy.restype = None
-    L.lom_elevation_last_error.argtypes = [vp]
-    L.lom_elevation_last_error.restype = C.c_char_p
-    L.lom_elevation_clear.argtypes = [vp]
-    L.lom_elevation_get_geometry.argtypes = [vp, C.POINTER(ElevationGeometry)]
-    L.lom_elevation_stream.argtypes = [vp]
-    L.lom_elevation_stream.restype = vp
-    L.lom_elevation_device.argtypes = [vp]
-    L.lom_elevation_wait_event.argtypes = [vp, vp]
-    L.lom_elevation_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_elevation_integrate.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(ElevationPointParams), C.POINTER(ElevationStats)]
-    L.lom_elevation_integrate_cloud.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(ElevationPointParams),
-                                                C.POINTER(ElevationStats)]
-    L.lom_elevation_integrate_cloud_device.argtypes = [vp, vp, C.c_size_t, C.c_size_t, vp, C.POINTER(ElevationPointParams), vp,
-                                                       C.POINTER(ElevationStats)]
-    L.lom_elevation_cells.argtypes = [vp, vp, vp, vp, vp, C.c_size_t]
-    L.lom_elevation_cells.restype = C.c_int64
-    L.lom_elevation_layers.argtypes = [vp, C.POINTER(ElevationLayerParams), vp, vp, vp, vp, vp, vp, C.c_size_t]
-    L.lom_elevation_cost.argtypes = [vp, C.POINTER(ElevationLayerParams), C.POINTER(ElevationCostParams), vp, C.c_size_t,
-                                     C.POINTER(ElevationSummary)]
-    L.lom_elevation_cost_device.argtypes = [vp, C.POINTER(ElevationLayerParams), C.POINTER(ElevationCostParams), C.POINTER(vp)]
-    L.lom_clearance_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
-    L.lom_clearance_destroy.argtypes = [vp]
-    L.lom_clearance_destroy.restype = None
-    L.lom_clearance_last_error.argtypes = [vp]
-    L.lom_clearance_last_error.restype = C.c_char_p
-    L.lom_clearance_clear.argtypes = [vp]
-    L.lom_clearance_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
-    L.lom_clearance_stream.argtypes = [vp]
-    L.lom_clearance_stream.restype = vp
-    L.lom_clearance_device.argtypes = [vp]
-    L.lom_clearance_wait_event.argtypes = [vp, vp]
-    L.lom_clearance_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_clearance_update.argtypes = [vp, vp, vp, C.POINTER(ClearanceParams), C.POINTER(ClearanceWindow), C.POINTER(ClearanceSummary)]
-    L.lom_clearance_update_device.argtypes = [vp, vp, vp, vp, C.POINTER(ClearanceParams), C.POINTER(ClearanceWindow),
-                                              C.POINTER(ClearanceSummary)]
-    L.lom_clearance_update_from_grids.argtypes = [vp, vp, C.POINTER(OccupancyRule), vp, C.POINTER(ElevationLayerParams),
-                                                  C.POINTER(ElevationCostParams), C.POINTER(ClearanceParams),
-                                                  C.POINTER(ClearanceWindow), C.POINTER(ClearanceSummary)]
-    L.lom_clearance_cost.argtypes = [vp, vp, C.c_size_t, C.POINTER(ClearanceSummary)]
-    L.lom_clearance_cost_device.argtypes = [vp, C.POINTER(vp)]
-    L.lom_clearance_distance_sq.argtypes = [vp, vp, C.c_size_t]
-    L.lom_clearance_distance.argtypes = [vp, vp, C.c_size_t]
-    L.lom_clearance_cost_table.argtypes = [C.POINTER(ClearanceParams), C.POINTER(OccupancyGeometry), vp, C.c_size_t]
-    L.lom_clearance_cost_table.restype = C.c_int64
-    L.lom_clearance_query.argtypes = [vp, vp, C.c_size_t, vp, vp]
-    L.lom_navfield_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
-    L.lom_navfield_destroy.argtypes = [vp]
-    L.lom_navfield_destroy.restype = None
-    L.lom_navfield_last_error.argtypes = [vp]
-    L.lom_navfield_last_error.restype = C.c_char_p
-    L.lom_navfield_clear.argtypes = [vp]
-    L.lom_navfield_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
-    L.lom_navfield_stream.argtypes = [vp]
-    L.lom_navfield_stream.restype = vp
-    L.lom_navfield_device.argtypes = [vp]
-    L.lom_navfield_wait_event.argtypes = [vp, vp]
-    L.lom_navfield_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_navfield_solve.argtypes = [vp, vp, C.POINTER(NavFieldParams), C.c_int, vp, C.c_size_t, C.POINTER(NavFieldSummary)]
-    L.lom_navfield_solve_device.argtypes = [vp, vp, vp, C.POINTER(NavFieldParams), C.c_int, vp, C.c_size_t, C.POINTER(NavFieldSummary)]
-    L.lom_navfield_solve_from_clearance.argtypes = [vp, vp, C.POINTER(NavFieldParams), C.c_int, vp, C.c_size_t,
-                                                    C.POINTER(NavFieldSummary)]
-    L.lom_navfield_potential.argtypes = [vp, vp, C.c_size_t]
-    L.lom_navfield_potential_device.argtypes = [vp, C.POINTER(vp)]
-    L.lom_navfield_paths.argtypes = [vp, C.c_int, vp, C.c_size_t, vp, C.c_size_t, vp]
-    L.lom_navfield_query.argtypes = [vp, vp, C.c_size_t, vp]
-    L.lom_navfield_cell_costs.argtypes = [C.POINTER(NavFieldParams), vp]
-    L.lom_navfield_stats.argtypes = [vp, C.POINTER(NavFieldSolveStats)]
-    L.lom_regions_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
-    L.lom_regions_destroy.argtypes = [vp]
-    L.lom_regions_destroy.restype = None
-    L.lom_regions_last_error.argtypes = [vp]
-    L.lom_regions_last_error.restype = C.c_char_p
-    L.lom_regions_clear.argtypes = [vp]
-    L.lom_regions_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
-    L.lom_regions_stream.argtypes = [vp]
-    L.lom_regions_stream.restype = vp
-    L.lom_regions_device.argtypes = [vp]
-    L.lom_regions_wait_event.argtypes = [vp, vp]
-    L.lom_regions_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_regions_extract.argtypes = [vp, vp, vp, vp, C.POINTER(RegionsParams), C.POINTER(RegionsSummary)]
-    L.lom_regions_extract_device.argtypes = [vp, vp, vp, vp, vp, C.POINTER(RegionsParams), C.POINTER(RegionsSummary)]
-    L.lom_regions_extract_from_grids.argtypes = [vp, vp, C.POINTER(OccupancyRule), vp, vp, C.POINTER(RegionsParams),
-                                                 C.POINTER(RegionsSummary)]
-    L.lom_regions_labels.argtypes = [vp, vp, C.c_size_t]
-    L.lom_regions_labels_device.argtypes = [vp, C.POINTER(vp)]
-    L.lom_regions_list.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.lom_regions_goals.argtypes = [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.lom_regions_query.argtypes = [vp, vp, C.c_size_t, vp]
-    L.lom_regions_stats.argtypes = [vp, C.POINTER(RegionsExtractStats)]
-    L.lom_visibility_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
-    L.lom_visibility_destroy.argtypes = [vp]
-    L.lom_visibility_destroy.restype = None
-    L.lom_visibility_last_error.argtypes = [vp]
-    L.lom_visibility_last_error.restype = C.c_char_p
-    L.lom_visibility_clear.argtypes = [vp]
-    L.lom_visibility_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
-    L.lom_visibility_stream.argtypes = [vp]
-    L.lom_visibility_stream.restype = vp
-    L.lom_visibility_device.argtypes = [vp]
-    L.lom_visibility_wait_event.argtypes = [vp, vp]
-    L.lom_visibility_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    L.lom_visibility_table.argtypes = [C.c_uint32, vp]
-    L.lom_visibility_cast.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(VisibilityParams), C.POINTER(VisibilitySummary)]
-    L.lom_visibility_cast_device.argtypes = [vp, vp, vp, vp, C.c_size_t, C.POINTER(VisibilityParams), C.POINTER(VisibilitySummary)]
-    L.lom_visibility_cast_from_occupancy.argtypes = [vp, vp, C.POINTER(OccupancyRule), vp, C.c_size_t, C.POINTER(VisibilityParams),
-                                                     C.POINTER(VisibilitySummary)]
-    L.lom_visibility_records.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.lom_visibility_beams.argtypes = [vp, vp, C.c_size_t]
-    L.lom_visibility_windows_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
-    L.lom_visibility_windows.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.lom_visibility_select.argtypes = [vp, C.POINTER(VisibilitySelectParams), vp, vp, C.POINTER(C.c_size_t)]
-    L.lom_visibility_select_from_navfield.argtypes = [vp, vp, C.POINTER(VisibilitySelectParams), vp, C.POINTER(C.c_size_t)]
-    L.lom_visibility_stats.argtypes = [vp, C.POINTER(VisibilityCallStats)]
-    L.lom_rollout_create.argtypes = [C.POINTER(OccupancyGeometry), C.c_int, C.POINTER(vp)]
-    L.lom_rollout_destroy.argtypes = [vp]
-    L.lom_rollout_destroy.restype = None
-    L.lom_rollout_last_error.argtypes = [vp]
-    L.lom_rollout_last_error.restype = C.c_char_p
-    L.lom_rollout_clear.argtypes = [vp]
-    L.lom_rollout_get_geometry.argtypes = [vp, C.POINTER(OccupancyGeometry)]
-    L.lom_rollout_stream.argtypes = [vp]
-    L.lom_rollout_stream.restype = vp
-    L.lom_rollout_device.argtypes = [vp]
-    L.lom_rollout_wait_event.argtypes = [vp, vp]
-    L.lom_rollout_set_option.argtypes = [vp, C.c_int, C.c_int64]
-    # states, m, commands, k, footprint, f, params, picks, summary: the tail of every evaluate form
-    tail = [vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(RolloutParams), vp, C.POINTER(RolloutSummary)]
-    L.lom_rollout_evaluate.argtypes = [vp, vp, vp] + tail
-    L.lom_rollout_evaluate_device.argtypes = [vp, vp, vp, vp, vp] + tail
-    L.lom_rollout_evaluate_from_grids.argtypes = [vp, vp, vp] + tail
-    L.lom_rollout_records.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.lom_rollout_stats.argtypes = [vp, C.POINTER(RolloutCallStats)]
-    L.lom_rollout_footprint_rectangle.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int, vp, C.c_size_t,
-                                                  C.POINTER(C.c_size_t)]
-    L.lom_rollout_state_from_pose.argtypes = [C.POINTER(OccupancyGeometry), C.c_float, C.c_float, C.c_float, vp]
-    L.lom_rollout_poses.argtypes = [C.POINTER(RolloutParams), vp, vp, vp]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
