@@ -1724,6 +1724,30 @@ int lom_clearance_query(lom_clearance *c, const float *xy, size_t n, float *dist
  * The result is a pure function of plane, parameters and goals: it does not depend on the tile shape, on the number of
  * launches, on the order in which workgroups run or on the test switches below.
  *
+ * Re-solve.  A field that has completed a solve keeps its plane, its table and P.  lom_navfield_resolve* takes a new
+ * full-grid int8 plane and an optional lom_clearance_window, with that struct's rules: the rectangle is clipped to the
+ * grid, NULL is the whole grid, an empty rectangle is LOM_OK and changes nothing.
+ *  a. Merged plane.  The kept plane with the cells of the clipped window replaced by the new plane's.  Cells outside the
+ *     window are not read: the caller need not keep them equal, they do not count.
+ *  b. Goals.  The cells with P == 0 before the call: the used goals of the last solve or re-solve.  No list is passed.  A
+ *     goal whose cell is impassable in the merged plane counts in goals_rejected and is gone for later re-solves;
+ *     goals_used + goals_rejected equals the previous goals_used.
+ *  c. Result.  P and the summary are, byte for byte, what lom_navfield_solve gives on the merged plane with the last
+ *     solve's parameters and those goals.  The kept plane becomes the merged plane; paths and queries read the new state;
+ *     lom_navfield_potential_device's pointer stays valid across the call.
+ *  d. Refusals.  Before the first successful solve since create or clear: LOM_ERR_STATE.  A NULL plane, or a clearance
+ *     grid of other geometry or on another device: LOM_ERR_ARG.  A refused call changes nothing and zeroes the summary.
+ * The work is incremental and still exact, because the field is the unique fixed point of a relaxation on positive
+ * weights.  A diff over the window finds the changed cells (cells_changed: the bytes that differ from the kept ones) and
+ * sets those that are now impassable to unreached; none changed ends the call there.  The raise phase then sets every
+ * reached cell unreached that no chain of supporters carries down to a goal under the merged plane -- a supporter of a
+ * is a cell b with an allowed step a -> b and P[b] + len * c[a] <= P[a]; cells_raised counts them, the least such set,
+ * which does not depend on the schedule -- and the relaxation of a solve lowers what is left, every value an upper bound,
+ * to the field.  LOM_NAV_OPT_TEST_RESOLVE_FORM chooses another way to the same bytes: 1, the threshold form, sets every
+ * reached cell with P > 0 and P >= pmin unreached instead, pmin the least positive P among the changed cells and their
+ * eight neighbours; 2 keeps only the goals and relaxes from them, the full solve on the same handle.  cells_raised is what
+ * the chosen form set unreached behind the diff.
+ *
  * lom_navfield_solve takes a host plane of width * height bytes; _solve_device a plane in HBM that is complete when
  * hip_event_or_null is (NULL: now); _solve_from_clearance takes lom_clearance_cost_device's plane and orders the two
  * streams by events in both directions -- a clearance grid whose resolution, origin, width or height differ bit for bit,
@@ -1747,6 +1771,13 @@ typedef struct {
     uint64_t launches, waits; /* of k_nav_relax in the last solve, and the host's waits for them */
     uint64_t tiles;           /* workgroups per launch */
 } lom_navfield_solve_stats;
+typedef struct {
+    uint64_t cells_changed;  /* cells of the clipped window whose byte differs from the kept one */
+    uint64_t cells_raised;   /* reached cells that the raise phase (or the reset of another form) set unreached */
+    uint64_t raise_launches, relax_launches; /* of k_nav_raise and k_nav_relax */
+    uint64_t waits;          /* the host's waits of the call, the diff's and the summary's included */
+    uint64_t tiles_marked;   /* tiles active in the first launch of the relaxation */
+} lom_navfield_resolve_counters; /* what lom_navfield_resolve_stats gives */
 #define LOM_NAV_UNREACHED 0xFFFFFFFFu
 #define LOM_NAV_MAX 0xFFFFFFFEu
 enum { LOM_NAV_UNKNOWN_PASSABLE = 1 }; /* a -1 cell is passable at unknown_cost */
@@ -1754,8 +1785,10 @@ enum { LOM_NAV_CELLS = 0, LOM_NAV_METRES = 1 }; /* what goals and starts are: in
 enum {
     LOM_NAV_OPT_TEST_INNER_CAP = 1, /* sweeps of a tile per launch, 1 .. 2^20; 1: a launch is one sweep per active tile; <= 0: the default */
     LOM_NAV_OPT_TEST_BATCH = 2,     /* launches per wait, 1 .. 256; <= 0: the default */
-    LOM_NAV_OPT_TEST_ALL_TILES = 3  /* 1: every tile is active in every launch; 0 or < 0, the default: only marked tiles.
-                                       Test switches: the bytes are the same. */
+    LOM_NAV_OPT_TEST_ALL_TILES = 3, /* 1: every tile is active in every launch; 0 or < 0, the default: only marked tiles */
+    LOM_NAV_OPT_TEST_RESOLVE_FORM = 4 /* of a re-solve: 0 or < 0, the default: raise, then relax; 1: the threshold form; 2: the
+                                         full solve from the kept goals.  Test switches: the bytes are the same.  The first
+                                         three act on both phases of a re-solve. */
 };
 int lom_navfield_create(const lom_occupancy_geometry *geometry, int device, lom_navfield **out);
 void lom_navfield_destroy(lom_navfield *f);
@@ -1773,6 +1806,15 @@ int lom_navfield_solve_device(lom_navfield *f, const int8_t *d_plane, void *hip_
                               int goal_kind, const void *goals, size_t n_goals, lom_navfield_summary *summary_or_null);
 int lom_navfield_solve_from_clearance(lom_navfield *f, lom_clearance *clearance, const lom_navfield_params *params, int goal_kind,
                                       const void *goals, size_t n_goals, lom_navfield_summary *summary_or_null);
+/* the re-solve: a host plane of width * height bytes, of which the window's rows are read; a plane in HBM that is complete
+ * when hip_event_or_null is; lom_clearance_cost_device's plane behind a (windowed) lom_clearance_update*, with the hand-off
+ * of _solve_from_clearance */
+int lom_navfield_resolve(lom_navfield *f, const int8_t *plane, const lom_clearance_window *window_or_null,
+                         lom_navfield_summary *summary_or_null);
+int lom_navfield_resolve_device(lom_navfield *f, const int8_t *d_plane, void *hip_event_or_null,
+                                const lom_clearance_window *window_or_null, lom_navfield_summary *summary_or_null);
+int lom_navfield_resolve_from_clearance(lom_navfield *f, lom_clearance *clearance, const lom_clearance_window *window_or_null,
+                                        lom_navfield_summary *summary_or_null);
 /* P over the whole grid, row-major: at most `cap` cells go to `out` (may be NULL with cap 0) */
 int lom_navfield_potential(lom_navfield *f, uint32_t *out, size_t cap);
 /* the same, left in HBM: width * height cells, valid until the next solve or clear on the handle */
@@ -1787,6 +1829,8 @@ int lom_navfield_query(lom_navfield *f, const float *xy, size_t n, uint32_t *out
 int lom_navfield_cell_costs(const lom_navfield_params *params, uint32_t *out256);
 /* the launches and waits of the last solve (zeros before the first) */
 int lom_navfield_stats(const lom_navfield *f, lom_navfield_solve_stats *out);
+/* the counts of the last re-solve (zeros before the first, and for an empty window) */
+int lom_navfield_resolve_stats(const lom_navfield *f, lom_navfield_resolve_counters *out);
 
 /* ---- frontier regions: connected cells labelled on the device, ranked goals (not in the reference) ----------------------
  * The navigation field answers what it costs to get somewhere.  This handle family answers where to go: it labels the

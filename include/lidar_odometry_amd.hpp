@@ -1183,6 +1183,26 @@ public:
         check(lom_navfield_solve_from_clearance(h_, clearance.handle(), &params, goal_kind, goals, n, &s));
         return s;
     }
+    // the re-solve: the window's cells (NULL: the whole grid) of a host plane of size() cells, for the goals the last solve used
+    lom_navfield_summary resolve(const int8_t *plane, const lom_clearance_window *window = nullptr)
+    {
+        lom_navfield_summary s;
+        check(lom_navfield_resolve(h_, plane, window, &s));
+        return s;
+    }
+    // ... of the plane a ClearanceGrid of this geometry left in HBM
+    lom_navfield_summary resolveFromClearance(ClearanceGrid &clearance, const lom_clearance_window *window = nullptr)
+    {
+        lom_navfield_summary s;
+        check(lom_navfield_resolve_from_clearance(h_, clearance.handle(), window, &s));
+        return s;
+    }
+    lom_navfield_resolve_counters resolveStats() const
+    {
+        lom_navfield_resolve_counters s;
+        check(lom_navfield_resolve_stats(h_, &s));
+        return s;
+    }
     std::vector<uint32_t> potential()
     {
         std::vector<uint32_t> out(size());

@@ -1415,6 +1415,33 @@ class NavField(_PlaneGrid):
         self._check(self._call("solve_from_clearance", self._h, clearance.handle, C.byref(p), kind, g.ctypes.data, len(g), C.byref(sm)))
         return sm.asdict()
 
+    def resolve(self, plane, window=None, device=False, hip_event=None):
+        """lom_navfield_resolve: the field of the kept plane with the cells of `window` ((x0, y0, width, height) in cells,
+        None: the whole grid) taken from the host plane `plane`, for the goals the last solve used -- or, with device=True,
+        lom_navfield_resolve_device: `plane` is a device pointer to a plane in HBM, complete when `hip_event` is.  Returns
+        capi.NavFieldSummary as a dict."""
+        sm = capi.NavFieldSummary()
+        if device:
+            rc = self._call("resolve_device", self._h, plane, hip_event, ClearanceGrid._window(window), C.byref(sm))
+        else:
+            plane = self._plane(plane, np.int8)
+            rc = self._call("resolve", self._h, plane.ctypes.data, ClearanceGrid._window(window), C.byref(sm))
+        self._check(rc)
+        return sm.asdict()
+
+    def resolveFromClearance(self, clearance, window=None):
+        """lom_navfield_resolve_from_clearance: the window of the cost plane a ClearanceGrid of this geometry left in HBM"""
+        sm = capi.NavFieldSummary()
+        self._check(self._call("resolve_from_clearance", self._h, clearance.handle, ClearanceGrid._window(window), C.byref(sm)))
+        return sm.asdict()
+
+    def resolveStats(self):
+        """capi.NavFieldResolveCounters of the last re-solve as a dict: cells_changed, cells_raised, raise_launches,
+        relax_launches, waits, tiles_marked"""
+        st = capi.NavFieldResolveCounters()
+        self._check(self._call("resolve_stats", self._h, C.byref(st)))
+        return st.asdict()
+
     def potential(self):
         """uint32 array of shape (height, width): P per cell, capi.NAV_UNREACHED where no goal is reached"""
         out = np.empty((self.height, self.width), np.uint32)

@@ -368,11 +368,21 @@ class NavFieldSolveStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class NavFieldResolveCounters(C.Structure):
+    """lom_navfield_resolve_counters"""
+    _fields_ = [("cells_changed", C.c_uint64), ("cells_raised", C.c_uint64), ("raise_launches", C.c_uint64),
+                ("relax_launches", C.c_uint64), ("waits", C.c_uint64), ("tiles_marked", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 assert C.sizeof(NavFieldParams) == 20 and C.sizeof(NavFieldSummary) == 64 and C.sizeof(NavFieldSolveStats) == 24
+assert C.sizeof(NavFieldResolveCounters) == 48
 NAV_UNREACHED, NAV_MAX = 0xFFFFFFFF, 0xFFFFFFFE
 NAV_UNKNOWN_PASSABLE = 1
 NAV_CELLS, NAV_METRES = 0, 1
-NAV_OPT_TEST_INNER_CAP, NAV_OPT_TEST_BATCH, NAV_OPT_TEST_ALL_TILES = 1, 2, 3
+NAV_OPT_TEST_INNER_CAP, NAV_OPT_TEST_BATCH, NAV_OPT_TEST_ALL_TILES, NAV_OPT_TEST_RESOLVE_FORM = 1, 2, 3, 4
 
 
 class RegionsParams(C.Structure):
@@ -783,6 +793,10 @@ PROTOTYPES = {
     "lom_navfield_solve": (_int, [_vp, _vp, _P(NavFieldParams), _int, _vp, _size, _P(NavFieldSummary)]),
     "lom_navfield_solve_device": (_int, [_vp, _vp, _vp, _P(NavFieldParams), _int, _vp, _size, _P(NavFieldSummary)]),
     "lom_navfield_solve_from_clearance": (_int, [_vp, _vp, _P(NavFieldParams), _int, _vp, _size, _P(NavFieldSummary)]),
+    "lom_navfield_resolve": (_int, [_vp, _vp, _P(ClearanceWindow), _P(NavFieldSummary)]),
+    "lom_navfield_resolve_device": (_int, [_vp, _vp, _vp, _P(ClearanceWindow), _P(NavFieldSummary)]),
+    "lom_navfield_resolve_from_clearance": (_int, [_vp, _vp, _P(ClearanceWindow), _P(NavFieldSummary)]),
+    "lom_navfield_resolve_stats": (_int, [_vp, _P(NavFieldResolveCounters)]),
     "lom_navfield_potential": (_int, [_vp, _vp, _size]),
     "lom_navfield_potential_device": (_int, [_vp, _P(_vp)]),
     "lom_navfield_paths": (_int, [_vp, _int, _vp, _size, _vp, _size, _vp]),

@@ -1,13 +1,16 @@
 // Navigation field: the least total cost to reach a goal, per cell, over an int8 cost plane; paths down it and point
 // queries.  Definitions: include/lidar_odometry_amd.h ("navigation field"); kernels: k_navfield.hpp; host planning (value
-// ranges, the cell-cost table, goal quantisation, tile counts, launch shapes): navfield_host.cpp; DESIGN.md 7m.  A handle
-// family of its own on the PlaneHandle core (plane_handle.hpp); no default path launches any of this.
+// ranges, the cell-cost table, goal quantisation, tile counts, launch shapes): navfield_host.cpp; DESIGN.md 7m.  The
+// re-solve after a local cost change (k_navfield_resolve.hpp) keeps what a solve left and repairs it.  A
+// handle family of its own on the PlaneHandle core (plane_handle.hpp); no default path launches any of this.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "clearance_host.hpp"
 #include "k_navfield.hpp"
+#include "k_navfield_resolve.hpp"
 #include "navfield_host.hpp"
 #include "plane_handle.hpp"
 
@@ -23,9 +26,10 @@ struct lom_navfield : lom::PlaneHandle {  // in_ev: the clearance grid's
     lom::DeviceBuf field;            // u32 per cell
     lom::DeviceBuf plane;            // the cost bytes of the last solve
     lom::DeviceBuf table;            // 256 u32: the cell costs of the last solve
-    lom::DeviceBuf marks;            // 2 x n_tiles u32: the tiles active in an even and in an odd launch
+    lom::DeviceBuf marks;            // 3 x n_tiles u32: the tiles active in an even and in an odd launch; a re-solve's seeds
     lom::DeviceBuf flags;            // kBatchMax u32: "launch j of the batch marked a tile"
-    lom::DeviceBuf words;            // the summary words
+    lom::DeviceBuf words;            // the summary words, and behind them a re-solve's
+    lom::DeviceBuf incoming;         // the window's rows of a re-solve's host plane, grow-only
     lom::DeviceBuf points;           // goals or starts as int32 pairs, grow-only
     lom::DeviceBuf path_cells, path_lengths;  // a paths call's results, grow-only
     lom::DeviceBuf q_xy, q_out;      // a query's points and results, grow-only
@@ -34,7 +38,11 @@ struct lom_navfield : lom::PlaneHandle {  // in_ev: the clearance grid's
     uint32_t inner_cap = navfield::kInnerCapDefault;  // LOM_NAV_OPT_TEST_INNER_CAP
     uint32_t batch = navfield::kBatchDefault;         // LOM_NAV_OPT_TEST_BATCH
     uint32_t all_tiles = 0;                           // LOM_NAV_OPT_TEST_ALL_TILES
+    uint32_t resolve_form = 0;                        // LOM_NAV_OPT_TEST_RESOLVE_FORM
     lom_navfield_solve_stats stats{};
+    lom_navfield_resolve_counters resolve_stats{};
+    bool solved = false;             // a solve has completed since create or clear: plane, table and P are a fixed point
+    uint32_t last_words[NW_COUNT] = {};  // ... and its summary words: what a re-solve that changes nothing reports
 
     NavArgs args() const { return NavArgs{geo.width, geo.height, tiles.tiles_x, tiles.tiles_y}; }
 };
@@ -92,6 +100,55 @@ int upload_points(lom_navfield *f, int kind, const void *pts, size_t n, std::vec
     return LOM_OK;
 }
 
+// A fixed point over tiles, in batches of launches with one wait each.  Launch k reads the marks of parity k & 1 and
+// writes the others: launch(cur, nxt, flag) enqueues it.  A launch behind the fixed point finds no active tile (or, with
+// all tiles, changes nothing) and marks nothing, so the batch may run ahead of what the host knows.  Both arrays are
+// clear when this returns LOM_OK.
+template <class Launch>
+int to_fixed_point(lom_navfield *f, uint64_t &launches, uint64_t &waits, const char *unsettled, Launch launch)
+{
+    uint32_t *const marks = f->marks.as<uint32_t>();
+    const uint64_t bound = navfield::launch_bound(f->geo.width, f->geo.height);
+    const uint32_t B = f->batch;
+    for (;;) {
+        LOM_HIP(f, hipMemsetAsync(f->flags.p, 0, (size_t)B * 4, f->stream));
+        for (uint32_t j = 0; j < B; j++) {
+            const uint32_t parity = (uint32_t)(launches & 1u);
+            launch(marks + (size_t)parity * f->tiles.n_tiles, marks + (size_t)(parity ^ 1u) * f->tiles.n_tiles, f->flags.as<uint32_t>() + j);
+            LOM_HIP(f, hipGetLastError());
+            launches++;
+        }
+        LOM_HIP(f, hipMemcpyAsync(f->h_flags.h, f->flags.p, (size_t)B * 4, hipMemcpyDeviceToHost, f->stream));
+        LOM_HIP(f, hipStreamSynchronize(f->stream));
+        waits++;
+        if (f->h_flags.as<uint32_t>()[B - 1u] == 0u) return LOM_OK;  // the last launch marked nothing: the fixed point
+        if (launches > bound) return fail(f, LOM_ERR_HIP, unsettled);
+    }
+}
+
+// the relaxation from the marks of the first array to its fixed point
+int relax(lom_navfield *f, uint64_t &launches, uint64_t &waits)
+{
+    const NavArgs a = f->args();
+    return to_fixed_point(f, launches, waits, "navigation field: the relaxation did not settle", [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
+        hipLaunchKernelGGL(k_nav_relax, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0, f->stream, f->plane.as<const int8_t>(),
+                           f->table.as<const uint32_t>(), a, f->inner_cap, f->all_tiles, f->field.as<uint32_t>(), cur, nxt, flag);
+    });
+}
+
+// the summary of the field as it stands: the report, the way out of the first n_words words, done_ev, the wait.  The words
+// are in h_flags.
+int report(lom_navfield *f, uint32_t n_words)
+{
+    hipLaunchKernelGGL(k_nav_report, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream, f->plane.as<const int8_t>(),
+                       f->table.as<const uint32_t>(), f->field.as<const uint32_t>(), f->args(), f->words.as<uint32_t>());
+    LOM_HIP(f, hipGetLastError());
+    LOM_HIP(f, hipMemcpyAsync(f->h_flags.h, f->words.p, (size_t)n_words * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    return LOM_OK;
+}
+
 // A solve over a plane in HBM that this stream may read now: the copy of the plane, the seed, the relaxation in batches of
 // launches with one wait each, the report, then the wait.  The arguments are valid.
 int solve_on_device(lom_navfield *f, const int8_t *d_plane, const lom_navfield_params &p, int goal_kind, const void *goals,
@@ -100,6 +157,7 @@ int solve_on_device(lom_navfield *f, const int8_t *d_plane, const lom_navfield_p
     // what can still fail for want of memory comes first: a refused call changes nothing
     std::vector<int32_t> goal_cells;
     if (const int rc = upload_points(f, goal_kind, goals, n_goals, goal_cells); rc != LOM_OK) return rc;
+    f->solved = false;
     navfield::cell_costs(p, f->h_table.as<uint32_t>());  // (every call waits for its work: nothing enqueued reads the block)
     LOM_HIP(f, hipMemcpyAsync(f->table.p, f->h_table.h, 256 * 4, hipMemcpyHostToDevice, f->stream));
     if (d_plane != f->plane.as<const int8_t>())
@@ -115,34 +173,90 @@ int solve_on_device(lom_navfield *f, const int8_t *d_plane, const lom_navfield_p
                            f->points.as<const int32_t>(), (uint32_t)n_goals, f->field.as<uint32_t>(), marks, f->words.as<uint32_t>());
         LOM_HIP(f, hipGetLastError());
     }
-    // Launch k reads the marks of parity k & 1 and writes the others.  A launch behind the fixed point finds no active
-    // tile (or, with all tiles, lowers nothing) and marks nothing, so the batch may run ahead of what the host knows.
     f->stats = lom_navfield_solve_stats{0, 0, f->tiles.n_tiles};
-    const uint64_t bound = navfield::launch_bound(f->geo.width, f->geo.height);
-    const uint32_t B = f->batch;
-    for (;;) {
-        LOM_HIP(f, hipMemsetAsync(f->flags.p, 0, (size_t)B * 4, f->stream));
-        for (uint32_t j = 0; j < B; j++) {
-            const uint32_t parity = (uint32_t)(f->stats.launches & 1u);
-            hipLaunchKernelGGL(k_nav_relax, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0, f->stream, plane, table, a,
-                               f->inner_cap, f->all_tiles, f->field.as<uint32_t>(), marks + (size_t)parity * f->tiles.n_tiles,
-                               marks + (size_t)(parity ^ 1u) * f->tiles.n_tiles, f->flags.as<uint32_t>() + j);
-            LOM_HIP(f, hipGetLastError());
-            f->stats.launches++;
-        }
-        LOM_HIP(f, hipMemcpyAsync(f->h_flags.h, f->flags.p, (size_t)B * 4, hipMemcpyDeviceToHost, f->stream));
-        LOM_HIP(f, hipStreamSynchronize(f->stream));
-        f->stats.waits++;
-        if (f->h_flags.as<uint32_t>()[B - 1u] == 0u) break;  // the last launch marked nothing: the fixed point
-        if (f->stats.launches > bound) return fail(f, LOM_ERR_HIP, "navigation field: the relaxation did not settle");
-    }
-    hipLaunchKernelGGL(k_nav_report, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream, plane, table,
-                       f->field.as<const uint32_t>(), a, f->words.as<uint32_t>());
-    LOM_HIP(f, hipGetLastError());
-    LOM_HIP(f, hipMemcpyAsync(f->h_flags.h, f->words.p, (size_t)NW_COUNT * 4, hipMemcpyDeviceToHost, f->stream));
-    LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
-    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    if (const int rc = relax(f, f->stats.launches, f->stats.waits); rc != LOM_OK) return rc;
+    if (const int rc = report(f, NW_COUNT); rc != LOM_OK) return rc;
+    std::memcpy(f->last_words, f->h_flags.h, sizeof f->last_words);
+    f->solved = true;
     if (summary) summary_from(f->h_flags.as<uint32_t>(), summary);
+    return LOM_OK;
+}
+
+// the refusals of every re-solve form that need no device: the code and the text, or LOM_OK
+int resolve_refusal(lom_navfield *f, bool have_plane)
+{
+    if (!have_plane) return fail(f, LOM_ERR_ARG, "navigation field re-solve: a cost plane");
+    if (!f->solved) return fail(f, LOM_ERR_STATE, "navigation field re-solve: no solve has completed since create or clear");
+    return LOM_OK;
+}
+
+// A re-solve from a plane in HBM that this stream may read now, over a window that is not empty: the diff and a wait;
+// then, where a cell changed, the raise phase to its fixed point (or the reset of another form), the relaxation from
+// the seeds to its fixed point, the report and the wait.  done_ev stands behind the diff, the one reader of d_new.
+int resolve_on_device(lom_navfield *f, const int8_t *d_new, const clearance::Rect &r, lom_navfield_summary *summary)
+{
+    const NavArgs a = f->args();
+    const navfield::TileRange tr = navfield::tile_range(r);
+    const uint32_t n_tiles = f->tiles.n_tiles, form = f->resolve_form;
+    const uint32_t *const table = f->table.as<const uint32_t>();
+    uint32_t *const field = f->field.as<uint32_t>(), *const words = f->words.as<uint32_t>();
+    uint32_t *const marks0 = f->marks.as<uint32_t>(), *const seeds = marks0 + (size_t)2 * n_tiles;
+    uint32_t *const h = f->h_flags.as<uint32_t>();
+    lom_navfield_resolve_counters &st = f->resolve_stats;
+    st = lom_navfield_resolve_counters{};
+    LOM_HIP(f, hipMemsetAsync(f->words.p, 0, (size_t)RW_END * 4, f->stream));
+    LOM_HIP(f, hipMemsetAsync(f->marks.p, 0, (size_t)3 * n_tiles * 4, f->stream));
+    // form 0: the seeds gather behind the raise phase, which starts from the diff's marks; form 1: the diff's marks are
+    // seeds at once; form 2: the goals' tiles are the seeds
+    hipLaunchKernelGGL(k_nav_diff, dim3(tr.n_tx, tr.n_ty), dim3(kNavThreads), 0, f->stream, d_new, table, a,
+                       NavWindow{r.x0, r.y0, r.x1, r.y1, tr.tx0, tr.ty0}, form == 1u ? 1u : 0u, f->plane.as<int8_t>(), field,
+                       form == 0u ? seeds : form == 1u ? marks0 : nullptr, form == 0u ? marks0 : nullptr, words);
+    LOM_HIP(f, hipGetLastError());
+    f->solved = false;
+    LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
+    LOM_HIP(f, hipMemcpyAsync(h, f->words.p, (size_t)RW_END * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    st.waits = 1;
+    st.cells_changed = h[RW_CHANGED];
+    const uint32_t rejected = h[NW_GOALS_REJECTED];
+    if (st.cells_changed != 0u) {
+        if (form == 0u) {
+            const int rc = to_fixed_point(f, st.raise_launches, st.waits, "navigation field: the raise phase did not settle",
+                                          [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
+                                              hipLaunchKernelGGL(k_nav_raise, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0,
+                                                                 f->stream, f->plane.as<const int8_t>(), table, a, f->inner_cap, f->all_tiles,
+                                                                 field, cur, nxt, seeds, flag, words);
+                                          });
+            if (rc != LOM_OK) return rc;
+            // (both arrays of the fixed point are clear: the seeds are the first launch's marks)
+            LOM_HIP(f, hipMemcpyAsync(marks0, seeds, (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, f->stream));
+        } else if (form == 1u) {
+            hipLaunchKernelGGL(k_nav_threshold, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream, a, field, marks0, words);
+            LOM_HIP(f, hipGetLastError());
+        } else {
+            hipLaunchKernelGGL(k_nav_reseed, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream,
+                               f->plane.as<const int8_t>(), table, a, field, marks0, words);
+            LOM_HIP(f, hipGetLastError());
+        }
+        if (const int rc = relax(f, st.relax_launches, st.waits); rc != LOM_OK) return rc;
+        if (const int rc = report(f, RW_END); rc != LOM_OK) return rc;
+        st.waits++;
+        st.cells_raised = h[RW_RAISED], st.tiles_marked = h[RW_TILES];
+        h[NW_GOALS_USED] = f->last_words[NW_GOALS_USED] - rejected;  // (the report counts cells: the goals are the host's to keep)
+        std::memcpy(f->last_words, h, sizeof f->last_words);
+    }
+    f->last_words[NW_GOALS_REJECTED] = rejected;
+    f->solved = true;
+    if (summary) summary_from(f->last_words, summary);
+    return LOM_OK;
+}
+
+// the summary of a re-solve over an empty window: the field as it stands, no goal rejected
+int resolve_nothing(lom_navfield *f, lom_navfield_summary *summary)
+{
+    f->resolve_stats = lom_navfield_resolve_counters{};
+    f->last_words[NW_GOALS_REJECTED] = 0u;
+    if (summary) summary_from(f->last_words, summary);
     return LOM_OK;
 }
 
@@ -163,7 +277,7 @@ int lom_navfield_create(const lom_occupancy_geometry *geometry, int device, lom_
     const size_t n = f->n_cells();
     if (rc == LOM_OK &&
         (alloc(f->field, n * 4) != hipSuccess || alloc(f->plane, n) != hipSuccess || alloc(f->table, 256 * 4) != hipSuccess ||
-         alloc(f->marks, (size_t)2 * f->tiles.n_tiles * 4) != hipSuccess ||
+         alloc(f->marks, (size_t)3 * f->tiles.n_tiles * 4) != hipSuccess ||
          alloc(f->flags, (size_t)navfield::kBatchMax * 4) != hipSuccess || alloc(f->words, 64) != hipSuccess))
         rc = create_fail(g_navfield_create_error, LOM_ERR_OOM, "hipMalloc (navigation field)");
     if (rc == LOM_OK) {
@@ -185,6 +299,7 @@ int lom_navfield_clear(lom_navfield *f)
 {
     if (!f) return LOM_ERR_ARG;
     LOM_HIP(f, hipSetDevice(f->device));
+    f->solved = false;
     if (const int rc = fill(f, true); rc != LOM_OK) return rc;
     LOM_HIP(f, hipStreamSynchronize(f->stream));
     return LOM_OK;
@@ -210,6 +325,10 @@ int lom_navfield_set_option(lom_navfield *f, int option, int64_t value)
     case LOM_NAV_OPT_TEST_ALL_TILES:
         if (value > 1) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_ALL_TILES: 0, 1, or < 0 for the default");
         f->all_tiles = value == 1 ? 1u : 0u;
+        return LOM_OK;
+    case LOM_NAV_OPT_TEST_RESOLVE_FORM:
+        if (value > 2) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_RESOLVE_FORM: 0, 1, 2, or < 0 for the default");
+        f->resolve_form = value <= 0 ? 0u : (uint32_t)value;
         return LOM_OK;
     default:
         return fail(f, LOM_ERR_ARG, "unknown navigation field option");
@@ -257,6 +376,56 @@ int lom_navfield_solve_from_clearance(lom_navfield *f, lom_clearance *clearance,
         return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
     if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
     if ((rc = solve_on_device(f, d_plane, *params, goal_kind, goals, n_goals, summary)) != LOM_OK) return rc;
+    return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
+}
+
+int lom_navfield_resolve_device(lom_navfield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_clearance_window *window_or_null,
+                                lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const int rc = resolve_refusal(f, d_plane != nullptr); rc != LOM_OK) return rc;
+    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
+    if (r.empty()) return resolve_nothing(f, summary);
+    LOM_HIP(f, hipSetDevice(f->device));
+    if (hip_event_or_null) LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event_or_null, 0));
+    return resolve_on_device(f, d_plane, r, summary);
+}
+
+int lom_navfield_resolve(lom_navfield *f, const int8_t *plane, const lom_clearance_window *window_or_null, lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const int rc = resolve_refusal(f, plane != nullptr); rc != LOM_OK) return rc;
+    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
+    if (r.empty()) return resolve_nothing(f, summary);
+    LOM_HIP(f, hipSetDevice(f->device));
+    // the rows of the window, whole, at their place in a plane of the device: the cells outside the window are not read
+    if (const int rc = ensure(f, f->incoming, f->n_cells()); rc != LOM_OK) return rc;
+    const size_t first = (size_t)r.y0 * f->geo.width, bytes = (size_t)(r.y1 - r.y0) * f->geo.width;
+    LOM_HIP(f, hipMemcpyAsync(f->incoming.as<int8_t>() + first, plane + first, bytes, hipMemcpyHostToDevice, f->stream));
+    return resolve_on_device(f, f->incoming.as<const int8_t>(), r, summary);
+}
+
+int lom_navfield_resolve_from_clearance(lom_navfield *f, lom_clearance *clearance, const lom_clearance_window *window_or_null,
+                                        lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const int rc = resolve_refusal(f, clearance != nullptr); rc != LOM_OK) return rc;
+    lom_occupancy_geometry g{};
+    (void)lom_clearance_get_geometry(clearance, &g);
+    int rc = plane_check_producer(f, kName, "clearance grid", g, lom_clearance_device(clearance));
+    if (rc != LOM_OK) return rc;
+    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
+    if (r.empty()) return resolve_nothing(f, summary);
+    LOM_HIP(f, hipSetDevice(f->device));
+    // the hand-off of plane_handle.hpp: read behind the clearance grid, re-solve, release to it
+    const int8_t *d_plane = nullptr;
+    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
+        return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
+    if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
+    if ((rc = resolve_on_device(f, d_plane, r, summary)) != LOM_OK) return rc;
     return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
 }
 
@@ -328,6 +497,13 @@ int lom_navfield_stats(const lom_navfield *f, lom_navfield_solve_stats *out)
 {
     if (!f || !out) return LOM_ERR_ARG;
     *out = f->stats;
+    return LOM_OK;
+}
+
+int lom_navfield_resolve_stats(const lom_navfield *f, lom_navfield_resolve_counters *out)
+{
+    if (!f || !out) return LOM_ERR_ARG;
+    *out = f->resolve_stats;
     return LOM_OK;
 }
 

@@ -1,6 +1,6 @@
-// Host planning of lom_navfield_*: value ranges, the cell-cost table, the quantisation of goals and starts, tile counts
-// and launch shapes.  Plain C++, no HIP: navfield.hip calls these, and tests/cpp/test_navfield.cpp compiles this file
-// alone.
+// Host planning of lom_navfield_*: value ranges, the cell-cost table, the quantisation of goals and starts, tile counts,
+// the tiles of a re-solve's window and launch shapes.  Plain C++, no HIP: navfield.hip calls these, and
+// tests/cpp/test_navfield.cpp compiles this file alone.
 #include "navfield_host.hpp"
 
 #include <cmath>
@@ -59,6 +59,13 @@ TileGrid tile_grid(uint32_t width, uint32_t height)
     t.tiles_x = (width + kTile - 1u) / kTile, t.tiles_y = (height + kTile - 1u) / kTile;
     t.n_tiles = t.tiles_x * t.tiles_y;  // at most 256 * 256
     return t;
+}
+
+TileRange tile_range(const clearance::Rect &window)
+{
+    if (window.empty()) return TileRange{0u, 0u, 0u, 0u};
+    const uint32_t tx0 = window.x0 / kTile, ty0 = window.y0 / kTile;
+    return TileRange{tx0, ty0, (window.x1 - 1u) / kTile - tx0 + 1u, (window.y1 - 1u) / kTile - ty0 + 1u};
 }
 
 uint32_t blocks_for(size_t n) { return n ? (uint32_t)((n + kThreads - 1u) / kThreads) : 1u; }

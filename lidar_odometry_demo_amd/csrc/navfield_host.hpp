@@ -1,12 +1,13 @@
 // Host planning of the navigation field (navfield_host.cpp), shared with navfield.hip.  Plain C++: nothing here needs a
 // device or a HIP header.  The value ranges of the geometry and the parameters, the cell-cost table, the quantisation of
-// goals and starts, the tile counts and the launch shapes.  Definitions: include/lidar_odometry_amd.h ("navigation
-// field").
+// goals and starts, the tile counts, the tiles of a re-solve's window and the launch shapes.  Definitions:
+// include/lidar_odometry_amd.h ("navigation field").
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 #include "../../include/lidar_odometry_amd.h"
+#include "clearance_host.hpp"  // Rect: a window clipped to the grid
 #include "plane_geometry.hpp"
 
 namespace lom {
@@ -44,6 +45,12 @@ bool cell_of_metres(const lom_occupancy_geometry &g, float x, float y, int32_t *
 // refuses those outside the grid), metres go through cell_of_metres.  false: an unknown kind.
 bool quantise(const lom_occupancy_geometry &g, int kind, const void *points, size_t n, int32_t *out);
 TileGrid tile_grid(uint32_t width, uint32_t height);
+// k_nav_diff: a workgroup per tile that holds a cell of the clipped window -- tiles [tx0, tx0 + n_tx) x [ty0, ty0 + n_ty);
+// none for an empty window
+struct TileRange {
+    uint32_t tx0, ty0, n_tx, n_ty;
+};
+TileRange tile_range(const clearance::Rect &window);
 // workgroups of kThreads lanes for n lanes (at least one)
 uint32_t blocks_for(size_t n);
 // More launches than any solve needs: a cell whose best route has d steps is final one launch after the next cell of
