@@ -1719,10 +1719,31 @@ int lom_clearance_query(lom_clearance *c, const float *xy, size_t n, float *dist
  *     is the full length even when it exceeds cap, only the first cap cells are written; the rest of a row is 0.  P falls
  *     strictly along a path, so a walk is bounded by the number of cells.
  *  7. Query.  n points in metres: the cell's P; LOM_NAV_UNREACHED for a point outside the grid or not a number.
+ *  8. Line of sight.  Cells A = (x0, y0) and B = (x1, y1), under c[] of step 1 with the parameters of the last solve, and
+ *     a threshold max_cell_cost.  A cell is clear iff c != 0 and (max_cell_cost == 0 or c <= max_cell_cost).  With dx =
+ *     x1 - x0, dy = y1 - y0, ax = |dx|, ay = |dy|, sx and sy their signs, and i, j the steps taken so far along x and y:
+ *     while (i, j) != (ax, ay), compare (2 i + 1) * ay with (2 j + 1) * ax (both below 2^27).  Less: x steps.  Greater: y
+ *     steps.  Equal: the segment passes through a lattice corner; both step at once, and B is not visible unless both side
+ *     cells (x + sx, y) and (x, y + sy) are clear -- the no-corner-cut rule of step 2.  Every cell stepped to, B included,
+ *     must be clear; the first one that is not ends the walk: not visible.  A itself is tested for nothing.  A == B is
+ *     visible.  A pair with either cell outside the grid is not visible.  The walk reaches B after ax + ay - (corners)
+ *     steps and reads the cells whose interior the open segment meets (tests/navfield_waypoints_ref.py restates that
+ *     on exact fractions).  lom_navfield_visible answers it for n pairs; after create or clear every cell is impassable,
+ *     so only A == B is visible.
+ *  9. Waypoints.  K starts, as in step 6, and lom_navfield_waypoint_params: max_cell_cost (0: any passable cell; neutral:
+ *     cells of cost byte 0 only), lookahead W in 1 .. 65535, route_cap >= 1 with K * route_cap <= 2^28, flags == 0;
+ *     anything else is LOM_ERR_ARG.  The route r[0 .. n - 1] of a start is the first n = min(length, route_cap) cells of
+ *     its step-6 path.  The anchor is a = 0 and r[0] is emitted; while a < n - 1 the next anchor is the greatest j in
+ *     (a, min(a + W, n - 1)] with r[j] visible from r[a] by step 8, a + 1 if none is, and r[next] is emitted.  Output: u16
+ *     (ix, iy) pairs in a [K, wp_cap] buffer, the rest of a row 0; counts[k], the full number of waypoints even above
+ *     wp_cap, 0 for a start that is not walked and 1 for a start on a goal; lengths[k], the full step-6 length, so a
+ *     route cut at route_cap shows.  The waypoints are a subsequence of the route with its first and last cell; W = 1
+ *     gives the route itself; every consecutive pair more than one route cell apart is visible.
  * After create or lom_navfield_clear every cell is unreached, every cell impassable.
  *
  * The result is a pure function of plane, parameters and goals: it does not depend on the tile shape, on the number of
- * launches, on the order in which workgroups run or on the test switches below.
+ * launches, on the order in which workgroups run or on the test switches below.  The waypoints of step 9 are a pure
+ * function of those, the starts and their three parameters.
  *
  * Re-solve.  A field that has completed a solve keeps its plane, its table and P.  lom_navfield_resolve* takes a new
  * full-grid int8 plane and an optional lom_clearance_window, with that struct's rules: the rectangle is clipped to the
@@ -1778,6 +1799,12 @@ typedef struct {
     uint64_t waits;          /* the host's waits of the call, the diff's and the summary's included */
     uint64_t tiles_marked;   /* tiles active in the first launch of the relaxation */
 } lom_navfield_resolve_counters; /* what lom_navfield_resolve_stats gives */
+typedef struct {
+    uint32_t max_cell_cost; /* a cell is clear up to this cell cost; 0: any passable cell */
+    uint32_t lookahead;     /* W: route cells a shortcut may skip to, 1 .. 65535 */
+    uint32_t route_cap;     /* cells of a route that are read, >= 1; n_starts * route_cap <= 2^28 */
+    uint32_t flags;         /* 0 */
+} lom_navfield_waypoint_params;
 #define LOM_NAV_UNREACHED 0xFFFFFFFFu
 #define LOM_NAV_MAX 0xFFFFFFFEu
 enum { LOM_NAV_UNKNOWN_PASSABLE = 1 }; /* a -1 cell is passable at unknown_cost */
@@ -1786,9 +1813,11 @@ enum {
     LOM_NAV_OPT_TEST_INNER_CAP = 1, /* sweeps of a tile per launch, 1 .. 2^20; 1: a launch is one sweep per active tile; <= 0: the default */
     LOM_NAV_OPT_TEST_BATCH = 2,     /* launches per wait, 1 .. 256; <= 0: the default */
     LOM_NAV_OPT_TEST_ALL_TILES = 3, /* 1: every tile is active in every launch; 0 or < 0, the default: only marked tiles */
-    LOM_NAV_OPT_TEST_RESOLVE_FORM = 4 /* of a re-solve: 0 or < 0, the default: raise, then relax; 1: the threshold form; 2: the
-                                         full solve from the kept goals.  Test switches: the bytes are the same.  The first
-                                         three act on both phases of a re-solve. */
+    LOM_NAV_OPT_TEST_RESOLVE_FORM = 4, /* of a re-solve: 0 or < 0, the default: raise, then relax; 1: the threshold form; 2: the
+                                          full solve from the kept goals.  Test switches: the bytes are the same.  The first
+                                          three act on both phases of a re-solve. */
+    LOM_NAV_OPT_TEST_SHORTCUT_SERIAL = 5 /* of step 9: 0 or < 0, the default: a wave per route, 64 candidates at a time; 1: a
+                                            lane per route, one candidate after another.  The bytes are the same. */
 };
 int lom_navfield_create(const lom_occupancy_geometry *geometry, int device, lom_navfield **out);
 void lom_navfield_destroy(lom_navfield *f);
@@ -1825,6 +1854,14 @@ int lom_navfield_paths(lom_navfield *f, int start_kind, const void *starts, size
                        uint32_t *lengths_out);
 /* step 7: n points (x, y in the grid's frame, f32 pairs in host memory, at most 2^30) */
 int lom_navfield_query(lom_navfield *f, const float *xy, size_t n, uint32_t *out);
+/* step 8: n int32 quadruples (x0, y0, x1, y1) in host memory, at most 2^24; out: a byte per pair, 1 = visible */
+int lom_navfield_visible(lom_navfield *f, const int32_t *pairs, size_t n, uint32_t max_cell_cost, uint8_t *out);
+/* step 9: starts as for lom_navfield_paths; cells_out: [n_starts, wp_cap] u16 pairs (may be NULL with wp_cap 0; n_starts *
+ * wp_cap at most 2^28), counts_out and lengths_out: n_starts u32 each (either may be NULL).  The routes stay in HBM: one
+ * trace, one shortcut pass, one wait.  A refused call writes nothing. */
+int lom_navfield_waypoints(lom_navfield *f, int start_kind, const void *starts, size_t n_starts,
+                           const lom_navfield_waypoint_params *params, uint16_t *cells_out, size_t wp_cap, uint32_t *counts_out,
+                           uint32_t *lengths_out);
 /* step 1 for these parameters; LOM_ERR_ARG for bad parameters.  Needs no handle and no device. */
 int lom_navfield_cell_costs(const lom_navfield_params *params, uint32_t *out256);
 /* the launches and waits of the last solve (zeros before the first) */

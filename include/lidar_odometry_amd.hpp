@@ -1149,6 +1149,13 @@ inline NavFieldParams navfieldParams(uint32_t neutral, uint32_t factor, uint32_t
     return NavFieldParams{neutral, factor, unknown_cost, max_passable, flags};
 }
 
+using NavFieldWaypointParams = lom_navfield_waypoint_params;  // {max_cell_cost, lookahead, route_cap, flags}
+
+inline NavFieldWaypointParams navfieldWaypointParams(uint32_t max_cell_cost, uint32_t lookahead, uint32_t route_cap, uint32_t flags = 0)
+{
+    return NavFieldWaypointParams{max_cell_cost, lookahead, route_cap, flags};
+}
+
 class NavField
     : public GridHandle<lom_navfield, lom_occupancy_geometry, lom_navfield_create, lom_navfield_destroy, lom_navfield_last_error,
                         lom_navfield_get_geometry, lom_navfield_clear, lom_navfield_set_option, lom_navfield_device, lom_navfield_stream,
@@ -1157,6 +1164,10 @@ public:
     struct Paths {  // cells: [K, cap] (ix, iy) pairs; lengths: the full length per start, 0 where none was walked
         std::vector<uint16_t> cells;
         std::vector<uint32_t> lengths;
+    };
+    struct Waypoints {  // cells: [K, wp_cap] (ix, iy) pairs; counts: the full number per start; lengths: the walk's full length
+        std::vector<uint16_t> cells;
+        std::vector<uint32_t> counts, lengths;
     };
 
     explicit NavField(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
@@ -1223,6 +1234,43 @@ public:
         std::vector<uint32_t> out(n);
         check(lom_navfield_query(h_, xy, n, out.data()));
         return out;
+    }
+    // pairs: n quadruples (x0, y0, x1, y1) of cells; a byte per pair, 1 where the second cell is in line of sight of the first
+    std::vector<uint8_t> visible(const int32_t *pairs, size_t n, uint32_t max_cell_cost = 0)
+    {
+        std::vector<uint8_t> out(n);
+        check(lom_navfield_visible(h_, pairs, n, max_cell_cost, out.data()));
+        return out;
+    }
+    // the walks of paths(), cut to any-angle waypoints by line-of-sight shortcuts; starts as for paths()
+    Waypoints waypoints(int start_kind, const void *starts, size_t n, const lom_navfield_waypoint_params &params, size_t wp_cap)
+    {
+        Waypoints w;
+        w.cells.assign(n * wp_cap * 2, 0), w.counts.assign(n, 0), w.lengths.assign(n, 0);
+        check(lom_navfield_waypoints(h_, start_kind, starts, n, &params, w.cells.data(), wp_cap, w.counts.data(), w.lengths.data()));
+        return w;
+    }
+    // the centres of n cells (ix, iy) in the grid's frame, (x, y) pairs: origin + (i + 0.5) * resolution
+    std::vector<double> waypointsMetres(const uint16_t *cells, size_t n) const
+    {
+        const lom_occupancy_geometry g = geometry();
+        std::vector<double> xy(2 * n);
+        for (size_t i = 0; i < n; i++) {
+            xy[2 * i] = (double)g.origin_x + ((double)cells[2 * i] + 0.5) * (double)g.resolution;
+            xy[2 * i + 1] = (double)g.origin_y + ((double)cells[2 * i + 1] + 0.5) * (double)g.resolution;
+        }
+        return xy;
+    }
+    // the length in metres of the polyline through n cells
+    double polylineLength(const uint16_t *cells, size_t n) const
+    {
+        const double r = (double)geometry().resolution;
+        double total = 0.0;
+        for (size_t i = 1; i < n; i++) {
+            const double dx = (double)cells[2 * i] - (double)cells[2 * i - 2], dy = (double)cells[2 * i + 1] - (double)cells[2 * i - 1];
+            total += std::sqrt(dx * dx + dy * dy);
+        }
+        return total * r;
     }
     lom_navfield_solve_stats stats() const
     {

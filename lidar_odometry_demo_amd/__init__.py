@@ -823,6 +823,12 @@ def navfieldParams(params):
     return _struct_from(capi.NavFieldParams, params, "navigation field parameters")
 
 
+def navfieldWaypointParams(params):
+    """capi.NavFieldWaypointParams from one, from a dict with its four fields, or from a 4-tuple in the struct's order
+    (max_cell_cost, lookahead, route_cap, flags).  There are no defaults."""
+    return _struct_from(capi.NavFieldWaypointParams, params, "navigation field waypoint parameters")
+
+
 def regionsParams(params):
     """capi.RegionsParams from one, from a dict with its seven fields, or from a 7-tuple in the struct's order (kind, lo, hi,
     max_cost, min_cells, rank, flags).  There are no defaults."""
@@ -1462,6 +1468,37 @@ class NavField(_PlaneGrid):
         out = np.empty(len(xy), np.uint32)
         self._check(self._call("query", self._h, xy.ctypes.data, len(xy), out.ctypes.data))
         return out
+
+    def visible(self, pairs, max_cell_cost=0):
+        """uint8 per pair of cells (x0, y0, x1, y1), an (n, 4) integer array: 1 where the second cell is in line of sight of
+        the first over cells of cost at most `max_cell_cost` (0: any passable cell), under the last solve's parameters"""
+        q = np.ascontiguousarray(pairs, np.int32).reshape(-1, 4)
+        out = np.zeros(len(q), np.uint8)
+        self._check(self._call("visible", self._h, q.ctypes.data, len(q), int(max_cell_cost), out.ctypes.data))
+        return out
+
+    def waypoints(self, starts, params, wp_cap, metres=False):
+        """(cells uint16 (K, wp_cap, 2), counts uint32 (K,), lengths uint32 (K,)): the walk from each start down the field,
+        cut to any-angle waypoints by line-of-sight shortcuts.  `params`: navfieldWaypointParams (max_cell_cost, lookahead,
+        route_cap, flags).  A count is the full number of waypoints and may exceed wp_cap; a length is the full length of
+        the walk and may exceed route_cap, of which only the first route_cap cells are cut."""
+        p = navfieldWaypointParams(params)
+        kind, s = self._points(starts, metres)
+        cells = np.zeros((len(s), int(wp_cap), 2), np.uint16)
+        counts, lengths = np.zeros(len(s), np.uint32), np.zeros(len(s), np.uint32)
+        self._check(self._call("waypoints", self._h, kind, s.ctypes.data, len(s), C.byref(p), cells.ctypes.data, int(wp_cap),
+                               counts.ctypes.data, lengths.ctypes.data))
+        return cells, counts, lengths
+
+    def waypointsMetres(self, cells):
+        """float64 (..., 2): the centres of cells (ix, iy) in the grid's frame, origin + (i + 0.5) * resolution"""
+        g = self.geometry()
+        return np.array([g["origin_x"], g["origin_y"]]) + (np.asarray(cells, np.float64) + 0.5) * g["resolution"]
+
+    def polylineLength(self, cells, count=None):
+        """the length in metres of the polyline through the first `count` (default: all) cells of an (n, 2) array"""
+        xy = self.waypointsMetres(np.asarray(cells).reshape(-1, 2)[:count])
+        return float(np.sqrt((np.diff(xy, axis=0) ** 2).sum(axis=1)).sum())
 
     def stats(self):
         """capi.NavFieldSolveStats of the last solve as a dict: launches, waits, tiles"""

@@ -377,12 +377,18 @@ class NavFieldResolveCounters(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class NavFieldWaypointParams(C.Structure):
+    """lom_navfield_waypoint_params"""
+    _fields_ = [("max_cell_cost", C.c_uint32), ("lookahead", C.c_uint32), ("route_cap", C.c_uint32), ("flags", C.c_uint32)]
+
+
 assert C.sizeof(NavFieldParams) == 20 and C.sizeof(NavFieldSummary) == 64 and C.sizeof(NavFieldSolveStats) == 24
-assert C.sizeof(NavFieldResolveCounters) == 48
+assert C.sizeof(NavFieldResolveCounters) == 48 and C.sizeof(NavFieldWaypointParams) == 16
 NAV_UNREACHED, NAV_MAX = 0xFFFFFFFF, 0xFFFFFFFE
 NAV_UNKNOWN_PASSABLE = 1
 NAV_CELLS, NAV_METRES = 0, 1
 NAV_OPT_TEST_INNER_CAP, NAV_OPT_TEST_BATCH, NAV_OPT_TEST_ALL_TILES, NAV_OPT_TEST_RESOLVE_FORM = 1, 2, 3, 4
+NAV_OPT_TEST_SHORTCUT_SERIAL = 5
 
 
 class RegionsParams(C.Structure):
@@ -801,6 +807,8 @@ PROTOTYPES = {
     "lom_navfield_potential_device": (_int, [_vp, _P(_vp)]),
     "lom_navfield_paths": (_int, [_vp, _int, _vp, _size, _vp, _size, _vp]),
     "lom_navfield_query": (_int, [_vp, _vp, _size, _vp]),
+    "lom_navfield_visible": (_int, [_vp, _vp, _size, _u32, _vp]),
+    "lom_navfield_waypoints": (_int, [_vp, _int, _vp, _size, _P(NavFieldWaypointParams), _vp, _size, _vp, _vp]),
     "lom_navfield_cell_costs": (_int, [_P(NavFieldParams), _vp]),
     "lom_navfield_stats": (_int, [_vp, _P(NavFieldSolveStats)]),
     # ---- frontier regions

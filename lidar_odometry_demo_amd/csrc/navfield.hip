@@ -1,8 +1,9 @@
 // Navigation field: the least total cost to reach a goal, per cell, over an int8 cost plane; paths down it and point
 // queries.  Definitions: include/lidar_odometry_amd.h ("navigation field"); kernels: k_navfield.hpp; host planning (value
 // ranges, the cell-cost table, goal quantisation, tile counts, launch shapes): navfield_host.cpp; DESIGN.md 7m.  The
-// re-solve after a local cost change (k_navfield_resolve.hpp) keeps what a solve left and repairs it.  A
-// handle family of its own on the PlaneHandle core (plane_handle.hpp); no default path launches any of this.
+// re-solve after a local cost change (k_navfield_resolve.hpp) keeps what a solve left and repairs it; the
+// line of sight and the waypoints (k_navfield_waypoints.hpp) read what it left.  A handle family of its own
+// on the PlaneHandle core (plane_handle.hpp); no default path launches any of this.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -11,6 +12,7 @@
 #include "clearance_host.hpp"
 #include "k_navfield.hpp"
 #include "k_navfield_resolve.hpp"
+#include "k_navfield_waypoints.hpp"
 #include "navfield_host.hpp"
 #include "plane_handle.hpp"
 
@@ -18,6 +20,7 @@ using namespace lom;
 
 static_assert(navfield::kThreads == kNavThreads && navfield::kTile == kNavTile && navfield::kMaxCellCost == kNavMaxCellCost,
               "navfield_host.hpp and k_navfield.hpp disagree");
+static_assert(navfield::kRoutesPerGroup == kNavRoutesPerGroup, "navfield_host.hpp and k_navfield_waypoints.hpp disagree");
 static_assert(LOM_NAV_UNREACHED == kNavUnreached && LOM_NAV_MAX == kNavMax, "the header and k_navfield.hpp disagree");
 
 // The field owns its stream and every buffer below.
@@ -33,12 +36,14 @@ struct lom_navfield : lom::PlaneHandle {  // in_ev: the clearance grid's
     lom::DeviceBuf points;           // goals or starts as int32 pairs, grow-only
     lom::DeviceBuf path_cells, path_lengths;  // a paths call's results, grow-only
     lom::DeviceBuf q_xy, q_out;      // a query's points and results, grow-only
+    lom::DeviceBuf wp_cells, wp_counts;  // a waypoints call's results, grow-only; its routes are in path_cells
     lom::PinnedBuf h_table;          // the table on its way in
     lom::PinnedBuf h_flags;          // the batch's flags and the summary words on their way out
     uint32_t inner_cap = navfield::kInnerCapDefault;  // LOM_NAV_OPT_TEST_INNER_CAP
     uint32_t batch = navfield::kBatchDefault;         // LOM_NAV_OPT_TEST_BATCH
     uint32_t all_tiles = 0;                           // LOM_NAV_OPT_TEST_ALL_TILES
     uint32_t resolve_form = 0;                        // LOM_NAV_OPT_TEST_RESOLVE_FORM
+    uint32_t shortcut_serial = 0;                     // LOM_NAV_OPT_TEST_SHORTCUT_SERIAL
     lom_navfield_solve_stats stats{};
     lom_navfield_resolve_counters resolve_stats{};
     bool solved = false;             // a solve has completed since create or clear: plane, table and P are a fixed point
@@ -330,6 +335,10 @@ int lom_navfield_set_option(lom_navfield *f, int option, int64_t value)
         if (value > 2) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_RESOLVE_FORM: 0, 1, 2, or < 0 for the default");
         f->resolve_form = value <= 0 ? 0u : (uint32_t)value;
         return LOM_OK;
+    case LOM_NAV_OPT_TEST_SHORTCUT_SERIAL:
+        if (value > 1) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_SHORTCUT_SERIAL: 0, 1, or < 0 for the default");
+        f->shortcut_serial = value == 1 ? 1u : 0u;
+        return LOM_OK;
     default:
         return fail(f, LOM_ERR_ARG, "unknown navigation field option");
     }
@@ -482,6 +491,72 @@ int lom_navfield_query(lom_navfield *f, const float *xy, size_t n, uint32_t *out
                        f->geo.resolution, f->geo.origin_x, f->geo.origin_y, f->args(), f->field.as<const uint32_t>(), f->q_out.as<uint32_t>());
     LOM_HIP(f, hipGetLastError());
     LOM_HIP(f, hipMemcpyAsync(out, f->q_out.p, n * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    return LOM_OK;
+}
+
+int lom_navfield_visible(lom_navfield *f, const int32_t *pairs, size_t n, uint32_t max_cell_cost, uint8_t *out)
+{
+    if (!f) return LOM_ERR_ARG;
+    if ((n && (!pairs || !out)) || n > navfield::kMaxVisiblePairs)
+        return fail(f, LOM_ERR_ARG, "navigation field visible: pairs and a byte for each, at most 2^24 of them");
+    if (!n) return LOM_OK;
+    LOM_HIP(f, hipSetDevice(f->device));
+    int rc;
+    if ((rc = ensure(f, f->q_xy, n * 16)) != LOM_OK || (rc = ensure(f, f->q_out, n)) != LOM_OK) return rc;
+    LOM_HIP(f, hipMemcpyAsync(f->q_xy.p, pairs, n * 16, hipMemcpyHostToDevice, f->stream));
+    hipLaunchKernelGGL(k_nav_visible, dim3(navfield::blocks_for(n)), dim3(kNavThreads), 0, f->stream, f->plane.as<const int8_t>(),
+                       f->table.as<const uint32_t>(), f->args(), f->q_xy.as<const int32_t>(), (uint32_t)n, max_cell_cost, f->q_out.as<uint8_t>());
+    LOM_HIP(f, hipGetLastError());
+    LOM_HIP(f, hipMemcpyAsync(out, f->q_out.p, n, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    return LOM_OK;
+}
+
+// (Aligned to a cache line, which makes the library's .text start on one: what is linked in front of navfield.o then keeps
+// its place within cache lines when the tables in front of .text grow by an export; profiles/navfield_waypoints_ab.txt.)
+__attribute__((aligned(64))) int lom_navfield_waypoints(lom_navfield *f, int start_kind, const void *starts, size_t n_starts,
+                                                        const lom_navfield_waypoint_params *params, uint16_t *cells_out, size_t wp_cap,
+                                                        uint32_t *counts_out, uint32_t *lengths_out)
+{
+    if (!f) return LOM_ERR_ARG;
+    if (start_kind != LOM_NAV_CELLS && start_kind != LOM_NAV_METRES) return fail(f, LOM_ERR_ARG, "navigation field: starts are LOM_NAV_CELLS or LOM_NAV_METRES");
+    if ((n_starts && !starts) || n_starts > navfield::kMaxPoints) return fail(f, LOM_ERR_ARG, "navigation field waypoints: starts, at most 2^24 of them");
+    if (!navfield::waypoint_params_ok(params, n_starts))
+        return fail(f, LOM_ERR_ARG, "navigation field waypoints: lookahead in 1 .. 65535, route_cap >= 1, n_starts * route_cap <= 2^28, flags 0");
+    if (!navfield::waypoint_output_ok(n_starts, wp_cap, cells_out))
+        return fail(f, LOM_ERR_ARG, "navigation field waypoints: an output of n_starts * wp_cap cells, at most 2^28");
+    if (!n_starts) return LOM_OK;
+    LOM_HIP(f, hipSetDevice(f->device));
+    const uint32_t K = (uint32_t)n_starts, route_cap = params->route_cap;
+    const size_t out_bytes = n_starts * wp_cap * 4;
+    int rc;
+    if ((rc = ensure(f, f->path_cells, std::max(n_starts * route_cap * 4, (size_t)256))) != LOM_OK ||
+        (rc = ensure(f, f->path_lengths, n_starts * 4)) != LOM_OK || (rc = ensure(f, f->wp_cells, std::max(out_bytes, (size_t)256))) != LOM_OK ||
+        (rc = ensure(f, f->wp_counts, n_starts * 4)) != LOM_OK)
+        return rc;
+    std::vector<int32_t> start_cells;
+    if ((rc = upload_points(f, start_kind, starts, n_starts, start_cells)) != LOM_OK) return rc;
+    if (out_bytes) LOM_HIP(f, hipMemsetAsync(f->wp_cells.p, 0, out_bytes, f->stream));
+    // the routes stay in the handle's path buffer: only the first min(length, route_cap) cells of a row are read
+    hipLaunchKernelGGL(k_nav_trace, dim3(navfield::blocks_for(n_starts)), dim3(kNavThreads), 0, f->stream, f->plane.as<const int8_t>(),
+                       f->table.as<const uint32_t>(), f->field.as<const uint32_t>(), f->args(), f->points.as<const int32_t>(), K, route_cap,
+                       f->path_cells.as<uint16_t>(), f->path_lengths.as<uint32_t>());
+    LOM_HIP(f, hipGetLastError());
+    if (f->shortcut_serial)
+        hipLaunchKernelGGL(k_nav_shortcut_serial, dim3(navfield::blocks_for(n_starts)), dim3(kNavThreads), 0, f->stream,
+                           f->plane.as<const int8_t>(), f->table.as<const uint32_t>(), f->args(), f->path_cells.as<const uint16_t>(),
+                           f->path_lengths.as<const uint32_t>(), K, route_cap, params->lookahead, params->max_cell_cost,
+                           f->wp_cells.as<uint16_t>(), (uint32_t)wp_cap, f->wp_counts.as<uint32_t>());
+    else
+        hipLaunchKernelGGL(k_nav_shortcut, dim3(navfield::shortcut_blocks_for(n_starts)), dim3(kNavThreads), 0, f->stream,
+                           f->plane.as<const int8_t>(), f->table.as<const uint32_t>(), f->args(), f->path_cells.as<const uint32_t>(),
+                           f->path_lengths.as<const uint32_t>(), K, route_cap, params->lookahead, params->max_cell_cost,
+                           f->wp_cells.as<uint32_t>(), (uint32_t)wp_cap, f->wp_counts.as<uint32_t>());
+    LOM_HIP(f, hipGetLastError());
+    if (out_bytes) LOM_HIP(f, hipMemcpyAsync(cells_out, f->wp_cells.p, out_bytes, hipMemcpyDeviceToHost, f->stream));
+    if (counts_out) LOM_HIP(f, hipMemcpyAsync(counts_out, f->wp_counts.p, n_starts * 4, hipMemcpyDeviceToHost, f->stream));
+    if (lengths_out) LOM_HIP(f, hipMemcpyAsync(lengths_out, f->path_lengths.p, n_starts * 4, hipMemcpyDeviceToHost, f->stream));
     LOM_HIP(f, hipStreamSynchronize(f->stream));
     return LOM_OK;
 }

@@ -70,6 +70,20 @@ TileRange tile_range(const clearance::Rect &window)
 
 uint32_t blocks_for(size_t n) { return n ? (uint32_t)((n + kThreads - 1u) / kThreads) : 1u; }
 
+bool waypoint_params_ok(const lom_navfield_waypoint_params *p, size_t n_starts)
+{
+    if (!p || p->flags != 0u || p->lookahead < 1u || p->lookahead > kMaxLookahead || p->route_cap < 1u) return false;
+    return (size_t)p->route_cap <= kMaxPathCells && n_starts <= kMaxPathCells / p->route_cap;
+}
+
+bool waypoint_output_ok(size_t n_starts, size_t wp_cap, const void *cells_out)
+{
+    if (wp_cap > kMaxPathCells || (wp_cap && n_starts > kMaxPathCells / wp_cap)) return false;
+    return !(n_starts && wp_cap && !cells_out);
+}
+
+uint32_t shortcut_blocks_for(size_t n_routes) { return n_routes ? (uint32_t)((n_routes + kRoutesPerGroup - 1u) / kRoutesPerGroup) : 1u; }
+
 uint64_t launch_bound(uint32_t width, uint32_t height) { return 2ull * width * height + 64ull; }
 
 }  // namespace navfield

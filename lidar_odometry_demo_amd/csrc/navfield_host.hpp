@@ -53,6 +53,16 @@ struct TileRange {
 TileRange tile_range(const clearance::Rect &window);
 // workgroups of kThreads lanes for n lanes (at least one)
 uint32_t blocks_for(size_t n);
+// Steps 8 and 9.  The parameters of lom_navfield_waypoints for n_starts starts: lookahead in 1 .. 65535, route_cap >= 1,
+// n_starts * route_cap <= 2^28, flags 0.
+constexpr uint32_t kMaxLookahead = 65535;
+constexpr size_t kMaxVisiblePairs = (size_t)1 << 24;  // of a lom_navfield_visible call
+constexpr uint32_t kRoutesPerGroup = 4;                // k_nav_shortcut: a wave per route
+bool waypoint_params_ok(const lom_navfield_waypoint_params *p, size_t n_starts);
+// ... and its output: n_starts * wp_cap <= 2^28 cells, which need a buffer where there are any
+bool waypoint_output_ok(size_t n_starts, size_t wp_cap, const void *cells_out);
+// workgroups of k_nav_shortcut for n routes (at least one)
+uint32_t shortcut_blocks_for(size_t n_routes);
 // More launches than any solve needs: a cell whose best route has d steps is final one launch after the next cell of
 // that route is, so d + 1 launches settle it, and d is below the number of cells.  2 * cells + 64.
 uint64_t launch_bound(uint32_t width, uint32_t height);
