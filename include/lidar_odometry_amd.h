@@ -2287,6 +2287,62 @@ int lom_rollout_state_from_pose(const lom_occupancy_geometry *geometry, float x_
 /* step 1 alone: the S + 1 poses of one candidate (commands: segments pairs) go to `out` */
 int lom_rollout_poses(const lom_rollout_params *params, const lom_rollout_state *state, const int16_t *commands, lom_rollout_state *out);
 
+/* ---- grid shift: a grid follows the robot by whole cells (not in the reference) -----------------------------------------
+ * Every grid family above fixes its geometry at create.  A shift moves the window by (dx, dy) whole cells: the content stays
+ * where it is in the world, what still overlaps is kept, what enters is cleared, and the seven families follow by ONE rule,
+ * so that handles of equal geometry shifted by the same (dx, dy) still agree bit for bit (what a consumer asks of its
+ * producers).  A new capability: no default path launches any of it.  DESIGN.md 7r.
+ *
+ * The rule.  out = in moved by (dx, dy) cells: width, height and resolution unchanged,
+ *   origin_x' = (float)((double)origin_x + (double)dx * (double)resolution), y likewise,
+ * from the CURRENT f32 origin alone.  The rounding to f32 is part of the definition: the result is exact for a dyadic
+ * resolution and a modest origin; with a resolution such as 0.1f the origin moves by under one ulp of itself per shift, so
+ * shifting out and back need not return the first origin's bits.  The geometry rule is the occupancy grid's (sides up to
+ * 16384), the widest of the families'.
+ * LOM_ERR_ARG: `in` fails the geometry rule or a pointer is NULL.  LOM_ERR_RANGE: an origin' that is not finite (out
+ * untouched).  in and out may be the same object.  Host code: no handle, no device. */
+int lom_grid_shift_geometry(const lom_occupancy_geometry *in, int32_t dx, int32_t dy, lom_occupancy_geometry *out);
+/* The shift that brings a robot at (x, y) metres back towards the middle.  Per axis, side n, shift d:
+ *   q = floor(((double)x - (double)origin) / (double)resolution)            (the grids' own index rule)
+ *   d = 0                                        if margin <= q < n - margin
+ *   d = trunc((q - n / 2) / quantum) * quantum   otherwise                  (n / 2: integer division; trunc: towards zero)
+ * margin + quantum <= n / 2 guarantees that after the shift the robot's cell lies in [margin, n - margin); d is a multiple
+ * of the quantum.  The caller takes the pose from lom_odometry_get_pose, asks this, and shifts its handles.
+ * LOM_ERR_ARG: a bad geometry or a NULL, x or y not finite, quantum == 0, or margin + quantum > n / 2 on either axis.
+ * LOM_ERR_RANGE: |q| > 2^40 or |d| > INT32_MAX.  On an error *dx = *dy = 0.  Host code: no handle, no device. */
+int lom_grid_follow(const lom_occupancy_geometry *g, double x, double y, uint32_t margin_cells, uint32_t quantum_cells, int32_t *dx,
+                    int32_t *dy);
+/* The two grids that hold state.  The geometry becomes lom_grid_shift_geometry(geometry, dx, dy) (an elevation grid's z_ref
+ * stays); cell (ix, iy) afterwards holds what cell (ix + dx, iy + dy) held before where that cell is in the grid, and
+ * elsewhere its cleared value: both counts 0; the record of lom_elevation_clear (sum 0, count 0, zmin INT32_MAX, zmax
+ * INT32_MIN).  dx == dy == 0 is LOM_OK with no launch; |dx| >= width or |dy| >= height equals a clear plus the new geometry.
+ * One launch moves everything, each destination cell written once, into a second block that is allocated at the first such
+ * call and swapped with the first behind the launch: a grid that shifts holds its state twice.  LOM_ERR_RANGE from the rule
+ * and LOM_ERR_OOM from that allocation leave the grid and its geometry untouched.  The call runs on the grid's stream,
+ * behind whatever consumers released to it (lom_*_wait_event), and returns with its work done.  A pointer from
+ * lom_occupancy_classify_device / lom_elevation_cost_device is invalid afterwards, as after any call on the handle; later
+ * integrate, classify, cost, layers, cells and counts use the new geometry with no further step.  (The seven shifts are
+ * declared through function types, like lom_archive_add_points: each family's own section lists what came with the family.) */
+typedef int(lom_occupancy_shift_fn)(lom_occupancy *g, int32_t dx, int32_t dy);
+typedef int(lom_elevation_shift_fn)(lom_elevation *g, int32_t dx, int32_t dy);
+lom_occupancy_shift_fn lom_occupancy_shift;
+lom_elevation_shift_fn lom_elevation_shift;
+/* The five planning families follow: the geometry moves by the same rule and the handle's state afterwards is exactly what
+ * its own lom_*_clear leaves (also for dx == dy == 0), so the next update / solve / extract / cast / evaluate is a full one:
+ * these handles are recomputed from their producers anyway.  Carrying the clearance distances or the field across a shift
+ * is not part of this.  LOM_ERR_RANGE from the rule leaves the handle untouched.  A consumer that was not shifted meets a
+ * shifted producer with the usual refusal, "... resolution, origin, width or height differs". */
+typedef int(lom_clearance_shift_fn)(lom_clearance *c, int32_t dx, int32_t dy);
+typedef int(lom_navfield_shift_fn)(lom_navfield *f, int32_t dx, int32_t dy);
+typedef int(lom_regions_shift_fn)(lom_regions *r, int32_t dx, int32_t dy);
+typedef int(lom_visibility_shift_fn)(lom_visibility *v, int32_t dx, int32_t dy);
+typedef int(lom_rollout_shift_fn)(lom_rollout *r, int32_t dx, int32_t dy);
+lom_clearance_shift_fn lom_clearance_shift;
+lom_navfield_shift_fn lom_navfield_shift;
+lom_regions_shift_fn lom_regions_shift;
+lom_visibility_shift_fn lom_visibility_shift;
+lom_rollout_shift_fn lom_rollout_shift;
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;

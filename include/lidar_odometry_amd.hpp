@@ -633,10 +633,10 @@ protected:
     H *h_ = nullptr;
 };
 
-// ... and of the seven grids, by the nine entry points every grid family has: construction from a geometry G and a
-// device, geometry(), the cell count, clear(), setOption(), device(), stream() (a hipStream_t) and waitEvent() (the
-// grid's stream waits for a hipEvent_t before what is enqueued next)
-template <typename H, typename G, auto Create, auto Destroy, auto LastError, auto GetGeometry, auto Clear, auto SetOption, auto Device,
+// ... and of the seven grids, by the ten entry points every grid family has: construction from a geometry G and a
+// device, geometry(), the cell count, clear(), shift(), setOption(), device(), stream() (a hipStream_t) and waitEvent()
+// (the grid's stream waits for a hipEvent_t before what is enqueued next)
+template <typename H, typename G, auto Create, auto Destroy, auto LastError, auto GetGeometry, auto Clear, auto Shift, auto SetOption, auto Device,
           auto Stream, auto WaitEvent>
 class GridHandle : public Handle<H, Destroy, LastError> {
 public:
@@ -647,6 +647,9 @@ public:
         return g;
     }
     void clear() { this->check(Clear(this->h_)); }
+    // the window moves by (dx, dy) whole cells ("grid shift"): an occupancy or elevation grid keeps what still overlaps and
+    // clears what enters; a planning grid is left as its clear() leaves it
+    void shift(int32_t dx, int32_t dy) { this->check(Shift(this->h_, dx, dy)); }
     void setOption(int option, int64_t value) { this->check(SetOption(this->h_, option, value)); }
     int device() const { return Device(this->h_); }
     void *stream() const { return Stream(this->h_); }
@@ -950,7 +953,7 @@ using OccupancySummary = lom_occupancy_summary;
 
 class OccupancyGrid
     : public GridHandle<lom_occupancy, lom_occupancy_geometry, lom_occupancy_create, lom_occupancy_destroy, lom_occupancy_last_error,
-                        lom_occupancy_get_geometry, lom_occupancy_clear, lom_occupancy_set_option, lom_occupancy_device,
+                        lom_occupancy_get_geometry, lom_occupancy_clear, lom_occupancy_shift, lom_occupancy_set_option, lom_occupancy_device,
                         lom_occupancy_stream, lom_occupancy_wait_event> {
 public:
     explicit OccupancyGrid(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
@@ -1003,7 +1006,7 @@ using ElevationSummary = lom_elevation_summary;
 
 class ElevationGrid
     : public GridHandle<lom_elevation, lom_elevation_geometry, lom_elevation_create, lom_elevation_destroy, lom_elevation_last_error,
-                        lom_elevation_get_geometry, lom_elevation_clear, lom_elevation_set_option, lom_elevation_device,
+                        lom_elevation_get_geometry, lom_elevation_clear, lom_elevation_shift, lom_elevation_set_option, lom_elevation_device,
                         lom_elevation_stream, lom_elevation_wait_event> {
 public:
     struct Cells {  // the accumulators, in quanta of 2^-8 m relative to z_ref
@@ -1078,7 +1081,7 @@ inline ClearanceParams clearanceParams(float inflation_radius, float inscribed_r
 
 class ClearanceGrid
     : public GridHandle<lom_clearance, lom_occupancy_geometry, lom_clearance_create, lom_clearance_destroy, lom_clearance_last_error,
-                        lom_clearance_get_geometry, lom_clearance_clear, lom_clearance_set_option, lom_clearance_device,
+                        lom_clearance_get_geometry, lom_clearance_clear, lom_clearance_shift, lom_clearance_set_option, lom_clearance_device,
                         lom_clearance_stream, lom_clearance_wait_event> {
 public:
     struct Query {  // NaN and -1 for a point outside the grid
@@ -1158,7 +1161,7 @@ inline NavFieldWaypointParams navfieldWaypointParams(uint32_t max_cell_cost, uin
 
 class NavField
     : public GridHandle<lom_navfield, lom_occupancy_geometry, lom_navfield_create, lom_navfield_destroy, lom_navfield_last_error,
-                        lom_navfield_get_geometry, lom_navfield_clear, lom_navfield_set_option, lom_navfield_device, lom_navfield_stream,
+                        lom_navfield_get_geometry, lom_navfield_clear, lom_navfield_shift, lom_navfield_set_option, lom_navfield_device, lom_navfield_stream,
                         lom_navfield_wait_event> {
 public:
     struct Paths {  // cells: [K, cap] (ix, iy) pairs; lengths: the full length per start, 0 where none was walked
@@ -1304,7 +1307,7 @@ inline RegionsParams regionsParams(int32_t kind, int8_t lo, int8_t hi, int8_t ma
 
 class RegionGrid
     : public GridHandle<lom_regions, lom_occupancy_geometry, lom_regions_create, lom_regions_destroy, lom_regions_last_error,
-                        lom_regions_get_geometry, lom_regions_clear, lom_regions_set_option, lom_regions_device, lom_regions_stream,
+                        lom_regions_get_geometry, lom_regions_clear, lom_regions_shift, lom_regions_set_option, lom_regions_device, lom_regions_stream,
                         lom_regions_wait_event> {
 public:
     explicit RegionGrid(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
@@ -1391,7 +1394,7 @@ inline std::vector<int32_t> visibilityTable(uint32_t beams)
 
 class VisibilityGrid
     : public GridHandle<lom_visibility, lom_occupancy_geometry, lom_visibility_create, lom_visibility_destroy, lom_visibility_last_error,
-                        lom_visibility_get_geometry, lom_visibility_clear, lom_visibility_set_option, lom_visibility_device,
+                        lom_visibility_get_geometry, lom_visibility_clear, lom_visibility_shift, lom_visibility_set_option, lom_visibility_device,
                         lom_visibility_stream, lom_visibility_wait_event> {
 public:
     explicit VisibilityGrid(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
@@ -1532,7 +1535,7 @@ inline std::vector<RolloutState> rolloutPoses(const RolloutParams &params, const
 
 class RolloutGrid
     : public GridHandle<lom_rollout, lom_occupancy_geometry, lom_rollout_create, lom_rollout_destroy, lom_rollout_last_error,
-                        lom_rollout_get_geometry, lom_rollout_clear, lom_rollout_set_option, lom_rollout_device, lom_rollout_stream,
+                        lom_rollout_get_geometry, lom_rollout_clear, lom_rollout_shift, lom_rollout_set_option, lom_rollout_device, lom_rollout_stream,
                         lom_rollout_wait_event> {
 public:
     struct Result {
@@ -1583,6 +1586,30 @@ public:
         return s;
     }
 };
+
+// ---- grid shift (not in the reference): the rule by which every grid's shift(dx, dy) moves its geometry -----
+// origin' = (float)((double)origin + (double)d * (double)resolution); needs no device
+inline lom_occupancy_geometry gridShiftGeometry(const lom_occupancy_geometry &geometry, int32_t dx, int32_t dy)
+{
+    lom_occupancy_geometry out;
+    const int rc = lom_grid_shift_geometry(&geometry, dx, dy, &out);
+    if (rc != LOM_OK) throw Error(rc, "grid shift: a valid geometry and an origin that stays finite");
+    return out;
+}
+
+struct GridShiftCells {
+    int32_t dx, dy;
+};
+// the shift, in multiples of quantum_cells, that brings a robot at (x, y) metres back towards the middle once its cell
+// leaves [margin_cells, n - margin_cells) on an axis; {0, 0} while it is inside; needs no device
+inline GridShiftCells gridFollow(const lom_occupancy_geometry &geometry, double x, double y, uint32_t margin_cells, uint32_t quantum_cells)
+{
+    GridShiftCells s{0, 0};
+    const int rc = lom_grid_follow(&geometry, x, y, margin_cells, quantum_cells, &s.dx, &s.dy);
+    if (rc != LOM_OK)
+        throw Error(rc, "grid follow: a valid geometry, a finite position, quantum >= 1, margin + quantum <= side / 2, a position within 2^40 cells");
+    return s;
+}
 
 // ---- LidarOdometry (src/lidar_odometry.h:20-85) --------------------------------------
 // For callers that do not keep the reference's own orchestration: processCloud, getCurrentPose and the

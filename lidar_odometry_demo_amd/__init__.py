@@ -1169,6 +1169,43 @@ class _Grid(_Handle):
     def clear(self):
         self._check(self._call("clear", self._h))
 
+    def shift(self, dx, dy):
+        """lom_<family>_shift: the window moves by (dx, dy) whole cells by the rule of grid_shift_geometry.  An occupancy or
+        elevation grid keeps what still overlaps and clears what enters; a planning grid is left as its clear() leaves it."""
+        self._check(self._call("shift", self._h, int(dx), int(dy)))
+
+
+def _occupancy_geometry(geometry):
+    """capi.OccupancyGeometry of one, of a grid's geometry() dict (an elevation grid's too), or of the 5-tuple (resolution,
+    origin_x, origin_y, width, height)"""
+    if isinstance(geometry, capi.OccupancyGeometry):
+        return geometry
+    if isinstance(geometry, dict):
+        geometry = [geometry[k] for k in ("resolution", "origin_x", "origin_y", "width", "height")]
+    return capi.OccupancyGeometry(*geometry)
+
+
+def grid_shift_geometry(geometry, dx, dy):
+    """lom_grid_shift_geometry: the geometry moved by (dx, dy) whole cells, as a capi.OccupancyGeometry; origin' =
+    f32(f64(origin) + dx * f64(resolution)).  Needs no device."""
+    out = capi.OccupancyGeometry()
+    rc = capi.lib().lom_grid_shift_geometry(C.byref(_occupancy_geometry(geometry)), int(dx), int(dy), C.byref(out))
+    if rc != 0:
+        raise LomError(rc, "grid shift: a valid geometry and an origin that stays finite")
+    return out
+
+
+def grid_follow(geometry, x, y, margin_cells, quantum_cells):
+    """lom_grid_follow: the shift (dx, dy), in multiples of quantum_cells, that brings a robot at (x, y) metres back towards
+    the middle once its cell leaves [margin_cells, n - margin_cells) on an axis; (0, 0) while it is inside.  Needs no device."""
+    dx, dy = C.c_int32(), C.c_int32()
+    rc = capi.lib().lom_grid_follow(C.byref(_occupancy_geometry(geometry)), float(x), float(y), int(margin_cells), int(quantum_cells),
+                                    C.byref(dx), C.byref(dy))
+    if rc != 0:
+        raise LomError(rc, "grid follow: a valid geometry, a finite position, quantum >= 1, margin + quantum <= side / 2, "
+                           "a position within 2^40 cells")
+    return int(dx.value), int(dy.value)
+
 
 class _PosedScanGrid(_Grid):
     """What OccupancyGrid and ElevationGrid share (csrc/grid_handle.hpp): a dense 2-D grid that integrates posed scans.  A

@@ -547,8 +547,9 @@ def _family(stem, create_args):
 
 
 def _grid_family(stem, geometry):
-    """the nine entry points every grid family has"""
+    """the ten entry points every grid family has"""
     return {**_family(stem, [_P(geometry), _int]), f"lom_{stem}_clear": (_int, [_vp]),
+            f"lom_{stem}_shift": (_int, [_vp, C.c_int32, C.c_int32]),
             f"lom_{stem}_get_geometry": (_int, [_vp, _P(geometry)]), f"lom_{stem}_stream": (_vp, [_vp]),
             f"lom_{stem}_device": (_int, [_vp]), f"lom_{stem}_wait_event": (_int, [_vp, _vp]),
             f"lom_{stem}_set_option": (_int, [_vp, _int, _i64])}
@@ -845,6 +846,9 @@ PROTOTYPES = {
     "lom_rollout_footprint_rectangle": (_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _int, _vp, _size, _P(_size)]),
     "lom_rollout_state_from_pose": (_int, [_P(OccupancyGeometry), _float, _float, _float, _vp]),
     "lom_rollout_poses": (_int, [_P(RolloutParams), _vp, _vp, _vp]),
+    # ---- grid shift (the families' own lom_<stem>_shift: _grid_family)
+    "lom_grid_shift_geometry": (_int, [_P(OccupancyGeometry), C.c_int32, C.c_int32, _P(OccupancyGeometry)]),
+    "lom_grid_follow": (_int, [_P(OccupancyGeometry), _double, _double, _u32, _u32, _P(C.c_int32), _P(C.c_int32)]),
     # ---- the odometry
     "lom_odometry_default_params": (None, [_P(OdometryParams)]),
     **_family("odometry", [_P(OdometryParams), _int]),
@@ -877,8 +881,10 @@ PROTOTYPES = {
 EXPORTED_BY_TYPE = ["lom_graph_pose_rotation_matrix"]
 # ... and the two of the same section that came with the occupancy grid, declared the same way
 EXPORTED_BY_TYPE_POINTS = ["lom_archive_add_points", "lom_archive_add_points_device"]
+# ... and the seven shifts of the "grid shift" section, one per grid family, declared the same way
+EXPORTED_BY_TYPE_SHIFT = [f"lom_{stem}_shift" for stem in ("occupancy", "elevation", "clearance", "navfield", "regions", "visibility", "rollout")]
 # every symbol include/lidar_odometry_amd.h declares with its parameters
-EXPORTED = [name for name in PROTOTYPES if name not in EXPORTED_BY_TYPE + EXPORTED_BY_TYPE_POINTS]
+EXPORTED = [name for name in PROTOTYPES if name not in EXPORTED_BY_TYPE + EXPORTED_BY_TYPE_POINTS + EXPORTED_BY_TYPE_SHIFT]
 
 # lom_option / counters of include/lidar_odometry_amd.h
 OPT_HOST_LM, OPT_DEVICE_PATIENCE_TICKS, OPT_DEBUG_LM_STAMPS, OPT_DEBUG_TIMING, OPT_NO_TEMPORAL_BOUND, OPT_COUNT_CANDIDATES = 1, 2, 3, 4, 5, 6

@@ -150,6 +150,7 @@ int lom_clearance_clear(lom_clearance *c)
     return LOM_OK;
 }
 
+int lom_clearance_shift(lom_clearance *c, int32_t dx, int32_t dy) { return plane_shift(c, "clearance", dx, dy, &lom_clearance_clear); }
 int lom_clearance_get_geometry(const lom_clearance *c, lom_occupancy_geometry *out) { return plane_get_geometry(c, out); }
 void *lom_clearance_stream(lom_clearance *c) { return plane_stream(c); }
 int lom_clearance_device(const lom_clearance *c) { return plane_device(c); }

@@ -13,6 +13,7 @@
 
 #include "elevation_host.hpp"
 #include "grid_handle.hpp"
+#include "grid_shift.hpp"
 #include "k_elevation.hpp"
 
 using namespace lom;
@@ -21,6 +22,7 @@ using namespace lom;
 struct lom_elevation : lom::GridHandle {
     lom_elevation_geometry geo{};
     lom::DeviceBuf cells;        // width * height records of 32 bytes
+    lom::DeviceBuf cells_shadow; // where a shift moves them to, from the first shift on (grid_handle.hpp)
     lom::DeviceBuf cost;         // int8 per cell
     lom::DeviceBuf layers;       // six f32 planes, from the first lom_elevation_layers on
     lom::DeviceBuf unpacked;     // a chunk of the records as four arrays, on its way out (lom_elevation_cells)
@@ -146,6 +148,27 @@ int lom_elevation_clear(lom_elevation *g)
     LOM_HIP(g, hipSetDevice(g->device));
     if (const int rc = clear_cells(g); rc != LOM_OK) return rc;
     LOM_HIP(g, hipStreamSynchronize(g->stream));
+    return LOM_OK;
+}
+
+int lom_elevation_shift(lom_elevation *g, int32_t dx, int32_t dy)
+{
+    if (!g) return LOM_ERR_ARG;
+    if (!dx && !dy) return LOM_OK;
+    const lom_occupancy_geometry plane{g->geo.resolution, g->geo.origin_x, g->geo.origin_y, g->geo.width, g->geo.height};
+    GridShift s;
+    int rc = grid_shift_plan(g, "elevation", plane, dx, dy, s);
+    if (rc != LOM_OK) return rc;
+    if (!s.keeps) {
+        if ((rc = lom_elevation_clear(g)) != LOM_OK) return rc;
+    } else {
+        LOM_HIP(g, hipSetDevice(g->device));
+        if ((rc = grid_shift_shadow(g, g->cells_shadow, g->n_cells() * sizeof(ElevCell), "hipMalloc (elevation shift)")) != LOM_OK) return rc;
+        LOM_HIP(g, launch_shift_rec32(g->stream, g->cells.p, g->cells_shadow.p, g->geo.width, g->geo.height, s.dx, s.dy));
+        if ((rc = grid_shift_wait(g)) != LOM_OK) return rc;
+        g->cells.swap(g->cells_shadow);
+    }
+    g->geo.origin_x = s.geo.origin_x, g->geo.origin_y = s.geo.origin_y;  // (z_ref stays)
     return LOM_OK;
 }
 

@@ -67,4 +67,27 @@ int grid_copy_out(GridHandle *g, int8_t *out, const DeviceBuf &cells, size_t n, 
     return grid_read_words(g, n_words, false);
 }
 
+int grid_shift_plan(GridHandle *g, const char *name, const lom_occupancy_geometry &geo, int32_t dx, int32_t dy, GridShift &out)
+{
+    // (the grid's geometry passed its create, so the rule can only refuse the new origin)
+    if (const int rc = plane::shift_geometry(&geo, dx, dy, &out.geo); rc != LOM_OK)
+        return fail(g, rc, (std::string(name) + ": shift: the origin moved by (dx, dy) cells is not finite").c_str());
+    const int64_t w = geo.width, h = geo.height;
+    out.keeps = dx > -w && dx < w && dy > -h && dy < h;
+    out.dx = (int32_t)std::max(-w, std::min(w, (int64_t)dx)), out.dy = (int32_t)std::max(-h, std::min(h, (int64_t)dy));
+    return LOM_OK;
+}
+
+int grid_shift_shadow(GridHandle *g, DeviceBuf &shadow, size_t bytes, const char *oom_text)
+{
+    if (shadow.p) return LOM_OK;  // (a grid's size never changes)
+    return alloc(shadow, bytes) == hipSuccess ? LOM_OK : fail(g, LOM_ERR_OOM, oom_text);
+}
+
+int grid_shift_wait(GridHandle *g)
+{
+    LOM_HIP(g, hipStreamSynchronize(g->stream));
+    return LOM_OK;
+}
+
 }  // namespace lom

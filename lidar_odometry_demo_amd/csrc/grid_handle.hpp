@@ -1,7 +1,8 @@
 // The handle of a dense 2-D grid that integrates posed scans, written once for lom_occupancy (occupancy.hip) and
 // lom_elevation (elevation.hip): the buffers of a call, what create and destroy do for both, the packed upload of a host
-// cloud, the staging and the read-back of a call (grid_handle.hip) and the integrate entry points (templates below).  A
-// family keeps its geometry, its own buffers and options, its kernels and their launches.  Nothing here launches a kernel.
+// cloud, the staging and the read-back of a call, the host part of a shift by whole cells (grid_handle.hip) and the
+// integrate entry points (templates below).  A family keeps its geometry, its own buffers and options, its kernels and
+// their launches.  Nothing here launches a kernel.
 #pragma once
 #include <cstring>
 #include <mutex>
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "archive_internal.hpp"
+#include "plane_geometry.hpp"
 
 namespace lom {
 
@@ -39,6 +41,22 @@ int grid_stage(GridHandle *g, const std::vector<assemble::AsmScan> &scans, uint3
 int grid_read_words(GridHandle *g, uint32_t n_words, bool record_done);
 // a per-cell int8 result for the caller: n bytes of `cells` to `out`, n_words summary words into h_words, then the wait
 int grid_copy_out(GridHandle *g, int8_t *out, const DeviceBuf &cells, size_t n, uint32_t n_words);
+
+// ---- the shift by whole cells (include/lidar_odometry_amd.h, "grid shift") --------------------------------------------
+// What a family's shift does around its one launch (grid_shift.hpp): ask grid_shift_plan; keeps false: its own clear, else
+// grid_shift_shadow for each block it moves, the launch from the block into its shadow, grid_shift_wait, and only then
+// the swap of block and shadow and the new geometry -- so a call that fails anywhere leaves the grid as it was.  The
+// shadows are allocated at the first shift that keeps something and stay: a grid that never shifts pays nothing.
+struct GridShift {
+    lom_occupancy_geometry geo;  // the geometry afterwards (plane_geometry.hpp: the rule)
+    int32_t dx, dy;              // clamped to |dx| <= width, |dy| <= height: what the kernels take
+    bool keeps;                  // some cell of the grid stays in it
+};
+// LOM_ERR_RANGE and "<name>: shift: ..." where the rule refuses; `geo`: the grid's own, an elevation grid's without z_ref
+int grid_shift_plan(GridHandle *g, const char *name, const lom_occupancy_geometry &geo, int32_t dx, int32_t dy, GridShift &out);
+// exactly `bytes` in `shadow`, once; LOM_ERR_OOM and `oom_text`
+int grid_shift_shadow(GridHandle *g, DeviceBuf &shadow, size_t bytes, const char *oom_text);
+int grid_shift_wait(GridHandle *g);  // the call returns with its work done
 
 // ---- the integrate entry points -------------------------------------------------------------------------------------
 // G, the family's handle, derives from GridHandle and brings: geo; Plan (has `scans`, an assemble::Plan); kName, the head

@@ -310,6 +310,7 @@ int lom_navfield_clear(lom_navfield *f)
     return LOM_OK;
 }
 
+int lom_navfield_shift(lom_navfield *f, int32_t dx, int32_t dy) { return plane_shift(f, "navigation field", dx, dy, &lom_navfield_clear); }
 int lom_navfield_get_geometry(const lom_navfield *f, lom_occupancy_geometry *out) { return plane_get_geometry(f, out); }
 void *lom_navfield_stream(lom_navfield *f) { return plane_stream(f); }
 int lom_navfield_device(const lom_navfield *f) { return plane_device(f); }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "grid_handle.hpp"
+#include "grid_shift.hpp"
 #include "k_occupancy.hpp"
 #include "occupancy_host.hpp"
 
@@ -20,6 +21,7 @@ using namespace lom;
 struct lom_occupancy : lom::GridHandle {
     lom_occupancy_geometry geo{};
     lom::DeviceBuf free_votes, seen_votes;  // width * height u32 each
+    lom::DeviceBuf free_shadow, seen_shadow;  // where a shift moves them to, from the first shift on (grid_handle.hpp)
     lom::DeviceBuf bitmaps;                 // [scan of a slice][pass, hit][row][word], grow-only
     lom::DeviceBuf cells;                   // start cells of a call
     lom::DeviceBuf cls;                     // the classification, int8 per cell
@@ -144,6 +146,30 @@ int lom_occupancy_clear(lom_occupancy *g)
     LOM_HIP(g, hipMemsetAsync(g->free_votes.p, 0, g->n_cells() * 4, g->stream));
     LOM_HIP(g, hipMemsetAsync(g->seen_votes.p, 0, g->n_cells() * 4, g->stream));
     LOM_HIP(g, hipStreamSynchronize(g->stream));
+    return LOM_OK;
+}
+
+int lom_occupancy_shift(lom_occupancy *g, int32_t dx, int32_t dy)
+{
+    if (!g) return LOM_ERR_ARG;
+    if (!dx && !dy) return LOM_OK;
+    GridShift s;
+    int rc = grid_shift_plan(g, "occupancy", g->geo, dx, dy, s);
+    if (rc != LOM_OK) return rc;
+    if (!s.keeps) {
+        if ((rc = lom_occupancy_clear(g)) != LOM_OK) return rc;
+        g->geo = s.geo;
+        return LOM_OK;
+    }
+    LOM_HIP(g, hipSetDevice(g->device));
+    const size_t count_bytes = g->n_cells() * 4;
+    if ((rc = grid_shift_shadow(g, g->free_shadow, count_bytes, "hipMalloc (occupancy shift)")) != LOM_OK) return rc;
+    if ((rc = grid_shift_shadow(g, g->seen_shadow, count_bytes, "hipMalloc (occupancy shift)")) != LOM_OK) return rc;
+    LOM_HIP(g, launch_shift_u32x2(g->stream, g->free_votes.as<const uint32_t>(), g->seen_votes.as<const uint32_t>(),
+                                  g->free_shadow.as<uint32_t>(), g->seen_shadow.as<uint32_t>(), g->geo.width, g->geo.height, s.dx, s.dy));
+    if ((rc = grid_shift_wait(g)) != LOM_OK) return rc;
+    g->free_votes.swap(g->free_shadow), g->seen_votes.swap(g->seen_shadow);
+    g->geo = s.geo;
     return LOM_OK;
 }
 

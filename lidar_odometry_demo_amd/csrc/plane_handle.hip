@@ -62,6 +62,14 @@ int plane_check_producer(PlaneHandle *h, const char *consumer, const char *produ
     return LOM_OK;
 }
 
+int plane_shifted_geometry(PlaneHandle *h, const char *name, int32_t dx, int32_t dy, lom_occupancy_geometry *out)
+{
+    // (the handle's geometry passed its create, so the rule can only refuse the new origin)
+    if (const int rc = plane::shift_geometry(&h->geo, dx, dy, out); rc != LOM_OK)
+        return fail(h, rc, (std::string(name) + ": shift: the origin moved by (dx, dy) cells is not finite").c_str());
+    return LOM_OK;
+}
+
 int plane_fail_producer(PlaneHandle *h, const char *consumer, const char *call, const char *producer_error)
 {
     return fail(h, LOM_ERR_HIP, (std::string(consumer) + ": " + call + ": " + producer_error).c_str());

@@ -1,9 +1,9 @@
 // The handle of a planning grid, written once for lom_clearance (clearance.hip), lom_navfield (navfield.hip), lom_regions
 // (regions.hip) and lom_visibility (visibility.hip): a dense 2-D grid of one geometry that reads planes other handles
 // leave in HBM on streams of their own.  What create and destroy do for all four, the small entry points, the read-back
-// of a buffer, and the hand-off of a producer's plane between two streams (code: plane_handle.hip).  A family
-// keeps its buffers, pinned blocks and options, its refusals, its kernels and their launches.  Nothing here launches a
-// kernel.
+// of a buffer, the shift by whole cells, and the hand-off of a producer's plane between two streams (code:
+// plane_handle.hip).  A family keeps its buffers, pinned blocks and options, its refusals, its kernels and their launches.
+// Nothing here launches a kernel.
 #pragma once
 #include <cstring>
 #include <new>
@@ -63,6 +63,23 @@ int plane_release(PlaneHandle *h, const char *consumer, P *producer, int (*wait_
 {
     if (wait_event(producer, h->done_ev) == LOM_OK) return LOM_OK;
     return fail(h, LOM_ERR_HIP, (std::string(consumer) + ": " + call).c_str());
+}
+
+// ---- the shift by whole cells (include/lidar_odometry_amd.h, "grid shift") --------------------------------------------
+// LOM_ERR_RANGE and "<name>: shift: ..." where the rule of plane_geometry.hpp refuses the new origin, else *out
+int plane_shifted_geometry(PlaneHandle *h, const char *name, int32_t dx, int32_t dy, lom_occupancy_geometry *out);
+// The geometry moves by the rule and the state becomes what the family's own clear leaves (also for dx == dy == 0): these
+// handles are recomputed from their producers anyway.  A refusal comes before the clear and leaves the handle untouched.
+// Carrying a clearance grid's distances or a navigation field across a shift is not part of this.
+template <class H>
+int plane_shift(H *h, const char *name, int32_t dx, int32_t dy, int (*clear)(H *))
+{
+    if (!h) return LOM_ERR_ARG;
+    lom_occupancy_geometry g;
+    if (const int rc = plane_shifted_geometry(h, name, dx, dy, &g); rc != LOM_OK) return rc;
+    if (const int rc = clear(h); rc != LOM_OK) return rc;
+    h->geo = g;
+    return LOM_OK;
 }
 
 // The head of a create: the geometry rule ("<name> geometry: ..."), the device checks, a fresh H on its device and

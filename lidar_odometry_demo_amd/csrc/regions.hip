@@ -198,6 +198,7 @@ int lom_regions_clear(lom_regions *r)
     return reset(r);
 }
 
+int lom_regions_shift(lom_regions *r, int32_t dx, int32_t dy) { return plane_shift(r, "region grid", dx, dy, &lom_regions_clear); }
 int lom_regions_get_geometry(const lom_regions *r, lom_occupancy_geometry *out) { return plane_get_geometry(r, out); }
 void *lom_regions_stream(lom_regions *r) { return plane_stream(r); }
 int lom_regions_device(const lom_regions *r) { return plane_device(r); }

@@ -209,6 +209,7 @@ int lom_rollout_clear(lom_rollout *r)
     return LOM_OK;
 }
 
+int lom_rollout_shift(lom_rollout *r, int32_t dx, int32_t dy) { return plane_shift(r, "rollout grid", dx, dy, &lom_rollout_clear); }
 int lom_rollout_get_geometry(const lom_rollout *r, lom_occupancy_geometry *out) { return plane_get_geometry(r, out); }
 void *lom_rollout_stream(lom_rollout *r) { return plane_stream(r); }
 int lom_rollout_device(const lom_rollout *r) { return plane_device(r); }

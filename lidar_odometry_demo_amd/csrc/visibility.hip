@@ -240,6 +240,7 @@ int lom_visibility_clear(lom_visibility *v)
     return LOM_OK;
 }
 
+int lom_visibility_shift(lom_visibility *v, int32_t dx, int32_t dy) { return plane_shift(v, "visibility grid", dx, dy, &lom_visibility_clear); }
 int lom_visibility_get_geometry(const lom_visibility *v, lom_occupancy_geometry *out) { return plane_get_geometry(v, out); }
 void *lom_visibility_stream(lom_visibility *v) { return plane_stream(v); }
 int lom_visibility_device(const lom_visibility *v) { return plane_device(v); }
