@@ -1769,6 +1769,49 @@ int lom_clearance_query(lom_clearance *c, const float *xy, size_t n, float *dist
  * eight neighbours; 2 keeps only the goals and relaxes from them, the full solve on the same handle.  cells_raised is what
  * the chosen form set unreached behind the diff.
  *
+ * Shift and re-solve.  lom_navfield_shift (grid shift, below) moves the geometry and clears the field.
+ * lom_navfield_shift_resolve* moves the geometry, keeps what still overlaps and re-solves the rest in one call, for a
+ * field that follows a robot.  It takes (dx, dy), a new full-grid int8 plane and an optional window, as a re-solve does.
+ *  1. Geometry.  The new geometry is lom_grid_shift_geometry(geometry, dx, dy), that rule and nothing else.  The window and
+ *     every plane are in the new geometry's cells.
+ *  2. Moved state.  Cell (ix, iy) takes the kept plane's byte and P of cell (ix + dx, iy + dy) where that lies in the
+ *     grid: the kept box, cells_kept cells.  Every other cell has entered: no kept byte, P unreached; cells_entered.
+ *  3. Merged plane.  Entered cells take the new plane's byte, window or not.  Kept cells inside the clipped window take
+ *     the new plane's byte.  Every other kept cell keeps its own byte and is not read from the new plane.  NULL window:
+ *     the whole grid.  An empty window is allowed: the entered cells still take their bytes.  The host form reads the
+ *     entered cells and the window; where the shift is not zero it uploads every row from the first to the last that
+ *     holds such a cell, whole.
+ *  4. Goals.  The cells with P == 0 in the moved state.  A goal whose source left the grid counts in goals_left; one that
+ *     is impassable in the merged plane counts in goals_rejected.  The previous goals_used equals goals_used +
+ *     goals_rejected + goals_left.
+ *  5. Result.  P and the summary are, byte for byte, what lom_navfield_solve gives on the merged plane in the new
+ *     geometry with the last solve's parameters and those goals.  Paths, waypoints, visibility and queries read the new
+ *     state.  A shift that keeps nothing (|dx| >= width or |dy| >= height) leaves the full solve of the new plane with no
+ *     goals, every cell unreached, and is LOM_OK.
+ *  6. (0, 0).  The call is lom_navfield_resolve* with the same arguments: same bytes, same summary, same
+ *     lom_navfield_resolve_stats; cells_kept is width * height.
+ *  7. Counters of the last call, through lom_navfield_resolve_stats.  cells_changed: the kept cells of the clipped window
+ *     whose byte differs from the kept one; entered cells are not in it.  cells_raised, under the default form: the size
+ *     of the least raised set of the moved state under the merged plane, behind the diff's drop of impassable cells.
+ *     lom_navfield_shift_stats gives cells_kept, cells_entered and goals_left of the last call.
+ *  8. Refusals.  A refused call changes nothing -- not P, plane, geometry, the solved state or the counters -- and zeroes
+ *     the summary.  A NULL plane: LOM_ERR_ARG.  No solve has completed since create or clear (lom_navfield_shift is a
+ *     clear): LOM_ERR_STATE.  The rule refuses the origin: LOM_ERR_RANGE.  A clearance grid whose geometry is not bit for
+ *     bit the SHIFTED geometry (shift it first), or one on another device: LOM_ERR_ARG.  A failed allocation:
+ *     LOM_ERR_OOM.  Every refusal comes before any device work.
+ *  9. Storage.  The moved state goes into a second block, the u32 field and the int8 plane, 5 bytes per cell, allocated
+ *     at the first call with a shift that is not zero and swapped with the first behind the launch: a field that never
+ *     shifts pays nothing.  lom_navfield_potential_device's pointer is therefore valid until the next solve, clear or
+ *     shift-resolve on the handle.
+ * 10. LOM_NAV_OPT_TEST_RESOLVE_FORM.  0, the default: raise, then relax.  2: the moved goals reseeded and the full
+ *     relaxation, the baseline on the same handle.  1, the threshold form: a shift that is not zero runs form 2 (its pmin
+ *     would have to cover the trailing borders as well); (0, 0) is the threshold form of a re-solve.  The bytes are the
+ *     same under all three.  INNER_CAP, BATCH and ALL_TILES act as in a re-solve.
+ * The device work is one pass over the destination (k_nav_shift_diff: the mover and the diff, every byte of the second
+ * block written once) and then what a re-solve runs.  The raise phase needs no new rule: a cell on a trailing border --
+ * column 0 for dx > 0, column width - 1 for dx < 0, rows likewise -- whose supporter left the grid has no supporter and
+ * rises, and what hung on it rises behind it; a goal that left is simply not there any more.
+ *
  * lom_navfield_solve takes a host plane of width * height bytes; _solve_device a plane in HBM that is complete when
  * hip_event_or_null is (NULL: now); _solve_from_clearance takes lom_clearance_cost_device's plane and orders the two
  * streams by events in both directions -- a clearance grid whose resolution, origin, width or height differ bit for bit,
@@ -1799,6 +1842,11 @@ typedef struct {
     uint64_t waits;          /* the host's waits of the call, the diff's and the summary's included */
     uint64_t tiles_marked;   /* tiles active in the first launch of the relaxation */
 } lom_navfield_resolve_counters; /* what lom_navfield_resolve_stats gives */
+typedef struct {
+    uint64_t cells_kept;    /* destination cells whose source lies in the grid */
+    uint64_t cells_entered; /* the others: width * height - cells_kept */
+    uint64_t goals_left;    /* goals whose cell left the grid */
+} lom_navfield_shift_counters; /* what lom_navfield_shift_stats gives */
 typedef struct {
     uint32_t max_cell_cost; /* a cell is clear up to this cell cost; 0: any passable cell */
     uint32_t lookahead;     /* W: route cells a shortcut may skip to, 1 .. 65535 */
@@ -1844,9 +1892,17 @@ int lom_navfield_resolve_device(lom_navfield *f, const int8_t *d_plane, void *hi
                                 const lom_clearance_window *window_or_null, lom_navfield_summary *summary_or_null);
 int lom_navfield_resolve_from_clearance(lom_navfield *f, lom_clearance *clearance, const lom_clearance_window *window_or_null,
                                         lom_navfield_summary *summary_or_null);
+/* the shift with a re-solve, in the three forms of a re-solve; the planes and the window are in the cells of the geometry
+ * moved by (dx, dy), and a clearance grid has been shifted by the same (dx, dy) before */
+int lom_navfield_shift_resolve(lom_navfield *f, int32_t dx, int32_t dy, const int8_t *plane, const lom_clearance_window *window_or_null,
+                               lom_navfield_summary *summary_or_null);
+int lom_navfield_shift_resolve_device(lom_navfield *f, int32_t dx, int32_t dy, const int8_t *d_plane, void *hip_event_or_null,
+                                      const lom_clearance_window *window_or_null, lom_navfield_summary *summary_or_null);
+int lom_navfield_shift_resolve_from_clearance(lom_navfield *f, int32_t dx, int32_t dy, lom_clearance *clearance,
+                                              const lom_clearance_window *window_or_null, lom_navfield_summary *summary_or_null);
 /* P over the whole grid, row-major: at most `cap` cells go to `out` (may be NULL with cap 0) */
 int lom_navfield_potential(lom_navfield *f, uint32_t *out, size_t cap);
-/* the same, left in HBM: width * height cells, valid until the next solve or clear on the handle */
+/* the same, left in HBM: width * height cells, valid until the next solve, clear or shift-resolve on the handle */
 int lom_navfield_potential_device(lom_navfield *f, const uint32_t **d_out);
 /* step 6: n_starts pairs of start_kind in host memory (at most 2^24, n_starts * cap at most 2^28); cells_out: [n_starts,
  * cap] u16 pairs (may be NULL with cap 0), lengths_out: n_starts u32 (may be NULL) */
@@ -1868,6 +1924,8 @@ int lom_navfield_cell_costs(const lom_navfield_params *params, uint32_t *out256)
 int lom_navfield_stats(const lom_navfield *f, lom_navfield_solve_stats *out);
 /* the counts of the last re-solve (zeros before the first, and for an empty window) */
 int lom_navfield_resolve_stats(const lom_navfield *f, lom_navfield_resolve_counters *out);
+/* the counts of the last shift with a re-solve (zeros before the first) */
+int lom_navfield_shift_stats(const lom_navfield *f, lom_navfield_shift_counters *out);
 
 /* ---- frontier regions: connected cells labelled on the device, ranked goals (not in the reference) ----------------------
  * The navigation field answers what it costs to get somewhere.  This handle family answers where to go: it labels the
@@ -2329,8 +2387,8 @@ lom_occupancy_shift_fn lom_occupancy_shift;
 lom_elevation_shift_fn lom_elevation_shift;
 /* The five planning families follow: the geometry moves by the same rule and the handle's state afterwards is exactly what
  * its own lom_*_clear leaves (also for dx == dy == 0), so the next update / solve / extract / cast / evaluate is a full one:
- * these handles are recomputed from their producers anyway.  Carrying the clearance distances or the field across a shift
- * is not part of this.  LOM_ERR_RANGE from the rule leaves the handle untouched.  A consumer that was not shifted meets a
+ * these handles are recomputed from their producers anyway.  Carrying the clearance distances across a shift is not part of
+ * this; a navigation field is carried by lom_navfield_shift_resolve* (navigation field, "Shift and re-solve").  LOM_ERR_RANGE from the rule leaves the handle untouched.  A consumer that was not shifted meets a
  * shifted producer with the usual refusal, "... resolution, origin, width or height differs". */
 typedef int(lom_clearance_shift_fn)(lom_clearance *c, int32_t dx, int32_t dy);
 typedef int(lom_navfield_shift_fn)(lom_navfield *f, int32_t dx, int32_t dy);

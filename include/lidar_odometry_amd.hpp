@@ -1217,6 +1217,27 @@ public:
         check(lom_navfield_resolve_stats(h_, &s));
         return s;
     }
+    // the shift with a re-solve: the geometry moves by (dx, dy) cells, the field moves with the world, the entered cells and
+    // the window's cells (NULL: the whole grid) take the bytes of a host plane of size() cells in the new geometry
+    lom_navfield_summary shiftResolve(int32_t dx, int32_t dy, const int8_t *plane, const lom_clearance_window *window = nullptr)
+    {
+        lom_navfield_summary s;
+        check(lom_navfield_shift_resolve(h_, dx, dy, plane, window, &s));
+        return s;
+    }
+    // ... of the plane a ClearanceGrid left in HBM after it was shifted by the same (dx, dy) and updated
+    lom_navfield_summary shiftResolveFromClearance(int32_t dx, int32_t dy, ClearanceGrid &clearance, const lom_clearance_window *window = nullptr)
+    {
+        lom_navfield_summary s;
+        check(lom_navfield_shift_resolve_from_clearance(h_, dx, dy, clearance.handle(), window, &s));
+        return s;
+    }
+    lom_navfield_shift_counters shiftStats() const
+    {
+        lom_navfield_shift_counters s;
+        check(lom_navfield_shift_stats(h_, &s));
+        return s;
+    }
     std::vector<uint32_t> potential()
     {
         std::vector<uint32_t> out(size());

@@ -1485,6 +1485,35 @@ class NavField(_PlaneGrid):
         self._check(self._call("resolve_stats", self._h, C.byref(st)))
         return st.asdict()
 
+    def shiftResolve(self, dx, dy, plane, window=None, device=False, hip_event=None):
+        """lom_navfield_shift_resolve: the geometry moves by (dx, dy) cells, the field and the kept plane move with the
+        world, the entered cells and the cells of `window` take the bytes of the host plane `plane` (in the new geometry's
+        cells), and the field is re-solved for the goals that are still in the grid -- or, with device=True,
+        lom_navfield_shift_resolve_device: `plane` is a device pointer to a plane in HBM, complete when `hip_event` is.
+        Returns capi.NavFieldSummary as a dict."""
+        sm = capi.NavFieldSummary()
+        if device:
+            rc = self._call("shift_resolve_device", self._h, int(dx), int(dy), plane, hip_event, ClearanceGrid._window(window), C.byref(sm))
+        else:
+            plane = self._plane(plane, np.int8)
+            rc = self._call("shift_resolve", self._h, int(dx), int(dy), plane.ctypes.data, ClearanceGrid._window(window), C.byref(sm))
+        self._check(rc)
+        return sm.asdict()
+
+    def shiftResolveFromClearance(self, dx, dy, clearance, window=None):
+        """lom_navfield_shift_resolve_from_clearance: the cost plane a ClearanceGrid left in HBM after it was shifted by
+        the same (dx, dy) and updated"""
+        sm = capi.NavFieldSummary()
+        self._check(self._call("shift_resolve_from_clearance", self._h, int(dx), int(dy), clearance.handle,
+                               ClearanceGrid._window(window), C.byref(sm)))
+        return sm.asdict()
+
+    def shiftStats(self):
+        """capi.NavFieldShiftCounters of the last shift with a re-solve as a dict: cells_kept, cells_entered, goals_left"""
+        st = capi.NavFieldShiftCounters()
+        self._check(self._call("shift_stats", self._h, C.byref(st)))
+        return st.asdict()
+
     def potential(self):
         """uint32 array of shape (height, width): P per cell, capi.NAV_UNREACHED where no goal is reached"""
         out = np.empty((self.height, self.width), np.uint32)

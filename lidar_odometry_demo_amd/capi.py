@@ -377,6 +377,14 @@ class NavFieldResolveCounters(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class NavFieldShiftCounters(C.Structure):
+    """lom_navfield_shift_counters"""
+    _fields_ = [("cells_kept", C.c_uint64), ("cells_entered", C.c_uint64), ("goals_left", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class NavFieldWaypointParams(C.Structure):
     """lom_navfield_waypoint_params"""
     _fields_ = [("max_cell_cost", C.c_uint32), ("lookahead", C.c_uint32), ("route_cap", C.c_uint32), ("flags", C.c_uint32)]
@@ -384,6 +392,7 @@ class NavFieldWaypointParams(C.Structure):
 
 assert C.sizeof(NavFieldParams) == 20 and C.sizeof(NavFieldSummary) == 64 and C.sizeof(NavFieldSolveStats) == 24
 assert C.sizeof(NavFieldResolveCounters) == 48 and C.sizeof(NavFieldWaypointParams) == 16
+assert C.sizeof(NavFieldShiftCounters) == 24
 NAV_UNREACHED, NAV_MAX = 0xFFFFFFFF, 0xFFFFFFFE
 NAV_UNKNOWN_PASSABLE = 1
 NAV_CELLS, NAV_METRES = 0, 1
@@ -804,6 +813,10 @@ PROTOTYPES = {
     "lom_navfield_resolve_device": (_int, [_vp, _vp, _vp, _P(ClearanceWindow), _P(NavFieldSummary)]),
     "lom_navfield_resolve_from_clearance": (_int, [_vp, _vp, _P(ClearanceWindow), _P(NavFieldSummary)]),
     "lom_navfield_resolve_stats": (_int, [_vp, _P(NavFieldResolveCounters)]),
+    "lom_navfield_shift_resolve": (_int, [_vp, C.c_int32, C.c_int32, _vp, _P(ClearanceWindow), _P(NavFieldSummary)]),
+    "lom_navfield_shift_resolve_device": (_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _P(ClearanceWindow), _P(NavFieldSummary)]),
+    "lom_navfield_shift_resolve_from_clearance": (_int, [_vp, C.c_int32, C.c_int32, _vp, _P(ClearanceWindow), _P(NavFieldSummary)]),
+    "lom_navfield_shift_stats": (_int, [_vp, _P(NavFieldShiftCounters)]),
     "lom_navfield_potential": (_int, [_vp, _vp, _size]),
     "lom_navfield_potential_device": (_int, [_vp, _P(_vp)]),
     "lom_navfield_paths": (_int, [_vp, _int, _vp, _size, _vp, _size, _vp]),

@@ -2,8 +2,9 @@
 // queries.  Definitions: include/lidar_odometry_amd.h ("navigation field"); kernels: k_navfield.hpp; host planning (value
 // ranges, the cell-cost table, goal quantisation, tile counts, launch shapes): navfield_host.cpp; DESIGN.md 7m.  The
 // re-solve after a local cost change (k_navfield_resolve.hpp) keeps what a solve left and repairs it; the
-// line of sight and the waypoints (k_navfield_waypoints.hpp) read what it left.  A handle family of its own
-// on the PlaneHandle core (plane_handle.hpp); no default path launches any of this.
+// line of sight and the waypoints (k_navfield_waypoints.hpp) read what it left; the shift with a re-solve
+// (k_navfield_shift.hpp) moves it into a second block and repairs it there.  A handle family of its own on
+// the PlaneHandle core (plane_handle.hpp); no default path launches any of this.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -12,6 +13,7 @@
 #include "clearance_host.hpp"
 #include "k_navfield.hpp"
 #include "k_navfield_resolve.hpp"
+#include "k_navfield_shift.hpp"
 #include "k_navfield_waypoints.hpp"
 #include "navfield_host.hpp"
 #include "plane_handle.hpp"
@@ -33,6 +35,7 @@ struct lom_navfield : lom::PlaneHandle {  // in_ev: the clearance grid's
     lom::DeviceBuf flags;            // kBatchMax u32: "launch j of the batch marked a tile"
     lom::DeviceBuf words;            // the summary words, and behind them a re-solve's
     lom::DeviceBuf incoming;         // the window's rows of a re-solve's host plane, grow-only
+    lom::DeviceBuf field2, plane2;   // the second block of a shift with a re-solve: empty until the first non-zero shift
     lom::DeviceBuf points;           // goals or starts as int32 pairs, grow-only
     lom::DeviceBuf path_cells, path_lengths;  // a paths call's results, grow-only
     lom::DeviceBuf q_xy, q_out;      // a query's points and results, grow-only
@@ -46,6 +49,7 @@ struct lom_navfield : lom::PlaneHandle {  // in_ev: the clearance grid's
     uint32_t shortcut_serial = 0;                     // LOM_NAV_OPT_TEST_SHORTCUT_SERIAL
     lom_navfield_solve_stats stats{};
     lom_navfield_resolve_counters resolve_stats{};
+    lom_navfield_shift_counters shift_stats{};
     bool solved = false;             // a solve has completed since create or clear: plane, table and P are a fixed point
     uint32_t last_words[NW_COUNT] = {};  // ... and its summary words: what a re-solve that changes nothing reports
 
@@ -265,6 +269,107 @@ int resolve_nothing(lom_navfield *f, lom_navfield_summary *summary)
     return LOM_OK;
 }
 
+// ---- the shift with a re-solve ------------------------------------------------------------------------------------------
+// What every form does before any device work: the refusals of a re-solve, the geometry by the rule (LOM_ERR_RANGE) and the
+// plan.
+int shift_resolve_head(lom_navfield *f, bool have_plane, int32_t dx, int32_t dy, lom_occupancy_geometry *g, navfield::ShiftPlan *plan)
+{
+    if (const int rc = resolve_refusal(f, have_plane); rc != LOM_OK) return rc;
+    if (const int rc = plane_shifted_geometry(f, kName, dx, dy, g); rc != LOM_OK) return rc;
+    *plan = navfield::shift_plan(f->geo.width, f->geo.height, dx, dy);
+    return LOM_OK;
+}
+
+// the second block, at the first call that moves: 5 bytes per cell
+int ensure_second_block(lom_navfield *f)
+{
+    if (f->field2.p && f->plane2.p) return LOM_OK;
+    release(f->field2), release(f->plane2);
+    if (alloc(f->field2, f->n_cells() * 4) != hipSuccess || alloc(f->plane2, f->n_cells()) != hipSuccess) {
+        release(f->field2), release(f->plane2);
+        return fail(f, LOM_ERR_OOM, "hipMalloc (navigation field, the second block of a shift)");
+    }
+    return LOM_OK;
+}
+
+// A shift of (0, 0) is the re-solve with the same arguments, under the geometry the rule gives for it (an origin of -0
+// becomes +0); a refusal puts the geometry back.
+template <class Resolve>
+int shift_resolve_in_place(lom_navfield *f, const lom_occupancy_geometry &g, Resolve resolve)
+{
+    const lom_occupancy_geometry before = f->geo;
+    f->geo = g;
+    const int rc = resolve();
+    if (rc != LOM_OK) {
+        f->geo = before;
+        return rc;
+    }
+    f->shift_stats = lom_navfield_shift_counters{f->n_cells(), 0u, 0u};
+    return LOM_OK;
+}
+
+// A shift that moves, from a plane in HBM that this stream may read now, in the new geometry's cells; r may be empty.  The
+// mover and diff in one launch into the second block, the swap behind it, and a wait; then the raise phase to its fixed
+// point (or the reset of form 2, which the threshold form runs as well: its pmin would have to cover the trailing
+// borders), the relaxation from the seeds, the report and the wait.  done_ev stands behind the first launch, the one
+// reader of d_new.  Every allocation has been made.
+int shift_resolve_on_device(lom_navfield *f, const navfield::ShiftPlan &plan, const lom_occupancy_geometry &g, const int8_t *d_new,
+                            const clearance::Rect &r, lom_navfield_summary *summary)
+{
+    const NavArgs a = f->args();
+    const uint32_t n_tiles = f->tiles.n_tiles;
+    const bool raise = f->resolve_form == 0u;
+    const uint32_t *const table = f->table.as<const uint32_t>();
+    uint32_t *const words = f->words.as<uint32_t>();
+    uint32_t *const marks0 = f->marks.as<uint32_t>(), *const seeds = marks0 + (size_t)2 * n_tiles;
+    uint32_t *const h = f->h_flags.as<uint32_t>();
+    lom_navfield_resolve_counters &st = f->resolve_stats;
+    st = lom_navfield_resolve_counters{};
+    LOM_HIP(f, hipMemsetAsync(f->words.p, 0, (size_t)SW_END * 4, f->stream));
+    LOM_HIP(f, hipMemsetAsync(f->marks.p, 0, (size_t)3 * n_tiles * 4, f->stream));
+    const clearance::Rect w = r.empty() ? clearance::Rect{0u, 0u, 0u, 0u} : r;
+    const NavShift s{plan.dx, plan.dy, plan.kept.x0, plan.kept.y0, plan.kept.x1, plan.kept.y1, w.x0, w.y0, w.x1, w.y1};
+    hipLaunchKernelGGL(k_nav_shift_diff, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0, f->stream, d_new, table, a, s,
+                       f->plane.as<const int8_t>(), f->field.as<const uint32_t>(), f->plane2.as<int8_t>(), f->field2.as<uint32_t>(),
+                       raise ? seeds : nullptr, raise ? marks0 : nullptr, words);
+    LOM_HIP(f, hipGetLastError());
+    f->solved = false;
+    swap(f->field, f->field2), swap(f->plane, f->plane2);
+    f->geo = g;
+    uint32_t *const field = f->field.as<uint32_t>();
+    LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
+    LOM_HIP(f, hipMemcpyAsync(h, f->words.p, (size_t)SW_END * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    st.waits = 1;
+    st.cells_changed = h[RW_CHANGED];
+    const uint32_t rejected = h[NW_GOALS_REJECTED], left = h[SW_GOALS_LEFT];
+    f->shift_stats = lom_navfield_shift_counters{plan.cells_kept, h[SW_ENTERED], left};
+    if (raise) {
+        const int rc = to_fixed_point(f, st.raise_launches, st.waits, "navigation field: the raise phase did not settle",
+                                      [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
+                                          hipLaunchKernelGGL(k_nav_raise, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0,
+                                                             f->stream, f->plane.as<const int8_t>(), table, a, f->inner_cap, f->all_tiles,
+                                                             field, cur, nxt, seeds, flag, words);
+                                      });
+        if (rc != LOM_OK) return rc;
+        LOM_HIP(f, hipMemcpyAsync(marks0, seeds, (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, f->stream));
+    } else {
+        hipLaunchKernelGGL(k_nav_reseed, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream,
+                           f->plane.as<const int8_t>(), table, a, field, marks0, words);
+        LOM_HIP(f, hipGetLastError());
+    }
+    if (const int rc = relax(f, st.relax_launches, st.waits); rc != LOM_OK) return rc;
+    if (const int rc = report(f, RW_END); rc != LOM_OK) return rc;
+    st.waits++;
+    st.cells_raised = h[RW_RAISED], st.tiles_marked = h[RW_TILES];
+    h[NW_GOALS_USED] = f->last_words[NW_GOALS_USED] - rejected - left;  // (the report counts cells: the goals are the host's to keep)
+    h[NW_GOALS_REJECTED] = rejected;
+    std::memcpy(f->last_words, h, sizeof f->last_words);
+    f->solved = true;
+    if (summary) summary_from(f->last_words, summary);
+    return LOM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -439,6 +544,71 @@ int lom_navfield_resolve_from_clearance(lom_navfield *f, lom_clearance *clearanc
     return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
 }
 
+int lom_navfield_shift_resolve_device(lom_navfield *f, int32_t dx, int32_t dy, const int8_t *d_plane, void *hip_event_or_null,
+                                      const lom_clearance_window *window_or_null, lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    lom_occupancy_geometry g;
+    navfield::ShiftPlan plan;
+    if (const int rc = shift_resolve_head(f, d_plane != nullptr, dx, dy, &g, &plan); rc != LOM_OK) return rc;
+    if (!plan.moves())
+        return shift_resolve_in_place(f, g, [&] { return lom_navfield_resolve_device(f, d_plane, hip_event_or_null, window_or_null, summary); });
+    LOM_HIP(f, hipSetDevice(f->device));
+    if (const int rc = ensure_second_block(f); rc != LOM_OK) return rc;
+    if (hip_event_or_null) LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event_or_null, 0));
+    return shift_resolve_on_device(f, plan, g, d_plane, clearance::clip(window_or_null, g), summary);
+}
+
+int lom_navfield_shift_resolve(lom_navfield *f, int32_t dx, int32_t dy, const int8_t *plane, const lom_clearance_window *window_or_null,
+                               lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    lom_occupancy_geometry g;
+    navfield::ShiftPlan plan;
+    if (const int rc = shift_resolve_head(f, plane != nullptr, dx, dy, &g, &plan); rc != LOM_OK) return rc;
+    if (!plan.moves()) return shift_resolve_in_place(f, g, [&] { return lom_navfield_resolve(f, plane, window_or_null, summary); });
+    LOM_HIP(f, hipSetDevice(f->device));
+    if (const int rc = ensure_second_block(f); rc != LOM_OK) return rc;
+    if (const int rc = ensure(f, f->incoming, f->n_cells()); rc != LOM_OK) return rc;
+    // the rows that hold an entered cell or a cell of the window, whole, at their place in a plane of the device
+    const clearance::Rect r = clearance::clip(window_or_null, g);
+    uint32_t y0, y1;
+    navfield::shift_upload_rows(plan, r, g.height, &y0, &y1);
+    const size_t first = (size_t)y0 * g.width, bytes = (size_t)(y1 - y0) * g.width;
+    if (bytes) LOM_HIP(f, hipMemcpyAsync(f->incoming.as<int8_t>() + first, plane + first, bytes, hipMemcpyHostToDevice, f->stream));
+    return shift_resolve_on_device(f, plan, g, f->incoming.as<const int8_t>(), r, summary);
+}
+
+int lom_navfield_shift_resolve_from_clearance(lom_navfield *f, int32_t dx, int32_t dy, lom_clearance *clearance,
+                                              const lom_clearance_window *window_or_null, lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    lom_occupancy_geometry g;
+    navfield::ShiftPlan plan;
+    if (const int rc = shift_resolve_head(f, clearance != nullptr, dx, dy, &g, &plan); rc != LOM_OK) return rc;
+    if (!plan.moves())
+        return shift_resolve_in_place(f, g, [&] { return lom_navfield_resolve_from_clearance(f, clearance, window_or_null, summary); });
+    // the clearance grid has been shifted already: its geometry is the new one, bit for bit
+    lom_occupancy_geometry cg{};
+    (void)lom_clearance_get_geometry(clearance, &cg);
+    if (!same_geometry(cg, g))
+        return fail(f, LOM_ERR_ARG, "navigation field: the clearance grid's resolution, origin, width or height differs from the shifted geometry");
+    if (lom_clearance_device(clearance) != f->device) return fail(f, LOM_ERR_ARG, "navigation field: the clearance grid lives on another device");
+    LOM_HIP(f, hipSetDevice(f->device));
+    int rc = ensure_second_block(f);
+    if (rc != LOM_OK) return rc;
+    // the hand-off of plane_handle.hpp: read behind the clearance grid, shift and re-solve, release to it
+    const int8_t *d_plane = nullptr;
+    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
+        return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
+    if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
+    if ((rc = shift_resolve_on_device(f, plan, g, d_plane, clearance::clip(window_or_null, g), summary)) != LOM_OK) return rc;
+    return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
+}
+
 int lom_navfield_potential(lom_navfield *f, uint32_t *out, size_t cap)
 {
     if (!f || (cap && !out)) return LOM_ERR_ARG;
@@ -580,6 +750,13 @@ int lom_navfield_resolve_stats(const lom_navfield *f, lom_navfield_resolve_count
 {
     if (!f || !out) return LOM_ERR_ARG;
     *out = f->resolve_stats;
+    return LOM_OK;
+}
+
+int lom_navfield_shift_stats(const lom_navfield *f, lom_navfield_shift_counters *out)
+{
+    if (!f || !out) return LOM_ERR_ARG;
+    *out = f->shift_stats;
     return LOM_OK;
 }
 

@@ -1,7 +1,7 @@
 // Host planning of the navigation field (navfield_host.cpp), shared with navfield.hip.  Plain C++: nothing here needs a
 // device or a HIP header.  The value ranges of the geometry and the parameters, the cell-cost table, the quantisation of
-// goals and starts, the tile counts, the tiles of a re-solve's window and the launch shapes.  Definitions:
-// include/lidar_odometry_amd.h ("navigation field").
+// goals and starts, the tile counts, the tiles of a re-solve's window, the plan of a shift with a re-solve and the launch
+// shapes.  Definitions: include/lidar_odometry_amd.h ("navigation field").
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -63,6 +63,34 @@ bool waypoint_params_ok(const lom_navfield_waypoint_params *p, size_t n_starts);
 bool waypoint_output_ok(size_t n_starts, size_t wp_cap, const void *cells_out);
 // workgroups of k_nav_shortcut for n routes (at least one)
 uint32_t shortcut_blocks_for(size_t n_routes);
+// ---- the shift with a re-solve ("Shift and re-solve") ---------------------------------------------------
+// Everything of lom_navfield_shift_resolve* that needs no device, for a grid of width x height cells moved by (dx, dy).
+//  - dx, dy: the shift clamped to |dx| <= width, |dy| <= height (a larger one keeps nothing, as these do), so that every
+//    index of the device pass fits 32 bits.
+//  - kept: the destination cells (ix, iy) whose source (ix + dx, iy + dy) lies in the grid, a box; {0, 0, 0, 0} where nothing
+//    is kept.  cells_kept + cells_entered = width * height.
+//  - entered[0 .. n_entered): the other cells as at most two disjoint rectangles: the whole rows outside the kept box's
+//    rows, then the columns outside its columns within its rows.
+//  - trailing[0 .. n_trailing): the tiles that hold a kept cell on a trailing border -- column 0 for dx > 0, column
+//    width - 1 for dx < 0, row 0 for dy > 0, row height - 1 for dy < 0 -- as at most two tile ranges (a column of tiles, a
+//    row of tiles; they may share a corner tile); trailing_cells counts those cells, a corner cell once.
+struct ShiftPlan {
+    int32_t dx, dy;
+    clearance::Rect kept;
+    clearance::Rect entered[2];
+    uint32_t n_entered;
+    uint64_t cells_kept, cells_entered;
+    TileRange trailing[2];
+    uint32_t n_trailing;
+    uint64_t trailing_cells;
+    bool moves() const { return dx != 0 || dy != 0; }
+};
+ShiftPlan shift_plan(uint32_t width, uint32_t height, int32_t dx, int32_t dy);
+// The rows [*y0, *y1) of a host plane that lom_navfield_shift_resolve uploads, whole: every row that holds an entered cell
+// or a cell of the clipped window (one run of rows: what lies between two such rows goes along).  Empty (*y0 == *y1 == 0)
+// where there is neither.
+void shift_upload_rows(const ShiftPlan &plan, const clearance::Rect &window, uint32_t height, uint32_t *y0, uint32_t *y1);
+
 // More launches than any solve needs: a cell whose best route has d steps is final one launch after the next cell of
 // that route is, so d + 1 launches settle it, and d is below the number of cells.  2 * cells + 64.
 uint64_t launch_bound(uint32_t width, uint32_t height);

@@ -70,7 +70,8 @@ int plane_release(PlaneHandle *h, const char *consumer, P *producer, int (*wait_
 int plane_shifted_geometry(PlaneHandle *h, const char *name, int32_t dx, int32_t dy, lom_occupancy_geometry *out);
 // The geometry moves by the rule and the state becomes what the family's own clear leaves (also for dx == dy == 0): these
 // handles are recomputed from their producers anyway.  A refusal comes before the clear and leaves the handle untouched.
-// Carrying a clearance grid's distances or a navigation field across a shift is not part of this.
+// Carrying a clearance grid's distances across a shift is not part of this; a navigation field is carried by
+// lom_navfield_shift_resolve* (navfield.hip).
 template <class H>
 int plane_shift(H *h, const char *name, int32_t dx, int32_t dy, int (*clear)(H *))
 {
