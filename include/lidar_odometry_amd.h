@@ -1927,6 +1927,124 @@ int lom_navfield_resolve_stats(const lom_navfield *f, lom_navfield_resolve_count
 /* the counts of the last shift with a re-solve (zeros before the first) */
 int lom_navfield_shift_stats(const lom_navfield *f, lom_navfield_shift_counters *out);
 
+/* ---- navigation field set: N fields over one cost plane in one call (not in the reference) -----------------------------
+ * A navigation field holds one field, and its solve is a chain of dependent launches along the wavefront.  Ordering a tour
+ * over frontier goals needs goal-to-goal travel costs, sharing goals among robots needs a field per robot, and cutting the
+ * free space into "nearest goal" cells needs all the fields at once.  This handle family solves N fields over the same
+ * plane and parameters side by side: every launch of the relaxation covers every field, so the launches and waits of a
+ * call are near those of its slowest field, not their sum.  Nothing is launched unless a caller creates a set.
+ *
+ * Grid.  lom_occupancy_geometry with the planning grids' rule, as a navigation field.  lom_navset_create takes max_fields
+ * in 1 .. LOM_NAVSET_MAX_FIELDS (65535); anything else is LOM_ERR_ARG.  Storage: 4 bytes per cell and field for max_fields
+ * fields, one copy of the plane (a byte per cell), and the marks (8 bytes per 32 x 32 tile and field).  A failed allocation
+ * is LOM_ERR_OOM and leaves no handle.
+ *
+ * Solve.  lom_navset_solve* takes one plane, one lom_navfield_params, one goal array of LOM_NAV_CELLS or LOM_NAV_METRES
+ * pairs and n_fields + 1 offsets into it: field i takes the goals [goal_offsets[i], goal_offsets[i + 1]).
+ *  1. Result.  Field i and summaries[i] are, byte for byte, what lom_navfield_solve gives for the same plane, parameters
+ *     and those goals: P, cells_blocked, cells_reached, cells_unreached, cells_invalid, goals_used (duplicates within a
+ *     field once), goals_rejected, range_exceeded and max_potential.  A field may have no goals (every cell unreached);
+ *     two fields may share goals, or have the same goals.  Each field is the unique fixed point of the navigation field's
+ *     relaxation and the fields share nothing but the read-only plane and table, so the bytes do not depend on the
+ *     schedule, on the number of fields solved beside it or on the test switches below.
+ *  2. Offsets.  n_fields is 0 .. max_fields.  The offsets start at 0, never fall, and end at n_goals <= 2^24; goals may be
+ *     NULL only where n_goals is 0.  Otherwise LOM_ERR_ARG.  n_fields == 0 is LOM_OK, reads neither offsets nor goals,
+ *     launches nothing and leaves a set of no fields.
+ *  3. Refusals.  A NULL plane, bad parameters, an unknown goal kind, bad offsets, or (from a clearance grid) a geometry
+ *     that is not bit for bit the set's or another device: LOM_ERR_ARG.  Every refusal comes before any device work,
+ *     changes nothing -- the fields, lom_navset_field_count and the counters of the last solve stay -- and zeroes the
+ *     first min(n_fields, max_fields) summaries.
+ *  4. Forms.  lom_navset_solve takes a host plane of width * height bytes; _solve_device a plane in HBM that is complete
+ *     when hip_event_or_null is (NULL: now); _solve_from_clearance takes lom_clearance_cost_device's plane and orders the
+ *     two streams by events in both directions.  The set keeps a copy of the plane.
+ * lom_navset_field_count gives the fields of the last solve, and 0 after create, lom_navset_clear or lom_navset_shift.  A
+ * solve with fewer fields than the one before leaves the fewer.  lom_navset_shift is the planning grids' shift: the geometry
+ * moves by the rule and the set becomes what a fresh, cleared set of the shifted geometry is.
+ *
+ * Fields.  Planar, [n_fields][height][width] u32 in lom_navfield_potential's form.  lom_navset_potential copies field i
+ * out; lom_navset_potential_device gives its place in HBM, valid until the next solve, clear or shift on the set.  An
+ * index outside 0 .. field_count - 1 is LOM_ERR_ARG.
+ *
+ * Gather.  n points, as cells or metres: out[i * n + j] is P of field i at point j, LOM_NAV_UNREACHED for a point outside
+ * the grid or not a number.  n <= 2^24 and field_count * n <= 2^28.  With the goals as the points this is the travel-cost
+ * matrix: out[i * n + j] is what it costs to go from goal j to the nearest goal of field i.  A step pays for the cell it
+ * leaves (navigation field, step 2), so the cost from a to b counts c[a] and not c[b], and the cost from b to a counts
+ * c[b] and not c[a]: the matrix is NOT symmetric unless the two end cells cost the same.
+ *
+ * Nearest.  Per cell, the least P over the fields and the least field index that attains it: owner_out (u16 per cell,
+ * LOM_NAVSET_NO_OWNER = 0xFFFF where no field reaches the cell), potential_out (u32 per cell, LOM_NAV_UNREACHED there)
+ * and cells_owned (u64 per field: the cells it owns); each may be NULL.  Invariant: potential_out is, byte for byte, P of
+ * the single lom_navfield_solve from the union of all fields' goals.  Before the first solve since create, clear or shift:
+ * LOM_ERR_STATE.  A set of no fields owns nothing: every owner is LOM_NAVSET_NO_OWNER.
+ *
+ * Paths.  lom_navfield_paths' walk (step 6) for n starts, start k on field field_of_start[k].  An index outside
+ * 0 .. field_count - 1 is LOM_ERR_ARG before any device work, and nothing is written.
+ *
+ * Adopt.  lom_navfield_adopt(f, s, i, summary_or_null), of the navigation field's own family, makes the navigation field f
+ * exactly what lom_navfield_solve of the set's plane, parameters and field i's goals would have left: P, the kept plane,
+ * the table, the solved state and the summary words.  Afterwards paths, waypoints, visible, query, resolve* and
+ * shift_resolve* on f give the bytes they give after the direct solve, and so do the consumers that take a lom_navfield
+ * (regions, visibility select, rollouts): the set needs no copy of them.  The copies stay in HBM and are ordered by the two
+ * handles' events.  A geometry that is not bit for bit the set's, another device or i outside 0 .. field_count - 1:
+ * LOM_ERR_ARG.  A set with no solve since create, clear or shift: LOM_ERR_STATE.  A refused call leaves f untouched and
+ * zeroes the summary.  lom_navfield_stats reads 0 launches and 0 waits after an adopt.
+ *
+ * Not part of this: a re-solve or a shift-resolve of a whole set (adopt a field and use the field's), waypoints on the set.
+ *
+ * Every argument is validated before any device work.  Every call returns with its work done.  Calls on one set are the
+ * caller's to serialise.  The error text is the set's (lom_navset_last_error). */
+typedef struct lom_navset lom_navset;
+typedef struct {
+    uint64_t launches, waits; /* of k_navset_relax in the last solve, and the host's waits for them */
+    uint64_t tiles;           /* workgroups per launch: tiles * fields */
+    uint64_t fields;          /* fields of the last solve */
+} lom_navset_solve_stats;
+#define LOM_NAVSET_NO_OWNER 0xFFFFu
+#define LOM_NAVSET_MAX_FIELDS 65535u
+enum {
+    LOM_NAVSET_OPT_TEST_INNER_CAP = 1, /* as LOM_NAV_OPT_TEST_INNER_CAP */
+    LOM_NAVSET_OPT_TEST_BATCH = 2,     /* launches per wait, as LOM_NAV_OPT_TEST_BATCH */
+    LOM_NAVSET_OPT_TEST_ALL_TILES = 3  /* every tile of every field in every launch.  Test switches: the bytes are the same. */
+};
+int lom_navset_create(const lom_occupancy_geometry *geometry, int device, size_t max_fields, lom_navset **out);
+void lom_navset_destroy(lom_navset *s);
+const char *lom_navset_last_error(const lom_navset *s); /* s == NULL: why the last create on this thread failed */
+int lom_navset_clear(lom_navset *s);                    /* no fields */
+/* the planning families' shift ("grid shift", below): the geometry moves by that rule, the state is lom_navset_clear's;
+ * LOM_ERR_RANGE from the rule leaves the set untouched */
+int lom_navset_shift(lom_navset *s, int32_t dx, int32_t dy);
+int lom_navset_get_geometry(const lom_navset *s, lom_occupancy_geometry *out);
+void *lom_navset_stream(lom_navset *s); /* hipStream_t */
+int lom_navset_device(const lom_navset *s);
+int lom_navset_wait_event(lom_navset *s, void *hip_event);
+int lom_navset_set_option(lom_navset *s, int option, int64_t value);
+size_t lom_navset_field_count(const lom_navset *s); /* s == NULL: 0 */
+/* goals: goal_offsets[n_fields] pairs of goal_kind in host memory; goal_offsets: n_fields + 1 u32 in host memory;
+ * summaries_or_null: n_fields of them */
+int lom_navset_solve(lom_navset *s, const int8_t *plane, const lom_navfield_params *params, int goal_kind, const void *goals,
+                     const uint32_t *goal_offsets, size_t n_fields, lom_navfield_summary *summaries_or_null);
+int lom_navset_solve_device(lom_navset *s, const int8_t *d_plane, void *hip_event_or_null, const lom_navfield_params *params,
+                            int goal_kind, const void *goals, const uint32_t *goal_offsets, size_t n_fields,
+                            lom_navfield_summary *summaries_or_null);
+int lom_navset_solve_from_clearance(lom_navset *s, lom_clearance *clearance, const lom_navfield_params *params, int goal_kind,
+                                    const void *goals, const uint32_t *goal_offsets, size_t n_fields,
+                                    lom_navfield_summary *summaries_or_null);
+/* P of field i over the whole grid, row-major: at most `cap` cells go to `out` (may be NULL with cap 0) */
+int lom_navset_potential(lom_navset *s, size_t i, uint32_t *out, size_t cap);
+/* the same, left in HBM: width * height cells, valid until the next solve, clear or shift on the set */
+int lom_navset_potential_device(lom_navset *s, size_t i, const uint32_t **d_out);
+/* points: n pairs of point_kind in host memory; out: [field_count, n] u32 */
+int lom_navset_gather(lom_navset *s, int point_kind, const void *points, size_t n, uint32_t *out);
+/* owner_out: width * height u16; potential_out: width * height u32; cells_owned: field_count u64; each may be NULL */
+int lom_navset_nearest(lom_navset *s, uint16_t *owner_out_or_null, uint32_t *potential_out_or_null, uint64_t *cells_owned_or_null);
+/* field_of_start: n_starts int32 in host memory; the rest as lom_navfield_paths */
+int lom_navset_paths(lom_navset *s, const int32_t *field_of_start, int start_kind, const void *starts, size_t n_starts,
+                     uint16_t *cells_out, size_t cap, uint32_t *lengths_out);
+/* the launches, waits, workgroups per launch and fields of the last solve (zeros before the first, and for no fields) */
+int lom_navset_stats(const lom_navset *s, lom_navset_solve_stats *out);
+/* field i of the set becomes the navigation field f ("Adopt", above) */
+int lom_navfield_adopt(lom_navfield *f, lom_navset *s, size_t i, lom_navfield_summary *summary_or_null);
+
 /* ---- frontier regions: connected cells labelled on the device, ranked goals (not in the reference) ----------------------
  * The navigation field answers what it costs to get somewhere.  This handle family answers where to go: it labels the
  * connected regions of a grid plane -- the frontier cells of an occupancy plane (FREE next to UNKNOWN, as an explorer

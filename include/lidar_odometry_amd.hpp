@@ -656,7 +656,12 @@ public:
     void waitEvent(void *hip_event) { this->check(WaitEvent(this->h_, hip_event)); }
 
 protected:
-    GridHandle(const G &geometry, int device) { this->created(Create(&geometry, device, &this->h_)); }
+    // (extra: what a family's create takes between the device and the handle -- a NavFieldSet's max_fields)
+    template <typename... Extra>
+    GridHandle(const G &geometry, int device, Extra... extra)
+    {
+        this->created(Create(&geometry, device, extra..., &this->h_));
+    }
     size_t cellCount() const
     {
         const G g = geometry();
@@ -1159,6 +1164,8 @@ inline NavFieldWaypointParams navfieldWaypointParams(uint32_t max_cell_cost, uin
     return NavFieldWaypointParams{max_cell_cost, lookahead, route_cap, flags};
 }
 
+class NavFieldSet;  // below
+
 class NavField
     : public GridHandle<lom_navfield, lom_occupancy_geometry, lom_navfield_create, lom_navfield_destroy, lom_navfield_last_error,
                         lom_navfield_get_geometry, lom_navfield_clear, lom_navfield_shift, lom_navfield_set_option, lom_navfield_device, lom_navfield_stream,
@@ -1302,6 +1309,8 @@ public:
         check(lom_navfield_stats(h_, &s));
         return s;
     }
+    // this field becomes what solve() of the plane, parameters and goals of field i of a set of this geometry would have left
+    inline lom_navfield_summary adopt(NavFieldSet &set, size_t i);
 };
 
 inline std::vector<uint32_t> navfieldCellCosts(const lom_navfield_params &params)
@@ -1310,6 +1319,92 @@ inline std::vector<uint32_t> navfieldCellCosts(const lom_navfield_params &params
     const int rc = lom_navfield_cell_costs(&params, out.data());
     if (rc != LOM_OK) throw Error(rc, "navigation field cell costs: bad parameters");
     return out;
+}
+
+// ---- NavFieldSet (not in the reference) ------------------------------------------------
+// N navigation fields over one cost plane, solved side by side in one call: field i and its summary are byte for byte what
+// NavField::solve() gives for the goals [goal_offsets[i], goal_offsets[i + 1]) of one goal array.  gather() reads every
+// field at points (with the goals as the points: the travel-cost matrix, which need not be symmetric -- a step pays for
+// the cell it leaves), nearest() partitions the grid by nearest goal, paths() walks down a named field, NavField::adopt()
+// makes one field a NavField.  Definitions: lidar_odometry_amd.h ("navigation field set").
+class NavFieldSet
+    : public GridHandle<lom_navset, lom_occupancy_geometry, lom_navset_create, lom_navset_destroy, lom_navset_last_error, lom_navset_get_geometry,
+                        lom_navset_clear, lom_navset_shift, lom_navset_set_option, lom_navset_device, lom_navset_stream, lom_navset_wait_event> {
+public:
+    struct Nearest {  // owner: LOM_NAVSET_NO_OWNER where no field reaches the cell; cells_owned: per field
+        std::vector<uint16_t> owner;
+        std::vector<uint32_t> potential;
+        std::vector<uint64_t> cells_owned;
+    };
+
+    NavFieldSet(const lom_occupancy_geometry &geometry, size_t max_fields, int device = 0) : GridHandle(geometry, device, max_fields) {}
+    size_t size() const { return cellCount(); }
+    size_t fieldCount() const { return lom_navset_field_count(h_); }
+    // a host plane of size() cells; goals: goal_offsets[n_fields] pairs of goal_kind; goal_offsets: n_fields + 1 values
+    std::vector<lom_navfield_summary> solve(const int8_t *plane, const lom_navfield_params &params, int goal_kind, const void *goals,
+                                            const uint32_t *goal_offsets, size_t n_fields)
+    {
+        std::vector<lom_navfield_summary> s(n_fields);
+        check(lom_navset_solve(h_, plane, &params, goal_kind, goals, goal_offsets, n_fields, s.data()));
+        return s;
+    }
+    // ... a plane in HBM that is complete when hip_event is (NULL: now)
+    std::vector<lom_navfield_summary> solveDevice(const int8_t *d_plane, void *hip_event, const lom_navfield_params &params, int goal_kind,
+                                                  const void *goals, const uint32_t *goal_offsets, size_t n_fields)
+    {
+        std::vector<lom_navfield_summary> s(n_fields);
+        check(lom_navset_solve_device(h_, d_plane, hip_event, &params, goal_kind, goals, goal_offsets, n_fields, s.data()));
+        return s;
+    }
+    // ... the plane a ClearanceGrid of this geometry left in HBM
+    std::vector<lom_navfield_summary> solveFromClearance(ClearanceGrid &clearance, const lom_navfield_params &params, int goal_kind,
+                                                         const void *goals, const uint32_t *goal_offsets, size_t n_fields)
+    {
+        std::vector<lom_navfield_summary> s(n_fields);
+        check(lom_navset_solve_from_clearance(h_, clearance.handle(), &params, goal_kind, goals, goal_offsets, n_fields, s.data()));
+        return s;
+    }
+    std::vector<uint32_t> potential(size_t i)
+    {
+        std::vector<uint32_t> out(size());
+        check(lom_navset_potential(h_, i, out.data(), out.size()));
+        return out;
+    }
+    // [fieldCount(), n]: P of every field at n points of point_kind
+    std::vector<uint32_t> gather(int point_kind, const void *points, size_t n)
+    {
+        std::vector<uint32_t> out(fieldCount() * n);
+        check(lom_navset_gather(h_, point_kind, points, n, out.data()));
+        return out;
+    }
+    Nearest nearest()
+    {
+        Nearest r;
+        r.owner.resize(size()), r.potential.resize(size()), r.cells_owned.assign(fieldCount(), 0);
+        check(lom_navset_nearest(h_, r.owner.data(), r.potential.data(), r.cells_owned.data()));
+        return r;
+    }
+    // NavField::paths()' walk, start k down field field_of_start[k]
+    NavField::Paths paths(const int32_t *field_of_start, int start_kind, const void *starts, size_t n, size_t cap)
+    {
+        NavField::Paths p;
+        p.cells.assign(n * cap * 2, 0), p.lengths.assign(n, 0);
+        check(lom_navset_paths(h_, field_of_start, start_kind, starts, n, p.cells.data(), cap, p.lengths.data()));
+        return p;
+    }
+    lom_navset_solve_stats stats() const
+    {
+        lom_navset_solve_stats s;
+        check(lom_navset_stats(h_, &s));
+        return s;
+    }
+};
+
+inline lom_navfield_summary NavField::adopt(NavFieldSet &set, size_t i)
+{
+    lom_navfield_summary s;
+    check(lom_navfield_adopt(h_, set.handle(), i, &s));
+    return s;
 }
 
 // ---- RegionGrid (not in the reference) -------------------------------------------------

@@ -1325,7 +1325,7 @@ class ElevationGrid(_PosedScanGrid):
 
 
 class _PlaneGrid(_Grid):
-    """What ClearanceGrid, NavField, RegionGrid, VisibilityGrid and RolloutGrid share (csrc/plane_handle.hpp): a dense 2-D grid of one
+    """What ClearanceGrid, NavField, NavFieldSet, RegionGrid, VisibilityGrid and RolloutGrid share (csrc/plane_handle.hpp): a dense 2-D grid of one
     lom_occupancy_geometry that takes planes of shape (height, width)."""
 
     _shape_text = "expected an int8 array of shape (height, width)"
@@ -1569,6 +1569,108 @@ class NavField(_PlaneGrid):
     def stats(self):
         """capi.NavFieldSolveStats of the last solve as a dict: launches, waits, tiles"""
         st = capi.NavFieldSolveStats()
+        self._check(self._call("stats", self._h, C.byref(st)))
+        return st.asdict()
+
+    def adopt(self, fieldset, i):
+        """lom_navfield_adopt: this field becomes what solve() of the plane, parameters and goals of field `i` of a
+        NavFieldSet of this geometry would have left; paths(), waypoints(), resolve() and the consumers that take a NavField
+        then read it.  Returns capi.NavFieldSummary as a dict."""
+        sm = capi.NavFieldSummary()
+        self._check(self._call("adopt", self._h, fieldset.handle, int(i), C.byref(sm)))
+        return sm.asdict()
+
+
+class NavFieldSet(_PlaneGrid):
+    """N navigation fields over one cost plane, solved in one call (lom_navset_*, include/lidar_odometry_amd.h "navigation
+    field set"): solve() takes a plane, one parameter set and a list of goal arrays, one per field; field i and its summary
+    are byte for byte what NavField.solve() gives for goals_per_field[i].  gather() reads every field at points (with the
+    goals as points: the travel-cost matrix), nearest() gives the partition of the grid by nearest goal, paths() walks down a
+    named field, NavField.adopt() makes one field a NavField.  Goals, starts and points are as NavField's."""
+
+    _family = "navset"
+
+    def __init__(self, resolution, origin_xy, width, height, max_fields, device=0):
+        geo = capi.OccupancyGeometry(float(resolution), float(origin_xy[0]), float(origin_xy[1]), int(width), int(height))
+        self._create(C.byref(geo), int(device), int(max_fields))
+        self.width, self.height, self.max_fields = int(geo.width), int(geo.height), int(max_fields)
+
+    @staticmethod
+    def _goals(goals_per_field, metres):
+        """(kind, contiguous (n, 2) array of all goals, uint32 offsets (n_fields + 1,))"""
+        per = [NavField._points(g, metres)[1] for g in goals_per_field]
+        offsets = np.zeros(len(per) + 1, np.uint32)
+        offsets[1:] = np.cumsum([len(g) for g in per])
+        kind, empty = NavField._points(np.zeros((0, 2)), metres)
+        return kind, np.ascontiguousarray(np.concatenate(per)) if per else empty, offsets
+
+    def _solve(self, name, head, params, goals_per_field, metres):
+        p = navfieldParams(params)
+        kind, g, offsets = self._goals(goals_per_field, metres)
+        n = len(offsets) - 1
+        sm = (capi.NavFieldSummary * max(n, 1))()
+        self._check(self._call(name, self._h, *head, C.byref(p), kind, g.ctypes.data, offsets.ctypes.data, n, sm))
+        return [sm[i].asdict() for i in range(n)]
+
+    def solve(self, plane, params, goals_per_field, metres=False):
+        """lom_navset_solve: a host plane and one goal array per field.  Returns a list of capi.NavFieldSummary dicts."""
+        plane = self._plane(plane, np.int8)
+        return self._solve("solve", (plane.ctypes.data,), params, goals_per_field, metres)
+
+    def solveDevice(self, d_plane, params, goals_per_field, metres=False, hip_event=None):
+        """lom_navset_solve_device: `d_plane` is a device pointer to a plane in HBM, complete when `hip_event` is"""
+        return self._solve("solve_device", (d_plane, hip_event), params, goals_per_field, metres)
+
+    def solveFromClearance(self, clearance, params, goals_per_field, metres=False):
+        """lom_navset_solve_from_clearance: the cost plane a ClearanceGrid of this geometry left in HBM"""
+        return self._solve("solve_from_clearance", (clearance.handle,), params, goals_per_field, metres)
+
+    def fieldCount(self):
+        """the fields of the last solve; 0 after create, clear() or shift()"""
+        return int(self._call("field_count", self._h))
+
+    def potential(self, i):
+        """uint32 array of shape (height, width): P of field i"""
+        out = np.empty((self.height, self.width), np.uint32)
+        self._check(self._call("potential", self._h, int(i), out.ctypes.data, out.size))
+        return out
+
+    def potentialDevice(self, i):
+        """the device pointer of field i, valid until the next solve(), clear() or shift()"""
+        p = C.c_void_p()
+        self._check(self._call("potential_device", self._h, int(i), C.byref(p)))
+        return p.value
+
+    def gather(self, points, metres=False):
+        """uint32 (fieldCount(), n): P of every field at every point, capi.NAV_UNREACHED outside the grid.  With the goals
+        as the points this is the travel-cost matrix; a step pays for the cell it leaves, so it need not be symmetric."""
+        kind, q = NavField._points(points, metres)
+        out = np.empty((self.fieldCount(), len(q)), np.uint32)
+        self._check(self._call("gather", self._h, kind, q.ctypes.data, len(q), out.ctypes.data))
+        return out
+
+    def nearest(self):
+        """(owner uint16 (height, width), potential uint32 (height, width), cells_owned uint64 (fieldCount(),)): per cell the
+        least P over the fields and the least field index that attains it, capi.NAVSET_NO_OWNER where none reaches it"""
+        owner, potential = np.empty((self.height, self.width), np.uint16), np.empty((self.height, self.width), np.uint32)
+        owned = np.zeros(self.fieldCount(), np.uint64)
+        self._check(self._call("nearest", self._h, owner.ctypes.data, potential.ctypes.data, owned.ctypes.data))
+        return owner, potential, owned
+
+    def paths(self, field_of_start, starts, cap, metres=False):
+        """(cells uint16 (K, cap, 2), lengths uint32 (K,)): NavField.paths()' walk, start k down field field_of_start[k]"""
+        kind, s = NavField._points(starts, metres)
+        which = np.ascontiguousarray(field_of_start, np.int32).reshape(-1)
+        if len(which) != len(s):
+            raise ValueError("one field index per start")
+        cells, lengths = np.zeros((len(s), int(cap), 2), np.uint16), np.zeros(len(s), np.uint32)
+        self._check(self._call("paths", self._h, which.ctypes.data, kind, s.ctypes.data, len(s), cells.ctypes.data, int(cap),
+                               lengths.ctypes.data))
+        return cells, lengths
+
+    def stats(self):
+        """capi.NavSetSolveStats of the last solve as a dict: launches, waits, tiles (workgroups per launch), fields"""
+        st = capi.NavSetSolveStats()
         self._check(self._call("stats", self._h, C.byref(st)))
         return st.asdict()
 

@@ -400,6 +400,19 @@ NAV_OPT_TEST_INNER_CAP, NAV_OPT_TEST_BATCH, NAV_OPT_TEST_ALL_TILES, NAV_OPT_TEST
 NAV_OPT_TEST_SHORTCUT_SERIAL = 5
 
 
+class NavSetSolveStats(C.Structure):
+    """lom_navset_solve_stats"""
+    _fields_ = [("launches", C.c_uint64), ("waits", C.c_uint64), ("tiles", C.c_uint64), ("fields", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(NavSetSolveStats) == 32
+NAVSET_NO_OWNER, NAVSET_MAX_FIELDS = 0xFFFF, 65535
+NAVSET_OPT_TEST_INNER_CAP, NAVSET_OPT_TEST_BATCH, NAVSET_OPT_TEST_ALL_TILES = 1, 2, 3
+
+
 class RegionsParams(C.Structure):
     """lom_regions_params"""
     _fields_ = [("kind", C.c_int32), ("lo", C.c_int8), ("hi", C.c_int8), ("max_cost", C.c_int8), ("min_cells", C.c_uint32),
@@ -825,6 +838,19 @@ PROTOTYPES = {
     "lom_navfield_waypoints": (_int, [_vp, _int, _vp, _size, _P(NavFieldWaypointParams), _vp, _size, _vp, _vp]),
     "lom_navfield_cell_costs": (_int, [_P(NavFieldParams), _vp]),
     "lom_navfield_stats": (_int, [_vp, _P(NavFieldSolveStats)]),
+    "lom_navfield_adopt": (_int, [_vp, _vp, _size, _P(NavFieldSummary)]),
+    **_grid_family("navset", OccupancyGeometry),
+    "lom_navset_create": (_int, [_P(OccupancyGeometry), _int, _size, _P(_vp)]),
+    "lom_navset_field_count": (_size, [_vp]),
+    "lom_navset_solve": (_int, [_vp, _vp, _P(NavFieldParams), _int, _vp, _vp, _size, _P(NavFieldSummary)]),
+    "lom_navset_solve_device": (_int, [_vp, _vp, _vp, _P(NavFieldParams), _int, _vp, _vp, _size, _P(NavFieldSummary)]),
+    "lom_navset_solve_from_clearance": (_int, [_vp, _vp, _P(NavFieldParams), _int, _vp, _vp, _size, _P(NavFieldSummary)]),
+    "lom_navset_potential": (_int, [_vp, _size, _vp, _size]),
+    "lom_navset_potential_device": (_int, [_vp, _size, _P(_vp)]),
+    "lom_navset_gather": (_int, [_vp, _int, _vp, _size, _vp]),
+    "lom_navset_nearest": (_int, [_vp, _vp, _vp, _vp]),
+    "lom_navset_paths": (_int, [_vp, _vp, _int, _vp, _size, _vp, _size, _vp]),
+    "lom_navset_stats": (_int, [_vp, _P(NavSetSolveStats)]),
     # ---- frontier regions
     **_grid_family("regions", OccupancyGeometry),
     "lom_regions_extract": (_int, [_vp, _vp, _vp, _vp, _P(RegionsParams), _P(RegionsSummary)]),

@@ -50,6 +50,45 @@ __device__ __forceinline__ bool nav_step_allowed(const int8_t *__restrict__ plan
     return d < 4u || (nav_cost_at(plane, table, width, height, bx, y) && nav_cost_at(plane, table, width, height, x, by));
 }
 
+// Step 6, the serial walk of one lane down a field from (x, y).  From cell a the first b in the fixed order with an allowed
+// step and P[b] + len * c[a] == P[a]; at the fixed point one exists, and P falls strictly, so the walk ends within n_cells
+// steps.  out: `cap` u16 pairs, the first `cap` cells of the path.  Returns the full length, start and goal counted, 0 for a
+// start that is not walked.  k_nav_trace and k_navset_trace (k_navset.hpp) call it.
+__device__ __forceinline__ uint32_t nav_walk(const int8_t *__restrict__ plane, const uint32_t *__restrict__ table,
+                                             const uint32_t *__restrict__ field, NavArgs a, int x, int y, uint32_t cap, uint16_t *out)
+{
+    const uint32_t n_cells = a.width * a.height;
+    uint32_t len = 0u;
+    if (x >= 0 && y >= 0 && x < (int)a.width && y < (int)a.height) {
+        uint32_t p = field[(size_t)y * a.width + (uint32_t)x];
+        while (p != kNavUnreached) {
+            if (len < cap) {
+                uint16_t *const o = out + (size_t)len * 2u;
+                o[0] = (uint16_t)x, o[1] = (uint16_t)y;
+            }
+            len++;
+            if (p == 0u || len >= n_cells) break;
+            const uint32_t c = nav_cost_at(plane, table, a.width, a.height, x, y);
+            uint32_t next = kNavUnreached;
+            for (uint32_t d = 0; d < 8u; d++) {
+                if (!nav_step_allowed(plane, table, a.width, a.height, x, y, d)) continue;
+                const int bx = x + nav_dx(d), by = y + nav_dy(d);
+                const uint32_t pb = field[(size_t)by * a.width + (uint32_t)bx], w = nav_len(d) * c;
+                if (pb <= kNavMax - w && pb + w == p) {
+                    x = bx, y = by, next = pb;
+                    break;
+                }
+            }
+            p = next;  // (unreached: no step fits -- never at the fixed point; the walk ends)
+        }
+    }
+    return len;
+}
+
+// The kernels of a lom_navfield.  A translation unit that only wants the device functions above for kernels of its own
+// (navset.hip, through k_navset.hpp) defines LOM_NAV_DEVICE_FUNCTIONS_ONLY: a kernel is instantiated in one place.
+#ifndef LOM_NAV_DEVICE_FUNCTIONS_ONLY
+
 // create, clear and the start of a solve: every cell unreached, no tile marked in either mark array
 __global__ __launch_bounds__(kNavThreads) void k_nav_fill(uint32_t n_cells, uint32_t n_marks, uint32_t *field, uint32_t *marks)
 {
@@ -110,6 +149,12 @@ __global__ __launch_bounds__(kNavThreads) void k_nav_seed(const int8_t *__restri
 //
 // inner_cap bounds the sweeps of a launch; a tile that stops there marks itself.  all_tiles (a test switch) runs every
 // tile in every launch.  *flag is set iff the launch marked a tile.
+//
+// nav_relax_tile (k_navset.hpp) is this body as a device function, for field blockIdx.z of a set, and the argument covers
+// it as well: the fields of a set share nothing but the read-only plane and table -- each has its own P and its own mark
+// words, and the one flag of a launch is only ever set.  This kernel keeps its own text: built through the shared function
+// it took 40 VGPRs where profiles/navfield_kernel_resources.txt records 48, and its resources are not to move.  A change to
+// one body is a change to both.
 __global__ __launch_bounds__(kNavThreads) void k_nav_relax(const int8_t *__restrict__ plane, const uint32_t *__restrict__ table, NavArgs a,
                                                            uint32_t inner_cap, uint32_t all_tiles, uint32_t *field, uint32_t *marks_cur,
                                                            uint32_t *marks_nxt, uint32_t *flag)
@@ -259,10 +304,8 @@ __global__ __launch_bounds__(kNavThreads) void k_nav_report(const int8_t *__rest
     }
 }
 
-// Step 6, a lane per start (cells; (-1, -1) where a start in metres is outside): the serial walk down the field.  From
-// cell a the first b in the fixed order with an allowed step and P[b] + len * c[a] == P[a]; at the fixed point one
-// exists, and P falls strictly, so the walk ends within n_cells steps.  out: [K, cap] u16 pairs, the first `cap` cells of
-// a path; lengths[k]: the full length, start and goal counted, 0 for a start that is not walked.
+// Step 6, a lane per start (cells; (-1, -1) where a start in metres is outside).  out: [K, cap] u16 pairs; lengths[k]: the
+// full length.
 __global__ __launch_bounds__(kNavThreads) void k_nav_trace(const int8_t *__restrict__ plane, const uint32_t *__restrict__ table,
                                                            const uint32_t *__restrict__ field, NavArgs a,
                                                            const int32_t *__restrict__ starts, uint32_t K, uint32_t cap, uint16_t *out,
@@ -270,33 +313,7 @@ __global__ __launch_bounds__(kNavThreads) void k_nav_trace(const int8_t *__restr
 {
     const uint32_t k = blockIdx.x * kNavThreads + threadIdx.x;
     if (k >= K) return;
-    int x = starts[2 * (size_t)k], y = starts[2 * (size_t)k + 1];
-    const uint32_t n_cells = a.width * a.height;
-    uint32_t len = 0u;
-    if (x >= 0 && y >= 0 && x < (int)a.width && y < (int)a.height) {
-        uint32_t p = field[(size_t)y * a.width + (uint32_t)x];
-        while (p != kNavUnreached) {
-            if (len < cap) {
-                uint16_t *const o = out + ((size_t)k * cap + len) * 2u;
-                o[0] = (uint16_t)x, o[1] = (uint16_t)y;
-            }
-            len++;
-            if (p == 0u || len >= n_cells) break;
-            const uint32_t c = nav_cost_at(plane, table, a.width, a.height, x, y);
-            uint32_t next = kNavUnreached;
-            for (uint32_t d = 0; d < 8u; d++) {
-                if (!nav_step_allowed(plane, table, a.width, a.height, x, y, d)) continue;
-                const int bx = x + nav_dx(d), by = y + nav_dy(d);
-                const uint32_t pb = field[(size_t)by * a.width + (uint32_t)bx], w = nav_len(d) * c;
-                if (pb <= kNavMax - w && pb + w == p) {
-                    x = bx, y = by, next = pb;
-                    break;
-                }
-            }
-            p = next;  // (unreached: no step fits -- never at the fixed point; the walk ends)
-        }
-    }
-    lengths[k] = len;
+    lengths[k] = nav_walk(plane, table, field, a, starts[2 * (size_t)k], starts[2 * (size_t)k + 1], cap, out + (size_t)k * cap * 2u);
 }
 
 // Step 7, a lane per point: the cell by the floor rule (f64 from the f32 values, compared before any conversion) and its
@@ -313,5 +330,7 @@ __global__ __launch_bounds__(kNavThreads) void k_nav_query(const float *__restri
     if (qx >= 0.0 && qx < (double)a.width && qy >= 0.0 && qy < (double)a.height) p = field[(size_t)(uint32_t)qy * a.width + (uint32_t)qx];
     out[i] = p;
 }
+
+#endif  // LOM_NAV_DEVICE_FUNCTIONS_ONLY
 
 }  // namespace lom

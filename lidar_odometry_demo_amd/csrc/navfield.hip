@@ -15,7 +15,9 @@
 #include "k_navfield_resolve.hpp"
 #include "k_navfield_shift.hpp"
 #include "k_navfield_waypoints.hpp"
+#include "nav_fixed_point.hpp"
 #include "navfield_host.hpp"
+#include "navset_host.hpp"
 #include "plane_handle.hpp"
 
 using namespace lom;
@@ -109,37 +111,11 @@ int upload_points(lom_navfield *f, int kind, const void *pts, size_t n, std::vec
     return LOM_OK;
 }
 
-// A fixed point over tiles, in batches of launches with one wait each.  Launch k reads the marks of parity k & 1 and
-// writes the others: launch(cur, nxt, flag) enqueues it.  A launch behind the fixed point finds no active tile (or, with
-// all tiles, changes nothing) and marks nothing, so the batch may run ahead of what the host knows.  Both arrays are
-// clear when this returns LOM_OK.
-template <class Launch>
-int to_fixed_point(lom_navfield *f, uint64_t &launches, uint64_t &waits, const char *unsettled, Launch launch)
-{
-    uint32_t *const marks = f->marks.as<uint32_t>();
-    const uint64_t bound = navfield::launch_bound(f->geo.width, f->geo.height);
-    const uint32_t B = f->batch;
-    for (;;) {
-        LOM_HIP(f, hipMemsetAsync(f->flags.p, 0, (size_t)B * 4, f->stream));
-        for (uint32_t j = 0; j < B; j++) {
-            const uint32_t parity = (uint32_t)(launches & 1u);
-            launch(marks + (size_t)parity * f->tiles.n_tiles, marks + (size_t)(parity ^ 1u) * f->tiles.n_tiles, f->flags.as<uint32_t>() + j);
-            LOM_HIP(f, hipGetLastError());
-            launches++;
-        }
-        LOM_HIP(f, hipMemcpyAsync(f->h_flags.h, f->flags.p, (size_t)B * 4, hipMemcpyDeviceToHost, f->stream));
-        LOM_HIP(f, hipStreamSynchronize(f->stream));
-        waits++;
-        if (f->h_flags.as<uint32_t>()[B - 1u] == 0u) return LOM_OK;  // the last launch marked nothing: the fixed point
-        if (launches > bound) return fail(f, LOM_ERR_HIP, unsettled);
-    }
-}
-
 // the relaxation from the marks of the first array to its fixed point
 int relax(lom_navfield *f, uint64_t &launches, uint64_t &waits)
 {
     const NavArgs a = f->args();
-    return to_fixed_point(f, launches, waits, "navigation field: the relaxation did not settle", [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
+    return to_fixed_point(f, f->tiles.n_tiles, launches, waits, "navigation field: the relaxation did not settle", [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
         hipLaunchKernelGGL(k_nav_relax, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0, f->stream, f->plane.as<const int8_t>(),
                            f->table.as<const uint32_t>(), a, f->inner_cap, f->all_tiles, f->field.as<uint32_t>(), cur, nxt, flag);
     });
@@ -230,7 +206,7 @@ int resolve_on_device(lom_navfield *f, const int8_t *d_new, const clearance::Rec
     const uint32_t rejected = h[NW_GOALS_REJECTED];
     if (st.cells_changed != 0u) {
         if (form == 0u) {
-            const int rc = to_fixed_point(f, st.raise_launches, st.waits, "navigation field: the raise phase did not settle",
+            const int rc = to_fixed_point(f, f->tiles.n_tiles, st.raise_launches, st.waits, "navigation field: the raise phase did not settle",
                                           [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
                                               hipLaunchKernelGGL(k_nav_raise, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0,
                                                                  f->stream, f->plane.as<const int8_t>(), table, a, f->inner_cap, f->all_tiles,
@@ -345,7 +321,7 @@ int shift_resolve_on_device(lom_navfield *f, const navfield::ShiftPlan &plan, co
     const uint32_t rejected = h[NW_GOALS_REJECTED], left = h[SW_GOALS_LEFT];
     f->shift_stats = lom_navfield_shift_counters{plan.cells_kept, h[SW_ENTERED], left};
     if (raise) {
-        const int rc = to_fixed_point(f, st.raise_launches, st.waits, "navigation field: the raise phase did not settle",
+        const int rc = to_fixed_point(f, f->tiles.n_tiles, st.raise_launches, st.waits, "navigation field: the raise phase did not settle",
                                       [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
                                           hipLaunchKernelGGL(k_nav_raise, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0,
                                                              f->stream, f->plane.as<const int8_t>(), table, a, f->inner_cap, f->all_tiles,
@@ -758,6 +734,38 @@ int lom_navfield_shift_stats(const lom_navfield *f, lom_navfield_shift_counters 
     if (!f || !out) return LOM_ERR_ARG;
     *out = f->shift_stats;
     return LOM_OK;
+}
+
+// Field i of a set becomes this field: what lom_navfield_solve of the set's plane, parameters and field i's goals leaves.
+// Three copies within HBM behind the set's stream, released to it behind done_ev; the marks are clear after any solve.
+int lom_navfield_adopt(lom_navfield *f, lom_navset *set, size_t i, lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (!set) return fail(f, LOM_ERR_ARG, "navigation field adopt: a navigation field set");
+    lom_occupancy_geometry g{};
+    (void)lom_navset_get_geometry(set, &g);
+    int rc = plane_check_producer(f, kName, "navigation field set", g, lom_navset_device(set));
+    if (rc != LOM_OK) return rc;
+    NavSetView v{};
+    if ((rc = navset_view(set, i, &v)) != LOM_OK) return fail(f, rc, lom_navset_last_error(set));
+    LOM_HIP(f, hipSetDevice(f->device));
+    if ((rc = plane_read_behind(f, 0, v.stream)) != LOM_OK) return rc;
+    f->solved = false;
+    LOM_HIP(f, hipMemcpyAsync(f->field.p, v.field, f->n_cells() * 4, hipMemcpyDeviceToDevice, f->stream));
+    LOM_HIP(f, hipMemcpyAsync(f->plane.p, v.plane, f->n_cells(), hipMemcpyDeviceToDevice, f->stream));
+    LOM_HIP(f, hipMemcpyAsync(f->table.p, v.table, 256 * 4, hipMemcpyDeviceToDevice, f->stream));
+    LOM_HIP(f, hipMemsetAsync(f->marks.p, 0, (size_t)2 * f->tiles.n_tiles * 4, f->stream));
+    LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    const lom_navfield_summary &m = v.summary;
+    const uint64_t words[NW_COUNT] = {m.cells_blocked, m.cells_reached, m.cells_unreached, m.cells_invalid, m.goals_used, m.goals_rejected,
+                                      m.range_exceeded, m.max_potential};  // in the order of the NW_ words
+    for (uint32_t k = 0; k < NW_COUNT; k++) f->last_words[k] = (uint32_t)words[k];
+    f->stats = lom_navfield_solve_stats{0, 0, f->tiles.n_tiles};
+    f->solved = true;
+    if (summary) *summary = m;
+    return plane_release(f, kName, set, lom_navset_wait_event, "lom_navset_wait_event");
 }
 
 }  // extern "C"
