@@ -2519,6 +2519,153 @@ lom_regions_shift_fn lom_regions_shift;
 lom_visibility_shift_fn lom_visibility_shift;
 lom_rollout_shift_fn lom_rollout_shift;
 
+/* ---- pose field: cost-to-go over cell and heading under a footprint (not in the reference) ---------------------------
+ * The navigation field is solved for a point: a robot that is longer than wide is routed round bends it cannot turn in, and
+ * the rollouts, which do test a footprint at a heading, then find every candidate blocked.  This handle family solves the
+ * field over states (cell, heading) for the robot's own footprint, with eight headings and unit primitives: the smallest
+ * exact form of kinodynamic planning.  Nothing is launched unless a caller creates a pose field.  The definition, operation
+ * by operation (tests/posefield_ref.py restates it with a heap Dijkstra on Python integers; everything is an integer and
+ * the field is the unique fixed point of a relaxation with positive weights, so every comparison is exact):
+ *
+ * Grid.  lom_occupancy_geometry with the navigation field's rules and limits.  A cell costs 70 bytes of HBM: P and L at 32
+ * bytes each (u32 per heading), the floor at 5 (u32 and the heading byte), the kept cost byte at 1.
+ *
+ * Input of a solve.  One full-grid int8 cost plane; lom_posefield_params: nav, a lom_navfield_params under its own rule;
+ * turn_cost, spin_cost, reverse_cost, each at most 2^24 - 1, spin_cost >= 1 under LOM_POSE_SPIN; flags of LOM_POSE_SPIN |
+ * LOM_POSE_REVERSE only; anything else is LOM_ERR_ARG.  c[] is exactly the table of lom_navfield_cell_costs(nav): 0 means
+ * impassable, and cells outside the grid are impassable.
+ *  1. Headings.  H = 8.  Heading h points along (hx, hy) = E, NE, N, NW, W, SW, S, SE for h = 0 .. 7: counter-clockwise,
+ *     +x is E and +y is N.  len(h) = 5 for an even h, 7 for an odd h.  In the rollouts' angle units heading h is the angle
+ *     8192 h, and the heading of an angle a is ((a + 4096) >> 13) & 7 (lom_posefield_heading_of_angle).
+ *  2. Footprint and stencils.  F samples (int32 fx, fy) in 1/256 cell in the robot's frame, with the rollouts' limits: 1 <=
+ *     F <= 1024, |fx|, |fy| <= 16384; anything else is LOM_ERR_ARG.  Per heading, with b = 512 h and (C, S) of
+ *     lom_visibility_table(4096), the rollouts' step 2 at angle 8192 h:  ox = (fx * C[b] - fy * S[b] + 128) >> 8,  oy =
+ *     (fx * S[b] + fy * C[b] + 128) >> 8, and the sample's cell offset is ((16384 + ox) >> 15, (16384 + oy) >> 15)
+ *     (arithmetic shifts): the cell a rollout reads for that sample at a pose on a cell's centre.  The distinct cell
+ *     offsets of a heading, sorted by (dy, dx), are its stencil; the host builds it.  lom_posefield_stencils gives the
+ *     eight without a handle or a device.  An offset reaches up to 91 cells.
+ *  3. Layers.  L[h][cell], u32: 0 if any stencil cell of h around the cell lies outside the grid or has c == 0, else the
+ *     greatest c over the stencil.  A state (cell, h) is passable iff L[h][cell] != 0.  lom_posefield_layers reads them.
+ *  4. Moves, from state (a, h) with s = L[h][a] != 0 and d(h) = (hx, hy).  A translation along +-d(h) to b is allowed iff
+ *     L[h][b] != 0 and, for an odd h, L[h] != 0 at the two cells that share an edge with both a and b (the side cells are
+ *     tested in the source heading's layer).  A rotation at cell b from h to h' = h +- 1 (mod 8) is allowed iff L[h][b] != 0
+ *     and L[h'][b] != 0.  In this fixed order:
+ *       0  F   (a + d(h), h)      translation                                     len(h) * s
+ *       1  FL  (a + d(h), h + 1)  translation, then rotation at the target cell   len(h) * s + turn_cost
+ *       2  FR  (a + d(h), h - 1)  the same                                        the same
+ *       3  SL  (a, h + 1)         rotation at a; only under LOM_POSE_SPIN         spin_cost
+ *       4  SR  (a, h - 1)         the same                                        the same
+ *       5  B   (a - d(h), h)      translation backwards; only under LOM_POSE_REVERSE   len(h) * s + reverse_cost
+ *     Every weight is positive and below 2^28: a move pays for the state it leaves.
+ *  5. Goals.  G int32 triples (ix, iy, h), at most 2^24.  h in 0 .. 7 names one state; h = -1 names every heading of the
+ *     cell whose layer is non-zero there.  A goal whose cell is outside the grid, whose h is outside -1 .. 7, or that names
+ *     no passable state counts in goals_rejected; goals_used counts the distinct goal states.  G = 0 or nothing used is
+ *     LOM_OK with everything unreached.
+ *  6. Field.  P[h][cell], u32, planar [8][height][width]: 0 on goal states; elsewhere the least total weight over all move
+ *     sequences to a goal state.  LOM_NAV_UNREACHED and LOM_NAV_MAX apply as in the navigation field: a candidate above
+ *     LOM_NAV_MAX is dropped, so exactly the states whose true value exceeds it read LOM_NAV_UNREACHED, and every state
+ *     behind them.  range_exceeded = 1 iff, at the fixed point, some reached state b and some allowed move a -> b have P[b]
+ *     + weight > LOM_NAV_MAX (computed in the summary pass).  Impassable states read LOM_NAV_UNREACHED.
+ *  7. Floor.  floor[cell] = the least P over h, u32 in lom_navfield_potential's form; floor_heading[cell], u8: the least h
+ *     that attains it, 8 where no heading is reached.  Both come from the summary pass; with lom_posefield_floor_device,
+ *     lom_rollout_evaluate_device and the other _device consumers take the floor as their potential plane as they are.
+ *  8. Summary.  states_blocked (L == 0), states_reached, states_unreached (passable, not reached) -- the three add up to
+ *     8 * width * height -- cells_reached (floor reached), cells_invalid (cost bytes outside -1 .. 100), goals_used,
+ *     goals_rejected, range_exceeded, max_potential (0 if nothing is reached).
+ *  9. Paths.  K int32 triples, at most 2^24; h = -1 starts at the floor_heading of the cell.  A start outside the grid,
+ *     with h outside -1 .. 7, or on an unreached state has length 0.  From a state with P > 0 the walk takes the first move
+ *     in the order of step 4 that is allowed and has P[target] + weight == P[state] -- one exists at the fixed point -- and
+ *     stops at P == 0.  Output: u16 triples (ix, iy, h) in a [K, cap] buffer, K * cap <= 2^28, the rest of a row 0; the
+ *     length counts start and goal and is the full length even above cap.  P falls strictly, so a walk is bounded by
+ *     8 * cells.
+ * 10. Query.  n points in metres by the floor rule, with one int32 heading each: P of that state, the floor for -1;
+ *     LOM_NAV_UNREACHED for a point outside the grid, a coordinate that is not a number or a heading outside -1 .. 7.
+ *
+ * The result is a pure function of plane, parameters, footprint and goals: it does not depend on the order in which lanes,
+ * waves or workgroups run, nor on the test switches below (k_posefield.hpp says why).
+ *
+ * lom_posefield_solve takes a host plane of width * height bytes; _solve_device a plane in HBM that is complete when
+ * hip_event_or_null is; _solve_from_clearance reads lom_clearance_cost_device in place with the event ordering and the bit
+ * for bit geometry check of lom_navfield_solve_from_clearance.  Footprint and goals are host memory in every form.  Every
+ * argument is validated and every allocation made before the first launch; a refused call changes nothing and zeroes the
+ * summary.  After create or clear every state is unreached and impassable, the floor unreached with heading 8.
+ * lom_posefield_shift is the planning grids' shift: the geometry moves by that rule, the state is lom_posefield_clear's.
+ * The relaxation runs to its fixed point through the navigation field's host loop with its bound of 2 * cells + 64
+ * launches; a solve that would need more ends with LOM_ERR_HIP.  Every call returns with its work done.  Calls on one
+ * handle are the caller's to serialise.  The error text is the handle's (lom_posefield_last_error).
+ * Measured on one MI355X (python tools/posefield_cost.py -> profiles/posefield_cost.json; HIP events, five alternating blocks,
+ * medians; lom_posefield_solve_device, one goal): 4096 x 4096 at 2 % obstacles 173.2 ms for a point and 187.5 ms for a 9 x 3-
+ * cell rectangle with both flags (352 launches, 22 waits), 80.9 and 99.5 ms at 0.01 %; 1174 x 160 2.7 to 7.1 ms (32 to 64
+ * launches).  The same call under LOM_POSE_OPT_TEST_ALL_TILES, the plain global sweep, takes 1.8 to 3.2 times as long at
+ * 4096 x 4096 and 1 to 2 % more at 1174 x 160, with the same bytes.  lom_navfield_solve_device on the same plane and goal
+ * cell, as context only: 46.6 / 20.2 ms and 2.87 / 1.42 ms.  What bounds k_pose_relax: NOT MEASURED.  DESIGN.md 7u. */
+#define LOM_POSE_HEADINGS 8
+typedef struct lom_posefield lom_posefield;
+typedef struct {
+    lom_navfield_params nav; /* the cell costs */
+    uint32_t turn_cost;      /* what FL and FR add, 0 .. 2^24 - 1 */
+    uint32_t spin_cost;      /* the weight of SL and SR, 1 .. 2^24 - 1 under LOM_POSE_SPIN (0 .. 2^24 - 1 otherwise) */
+    uint32_t reverse_cost;   /* what B adds, 0 .. 2^24 - 1 */
+    uint32_t flags;          /* LOM_POSE_* */
+} lom_posefield_params;
+typedef struct {
+    uint64_t states_blocked, states_reached, states_unreached, cells_reached, cells_invalid, goals_used, goals_rejected,
+        range_exceeded, max_potential;
+} lom_posefield_summary;
+typedef struct {
+    uint64_t launches, waits; /* of k_pose_relax in the last solve, and the host's waits for them */
+    uint64_t tiles;           /* workgroups per launch */
+} lom_posefield_solve_stats;
+enum { LOM_POSE_SPIN = 1, LOM_POSE_REVERSE = 2 };
+enum {
+    LOM_POSE_OPT_TEST_INNER_CAP = 1, /* as LOM_NAV_OPT_TEST_INNER_CAP */
+    LOM_POSE_OPT_TEST_BATCH = 2,     /* launches per wait, as LOM_NAV_OPT_TEST_BATCH */
+    LOM_POSE_OPT_TEST_ALL_TILES = 3  /* as LOM_NAV_OPT_TEST_ALL_TILES.  Test switches: the bytes are the same. */
+};
+int lom_posefield_create(const lom_occupancy_geometry *geometry, int device, lom_posefield **out);
+void lom_posefield_destroy(lom_posefield *f);
+const char *lom_posefield_last_error(const lom_posefield *f); /* f == NULL: why the last create on this thread failed */
+int lom_posefield_clear(lom_posefield *f);                    /* every state unreached and impassable */
+int lom_posefield_shift(lom_posefield *f, int32_t dx, int32_t dy);
+int lom_posefield_get_geometry(const lom_posefield *f, lom_occupancy_geometry *out);
+void *lom_posefield_stream(lom_posefield *f); /* hipStream_t */
+int lom_posefield_device(const lom_posefield *f);
+int lom_posefield_wait_event(lom_posefield *f, void *hip_event);
+int lom_posefield_set_option(lom_posefield *f, int option, int64_t value);
+/* footprint: n_samples (fx, fy) int32 pairs; goals: n_goals (ix, iy, h) int32 triples (may be NULL with n_goals 0) */
+int lom_posefield_solve(lom_posefield *f, const int8_t *plane, const lom_posefield_params *params, const int32_t *footprint,
+                        size_t n_samples, const int32_t *goals, size_t n_goals, lom_posefield_summary *summary_or_null);
+int lom_posefield_solve_device(lom_posefield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_posefield_params *params,
+                               const int32_t *footprint, size_t n_samples, const int32_t *goals, size_t n_goals,
+                               lom_posefield_summary *summary_or_null);
+int lom_posefield_solve_from_clearance(lom_posefield *f, lom_clearance *clearance, const lom_posefield_params *params,
+                                       const int32_t *footprint, size_t n_samples, const int32_t *goals, size_t n_goals,
+                                       lom_posefield_summary *summary_or_null);
+/* P, [8][height][width]: at most `cap` states go to `out` (may be NULL with cap 0) */
+int lom_posefield_potential(lom_posefield *f, uint32_t *out, size_t cap);
+/* the same, left in HBM: 8 * width * height states, valid until the next solve, clear or shift on the handle */
+int lom_posefield_potential_device(lom_posefield *f, const uint32_t **d_out);
+/* L, [8][height][width], likewise */
+int lom_posefield_layers(lom_posefield *f, uint32_t *out, size_t cap);
+/* step 7: at most `cap` cells go to each of floor_out and heading_out (either may be NULL) */
+int lom_posefield_floor(lom_posefield *f, uint32_t *floor_out, uint8_t *heading_out, size_t cap);
+/* the same, left in HBM (either pointer may be NULL), valid as lom_posefield_potential_device's */
+int lom_posefield_floor_device(lom_posefield *f, const uint32_t **d_floor_out, const uint8_t **d_heading_out);
+/* step 9: n_starts triples in host memory; states_out: [n_starts, cap] u16 triples (may be NULL with cap 0), lengths_out:
+ * n_starts u32 (may be NULL) */
+int lom_posefield_paths(lom_posefield *f, const int32_t *starts, size_t n_starts, uint16_t *states_out, size_t cap,
+                        uint32_t *lengths_out);
+/* step 10: n points (x, y in the grid's frame, f32 pairs) and n int32 headings in host memory, at most 2^30 */
+int lom_posefield_query(lom_posefield *f, const float *xy, const int32_t *headings, size_t n, uint32_t *out);
+/* the launches and waits of the last solve (zeros before the first) */
+int lom_posefield_stats(const lom_posefield *f, lom_posefield_solve_stats *out);
+/* Host-only helpers; neither needs a handle or a device.
+ * Step 2: counts_out[h], the cells of the stencil of heading h; at most `cap` (dx, dy) int32 pairs go to `cells_out` (may be
+ * NULL with cap 0), heading after heading.  LOM_ERR_ARG for a bad footprint or a NULL counts_out. */
+int lom_posefield_stencils(const int32_t *footprint, size_t n_samples, int32_t *cells_out, size_t cap, uint32_t *counts_out);
+/* step 1: the heading of an angle in 1/65536 turn (any value: it is taken mod 65536) */
+uint32_t lom_posefield_heading_of_angle(uint32_t angle);
+
 /* LidarOdometry::Params, src/lidar_odometry.h:23-48 */
 typedef struct {
     float lidar_min_range, lidar_max_range;

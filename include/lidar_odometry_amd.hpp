@@ -1407,6 +1407,125 @@ inline lom_navfield_summary NavField::adopt(NavFieldSet &set, size_t i)
     return s;
 }
 
+// ---- PoseField (not in the reference) --------------------------------------------------
+// The cost-to-go over cell and heading under a robot's footprint: solve() takes an int8 cost plane, a footprint (F pairs
+// of int32 fx, fy in 1/256 cell, robot frame) and goals (n triples of int32 ix, iy, h; h = -1: every passable heading of
+// the cell); heading h of 0 .. 7 points along E, NE, N, NW, W, SW, S, SE.  floor() is the least over the headings, in
+// NavField::potential()'s form.  Definitions: lidar_odometry_amd.h ("pose field").
+using PoseFieldParams = lom_posefield_params;  // {nav, turn_cost, spin_cost, reverse_cost, flags}
+using PoseFieldSummary = lom_posefield_summary;
+
+inline PoseFieldParams posefieldParams(const lom_navfield_params &nav, uint32_t turn_cost, uint32_t spin_cost, uint32_t reverse_cost,
+                                       uint32_t flags = 0)
+{
+    return PoseFieldParams{nav, turn_cost, spin_cost, reverse_cost, flags};
+}
+// the heading 0 .. 7 of an angle in 1/65536 turn; needs no device
+inline uint32_t posefieldHeadingOfAngle(uint32_t angle) { return lom_posefield_heading_of_angle(angle); }
+// the eight stencils of a footprint, (dx, dy) pairs per heading, sorted by (dy, dx); needs no device
+inline std::vector<std::vector<int32_t>> posefieldStencils(const int32_t *footprint, size_t n_samples)
+{
+    uint32_t counts[LOM_POSE_HEADINGS] = {};
+    if (lom_posefield_stencils(footprint, n_samples, nullptr, 0, counts) != LOM_OK) throw Error(LOM_ERR_ARG, "lom_posefield_stencils");
+    size_t total = 0;
+    for (uint32_t c : counts) total += c;
+    std::vector<int32_t> cells(2 * total);
+    (void)lom_posefield_stencils(footprint, n_samples, cells.data(), total, counts);
+    std::vector<std::vector<int32_t>> out(LOM_POSE_HEADINGS);
+    size_t at = 0;
+    for (size_t h = 0; h < LOM_POSE_HEADINGS; at += 2 * (size_t)counts[h], h++) out[h].assign(cells.begin() + at, cells.begin() + at + 2 * (size_t)counts[h]);
+    return out;
+}
+
+class PoseField
+    : public GridHandle<lom_posefield, lom_occupancy_geometry, lom_posefield_create, lom_posefield_destroy, lom_posefield_last_error,
+                        lom_posefield_get_geometry, lom_posefield_clear, lom_posefield_shift, lom_posefield_set_option, lom_posefield_device,
+                        lom_posefield_stream, lom_posefield_wait_event> {
+public:
+    struct Paths {  // states: [K, cap] (ix, iy, h) triples; lengths: the full length per start, 0 where none was walked
+        std::vector<uint16_t> states;
+        std::vector<uint32_t> lengths;
+    };
+    struct Floor {  // heading: the least heading that attains the floor, 8 where none is reached
+        std::vector<uint32_t> floor;
+        std::vector<uint8_t> heading;
+    };
+
+    explicit PoseField(const lom_occupancy_geometry &geometry, int device = 0) : GridHandle(geometry, device) {}
+    size_t size() const { return cellCount(); }
+    // a host plane of size() cells
+    PoseFieldSummary solve(const int8_t *plane, const PoseFieldParams &params, const int32_t *footprint, size_t n_samples,
+                           const int32_t *goals, size_t n_goals)
+    {
+        PoseFieldSummary s;
+        check(lom_posefield_solve(h_, plane, &params, footprint, n_samples, goals, n_goals, &s));
+        return s;
+    }
+    // ... a plane in HBM that is complete when hip_event is (NULL: now)
+    PoseFieldSummary solveDevice(const int8_t *d_plane, void *hip_event, const PoseFieldParams &params, const int32_t *footprint,
+                                 size_t n_samples, const int32_t *goals, size_t n_goals)
+    {
+        PoseFieldSummary s;
+        check(lom_posefield_solve_device(h_, d_plane, hip_event, &params, footprint, n_samples, goals, n_goals, &s));
+        return s;
+    }
+    // ... the plane a ClearanceGrid of this geometry left in HBM
+    PoseFieldSummary solveFromClearance(ClearanceGrid &clearance, const PoseFieldParams &params, const int32_t *footprint, size_t n_samples,
+                                        const int32_t *goals, size_t n_goals)
+    {
+        PoseFieldSummary s;
+        check(lom_posefield_solve_from_clearance(h_, clearance.handle(), &params, footprint, n_samples, goals, n_goals, &s));
+        return s;
+    }
+    std::vector<uint32_t> potential()  // [8][height][width]
+    {
+        std::vector<uint32_t> out(size() * LOM_POSE_HEADINGS);
+        check(lom_posefield_potential(h_, out.data(), out.size()));
+        return out;
+    }
+    std::vector<uint32_t> layers()  // [8][height][width]
+    {
+        std::vector<uint32_t> out(size() * LOM_POSE_HEADINGS);
+        check(lom_posefield_layers(h_, out.data(), out.size()));
+        return out;
+    }
+    Floor floor()
+    {
+        Floor f;
+        f.floor.resize(size()), f.heading.resize(size());
+        check(lom_posefield_floor(h_, f.floor.data(), f.heading.data(), f.floor.size()));
+        return f;
+    }
+    // the floor in HBM, a potential plane for RolloutGrid's device form; valid until the next solve(), clear() or shift()
+    const uint32_t *floorDevice()
+    {
+        const uint32_t *d = nullptr;
+        check(lom_posefield_floor_device(h_, &d, nullptr));
+        return d;
+    }
+    // starts: n triples (ix, iy, h), h = -1 for the floor's heading
+    Paths paths(const int32_t *starts, size_t n, size_t cap)
+    {
+        Paths p;
+        p.states.assign(n * cap * 3, 0), p.lengths.assign(n, 0);
+        check(lom_posefield_paths(h_, starts, n, p.states.data(), cap, p.lengths.data()));
+        return p;
+    }
+    // xy: n pairs in the grid's frame; headings: n values, -1 for the floor
+    std::vector<uint32_t> query(const float *xy, const int32_t *headings, size_t n)
+    {
+        std::vector<uint32_t> out(n);
+        check(lom_posefield_query(h_, xy, headings, n, out.data()));
+        return out;
+    }
+    lom_posefield_solve_stats stats() const
+    {
+        lom_posefield_solve_stats s;
+        check(lom_posefield_stats(h_, &s));
+        return s;
+    }
+};
+
 // ---- RegionGrid (not in the reference) -------------------------------------------------
 // Connected regions of a grid plane on the device: extract() takes an int8 plane (row-major with y as the row, what
 // OccupancyGrid::classify() writes), optionally a cost plane and a NavField potential, labels the regions of the

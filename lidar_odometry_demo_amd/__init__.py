@@ -1325,7 +1325,7 @@ class ElevationGrid(_PosedScanGrid):
 
 
 class _PlaneGrid(_Grid):
-    """What ClearanceGrid, NavField, NavFieldSet, RegionGrid, VisibilityGrid and RolloutGrid share (csrc/plane_handle.hpp): a dense 2-D grid of one
+    """What ClearanceGrid, NavField, NavFieldSet, PoseField, RegionGrid, VisibilityGrid and RolloutGrid share (csrc/plane_handle.hpp): a dense 2-D grid of one
     lom_occupancy_geometry that takes planes of shape (height, width)."""
 
     _shape_text = "expected an int8 array of shape (height, width)"
@@ -1673,6 +1673,134 @@ class NavFieldSet(_PlaneGrid):
         st = capi.NavSetSolveStats()
         self._check(self._call("stats", self._h, C.byref(st)))
         return st.asdict()
+
+
+class PoseField(_PlaneGrid):
+    """The pose field on the device (lom_posefield_*, include/lidar_odometry_amd.h "pose field"): solve() takes an int8 cost
+    plane of shape (height, width), a footprint -- (F, 2) int32 samples in 1/256 cell in the robot's frame, what
+    rolloutFootprintRectangle gives -- and goals, (n, 3) int32 triples (ix, iy, h) with h = -1 for every passable heading of
+    the cell, and leaves per cell and heading the least total cost to reach a goal state (uint32, capi.NAV_UNREACHED where
+    there is no way).  Heading h of 0 .. 7 points along E, NE, N, NW, W, SW, S, SE.  floor() is the least over the headings,
+    in NavField.potential()'s form; paths() walks down the field, query() reads it at points in metres."""
+
+    _family = "posefield"
+
+    @staticmethod
+    def _triples(a):
+        return np.ascontiguousarray(a, np.int32).reshape(-1, 3)
+
+    def _solve(self, name, head, params, footprint, goals):
+        p, sm = posefieldParams(params), capi.PoseFieldSummary()
+        fp, g = np.ascontiguousarray(footprint, np.int32).reshape(-1, 2), self._triples(goals)
+        self._check(self._call(name, self._h, *head, C.byref(p), fp.ctypes.data, len(fp), g.ctypes.data, len(g), C.byref(sm)))
+        return sm.asdict()
+
+    def solve(self, plane, params, footprint, goals, device=False, hip_event=None):
+        """lom_posefield_solve: a host plane -- or, with device=True, lom_posefield_solve_device: `plane` is a device pointer
+        to a plane in HBM, complete when `hip_event` is.  Returns capi.PoseFieldSummary as a dict."""
+        if device:
+            return self._solve("solve_device", (plane, hip_event), params, footprint, goals)
+        plane = self._plane(plane, np.int8)
+        return self._solve("solve", (plane.ctypes.data,), params, footprint, goals)
+
+    def solveFromClearance(self, clearance, params, footprint, goals):
+        """lom_posefield_solve_from_clearance: the cost plane a ClearanceGrid of this geometry left in HBM"""
+        return self._solve("solve_from_clearance", (clearance.handle,), params, footprint, goals)
+
+    def potential(self):
+        """uint32 array of shape (8, height, width): P per heading and cell"""
+        out = np.empty((capi.POSE_HEADINGS, self.height, self.width), np.uint32)
+        self._check(self._call("potential", self._h, out.ctypes.data, out.size))
+        return out
+
+    def potentialDevice(self):
+        """the device pointer of P, valid until the next solve(), clear() or shift()"""
+        p = C.c_void_p()
+        self._check(self._call("potential_device", self._h, C.byref(p)))
+        return p.value
+
+    def layers(self):
+        """uint32 array of shape (8, height, width): L per heading and cell, 0 where the footprint does not fit"""
+        out = np.empty((capi.POSE_HEADINGS, self.height, self.width), np.uint32)
+        self._check(self._call("layers", self._h, out.ctypes.data, out.size))
+        return out
+
+    def floor(self):
+        """(floor uint32 (height, width), heading uint8 (height, width)): the least P over the headings and the least
+        heading that attains it, 8 where none is reached"""
+        fl, fh = np.empty((self.height, self.width), np.uint32), np.empty((self.height, self.width), np.uint8)
+        self._check(self._call("floor", self._h, fl.ctypes.data, fh.ctypes.data, fl.size))
+        return fl, fh
+
+    def floorDevice(self):
+        """(floor, heading) device pointers, valid as potentialDevice()'s; the floor is a potential plane for
+        RolloutGrid.evaluate(..., device=True)"""
+        fl, fh = C.c_void_p(), C.c_void_p()
+        self._check(self._call("floor_device", self._h, C.byref(fl), C.byref(fh)))
+        return fl.value, fh.value
+
+    def paths(self, starts, cap):
+        """(states uint16 (K, cap, 3), lengths uint32 (K,)): the walk from each start (ix, iy, h), h = -1 for the floor's
+        heading, down the field; a length counts start and goal, is 0 for a start that is not walked, and may exceed cap"""
+        s = self._triples(starts)
+        states, lengths = np.zeros((len(s), int(cap), 3), np.uint16), np.zeros(len(s), np.uint32)
+        self._check(self._call("paths", self._h, s.ctypes.data, len(s), states.ctypes.data, int(cap), lengths.ctypes.data))
+        return states, lengths
+
+    def query(self, xy, headings):
+        """uint32 P of the states at the points xy (n, 2) in the grid's frame with one heading each, -1 for the floor;
+        capi.NAV_UNREACHED outside the grid"""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        h = np.ascontiguousarray(headings, np.int32).reshape(-1)
+        if len(h) != len(xy):
+            raise ValueError("one heading per point")
+        out = np.empty(len(xy), np.uint32)
+        self._check(self._call("query", self._h, xy.ctypes.data, h.ctypes.data, len(xy), out.ctypes.data))
+        return out
+
+    def stats(self):
+        """capi.PoseFieldSolveStats of the last solve as a dict: launches, waits, tiles"""
+        st = capi.PoseFieldSolveStats()
+        self._check(self._call("stats", self._h, C.byref(st)))
+        return st.asdict()
+
+
+def posefieldParams(params):
+    """capi.PoseFieldParams from one, from a dict with its five fields, or from a 5-tuple in the struct's order (nav,
+    turn_cost, spin_cost, reverse_cost, flags); nav is whatever navfieldParams takes.  There are no defaults."""
+    if isinstance(params, capi.PoseFieldParams):
+        return params
+    names = [k for k, _ in capi.PoseFieldParams._fields_]
+    if isinstance(params, dict):
+        if sorted(params) != sorted(names):
+            raise TypeError(f"pose field parameters: exactly {names}")
+        vals = [params[k] for k in names]
+    else:
+        vals = list(params)
+        if len(vals) != len(names):
+            raise TypeError(f"pose field parameters: exactly {names}")
+    return capi.PoseFieldParams(navfieldParams(vals[0]), *[int(v) for v in vals[1:]])
+
+
+posefield_params = posefieldParams
+
+
+def posefieldStencils(footprint):
+    """lom_posefield_stencils: a list of eight (n_h, 2) int32 arrays, the (dx, dy) cell offsets the footprint covers at
+    heading h, sorted by (dy, dx); needs no device"""
+    fp = np.ascontiguousarray(footprint, np.int32).reshape(-1, 2)
+    counts = np.zeros(capi.POSE_HEADINGS, np.uint32)
+    rc = capi.lib().lom_posefield_stencils(fp.ctypes.data, len(fp), None, 0, counts.ctypes.data)
+    if rc != 0:
+        raise LomError(int(rc), "pose field stencils: a footprint of 1 .. 1024 samples with |fx|, |fy| <= 16384")
+    cells = np.zeros((int(counts.sum()), 2), np.int32)
+    capi.lib().lom_posefield_stencils(fp.ctypes.data, len(fp), cells.ctypes.data, len(cells), counts.ctypes.data)
+    return np.split(cells, np.cumsum(counts)[:-1].astype(np.int64))
+
+
+def posefieldHeadingOfAngle(angle):
+    """lom_posefield_heading_of_angle: the heading 0 .. 7 of an angle in 1/65536 turn; needs no device"""
+    return int(capi.lib().lom_posefield_heading_of_angle(int(angle) & 0xFFFFFFFF))
 
 
 def navfieldCellCosts(params):

@@ -413,6 +413,36 @@ NAVSET_NO_OWNER, NAVSET_MAX_FIELDS = 0xFFFF, 65535
 NAVSET_OPT_TEST_INNER_CAP, NAVSET_OPT_TEST_BATCH, NAVSET_OPT_TEST_ALL_TILES = 1, 2, 3
 
 
+class PoseFieldParams(C.Structure):
+    """lom_posefield_params"""
+    _fields_ = [("nav", NavFieldParams), ("turn_cost", C.c_uint32), ("spin_cost", C.c_uint32), ("reverse_cost", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class PoseFieldSummary(C.Structure):
+    """lom_posefield_summary"""
+    _fields_ = [("states_blocked", C.c_uint64), ("states_reached", C.c_uint64), ("states_unreached", C.c_uint64),
+                ("cells_reached", C.c_uint64), ("cells_invalid", C.c_uint64), ("goals_used", C.c_uint64),
+                ("goals_rejected", C.c_uint64), ("range_exceeded", C.c_uint64), ("max_potential", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class PoseFieldSolveStats(C.Structure):
+    """lom_posefield_solve_stats"""
+    _fields_ = [("launches", C.c_uint64), ("waits", C.c_uint64), ("tiles", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(PoseFieldParams) == 36 and C.sizeof(PoseFieldSummary) == 72 and C.sizeof(PoseFieldSolveStats) == 24
+POSE_HEADINGS = 8
+POSE_SPIN, POSE_REVERSE = 1, 2
+POSE_OPT_TEST_INNER_CAP, POSE_OPT_TEST_BATCH, POSE_OPT_TEST_ALL_TILES = 1, 2, 3
+
+
 class RegionsParams(C.Structure):
     """lom_regions_params"""
     _fields_ = [("kind", C.c_int32), ("lo", C.c_int8), ("hi", C.c_int8), ("max_cost", C.c_int8), ("min_cells", C.c_uint32),
@@ -851,6 +881,21 @@ PROTOTYPES = {
     "lom_navset_nearest": (_int, [_vp, _vp, _vp, _vp]),
     "lom_navset_paths": (_int, [_vp, _vp, _int, _vp, _size, _vp, _size, _vp]),
     "lom_navset_stats": (_int, [_vp, _P(NavSetSolveStats)]),
+    # ---- pose field
+    **_grid_family("posefield", OccupancyGeometry),
+    "lom_posefield_solve": (_int, [_vp, _vp, _P(PoseFieldParams), _vp, _size, _vp, _size, _P(PoseFieldSummary)]),
+    "lom_posefield_solve_device": (_int, [_vp, _vp, _vp, _P(PoseFieldParams), _vp, _size, _vp, _size, _P(PoseFieldSummary)]),
+    "lom_posefield_solve_from_clearance": (_int, [_vp, _vp, _P(PoseFieldParams), _vp, _size, _vp, _size, _P(PoseFieldSummary)]),
+    "lom_posefield_potential": (_int, [_vp, _vp, _size]),
+    "lom_posefield_potential_device": (_int, [_vp, _P(_vp)]),
+    "lom_posefield_layers": (_int, [_vp, _vp, _size]),
+    "lom_posefield_floor": (_int, [_vp, _vp, _vp, _size]),
+    "lom_posefield_floor_device": (_int, [_vp, _P(_vp), _P(_vp)]),
+    "lom_posefield_paths": (_int, [_vp, _vp, _size, _vp, _size, _vp]),
+    "lom_posefield_query": (_int, [_vp, _vp, _vp, _size, _vp]),
+    "lom_posefield_stats": (_int, [_vp, _P(PoseFieldSolveStats)]),
+    "lom_posefield_stencils": (_int, [_vp, _size, _vp, _size, _vp]),
+    "lom_posefield_heading_of_angle": (_u32, [_u32]),
     # ---- frontier regions
     **_grid_family("regions", OccupancyGeometry),
     "lom_regions_extract": (_int, [_vp, _vp, _vp, _vp, _P(RegionsParams), _P(RegionsSummary)]),

@@ -1,5 +1,5 @@
-// The host loop of a relaxation over tiles, written once for lom_navfield (navfield.hip) and lom_navset (navset.hip).
-// Host code; launches nothing itself.
+// The host loop of a relaxation over tiles, written once for lom_navfield (navfield.hip), lom_navset (navset.hip) and
+// lom_posefield (posefield.hip).  Host code; launches nothing itself.
 #pragma once
 #include "device_handle.hpp"
 #include "navfield_host.hpp"
