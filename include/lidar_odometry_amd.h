@@ -2598,7 +2598,54 @@ lom_rollout_shift_fn lom_rollout_shift;
  * cell rectangle with both flags (352 launches, 22 waits), 80.9 and 99.5 ms at 0.01 %; 1174 x 160 2.7 to 7.1 ms (32 to 64
  * launches).  The same call under LOM_POSE_OPT_TEST_ALL_TILES, the plain global sweep, takes 1.8 to 3.2 times as long at
  * 4096 x 4096 and 1 to 2 % more at 1174 x 160, with the same bytes.  lom_navfield_solve_device on the same plane and goal
- * cell, as context only: 46.6 / 20.2 ms and 2.87 / 1.42 ms.  What bounds k_pose_relax: NOT MEASURED.  DESIGN.md 7u. */
+ * cell, as context only: 46.6 / 20.2 ms and 2.87 / 1.42 ms.  What bounds k_pose_relax: NOT MEASURED.  DESIGN.md 7u.
+ *
+ * Re-solve.  A pose field that has completed a solve keeps its plane, its table, its stencils, its lom_posefield_params,
+ * the layers and P.  lom_posefield_resolve* takes a new full-grid int8 plane and an optional lom_clearance_window, with that
+ * struct's rules: the rectangle is clipped to the grid, NULL is the whole grid, an empty rectangle is LOM_OK and changes
+ * nothing.  No footprint, parameters or goals are passed: they are the last solve's.
+ *  a. Merged plane.  The kept plane with the cells of the clipped window replaced by the new plane's.  Cells outside the
+ *     window are not read; the host form uploads only the rows of the window.
+ *  b. Layers.  L of the merged plane is exactly what lom_posefield_solve computes for it (step 3) with the last solve's
+ *     footprint and parameters.
+ *  c. Goals.  The states with P == 0 before the call: the goal states the last solve or re-solve used.  A goal state whose
+ *     layer is 0 under the merged plane counts in goals_rejected and is gone for later re-solves; goals_used +
+ *     goals_rejected equals the previous goals_used.  The goals are states, not cells: a heading of a goal cell that the
+ *     last solve skipped because it was impassable there does not become a goal when the change makes it passable, whether
+ *     the goal was named with h = -1 or not.
+ *  d. Result.  L, P, the floor, its heading and the summary are, byte for byte, what lom_posefield_solve leaves on the
+ *     merged plane with the last solve's footprint and parameters and those goal states passed as explicit (ix, iy, h)
+ *     triples.  The kept plane becomes the merged plane; paths and queries read the new state; the pointers of
+ *     lom_posefield_potential_device and lom_posefield_floor_device stay valid across the call.
+ *  e. Refusals.  No completed solve since create, clear or shift: LOM_ERR_STATE.  A NULL plane, or a clearance grid of
+ *     other geometry or on another device: LOM_ERR_ARG.  Every refusal comes before any device work, changes nothing (the
+ *     counters of lom_posefield_resolve_stats included) and zeroes the summary.
+ *  f. Counters of the last re-solve, through lom_posefield_resolve_stats.  cells_changed: the bytes of the clipped window
+ *     that differ from the kept ones.  states_changed: the (cell, heading) whose layer differs.  states_raised: the states
+ *     that were reached and passable under the merged plane and that the raise phase set unreached -- the least such set,
+ *     below; under form 1 every reached state but the goal states.  raise_launches, relax_launches, waits, tiles_marked as
+ *     lom_navfield_resolve_counters'.  cells_changed == 0 ends the call behind the diff: nothing else is launched, the state
+ *     is untouched and the summary is the last one with goals_rejected 0.
+ * The work is incremental and still exact.  A diff over the window (k_pose_diff) merges the plane and finds the changed
+ * cells and their bounding box; from there the work is sized by what changed, not by the window.  One launch
+ * (k_pose_relayer) recomputes the layers per heading over the changed box dilated by that heading's stencil, sets the
+ * states that are now impassable to unreached and marks the tiles that hold a changed state or read one as halo.  The
+ * raise phase (k_pose_raise) then sets every reached state unreached that no chain of supporters carries down to a goal
+ * state under the new layers -- a supporter of state a is a state b with an allowed move a -> b of step 4 and P[b] + weight
+ * <= P[a]; every weight is positive (a translation at least 5, a spin spin_cost >= 1), so the set is well defined and does
+ * not depend on the schedule -- and the relaxation of a solve lowers what is left, every value an upper bound, to the
+ * field; the summary pass of a solve runs once.  LOM_POSE_OPT_TEST_RESOLVE_FORM 1 is the baseline on the same handle: the
+ * layers over the whole merged plane, every state but the goal states unreached, the full relaxation; same bytes, same
+ * summary.  LOM_POSE_OPT_TEST_INNER_CAP, _BATCH and _ALL_TILES act on the raise phase and the relaxation alike.  A seed
+ * array of one u32 per tile is allocated at the first re-solve.
+ * Measured on one MI355X (python tools/posefield_resolve_cost.py -> profiles/posefield_resolve_cost.json; HIP events, five
+ * alternating blocks, medians; a wall of 64 cells put into / taken out of a 64 x 64 window, both planes in HBM, one goal in a
+ * corner; the default form against form 1 on the same handle, same bytes in all 48 cases): with the window in the far
+ * corner from the goal 5.2 to 6.3 ms against 155 to 447 ms at 4096 x 4096 (26x to 86x) and 0.50 to 1.57 ms against 4.8 to
+ * 14.1 ms at 1174 x 160 (5.2x to 19x); half way ahead in all 32 cases (1.2x to 71x); next to the goal with the wall going
+ * in it LOSES in 10 of 16 cases (0.35x to 0.79x; 416 to 550 ms against 157 to 204 at 4096 x 4096 and 0.01 % obstacles),
+ * since nearly every state rises and is solved again, and is ahead when the wall comes out (1.1x to 5.3x).  What bounds
+ * k_pose_raise: NOT MEASURED.  DESIGN.md 7v. */
 #define LOM_POSE_HEADINGS 8
 typedef struct lom_posefield lom_posefield;
 typedef struct {
@@ -2616,11 +2663,21 @@ typedef struct {
     uint64_t launches, waits; /* of k_pose_relax in the last solve, and the host's waits for them */
     uint64_t tiles;           /* workgroups per launch */
 } lom_posefield_solve_stats;
+typedef struct {
+    uint64_t cells_changed;  /* bytes of the clipped window that differ from the kept ones */
+    uint64_t states_changed; /* (cell, heading) whose layer differs */
+    uint64_t states_raised;  /* reached states the raise phase (form 1: the reset) set unreached */
+    uint64_t raise_launches, relax_launches; /* of k_pose_raise and k_pose_relax */
+    uint64_t waits;          /* the host's waits, the diff's included */
+    uint64_t tiles_marked;   /* seeds of the relaxation */
+} lom_posefield_resolve_counters; /* what lom_posefield_resolve_stats gives */
 enum { LOM_POSE_SPIN = 1, LOM_POSE_REVERSE = 2 };
 enum {
     LOM_POSE_OPT_TEST_INNER_CAP = 1, /* as LOM_NAV_OPT_TEST_INNER_CAP */
     LOM_POSE_OPT_TEST_BATCH = 2,     /* launches per wait, as LOM_NAV_OPT_TEST_BATCH */
-    LOM_POSE_OPT_TEST_ALL_TILES = 3  /* as LOM_NAV_OPT_TEST_ALL_TILES.  Test switches: the bytes are the same. */
+    LOM_POSE_OPT_TEST_ALL_TILES = 3, /* as LOM_NAV_OPT_TEST_ALL_TILES */
+    LOM_POSE_OPT_TEST_RESOLVE_FORM = 4 /* 0 or < 0, the default: raise, then relax; 1: the baseline, the full solve on the
+                                          same handle.  Test switches: the bytes are the same. */
 };
 int lom_posefield_create(const lom_occupancy_geometry *geometry, int device, lom_posefield **out);
 void lom_posefield_destroy(lom_posefield *f);
@@ -2641,6 +2698,15 @@ int lom_posefield_solve_device(lom_posefield *f, const int8_t *d_plane, void *hi
 int lom_posefield_solve_from_clearance(lom_posefield *f, lom_clearance *clearance, const lom_posefield_params *params,
                                        const int32_t *footprint, size_t n_samples, const int32_t *goals, size_t n_goals,
                                        lom_posefield_summary *summary_or_null);
+/* Re-solve (above): plane as lom_posefield_solve's, d_plane as _solve_device's, clearance as _solve_from_clearance's */
+int lom_posefield_resolve(lom_posefield *f, const int8_t *plane, const lom_clearance_window *window_or_null,
+                          lom_posefield_summary *summary_or_null);
+int lom_posefield_resolve_device(lom_posefield *f, const int8_t *d_plane, void *hip_event_or_null,
+                                 const lom_clearance_window *window_or_null, lom_posefield_summary *summary_or_null);
+int lom_posefield_resolve_from_clearance(lom_posefield *f, lom_clearance *clearance, const lom_clearance_window *window_or_null,
+                                         lom_posefield_summary *summary_or_null);
+/* the counters of the last re-solve (zeros before the first) */
+int lom_posefield_resolve_stats(const lom_posefield *f, lom_posefield_resolve_counters *out);
 /* P, [8][height][width]: at most `cap` states go to `out` (may be NULL with cap 0) */
 int lom_posefield_potential(lom_posefield *f, uint32_t *out, size_t cap);
 /* the same, left in HBM: 8 * width * height states, valid until the next solve, clear or shift on the handle */

@@ -1477,6 +1477,32 @@ public:
         check(lom_posefield_solve_from_clearance(h_, clearance.handle(), &params, footprint, n_samples, goals, n_goals, &s));
         return s;
     }
+    // Re-solve: the field of the kept plane with the cells of `window` (NULL: the whole grid) taken from `plane`, for the
+    // footprint, parameters and goal states of the last solve
+    PoseFieldSummary resolve(const int8_t *plane, const lom_clearance_window *window = nullptr)
+    {
+        PoseFieldSummary s;
+        check(lom_posefield_resolve(h_, plane, window, &s));
+        return s;
+    }
+    PoseFieldSummary resolveDevice(const int8_t *d_plane, void *hip_event, const lom_clearance_window *window = nullptr)
+    {
+        PoseFieldSummary s;
+        check(lom_posefield_resolve_device(h_, d_plane, hip_event, window, &s));
+        return s;
+    }
+    PoseFieldSummary resolveFromClearance(ClearanceGrid &clearance, const lom_clearance_window *window = nullptr)
+    {
+        PoseFieldSummary s;
+        check(lom_posefield_resolve_from_clearance(h_, clearance.handle(), window, &s));
+        return s;
+    }
+    lom_posefield_resolve_counters resolveStats() const
+    {
+        lom_posefield_resolve_counters s;
+        check(lom_posefield_resolve_stats(h_, &s));
+        return s;
+    }
     std::vector<uint32_t> potential()  // [8][height][width]
     {
         std::vector<uint32_t> out(size() * LOM_POSE_HEADINGS);

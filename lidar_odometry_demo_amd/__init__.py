@@ -1707,6 +1707,33 @@ class PoseField(_PlaneGrid):
         """lom_posefield_solve_from_clearance: the cost plane a ClearanceGrid of this geometry left in HBM"""
         return self._solve("solve_from_clearance", (clearance.handle,), params, footprint, goals)
 
+    def resolve(self, plane, window=None, device=False, hip_event=None):
+        """lom_posefield_resolve: the pose field of the kept plane with the cells of `window` ((x0, y0, width, height) in
+        cells, None: the whole grid) taken from the host plane `plane`, for the footprint, parameters and goal states of the
+        last solve -- or, with device=True, lom_posefield_resolve_device: `plane` is a device pointer to a plane in HBM,
+        complete when `hip_event` is.  Returns capi.PoseFieldSummary as a dict."""
+        sm = capi.PoseFieldSummary()
+        if device:
+            rc = self._call("resolve_device", self._h, plane, hip_event, ClearanceGrid._window(window), C.byref(sm))
+        else:
+            plane = self._plane(plane, np.int8)
+            rc = self._call("resolve", self._h, plane.ctypes.data, ClearanceGrid._window(window), C.byref(sm))
+        self._check(rc)
+        return sm.asdict()
+
+    def resolveFromClearance(self, clearance, window=None):
+        """lom_posefield_resolve_from_clearance: the window of the cost plane a ClearanceGrid of this geometry left in HBM"""
+        sm = capi.PoseFieldSummary()
+        self._check(self._call("resolve_from_clearance", self._h, clearance.handle, ClearanceGrid._window(window), C.byref(sm)))
+        return sm.asdict()
+
+    def resolveStats(self):
+        """capi.PoseFieldResolveCounters of the last re-solve as a dict: cells_changed, states_changed, states_raised,
+        raise_launches, relax_launches, waits, tiles_marked"""
+        st = capi.PoseFieldResolveCounters()
+        self._check(self._call("resolve_stats", self._h, C.byref(st)))
+        return st.asdict()
+
     def potential(self):
         """uint32 array of shape (8, height, width): P per heading and cell"""
         out = np.empty((capi.POSE_HEADINGS, self.height, self.width), np.uint32)

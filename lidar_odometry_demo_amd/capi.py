@@ -437,10 +437,20 @@ class PoseFieldSolveStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class PoseFieldResolveCounters(C.Structure):
+    """lom_posefield_resolve_counters"""
+    _fields_ = [("cells_changed", C.c_uint64), ("states_changed", C.c_uint64), ("states_raised", C.c_uint64),
+                ("raise_launches", C.c_uint64), ("relax_launches", C.c_uint64), ("waits", C.c_uint64), ("tiles_marked", C.c_uint64)]
+
+    def asdict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 assert C.sizeof(PoseFieldParams) == 36 and C.sizeof(PoseFieldSummary) == 72 and C.sizeof(PoseFieldSolveStats) == 24
+assert C.sizeof(PoseFieldResolveCounters) == 56
 POSE_HEADINGS = 8
 POSE_SPIN, POSE_REVERSE = 1, 2
-POSE_OPT_TEST_INNER_CAP, POSE_OPT_TEST_BATCH, POSE_OPT_TEST_ALL_TILES = 1, 2, 3
+POSE_OPT_TEST_INNER_CAP, POSE_OPT_TEST_BATCH, POSE_OPT_TEST_ALL_TILES, POSE_OPT_TEST_RESOLVE_FORM = 1, 2, 3, 4
 
 
 class RegionsParams(C.Structure):
@@ -886,6 +896,10 @@ PROTOTYPES = {
     "lom_posefield_solve": (_int, [_vp, _vp, _P(PoseFieldParams), _vp, _size, _vp, _size, _P(PoseFieldSummary)]),
     "lom_posefield_solve_device": (_int, [_vp, _vp, _vp, _P(PoseFieldParams), _vp, _size, _vp, _size, _P(PoseFieldSummary)]),
     "lom_posefield_solve_from_clearance": (_int, [_vp, _vp, _P(PoseFieldParams), _vp, _size, _vp, _size, _P(PoseFieldSummary)]),
+    "lom_posefield_resolve": (_int, [_vp, _vp, _P(ClearanceWindow), _P(PoseFieldSummary)]),
+    "lom_posefield_resolve_device": (_int, [_vp, _vp, _vp, _P(ClearanceWindow), _P(PoseFieldSummary)]),
+    "lom_posefield_resolve_from_clearance": (_int, [_vp, _vp, _P(ClearanceWindow), _P(PoseFieldSummary)]),
+    "lom_posefield_resolve_stats": (_int, [_vp, _P(PoseFieldResolveCounters)]),
     "lom_posefield_potential": (_int, [_vp, _vp, _size]),
     "lom_posefield_potential_device": (_int, [_vp, _P(_vp)]),
     "lom_posefield_layers": (_int, [_vp, _vp, _size]),

@@ -88,4 +88,17 @@ struct PoseLayerCells {
     }
 };
 
+// a rectangle of cells [x0, x1) x [y0, y1); empty where x0 >= x1 or y0 >= y1
+struct PoseBox {
+    uint32_t x0, y0, x1, y1;
+    bool empty() const { return x0 >= x1 || y0 >= y1; }
+};
+
+// the boxes of a re-solve's k_pose_relayer: per heading the states whose stencil can cover a changed cell, and the box that
+// holds the eight (posefield_host.cpp builds them)
+struct PoseBoxes {
+    PoseBox of[kPoseHeadings];
+    PoseBox all;
+};
+
 }  // namespace lom

@@ -2,13 +2,15 @@
 // plane; the floor over the headings, paths down the field and point queries.  Definitions: include/lidar_odometry_amd.h
 // ("pose field"); kernels: k_posefield.hpp; the move rule: pose_rule.hpp; host planning (value ranges, stencils, tile
 // counts, launch shapes): posefield_host.cpp; DESIGN.md 7u.  A handle family of its own on the PlaneHandle core
-// (plane_handle.hpp); the host loop to the fixed point is nav_fixed_point.hpp's.  No default path launches any of this.
+// (plane_handle.hpp); the host loop to the fixed point is nav_fixed_point.hpp's.  The re-solve after a local cost change
+// (k_posefield_resolve.hpp) keeps what a solve left and repairs it.  No default path launches any of this.
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
-#include "k_posefield.hpp"
+#include "k_posefield_resolve.hpp"
 #include "nav_fixed_point.hpp"
 #include "navfield_host.hpp"
 #include "plane_handle.hpp"
@@ -21,6 +23,7 @@ static_assert(posefield::kThreads == kPoseThreads && posefield::kTileX == kPoseT
               "posefield_host.hpp and k_posefield.hpp disagree");
 static_assert(LOM_NAV_UNREACHED == kPoseUnreached && LOM_NAV_MAX == kPoseMax, "the header and k_posefield.hpp disagree");
 static_assert((kPoseHeadings * kPoseHaloCells * 2u + 4u) * 4u <= 64u * 1024u, "the LDS of k_pose_relax stays at or below 64 KB");
+static_assert((size_t)QW_END * 4u <= 128u, "the words of a re-solve fit the block");
 
 // The field owns its stream and every buffer below.
 struct lom_posefield : lom::PlaneHandle {  // in_ev: the clearance grid's
@@ -35,7 +38,9 @@ struct lom_posefield : lom::PlaneHandle {  // in_ev: the clearance grid's
     lom::DeviceBuf stencil_first;    // 9 u32: where a heading's cells start
     lom::DeviceBuf marks;            // 2 x n_tiles u32: the tiles active in an even and in an odd launch
     lom::DeviceBuf flags;            // kBatchMax u32: "launch j of the batch marked a tile"
-    lom::DeviceBuf words;            // the summary words
+    lom::DeviceBuf words;            // the summary words, and behind them a re-solve's
+    lom::DeviceBuf seeds;            // n_tiles u32: the seeds of a re-solve's relaxation; empty until the first re-solve
+    lom::DeviceBuf incoming;         // the window's rows of a re-solve's host plane, grow-only
     lom::DeviceBuf points;           // goals or starts as int32 triples, grow-only
     lom::DeviceBuf path_states, path_lengths;  // a paths call's results, grow-only
     lom::DeviceBuf q_xy, q_h, q_out; // a query's points, headings and results, grow-only
@@ -44,8 +49,13 @@ struct lom_posefield : lom::PlaneHandle {  // in_ev: the clearance grid's
     uint32_t inner_cap = navfield::kInnerCapDefault;  // LOM_POSE_OPT_TEST_INNER_CAP
     uint32_t batch = navfield::kBatchDefault;         // LOM_POSE_OPT_TEST_BATCH
     uint32_t all_tiles = 0;                           // LOM_POSE_OPT_TEST_ALL_TILES
+    uint32_t resolve_form = 0;                        // LOM_POSE_OPT_TEST_RESOLVE_FORM
     PoseCosts costs{};               // of the last solve: what paths walk under
+    posefield::Stencils stencils{};  // of the last solve: what a re-solve dilates the changed box by
     lom_posefield_solve_stats stats{};
+    lom_posefield_resolve_counters resolve_stats{};
+    bool solved = false;             // a solve has completed since create, clear or shift: plane, layers and P are a fixed point
+    uint32_t last_words[PW_COUNT] = {};  // ... and its summary words: what a re-solve that changes nothing reports
 
     PoseArgs args() const { return PoseArgs{geo.width, geo.height, tiles.tiles_x, tiles.tiles_y}; }
     size_t n_states() const { return n_cells() * kPoseHeadings; }
@@ -97,14 +107,41 @@ const char *solve_refusal(bool have_plane, const lom_posefield_params *p, const 
     return nullptr;
 }
 
+// the relaxation from the marks of the first array to its fixed point
+int relax(lom_posefield *f, uint64_t &launches, uint64_t &waits)
+{
+    const PoseArgs a = f->args();
+    return to_fixed_point(f, f->tiles.n_tiles, launches, waits, "pose field: the relaxation did not settle",
+                          [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
+                              hipLaunchKernelGGL(k_pose_relax, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kPoseThreads), 0, f->stream,
+                                                 f->layers.as<const uint32_t>(), a, f->costs, f->inner_cap, f->all_tiles, f->field.as<uint32_t>(),
+                                                 cur, nxt, flag);
+                          });
+}
+
+// the summary of the field as it stands: the report, the way out of the first n_words words, done_ev, the wait.  The words
+// are in h_flags.
+int report(lom_posefield *f, uint32_t n_words)
+{
+    hipLaunchKernelGGL(k_pose_report, dim3(posefield::report_groups(f->n_cells())), dim3(kPoseThreads), 0, f->stream,
+                       f->plane.as<const int8_t>(), f->layers.as<const uint32_t>(), f->field.as<const uint32_t>(), f->args(), f->costs,
+                       f->floor.as<uint32_t>(), f->floor_heading.as<uint8_t>(), f->words.as<uint32_t>());
+    LOM_HIP(f, hipGetLastError());
+    LOM_HIP(f, hipMemcpyAsync(f->h_flags.h, f->words.p, (size_t)n_words * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    return LOM_OK;
+}
+
 // A solve over a plane in HBM that this stream may read now: the copy of the plane, the layers, the seed, the relaxation
 // in batches of launches with one wait each, the report, then the wait.  The arguments are valid.
 int solve_on_device(lom_posefield *f, const int8_t *d_plane, const lom_posefield_params &p, const int32_t *footprint, size_t n_samples,
                     const int32_t *goals, size_t n_goals, lom_posefield_summary *summary)
 {
     // what needs no device and what can still fail for want of memory come first: a refused call changes nothing
-    const posefield::Stencils st = posefield::stencils(footprint, n_samples);
+    posefield::Stencils st = posefield::stencils(footprint, n_samples);
     if (const int rc = n_goals ? ensure(f, f->points, n_goals * 12) : LOM_OK; rc != LOM_OK) return rc;
+    f->solved = false;
     // (every call waits for its work: nothing enqueued reads the staging block)
     uint32_t *const staging = f->h_table.as<uint32_t>();
     navfield::cell_costs(p.nav, staging);
@@ -132,20 +169,101 @@ int solve_on_device(lom_posefield *f, const int8_t *d_plane, const lom_posefield
         LOM_HIP(f, hipGetLastError());
     }
     f->stats = lom_posefield_solve_stats{0, 0, f->tiles.n_tiles};
-    const int rc = to_fixed_point(f, f->tiles.n_tiles, f->stats.launches, f->stats.waits, "pose field: the relaxation did not settle",
-                                  [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
-                                      hipLaunchKernelGGL(k_pose_relax, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kPoseThreads), 0, f->stream,
-                                                         layers, a, f->costs, f->inner_cap, f->all_tiles, f->field.as<uint32_t>(), cur, nxt, flag);
-                                  });
-    if (rc != LOM_OK) return rc;
-    hipLaunchKernelGGL(k_pose_report, dim3(posefield::report_groups(f->n_cells())), dim3(kPoseThreads), 0, f->stream,
-                       f->plane.as<const int8_t>(), layers, f->field.as<const uint32_t>(), a, f->costs, f->floor.as<uint32_t>(),
-                       f->floor_heading.as<uint8_t>(), f->words.as<uint32_t>());
-    LOM_HIP(f, hipGetLastError());
-    LOM_HIP(f, hipMemcpyAsync(f->h_flags.h, f->words.p, (size_t)PW_COUNT * 4, hipMemcpyDeviceToHost, f->stream));
-    LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
-    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    if (const int rc = relax(f, f->stats.launches, f->stats.waits); rc != LOM_OK) return rc;
+    if (const int rc = report(f, PW_COUNT); rc != LOM_OK) return rc;
+    std::memcpy(f->last_words, f->h_flags.h, sizeof f->last_words);
+    f->stencils = std::move(st);
+    f->solved = true;
     if (summary) summary_from(f->h_flags.as<uint32_t>(), summary);
+    return LOM_OK;
+}
+
+// the refusals of every re-solve form that need no device: the code and the text, or LOM_OK
+int resolve_refusal(lom_posefield *f, bool have_plane)
+{
+    if (!have_plane) return fail(f, LOM_ERR_ARG, "pose field re-solve: a cost plane");
+    if (!f->solved) return fail(f, LOM_ERR_STATE, "pose field re-solve: no solve has completed since create, clear or shift");
+    return LOM_OK;
+}
+
+// A re-solve from a plane in HBM that this stream may read now, over a window that is not empty: the diff and a wait; then,
+// where a cell changed, the layers over the dilated boxes, the raise phase to its fixed point (form 1: the layers over the
+// whole plane and the reset), the relaxation from the seeds to its fixed point, the report and the wait.  done_ev stands
+// behind the diff, the one reader of d_new.
+int resolve_on_device(lom_posefield *f, const int8_t *d_new, const clearance::Rect &r, lom_posefield_summary *summary)
+{
+    const PoseArgs a = f->args();
+    const uint32_t n_tiles = f->tiles.n_tiles, form = f->resolve_form;
+    // what can still fail for want of memory comes first: a refused call changes nothing
+    if (const int rc = ensure(f, f->seeds, (size_t)n_tiles * 4); rc != LOM_OK) return rc;
+    const int8_t *const plane = f->plane.as<const int8_t>();
+    const uint32_t *const table = f->table.as<const uint32_t>();
+    uint32_t *const layers = f->layers.as<uint32_t>(), *const field = f->field.as<uint32_t>(), *const words = f->words.as<uint32_t>();
+    uint32_t *const marks0 = f->marks.as<uint32_t>(), *const seeds = f->seeds.as<uint32_t>();
+    uint32_t *const h = f->h_flags.as<uint32_t>();
+    lom_posefield_resolve_counters &st = f->resolve_stats;
+    st = lom_posefield_resolve_counters{};
+    LOM_HIP(f, hipMemsetAsync(f->words.p, 0, (size_t)QW_END * 4, f->stream));
+    hipLaunchKernelGGL(k_pose_diff, dim3((r.x1 - r.x0 + kPoseTileX - 1u) / kPoseTileX, (r.y1 - r.y0 + kPoseTileY - 1u) / kPoseTileY),
+                       dim3(kPoseThreads), 0, f->stream, d_new, a, PoseBox{r.x0, r.y0, r.x1, r.y1}, f->plane.as<int8_t>(), words);
+    LOM_HIP(f, hipGetLastError());
+    f->solved = false;
+    LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
+    LOM_HIP(f, hipMemcpyAsync(h, f->words.p, (size_t)QW_END * 4, hipMemcpyDeviceToHost, f->stream));
+    LOM_HIP(f, hipStreamSynchronize(f->stream));
+    st.waits = 1;
+    st.cells_changed = h[QW_CHANGED];
+    uint32_t rejected = 0u;
+    if (st.cells_changed != 0u) {
+        const PoseBoxes boxes = posefield::relayer_boxes(f->stencils, PoseBox{~h[QW_X0_INV], ~h[QW_Y0_INV], h[QW_X1], h[QW_Y1]}, a.width, a.height);
+        LOM_HIP(f, hipMemsetAsync(f->marks.p, 0, (size_t)2 * n_tiles * 4, f->stream));
+        LOM_HIP(f, hipMemsetAsync(f->seeds.p, 0, (size_t)n_tiles * 4, f->stream));
+        // form 0: the seeds gather from here on, and the raise phase starts from the same tiles; form 1: the goal states'
+        // tiles are the seeds, and this launch only counts and takes the goal states that became impassable
+        if (!boxes.all.empty()) {
+            const size_t lanes = (size_t)(boxes.all.x1 - boxes.all.x0) * (boxes.all.y1 - boxes.all.y0);
+            hipLaunchKernelGGL(k_pose_relayer, dim3(posefield::blocks_for(lanes), kPoseHeadings), dim3(kPoseThreads), 0, f->stream, plane, table, a,
+                               f->stencil_cells.as<const uint32_t>(), f->stencil_first.as<const uint32_t>(), boxes, layers, field,
+                               form == 0u ? marks0 : nullptr, form == 0u ? seeds : nullptr, words);
+            LOM_HIP(f, hipGetLastError());
+        }
+        if (form == 0u) {
+            const int rc = to_fixed_point(f, n_tiles, st.raise_launches, st.waits, "pose field: the raise phase did not settle",
+                                          [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
+                                              hipLaunchKernelGGL(k_pose_raise, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kPoseThreads), 0,
+                                                                 f->stream, layers, a, f->costs, f->inner_cap, f->all_tiles, field, cur, nxt, seeds,
+                                                                 flag, words);
+                                          });
+            if (rc != LOM_OK) return rc;
+            // (both arrays of the fixed point are clear: the seeds are the first launch's marks)
+            LOM_HIP(f, hipMemcpyAsync(marks0, seeds, (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, f->stream));
+        } else {
+            hipLaunchKernelGGL(k_pose_layers, dim3(posefield::blocks_for(f->n_cells()), kPoseHeadings), dim3(kPoseThreads), 0, f->stream, plane,
+                               table, a, f->stencil_cells.as<const uint32_t>(), f->stencil_first.as<const uint32_t>(), layers);
+            LOM_HIP(f, hipGetLastError());
+            hipLaunchKernelGGL(k_pose_reseed, dim3(posefield::blocks_for(f->n_cells())), dim3(kPoseThreads), 0, f->stream, a, field, marks0, words);
+            LOM_HIP(f, hipGetLastError());
+        }
+        if (const int rc = relax(f, st.relax_launches, st.waits); rc != LOM_OK) return rc;
+        if (const int rc = report(f, QW_END); rc != LOM_OK) return rc;
+        st.waits++;
+        st.states_changed = h[QW_STATES], st.states_raised = h[QW_RAISED], st.tiles_marked = h[QW_TILES];
+        rejected = h[PW_GOALS_REJECTED];
+        h[PW_GOALS_USED] = f->last_words[PW_GOALS_USED] - rejected;  // (the report counts states: the goals are the host's to keep)
+        std::memcpy(f->last_words, h, sizeof f->last_words);
+    }
+    f->last_words[PW_GOALS_REJECTED] = rejected;
+    f->solved = true;
+    if (summary) summary_from(f->last_words, summary);
+    return LOM_OK;
+}
+
+// the summary of a re-solve over an empty window: the field as it stands, no goal rejected
+int resolve_nothing(lom_posefield *f, lom_posefield_summary *summary)
+{
+    f->resolve_stats = lom_posefield_resolve_counters{};
+    f->last_words[PW_GOALS_REJECTED] = 0u;
+    if (summary) summary_from(f->last_words, summary);
     return LOM_OK;
 }
 
@@ -169,7 +287,7 @@ int lom_posefield_create(const lom_occupancy_geometry *geometry, int device, lom
          alloc(f->floor_heading, n) != hipSuccess || alloc(f->plane, n) != hipSuccess || alloc(f->table, 256 * 4) != hipSuccess ||
          alloc(f->stencil_cells, kStencilWords * 4) != hipSuccess || alloc(f->stencil_first, 16 * 4) != hipSuccess ||
          alloc(f->marks, (size_t)2 * f->tiles.n_tiles * 4) != hipSuccess || alloc(f->flags, (size_t)navfield::kBatchMax * 4) != hipSuccess ||
-         alloc(f->words, 64) != hipSuccess))
+         alloc(f->words, 128) != hipSuccess))
         rc = create_fail(g_posefield_create_error, LOM_ERR_OOM, "hipMalloc (pose field)");
     if (rc == LOM_OK) {
         if (fill(f, true) != LOM_OK || (e = hipStreamSynchronize(f->stream)) != hipSuccess)
@@ -191,6 +309,7 @@ int lom_posefield_clear(lom_posefield *f)
     if (!f) return LOM_ERR_ARG;
     LOM_HIP(f, hipSetDevice(f->device));
     f->costs = PoseCosts{};
+    f->solved = false;
     if (const int rc = fill(f, true); rc != LOM_OK) return rc;
     LOM_HIP(f, hipStreamSynchronize(f->stream));
     return LOM_OK;
@@ -217,6 +336,10 @@ int lom_posefield_set_option(lom_posefield *f, int option, int64_t value)
     case LOM_POSE_OPT_TEST_ALL_TILES:
         if (value > 1) return fail(f, LOM_ERR_ARG, "LOM_POSE_OPT_TEST_ALL_TILES: 0, 1, or < 0 for the default");
         f->all_tiles = value == 1 ? 1u : 0u;
+        return LOM_OK;
+    case LOM_POSE_OPT_TEST_RESOLVE_FORM:
+        if (value > 1) return fail(f, LOM_ERR_ARG, "LOM_POSE_OPT_TEST_RESOLVE_FORM: 0, 1, or < 0 for the default");
+        f->resolve_form = value == 1 ? 1u : 0u;
         return LOM_OK;
     default:
         return fail(f, LOM_ERR_ARG, "unknown pose field option");
@@ -267,6 +390,63 @@ int lom_posefield_solve_from_clearance(lom_posefield *f, lom_clearance *clearanc
     if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
     if ((rc = solve_on_device(f, d_plane, *params, footprint, n_samples, goals, n_goals, summary)) != LOM_OK) return rc;
     return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
+}
+
+int lom_posefield_resolve_device(lom_posefield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_clearance_window *window_or_null,
+                                 lom_posefield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const int rc = resolve_refusal(f, d_plane != nullptr); rc != LOM_OK) return rc;
+    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
+    if (r.empty()) return resolve_nothing(f, summary);
+    LOM_HIP(f, hipSetDevice(f->device));
+    if (hip_event_or_null) LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event_or_null, 0));
+    return resolve_on_device(f, d_plane, r, summary);
+}
+
+int lom_posefield_resolve(lom_posefield *f, const int8_t *plane, const lom_clearance_window *window_or_null, lom_posefield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const int rc = resolve_refusal(f, plane != nullptr); rc != LOM_OK) return rc;
+    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
+    if (r.empty()) return resolve_nothing(f, summary);
+    LOM_HIP(f, hipSetDevice(f->device));
+    // the rows of the window, whole, at their place in a plane of the device: the cells outside the window are not read
+    if (const int rc = ensure(f, f->incoming, f->n_cells()); rc != LOM_OK) return rc;
+    const size_t first = (size_t)r.y0 * f->geo.width, bytes = (size_t)(r.y1 - r.y0) * f->geo.width;
+    LOM_HIP(f, hipMemcpyAsync(f->incoming.as<int8_t>() + first, plane + first, bytes, hipMemcpyHostToDevice, f->stream));
+    return resolve_on_device(f, f->incoming.as<const int8_t>(), r, summary);
+}
+
+int lom_posefield_resolve_from_clearance(lom_posefield *f, lom_clearance *clearance, const lom_clearance_window *window_or_null,
+                                         lom_posefield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const int rc = resolve_refusal(f, clearance != nullptr); rc != LOM_OK) return rc;
+    lom_occupancy_geometry g{};
+    (void)lom_clearance_get_geometry(clearance, &g);
+    int rc = plane_check_producer(f, kName, "clearance grid", g, lom_clearance_device(clearance));
+    if (rc != LOM_OK) return rc;
+    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
+    if (r.empty()) return resolve_nothing(f, summary);
+    LOM_HIP(f, hipSetDevice(f->device));
+    // the hand-off of plane_handle.hpp: read behind the clearance grid, re-solve, release to it
+    const int8_t *d_plane = nullptr;
+    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
+        return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
+    if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
+    if ((rc = resolve_on_device(f, d_plane, r, summary)) != LOM_OK) return rc;
+    return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
+}
+
+int lom_posefield_resolve_stats(const lom_posefield *f, lom_posefield_resolve_counters *out)
+{
+    if (!f || !out) return LOM_ERR_ARG;
+    *out = f->resolve_stats;
+    return LOM_OK;
 }
 
 int lom_posefield_potential(lom_posefield *f, uint32_t *out, size_t cap)

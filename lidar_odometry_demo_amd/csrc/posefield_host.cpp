@@ -12,7 +12,8 @@
 namespace lom {
 namespace posefield {
 
-static_assert(sizeof(lom_posefield_params) == 36 && sizeof(lom_posefield_summary) == 72 && sizeof(lom_posefield_solve_stats) == 24,
+static_assert(sizeof(lom_posefield_params) == 36 && sizeof(lom_posefield_summary) == 72 && sizeof(lom_posefield_solve_stats) == 24 &&
+                  sizeof(lom_posefield_resolve_counters) == 56,
               "the layouts the header documents");
 static_assert(kMaxCost == navfield::kMaxCellCost, "a layer value is a cell cost");
 
@@ -55,6 +56,30 @@ Stencils stencils(const int32_t *footprint, size_t f)
         st.first[h + 1] = st.first[h] + (uint32_t)cells.size();
     }
     return st;
+}
+
+PoseBoxes relayer_boxes(const Stencils &st, const PoseBox &changed, uint32_t width, uint32_t height)
+{
+    PoseBoxes b{};
+    const int64_t cx0 = changed.x0, cy0 = changed.y0, cx1 = std::min(changed.x1, width), cy1 = std::min(changed.y1, height);
+    if (cx0 >= cx1 || cy0 >= cy1) return b;
+    int64_t ax0 = width, ay0 = height, ax1 = 0, ay1 = 0;
+    for (uint32_t h = 0; h < kPoseHeadings; h++) {
+        if (!st.count(h)) continue;
+        int64_t lo_x = INT32_MAX, hi_x = INT32_MIN, lo_y = INT32_MAX, hi_y = INT32_MIN;  // the extents of the stencil
+        for (uint32_t k = st.first[h]; k < st.first[h + 1]; k++) {
+            const int64_t dx = st.cells[2 * (size_t)k], dy = st.cells[2 * (size_t)k + 1];
+            lo_x = std::min(lo_x, dx), hi_x = std::max(hi_x, dx), lo_y = std::min(lo_y, dy), hi_y = std::max(hi_y, dy);
+        }
+        // x + dx in [cx0, cx1) for some dx in [lo_x, hi_x]: x in [cx0 - hi_x, cx1 - lo_x)
+        const int64_t x0 = std::max<int64_t>(0, cx0 - hi_x), x1 = std::min<int64_t>(width, cx1 - lo_x);
+        const int64_t y0 = std::max<int64_t>(0, cy0 - hi_y), y1 = std::min<int64_t>(height, cy1 - lo_y);
+        if (x0 >= x1 || y0 >= y1) continue;
+        b.of[h] = PoseBox{(uint32_t)x0, (uint32_t)y0, (uint32_t)x1, (uint32_t)y1};
+        ax0 = std::min(ax0, x0), ay0 = std::min(ay0, y0), ax1 = std::max(ax1, x1), ay1 = std::max(ay1, y1);
+    }
+    if (ax0 < ax1 && ay0 < ay1) b.all = PoseBox{(uint32_t)ax0, (uint32_t)ay0, (uint32_t)ax1, (uint32_t)ay1};
+    return b;
 }
 
 TileGrid tile_grid(uint32_t width, uint32_t height)

@@ -44,6 +44,11 @@ struct Stencils {
     uint32_t count(uint32_t h) const { return first[h + 1] - first[h]; }
 };
 Stencils stencils(const int32_t *footprint, size_t f);
+// A re-solve's k_pose_relayer: per heading the box of the cells (x, y) with (x + dx, y + dy) inside `changed` for some cell
+// (dx, dy) of that heading's stencil -- the bounding box of `changed` dilated by the mirrored stencil -- clipped to the grid
+// (empty where nothing of it is inside), and `all`, the box that holds the eight (empty where all are).  `changed` is
+// clipped to the grid first; an empty one gives empty boxes.
+PoseBoxes relayer_boxes(const Stencils &st, const PoseBox &changed, uint32_t width, uint32_t height);
 
 // k_pose_relax: a workgroup per tile, tiles_x x tiles_y of them; the last column and row may be cut
 struct TileGrid {
