@@ -12,14 +12,7 @@
 #include <string>
 #include <vector>
 
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
+#include "check.hpp"
 
 #ifdef ASSEMBLE_HOST_STANDALONE
 #include "assemble_host.hpp"
@@ -135,9 +128,7 @@ int main()
     double R[9];
     CHECK(lom_graph_pose_rotation_matrix(&ident, R) == LOM_OK && R[0] == 1.0 && R[4] == 1.0 && R[8] == 1.0 && R[1] == 0.0);
     CHECK(lom_graph_pose_rotation_matrix(nullptr, R) == LOM_ERR_ARG && lom_graph_pose_rotation_matrix(&ident, nullptr) == LOM_ERR_ARG);
-    if (g_failed) return 1;
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }
 #else
 #include "lidar_odometry_amd.hpp"
@@ -191,8 +182,6 @@ int main()
         a.clear();
         CHECK(a.size() == 0 && a.pointCount() == 0);
     }
-    if (g_failed) return 1;
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }
 #endif

@@ -6,18 +6,10 @@
 #include <cstring>
 #include <vector>
 
+#include "check.hpp"
 #include "lidar_odometry_amd.hpp"
 
 using namespace lom;
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            g_fail++;                                                      \
-        }                                                                  \
-    } while (0)
 
 static Quaternionf angleAxis(float angle, float ax, float ay, float az)
 {
@@ -74,28 +66,27 @@ int main()
         }
         CloudMatcher batch, single;
         const std::vector<Pose3D> got = batch.alignBatch(keyframe, ptrs, guesses);
-        EXPECT(got.size() == guess_poses.size() && batch.batch_stats.size() == guess_poses.size());
+        CHECK(got.size() == guess_poses.size() && batch.batch_stats.size() == guess_poses.size());
         std::vector<lom_align_stats> singles;
         for (size_t i = 0; i < guess_poses.size() && i < got.size(); i++) {
             const Pose3D want = single.align(keyframe, *clouds[i], Pose3D());
             singles.push_back(single.last_stats);
-            EXPECT(same_bits(got[i], want));
+            CHECK(same_bits(got[i], want));
             const lom_align_stats &a = batch.batch_stats[i], &b = single.last_stats;
-            EXPECT(a.outer_iterations == b.outer_iterations && a.lm_iterations == b.lm_iterations);
-            EXPECT(a.evaluations == b.evaluations && a.queries == b.queries && a.valid_last == b.valid_last);
-            EXPECT(std::memcmp(&a.final_cost, &b.final_cost, 8) == 0 && std::memcmp(&a.last_step_norm, &b.last_step_norm, 8) == 0);
-            EXPECT(a.host_fallback == 0 && a.lm_workgroups == b.lm_workgroups);
-            EXPECT(got[i].relativeTo(guess_poses[i]).translation.norm() < 0.05);  // test.cpp:261
+            CHECK(a.outer_iterations == b.outer_iterations && a.lm_iterations == b.lm_iterations);
+            CHECK(a.evaluations == b.evaluations && a.queries == b.queries && a.valid_last == b.valid_last);
+            CHECK(std::memcmp(&a.final_cost, &b.final_cost, 8) == 0 && std::memcmp(&a.last_step_norm, &b.last_step_norm, 8) == 0);
+            CHECK(a.host_fallback == 0 && a.lm_workgroups == b.lm_workgroups);
+            CHECK(got[i].relativeTo(guess_poses[i]).translation.norm() < 0.05);  // test.cpp:261
         }
         std::vector<lom_align_result> r(singles.size());
         for (size_t i = 0; i < singles.size(); i++) r[i].stats = singles[i];
-        EXPECT(batch.best == lom_align_batch_best(r.data(), (int)r.size()));
+        CHECK(batch.best == lom_align_batch_best(r.data(), (int)r.size()));
         // nothing to do is not an error
-        EXPECT(batch.alignBatch(keyframe, {}, {}).empty() && batch.best == -1);
+        CHECK(batch.alignBatch(keyframe, {}, {}).empty() && batch.best == -1);
     } catch (const lom::Error &e) {
         std::printf("lom::Error %d: %s\n", e.code, e.what());
         return 2;
     }
-    std::printf(g_fail ? "FAILED (%d)\n" : "ALL PASSED\n", g_fail);
-    return g_fail ? 1 : 0;
+    return check_done();
 }

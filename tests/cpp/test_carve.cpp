@@ -2,6 +2,7 @@
 // size the carve leaves and the number of voxels it erased (tests/test_carve_gpu.py builds the same map and rays).
 #include <cstdio>
 
+#include "check.hpp"
 #include "lidar_odometry_amd.hpp"
 
 int main()
@@ -24,7 +25,8 @@ int main()
         p.max_range = 6.0f;
         p.min_crossings = 1;
         const lom_carve_stats st = grid.carveRays(lom::Vector3f(0.1f, 0.1f, 0.1f), rays, p);
-        if (st.rays_walked + st.rays_skipped != 12) return 2;
+        CHECK(st.rays_walked + st.rays_skipped == 12);
+        if (check_done()) return 1;
         std::printf("%zu %u\n", grid.size(), st.voxels_erased);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "%s\n", e.what());

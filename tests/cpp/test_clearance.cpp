@@ -7,16 +7,8 @@
 #include <limits>
 #include <vector>
 
+#include "check.hpp"
 #include "clearance_host.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 using namespace lom;
 using namespace lom::clearance;
@@ -184,10 +176,5 @@ int main()
     test_ranges();
     test_table();
     test_rectangles();
-    if (g_failed) {
-        std::printf("%d checks failed\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

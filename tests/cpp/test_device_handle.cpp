@@ -8,16 +8,8 @@
 #include <type_traits>
 #include <utility>
 
+#include "check.hpp"
 #include "device_handle.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 using namespace lom;
 
@@ -133,10 +125,5 @@ int main()
     test_empty_buffers<DeviceBuf>();
     test_empty_buffers<PinnedBuf>();
     test_errors();
-    if (g_failed) {
-        std::printf("%d check(s) failed\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

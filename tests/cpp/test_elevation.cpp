@@ -12,14 +12,7 @@
 #include <string>
 #include <vector>
 
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
+#include "check.hpp"
 
 #ifdef ELEVATION_HOST_STANDALONE
 #include "elevation_host.hpp"
@@ -200,12 +193,7 @@ int main()
         CHECK(pl.launches.empty() && pl.scans.scans.empty());
         CHECK(plan(nullptr, 0, nullptr, nullptr, 0, geo, nullptr, 0, pl, why) == LOM_ERR_ARG);  // the parameters count even then
     }
-    if (g_failed) {
-        std::printf("%d checks failed\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }
 
 #else
@@ -258,11 +246,8 @@ int main()
             threw = true;
         }
         CHECK(threw);
-        if (g_failed) {
-            std::printf("%d checks failed\n", g_failed);
-            return 1;
-        }
-        std::printf("ALL PASSED\n%llu %llu %llu\n", (unsigned long long)sm.cells_unknown, (unsigned long long)sm.cells_lethal,
+        if (check_done()) return 1;
+        std::printf("%llu %llu %llu\n", (unsigned long long)sm.cells_unknown, (unsigned long long)sm.cells_lethal,
                     (unsigned long long)sm.cells_costed);
         return 0;
     } catch (const std::exception &e) {

@@ -7,14 +7,7 @@
 #include <cstdlib>
 #include <vector>
 
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
+#include "check.hpp"
 
 #ifdef GRAPH_HOST_STANDALONE
 #include "graph_host.hpp"
@@ -88,9 +81,7 @@ int main()
     CHECK(x[5] == 1.0 && x[3] == 0.0);
     double lambda = 1.0, nu = 2.0, rho = 0.0;
     CHECK(lom_graph_lm_policy(10.0, 11.0, 3.0, &lambda, &nu, &rho) == 0 && lambda == 2.0 && nu == 4.0 && rho < 0.0);
-    if (g_failed) return 1;
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }
 #else
 #include "lidar_odometry_amd.hpp"
@@ -153,8 +144,6 @@ int main()
         const lom::GraphStats st = g.optimize(prm);
         CHECK(st.stop_reason == LOM_GRAPH_STOP_GRADIENT && g.poses().size() == 2 && g.chi2().size() == 1);
     }
-    if (g_failed) return 1;
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }
 #endif

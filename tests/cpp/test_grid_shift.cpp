@@ -11,17 +11,9 @@
 #include <type_traits>
 #include <vector>
 
+#include "check.hpp"
 #include "lidar_odometry_amd.hpp"
 #include "plane_geometry.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            if (g_failed < 20) std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 // every grid of the mirror has shift(dx, dy) (the signature is checked; nothing here needs a device)
 template <class G>
@@ -172,10 +164,5 @@ int main(int argc, char **argv)
     test_follow_table(f);
     std::fclose(f);
     test_follow_refusals();
-    if (g_failed) {
-        std::printf("%d checks FAILED\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

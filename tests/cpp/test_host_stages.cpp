@@ -15,21 +15,11 @@
 #include <thread>
 #include <vector>
 
+#include "check.hpp"
 #include "host_stages.hpp"
 #include "stage_words.hpp"
 
 using namespace lom;
-
-static int failures = 0;
-#define CHECK(cond, ...)                                  \
-    do {                                                  \
-        if (!(cond)) {                                    \
-            failures++;                                   \
-            std::printf("FAILED %s:%d  ", __FILE__, __LINE__); \
-            std::printf(__VA_ARGS__);                     \
-            std::printf("\n");                            \
-        }                                                 \
-    } while (0)
 
 // ---- the four stages, chained as the odometry chains them -----------------------------------------
 struct StageOutputs {
@@ -286,10 +276,5 @@ int main(int argc, char **argv)
         std::printf("usage: test_host_stages stages <frame.bin> | threads\n");
         return 2;
     }
-    if (failures) {
-        std::printf("%d check(s) FAILED\n", failures);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

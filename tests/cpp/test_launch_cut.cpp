@@ -8,18 +8,10 @@
 #include <string>
 #include <vector>
 
+#include "check.hpp"
 #include "elevation_host.hpp"
 #include "occupancy_host.hpp"
 #include "vote_host.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 using namespace lom;
 using assemble::Launch;
@@ -105,7 +97,5 @@ int main()
           same(two[2], Launch{6, 2, 300, 2}) && same(two[3], Launch{10, 2, 255, 1}));
     CHECK(all.size() == 1 && same(all[0], Launch{0, 12, 300, 2}));
     CHECK(assemble::cut_launches(assemble::Plan(), 1).empty() && assemble::cut_launches(assemble::Plan(), 64).empty());
-    if (g_failed) return 1;
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

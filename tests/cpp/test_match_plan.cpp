@@ -9,16 +9,8 @@
 #include <tuple>
 #include <vector>
 
+#include "check.hpp"
 #include "match_plan.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 using namespace lom;
 
@@ -360,7 +352,5 @@ int main()
         for (uint32_t &v : n) v = qn[pick(kinds)];
         check_quality(n, partition_cus, round_max);
     }
-    if (g_failed) return 1;
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

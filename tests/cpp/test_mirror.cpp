@@ -9,18 +9,10 @@
 
 #include <thread>
 
+#include "check.hpp"
 #include "lidar_odometry_amd.hpp"
 
 using namespace lom;
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            g_fail++;                                                      \
-        }                                                                  \
-    } while (0)
 
 static Quaternionf angleAxis(float angle, float ax, float ay, float az)
 {
@@ -35,13 +27,13 @@ static void VoxelGrid_UniquePoints()  // test.cpp:26-55
     for (auto &p : pts) input_cloud.points.emplace_back(p[0], p[1], p[2]);
     VoxelGrid voxel_grid(0.5, 1);
     voxel_grid.addCloud(input_cloud);
-    EXPECT(voxel_grid.size() == input_cloud.size());
+    CHECK(voxel_grid.size() == input_cloud.size());
     auto output_cloud = voxel_grid.getCloud();
-    EXPECT(input_cloud.size() == output_cloud->size());
+    CHECK(input_cloud.size() == output_cloud->size());
     for (const auto &o : output_cloud->points) {
         auto it = std::find_if(input_cloud.points.begin(), input_cloud.points.end(),
                                [&o](const PointNormal &i) { return o.x == i.x && o.y == i.y && o.z == i.z; });
-        EXPECT(it != input_cloud.points.end());
+        CHECK(it != input_cloud.points.end());
         if (it != input_cloud.points.end()) input_cloud.points.erase(it);
     }
 }
@@ -55,10 +47,10 @@ static void VoxelGrid_DuplicatePoints()  // test.cpp:57-75
     input_cloud.points.emplace_back(1, 0, 0);
     VoxelGrid voxel_grid(0.5, 1);
     voxel_grid.addCloud(input_cloud);
-    EXPECT(voxel_grid.size() == size_t(2));
+    CHECK(voxel_grid.size() == size_t(2));
     auto output_cloud = voxel_grid.getCloud();
-    EXPECT(output_cloud->size() == size_t(2));
-    EXPECT(!(output_cloud->points.at(0).x == output_cloud->points.at(1).x &&
+    CHECK(output_cloud->size() == size_t(2));
+    CHECK(!(output_cloud->points.at(0).x == output_cloud->points.at(1).x &&
              output_cloud->points.at(0).y == output_cloud->points.at(1).y &&
              output_cloud->points.at(0).z == output_cloud->points.at(1).z));
 }
@@ -68,14 +60,14 @@ static void Pose3D_ComposeRelativeInverse()  // test.cpp:77-149 (group identitie
     const Pose3D a({1, 0.5f, -0.5f}, angleAxis(0.456f, 0.0976f, 0.1952f, 0.9759f));
     const Pose3D b({-1, -0.6f, 0}, angleAxis(-0.245f, -1, 0, 0));
     const Pose3D id = a.compose(a.inverse());
-    EXPECT(std::fabs(id.translation.norm()) < 1e-5f);
-    EXPECT(std::fabs(std::fabs(id.rotation.dot(Quaternionf::Identity())) - 1.f) < 1e-6f);
+    CHECK(std::fabs(id.translation.norm()) < 1e-5f);
+    CHECK(std::fabs(std::fabs(id.rotation.dot(Quaternionf::Identity())) - 1.f) < 1e-6f);
     const Pose3D rel = a.relativeTo(b);  // a^-1 * b
     const Pose3D back = a.compose(rel);
-    EXPECT(std::fabs(back.translation.x() - b.translation.x()) < 1e-5f);
-    EXPECT(std::fabs(back.translation.y() - b.translation.y()) < 1e-5f);
-    EXPECT(std::fabs(back.translation.z() - b.translation.z()) < 1e-5f);
-    EXPECT(std::fabs(std::fabs(back.rotation.dot(b.rotation)) - 1.f) < 1e-6f);
+    CHECK(std::fabs(back.translation.x() - b.translation.x()) < 1e-5f);
+    CHECK(std::fabs(back.translation.y() - b.translation.y()) < 1e-5f);
+    CHECK(std::fabs(back.translation.z() - b.translation.z()) < 1e-5f);
+    CHECK(std::fabs(std::fabs(back.rotation.dot(b.rotation)) - 1.f) < 1e-6f);
 }
 
 static void CloudTransformer_RigidTransform()  // test.cpp:151-189
@@ -93,7 +85,7 @@ static void CloudTransformer_RigidTransform()  // test.cpp:151-189
         const float ex = R[0] * p.x + R[1] * p.y + R[2] * p.z + 1.f;
         const float ey = R[3] * p.x + R[4] * p.y + R[5] * p.z + 1.f;
         const float ez = R[6] * p.x + R[7] * p.y + R[8] * p.z + 1.f;
-        EXPECT(std::fabs(transformed->at(i).x - ex) < 1e-6f && std::fabs(transformed->at(i).y - ey) < 1e-6f &&
+        CHECK(std::fabs(transformed->at(i).x - ex) < 1e-6f && std::fabs(transformed->at(i).y - ey) < 1e-6f &&
                std::fabs(transformed->at(i).z - ez) < 1e-6f);
     }
 }
@@ -127,7 +119,7 @@ static void CloudMatcher_MatchingTest()  // protocol of test.cpp:226-262 on a sy
     VoxelGrid voxel_filter(0.5, 1);
     voxel_filter.addCloudWithoutNormals(full_cloud);
     auto subsampled_cloud = voxel_filter.getCloudWithoutNormals();
-    EXPECT(subsampled_cloud->size() > 3000);
+    CHECK(subsampled_cloud->size() > 3000);
 
     CloudMatcher matcher;
     const float d = 3.14159265358979f / 180.f;
@@ -145,9 +137,9 @@ static void CloudMatcher_MatchingTest()  // protocol of test.cpp:226-262 on a sy
         auto final_transform = matcher.align(keyframe, *guess_cloud, Pose3D());
         auto error = final_transform.relativeTo(guess_pose);
         const double rotation_error = 1.0 - std::fabs(final_transform.rotation.dot(guess_pose.rotation));
-        EXPECT(error.translation.norm() < 0.05);  // test.cpp:261
-        EXPECT(rotation_error < 0.01);            // test.cpp:262
-        EXPECT(matcher.last_stats.outer_iterations >= 5 && matcher.last_stats.outer_iterations <= 35);
+        CHECK(error.translation.norm() < 0.05);  // test.cpp:261
+        CHECK(rotation_error < 0.01);            // test.cpp:262
+        CHECK(matcher.last_stats.outer_iterations >= 5 && matcher.last_stats.outer_iterations <= 35);
     }
     // `const VoxelGrid&` (cloud_matcher.h:15-16): the seven guesses again, one thread each, all at once against the one
     // keyframe -- every thread must get the pose the serial loop above got for its guess, bit for bit
@@ -173,19 +165,19 @@ static void CloudMatcher_MatchingTest()  // protocol of test.cpp:226-262 on a sy
             for (int k = 0; k < 4; k++) same = same && serial[i].rotation.q[k] == parallel[i].rotation.q[k];
             equal += same;
             const double terr = parallel[i].relativeTo(guess_poses[i]).translation.norm();
-            EXPECT(terr < 0.05);
+            CHECK(terr < 0.05);
         }
-        EXPECT(equal >= (int)guess_poses.size() - 1);  // (a solve that found the GPU too full redoes itself host-driven: 1e-6)
+        CHECK(equal >= (int)guess_poses.size() - 1);  // (a solve that found the GPU too full redoes itself host-driven: 1e-6)
     }
     // findMatchingPairs / getCorrespondence shapes
     auto pairs = keyframe.findMatchingPairs(*subsampled_cloud, Pose3D(), 0.3f);
-    EXPECT(!pairs.empty() && pairs.size() <= subsampled_cloud->size());
+    CHECK(!pairs.empty() && pairs.size() <= subsampled_cloud->size());
     auto c = keyframe.getCorrespondence(Vector3f(12.5f, 12.5f, 1.02f), 0.3f * 0.3f);
-    EXPECT(c.valid && std::fabs(c.plane_normal[2] - 1.0) < 1e-6 && std::fabs(c.plane_origin[2] - 1.0) < 1e-6);
+    CHECK(c.valid && std::fabs(c.plane_normal[2] - 1.0) < 1e-6 && std::fabs(c.plane_origin[2] - 1.0) < 1e-6);
     // radiusCleanup keeps the voxels whose first point is within the radius (voxel_grid.h:236-246)
     const size_t before = keyframe.size();
     keyframe.radiusCleanup(Vector3f(2, 2, 1), 5.0f);
-    EXPECT(keyframe.size() < before && keyframe.size() > 0);
+    CHECK(keyframe.size() < before && keyframe.size() > 0);
 }
 
 // LidarOdometry (lidar_odometry.h:65-76) over a synthetic room: 16 beams x 900 azimuth steps ray-cast
@@ -224,17 +216,17 @@ static void LidarOdometry_RoomSequence()
         }
         odometry.processCloud(cloud);
         const auto st = odometry.lastFrameStats();
-        EXPECT(st.planar_points > 2000 && st.filtered_points > 1000);
-        if (f == 0) EXPECT(st.initialised_keyframe == 1);
-        if (f > 0) EXPECT(st.outer_iterations >= 5 && st.matching_points > 200);
+        CHECK(st.planar_points > 2000 && st.filtered_points > 1000);
+        if (f == 0) CHECK(st.initialised_keyframe == 1);
+        if (f > 0) CHECK(st.outer_iterations >= 5 && st.matching_points > 200);
     }
     const Pose3D pose = odometry.getCurrentPose();
-    EXPECT(std::fabs(pose.translation.x() - 0.1f * (float)(n_frames - 1)) < 0.1f);
-    EXPECT(std::fabs(pose.translation.y()) < 0.05f && std::fabs(pose.translation.z()) < 0.05f);
-    EXPECT(std::fabs(pose.rotation.w()) > 0.9999f);
+    CHECK(std::fabs(pose.translation.x() - 0.1f * (float)(n_frames - 1)) < 0.1f);
+    CHECK(std::fabs(pose.translation.y()) < 0.05f && std::fabs(pose.translation.z()) < 0.05f);
+    CHECK(std::fabs(pose.rotation.w()) > 0.9999f);
     auto sparse = odometry.getKeyFrameCloud();
     auto full = odometry.getFullKeyFrameCloud();
-    EXPECT(sparse->size() > 1000 && full->size() >= sparse->size());
+    CHECK(sparse->size() > 1000 && full->size() >= sparse->size());
 }
 
 // The reference's own orchestration (src/lidar_odometry.cpp:22-77), written with the mirror's classes exactly as the
@@ -317,28 +309,28 @@ static void ReferenceOrchestration_EqualsLidarOdometry()
         const auto cloud = room_frame(0.1f * (float)f);
         // the stages on their own: sizes and value ranges
         auto normalized = utils::pointTimeNormalize(cloud);
-        EXPECT(normalized->size() == cloud.size());
+        CHECK(normalized->size() == cloud.size());
         float tmin = 1e9f, tmax = -1e9f;
         for (const auto &p : normalized->points) tmin = std::fmin(tmin, p.time), tmax = std::fmax(tmax, p.time);
-        EXPECT(tmin == 0.f && tmax == 1.f);
+        CHECK(tmin == 0.f && tmax == 1.f);
         auto [planar, rest] = CloudClassifier::classify(*normalized);
-        EXPECT(planar->size() > 2000 && planar->size() + rest->size() <= 16 * 900);
+        CHECK(planar->size() > 2000 && planar->size() + rest->size() <= 16 * 900);
         for (size_t i = 0; i < planar->size(); i += 97) {
             const auto &p = planar->points[i];
             const float nn = p.normal_x * p.normal_x + p.normal_y * p.normal_y + p.normal_z * p.normal_z;
-            EXPECT(std::fabs(nn - 1.f) < 1e-4f);
+            CHECK(std::fabs(nn - 1.f) < 1e-4f);
         }
         auto near = utils::rangeFilter(*planar, 0.f, 10.f);
-        EXPECT(near->size() > 0 && near->size() < planar->size());
-        for (const auto &p : near->points) EXPECT(p.x * p.x + p.y * p.y + p.z * p.z <= 100.f);
+        CHECK(near->size() > 0 && near->size() < planar->size());
+        for (const auto &p : near->points) CHECK(p.x * p.x + p.y * p.y + p.z * p.z <= 100.f);
         // the two orchestrations
         odometry.processCloud(cloud);
         by_hand.processCloud(cloud);
         const Pose3D a = odometry.getCurrentPose(), b = by_hand.current_transform_;
-        for (int k = 0; k < 3; k++) EXPECT(a.translation.v[k] == b.translation.v[k]);
-        for (int k = 0; k < 4; k++) EXPECT(a.rotation.q[k] == b.rotation.q[k]);
+        for (int k = 0; k < 3; k++) CHECK(a.translation.v[k] == b.translation.v[k]);
+        for (int k = 0; k < 4; k++) CHECK(a.rotation.q[k] == b.rotation.q[k]);
     }
-    EXPECT((size_t)odometry.lastFrameStats().keyframe_voxels == by_hand.keyframe_.size());
+    CHECK((size_t)odometry.lastFrameStats().keyframe_voxels == by_hand.keyframe_.size());
 }
 
 int main()
@@ -355,6 +347,5 @@ int main()
         std::printf("lom::Error %d: %s\n", e.code, e.what());
         return 2;
     }
-    std::printf(g_fail ? "FAILED (%d)\n" : "ALL PASSED\n", g_fail);
-    return g_fail ? 1 : 0;
+    return check_done();
 }

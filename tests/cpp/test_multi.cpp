@@ -7,18 +7,10 @@
 #include <cstring>
 #include <vector>
 
+#include "check.hpp"
 #include "lidar_odometry_amd.hpp"
 
 using namespace lom;
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            g_fail++;                                                      \
-        }                                                                  \
-    } while (0)
 
 static Quaternionf angleAxis(float angle, float ax, float ay, float az)
 {
@@ -105,17 +97,17 @@ int main()
         }
         CloudMatcher multi, single;
         const std::vector<Pose3D> got = multi.alignMulti(keyframes, ptrs, guesses);
-        EXPECT(got.size() == truths.size() && multi.batch_stats.size() == truths.size());
+        CHECK(got.size() == truths.size() && multi.batch_stats.size() == truths.size());
         for (size_t i = 0; i < truths.size() && i < got.size(); i++) {
             const Pose3D want = single.align(*keyframes[i], *clouds[i], Pose3D());
-            EXPECT(same_bits(got[i], want));
+            CHECK(same_bits(got[i], want));
             const lom_align_stats &a = multi.batch_stats[i], &b = single.last_stats;
-            EXPECT(a.outer_iterations == b.outer_iterations && a.lm_iterations == b.lm_iterations);
-            EXPECT(a.evaluations == b.evaluations && a.queries == b.queries && a.valid_last == b.valid_last);
-            EXPECT(std::memcmp(&a.final_cost, &b.final_cost, 8) == 0 && std::memcmp(&a.last_step_norm, &b.last_step_norm, 8) == 0);
-            EXPECT(a.host_fallback == 0 && a.lm_workgroups == b.lm_workgroups);
+            CHECK(a.outer_iterations == b.outer_iterations && a.lm_iterations == b.lm_iterations);
+            CHECK(a.evaluations == b.evaluations && a.queries == b.queries && a.valid_last == b.valid_last);
+            CHECK(std::memcmp(&a.final_cost, &b.final_cost, 8) == 0 && std::memcmp(&a.last_step_norm, &b.last_step_norm, 8) == 0);
+            CHECK(a.host_fallback == 0 && a.lm_workgroups == b.lm_workgroups);
         }
-        EXPECT(multi.alignMulti({}, {}, {}).empty() && multi.best == -1);
+        CHECK(multi.alignMulti({}, {}, {}).empty() && multi.best == -1);
 
         // ---- processBatch: two streams in two rooms against the same frames through processCloud ----
         LidarOdometry::Params prm;
@@ -126,7 +118,7 @@ int main()
             const LidarOdometry::CloudType fa = room_scan(0.15f * (float)f, 0.f, 30.f, 20.f);
             const LidarOdometry::CloudType fb = room_scan(0.f, 0.1f * (float)f, 25.f, 35.f);
             const std::vector<int> st = LidarOdometry::processBatch(both, {&fa, &fb});
-            EXPECT(st.size() == 2 && st[0] == LOM_OK && st[1] == LOM_OK);
+            CHECK(st.size() == 2 && st[0] == LOM_OK && st[1] == LOM_OK);
             sa.processCloud(fa);
             sb.processCloud(fb);
             ok = ok && same_bits(a.getCurrentPose(), sa.getCurrentPose()) && same_bits(b.getCurrentPose(), sb.getCurrentPose());
@@ -134,8 +126,8 @@ int main()
             ok = ok && x.matching_points == y.matching_points && x.queries == y.queries &&
                  x.outer_iterations == y.outer_iterations && x.keyframe_voxels == y.keyframe_voxels;
         }
-        EXPECT(ok);
-        EXPECT(a.getKeyFrameCloud()->points.size() == sa.getKeyFrameCloud()->points.size());
+        CHECK(ok);
+        CHECK(a.getKeyFrameCloud()->points.size() == sa.getKeyFrameCloud()->points.size());
         // the same odometry twice is refused before anything moves
         const LidarOdometry::CloudType fa = room_scan(1.f, 0.f, 30.f, 20.f);
         bool threw = false;
@@ -144,12 +136,11 @@ int main()
         } catch (const lom::Error &e) {
             threw = e.code == LOM_ERR_ARG;
         }
-        EXPECT(threw);
-        EXPECT(same_bits(a.getCurrentPose(), sa.getCurrentPose()));
+        CHECK(threw);
+        CHECK(same_bits(a.getCurrentPose(), sa.getCurrentPose()));
     } catch (const lom::Error &e) {
         std::printf("lom::Error %d: %s\n", e.code, e.what());
         return 2;
     }
-    std::printf(g_fail ? "FAILED (%d)\n" : "ALL PASSED\n", g_fail);
-    return g_fail ? 1 : 0;
+    return check_done();
 }

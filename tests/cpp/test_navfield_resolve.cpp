@@ -2,21 +2,13 @@
 // navfield::tile_range (csrc/navfield_host.cpp) against a count of the tiles that hold a cell of the clipped window.
 // Plain C++: no HIP header is on the include path.
 #include <cstdio>
-#include <cstdlib>
 #include <initializer_list>
 
+#include "check.hpp"
 #include "clearance_host.hpp"
 #include "navfield_host.hpp"
 
 using namespace lom;
-
-#define CHECK(c)                                                         \
-    do {                                                                 \
-        if (!(c)) {                                                      \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); \
-            std::exit(1);                                                \
-        }                                                                \
-    } while (0)
 
 static void check_window(uint32_t w, uint32_t h, const lom_clearance_window *win)
 {
@@ -61,6 +53,5 @@ int main()
     CHECK(navfield::tile_range(clearance::clip(&outside, g)).n_tx == 0 && navfield::tile_range(clearance::clip(&far, g)).n_ty == 0);
     t = navfield::tile_range(clearance::clip(nullptr, g));
     CHECK(t.tx0 == 0 && t.ty0 == 0 && t.n_tx == 5 && t.n_ty == 3);
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

@@ -10,17 +10,9 @@
 #include <cstring>
 #include <vector>
 
+#include "check.hpp"
 #include "nav_los_rule.hpp"
 #include "navfield_host.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 using namespace lom;
 using namespace lom::navfield;
@@ -110,10 +102,6 @@ int main(int argc, char **argv)
     }
     std::fclose(in);
     if (std::fclose(out) != 0) return 2;
-    if (g_failed) {
-        std::printf("%d checks failed\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED %u cases, %zu pairs visible\n", n_cases, n_seen);
-    return 0;
+    std::printf("%u cases, %zu pairs visible\n", n_cases, n_seen);
+    return check_done();
 }

@@ -6,16 +6,8 @@
 #include <cstring>
 #include <vector>
 
+#include "check.hpp"
 #include "navset_host.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 using namespace lom;
 using namespace lom::navset;
@@ -125,10 +117,5 @@ int main()
     test_sizes_and_shapes();
     test_gather_and_paths();
     test_summary();
-    if (g_failed) {
-        std::printf("%d checks FAILED\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

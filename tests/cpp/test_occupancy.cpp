@@ -12,14 +12,7 @@
 #include <string>
 #include <vector>
 
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
+#include "check.hpp"
 
 #ifdef OCCUPANCY_HOST_STANDALONE
 #include "occupancy_host.hpp"
@@ -258,12 +251,7 @@ int main()
         CHECK(lom::occupancy::plan(table.data(), table.size(), ids.data(), poses.data(), 1, geo, &good, 0, plan, why) == LOM_OK);
         CHECK(plan.slices.empty() && plan.scans.scans.size() == 1 && plan.scans.points_in == 0);
     }
-    if (g_failed) {
-        std::printf("%d checks failed\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }
 
 #else
@@ -311,11 +299,8 @@ int main()
             threw = true;
         }
         CHECK(threw);
-        if (g_failed) {
-            std::printf("%d checks failed\n", g_failed);
-            return 1;
-        }
-        std::printf("ALL PASSED\n%llu %llu\n", (unsigned long long)sm.cells_free, (unsigned long long)sm.cells_occupied);
+        if (check_done()) return 1;
+        std::printf("%llu %llu\n", (unsigned long long)sm.cells_free, (unsigned long long)sm.cells_occupied);
         return 0;
     } catch (const std::exception &e) {
         std::printf("exception: %s\n", e.what());

@@ -10,19 +10,11 @@
 #include <cstdio>
 #include <random>
 
+#include "check.hpp"
 #include "k_eval.hpp"
 
 using namespace lom;
 typedef long double ld;
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 // residual and the three rotation columns of the tangent Jacobian in long double, as the reference writes them:
 // Eigen's quaternion * vector for the residual, the four dR/dq_k matrices, then Ceres' 4x3 plus-Jacobian
@@ -263,10 +255,5 @@ int main()
     test_point_terms(4800);
     test_huber(4000);
     test_sums();
-    if (g_failed) {
-        std::printf("%d CHECKS FAILED\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

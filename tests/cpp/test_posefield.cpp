@@ -8,16 +8,8 @@
 #include <cstring>
 #include <vector>
 
+#include "check.hpp"
 #include "posefield_host.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 using namespace lom;
 using namespace lom::posefield;
@@ -213,10 +205,5 @@ int main()
     test_moves();
     test_params_and_footprints();
     test_shapes();
-    if (g_failed) {
-        std::printf("%d checks failed\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

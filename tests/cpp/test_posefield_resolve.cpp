@@ -7,18 +7,10 @@
 #include <cstdlib>
 #include <vector>
 
+#include "check.hpp"
 #include "posefield_host.hpp"
 
 using namespace lom;
-
-static int g_failed = 0;
-#define CHECK(c)                                                   \
-    do {                                                           \
-        if (!(c)) {                                                \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); \
-            g_failed++;                                            \
-        }                                                          \
-    } while (0)
 
 // xs = -back, -back + spacing, ... while < front, then front; ys likewise: the rectangle lattice of the tests' footprints
 static std::vector<int32_t> rectangle(int front, int back, int half, int spacing)
@@ -127,7 +119,5 @@ int main()
     const PoseBoxes p = posefield::relayer_boxes(posefield::stencils(point, 1), PoseBox{5, 6, 9, 8}, 65, 17);
     for (const PoseBox &g : p.of) CHECK(g.x0 == 5 && g.y0 == 6 && g.x1 == 9 && g.y1 == 8);
     CHECK(p.all.x0 == 5 && p.all.y0 == 6 && p.all.x1 == 9 && p.all.y1 == 8);
-    if (g_failed) return 1;
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

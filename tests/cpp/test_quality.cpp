@@ -8,6 +8,7 @@
 #include <cstring>
 #include <vector>
 
+#include "check.hpp"
 #include "lidar_odometry_amd.hpp"
 
 using namespace lom;
@@ -20,15 +21,6 @@ static_assert(sizeof(lom_quality_report) == 920 && offsetof(lom_quality_report, 
                   offsetof(lom_quality_report, degenerate_t) == 904 && offsetof(lom_quality_report, covariance_valid) == 912,
               "lom_quality_report: the layout the Python binding and tests/quality_ref.py state");
 static_assert(LOM_ABI_VERSION == 2 && LOM_OPT_QUALITY_REPORT == 8 && LOM_NQSUMS == 36, "ABI constants");
-
-static int g_fail = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            g_fail++;                                                      \
-        }                                                                  \
-    } while (0)
 
 static bool same_bits(const Pose3D &a, const Pose3D &b)
 {
@@ -96,14 +88,14 @@ int main()
             // the same bytes from the C entry on the map handle, and again from the mirror
             lom_quality_report c;
             const lom_pose g = pose.c();
-            EXPECT(lom_match_quality(keyframe.handle(), &scan.points.data()->x, scan.points.size(), sizeof(PointXYZ), g.t, g.q,
+            CHECK(lom_match_quality(keyframe.handle(), &scan.points.data()->x, scan.points.size(), sizeof(PointXYZ), g.t, g.q,
                                      0.3f, 0.01f, 0.01f, &c, nullptr) == LOM_OK);
-            EXPECT(std::memcmp(&c, &q, sizeof q) == 0);
+            CHECK(std::memcmp(&c, &q, sizeof q) == 0);
             const QualityReport again = m.quality(keyframe, scan, pose, 0.3f, 0.01f, 0.01f);
-            EXPECT(std::memcmp(&again, &q, sizeof q) == 0);
-            EXPECT(q.queries == (int64_t)scan.points.size() && q.valid > q.queries / 2);
-            EXPECT(q.inliers <= q.valid && q.inliers > q.valid / 10 * 9);
-            EXPECT(res.size() == scan.points.size());
+            CHECK(std::memcmp(&again, &q, sizeof q) == 0);
+            CHECK(q.queries == (int64_t)scan.points.size() && q.valid > q.queries / 2);
+            CHECK(q.inliers <= q.valid && q.inliers > q.valid / 10 * 9);
+            CHECK(res.size() == scan.points.size());
             int64_t finite = 0;
             double sum2 = 0.0;
             for (float r : res)
@@ -111,20 +103,20 @@ int main()
                     finite++;
                     sum2 += (double)r * (double)r;
                 }
-            EXPECT(finite == q.valid);
-            EXPECT(std::fabs(std::sqrt(sum2 / (double)q.valid) - q.rmse) < 1e-6 * q.rmse);
-            EXPECT(q.rmse > 0.015 && q.rmse < 0.06);  // offsets 0.05 (z), 0.03 (y), 0.02 (x) from the planes
-            EXPECT(q.max_abs_residual >= 0.0499 && q.max_abs_residual < 0.3001);  // |r| <= the distance to the winner < the gate
+            CHECK(finite == q.valid);
+            CHECK(std::fabs(std::sqrt(sum2 / (double)q.valid) - q.rmse) < 1e-6 * q.rmse);
+            CHECK(q.rmse > 0.015 && q.rmse < 0.06);  // offsets 0.05 (z), 0.03 (y), 0.02 (x) from the planes
+            CHECK(q.max_abs_residual >= 0.0499 && q.max_abs_residual < 0.3001);  // |r| <= the distance to the winner < the gate
             for (int a = 0; a < 6; a++)
-                for (int b = 0; b < 6; b++) EXPECT(q.information[a * 6 + b] == q.information[b * 6 + a]);
-            EXPECT(std::fabs(q.eig_t[0] + q.eig_t[1] + q.eig_t[2] - 1.0) < 1e-9);
+                for (int b = 0; b < 6; b++) CHECK(q.information[a * 6 + b] == q.information[b * 6 + a]);
+            CHECK(std::fabs(q.eig_t[0] + q.eig_t[1] + q.eig_t[2] - 1.0) < 1e-9);
             if (planes == 3) {
-                EXPECT(q.degenerate_t == 0 && q.degenerate_r == 0 && q.covariance_valid == 1);
-                EXPECT(q.eig_t[0] > 0.2);
-                for (int a = 0; a < 6; a++) EXPECT(q.covariance[a * 6 + a] > 0.0);
+                CHECK(q.degenerate_t == 0 && q.degenerate_r == 0 && q.covariance_valid == 1);
+                CHECK(q.eig_t[0] > 0.2);
+                for (int a = 0; a < 6; a++) CHECK(q.covariance[a * 6 + a] > 0.0);
             } else {  // nothing constrains x: an exact zero share along +-x, a zero pivot
-                EXPECT(q.eig_t[0] == 0.0 && std::fabs(q.eigvec_t[0]) == 1.0 && q.eigvec_t[1] == 0.0 && q.eigvec_t[2] == 0.0);
-                EXPECT(q.degenerate_t == 1 && q.covariance_valid == 0 && q.covariance[0] == 0.0);
+                CHECK(q.eig_t[0] == 0.0 && std::fabs(q.eigvec_t[0]) == 1.0 && q.eigvec_t[1] == 0.0 && q.eigvec_t[2] == 0.0);
+                CHECK(q.degenerate_t == 1 && q.covariance_valid == 0 && q.covariance[0] == 0.0);
             }
         }
 
@@ -142,7 +134,7 @@ int main()
                 } catch (const lom::Error &e) {
                     early = e.code == LOM_ERR_STATE;
                 }
-                EXPECT(early);
+                CHECK(early);
             }
             on.processCloud(fr);
             off.processCloud(fr);
@@ -159,11 +151,10 @@ int main()
             }
             ok = ok && threw;
         }
-        EXPECT(ok);
+        CHECK(ok);
     } catch (const lom::Error &e) {
         std::printf("lom::Error %d: %s\n", e.code, e.what());
         return 2;
     }
-    std::printf(g_fail ? "FAILED (%d)\n" : "ALL PASSED\n", g_fail);
-    return g_fail ? 1 : 0;
+    return check_done();
 }

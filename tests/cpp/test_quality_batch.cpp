@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 
+#include "check.hpp"
 #include "lidar_odometry_amd.hpp"
 
 using namespace lom;
@@ -19,34 +20,25 @@ static_assert(sizeof(lom_quality_problem) == 56 && offsetof(lom_quality_problem,
                   offsetof(lom_quality_problem, q_wxyz) == 36,
               "lom_quality_problem: the layout the Python binding states");
 
-static int g_fail = 0;
-#define EXPECT(cond)                                                       \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
-            g_fail++;                                                      \
-        }                                                                  \
-    } while (0)
-
 static void lattice_case(const Pose3D &centre, const Vector3f &half, const Vector3f &step, float half_yaw, float step_yaw,
                          int expect_nodes)
 {
     const lom_pose c = centre.c();
     const int n = lom_pose_lattice(&c, half.v, step.v, half_yaw, step_yaw, nullptr, 0);
-    EXPECT(n == expect_nodes);
+    CHECK(n == expect_nodes);
     std::vector<lom_pose> raw((size_t)(n > 0 ? n : 0));
-    EXPECT(lom_pose_lattice(&c, half.v, step.v, half_yaw, step_yaw, raw.data(), n) == n);
+    CHECK(lom_pose_lattice(&c, half.v, step.v, half_yaw, step_yaw, raw.data(), n) == n);
     const std::vector<Pose3D> got = poseLattice(centre, half, step, half_yaw, step_yaw);
-    EXPECT((int)got.size() == n);
+    CHECK((int)got.size() == n);
     for (size_t i = 0; i < got.size() && i < raw.size(); i++) {
-        EXPECT(std::memcmp(got[i].translation.v, raw[i].t, sizeof raw[i].t) == 0);
-        EXPECT(std::memcmp(got[i].rotation.q, raw[i].q, sizeof raw[i].q) == 0);
+        CHECK(std::memcmp(got[i].translation.v, raw[i].t, sizeof raw[i].t) == 0);
+        CHECK(std::memcmp(got[i].rotation.q, raw[i].q, sizeof raw[i].q) == 0);
     }
     if (n > 1) {  // z innermost, ascending from the negative end; the centre in the middle
         const Pose3D &mid = got[(size_t)n / 2];
-        EXPECT(mid.translation.v[0] == centre.translation.v[0] && mid.translation.v[1] == centre.translation.v[1] &&
+        CHECK(mid.translation.v[0] == centre.translation.v[0] && mid.translation.v[1] == centre.translation.v[1] &&
                mid.translation.v[2] == centre.translation.v[2]);
-        EXPECT(got.front().translation.v[0] <= centre.translation.v[0] && got.back().translation.v[0] >= centre.translation.v[0]);
+        CHECK(got.front().translation.v[0] <= centre.translation.v[0] && got.back().translation.v[0] >= centre.translation.v[0]);
     }
 }
 
@@ -61,14 +53,14 @@ int main()
         const Pose3D bad(Vector3f(NAN, 0.f, 0.f), Quaternionf());
         const lom_pose c = bad.c();
         const float h[3] = {1.f, 1.f, 1.f}, s[3] = {0.5f, 0.5f, 0.5f};
-        EXPECT(lom_pose_lattice(&c, h, s, 0.f, 0.f, nullptr, 0) == LOM_ERR_ARG);
+        CHECK(lom_pose_lattice(&c, h, s, 0.f, 0.f, nullptr, 0) == LOM_ERR_ARG);
         bool thrown = false;
         try {
             poseLattice(bad, Vector3f(1.f, 1.f, 1.f), Vector3f(0.5f, 0.5f, 0.5f));
         } catch (const Error &e) {
             thrown = e.code == LOM_ERR_ARG;
         }
-        EXPECT(thrown);
+        CHECK(thrown);
     }
     {  // best-of: the mirror is the C function
         std::vector<QualityReport> r(5);
@@ -80,18 +72,13 @@ int main()
             r[(size_t)i].valid = rows[i][1];
             r[(size_t)i].cost = cost[i];
         }
-        EXPECT(lom_quality_batch_best(r.data(), 5) == 3);
-        EXPECT(CloudMatcher::bestQuality(r) == 3);
+        CHECK(lom_quality_batch_best(r.data(), 5) == 3);
+        CHECK(CloudMatcher::bestQuality(r) == 3);
         for (int count = 0; count <= 5; count++) {
             const std::vector<QualityReport> head(r.begin(), r.begin() + count);
-            EXPECT(CloudMatcher::bestQuality(head) == lom_quality_batch_best(r.data(), count));
+            CHECK(CloudMatcher::bestQuality(head) == lom_quality_batch_best(r.data(), count));
         }
-        EXPECT(CloudMatcher::bestQuality({}) == -1 && lom_quality_batch_best(nullptr, 3) == -1);
+        CHECK(CloudMatcher::bestQuality({}) == -1 && lom_quality_batch_best(nullptr, 3) == -1);
     }
-    if (g_fail) {
-        std::printf("%d FAILED\n", g_fail);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

@@ -9,17 +9,9 @@
 #include <limits>
 #include <vector>
 
+#include "check.hpp"
 #include "rollout_host.hpp"
 #include "rollout_rule.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 using namespace lom;
 using namespace lom::rollout;
@@ -260,10 +252,5 @@ int main(int argc, char **argv)
     test_key();
     test_helpers();
     if (argc > 1) test_vectors(argv[1], tab);
-    if (g_failed) {
-        std::printf("%d CHECKS FAILED\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

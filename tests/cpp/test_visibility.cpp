@@ -7,16 +7,8 @@
 #include <limits>
 #include <vector>
 
+#include "check.hpp"
 #include "visibility_host.hpp"
-
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
 
 using namespace lom;
 using namespace lom::visibility;
@@ -167,10 +159,5 @@ int main()
     test_table();
     test_windows_and_shapes();
     test_key();
-    if (g_failed) {
-        std::printf("%d checks failed\n", g_failed);
-        return 1;
-    }
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }

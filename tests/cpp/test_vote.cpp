@@ -11,14 +11,7 @@
 #include <string>
 #include <vector>
 
-static int g_failed = 0;
-#define CHECK(cond)                                                        \
-    do {                                                                   \
-        if (!(cond)) {                                                     \
-            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);  \
-            g_failed++;                                                    \
-        }                                                                  \
-    } while (0)
+#include "check.hpp"
 
 #ifdef VOTE_HOST_STANDALONE
 #include "vote_host.hpp"
@@ -136,9 +129,7 @@ int main()
     }
     // the step bound is the carve's
     CHECK(max_steps(60.f, 0.5f) == 3u * 122u && max_steps(6.f, 0.2f) == 3u * 32u && max_steps(3.4e38f, 0.5f) == 3u * 2097154u);
-    if (g_failed) return 1;
-    std::printf("ALL PASSED\n");
-    return 0;
+    return check_done();
 }
 #else
 #include "lidar_odometry_amd.hpp"
@@ -188,8 +179,8 @@ int main()
         threw = e.code == LOM_ERR_ARG;
     }
     CHECK(threw && grid.size() == before - want);
-    if (g_failed) return 1;
-    std::printf("ALL PASSED\n%zu %u\n", grid.size(), (unsigned)st.voxels_erased);
+    if (check_done()) return 1;
+    std::printf("%zu %u\n", grid.size(), (unsigned)st.voxels_erased);
     return 0;
 }
 #endif

@@ -5,14 +5,14 @@ and with the reference-algorithm counts)."""
 import ctypes as C
 import json
 import os
-import subprocess
 import threading
 
 import numpy as np
 import pytest
 
+from tests import cpp_program
 from tests import scenes
-from tests.conftest import GOLDEN, ROOT
+from tests.conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 
@@ -348,11 +348,5 @@ def test_python_mirror_on_scan_context(lom, synth):
 
 
 def test_cpp_mirror_align_batch(tmp_path, lom):
-    exe = str(tmp_path / "test_batch")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_batch.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "ALL PASSED" in r.stdout
+    exe = cpp_program.build_with_library(tmp_path, "test_batch.cpp")
+    cpp_program.run(exe, timeout=300)

@@ -1,14 +1,11 @@
 """Ray carving on the device against tests/carve_ref.py: crossing counts and hit flags per live voxel exactly equal,
 and after a carve the size, the full export (points and normals, byte for byte) and every stats field exactly equal."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from tests import carve_ref as R
+from tests import cpp_program
 from tests import scenes
-from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -379,14 +376,8 @@ def test_scan_context_is_refused(lom, room):
 
 def test_cpp_mirror(tmp_path, lom, oracle):
     """VoxelGrid::carveRays of the C++ mirror compiles with plain g++ and leaves the size the Python call leaves."""
-    exe = str(tmp_path / "test_carve")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_carve.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    size, erased = [int(v) for v in r.stdout.split()[-2:]]
+    exe = cpp_program.build_with_library(tmp_path, "test_carve.cpp")
+    size, erased = [int(v) for v in cpp_program.run(exe, timeout=120).split()[-2:]]
     # the same map and rays here (tests/cpp/test_carve.cpp)
     c = np.arange(-4, 5)
     cells = np.stack([a.ravel() for a in np.meshgrid(c, c, c, indexing="ij")], 1).astype(np.float32)

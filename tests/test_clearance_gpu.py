@@ -2,16 +2,14 @@
 metres as bytes -- all exactly equal.  The distance is an integer; the cost is looked up in the library's own table, which
 is compared with the reference's entry by entry (equal or off by one: the last ulp of exp) before it is used."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import clearance_ref as K
+from tests import cpp_program
 from tests import elevation_ref as E
 from tests import occupancy_ref as O
-from tests.conftest import ROOT
 from tests.test_occupancy_gpu import archive_of
 from tests.test_vote_gpu import pose_in_room, room_scan
 
@@ -388,14 +386,9 @@ def test_device_form_and_a_callers_event(lom):
 # ---- mirrors -------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom):
     """lom::ClearanceGrid of the C++ mirror compiles with plain g++ and leaves what the reference leaves."""
-    exe = str(tmp_path / "test_clearance_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_clearance_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    got = [int(v) for v in r.stdout.split()[-8:]]
+    exe = cpp_program.build_with_library(tmp_path, "test_clearance_mirror.cpp")
+    stdout = cpp_program.run(exe, timeout=120)
+    got = [int(v) for v in stdout.split()[-8:]]
     # the same grid and planes here (tests/cpp/test_clearance_mirror.cpp)
     i = np.arange(45 * 37)
     occ = np.where(i % 97 == 5, 100, np.where(i % 3 == 0, -1, 0)).astype(np.int8).reshape(37, 45)

@@ -2,31 +2,16 @@
 compiles with plain g++ against the C ABI (CPU check) and passes the reference's gtest
 cases restated in tests/cpp/test_mirror.cpp (GPU check)."""
 import os
-import subprocess
 
 import pytest
 
-from tests.conftest import ROOT
-
-SRC = os.path.join(ROOT, "tests", "cpp", "test_mirror.cpp")
-LIBDIR = os.path.join(ROOT, "lidar_odometry_demo_amd")
-
-
-def _build(out):
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), SRC, "-o", out,
-           "-L", LIBDIR, "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{LIBDIR}", "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.check_call(cmd)
-    return out
+from tests import cpp_program
 
 
 def test_mirror_header_compiles_and_links(tmp_path, lom):
-    exe = _build(str(tmp_path / "test_mirror"))
-    assert os.path.exists(exe)
+    assert os.path.exists(cpp_program.build_with_library(tmp_path, "test_mirror.cpp"))
 
 
 @pytest.mark.gpu
 def test_mirror_passes_reference_cases(tmp_path, lom):
-    exe = _build(str(tmp_path / "test_mirror"))
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "ALL PASSED" in r.stdout
+    cpp_program.run(cpp_program.build_with_library(tmp_path, "test_mirror.cpp"), timeout=300)

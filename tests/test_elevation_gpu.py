@@ -2,15 +2,13 @@
 field, the six layers as bytes, the cost and its summary -- all exactly equal: the accumulators are integers and every f64
 operation of the layers is rounded on its own, so there is no tolerance anywhere."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_program
 from tests import elevation_ref as E
 from tests import occupancy_ref as O
-from tests.conftest import ROOT
 from tests.test_occupancy_gpu import archive_of
 from tests.test_vote_gpu import pose_in_room, room_scan
 
@@ -433,14 +431,9 @@ def test_refusals_leave_the_cells_unchanged(lom, room):
 # ---- mirrors ---------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom):
     """lom::ElevationGrid of the C++ mirror compiles with plain g++ and leaves what the Python calls leave."""
-    exe = str(tmp_path / "test_elevation")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_elevation.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    n_unknown, n_lethal, n_costed = [int(v) for v in r.stdout.split()[-3:]]
+    exe = cpp_program.build_with_library(tmp_path, "test_elevation.cpp")
+    stdout = cpp_program.run(exe, timeout=120)
+    n_unknown, n_lethal, n_costed = [int(v) for v in stdout.split()[-3:]]
     # the same grid and points here (tests/cpp/test_elevation.cpp)
     k = np.arange(400)
     pts = np.stack([0.37 * (k % 20) + 0.2, 0.41 * (k // 20) + 0.1, 0.06 * (k % 20) - 0.9 + 0.5 * ((k // 20) == 9)], 1).astype(np.float32)

@@ -2,30 +2,13 @@
 the mirror lom::PoseGraph (include/lidar_odometry_amd.hpp) and the stateless host functions; with -DGRAPH_HOST_STANDALONE
 it compiles csrc/graph_host.cpp itself under -fsanitize=address,undefined into a program of its own and runs the gauge
 check, the CSR build and the Cholesky on degenerate shapes.  Host code only: no GPU needed."""
-import os
-import subprocess
-
-from tests.conftest import ROOT
-
-SRC = os.path.join(ROOT, "tests", "cpp", "test_graph.cpp")
+from tests import cpp_program
 
 
 def test_cpp_mirror_graph(tmp_path, lom):
-    exe = str(tmp_path / "test_graph")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"), SRC, "-o", exe,
-                           "-L", libdir, "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "ALL PASSED" in r.stdout
+    cpp_program.run(cpp_program.build_with_library(tmp_path, "test_graph.cpp"), timeout=300)
 
 
 def test_graph_host_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "test_graph_host")
-    csrc = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-DGRAPH_HOST_STANDALONE", "-I", os.path.join(ROOT, "include"),
-                           "-I", csrc, SRC, os.path.join(csrc, "graph_host.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ALL PASSED" in r.stdout
+    exe = cpp_program.build_host(tmp_path, "test_graph.cpp", ["graph_host.cpp"], ["-DGRAPH_HOST_STANDALONE", "-I", cpp_program.INCLUDE])
+    cpp_program.run(exe, timeout=300)

@@ -3,17 +3,13 @@ the rule every handle's shift takes -- and its C ABI, csrc/grid_shift_host.cpp, 
 program of its own, with no HIP header on its include path and against the C++ mirror's new members, and runs it directly
 over the table of cases of tests/test_grid_shift_host.py: the answers are tests/grid_shift_ref.py's.  Host code only: no GPU
 needed, nothing loaded into Python."""
-import os
 import struct
-import subprocess
 
 import numpy as np
 
+from tests import cpp_program
 from tests import grid_shift_ref as R
-from tests.conftest import ROOT
 from tests.test_grid_shift_host import DYADIC, EDGE, EDGE_CASES, SHIFTS, TENTH, admissible
-
-SRC = os.path.join(ROOT, "tests", "cpp", "test_grid_shift.cpp")
 
 
 def shift_cases():
@@ -32,11 +28,7 @@ def shift_cases():
 
 
 def test_rule_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "test_grid_shift")
-    csrc = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-ffp-contract=off", "-I", csrc, "-I", os.path.join(ROOT, "include"), SRC,
-                           os.path.join(csrc, "grid_shift_host.cpp"), "-o", exe])
+    exe = cpp_program.build_host(tmp_path, "test_grid_shift.cpp", ["grid_shift_host.cpp"], ["-ffp-contract=off", "-I", cpp_program.INCLUDE])
     cases = shift_cases()
     blob = [np.uint32(len(cases)).tobytes()]
     for g, dx, dy in cases:
@@ -53,6 +45,4 @@ def test_rule_under_sanitizers(tmp_path):
     assert n_rows == 2870
     src = tmp_path / "cases.bin"
     src.write_bytes(b"".join(blob))
-    r = subprocess.run([exe, str(src)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ALL PASSED" in r.stdout and "follow calls: 2525600" in r.stdout
+    assert "follow calls: 2525600" in cpp_program.run(exe, str(src), timeout=300)

@@ -4,24 +4,13 @@ throws the status its family's create returns and the text lom_<family>_last_err
 it has always thrown -- which is also what the same create says through ctypes.  With a device (marked gpu): create at the
 smallest size, geometry and cell count, clear, one refusal per class that reaches no kernel, destroy."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
-from tests.conftest import ROOT
+from tests import cpp_program
 
 CLASSES = ["FrontEnd", "PlaceDatabase", "PoseGraph", "ScanArchive", "OccupancyGrid", "ElevationGrid", "ClearanceGrid", "NavField",
            "RegionGrid", "VisibilityGrid", "RolloutGrid"]
-
-
-def build(tmp_path):
-    exe = str(tmp_path / "test_handles_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_handles_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
 
 
 def creates(capi):
@@ -41,12 +30,10 @@ def creates(capi):
 
 
 def test_constructors_throw_what_create_says(tmp_path, lom):
-    exe = build(tmp_path)  # the static_asserts: no class can be copied
+    exe = cpp_program.build_with_library(tmp_path, "test_handles_mirror.cpp", ["-Werror"])  # the static_asserts: no class can be copied
     if lom.capi.lib().lom_device_count() > 0:
         pytest.skip("a GPU is visible; the refused creates are for CPU-only hosts")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.rstrip("\n").split("\n")[:-1]
+    lines = cpp_program.run(exe, timeout=120).rstrip("\n").split("\n")[:-1]
     want = creates(lom.capi)
     assert [name for name, _, _ in want] == CLASSES
     assert lines == [f"{name} {rc} {text}" for name, rc, text in want]
@@ -55,9 +42,8 @@ def test_constructors_throw_what_create_says(tmp_path, lom):
 
 @pytest.mark.gpu
 def test_every_class_on_the_device(tmp_path, lom):
-    r = subprocess.run([build(tmp_path), "device"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.rstrip("\n").split("\n")[:-1]
+    exe = cpp_program.build_with_library(tmp_path, "test_handles_mirror.cpp", ["-Werror"])
+    lines = cpp_program.run(exe, "device", timeout=120).rstrip("\n").split("\n")[:-1]
     assert [line.split(" ")[:2] for line in lines] == [[name, str(lom.capi.ERR_ARG)] for name in CLASSES]
     texts = dict(line.split(" ", 2)[::2] for line in lines if line.count(" ") > 1)
     assert texts["OccupancyGrid"] == "unknown occupancy option" and texts["RolloutGrid"] == "unknown rollout grid option"

@@ -5,31 +5,14 @@ of the synth sequence (equal as bytes; the serial results are pinned to the orac
 table of decode_stage_words (csrc/stage_words.hpp); under -fsanitize=thread it drives Pool and Deferred
 (csrc/host_threads.hpp) on their spinning and parked paths, where no report is the pass condition."""
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 from lidar_odometry_demo_amd import synth
-from tests.conftest import ROOT
+from tests import cpp_program
 
-CSRC = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
-SRC = [os.path.join(ROOT, "tests", "cpp", "test_host_stages.cpp"), os.path.join(CSRC, "host_stages.cpp"),
-       os.path.join(CSRC, "host_threads.cpp")]
-
-
-def _build(tmp_path, name, sanitize):
-    exe = str(tmp_path / name)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Wno-unused-parameter",
-                           *sanitize, "-I", CSRC, *SRC, "-o", exe, "-pthread"])
-    return exe
-
-
-def _run(cmd, env=None):
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ALL PASSED" in r.stdout
-    return r
+CSRC_FILES = ["host_stages.cpp", "host_threads.cpp"]
+FLAGS = ["-ffp-contract=off", "-Wno-unused-parameter", "-pthread"]
 
 
 def test_pooled_stages_and_stage_word_decoder_under_asan_ubsan(tmp_path):
@@ -37,11 +20,11 @@ def test_pooled_stages_and_stage_word_decoder_under_asan_ubsan(tmp_path):
     assert frame.dtype.itemsize == 32 and len(frame) == 26579 and len(np.unique(frame["ring"])) == 16
     path = str(tmp_path / "frame0.bin")
     frame.tofile(path)
-    exe = _build(tmp_path, "test_host_stages_asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
-    _run([exe, "stages", path])
+    exe = cpp_program.build_host(tmp_path, "test_host_stages.cpp", CSRC_FILES, FLAGS)
+    cpp_program.run(exe, "stages", path, timeout=600)
 
 
 def test_pool_and_deferred_under_tsan(tmp_path):
-    exe = _build(tmp_path, "test_host_stages_tsan", ["-fsanitize=thread"])
-    r = _run([exe, "threads"], env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66"))
-    assert "ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
+    exe = cpp_program.build_host(tmp_path, "test_host_stages.cpp", CSRC_FILES, FLAGS, ["-fsanitize=thread"])
+    cpp_program.run(exe, "threads", timeout=600, stderr_without="ThreadSanitizer",
+                    env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1 exitcode=66"))

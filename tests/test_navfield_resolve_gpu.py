@@ -5,17 +5,15 @@ full solve from the kept goals) and every setting of the test switches; under th
 the least raised set.  Every case hands over garbage outside its window.  The references of a case are computed once and
 shared."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import clearance_ref as K
+from tests import cpp_program
 from tests import navfield_ref as N
 from tests import navfield_resolve_ref as RR
 from tests import navfield_scenes as S
-from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -443,14 +441,9 @@ def test_the_chain_with_a_resolve_in_its_second_round(lom):
 # ---- mirrors -------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom):
     """lom::NavField::resolve of the C++ mirror compiles with plain g++ and leaves the bytes the Python package leaves."""
-    exe = str(tmp_path / "test_navfield_resolve_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_navfield_resolve_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.strip().split("\n")
+    exe = cpp_program.build_with_library(tmp_path, "test_navfield_resolve_mirror.cpp")
+    stdout = cpp_program.run(exe, timeout=120)
+    lines = stdout.strip().split("\n")
     got_summary = [int(v) for v in lines[-3].split()]
     got_stats = [int(v) for v in lines[-2].split()]
     got_field = np.array([int(v) for v in lines[-1].split()], np.uint64).astype(np.uint32)

@@ -6,10 +6,10 @@ import ctypes as C
 import os
 import random
 import re
-import subprocess
 
 import numpy as np
 
+from tests import cpp_program
 from tests import navfield_ref as N
 from tests import navfield_resolve_ref as RR
 from tests import navfield_scenes as S
@@ -102,13 +102,8 @@ def test_two_rooms_and_their_door():
 def test_tile_range_under_sanitizers(tmp_path):
     """tests/cpp/test_navfield_resolve.cpp compiles csrc/navfield_host.cpp and csrc/clearance_host.cpp alone: the clipped
     window's tiles at the grid's edges, at tile borders and for windows outside the grid"""
-    exe = str(tmp_path / "test_navfield_resolve")
-    csrc = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-I", csrc, os.path.join(ROOT, "tests", "cpp", "test_navfield_resolve.cpp"),
-                           os.path.join(csrc, "navfield_host.cpp"), os.path.join(csrc, "clearance_host.cpp"), "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    exe = cpp_program.build_host(tmp_path, "test_navfield_resolve.cpp", ["navfield_host.cpp", "clearance_host.cpp"])
+    cpp_program.run(exe, timeout=300)
 
 
 def test_new_symbols_are_declared(lom):

@@ -4,20 +4,18 @@ tolerance anywhere: the field, the summary, cells_changed and (under the default
 lom_navfield_shift_stats, the geometry's bits, and paths, queries, waypoints and visibility on the new state.  Every case hands
 over garbage where the new plane is not read.  The references of a case are computed once and shared."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import clearance_ref as K
+from tests import cpp_program
 from tests import grid_shift_ref as GS
 from tests import navfield_ref as N
 from tests import navfield_resolve_ref as RR
 from tests import navfield_scenes as S
 from tests import navfield_shift_ref as SR
 from tests import navfield_waypoints_ref as W
-from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -530,14 +528,9 @@ def test_refusals_change_nothing_and_zero_the_summary(lom):
 # ---- mirrors -------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom):
     """lom::NavField::shiftResolve of the C++ mirror compiles with plain g++ and leaves the bytes the reference gives"""
-    exe = str(tmp_path / "test_navfield_shift_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_navfield_shift_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.strip().split("\n")
+    exe = cpp_program.build_with_library(tmp_path, "test_navfield_shift_mirror.cpp")
+    stdout = cpp_program.run(exe, timeout=120)
+    lines = stdout.strip().split("\n")
     got_summary = [int(v) for v in lines[-3].split()]
     got_stats = [int(v) for v in lines[-2].split()]
     got_field = np.array([int(v) for v in lines[-1].split()], np.uint64).astype(np.uint32)

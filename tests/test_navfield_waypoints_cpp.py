@@ -2,17 +2,13 @@
 csrc/nav_los_rule.hpp -- the rule the kernels run -- and csrc/navfield_host.cpp under -fsanitize=address,undefined into a
 program of its own, with no HIP header on its include path, runs it on planes, pairs and routes written here, and its
 answers equal tests/navfield_waypoints_ref.py's byte for byte.  Host code only: no GPU needed, nothing loaded into Python."""
-import os
-import subprocess
-
 import numpy as np
 
+from tests import cpp_program
 from tests import navfield_ref as N
 from tests import navfield_scenes as S
 from tests import navfield_waypoints_ref as Wr
-from tests.conftest import ROOT
 
-SRC = os.path.join(ROOT, "tests", "cpp", "test_navfield_waypoints.cpp")
 P0 = N.params(50, 3, 400, 98)
 P1 = N.params(50, 3, 400, 90, N.UNKNOWN_PASSABLE)
 
@@ -38,11 +34,7 @@ def cases():
 
 
 def test_rule_and_planner_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "test_navfield_waypoints")
-    csrc = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-I", csrc, SRC, os.path.join(csrc, "navfield_host.cpp"),
-                           "-o", exe])
+    exe = cpp_program.build_host(tmp_path, "test_navfield_waypoints.cpp", ["navfield_host.cpp"])
     all_cases = cases()
     blob, want = [np.uint32(len(all_cases)).tobytes()], []
     n_visible = n_cut = 0
@@ -66,7 +58,5 @@ def test_rule_and_planner_under_sanitizers(tmp_path):
     assert n_visible > 200 and n_cut > 20                   # the cases say something
     src, dst = tmp_path / "cases.bin", tmp_path / "answers.bin"
     src.write_bytes(b"".join(blob))
-    r = subprocess.run([exe, str(src), str(dst)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ALL PASSED" in r.stdout
+    cpp_program.run(exe, str(src), str(dst), timeout=300)
     assert dst.read_bytes() == b"".join(want)

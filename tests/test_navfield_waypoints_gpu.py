@@ -1,18 +1,15 @@
 """Line of sight and waypoints of the navigation field on the device against tests/navfield_waypoints_ref.py: counts,
 lengths, waypoint bytes and the visibility bytes, all exactly equal, in the wave form and under the serial switch.  The
 reference of a case -- the solve, and every line of sight it was asked for -- is computed once and shared."""
-import os
-import subprocess
-
 import ctypes as C
 import numpy as np
 import pytest
 
 from tests import clearance_ref as K
+from tests import cpp_program
 from tests import navfield_ref as N
 from tests import navfield_scenes as S
 from tests import navfield_waypoints_ref as Wr
-from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -394,14 +391,9 @@ def test_the_chain_from_the_clearance_grid(lom):
 def test_cpp_mirror(tmp_path, lom):
     """lom::NavField::waypoints and ::visible of the C++ mirror compile with plain g++ and leave the bytes the Python package
     leaves."""
-    exe = str(tmp_path / "test_navfield_waypoints_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_navfield_waypoints_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.strip().split("\n")
+    exe = cpp_program.build_with_library(tmp_path, "test_navfield_waypoints_mirror.cpp")
+    stdout = cpp_program.run(exe, timeout=120)
+    lines = stdout.strip().split("\n")
     got = [np.array([int(v) for v in line.split()], np.int64) for line in lines[-4:]]
     # the same grid, plane, goal, starts and pairs here (tests/cpp/test_navfield_waypoints_mirror.cpp)
     w, h, wp_cap = 45, 37, 64

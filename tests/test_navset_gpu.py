@@ -7,18 +7,16 @@ What a set of n_fields is solved under: all eight settings of the switches at n_
 the other counts take one setting each, rotated with the scene, so that every count meets every setting over the scenes
 of a shape.  No test asserts a time or a launch count."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import clearance_ref as K
+from tests import cpp_program
 from tests import navfield_ref as N
 from tests import navfield_scenes as S
 from tests import navset_ref as NS
 from tests import rollout_ref as R
-from tests.conftest import ROOT
 from tests.rollout_scenes import commands_of, states_of
 
 pytestmark = pytest.mark.gpu
@@ -573,14 +571,9 @@ def test_every_refusal_changes_nothing(lom):
 # ---- 8: the C++ mirror -------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom):
     """lom::NavFieldSet and lom::NavField::adopt of the C++ mirror compile with plain g++ and leave the bytes the reference gives"""
-    exe = str(tmp_path / "test_navset_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_navset_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe, "device"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.strip().split("\n")
+    exe = cpp_program.build_with_library(tmp_path, "test_navset_mirror.cpp")
+    stdout = cpp_program.run(exe, "device", timeout=120)
+    lines = stdout.strip().split("\n")
     # the same grid, plane and goals here (tests/cpp/test_navset_mirror.cpp)
     w, h = 45, 37
     i = np.arange(w * h)

@@ -3,21 +3,10 @@ compiles csrc/occupancy_host.cpp and csrc/assemble_host.cpp themselves under -fs
 its own -- every refusal, the slices of 1, 63, 64, 65 and 129 scans, bounding boxes clipped at the grid's edges and for
 origins outside it, the step bound, the scratch-budget slice size.  Host code only: no GPU needed, and nothing is loaded
 into Python."""
-import os
-import subprocess
-
-from tests.conftest import ROOT
-
-SRC = os.path.join(ROOT, "tests", "cpp", "test_occupancy.cpp")
+from tests import cpp_program
 
 
 def test_occupancy_host_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "test_occupancy_host")
-    csrc = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-DOCCUPANCY_HOST_STANDALONE", "-I", os.path.join(ROOT, "include"),
-                           "-I", csrc, SRC, os.path.join(csrc, "occupancy_host.cpp"), os.path.join(csrc, "assemble_host.cpp"),
-                           "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ALL PASSED" in r.stdout
+    exe = cpp_program.build_host(tmp_path, "test_occupancy.cpp", ["occupancy_host.cpp", "assemble_host.cpp"],
+                                 ["-DOCCUPANCY_HOST_STANDALONE", "-I", cpp_program.INCLUDE])
+    cpp_program.run(exe, timeout=300)

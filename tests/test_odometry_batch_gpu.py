@@ -3,14 +3,12 @@ streams per call.  The reference for every stream is the same frame sequence thr
 every pose bit for bit, the frame stats, the temp cloud and the final keyframe."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from lidar_odometry_demo_amd import synth
-from tests.conftest import ROOT
+from tests import cpp_program
 
 pytestmark = pytest.mark.gpu
 
@@ -140,11 +138,5 @@ def test_argument_errors_move_no_stream(lom):
 
 
 def test_cpp_mirror_process_batch(tmp_path, lom):
-    exe = str(tmp_path / "test_multi")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_multi.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "ALL PASSED" in r.stdout
+    exe = cpp_program.build_with_library(tmp_path, "test_multi.cpp")
+    cpp_program.run(exe, timeout=300)

@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+from tests import cpp_program
 from tests.conftest import ROOT
 
 CSRC = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
@@ -22,7 +23,4 @@ def test_point_terms_new_forms_against_old(tmp_path, sanitize):
     exe = str(tmp_path / "test_point_terms")
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra",
                            "-Wno-unused-parameter", *sanitize, "-I", CSRC, SRC, "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    print(r.stdout)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ALL PASSED" in r.stdout
+    print(cpp_program.run(exe, timeout=300))

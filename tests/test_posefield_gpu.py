@@ -4,18 +4,16 @@ test switches.  The reference of a case is computed once and shared.  Goals are 
 passable, and the tests that are about coverage assert on the reference, before they look at the device, that a case
 reaches at least half of the passable states."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import clearance_ref as K
+from tests import cpp_program
 from tests import navfield_ref as N
 from tests import posefield_ref as R
 from tests import posefield_scenes as S
 from tests import rollout_ref as X
-from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -499,14 +497,9 @@ def test_two_solves_agree_and_a_refused_call_changes_nothing(lom):
 # ---- mirrors -------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom):
     """lom::PoseField of the C++ mirror compiles with plain g++ and leaves the bytes the Python package leaves."""
-    exe = str(tmp_path / "test_posefield_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_posefield_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe, "device"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.strip().split("\n")
+    exe = cpp_program.build_with_library(tmp_path, "test_posefield_mirror.cpp")
+    stdout = cpp_program.run(exe, "device", timeout=120)
+    lines = stdout.strip().split("\n")
     got_summary = [int(v) for v in lines[-3].split()]
     got_field = np.array([int(v) for v in lines[-2].split()], np.uint64).astype(np.uint32)
     got_floor = np.array([int(v) for v in lines[-1].split()], np.uint64).astype(np.uint32)

@@ -2,20 +2,9 @@
 checks, word, tile and lane counts, the centroid rounding, the list sort -- under -fsanitize=address,undefined into a
 program of its own, with no HIP header on its include path.  Host code only: no GPU needed, and nothing is loaded into
 Python."""
-import os
-import subprocess
-
-from tests.conftest import ROOT
-
-SRC = os.path.join(ROOT, "tests", "cpp", "test_regions.cpp")
+from tests import cpp_program
 
 
 def test_regions_host_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "test_regions")
-    csrc = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-I", csrc, SRC, os.path.join(csrc, "regions_host.cpp"),
-                           "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ALL PASSED" in r.stdout
+    exe = cpp_program.build_host(tmp_path, "test_regions.cpp", ["regions_host.cpp"])
+    cpp_program.run(exe, timeout=300)

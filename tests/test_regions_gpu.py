@@ -2,19 +2,17 @@
 list under each rank, both goal kinds and the query -- all exactly equal, under every setting of the test switches.  The
 reference of a case is computed once and shared."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import clearance_ref as K
+from tests import cpp_program
 from tests import navfield_ref as N
 from tests import navfield_scenes as S
 from tests import occupancy_ref as O
 from tests import regions_ref as R
 from tests import regions_scenes as RS
-from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -306,14 +304,9 @@ def test_device_form_and_a_callers_event(lom):
 # ---- mirrors -------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom):
     """lom::RegionGrid of the C++ mirror compiles with plain g++ and leaves the bytes the Python package leaves."""
-    exe = str(tmp_path / "test_regions_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_regions_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.rstrip("\n").split("\n")
+    exe = cpp_program.build_with_library(tmp_path, "test_regions_mirror.cpp")
+    stdout = cpp_program.run(exe, timeout=120)
+    lines = stdout.rstrip("\n").split("\n")
     got_summary = [int(v) for v in lines[-3].split()]
     got_labels = np.array([int(v) for v in lines[-2].split()], np.uint64).astype(np.uint32)
     got_list = np.array([int(v) for v in lines[-1].split()], np.uint64).reshape(-1, 15)

@@ -5,16 +5,12 @@ the reach bound behind the staged window, launch shapes, the key's bit budget, t
 vectors tests/rollout_ref.py writes: the table, poses step by step and in closed form, pose tests.  The C++ mirror's rollout
 part compiles and its host-only helpers run.  Host code only: no GPU needed, and nothing is loaded into Python but the
 library for its table."""
-import os
-import subprocess
-
 import numpy as np
 
+from tests import cpp_program
 from tests import navfield_scenes as S
 from tests import rollout_ref as R
-from tests.conftest import ROOT
 
-CSRC = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
 CELL = 32768
 
 
@@ -54,23 +50,13 @@ def write_vectors(path, table):
 
 
 def test_rollout_host_and_rule_under_sanitizers(tmp_path, lom):
-    exe, vectors = str(tmp_path / "test_rollout"), str(tmp_path / "vectors.txt")
+    vectors = str(tmp_path / "vectors.txt")
     write_vectors(vectors, lom.visibilityTable(R.TABLE))
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-I", CSRC, os.path.join(ROOT, "tests", "cpp", "test_rollout.cpp"),
-                           os.path.join(CSRC, "rollout_host.cpp"), os.path.join(CSRC, "visibility_host.cpp"), "-o", exe])
-    r = subprocess.run([exe, vectors], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ALL PASSED" in r.stdout and "vectors:" in r.stdout
+    exe = cpp_program.build_host(tmp_path, "test_rollout.cpp", ["rollout_host.cpp", "visibility_host.cpp"])
+    assert "vectors:" in cpp_program.run(exe, vectors, timeout=300)
 
 
 def test_cpp_mirror_compiles_and_its_helpers_run(tmp_path):
     """lom::RolloutGrid and the helpers of the C++ mirror compile with plain g++; without an argument the program only runs
     the helpers, which need no device (tests/test_rollout_gpu.py runs the rest)."""
-    exe = str(tmp_path / "test_rollout_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_rollout_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
+    cpp_program.run(cpp_program.build_with_library(tmp_path, "test_rollout_mirror.cpp"), timeout=120)

@@ -2,18 +2,16 @@
 reference's under every setting of the three test switches, over shapes, planes, (L, Tn), footprint sizes, candidate and
 state counts; first blocks at the chunk border; ties; the chain ClearanceGrid -> NavField -> RolloutGrid; refused calls."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import clearance_ref as K
+from tests import cpp_program
 from tests import navfield_ref as N
 from tests import navfield_scenes as S
 from tests import regions_scenes as RS
 from tests import rollout_ref as R
-from tests.conftest import ROOT
 from tests.rollout_scenes import CELL, commands_of, footprint_of, states_of
 
 pytestmark = pytest.mark.gpu
@@ -260,14 +258,9 @@ def test_from_grids_the_chain_and_refused_calls(lom, table):
 # ---- mirrors ---------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom, table):
     """lom::RolloutGrid of the C++ mirror leaves the bytes the Python package and the reference leave."""
-    exe = str(tmp_path / "test_rollout_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_rollout_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe, "device"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.rstrip("\n").split("\n")
+    exe = cpp_program.build_with_library(tmp_path, "test_rollout_mirror.cpp")
+    stdout = cpp_program.run(exe, "device", timeout=120)
+    lines = stdout.rstrip("\n").split("\n")
     got_summary = [int(v) for v in lines[-3].split()]
     got_picks = np.array([int(v) for v in lines[-2].split()], np.int64).reshape(-1, 3)
     got_records = np.array([int(v) for v in lines[-1].split()], np.int64).reshape(-1, 8)

@@ -2,19 +2,17 @@
 the summary and the selection's list -- all exactly equal, under every setting of the test switches.  The reference of a
 case is computed once (cast_fast, which tests/test_visibility_host.py holds equal to the beam-by-beam form) and shared."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import cpp_program
 from tests import navfield_ref as N
 from tests import navfield_scenes as S
 from tests import occupancy_ref as O
 from tests import regions_ref as R
 from tests import regions_scenes as RS
 from tests import visibility_ref as V
-from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -323,14 +321,9 @@ def test_device_form_and_a_callers_event(lom):
 # ---- mirrors -------------------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom):
     """lom::VisibilityGrid of the C++ mirror compiles with plain g++ and leaves the bytes the Python package leaves."""
-    exe = str(tmp_path / "test_visibility_mirror")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_visibility_mirror.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = r.stdout.rstrip("\n").split("\n")
+    exe = cpp_program.build_with_library(tmp_path, "test_visibility_mirror.cpp")
+    stdout = cpp_program.run(exe, timeout=120)
+    lines = stdout.rstrip("\n").split("\n")
     got_summary = [int(v) for v in lines[-5].split()]
     got_records = np.array([int(v) for v in lines[-4].split()], np.int64).reshape(-1, 8)
     got_beams = np.array([int(v) for v in lines[-3].split()], np.uint64).astype(np.uint32)

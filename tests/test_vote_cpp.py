@@ -2,21 +2,10 @@
 csrc/vote_host.cpp and csrc/assemble_host.cpp themselves under -fsanitize=address,undefined into a program of its own --
 refusals, the slices of 1, 63, 64, 65 and 129 scans, descriptor offsets, the origin's verdict, the step bound.  Host code
 only: no GPU needed, and nothing is loaded into Python."""
-import os
-import subprocess
-
-from tests.conftest import ROOT
-
-SRC = os.path.join(ROOT, "tests", "cpp", "test_vote.cpp")
+from tests import cpp_program
 
 
 def test_vote_host_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "test_vote_host")
-    csrc = os.path.join(ROOT, "lidar_odometry_demo_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-DVOTE_HOST_STANDALONE", "-I", os.path.join(ROOT, "include"),
-                           "-I", csrc, SRC, os.path.join(csrc, "vote_host.cpp"), os.path.join(csrc, "assemble_host.cpp"),
-                           "-o", exe])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "ALL PASSED" in r.stdout
+    exe = cpp_program.build_host(tmp_path, "test_vote.cpp", ["vote_host.cpp", "assemble_host.cpp"],
+                                 ["-DVOTE_HOST_STANDALONE", "-I", cpp_program.INCLUDE])
+    cpp_program.run(exe, timeout=300)

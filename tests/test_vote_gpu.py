@@ -1,17 +1,14 @@
 """Scan votes on the device against tests/vote_ref.py: free and seen per live voxel exactly equal, and after
 carveScans the size, the full export (points and normals, byte for byte) and every stats field exactly equal."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from tests import assemble_ref as A
 from tests import carve_ref as R
+from tests import cpp_program
 from tests import scenes
 from tests import vote_ref as V
 from tests import vote_scene as S
-from tests.conftest import ROOT
 from tests.test_carve_gpu import Pair, lattice_points, room_points
 
 pytestmark = pytest.mark.gpu
@@ -438,14 +435,9 @@ def test_mover_scene_equals_the_reference(lom):
 # ---- 10: mirrors -----------------------------------------------------------------------------------------------------------
 def test_cpp_mirror(tmp_path, lom, oracle):
     """VoxelGrid::carveScans / scanVotes of the C++ mirror compile with plain g++ and leave what the Python calls leave."""
-    exe = str(tmp_path / "test_vote")
-    libdir = os.path.join(ROOT, "lidar_odometry_demo_amd")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_vote.cpp"), "-o", exe, "-L", libdir,
-                           "-llidar_odometry_amd", "-pthread", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"])
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
-    size, erased = [int(v) for v in r.stdout.split()[-2:]]
+    exe = cpp_program.build_with_library(tmp_path, "test_vote.cpp")
+    stdout = cpp_program.run(exe, timeout=120)
+    size, erased = [int(v) for v in stdout.split()[-2:]]
     # the same map and scans here (tests/cpp/test_vote.cpp)
     c = np.arange(-4, 5)
     cells = np.stack([a.ravel() for a in np.meshgrid(c, c, c, indexing="ij")], 1).astype(np.float32)
