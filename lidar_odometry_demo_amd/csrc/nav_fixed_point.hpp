@@ -34,4 +34,13 @@ int to_fixed_point(H *f, size_t marks_per_parity, uint64_t &launches, uint64_t &
     }
 }
 
+// One test option of such a handle (inner_cap, batch, all_tiles, a form): a value above `max` is refused with the option's
+// text, a value <= 0 gives the default.
+inline int set_test_option(DeviceHandle *f, uint32_t &slot, int64_t value, uint32_t max, uint32_t def, const char *range_text)
+{
+    if (value > (int64_t)max) return fail(f, LOM_ERR_ARG, range_text);
+    slot = value <= 0 ? def : (uint32_t)value;
+    return LOM_OK;
+}
+
 }  // namespace lom

@@ -4,7 +4,9 @@
 // re-solve after a local cost change (k_navfield_resolve.hpp) keeps what a solve left and repairs it; the
 // line of sight and the waypoints (k_navfield_waypoints.hpp) read what it left; the shift with a re-solve
 // (k_navfield_shift.hpp) moves it into a second block and repairs it there.  A handle family of its own on
-// the PlaneHandle core (plane_handle.hpp); no default path launches any of this.
+// the PlaneHandle core (plane_handle.hpp); the three forms in which a cost plane arrives -- host, device, clearance grid --
+// are its PlaneSource, and every exported solve, re-solve and shift forwards to one function over it.  No
+// default path launches any of this.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -175,9 +177,48 @@ int resolve_refusal(lom_navfield *f, bool have_plane)
     return LOM_OK;
 }
 
+// The repair behind the first launch and wait of a re-solve or of a shift with one: the raise phase to its fixed point
+// and its seeds as the first marks (form 0), or the reset of another form (1: the threshold, 2: the goals' tiles); the
+// relaxation from the seeds to its fixed point; the report and the wait; the counters.  The report counts cells, the goals
+// are the host's to keep: goals_used falls by `goals_gone`, those rejected and those that left the grid.
+int repair(lom_navfield *f, uint32_t form, uint32_t goals_gone)
+{
+    const NavArgs a = f->args();
+    const uint32_t n_tiles = f->tiles.n_tiles;
+    const uint32_t *const table = f->table.as<const uint32_t>();
+    uint32_t *const field = f->field.as<uint32_t>(), *const words = f->words.as<uint32_t>();
+    uint32_t *const marks0 = f->marks.as<uint32_t>(), *const seeds = marks0 + (size_t)2 * n_tiles;
+    uint32_t *const h = f->h_flags.as<uint32_t>();
+    lom_navfield_resolve_counters &st = f->resolve_stats;
+    if (form == 0u) {
+        const int rc = to_fixed_point(f, f->tiles.n_tiles, st.raise_launches, st.waits, "navigation field: the raise phase did not settle",
+                                      [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
+                                          hipLaunchKernelGGL(k_nav_raise, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0,
+                                                             f->stream, f->plane.as<const int8_t>(), table, a, f->inner_cap, f->all_tiles,
+                                                             field, cur, nxt, seeds, flag, words);
+                                      });
+        if (rc != LOM_OK) return rc;
+        // (both arrays of the fixed point are clear: the seeds are the first launch's marks)
+        LOM_HIP(f, hipMemcpyAsync(marks0, seeds, (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, f->stream));
+    } else if (form == 1u) {
+        hipLaunchKernelGGL(k_nav_threshold, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream, a, field, marks0, words);
+        LOM_HIP(f, hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(k_nav_reseed, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream,
+                           f->plane.as<const int8_t>(), table, a, field, marks0, words);
+        LOM_HIP(f, hipGetLastError());
+    }
+    if (const int rc = relax(f, st.relax_launches, st.waits); rc != LOM_OK) return rc;
+    if (const int rc = report(f, RW_END); rc != LOM_OK) return rc;
+    st.waits++;
+    st.cells_raised = h[RW_RAISED], st.tiles_marked = h[RW_TILES];
+    h[NW_GOALS_USED] = f->last_words[NW_GOALS_USED] - goals_gone;
+    std::memcpy(f->last_words, h, sizeof f->last_words);
+    return LOM_OK;
+}
+
 // A re-solve from a plane in HBM that this stream may read now, over a window that is not empty: the diff and a wait;
-// then, where a cell changed, the raise phase to its fixed point (or the reset of another form), the relaxation from
-// the seeds to its fixed point, the report and the wait.  done_ev stands behind the diff, the one reader of d_new.
+// then, where a cell changed, the repair.  done_ev stands behind the diff, the one reader of d_new.
 int resolve_on_device(lom_navfield *f, const int8_t *d_new, const clearance::Rect &r, lom_navfield_summary *summary)
 {
     const NavArgs a = f->args();
@@ -204,32 +245,8 @@ int resolve_on_device(lom_navfield *f, const int8_t *d_new, const clearance::Rec
     st.waits = 1;
     st.cells_changed = h[RW_CHANGED];
     const uint32_t rejected = h[NW_GOALS_REJECTED];
-    if (st.cells_changed != 0u) {
-        if (form == 0u) {
-            const int rc = to_fixed_point(f, f->tiles.n_tiles, st.raise_launches, st.waits, "navigation field: the raise phase did not settle",
-                                          [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
-                                              hipLaunchKernelGGL(k_nav_raise, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0,
-                                                                 f->stream, f->plane.as<const int8_t>(), table, a, f->inner_cap, f->all_tiles,
-                                                                 field, cur, nxt, seeds, flag, words);
-                                          });
-            if (rc != LOM_OK) return rc;
-            // (both arrays of the fixed point are clear: the seeds are the first launch's marks)
-            LOM_HIP(f, hipMemcpyAsync(marks0, seeds, (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, f->stream));
-        } else if (form == 1u) {
-            hipLaunchKernelGGL(k_nav_threshold, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream, a, field, marks0, words);
-            LOM_HIP(f, hipGetLastError());
-        } else {
-            hipLaunchKernelGGL(k_nav_reseed, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream,
-                               f->plane.as<const int8_t>(), table, a, field, marks0, words);
-            LOM_HIP(f, hipGetLastError());
-        }
-        if (const int rc = relax(f, st.relax_launches, st.waits); rc != LOM_OK) return rc;
-        if (const int rc = report(f, RW_END); rc != LOM_OK) return rc;
-        st.waits++;
-        st.cells_raised = h[RW_RAISED], st.tiles_marked = h[RW_TILES];
-        h[NW_GOALS_USED] = f->last_words[NW_GOALS_USED] - rejected;  // (the report counts cells: the goals are the host's to keep)
-        std::memcpy(f->last_words, h, sizeof f->last_words);
-    }
+    if (st.cells_changed != 0u)
+        if (const int rc = repair(f, form, rejected); rc != LOM_OK) return rc;
     f->last_words[NW_GOALS_REJECTED] = rejected;
     f->solved = true;
     if (summary) summary_from(f->last_words, summary);
@@ -246,16 +263,6 @@ int resolve_nothing(lom_navfield *f, lom_navfield_summary *summary)
 }
 
 // ---- the shift with a re-solve ------------------------------------------------------------------------------------------
-// What every form does before any device work: the refusals of a re-solve, the geometry by the rule (LOM_ERR_RANGE) and the
-// plan.
-int shift_resolve_head(lom_navfield *f, bool have_plane, int32_t dx, int32_t dy, lom_occupancy_geometry *g, navfield::ShiftPlan *plan)
-{
-    if (const int rc = resolve_refusal(f, have_plane); rc != LOM_OK) return rc;
-    if (const int rc = plane_shifted_geometry(f, kName, dx, dy, g); rc != LOM_OK) return rc;
-    *plan = navfield::shift_plan(f->geo.width, f->geo.height, dx, dy);
-    return LOM_OK;
-}
-
 // the second block, at the first call that moves: 5 bytes per cell
 int ensure_second_block(lom_navfield *f)
 {
@@ -268,27 +275,10 @@ int ensure_second_block(lom_navfield *f)
     return LOM_OK;
 }
 
-// A shift of (0, 0) is the re-solve with the same arguments, under the geometry the rule gives for it (an origin of -0
-// becomes +0); a refusal puts the geometry back.
-template <class Resolve>
-int shift_resolve_in_place(lom_navfield *f, const lom_occupancy_geometry &g, Resolve resolve)
-{
-    const lom_occupancy_geometry before = f->geo;
-    f->geo = g;
-    const int rc = resolve();
-    if (rc != LOM_OK) {
-        f->geo = before;
-        return rc;
-    }
-    f->shift_stats = lom_navfield_shift_counters{f->n_cells(), 0u, 0u};
-    return LOM_OK;
-}
-
 // A shift that moves, from a plane in HBM that this stream may read now, in the new geometry's cells; r may be empty.  The
-// mover and diff in one launch into the second block, the swap behind it, and a wait; then the raise phase to its fixed
-// point (or the reset of form 2, which the threshold form runs as well: its pmin would have to cover the trailing
-// borders), the relaxation from the seeds, the report and the wait.  done_ev stands behind the first launch, the one
-// reader of d_new.  Every allocation has been made.
+// mover and diff in one launch into the second block, the swap behind it, and a wait; then the repair, whatever changed
+// (the threshold form runs the reset of form 2: its pmin would have to cover the trailing borders).  done_ev stands behind
+// the first launch, the one reader of d_new.  Every allocation has been made.
 int shift_resolve_on_device(lom_navfield *f, const navfield::ShiftPlan &plan, const lom_occupancy_geometry &g, const int8_t *d_new,
                             const clearance::Rect &r, lom_navfield_summary *summary)
 {
@@ -312,7 +302,6 @@ int shift_resolve_on_device(lom_navfield *f, const navfield::ShiftPlan &plan, co
     f->solved = false;
     swap(f->field, f->field2), swap(f->plane, f->plane2);
     f->geo = g;
-    uint32_t *const field = f->field.as<uint32_t>();
     LOM_HIP(f, hipEventRecord(f->done_ev, f->stream));
     LOM_HIP(f, hipMemcpyAsync(h, f->words.p, (size_t)SW_END * 4, hipMemcpyDeviceToHost, f->stream));
     LOM_HIP(f, hipStreamSynchronize(f->stream));
@@ -320,30 +309,97 @@ int shift_resolve_on_device(lom_navfield *f, const navfield::ShiftPlan &plan, co
     st.cells_changed = h[RW_CHANGED];
     const uint32_t rejected = h[NW_GOALS_REJECTED], left = h[SW_GOALS_LEFT];
     f->shift_stats = lom_navfield_shift_counters{plan.cells_kept, h[SW_ENTERED], left};
-    if (raise) {
-        const int rc = to_fixed_point(f, f->tiles.n_tiles, st.raise_launches, st.waits, "navigation field: the raise phase did not settle",
-                                      [&](uint32_t *cur, uint32_t *nxt, uint32_t *flag) {
-                                          hipLaunchKernelGGL(k_nav_raise, dim3(f->tiles.tiles_x, f->tiles.tiles_y), dim3(kNavThreads), 0,
-                                                             f->stream, f->plane.as<const int8_t>(), table, a, f->inner_cap, f->all_tiles,
-                                                             field, cur, nxt, seeds, flag, words);
-                                      });
-        if (rc != LOM_OK) return rc;
-        LOM_HIP(f, hipMemcpyAsync(marks0, seeds, (size_t)n_tiles * 4, hipMemcpyDeviceToDevice, f->stream));
-    } else {
-        hipLaunchKernelGGL(k_nav_reseed, dim3(navfield::blocks_for(f->n_cells())), dim3(kNavThreads), 0, f->stream,
-                           f->plane.as<const int8_t>(), table, a, field, marks0, words);
-        LOM_HIP(f, hipGetLastError());
-    }
-    if (const int rc = relax(f, st.relax_launches, st.waits); rc != LOM_OK) return rc;
-    if (const int rc = report(f, RW_END); rc != LOM_OK) return rc;
-    st.waits++;
-    st.cells_raised = h[RW_RAISED], st.tiles_marked = h[RW_TILES];
-    h[NW_GOALS_USED] = f->last_words[NW_GOALS_USED] - rejected - left;  // (the report counts cells: the goals are the host's to keep)
-    h[NW_GOALS_REJECTED] = rejected;
-    std::memcpy(f->last_words, h, sizeof f->last_words);
+    if (const int rc = repair(f, raise ? 0u : 2u, rejected + left); rc != LOM_OK) return rc;
+    f->last_words[NW_GOALS_REJECTED] = rejected;
     f->solved = true;
     if (summary) summary_from(f->last_words, summary);
     return LOM_OK;
+}
+
+// ---- one function per operation over the source of the plane (plane_handle.hpp) ---------------------------
+// Each in one order: the refusals, the way out that needs no device, what can fail for want of memory, open, upload, body, close.
+int solve_from(lom_navfield *f, const PlaneSource &src, const lom_navfield_params *params, int goal_kind, const void *goals, size_t n_goals,
+               lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const char *why = solve_refusal(src.given(), params, goal_kind, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
+    if (const int rc = plane_source_check(f, kName, src, f->geo); rc != LOM_OK) return rc;
+    LOM_HIP(f, hipSetDevice(f->device));
+    // the goals first: their buffer is what can still be refused (no memory); then a host plane goes straight to the field's copy
+    if (const int rc = n_goals ? ensure(f, f->points, n_goals * 8) : LOM_OK; rc != LOM_OK) return rc;
+    const int8_t *d_plane = nullptr;
+    if (const int rc = plane_source_open(f, kName, src, &d_plane); rc != LOM_OK) return rc;
+    if (src.host) {
+        LOM_HIP(f, hipMemcpyAsync(f->plane.p, src.host, f->n_cells(), hipMemcpyHostToDevice, f->stream));
+        d_plane = f->plane.as<const int8_t>();
+    }
+    if (const int rc = solve_on_device(f, d_plane, *params, goal_kind, goals, n_goals, summary); rc != LOM_OK) return rc;
+    return plane_source_close(f, kName, src);
+}
+
+int resolve_from(lom_navfield *f, const PlaneSource &src, const lom_clearance_window *window_or_null, lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const int rc = resolve_refusal(f, src.given()); rc != LOM_OK) return rc;
+    if (const int rc = plane_source_check(f, kName, src, f->geo); rc != LOM_OK) return rc;
+    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
+    if (r.empty()) return resolve_nothing(f, summary);
+    LOM_HIP(f, hipSetDevice(f->device));
+    const int8_t *d_plane = nullptr;
+    if (const int rc = plane_source_open(f, kName, src, &d_plane); rc != LOM_OK) return rc;
+    if (src.host) {
+        // the rows of the window, whole, at their place in a plane of the device: the cells outside the window are not read
+        if (const int rc = ensure(f, f->incoming, f->n_cells()); rc != LOM_OK) return rc;
+        const size_t first = (size_t)r.y0 * f->geo.width, bytes = (size_t)(r.y1 - r.y0) * f->geo.width;
+        LOM_HIP(f, hipMemcpyAsync(f->incoming.as<int8_t>() + first, src.host + first, bytes, hipMemcpyHostToDevice, f->stream));
+        d_plane = f->incoming.as<const int8_t>();
+    }
+    if (const int rc = resolve_on_device(f, d_plane, r, summary); rc != LOM_OK) return rc;
+    return plane_source_close(f, kName, src);
+}
+
+// The refusals of a re-solve, the geometry by the rule (LOM_ERR_RANGE) and the plan come before any device work.
+int shift_resolve_from(lom_navfield *f, const PlaneSource &src, int32_t dx, int32_t dy, const lom_clearance_window *window_or_null,
+                       lom_navfield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const int rc = resolve_refusal(f, src.given()); rc != LOM_OK) return rc;
+    lom_occupancy_geometry g;
+    if (const int rc = plane_shifted_geometry(f, kName, dx, dy, &g); rc != LOM_OK) return rc;
+    const navfield::ShiftPlan plan = navfield::shift_plan(f->geo.width, f->geo.height, dx, dy);
+    if (!plan.moves()) {
+        // A shift of (0, 0) is the re-solve with the same arguments, under the geometry the rule gives for it (an origin of
+        // -0 becomes +0); a refusal puts the geometry back.
+        const lom_occupancy_geometry before = f->geo;
+        f->geo = g;
+        if (const int rc = resolve_from(f, src, window_or_null, summary); rc != LOM_OK) {
+            f->geo = before;
+            return rc;
+        }
+        f->shift_stats = lom_navfield_shift_counters{f->n_cells(), 0u, 0u};
+        return LOM_OK;
+    }
+    // a clearance grid has been shifted already: its geometry is the new one, bit for bit
+    if (const int rc = plane_source_check(f, kName, src, g, " from the shifted geometry"); rc != LOM_OK) return rc;
+    LOM_HIP(f, hipSetDevice(f->device));
+    if (const int rc = ensure_second_block(f); rc != LOM_OK) return rc;
+    const clearance::Rect r = clearance::clip(window_or_null, g);
+    const int8_t *d_plane = nullptr;
+    if (const int rc = plane_source_open(f, kName, src, &d_plane); rc != LOM_OK) return rc;
+    if (src.host) {
+        // the rows that hold an entered cell or a cell of the window, whole, at their place in a plane of the device
+        if (const int rc = ensure(f, f->incoming, f->n_cells()); rc != LOM_OK) return rc;
+        uint32_t y0, y1;
+        navfield::shift_upload_rows(plan, r, g.height, &y0, &y1);
+        const size_t first = (size_t)y0 * g.width, bytes = (size_t)(y1 - y0) * g.width;
+        if (bytes) LOM_HIP(f, hipMemcpyAsync(f->incoming.as<int8_t>() + first, src.host + first, bytes, hipMemcpyHostToDevice, f->stream));
+        d_plane = f->incoming.as<const int8_t>();
+    }
+    if (const int rc = shift_resolve_on_device(f, plan, g, d_plane, r, summary); rc != LOM_OK) return rc;
+    return plane_source_close(f, kName, src);
 }
 
 }  // namespace
@@ -402,187 +458,72 @@ int lom_navfield_set_option(lom_navfield *f, int option, int64_t value)
     if (!f) return LOM_ERR_ARG;
     switch (option) {
     case LOM_NAV_OPT_TEST_INNER_CAP:
-        if (value > (int64_t)navfield::kInnerCapMax) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_INNER_CAP: 1 .. 2^20, or <= 0 for the default");
-        f->inner_cap = value <= 0 ? navfield::kInnerCapDefault : (uint32_t)value;
-        return LOM_OK;
+        return set_test_option(f, f->inner_cap, value, navfield::kInnerCapMax, navfield::kInnerCapDefault,
+                               "LOM_NAV_OPT_TEST_INNER_CAP: 1 .. 2^20, or <= 0 for the default");
     case LOM_NAV_OPT_TEST_BATCH:
-        if (value > (int64_t)navfield::kBatchMax) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_BATCH: 1 .. 256, or <= 0 for the default");
-        f->batch = value <= 0 ? navfield::kBatchDefault : (uint32_t)value;
-        return LOM_OK;
-    case LOM_NAV_OPT_TEST_ALL_TILES:
-        if (value > 1) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_ALL_TILES: 0, 1, or < 0 for the default");
-        f->all_tiles = value == 1 ? 1u : 0u;
-        return LOM_OK;
+        return set_test_option(f, f->batch, value, navfield::kBatchMax, navfield::kBatchDefault,
+                               "LOM_NAV_OPT_TEST_BATCH: 1 .. 256, or <= 0 for the default");
+    case LOM_NAV_OPT_TEST_ALL_TILES: return set_test_option(f, f->all_tiles, value, 1, 0, "LOM_NAV_OPT_TEST_ALL_TILES: 0, 1, or < 0 for the default");
     case LOM_NAV_OPT_TEST_RESOLVE_FORM:
-        if (value > 2) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_RESOLVE_FORM: 0, 1, 2, or < 0 for the default");
-        f->resolve_form = value <= 0 ? 0u : (uint32_t)value;
-        return LOM_OK;
+        return set_test_option(f, f->resolve_form, value, 2, 0, "LOM_NAV_OPT_TEST_RESOLVE_FORM: 0, 1, 2, or < 0 for the default");
     case LOM_NAV_OPT_TEST_SHORTCUT_SERIAL:
-        if (value > 1) return fail(f, LOM_ERR_ARG, "LOM_NAV_OPT_TEST_SHORTCUT_SERIAL: 0, 1, or < 0 for the default");
-        f->shortcut_serial = value == 1 ? 1u : 0u;
-        return LOM_OK;
+        return set_test_option(f, f->shortcut_serial, value, 1, 0, "LOM_NAV_OPT_TEST_SHORTCUT_SERIAL: 0, 1, or < 0 for the default");
     default:
         return fail(f, LOM_ERR_ARG, "unknown navigation field option");
     }
 }
 
-int lom_navfield_solve_device(lom_navfield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_navfield_params *params,
-                              int goal_kind, const void *goals, size_t n_goals, lom_navfield_summary *summary)
-{
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const char *why = solve_refusal(d_plane != nullptr, params, goal_kind, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
-    LOM_HIP(f, hipSetDevice(f->device));
-    if (hip_event_or_null) LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event_or_null, 0));
-    return solve_on_device(f, d_plane, *params, goal_kind, goals, n_goals, summary);
-}
-
 int lom_navfield_solve(lom_navfield *f, const int8_t *plane, const lom_navfield_params *params, int goal_kind, const void *goals,
                        size_t n_goals, lom_navfield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const char *why = solve_refusal(plane != nullptr, params, goal_kind, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
-    LOM_HIP(f, hipSetDevice(f->device));
-    // the goals first: their buffer is what can still be refused (no memory); then the plane goes straight to the field's copy
-    if (const int rc = n_goals ? ensure(f, f->points, n_goals * 8) : LOM_OK; rc != LOM_OK) return rc;
-    LOM_HIP(f, hipMemcpyAsync(f->plane.p, plane, f->n_cells(), hipMemcpyHostToDevice, f->stream));
-    return solve_on_device(f, f->plane.as<const int8_t>(), *params, goal_kind, goals, n_goals, summary);
+    return solve_from(f, plane_from_host(plane), params, goal_kind, goals, n_goals, summary);
+}
+
+int lom_navfield_solve_device(lom_navfield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_navfield_params *params,
+                              int goal_kind, const void *goals, size_t n_goals, lom_navfield_summary *summary)
+{
+    return solve_from(f, plane_from_device(d_plane, hip_event_or_null), params, goal_kind, goals, n_goals, summary);
 }
 
 int lom_navfield_solve_from_clearance(lom_navfield *f, lom_clearance *clearance, const lom_navfield_params *params, int goal_kind,
                                       const void *goals, size_t n_goals, lom_navfield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const char *why = solve_refusal(clearance != nullptr, params, goal_kind, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
-    lom_occupancy_geometry g{};
-    (void)lom_clearance_get_geometry(clearance, &g);
-    int rc = plane_check_producer(f, kName, "clearance grid", g, lom_clearance_device(clearance));
-    if (rc != LOM_OK) return rc;
-    LOM_HIP(f, hipSetDevice(f->device));
-    // the hand-off of plane_handle.hpp: read behind the clearance grid, solve, release to it
-    const int8_t *d_plane = nullptr;
-    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
-        return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
-    if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
-    if ((rc = solve_on_device(f, d_plane, *params, goal_kind, goals, n_goals, summary)) != LOM_OK) return rc;
-    return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
+    return solve_from(f, plane_from_clearance(clearance), params, goal_kind, goals, n_goals, summary);
+}
+
+int lom_navfield_resolve(lom_navfield *f, const int8_t *plane, const lom_clearance_window *window_or_null, lom_navfield_summary *summary)
+{
+    return resolve_from(f, plane_from_host(plane), window_or_null, summary);
 }
 
 int lom_navfield_resolve_device(lom_navfield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_clearance_window *window_or_null,
                                 lom_navfield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const int rc = resolve_refusal(f, d_plane != nullptr); rc != LOM_OK) return rc;
-    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
-    if (r.empty()) return resolve_nothing(f, summary);
-    LOM_HIP(f, hipSetDevice(f->device));
-    if (hip_event_or_null) LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event_or_null, 0));
-    return resolve_on_device(f, d_plane, r, summary);
-}
-
-int lom_navfield_resolve(lom_navfield *f, const int8_t *plane, const lom_clearance_window *window_or_null, lom_navfield_summary *summary)
-{
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const int rc = resolve_refusal(f, plane != nullptr); rc != LOM_OK) return rc;
-    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
-    if (r.empty()) return resolve_nothing(f, summary);
-    LOM_HIP(f, hipSetDevice(f->device));
-    // the rows of the window, whole, at their place in a plane of the device: the cells outside the window are not read
-    if (const int rc = ensure(f, f->incoming, f->n_cells()); rc != LOM_OK) return rc;
-    const size_t first = (size_t)r.y0 * f->geo.width, bytes = (size_t)(r.y1 - r.y0) * f->geo.width;
-    LOM_HIP(f, hipMemcpyAsync(f->incoming.as<int8_t>() + first, plane + first, bytes, hipMemcpyHostToDevice, f->stream));
-    return resolve_on_device(f, f->incoming.as<const int8_t>(), r, summary);
+    return resolve_from(f, plane_from_device(d_plane, hip_event_or_null), window_or_null, summary);
 }
 
 int lom_navfield_resolve_from_clearance(lom_navfield *f, lom_clearance *clearance, const lom_clearance_window *window_or_null,
                                         lom_navfield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const int rc = resolve_refusal(f, clearance != nullptr); rc != LOM_OK) return rc;
-    lom_occupancy_geometry g{};
-    (void)lom_clearance_get_geometry(clearance, &g);
-    int rc = plane_check_producer(f, kName, "clearance grid", g, lom_clearance_device(clearance));
-    if (rc != LOM_OK) return rc;
-    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
-    if (r.empty()) return resolve_nothing(f, summary);
-    LOM_HIP(f, hipSetDevice(f->device));
-    // the hand-off of plane_handle.hpp: read behind the clearance grid, re-solve, release to it
-    const int8_t *d_plane = nullptr;
-    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
-        return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
-    if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
-    if ((rc = resolve_on_device(f, d_plane, r, summary)) != LOM_OK) return rc;
-    return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
-}
-
-int lom_navfield_shift_resolve_device(lom_navfield *f, int32_t dx, int32_t dy, const int8_t *d_plane, void *hip_event_or_null,
-                                      const lom_clearance_window *window_or_null, lom_navfield_summary *summary)
-{
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    lom_occupancy_geometry g;
-    navfield::ShiftPlan plan;
-    if (const int rc = shift_resolve_head(f, d_plane != nullptr, dx, dy, &g, &plan); rc != LOM_OK) return rc;
-    if (!plan.moves())
-        return shift_resolve_in_place(f, g, [&] { return lom_navfield_resolve_device(f, d_plane, hip_event_or_null, window_or_null, summary); });
-    LOM_HIP(f, hipSetDevice(f->device));
-    if (const int rc = ensure_second_block(f); rc != LOM_OK) return rc;
-    if (hip_event_or_null) LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event_or_null, 0));
-    return shift_resolve_on_device(f, plan, g, d_plane, clearance::clip(window_or_null, g), summary);
+    return resolve_from(f, plane_from_clearance(clearance), window_or_null, summary);
 }
 
 int lom_navfield_shift_resolve(lom_navfield *f, int32_t dx, int32_t dy, const int8_t *plane, const lom_clearance_window *window_or_null,
                                lom_navfield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    lom_occupancy_geometry g;
-    navfield::ShiftPlan plan;
-    if (const int rc = shift_resolve_head(f, plane != nullptr, dx, dy, &g, &plan); rc != LOM_OK) return rc;
-    if (!plan.moves()) return shift_resolve_in_place(f, g, [&] { return lom_navfield_resolve(f, plane, window_or_null, summary); });
-    LOM_HIP(f, hipSetDevice(f->device));
-    if (const int rc = ensure_second_block(f); rc != LOM_OK) return rc;
-    if (const int rc = ensure(f, f->incoming, f->n_cells()); rc != LOM_OK) return rc;
-    // the rows that hold an entered cell or a cell of the window, whole, at their place in a plane of the device
-    const clearance::Rect r = clearance::clip(window_or_null, g);
-    uint32_t y0, y1;
-    navfield::shift_upload_rows(plan, r, g.height, &y0, &y1);
-    const size_t first = (size_t)y0 * g.width, bytes = (size_t)(y1 - y0) * g.width;
-    if (bytes) LOM_HIP(f, hipMemcpyAsync(f->incoming.as<int8_t>() + first, plane + first, bytes, hipMemcpyHostToDevice, f->stream));
-    return shift_resolve_on_device(f, plan, g, f->incoming.as<const int8_t>(), r, summary);
+    return shift_resolve_from(f, plane_from_host(plane), dx, dy, window_or_null, summary);
+}
+
+int lom_navfield_shift_resolve_device(lom_navfield *f, int32_t dx, int32_t dy, const int8_t *d_plane, void *hip_event_or_null,
+                                      const lom_clearance_window *window_or_null, lom_navfield_summary *summary)
+{
+    return shift_resolve_from(f, plane_from_device(d_plane, hip_event_or_null), dx, dy, window_or_null, summary);
 }
 
 int lom_navfield_shift_resolve_from_clearance(lom_navfield *f, int32_t dx, int32_t dy, lom_clearance *clearance,
                                               const lom_clearance_window *window_or_null, lom_navfield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    lom_occupancy_geometry g;
-    navfield::ShiftPlan plan;
-    if (const int rc = shift_resolve_head(f, clearance != nullptr, dx, dy, &g, &plan); rc != LOM_OK) return rc;
-    if (!plan.moves())
-        return shift_resolve_in_place(f, g, [&] { return lom_navfield_resolve_from_clearance(f, clearance, window_or_null, summary); });
-    // the clearance grid has been shifted already: its geometry is the new one, bit for bit
-    lom_occupancy_geometry cg{};
-    (void)lom_clearance_get_geometry(clearance, &cg);
-    if (!same_geometry(cg, g))
-        return fail(f, LOM_ERR_ARG, "navigation field: the clearance grid's resolution, origin, width or height differs from the shifted geometry");
-    if (lom_clearance_device(clearance) != f->device) return fail(f, LOM_ERR_ARG, "navigation field: the clearance grid lives on another device");
-    LOM_HIP(f, hipSetDevice(f->device));
-    int rc = ensure_second_block(f);
-    if (rc != LOM_OK) return rc;
-    // the hand-off of plane_handle.hpp: read behind the clearance grid, shift and re-solve, release to it
-    const int8_t *d_plane = nullptr;
-    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
-        return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
-    if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
-    if ((rc = shift_resolve_on_device(f, plan, g, d_plane, clearance::clip(window_or_null, g), summary)) != LOM_OK) return rc;
-    return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
+    return shift_resolve_from(f, plane_from_clearance(clearance), dx, dy, window_or_null, summary);
 }
 
 int lom_navfield_potential(lom_navfield *f, uint32_t *out, size_t cap)

@@ -2,8 +2,9 @@
 // the nearest-goal partition and paths over them.  Definitions: include/lidar_odometry_amd.h ("navigation field set");
 // kernels: k_navset.hpp (the tile body, the walk and the step rules are k_navfield.hpp's); host planning (the offsets
 // rule, sizes, launch shapes): navset_host.cpp; DESIGN.md 7t.  A handle family of its own on the PlaneHandle core
-// (plane_handle.hpp); no default path launches any of this.  lom_navfield_adopt (navfield.hip) makes a field of the set a
-// lom_navfield, so the set needs no copy of that family's consumers.
+// (plane_handle.hpp), the three forms of the cost plane through its PlaneSource; no default path launches
+// any of this.  lom_navfield_adopt (navfield.hip) makes a field of the set a lom_navfield, so the set needs no copy of that
+// family's consumers.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -159,6 +160,32 @@ int solve_nothing(lom_navset *s)
     return LOM_OK;
 }
 
+// The solve over the source of the plane (plane_handle.hpp), in one order: the refusals, the solve of no
+// fields, what can fail for want of memory, open, upload, body, close.
+int solve_from(lom_navset *s, const PlaneSource &src, const lom_navfield_params *params, int goal_kind, const void *goals,
+               const uint32_t *goal_offsets, size_t n_fields, lom_navfield_summary *summaries)
+{
+    if (!s) return LOM_ERR_ARG;
+    zero(summaries, std::min<size_t>(n_fields, s->max_fields));
+    size_t n_goals;
+    if (const char *why = solve_refusal(s, src.given(), params, goal_kind, goals, goal_offsets, n_fields, &n_goals)) return fail(s, LOM_ERR_ARG, why);
+    if (const int rc = plane_source_check(s, kName, src, s->geo); rc != LOM_OK) return rc;
+    if (!n_fields) return solve_nothing(s);
+    LOM_HIP(s, hipSetDevice(s->device));
+    // the goals first: their buffers are what can still be refused (no memory); then a host plane goes straight to the set's copy
+    int rc;
+    if (n_goals && ((rc = ensure(s, s->points, n_goals * 8)) != LOM_OK || (rc = ensure(s, s->field_of, n_goals * 4)) != LOM_OK)) return rc;
+    const int8_t *d_plane = nullptr;
+    if ((rc = plane_source_open(s, kName, src, &d_plane)) != LOM_OK) return rc;
+    if (src.host) {
+        s->solved = false, s->n_fields = 0;
+        LOM_HIP(s, hipMemcpyAsync(s->plane.p, src.host, s->n_cells(), hipMemcpyHostToDevice, s->stream));
+        d_plane = s->plane.as<const int8_t>();
+    }
+    if ((rc = solve_on_device(s, d_plane, *params, goal_kind, goals, goal_offsets, n_goals, (uint32_t)n_fields, summaries)) != LOM_OK) return rc;
+    return plane_source_close(s, kName, src);
+}
+
 }  // namespace
 
 namespace lom {
@@ -237,17 +264,13 @@ int lom_navset_set_option(lom_navset *s, int option, int64_t value)
     if (!s) return LOM_ERR_ARG;
     switch (option) {
     case LOM_NAVSET_OPT_TEST_INNER_CAP:
-        if (value > (int64_t)navfield::kInnerCapMax) return fail(s, LOM_ERR_ARG, "LOM_NAVSET_OPT_TEST_INNER_CAP: 1 .. 2^20, or <= 0 for the default");
-        s->inner_cap = value <= 0 ? navfield::kInnerCapDefault : (uint32_t)value;
-        return LOM_OK;
+        return set_test_option(s, s->inner_cap, value, navfield::kInnerCapMax, navfield::kInnerCapDefault,
+                               "LOM_NAVSET_OPT_TEST_INNER_CAP: 1 .. 2^20, or <= 0 for the default");
     case LOM_NAVSET_OPT_TEST_BATCH:
-        if (value > (int64_t)navfield::kBatchMax) return fail(s, LOM_ERR_ARG, "LOM_NAVSET_OPT_TEST_BATCH: 1 .. 256, or <= 0 for the default");
-        s->batch = value <= 0 ? navfield::kBatchDefault : (uint32_t)value;
-        return LOM_OK;
+        return set_test_option(s, s->batch, value, navfield::kBatchMax, navfield::kBatchDefault,
+                               "LOM_NAVSET_OPT_TEST_BATCH: 1 .. 256, or <= 0 for the default");
     case LOM_NAVSET_OPT_TEST_ALL_TILES:
-        if (value > 1) return fail(s, LOM_ERR_ARG, "LOM_NAVSET_OPT_TEST_ALL_TILES: 0, 1, or < 0 for the default");
-        s->all_tiles = value == 1 ? 1u : 0u;
-        return LOM_OK;
+        return set_test_option(s, s->all_tiles, value, 1, 0, "LOM_NAVSET_OPT_TEST_ALL_TILES: 0, 1, or < 0 for the default");
     default:
         return fail(s, LOM_ERR_ARG, "unknown navigation field set option");
     }
@@ -255,57 +278,22 @@ int lom_navset_set_option(lom_navset *s, int option, int64_t value)
 
 size_t lom_navset_field_count(const lom_navset *s) { return s ? s->n_fields : 0; }
 
-int lom_navset_solve_device(lom_navset *s, const int8_t *d_plane, void *hip_event_or_null, const lom_navfield_params *params, int goal_kind,
-                            const void *goals, const uint32_t *goal_offsets, size_t n_fields, lom_navfield_summary *summaries)
-{
-    if (!s) return LOM_ERR_ARG;
-    zero(summaries, std::min<size_t>(n_fields, s->max_fields));
-    size_t n_goals;
-    if (const char *why = solve_refusal(s, d_plane != nullptr, params, goal_kind, goals, goal_offsets, n_fields, &n_goals)) return fail(s, LOM_ERR_ARG, why);
-    if (!n_fields) return solve_nothing(s);
-    LOM_HIP(s, hipSetDevice(s->device));
-    if (hip_event_or_null) LOM_HIP(s, hipStreamWaitEvent(s->stream, (hipEvent_t)hip_event_or_null, 0));
-    return solve_on_device(s, d_plane, *params, goal_kind, goals, goal_offsets, n_goals, (uint32_t)n_fields, summaries);
-}
-
 int lom_navset_solve(lom_navset *s, const int8_t *plane, const lom_navfield_params *params, int goal_kind, const void *goals,
                      const uint32_t *goal_offsets, size_t n_fields, lom_navfield_summary *summaries)
 {
-    if (!s) return LOM_ERR_ARG;
-    zero(summaries, std::min<size_t>(n_fields, s->max_fields));
-    size_t n_goals;
-    if (const char *why = solve_refusal(s, plane != nullptr, params, goal_kind, goals, goal_offsets, n_fields, &n_goals)) return fail(s, LOM_ERR_ARG, why);
-    if (!n_fields) return solve_nothing(s);
-    LOM_HIP(s, hipSetDevice(s->device));
-    // the goals first: their buffers are what can still be refused (no memory); then the plane goes straight to the set's copy
-    int rc;
-    if (n_goals && ((rc = ensure(s, s->points, n_goals * 8)) != LOM_OK || (rc = ensure(s, s->field_of, n_goals * 4)) != LOM_OK)) return rc;
-    s->solved = false, s->n_fields = 0;
-    LOM_HIP(s, hipMemcpyAsync(s->plane.p, plane, s->n_cells(), hipMemcpyHostToDevice, s->stream));
-    return solve_on_device(s, s->plane.as<const int8_t>(), *params, goal_kind, goals, goal_offsets, n_goals, (uint32_t)n_fields, summaries);
+    return solve_from(s, plane_from_host(plane), params, goal_kind, goals, goal_offsets, n_fields, summaries);
+}
+
+int lom_navset_solve_device(lom_navset *s, const int8_t *d_plane, void *hip_event_or_null, const lom_navfield_params *params, int goal_kind,
+                            const void *goals, const uint32_t *goal_offsets, size_t n_fields, lom_navfield_summary *summaries)
+{
+    return solve_from(s, plane_from_device(d_plane, hip_event_or_null), params, goal_kind, goals, goal_offsets, n_fields, summaries);
 }
 
 int lom_navset_solve_from_clearance(lom_navset *s, lom_clearance *clearance, const lom_navfield_params *params, int goal_kind, const void *goals,
                                     const uint32_t *goal_offsets, size_t n_fields, lom_navfield_summary *summaries)
 {
-    if (!s) return LOM_ERR_ARG;
-    zero(summaries, std::min<size_t>(n_fields, s->max_fields));
-    size_t n_goals;
-    if (const char *why = solve_refusal(s, clearance != nullptr, params, goal_kind, goals, goal_offsets, n_fields, &n_goals))
-        return fail(s, LOM_ERR_ARG, why);
-    lom_occupancy_geometry g{};
-    (void)lom_clearance_get_geometry(clearance, &g);
-    int rc = plane_check_producer(s, kName, "clearance grid", g, lom_clearance_device(clearance));
-    if (rc != LOM_OK) return rc;
-    if (!n_fields) return solve_nothing(s);
-    LOM_HIP(s, hipSetDevice(s->device));
-    // the hand-off of plane_handle.hpp: read behind the clearance grid, solve, release to it
-    const int8_t *d_plane = nullptr;
-    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
-        return plane_fail_producer(s, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
-    if ((rc = plane_read_behind(s, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
-    if ((rc = solve_on_device(s, d_plane, *params, goal_kind, goals, goal_offsets, n_goals, (uint32_t)n_fields, summaries)) != LOM_OK) return rc;
-    return plane_release(s, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
+    return solve_from(s, plane_from_clearance(clearance), params, goal_kind, goals, goal_offsets, n_fields, summaries);
 }
 
 int lom_navset_potential(lom_navset *s, size_t i, uint32_t *out, size_t cap)

@@ -1,5 +1,5 @@
-// The host core of a planning grid's handle (plane_handle.hpp): what lom_clearance, lom_navfield, lom_regions and
-// lom_visibility all own and do around their kernels.  No kernel is launched here.
+// The host core of a planning grid's handle (plane_handle.hpp): what the seven planning families all own and do around
+// their kernels.  No kernel is launched here.
 #include "plane_handle.hpp"
 
 namespace lom {
@@ -54,12 +54,19 @@ int plane_copy_out(PlaneHandle *h, void *out, const DeviceBuf &buf, size_t n_byt
     return LOM_OK;
 }
 
-int plane_check_producer(PlaneHandle *h, const char *consumer, const char *producer, const lom_occupancy_geometry &g, int device)
+// the producer's geometry `g` against `want`, then its device against the handle's: the two texts of the hand-off, once
+static int check_producer(PlaneHandle *h, const char *consumer, const char *producer, const lom_occupancy_geometry &g,
+                          const lom_occupancy_geometry &want, const char *differs_tail, int device)
 {
     const std::string head = std::string(consumer) + ": the " + producer;
-    if (!same_geometry(g, h->geo)) return fail(h, LOM_ERR_ARG, (head + "'s resolution, origin, width or height differs").c_str());
+    if (!same_geometry(g, want)) return fail(h, LOM_ERR_ARG, (head + "'s resolution, origin, width or height differs" + differs_tail).c_str());
     if (device != h->device) return fail(h, LOM_ERR_ARG, (head + " lives on another device").c_str());
     return LOM_OK;
+}
+
+int plane_check_producer(PlaneHandle *h, const char *consumer, const char *producer, const lom_occupancy_geometry &g, int device)
+{
+    return check_producer(h, consumer, producer, g, h->geo, "", device);
 }
 
 int plane_shifted_geometry(PlaneHandle *h, const char *name, int32_t dx, int32_t dy, lom_occupancy_geometry *out)
@@ -80,6 +87,30 @@ int plane_read_behind(PlaneHandle *h, int k, void *producer_stream)
     LOM_HIP(h, hipEventRecord(h->in_ev[k], (hipStream_t)producer_stream));
     LOM_HIP(h, hipStreamWaitEvent(h->stream, h->in_ev[k], 0));
     return LOM_OK;
+}
+
+int plane_source_check(PlaneHandle *h, const char *consumer, const PlaneSource &s, const lom_occupancy_geometry &g, const char *differs_tail)
+{
+    if (!s.clearance) return LOM_OK;
+    lom_occupancy_geometry cg{};
+    (void)lom_clearance_get_geometry(s.clearance, &cg);
+    return check_producer(h, consumer, "clearance grid", cg, g, differs_tail, lom_clearance_device(s.clearance));
+}
+
+int plane_source_open(PlaneHandle *h, const char *consumer, const PlaneSource &s, const int8_t **d_plane)
+{
+    *d_plane = s.device;
+    if (s.event) LOM_HIP(h, hipStreamWaitEvent(h->stream, (hipEvent_t)s.event, 0));
+    if (!s.clearance) return LOM_OK;
+    if (lom_clearance_cost_device(s.clearance, d_plane) != LOM_OK || !*d_plane)
+        return plane_fail_producer(h, consumer, "lom_clearance_cost_device", lom_clearance_last_error(s.clearance));
+    return plane_read_behind(h, 0, lom_clearance_stream(s.clearance));
+}
+
+int plane_source_close(PlaneHandle *h, const char *consumer, const PlaneSource &s)
+{
+    if (!s.clearance) return LOM_OK;
+    return plane_release(h, consumer, s.clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
 }
 
 }  // namespace lom

@@ -1,9 +1,10 @@
 // The handle of a planning grid, written once for lom_clearance (clearance.hip), lom_navfield (navfield.hip), lom_regions
-// (regions.hip) and lom_visibility (visibility.hip): a dense 2-D grid of one geometry that reads planes other handles
-// leave in HBM on streams of their own.  What create and destroy do for all four, the small entry points, the read-back
-// of a buffer, the shift by whole cells, and the hand-off of a producer's plane between two streams (code:
-// plane_handle.hip).  A family keeps its buffers, pinned blocks and options, its refusals, its kernels and their launches.
-// Nothing here launches a kernel.
+// (regions.hip), lom_visibility (visibility.hip), lom_rollout (rollout.hip), lom_navset (navset.hip) and lom_posefield
+// (posefield.hip): a dense 2-D grid of one geometry that reads planes other handles leave in HBM on streams of their own.
+// What create and destroy do for all seven, the small entry points, the read-back of a buffer, the shift by whole cells,
+// the hand-off of a producer's plane between two streams and the three forms in which a cost plane reaches a solver
+// (code: plane_handle.hip).  A family keeps its buffers, pinned blocks and options, its refusals, its kernels
+// and their launches.  Nothing here launches a kernel.
 #pragma once
 #include <cstring>
 #include <new>
@@ -64,6 +65,32 @@ int plane_release(PlaneHandle *h, const char *consumer, P *producer, int (*wait_
     if (wait_event(producer, h->done_ev) == LOM_OK) return LOM_OK;
     return fail(h, LOM_ERR_HIP, (std::string(consumer) + ": " + call).c_str());
 }
+
+// ---- the source of a cost plane ("the three forms") -------------------------------------------------------
+// In which form a caller gave an int8 cost plane to a solver over it (lom_navfield, lom_navset, lom_posefield): a host
+// pointer, a device pointer with an optional event, or a clearance grid.  One of the three is set; none: no plane was given.
+struct PlaneSource {
+    const int8_t *host = nullptr;
+    const int8_t *device = nullptr;
+    void *event = nullptr;  // `device` is complete behind it; may be NULL
+    lom_clearance *clearance = nullptr;
+
+    bool given() const { return host || device || clearance; }
+};
+inline PlaneSource plane_from_host(const int8_t *plane) { return PlaneSource{plane, nullptr, nullptr, nullptr}; }
+inline PlaneSource plane_from_device(const int8_t *d_plane, void *hip_event_or_null) { return PlaneSource{nullptr, d_plane, hip_event_or_null, nullptr}; }
+inline PlaneSource plane_from_clearance(lom_clearance *clearance) { return PlaneSource{nullptr, nullptr, nullptr, clearance}; }
+
+// The producer's refusals for a clearance grid, in plane_check_producer's words, against `g`: the handle's own geometry, or
+// the one a shift is about to give it -- `differs_tail` then ends the geometry's text.  LOM_OK for a host or a device pointer.
+int plane_source_check(PlaneHandle *h, const char *consumer, const PlaneSource &s, const lom_occupancy_geometry &g, const char *differs_tail = "");
+// Open, with the handle's device current: *d_plane is the plane in HBM, and what is enqueued on the handle's stream next
+// may read it.  A device pointer: behind its event, if there is one.  A clearance grid: its cost plane, read behind its
+// stream through in_ev[0] (plane_fail_producer where it does not give the plane).  A host pointer: *d_plane stays NULL --
+// the family uploads, because what an operation reads of a host plane differs.
+int plane_source_open(PlaneHandle *h, const char *consumer, const PlaneSource &s, const int8_t **d_plane);
+// Close, once the body has returned LOM_OK: plane_release to a clearance grid, nothing otherwise.
+int plane_source_close(PlaneHandle *h, const char *consumer, const PlaneSource &s);
 
 // ---- the shift by whole cells (include/lidar_odometry_amd.h, "grid shift") --------------------------------------------
 // LOM_ERR_RANGE and "<name>: shift: ..." where the rule of plane_geometry.hpp refuses the new origin, else *out

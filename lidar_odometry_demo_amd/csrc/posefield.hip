@@ -2,8 +2,9 @@
 // plane; the floor over the headings, paths down the field and point queries.  Definitions: include/lidar_odometry_amd.h
 // ("pose field"); kernels: k_posefield.hpp; the move rule: pose_rule.hpp; host planning (value ranges, stencils, tile
 // counts, launch shapes): posefield_host.cpp; DESIGN.md 7u.  A handle family of its own on the PlaneHandle core
-// (plane_handle.hpp); the host loop to the fixed point is nav_fixed_point.hpp's.  The re-solve after a local cost change
-// (k_posefield_resolve.hpp) keeps what a solve left and repairs it.  No default path launches any of this.
+// (plane_handle.hpp), the three forms of the cost plane through its PlaneSource; the host loop to the fixed
+// point is nav_fixed_point.hpp's.  The re-solve after a local cost change (k_posefield_resolve.hpp) keeps
+// what a solve left and repairs it.  No default path launches any of this.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -267,6 +268,50 @@ int resolve_nothing(lom_posefield *f, lom_posefield_summary *summary)
     return LOM_OK;
 }
 
+// ---- one function per operation over the source of the plane (plane_handle.hpp) ---------------------------
+// Each in one order: the refusals, the way out that needs no device, what can fail for want of memory, open, upload, body, close.
+int solve_from(lom_posefield *f, const PlaneSource &src, const lom_posefield_params *params, const int32_t *footprint, size_t n_samples,
+               const int32_t *goals, size_t n_goals, lom_posefield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const char *why = solve_refusal(src.given(), params, footprint, n_samples, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
+    if (const int rc = plane_source_check(f, kName, src, f->geo); rc != LOM_OK) return rc;
+    LOM_HIP(f, hipSetDevice(f->device));
+    // the goals first: their buffer is what can still be refused (no memory); then a host plane goes straight to the field's copy
+    if (const int rc = n_goals ? ensure(f, f->points, n_goals * 12) : LOM_OK; rc != LOM_OK) return rc;
+    const int8_t *d_plane = nullptr;
+    if (const int rc = plane_source_open(f, kName, src, &d_plane); rc != LOM_OK) return rc;
+    if (src.host) {
+        LOM_HIP(f, hipMemcpyAsync(f->plane.p, src.host, f->n_cells(), hipMemcpyHostToDevice, f->stream));
+        d_plane = f->plane.as<const int8_t>();
+    }
+    if (const int rc = solve_on_device(f, d_plane, *params, footprint, n_samples, goals, n_goals, summary); rc != LOM_OK) return rc;
+    return plane_source_close(f, kName, src);
+}
+
+int resolve_from(lom_posefield *f, const PlaneSource &src, const lom_clearance_window *window_or_null, lom_posefield_summary *summary)
+{
+    if (summary) std::memset(summary, 0, sizeof *summary);
+    if (!f) return LOM_ERR_ARG;
+    if (const int rc = resolve_refusal(f, src.given()); rc != LOM_OK) return rc;
+    if (const int rc = plane_source_check(f, kName, src, f->geo); rc != LOM_OK) return rc;
+    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
+    if (r.empty()) return resolve_nothing(f, summary);
+    LOM_HIP(f, hipSetDevice(f->device));
+    const int8_t *d_plane = nullptr;
+    if (const int rc = plane_source_open(f, kName, src, &d_plane); rc != LOM_OK) return rc;
+    if (src.host) {
+        // the rows of the window, whole, at their place in a plane of the device: the cells outside the window are not read
+        if (const int rc = ensure(f, f->incoming, f->n_cells()); rc != LOM_OK) return rc;
+        const size_t first = (size_t)r.y0 * f->geo.width, bytes = (size_t)(r.y1 - r.y0) * f->geo.width;
+        LOM_HIP(f, hipMemcpyAsync(f->incoming.as<int8_t>() + first, src.host + first, bytes, hipMemcpyHostToDevice, f->stream));
+        d_plane = f->incoming.as<const int8_t>();
+    }
+    if (const int rc = resolve_on_device(f, d_plane, r, summary); rc != LOM_OK) return rc;
+    return plane_source_close(f, kName, src);
+}
+
 }  // namespace
 
 extern "C" {
@@ -326,120 +371,55 @@ int lom_posefield_set_option(lom_posefield *f, int option, int64_t value)
     if (!f) return LOM_ERR_ARG;
     switch (option) {
     case LOM_POSE_OPT_TEST_INNER_CAP:
-        if (value > (int64_t)navfield::kInnerCapMax) return fail(f, LOM_ERR_ARG, "LOM_POSE_OPT_TEST_INNER_CAP: 1 .. 2^20, or <= 0 for the default");
-        f->inner_cap = value <= 0 ? navfield::kInnerCapDefault : (uint32_t)value;
-        return LOM_OK;
+        return set_test_option(f, f->inner_cap, value, navfield::kInnerCapMax, navfield::kInnerCapDefault,
+                               "LOM_POSE_OPT_TEST_INNER_CAP: 1 .. 2^20, or <= 0 for the default");
     case LOM_POSE_OPT_TEST_BATCH:
-        if (value > (int64_t)navfield::kBatchMax) return fail(f, LOM_ERR_ARG, "LOM_POSE_OPT_TEST_BATCH: 1 .. 256, or <= 0 for the default");
-        f->batch = value <= 0 ? navfield::kBatchDefault : (uint32_t)value;
-        return LOM_OK;
+        return set_test_option(f, f->batch, value, navfield::kBatchMax, navfield::kBatchDefault,
+                               "LOM_POSE_OPT_TEST_BATCH: 1 .. 256, or <= 0 for the default");
     case LOM_POSE_OPT_TEST_ALL_TILES:
-        if (value > 1) return fail(f, LOM_ERR_ARG, "LOM_POSE_OPT_TEST_ALL_TILES: 0, 1, or < 0 for the default");
-        f->all_tiles = value == 1 ? 1u : 0u;
-        return LOM_OK;
+        return set_test_option(f, f->all_tiles, value, 1, 0, "LOM_POSE_OPT_TEST_ALL_TILES: 0, 1, or < 0 for the default");
     case LOM_POSE_OPT_TEST_RESOLVE_FORM:
-        if (value > 1) return fail(f, LOM_ERR_ARG, "LOM_POSE_OPT_TEST_RESOLVE_FORM: 0, 1, or < 0 for the default");
-        f->resolve_form = value == 1 ? 1u : 0u;
-        return LOM_OK;
+        return set_test_option(f, f->resolve_form, value, 1, 0, "LOM_POSE_OPT_TEST_RESOLVE_FORM: 0, 1, or < 0 for the default");
     default:
         return fail(f, LOM_ERR_ARG, "unknown pose field option");
     }
+}
+
+int lom_posefield_solve(lom_posefield *f, const int8_t *plane, const lom_posefield_params *params, const int32_t *footprint,
+                        size_t n_samples, const int32_t *goals, size_t n_goals, lom_posefield_summary *summary)
+{
+    return solve_from(f, plane_from_host(plane), params, footprint, n_samples, goals, n_goals, summary);
 }
 
 int lom_posefield_solve_device(lom_posefield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_posefield_params *params,
                                const int32_t *footprint, size_t n_samples, const int32_t *goals, size_t n_goals,
                                lom_posefield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const char *why = solve_refusal(d_plane != nullptr, params, footprint, n_samples, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
-    LOM_HIP(f, hipSetDevice(f->device));
-    if (hip_event_or_null) LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event_or_null, 0));
-    return solve_on_device(f, d_plane, *params, footprint, n_samples, goals, n_goals, summary);
-}
-
-int lom_posefield_solve(lom_posefield *f, const int8_t *plane, const lom_posefield_params *params, const int32_t *footprint,
-                        size_t n_samples, const int32_t *goals, size_t n_goals, lom_posefield_summary *summary)
-{
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const char *why = solve_refusal(plane != nullptr, params, footprint, n_samples, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
-    LOM_HIP(f, hipSetDevice(f->device));
-    // the goals first: their buffer is what can still be refused (no memory); then the plane goes straight to the field's copy
-    if (const int rc = n_goals ? ensure(f, f->points, n_goals * 12) : LOM_OK; rc != LOM_OK) return rc;
-    LOM_HIP(f, hipMemcpyAsync(f->plane.p, plane, f->n_cells(), hipMemcpyHostToDevice, f->stream));
-    return solve_on_device(f, f->plane.as<const int8_t>(), *params, footprint, n_samples, goals, n_goals, summary);
+    return solve_from(f, plane_from_device(d_plane, hip_event_or_null), params, footprint, n_samples, goals, n_goals, summary);
 }
 
 int lom_posefield_solve_from_clearance(lom_posefield *f, lom_clearance *clearance, const lom_posefield_params *params,
                                        const int32_t *footprint, size_t n_samples, const int32_t *goals, size_t n_goals,
                                        lom_posefield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const char *why = solve_refusal(clearance != nullptr, params, footprint, n_samples, goals, n_goals)) return fail(f, LOM_ERR_ARG, why);
-    lom_occupancy_geometry g{};
-    (void)lom_clearance_get_geometry(clearance, &g);
-    int rc = plane_check_producer(f, kName, "clearance grid", g, lom_clearance_device(clearance));
-    if (rc != LOM_OK) return rc;
-    LOM_HIP(f, hipSetDevice(f->device));
-    // the hand-off of plane_handle.hpp: read behind the clearance grid, solve, release to it
-    const int8_t *d_plane = nullptr;
-    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
-        return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
-    if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
-    if ((rc = solve_on_device(f, d_plane, *params, footprint, n_samples, goals, n_goals, summary)) != LOM_OK) return rc;
-    return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
+    return solve_from(f, plane_from_clearance(clearance), params, footprint, n_samples, goals, n_goals, summary);
+}
+
+int lom_posefield_resolve(lom_posefield *f, const int8_t *plane, const lom_clearance_window *window_or_null, lom_posefield_summary *summary)
+{
+    return resolve_from(f, plane_from_host(plane), window_or_null, summary);
 }
 
 int lom_posefield_resolve_device(lom_posefield *f, const int8_t *d_plane, void *hip_event_or_null, const lom_clearance_window *window_or_null,
                                  lom_posefield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const int rc = resolve_refusal(f, d_plane != nullptr); rc != LOM_OK) return rc;
-    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
-    if (r.empty()) return resolve_nothing(f, summary);
-    LOM_HIP(f, hipSetDevice(f->device));
-    if (hip_event_or_null) LOM_HIP(f, hipStreamWaitEvent(f->stream, (hipEvent_t)hip_event_or_null, 0));
-    return resolve_on_device(f, d_plane, r, summary);
-}
-
-int lom_posefield_resolve(lom_posefield *f, const int8_t *plane, const lom_clearance_window *window_or_null, lom_posefield_summary *summary)
-{
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const int rc = resolve_refusal(f, plane != nullptr); rc != LOM_OK) return rc;
-    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
-    if (r.empty()) return resolve_nothing(f, summary);
-    LOM_HIP(f, hipSetDevice(f->device));
-    // the rows of the window, whole, at their place in a plane of the device: the cells outside the window are not read
-    if (const int rc = ensure(f, f->incoming, f->n_cells()); rc != LOM_OK) return rc;
-    const size_t first = (size_t)r.y0 * f->geo.width, bytes = (size_t)(r.y1 - r.y0) * f->geo.width;
-    LOM_HIP(f, hipMemcpyAsync(f->incoming.as<int8_t>() + first, plane + first, bytes, hipMemcpyHostToDevice, f->stream));
-    return resolve_on_device(f, f->incoming.as<const int8_t>(), r, summary);
+    return resolve_from(f, plane_from_device(d_plane, hip_event_or_null), window_or_null, summary);
 }
 
 int lom_posefield_resolve_from_clearance(lom_posefield *f, lom_clearance *clearance, const lom_clearance_window *window_or_null,
                                          lom_posefield_summary *summary)
 {
-    if (summary) std::memset(summary, 0, sizeof *summary);
-    if (!f) return LOM_ERR_ARG;
-    if (const int rc = resolve_refusal(f, clearance != nullptr); rc != LOM_OK) return rc;
-    lom_occupancy_geometry g{};
-    (void)lom_clearance_get_geometry(clearance, &g);
-    int rc = plane_check_producer(f, kName, "clearance grid", g, lom_clearance_device(clearance));
-    if (rc != LOM_OK) return rc;
-    const clearance::Rect r = clearance::clip(window_or_null, f->geo);
-    if (r.empty()) return resolve_nothing(f, summary);
-    LOM_HIP(f, hipSetDevice(f->device));
-    // the hand-off of plane_handle.hpp: read behind the clearance grid, re-solve, release to it
-    const int8_t *d_plane = nullptr;
-    if (lom_clearance_cost_device(clearance, &d_plane) != LOM_OK || !d_plane)
-        return plane_fail_producer(f, kName, "lom_clearance_cost_device", lom_clearance_last_error(clearance));
-    if ((rc = plane_read_behind(f, 0, lom_clearance_stream(clearance))) != LOM_OK) return rc;
-    if ((rc = resolve_on_device(f, d_plane, r, summary)) != LOM_OK) return rc;
-    return plane_release(f, kName, clearance, lom_clearance_wait_event, "lom_clearance_wait_event");
+    return resolve_from(f, plane_from_clearance(clearance), window_or_null, summary);
 }
 
 int lom_posefield_resolve_stats(const lom_posefield *f, lom_posefield_resolve_counters *out)
